@@ -22,6 +22,11 @@ RCCL all-gather of per-shard top-k per batch of Q queries (in the timed region).
 scored / its launch duration measured with HIP events on the launch stream.
 "cpu_baseline" times the CPU oracle (oracle/, a port — the reference's arithmetic is inside an
 external ffmpeg binary that is not available) on a bounded sample of the same frames.
+
+A plain run sets up, warms up, times the K steps of the headline (scene) leg and prints the line; its
+"match", "cpu_baseline", "config0", "h2d" and "e2e" legs run only with --full.  --dump-outputs DIR writes
+what the last timed step handed its caller as DIR/<name>.npy (float64): the inputs are seeded, so two
+builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -56,6 +61,11 @@ def parse(argv=None):
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--frames", type=int, default=10000, help="1080p frames per GPU per step")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs (corpus match, CPU baselines, config0, H2D, e2e); --corpus, "
+                         "--queries and the --match-*, --cpu-*, --e2e-* and --no-* options apply only then")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (sad, mafd, score, selected, cuts) as DIR/<name>.npy")
     ap.add_argument("--corpus", type=int, default=100000, help="corpus videos, sharded over the ranks (configs[3])")
     ap.add_argument("--queries", type=int, default=4096,
                     help="query videos per match batch (sized so that a 1/8 shard is still well above the fixed "
@@ -130,6 +140,21 @@ def bench_scene(args, rank, world, dev):
     step_ms = [a.elapsed_time(b) for a, b in ev]
     n_cuts = int(scorer.selected[:T].sum().item())
     return dict(frames=frames, scorer=scorer, wall=wall, step_ms=step_ms, n_cuts=n_cuts)
+
+
+def dump_outputs(out_dir: str, scorer, T: int, rank: int, world: int) -> None:
+    """What SceneScorer.score_batch hands its caller after the last timed step - the views (sad, mafd, score,
+    selected) and the compacted cut list - as float64 .npy files (every value is exact in float64).  Every step
+    scores the same seeded frames with carry=False, so the last step's outputs are every step's.  With N > 1 each
+    rank writes its own files (<name>_rank<r>.npy)."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    n = int(scorer.cuts[0].item())
+    arrays = {"sad": scorer.sad[:T], "mafd": scorer.mafd[:T], "score": scorer.score[:T],
+              "selected": scorer.selected[:T], "cuts": scorer.cuts[1:1 + n]}
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), t.cpu().numpy().astype(np.float64))
 
 
 def cpu_baseline_scene(frames: torch.Tensor, n_frames: int, n_threads: int, min_seconds: float = 1.5):
@@ -965,7 +990,7 @@ def main(argv=None):
     # first) the two streams landed on queues 2 and 6 and the batches serialised: 0.45 ms per batch
     # instead of 0.34 (profiles/r3_shard_pipeline.txt).
     match_leg = None
-    if not args.no_match:
+    if args.full and not args.no_match:
         try:
             match_leg = bench_match(args, rank, world, dev)
         except Exception as e:            # the headline (scene) leg below must not die with the secondary one
@@ -975,6 +1000,8 @@ def main(argv=None):
 
     res = bench_scene(args, rank, world, dev)
     T, K = args.frames, args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res["scorer"], T, rank, world)
     wall = res["wall"]
     fps = world * T * K / wall
     # ONE time base for value, ms_per_step and the roofline: the timed region (barrier + synchronize on both
@@ -1033,6 +1060,13 @@ def main(argv=None):
                                     f"{match_leg['rccl_ranks']} RCCL rank(s)",
                         "avg_launch_ms": match_leg["ms_per_batch"], "pairs_per_s": match_leg["value"]})
     out["roofline"]["kernels"] = kernels
+    if not args.full:                     # a plain run: the headline figure and nothing else
+        out["cpu_baseline"] = None
+        if dist.is_initialized():
+            dist.barrier()
+            dist.destroy_process_group()
+        emit()
+        return
     if rank == 0:
         out["h2d"] = h2d_cost(dev)
     if rank == 0 and world == 1 and not args.no_cpu:

@@ -12,7 +12,7 @@ REPO=$(pwd)
 OUT=$REPO/gpurun_out/final_$TAG
 mkdir -p $OUT
 if [ "$PART" != "b" ]; then
-echo "== bench (un-profiled)";            python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; echo rc=$?
+echo "== bench (un-profiled)";            python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; echo rc=$?
 echo "== scene kernel trace + FETCH/WRITE"; bash profiles/run_profile.sh $TAG > $OUT/run_profile.log 2>&1; echo rc=$?
 echo "== matcher trace + counters"
 for w in topk shard8 index index1 join q1_100k q1_5k tile; do bash profiles/pmc_match.sh $TAG $w >> $OUT/pmc_match.log 2>&1; echo "  $w done"; done

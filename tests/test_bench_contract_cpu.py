@@ -1,5 +1,5 @@
 """The shape of bench.py's one JSON line, checked on the line the final build printed on the GPU box
-(profiles/r5_bench.json): the driver's contract fields, the roofline and cpu_baseline objects, and
+(profiles/r5_bench.json, a `--full` run): the driver's contract fields, the roofline and cpu_baseline objects, and
 the arithmetic that ties them together.  (bench.py itself needs a GPU: tests/test_abi.py checks that
 it refuses to run without one.)"""
 import json
