@@ -164,8 +164,7 @@ static int tvz_match_sharded_impl(tvz_corpus *c, tvz_comm *comm, const double *d
     if (prev >= 0 && prev != comm->device) (void)hipSetDevice(prev);
     if (herr != hipSuccess) return tvz::fail(TVZ_ERR_HIP, "ordering the collective failed: %s", hipGetErrorString(herr));
     if (grc) return nccl_fail("ncclAllGather", grc);
-    return tvz_topk_merge_ws(gathered, comm->n_ranks, Q, k, d_topk, d_totals, d_workspace, max_query_len, cap,
-                             hip_stream);
+    return tvz_topk_merge(gathered, comm->n_ranks, Q, k, d_topk, d_totals, hip_stream);
 }
 
 TVZ_EXPORT int tvz_comm_unique_id(void *out_id) { TVZ_GUARDED(tvz_comm_unique_id_impl(out_id)); }

@@ -305,6 +305,13 @@ int compact(tvz_corpus *c) {
     return upload_all(c, 0, 0);
 }
 
+static bool tvz_debug() { static const bool on = getenv("TVZ_DEBUG") != nullptr; return on; }
+static double tvz_now_us() {
+    timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3;
+}
+
 // ---- inverted index: build ---------------------------------------------------------------------
 void index_drop(tvz_corpus *c) {
     Index &ix = c->ix;
@@ -372,28 +379,112 @@ int wait_stream_polling(hipStream_t st, hipEvent_t ev) {
     }
 }
 
-// Build the index of rows [0, n_rows) of the row table image `d_rows` (keys in c->keys) into
-// generation `b` on stream `st`, and wait for it.  `b` must have no reader; nothing of the handle's
-// published state is touched.  rows_cap / keys_cap: the corpus RESERVATION the buffers are sized
-// with, so the rebuilds that upserts trigger allocate nothing until the corpus outgrows it.
-int build_kernels(tvz_corpus *c, IndexBuf &b, const Row *d_rows, int64_t n_rows, int64_t live_keys,
-                  int64_t rows_cap, int64_t keys_cap, hipStream_t st) {
-    Index &ix = c->ix;
-    // posting offsets and counts are 32-bit: a larger shard is swept (shard it over more GPUs)
-    if (n_rows == 0 || live_keys >= (int64_t)0xfffffff0LL)
-        return tvz::fail(TVZ_ERR_UNSUPPORTED, "corpus of %lld rows / %lld keys gets no index", (long long)n_rows,
-                         (long long)live_keys);
-    const int n_sub = (int)tvz::ceil_div(n_rows, kSubRows);
-    TVZ_REQUIRE(n_sub <= 4096, "too many rows for the index (%lld)", (long long)n_rows);
-    const int ks = ix_ks(n_sub), es = ix_entry_bytes(ks);
-    // (+64: the lookup's last step reads up to 63 postings past the last list and discards them; x2 +
+// The sizes of one generation's buffers and of the partitioned build's scratch, in elements, for a build of
+// `live_keys` keys into a corpus reservation of rows_cap rows / keys_cap keys.  The build ensures them; build_index
+// pre-sizes the shadow generation with them.
+struct GenSizes {
+    int64_t rows;     // ivid; the delta table holds delta_capacity(rows)
+    int64_t pairs;    // (key, row) pairs: ix.pkeys / ix.prows
+    // classic postings (+64: the lookup's last step reads up to 63 postings past the last list and discards them; x2 +
     // a line per size class and slice: the partitioned build pads keys to line-friendly places)
-    const int64_t post_cap = 2 * std::max<int64_t>(keys_cap, live_keys) + (int64_t)kIxMaxParts * kIxClasses * 64 + kIxPostPad;
-    if (int rc = ensure(b.ivid, std::max<int64_t>(rows_cap, n_rows), 0)) return rc;
-    if (int rc = ensure(b.drows, delta_capacity(std::max<int64_t>(rows_cap, n_rows)), 0)) return rc;
-    // ONE directory over the distinct keys of all rows, load <= 0.25 (kIxDirLoadPct).  Sized from a guess -
-    // a fingerprint corpus repeats its keys many times over (cuts sit on frame grids) - and doubled
-    // while too crowded
+    int64_t post() const { return 2 * pairs + (int64_t)kIxMaxParts * kIxClasses * 64 + kIxPostPad; }
+    int64_t ext16() const { return 2 * pairs + 64 * 1024; }      // external lists: whole lines, lists of > 40 postings only
+    int64_t bucket_dir_bytes(uint32_t nb) const { return (int64_t)nb * kBkBytes + 2 * (ext16() + kIxPostPad); }
+};
+
+GenSizes gen_sizes(int64_t n_rows, int64_t live_keys, int64_t rows_cap, int64_t keys_cap) {
+    return {std::max<int64_t>(rows_cap, n_rows), std::max<int64_t>(keys_cap, live_keys)};
+}
+
+// the classic directory of 2^log2 entries of `es` bytes, and the unpartitioned build's fill cursors for it
+int64_t classic_dir_bytes(int log2, int es) { return ((int64_t)1 << log2) * es; }
+int64_t fillc_words(int log2, int ks) { return ((int64_t)1 << log2) * (ks ? ks / 2 : 1); }
+
+// The first half of the partitioned build, the same for both directory formats: every row's ivid entry, and the
+// (key, row) pairs of rows [0, n_rows) grouped by directory slice in ix.pkeys / ix.prows; ix.pcnt holds the per-slice
+// counts, then the slice starts (ix.pcnt.p + kIxMaxParts), then the scatter cursors.
+int build_partition(tvz_corpus *c, const Row *d_rows, int64_t n_rows, int64_t live_keys, int64_t pairs, int bits,
+                    int64_t n_parts, int32_t *ivid, hipStream_t st) {
+    Index &ix = c->ix;
+    if (int rc = ensure(ix.pkeys, pairs, 0)) return rc;
+    if (int rc = ensure(ix.prows, pairs, 0)) return rc;
+    if (int rc = ensure(ix.pcnt, 6 * (int64_t)kIxMaxParts + 8, 0)) return rc;
+    uint32_t *cnt = ix.pcnt.p, *start = cnt + kIxMaxParts, *cur = start + kIxMaxParts + 1;
+    // rows per block of the partition kernels: ~16 pairs per block and slice, so that a block's
+    // one reservation per slice is a small share of its work
+    const int64_t mean_len = std::max<int64_t>(1, live_keys / n_rows);
+    const int32_t rpb = (int32_t)std::min<int64_t>(4096, std::max<int64_t>(kBlock / 64 * 2, 16 * n_parts / mean_len));
+    hipLaunchKernelGGL(ix_part_clear_kernel, dim3(4), dim3(kBlock), 0, st, cnt, (int)n_parts, ix.info);
+    hipLaunchKernelGGL(ix_partition_kernel, dim3((unsigned)tvz::ceil_div(n_rows, rpb)), dim3(kBlock), (size_t)n_parts * 4, st,
+                       d_rows, n_rows, rpb, c->keys.p, bits, (int)n_parts, cnt, ivid);
+    hipLaunchKernelGGL(ix_part_scan_kernel, dim3(1), dim3(1024), 0, st, cnt, (int)n_parts, start, cur, ix.info);
+    // the scatter: rows worth about one staging area per block
+    const int32_t srpb = (int32_t)std::max<int64_t>(1, kIxStagePairs / mean_len);
+    const size_t sclds = (size_t)kIxStagePairs * 12 + ((size_t)3 * n_parts + 1) * 4;
+    hipLaunchKernelGGL(ix_scatter_kernel, dim3((unsigned)tvz::ceil_div(n_rows, srpb)), dim3(kIxScatterBlock), sclds,
+                       st, d_rows, n_rows, srpb, c->keys.p, bits, (int)n_parts, cur, ix.pkeys.p, ix.prows.p);
+    return TVZ_OK;
+}
+
+// the build's result, read back once its launches are done
+int read_build_info(Index &ix, hipStream_t st, IxBuildInfo &info) {
+    TVZ_HIP(hipGetLastError());
+    TVZ_HIP(hipMemcpyAsync(ix.h_info, ix.info, sizeof(info), hipMemcpyDeviceToHost, st));
+    if (int rc = wait_stream_polling(st, ix.build_ev)) return rc;
+    info = *ix.h_info;
+    return TVZ_OK;
+}
+
+// One sub-index: the bucket directory (tvz_bucket_dir.h).  Bytes the records need: 8 per distinct key + 2 per posting;
+// buckets for a fill of kBkFillPct % of their payload.  Fuller: more lists do not fit beside their bucket's other
+// records and move to the external area - a second line for every lookup that asks for them, and the long lists are
+// the ones asked for most; emptier: a larger table.  The distinct keys are known from the last build, else guessed and
+// the build repeated once at the size the count revealed.  Leaves b.nb = 0 when the keys do not fit (the classic
+// format then).
+int build_bucket_dir(tvz_corpus *c, IndexBuf &b, const Row *d_rows, int64_t n_rows, int64_t live_keys,
+                     const GenSizes &sz, hipStream_t st, IxBuildInfo &info) {
+    Index &ix = c->ix;
+    auto buckets_for = [&](double distinct) {
+        const double bytes = 8.0 * distinct + 2.0 * (double)live_keys;
+        const int64_t want = (int64_t)(bytes * 100.0 / ((double)kBkFillPct * kBkPayload)) + 1;
+        return (uint32_t)std::min<int64_t>(tvz::round_up(std::max<int64_t>(want, kBkSlice), kBkSlice), (int64_t)kIxMaxParts * kBkSlice);
+    };
+    double distinct = ix.hint_post > 0 ? (double)ix.hint_distinct * (double)live_keys / (double)ix.hint_post * 1.1
+                                       : (double)live_keys / 4.0;
+    uint32_t nb = buckets_for(distinct);
+    bool resized = false;
+    for (int attempt = 0; attempt < 8; ++attempt) {
+        const int64_t n_parts = nb / kBkSlice;
+        if (int rc = build_partition(c, d_rows, n_rows, live_keys, sz.pairs, -(int)nb, n_parts, b.ivid.p, st)) return rc;
+        if (int rc = ensure(b.dir, sz.bucket_dir_bytes(nb), 0)) return rc;
+        hipLaunchKernelGGL(bk_slice_build_kernel, dim3((unsigned)n_parts), dim3(kBkBuildBlock), kBkBuildLds, st,
+                           ix.pkeys.p, ix.prows.p, ix.pcnt.p + kIxMaxParts, b.dir.p, nb,
+                           (uint32_t)std::min<int64_t>(sz.ext16(), 0x7fffffffLL), ix.info);
+        if (int rc = read_build_info(ix, st, info)) return rc;
+        if (!info.failed) {
+            const uint32_t fit = buckets_for((double)info.n_distinct);
+            // (a first build that guessed the distinct keys: once more at the right size if it is off by a quarter)
+            if (!resized && (fit > nb + nb / 4 || fit + fit / 4 < nb)) { nb = fit; resized = true; continue; }
+            b.nb = nb;
+            b.ks = 0;
+            b.dir_log2 = 0;
+            b.slice_log2 = 0;
+            return TVZ_OK;
+        }
+        if (nb >= (uint32_t)kIxMaxParts * kBkSlice) break;            // too many keys for slices of 256 buckets: classic format
+        nb = (uint32_t)std::min<int64_t>(tvz::round_up((int64_t)nb + nb / 2, kBkSlice), (int64_t)kIxMaxParts * kBkSlice);
+    }
+    return TVZ_OK;
+}
+
+// The classic directory (tvz_index_kernels.h): ONE directory over the distinct keys of all rows, load <= 0.25
+// (kIxDirLoadPct).  Sized from a guess - a fingerprint corpus repeats its keys many times over (cuts sit on frame
+// grids) - and doubled while too crowded.
+int build_classic(tvz_corpus *c, IndexBuf &b, const Row *d_rows, int64_t n_rows, int64_t live_keys,
+                  const GenSizes &sz, int n_sub, hipStream_t st, IxBuildInfo &info) {
+    Index &ix = c->ix;
+    const int ks = ix_ks(n_sub), es = ix_entry_bytes(ks);
+    const int64_t post_cap = sz.post();
     // the size for `distinct` keys: load <= kIxDirLoadPct - unless that directory is too large for the
     // partitioned build while one of half the size (load <= 0.5) is not (1 M rows x 62 sub-indexes: 144-byte
     // entries, 4,096 slices of 128 KB at load 0.5)
@@ -409,87 +500,6 @@ int build_kernels(tvz_corpus *c, IndexBuf &b, const Row *d_rows, int64_t n_rows,
         if (!partitionable(lg) && partitionable(lg - 1) && (double)((int64_t)1 << (lg - 1)) >= 2.0 * distinct) --lg;
         return lg;
     };
-    b.nb = 0;
-    if (n_sub == 1) {
-        // ---- one sub-index: the bucket directory (tvz_bucket_dir.h) ----
-        // bytes the records need: 8 per distinct key + 2 per posting; buckets for a fill of kBkFillPct % of their
-        // payload.  Fuller: more lists do not fit beside their bucket's other records and move to the external area -
-        // a second line for every lookup that asks for them, and the long lists are the ones asked for most; emptier:
-        // a larger table.  The distinct keys are known from the last build, else guessed and the build repeated once
-        // at the size the count revealed.
-        const int64_t pairs_cap = std::max<int64_t>(keys_cap, live_keys);
-        const int64_t ext_cap16 = 2 * pairs_cap + 64 * 1024;              // external lists: whole lines, lists of > 40 postings only
-        auto buckets_for = [&](double distinct) {
-            const double bytes = 8.0 * distinct + 2.0 * (double)live_keys;
-            const int64_t want = (int64_t)(bytes * 100.0 / ((double)kBkFillPct * kBkPayload)) + 1;
-            return (uint32_t)std::min<int64_t>(tvz::round_up(std::max<int64_t>(want, kBkSlice), kBkSlice), (int64_t)kIxMaxParts * kBkSlice);
-        };
-        double distinct = ix.hint_post > 0 ? (double)ix.hint_distinct * (double)live_keys / (double)ix.hint_post * 1.1
-                                           : (double)live_keys / 4.0;
-        uint32_t nb = buckets_for(distinct);
-        bool resized = false, ok = false;
-        if (int rc = ensure(ix.pkeys, pairs_cap, 0)) return rc;
-        if (int rc = ensure(ix.prows, pairs_cap, 0)) return rc;
-        if (int rc = ensure(ix.pcnt, 6 * (int64_t)kIxMaxParts + 8, 0)) return rc;
-        IxBuildInfo info{};
-        for (int attempt = 0; attempt < 8; ++attempt) {
-            const int64_t n_parts = nb / kBkSlice;
-            const int64_t dir_bytes = (int64_t)nb * kBkBytes + 2 * (ext_cap16 + kIxPostPad);
-            if (int rc = ensure(b.dir, dir_bytes, 0)) return rc;
-            uint32_t *cnt = ix.pcnt.p, *start = cnt + kIxMaxParts, *cur = start + kIxMaxParts + 1;
-            const int bits = -(int)nb;
-            const int64_t mean_len = std::max<int64_t>(1, live_keys / n_rows);
-            const int32_t rpb = (int32_t)std::min<int64_t>(4096, std::max<int64_t>(kBlock / 64 * 2, 16 * n_parts / mean_len));
-            hipLaunchKernelGGL(ix_part_clear_kernel, dim3(4), dim3(kBlock), 0, st, cnt, (int)n_parts, ix.info);
-            hipLaunchKernelGGL(ix_partition_kernel, dim3((unsigned)tvz::ceil_div(n_rows, rpb)), dim3(kBlock), (size_t)n_parts * 4, st,
-                               d_rows, n_rows, rpb, c->keys.p, bits, (int)n_parts, cnt, b.ivid.p);
-            hipLaunchKernelGGL(ix_part_scan_kernel, dim3(1), dim3(1024), 0, st, cnt, (int)n_parts, start, cur, ix.info);
-            const int32_t srpb = (int32_t)std::max<int64_t>(1, kIxStagePairs / mean_len);
-            const size_t sclds = (size_t)kIxStagePairs * 12 + ((size_t)3 * n_parts + 1) * 4;
-            hipLaunchKernelGGL(ix_scatter_kernel, dim3((unsigned)tvz::ceil_div(n_rows, srpb)), dim3(kIxScatterBlock), sclds,
-                               st, d_rows, n_rows, srpb, c->keys.p, bits, (int)n_parts, cur, ix.pkeys.p, ix.prows.p);
-            hipLaunchKernelGGL(bk_slice_build_kernel, dim3((unsigned)n_parts), dim3(kBkBuildBlock), kBkBuildLds, st,
-                               ix.pkeys.p, ix.prows.p, start, b.dir.p, nb, (uint32_t)std::min<int64_t>(ext_cap16, 0x7fffffffLL), ix.info);
-            TVZ_HIP(hipGetLastError());
-            TVZ_HIP(hipMemcpyAsync(ix.h_info, ix.info, sizeof(info), hipMemcpyDeviceToHost, st));
-            if (int rc = wait_stream_polling(st, ix.build_ev)) return rc;
-            info = *ix.h_info;
-            if (!info.failed) {
-                const uint32_t fit = buckets_for((double)info.n_distinct);
-                // (a first build that guessed the distinct keys: once more at the right size if it is off by a quarter)
-                if (!resized && (fit > nb + nb / 4 || fit + fit / 4 < nb)) { nb = fit; resized = true; continue; }
-                ok = true;
-                break;
-            }
-            if (nb >= (uint32_t)kIxMaxParts * kBkSlice) break;            // too many keys for slices of 256 buckets: classic format
-            nb = (uint32_t)std::min<int64_t>(tvz::round_up((int64_t)nb + nb / 2, kBkSlice), (int64_t)kIxMaxParts * kBkSlice);
-        }
-        if (ok) {
-            if ((int64_t)info.cursor != live_keys)
-                return tvz::fail(TVZ_ERR_INVALID, "internal: index holds %u postings for %lld keys", info.cursor,
-                                 (long long)live_keys);
-            b.nb = nb;
-            b.slice_log2 = 0;
-            b.n_sub = 1;
-            b.ks = 0;
-            b.dir_log2 = 0;
-            b.n_main = n_rows;
-            b.n_post = info.cursor;
-            b.n_distinct = info.n_distinct;
-            b.n_spilled = info.n_spilled;
-            b.n_ext = info.n_ext;
-            b.max_spill = info.max_spill;
-            b.ext_used = info.ext_cursor;
-            ix.hint_post = (int64_t)info.cursor;
-            ix.hint_distinct = (int64_t)info.n_distinct;
-            if (getenv("TVZ_DEBUG"))
-                fprintf(stderr, "[tvz] bucket directory: %u buckets (%.1f MB) for %u keys / %u postings, fill %.2f, %u keys walked on "
-                        "(max %u buckets), %u external lists (%.1f MB)\n", nb, nb * 128e-6, info.n_distinct, info.cursor,
-                        (8.0 * info.n_distinct + 2.0 * info.cursor) / ((double)nb * kBkPayload), info.n_spilled, info.max_spill,
-                        info.n_ext, info.ext_cursor * 2e-6);
-            return TVZ_OK;
-        }
-    }
     if (int rc = ensure(b.post, post_cap, 0)) return rc;
     int log2 = 10;
     if (ix.hint_post > 0) {
@@ -501,13 +511,12 @@ int build_kernels(tvz_corpus *c, IndexBuf &b, const Row *d_rows, int64_t n_rows,
     // one row per wave and SHORT-LIVED blocks (no grid-stride loop): a background build shares the GPU
     // with lookups, whose few blocks get a CU as soon as any of these retires
     const int64_t blocks = tvz::ceil_div(n_rows, kBlock / 64);
-    IxBuildInfo info{};
     int slice_log2 = 0;
     bool shrunk = false;
     while (true) {
         TVZ_REQUIRE(log2 <= 30, "index directory would exceed 2^30 entries");
         const int64_t dn = (int64_t)1 << log2;
-        if (int rc = ensure(b.dir, dn * es, 0)) return rc;
+        if (int rc = ensure(b.dir, classic_dir_bytes(log2, es), 0)) return rc;
         // Directory slices of ~32 KB (one block builds a slice in LDS; three such blocks leave room on
         // a CU for a lookup's block); larger ones if the slices would otherwise outnumber what the
         // partition kernels keep in LDS.  A directory of more than kIxMaxParts slices of 128 KB takes
@@ -521,28 +530,10 @@ int build_kernels(tvz_corpus *c, IndexBuf &b, const Row *d_rows, int64_t n_rows,
         if (!partitioned) slice_log2 = log2;
         const int bits = ix_dir_bits(log2, slice_log2);
         if (partitioned) {
-            const int64_t pairs_cap = std::max<int64_t>(keys_cap, live_keys);
-            if (int rc = ensure(ix.pkeys, pairs_cap, 0)) return rc;
-            if (int rc = ensure(ix.prows, pairs_cap, 0)) return rc;
-            if (int rc = ensure(ix.pcnt, 6 * (int64_t)kIxMaxParts + 8, 0)) return rc;
-            uint32_t *cnt = ix.pcnt.p, *start = cnt + kIxMaxParts, *cur = start + kIxMaxParts + 1;
-            uint32_t *ptot = cur + kIxMaxParts, *pstart = ptot + kIxMaxParts, *scratch = pstart + kIxMaxParts + 1;
-            // rows per block of the partition kernels: ~16 pairs per block and slice, so that a block's
-            // one reservation per slice is a small share of its work
-            const int64_t mean_len = std::max<int64_t>(1, live_keys / n_rows);
-            const int32_t rpb = (int32_t)std::min<int64_t>(4096, std::max<int64_t>(kBlock / 64 * 2, 16 * n_parts / mean_len));
-            const unsigned pblocks = (unsigned)tvz::ceil_div(n_rows, rpb);
-            const size_t plds = (size_t)n_parts * 4;
+            if (int rc = build_partition(c, d_rows, n_rows, live_keys, sz.pairs, bits, n_parts, b.ivid.p, st)) return rc;
+            uint32_t *start = ix.pcnt.p + kIxMaxParts, *ptot = start + 2 * kIxMaxParts + 1, *pstart = ptot + kIxMaxParts;
+            uint32_t *scratch = pstart + kIxMaxParts + 1;
             const size_t slds = std::max<size_t>(((size_t)es << slice_log2), (size_t)kIxSliceLdsFloor);
-            hipLaunchKernelGGL(ix_part_clear_kernel, dim3(4), dim3(kBlock), 0, st, cnt, (int)n_parts, ix.info);
-            hipLaunchKernelGGL(ix_partition_kernel, dim3(pblocks), dim3(kBlock), plds, st, d_rows, n_rows, rpb,
-                               c->keys.p, bits, (int)n_parts, cnt, b.ivid.p);
-            hipLaunchKernelGGL(ix_part_scan_kernel, dim3(1), dim3(1024), 0, st, cnt, (int)n_parts, start, cur, ix.info);
-            // the scatter: rows worth about one staging area per block
-            const int32_t srpb = (int32_t)std::max<int64_t>(1, kIxStagePairs / mean_len);
-            const size_t sclds = (size_t)kIxStagePairs * 12 + ((size_t)3 * n_parts + 1) * 4;
-            hipLaunchKernelGGL(ix_scatter_kernel, dim3((unsigned)tvz::ceil_div(n_rows, srpb)), dim3(kIxScatterBlock), sclds,
-                               st, d_rows, n_rows, srpb, c->keys.p, bits, (int)n_parts, cur, ix.pkeys.p, ix.prows.p);
             hipLaunchKernelGGL(ix_slice_count_kernel, dim3((unsigned)n_parts), dim3(kIxSliceBlock), slds, st,
                                ix.pkeys.p, ix.prows.p, start, b.dir.p, es, ks, bits, ptot, ix.info);
             hipLaunchKernelGGL(ix_part_scan_kernel, dim3(1), dim3(1024), 0, st, ptot, (int)n_parts, pstart, scratch,
@@ -550,18 +541,15 @@ int build_kernels(tvz_corpus *c, IndexBuf &b, const Row *d_rows, int64_t n_rows,
             hipLaunchKernelGGL(ix_slice_fill_kernel, dim3((unsigned)n_parts), dim3(kIxSliceBlock), slds, st,
                                ix.pkeys.p, ix.prows.p, start, pstart, b.dir.p, es, ks, bits, b.post.p);
         } else {
-            const int64_t fw = ks ? ks / 2 : 1;
-            if (int rc = ensure(ix.fillc, tvz::round_up(dn * fw, 4), 0)) return rc;
+            const int64_t fillc = tvz::round_up(fillc_words(log2, ks), 4);
+            if (int rc = ensure(ix.fillc, fillc, 0)) return rc;
             hipLaunchKernelGGL(ix_clear_kernel, dim3(2048), dim3(kBlock), 0, st, reinterpret_cast<uint4 *>(b.dir.p),
                                (size_t)(dn * es / 16), es / 16, reinterpret_cast<uint4 *>(ix.fillc.p),
-                               (size_t)(tvz::round_up(dn * fw, 4) / 4), ix.info);
+                               (size_t)(fillc / 4), ix.info);
             hipLaunchKernelGGL(ix_count_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, d_rows, n_rows, c->keys.p,
                                b.dir.p, es, ks, bits, b.ivid.p, ix.info);
         }
-        TVZ_HIP(hipGetLastError());
-        TVZ_HIP(hipMemcpyAsync(ix.h_info, ix.info, sizeof(info), hipMemcpyDeviceToHost, st));
-        if (int rc = wait_stream_polling(st, ix.build_ev)) return rc;
-        info = *ix.h_info;
+        if (int rc = read_build_info(ix, st, info)) return rc;
         if (!info.failed && (int64_t)info.n_distinct * 2 <= dn) {            // accepted up to load 0.5; sized for kIxDirLoadPct
             // A directory guessed from the key count of a corpus that repeats its keys (the first
             // build of a handle) comes out many times too large - 4 M entries for 442 k distinct keys
@@ -575,26 +563,57 @@ int build_kernels(tvz_corpus *c, IndexBuf &b, const Row *d_rows, int64_t n_rows,
                                (size_t)dn, es, ks, ix.info);
             hipLaunchKernelGGL(ix_fill_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, d_rows, n_rows, c->keys.p,
                                b.dir.p, es, ks, bits, ix.fillc.p, b.post.p);
-            TVZ_HIP(hipGetLastError());
-            TVZ_HIP(hipMemcpyAsync(ix.h_info, ix.info, sizeof(info), hipMemcpyDeviceToHost, st));
-            if (int rc = wait_stream_polling(st, ix.build_ev)) return rc;
-            info = *ix.h_info;
+            if (int rc = read_build_info(ix, st, info)) return rc;
             break;
         }
         ++log2;                                       // too crowded (or a slice overflowed): twice the directory
     }
+    b.ks = ks;
+    b.dir_log2 = log2;
+    b.slice_log2 = slice_log2;
+    return TVZ_OK;
+}
+
+// Build the index of rows [0, n_rows) of the row table image `d_rows` (keys in c->keys) into
+// generation `b` on stream `st`, and wait for it.  `b` must have no reader; nothing of the handle's
+// published state is touched.  rows_cap / keys_cap: the corpus RESERVATION the buffers are sized
+// with, so the rebuilds that upserts trigger allocate nothing until the corpus outgrows it.
+int build_kernels(tvz_corpus *c, IndexBuf &b, const Row *d_rows, int64_t n_rows, int64_t live_keys,
+                  int64_t rows_cap, int64_t keys_cap, hipStream_t st) {
+    Index &ix = c->ix;
+    // posting offsets and counts are 32-bit: a larger shard is swept (shard it over more GPUs)
+    if (n_rows == 0 || live_keys >= (int64_t)0xfffffff0LL)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "corpus of %lld rows / %lld keys gets no index", (long long)n_rows,
+                         (long long)live_keys);
+    const int n_sub = (int)tvz::ceil_div(n_rows, kSubRows);
+    TVZ_REQUIRE(n_sub <= 4096, "too many rows for the index (%lld)", (long long)n_rows);
+    const GenSizes sz = gen_sizes(n_rows, live_keys, rows_cap, keys_cap);
+    if (int rc = ensure(b.ivid, sz.rows, 0)) return rc;
+    if (int rc = ensure(b.drows, delta_capacity(sz.rows), 0)) return rc;
+    IxBuildInfo info{};
+    b.nb = 0;
+    if (n_sub == 1)
+        if (int rc = build_bucket_dir(c, b, d_rows, n_rows, live_keys, sz, st, info)) return rc;
+    if (b.nb == 0)
+        if (int rc = build_classic(c, b, d_rows, n_rows, live_keys, sz, n_sub, st, info)) return rc;
     if ((int64_t)info.cursor != live_keys)
         return tvz::fail(TVZ_ERR_INVALID, "internal: index holds %u postings for %lld keys", info.cursor,
                          (long long)live_keys);
-    b.slice_log2 = slice_log2;
     b.n_sub = n_sub;
-    b.ks = ks;
-    b.dir_log2 = log2;
     b.n_main = n_rows;
     b.n_post = info.cursor;
+    b.n_distinct = info.n_distinct;
+    b.n_spilled = info.n_spilled;
+    b.n_ext = info.n_ext;
+    b.max_spill = info.max_spill;
+    b.ext_used = info.ext_cursor;
     ix.hint_post = (int64_t)info.cursor;
     ix.hint_distinct = (int64_t)info.n_distinct;
-    b.n_distinct = info.n_distinct;
+    if (b.nb && tvz_debug())
+        fprintf(stderr, "[tvz] bucket directory: %u buckets (%.1f MB) for %u keys / %u postings, fill %.2f, %u keys walked on "
+                "(max %u buckets), %u external lists (%.1f MB)\n", b.nb, b.nb * 128e-6, info.n_distinct, info.cursor,
+                (8.0 * info.n_distinct + 2.0 * info.cursor) / ((double)b.nb * kBkPayload), info.n_spilled, info.max_spill,
+                info.n_ext, info.ext_cursor * 2e-6);
     return TVZ_OK;
 }
 
@@ -613,17 +632,19 @@ int build_index(tvz_corpus *c) {
     ++ix.builds;
     // size the OTHER generation and the snapshot buffer now, while nobody is waiting: a background
     // rebuild then allocates nothing (hipMalloc / hipFree synchronise the whole device - a lookup in
-    // flight would wait for them)
+    // flight would wait for them).  `post` as large as the current generation's: nothing for a bucket directory,
+    // whose postings live in `dir`.
     IndexBuf &o = ix.buf[ix.cur ^ 1];
     const IndexBuf &n = ix.buf[ix.cur];
-    const int64_t dir_bytes = n.nb ? n.dir.cap / 2 : ((int64_t)1 << n.dir_log2) * ix_entry_bytes(n.ks);
+    const GenSizes sz = gen_sizes(n_rows, c->live_keys, c->rows.cap, c->keys.cap);
+    const int64_t dir_bytes = n.nb ? n.dir.cap / 2 : classic_dir_bytes(n.dir_log2, ix_entry_bytes(n.ks));
     (void)ensure(o.dir, 2 * dir_bytes, 0);         // room for the directory to double once
     if (n.slice_log2 == n.dir_log2)                // the unpartitioned build's cursors
-        (void)ensure(ix.fillc, 2 * (((int64_t)1 << n.dir_log2) * (n.ks ? n.ks / 2 : 1)), 0);
+        (void)ensure(ix.fillc, 2 * fillc_words(n.dir_log2, n.ks), 0);
     (void)ensure(o.post, n.post.cap, 0);
     (void)ensure(o.ivid, n.ivid.cap, 0);
     (void)ensure(o.drows, n.drows.cap, 0);
-    (void)ensure(ix.snap_rows, c->rows.cap, 0);
+    (void)ensure(ix.snap_rows, sz.rows, 0);
     (void)ensure(ix.dead_rows, n.drows.cap, 0);
     return TVZ_OK;
 }
@@ -641,13 +662,6 @@ void wait_no_build(tvz_corpus *c, std::unique_lock<std::shared_mutex> &lk) {
 // stream, and the swap - a few host operations plus one small copy and one small kernel on the
 // mutation stream - publishes it.  Matches enqueued before the swap finish on the old generation,
 // whose buffers stay untouched until the NEXT rebuild (which first waits for them).
-static bool tvz_debug() { static const bool on = getenv("TVZ_DEBUG") != nullptr; return on; }
-static double tvz_now_us() {
-    timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3;
-}
-
 int rebuild_in_background(tvz_corpus *c, std::unique_lock<std::shared_mutex> &lk) {
     Index &ix = c->ix;
     const double t_dbg0 = tvz_debug() ? tvz_now_us() : 0.0;
@@ -856,8 +870,11 @@ struct WsLayout {
     int32_t *flags = nullptr;       // [Q] queries the one-wave top-k left to the block kernels
     int32_t *pair = nullptr;        // [2][Q][k+1][3] fused lookup: the index's block + the delta sweep's, merged into `local`
     unsigned char *longq = nullptr; // scratch of the batch's long queries (> 4,095 timestamps): LAST, so that a larger
-    size_t longq_bytes = 0;         //   workspace (tvz_match_workspace_bytes_long) simply has more of it
-    size_t total = 0;
+    size_t total = 0;               //   workspace (tvz_match_workspace_bytes_long) simply has more of it
+    // the long queries' scratch in the caller's workspace of `bytes` at `base`: its whole tail from `longq` on
+    size_t longq_bytes(const void *base, size_t bytes) const {
+        return longq ? (size_t)(static_cast<const unsigned char *>(base) + bytes - longq) : 0;
+    }
 };
 
 // scratch the long queries of a batch need (ts_longq_sort_kernel): per query of n keys a power-of-two sort buffer
@@ -900,8 +917,7 @@ WsLayout ws_layout(void *base, int32_t Q, int32_t max_query_len, int32_t cap, in
         const int64_t T = total_query_keys > 0 ? total_query_keys : (int64_t)true_max_len;
         const int64_t L = std::min<int64_t>(Q > 0 ? Q : 1, T / (kMaxQueryLen + 1) + 1);
         w.longq = reinterpret_cast<unsigned char *>(p);
-        w.longq_bytes = longq_bytes_bound(T, L);
-        p += al256(w.longq_bytes);
+        p += al256(longq_bytes_bound(T, L));
     }
     w.total = (size_t)(p - p0) + 256;
     return w;
@@ -1137,21 +1153,26 @@ bool index_topk_usable(const tvz_corpus *c, int32_t Q, int32_t max_query_len, in
     return ix_lds_bytes(max_query_len, ix.n_sub, true) <= (size_t)kIxMaxLds;
 }
 
+// Can the one-wave lookup (tvz_index_wave_kernels.h) answer the batch?  A handle of ONE sub-index (a rank's share of
+// an 8-way sharded 100k-video table) of up to kWqRows rows in the bucket format, queries of up to kWqMaxLen timestamps,
+// and what the fused lookup takes (index_topk_usable).
+bool wave_usable(const tvz_corpus *c, int32_t max_query_len, int32_t min_match, int32_t k, int32_t algo) {
+    if (!kWqUsable || !c->ix.valid || (algo != TVZ_ALGO_AUTO && algo != TVZ_ALGO_INDEX)) return false;
+    const IndexBuf &ix = c->ix.now();
+    return ix.n_sub == 1 && ix.nb > 0 && ix.n_main <= kWqRows && max_query_len <= kWqMaxLen && min_match >= 1 &&
+           min_match <= kTop && k <= kIxTkMaxK;
+}
+
 // (A separate probe pass in front of this kernel - every directory probe of the batch in one launch, the
 // lookup blocks starting from coalesced records - was measured in round 4 and lost: the lookup got 10.7 us
 // faster on a 1/8 shard, the probe pass cost 27 us: profiles/r4_probe_prepass.txt.)
 int launch_index_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
                       int32_t max_query_len, int32_t min_match, const int32_t *d_exclude_ids, int32_t cap,
-                      int32_t k, int32_t *d_block, int32_t flags, hipStream_t st) {
+                      int32_t k, int32_t *d_block, bool wave, int32_t flags, hipStream_t st) {
     const IndexBuf &ix = c->ix.now();
-    // A handle of ONE sub-index (a rank's share of an 8-way sharded 100k-video table) and queries of up to 512
-    // timestamps: one WAVE per query (tvz_index_wave_kernels.h) - no barriers, every probe of the query in flight at
-    // once, the postings in registers between the passes.
-    const bool wave_fits = kWqUsable && ix.n_sub == 1 && ix.nb > 0 && ix.n_main <= kWqRows && max_query_len <= kWqMaxLen;
-    if ((flags & TVZ_ALGO_WAVE) && !wave_fits)
-        return tvz::fail(TVZ_ERR_UNSUPPORTED, "TVZ_ALGO_WAVE: the one-wave lookup takes a handle of one sub-index (this one: %d) of up to %d rows "
-                         "and queries of up to %d timestamps (max_query_len %d)", ix.n_sub, kWqRows, kWqMaxLen, max_query_len);
-    if (wave_fits && (flags & (TVZ_ALGO_WAVE | TVZ_ALGO_PREFER_WAVE)) && !(flags & (TVZ_ALGO_NO_WAVE | TVZ_ALGO_PAIR))) {
+    // wave (wave_usable and asked for): one WAVE per query - no barriers, every probe of the query in flight at once,
+    // the postings in registers between the passes.
+    if (wave) {
         const size_t lds = wq_lds_bytes(max_query_len);
 #define TVZ_WQK(MODE)                                                                                        \
     hipLaunchKernelGGL((ts_match_wq_topk_kernel<MODE>), dim3((unsigned)Q), dim3(64), lds, st, ix.dir.p,        \
@@ -1365,10 +1386,7 @@ int launch_topk_local(const int32_t *d_hits, const int32_t *d_hits_n, int32_t ns
 
 // merge of n_lists per-rank blocks of k + 1 rows (mode 2) / plain top-k over n_lists lists (mode 0)
 int launch_topk_lists(const int32_t *d_lists, const int32_t *d_lists_n, int32_t n_lists, int32_t Q, int32_t cap,
-                      int32_t k, int32_t *d_topk, int mode, int32_t *d_totals, int32_t *d_flags, hipStream_t st) {
-    const int32_t *flags = nullptr;
-    unsigned grid = (unsigned)Q;
-    (void)d_flags;
+                      int32_t k, int32_t *d_topk, int mode, int32_t *d_totals, hipStream_t st) {
     if (mode == 2 && n_lists <= 16 && k <= 64) {
         // the gathered blocks are sorted (tvz_match_topk / tvz_topk_shard wrote them): a k-way merge, 64 / G queries
         // per wave, instead of a selection over an unordered set
@@ -1395,8 +1413,8 @@ int launch_topk_lists(const int32_t *d_lists, const int32_t *d_lists_n, int32_t 
         TVZ_HIP(hipGetLastError());
         return TVZ_OK;
     }
-    hipLaunchKernelGGL(ts_topk_kernel, dim3(grid), dim3(kBlock), 0, st, d_lists, d_lists_n, n_lists, Q,
-                       cap, k, d_topk, mode, d_totals, flags);
+    hipLaunchKernelGGL(ts_topk_kernel, dim3((unsigned)Q), dim3(kBlock), 0, st, d_lists, d_lists_n, n_lists, Q,
+                       cap, k, d_topk, mode, d_totals, static_cast<const int32_t *>(nullptr));
     TVZ_HIP(hipGetLastError());
     return TVZ_OK;
 }
@@ -1434,14 +1452,12 @@ int tvz_match_topk_local(tvz_corpus *c, const double *d_queries, const int64_t *
     DeviceGuard dg(c->device);
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
     std::shared_lock<std::shared_mutex> lk(c->mu);
-    if (flags & TVZ_ALGO_WAVE) {          // asked for by name: say why not, instead of quietly taking another path
-        const bool fits = c->ix.valid && c->ix.now().n_sub == 1 && c->ix.now().nb > 0 && max_query_len <= kWqMaxLen && min_match >= 1 &&
-                          min_match <= kTop && k <= kIxTkMaxK && (algo == TVZ_ALGO_AUTO || algo == TVZ_ALGO_INDEX);
-        if (!fits)
-            return tvz::fail(TVZ_ERR_UNSUPPORTED, "TVZ_ALGO_WAVE: the one-wave lookup takes an indexed handle of ONE sub-index "
-                             "(this one: %d), queries of up to %d timestamps (max_query_len %d), min_match 1..5, k <= %d",
-                             c->ix.valid ? c->ix.now().n_sub : 0, kWqMaxLen, max_query_len, kIxTkMaxK);
-    }
+    const bool wave_ok = wave_usable(c, max_query_len, min_match, k, algo);
+    if ((flags & TVZ_ALGO_WAVE) && !wave_ok)          // asked for by name: say why not, instead of quietly taking another path
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "TVZ_ALGO_WAVE: the one-wave lookup takes an indexed handle of ONE sub-index "
+                         "(this one: %d) of up to %d rows, queries of up to %d timestamps (max_query_len %d), min_match 1..5, "
+                         "k <= %d", c->ix.valid ? c->ix.now().n_sub : 0, kWqRows, kWqMaxLen, max_query_len, kIxTkMaxK);
+    const bool wave = wave_ok && (flags & (TVZ_ALGO_WAVE | TVZ_ALGO_PREFER_WAVE)) && !(flags & (TVZ_ALGO_NO_WAVE | TVZ_ALGO_PAIR));
     if ((algo == TVZ_ALGO_AUTO || algo == TVZ_ALGO_INDEX) && index_topk_usable(c, Q, max_query_len, min_match, k)) {
         // the lookup keeps the k best itself: no hit list, no top-k launch.  Rows added or replaced since
         // the build are swept as usual; their block and the lookup's are merged (k + 1 rows each).
@@ -1449,7 +1465,7 @@ int tvz_match_topk_local(tvz_corpus *c, const double *d_queries, const int64_t *
         const int64_t n_delta = c->ix.n_delta;
         int32_t *blk = n_delta ? w.pair : d_out;
         if (int rc = launch_index_topk(c, d_queries, d_q_offsets, Q, max_query_len, min_match, d_exclude_ids, cap, k,
-                                       blk, flags, st))
+                                       blk, wave, flags, st))
             return rc;
         if (n_delta) {
             const RowSpan span{c->ix.now().drows.p, n_delta};
@@ -1467,21 +1483,12 @@ int tvz_match_topk_local(tvz_corpus *c, const double *d_queries, const int64_t *
         return record(c, st);
     }
     // the sweeps count into one-counter-per-line scratch; the select kernel reads it as it is
-    // (the long queries' scratch is the workspace's tail: all of it, however the caller sized it)
-    const size_t lq_bytes = w.longq ? (size_t)(static_cast<unsigned char *>(d_workspace) + workspace_bytes - w.longq) : 0;
-    if (int rc = launch_match(c, d_queries, d_q_offsets, Q, max_query_len, min_match, d_exclude_ids,
-                              cap, w.hits, w.counters, kCountStride, w.join, w.join_bytes, algo, st, w.longq, lq_bytes))
+    if (int rc = launch_match(c, d_queries, d_q_offsets, Q, max_query_len, min_match, d_exclude_ids, cap, w.hits,
+                              w.counters, kCountStride, w.join, w.join_bytes, algo, st, w.longq,
+                              w.longq_bytes(d_workspace, workspace_bytes)))
         return rc;
     if (int rc = launch_topk_local(w.hits, w.counters, kCountStride, Q, cap, k, d_out, 1, w.flags, st)) return rc;
     return record(c, st);
-}
-
-// merge of the gathered per-rank blocks with the workspace's flag array (tvz_match_sharded)
-int tvz_topk_merge_ws(const int32_t *d_gathered, int32_t n_ranks, int32_t Q, int32_t k, int32_t *d_topk,
-                      int32_t *d_totals, void *d_workspace, int32_t max_query_len, int32_t cap, void *hip_stream) {
-    const WsLayout w = ws_layout(d_workspace, Q, max_query_len, cap, k, n_ranks);
-    return launch_topk_lists(d_gathered, nullptr, n_ranks, Q, k + 1, k, d_topk, 2, d_totals, w.flags,
-                             reinterpret_cast<hipStream_t>(hip_stream));
 }
 
 int32_t *tvz_ws_local_block(void *d_workspace, int32_t Q, int32_t max_query_len, int32_t cap,
@@ -1659,46 +1666,35 @@ static int tvz_corpus_upload_impl(tvz_corpus *c, const int32_t *h_video_ids,
     // 100k-row table: 20 M keys) is cut into row ranges for the host's cores; the ranges' key runs are
     // appended in row order afterwards
     const int n_thr = n_rows >= 8192 ? (int)std::min<int64_t>(16, std::max(1u, std::thread::hardware_concurrency())) : 1;
-    if (n_thr > 1) {
-        struct Part { std::vector<int64_t> keys; std::vector<int32_t> lens; };
-        std::vector<Part> parts((size_t)n_thr);
-        std::vector<std::thread> pool;
-        for (int t = 0; t < n_thr; ++t)
-            pool.emplace_back([&, t] {
-                const int64_t r0 = n_rows * t / n_thr, r1 = n_rows * (t + 1) / n_thr;
-                Part &p = parts[(size_t)t];
-                p.keys.reserve((size_t)(h_offsets[r1] - h_offsets[r0] + (r1 - r0)));
-                p.lens.reserve((size_t)(r1 - r0));
-                for (int64_t r = r0; r < r1; ++r)
-                    p.lens.push_back((int32_t)canon_row(h_keys + h_offsets[r], h_offsets[r + 1] - h_offsets[r], p.keys));
-            });
-        for (std::thread &th : pool) th.join();
-        for (int t = 0; t < n_thr; ++t) {
-            const int64_t r0 = n_rows * t / n_thr;
-            const Part &p = parts[(size_t)t];
-            int64_t off = (int64_t)c->h_keys.size();
-            c->h_keys.insert(c->h_keys.end(), p.keys.begin(), p.keys.end());
-            for (size_t i = 0; i < p.lens.size(); ++i) {
-                const int64_t r = r0 + (int64_t)i;
-                Row row;
-                row.off = off;
-                row.len = p.lens[i];
-                row.vid = h_video_ids[r];
-                off += (row.len + 1) & ~(int64_t)1;          // (canon_row pads every row to an even count)
-                c->first_row.emplace(row.vid, r);
-                c->h_rows.push_back(row);
-                c->live_keys += row.len;
-            }
-        }
+    struct Part { std::vector<int64_t> keys; std::vector<int32_t> lens; };
+    std::vector<Part> parts((size_t)n_thr);
+    auto canon_part = [&](int t) {       // rows [r0, r1) -> their canonical keys + lengths
+        const int64_t r0 = n_rows * t / n_thr, r1 = n_rows * (t + 1) / n_thr;
+        if (r0 == r1) return;            // (no rows: h_offsets may be NULL)
+        Part &p = parts[(size_t)t];
+        p.keys.reserve((size_t)(h_offsets[r1] - h_offsets[r0] + (r1 - r0)));
+        p.lens.reserve((size_t)(r1 - r0));
+        for (int64_t r = r0; r < r1; ++r)
+            p.lens.push_back((int32_t)canon_row(h_keys + h_offsets[r], h_offsets[r + 1] - h_offsets[r], p.keys));
+    };
+    if (n_thr == 1) {
+        canon_part(0);
     } else {
-        for (int64_t r = 0; r < n_rows; ++r) {
-            Row row;
-            row.off = (int64_t)c->h_keys.size();
-            row.len = (int32_t)canon_row(h_keys + h_offsets[r], h_offsets[r + 1] - h_offsets[r], c->h_keys);
-            row.vid = h_video_ids[r];
+        std::vector<std::thread> pool;
+        for (int t = 0; t < n_thr; ++t) pool.emplace_back(canon_part, t);
+        for (std::thread &th : pool) th.join();
+    }
+    int64_t r = 0;
+    for (const Part &p : parts) {
+        int64_t off = (int64_t)c->h_keys.size();
+        c->h_keys.insert(c->h_keys.end(), p.keys.begin(), p.keys.end());
+        for (const int32_t len : p.lens) {
+            const Row row{off, len, h_video_ids[r]};
+            off += (len + 1) & ~(int64_t)1;                  // (canon_row pads every row to an even count)
             c->first_row.emplace(row.vid, r);
             c->h_rows.push_back(row);
-            c->live_keys += row.len;
+            c->live_keys += len;
+            ++r;
         }
     }
     // room for the table to double before anything has to grow
@@ -1934,10 +1930,8 @@ static int tvz_match_impl(tvz_corpus *c, const double *d_queries, const int64_t 
         if (workspace_bytes >= w.total) {
             ws = w.join;
             ws_bytes = w.join_bytes;
-            if (w.longq) {               // the long queries' scratch is the workspace's tail: all of it
-                lq = w.longq;
-                lq_bytes = (size_t)(static_cast<unsigned char *>(d_workspace) + workspace_bytes - w.longq);
-            }
+            lq = w.longq;
+            lq_bytes = w.longq_bytes(d_workspace, workspace_bytes);
             if (Q > 1) {                 // a lone query's counter shares its line with nobody: no gather launch
                 cnt = w.counters;
                 ns = kCountStride;
@@ -1969,49 +1963,37 @@ static int tvz_match_topk_impl(tvz_corpus *c, const double *d_queries, const int
                                 cap, k, d_out, d_workspace, workspace_bytes, 1, algo, hip_stream, nullptr);
 }
 
-static int tvz_find_duplicates_impl(tvz_corpus *c, const double *h_query, int64_t n,
-                                   int32_t min_match, int32_t exclude_id, int64_t cap,
-                                   int32_t *h_out_ids, int32_t *h_out_counts, int32_t *h_out_kth,
-                                   int64_t *n_out) {
-    TVZ_REQUIRE(c != nullptr && n_out != nullptr, "NULL argument");
-    TVZ_REQUIRE(n >= 0 && cap >= 0 && cap <= INT32_MAX, "bad size");
-    TVZ_REQUIRE(n == 0 || h_query, "h_query is NULL");
-    TVZ_REQUIRE(cap == 0 || (h_out_ids && h_out_counts), "NULL outputs");
-    TVZ_REQUIRE(n <= INT32_MAX, "query too long");
-    DeviceGuard dg(c->device);
-    Staging *s = nullptr;
-    if (int rc = staging_get(c, &s)) return rc;
-    struct Put { tvz_corpus *c; Staging *s; ~Put() { staging_put(c, s); } } put{c, s};
-    struct Hit { int32_t vid, cnt, kth; };
-    std::vector<Hit> long_hits;            // only the rare paths below use it
-    const Hit *found = nullptr;
-    int64_t n_found = 0;                   // hits the device reported (before the cap)
-    int64_t n_have = 0;                    // hits available in `found`
-    const int32_t excl = exclude_id >= 0 ? exclude_id : -1;
-    const bool one_launch = n <= kMaxQueryLen && min_match <= kTop;
-    if (one_launch) {
-        // ---- ONE launch + ONE synchronisation: the kernel writes its hits to pinned host memory;
-        // a query of up to 440 timestamps travels in the kernel arguments (no copy at all)
-        const bool by_value = n <= kQ1ByValKeys;
-        QByVal qv;
-        if (by_value) {
-            qv.n = (int32_t)n;
-            qv.pad = 0;
-            if (n) memcpy(qv.k, h_query, (size_t)n * 8);
-        } else {
-            s->h_query[0] = 0;
-            s->h_query[1] = n;
-            memcpy(s->h_query + 2, h_query, (size_t)n * 8);
-            TVZ_HIP(hipMemcpyAsync(s->d_query, s->h_query, (size_t)(n + 2) * 8, hipMemcpyHostToDevice, s->stream));
-        }
-        Hit *hh = reinterpret_cast<Hit *>(s->h_hits);
-        int64_t w = 0;
-        // with an index: rows unchanged since its build are answered by the lookup kernel (one
-        // block), rows in the delta table by the sweep - both write to pinned host memory, one
-        // synchronisation for the two.  A query the lookup refuses (> 4 G postings) is swept.
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            int blocks = 0, region = 0, n_sub = 0;
-            bool used_index = false;
+namespace {
+
+struct Hit { int32_t vid, cnt, kth; };
+
+// tvz_find_duplicates of a query of up to 4,095 timestamps with min_match <= 5: ONE launch + ONE synchronisation, the
+// kernel writes its hits to pinned host memory; a query of up to 440 timestamps travels in the kernel arguments (no
+// copy at all).  Leaves the hits at the start of s->h_hits, *n_hits of them.
+int find_pinned(tvz_corpus *c, Staging *s, const double *h_query, int64_t n, int32_t min_match, int32_t excl,
+                int64_t *n_hits) {
+    *n_hits = 0;
+    const bool by_value = n <= kQ1ByValKeys;
+    QByVal qv;
+    if (by_value) {
+        qv.n = (int32_t)n;
+        qv.pad = 0;
+        if (n) memcpy(qv.k, h_query, (size_t)n * 8);
+    } else {
+        s->h_query[0] = 0;
+        s->h_query[1] = n;
+        memcpy(s->h_query + 2, h_query, (size_t)n * 8);
+        TVZ_HIP(hipMemcpyAsync(s->d_query, s->h_query, (size_t)(n + 2) * 8, hipMemcpyHostToDevice, s->stream));
+    }
+    // with an index: rows unchanged since its build are answered by the lookup kernel (one
+    // block), rows in the delta table by the sweep - both write to pinned host memory, one
+    // synchronisation for the two.  A query the lookup refuses (> 4 G postings) is swept.
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        int blocks = 0, region = 0, n_sub = 0;
+        {
+            // drain() waits while a sweep of this staging is in flight: set at its launch, cleared once it is done
+            // (or failed to launch)
+            struct Busy { Staging *s; ~Busy() { s->busy.store(0, std::memory_order_release); } } busy{s};
             {
                 std::shared_lock<std::shared_mutex> lk(c->mu);
                 const int64_t n_rows = (int64_t)c->h_rows.size();
@@ -2020,16 +2002,14 @@ static int tvz_find_duplicates_impl(tvz_corpus *c, const double *h_query, int64_
                         n_rows > s->ix_slots) {
                         // the corpus outgrew its reservation (see tvz_corpus_reserve): grow this staging
                         if (int rc = staging_size(s, std::max<int64_t>(2 * n_rows, c->stage_rows))) return rc;
-                        hh = reinterpret_cast<Hit *>(s->h_hits);
                     }
                     if (int rc = wait_mutations(c, s->stream)) return rc;
                     const double *dq = by_value ? nullptr : reinterpret_cast<const double *>(s->d_query + 2);
                     const int64_t *dqo = by_value ? nullptr : s->d_query;
                     RowSpan span{c->rows.p, n_rows};
-                    s->busy.store(1, std::memory_order_release);         // drain() waits for this sweep
+                    s->busy.store(1, std::memory_order_release);
                     bool fused = false;
                     if (attempt == 0 && index_usable(c, min_match)) {
-                        used_index = true;
                         const IndexBuf &ib = c->ix.now();
                         n_sub = ib.n_sub;
                         s->gen = c->ix.cur;
@@ -2052,14 +2032,10 @@ static int tvz_find_duplicates_impl(tvz_corpus *c, const double *h_query, int64_
                        c->keys.p, s_log2, ho, by_value ? qv : kNoQuery)
                             if (min_match <= 2) TVZ_FUSED(false); else TVZ_FUSED(true);
 #undef TVZ_FUSED
-                            if (hipGetLastError() != hipSuccess) {
-                                s->busy.store(0, std::memory_order_release);
-                                return tvz::fail(TVZ_ERR_HIP, "fused lookup launch failed");
-                            }
+                            if (hipGetLastError() != hipSuccess) return tvz::fail(TVZ_ERR_HIP, "fused lookup launch failed");
                         } else if (int rc = launch_index<true>(c, dq, dqo, 1, (int32_t)n, min_match, nullptr, excl, 0,
                                                                s->dh_ix_hits, s->dh_counts + kQ1MaxBlocks, 1, s->stream,
                                                                by_value ? &qv : nullptr)) {
-                            s->busy.store(0, std::memory_order_release);
                             return rc;
                         }
                     }
@@ -2069,157 +2045,171 @@ static int tvz_find_duplicates_impl(tvz_corpus *c, const double *h_query, int64_
                         const HostOut ho{s->dh_hits, s->dh_counts, region};
                         if (int rc = launch_q1<true>(c, span, dq, dqo, 1, (int32_t)n, min_match, nullptr, excl, 0,
                                                      nullptr, nullptr, 1, blocks, ho, s->stream,
-                                                     by_value ? &qv : nullptr)) {
-                            s->busy.store(0, std::memory_order_release);
+                                                     by_value ? &qv : nullptr))
                             return rc;
-                        }
                     }
                 }
             }
             // (polling the per-block counts from the host instead was tried: it needs a system-scope
             // release per block, which saved 1.5 us at 5k rows and cost 60 us at 100k)
-            {
-                const hipError_t e = hipStreamSynchronize(s->stream);
-                s->busy.store(0, std::memory_order_release);
-                if (e != hipSuccess)
-                    return tvz::fail(TVZ_ERR_HIP, "single-query match failed: %s", hipGetErrorString(e));
-            }
-            bool refused = false;
-            for (int b = 0; b < n_sub; ++b) refused = refused || s->h_counts[kQ1MaxBlocks + b] < 0;
-            if (refused) continue;                                        // sweep everything instead
-            // compact the per-block regions in place (block order; sorted below anyway)
-            w = 0;
-            for (int b = 0; b < blocks; ++b) {
-                const int32_t nb = s->h_counts[b];
-                if (nb < 0) return tvz::fail(TVZ_ERR_INVALID, "internal: query table overflow");
-                const Hit *src = hh + (int64_t)b * region;
-                if (src != hh + w) memmove(hh + w, src, (size_t)nb * sizeof(Hit));
-                w += nb;
-            }
-            for (int b = 0; b < n_sub; ++b) {                              // the lookup's regions, one per sub-index
-                const int64_t nb = std::min<int64_t>(s->h_counts[kQ1MaxBlocks + b], kSubRows);
-                if (nb) memcpy(hh + w, reinterpret_cast<const Hit *>(s->h_ix_hits) + (int64_t)b * kSubRows,
-                               (size_t)nb * sizeof(Hit));
-                w += nb;
-            }
-            (void)used_index;
-            break;
+            const hipError_t e = hipStreamSynchronize(s->stream);
+            if (e != hipSuccess) return tvz::fail(TVZ_ERR_HIP, "single-query match failed: %s", hipGetErrorString(e));
         }
-        found = hh;
-        n_found = n_have = w;
-    } else {
-        // ---- rare paths (min_match > 5, or a query longer than a tile): device hit list, a
-        // fix-up pass for kth, explicit copies back
-        const int64_t want = std::max<int64_t>(cap, 1);
-        if (want > s->d_hit_slots) {
-            if (s->d_hits) (void)hipFree(s->d_hits);
-            s->d_hits = nullptr;
-            s->d_hit_slots = 0;
-            TVZ_HIP(hipMalloc(&s->d_hits, (size_t)want * 12));
-            s->d_hit_slots = want;
+        bool refused = false;
+        for (int b = 0; b < n_sub; ++b) refused = refused || s->h_counts[kQ1MaxBlocks + b] < 0;
+        if (refused) continue;                                        // sweep everything instead
+        // compact the per-block regions in place (block order; sorted by the caller anyway)
+        Hit *hh = reinterpret_cast<Hit *>(s->h_hits);
+        int64_t w = 0;
+        for (int b = 0; b < blocks; ++b) {
+            const int32_t nb = s->h_counts[b];
+            if (nb < 0) return tvz::fail(TVZ_ERR_INVALID, "internal: query table overflow");
+            const Hit *src = hh + (int64_t)b * region;
+            if (src != hh + w) memmove(hh + w, src, (size_t)nb * sizeof(Hit));
+            w += nb;
         }
-        std::vector<int64_t> uq;
-        std::vector<int32_t> mult;
-        const bool longq = n > kMaxQueryLen;
-        int64_t *d_q = s->d_query;
-        if (longq) {
-            // sorted distinct keys + multiplicities, searched per row key; the raw query (for the
-            // fix-up walk) travels behind them
-            std::vector<int64_t> sk;
-            sk.reserve((size_t)n);
-            for (int64_t i = 0; i < n; ++i) {
-                int64_t k;
-                if (canon_key(h_query[i], k)) sk.push_back(k);
-            }
-            std::sort(sk.begin(), sk.end());
-            for (size_t i = 0; i < sk.size(); ++i) {
-                if (!uq.empty() && uq.back() == sk[i]) ++mult.back();
-                else { uq.push_back(sk[i]); mult.push_back(1); }
-            }
-            const int64_t m = (int64_t)uq.size();
-            if (m + n + 3 > s->sq_cap) {
-                if (s->d_sq) (void)hipFree(s->d_sq);
-                if (s->d_smult) (void)hipFree(s->d_smult);
-                s->d_sq = nullptr; s->d_smult = nullptr; s->sq_cap = 0;
-                TVZ_HIP(hipMalloc(&s->d_sq, (size_t)(m + n + 3) * 8));
-                TVZ_HIP(hipMalloc(&s->d_smult, (size_t)(m + 1) * 4));
-                s->sq_cap = m + n + 3;
-            }
-            d_q = s->d_sq + m;                                   // {0, n} + raw query
-            const int64_t qoff[2] = {0, n};
-            TVZ_HIP(hipMemcpyAsync(d_q, qoff, 16, hipMemcpyHostToDevice, s->stream));
-            TVZ_HIP(hipMemcpyAsync(d_q + 2, h_query, (size_t)n * 8, hipMemcpyHostToDevice, s->stream));
-            if (m) {
-                TVZ_HIP(hipMemcpyAsync(s->d_sq, uq.data(), (size_t)m * 8, hipMemcpyHostToDevice, s->stream));
-                TVZ_HIP(hipMemcpyAsync(s->d_smult, mult.data(), (size_t)m * 4, hipMemcpyHostToDevice, s->stream));
-            }
-        } else {
-            s->h_query[0] = 0;
-            s->h_query[1] = n;
-            if (n) memcpy(s->h_query + 2, h_query, (size_t)n * 8);
-            TVZ_HIP(hipMemcpyAsync(s->d_query, s->h_query, (size_t)(n + 2) * 8, hipMemcpyHostToDevice, s->stream));
+        for (int b = 0; b < n_sub; ++b) {                              // the lookup's regions, one per sub-index
+            const int64_t nb = std::min<int64_t>(s->h_counts[kQ1MaxBlocks + b], kSubRows);
+            if (nb) memcpy(hh + w, reinterpret_cast<const Hit *>(s->h_ix_hits) + (int64_t)b * kSubRows,
+                           (size_t)nb * sizeof(Hit));
+            w += nb;
         }
-        {
-            std::shared_lock<std::shared_mutex> lk(c->mu);
-            const int64_t n_rows = (int64_t)c->h_rows.size();
-            if (int rc = wait_mutations(c, s->stream)) return rc;
-            if (int rc = launch_prep(s->d_hits_n, 1, 1, nullptr, 0, nullptr, 0, s->stream)) return rc;
-            if (n_rows) {
-                if (longq) {
-                    hipLaunchKernelGGL(ts_match_longq_kernel, dim3((unsigned)tvz::ceil_div(n_rows, kGroupsPerBlock)),
-                                       dim3(kBlock), 0, s->stream, c->rows.p, n_rows, c->keys.p, s->d_sq,
-                                       s->d_smult, (int32_t)uq.size(), min_match, -1, (int32_t)want, s->d_hits,
-                                       s->d_hits_n, static_cast<const int32_t *>(nullptr), static_cast<const int32_t *>(nullptr));
-                    TVZ_HIP(hipGetLastError());
-                    if (min_match > 0) {
-                        hipLaunchKernelGGL(ts_kth_fixup_kernel, dim3(1), dim3(kBlock), 0, s->stream, c->rows.p,
-                                           c->keys.p, reinterpret_cast<const double *>(d_q + 2), d_q, min_match,
-                                           (int32_t)want, s->d_hits, s->d_hits_n, 1);
-                        TVZ_HIP(hipGetLastError());
-                    }
-                } else {
-                    // min_match > 5 (or <= 0): what a batch of one takes - on an indexed handle the lookup with a
-                    // count-only pass B + the kth fix-up walk and a sweep of the delta table, else the single-query
-                    // sweep; the fix-ups are part of those paths
-                    if (int rc = launch_match_short(c, reinterpret_cast<const double *>(d_q + 2), d_q, 1, (int32_t)n, min_match,
-                                                    nullptr, (int32_t)want, s->d_hits, s->d_hits_n, 1, nullptr, 0,
-                                                    TVZ_ALGO_AUTO, s->stream))
-                        return rc;
-                }
-            }
-            if (int rc = record(c, s->stream)) return rc;
-        }
-        int32_t h_n = 0;
-        TVZ_HIP(hipMemcpyAsync(&h_n, s->d_hits_n, 4, hipMemcpyDeviceToHost, s->stream));
-        TVZ_HIP(hipStreamSynchronize(s->stream));   // also: uq / mult / h_query were read by now
-        n_found = h_n;
-        n_have = std::min<int64_t>(n_found, want);
-        long_hits.resize((size_t)n_have);
-        if (n_have) {
-            TVZ_HIP(hipMemcpyAsync(long_hits.data(), s->d_hits, (size_t)n_have * 12, hipMemcpyDeviceToHost, s->stream));
-            TVZ_HIP(hipStreamSynchronize(s->stream));
-        }
-        // the exclusion is applied here on these paths
-        if (excl >= 0) {
-            const size_t before = long_hits.size();
-            long_hits.erase(std::remove_if(long_hits.begin(), long_hits.end(),
-                                           [&](const Hit &h) { return h.vid == excl; }), long_hits.end());
-            n_found -= (int64_t)(before - long_hits.size());
-            n_have = (int64_t)long_hits.size();
-        }
-        found = long_hits.data();
+        *n_hits = w;
+        break;
     }
-    Hit *hh = const_cast<Hit *>(found);
-    std::sort(hh, hh + n_have, [](const Hit &a, const Hit &b) {
+    return TVZ_OK;
+}
+
+// tvz_find_duplicates on the rare paths (min_match > 5, or a query longer than a tile): a device hit list, a fix-up
+// pass for kth, explicit copies back, and the exclusion applied here.  *n_found: the hits the device reported, less
+// the excluded ones (`hits` holds at most max(cap, 1) of them).
+int find_device(tvz_corpus *c, Staging *s, const double *h_query, int64_t n, int32_t min_match, int32_t excl,
+                int64_t cap, std::vector<Hit> &hits, int64_t *n_found) {
+    const int64_t want = std::max<int64_t>(cap, 1);
+    if (want > s->d_hit_slots) {
+        if (s->d_hits) (void)hipFree(s->d_hits);
+        s->d_hits = nullptr;
+        s->d_hit_slots = 0;
+        TVZ_HIP(hipMalloc(&s->d_hits, (size_t)want * 12));
+        s->d_hit_slots = want;
+    }
+    std::vector<int64_t> uq;
+    std::vector<int32_t> mult;
+    const bool longq = n > kMaxQueryLen;
+    int64_t *d_q = s->d_query;
+    if (longq) {
+        // sorted distinct keys + multiplicities, searched per row key; the raw query (for the
+        // fix-up walk) travels behind them
+        sorted_distinct(h_query, n, uq, mult);
+        const int64_t m = (int64_t)uq.size();
+        if (m + n + 3 > s->sq_cap) {
+            if (s->d_sq) (void)hipFree(s->d_sq);
+            if (s->d_smult) (void)hipFree(s->d_smult);
+            s->d_sq = nullptr; s->d_smult = nullptr; s->sq_cap = 0;
+            TVZ_HIP(hipMalloc(&s->d_sq, (size_t)(m + n + 3) * 8));
+            TVZ_HIP(hipMalloc(&s->d_smult, (size_t)(m + 1) * 4));
+            s->sq_cap = m + n + 3;
+        }
+        d_q = s->d_sq + m;                                   // {0, n} + raw query
+        const int64_t qoff[2] = {0, n};
+        TVZ_HIP(hipMemcpyAsync(d_q, qoff, 16, hipMemcpyHostToDevice, s->stream));
+        TVZ_HIP(hipMemcpyAsync(d_q + 2, h_query, (size_t)n * 8, hipMemcpyHostToDevice, s->stream));
+        if (m) {
+            TVZ_HIP(hipMemcpyAsync(s->d_sq, uq.data(), (size_t)m * 8, hipMemcpyHostToDevice, s->stream));
+            TVZ_HIP(hipMemcpyAsync(s->d_smult, mult.data(), (size_t)m * 4, hipMemcpyHostToDevice, s->stream));
+        }
+    } else {
+        s->h_query[0] = 0;
+        s->h_query[1] = n;
+        if (n) memcpy(s->h_query + 2, h_query, (size_t)n * 8);
+        TVZ_HIP(hipMemcpyAsync(s->d_query, s->h_query, (size_t)(n + 2) * 8, hipMemcpyHostToDevice, s->stream));
+    }
+    {
+        std::shared_lock<std::shared_mutex> lk(c->mu);
+        const int64_t n_rows = (int64_t)c->h_rows.size();
+        if (int rc = wait_mutations(c, s->stream)) return rc;
+        if (int rc = launch_prep(s->d_hits_n, 1, 1, nullptr, 0, nullptr, 0, s->stream)) return rc;
+        if (n_rows) {
+            if (longq) {
+                hipLaunchKernelGGL(ts_match_longq_kernel, dim3((unsigned)tvz::ceil_div(n_rows, kGroupsPerBlock)),
+                                   dim3(kBlock), 0, s->stream, c->rows.p, n_rows, c->keys.p, s->d_sq,
+                                   s->d_smult, (int32_t)uq.size(), min_match, -1, (int32_t)want, s->d_hits,
+                                   s->d_hits_n, static_cast<const int32_t *>(nullptr), static_cast<const int32_t *>(nullptr));
+                TVZ_HIP(hipGetLastError());
+                if (min_match > 0) {
+                    hipLaunchKernelGGL(ts_kth_fixup_kernel, dim3(1), dim3(kBlock), 0, s->stream, c->rows.p,
+                                       c->keys.p, reinterpret_cast<const double *>(d_q + 2), d_q, min_match,
+                                       (int32_t)want, s->d_hits, s->d_hits_n, 1);
+                    TVZ_HIP(hipGetLastError());
+                }
+            } else {
+                // min_match > 5 (or <= 0): what a batch of one takes - on an indexed handle the lookup with a
+                // count-only pass B + the kth fix-up walk and a sweep of the delta table, else the single-query
+                // sweep; the fix-ups are part of those paths
+                if (int rc = launch_match_short(c, reinterpret_cast<const double *>(d_q + 2), d_q, 1, (int32_t)n, min_match,
+                                                nullptr, (int32_t)want, s->d_hits, s->d_hits_n, 1, nullptr, 0,
+                                                TVZ_ALGO_AUTO, s->stream))
+                    return rc;
+            }
+        }
+        if (int rc = record(c, s->stream)) return rc;
+    }
+    int32_t h_n = 0;
+    TVZ_HIP(hipMemcpyAsync(&h_n, s->d_hits_n, 4, hipMemcpyDeviceToHost, s->stream));
+    TVZ_HIP(hipStreamSynchronize(s->stream));   // also: uq / mult / h_query were read by now
+    *n_found = h_n;
+    hits.resize((size_t)std::min<int64_t>(h_n, want));
+    if (!hits.empty()) {
+        TVZ_HIP(hipMemcpyAsync(hits.data(), s->d_hits, hits.size() * 12, hipMemcpyDeviceToHost, s->stream));
+        TVZ_HIP(hipStreamSynchronize(s->stream));
+    }
+    if (excl >= 0) {
+        const size_t before = hits.size();
+        hits.erase(std::remove_if(hits.begin(), hits.end(), [&](const Hit &h) { return h.vid == excl; }), hits.end());
+        *n_found -= (int64_t)(before - hits.size());
+    }
+    return TVZ_OK;
+}
+
+}  // namespace
+
+static int tvz_find_duplicates_impl(tvz_corpus *c, const double *h_query, int64_t n,
+                                   int32_t min_match, int32_t exclude_id, int64_t cap,
+                                   int32_t *h_out_ids, int32_t *h_out_counts, int32_t *h_out_kth,
+                                   int64_t *n_out) {
+    TVZ_REQUIRE(c != nullptr && n_out != nullptr, "NULL argument");
+    TVZ_REQUIRE(n >= 0 && cap >= 0 && cap <= INT32_MAX, "bad size");
+    TVZ_REQUIRE(n == 0 || h_query, "h_query is NULL");
+    TVZ_REQUIRE(cap == 0 || (h_out_ids && h_out_counts), "NULL outputs");
+    TVZ_REQUIRE(n <= INT32_MAX, "query too long");
+    DeviceGuard dg(c->device);
+    Staging *s = nullptr;
+    if (int rc = staging_get(c, &s)) return rc;
+    struct Put { tvz_corpus *c; Staging *s; ~Put() { staging_put(c, s); } } put{c, s};
+    const int32_t excl = exclude_id >= 0 ? exclude_id : -1;
+    std::vector<Hit> dev_hits;             // only the rare paths use it
+    Hit *hits = nullptr;
+    int64_t n_found = 0;                   // hits the device reported (before the cap)
+    int64_t n_have = 0;                    // hits available in `hits`
+    if (n <= kMaxQueryLen && min_match <= kTop) {
+        if (int rc = find_pinned(c, s, h_query, n, min_match, excl, &n_found)) return rc;
+        hits = reinterpret_cast<Hit *>(s->h_hits);
+        n_have = n_found;
+    } else {
+        if (int rc = find_device(c, s, h_query, n, min_match, excl, cap, dev_hits, &n_found)) return rc;
+        hits = dev_hits.data();
+        n_have = (int64_t)dev_hits.size();
+    }
+    std::sort(hits, hits + n_have, [](const Hit &a, const Hit &b) {
         if (a.vid != b.vid) return a.vid < b.vid;
         if (a.cnt != b.cnt) return a.cnt < b.cnt;
         return a.kth < b.kth;
     });
     const int64_t w = std::min<int64_t>(n_have, cap);
     for (int64_t i = 0; i < w; ++i) {
-        h_out_ids[i] = hh[i].vid;
-        h_out_counts[i] = hh[i].cnt;
-        if (h_out_kth) h_out_kth[i] = hh[i].kth;
+        h_out_ids[i] = hits[i].vid;
+        h_out_counts[i] = hits[i].cnt;
+        if (h_out_kth) h_out_kth[i] = hits[i].kth;
     }
     // truncated: report the true count so the caller can retry with cap >= *n_out
     *n_out = n_found;
@@ -2234,7 +2224,7 @@ static int tvz_topk_impl(const int32_t *d_lists, const int32_t *d_lists_n, int32
     TVZ_REQUIRE((d_lists || cap == 0) && d_topk, "NULL argument");
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
     if (n_lists == 1) return launch_topk_local(d_lists, d_lists_n, 1, Q, cap, k, d_topk, 0, nullptr, st);
-    return launch_topk_lists(d_lists, d_lists_n, n_lists, Q, cap, k, d_topk, 0, nullptr, nullptr, st);
+    return launch_topk_lists(d_lists, d_lists_n, n_lists, Q, cap, k, d_topk, 0, nullptr, st);
 }
 
 static int tvz_topk_shard_impl(const int32_t *d_hits, const int32_t *d_hits_n, int32_t Q,
@@ -2247,7 +2237,14 @@ static int tvz_topk_shard_impl(const int32_t *d_hits, const int32_t *d_hits_n, i
 }
 
 static int tvz_topk_merge_impl(const int32_t *d_gathered, int32_t n_ranks, int32_t Q, int32_t k,
-                               int32_t *d_topk, int32_t *d_totals, void *hip_stream);
+                              int32_t *d_topk, int32_t *d_totals, void *hip_stream) {
+    TVZ_REQUIRE(n_ranks >= 1 && Q >= 0, "bad list shape");
+    TVZ_REQUIRE(k >= 1 && k <= kSortCap / 2, "k=%d out of range [1, %d]", k, kSortCap / 2);
+    if (Q == 0) return TVZ_OK;
+    TVZ_REQUIRE(d_gathered && d_topk, "NULL argument");
+    return launch_topk_lists(d_gathered, nullptr, n_ranks, Q, k + 1, k, d_topk, 2, d_totals,
+                             reinterpret_cast<hipStream_t>(hip_stream));
+}
 
 static int tvz_match_topk_shards_impl(tvz_corpus *const *shards, int32_t n_shards, const double *d_queries,
                                       const int64_t *d_q_offsets, int32_t Q, int32_t max_query_len,
@@ -2267,16 +2264,6 @@ static int tvz_match_topk_shards_impl(tvz_corpus *const *shards, int32_t n_shard
     }
     DeviceGuard dg(shards[0]->device);
     return tvz_topk_merge_impl(d_blocks, n_shards, Q, k, d_topk, d_totals, hip_stream);
-}
-
-static int tvz_topk_merge_impl(const int32_t *d_gathered, int32_t n_ranks, int32_t Q, int32_t k,
-                              int32_t *d_topk, int32_t *d_totals, void *hip_stream) {
-    TVZ_REQUIRE(n_ranks >= 1 && Q >= 0, "bad list shape");
-    TVZ_REQUIRE(k >= 1 && k <= kSortCap / 2, "k=%d out of range [1, %d]", k, kSortCap / 2);
-    if (Q == 0) return TVZ_OK;
-    TVZ_REQUIRE(d_gathered && d_topk, "NULL argument");
-    return launch_topk_lists(d_gathered, nullptr, n_ranks, Q, k + 1, k, d_topk, 2, d_totals, nullptr,
-                             reinterpret_cast<hipStream_t>(hip_stream));
 }
 
 static int tvz_align_impl(tvz_corpus *c, const double *d_query, int32_t n, double eps,
