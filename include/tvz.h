@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define TVZ_VERSION 400 /* 0.4.0: the index answers every min_match >= 1; tvz_match_topk keeps the top-k inside the lookup; tvz_match_topk_shards */
+#define TVZ_VERSION 401 /* 0.4.1: tvz_align takes its output capacity and reports the row count (0.4.0: the index answers every min_match >= 1; tvz_match_topk keeps the top-k inside the lookup; tvz_match_topk_shards) */
 
 typedef enum tvz_status {
     TVZ_OK = 0,
@@ -372,12 +372,17 @@ int tvz_match_sharded(tvz_corpus *c, tvz_comm *comm, const double *d_queries,
  * shift/tolerance-aware comparison, which this reports ALONGSIDE the exact one.  For one query
  * against every corpus row, every (query_i, row_j) difference votes into bins of width eps over
  * [-max_offset, +max_offset] (bin = floor(diff/eps + 0.5)):
- *   d_out : int32[n_rows][5] = (video_id, row_len, best_bin, votes_in_best_bin, votes_in_bin_0)
- * best_bin ties: smaller |bin| first, then the negative one.  A cut-shifted copy shows as
- * votes ~ min(n, row_len) at best_bin = shift/eps; tolerant Jaccard = v / (n + row_len - v).
- * Needs 2*round(max_offset/eps)+1 <= 4096 bins. */
+ *   d_out : int32[out_rows][5] = (video_id, row_len, best_bin, votes_in_best_bin, votes_in_bin_0)
+ * Rows are sets (NaN dropped, -0.0 folded to +0.0); query NaNs are skipped and query duplicates
+ * each vote.  `votes` counts (query value, row key) PAIRS: with cuts closer than eps it can exceed
+ * min(n, row_len).  best_bin ties: smaller |bin| first, then the negative one; no votes at all ->
+ * best_bin 0.  A cut-shifted copy shows as votes ~ min(n, row_len) at best_bin = shift/eps;
+ * tolerant Jaccard = v / (n + row_len - v) with v = min(votes, n, row_len).
+ * *n_rows = the handle's row count, read under its lock; the first min(out_rows, *n_rows) rows are
+ * written, nothing beyond them (rows upserted after the caller sized d_out: call again with room).
+ * Needs 2*round(max_offset/eps)+1 <= 4096 bins (else TVZ_ERR_UNSUPPORTED); eps > 0, max_offset >= 0. */
 int tvz_align(tvz_corpus *c, const double *d_query, int32_t n, double eps, double max_offset,
-              int32_t *d_out, void *hip_stream);
+              int32_t *d_out, int64_t out_rows, int64_t *n_rows, void *hip_stream);
 
 /* ------------------------------------------------------------------------
  * Frame feeder I/O - the host side of what replaces the stderr pipe of

@@ -13,6 +13,14 @@ def _declared():
     return sorted(set(re.findall(r"\b(tvz_[a-z0-9_]+)\s*\(", src)))
 
 
+def _header_version():
+    """TVZ_VERSION as include/tvz.h defines it: the number the library, the binding and every C consumer
+    must agree on (an ABI change bumps it in the header, and these tests follow without an edit)."""
+    m = re.search(r"^#define TVZ_VERSION (\d+)\b", open(os.path.join(ROOT, "include", "tvz.h")).read(), flags=re.M)
+    assert m, "include/tvz.h defines no TVZ_VERSION"
+    return int(m.group(1))
+
+
 def test_header_declares_the_path():
     names = _declared()
     for must in ("tvz_luma_sad_u8", "tvz_scene_select", "tvz_scene_scores_u8", "tvz_corpus_create",
@@ -23,14 +31,14 @@ def test_header_declares_the_path():
         assert must in names
 
 
-def test_library_builds_loads_and_exports_every_symbol():
+def test_library_builds_loads_exports_every_symbol_at_the_header_version():
     from tvidz_amd import _lib, build
     build.build()
     lib = _lib.load()
     for name in _declared():
         assert hasattr(lib, name), f"{name} declared in tvz.h but not exported"
         assert name in _lib.SIGNATURES, f"{name} has no ctypes signature"
-    assert lib.tvz_version() == _lib.VERSION == 400
+    assert lib.tvz_version() == _lib.VERSION == _header_version() > 0
     assert lib.tvz_scene_workspace_bytes(10000, 1080, 1920) > 0
     assert lib.tvz_scene_workspace_bytes(-1, 1080, 1920) == 0
     assert lib.tvz_scene_state_bytes(1080, 1920, 1) >= 2 * 1080 * 1920
@@ -107,12 +115,15 @@ def test_entry_points_fail_gracefully_without_a_gpu():
     assert lib.tvz_match_topk(None, None, None, 1, 1, 1, None, 1, 4, None, None, 0, 0, None) != 0
     assert lib.tvz_match_sharded(None, None, None, None, 1, 1, 1, None, 1, 4, None, None, None, 0, 0, None) != 0
     assert lib.tvz_corpus_reserve(None, 1, 1) != 0
+    n_rows = C.c_int64(-7)
+    assert lib.tvz_align(None, None, 0, 0.1, 1.0, None, 0, C.byref(n_rows), None) != 0
+    assert n_rows.value == -7                                              # a refusal reports no row count
     from tvidz_amd import scene
     with pytest.raises(RuntimeError):
         scene.SceneScorer(32, 32, 4, "cpu")
 
 
-def test_diagnostic_builds_are_quarantined(tmp_path):
+def test_diagnostic_builds_report_the_negated_header_version_and_are_quarantined(tmp_path):
     """A library compiled with one of the TVZ_IX_* diagnostic defines (profiles/variant_build.sh: some return WRONG
     results on purpose) reports a negated version, and the product binding refuses to load it; build.build()
     ignores TVZ_CXXFLAGS unless TVZ_DIAGNOSTIC=1 says the build is meant to be one."""
@@ -132,7 +143,7 @@ def test_diagnostic_builds_are_quarantined(tmp_path):
     env = dict(os.environ, TVZ_LIB=so)
     env.pop("TVZ_ALLOW_DIAGNOSTIC", None)
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
-    assert out.stdout.split() == ["-400", "REFUSED", "True"], (out.stdout, out.stderr)
+    assert out.stdout.split() == [str(-_header_version()), "REFUSED", "True"], (out.stdout, out.stderr)
     # the product build does not take flags from a stray environment variable
     src = open(os.path.join(ROOT, "tvidz_amd", "build.py")).read()
     assert 'os.environ.get("TVZ_DIAGNOSTIC") == "1"' in src and "TVZ_CXXFLAGS ignored" in src

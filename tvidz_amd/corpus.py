@@ -157,15 +157,23 @@ class DeviceCorpus:
 
     # ---- opt-in alignment score (never the verdict; see include/tvz.h tvz_align) ----
     def align(self, timestamps: Sequence[float], eps: float = 0.1, max_offset: float = 60.0):
-        """-> int32 array [n_rows,5]: (video_id, row_len, best_bin, votes, votes_at_zero_shift)."""
-        n_rows = self.stats()[0]
+        """-> int32 array [n_rows,5]: (video_id, row_len, best_bin, votes, votes_at_zero_shift), one
+        entry per row of the table as the kernel saw it.  `votes` counts (query, row) pairs: it can
+        exceed min(len(timestamps), row_len) when cuts are closer than eps."""
         dev = torch.device("cuda", self.device)
         q = torch.as_tensor(np.asarray(timestamps, dtype=np.float64)).to(dev)
-        out = torch.empty((max(n_rows, 1), 5), dtype=torch.int32, device=dev)
-        _lib.check(self.lib.tvz_align(self._h, q.data_ptr() if q.numel() else None, q.numel(),
-                                      float(eps), float(max_offset), out.data_ptr(),
-                                      torch.cuda.current_stream(dev).cuda_stream))
-        return out[:n_rows].cpu().numpy()
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        n_rows = C.c_int64(0)
+        cap = max(self.stats()[0], 1)
+        for _ in range(8):
+            out = torch.empty((cap, 5), dtype=torch.int32, device=dev)
+            _lib.check(self.lib.tvz_align(self._h, q.data_ptr() if q.numel() else None, q.numel(),
+                                          float(eps), float(max_offset), out.data_ptr(), cap,
+                                          C.byref(n_rows), stream))
+            if n_rows.value <= cap:
+                return out[:n_rows.value].cpu().numpy()
+            cap = n_rows.value + n_rows.value // 4 + 64     # rows were upserted since stats(): retry with room
+        raise RuntimeError("tvz_align: the table kept growing faster than the output was resized")
 
     # ---- batched, device resident ----
     def _check_queries(self, d_queries, d_q_offsets):

@@ -2267,23 +2267,28 @@ static int tvz_match_topk_shards_impl(tvz_corpus *const *shards, int32_t n_shard
 }
 
 static int tvz_align_impl(tvz_corpus *c, const double *d_query, int32_t n, double eps,
-                         double max_offset, int32_t *d_out, void *hip_stream) {
-    TVZ_REQUIRE(c != nullptr, "corpus is NULL");
+                         double max_offset, int32_t *d_out, int64_t out_rows, int64_t *n_rows_out,
+                         void *hip_stream) {
+    TVZ_REQUIRE(c != nullptr && n_rows_out != nullptr, "NULL argument");
     TVZ_REQUIRE(n >= 0 && (n == 0 || d_query), "bad query");
+    TVZ_REQUIRE(out_rows >= 0, "out_rows must be >= 0");
     TVZ_REQUIRE(eps > 0.0 && max_offset >= 0.0, "eps must be > 0 and max_offset >= 0");
     const double nb = floor(max_offset / eps + 0.5);
-    if (2 * nb + 1 > kAlignMaxBins)
+    if (!(2 * nb + 1 <= kAlignMaxBins))                 // also refuses NaN (eps = max_offset = inf)
         return tvz::fail(TVZ_ERR_UNSUPPORTED, "max_offset/eps = %.0f needs more than %d bins", nb,
                          kAlignMaxBins);
     DeviceGuard dg(c->device);
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
     std::shared_lock<std::shared_mutex> lk(c->mu);
     const int64_t n_rows = (int64_t)c->h_rows.size();
-    if (n_rows == 0) return TVZ_OK;
+    *n_rows_out = n_rows;
+    // the caller sized d_out before this call; rows upserted since then are counted, not written
+    const int64_t n_write = std::min(n_rows, out_rows);
+    if (n_write == 0) return TVZ_OK;
     TVZ_REQUIRE(d_out != nullptr, "d_out is NULL");
     if (int rc = wait_mutations(c, st)) return rc;
-    const int64_t blocks = std::min<int64_t>(tvz::ceil_div(n_rows, kBlock / 64), 256 * 8);
-    hipLaunchKernelGGL(ts_align_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, c->rows.p, n_rows,
+    const int64_t blocks = std::min<int64_t>(tvz::ceil_div(n_write, kBlock / 64), 256 * 8);
+    hipLaunchKernelGGL(ts_align_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, c->rows.p, n_write,
                        c->keys.p, d_query, n, eps, (int32_t)nb, d_out);
     TVZ_HIP(hipGetLastError());
     return record(c, st);
@@ -2421,6 +2426,7 @@ TVZ_EXPORT int tvz_topk_merge(const int32_t *d_gathered, int32_t n_ranks, int32_
 }
 
 TVZ_EXPORT int tvz_align(tvz_corpus *c, const double *d_query, int32_t n, double eps,
-                         double max_offset, int32_t *d_out, void *hip_stream) {
-    TVZ_GUARDED(tvz_align_impl(c, d_query, n, eps, max_offset, d_out, hip_stream));
+                         double max_offset, int32_t *d_out, int64_t out_rows, int64_t *n_rows,
+                         void *hip_stream) {
+    TVZ_GUARDED(tvz_align_impl(c, d_query, n, eps, max_offset, d_out, out_rows, n_rows, hip_stream));
 }

@@ -317,7 +317,9 @@ class Inspector:
                 scene_timestamps, eps=self.near_eps, max_offset=self.near_max_offset):
             if vid == video_id or row_len == 0:
                 continue
-            jacc = votes / float(len(scene_timestamps) + row_len - votes)
+            # votes counts (query, row) pairs: cuts closer than eps can give more than either list holds
+            v = min(int(votes), len(scene_timestamps), int(row_len))
+            jacc = v / float(len(scene_timestamps) + row_len - v)
             if jacc >= self.near_jaccard:
                 v = self.store.get_video_by_id(int(vid))
                 out.append({"filename": v.filename if v else None, "video_id": int(vid),

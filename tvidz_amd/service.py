@@ -218,6 +218,12 @@ class ShardedCorpus:
         for s in self.shards:
             s.close()
 
+    def align(self, timestamps, eps: float = 0.1, max_offset: float = 60.0):
+        """DeviceCorpus.align over every shard: each row lives in exactly one shard, so the per-shard
+        results together are the table's (in shard order, not the single handle's row order)."""
+        return np.concatenate([s.align(timestamps, eps=eps, max_offset=max_offset) for s in self.shards]
+                              + [np.zeros((0, 5), dtype=np.int32)])
+
     # ---- matches ----
     def _exact(self, q, min_match, exclude_id, with_kth):
         out = []
