@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define TVZ_VERSION 401 /* 0.4.1: tvz_align takes its output capacity and reports the row count (0.4.0: the index answers every min_match >= 1; tvz_match_topk keeps the top-k inside the lookup; tvz_match_topk_shards) */
+#define TVZ_VERSION 402 /* 0.4.2: tvz_find_duplicates_tol / tvz_match_tol, the opt-in tolerant match (0.4.1: tvz_align takes its output capacity and reports the row count (0.4.0: the index answers every min_match >= 1; tvz_match_topk keeps the top-k inside the lookup; tvz_match_topk_shards)) */
 
 typedef enum tvz_status {
     TVZ_OK = 0,
@@ -383,6 +383,54 @@ int tvz_match_sharded(tvz_corpus *c, tvz_comm *comm, const double *d_queries,
  * Needs 2*round(max_offset/eps)+1 <= 4096 bins (else TVZ_ERR_UNSUPPORTED); eps > 0, max_offset >= 0. */
 int tvz_align(tvz_corpus *c, const double *d_query, int32_t n, double eps, double max_offset,
               int32_t *d_out, int64_t out_rows, int64_t *n_rows, void *hip_stream);
+
+/* ------------------------------------------------------------------------
+ * Opt-in TOLERANT duplicate match.  NOT the reference's verdict: db.py:79,85-91 match exact float64
+ * values, and that stays the default everywhere (tolerance 0).  README.md:291 promises "0.1 second
+ * precision"; a corpus that mixes containers or frame rates needs it: the same 30 fps video muxed with
+ * time base 1/15360 and 1/1000 prints a different %.6g pts_time for two frames in three (<= 0.34 ms
+ * apart), a 30 -> 25 fps conversion moves a cut by up to 33.3 ms.
+ *
+ * For query q (a multiset, in order) and corpus row r (a set of canonical keys: NaN dropped, -0.0
+ * folded to +0.0):
+ *   match(i, r) <=> q[i] is not NaN and exists key in r: key == q[i] or fabs(q[i] - key) <= tol
+ *   count       =   #{ i : match(i, r) }   (query multiplicity counts; a row key may serve several q[i])
+ *   kth         =   index i of the min_match-th matching query element (TVZ_KTH_NEVER if
+ *                   count < min_match, -1 if min_match <= 0)           (as tvz_match)
+ *   hit        <=>  count >= min_match and video_id != exclude_id
+ * q[i] - key is ONE IEEE double subtraction rounded to nearest (no FMA, no rewrite to q >= key - tol,
+ * no fast-math; f64 subnormals are not flushed), so a numpy restatement is bit-exact; the == term keeps
+ * +-inf matching itself.  tol must be finite and >= 0: NaN, inf or a negative value return
+ * TVZ_ERR_INVALID and write nothing.  tol = 0 IS the exact verdict (for finite doubles fl(a - b) == 0
+ * exactly when a == b): ids, counts and kth then equal tvz_find_duplicates / tvz_match bit for bit.
+ * At large tolerances unrelated long videos match by chance: at 0.1 s a 200-cut query meets about two
+ * keys of a random 200-cut row of a 10-minute-to-2-hour corpus.  Pass ~1 ms for remuxes, half a frame
+ * for frame-rate conversions.
+ * Cost: one sweep of the row table and key arena per query (no index), each key searched in the
+ * numerically sorted query (in LDS up to 8,192 timestamps, in device memory beyond).
+ * ------------------------------------------------------------------------ */
+
+/* host in / host out: the tolerant drop-in for db.find_duplicates (+ kth for the streaming loop).
+ * Output rules of tvz_find_duplicates: results sorted by (video_id, count, kth), *n_out = the number of
+ * hits (the true count when it exceeds cap; only cap are written), h_out_kth may be NULL, any query
+ * length.  One launch (two for min_match > 5) + one stream synchronisation, the hits written into
+ * pinned host memory of the handle; no device allocation for queries of up to 4,095 timestamps. */
+int tvz_find_duplicates_tol(tvz_corpus *c, const double *h_query, int64_t n, double tol,
+                            int32_t min_match, int32_t exclude_id, int64_t cap, int32_t *h_out_ids,
+                            int32_t *h_out_counts, int32_t *h_out_kth, int64_t *n_out);
+/* Scratch of tvz_match_tol: per query a count, and the sorted copy of every query (12 B per
+ * timestamp).  total_query_keys = the length of d_queries (0: Q x max_query_len). */
+size_t tvz_match_tol_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys);
+/* Batched, device-resident; hit lists in tvz_match's layout (d_hits int32[Q][cap][3] of (video_id,
+ * count, kth) in unspecified order, d_hits_n int32[Q] = hits found, may exceed cap), so tvz_topk /
+ * tvz_topk_shard apply.  d_hits_n = INT32_MIN for a query longer than max_query_len (as tvz_match),
+ * and for one whose sorted copy does not fit the workspace (size it with the batch's key count).
+ * A workspace without room for the per-query counts returns TVZ_ERR_WORKSPACE and says how many
+ * bytes are missing.  Enqueues only (no host synchronisation, no allocation). */
+int tvz_match_tol(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
+                  int32_t max_query_len, double tol, int32_t min_match, const int32_t *d_exclude_ids,
+                  int32_t cap, int32_t *d_hits, int32_t *d_hits_n, void *d_workspace,
+                  size_t workspace_bytes, void *hip_stream);
 
 /* ------------------------------------------------------------------------
  * Frame feeder I/O - the host side of what replaces the stderr pipe of

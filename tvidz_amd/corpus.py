@@ -49,6 +49,11 @@ def workspace_bytes(Q: int, max_query_len: int, cap: int = 0, k: int = 0, n_rank
                                                      int(n_ranks)))
 
 
+def tol_workspace_bytes(Q: int, max_query_len: int, total_query_keys: int = 0) -> int:
+    """tvz_match_tol_workspace_bytes: scratch of the tolerant batched match (the sorted copy of every query)."""
+    return int(_lib.load().tvz_match_tol_workspace_bytes(int(Q), int(max_query_len), int(total_query_keys)))
+
+
 class DeviceCorpus:
     """tvz_corpus handle: rows of (video_id, sorted-unique canonical float64 keys) in HBM."""
 
@@ -137,16 +142,26 @@ class DeviceCorpus:
             self._tls.buf = b
         return b
 
+    # this handle answers tolerant asks (inspector.Inspector(match_tolerance > 0) checks for it)
+    supports_tolerance = True
+
     def find_duplicates(self, new_timestamps: Sequence[float], min_match: int = 5,
-                        exclude_id: int = -1, with_kth: bool = False):
+                        exclude_id: int = -1, with_kth: bool = False, tolerance: float = 0.0):
         """One kernel launch + one stream synchronisation inside the library (for queries of up to
-        4095 timestamps with min_match <= 5); the output arrays are per-thread and reused."""
+        4095 timestamps with min_match <= 5); the output arrays are per-thread and reused.
+        `tolerance` > 0: the opt-in tolerant match (tvz_find_duplicates_tol, include/tvz.h), NOT the
+        reference's exact verdict; exactly 0 makes the exact call."""
         q = np.ascontiguousarray(np.asarray(new_timestamps, dtype=np.float64))
         cap = max(self._row_bound, 1)
+        tol = float(tolerance)
         while True:
             ids, cnt, kth, n, p_ids, p_cnt, p_kth, p_n = self._out_buffers(cap)
-            _lib.check(self.lib.tvz_find_duplicates(self._h, _ptr(q), q.size, int(min_match),
-                                                    int(exclude_id), ids.size, p_ids, p_cnt, p_kth, p_n))
+            if tol == 0.0:
+                _lib.check(self.lib.tvz_find_duplicates(self._h, _ptr(q), q.size, int(min_match),
+                                                        int(exclude_id), ids.size, p_ids, p_cnt, p_kth, p_n))
+            else:
+                _lib.check(self.lib.tvz_find_duplicates_tol(self._h, _ptr(q), q.size, tol, int(min_match),
+                                                            int(exclude_id), ids.size, p_ids, p_cnt, p_kth, p_n))
             if n.value <= ids.size:
                 break
             cap = int(n.value)  # rows were added concurrently: retry with room for all
@@ -213,6 +228,25 @@ class DeviceCorpus:
             int(min_match), d_exclude_ids.data_ptr() if d_exclude_ids is not None else None,
             int(cap), out_hits.data_ptr(), out_n.data_ptr(), ws.data_ptr(), ws.numel(), int(algo),
             s.cuda_stream))
+        return out_hits, out_n
+
+    def match_tol(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, tol: float,
+                  min_match: int, cap: int, d_exclude_ids: Optional[torch.Tensor] = None,
+                  out_hits: Optional[torch.Tensor] = None, out_n: Optional[torch.Tensor] = None,
+                  stream: Optional[torch.cuda.Stream] = None, workspace: Optional[torch.Tensor] = None):
+        """The tolerant form of `match` (tvz_match_tol): enqueue Q queries; returns (hits int32[Q,cap,3],
+        hits_n int32[Q]) device tensors in match's layout (topk applies)."""
+        dev, Q = self._check_queries(d_queries, d_q_offsets)
+        if out_hits is None:
+            out_hits = torch.empty((Q, cap, 3), dtype=torch.int32, device=dev)
+        if out_n is None:
+            out_n = torch.empty(Q, dtype=torch.int32, device=dev)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        ws = self._workspace(workspace, tol_workspace_bytes(Q, max_query_len, d_queries.numel()), dev, s)
+        _lib.check(self.lib.tvz_match_tol(
+            self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(tol),
+            int(min_match), d_exclude_ids.data_ptr() if d_exclude_ids is not None else None,
+            int(cap), out_hits.data_ptr(), out_n.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
         return out_hits, out_n
 
     def match_topk(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int,

@@ -18,6 +18,7 @@
 // Kernels: tvz_match_kernels.h.  No process-global mutable state: the sweep algorithm is a
 // per-call argument and scratch is the caller's workspace.
 #include <algorithm>
+#include <cfloat>
 #include <cstdlib>
 #include <ctime>
 #include <atomic>
@@ -31,6 +32,7 @@
 #include "tvz_match_kernels.h"
 #include "tvz_index_kernels.h"
 #include "tvz_index_wave_kernels.h"
+#include "tvz_tol_kernels.h"
 
 namespace {
 
@@ -61,6 +63,13 @@ struct Staging {
     int64_t *d_sq = nullptr;         // long queries: sorted distinct keys + multiplicities
     int32_t *d_smult = nullptr;
     int64_t sq_cap = 0;
+    // tvz_find_duplicates_tol: the sorted query (values, then positions) of up to kMaxQueryLen timestamps,
+    // pinned + its device copy; longer queries use the growable d_tol_big
+    unsigned char *h_tol = nullptr;
+    unsigned char *d_tol = nullptr;
+    unsigned char *d_tol_big = nullptr;
+    size_t tol_big_bytes = 0;
+    std::vector<std::pair<double, int32_t>> tol_sort;   // host sort scratch (keeps its capacity)
     std::atomic<int> busy{0};        // a sweep of this staging is in flight (drain() waits for it)
     int gen = 0;                     // index generation that sweep reads
 };
@@ -70,6 +79,8 @@ constexpr int kQ1MaxBlocks = 2048;
 constexpr int kStageGroups = kIxBlock / kGroup;   // row groups of the widest sweep block (the fused lookup's): every
                                                   // block's hit region rounds up to whole row groups
 constexpr int64_t kQueryStageKeys = kMaxQueryLen + 1;
+// a query's sorted values + positions (12 B per timestamp), then for min_match > 5 the raw query (8 B per timestamp)
+constexpr size_t kTolStageBytes = (size_t)kQueryStageKeys * 20 + 64;
 constexpr int kRingSlots = 16;                    // pinned upsert payload ring
 constexpr int64_t kRingSlotKeys = 8192;           // 64 KiB each
 
@@ -736,6 +747,9 @@ void staging_free(Staging *s) {
     if (s->d_hits_n) (void)hipFree(s->d_hits_n);
     if (s->d_sq) (void)hipFree(s->d_sq);
     if (s->d_smult) (void)hipFree(s->d_smult);
+    if (s->h_tol) (void)hipHostFree(s->h_tol);
+    if (s->d_tol) (void)hipFree(s->d_tol);
+    if (s->d_tol_big) (void)hipFree(s->d_tol_big);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
 }
@@ -776,6 +790,8 @@ int staging_new(tvz_corpus *c, Staging **out) {
     TVZ_HIP(hipHostMalloc(&s->h_query, (size_t)(kQueryStageKeys + 2) * 8, hipHostMallocDefault));
     TVZ_HIP(hipMalloc(&s->d_query, (size_t)(kQueryStageKeys + 2) * 8));
     TVZ_HIP(hipMalloc(&s->d_hits_n, sizeof(int32_t)));
+    TVZ_HIP(hipHostMalloc(&s->h_tol, kTolStageBytes, hipHostMallocDefault));
+    TVZ_HIP(hipMalloc(&s->d_tol, kTolStageBytes));
     if (int rc = staging_size(s, c->stage_rows)) return rc;
     g.s = nullptr;
     {
@@ -2294,6 +2310,222 @@ static int tvz_align_impl(tvz_corpus *c, const double *d_query, int32_t n, doubl
     return record(c, st);
 }
 
+// ---- tolerant match (tvz_tol_kernels.h) ---------------------------------------------------------------------
+namespace {
+
+int check_tol(double tol) {
+    if (!(tol >= 0.0 && tol <= DBL_MAX))                // refuses NaN, +-inf and negative values
+        return tvz::fail(TVZ_ERR_INVALID, "tol must be finite and >= 0 (got %g)", tol);
+    return TVZ_OK;
+}
+
+// The sweep, one launch: the sorted query's values sv[..) and positions sp[..) (per query, see ts_match_tol_kernel),
+// in LDS when lds_keys > 0 (every query of the launch has at most lds_keys values).
+template <bool HOSTOUT>
+int launch_tol(tvz_corpus *c, int64_t n_rows, const double *sv, const int32_t *sp, const int64_t *q_offsets,
+               const int32_t *qm, int32_t m_one, int32_t lds_keys, int32_t Q, double tol, int32_t min_match,
+               const int32_t *d_exclude_ids, int32_t exclude_one, int32_t cap, int32_t *d_hits, int32_t *d_hits_n,
+               int blocks_x, HostOut ho, hipStream_t st) {
+    const size_t lds = lds_keys > 0 ? tol_lds_bytes(lds_keys) : 0;
+    TVZ_REQUIRE(lds + kQ1Stage * 12 + 64 <= (size_t)kLdsPerWorkgroup, "tolerant sweep: %zu B of LDS exceed a gfx950 workgroup's",
+                lds);
+    const dim3 grid((unsigned)blocks_x, (unsigned)Q);
+#define TVZ_TOL(MODE, LDSQ)                                                                                         \
+    hipLaunchKernelGGL((ts_match_tol_kernel<MODE, HOSTOUT, LDSQ>), grid, dim3(kTolBlock), lds, st, c->rows.p, n_rows, \
+                       c->keys.p, sv, sp, q_offsets, qm, m_one, lds_keys, tol, min_match, d_exclude_ids, exclude_one,  \
+                       cap, d_hits, d_hits_n, ho)
+    const int mode = (min_match <= 0 || min_match > kTop) ? kTolModeCount : (min_match <= 2 ? kTolModeM2 : kTolModeTop5);
+    if (lds_keys > 0) {
+        if (mode == kTolModeM2) TVZ_TOL(kTolModeM2, true);
+        else if (mode == kTolModeTop5) TVZ_TOL(kTolModeTop5, true);
+        else TVZ_TOL(kTolModeCount, true);
+    } else {
+        if (mode == kTolModeM2) TVZ_TOL(kTolModeM2, false);
+        else if (mode == kTolModeTop5) TVZ_TOL(kTolModeTop5, false);
+        else TVZ_TOL(kTolModeCount, false);
+    }
+#undef TVZ_TOL
+    TVZ_HIP(hipGetLastError());
+    return TVZ_OK;
+}
+
+// workspace of tvz_match_tol: per query its count of non-NaN values, then room for `keys` sorted values + positions
+struct TolWs {
+    int32_t *qm = nullptr;
+    double *sv = nullptr;
+    int32_t *sp = nullptr;
+    int64_t room = 0;
+    size_t total = 0;
+};
+
+TolWs tol_ws_layout(void *base, int32_t Q, int64_t keys) {
+    TolWs w;
+    uintptr_t p = (reinterpret_cast<uintptr_t>(base) + 255) & ~(uintptr_t)255;
+    const uintptr_t p0 = p;
+    w.qm = reinterpret_cast<int32_t *>(p);
+    p += al256((size_t)Q * 4);
+    w.sv = reinterpret_cast<double *>(p);
+    p += al256((size_t)keys * 8);
+    w.sp = reinterpret_cast<int32_t *>(p);
+    p += al256((size_t)keys * 4);
+    w.room = keys;
+    w.total = (size_t)(p - p0) + 256;
+    return w;
+}
+
+// the most sorted values a workspace of `bytes` holds next to Q counts (-1: not even the counts)
+size_t tol_ws_fixed(int32_t Q) { return al256((size_t)Q * 4) + 256 + 2 * 255; }
+int64_t tol_ws_room(int32_t Q, size_t bytes) {
+    return bytes < tol_ws_fixed(Q) ? -1 : (int64_t)((bytes - tol_ws_fixed(Q)) / 12);
+}
+
+}  // namespace
+
+static int tvz_find_duplicates_tol_impl(tvz_corpus *c, const double *h_query, int64_t n, double tol,
+                                        int32_t min_match, int32_t exclude_id, int64_t cap, int32_t *h_out_ids,
+                                        int32_t *h_out_counts, int32_t *h_out_kth, int64_t *n_out) {
+    TVZ_REQUIRE(c != nullptr && n_out != nullptr, "NULL argument");
+    TVZ_REQUIRE(n >= 0 && cap >= 0 && cap <= INT32_MAX, "bad size");
+    TVZ_REQUIRE(n == 0 || h_query, "h_query is NULL");
+    TVZ_REQUIRE(cap == 0 || (h_out_ids && h_out_counts), "NULL outputs");
+    TVZ_REQUIRE(n <= INT32_MAX, "query too long");
+    if (int rc = check_tol(tol)) return rc;
+    DeviceGuard dg(c->device);
+    Staging *s = nullptr;
+    if (int rc = staging_get(c, &s)) return rc;
+    struct Put { tvz_corpus *c; Staging *s; ~Put() { staging_put(c, s); } } put{c, s};
+    const int32_t excl = exclude_id >= 0 ? exclude_id : -1;
+    // the query, sorted by value with its original positions, NaNs dropped (-0.0 folded to +0.0)
+    std::vector<std::pair<double, int32_t>> &srt = s->tol_sort;
+    srt.clear();
+    srt.reserve((size_t)n);
+    for (int64_t i = 0; i < n; ++i)
+        if (h_query[i] == h_query[i]) srt.emplace_back(h_query[i] == 0.0 ? 0.0 : h_query[i], (int32_t)i);
+    std::sort(srt.begin(), srt.end());
+    const int64_t m = (int64_t)srt.size();
+    const int64_t m_even = (m + 1) & ~(int64_t)1;
+    const bool fixup = min_match > kTop;                 // kth by the fix-up pass, which walks the raw query
+    const size_t sorted_bytes = (size_t)m_even * 8 + (size_t)m * 4;
+    const size_t raw_at = (sorted_bytes + 15) & ~(size_t)15;
+    const size_t bytes = fixup ? raw_at + (size_t)n * 8 : sorted_bytes;
+    std::vector<unsigned char> big;                      // queries of more than kMaxQueryLen timestamps only
+    unsigned char *h = s->h_tol, *d = s->d_tol;
+    if (n > kMaxQueryLen || bytes > kTolStageBytes) {
+        if (bytes > s->tol_big_bytes) {
+            if (s->d_tol_big) (void)hipFree(s->d_tol_big);
+            s->d_tol_big = nullptr;
+            s->tol_big_bytes = 0;
+            TVZ_HIP(hipMalloc(&s->d_tol_big, bytes));
+            s->tol_big_bytes = bytes;
+        }
+        big.resize(bytes);
+        h = big.data();
+        d = s->d_tol_big;
+    }
+    double *hv = reinterpret_cast<double *>(h);
+    int32_t *hp = reinterpret_cast<int32_t *>(h + (size_t)m_even * 8);
+    for (int64_t t = 0; t < m; ++t) {
+        hv[t] = srt[t].first;
+        hp[t] = srt[t].second;
+    }
+    if (fixup && n) memcpy(h + raw_at, h_query, (size_t)n * 8);
+    if (bytes) TVZ_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s->stream));
+    const double *dv = reinterpret_cast<const double *>(d);
+    const int32_t *dp = reinterpret_cast<const int32_t *>(d + (size_t)m_even * 8);
+    int blocks = 0, region = 0;
+    {
+        struct Busy { Staging *s; ~Busy() { s->busy.store(0, std::memory_order_release); } } busy{s};
+        {
+            std::shared_lock<std::shared_mutex> lk(c->mu);
+            const int64_t n_rows = (int64_t)c->h_rows.size();
+            if (n_rows) {
+                if (n_rows > c->stage_rows || n_rows + (int64_t)kQ1MaxBlocks * kStageGroups > s->hit_slots) {
+                    // the corpus outgrew its reservation (see tvz_corpus_reserve): grow this staging
+                    if (int rc = staging_size(s, std::max<int64_t>(2 * n_rows, c->stage_rows))) return rc;
+                }
+                if (int rc = wait_mutations(c, s->stream)) return rc;
+                s->busy.store(1, std::memory_order_release);
+                blocks = q1_blocks(n_rows, 1);
+                region = (int)(tvz::ceil_div(n_rows, (int64_t)blocks * kTolGroups) * kTolGroups);
+                const HostOut ho{s->dh_hits, s->dh_counts, region};
+                const int32_t lds_keys = m <= kTolLdsKeys ? (int32_t)std::max<int64_t>(m, 1) : 0;
+                if (int rc = launch_tol<true>(c, n_rows, dv, dp, nullptr, nullptr, (int32_t)m, lds_keys, 1, tol,
+                                              min_match, nullptr, excl, 0, nullptr, nullptr, blocks, ho, s->stream))
+                    return rc;
+                if (fixup) {
+                    hipLaunchKernelGGL(ts_tol_kth_fixup_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, s->stream,
+                                       c->rows.p, c->keys.p, reinterpret_cast<const double *>(d + raw_at),
+                                       static_cast<const int64_t *>(nullptr), (int32_t)n, tol, min_match, s->dh_hits,
+                                       s->dh_counts, region);
+                    TVZ_HIP(hipGetLastError());
+                }
+            }
+        }
+        const hipError_t e = hipStreamSynchronize(s->stream);
+        if (e != hipSuccess) return tvz::fail(TVZ_ERR_HIP, "tolerant single-query match failed: %s", hipGetErrorString(e));
+    }
+    // compact the per-block regions in place
+    Hit *hh = reinterpret_cast<Hit *>(s->h_hits);
+    int64_t w = 0;
+    for (int b = 0; b < blocks; ++b) {
+        const int32_t nb = s->h_counts[b];
+        if (nb < 0) return tvz::fail(TVZ_ERR_INVALID, "internal: tolerant query table overflow");
+        const Hit *src = hh + (int64_t)b * region;
+        if (src != hh + w) memmove(hh + w, src, (size_t)nb * sizeof(Hit));
+        w += nb;
+    }
+    std::sort(hh, hh + w, [](const Hit &a, const Hit &b) {
+        if (a.vid != b.vid) return a.vid < b.vid;
+        if (a.cnt != b.cnt) return a.cnt < b.cnt;
+        return a.kth < b.kth;
+    });
+    const int64_t nw = std::min<int64_t>(w, cap);
+    for (int64_t i = 0; i < nw; ++i) {
+        h_out_ids[i] = hh[i].vid;
+        h_out_counts[i] = hh[i].cnt;
+        if (h_out_kth) h_out_kth[i] = hh[i].kth;
+    }
+    *n_out = w;                                          // the true count, also when it exceeds cap
+    return TVZ_OK;
+}
+
+static int tvz_match_tol_impl(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
+                              int32_t max_query_len, double tol, int32_t min_match, const int32_t *d_exclude_ids,
+                              int32_t cap, int32_t *d_hits, int32_t *d_hits_n, void *d_workspace,
+                              size_t workspace_bytes, void *hip_stream) {
+    if (int rc = check_batch_args(c, d_queries, d_q_offsets, Q, max_query_len, cap)) return rc;
+    if (int rc = check_tol(tol)) return rc;
+    if (Q == 0) return TVZ_OK;
+    TVZ_REQUIRE(d_hits_n && (cap == 0 || d_hits), "NULL output");
+    const int64_t room = tol_ws_room(Q, d_workspace ? workspace_bytes : 0);
+    if (room < 0) {
+        const size_t have = d_workspace ? workspace_bytes : 0;
+        return tvz::fail(TVZ_ERR_WORKSPACE, "tolerant match: workspace of %zu bytes, %zu bytes missing (size it with "
+                                            "tvz_match_tol_workspace_bytes)", have, tol_ws_fixed(Q) - have);
+    }
+    const TolWs w = tol_ws_layout(d_workspace, Q, room);
+    DeviceGuard dg(c->device);
+    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+    // per query: sorted values + positions, counts, hit counters = 0
+    hipLaunchKernelGGL(ts_tol_sort_kernel, dim3((unsigned)tvz::ceil_div(std::max(max_query_len, 1), kTolSortBlock), (unsigned)Q),
+                       dim3(kTolSortBlock), 0, st, d_queries, d_q_offsets, max_query_len, w.room, w.sv, w.sp, w.qm,
+                       d_hits_n);
+    TVZ_HIP(hipGetLastError());
+    std::shared_lock<std::shared_mutex> lk(c->mu);
+    const int64_t n_rows = (int64_t)c->h_rows.size();
+    if (int rc = wait_mutations(c, st)) return rc;
+    const int32_t lds_keys = max_query_len <= kTolLdsKeys ? std::max(max_query_len, 1) : 0;
+    if (int rc = launch_tol<false>(c, n_rows, w.sv, w.sp, d_q_offsets, w.qm, 0, lds_keys, Q, tol, min_match,
+                                   d_exclude_ids, -1, cap, d_hits, d_hits_n, q1_blocks(n_rows, Q), HostOut{}, st))
+        return rc;
+    if (min_match > kTop && n_rows) {
+        hipLaunchKernelGGL(ts_tol_kth_fixup_kernel, dim3((unsigned)Q), dim3(kBlock), 0, st, c->rows.p, c->keys.p,
+                           d_queries, d_q_offsets, 0, tol, min_match, d_hits, d_hits_n, cap);
+        TVZ_HIP(hipGetLastError());
+    }
+    return record(c, st);
+}
+
 #ifdef TVZ_IX_STAMP
 // diagnostic build only: read (and clear) the per-phase cycle totals of ts_match_index_kernel
 TVZ_EXPORT int tvz_debug_ix_stamps(unsigned long long *out16) {
@@ -2429,4 +2661,25 @@ TVZ_EXPORT int tvz_align(tvz_corpus *c, const double *d_query, int32_t n, double
                          double max_offset, int32_t *d_out, int64_t out_rows, int64_t *n_rows,
                          void *hip_stream) {
     TVZ_GUARDED(tvz_align_impl(c, d_query, n, eps, max_offset, d_out, out_rows, n_rows, hip_stream));
+}
+
+TVZ_EXPORT int tvz_find_duplicates_tol(tvz_corpus *c, const double *h_query, int64_t n, double tol, int32_t min_match,
+                                       int32_t exclude_id, int64_t cap, int32_t *h_out_ids, int32_t *h_out_counts,
+                                       int32_t *h_out_kth, int64_t *n_out) {
+    TVZ_GUARDED(tvz_find_duplicates_tol_impl(c, h_query, n, tol, min_match, exclude_id, cap, h_out_ids, h_out_counts,
+                                             h_out_kth, n_out));
+}
+
+TVZ_EXPORT size_t tvz_match_tol_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys) {
+    if (Q < 0 || max_query_len < 0 || total_query_keys < 0) return 0;
+    const int64_t keys = total_query_keys > 0 ? total_query_keys : (int64_t)Q * max_query_len;
+    return tol_ws_fixed(Q) + (size_t)keys * 12;          // tol_ws_room() of this many bytes is `keys`
+}
+
+TVZ_EXPORT int tvz_match_tol(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
+                             int32_t max_query_len, double tol, int32_t min_match, const int32_t *d_exclude_ids,
+                             int32_t cap, int32_t *d_hits, int32_t *d_hits_n, void *d_workspace, size_t workspace_bytes,
+                             void *hip_stream) {
+    TVZ_GUARDED(tvz_match_tol_impl(c, d_queries, d_q_offsets, Q, max_query_len, tol, min_match, d_exclude_ids, cap,
+                                   d_hits, d_hits_n, d_workspace, workspace_bytes, hip_stream));
 }

@@ -1,0 +1,439 @@
+// tvz_tol_kernels.h — opt-in tolerant duplicate match (tvz_find_duplicates_tol / tvz_match_tol), gfx950 wave64.
+// Included by tvz_match.hip only, after tvz_match_kernels.h (Row, canon_key, dpp16, HostOut, the Q1 staging).
+//
+// Contract (include/tvz.h): query element q[i] matches row r iff q[i] is not NaN and some key of r has
+//   key == q[i]  or  fabs(q[i] - key) <= tol       (ONE IEEE double subtraction, rounded to nearest)
+// count = matching elements (query multiplicity counts), kth = index of the min_match-th of them.
+//
+// Why a sorted search is exact: for a fixed key, fl(q - key) never decreases as q grows, so the query values
+// that match one key form ONE contiguous run [lo, hi) of the numerically sorted query, and lo, hi never
+// decrease as the key grows.  A row's count is the size of the union of its keys' runs.  The arena keeps a
+// row's keys sorted by their int64 bit pattern: the p negative keys first in DECREASING numeric order, then
+// +0.0 and the positive keys in increasing order.  Walking the arena order, key j's new elements are
+//   negative key:  [lo_j, min(hi_j, lo_{j-1}))      (its numerically larger neighbour j-1 was seen first)
+//   positive key:  [max(lo_j, hi_{j-1}), hi_j)      (the first positive key takes hi of arena key 0, the
+//                                                    numerically largest negative one, as its hi_{j-1})
+// so every union element is visited exactly once: the count is the sum of the new runs and the kth comes
+// from the smallest original positions kept in registers per lane (min_match 1..5) or a fix-up pass.
+//
+// ts_tol_sort_kernel      batch query preparation: per query the non-NaN values sorted (rank sort over LDS
+//                         tiles) with their original positions, into the caller's workspace.
+// ts_match_tol_kernel     one sweep of the row table + key arena per query: a 16-lane group per row,
+//                         unconditional 16-byte key loads, the next row entry fetched one row ahead; per key
+//                         two searches of the sorted query (LDS table, or device memory for a long query).
+// ts_tol_kth_fixup_kernel kth for min_match > 5: per hit, the query walked in its original order.
+#pragma once
+
+namespace {
+
+constexpr int kTolBlock = 256;
+constexpr int kTolGroups = kTolBlock / kGroup;        // rows in flight per block
+constexpr int kTolLd = 4;                              // 16-byte key loads per lane and step
+constexpr int kTolStepKeys = kTolLd * 2 * kGroup;      // 128 keys of a row per step
+// Sorted queries of up to this many values live in LDS (8 B value + 4 B position each: 96 KiB at the limit);
+// a longer one is searched where the preparation left it, in device memory.  Same results either way.
+constexpr int kTolLdsKeys = 8192;
+constexpr int kTolModeM2 = 0;                          // min_match 1..2: two smallest positions per lane
+constexpr int kTolModeTop5 = 1;                        // min_match 3..5: five smallest positions per lane
+constexpr int kTolModeCount = 2;                       // min_match <= 0 (kth = -1) or > 5 (fix-up pass)
+constexpr int kTolSortBlock = 256;
+constexpr int kTolSortTile = 2048;                     // query values per LDS tile of the rank sort
+
+inline size_t tol_lds_bytes(int64_t keys) {
+    const int64_t k = (keys + 1) & ~(int64_t)1;        // positions start 16-byte aligned
+    return (size_t)k * 12;
+}
+
+// the contract's predicate, verbatim: no rewrite to q >= key - tol (that rounds differently)
+__device__ __forceinline__ bool tol_match(double q, double k, double tol) {
+    return q == k || fabs(q - k) <= tol;
+}
+
+// lo = #{t : s[t] < k and s[t] does not match k}: a prefix of the sorted query
+__device__ __forceinline__ int tol_lo(const double *s, int m, double k, double tol) {
+    int lo = 0, len = m;
+    while (len > 0) {
+        const int half = len >> 1;
+        const double v = s[lo + half];
+        if (v < k && !(fabs(v - k) <= tol)) {
+            lo += half + 1;
+            len -= half + 1;
+        } else {
+            len = half;
+        }
+    }
+    return lo;
+}
+
+// hi = first t >= from with s[t] > k and s[t] not matching k (everything in [from, hi) matches).  Runs are
+// short at the tolerances this is for: two linear probes, then a binary search of the rest.
+__device__ __forceinline__ int tol_hi(const double *s, int m, int from, double k, double tol) {
+    int t = from;
+    for (int probe = 0; probe < 2; ++probe) {
+        if (t >= m) return t;
+        const double v = s[t];
+        if (v > k && !(fabs(v - k) <= tol)) return t;
+        ++t;
+    }
+    int len = m - t;
+    while (len > 0) {
+        const int half = len >> 1;
+        const double v = s[t + half];
+        if (v > k && !(fabs(v - k) <= tol)) {
+            len = half;
+        } else {
+            t += half + 1;
+            len -= half + 1;
+        }
+    }
+    return t;
+}
+
+__device__ __forceinline__ void tol_insert5(uint32_t (&tk)[kTop], uint32_t v) {
+#pragma unroll
+    for (int t = 0; t < kTop; ++t) {
+        const uint32_t lo = tk[t] < v ? tk[t] : v;
+        v = tk[t] < v ? v : tk[t];
+        tk[t] = lo;
+    }
+}
+
+// Batch query preparation.  grid = (ceil(max_query_len / kTolSortBlock), Q).  Query q's non-NaN values go,
+// ascending (ties by position; -0.0 folded to +0.0), to sv/sp[(q_offsets[q] - q_offsets[0]) + rank];
+// qm[q] = how many.  A query longer than max_query_len, or one that does not fit the workspace's
+// `room` values, gets qm[q] = -1 (the sweep flags it).  hits_n[q] = 0 for the sweep that follows.
+__global__ __launch_bounds__(kTolSortBlock) void ts_tol_sort_kernel(
+    const double *__restrict__ queries, const int64_t *__restrict__ q_offsets, int32_t max_len, int64_t room,
+    double *__restrict__ sv, int32_t *__restrict__ sp, int32_t *__restrict__ qm, int32_t *__restrict__ hits_n) {
+    __shared__ double tile[kTolSortTile];
+    __shared__ int32_t s_nan;
+    const int q = blockIdx.y;
+    const int64_t o0 = q_offsets[0];
+    const int64_t qo = q_offsets[q];
+    const int64_t n = q_offsets[q + 1] - qo;
+    const int64_t at = qo - o0;
+    const bool lead = blockIdx.x == 0;
+    if (lead && threadIdx.x == 0) {
+        hits_n[q] = 0;
+        s_nan = 0;
+    }
+    if (n > max_len || n < 0 || at < 0 || at + n > room) {
+        if (lead && threadIdx.x == 0) qm[q] = -1;
+        return;                                              // block-uniform
+    }
+    if (!lead && (int64_t)blockIdx.x * kTolSortBlock >= n) return;
+    const int64_t i = (int64_t)blockIdx.x * kTolSortBlock + threadIdx.x;
+    const double vi = i < n ? queries[qo + i] : 0.0;
+    const bool live = i < n && vi == vi;
+    int32_t rank = 0, nan_local = 0;
+    for (int64_t t0 = 0; t0 < n; t0 += kTolSortTile) {
+        const int tn = (int)(n - t0 < kTolSortTile ? n - t0 : kTolSortTile);
+        __syncthreads();
+        for (int e = threadIdx.x; e < tn; e += kTolSortBlock) {
+            const double v = queries[qo + t0 + e];
+            tile[e] = v;
+            nan_local += (v != v);
+        }
+        __syncthreads();
+        if (live) {
+            const int before_me = (int)(i - t0 < 0 ? 0 : (i - t0 < tn ? i - t0 : tn));   // tile elements ahead of i
+            for (int e = 0; e < tn; ++e) {
+                const double v = tile[e];                    // the same address in every lane: a broadcast
+                rank += (v < vi) | ((v == vi) & (e < before_me));
+            }
+        }
+    }
+    if (live) {
+        sv[at + rank] = vi == 0.0 ? 0.0 : vi;
+        sp[at + rank] = (int32_t)i;
+    }
+    if (lead) {
+        if (nan_local) atomicAdd(&s_nan, nan_local);
+        __syncthreads();
+        if (threadIdx.x == 0) qm[q] = (int32_t)(n - s_nan);
+    }
+}
+
+// The sweep.  grid = (row blocks, Q).  Sorted query q: values sv[at .. at+m), positions sp[..], with
+// at = q_offsets[q] - q_offsets[0] and m = qm[q] (batch); q_offsets == nullptr: one query of m_one values at 0.
+// LDSQ: the sorted query is copied to LDS first (m <= the dynamic LDS the launch gave: lds_keys).
+template <int MODE, bool HOSTOUT, bool LDSQ>
+__global__ __launch_bounds__(kTolBlock) void ts_match_tol_kernel(
+    const Row *__restrict__ rows, int64_t n_rows, const int64_t *__restrict__ keys,
+    const double *__restrict__ sv, const int32_t *__restrict__ sp, const int64_t *__restrict__ q_offsets,
+    const int32_t *__restrict__ qm, int32_t m_one, int32_t lds_keys, double tol, int32_t min_match,
+    const int32_t *__restrict__ exclude_ids, int32_t exclude_one, int32_t cap, int32_t *__restrict__ hits,
+    int32_t *__restrict__ hits_n, HostOut ho) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __shared__ int32_t s_stage[HOSTOUT ? 1 : kQ1Stage * 3];
+    __shared__ int32_t s_nhits, s_stage_base;
+    const int q = blockIdx.y;
+    const int bx = blockIdx.x;
+    int64_t at = 0;
+    int32_t m = m_one;
+    if (q_offsets) {
+        at = q_offsets[q] - q_offsets[0];
+        m = qm[q];
+    }
+    if (m < 0 || (LDSQ && m > lds_keys)) {
+        // longer than the caller's max_query_len, or no room for it in the workspace
+        if (!HOSTOUT && threadIdx.x == 0 && bx == 0) hits_n[q] = INT32_MIN;
+        if (HOSTOUT && threadIdx.x == 0) ho.counts[bx] = INT32_MIN;
+        return;                                                      // block-uniform
+    }
+    const double *s = sv + at;
+    const int32_t *pos = sp + at;
+    if constexpr (LDSQ) {
+        double *lv = reinterpret_cast<double *>(smem);
+        int32_t *lp = reinterpret_cast<int32_t *>(smem + (size_t)((lds_keys + 1) & ~1) * 8);
+        for (int e = threadIdx.x; e < m; e += kTolBlock) {
+            lv[e] = s[e];
+            lp[e] = pos[e];
+        }
+        s = lv;
+        pos = lp;
+    }
+    if (threadIdx.x == 0) s_nhits = 0;
+    __syncthreads();
+
+    const int gl = threadIdx.x & (kGroup - 1);
+    const int g = threadIdx.x / kGroup;
+    const int32_t excl = exclude_ids ? exclude_ids[q] : exclude_one;
+    const int64_t stride = (int64_t)gridDim.x * kTolGroups;
+    int64_t r = (int64_t)bx * kTolGroups + g;
+    const int64_t last_row = n_rows - 1;
+    Row row = {};
+    if (r < n_rows) row = load_row(rows + r);
+    while (r < n_rows) {
+        const int64_t rn = r + stride;
+        const Row nrow = load_row(rows + (rn < n_rows ? rn : last_row)); // lands while this row is searched
+        const int64_t *rk = keys + row.off;
+        const int len = row.len;
+        uint32_t cnt = 0, m1 = 0xffffffffu, m2 = 0xffffffffu;
+        uint32_t tk[kTop];
+#pragma unroll
+        for (int t = 0; t < kTop; ++t) tk[t] = 0xffffffffu;
+        auto acc_range = [&](int a, int b) {
+            if (b <= a) return;
+            cnt += (uint32_t)(b - a);
+            if constexpr (MODE == kTolModeM2) {
+                for (int t = a; t < b; ++t) {
+                    const uint32_t p = (uint32_t)pos[t];
+                    const uint32_t lo = m1 < p ? m1 : p, hi = m1 < p ? p : m1;
+                    m1 = lo;
+                    m2 = m2 < hi ? m2 : hi;
+                }
+            } else if constexpr (MODE == kTolModeTop5) {
+                for (int t = a; t < b; ++t) tol_insert5(tk, (uint32_t)pos[t]);
+            }
+        };
+        // packed union state a key hands to its arena successor: (neg ? lo : hi) | neg << 31
+        uint32_t carry = 0;
+        int64_t k0 = 0;                      // the row's first arena key (numerically largest negative, if any)
+        int hi0 = -1;                        // its hi, computed by the lane that needs it
+        for (int base = 0; base < len; base += kTolStepKeys) {
+            longlong2 cur[kTolLd];
+#pragma unroll
+            for (int j = 0; j < kTolLd; ++j) {
+                const int i = base + gl * 2 + j * 2 * kGroup;
+                const int64_t *p = (i < len) ? rk + i : keys;                 // unconditional 16-byte loads
+                cur[j] = *reinterpret_cast<const longlong2 *>(p);
+            }
+            if (base == 0) k0 = __shfl(cur[0].x, 0, kGroup);               // group-uniform step
+#pragma unroll
+            for (int j = 0; j < kTolLd; ++j) {
+                const int i = base + gl * 2 + j * 2 * kGroup;
+                const bool vx = i < len, vy = i + 1 < len;
+                const int64_t bx_ = cur[j].x, by_ = cur[j].y;
+                const bool nx = bx_ < 0, ny = by_ < 0;
+                int lox = 0, hix = 0, loy = 0, hiy = 0;
+                if (vx) {
+                    const double kx = __longlong_as_double(bx_);
+                    lox = tol_lo(s, m, kx, tol);
+                    hix = tol_hi(s, m, lox, kx, tol);
+                }
+                if (vy) {
+                    const double ky = __longlong_as_double(by_);
+                    loy = tol_lo(s, m, ky, tol);
+                    hiy = tol_hi(s, m, loy, ky, tol);
+                }
+                const uint32_t cy = (uint32_t)(ny ? loy : hiy) | (ny ? 0x80000000u : 0u);
+                // arena predecessor of x: y of lane gl-1; for lane 0 the y of lane 15 one load earlier
+                const uint32_t t = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)cy, 0x121, 0xf, 0xf, false);  // row_ror:1
+                const uint32_t px = gl == 0 ? carry : t;
+                carry = t;
+                auto first_pos_prev = [&]() -> int {                         // hi of arena key 0
+                    if (hi0 < 0) {
+                        const double kk = __longlong_as_double(k0);
+                        hi0 = tol_hi(s, m, tol_lo(s, m, kk, tol), kk, tol);
+                    }
+                    return hi0;
+                };
+                if (vx) {
+                    const bool none = i == 0;
+                    const bool pneg = (px >> 31) != 0;
+                    const int pv = (int)(px & 0x7fffffffu);
+                    if (nx) {
+                        acc_range(lox, none ? hix : (hix < pv ? hix : pv));
+                    } else {
+                        const int prev = none ? 0 : (pneg ? first_pos_prev() : pv);
+                        acc_range(lox > prev ? lox : prev, hix);
+                    }
+                }
+                if (vy) {
+                    if (ny) {
+                        acc_range(loy, hiy < lox ? hiy : lox);
+                    } else {
+                        const int prev = nx ? first_pos_prev() : hix;
+                        acc_range(loy > prev ? loy : prev, hiy);
+                    }
+                }
+            }
+        }
+#define TVZ_SUM_STEP(C) cnt += dpp16<C>(cnt);
+        TVZ_ROW16_BUTTERFLY(TVZ_SUM_STEP)
+#undef TVZ_SUM_STEP
+        const bool hit = (int64_t)cnt >= (int64_t)min_match && row.vid != excl;
+        if (__ballot(hit) != 0ull) {
+            if constexpr (MODE == kTolModeM2) {
+#define TVZ_M2_STEP(C) { const uint32_t p1 = dpp16<C>(m1), p2 = dpp16<C>(m2); \
+                const uint32_t lo = m1 < p1 ? m1 : p1, hi = m1 < p1 ? p1 : m1, r2 = m2 < p2 ? m2 : p2; \
+                m1 = lo; m2 = hi < r2 ? hi : r2; }
+                TVZ_ROW16_BUTTERFLY(TVZ_M2_STEP)
+#undef TVZ_M2_STEP
+            } else if constexpr (MODE == kTolModeTop5) {
+                // each step merges two DISJOINT sets of positions (every union element is visited once)
+#define TVZ_T5_STEP(C) { uint32_t o[kTop]; \
+                _Pragma("unroll") for (int t = 0; t < kTop; ++t) o[t] = dpp16<C>(tk[t]); \
+                _Pragma("unroll") for (int t = 0; t < kTop; ++t) tol_insert5(tk, o[t]); }
+                TVZ_ROW16_BUTTERFLY(TVZ_T5_STEP)
+#undef TVZ_T5_STEP
+            }
+        }
+        if (hit && gl == 0) {
+            int32_t kth;
+            if (min_match <= 0) kth = -1;
+            else if constexpr (MODE == kTolModeM2) kth = (int32_t)(min_match == 1 ? m1 : m2);
+            else if constexpr (MODE == kTolModeTop5) kth = (int32_t)tk[min_match - 1];
+            else kth = -2 - (int32_t)r;                          // resolved by ts_tol_kth_fixup_kernel
+            const int slot = atomicAdd(&s_nhits, 1);             // LDS
+            if constexpr (HOSTOUT) {
+                int32_t *h = ho.hits + ((int64_t)bx * ho.region + slot) * 3;
+                h[0] = row.vid;
+                h[1] = (int32_t)cnt;
+                h[2] = kth;
+            } else if (slot < kQ1Stage) {
+                s_stage[slot * 3 + 0] = row.vid;
+                s_stage[slot * 3 + 1] = (int32_t)cnt;
+                s_stage[slot * 3 + 2] = kth;
+            } else {                                             // a block with > 256 hits: the rest one by one
+                const int gs = atomicAdd(&hits_n[q], 1);
+                if (gs < cap) {
+                    int32_t *h = hits + ((int64_t)q * cap + gs) * 3;
+                    h[0] = row.vid;
+                    h[1] = (int32_t)cnt;
+                    h[2] = kth;
+                }
+            }
+        }
+        row = nrow;
+        r = rn;
+    }
+    __syncthreads();
+    if constexpr (HOSTOUT) {
+        if (threadIdx.x == 0) ho.counts[bx] = s_nhits;
+    } else {
+        const int staged = s_nhits < kQ1Stage ? s_nhits : kQ1Stage;
+        if (staged == 0) return;                                 // block-uniform
+        if (threadIdx.x == 0) s_stage_base = atomicAdd(&hits_n[q], staged);
+        __syncthreads();
+        const int hb = s_stage_base;
+        int32_t *dst = hits + ((int64_t)q * cap + hb) * 3;
+        const int room = cap - hb < staged ? (cap - hb > 0 ? cap - hb : 0) : staged;
+        for (int i = threadIdx.x; i < room * 3; i += kTolBlock) dst[i] = s_stage[i];
+    }
+}
+
+// does some key of the row match q?  The row's numeric order is arena [p-1 .. 0] then [p .. len-1] (p = negative
+// keys); the keys matching q are contiguous in it, so if any does, the nearest key below or at q, or the
+// nearest above it, does.
+__device__ __forceinline__ bool tol_row_has(const int64_t *rk, int len, int p, double q, double tol) {
+    int lo = 0, n = len;                          // first numeric index t with key(t) >= q
+    while (n > 0) {
+        const int half = n >> 1;
+        const int t = lo + half;
+        const double v = __longlong_as_double(rk[t < p ? p - 1 - t : t]);
+        if (v < q) {
+            lo = t + 1;
+            n -= half + 1;
+        } else {
+            n = half;
+        }
+    }
+    bool hit = false;
+    if (lo < len) hit = tol_match(q, __longlong_as_double(rk[lo < p ? p - 1 - lo : lo]), tol);
+    if (lo > 0) {
+        const int t = lo - 1;
+        hit = hit || tol_match(q, __longlong_as_double(rk[t < p ? p - 1 - t : t]), tol);
+    }
+    return hit;
+}
+
+// kth for min_match > 5: list b (a query's hit list, or one block's region of a single query's pinned hits)
+// holds min(counts[b], region) hits whose kth field is -2 - row; the query (raw, in its original order) is
+// queries[q_offsets[b] ..) or, with q_offsets == nullptr, queries[0 .. n_one).  A 16-lane group per hit.
+__global__ __launch_bounds__(kBlock) void ts_tol_kth_fixup_kernel(
+    const Row *__restrict__ rows, const int64_t *__restrict__ keys, const double *__restrict__ queries,
+    const int64_t *__restrict__ q_offsets, int32_t n_one, double tol, int32_t min_match,
+    int32_t *__restrict__ hits, const int32_t *__restrict__ counts, int32_t region) {
+    const int b = blockIdx.x;
+    const int gl = threadIdx.x & (kGroup - 1);
+    const int g = threadIdx.x / kGroup;
+    const int gshift = (threadIdx.x & 63) & ~(kGroup - 1);
+    int n = counts[b];
+    if (n > region) n = region;
+    int64_t qo = 0, qlen = n_one;
+    if (q_offsets) {
+        qo = q_offsets[b];
+        qlen = q_offsets[b + 1] - qo;
+    }
+    const double *qv = queries + qo;
+    for (int j = g; j < n; j += kGroupsPerBlock) {
+        int32_t *h = hits + ((int64_t)b * region + j) * 3;
+        const int32_t code = h[2];
+        if (code > -2) continue;
+        const Row row = load_row(rows + (-2 - (int64_t)code));
+        const int64_t *rk = keys + row.off;
+        int p0 = 0, pn = row.len;                     // p = keys with a negative bit pattern (they come first)
+        while (pn > 0) {
+            const int half = pn >> 1;
+            if (rk[p0 + half] < 0) {
+                p0 += half + 1;
+                pn -= half + 1;
+            } else {
+                pn = half;
+            }
+        }
+        int kth = TVZ_KTH_NEVER;
+        int running = 0;
+        for (int64_t base = 0; base < qlen && kth == TVZ_KTH_NEVER; base += kGroup) {
+            const int64_t i = base + gl;
+            bool hit = false;
+            if (i < qlen) {
+                const double x = qv[i];
+                hit = x == x && tol_row_has(rk, row.len, p0, x, tol);
+            }
+            const uint32_t m16 = (uint32_t)(__ballot(hit) >> gshift) & 0xffffu;
+            const int c = __popc(m16);
+            if (running + c >= min_match) {
+                uint32_t mm = m16;
+                for (int need = min_match - running; need > 1; --need) mm &= mm - 1;
+                kth = (int)(base + (__ffs(mm) - 1));
+            }
+            running += c;
+        }
+        if (gl == 0) h[2] = kth;
+    }
+}
+
+}  // namespace

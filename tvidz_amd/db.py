@@ -437,12 +437,20 @@ class Store:
             finally:
                 session.close()
 
-    def find_duplicates(self, new_timestamps, min_match=5) -> List[Tuple[int, int]]:   # db.py:76-94
+    def find_duplicates(self, new_timestamps, min_match=5, tolerance=0.0) -> List[Tuple[int, int]]:   # db.py:76-94
+        """`tolerance` > 0: the opt-in tolerant match (include/tvz.h tvz_find_duplicates_tol), not the
+        reference's exact verdict."""
+        if tolerance:
+            return self.corpus.find_duplicates(new_timestamps, min_match, tolerance=tolerance)
         return self.corpus.find_duplicates(new_timestamps, min_match)
 
-    def find_duplicates_kth(self, new_timestamps, min_match=5, exclude_id=-1):
+    def find_duplicates_kth(self, new_timestamps, min_match=5, exclude_id=-1, tolerance=0.0):
         """(video_id, match_count, kth): kth = index of the min_match-th matching query element;
-        one call replaces the per-prefix loop of app.py:231-255 (see include/tvz.h)."""
+        one call replaces the per-prefix loop of app.py:231-255 (see include/tvz.h).  `tolerance` > 0:
+        the opt-in tolerant match."""
+        if tolerance:
+            return self.corpus.find_duplicates(new_timestamps, min_match, exclude_id=exclude_id,
+                                               with_kth=True, tolerance=tolerance)
         return self.corpus.find_duplicates(new_timestamps, min_match, exclude_id=exclude_id,
                                            with_kth=True)
 
@@ -573,7 +581,9 @@ def update_duplicates(video_id, duplicate_ids):
     return store().update_duplicates(video_id, duplicate_ids)
 
 
-def find_duplicates(new_timestamps, min_match=5):
+def find_duplicates(new_timestamps, min_match=5, tolerance=0.0):
+    if tolerance:
+        return store().find_duplicates(new_timestamps, min_match, tolerance=tolerance)
     return store().find_duplicates(new_timestamps, min_match)
 
 

@@ -29,6 +29,7 @@ from __future__ import annotations
 
 import json
 import os
+import sys
 import threading
 import time
 import uuid
@@ -82,8 +83,18 @@ class Inspector:
                  pts_policy: str = scene.PTS_POLICY_G6, batch: int = 256, max_workers: int = 16,
                  near_duplicates: bool = False, near_eps: float = 1.0 / 30, near_max_offset: float = 30.0,
                  near_jaccard: float = 0.8, slot_bytes: int = 64 << 20, n_slots: Optional[int] = None,
-                 profile: bool = False):
+                 profile: bool = False, match_tolerance: float = 0.0):
         self.store = store
+        # opt-in, never the default: duplicates by the TOLERANT count (include/tvz.h tvz_find_duplicates_tol)
+        # instead of the reference's exact float64 equality; the verdict, the truncation at kth and the stored
+        # duplicates all follow it.  Refused here, before any upload, where the store's corpus cannot do it.
+        self.match_tolerance = float(match_tolerance)
+        if not (0.0 <= self.match_tolerance <= sys.float_info.max):
+            raise ValueError(f"match_tolerance must be finite and >= 0, got {match_tolerance!r}")
+        if self.match_tolerance > 0.0 and not getattr(getattr(store, "corpus", None), "supports_tolerance", False):
+            raise RuntimeError(f"match_tolerance={self.match_tolerance}: the store's corpus "
+                               f"({type(getattr(store, 'corpus', None)).__name__}) has no tolerant match; "
+                               "use a DeviceCorpus or a service.ShardedCorpus")
         self.device = torch.device(device)
         self.frame_source = frame_source or s3_frame_source
         self.threshold = threshold
@@ -279,7 +290,11 @@ class Inspector:
         have stopped -, persist, and on the first hit: truncate, record the duplicates, stop.
         -> (scene_timestamps, stop).  `dups_to_report` is extended in place."""
         t = time.perf_counter()
-        hits = self.store.find_duplicates_kth(scene_timestamps, self.min_match, exclude_id=video_id)   # :235-237
+        if self.match_tolerance > 0.0:
+            hits = self.store.find_duplicates_kth(scene_timestamps, self.min_match, exclude_id=video_id,
+                                                  tolerance=self.match_tolerance)
+        else:
+            hits = self.store.find_duplicates_kth(scene_timestamps, self.min_match, exclude_id=video_id)   # :235-237
         t = self._phase("match", t)
         hits = [h for h in hits if h[2] < KTH_NEVER]
         if hits:

@@ -225,19 +225,27 @@ class ShardedCorpus:
                               + [np.zeros((0, 5), dtype=np.int32)])
 
     # ---- matches ----
-    def _exact(self, q, min_match, exclude_id, with_kth):
+    supports_tolerance = True             # tolerant asks go to every shard in turn (inspector.Inspector checks)
+
+    def _exact(self, q, min_match, exclude_id, with_kth, tolerance=0.0):
         out = []
         for s in self.shards:
-            out += s.find_duplicates(q, min_match, exclude_id=exclude_id, with_kth=True)
+            if tolerance:
+                out += s.find_duplicates(q, min_match, exclude_id=exclude_id, with_kth=True, tolerance=tolerance)
+            else:
+                out += s.find_duplicates(q, min_match, exclude_id=exclude_id, with_kth=True)
         out.sort()
         return out if with_kth else [(v, c) for v, c, _ in out]
 
     def find_duplicates(self, new_timestamps: Sequence[float], min_match: int = 5, exclude_id: int = -1,
-                        with_kth: bool = False):
+                        with_kth: bool = False, tolerance: float = 0.0):
         """with_kth (the driver's per-micro-batch ask): through the tick -> the k best rows by
         (kth, video_id), which hold the verdict; otherwise (db.find_duplicates, db.py:76-94: every
-        row with its count) the shards are asked one by one."""
+        row with its count) the shards are asked one by one.  `tolerance` > 0 (the opt-in tolerant
+        match): every shard in turn, never the tick's exact top-k."""
         q = np.ascontiguousarray(np.asarray(new_timestamps, dtype=np.float64))
+        if tolerance:
+            return self._exact(q, min_match, exclude_id, with_kth, tolerance=float(tolerance))
         if not with_kth or q.size > MAX_BATCH_LEN or not 1 <= int(min_match) <= 5:
             return self._exact(q, min_match, exclude_id, with_kth)
         rows, total = self.batcher.submit(q, min_match, exclude_id).result()
