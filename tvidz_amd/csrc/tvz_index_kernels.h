@@ -661,12 +661,12 @@ inline size_t ix_lds_bytes(int max_len, int spb, bool topk = false) {
 }
 
 // MODE (how a candidate's slot accounts for its postings):
-//   kIxM2    (min_match 1..2): the two smallest positions in two atomicMin words - two plain LDS atomics
-//            per candidate posting instead of the 5 x 12-bit CAS loop;
-//   kIxTop5  (min_match 3..5): the five smallest positions in one 64-bit CAS word;
-//   kIxCount (min_match > 5): the count alone; a hit leaves with kth = -2 - row and ts_kth_fixup_kernel
-//            resolves it (the walk the sweeps use for min_match > 5), so that an indexed corpus never
-//            falls back to sweeping every row.
+//   kModeM2    (min_match 1..2): the two smallest positions in two atomicMin words - two plain LDS atomics
+//              per candidate posting instead of the 5 x 12-bit CAS loop;
+//   kModeTop5  (min_match 3..5): the five smallest positions in one 64-bit CAS word;
+//   kModeCount (min_match > 5): the count alone; a hit leaves with kth = -2 - row and ts_kth_fixup_kernel
+//              resolves it (the walk the sweeps use for min_match > 5), so that an indexed corpus never
+//              falls back to sweeping every row.
 // grid = (Q, groups): block (q, g) walks sub-indexes [g * spb, min(n_sub, (g + 1) * spb)).
 //   HOSTOUT (tvz_find_duplicates): hits = pinned host memory [n_sub][kSubRows][3], hits_n[sub] = the
 //            sub-index's hit count (every sub-index has its own region: no atomics, any grouping).
@@ -696,7 +696,6 @@ inline size_t ix_lds_bytes(int max_len, int spb, bool topk = false) {
 // done, emit scan); every LDS array is reset inside the phases by the threads that used it last.
 // (Profiled with s_memtime stamps, profiles/ix_stamps.py: with block-wide compaction 55 % of a
 // block's cycles were barrier waits.)
-constexpr int kIxM2 = 0, kIxTop5 = 1, kIxCount = 2;
 
 // The loops over a long query's later chunks (more than 512 timestamps: rare) address LDS from the lane
 // number; hoisted out of the sub-index loop those addresses were live across the whole kernel - at the
@@ -722,16 +721,16 @@ __device__ __forceinline__ void ix_lookup_body(
     int32_t min_match, const int32_t *__restrict__ exclude_ids, int32_t exclude_one, int32_t cap,
     int32_t *__restrict__ hits, int32_t *__restrict__ hits_n, int32_t ns, const QByVal *qv, const int q_first,
     const int group, const int n_groups, const int32_t tk_k = 0, const int32_t Q = 0) {
-    static_assert(!(TOPK && (HOSTOUT || MODE == kIxCount)), "the fused top-k needs kth in the block and a device list");
+    static_assert(!(TOPK && (HOSTOUT || MODE == kModeCount)), "the fused top-k needs kth in the block and a device list");
     static_assert(NQ == 1 || (NQ == 2 && TOPK), "two queries per block: the top-k form only");
-    constexpr bool TOP5 = MODE == kIxTop5;
+    constexpr bool TOP5 = MODE == kModeTop5;
     const int dir_log2 = dir_bits & 0xff;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint32_t *bm1 = reinterpret_cast<uint32_t *>(smem);
     uint32_t *bm2 = bm1 + kIxWords;
     uint32_t *tcnt = bm2 + kIxWords;
     unsigned long long *ttop = reinterpret_cast<unsigned long long *>(tcnt + kIxSlots);
-    uint32_t *m1 = reinterpret_cast<uint32_t *>(ttop), *m2 = m1 + kIxSlots;   // kIxM2: the same 8 B per slot
+    uint32_t *m1 = reinterpret_cast<uint32_t *>(ttop), *m2 = m1 + kIxSlots;   // kModeM2: the same 8 B per slot
     uint32_t *pcache_all = reinterpret_cast<uint32_t *>(ttop + kIxSlots);  // cached postings: row | position << kSubLog2
     const int L = NQ * (max_len > 0 ? max_len : 1);        // positions of all of the block's queries
     uint2 *lst_all = reinterpret_cast<uint2 *>(pcache_all + kIxCache);  // per wave: non-empty list j = {first posting - local start, position}
@@ -793,7 +792,7 @@ __device__ __forceinline__ void ix_lookup_body(
     uint32_t *lbits = lbits_all + wave * kIxLW;
     auto reset_slot = [&](uint32_t k) {
         tcnt[k] = 0;
-        if (TOP5) ttop[k] = kTopNone; else if (MODE == kIxM2) { m1[k] = 0xffffffffu; m2[k] = 0xffffffffu; }
+        if (TOP5) ttop[k] = kTopNone; else if (MODE == kModeM2) { m1[k] = 0xffffffffu; m2[k] = 0xffffffffu; }
     };
     for (int i = threadIdx.x; i < kIxWords; i += kIxBlock) { bm1[i] = 0; bm2[i] = 0; }
     for (int i = threadIdx.x; i < kIxWaves * kIxLW; i += kIxBlock) lbits_all[i] = 0;
@@ -1083,7 +1082,7 @@ __device__ __forceinline__ void ix_lookup_body(
                         if (old == seen) break;
                         seen = old;
                     }
-                } else if constexpr (MODE == kIxM2) {
+                } else if constexpr (MODE == kModeM2) {
                     const uint32_t o = atomicMin(&m1[idx], pos);             // positions of one row are distinct
                     atomicMin(&m2[idx], o > pos ? o : pos);                  // larger of two hits >= 2nd smallest
                 }
@@ -1131,7 +1130,7 @@ __device__ __forceinline__ void ix_lookup_body(
             // emit: one slot per thread and round; the slots that reached min_match and are live hits get
             // a place by a block-wide scan - one reservation per block, none when the block owns the list
             auto kth_of = [&](uint32_t k) -> int32_t {
-                if constexpr (MODE == kIxCount) return -2 - (int32_t)(row0 + elist[k]);   // ts_kth_fixup_kernel resolves it
+                if constexpr (MODE == kModeCount) return -2 - (int32_t)(row0 + elist[k]);   // ts_kth_fixup_kernel resolves it
                 else if constexpr (TOP5) return (int32_t)((uint32_t)(ttop[k] >> (12 * (min_match - 1))) & 0xfffu);
                 else return (int32_t)(min_match == 1 ? m1[k] : m2[k]);
             };
@@ -1389,14 +1388,15 @@ __global__ __launch_bounds__(kIxBlock) __attribute__((amdgpu_waves_per_eu(8, 8))
     const Row *__restrict__ delta_rows, int64_t n_delta, const int64_t *__restrict__ keys, int32_t s_log2,
     HostOut ho, const QByVal qv) {
     if ((int)blockIdx.x < n_groups)
-        ix_lookup_body<true, TOP5 ? kIxTop5 : kIxM2, false>(dir, dir_bits, ks, post, ivid, n_indexed, n_sub, spb, queries,
-                                                            q_offsets, max_len, min_match, nullptr, exclude_one, 0, ix_hits,
-                                                            ix_hits_n, 1, &qv, 0, (int)blockIdx.x, n_groups);
+        ix_lookup_body<true, TOP5 ? kModeTop5 : kModeM2, false>(dir, dir_bits, ks, post, ivid, n_indexed, n_sub, spb,
+                                                                queries, q_offsets, max_len, min_match, nullptr,
+                                                                exclude_one, 0, ix_hits, ix_hits_n, 1, &qv, 0,
+                                                                (int)blockIdx.x, n_groups);
     else
-        q1_body<TOP5 ? kQ1ModeTop5 : kQ1ModeM2, true, kIxBlock>(delta_rows, n_delta, keys, queries, q_offsets, min_match,
-                                                               nullptr, exclude_one, 0, nullptr, nullptr, 1, s_log2, ho,
-                                                               qv, (int)blockIdx.x - n_groups,
-                                                               (int)gridDim.x - n_groups, 0);
+        q1_body<TOP5 ? kModeTop5 : kModeM2, true, kIxBlock>(delta_rows, n_delta, keys, queries, q_offsets, min_match,
+                                                            nullptr, exclude_one, 0, nullptr, nullptr, 1, s_log2, ho,
+                                                            qv, (int)blockIdx.x - n_groups,
+                                                            (int)gridDim.x - n_groups, 0);
 }
 
 }  // namespace

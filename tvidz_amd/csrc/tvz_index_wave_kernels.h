@@ -69,14 +69,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
     const int32_t *__restrict__ ivid, int64_t n_indexed, const double *__restrict__ queries,
     const int64_t *__restrict__ q_offsets, int32_t Q, int32_t max_len, int32_t min_match,
     const int32_t *__restrict__ exclude_ids, int32_t cap, int32_t tk_k, int32_t *__restrict__ topk) {
-    static_assert(MODE == kIxM2 || MODE == kIxTop5, "kth is known inside the wave for min_match 1..5");
-    constexpr bool TOP5 = MODE == kIxTop5;
+    static_assert(MODE == kModeM2 || MODE == kModeTop5, "kth is known inside the wave for min_match 1..5");
+    constexpr bool TOP5 = MODE == kModeTop5;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint32_t *bm1 = reinterpret_cast<uint32_t *>(smem);
     uint32_t *bm2 = bm1 + kWqWords;
     uint32_t *tcnt = bm2 + kWqWords;
     unsigned long long *ttop = reinterpret_cast<unsigned long long *>(tcnt + kWqSlots);
-    uint32_t *m12 = reinterpret_cast<uint32_t *>(ttop);   // kIxM2: the same 8 B per slot = {smallest, second smallest} position
+    uint32_t *m12 = reinterpret_cast<uint32_t *>(ttop);   // kModeM2: the same 8 B per slot = {smallest, second smallest} position
     uint32_t *lbits = reinterpret_cast<uint32_t *>(ttop + kWqSlots);                 // bit t: a list starts at local posting t
     unsigned long long *tkb = reinterpret_cast<unsigned long long *>(lbits + kWqRegPost / 32);   // kept hits
     uint32_t *kh = reinterpret_cast<uint32_t *>(tkb + kIxTkCap);                     // hits per kth bin

@@ -26,6 +26,7 @@
 #include <mutex>
 #include <shared_mutex>
 #include <thread>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -36,10 +37,27 @@
 
 namespace {
 
+// A device buffer of `cap` elements, grown by ensure(); it frees itself.
 template <typename T>
 struct DevBuf {
     T *p = nullptr;
     int64_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+};
+
+// A pinned host buffer (pinned_alloc); a MAPPED one is also addressable from the device at `d`, where the
+// single-query kernels write their hits.  It frees itself.
+template <typename T>
+struct Pinned {
+    T *h = nullptr;
+    T *d = nullptr;
+    Pinned() = default;
+    Pinned(const Pinned &) = delete;
+    Pinned &operator=(const Pinned &) = delete;
+    ~Pinned() { if (h) (void)hipHostFree(h); }
 };
 
 // Per-thread-of-control scratch of tvz_find_duplicates: its own stream, a pinned query buffer
@@ -47,31 +65,26 @@ struct DevBuf {
 // upload for the reserved row count, so a query allocates nothing.
 struct Staging {
     hipStream_t stream = nullptr;
-    int64_t *h_query = nullptr;      // pinned: {0, n} + canonical-order query keys (as double bits)
-    int64_t *d_query = nullptr;      // device copy of the same
-    int32_t *h_hits = nullptr;       // pinned + mapped: [blocks][region][3]
-    int32_t *dh_hits = nullptr;      // the device alias of h_hits
-    int32_t *h_counts = nullptr;     // pinned + mapped: [kQ1MaxBlocks]
-    int32_t *dh_counts = nullptr;
-    int64_t hit_slots = 0;           // capacity of h_hits in hits
-    int32_t *h_ix_hits = nullptr;    // pinned + mapped: hits of the index lookup [ix_slots][3]
-    int32_t *dh_ix_hits = nullptr;
+    Pinned<int64_t> query;           // {0, n} + canonical-order query keys (as double bits)
+    DevBuf<int64_t> d_query;         // device copy of the same
+    Pinned<int32_t> hits;            // mapped: [blocks][region][3]
+    Pinned<int32_t> counts;          // mapped: [kQ1MaxBlocks] per sweep block, then one per sub-index
+    int64_t hit_slots = 0;           // capacity of `hits` in hits
+    Pinned<int32_t> ix_hits;         // mapped: hits of the index lookup [ix_slots][3]
     int64_t ix_slots = 0;
-    int32_t *d_hits = nullptr;       // device hit list for the paths that need a fix-up pass
-    int32_t *d_hits_n = nullptr;
-    int64_t d_hit_slots = 0;
-    int64_t *d_sq = nullptr;         // long queries: sorted distinct keys + multiplicities
-    int32_t *d_smult = nullptr;
-    int64_t sq_cap = 0;
+    DevBuf<int32_t> d_hits;          // device hit list [3 per hit] for the paths that need a fix-up pass
+    DevBuf<int32_t> d_hits_n;
+    DevBuf<int64_t> d_sq;            // long queries: sorted distinct keys + multiplicities
+    DevBuf<int32_t> d_smult;
     // tvz_find_duplicates_tol: the sorted query (values, then positions) of up to kMaxQueryLen timestamps,
     // pinned + its device copy; longer queries use the growable d_tol_big
-    unsigned char *h_tol = nullptr;
-    unsigned char *d_tol = nullptr;
-    unsigned char *d_tol_big = nullptr;
-    size_t tol_big_bytes = 0;
+    Pinned<unsigned char> tol;
+    DevBuf<unsigned char> d_tol;
+    DevBuf<unsigned char> d_tol_big;
     std::vector<std::pair<double, int32_t>> tol_sort;   // host sort scratch (keeps its capacity)
     std::atomic<int> busy{0};        // a sweep of this staging is in flight (drain() waits for it)
     int gen = 0;                     // index generation that sweep reads
+    ~Staging() { if (stream) (void)hipStreamDestroy(stream); }
 };
 
 
@@ -248,6 +261,16 @@ int ensure(DevBuf<T> &b, int64_t need, int64_t keep) {
     if (b.p) (void)hipFree(b.p);
     b.p = np;
     b.cap = cap;
+    return TVZ_OK;
+}
+
+// (re)allocate a pinned buffer of n elements, mapped into the device's address space if asked; old contents are lost
+template <typename T>
+int pinned_alloc(Pinned<T> &b, int64_t n, bool mapped) {
+    if (b.h) (void)hipHostFree(b.h);
+    b.h = b.d = nullptr;
+    TVZ_HIP(hipHostMalloc(&b.h, (size_t)n * sizeof(T), mapped ? hipHostMallocMapped : hipHostMallocDefault));
+    if (mapped) TVZ_HIP(hipHostGetDevicePointer(reinterpret_cast<void **>(&b.d), b.h, 0));
     return TVZ_OK;
 }
 
@@ -737,61 +760,35 @@ int rebuild_in_background(tvz_corpus *c, std::unique_lock<std::shared_mutex> &lk
 }
 
 // ---- single-query staging --------------------------------------------------------------------
-void staging_free(Staging *s) {
-    if (s->h_query) (void)hipHostFree(s->h_query);
-    if (s->d_query) (void)hipFree(s->d_query);
-    if (s->h_hits) (void)hipHostFree(s->h_hits);
-    if (s->h_ix_hits) (void)hipHostFree(s->h_ix_hits);
-    if (s->h_counts) (void)hipHostFree(s->h_counts);
-    if (s->d_hits) (void)hipFree(s->d_hits);
-    if (s->d_hits_n) (void)hipFree(s->d_hits_n);
-    if (s->d_sq) (void)hipFree(s->d_sq);
-    if (s->d_smult) (void)hipFree(s->d_smult);
-    if (s->h_tol) (void)hipHostFree(s->h_tol);
-    if (s->d_tol) (void)hipFree(s->d_tol);
-    if (s->d_tol_big) (void)hipFree(s->d_tol_big);
-    if (s->stream) (void)hipStreamDestroy(s->stream);
-    delete s;
-}
-
 // room for the hits of `rows` corpus rows (every block's region rounds up to whole row groups)
 int staging_size(Staging *s, int64_t rows) {
     const int64_t slots = rows + (int64_t)kQ1MaxBlocks * kStageGroups;
     if (slots <= s->hit_slots) return TVZ_OK;
-    if (s->h_hits) (void)hipHostFree(s->h_hits);
-    s->h_hits = nullptr;
-    s->hit_slots = 0;
-    TVZ_HIP(hipHostMalloc(&s->h_hits, (size_t)slots * 12, hipHostMallocMapped));
-    TVZ_HIP(hipHostGetDevicePointer(reinterpret_cast<void **>(&s->dh_hits), s->h_hits, 0));
-    s->hit_slots = slots;
-    if (s->h_ix_hits) (void)hipHostFree(s->h_ix_hits);
-    s->h_ix_hits = nullptr;
-    s->ix_slots = 0;
     // index lookups: one region of kSubRows hits and one count per sub-index
     const int64_t subs = tvz::ceil_div(std::max<int64_t>(rows, 1), kSubRows);
-    TVZ_HIP(hipHostMalloc(&s->h_ix_hits, (size_t)subs * kSubRows * 12, hipHostMallocMapped));
-    TVZ_HIP(hipHostGetDevicePointer(reinterpret_cast<void **>(&s->dh_ix_hits), s->h_ix_hits, 0));
+    s->hit_slots = 0;
+    s->ix_slots = 0;
+    if (int rc = pinned_alloc(s->hits, slots * 3, true)) return rc;
+    if (int rc = pinned_alloc(s->ix_hits, subs * kSubRows * 3, true)) return rc;
+    if (int rc = pinned_alloc(s->counts, kQ1MaxBlocks + subs, true)) return rc;
+    s->hit_slots = slots;
     s->ix_slots = subs * kSubRows;
-    if (s->h_counts) (void)hipHostFree(s->h_counts);
-    s->h_counts = nullptr;
-    TVZ_HIP(hipHostMalloc(&s->h_counts, (size_t)(kQ1MaxBlocks + subs) * 4, hipHostMallocMapped));
-    TVZ_HIP(hipHostGetDevicePointer(reinterpret_cast<void **>(&s->dh_counts), s->h_counts, 0));
     return TVZ_OK;
 }
 
 int staging_new(tvz_corpus *c, Staging **out) {
     Staging *s = new Staging();
-    struct Guard { Staging *s; ~Guard() { if (s) staging_free(s); } } g{s};
+    struct Guard { Staging *s; ~Guard() { delete s; } } g{s};
     {                                    // single-query lookups: ahead of background index builds
         int least = 0, greatest = 0;
         TVZ_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
         TVZ_HIP(hipStreamCreateWithPriority(&s->stream, hipStreamNonBlocking, greatest));
     }
-    TVZ_HIP(hipHostMalloc(&s->h_query, (size_t)(kQueryStageKeys + 2) * 8, hipHostMallocDefault));
-    TVZ_HIP(hipMalloc(&s->d_query, (size_t)(kQueryStageKeys + 2) * 8));
-    TVZ_HIP(hipMalloc(&s->d_hits_n, sizeof(int32_t)));
-    TVZ_HIP(hipHostMalloc(&s->h_tol, kTolStageBytes, hipHostMallocDefault));
-    TVZ_HIP(hipMalloc(&s->d_tol, kTolStageBytes));
+    if (int rc = pinned_alloc(s->query, kQueryStageKeys + 2, false)) return rc;
+    if (int rc = ensure(s->d_query, kQueryStageKeys + 2, 0)) return rc;
+    if (int rc = ensure(s->d_hits_n, 1, 0)) return rc;
+    if (int rc = pinned_alloc(s->tol, (int64_t)kTolStageBytes, false)) return rc;
+    if (int rc = ensure(s->d_tol, (int64_t)kTolStageBytes, 0)) return rc;
     if (int rc = staging_size(s, c->stage_rows)) return rc;
     g.s = nullptr;
     {
@@ -1013,6 +1010,24 @@ int launch_join(tvz_corpus *c, RowSpan span, bool zero_counts, const double *d_q
     return TVZ_OK;
 }
 
+// the status of the launch just enqueued
+int launched() {
+    TVZ_HIP(hipGetLastError());
+    return TVZ_OK;
+}
+
+// launch(std::integral_constant<int, kth_mode(min_match)>{}): the one place a launch turns min_match into its kernel's
+// MODE.  COUNT = false: the kernel has no count-only form, its callers admit min_match 1..5 only.
+template <bool COUNT = true, typename Launch>
+int by_mode(int32_t min_match, Launch &&launch) {
+    switch (kth_mode(min_match)) {
+    case kModeM2: return launch(std::integral_constant<int, kModeM2>{});
+    case kModeTop5: return launch(std::integral_constant<int, kModeTop5>{});
+    }
+    if constexpr (COUNT) return launch(std::integral_constant<int, kModeCount>{});
+    else return tvz::fail(TVZ_ERR_UNSUPPORTED, "internal: min_match %d without a count-only kernel", (int)min_match);
+}
+
 template <bool HOSTOUT>
 int launch_q1(tvz_corpus *c, RowSpan span, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
               int32_t max_query_len, int32_t min_match, const int32_t *d_exclude_ids,
@@ -1034,16 +1049,12 @@ int launch_q1(tvz_corpus *c, RowSpan span, const double *d_queries, const int64_
                 "single-query sweep: %zu B of dynamic + %d B of static LDS exceed the %d B a gfx950 workgroup can have",
                 lds, kQ1StaticLds, kLdsPerWorkgroup);
     const dim3 grid((unsigned)blocks_x, (unsigned)Q);
-#define TVZ_Q1(MODE)                                                                              \
-    hipLaunchKernelGGL((ts_match_q1_kernel<MODE, HOSTOUT>), grid, dim3(kQ1Block), lds, st, span.p, \
-                       n_rows, c->keys.p, d_queries, d_q_offsets, min_match, d_exclude_ids,          \
-                       exclude_one, cap, d_hits, d_hits_n, ns, s_log2, ho, qv)
-    if (min_match <= 0 || min_match > kTop) TVZ_Q1(kQ1ModeCount);
-    else if (min_match <= 2) TVZ_Q1(kQ1ModeM2);
-    else TVZ_Q1(kQ1ModeTop5);
-#undef TVZ_Q1
-    TVZ_HIP(hipGetLastError());
-    return TVZ_OK;
+    return by_mode(min_match, [&](auto mode) {
+        hipLaunchKernelGGL((ts_match_q1_kernel<mode.value, HOSTOUT>), grid, dim3(kQ1Block), lds, st, span.p, n_rows,
+                           c->keys.p, d_queries, d_q_offsets, min_match, d_exclude_ids, exclude_one, cap, d_hits,
+                           d_hits_n, ns, s_log2, ho, qv);
+        return launched();
+    });
 }
 
 int q1_blocks(int64_t n_rows, int32_t Q) {
@@ -1126,6 +1137,8 @@ int index_subs_per_block(int32_t Q, int n_sub, int32_t max_query_len, bool hosto
 // index lookup of Q queries.  *alone_out = the kernel OWNS the hit counters (one block per query:
 // it stores them; nothing has to be zeroed before).  Otherwise the blocks ADD to the queries'
 // counters, which this zeroes first - or, HOSTOUT, every sub-index writes its own region and count.
+// Callers check index_usable first: min_match >= 1, so min_match > 5 is the only count-only case (the
+// kth fix-up below), and HOSTOUT (tvz_find_duplicates) only ever sees 1..5.
 template <bool HOSTOUT>
 int launch_index(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
                  int32_t max_query_len, int32_t min_match, const int32_t *d_exclude_ids, int32_t exclude_one,
@@ -1138,17 +1151,14 @@ int launch_index(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offs
     if (!HOSTOUT && groups > 1)
         if (int rc = launch_prep(d_hits_n, ns, Q, nullptr, 0, nullptr, 0, st)) return rc;
     const size_t lds = ix_lds_bytes(max_query_len, spb);
-#define TVZ_IX(MODE)                                                                                        \
-    hipLaunchKernelGGL((ts_match_index_kernel<HOSTOUT, MODE>), dim3((unsigned)Q, (unsigned)groups),          \
-                       dim3(kIxBlock), lds, st, ix.dir.p, ix.dir_bits(), ix.ks, ix.post_ptr(), ix.ivid.p, ix.n_main, \
-                       ix.n_sub, spb, d_queries, d_q_offsets, max_query_len, min_match, d_exclude_ids,        \
-                       exclude_one, cap, d_hits, d_hits_n, ns, byval ? *byval : kNoQuery)
-    if (min_match <= 2) TVZ_IX(kIxM2);
-    else if (min_match <= kTop) TVZ_IX(kIxTop5);
-    else if constexpr (!HOSTOUT) TVZ_IX(kIxCount);
-    else return tvz::fail(TVZ_ERR_UNSUPPORTED, "internal: min_match > 5 straight to host memory");
-#undef TVZ_IX
-    TVZ_HIP(hipGetLastError());
+    if (int rc = by_mode<!HOSTOUT>(min_match, [&](auto mode) {
+            hipLaunchKernelGGL((ts_match_index_kernel<HOSTOUT, mode.value>), dim3((unsigned)Q, (unsigned)groups),
+                               dim3(kIxBlock), lds, st, ix.dir.p, ix.dir_bits(), ix.ks, ix.post_ptr(), ix.ivid.p,
+                               ix.n_main, ix.n_sub, spb, d_queries, d_q_offsets, max_query_len, min_match,
+                               d_exclude_ids, exclude_one, cap, d_hits, d_hits_n, ns, byval ? *byval : kNoQuery);
+            return launched();
+        }))
+        return rc;
     if (!HOSTOUT && min_match > kTop) {
         // the hits left with kth = -2 - row (a row of the MAIN table: unchanged since the build, or it
         // would be dead in the index); resolved here, before a delta sweep appends codes of its own table
@@ -1190,14 +1200,12 @@ int launch_index_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q
     // the postings in registers between the passes.
     if (wave) {
         const size_t lds = wq_lds_bytes(max_query_len);
-#define TVZ_WQK(MODE)                                                                                        \
-    hipLaunchKernelGGL((ts_match_wq_topk_kernel<MODE>), dim3((unsigned)Q), dim3(64), lds, st, ix.dir.p,        \
-                       ix.dir_bits(), ix.post_ptr(), ix.ivid.p, ix.n_main, d_queries, d_q_offsets, Q, max_query_len, \
-                       min_match, d_exclude_ids, cap, k, d_block)
-        if (min_match <= 2) TVZ_WQK(kIxM2); else TVZ_WQK(kIxTop5);
-#undef TVZ_WQK
-        TVZ_HIP(hipGetLastError());
-        return TVZ_OK;
+        return by_mode<false>(min_match, [&](auto mode) {
+            hipLaunchKernelGGL((ts_match_wq_topk_kernel<mode.value>), dim3((unsigned)Q), dim3(64), lds, st, ix.dir.p,
+                               ix.dir_bits(), ix.post_ptr(), ix.ivid.p, ix.n_main, d_queries, d_q_offsets, Q,
+                               max_query_len, min_match, d_exclude_ids, cap, k, d_block);
+            return launched();
+        });
     }
     // Two queries per block - their directory probes share the block's one probe phase (profiles/r4_pair.txt) -
     // when the LDS of both still leaves four blocks on a CU, and when half as many blocks still fill the chip
@@ -1213,15 +1221,15 @@ int launch_index_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q
                       lds2 + 256 <= (size_t)kLdsPerWorkgroup / 4 && !no_pair;   // (+ the body's static LDS)
     const size_t lds = pair ? lds2 : ix_lds_bytes(max_query_len, ix.n_sub, true);
     const unsigned grid = pair ? (unsigned)((Q + 1) / 2) : (unsigned)Q;
-#define TVZ_IXK(MODE, NQ)                                                                                   \
-    hipLaunchKernelGGL((ts_match_index_topk_kernel<MODE, NQ>), dim3(grid), dim3(kIxBlock), lds, st,           \
-                       ix.dir.p, ix.dir_bits(), ix.ks, ix.post_ptr(), ix.ivid.p, ix.n_main, ix.n_sub, d_queries,   \
-                       d_q_offsets, Q, max_query_len, min_match, d_exclude_ids, cap, k, d_block)
-    if (pair) { if (min_match <= 2) TVZ_IXK(kIxM2, 2); else TVZ_IXK(kIxTop5, 2); }
-    else { if (min_match <= 2) TVZ_IXK(kIxM2, 1); else TVZ_IXK(kIxTop5, 1); }
+    return by_mode<false>(min_match, [&](auto mode) {
+#define TVZ_IXK(NQ)                                                                                            \
+    hipLaunchKernelGGL((ts_match_index_topk_kernel<mode.value, NQ>), dim3(grid), dim3(kIxBlock), lds, st, ix.dir.p, \
+                       ix.dir_bits(), ix.ks, ix.post_ptr(), ix.ivid.p, ix.n_main, ix.n_sub, d_queries, d_q_offsets, Q, \
+                       max_query_len, min_match, d_exclude_ids, cap, k, d_block)
+        if (pair) TVZ_IXK(2); else TVZ_IXK(1);
 #undef TVZ_IXK
-    TVZ_HIP(hipGetLastError());
-    return TVZ_OK;
+        return launched();
+    });
 }
 
 int launch_match_short(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
@@ -1549,17 +1557,17 @@ static int tvz_corpus_create_impl(tvz_corpus **out, int device) {
 #define TVZ_IX_ATTR(H, M)                                                                          \
     TVZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ts_match_index_kernel<H, M>),           \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, kIxMaxLds))
-    TVZ_IX_ATTR(false, kIxM2); TVZ_IX_ATTR(false, kIxTop5); TVZ_IX_ATTR(false, kIxCount);
-    TVZ_IX_ATTR(true, kIxM2); TVZ_IX_ATTR(true, kIxTop5);
+    TVZ_IX_ATTR(false, kModeM2); TVZ_IX_ATTR(false, kModeTop5); TVZ_IX_ATTR(false, kModeCount);
+    TVZ_IX_ATTR(true, kModeM2); TVZ_IX_ATTR(true, kModeTop5);
 #undef TVZ_IX_ATTR
 #define TVZ_IXK_ATTR(M, NQ)                                                                       \
     TVZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ts_match_index_topk_kernel<M, NQ>),    \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, kIxMaxLds))
-    TVZ_IXK_ATTR(kIxM2, 1); TVZ_IXK_ATTR(kIxTop5, 1); TVZ_IXK_ATTR(kIxM2, 2); TVZ_IXK_ATTR(kIxTop5, 2);
+    TVZ_IXK_ATTR(kModeM2, 1); TVZ_IXK_ATTR(kModeTop5, 1); TVZ_IXK_ATTR(kModeM2, 2); TVZ_IXK_ATTR(kModeTop5, 2);
 #undef TVZ_IXK_ATTR
-    TVZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ts_match_wq_topk_kernel<kIxM2>),
+    TVZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ts_match_wq_topk_kernel<kModeM2>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)wq_lds_bytes(kWqMaxLen)));
-    TVZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ts_match_wq_topk_kernel<kIxTop5>),
+    TVZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ts_match_wq_topk_kernel<kModeTop5>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)wq_lds_bytes(kWqMaxLen)));
     TVZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bk_slice_build_kernel),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBkBuildLds));
@@ -1578,9 +1586,9 @@ static int tvz_corpus_create_impl(tvz_corpus **out, int device) {
 #define TVZ_Q1_ATTR(M, H)                                                                     \
     TVZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ts_match_q1_kernel<M, H>),       \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, q1max))
-    TVZ_Q1_ATTR(kQ1ModeM2, false); TVZ_Q1_ATTR(kQ1ModeM2, true);
-    TVZ_Q1_ATTR(kQ1ModeTop5, false); TVZ_Q1_ATTR(kQ1ModeTop5, true);
-    TVZ_Q1_ATTR(kQ1ModeCount, false); TVZ_Q1_ATTR(kQ1ModeCount, true);
+    TVZ_Q1_ATTR(kModeM2, false); TVZ_Q1_ATTR(kModeM2, true);
+    TVZ_Q1_ATTR(kModeTop5, false); TVZ_Q1_ATTR(kModeTop5, true);
+    TVZ_Q1_ATTR(kModeCount, false); TVZ_Q1_ATTR(kModeCount, true);
 #undef TVZ_Q1_ATTR
     // default reservation: 64 Ki rows / 2 Mi keys (16 MiB) and two single-query stagings, so a
     // fresh service handles its first uploads without allocating on the hot calls
@@ -1605,27 +1613,13 @@ static int tvz_corpus_destroy_impl(tvz_corpus *c) {
         std::unique_lock<std::shared_mutex> lk(c->mu);
         wait_no_build(c, lk);
         if (c->mstream) (void)drain(c);
-        for (Staging *s : c->all_staging) staging_free(s);
+        for (Staging *s : c->all_staging) delete s;
         c->all_staging.clear();
         c->free_staging.clear();
         for (RingSlot &s : c->ring) {
             if (s.h) (void)hipHostFree(s.h);
             if (s.ev) (void)hipEventDestroy(s.ev);
         }
-        if (c->keys.p) (void)hipFree(c->keys.p);
-        if (c->rows.p) (void)hipFree(c->rows.p);
-        for (IndexBuf &b : c->ix.buf) {
-            if (b.dir.p) (void)hipFree(b.dir.p);
-            if (b.post.p) (void)hipFree(b.post.p);
-            if (b.ivid.p) (void)hipFree(b.ivid.p);
-            if (b.drows.p) (void)hipFree(b.drows.p);
-        }
-        if (c->ix.fillc.p) (void)hipFree(c->ix.fillc.p);
-        if (c->ix.pkeys.p) (void)hipFree(c->ix.pkeys.p);
-        if (c->ix.prows.p) (void)hipFree(c->ix.prows.p);
-        if (c->ix.pcnt.p) (void)hipFree(c->ix.pcnt.p);
-        if (c->ix.snap_rows.p) (void)hipFree(c->ix.snap_rows.p);
-        if (c->ix.dead_rows.p) (void)hipFree(c->ix.dead_rows.p);
         if (c->ix.info) (void)hipFree(c->ix.info);
         if (c->ix.h_info) (void)hipHostFree(c->ix.h_info);
         if (c->ix.h_swap_rows) (void)hipHostFree(c->ix.h_swap_rows);
@@ -1983,9 +1977,90 @@ namespace {
 
 struct Hit { int32_t vid, cnt, kth; };
 
-// tvz_find_duplicates of a query of up to 4,095 timestamps with min_match <= 5: ONE launch + ONE synchronisation, the
-// kernel writes its hits to pinned host memory; a query of up to 440 timestamps travels in the kernel arguments (no
-// copy at all).  Leaves the hits at the start of s->h_hits, *n_hits of them.
+// the argument checks of tvz_find_duplicates and tvz_find_duplicates_tol
+int check_find_args(const tvz_corpus *c, const double *h_query, int64_t n, int64_t cap, const int32_t *h_out_ids,
+                    const int32_t *h_out_counts, const int64_t *n_out) {
+    TVZ_REQUIRE(c != nullptr && n_out != nullptr, "NULL argument");
+    TVZ_REQUIRE(n >= 0 && cap >= 0 && cap <= INT32_MAX, "bad size");
+    TVZ_REQUIRE(n == 0 || h_query, "h_query is NULL");
+    TVZ_REQUIRE(cap == 0 || (h_out_ids && h_out_counts), "NULL outputs");
+    TVZ_REQUIRE(n <= INT32_MAX, "query too long");
+    return TVZ_OK;
+}
+
+// a staging checked out for one call (staging_get fills s); it goes back on every exit
+struct StagingLease {
+    tvz_corpus *c;
+    Staging *s = nullptr;
+    ~StagingLease() { if (s) staging_put(c, s); }
+};
+
+// The output rules of the single-query calls: hits[0, n_have) sorted by (video_id, count, kth), the first `cap` of
+// them written out, and *n_out = n_found - the true count, so that a truncated caller can retry with cap >= *n_out.
+void copy_out(Hit *hits, int64_t n_have, int64_t n_found, int64_t cap, int32_t *h_out_ids, int32_t *h_out_counts,
+              int32_t *h_out_kth, int64_t *n_out) {
+    std::sort(hits, hits + n_have, [](const Hit &a, const Hit &b) {
+        if (a.vid != b.vid) return a.vid < b.vid;
+        if (a.cnt != b.cnt) return a.cnt < b.cnt;
+        return a.kth < b.kth;
+    });
+    const int64_t w = std::min<int64_t>(n_have, cap);
+    for (int64_t i = 0; i < w; ++i) {
+        h_out_ids[i] = hits[i].vid;
+        h_out_counts[i] = hits[i].cnt;
+        if (h_out_kth) h_out_kth[i] = hits[i].kth;
+    }
+    *n_out = n_found;
+}
+
+// The pinned single-query sweep of tvz_find_duplicates (find_pinned) and tvz_find_duplicates_tol: the kernels write
+// their hits into the staging's pinned, mapped memory, and ONE synchronisation waits for all of them.  For a corpus
+// of n_rows > 0 rows, launch(n_rows, blocks, region) enqueues them on s->stream - under the shared lock, behind every
+// mutation that has returned - and says where the sweep's hits land: `blocks` regions of `region` hits, counted in
+// s->counts.  s->busy (drain() and its kin wait on it) is set just before the launch and cleared after the
+// synchronisation or on any failure; the synchronisation is made outside the lock, so an upsert never waits behind
+// it.  Leaves the sweep's hits compacted at the start of s->hits, *n_hits of them; `what` names the call in errors.
+template <typename Launch>
+int pinned_sweep(tvz_corpus *c, Staging *s, const char *what, Launch &&launch, int64_t *n_hits) {
+    int blocks = 0, region = 0;
+    {
+        struct Busy { Staging *s; ~Busy() { s->busy.store(0, std::memory_order_release); } } busy{s};
+        {
+            std::shared_lock<std::shared_mutex> lk(c->mu);
+            const int64_t n_rows = (int64_t)c->h_rows.size();
+            if (n_rows) {
+                if (n_rows > c->stage_rows || n_rows + (int64_t)kQ1MaxBlocks * kStageGroups > s->hit_slots ||
+                    n_rows > s->ix_slots) {
+                    // the corpus outgrew its reservation (see tvz_corpus_reserve): grow this staging
+                    if (int rc = staging_size(s, std::max<int64_t>(2 * n_rows, c->stage_rows))) return rc;
+                }
+                if (int rc = wait_mutations(c, s->stream)) return rc;
+                s->busy.store(1, std::memory_order_release);
+                if (int rc = launch(n_rows, blocks, region)) return rc;
+            }
+        }
+        // (polling the per-block counts from the host instead was tried: it needs a system-scope
+        // release per block, which saved 1.5 us at 5k rows and cost 60 us at 100k)
+        const hipError_t e = hipStreamSynchronize(s->stream);
+        if (e != hipSuccess) return tvz::fail(TVZ_ERR_HIP, "%ssingle-query match failed: %s", what, hipGetErrorString(e));
+    }
+    // compact the per-block regions in place (block order; sorted by the caller anyway)
+    Hit *hh = reinterpret_cast<Hit *>(s->hits.h);
+    int64_t w = 0;
+    for (int b = 0; b < blocks; ++b) {
+        const int32_t nb = s->counts.h[b];
+        if (nb < 0) return tvz::fail(TVZ_ERR_INVALID, "internal: %squery table overflow", what);
+        const Hit *src = hh + (int64_t)b * region;
+        if (src != hh + w) memmove(hh + w, src, (size_t)nb * sizeof(Hit));
+        w += nb;
+    }
+    *n_hits = w;
+    return TVZ_OK;
+}
+
+// tvz_find_duplicates of a query of up to 4,095 timestamps with min_match <= 5: ONE launch + ONE synchronisation
+// (pinned_sweep); a query of up to 440 timestamps travels in the kernel arguments (no copy at all).  Leaves the hits
+// at the start of s->hits, *n_hits of them.
 int find_pinned(tvz_corpus *c, Staging *s, const double *h_query, int64_t n, int32_t min_match, int32_t excl,
                 int64_t *n_hits) {
     *n_hits = 0;
@@ -1996,101 +2071,67 @@ int find_pinned(tvz_corpus *c, Staging *s, const double *h_query, int64_t n, int
         qv.pad = 0;
         if (n) memcpy(qv.k, h_query, (size_t)n * 8);
     } else {
-        s->h_query[0] = 0;
-        s->h_query[1] = n;
-        memcpy(s->h_query + 2, h_query, (size_t)n * 8);
-        TVZ_HIP(hipMemcpyAsync(s->d_query, s->h_query, (size_t)(n + 2) * 8, hipMemcpyHostToDevice, s->stream));
+        s->query.h[0] = 0;
+        s->query.h[1] = n;
+        memcpy(s->query.h + 2, h_query, (size_t)n * 8);
+        TVZ_HIP(hipMemcpyAsync(s->d_query.p, s->query.h, (size_t)(n + 2) * 8, hipMemcpyHostToDevice, s->stream));
     }
+    const double *dq = by_value ? nullptr : reinterpret_cast<const double *>(s->d_query.p + 2);
+    const int64_t *dqo = by_value ? nullptr : s->d_query.p;
     // with an index: rows unchanged since its build are answered by the lookup kernel (one
     // block), rows in the delta table by the sweep - both write to pinned host memory, one
     // synchronisation for the two.  A query the lookup refuses (> 4 G postings) is swept.
     for (int attempt = 0; attempt < 2; ++attempt) {
-        int blocks = 0, region = 0, n_sub = 0;
-        {
-            // drain() waits while a sweep of this staging is in flight: set at its launch, cleared once it is done
-            // (or failed to launch)
-            struct Busy { Staging *s; ~Busy() { s->busy.store(0, std::memory_order_release); } } busy{s};
-            {
-                std::shared_lock<std::shared_mutex> lk(c->mu);
-                const int64_t n_rows = (int64_t)c->h_rows.size();
-                if (n_rows) {
-                    if (n_rows > c->stage_rows || n_rows + (int64_t)kQ1MaxBlocks * kStageGroups > s->hit_slots ||
-                        n_rows > s->ix_slots) {
-                        // the corpus outgrew its reservation (see tvz_corpus_reserve): grow this staging
-                        if (int rc = staging_size(s, std::max<int64_t>(2 * n_rows, c->stage_rows))) return rc;
-                    }
-                    if (int rc = wait_mutations(c, s->stream)) return rc;
-                    const double *dq = by_value ? nullptr : reinterpret_cast<const double *>(s->d_query + 2);
-                    const int64_t *dqo = by_value ? nullptr : s->d_query;
-                    RowSpan span{c->rows.p, n_rows};
-                    s->busy.store(1, std::memory_order_release);
-                    bool fused = false;
-                    if (attempt == 0 && index_usable(c, min_match)) {
-                        const IndexBuf &ib = c->ix.now();
-                        n_sub = ib.n_sub;
-                        s->gen = c->ix.cur;
-                        span = RowSpan{ib.drows.p, c->ix.n_delta};
-                        const int s_log2 = q1_slots_log2((int32_t)n);
-                        const size_t lds = std::max(ix_lds_bytes((int32_t)n, 1), q1_lds_bytes(s_log2));
-                        if (span.n && lds <= (size_t)kIxMaxLds) {
-                            // lookup + delta sweep in ONE launch (the streaming driver's call: its own row is
-                            // always in the delta table)
-                            fused = true;
-                            constexpr int kFG = kIxBlock / kGroup;                // row groups per sweep block
-                            blocks = (int)std::max<int64_t>(1, std::min<int64_t>(tvz::ceil_div(span.n, kFG), kQ1MaxBlocks));
-                            region = (int)(tvz::ceil_div(span.n, (int64_t)blocks * kFG) * kFG);
-                            const HostOut ho{s->dh_hits, s->dh_counts, region};
-                            static const QByVal kNoQuery = {};
-#define TVZ_FUSED(TOP5)                                                                                               \
-    hipLaunchKernelGGL((ts_find_fused_kernel<TOP5>), dim3((unsigned)(n_sub + blocks)), dim3(kIxBlock), lds, s->stream, \
-                       ib.dir.p, ib.dir_bits(), ib.ks, ib.post_ptr(), ib.ivid.p, ib.n_main, ib.n_sub, 1, n_sub, dq, dqo,       \
-                       (int32_t)n, min_match, excl, s->dh_ix_hits, s->dh_counts + kQ1MaxBlocks, span.p, span.n,         \
-                       c->keys.p, s_log2, ho, by_value ? qv : kNoQuery)
-                            if (min_match <= 2) TVZ_FUSED(false); else TVZ_FUSED(true);
-#undef TVZ_FUSED
-                            if (hipGetLastError() != hipSuccess) return tvz::fail(TVZ_ERR_HIP, "fused lookup launch failed");
-                        } else if (int rc = launch_index<true>(c, dq, dqo, 1, (int32_t)n, min_match, nullptr, excl, 0,
-                                                               s->dh_ix_hits, s->dh_counts + kQ1MaxBlocks, 1, s->stream,
-                                                               by_value ? &qv : nullptr)) {
-                            return rc;
-                        }
-                    }
-                    if (span.n && !fused) {
-                        blocks = q1_blocks(span.n, 1);
-                        region = (int)(tvz::ceil_div(span.n, (int64_t)blocks * kQ1Groups) * kQ1Groups);
-                        const HostOut ho{s->dh_hits, s->dh_counts, region};
-                        if (int rc = launch_q1<true>(c, span, dq, dqo, 1, (int32_t)n, min_match, nullptr, excl, 0,
-                                                     nullptr, nullptr, 1, blocks, ho, s->stream,
-                                                     by_value ? &qv : nullptr))
-                            return rc;
-                    }
+        int n_sub = 0;
+        auto launch = [&](int64_t n_rows, int &blocks, int &region) -> int {
+            RowSpan span{c->rows.p, n_rows};
+            if (attempt == 0 && index_usable(c, min_match)) {
+                const IndexBuf &ib = c->ix.now();
+                n_sub = ib.n_sub;
+                s->gen = c->ix.cur;
+                span = RowSpan{ib.drows.p, c->ix.n_delta};
+                const int s_log2 = q1_slots_log2((int32_t)n);
+                const size_t lds = std::max(ix_lds_bytes((int32_t)n, 1), q1_lds_bytes(s_log2));
+                if (span.n && lds <= (size_t)kIxMaxLds) {
+                    // lookup + delta sweep in ONE launch (the streaming driver's call: its own row is
+                    // always in the delta table)
+                    constexpr int kFG = kIxBlock / kGroup;                // row groups per sweep block
+                    blocks = (int)std::max<int64_t>(1, std::min<int64_t>(tvz::ceil_div(span.n, kFG), kQ1MaxBlocks));
+                    region = (int)(tvz::ceil_div(span.n, (int64_t)blocks * kFG) * kFG);
+                    const HostOut ho{s->hits.d, s->counts.d, region};
+                    static const QByVal kNoQuery = {};
+                    return by_mode<false>(min_match, [&](auto mode) -> int {
+                        hipLaunchKernelGGL((ts_find_fused_kernel<mode.value == kModeTop5>), dim3((unsigned)(n_sub + blocks)),
+                                           dim3(kIxBlock), lds, s->stream, ib.dir.p, ib.dir_bits(), ib.ks, ib.post_ptr(),
+                                           ib.ivid.p, ib.n_main, ib.n_sub, 1, n_sub, dq, dqo, (int32_t)n, min_match, excl,
+                                           s->ix_hits.d, s->counts.d + kQ1MaxBlocks, span.p, span.n, c->keys.p, s_log2,
+                                           ho, by_value ? qv : kNoQuery);
+                        if (hipGetLastError() != hipSuccess) return tvz::fail(TVZ_ERR_HIP, "fused lookup launch failed");
+                        return TVZ_OK;
+                    });
                 }
+                if (int rc = launch_index<true>(c, dq, dqo, 1, (int32_t)n, min_match, nullptr, excl, 0, s->ix_hits.d,
+                                                s->counts.d + kQ1MaxBlocks, 1, s->stream, by_value ? &qv : nullptr))
+                    return rc;
             }
-            // (polling the per-block counts from the host instead was tried: it needs a system-scope
-            // release per block, which saved 1.5 us at 5k rows and cost 60 us at 100k)
-            const hipError_t e = hipStreamSynchronize(s->stream);
-            if (e != hipSuccess) return tvz::fail(TVZ_ERR_HIP, "single-query match failed: %s", hipGetErrorString(e));
-        }
+            if (!span.n) return TVZ_OK;
+            blocks = q1_blocks(span.n, 1);
+            region = (int)(tvz::ceil_div(span.n, (int64_t)blocks * kQ1Groups) * kQ1Groups);
+            const HostOut ho{s->hits.d, s->counts.d, region};
+            return launch_q1<true>(c, span, dq, dqo, 1, (int32_t)n, min_match, nullptr, excl, 0, nullptr, nullptr, 1,
+                                   blocks, ho, s->stream, by_value ? &qv : nullptr);
+        };
+        if (int rc = pinned_sweep(c, s, "", launch, n_hits)) return rc;
         bool refused = false;
-        for (int b = 0; b < n_sub; ++b) refused = refused || s->h_counts[kQ1MaxBlocks + b] < 0;
+        for (int b = 0; b < n_sub; ++b) refused = refused || s->counts.h[kQ1MaxBlocks + b] < 0;
         if (refused) continue;                                        // sweep everything instead
-        // compact the per-block regions in place (block order; sorted by the caller anyway)
-        Hit *hh = reinterpret_cast<Hit *>(s->h_hits);
-        int64_t w = 0;
-        for (int b = 0; b < blocks; ++b) {
-            const int32_t nb = s->h_counts[b];
-            if (nb < 0) return tvz::fail(TVZ_ERR_INVALID, "internal: query table overflow");
-            const Hit *src = hh + (int64_t)b * region;
-            if (src != hh + w) memmove(hh + w, src, (size_t)nb * sizeof(Hit));
-            w += nb;
-        }
+        Hit *hh = reinterpret_cast<Hit *>(s->hits.h);
         for (int b = 0; b < n_sub; ++b) {                              // the lookup's regions, one per sub-index
-            const int64_t nb = std::min<int64_t>(s->h_counts[kQ1MaxBlocks + b], kSubRows);
-            if (nb) memcpy(hh + w, reinterpret_cast<const Hit *>(s->h_ix_hits) + (int64_t)b * kSubRows,
+            const int64_t nb = std::min<int64_t>(s->counts.h[kQ1MaxBlocks + b], kSubRows);
+            if (nb) memcpy(hh + *n_hits, reinterpret_cast<const Hit *>(s->ix_hits.h) + (int64_t)b * kSubRows,
                            (size_t)nb * sizeof(Hit));
-            w += nb;
+            *n_hits += nb;
         }
-        *n_hits = w;
         break;
     }
     return TVZ_OK;
@@ -2102,60 +2143,48 @@ int find_pinned(tvz_corpus *c, Staging *s, const double *h_query, int64_t n, int
 int find_device(tvz_corpus *c, Staging *s, const double *h_query, int64_t n, int32_t min_match, int32_t excl,
                 int64_t cap, std::vector<Hit> &hits, int64_t *n_found) {
     const int64_t want = std::max<int64_t>(cap, 1);
-    if (want > s->d_hit_slots) {
-        if (s->d_hits) (void)hipFree(s->d_hits);
-        s->d_hits = nullptr;
-        s->d_hit_slots = 0;
-        TVZ_HIP(hipMalloc(&s->d_hits, (size_t)want * 12));
-        s->d_hit_slots = want;
-    }
+    if (int rc = ensure(s->d_hits, want * 3, 0)) return rc;
     std::vector<int64_t> uq;
     std::vector<int32_t> mult;
     const bool longq = n > kMaxQueryLen;
-    int64_t *d_q = s->d_query;
+    int64_t *d_q = s->d_query.p;
     if (longq) {
         // sorted distinct keys + multiplicities, searched per row key; the raw query (for the
         // fix-up walk) travels behind them
         sorted_distinct(h_query, n, uq, mult);
         const int64_t m = (int64_t)uq.size();
-        if (m + n + 3 > s->sq_cap) {
-            if (s->d_sq) (void)hipFree(s->d_sq);
-            if (s->d_smult) (void)hipFree(s->d_smult);
-            s->d_sq = nullptr; s->d_smult = nullptr; s->sq_cap = 0;
-            TVZ_HIP(hipMalloc(&s->d_sq, (size_t)(m + n + 3) * 8));
-            TVZ_HIP(hipMalloc(&s->d_smult, (size_t)(m + 1) * 4));
-            s->sq_cap = m + n + 3;
-        }
-        d_q = s->d_sq + m;                                   // {0, n} + raw query
+        if (int rc = ensure(s->d_sq, m + n + 3, 0)) return rc;
+        if (int rc = ensure(s->d_smult, m + 1, 0)) return rc;
+        d_q = s->d_sq.p + m;                                 // {0, n} + raw query
         const int64_t qoff[2] = {0, n};
         TVZ_HIP(hipMemcpyAsync(d_q, qoff, 16, hipMemcpyHostToDevice, s->stream));
         TVZ_HIP(hipMemcpyAsync(d_q + 2, h_query, (size_t)n * 8, hipMemcpyHostToDevice, s->stream));
         if (m) {
-            TVZ_HIP(hipMemcpyAsync(s->d_sq, uq.data(), (size_t)m * 8, hipMemcpyHostToDevice, s->stream));
-            TVZ_HIP(hipMemcpyAsync(s->d_smult, mult.data(), (size_t)m * 4, hipMemcpyHostToDevice, s->stream));
+            TVZ_HIP(hipMemcpyAsync(s->d_sq.p, uq.data(), (size_t)m * 8, hipMemcpyHostToDevice, s->stream));
+            TVZ_HIP(hipMemcpyAsync(s->d_smult.p, mult.data(), (size_t)m * 4, hipMemcpyHostToDevice, s->stream));
         }
     } else {
-        s->h_query[0] = 0;
-        s->h_query[1] = n;
-        if (n) memcpy(s->h_query + 2, h_query, (size_t)n * 8);
-        TVZ_HIP(hipMemcpyAsync(s->d_query, s->h_query, (size_t)(n + 2) * 8, hipMemcpyHostToDevice, s->stream));
+        s->query.h[0] = 0;
+        s->query.h[1] = n;
+        if (n) memcpy(s->query.h + 2, h_query, (size_t)n * 8);
+        TVZ_HIP(hipMemcpyAsync(s->d_query.p, s->query.h, (size_t)(n + 2) * 8, hipMemcpyHostToDevice, s->stream));
     }
     {
         std::shared_lock<std::shared_mutex> lk(c->mu);
         const int64_t n_rows = (int64_t)c->h_rows.size();
         if (int rc = wait_mutations(c, s->stream)) return rc;
-        if (int rc = launch_prep(s->d_hits_n, 1, 1, nullptr, 0, nullptr, 0, s->stream)) return rc;
+        if (int rc = launch_prep(s->d_hits_n.p, 1, 1, nullptr, 0, nullptr, 0, s->stream)) return rc;
         if (n_rows) {
             if (longq) {
                 hipLaunchKernelGGL(ts_match_longq_kernel, dim3((unsigned)tvz::ceil_div(n_rows, kGroupsPerBlock)),
-                                   dim3(kBlock), 0, s->stream, c->rows.p, n_rows, c->keys.p, s->d_sq,
-                                   s->d_smult, (int32_t)uq.size(), min_match, -1, (int32_t)want, s->d_hits,
-                                   s->d_hits_n, static_cast<const int32_t *>(nullptr), static_cast<const int32_t *>(nullptr));
+                                   dim3(kBlock), 0, s->stream, c->rows.p, n_rows, c->keys.p, s->d_sq.p,
+                                   s->d_smult.p, (int32_t)uq.size(), min_match, -1, (int32_t)want, s->d_hits.p,
+                                   s->d_hits_n.p, static_cast<const int32_t *>(nullptr), static_cast<const int32_t *>(nullptr));
                 TVZ_HIP(hipGetLastError());
                 if (min_match > 0) {
                     hipLaunchKernelGGL(ts_kth_fixup_kernel, dim3(1), dim3(kBlock), 0, s->stream, c->rows.p,
                                        c->keys.p, reinterpret_cast<const double *>(d_q + 2), d_q, min_match,
-                                       (int32_t)want, s->d_hits, s->d_hits_n, 1);
+                                       (int32_t)want, s->d_hits.p, s->d_hits_n.p, 1);
                     TVZ_HIP(hipGetLastError());
                 }
             } else {
@@ -2163,7 +2192,7 @@ int find_device(tvz_corpus *c, Staging *s, const double *h_query, int64_t n, int
                 // count-only pass B + the kth fix-up walk and a sweep of the delta table, else the single-query
                 // sweep; the fix-ups are part of those paths
                 if (int rc = launch_match_short(c, reinterpret_cast<const double *>(d_q + 2), d_q, 1, (int32_t)n, min_match,
-                                                nullptr, (int32_t)want, s->d_hits, s->d_hits_n, 1, nullptr, 0,
+                                                nullptr, (int32_t)want, s->d_hits.p, s->d_hits_n.p, 1, nullptr, 0,
                                                 TVZ_ALGO_AUTO, s->stream))
                     return rc;
             }
@@ -2171,12 +2200,12 @@ int find_device(tvz_corpus *c, Staging *s, const double *h_query, int64_t n, int
         if (int rc = record(c, s->stream)) return rc;
     }
     int32_t h_n = 0;
-    TVZ_HIP(hipMemcpyAsync(&h_n, s->d_hits_n, 4, hipMemcpyDeviceToHost, s->stream));
+    TVZ_HIP(hipMemcpyAsync(&h_n, s->d_hits_n.p, 4, hipMemcpyDeviceToHost, s->stream));
     TVZ_HIP(hipStreamSynchronize(s->stream));   // also: uq / mult / h_query were read by now
     *n_found = h_n;
     hits.resize((size_t)std::min<int64_t>(h_n, want));
     if (!hits.empty()) {
-        TVZ_HIP(hipMemcpyAsync(hits.data(), s->d_hits, hits.size() * 12, hipMemcpyDeviceToHost, s->stream));
+        TVZ_HIP(hipMemcpyAsync(hits.data(), s->d_hits.p, hits.size() * 12, hipMemcpyDeviceToHost, s->stream));
         TVZ_HIP(hipStreamSynchronize(s->stream));
     }
     if (excl >= 0) {
@@ -2193,42 +2222,21 @@ static int tvz_find_duplicates_impl(tvz_corpus *c, const double *h_query, int64_
                                    int32_t min_match, int32_t exclude_id, int64_t cap,
                                    int32_t *h_out_ids, int32_t *h_out_counts, int32_t *h_out_kth,
                                    int64_t *n_out) {
-    TVZ_REQUIRE(c != nullptr && n_out != nullptr, "NULL argument");
-    TVZ_REQUIRE(n >= 0 && cap >= 0 && cap <= INT32_MAX, "bad size");
-    TVZ_REQUIRE(n == 0 || h_query, "h_query is NULL");
-    TVZ_REQUIRE(cap == 0 || (h_out_ids && h_out_counts), "NULL outputs");
-    TVZ_REQUIRE(n <= INT32_MAX, "query too long");
+    if (int rc = check_find_args(c, h_query, n, cap, h_out_ids, h_out_counts, n_out)) return rc;
     DeviceGuard dg(c->device);
-    Staging *s = nullptr;
-    if (int rc = staging_get(c, &s)) return rc;
-    struct Put { tvz_corpus *c; Staging *s; ~Put() { staging_put(c, s); } } put{c, s};
+    StagingLease lease{c};
+    if (int rc = staging_get(c, &lease.s)) return rc;
     const int32_t excl = exclude_id >= 0 ? exclude_id : -1;
-    std::vector<Hit> dev_hits;             // only the rare paths use it
-    Hit *hits = nullptr;
     int64_t n_found = 0;                   // hits the device reported (before the cap)
-    int64_t n_have = 0;                    // hits available in `hits`
     if (n <= kMaxQueryLen && min_match <= kTop) {
-        if (int rc = find_pinned(c, s, h_query, n, min_match, excl, &n_found)) return rc;
-        hits = reinterpret_cast<Hit *>(s->h_hits);
-        n_have = n_found;
+        if (int rc = find_pinned(c, lease.s, h_query, n, min_match, excl, &n_found)) return rc;
+        copy_out(reinterpret_cast<Hit *>(lease.s->hits.h), n_found, n_found, cap, h_out_ids, h_out_counts, h_out_kth,
+                 n_out);
     } else {
-        if (int rc = find_device(c, s, h_query, n, min_match, excl, cap, dev_hits, &n_found)) return rc;
-        hits = dev_hits.data();
-        n_have = (int64_t)dev_hits.size();
+        std::vector<Hit> hits;             // only the rare paths use it
+        if (int rc = find_device(c, lease.s, h_query, n, min_match, excl, cap, hits, &n_found)) return rc;
+        copy_out(hits.data(), (int64_t)hits.size(), n_found, cap, h_out_ids, h_out_counts, h_out_kth, n_out);
     }
-    std::sort(hits, hits + n_have, [](const Hit &a, const Hit &b) {
-        if (a.vid != b.vid) return a.vid < b.vid;
-        if (a.cnt != b.cnt) return a.cnt < b.cnt;
-        return a.kth < b.kth;
-    });
-    const int64_t w = std::min<int64_t>(n_have, cap);
-    for (int64_t i = 0; i < w; ++i) {
-        h_out_ids[i] = hits[i].vid;
-        h_out_counts[i] = hits[i].cnt;
-        if (h_out_kth) h_out_kth[i] = hits[i].kth;
-    }
-    // truncated: report the true count so the caller can retry with cap >= *n_out
-    *n_out = n_found;
     return TVZ_OK;
 }
 
@@ -2330,23 +2338,15 @@ int launch_tol(tvz_corpus *c, int64_t n_rows, const double *sv, const int32_t *s
     TVZ_REQUIRE(lds + kQ1Stage * 12 + 64 <= (size_t)kLdsPerWorkgroup, "tolerant sweep: %zu B of LDS exceed a gfx950 workgroup's",
                 lds);
     const dim3 grid((unsigned)blocks_x, (unsigned)Q);
-#define TVZ_TOL(MODE, LDSQ)                                                                                         \
-    hipLaunchKernelGGL((ts_match_tol_kernel<MODE, HOSTOUT, LDSQ>), grid, dim3(kTolBlock), lds, st, c->rows.p, n_rows, \
-                       c->keys.p, sv, sp, q_offsets, qm, m_one, lds_keys, tol, min_match, d_exclude_ids, exclude_one,  \
-                       cap, d_hits, d_hits_n, ho)
-    const int mode = (min_match <= 0 || min_match > kTop) ? kTolModeCount : (min_match <= 2 ? kTolModeM2 : kTolModeTop5);
-    if (lds_keys > 0) {
-        if (mode == kTolModeM2) TVZ_TOL(kTolModeM2, true);
-        else if (mode == kTolModeTop5) TVZ_TOL(kTolModeTop5, true);
-        else TVZ_TOL(kTolModeCount, true);
-    } else {
-        if (mode == kTolModeM2) TVZ_TOL(kTolModeM2, false);
-        else if (mode == kTolModeTop5) TVZ_TOL(kTolModeTop5, false);
-        else TVZ_TOL(kTolModeCount, false);
-    }
+    return by_mode(min_match, [&](auto mode) {
+#define TVZ_TOL(LDSQ)                                                                                                 \
+    hipLaunchKernelGGL((ts_match_tol_kernel<mode.value, HOSTOUT, LDSQ>), grid, dim3(kTolBlock), lds, st, c->rows.p,   \
+                       n_rows, c->keys.p, sv, sp, q_offsets, qm, m_one, lds_keys, tol, min_match, d_exclude_ids,      \
+                       exclude_one, cap, d_hits, d_hits_n, ho)
+        if (lds_keys > 0) TVZ_TOL(true); else TVZ_TOL(false);
 #undef TVZ_TOL
-    TVZ_HIP(hipGetLastError());
-    return TVZ_OK;
+        return launched();
+    });
 }
 
 // workspace of tvz_match_tol: per query its count of non-NaN values, then room for `keys` sorted values + positions
@@ -2384,16 +2384,12 @@ int64_t tol_ws_room(int32_t Q, size_t bytes) {
 static int tvz_find_duplicates_tol_impl(tvz_corpus *c, const double *h_query, int64_t n, double tol,
                                         int32_t min_match, int32_t exclude_id, int64_t cap, int32_t *h_out_ids,
                                         int32_t *h_out_counts, int32_t *h_out_kth, int64_t *n_out) {
-    TVZ_REQUIRE(c != nullptr && n_out != nullptr, "NULL argument");
-    TVZ_REQUIRE(n >= 0 && cap >= 0 && cap <= INT32_MAX, "bad size");
-    TVZ_REQUIRE(n == 0 || h_query, "h_query is NULL");
-    TVZ_REQUIRE(cap == 0 || (h_out_ids && h_out_counts), "NULL outputs");
-    TVZ_REQUIRE(n <= INT32_MAX, "query too long");
+    if (int rc = check_find_args(c, h_query, n, cap, h_out_ids, h_out_counts, n_out)) return rc;
     if (int rc = check_tol(tol)) return rc;
     DeviceGuard dg(c->device);
-    Staging *s = nullptr;
-    if (int rc = staging_get(c, &s)) return rc;
-    struct Put { tvz_corpus *c; Staging *s; ~Put() { staging_put(c, s); } } put{c, s};
+    StagingLease lease{c};
+    if (int rc = staging_get(c, &lease.s)) return rc;
+    Staging *s = lease.s;
     const int32_t excl = exclude_id >= 0 ? exclude_id : -1;
     // the query, sorted by value with its original positions, NaNs dropped (-0.0 folded to +0.0)
     std::vector<std::pair<double, int32_t>> &srt = s->tol_sort;
@@ -2409,18 +2405,12 @@ static int tvz_find_duplicates_tol_impl(tvz_corpus *c, const double *h_query, in
     const size_t raw_at = (sorted_bytes + 15) & ~(size_t)15;
     const size_t bytes = fixup ? raw_at + (size_t)n * 8 : sorted_bytes;
     std::vector<unsigned char> big;                      // queries of more than kMaxQueryLen timestamps only
-    unsigned char *h = s->h_tol, *d = s->d_tol;
+    unsigned char *h = s->tol.h, *d = s->d_tol.p;
     if (n > kMaxQueryLen || bytes > kTolStageBytes) {
-        if (bytes > s->tol_big_bytes) {
-            if (s->d_tol_big) (void)hipFree(s->d_tol_big);
-            s->d_tol_big = nullptr;
-            s->tol_big_bytes = 0;
-            TVZ_HIP(hipMalloc(&s->d_tol_big, bytes));
-            s->tol_big_bytes = bytes;
-        }
+        if (int rc = ensure(s->d_tol_big, (int64_t)bytes, 0)) return rc;
         big.resize(bytes);
         h = big.data();
-        d = s->d_tol_big;
+        d = s->d_tol_big.p;
     }
     double *hv = reinterpret_cast<double *>(h);
     int32_t *hp = reinterpret_cast<int32_t *>(h + (size_t)m_even * 8);
@@ -2432,60 +2422,23 @@ static int tvz_find_duplicates_tol_impl(tvz_corpus *c, const double *h_query, in
     if (bytes) TVZ_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s->stream));
     const double *dv = reinterpret_cast<const double *>(d);
     const int32_t *dp = reinterpret_cast<const int32_t *>(d + (size_t)m_even * 8);
-    int blocks = 0, region = 0;
-    {
-        struct Busy { Staging *s; ~Busy() { s->busy.store(0, std::memory_order_release); } } busy{s};
-        {
-            std::shared_lock<std::shared_mutex> lk(c->mu);
-            const int64_t n_rows = (int64_t)c->h_rows.size();
-            if (n_rows) {
-                if (n_rows > c->stage_rows || n_rows + (int64_t)kQ1MaxBlocks * kStageGroups > s->hit_slots) {
-                    // the corpus outgrew its reservation (see tvz_corpus_reserve): grow this staging
-                    if (int rc = staging_size(s, std::max<int64_t>(2 * n_rows, c->stage_rows))) return rc;
-                }
-                if (int rc = wait_mutations(c, s->stream)) return rc;
-                s->busy.store(1, std::memory_order_release);
-                blocks = q1_blocks(n_rows, 1);
-                region = (int)(tvz::ceil_div(n_rows, (int64_t)blocks * kTolGroups) * kTolGroups);
-                const HostOut ho{s->dh_hits, s->dh_counts, region};
-                const int32_t lds_keys = m <= kTolLdsKeys ? (int32_t)std::max<int64_t>(m, 1) : 0;
-                if (int rc = launch_tol<true>(c, n_rows, dv, dp, nullptr, nullptr, (int32_t)m, lds_keys, 1, tol,
-                                              min_match, nullptr, excl, 0, nullptr, nullptr, blocks, ho, s->stream))
-                    return rc;
-                if (fixup) {
-                    hipLaunchKernelGGL(ts_tol_kth_fixup_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, s->stream,
-                                       c->rows.p, c->keys.p, reinterpret_cast<const double *>(d + raw_at),
-                                       static_cast<const int64_t *>(nullptr), (int32_t)n, tol, min_match, s->dh_hits,
-                                       s->dh_counts, region);
-                    TVZ_HIP(hipGetLastError());
-                }
-            }
-        }
-        const hipError_t e = hipStreamSynchronize(s->stream);
-        if (e != hipSuccess) return tvz::fail(TVZ_ERR_HIP, "tolerant single-query match failed: %s", hipGetErrorString(e));
-    }
-    // compact the per-block regions in place
-    Hit *hh = reinterpret_cast<Hit *>(s->h_hits);
-    int64_t w = 0;
-    for (int b = 0; b < blocks; ++b) {
-        const int32_t nb = s->h_counts[b];
-        if (nb < 0) return tvz::fail(TVZ_ERR_INVALID, "internal: tolerant query table overflow");
-        const Hit *src = hh + (int64_t)b * region;
-        if (src != hh + w) memmove(hh + w, src, (size_t)nb * sizeof(Hit));
-        w += nb;
-    }
-    std::sort(hh, hh + w, [](const Hit &a, const Hit &b) {
-        if (a.vid != b.vid) return a.vid < b.vid;
-        if (a.cnt != b.cnt) return a.cnt < b.cnt;
-        return a.kth < b.kth;
-    });
-    const int64_t nw = std::min<int64_t>(w, cap);
-    for (int64_t i = 0; i < nw; ++i) {
-        h_out_ids[i] = hh[i].vid;
-        h_out_counts[i] = hh[i].cnt;
-        if (h_out_kth) h_out_kth[i] = hh[i].kth;
-    }
-    *n_out = w;                                          // the true count, also when it exceeds cap
+    auto launch = [&](int64_t n_rows, int &blocks, int &region) -> int {
+        blocks = q1_blocks(n_rows, 1);
+        region = (int)(tvz::ceil_div(n_rows, (int64_t)blocks * kTolGroups) * kTolGroups);
+        const HostOut ho{s->hits.d, s->counts.d, region};
+        const int32_t lds_keys = m <= kTolLdsKeys ? (int32_t)std::max<int64_t>(m, 1) : 0;
+        if (int rc = launch_tol<true>(c, n_rows, dv, dp, nullptr, nullptr, (int32_t)m, lds_keys, 1, tol, min_match,
+                                      nullptr, excl, 0, nullptr, nullptr, blocks, ho, s->stream))
+            return rc;
+        if (!fixup) return TVZ_OK;
+        hipLaunchKernelGGL(ts_tol_kth_fixup_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, s->stream, c->rows.p,
+                           c->keys.p, reinterpret_cast<const double *>(d + raw_at), static_cast<const int64_t *>(nullptr),
+                           (int32_t)n, tol, min_match, s->hits.d, s->counts.d, region);
+        return launched();
+    };
+    int64_t n_hits = 0;
+    if (int rc = pinned_sweep(c, s, "tolerant ", launch, &n_hits)) return rc;
+    copy_out(reinterpret_cast<Hit *>(s->hits.h), n_hits, n_hits, cap, h_out_ids, h_out_counts, h_out_kth, n_out);
     return TVZ_OK;
 }
 

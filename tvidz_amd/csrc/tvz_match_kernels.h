@@ -122,6 +122,15 @@ constexpr size_t kTileLds = (size_t)kTileSlots * 4 + (size_t)kTileMaxEntries * 8
 constexpr int kTop = 5;
 constexpr unsigned long long kTopNone = 0x0fffffffffffffffULL;   // 5 fields of 0xfff
 
+// How much of kth a kernel tracks: the MODE template argument of the Q1, tolerant, index and one-wave kernels, picked
+// from min_match by kth_mode (the fused lookup's TOP5 is MODE == kModeTop5).
+constexpr int kModeM2 = 0;                            // min_match 1..2: the two smallest positions
+constexpr int kModeTop5 = 1;                          // min_match 3..5: the five smallest positions
+constexpr int kModeCount = 2;                         // the count alone: kth = -1 (min_match <= 0) or by a fix-up (> 5)
+constexpr int kth_mode(int32_t min_match) {
+    return min_match < 1 || min_match > kTop ? kModeCount : min_match <= 2 ? kModeM2 : kModeTop5;
+}
+
 __device__ __forceinline__ unsigned long long top5_insert(unsigned long long p, uint32_t x) {
     uint32_t a[kTop];
 #pragma unroll
@@ -1011,9 +1020,6 @@ constexpr int kQ1Block = 256;
 constexpr int kQ1Groups = kQ1Block / kGroup;          // rows in flight per block
 constexpr int kQ1MinLog2 = 8, kQ1MaxLog2 = 13;        // 256 .. 8192 slots (2 KiB .. 64 KiB of keys)
 constexpr int kQ1BloomMaxLog2 = 12;                   // <= 4096 words (32 KiB)
-constexpr int kQ1ModeM2 = 0;                          // min_match 1..2: two smallest positions
-constexpr int kQ1ModeTop5 = 1;                        // min_match 3..5: five smallest positions
-constexpr int kQ1ModeCount = 2;                       // min_match <= 0 (kth = -1) or > 5 (fix-up)
 
 struct HostOut {           // tvz_find_duplicates: hits go straight to pinned host memory
     int32_t *hits;         // [blocks][region][3]
@@ -1184,11 +1190,11 @@ __device__ __forceinline__ void q1_body(
             unsigned long long top = kTopNone;
             auto acc = [&](uint32_t pos) {
                 ++cnt;
-                if constexpr (MODE == kQ1ModeM2) {
+                if constexpr (MODE == kModeM2) {
                     const uint32_t lo = m1 < pos ? m1 : pos, hi = m1 < pos ? pos : m1;
                     m1 = lo;
                     m2 = m2 < hi ? m2 : hi;
-                } else if constexpr (MODE == kQ1ModeTop5) {
+                } else if constexpr (MODE == kModeTop5) {
                     top = top5_insert(top, pos);
                 }
             };
@@ -1233,13 +1239,13 @@ __device__ __forceinline__ void q1_body(
 #undef TVZ_SUM_STEP
             const bool hit = cand && (int64_t)cnt >= (int64_t)min_match && row.vid != excl;
             if (__ballot(hit) != 0ull) {
-                if constexpr (MODE == kQ1ModeM2) {
+                if constexpr (MODE == kModeM2) {
 #define TVZ_M2_STEP(C) { const uint32_t p1 = dpp16<C>(m1), p2 = dpp16<C>(m2); \
                     const uint32_t lo = m1 < p1 ? m1 : p1, hi = m1 < p1 ? p1 : m1, r2 = m2 < p2 ? m2 : p2; \
                     m1 = lo; m2 = hi < r2 ? hi : r2; }
                     TVZ_ROW16_BUTTERFLY(TVZ_M2_STEP)
 #undef TVZ_M2_STEP
-                } else if constexpr (MODE == kQ1ModeTop5) {
+                } else if constexpr (MODE == kModeTop5) {
 #define TVZ_T5_STEP(C) { const unsigned long long p = dpp16_64<C>(top); \
                     _Pragma("unroll") for (int i = 0; i < kTop; ++i) top = top5_insert(top, (uint32_t)(p >> (12 * i)) & 0xfffu); }
                     TVZ_ROW16_BUTTERFLY(TVZ_T5_STEP)
@@ -1249,8 +1255,8 @@ __device__ __forceinline__ void q1_body(
             if (hit && gl == 0) {
                 int32_t kth;
                 if (min_match <= 0) kth = -1;
-                else if constexpr (MODE == kQ1ModeM2) kth = (int32_t)(min_match == 1 ? m1 : m2);
-                else if constexpr (MODE == kQ1ModeTop5) kth = (int32_t)((top >> (12 * (min_match - 1))) & 0xfffu);
+                else if constexpr (MODE == kModeM2) kth = (int32_t)(min_match == 1 ? m1 : m2);
+                else if constexpr (MODE == kModeTop5) kth = (int32_t)((top >> (12 * (min_match - 1))) & 0xfffu);
                 else kth = -2 - (int32_t)r;                 // resolved by ts_kth_fixup_kernel
                 const int slot = atomicAdd(&s_nhits, 1);            // LDS
                 if constexpr (HOSTOUT) {

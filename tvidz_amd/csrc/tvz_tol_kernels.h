@@ -33,9 +33,6 @@ constexpr int kTolStepKeys = kTolLd * 2 * kGroup;      // 128 keys of a row per 
 // Sorted queries of up to this many values live in LDS (8 B value + 4 B position each: 96 KiB at the limit);
 // a longer one is searched where the preparation left it, in device memory.  Same results either way.
 constexpr int kTolLdsKeys = 8192;
-constexpr int kTolModeM2 = 0;                          // min_match 1..2: two smallest positions per lane
-constexpr int kTolModeTop5 = 1;                        // min_match 3..5: five smallest positions per lane
-constexpr int kTolModeCount = 2;                       // min_match <= 0 (kth = -1) or > 5 (fix-up pass)
 constexpr int kTolSortBlock = 256;
 constexpr int kTolSortTile = 2048;                     // query values per LDS tile of the rank sort
 
@@ -216,14 +213,14 @@ __global__ __launch_bounds__(kTolBlock) void ts_match_tol_kernel(
         auto acc_range = [&](int a, int b) {
             if (b <= a) return;
             cnt += (uint32_t)(b - a);
-            if constexpr (MODE == kTolModeM2) {
+            if constexpr (MODE == kModeM2) {
                 for (int t = a; t < b; ++t) {
                     const uint32_t p = (uint32_t)pos[t];
                     const uint32_t lo = m1 < p ? m1 : p, hi = m1 < p ? p : m1;
                     m1 = lo;
                     m2 = m2 < hi ? m2 : hi;
                 }
-            } else if constexpr (MODE == kTolModeTop5) {
+            } else if constexpr (MODE == kModeTop5) {
                 for (int t = a; t < b; ++t) tol_insert5(tk, (uint32_t)pos[t]);
             }
         };
@@ -295,13 +292,13 @@ __global__ __launch_bounds__(kTolBlock) void ts_match_tol_kernel(
 #undef TVZ_SUM_STEP
         const bool hit = (int64_t)cnt >= (int64_t)min_match && row.vid != excl;
         if (__ballot(hit) != 0ull) {
-            if constexpr (MODE == kTolModeM2) {
+            if constexpr (MODE == kModeM2) {
 #define TVZ_M2_STEP(C) { const uint32_t p1 = dpp16<C>(m1), p2 = dpp16<C>(m2); \
                 const uint32_t lo = m1 < p1 ? m1 : p1, hi = m1 < p1 ? p1 : m1, r2 = m2 < p2 ? m2 : p2; \
                 m1 = lo; m2 = hi < r2 ? hi : r2; }
                 TVZ_ROW16_BUTTERFLY(TVZ_M2_STEP)
 #undef TVZ_M2_STEP
-            } else if constexpr (MODE == kTolModeTop5) {
+            } else if constexpr (MODE == kModeTop5) {
                 // each step merges two DISJOINT sets of positions (every union element is visited once)
 #define TVZ_T5_STEP(C) { uint32_t o[kTop]; \
                 _Pragma("unroll") for (int t = 0; t < kTop; ++t) o[t] = dpp16<C>(tk[t]); \
@@ -313,8 +310,8 @@ __global__ __launch_bounds__(kTolBlock) void ts_match_tol_kernel(
         if (hit && gl == 0) {
             int32_t kth;
             if (min_match <= 0) kth = -1;
-            else if constexpr (MODE == kTolModeM2) kth = (int32_t)(min_match == 1 ? m1 : m2);
-            else if constexpr (MODE == kTolModeTop5) kth = (int32_t)tk[min_match - 1];
+            else if constexpr (MODE == kModeM2) kth = (int32_t)(min_match == 1 ? m1 : m2);
+            else if constexpr (MODE == kModeTop5) kth = (int32_t)tk[min_match - 1];
             else kth = -2 - (int32_t)r;                          // resolved by ts_tol_kth_fixup_kernel
             const int slot = atomicAdd(&s_nhits, 1);             // LDS
             if constexpr (HOSTOUT) {

@@ -230,10 +230,7 @@ class ShardedCorpus:
     def _exact(self, q, min_match, exclude_id, with_kth, tolerance=0.0):
         out = []
         for s in self.shards:
-            if tolerance:
-                out += s.find_duplicates(q, min_match, exclude_id=exclude_id, with_kth=True, tolerance=tolerance)
-            else:
-                out += s.find_duplicates(q, min_match, exclude_id=exclude_id, with_kth=True)
+            out += s.find_duplicates(q, min_match, exclude_id=exclude_id, with_kth=True, tolerance=tolerance)
         out.sort()
         return out if with_kth else [(v, c) for v, c, _ in out]
 
