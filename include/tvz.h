@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define TVZ_VERSION 402 /* 0.4.2: tvz_find_duplicates_tol / tvz_match_tol, the opt-in tolerant match (0.4.1: tvz_align takes its output capacity and reports the row count (0.4.0: the index answers every min_match >= 1; tvz_match_topk keeps the top-k inside the lookup; tvz_match_topk_shards)) */
+#define TVZ_VERSION 403 /* 0.4.3: tvz_match_tol_topk / tvz_match_tol_sharded, the tolerant sweep keeps the per-shard top-k itself (0.4.2: tvz_find_duplicates_tol / tvz_match_tol, the opt-in tolerant match (0.4.1: tvz_align takes its output capacity and reports the row count (0.4.0: the index answers every min_match >= 1; tvz_match_topk keeps the top-k inside the lookup; tvz_match_topk_shards))) */
 
 typedef enum tvz_status {
     TVZ_OK = 0,
@@ -431,6 +431,44 @@ int tvz_match_tol(tvz_corpus *c, const double *d_queries, const int64_t *d_q_off
                   int32_t max_query_len, double tol, int32_t min_match, const int32_t *d_exclude_ids,
                   int32_t cap, int32_t *d_hits, int32_t *d_hits_n, void *d_workspace,
                   size_t workspace_bytes, void *hip_stream);
+
+/* The tolerant match with the per-shard top-k kept inside the sweep: no hit lists, no cap.  The match is the
+ * tolerant contract above, word for word (tol finite and >= 0, else TVZ_ERR_INVALID and nothing written; tol = 0
+ * is the exact verdict).  A hit is the sortable word kth << 44 | video_id << 12 | count of the index lookups; every
+ * sweep block keeps its k smallest words on chip and writes them, with ONE atomic for its hit count, at its end;
+ * a second kernel selects each query's k smallest.  Nothing in device memory grows with the number of hits.
+ *   d_out : int32[Q][k+1][3], the block of tvz_match_topk (so tvz_topk_merge and the all-gather take it
+ *           unchanged): the k best hits ascending by (kth, video_id, count), padded with (-1, 0, TVZ_KTH_NEVER),
+ *           + a row (-1, n_hits, TVZ_KTH_NEVER).  The k rows are EXACT and n_hits is the true count however many
+ *           rows hit; it is never negated.  n_hits = INT32_MIN (all rows padding) for a query longer than
+ *           max_query_len or one whose sorted copy does not fit the workspace; 0 on an empty corpus.
+ * TVZ_ERR_UNSUPPORTED, by name: min_match outside 1..5 (kth would need the fix-up pass over hit lists), k outside
+ * 1..64, max_query_len > 4,095 (count must fit the word's 12 bits; the sorted query is always in LDS).  Use
+ * tvz_match_tol + tvz_topk_shard for those.
+ * Workspace = tvz_match_tol_workspace_bytes(Q, max_query_len, total_query_keys)       (the sorted queries)
+ *           + 4 Q                                                                     (hit totals)
+ *           + max(6080, 95 Q) x k x 8                                                  (one kept list per sweep block:
+ *             the sweep runs min(rows / 16, 6080 / Q clamped to 95..2048) row blocks per query)
+ *           + (1 + max(n_ranks, 1)) x Q x (k + 1) x 12                                 (local + gathered blocks)
+ *           + alignment (each part to 256 B).  For Q >= 64 that is below what tvz_match_tol at cap = 4,096 +
+ * tvz_topk_shard need (95 lists of k = 64 words + the total: under the Q x 4096 x 12 B of hit lists alone).  Too small: TVZ_ERR_WORKSPACE with the bytes missing.
+ * Enqueues only (no host synchronisation, no allocation); rows upserted before the call are seen. */
+size_t tvz_match_tol_topk_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys,
+                                          int32_t k, int32_t n_ranks);
+int tvz_match_tol_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
+                       int32_t max_query_len, double tol, int32_t min_match, const int32_t *d_exclude_ids,
+                       int32_t k, int32_t *d_out, void *d_workspace, size_t workspace_bytes,
+                       void *hip_stream);
+/* tvz_match_sharded for the tolerant match: tvz_match_tol_topk into the workspace's own block -> the ONE
+ * ncclAllGather -> tvz_topk_merge.  d_topk int32[Q][k][3], d_totals int32[Q]: every block is exact, so a
+ * total is the true hit count and is not negated for an overflow - there is none.  The one negative total left
+ * is tvz_topk_merge's answer to a query some rank refused (n_hits = INT32_MIN in its block: longer than
+ * max_query_len): the merge sums |n_hits| clamped to INT32_MAX and negates, as for any negative block total.  Workspace: the function above with the
+ * communicator's n_ranks. */
+int tvz_match_tol_sharded(tvz_corpus *c, tvz_comm *comm, const double *d_queries, const int64_t *d_q_offsets,
+                          int32_t Q, int32_t max_query_len, double tol, int32_t min_match,
+                          const int32_t *d_exclude_ids, int32_t k, int32_t *d_topk, int32_t *d_totals,
+                          void *d_workspace, size_t workspace_bytes, void *hip_stream);
 
 /* ------------------------------------------------------------------------
  * Frame feeder I/O - the host side of what replaces the stderr pipe of

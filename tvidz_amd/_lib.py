@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("TVZ_LIB") or os.path.join(_HERE, "libtvz.so")
 
 KTH_NEVER = 0x7FFFFFFF
-VERSION = 402
+VERSION = 403
 
 # name -> (restype, argtypes); mirrors include/tvz.h one to one
 _P = C.c_void_p
@@ -71,6 +71,11 @@ SIGNATURES = {
     "tvz_match_tol_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64]),
     "tvz_match_tol": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_double, C.c_int32, _P, C.c_int32, _P, _P, _P,
                                 C.c_size_t, _P]),
+    "tvz_match_tol_topk_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
+    "tvz_match_tol_topk": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_double, C.c_int32, _P, C.c_int32, _P, _P,
+                                     C.c_size_t, _P]),
+    "tvz_match_tol_sharded": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_double, C.c_int32, _P, C.c_int32,
+                                        _P, _P, _P, C.c_size_t, _P]),
     "tvz_align": (C.c_int, [_P, _P, C.c_int32, C.c_double, C.c_double, _P, C.c_int64, C.POINTER(C.c_int64), _P]),
     "tvz_read_records": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, _P,
                                    C.POINTER(C.c_int64)]),

@@ -54,6 +54,14 @@ def tol_workspace_bytes(Q: int, max_query_len: int, total_query_keys: int = 0) -
     return int(_lib.load().tvz_match_tol_workspace_bytes(int(Q), int(max_query_len), int(total_query_keys)))
 
 
+def tol_topk_workspace_bytes(Q: int, max_query_len: int, total_query_keys: int = 0, k: int = 16,
+                             n_ranks: int = 1) -> int:
+    """tvz_match_tol_topk_workspace_bytes: the sorted queries, one kept list of k words per sweep block, the local
+    block and `n_ranks` gathered ones - nothing in it grows with the number of hits."""
+    return int(_lib.load().tvz_match_tol_topk_workspace_bytes(int(Q), int(max_query_len), int(total_query_keys),
+                                                              int(k), int(n_ranks)))
+
+
 class DeviceCorpus:
     """tvz_corpus handle: rows of (video_id, sorted-unique canonical float64 keys) in HBM."""
 
@@ -266,6 +274,24 @@ class DeviceCorpus:
             int(cap), int(k), out.data_ptr(), ws.data_ptr(), ws.numel(), int(algo), s.cuda_stream))
         return out
 
+    def match_tol_topk(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, tol: float,
+                       min_match: int, k: int, d_exclude_ids: Optional[torch.Tensor] = None,
+                       out: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
+                       workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The tolerant sweep with the per-shard top-k kept inside it (tvz_match_tol_topk; min_match 1..5, k <= 64,
+        queries of up to 4,095 timestamps): -> int32 [Q,k+1,3] in match_topk's layout.  No cap: the k rows are the
+        exact k best and the tail row's n_hits is the true count."""
+        dev, Q = self._check_queries(d_queries, d_q_offsets)
+        if out is None:
+            out = torch.empty((Q, k + 1, 3), dtype=torch.int32, device=dev)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        ws = self._workspace(workspace, tol_topk_workspace_bytes(Q, max_query_len, d_queries.numel(), k), dev, s)
+        _lib.check(self.lib.tvz_match_tol_topk(
+            self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(tol),
+            int(min_match), d_exclude_ids.data_ptr() if d_exclude_ids is not None else None,
+            int(k), out.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
+        return out
+
 
 class Comm:
     """tvz_comm handle: the RCCL communicator of the sharded match, owned by libtvz.so (a non-Python
@@ -309,14 +335,7 @@ class Comm:
         call; -> (merged int32 [Q,k,3], totals int32 [Q]), identical on every rank.  `out` =
         (merged, totals) buffers to write into (a caller streaming batches keeps its own)."""
         dev, Q = corpus._check_queries(d_queries, d_q_offsets)
-        if out is not None:
-            merged, totals = out
-            if merged.shape != (Q, k, 3) or totals.shape != (Q,) or merged.dtype != torch.int32 \
-                    or totals.dtype != torch.int32 or not merged.is_contiguous():
-                raise RuntimeError("out must be (int32 [Q,k,3], int32 [Q])")
-        else:
-            merged = torch.empty((Q, k, 3), dtype=torch.int32, device=dev)
-            totals = torch.empty(Q, dtype=torch.int32, device=dev)
+        merged, totals = self._merged_out(out, Q, k, dev)
         s = stream if stream is not None else torch.cuda.current_stream(dev)
         ws = corpus._workspace(workspace, workspace_bytes(Q, max_query_len, cap, k, self.n_ranks, d_queries.numel()), dev, s)
         _lib.check(self.lib.tvz_match_sharded(
@@ -324,6 +343,36 @@ class Comm:
             int(min_match), d_exclude_ids.data_ptr() if d_exclude_ids is not None else None,
             int(cap), int(k), merged.data_ptr(), totals.data_ptr(), ws.data_ptr(), ws.numel(),
             int(algo), s.cuda_stream))
+        return merged, totals
+
+    def _merged_out(self, out, Q: int, k: int, dev):
+        if out is not None:
+            merged, totals = out
+            if merged.shape != (Q, k, 3) or totals.shape != (Q,) or merged.dtype != torch.int32 \
+                    or totals.dtype != torch.int32 or not merged.is_contiguous():
+                raise RuntimeError("out must be (int32 [Q,k,3], int32 [Q])")
+            return merged, totals
+        return (torch.empty((Q, k, 3), dtype=torch.int32, device=dev),
+                torch.empty(Q, dtype=torch.int32, device=dev))
+
+    def match_tol_sharded(self, corpus: DeviceCorpus, d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
+                          max_query_len: int, tol: float, min_match: int, k: int,
+                          d_exclude_ids: Optional[torch.Tensor] = None,
+                          workspace: Optional[torch.Tensor] = None,
+                          stream: Optional[torch.cuda.Stream] = None,
+                          out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+        """The tolerant form of `match_sharded` (tvz_match_tol_sharded): the sweep that keeps its k best ->
+        ncclAllGather -> merge; -> (merged int32 [Q,k,3], totals int32 [Q]: true counts, negative only
+        for a query longer than max_query_len)."""
+        dev, Q = corpus._check_queries(d_queries, d_q_offsets)
+        merged, totals = self._merged_out(out, Q, k, dev)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        ws = corpus._workspace(workspace, tol_topk_workspace_bytes(Q, max_query_len, d_queries.numel(), k, self.n_ranks),
+                               dev, s)
+        _lib.check(self.lib.tvz_match_tol_sharded(
+            corpus._h, self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(tol),
+            int(min_match), d_exclude_ids.data_ptr() if d_exclude_ids is not None else None,
+            int(k), merged.data_ptr(), totals.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
         return merged, totals
 
 

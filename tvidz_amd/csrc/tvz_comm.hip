@@ -126,21 +126,10 @@ static int tvz_comm_destroy_impl(tvz_comm *comm) {
     return TVZ_OK;
 }
 
-static int tvz_match_sharded_impl(tvz_corpus *c, tvz_comm *comm, const double *d_queries,
-                                  const int64_t *d_q_offsets, int32_t Q, int32_t max_query_len,
-                                  int32_t min_match, const int32_t *d_exclude_ids, int32_t cap,
-                                  int32_t k, int32_t *d_topk, int32_t *d_totals, void *d_workspace,
-                                  size_t workspace_bytes, int32_t algo, void *hip_stream) {
-    TVZ_REQUIRE(comm != nullptr && comm->comm != nullptr, "communicator is NULL");
-    TVZ_REQUIRE(Q == 0 || d_topk != nullptr, "d_topk is NULL");
-    if (Q == 0) return TVZ_OK;
-    int32_t *gathered = nullptr;
-    // local sweep + per-shard top-k into the workspace's own block
-    if (int rc = tvz_match_topk_local(c, d_queries, d_q_offsets, Q, max_query_len, min_match,
-                                      d_exclude_ids, cap, k, nullptr, d_workspace, workspace_bytes,
-                                      comm->n_ranks, algo, hip_stream, &gathered))
-        return rc;
-    const int32_t *local = tvz_ws_local_block(d_workspace, Q, max_query_len, cap, k, comm->n_ranks);
+// The exchange behind a local per-shard top-k: ONE ncclAllGather of the ranks' int32[Q][k+1][3] blocks on
+// `hip_stream`, ordered behind the communicator's previous collective, then the merge every rank runs alike.
+static int gather_and_merge(tvz_comm *comm, const int32_t *local, int32_t *gathered, int32_t Q, int32_t k,
+                            int32_t *d_topk, int32_t *d_totals, void *hip_stream) {
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
     const size_t count = (size_t)Q * (size_t)(k + 1) * 3;
     // RCCL enqueues on the communicator's device: make it current for the call (a host that drives
@@ -167,6 +156,41 @@ static int tvz_match_sharded_impl(tvz_corpus *c, tvz_comm *comm, const double *d
     return tvz_topk_merge(gathered, comm->n_ranks, Q, k, d_topk, d_totals, hip_stream);
 }
 
+static int tvz_match_sharded_impl(tvz_corpus *c, tvz_comm *comm, const double *d_queries,
+                                  const int64_t *d_q_offsets, int32_t Q, int32_t max_query_len,
+                                  int32_t min_match, const int32_t *d_exclude_ids, int32_t cap,
+                                  int32_t k, int32_t *d_topk, int32_t *d_totals, void *d_workspace,
+                                  size_t workspace_bytes, int32_t algo, void *hip_stream) {
+    TVZ_REQUIRE(comm != nullptr && comm->comm != nullptr, "communicator is NULL");
+    TVZ_REQUIRE(Q == 0 || d_topk != nullptr, "d_topk is NULL");
+    if (Q == 0) return TVZ_OK;
+    int32_t *gathered = nullptr;
+    // local sweep + per-shard top-k into the workspace's own block
+    if (int rc = tvz_match_topk_local(c, d_queries, d_q_offsets, Q, max_query_len, min_match,
+                                      d_exclude_ids, cap, k, nullptr, d_workspace, workspace_bytes,
+                                      comm->n_ranks, algo, hip_stream, &gathered))
+        return rc;
+    const int32_t *local = tvz_ws_local_block(d_workspace, Q, max_query_len, cap, k, comm->n_ranks);
+    return gather_and_merge(comm, local, gathered, Q, k, d_topk, d_totals, hip_stream);
+}
+
+static int tvz_match_tol_sharded_impl(tvz_corpus *c, tvz_comm *comm, const double *d_queries,
+                                      const int64_t *d_q_offsets, int32_t Q, int32_t max_query_len, double tol,
+                                      int32_t min_match, const int32_t *d_exclude_ids, int32_t k, int32_t *d_topk,
+                                      int32_t *d_totals, void *d_workspace, size_t workspace_bytes,
+                                      void *hip_stream) {
+    TVZ_REQUIRE(comm != nullptr && comm->comm != nullptr, "communicator is NULL");
+    TVZ_REQUIRE(Q <= 0 || d_topk != nullptr, "d_topk is NULL");
+    int32_t *local = nullptr, *gathered = nullptr;
+    // the tolerant sweep keeps its k best itself and writes them into the workspace's own block
+    if (int rc = tvz_match_tol_topk_local(c, d_queries, d_q_offsets, Q, max_query_len, tol, min_match, d_exclude_ids,
+                                          k, nullptr, d_workspace, workspace_bytes, comm->n_ranks, hip_stream, &local,
+                                          &gathered))
+        return rc;
+    if (Q == 0) return TVZ_OK;
+    return gather_and_merge(comm, local, gathered, Q, k, d_topk, d_totals, hip_stream);
+}
+
 TVZ_EXPORT int tvz_comm_unique_id(void *out_id) { TVZ_GUARDED(tvz_comm_unique_id_impl(out_id)); }
 
 TVZ_EXPORT int tvz_comm_init(tvz_comm **out, const void *unique_id, int32_t n_ranks, int32_t rank,
@@ -189,4 +213,11 @@ TVZ_EXPORT int tvz_match_sharded(tvz_corpus *c, tvz_comm *comm, const double *d_
                                  int32_t k, int32_t *d_topk, int32_t *d_totals, void *d_workspace,
                                  size_t workspace_bytes, int32_t algo, void *hip_stream) {
     TVZ_GUARDED(tvz_match_sharded_impl(c, comm, d_queries, d_q_offsets, Q, max_query_len, min_match, d_exclude_ids, cap, k, d_topk, d_totals, d_workspace, workspace_bytes, algo, hip_stream));
+}
+
+TVZ_EXPORT int tvz_match_tol_sharded(tvz_corpus *c, tvz_comm *comm, const double *d_queries,
+                                     const int64_t *d_q_offsets, int32_t Q, int32_t max_query_len, double tol,
+                                     int32_t min_match, const int32_t *d_exclude_ids, int32_t k, int32_t *d_topk,
+                                     int32_t *d_totals, void *d_workspace, size_t workspace_bytes, void *hip_stream) {
+    TVZ_GUARDED(tvz_match_tol_sharded_impl(c, comm, d_queries, d_q_offsets, Q, max_query_len, tol, min_match, d_exclude_ids, k, d_topk, d_totals, d_workspace, workspace_bytes, hip_stream));
 }

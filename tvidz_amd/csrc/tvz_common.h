@@ -75,3 +75,9 @@ int tvz_match_topk_local(tvz_corpus *c, const double *d_queries, const int64_t *
                          void *hip_stream, int32_t **gathered_out);
 int32_t *tvz_ws_local_block(void *d_workspace, int32_t Q, int32_t max_query_len, int32_t cap,
                             int32_t k, int32_t n_ranks);
+// The tolerant counterpart (tvz_match.hip): the sweep keeps the k best itself; *local_out = where the block went
+// (d_out, or the workspace's own area for d_out = NULL), *gathered_out = the workspace's [n_ranks][Q][k+1][3].
+int tvz_match_tol_topk_local(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
+                             int32_t max_query_len, double tol, int32_t min_match, const int32_t *d_exclude_ids,
+                             int32_t k, int32_t *d_out, void *d_workspace, size_t workspace_bytes, int32_t n_ranks,
+                             void *hip_stream, int32_t **local_out, int32_t **gathered_out);

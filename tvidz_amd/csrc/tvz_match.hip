@@ -2479,6 +2479,109 @@ static int tvz_match_tol_impl(tvz_corpus *c, const double *d_queries, const int6
     return record(c, st);
 }
 
+namespace {
+
+// Workspace of the top-k form, in front of tvz_match_tol's own (which takes the rest): the queries' hit totals,
+// one kept list per sweep block, the local block and the gathered ones.  The sizing function knows no row count:
+// the lists are sized by the grid's upper bound, Q * tol_topk_max_blocks(Q) <= tol_topk_max_lists(Q).
+struct TolTopkWs {
+    int32_t *totals = nullptr;             // [Q]
+    unsigned long long *part = nullptr;    // [Q][blocks][k]
+    int32_t *local = nullptr;              // [Q][k+1][3]
+    int32_t *gathered = nullptr;           // [n_ranks][Q][k+1][3]
+    unsigned char *rest = nullptr;         // tvz_match_tol's workspace
+    size_t fixed = 0;                      // bytes in front of `rest`, the base's alignment included
+};
+
+TolTopkWs tol_topk_ws_layout(void *base, int32_t Q, int32_t k, int32_t n_ranks) {
+    TolTopkWs w;
+    uintptr_t p = (reinterpret_cast<uintptr_t>(base) + 255) & ~(uintptr_t)255;
+    const size_t block = (size_t)Q * (size_t)(k + 1) * 12;
+    w.totals = reinterpret_cast<int32_t *>(p);
+    p += al256((size_t)Q * 4);
+    w.part = reinterpret_cast<unsigned long long *>(p);
+    p += al256((size_t)tol_topk_max_lists(Q) * (size_t)k * 8);
+    w.local = reinterpret_cast<int32_t *>(p);
+    p += al256(block);
+    w.gathered = reinterpret_cast<int32_t *>(p);
+    p += al256((size_t)(n_ranks > 1 ? n_ranks : 1) * block);
+    w.rest = reinterpret_cast<unsigned char *>(p);
+    w.fixed = (size_t)(p - ((reinterpret_cast<uintptr_t>(base) + 255) & ~(uintptr_t)255)) + 255;
+    return w;
+}
+
+}  // namespace
+
+// used by tvz_comm.hip (same shared object, not exported): sort -> sweep that keeps the k best -> per-query
+// selection.  d_out = NULL writes the block into the workspace's own area; local_out / gathered_out name it and
+// the all-gather's target.
+int tvz_match_tol_topk_local(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
+                             int32_t max_query_len, double tol, int32_t min_match, const int32_t *d_exclude_ids,
+                             int32_t k, int32_t *d_out, void *d_workspace, size_t workspace_bytes, int32_t n_ranks,
+                             void *hip_stream, int32_t **local_out, int32_t **gathered_out) {
+    if (int rc = check_batch_args(c, d_queries, d_q_offsets, Q, max_query_len, 0)) return rc;
+    if (int rc = check_tol(tol)) return rc;
+    if (min_match < 1 || min_match > kTop)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "tolerant top-k: min_match %d outside 1..%d (kth needs the hit lists of "
+                                              "tvz_match_tol)", (int)min_match, kTop);
+    if (k < 1 || k > kTolTopkMaxK)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "tolerant top-k: k=%d outside 1..%d", (int)k, kTolTopkMaxK);
+    if (max_query_len > kTolTopkMaxLen)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "tolerant top-k: max_query_len %d above %d (use tvz_match_tol)",
+                         (int)max_query_len, kTolTopkMaxLen);
+    if (Q == 0) return TVZ_OK;
+    const TolTopkWs w = tol_topk_ws_layout(d_workspace, Q, k, n_ranks);
+    const size_t have = d_workspace ? workspace_bytes : 0;
+    const int64_t room = have < w.fixed ? -1 : tol_ws_room(Q, have - w.fixed);
+    if (room < 0)
+        return tvz::fail(TVZ_ERR_WORKSPACE, "tolerant top-k: workspace of %zu bytes, %zu bytes missing (size it with "
+                                            "tvz_match_tol_topk_workspace_bytes)", have, w.fixed + tol_ws_fixed(Q) - have);
+    TVZ_REQUIRE(d_out || local_out, "NULL output");
+    if (d_out == nullptr) d_out = w.local;
+    if (local_out) *local_out = d_out;
+    if (gathered_out) *gathered_out = w.gathered;
+    const TolWs t = tol_ws_layout(w.rest, Q, room);
+    const int32_t lds_keys = std::max(max_query_len, 1);
+    const size_t lds = tol_lds_bytes(lds_keys);
+    TVZ_REQUIRE(lds + kTolTopkStaticLds <= (size_t)kLdsPerWorkgroup,
+                "tolerant top-k sweep: %zu B of dynamic + %d B of static LDS exceed a gfx950 workgroup's", lds,
+                kTolTopkStaticLds);
+    DeviceGuard dg(c->device);
+    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+    // per query: sorted values + positions, counts, hit totals = 0
+    hipLaunchKernelGGL(ts_tol_sort_kernel, dim3((unsigned)tvz::ceil_div(lds_keys, kTolSortBlock), (unsigned)Q),
+                       dim3(kTolSortBlock), 0, st, d_queries, d_q_offsets, max_query_len, t.room, t.sv, t.sp, t.qm,
+                       w.totals);
+    TVZ_HIP(hipGetLastError());
+    std::shared_lock<std::shared_mutex> lk(c->mu);
+    const int64_t n_rows = (int64_t)c->h_rows.size();
+    if (int rc = wait_mutations(c, st)) return rc;
+    const int blocks = n_rows ? std::min(q1_blocks(n_rows, Q), tol_topk_max_blocks(Q)) : 0;
+    if (blocks) {
+        const dim3 grid((unsigned)blocks, (unsigned)Q);
+        if (int rc = by_mode<false>(min_match, [&](auto mode) {
+                hipLaunchKernelGGL((ts_tol_topk_kernel<mode.value>), grid, dim3(kTolBlock), lds, st, c->rows.p, n_rows,
+                                   c->keys.p, t.sv, t.sp, d_q_offsets, t.qm, lds_keys, tol, min_match, d_exclude_ids, k,
+                                   w.part, w.totals);
+                return launched();
+            }))
+            return rc;
+    }
+    hipLaunchKernelGGL(ts_tol_topk_reduce_kernel, dim3((unsigned)Q), dim3(kTolReduceBlock), 0, st, w.part, blocks, k,
+                       t.qm, lds_keys, w.totals, d_out);
+    TVZ_HIP(hipGetLastError());
+    return record(c, st);
+}
+
+static int tvz_match_tol_topk_impl(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
+                                   int32_t max_query_len, double tol, int32_t min_match,
+                                   const int32_t *d_exclude_ids, int32_t k, int32_t *d_out, void *d_workspace,
+                                   size_t workspace_bytes, void *hip_stream) {
+    TVZ_REQUIRE(Q <= 0 || d_out != nullptr, "d_out is NULL");
+    return tvz_match_tol_topk_local(c, d_queries, d_q_offsets, Q, max_query_len, tol, min_match, d_exclude_ids, k,
+                                    d_out, d_workspace, workspace_bytes, 1, hip_stream, nullptr, nullptr);
+}
+
 #ifdef TVZ_IX_STAMP
 // diagnostic build only: read (and clear) the per-phase cycle totals of ts_match_index_kernel
 TVZ_EXPORT int tvz_debug_ix_stamps(unsigned long long *out16) {
@@ -2635,4 +2738,19 @@ TVZ_EXPORT int tvz_match_tol(tvz_corpus *c, const double *d_queries, const int64
                              void *hip_stream) {
     TVZ_GUARDED(tvz_match_tol_impl(c, d_queries, d_q_offsets, Q, max_query_len, tol, min_match, d_exclude_ids, cap,
                                    d_hits, d_hits_n, d_workspace, workspace_bytes, hip_stream));
+}
+
+TVZ_EXPORT size_t tvz_match_tol_topk_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys,
+                                                     int32_t k, int32_t n_ranks) {
+    if (Q < 0 || max_query_len < 0 || total_query_keys < 0 || k < 1 || n_ranks < 0) return 0;
+    return tol_topk_ws_layout(nullptr, Q, k, n_ranks).fixed +
+           tvz_match_tol_workspace_bytes(Q, max_query_len, total_query_keys);
+}
+
+TVZ_EXPORT int tvz_match_tol_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
+                                  int32_t max_query_len, double tol, int32_t min_match, const int32_t *d_exclude_ids,
+                                  int32_t k, int32_t *d_out, void *d_workspace, size_t workspace_bytes,
+                                  void *hip_stream) {
+    TVZ_GUARDED(tvz_match_tol_topk_impl(c, d_queries, d_q_offsets, Q, max_query_len, tol, min_match, d_exclude_ids, k,
+                                        d_out, d_workspace, workspace_bytes, hip_stream));
 }

@@ -22,6 +22,8 @@
 //                         unconditional 16-byte key loads, the next row entry fetched one row ahead; per key
 //                         two searches of the sorted query (LDS table, or device memory for a long query).
 // ts_tol_kth_fixup_kernel kth for min_match > 5: per hit, the query walked in its original order.
+// ts_tol_topk_kernel      the sweep that keeps the k best hits of its block on chip (min_match 1..5) and
+// ts_tol_topk_reduce_kernel  the per-query selection over the blocks' lists: tvz_match_tol_topk.
 #pragma once
 
 namespace {
@@ -92,6 +94,118 @@ __device__ __forceinline__ void tol_insert5(uint32_t (&tk)[kTop], uint32_t v) {
         const uint32_t lo = tk[t] < v ? tk[t] : v;
         v = tk[t] < v ? v : tk[t];
         tk[t] = lo;
+    }
+}
+
+// One row against the sorted query s[0 .. m) (positions pos[..]): the 16 lanes of a group walk the row's keys
+// rk[0 .. len), 128 per step.  Returns cnt summed over the group and, per lane, the smallest positions it met
+// (m1, m2 or tk by MODE; tol_row_kth reduces them).  `keys` is any readable address for the lanes past the end.
+template <int MODE>
+__device__ __forceinline__ void tol_row_scan(const int64_t *__restrict__ keys, const int64_t *rk, int len, const double *s,
+                                             const int32_t *pos, int m, double tol, int gl, uint32_t &cnt, uint32_t &m1,
+                                             uint32_t &m2, uint32_t (&tk)[kTop]) {
+    cnt = 0;
+    m1 = m2 = 0xffffffffu;
+#pragma unroll
+    for (int t = 0; t < kTop; ++t) tk[t] = 0xffffffffu;
+    auto acc_range = [&](int a, int b) {
+        if (b <= a) return;
+        cnt += (uint32_t)(b - a);
+        if constexpr (MODE == kModeM2) {
+            for (int t = a; t < b; ++t) {
+                const uint32_t p = (uint32_t)pos[t];
+                const uint32_t lo = m1 < p ? m1 : p, hi = m1 < p ? p : m1;
+                m1 = lo;
+                m2 = m2 < hi ? m2 : hi;
+            }
+        } else if constexpr (MODE == kModeTop5) {
+            for (int t = a; t < b; ++t) tol_insert5(tk, (uint32_t)pos[t]);
+        }
+    };
+    // packed union state a key hands to its arena successor: (neg ? lo : hi) | neg << 31
+    uint32_t carry = 0;
+    int64_t k0 = 0;                      // the row's first arena key (numerically largest negative, if any)
+    int hi0 = -1;                        // its hi, computed by the lane that needs it
+    for (int base = 0; base < len; base += kTolStepKeys) {
+        longlong2 cur[kTolLd];
+#pragma unroll
+        for (int j = 0; j < kTolLd; ++j) {
+            const int i = base + gl * 2 + j * 2 * kGroup;
+            const int64_t *p = (i < len) ? rk + i : keys;                 // unconditional 16-byte loads
+            cur[j] = *reinterpret_cast<const longlong2 *>(p);
+        }
+        if (base == 0) k0 = __shfl(cur[0].x, 0, kGroup);               // group-uniform step
+#pragma unroll
+        for (int j = 0; j < kTolLd; ++j) {
+            const int i = base + gl * 2 + j * 2 * kGroup;
+            const bool vx = i < len, vy = i + 1 < len;
+            const int64_t bx_ = cur[j].x, by_ = cur[j].y;
+            const bool nx = bx_ < 0, ny = by_ < 0;
+            int lox = 0, hix = 0, loy = 0, hiy = 0;
+            if (vx) {
+                const double kx = __longlong_as_double(bx_);
+                lox = tol_lo(s, m, kx, tol);
+                hix = tol_hi(s, m, lox, kx, tol);
+            }
+            if (vy) {
+                const double ky = __longlong_as_double(by_);
+                loy = tol_lo(s, m, ky, tol);
+                hiy = tol_hi(s, m, loy, ky, tol);
+            }
+            const uint32_t cy = (uint32_t)(ny ? loy : hiy) | (ny ? 0x80000000u : 0u);
+            // arena predecessor of x: y of lane gl-1; for lane 0 the y of lane 15 one load earlier
+            const uint32_t t = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)cy, 0x121, 0xf, 0xf, false);  // row_ror:1
+            const uint32_t px = gl == 0 ? carry : t;
+            carry = t;
+            auto first_pos_prev = [&]() -> int {                         // hi of arena key 0
+                if (hi0 < 0) {
+                    const double kk = __longlong_as_double(k0);
+                    hi0 = tol_hi(s, m, tol_lo(s, m, kk, tol), kk, tol);
+                }
+                return hi0;
+            };
+            if (vx) {
+                const bool none = i == 0;
+                const bool pneg = (px >> 31) != 0;
+                const int pv = (int)(px & 0x7fffffffu);
+                if (nx) {
+                    acc_range(lox, none ? hix : (hix < pv ? hix : pv));
+                } else {
+                    const int prev = none ? 0 : (pneg ? first_pos_prev() : pv);
+                    acc_range(lox > prev ? lox : prev, hix);
+                }
+            }
+            if (vy) {
+                if (ny) {
+                    acc_range(loy, hiy < lox ? hiy : lox);
+                } else {
+                    const int prev = nx ? first_pos_prev() : hix;
+                    acc_range(loy > prev ? loy : prev, hiy);
+                }
+            }
+        }
+    }
+#define TVZ_SUM_STEP(C) cnt += dpp16<C>(cnt);
+    TVZ_ROW16_BUTTERFLY(TVZ_SUM_STEP)
+#undef TVZ_SUM_STEP
+}
+
+// The butterfly behind tol_row_scan: every lane of the group leaves with the group's smallest positions.
+template <int MODE>
+__device__ __forceinline__ void tol_row_reduce(uint32_t &m1, uint32_t &m2, uint32_t (&tk)[kTop]) {
+    if constexpr (MODE == kModeM2) {
+#define TVZ_M2_STEP(C) { const uint32_t p1 = dpp16<C>(m1), p2 = dpp16<C>(m2); \
+        const uint32_t lo = m1 < p1 ? m1 : p1, hi = m1 < p1 ? p1 : m1, r2 = m2 < p2 ? m2 : p2; \
+        m1 = lo; m2 = hi < r2 ? hi : r2; }
+        TVZ_ROW16_BUTTERFLY(TVZ_M2_STEP)
+#undef TVZ_M2_STEP
+    } else if constexpr (MODE == kModeTop5) {
+        // each step merges two DISJOINT sets of positions (every union element is visited once)
+#define TVZ_T5_STEP(C) { uint32_t o[kTop]; \
+        _Pragma("unroll") for (int t = 0; t < kTop; ++t) o[t] = dpp16<C>(tk[t]); \
+        _Pragma("unroll") for (int t = 0; t < kTop; ++t) tol_insert5(tk, o[t]); }
+        TVZ_ROW16_BUTTERFLY(TVZ_T5_STEP)
+#undef TVZ_T5_STEP
     }
 }
 
@@ -204,109 +318,10 @@ __global__ __launch_bounds__(kTolBlock) void ts_match_tol_kernel(
     while (r < n_rows) {
         const int64_t rn = r + stride;
         const Row nrow = load_row(rows + (rn < n_rows ? rn : last_row)); // lands while this row is searched
-        const int64_t *rk = keys + row.off;
-        const int len = row.len;
-        uint32_t cnt = 0, m1 = 0xffffffffu, m2 = 0xffffffffu;
-        uint32_t tk[kTop];
-#pragma unroll
-        for (int t = 0; t < kTop; ++t) tk[t] = 0xffffffffu;
-        auto acc_range = [&](int a, int b) {
-            if (b <= a) return;
-            cnt += (uint32_t)(b - a);
-            if constexpr (MODE == kModeM2) {
-                for (int t = a; t < b; ++t) {
-                    const uint32_t p = (uint32_t)pos[t];
-                    const uint32_t lo = m1 < p ? m1 : p, hi = m1 < p ? p : m1;
-                    m1 = lo;
-                    m2 = m2 < hi ? m2 : hi;
-                }
-            } else if constexpr (MODE == kModeTop5) {
-                for (int t = a; t < b; ++t) tol_insert5(tk, (uint32_t)pos[t]);
-            }
-        };
-        // packed union state a key hands to its arena successor: (neg ? lo : hi) | neg << 31
-        uint32_t carry = 0;
-        int64_t k0 = 0;                      // the row's first arena key (numerically largest negative, if any)
-        int hi0 = -1;                        // its hi, computed by the lane that needs it
-        for (int base = 0; base < len; base += kTolStepKeys) {
-            longlong2 cur[kTolLd];
-#pragma unroll
-            for (int j = 0; j < kTolLd; ++j) {
-                const int i = base + gl * 2 + j * 2 * kGroup;
-                const int64_t *p = (i < len) ? rk + i : keys;                 // unconditional 16-byte loads
-                cur[j] = *reinterpret_cast<const longlong2 *>(p);
-            }
-            if (base == 0) k0 = __shfl(cur[0].x, 0, kGroup);               // group-uniform step
-#pragma unroll
-            for (int j = 0; j < kTolLd; ++j) {
-                const int i = base + gl * 2 + j * 2 * kGroup;
-                const bool vx = i < len, vy = i + 1 < len;
-                const int64_t bx_ = cur[j].x, by_ = cur[j].y;
-                const bool nx = bx_ < 0, ny = by_ < 0;
-                int lox = 0, hix = 0, loy = 0, hiy = 0;
-                if (vx) {
-                    const double kx = __longlong_as_double(bx_);
-                    lox = tol_lo(s, m, kx, tol);
-                    hix = tol_hi(s, m, lox, kx, tol);
-                }
-                if (vy) {
-                    const double ky = __longlong_as_double(by_);
-                    loy = tol_lo(s, m, ky, tol);
-                    hiy = tol_hi(s, m, loy, ky, tol);
-                }
-                const uint32_t cy = (uint32_t)(ny ? loy : hiy) | (ny ? 0x80000000u : 0u);
-                // arena predecessor of x: y of lane gl-1; for lane 0 the y of lane 15 one load earlier
-                const uint32_t t = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)cy, 0x121, 0xf, 0xf, false);  // row_ror:1
-                const uint32_t px = gl == 0 ? carry : t;
-                carry = t;
-                auto first_pos_prev = [&]() -> int {                         // hi of arena key 0
-                    if (hi0 < 0) {
-                        const double kk = __longlong_as_double(k0);
-                        hi0 = tol_hi(s, m, tol_lo(s, m, kk, tol), kk, tol);
-                    }
-                    return hi0;
-                };
-                if (vx) {
-                    const bool none = i == 0;
-                    const bool pneg = (px >> 31) != 0;
-                    const int pv = (int)(px & 0x7fffffffu);
-                    if (nx) {
-                        acc_range(lox, none ? hix : (hix < pv ? hix : pv));
-                    } else {
-                        const int prev = none ? 0 : (pneg ? first_pos_prev() : pv);
-                        acc_range(lox > prev ? lox : prev, hix);
-                    }
-                }
-                if (vy) {
-                    if (ny) {
-                        acc_range(loy, hiy < lox ? hiy : lox);
-                    } else {
-                        const int prev = nx ? first_pos_prev() : hix;
-                        acc_range(loy > prev ? loy : prev, hiy);
-                    }
-                }
-            }
-        }
-#define TVZ_SUM_STEP(C) cnt += dpp16<C>(cnt);
-        TVZ_ROW16_BUTTERFLY(TVZ_SUM_STEP)
-#undef TVZ_SUM_STEP
+        uint32_t cnt, m1, m2, tk[kTop];
+        tol_row_scan<MODE>(keys, keys + row.off, row.len, s, pos, m, tol, gl, cnt, m1, m2, tk);
         const bool hit = (int64_t)cnt >= (int64_t)min_match && row.vid != excl;
-        if (__ballot(hit) != 0ull) {
-            if constexpr (MODE == kModeM2) {
-#define TVZ_M2_STEP(C) { const uint32_t p1 = dpp16<C>(m1), p2 = dpp16<C>(m2); \
-                const uint32_t lo = m1 < p1 ? m1 : p1, hi = m1 < p1 ? p1 : m1, r2 = m2 < p2 ? m2 : p2; \
-                m1 = lo; m2 = hi < r2 ? hi : r2; }
-                TVZ_ROW16_BUTTERFLY(TVZ_M2_STEP)
-#undef TVZ_M2_STEP
-            } else if constexpr (MODE == kModeTop5) {
-                // each step merges two DISJOINT sets of positions (every union element is visited once)
-#define TVZ_T5_STEP(C) { uint32_t o[kTop]; \
-                _Pragma("unroll") for (int t = 0; t < kTop; ++t) o[t] = dpp16<C>(tk[t]); \
-                _Pragma("unroll") for (int t = 0; t < kTop; ++t) tol_insert5(tk, o[t]); }
-                TVZ_ROW16_BUTTERFLY(TVZ_T5_STEP)
-#undef TVZ_T5_STEP
-            }
-        }
+        if (__ballot(hit) != 0ull) tol_row_reduce<MODE>(m1, m2, tk);
         if (hit && gl == 0) {
             int32_t kth;
             if (min_match <= 0) kth = -1;
@@ -430,6 +445,237 @@ __global__ __launch_bounds__(kBlock) void ts_tol_kth_fixup_kernel(
             running += c;
         }
         if (gl == 0) h[2] = kth;
+    }
+}
+
+// ---- the top-k form (tvz_match_tol_topk / tvz_match_tol_sharded) ------------------------------------------------
+// The same row walk; a hit becomes the index lookups' sortable word kth << 44 | video_id << 12 | count
+// (ix_tk_pack: its numeric order is the (kth, video_id, count) order of the blocks tvz_topk_merge takes) and stays
+// on chip.  Each WAVE keeps the k smallest words it has met, ascending and padded with all-ones, in 64 LDS words of
+// its own, next to a 64-word stage that takes the hits below the list's current k-th word.  When the stage may
+// overflow the wave alone ranks list + stage (rank = words below, ties by slot: equal words are all kept) and
+// writes the k smallest back - no block barrier inside the row loop.  Behind the loop's one barrier the block
+// takes the other three lists into the first wave's the same way and writes its k words to part[q][block][..]; nothing grows with the hit count.
+constexpr int kTolTopkMaxK = 64;                       // one word per lane
+constexpr int kTolTopkWaves = kTolBlock / 64;
+constexpr int kTolTopkStaticLds = kTolTopkWaves * 64 * 8 * 2 + 64;   // lists + stages + a few words
+constexpr int kTolTopkMaxLen = 4095;                   // count fits the word's 12 bits; the query fits LDS
+constexpr int kTolReduceBlock = 1024;
+constexpr int kTolReduceWaves = kTolReduceBlock / 64;
+constexpr int kTolReduceLd = 8;                        // lists a wave loads per step (their loads in flight together)
+constexpr unsigned long long kTolPad = ~0ull;
+
+// Row blocks per query of the top-k sweep (one partial list each): about 6,080 blocks in all, at most 2,048 (q1_blocks' own limit: a lone query fills the machine) and at
+// least 95 per query.  The sweep is bound by its searches, not by the lists, and more, shorter blocks balance
+// better (profiles/tol_topk.txt: 64 per query cost 3 % against 96); 95 is what the workspace allows at Q >= 64 -
+// 95 lists of k = 64 words and the query's hit total fit the 4,096 x 12 B of the hit list they replace
+// (include/tvz.h states the formula).
+constexpr int kTolTopkMinBlocks = 95;
+constexpr int kTolTopkGridBlocks = kTolTopkMinBlocks * 64;
+inline int tol_topk_max_blocks(int32_t Q) {
+    const int per_q = kTolTopkGridBlocks / (Q > 0 ? Q : 1);
+    return per_q < kTolTopkMinBlocks ? kTolTopkMinBlocks : per_q > 2048 ? 2048 : per_q;
+}
+// ... so a batch never has more partial lists than this (the workspace's size, monotone in Q)
+inline int64_t tol_topk_max_lists(int32_t Q) {
+    const int64_t big = (int64_t)kTolTopkMinBlocks * Q;
+    return big > kTolTopkGridBlocks ? big : kTolTopkGridBlocks;
+}
+
+// One wave: kept[0..64) (ascending, padded) and stage[0 .. n_stage) -> kept = the k smallest of both, ascending,
+// padded.  Returns the new k-th word (kTolPad while fewer than k are known).
+__device__ __forceinline__ unsigned long long tol_topk_compact(unsigned long long *kept, const unsigned long long *stage,
+                                                               int n_stage, int k, int lane) {
+    const unsigned long long a = kept[lane];
+    const unsigned long long b = lane < n_stage ? stage[lane] : kTolPad;
+    int ra = 0, rb = 0;
+#pragma unroll 4
+    for (int t = 0; t < 64; ++t) {
+        const unsigned long long v = kept[t];                 // the same address in every lane: a broadcast
+        ra += (v < a) | ((v == a) & (t < lane));
+        rb += v <= b;                                         // list slots come before stage slots
+    }
+#pragma unroll 4
+    for (int t = 0; t < n_stage; ++t) {
+        const unsigned long long v = stage[t];
+        ra += v < a;
+        rb += (v < b) | ((v == b) & (t < lane));
+    }
+    __builtin_amdgcn_wave_barrier();                          // every lane has read before any lane writes
+    // the 64 + n_stage ranks are distinct and cover 0..63: every list slot is written exactly once
+    if (ra < 64) kept[ra] = ra < k ? a : kTolPad;
+    if (lane < n_stage && rb < 64) kept[rb] = rb < k ? b : kTolPad;
+    __builtin_amdgcn_wave_barrier();
+    return kept[k - 1];
+}
+
+// One wave takes up to 64 more words (one per lane, kTolPad where there is none) towards its list: those below the
+// list's k-th word `thr` are appended to the stage, which is compacted only when they would not fit - a sorted list
+// from another block rarely has more than a few words below a live threshold, so most lists cost their load and a
+// ballot.  tol_topk_flush compacts what is left.
+__device__ __forceinline__ void tol_topk_take(unsigned long long *kept, unsigned long long *stage, int &n_stage,
+                                              unsigned long long w, unsigned long long &thr, int k, int lane) {
+    bool cand = w < thr;
+    unsigned long long cb = __ballot(cand);
+    if (cb == 0ull) return;
+    if (n_stage + __popcll(cb) > 64) {
+        __builtin_amdgcn_wave_barrier();
+        thr = tol_topk_compact(kept, stage, n_stage, k, lane);
+        n_stage = 0;
+        cand = w < thr;
+        cb = __ballot(cand);
+        if (cb == 0ull) return;
+    }
+    const int before = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(cb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cb, 0u));
+    if (cand) stage[n_stage + before] = w;
+    n_stage += __popcll(cb);
+}
+
+__device__ __forceinline__ void tol_topk_flush(unsigned long long *kept, unsigned long long *stage, int &n_stage,
+                                               unsigned long long &thr, int k, int lane) {
+    if (n_stage == 0) return;
+    __builtin_amdgcn_wave_barrier();
+    thr = tol_topk_compact(kept, stage, n_stage, k, lane);
+    n_stage = 0;
+}
+
+// grid = (row blocks, Q), the sorted query always in LDS (lds_keys >= every query's length, <= kTolTopkMaxLen).
+// part: uint64[Q][gridDim.x][k]; totals[q] (zeroed by ts_tol_sort_kernel) += the block's hits, one atomic.
+template <int MODE>
+__global__ __launch_bounds__(kTolBlock) void ts_tol_topk_kernel(
+    const Row *__restrict__ rows, int64_t n_rows, const int64_t *__restrict__ keys, const double *__restrict__ sv,
+    const int32_t *__restrict__ sp, const int64_t *__restrict__ q_offsets, const int32_t *__restrict__ qm,
+    int32_t lds_keys, double tol, int32_t min_match, const int32_t *__restrict__ exclude_ids, int32_t k,
+    unsigned long long *__restrict__ part, int32_t *__restrict__ totals) {
+    static_assert(MODE == kModeM2 || MODE == kModeTop5, "kth is known inside the sweep for min_match 1..5");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __shared__ unsigned long long s_kept[kTolTopkWaves * 64], s_stg[kTolTopkWaves * 64];
+    __shared__ int32_t s_nhits;
+    const int q = blockIdx.y;
+    const int bx = blockIdx.x;
+    const int64_t at = q_offsets[q] - q_offsets[0];
+    const int32_t m = qm[q];
+    if (m < 0 || m > lds_keys) return;       // refused by the preparation: ts_tol_topk_reduce_kernel flags it
+    double *lv = reinterpret_cast<double *>(smem);
+    int32_t *lp = reinterpret_cast<int32_t *>(smem + (size_t)((lds_keys + 1) & ~1) * 8);
+    for (int e = threadIdx.x; e < m; e += kTolBlock) {
+        lv[e] = sv[at + e];
+        lp[e] = sp[at + e];
+    }
+    const double *s = lv;
+    const int32_t *pos = lp;
+    const int lane = threadIdx.x & 63;
+    const int wv = threadIdx.x >> 6;
+    unsigned long long *kept = s_kept + wv * 64, *stage = s_stg + wv * 64;
+    kept[lane] = kTolPad;
+    if (threadIdx.x == 0) s_nhits = 0;
+    __syncthreads();
+
+    const int gl = threadIdx.x & (kGroup - 1);
+    const int g = threadIdx.x / kGroup;
+    const int32_t excl = exclude_ids ? exclude_ids[q] : -1;
+    const int64_t stride = (int64_t)gridDim.x * kTolGroups;
+    int64_t r = (int64_t)bx * kTolGroups + g;
+    int64_t r_wave = (int64_t)bx * kTolGroups + wv * (64 / kGroup);    // the wave's first group: its longest loop
+    const int64_t last_row = n_rows - 1;
+    Row row = load_row(rows + (r < n_rows ? r : last_row));
+    unsigned long long thr = kTolPad;        // the list's k-th word: hits at or above it cannot enter
+    int n_stage = 0, n_hits = 0;             // wave-uniform
+    while (r_wave < n_rows) {                // wave-uniform: the wave compacts as one
+        const int64_t rn = r + stride;
+        const Row nrow = load_row(rows + (rn < n_rows ? rn : last_row));
+        const bool live = r < n_rows;
+        uint32_t cnt, m1, m2, tk[kTop];
+        tol_row_scan<MODE>(keys, keys + row.off, live ? row.len : 0, s, pos, m, tol, gl, cnt, m1, m2, tk);
+        const bool hit = live && (int64_t)cnt >= (int64_t)min_match && row.vid != excl;
+        if (__ballot(hit) != 0ull) {
+            tol_row_reduce<MODE>(m1, m2, tk);
+            uint32_t kth;
+            if constexpr (MODE == kModeM2) kth = min_match == 1 ? m1 : m2;
+            else kth = tk[min_match - 1];
+            const unsigned long long word = ix_tk_pack((int32_t)kth, row.vid, cnt);
+            const bool lead = hit && gl == 0;
+            n_hits += __popcll(__ballot(lead));
+            const bool cand = lead && word < thr;
+            const unsigned long long cb = __ballot(cand);
+            if (cb != 0ull) {
+                const int before = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(cb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cb, 0u));
+                if (cand) stage[n_stage + before] = word;
+                n_stage += __popcll(cb);
+                if (n_stage > 64 - 64 / kGroup) {                    // the next step may bring one per group
+                    __builtin_amdgcn_wave_barrier();
+                    thr = tol_topk_compact(kept, stage, n_stage, k, lane);
+                    n_stage = 0;
+                }
+            }
+        }
+        row = nrow;
+        r = rn;
+        r_wave += stride;
+    }
+    tol_topk_flush(kept, stage, n_stage, thr, k, lane);
+    if (lane == 0 && n_hits) atomicAdd(&s_nhits, n_hits);            // LDS
+    __syncthreads();
+    if (wv == 0) {                                                   // wave 0 takes the other waves' lists into its own
+#pragma unroll 1
+        for (int j = 1; j < kTolTopkWaves; ++j) tol_topk_take(kept, stage, n_stage, s_kept[j * 64 + lane], thr, k, lane);
+        tol_topk_flush(kept, stage, n_stage, thr, k, lane);
+        if (lane < k) part[((int64_t)q * gridDim.x + bx) * k + lane] = kept[lane];
+    }
+    if (threadIdx.x == 0 && s_nhits) atomicAdd(&totals[q], s_nhits);
+}
+
+// One block per query: the k smallest words of its n_lists sorted partial lists -> d_out[q] = int32[k+1][3]: k rows
+// (video_id, count, kth) ascending, padding (-1, 0, TVZ_KTH_NEVER), then (-1, n_hits, TVZ_KTH_NEVER).  A wave takes
+// every kTolReduceWaves-th list, kTolReduceLd lists per step (their loads in flight together), and keeps its k best as
+// the sweep does; a list whose words are all at or above the wave's k-th word costs its load only.
+// A query the preparation refused (qm < 0 or > lds_keys): all padding, n_hits = INT32_MIN.
+__global__ __launch_bounds__(kTolReduceBlock) void ts_tol_topk_reduce_kernel(
+    const unsigned long long *__restrict__ part, int32_t n_lists, int32_t k, const int32_t *__restrict__ qm,
+    int32_t lds_keys, const int32_t *__restrict__ totals, int32_t *__restrict__ d_out) {
+    __shared__ unsigned long long s_kept[kTolReduceWaves * 64], s_stg[kTolReduceWaves * 64];
+    const int q = blockIdx.x;
+    const int lane = threadIdx.x & 63;
+    const int wv = threadIdx.x >> 6;
+    int32_t *out = d_out + (int64_t)q * (k + 1) * 3;
+    const int32_t m = qm[q];
+    const bool refused = m < 0 || m > lds_keys;
+    unsigned long long *kept = s_kept + wv * 64, *stage = s_stg + wv * 64;
+    kept[lane] = kTolPad;
+    if (!refused) {
+        const unsigned long long *lists = part + (int64_t)q * n_lists * k;
+        unsigned long long thr = kTolPad;
+        int n_stage = 0;
+        for (int l0 = wv; l0 < n_lists; l0 += kTolReduceLd * kTolReduceWaves) {   // wave-uniform
+            unsigned long long w[kTolReduceLd];
+#pragma unroll
+            for (int j = 0; j < kTolReduceLd; ++j) {
+                const int l = l0 + j * kTolReduceWaves;
+                w[j] = (l < n_lists && lane < k) ? lists[(int64_t)l * k + lane] : kTolPad;
+            }
+#pragma unroll
+            for (int j = 0; j < kTolReduceLd; ++j) tol_topk_take(kept, stage, n_stage, w[j], thr, k, lane);
+        }
+        tol_topk_flush(kept, stage, n_stage, thr, k, lane);
+        __syncthreads();
+        if (wv == 0) {
+#pragma unroll 1
+            for (int j = 1; j < kTolReduceWaves; ++j) tol_topk_take(kept, stage, n_stage, s_kept[j * 64 + lane], thr, k, lane);
+            tol_topk_flush(kept, stage, n_stage, thr, k, lane);
+        }
+    }
+    if (wv != 0) return;
+    const unsigned long long w = kept[lane];                             // all padding for a refused query
+    if (lane < k) {
+        const bool pad = w == kTolPad;
+        out[lane * 3 + 0] = pad ? -1 : (int32_t)((w >> 12) & 0xffffffffu);
+        out[lane * 3 + 1] = pad ? 0 : (int32_t)(w & 0xfffu);
+        out[lane * 3 + 2] = pad ? TVZ_KTH_NEVER : (int32_t)(w >> 44);
+    }
+    if (lane == 0) {
+        out[k * 3 + 0] = -1;
+        out[k * 3 + 1] = refused ? INT32_MIN : totals[q];
+        out[k * 3 + 2] = TVZ_KTH_NEVER;
     }
 }
 

@@ -525,11 +525,17 @@ class Store:
 
 def create_schema(url: Optional[str] = None) -> None:
     """db.py:30 (`Base.metadata.create_all`) on its own: the parent of the N-rank service makes the
-    tables once, before the rank processes open the same database side by side."""
+    tables once, before the rank processes open the same database side by side.  A SQLite file is also
+    switched to WAL here, once: the switch needs the file to itself and does not wait in the busy handler,
+    so two ranks issuing it at the same moment (Store's connect hook) lost one of them to "database is
+    locked" at start-up; on a file that is in WAL mode already their pragma changes nothing."""
     url = url or os.environ.get("POSTGRES_URL", DEFAULT_URL)
     eng = create_engine(url)
     try:
         Base.metadata.create_all(eng)
+        if url.startswith("sqlite") and ":memory:" not in url and url not in ("sqlite://", "sqlite:///"):
+            with eng.connect() as c:
+                c.exec_driver_sql("PRAGMA journal_mode=WAL")
     finally:
         eng.dispose()
 

@@ -293,6 +293,9 @@ class RankCorpus:
                  (sharded.ShardedMatcher or RcclShardedMatcher: local match -> per-shard top-k -> one
                  all-gather -> merge, identical on every rank); the k best rows by (kth, video_id) hold
                  the verdict unless the rows sharing the earliest prefix may continue past k;
+      (Either kind carries the ask's tolerance - 0 = the exact verdict, above it the opt-in tolerant match of
+      include/tvz.h - as a fifth field of its header; asks are batched per (min_match, tolerance), so exact and
+      tolerant asks of different ranks share a tick.)
       ASK_EXACT  every row that reaches min_match, as db.find_duplicates returns them (db.py:85-91):
                  each rank asks its own shard (`shard.find_duplicates`, any query length, any min_match),
                  the per-rank hit counts are all-gathered, then the variable-length hit lists (padded to
@@ -303,6 +306,7 @@ class RankCorpus:
 
     `shard`: this rank's DeviceCorpus (or a stand-in with upload/upsert/clear/find_duplicates);
     `matcher.match_topk(d_q, d_off, max_len, min_match, d_excl) -> (merged [Q,k,3], totals [Q])`;
+    a tolerant ask needs `supports_tolerance` on both and passes `tolerance=` to either (never at 0);
     `xdev`: where the exchanged tensors live ("cpu" for gloo, the GPU for RCCL);
     `group`: a process group used by NOTHING else (the tick thread issues collectives on it
     concurrently with whatever the other threads of the process do on theirs);
@@ -362,31 +366,48 @@ class RankCorpus:
         return self.shard.stats()
 
     # ---- matches ----
-    def _ask(self, q, min_match, exclude_id, kind):
+    @property
+    def supports_tolerance(self) -> bool:
+        """Can this corpus answer a tolerant ask?  Only when both its shard (the exact round) and its matcher (the
+        top-k round) can (inspector.Inspector checks it before it takes a match_tolerance)."""
+        return bool(getattr(self.shard, "supports_tolerance", False)) and \
+            bool(getattr(self.matcher, "supports_tolerance", False))
+
+    def _ask(self, q, min_match, exclude_id, kind, tolerance=0.0):
         fut: Future = Future()
         with self._cv:
             if self.broken is not None:
                 raise RuntimeError(f"rank corpus is broken: {self.broken!r}")
             if self._stop:
                 raise RuntimeError("rank corpus is closed")
-            self._pending.append((q, int(min_match), int(exclude_id), int(kind), fut))
+            self._pending.append((q, int(min_match), int(exclude_id), int(kind), fut, float(tolerance)))
             self._cv.notify()
         return fut.result()
 
-    def find_duplicates(self, new_timestamps, min_match: int = 5, exclude_id: int = -1, with_kth: bool = False):
+    def find_duplicates(self, new_timestamps, min_match: int = 5, exclude_id: int = -1, with_kth: bool = False,
+                        tolerance: float = 0.0):
         """with_kth (the driver): the rows that decide the verdict - the merged top-k when it is
         conclusive, every matching row otherwise.  Without (db.find_duplicates, db.py:76-94): every
-        matching row with its count, sorted by video_id."""
+        matching row with its count, sorted by video_id.  `tolerance` > 0: the opt-in tolerant match, same routes;
+        refused HERE, in the caller, when the shard or the matcher cannot - a matcher that throws on one rank
+        inside a tick would strand the others."""
+        tolerance = float(tolerance)
+        if not (0.0 <= tolerance <= sys.float_info.max):
+            raise ValueError(f"tolerance must be finite and >= 0, got {tolerance!r}")
+        if tolerance and not self.supports_tolerance:
+            raise RuntimeError(f"tolerance={tolerance}: this rank corpus has no tolerant match (its shard "
+                               f"{type(self.shard).__name__} or its matcher {type(self.matcher).__name__} lacks "
+                               f"supports_tolerance)")
         q = np.ascontiguousarray(np.asarray(new_timestamps, dtype=np.float64))
         if q.size <= MAX_BATCH_LEN and 1 <= int(min_match) <= 5:
-            rows, total = self._ask(q, min_match, exclude_id, ASK_TOPK)
+            rows, total = self._ask(q, min_match, exclude_id, ASK_TOPK, tolerance)
             hits, exact = _hits_from_topk(rows, total)
             if with_kth and exact:
                 return hits
             if not with_kth and 0 <= total <= len(hits):          # the k best ARE all of them
                 return sorted((v, c) for v, c, _ in hits)
         self.exact_asks += 1
-        hits = self._ask(q, min_match, exclude_id, ASK_EXACT)
+        hits = self._ask(q, min_match, exclude_id, ASK_EXACT, tolerance)
         return hits if with_kth else [(v, c) for v, c, _ in hits]
 
     def _gather(self, t: torch.Tensor) -> torch.Tensor:
@@ -445,23 +466,28 @@ class RankCorpus:
     def _exchange_and_answer(self, take, allmeta):
         Qcap, Lcap = int(allmeta[:, 0].max()), max(int(allmeta[:, 1].max()), 1)
         # 2) the asks, padded to the largest rank's block, as ONE float64 block per rank:
-        #    [Qcap, 4 + Lcap] = (len, exclude, min_match, kind | keys...); small integers are exact in float64
-        blk = np.zeros((Qcap, 4 + Lcap), dtype=np.float64)
-        for i, (q, mm, ex, kind, _) in enumerate(take):
-            blk[i, 0], blk[i, 1], blk[i, 2], blk[i, 3] = len(q), ex, mm, kind
-            blk[i, 4:4 + len(q)] = q
-        g = self._gather(torch.from_numpy(blk).to(self.xdev)).cpu().numpy()       # [world, Qcap, 4 + Lcap]
+        #    [Qcap, 5 + Lcap] = (len, exclude, min_match, kind, tolerance | keys...); small integers are exact in
+        #    float64, and the tolerance IS one
+        blk = np.zeros((Qcap, 5 + Lcap), dtype=np.float64)
+        for i, (q, mm, ex, kind, _, tol) in enumerate(take):
+            blk[i, 0], blk[i, 1], blk[i, 2], blk[i, 3], blk[i, 4] = len(q), ex, mm, kind, tol
+            blk[i, 5:5 + len(q)] = q
+        g = self._gather(torch.from_numpy(blk).to(self.xdev)).cpu().numpy()       # [world, Qcap, 5 + Lcap]
         g_info = g[:, :, :4].astype(np.int64)
-        g_keys = g[:, :, 4:]
+        g_keys = g[:, :, 5:]
         # the global batch, in the same order on every rank: rank-major; rows past a rank's count are padding
         valid = np.arange(Qcap)[None, :] < allmeta[:, 0][:, None]                  # [world, Qcap]
         rr, ii = np.nonzero(valid)
         lens_all, excl_all, mm_all, kind_all = (g_info[rr, ii, c] for c in range(4))
+        tol_all = g[rr, ii, 4]
         mine = rr == self.rank
         mdev = getattr(self.matcher, "dev", torch.device("cpu"))
-        # 3) top-k asks, one batched sharded match per min_match (vectorised un-padding: no per-ask Python)
-        for mm in sorted(set(int(m) for m in mm_all[kind_all == ASK_TOPK])):
-            sel = np.flatnonzero((kind_all == ASK_TOPK) & (mm_all == mm))
+        # 3) top-k asks, one batched sharded match per (min_match, tolerance) (vectorised un-padding: no per-ask
+        #    Python); the matcher hears of a tolerance only when there is one
+        topk = kind_all == ASK_TOPK
+        for mm, tol in sorted(set(zip(mm_all[topk].tolist(), tol_all[topk].tolist()))):
+            tol_kw = {"tolerance": tol} if tol else {}
+            sel = np.flatnonzero(topk & (mm_all == mm) & (tol_all == tol))
             lens = lens_all[sel]
             offs = np.zeros(len(sel) + 1, dtype=np.int64)
             np.cumsum(lens, out=offs[1:])
@@ -475,7 +501,8 @@ class RankCorpus:
                     self._stream = torch.cuda.Stream(mdev, priority=-1)
                 with torch.cuda.device(mdev), torch.cuda.stream(self._stream):
                     d_q, d_off, d_ex, _ = self._stager.put_flat(flat, lens, excl_all[sel].astype(np.int32))
-                    merged, totals = self.matcher.match_topk(d_q, d_off, int(lens.max()) if len(lens) else 0, mm, d_ex)
+                    merged, totals = self.matcher.match_topk(d_q, d_off, int(lens.max()) if len(lens) else 0, mm, d_ex,
+                                                             **tol_kw)
                     Qn, k = merged.shape[0], merged.shape[1]
                     # ONE device-to-host copy per batch: rows and totals together
                     both = torch.cat([merged.reshape(Qn, k * 3), totals.reshape(Qn, 1)], dim=1).cpu().numpy()
@@ -485,7 +512,8 @@ class RankCorpus:
                 d_q = torch.from_numpy(np.ascontiguousarray(flat, dtype=np.float64))
                 d_off = torch.from_numpy(offs)
                 d_ex = torch.from_numpy(excl_all[sel].astype(np.int32))
-                merged, totals = self.matcher.match_topk(d_q, d_off, int(lens.max()) if len(lens) else 0, mm, d_ex)
+                merged, totals = self.matcher.match_topk(d_q, d_off, int(lens.max()) if len(lens) else 0, mm, d_ex,
+                                                         **tol_kw)
                 Qn, k = merged.shape[0], merged.shape[1]
                 both = torch.cat([merged.reshape(Qn, k * 3), totals.reshape(Qn, 1).to(merged.dtype)], dim=1).numpy()
             for j in np.flatnonzero(mine[sel]):
@@ -500,7 +528,9 @@ class RankCorpus:
                 try:
                     if self._local_error is not None:
                         raise self._local_error
-                    local.append(self.shard.find_duplicates(q, int(mm_all[a]), exclude_id=int(excl_all[a]), with_kth=True))
+                    tol_kw = {"tolerance": float(tol_all[a])} if tol_all[a] else {}
+                    local.append(self.shard.find_duplicates(q, int(mm_all[a]), exclude_id=int(excl_all[a]), with_kth=True,
+                                                            **tol_kw))
                 except Exception as e:                       # noqa: BLE001 - this rank's own work: finish the tick's collectives
                     self._local_error = e                    # with a poisoned count (below): every rank stops in this tick
                     local.append([])
@@ -606,7 +636,8 @@ def _hip_parts(rank: int, world: int, group, a):
     # of the top-k blocks per batch) lives behind the C ABI in `comm`
     xdev = f"cuda:{a.device}" if a.backend == "nccl" else "cpu"
     return dict(shard=shard, matcher=matcher, xdev=xdev,
-                inspector=lambda store: Inspector(store, device=f"cuda:{a.device}", max_workers=a.workers))
+                inspector=lambda store: Inspector(store, device=f"cuda:{a.device}", max_workers=a.workers,
+                                                  match_tolerance=a.match_tolerance))
 
 
 def parent_gone(parent_pid: int) -> bool:
@@ -751,11 +782,15 @@ class RankService:
 
     def __init__(self, ranks: int, db_url: str, base_port: int = 5000, backend: str = "gloo", parts: str = "",
                  devices: Optional[List[int]] = None, k: int = 64, cap: int = 4096, workers: int = 16,
-                 tick_s: float = 0.0005, env: Optional[dict] = None, ready_timeout: float = 300.0):
+                 tick_s: float = 0.0005, env: Optional[dict] = None, ready_timeout: float = 300.0,
+                 match_tolerance: float = 0.0):
         import socket
         import subprocess
         from . import db
         self.ranks = int(ranks)
+        match_tolerance = float(match_tolerance)
+        if not (0.0 <= match_tolerance <= sys.float_info.max):           # Inspector's rule, before any rank starts
+            raise ValueError(f"match_tolerance must be finite and >= 0, got {match_tolerance!r}")
         db.create_schema(db_url)                                # once, before N processes open it side by side
         with socket.socket() as s:                              # a free rendezvous port
             s.bind(("127.0.0.1", 0))
@@ -768,7 +803,8 @@ class RankService:
                    "--master-port", str(master_port), "--http-port", str(base_port + 1 + r), "--db", db_url,
                    "--backend", backend, "--device", str(devices[r]), "--k", str(k), "--cap", str(cap),
                    "--workers", str(workers), "--tick-s", str(tick_s), "--parent-pid", str(os.getpid())] + \
-                  (["--parts", parts] if parts else [])
+                  (["--parts", parts] if parts else []) + \
+                  (["--match-tolerance", repr(match_tolerance)] if match_tolerance else [])
             e = dict(os.environ)
             e.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")     # dmabuf IPC: RCCL between processes needs it here
             e.update(env or {})
@@ -825,6 +861,9 @@ def main(argv=None) -> int:  # pragma: no cover - exercised through subprocesses
     ap.add_argument("--cap", type=int, default=4096)
     ap.add_argument("--workers", type=int, default=16)
     ap.add_argument("--tick-s", type=float, default=0.0005)
+    ap.add_argument("--match-tolerance", type=float, default=0.0,
+                    help="seconds; > 0 turns on the opt-in tolerant duplicate match (Inspector(match_tolerance=...)): "
+                         "~0.001 for remuxes, half a frame for frame-rate conversions; 0 = the exact verdict")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--rank", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--master-port", type=int, default=29500, help=argparse.SUPPRESS)
@@ -835,7 +874,7 @@ def main(argv=None) -> int:  # pragma: no cover - exercised through subprocesses
     if a.child:
         return _child_main(a)
     svc = RankService(a.ranks, a.db, base_port=a.port, backend=a.backend, parts=a.parts, k=a.k, cap=a.cap,
-                      workers=a.workers, tick_s=a.tick_s)
+                      workers=a.workers, tick_s=a.tick_s, match_tolerance=a.match_tolerance)
 
     def monitor():
         while True:

@@ -42,6 +42,8 @@ def shard_csr(ids: np.ndarray, offsets: np.ndarray, keys: np.ndarray, rank: int,
 class HipBackend:
     """The product backend: DeviceCorpus.match + the top-k kernels on this rank's GPU."""
 
+    supports_tolerance = True
+
     def __init__(self, corpus):
         from . import corpus as tc
         self._tc = tc
@@ -50,8 +52,11 @@ class HipBackend:
     def match(self, d_q, d_off, max_len, min_match, cap, d_excl):
         return self.corpus.match(d_q, d_off, max_len, min_match, cap, d_exclude_ids=d_excl)
 
-    def local_topk(self, d_q, d_off, max_len, min_match, cap, k, d_excl):
-        """sweep + per-shard top-k behind one library call (tvz_match_topk)."""
+    def local_topk(self, d_q, d_off, max_len, min_match, cap, k, d_excl, tolerance: float = 0.0):
+        """sweep + per-shard top-k behind one library call (tvz_match_topk; with a tolerance tvz_match_tol_topk,
+        the sweep that keeps its k best itself and has no cap)."""
+        if tolerance:
+            return self.corpus.match_tol_topk(d_q, d_off, max_len, tolerance, min_match, k, d_exclude_ids=d_excl)
         return self.corpus.match_topk(d_q, d_off, max_len, min_match, cap, k, d_exclude_ids=d_excl)
 
     def topk_shard(self, hits, hits_n, k):
@@ -77,12 +82,22 @@ class ShardedMatcher:
         # run the all-gather even in a 1-rank group (used to rehearse the RCCL path on one GPU)
         self.collective = self.world > 1 or (always_collective and inited)
 
+    @property
+    def supports_tolerance(self) -> bool:
+        return bool(getattr(self.backend, "supports_tolerance", False))
+
     def submit(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int,
-               min_match: int, d_exclude_ids: Optional[torch.Tensor] = None):
+               min_match: int, d_exclude_ids: Optional[torch.Tensor] = None, tolerance: float = 0.0):
         """Enqueue local match + per-shard top-k and START the all-gather; returns a ticket for
         finish().  Submitting batch i+1 before finishing batch i overlaps the collective of one
-        batch with the match kernels of the next (RCCL runs on its own stream)."""
-        if hasattr(self.backend, "local_topk"):
+        batch with the match kernels of the next (RCCL runs on its own stream).
+        `tolerance` > 0: the opt-in tolerant match; the backend must say `supports_tolerance`."""
+        if tolerance:
+            if not self.supports_tolerance:
+                raise RuntimeError(f"{type(self.backend).__name__} has no tolerant match (supports_tolerance)")
+            local = self.backend.local_topk(d_queries, d_q_offsets, max_query_len, min_match, self.cap,
+                                            self.k, d_exclude_ids, tolerance=float(tolerance))
+        elif hasattr(self.backend, "local_topk"):
             local = self.backend.local_topk(d_queries, d_q_offsets, max_query_len, min_match, self.cap,
                                             self.k, d_exclude_ids)     # [Q, k+1, 3]
         else:
@@ -107,8 +122,9 @@ class ShardedMatcher:
         return self.backend.topk_merge(gathered, self.k)
 
     def match_topk(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int,
-                   min_match: int, d_exclude_ids: Optional[torch.Tensor] = None):
-        return self.finish(self.submit(d_queries, d_q_offsets, max_query_len, min_match, d_exclude_ids))
+                   min_match: int, d_exclude_ids: Optional[torch.Tensor] = None, tolerance: float = 0.0):
+        return self.finish(self.submit(d_queries, d_q_offsets, max_query_len, min_match, d_exclude_ids,
+                                       tolerance=tolerance))
 
 
 def make_comm(device: int, group=None):
@@ -159,9 +175,13 @@ class RcclShardedMatcher:
         self._plans = {}                    # (slot, query tensors, shape) -> the library call's arguments (submit)
         self._lib = _lib
         self._call = comm.lib.tvz_match_sharded
+        self._call_tol = comm.lib.tvz_match_tol_sharded
+
+    supports_tolerance = True
 
     def submit(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int,
-               min_match: int, d_exclude_ids: Optional[torch.Tensor] = None, inputs_ready: bool = False):
+               min_match: int, d_exclude_ids: Optional[torch.Tensor] = None, inputs_ready: bool = False,
+               tolerance: float = 0.0):
         """Enqueue one batch; the returned ticket's tensors belong to this matcher and are
         overwritten by the submit() `n_streams` calls later - consume them (or copy) before that.
         Nothing is allocated per batch: at 8 GPUs a batch is ~0.1 ms of device time, and fresh
@@ -172,8 +192,11 @@ class RcclShardedMatcher:
         is a marker in the caller's queue BEHIND the caller's earlier finish() waits - a chain of
         cross-queue barriers the command processor resolves in 10-40 us, which at 8 GPUs (a batch
         is ~60 us of kernels) left the chip idle between two batches' match kernels
-        (profiles/r3_shard_pipeline.txt)."""
+        (profiles/r3_shard_pipeline.txt).
+        `tolerance` > 0: the opt-in tolerant match (tvz_match_tol_sharded: the sweep keeps its k best itself, `cap`
+        and `algo` play no part); it is part of the plan's key and the plan has its own workspace size."""
         from . import corpus as tc
+        tolerance = float(tolerance)
         i = self._i
         self._i = (i + 1) % len(self.streams)
         st = self.streams[i]
@@ -183,11 +206,16 @@ class RcclShardedMatcher:
         # the un-planned submit was 30 us of interpreter time, the pipeline's actual bound.
         key = (i, d_queries.data_ptr(), d_q_offsets.data_ptr(), int(max_query_len), int(min_match),
                d_exclude_ids.data_ptr() if d_exclude_ids is not None else 0, d_queries.numel(), d_q_offsets.numel())
+        if tolerance:
+            key += (tolerance,)
         plan = self._plans.get(key)
         if plan is None:
             Q = d_q_offsets.numel() - 1
             self.corpus._check_queries(d_queries, d_q_offsets)
-            need = tc.workspace_bytes(Q, max_query_len, self.cap, self.k, self.world, d_queries.numel())
+            if tolerance:
+                need = tc.tol_topk_workspace_bytes(Q, max_query_len, d_queries.numel(), self.k, self.world)
+            else:
+                need = tc.workspace_bytes(Q, max_query_len, self.cap, self.k, self.world, d_queries.numel())
             if self.ws[i] is None or self.ws[i].numel() < need:
                 self.ws[i] = torch.empty(need, dtype=torch.uint8, device=self.dev)
                 self._plans = {k_: v for k_, v in self._plans.items() if k_[0] != i}     # (their workspace is gone)
@@ -196,16 +224,23 @@ class RcclShardedMatcher:
                                torch.empty(Q, dtype=torch.int32, device=self.dev))
                 self._plans = {k_: v for k_, v in self._plans.items() if k_[0] != i}
             merged, totals = self.out[i]
-            args = (self.corpus._h, self.comm._h, key[1], key[2], Q, key[3], key[4], key[5] or None, self.cap, self.k,
-                    merged.data_ptr(), totals.data_ptr(), self.ws[i].data_ptr(), self.ws[i].numel(), self.algo,
-                    st.cuda_stream)
+            if tolerance:
+                call = self._call_tol
+                args = (self.corpus._h, self.comm._h, key[1], key[2], Q, key[3], tolerance, key[4], key[5] or None,
+                        self.k, merged.data_ptr(), totals.data_ptr(), self.ws[i].data_ptr(), self.ws[i].numel(),
+                        st.cuda_stream)
+            else:
+                call = self._call
+                args = (self.corpus._h, self.comm._h, key[1], key[2], Q, key[3], key[4], key[5] or None, self.cap,
+                        self.k, merged.data_ptr(), totals.data_ptr(), self.ws[i].data_ptr(), self.ws[i].numel(),
+                        self.algo, st.cuda_stream)
             if len(self._plans) > 256:
                 self._plans.clear()
-            plan = self._plans[key] = (args, merged, totals, self.ws[i])
-        args, merged, totals, _ws = plan
+            plan = self._plans[key] = (args, merged, totals, self.ws[i], call)
+        args, merged, totals, _ws, call = plan
         if not inputs_ready:
             st.wait_stream(torch.cuda.current_stream(self.dev))   # the queries are complete before the match reads them
-        rc = self._call(*args)
+        rc = call(*args)
         if rc:
             self._lib.check(rc)
         ev = self.events[i]
@@ -223,8 +258,9 @@ class RcclShardedMatcher:
             torch.cuda.current_stream(self.dev).wait_event(ev)
         return merged, totals
 
-    def match_topk(self, d_queries, d_q_offsets, max_query_len, min_match, d_exclude_ids=None):
-        return self.finish(self.submit(d_queries, d_q_offsets, max_query_len, min_match, d_exclude_ids))
+    def match_topk(self, d_queries, d_q_offsets, max_query_len, min_match, d_exclude_ids=None, tolerance: float = 0.0):
+        return self.finish(self.submit(d_queries, d_q_offsets, max_query_len, min_match, d_exclude_ids,
+                                       tolerance=tolerance))
 
 
 def verdicts_from_topk(merged: np.ndarray):
