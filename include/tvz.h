@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define TVZ_VERSION 403 /* 0.4.3: tvz_match_tol_topk / tvz_match_tol_sharded, the tolerant sweep keeps the per-shard top-k itself (0.4.2: tvz_find_duplicates_tol / tvz_match_tol, the opt-in tolerant match (0.4.1: tvz_align takes its output capacity and reports the row count (0.4.0: the index answers every min_match >= 1; tvz_match_topk keeps the top-k inside the lookup; tvz_match_topk_shards))) */
+#define TVZ_VERSION 403 /* 0.4.3 (unchanged by tvz_corpus_tol_index / tvz_corpus_tol_index_stats: new exports only, nothing existing changes): tvz_match_tol_topk / tvz_match_tol_sharded, the tolerant sweep keeps the per-shard top-k itself (0.4.2: tvz_find_duplicates_tol / tvz_match_tol, the opt-in tolerant match (0.4.1: tvz_align takes its output capacity and reports the row count (0.4.0: the index answers every min_match >= 1; tvz_match_topk keeps the top-k inside the lookup; tvz_match_topk_shards))) */
 
 typedef enum tvz_status {
     TVZ_OK = 0,
@@ -469,6 +469,34 @@ int tvz_match_tol_sharded(tvz_corpus *c, tvz_comm *comm, const double *d_queries
                           int32_t Q, int32_t max_query_len, double tol, int32_t min_match,
                           const int32_t *d_exclude_ids, int32_t k, int32_t *d_topk, int32_t *d_totals,
                           void *d_workspace, size_t workspace_bytes, void *hip_stream);
+
+/* Opt-in CELL POSTINGS for the batched tolerant calls, PER HANDLE (default off: a handle that never calls this
+ * behaves and allocates exactly as before).  cell > 0: from now on every generation of the index - tvz_corpus_upload,
+ * tvz_corpus_build_index, the background rebuild - also carries, per cell of `cell` seconds
+ * (cell_of(x) = clamp(floor(x / cell), -2^40, +2^40): keys beyond +-2^40 cells, +-inf among them, share the two end
+ * cells - slow there, still correct), the indexed rows that own a key in it, and the rows' 16-byte entries as they were
+ * at the build's snapshot; a handle that already has an index builds one now (waits for matches in flight).  cell = 0:
+ * off; the next build drops the postings.  cell must be 0 or finite and >= TVZ_TOL_CELL_MIN (x / cell then stays far
+ * inside int64 for real timestamps); anything else returns TVZ_ERR_INVALID and changes nothing.
+ * tvz_match_tol, tvz_match_tol_topk and tvz_match_tol_sharded then answer a batch from the postings near the queries'
+ * timestamps instead of reading the whole corpus - every (query element, cell within tol) posting marks its row, rows
+ * marked often enough are verified by the sweep's own row walk on the generation's row entry, the delta table is
+ * swept as before - whenever tol <= cell, min_match is 1..5 and max_query_len <= 8,192 (list form) / 4,095 (top-k
+ * form).  Every other call does what it did.  The contract above does not change by a bit: ids, counts, kth, totals
+ * and top-k blocks equal those of a handle without postings (the hit lists of tvz_match_tol in a different,
+ * unspecified, order); the workspace formulas still suffice.  tvz_find_duplicates_tol always sweeps.
+ * For which tolerances it pays: where cell (>= tol) is small against the spacing of a video's cuts, so that few rows
+ * own a key near a query's - at tol = cell = 1 ms on a 100k-row corpus a query of 200 timestamps verifies a few
+ * thousand rows instead of reading 100,000 (profiles/tol_index.txt).  At 0.1 s most rows are candidates and the
+ * lookup verifies nearly the whole corpus after paying for the postings: leave it off, or keep cell small and let
+ * such calls sweep (tol > cell).  Cost: 2 B per (cell, row) posting + a directory + 16 B per row and generation, and a
+ * second index build per rebuild. */
+#define TVZ_TOL_CELL_MIN 9.5367431640625e-07 /* 2^-20 s */
+int tvz_corpus_tol_index(tvz_corpus *c, double cell);
+/* *cell = the cell width of the current generation's postings (0: none); out[0] = cells in use, out[1] = cell
+ * postings, out[2] = builds so far that carried cell postings, out[3] = rows in the delta table the lookup shares
+ * with the exact index.  out[0], out[1], out[3] are 0 while there are none.  cell / out may be NULL. */
+int tvz_corpus_tol_index_stats(tvz_corpus *c, double *cell, int64_t out[4]);
 
 /* ------------------------------------------------------------------------
  * Frame feeder I/O - the host side of what replaces the stderr pipe of

@@ -133,6 +133,18 @@ class DeviceCorpus:
         return dict(zip(("buckets", "keys_walked_on", "max_walk", "external_lists", "external_postings", "sub_indexes"),
                         (int(x) for x in v)))
 
+    def set_tol_index(self, cell: float) -> None:
+        """tvz_corpus_tol_index: cell > 0 makes every index generation of this handle also carry cell postings of `cell`
+        seconds (and builds them now if the handle has an index), which the batched tolerant calls then use for
+        tol <= cell; 0 turns them off (the next build drops them).  Results never depend on it."""
+        _lib.check(self.lib.tvz_corpus_tol_index(self._h, float(cell)))
+
+    def tol_index_stats(self) -> dict:
+        """cell (0.0: no cell postings) / cells / postings / builds that carried cell postings / delta_rows."""
+        cell, v = C.c_double(), (C.c_int64 * 4)()
+        _lib.check(self.lib.tvz_corpus_tol_index_stats(self._h, C.byref(cell), v))
+        return dict(zip(("cell", "cells", "postings", "builds", "delta_rows"), [float(cell.value)] + [int(x) for x in v]))
+
     def stats(self) -> Tuple[int, int, int]:
         a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
         _lib.check(self.lib.tvz_corpus_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))

@@ -93,6 +93,30 @@ __device__ __forceinline__ uint32_t ix_slot(int64_t k, int dir_log2) {
     return (q1_mix(k) * 0x9E3779B1u) >> (32 - dir_log2);
 }
 
+// Cell postings (tvz_tol_index_kernels.h): the same directory and posting build over CELL ids instead of key bits.
+// cell_of(x) = clamp(floor(x / w), -L, +L), computed in double (IEEE division, correctly rounded) and then converted:
+// monotone in x; keys beyond +-L w - +-inf among them - land in the two end cells.  Never kEmpty (a NaN pattern).
+constexpr double kTolCellLimit = 1099511627776.0;        // L = 2^40
+__host__ __device__ __forceinline__ int64_t tol_cell_of(double x, double w) {
+    double c = floor(x / w);
+    c = c < -kTolCellLimit ? -kTolCellLimit : c;
+    c = c > kTolCellLimit ? kTolCellLimit : c;
+    return (int64_t)c;
+}
+// What the build hashes for key i of a row (rk = the row's keys in the arena): its bits (cellw == 0, the exact index)
+// or its cell id (cellw > 0).  false = no posting for this key: its cell is the cell of the key before it.  A row's
+// arena order is monotone in value on either side of zero (tvz_tol_kernels.h) and a negative key's cell is below 0, so
+// equal cells are neighbours: every (cell, row) pair is posted ONCE, and a (cell, sub-index) count stays within the
+// sub-index's 2^14 rows - its uint16 - however wide the cell.
+__device__ __forceinline__ bool ix_build_key(const int64_t *__restrict__ rk, int i, double cellw, int64_t &k) {
+    k = rk[i];
+    if (cellw > 0.0) {
+        k = tol_cell_of(__longlong_as_double(k), cellw);
+        if (i > 0 && tol_cell_of(__longlong_as_double(rk[i - 1]), cellw) == k) return false;
+    }
+    return true;
+}
+
 // every entry = {free, 0, 0, counts 0}; the fill cursors = 0
 __global__ __launch_bounds__(kBlock) void ix_clear_kernel(uint4 *__restrict__ dir16, size_t n16, int es16,
                                                           uint4 *__restrict__ zero16, size_t nz16,
@@ -146,7 +170,7 @@ __device__ __forceinline__ int64_t ix_find(unsigned char *dir, int es, int dir_b
 __global__ __launch_bounds__(kBlock) void ix_count_kernel(const Row *__restrict__ rows, int64_t n_rows,
                                                           const int64_t *__restrict__ keys, unsigned char *dir,
                                                           int es, int ks, int dir_bits, int32_t *__restrict__ ivid,
-                                                          IxBuildInfo *info) {
+                                                          IxBuildInfo *info, double cellw) {
     const int lane = threadIdx.x & 63;
     for (int64_t r = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); r < n_rows;
          r += (int64_t)gridDim.x * (kBlock / 64)) {
@@ -156,7 +180,9 @@ __global__ __launch_bounds__(kBlock) void ix_count_kernel(const Row *__restrict_
         uint32_t mine = 0;
         for (int i = lane; i < row.len; i += 64) {
             bool is_new;
-            const int64_t s = ix_find<true>(dir, es, dir_bits, keys[row.off + i], is_new);
+            int64_t bk;
+            if (!ix_build_key(keys + row.off, i, cellw, bk)) continue;
+            const int64_t s = ix_find<true>(dir, es, dir_bits, bk, is_new);
             if (s < 0) { info->failed = 1; continue; }
             unsigned char *e = dir + (size_t)s * es;
             if (ks) atomicAdd(reinterpret_cast<uint32_t *>(e + 16) + (sub >> 1), 1u << ((sub & 1u) * 16u));
@@ -214,7 +240,7 @@ __global__ __launch_bounds__(kBlock) void ix_offsets_kernel(unsigned char *dir, 
 __global__ __launch_bounds__(kBlock) void ix_fill_kernel(const Row *__restrict__ rows, int64_t n_rows,
                                                          const int64_t *__restrict__ keys, unsigned char *dir, int es,
                                                          int ks, int dir_bits, uint32_t *__restrict__ fillc,
-                                                         uint16_t *__restrict__ post) {
+                                                         uint16_t *__restrict__ post, double cellw) {
     const int lane = threadIdx.x & 63;
     const int fw = ks ? ks / 2 : 1;                    // fill-cursor words per entry
     for (int64_t r = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); r < n_rows;
@@ -223,7 +249,9 @@ __global__ __launch_bounds__(kBlock) void ix_fill_kernel(const Row *__restrict__
         const uint32_t sub = (uint32_t)(r >> kSubLog2);
         for (int i = lane; i < row.len; i += 64) {
             bool is_new;
-            const int64_t s = ix_find<false>(dir, es, dir_bits, keys[row.off + i], is_new);
+            int64_t bk;
+            if (!ix_build_key(keys + row.off, i, cellw, bk)) continue;
+            const int64_t s = ix_find<false>(dir, es, dir_bits, bk, is_new);
             if (s < 0) continue;                       // cannot happen after a successful count pass
             const unsigned char *e = dir + (size_t)s * es;
             uint32_t p = reinterpret_cast<const DirHead *>(e)->base;
@@ -260,7 +288,7 @@ __global__ void ix_part_clear_kernel(uint32_t *__restrict__ hist, int n, IxBuild
 // in turns), counts in an LDS histogram and adds its non-zero counts to the global ones
 __global__ __launch_bounds__(kBlock) void ix_partition_kernel(
     const Row *__restrict__ rows, int64_t n_rows, int32_t rpb, const int64_t *__restrict__ keys, int dir_bits,
-    int n_parts, uint32_t *__restrict__ gcnt, int32_t *__restrict__ ivid) {
+    int n_parts, uint32_t *__restrict__ gcnt, int32_t *__restrict__ ivid, double cellw) {
     extern __shared__ uint32_t ix_part_sh[];
     uint32_t *hist = ix_part_sh;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -271,8 +299,10 @@ __global__ __launch_bounds__(kBlock) void ix_partition_kernel(
     for (int64_t r = r0 + wave; r < r1; r += kBlock / 64) {
         const Row row = load_row(rows + r);
         if (lane == 0) ivid[r] = row.vid;
-        for (int i = lane; i < row.len; i += 64)
-            atomicAdd(&hist[ix_part_of(keys[row.off + i], dir_bits)], 1u);
+        for (int i = lane; i < row.len; i += 64) {
+            int64_t bk;
+            if (ix_build_key(keys + row.off, i, cellw, bk)) atomicAdd(&hist[ix_part_of(bk, dir_bits)], 1u);
+        }
     }
     __syncthreads();
     for (int i = threadIdx.x; i < n_parts; i += kBlock)
@@ -292,7 +322,7 @@ constexpr int kIxStagePairs = 8192;        // 96 KB of LDS: 8 B key + 4 B row
 
 __global__ __launch_bounds__(kIxScatterBlock) void ix_scatter_kernel(
     const Row *__restrict__ rows, int64_t n_rows, int32_t rpb, const int64_t *__restrict__ keys, int dir_bits,
-    int n_parts, uint32_t *__restrict__ gcur, int64_t *__restrict__ pkeys, uint32_t *__restrict__ prows) {
+    int n_parts, uint32_t *__restrict__ gcur, int64_t *__restrict__ pkeys, uint32_t *__restrict__ prows, double cellw) {
     extern __shared__ __attribute__((aligned(16))) unsigned char ix_scat_sh[];
     int64_t *st_k = reinterpret_cast<int64_t *>(ix_scat_sh);                       // [kIxStagePairs]
     uint32_t *st_r = reinterpret_cast<uint32_t *>(st_k + kIxStagePairs);           // [kIxStagePairs]
@@ -307,8 +337,10 @@ __global__ __launch_bounds__(kIxScatterBlock) void ix_scatter_kernel(
     const int64_t r1 = r0 + rpb < n_rows ? r0 + rpb : n_rows;
     for (int64_t r = r0 + wave; r < r1; r += kIxScatterBlock / 64) {
         const Row row = load_row(rows + r);
-        for (int i = lane; i < row.len; i += 64)
-            atomicAdd(&hist[ix_part_of(keys[row.off + i], dir_bits)], 1u);
+        for (int i = lane; i < row.len; i += 64) {
+            int64_t bk;
+            if (ix_build_key(keys + row.off, i, cellw, bk)) atomicAdd(&hist[ix_part_of(bk, dir_bits)], 1u);
+        }
     }
     __syncthreads();
     // local and global ranges: thread t owns the slices [t * per, (t + 1) * per)
@@ -337,7 +369,8 @@ __global__ __launch_bounds__(kIxScatterBlock) void ix_scatter_kernel(
     for (int64_t r = r0 + wave; r < r1; r += kIxScatterBlock / 64) {
         const Row row = load_row(rows + r);
         for (int i = lane; i < row.len; i += 64) {
-            const int64_t k = keys[row.off + i];
+            int64_t k;
+            if (!ix_build_key(keys + row.off, i, cellw, k)) continue;
             const uint32_t p = ix_part_of(k, dir_bits);
             const uint32_t j = atomicAdd(&hist[p], 1u);
             const uint32_t t = lstart[p] + j;

@@ -34,6 +34,7 @@
 #include "tvz_index_kernels.h"
 #include "tvz_index_wave_kernels.h"
 #include "tvz_tol_kernels.h"
+#include "tvz_tol_index_kernels.h"
 
 namespace {
 
@@ -146,6 +147,16 @@ struct IndexBuf {
     int64_t n_main = 0;               // rows [0, n_main) are indexed
     int64_t n_post = 0, n_distinct = 0;
     int64_t n_spilled = 0, n_ext = 0, max_spill = 0, ext_used = 0;   // bucket directory: keys outside their home bucket / with external lists
+    // Cell postings of the tolerant lookup (tvz_tol_index_kernels.h), carried only while the handle asks for them
+    // (t_cell > 0: the cell width this generation was built with): a classic directory over the CELL ids of the same
+    // rows [0, n_main), built from the same snapshot, and the rows' 16-byte entries as they were at that snapshot.
+    DevBuf<unsigned char> tdir;
+    DevBuf<uint16_t> tpost;
+    DevBuf<Row> irows;
+    double t_cell = 0.0;
+    int t_dir_log2 = 0, t_slice_log2 = 0, t_ks = 0;
+    int64_t t_post = 0, t_cells = 0;
+    int t_dir_bits() const { return ix_dir_bits(t_dir_log2, t_slice_log2); }
 };
 
 struct Index {
@@ -155,6 +166,9 @@ struct Index {
     int64_t n_delta = 0;
     int64_t builds = 0;
     int64_t hint_post = 0, hint_distinct = 0;   // postings / distinct keys of the last build (sizes the next directory)
+    double tol_cell = 0.0;            // tvz_corpus_tol_index: > 0 = every build also makes cell postings of this width
+    int64_t tol_builds = 0;           // builds that carried them
+    int64_t thint_post = 0, thint_distinct = 0;   // the same hints for the cell directory
     std::unordered_map<int64_t, int32_t> delta_slot;   // row index -> slot in buf[cur].drows
     // build scratch (only the builder touches it)
     IxBuildInfo *info = nullptr;      // device
@@ -438,7 +452,7 @@ int64_t fillc_words(int log2, int ks) { return ((int64_t)1 << log2) * (ks ? ks /
 // (key, row) pairs of rows [0, n_rows) grouped by directory slice in ix.pkeys / ix.prows; ix.pcnt holds the per-slice
 // counts, then the slice starts (ix.pcnt.p + kIxMaxParts), then the scatter cursors.
 int build_partition(tvz_corpus *c, const Row *d_rows, int64_t n_rows, int64_t live_keys, int64_t pairs, int bits,
-                    int64_t n_parts, int32_t *ivid, hipStream_t st) {
+                    int64_t n_parts, int32_t *ivid, hipStream_t st, double cellw = 0.0) {
     Index &ix = c->ix;
     if (int rc = ensure(ix.pkeys, pairs, 0)) return rc;
     if (int rc = ensure(ix.prows, pairs, 0)) return rc;
@@ -450,13 +464,13 @@ int build_partition(tvz_corpus *c, const Row *d_rows, int64_t n_rows, int64_t li
     const int32_t rpb = (int32_t)std::min<int64_t>(4096, std::max<int64_t>(kBlock / 64 * 2, 16 * n_parts / mean_len));
     hipLaunchKernelGGL(ix_part_clear_kernel, dim3(4), dim3(kBlock), 0, st, cnt, (int)n_parts, ix.info);
     hipLaunchKernelGGL(ix_partition_kernel, dim3((unsigned)tvz::ceil_div(n_rows, rpb)), dim3(kBlock), (size_t)n_parts * 4, st,
-                       d_rows, n_rows, rpb, c->keys.p, bits, (int)n_parts, cnt, ivid);
+                       d_rows, n_rows, rpb, c->keys.p, bits, (int)n_parts, cnt, ivid, cellw);
     hipLaunchKernelGGL(ix_part_scan_kernel, dim3(1), dim3(1024), 0, st, cnt, (int)n_parts, start, cur, ix.info);
     // the scatter: rows worth about one staging area per block
     const int32_t srpb = (int32_t)std::max<int64_t>(1, kIxStagePairs / mean_len);
     const size_t sclds = (size_t)kIxStagePairs * 12 + ((size_t)3 * n_parts + 1) * 4;
     hipLaunchKernelGGL(ix_scatter_kernel, dim3((unsigned)tvz::ceil_div(n_rows, srpb)), dim3(kIxScatterBlock), sclds,
-                       st, d_rows, n_rows, srpb, c->keys.p, bits, (int)n_parts, cur, ix.pkeys.p, ix.prows.p);
+                       st, d_rows, n_rows, srpb, c->keys.p, bits, (int)n_parts, cur, ix.pkeys.p, ix.prows.p, cellw);
     return TVZ_OK;
 }
 
@@ -514,9 +528,17 @@ int build_bucket_dir(tvz_corpus *c, IndexBuf &b, const Row *d_rows, int64_t n_ro
 // The classic directory (tvz_index_kernels.h): ONE directory over the distinct keys of all rows, load <= 0.25
 // (kIxDirLoadPct).  Sized from a guess - a fingerprint corpus repeats its keys many times over (cuts sit on frame
 // grids) - and doubled while too crowded.
+// cellw > 0: the CELL directory of the tolerant lookup instead - the same build over cell ids (ix_build_key) into
+// b.tdir / b.tpost, sized from its own hints (the first time: from the key directory's distinct keys, an upper bound
+// on the distinct cells - every key has one cell).  Every (cell, row) pair is posted ONCE (ix_build_key drops a key
+// whose cell is its arena predecessor's): the uint16 counts per (cell, sub-index) rely on it.
 int build_classic(tvz_corpus *c, IndexBuf &b, const Row *d_rows, int64_t n_rows, int64_t live_keys,
-                  const GenSizes &sz, int n_sub, hipStream_t st, IxBuildInfo &info) {
+                  const GenSizes &sz, int n_sub, hipStream_t st, IxBuildInfo &info, double cellw = 0.0) {
     Index &ix = c->ix;
+    const bool cells = cellw > 0.0;
+    DevBuf<unsigned char> &b_dir = cells ? b.tdir : b.dir;
+    DevBuf<uint16_t> &b_post = cells ? b.tpost : b.post;
+    const int64_t hint_post = cells ? ix.thint_post : ix.hint_post, hint_distinct = cells ? ix.thint_distinct : ix.hint_distinct;
     const int ks = ix_ks(n_sub), es = ix_entry_bytes(ks);
     const int64_t post_cap = sz.post();
     // the size for `distinct` keys: load <= kIxDirLoadPct - unless that directory is too large for the
@@ -534,11 +556,13 @@ int build_classic(tvz_corpus *c, IndexBuf &b, const Row *d_rows, int64_t n_rows,
         if (!partitionable(lg) && partitionable(lg - 1) && (double)((int64_t)1 << (lg - 1)) >= 2.0 * distinct) --lg;
         return lg;
     };
-    if (int rc = ensure(b.post, post_cap, 0)) return rc;
+    if (int rc = ensure(b_post, post_cap, 0)) return rc;
     int log2 = 10;
-    if (ix.hint_post > 0) {
+    if (hint_post > 0) {
         // the last build knows how often this corpus repeats its keys: one pass, no retry
-        log2 = size_for((double)ix.hint_distinct * (double)live_keys / (double)ix.hint_post * 1.25);
+        log2 = size_for((double)hint_distinct * (double)live_keys / (double)hint_post * 1.25);
+    } else if (cells && ix.hint_distinct > 0) {
+        log2 = size_for((double)ix.hint_distinct);     // (the key directory of this snapshot was built a moment ago)
     } else {
         while (((int64_t)1 << log2) < live_keys / 8) ++log2;
     }
@@ -550,7 +574,7 @@ int build_classic(tvz_corpus *c, IndexBuf &b, const Row *d_rows, int64_t n_rows,
     while (true) {
         TVZ_REQUIRE(log2 <= 30, "index directory would exceed 2^30 entries");
         const int64_t dn = (int64_t)1 << log2;
-        if (int rc = ensure(b.dir, classic_dir_bytes(log2, es), 0)) return rc;
+        if (int rc = ensure(b_dir, classic_dir_bytes(log2, es), 0)) return rc;
         // Directory slices of ~32 KB (one block builds a slice in LDS; three such blocks leave room on
         // a CU for a lookup's block); larger ones if the slices would otherwise outnumber what the
         // partition kernels keep in LDS.  A directory of more than kIxMaxParts slices of 128 KB takes
@@ -564,24 +588,24 @@ int build_classic(tvz_corpus *c, IndexBuf &b, const Row *d_rows, int64_t n_rows,
         if (!partitioned) slice_log2 = log2;
         const int bits = ix_dir_bits(log2, slice_log2);
         if (partitioned) {
-            if (int rc = build_partition(c, d_rows, n_rows, live_keys, sz.pairs, bits, n_parts, b.ivid.p, st)) return rc;
+            if (int rc = build_partition(c, d_rows, n_rows, live_keys, sz.pairs, bits, n_parts, b.ivid.p, st, cellw)) return rc;
             uint32_t *start = ix.pcnt.p + kIxMaxParts, *ptot = start + 2 * kIxMaxParts + 1, *pstart = ptot + kIxMaxParts;
             uint32_t *scratch = pstart + kIxMaxParts + 1;
             const size_t slds = std::max<size_t>(((size_t)es << slice_log2), (size_t)kIxSliceLdsFloor);
             hipLaunchKernelGGL(ix_slice_count_kernel, dim3((unsigned)n_parts), dim3(kIxSliceBlock), slds, st,
-                               ix.pkeys.p, ix.prows.p, start, b.dir.p, es, ks, bits, ptot, ix.info);
+                               ix.pkeys.p, ix.prows.p, start, b_dir.p, es, ks, bits, ptot, ix.info);
             hipLaunchKernelGGL(ix_part_scan_kernel, dim3(1), dim3(1024), 0, st, ptot, (int)n_parts, pstart, scratch,
                                static_cast<IxBuildInfo *>(nullptr));
             hipLaunchKernelGGL(ix_slice_fill_kernel, dim3((unsigned)n_parts), dim3(kIxSliceBlock), slds, st,
-                               ix.pkeys.p, ix.prows.p, start, pstart, b.dir.p, es, ks, bits, b.post.p);
+                               ix.pkeys.p, ix.prows.p, start, pstart, b_dir.p, es, ks, bits, b_post.p);
         } else {
             const int64_t fillc = tvz::round_up(fillc_words(log2, ks), 4);
             if (int rc = ensure(ix.fillc, fillc, 0)) return rc;
-            hipLaunchKernelGGL(ix_clear_kernel, dim3(2048), dim3(kBlock), 0, st, reinterpret_cast<uint4 *>(b.dir.p),
+            hipLaunchKernelGGL(ix_clear_kernel, dim3(2048), dim3(kBlock), 0, st, reinterpret_cast<uint4 *>(b_dir.p),
                                (size_t)(dn * es / 16), es / 16, reinterpret_cast<uint4 *>(ix.fillc.p),
                                (size_t)(fillc / 4), ix.info);
             hipLaunchKernelGGL(ix_count_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, d_rows, n_rows, c->keys.p,
-                               b.dir.p, es, ks, bits, b.ivid.p, ix.info);
+                               b_dir.p, es, ks, bits, b.ivid.p, ix.info, cellw);
         }
         if (int rc = read_build_info(ix, st, info)) return rc;
         if (!info.failed && (int64_t)info.n_distinct * 2 <= dn) {            // accepted up to load 0.5; sized for kIxDirLoadPct
@@ -593,14 +617,20 @@ int build_classic(tvz_corpus *c, IndexBuf &b, const Row *d_rows, int64_t n_rows,
             const int fit = size_for((double)info.n_distinct);
             if (!shrunk && (fit + 1 < log2 || fit > log2)) { log2 = fit; shrunk = true; continue; }   // (or too small for the target load)
             if (partitioned) break;
-            hipLaunchKernelGGL(ix_offsets_kernel, dim3((unsigned)tvz::ceil_div(dn, kBlock)), dim3(kBlock), 0, st, b.dir.p,
+            hipLaunchKernelGGL(ix_offsets_kernel, dim3((unsigned)tvz::ceil_div(dn, kBlock)), dim3(kBlock), 0, st, b_dir.p,
                                (size_t)dn, es, ks, ix.info);
             hipLaunchKernelGGL(ix_fill_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, d_rows, n_rows, c->keys.p,
-                               b.dir.p, es, ks, bits, ix.fillc.p, b.post.p);
+                               b_dir.p, es, ks, bits, ix.fillc.p, b_post.p, cellw);
             if (int rc = read_build_info(ix, st, info)) return rc;
             break;
         }
         ++log2;                                       // too crowded (or a slice overflowed): twice the directory
+    }
+    if (cells) {
+        b.t_ks = ks;
+        b.t_dir_log2 = log2;
+        b.t_slice_log2 = slice_log2;
+        return TVZ_OK;
     }
     b.ks = ks;
     b.dir_log2 = log2;
@@ -612,8 +642,10 @@ int build_classic(tvz_corpus *c, IndexBuf &b, const Row *d_rows, int64_t n_rows,
 // generation `b` on stream `st`, and wait for it.  `b` must have no reader; nothing of the handle's
 // published state is touched.  rows_cap / keys_cap: the corpus RESERVATION the buffers are sized
 // with, so the rebuilds that upserts trigger allocate nothing until the corpus outgrows it.
+// cellw > 0 (the handle's tvz_corpus_tol_index width, read under its lock by the caller): the generation also gets the
+// cell postings and the rows' entries of this snapshot.
 int build_kernels(tvz_corpus *c, IndexBuf &b, const Row *d_rows, int64_t n_rows, int64_t live_keys,
-                  int64_t rows_cap, int64_t keys_cap, hipStream_t st) {
+                  int64_t rows_cap, int64_t keys_cap, hipStream_t st, double cellw) {
     Index &ix = c->ix;
     // posting offsets and counts are 32-bit: a larger shard is swept (shard it over more GPUs)
     if (n_rows == 0 || live_keys >= (int64_t)0xfffffff0LL)
@@ -643,6 +675,23 @@ int build_kernels(tvz_corpus *c, IndexBuf &b, const Row *d_rows, int64_t n_rows,
     b.ext_used = info.ext_cursor;
     ix.hint_post = (int64_t)info.cursor;
     ix.hint_distinct = (int64_t)info.n_distinct;
+    b.t_cell = 0.0;
+    b.t_post = b.t_cells = 0;
+    if (cellw > 0.0) {
+        IxBuildInfo tinfo{};
+        if (int rc = build_classic(c, b, d_rows, n_rows, live_keys, sz, n_sub, st, tinfo, cellw)) return rc;
+        if ((int64_t)tinfo.cursor > live_keys)         // (one posting per cell and row: at most one per key)
+            return tvz::fail(TVZ_ERR_INVALID, "internal: cell index holds %u postings for %lld keys", tinfo.cursor,
+                             (long long)live_keys);
+        if (int rc = ensure(b.irows, sz.rows, 0)) return rc;
+        TVZ_HIP(hipMemcpyAsync(b.irows.p, d_rows, (size_t)n_rows * sizeof(Row), hipMemcpyDeviceToDevice, st));
+        if (int rc = wait_stream_polling(st, ix.build_ev)) return rc;
+        b.t_cell = cellw;
+        b.t_post = (int64_t)tinfo.cursor;
+        b.t_cells = (int64_t)tinfo.n_distinct;
+        ix.thint_post = b.t_post;
+        ix.thint_distinct = b.t_cells;
+    }
     if (b.nb && tvz_debug())
         fprintf(stderr, "[tvz] bucket directory: %u buckets (%.1f MB) for %u keys / %u postings, fill %.2f, %u keys walked on "
                 "(max %u buckets), %u external lists (%.1f MB)\n", b.nb, b.nb * 128e-6, info.n_distinct, info.cursor,
@@ -659,11 +708,12 @@ int build_index(tvz_corpus *c) {
     const int64_t n_rows = (int64_t)c->h_rows.size();
     if (n_rows == 0 || c->live_keys >= (int64_t)0xfffffff0LL) return TVZ_OK;
     IndexBuf &b = ix.buf[ix.cur ^ 1];
-    if (int rc = build_kernels(c, b, c->rows.p, n_rows, c->live_keys, c->rows.cap, c->keys.cap, c->mstream))
+    if (int rc = build_kernels(c, b, c->rows.p, n_rows, c->live_keys, c->rows.cap, c->keys.cap, c->mstream, ix.tol_cell))
         return rc;
     ix.cur ^= 1;
     ix.valid = true;
     ++ix.builds;
+    if (b.t_cell > 0.0) ++ix.tol_builds;
     // size the OTHER generation and the snapshot buffer now, while nobody is waiting: a background
     // rebuild then allocates nothing (hipMalloc / hipFree synchronise the whole device - a lookup in
     // flight would wait for them).  `post` as large as the current generation's: nothing for a bucket directory,
@@ -678,6 +728,12 @@ int build_index(tvz_corpus *c) {
     (void)ensure(o.post, n.post.cap, 0);
     (void)ensure(o.ivid, n.ivid.cap, 0);
     (void)ensure(o.drows, n.drows.cap, 0);
+    if (n.t_cell > 0.0) {                          // the cell postings' buffers, the same way
+        (void)ensure(o.tdir, 2 * classic_dir_bytes(n.t_dir_log2, ix_entry_bytes(n.t_ks)), 0);
+        if (n.t_slice_log2 == n.t_dir_log2) (void)ensure(ix.fillc, 2 * fillc_words(n.t_dir_log2, n.t_ks), 0);
+        (void)ensure(o.tpost, n.tpost.cap, 0);
+        (void)ensure(o.irows, n.irows.cap, 0);
+    }
     (void)ensure(ix.snap_rows, sz.rows, 0);
     (void)ensure(ix.dead_rows, n.drows.cap, 0);
     return TVZ_OK;
@@ -701,6 +757,7 @@ int rebuild_in_background(tvz_corpus *c, std::unique_lock<std::shared_mutex> &lk
     const double t_dbg0 = tvz_debug() ? tvz_now_us() : 0.0;
     const int64_t n_snap = (int64_t)c->h_rows.size();
     const int64_t live = c->live_keys, rows_cap = c->rows.cap, keys_cap = c->keys.cap;
+    const double cellw = ix.tol_cell;
     const int shadow = ix.cur ^ 1;
     if (int rc = wait_generation_idle(c, shadow)) return rc;
     if (int rc = ensure(ix.snap_rows, std::max<int64_t>(rows_cap, n_snap), 0)) return rc;
@@ -714,7 +771,7 @@ int rebuild_in_background(tvz_corpus *c, std::unique_lock<std::shared_mutex> &lk
     ix.since_snap.clear();
     lk.unlock();
     const double t_dbg1 = tvz_debug() ? tvz_now_us() : 0.0;
-    int rc = build_kernels(c, ix.buf[shadow], ix.snap_rows.p, n_snap, live, rows_cap, keys_cap, ix.bstream);
+    int rc = build_kernels(c, ix.buf[shadow], ix.snap_rows.p, n_snap, live, rows_cap, keys_cap, ix.bstream, cellw);
     char msg[512];
     if (rc) snprintf(msg, sizeof msg, "%s", tvz::err_buf());
     const double t_dbg2 = tvz_debug() ? tvz_now_us() : 0.0;
@@ -756,6 +813,7 @@ int rebuild_in_background(tvz_corpus *c, std::unique_lock<std::shared_mutex> &lk
     ix.cur = shadow;
     ix.valid = true;
     ++ix.builds;
+    if (nb.t_cell > 0.0) ++ix.tol_builds;
     return TVZ_OK;
 }
 
@@ -1918,6 +1976,43 @@ static int tvz_corpus_index_stats_impl(tvz_corpus *c, int64_t *n_indexed, int64_
     return TVZ_OK;
 }
 
+static int tvz_corpus_tol_index_impl(tvz_corpus *c, double cell) {
+    TVZ_REQUIRE(c != nullptr, "corpus is NULL");
+    if (!(cell == 0.0 || (cell >= TVZ_TOL_CELL_MIN && cell <= DBL_MAX)))     // refuses NaN, inf, negatives, tiny cells
+        return tvz::fail(TVZ_ERR_INVALID, "cell must be 0 (off) or finite and >= %g s (got %g)", TVZ_TOL_CELL_MIN, cell);
+    DeviceGuard dg(c->device);
+    std::unique_lock<std::shared_mutex> lk(c->mu);
+    wait_no_build(c, lk);
+    Index &ix = c->ix;
+    const double before = ix.tol_cell;
+    ix.tol_cell = cell;
+    if (cell == 0.0 || !ix.valid || ix.now().t_cell == cell) return TVZ_OK;   // off: the next build drops the postings
+    int rc = drain(c);
+    if (!rc) {
+        c->ix_next_try_rows = 2 * (int64_t)c->h_rows.size();
+        rc = build_index(c);
+    }
+    // a build that failed (no memory for the postings) leaves the handle as it was asked before this call - and, as
+    // after any failed build, without an index until the next one: every match sweeps
+    if (rc) ix.tol_cell = before;
+    return rc;
+}
+
+static int tvz_corpus_tol_index_stats_impl(tvz_corpus *c, double *cell, int64_t *out) {
+    TVZ_REQUIRE(c != nullptr, "corpus is NULL");
+    std::shared_lock<std::shared_mutex> lk(c->mu);
+    const Index &ix = c->ix;
+    const bool on = ix.valid && ix.now().t_cell > 0.0;
+    if (cell) *cell = on ? ix.now().t_cell : 0.0;
+    if (out) {
+        out[0] = on ? ix.now().t_cells : 0;
+        out[1] = on ? ix.now().t_post : 0;
+        out[2] = ix.tol_builds;
+        out[3] = on ? ix.n_delta : 0;
+    }
+    return TVZ_OK;
+}
+
 static int tvz_match_impl(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets,
                          int32_t Q, int32_t max_query_len, int32_t min_match,
                          const int32_t *d_exclude_ids, int32_t cap, int32_t *d_hits,
@@ -2330,7 +2425,7 @@ int check_tol(double tol) {
 // The sweep, one launch: the sorted query's values sv[..) and positions sp[..) (per query, see ts_match_tol_kernel),
 // in LDS when lds_keys > 0 (every query of the launch has at most lds_keys values).
 template <bool HOSTOUT>
-int launch_tol(tvz_corpus *c, int64_t n_rows, const double *sv, const int32_t *sp, const int64_t *q_offsets,
+int launch_tol(tvz_corpus *c, const Row *rows, int64_t n_rows, const double *sv, const int32_t *sp, const int64_t *q_offsets,
                const int32_t *qm, int32_t m_one, int32_t lds_keys, int32_t Q, double tol, int32_t min_match,
                const int32_t *d_exclude_ids, int32_t exclude_one, int32_t cap, int32_t *d_hits, int32_t *d_hits_n,
                int blocks_x, HostOut ho, hipStream_t st) {
@@ -2340,7 +2435,7 @@ int launch_tol(tvz_corpus *c, int64_t n_rows, const double *sv, const int32_t *s
     const dim3 grid((unsigned)blocks_x, (unsigned)Q);
     return by_mode(min_match, [&](auto mode) {
 #define TVZ_TOL(LDSQ)                                                                                                 \
-    hipLaunchKernelGGL((ts_match_tol_kernel<mode.value, HOSTOUT, LDSQ>), grid, dim3(kTolBlock), lds, st, c->rows.p,   \
+    hipLaunchKernelGGL((ts_match_tol_kernel<mode.value, HOSTOUT, LDSQ>), grid, dim3(kTolBlock), lds, st, rows,        \
                        n_rows, c->keys.p, sv, sp, q_offsets, qm, m_one, lds_keys, tol, min_match, d_exclude_ids,      \
                        exclude_one, cap, d_hits, d_hits_n, ho)
         if (lds_keys > 0) TVZ_TOL(true); else TVZ_TOL(false);
@@ -2377,6 +2472,50 @@ TolWs tol_ws_layout(void *base, int32_t Q, int64_t keys) {
 size_t tol_ws_fixed(int32_t Q) { return al256((size_t)Q * 4) + 256 + 2 * 255; }
 int64_t tol_ws_room(int32_t Q, size_t bytes) {
     return bytes < tol_ws_fixed(Q) ? -1 : (int64_t)((bytes - tol_ws_fixed(Q)) / 12);
+}
+
+// ---- the lookup through cell postings (tvz_tol_index_kernels.h) ----
+// Taken when the current generation carries cell postings at least as wide as the tolerance, min_match is one the row
+// walk resolves itself (1..5) and the sorted queries fit LDS; every other call sweeps as before.  Caller holds mu.
+bool tol_index_usable(const tvz_corpus *c, double tol, int32_t min_match, int32_t lds_keys) {
+    const Index &ix = c->ix;
+    return ix.valid && ix.now().t_cell > 0.0 && tol <= ix.now().t_cell && min_match >= 1 && min_match <= kTop &&
+           lds_keys > 0 && tol_index_lds_bytes(lds_keys, lds_keys <= kTolIxSlotKeys) + kTolIxStaticLds <= (size_t)kLdsPerWorkgroup;
+}
+
+// Blocks per query: a large batch fills the chip with one block per query, which then walks every sub-index; a small
+// one gives every sub-index (or run of them) a block of its own and, below that, splits a sub-index's candidates over
+// up to eight blocks (each repeats the cheap pass A) - about 1,024 blocks in all, at most kTolIxMaxGroups per query.
+struct TolIxShape {
+    int spb = 1, groups = 1, split = 1;
+    int blocks() const { return groups * split; }
+};
+TolIxShape tol_index_shape(int n_sub, int32_t Q) {
+    TolIxShape sh;
+    const int want = std::max(1, 1024 / std::max(Q, 1));
+    sh.groups = std::max(1, std::min(std::min(n_sub, kTolIxMaxGroups), want));
+    sh.spb = (int)tvz::ceil_div(n_sub, sh.groups);
+    sh.groups = (int)tvz::ceil_div(n_sub, sh.spb);
+    sh.split = std::max(1, std::min(std::min(8, want / sh.groups), kTolIxMaxGroups / sh.groups));
+    return sh;
+}
+
+template <bool TOPK>
+int launch_tol_index(tvz_corpus *c, const TolIxShape &sh, const double *sv, const int32_t *sp, const int64_t *q_offsets,
+                     const int32_t *qm, int32_t lds_keys, int32_t Q, double tol, int32_t min_match,
+                     const int32_t *d_exclude_ids, int32_t cap, int32_t *d_hits, int32_t *d_hits_n, int32_t k,
+                     unsigned long long *part, int32_t n_lists, hipStream_t st) {
+    const IndexBuf &b = c->ix.now();
+    const dim3 grid((unsigned)sh.blocks(), (unsigned)Q);
+    const bool keep_slots = sh.spb > 1 && lds_keys <= kTolIxSlotKeys;
+    return by_mode<false>(min_match, [&](auto mode) {
+        hipLaunchKernelGGL((ts_tol_index_kernel<mode.value, TOPK>), grid, dim3(kTolBlock),
+                           tol_index_lds_bytes(lds_keys, keep_slots), st,
+                           b.tdir.p, b.t_dir_bits(), b.t_ks, b.tpost.p, b.ivid.p, b.irows.p, b.n_main, b.n_sub, sh.spb,
+                           sh.split, b.t_cell, c->keys.p, sv, sp, q_offsets, qm, lds_keys, tol, min_match, d_exclude_ids,
+                           cap, d_hits, d_hits_n, k, part, n_lists, keep_slots ? 1 : 0);
+        return launched();
+    });
 }
 
 }  // namespace
@@ -2427,7 +2566,7 @@ static int tvz_find_duplicates_tol_impl(tvz_corpus *c, const double *h_query, in
         region = (int)(tvz::ceil_div(n_rows, (int64_t)blocks * kTolGroups) * kTolGroups);
         const HostOut ho{s->hits.d, s->counts.d, region};
         const int32_t lds_keys = m <= kTolLdsKeys ? (int32_t)std::max<int64_t>(m, 1) : 0;
-        if (int rc = launch_tol<true>(c, n_rows, dv, dp, nullptr, nullptr, (int32_t)m, lds_keys, 1, tol, min_match,
+        if (int rc = launch_tol<true>(c, c->rows.p, n_rows, dv, dp, nullptr, nullptr, (int32_t)m, lds_keys, 1, tol, min_match,
                                       nullptr, excl, 0, nullptr, nullptr, blocks, ho, s->stream))
             return rc;
         if (!fixup) return TVZ_OK;
@@ -2468,7 +2607,20 @@ static int tvz_match_tol_impl(tvz_corpus *c, const double *d_queries, const int6
     const int64_t n_rows = (int64_t)c->h_rows.size();
     if (int rc = wait_mutations(c, st)) return rc;
     const int32_t lds_keys = max_query_len <= kTolLdsKeys ? std::max(max_query_len, 1) : 0;
-    if (int rc = launch_tol<false>(c, n_rows, w.sv, w.sp, d_q_offsets, w.qm, 0, lds_keys, Q, tol, min_match,
+    if (tol_index_usable(c, tol, min_match, lds_keys)) {
+        // the indexed rows through their cell postings, the delta table by the sweep: every row is in exactly one
+        const Index &ix = c->ix;
+        if (int rc = launch_tol_index<false>(c, tol_index_shape(ix.now().n_sub, Q), w.sv, w.sp, d_q_offsets, w.qm, lds_keys,
+                                             Q, tol, min_match, d_exclude_ids, cap, d_hits, d_hits_n, 0, nullptr, 0, st))
+            return rc;
+        if (ix.n_delta)
+            if (int rc = launch_tol<false>(c, ix.now().drows.p, ix.n_delta, w.sv, w.sp, d_q_offsets, w.qm, 0, lds_keys, Q,
+                                           tol, min_match, d_exclude_ids, -1, cap, d_hits, d_hits_n,
+                                           q1_blocks(ix.n_delta, Q), HostOut{}, st))
+                return rc;
+        return record(c, st);
+    }
+    if (int rc = launch_tol<false>(c, c->rows.p, n_rows, w.sv, w.sp, d_q_offsets, w.qm, 0, lds_keys, Q, tol, min_match,
                                    d_exclude_ids, -1, cap, d_hits, d_hits_n, q1_blocks(n_rows, Q), HostOut{}, st))
         return rc;
     if (min_match > kTop && n_rows) {
@@ -2556,18 +2708,37 @@ int tvz_match_tol_topk_local(tvz_corpus *c, const double *d_queries, const int64
     std::shared_lock<std::shared_mutex> lk(c->mu);
     const int64_t n_rows = (int64_t)c->h_rows.size();
     if (int rc = wait_mutations(c, st)) return rc;
-    const int blocks = n_rows ? std::min(q1_blocks(n_rows, Q), tol_topk_max_blocks(Q)) : 0;
+    // The rows the sweep reads and the lists in front of its own: with cell postings the indexed rows are answered by
+    // the lookup (one list per block of it) and the sweep is left the delta table; the selection takes all lists alike.
+    const Row *sweep_rows = c->rows.p;
+    int64_t sweep_n = n_rows;
+    int lists0 = 0;
+    TolIxShape sh;
+    if (tol_index_usable(c, tol, min_match, lds_keys)) {
+        const Index &ix = c->ix;
+        sh = tol_index_shape(ix.now().n_sub, Q);
+        lists0 = sh.blocks();
+        sweep_rows = ix.now().drows.p;
+        sweep_n = ix.n_delta;
+    }
+    // (lists0 <= kTolIxMaxGroups < kTolTopkMinBlocks: the workspace's tol_topk_max_lists(Q) lists still suffice)
+    const int blocks = sweep_n ? std::min(q1_blocks(sweep_n, Q), tol_topk_max_blocks(Q) - lists0) : 0;
+    const int n_lists = lists0 + blocks;
+    if (lists0)
+        if (int rc = launch_tol_index<true>(c, sh, t.sv, t.sp, d_q_offsets, t.qm, lds_keys,
+                                            Q, tol, min_match, d_exclude_ids, 0, nullptr, w.totals, k, w.part, n_lists, st))
+            return rc;
     if (blocks) {
         const dim3 grid((unsigned)blocks, (unsigned)Q);
         if (int rc = by_mode<false>(min_match, [&](auto mode) {
-                hipLaunchKernelGGL((ts_tol_topk_kernel<mode.value>), grid, dim3(kTolBlock), lds, st, c->rows.p, n_rows,
+                hipLaunchKernelGGL((ts_tol_topk_kernel<mode.value>), grid, dim3(kTolBlock), lds, st, sweep_rows, sweep_n,
                                    c->keys.p, t.sv, t.sp, d_q_offsets, t.qm, lds_keys, tol, min_match, d_exclude_ids, k,
-                                   w.part, w.totals);
+                                   w.part, n_lists, lists0, w.totals);
                 return launched();
             }))
             return rc;
     }
-    hipLaunchKernelGGL(ts_tol_topk_reduce_kernel, dim3((unsigned)Q), dim3(kTolReduceBlock), 0, st, w.part, blocks, k,
+    hipLaunchKernelGGL(ts_tol_topk_reduce_kernel, dim3((unsigned)Q), dim3(kTolReduceBlock), 0, st, w.part, n_lists, k,
                        t.qm, lds_keys, w.totals, d_out);
     TVZ_HIP(hipGetLastError());
     return record(c, st);
@@ -2650,6 +2821,14 @@ TVZ_EXPORT int tvz_corpus_bucket_stats(tvz_corpus *c, int64_t out[6]) {
 TVZ_EXPORT int tvz_corpus_index_stats(tvz_corpus *c, int64_t *n_indexed_rows, int64_t *n_delta_rows,
                                       int64_t *n_postings, int64_t *n_distinct_keys, int64_t *n_builds) {
     TVZ_GUARDED(tvz_corpus_index_stats_impl(c, n_indexed_rows, n_delta_rows, n_postings, n_distinct_keys, n_builds));
+}
+
+TVZ_EXPORT int tvz_corpus_tol_index(tvz_corpus *c, double cell) {
+    TVZ_GUARDED(tvz_corpus_tol_index_impl(c, cell));
+}
+
+TVZ_EXPORT int tvz_corpus_tol_index_stats(tvz_corpus *c, double *cell, int64_t out[4]) {
+    TVZ_GUARDED(tvz_corpus_tol_index_stats_impl(c, cell, out));
 }
 
 TVZ_EXPORT int tvz_corpus_upsert(tvz_corpus *c, int32_t video_id, const double *h_keys, int64_t n) {

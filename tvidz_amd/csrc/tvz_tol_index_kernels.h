@@ -1,0 +1,320 @@
+// tvz_tol_index_kernels.h — the tolerant match through CELL postings (tvz_corpus_tol_index), gfx950 wave64.
+// Included by tvz_match.hip only, after tvz_index_kernels.h (directory format, tol_cell_of) and tvz_tol_kernels.h
+// (tol_row_scan / tol_row_reduce, the top-k lists).
+//
+// The sweeps of tvz_tol_kernels.h read every row to learn, almost always, that it has nothing near the query.  A
+// generation of the index that carries cell postings knows, per cell of `w` seconds, the indexed rows that own a key in
+// it (a classic directory over cell ids, postings ordered by sub-index of 2^14 rows - the exact index's format and
+// build), and the 16-byte entry of every indexed row as it was at the build's snapshot.
+//
+// Probe range.  For query element q the cells [tol_cell_of(a), tol_cell_of(b)] are probed, with
+//     a = fl(fl(q - tol) - m),   b = fl(fl(q + tol) + m),   m = w / 1024 (exact: a power-of-two scaling).
+// Claim: every key with  key == q or fabs(fl(q - key)) <= tol  has  tol_cell_of(key)  inside, given tol <= w.
+//   tol_cell_of is monotone (a correctly rounded division by w > 0, floor and clamp all are), so a <= key <= b is
+//   enough wherever a and b are not clamped away.  Take the upper side, the lower one mirrors it.
+//   * fl(key - q) <= tol and fl is monotone with fl(tol) = tol, so key - q < tol + ulp(tol) <= tol + 2^-52 w.
+//   * b >= (q + tol + m) (1 - 2^-53)^2, so b >= q + tol + m - 2^-52 (|q| + tol + m).
+//   * For |q| <= 2^41 w that error is below 2^-11 w + 2^-51 w, and m = 2^-10 w covers it and the 2^-52 w above: key <= b.
+//   * For |q| > 2^41 w: a matching key has |key| >= |q| - tol - 2^-52 w > 2^40 w = L w and the sign of q, so it lies in
+//     the end cell on q's side; b >= q (1 - 2^-52) (or a <= q (1 - 2^-52) for negative q) is beyond L w too, and the
+//     other end of the range is at most (at least) that end cell by the clamp.  +-inf: a = b = q, the end cell, and
+//     the == term's only partner is the same infinity, in that cell.
+//   The range is short: (b - a) / w <= 2 + 2^-9 + rounding below 2^-11, so floor(b / w) - floor(a / w) <= 3: at most
+//   FOUR cells per element (tests/test_tol_index_cpu.py checks claim and length on random and adversarial values).
+//
+// One block per (query, group of sub-indexes, part): per sub-index
+//   pass A  thread t takes (element, cell) pairs of the sorted query in LDS: probes the cell's directory entry and sets,
+//           for every posting of the cell in this sub-index, the row's bit in seen1 - or in seen2 if seen1 was set.
+//           A row that reaches min_match >= 2 has two distinct matching elements, each with a posting of the row in its
+//           range: the candidates are seen2 (seen1 for min_match 1).  A superset - cells straddle the tolerance;
+//   rank    prefix popcounts of the candidate bitmap;
+//   verify  candidate j (of this block's part) -> bitmap word by a search of the ranks, bit by selection; a 16-lane
+//           group runs the sweeps' own row walk (tol_row_scan) on the GENERATION's row entry: count and kth are the
+//           sweep's, bit for bit; rows replaced since the build (ivid < 0) are the delta sweep's;
+//   emit    as the sweep of the same form: hits staged in LDS and appended (tvz_match_tol), or the k best words kept
+//           per wave and written as one partial list with one atomic for the total (tvz_match_tol_topk).
+// Nothing in device memory grows with candidates or hits.
+#pragma once
+
+namespace {
+
+constexpr int kTolIxWords = kSubRows / 32;               // words per bitmap: a sub-index exactly
+constexpr int kTolIxWpt = kTolIxWords / kTolBlock;       // bitmap words per thread (rank)
+static_assert(kTolIxWpt >= 1 && kTolIxWpt * kTolBlock == kTolIxWords, "whole bitmap words per thread");
+constexpr int kTolIxCells = 4;                           // cells per element the proof above allows
+constexpr int kTolIxMaxGroups = 64;                      // blocks per query at most (the top-k form: one list each)
+// static LDS of the two forms (bitmaps 4 KiB, ranks 1 KiB, the parked arguments and a few words; + the hit stage or
+// the waves' lists): an upper bound, tests/test_tol_index_cpu.py holds the code objects against it
+constexpr int kTolIxStaticLds = kTolIxWords * 10 + 256 + (kQ1Stage * 12 > kTolTopkWaves * 64 * 16 ? kQ1Stage * 12 : kTolTopkWaves * 64 * 16);
+
+__device__ __forceinline__ void tol_probe_range(double q, double tol, double w, int64_t &c_lo, int64_t &c_hi) {
+    const double m = w * 0x1p-10;
+    c_lo = tol_cell_of((q - tol) - m, w);
+    c_hi = tol_cell_of((q + tol) + m, w);
+}
+
+// What pass A, a candidate's first two loads and the output paths read, parked in LDS: as kernel arguments they would
+// sit in scalar registers across the row walk, which needs every one of them (the compiler spilled 30 of them to
+// vector lanes); read back from LDS they are vector registers for as long as they are used.
+struct TolIxParked {
+    const unsigned char *dir;
+    const uint16_t *post;
+    double cellw, tol;
+    const int32_t *ivid;
+    const Row *irows;
+    const int64_t *keys;
+    int32_t *hits, *hits_n;
+    unsigned long long *part;
+    int32_t dir_bits, ks, cap, n_lists;
+    int32_t slots_at, excl;             // LDS offset of the kept directory slots (one per pass-A task); 0 = none kept
+};
+constexpr uint32_t kTolIxNoSlot = 0xffffffffu;     // a task's cell has no directory entry (or the task has no cell)
+constexpr uint32_t kTolIxRedo = 0xfffffffeu;       // a task with cells beyond its first: not kept, probed again
+// A block that walks several sub-indexes keeps every task's directory slot from its first pass A (4 B per task, 16 B
+// per query timestamp) when that fits next to the sorted query: the later passes then read the entry straight away -
+// no cell arithmetic, no probe sequence.  Queries too long for it probe again per sub-index; same results.
+constexpr int kTolIxSlotKeys = 2048;
+inline size_t tol_index_lds_bytes(int32_t lds_keys, bool keep_slots) {
+    return tol_lds_bytes(lds_keys) + (keep_slots ? (size_t)lds_keys * kTolIxCells * 4 : 0);
+}
+
+// grid = (n_groups * split, Q).  Block bx walks sub-indexes [grp * spb, ..) with grp = bx / split and verifies the
+// candidates j with j / 16 mod split == bx mod split.  Sorted queries as ts_match_tol_kernel takes them (always in LDS).
+// TOPK: part = uint64[Q][n_lists][k], this block's list is number bx; totals[q] += its hits.
+// else: hits = [Q][cap][3], hits_n[q] += (zeroed by ts_tol_sort_kernel; the delta sweep adds to the same count).
+template <int MODE, bool TOPK>
+__global__ __launch_bounds__(kTolBlock) void ts_tol_index_kernel(
+    const unsigned char *__restrict__ dir, int dir_bits, int ks, const uint16_t *__restrict__ post,
+    const int32_t *__restrict__ ivid, const Row *__restrict__ irows, int64_t n_indexed, int32_t n_sub, int32_t spb,
+    int32_t split, double cellw, const int64_t *__restrict__ keys, const double *__restrict__ sv,
+    const int32_t *__restrict__ sp, const int64_t *__restrict__ q_offsets, const int32_t *__restrict__ qm,
+    int32_t lds_keys, double tol, int32_t min_match, const int32_t *__restrict__ exclude_ids, int32_t cap,
+    int32_t *__restrict__ hits, int32_t *__restrict__ hits_n, int32_t k, unsigned long long *__restrict__ part,
+    int32_t n_lists, int32_t keep_slots) {
+    static_assert(MODE == kModeM2 || MODE == kModeTop5, "kth is known inside the walk for min_match 1..5");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __shared__ uint32_t s_bm1[kTolIxWords], s_bm2[kTolIxWords];
+    __shared__ uint16_t s_rank[kTolIxWords];
+    __shared__ uint32_t s_ws[kTolBlock / 64];
+    __shared__ int32_t s_nhits, s_stage_base;
+    __shared__ TolIxParked s_arg;
+    __shared__ int32_t s_stage[TOPK ? 1 : kQ1Stage * 3];
+    __shared__ unsigned long long s_kept[TOPK ? kTolTopkWaves * 64 : 1], s_stg[TOPK ? kTolTopkWaves * 64 : 1];
+    const int q = blockIdx.y;
+    const int bx = blockIdx.x;
+    const int64_t at = q_offsets[q] - q_offsets[0];
+    const int32_t m = qm[q];
+    if (m < 0 || m > lds_keys) {             // refused by the preparation
+        if (!TOPK && threadIdx.x == 0 && bx == 0) hits_n[q] = INT32_MIN;
+        return;                              // (TOPK: ts_tol_topk_reduce_kernel flags it)
+    }
+    double *lv = reinterpret_cast<double *>(smem);
+    int32_t *lp = reinterpret_cast<int32_t *>(smem + (size_t)((lds_keys + 1) & ~1) * 8);
+    for (int e = threadIdx.x; e < m; e += kTolBlock) {
+        lv[e] = sv[at + e];
+        lp[e] = sp[at + e];
+    }
+    const double *s = lv;
+    const int32_t *pos = lp;
+    const int lane = threadIdx.x & 63;
+    const int wv = threadIdx.x >> 6;
+    const int gl = threadIdx.x & (kGroup - 1);
+    const int g = threadIdx.x / kGroup;
+    unsigned long long *kept = s_kept + (TOPK ? wv * 64 : 0), *stage = s_stg + (TOPK ? wv * 64 : 0);
+    if (TOPK) kept[lane] = kTolPad;
+    for (int i = threadIdx.x; i < kTolIxWords; i += kTolBlock) { s_bm1[i] = 0; s_bm2[i] = 0; }
+    if (threadIdx.x == 0) {
+        s_nhits = 0;
+        s_arg.dir = dir;
+        s_arg.post = post;
+        s_arg.cellw = cellw;
+        s_arg.tol = tol;
+        s_arg.ivid = ivid;
+        s_arg.irows = irows;
+        s_arg.keys = keys;
+        s_arg.hits = hits;
+        s_arg.hits_n = hits_n;
+        s_arg.part = part;
+        s_arg.n_lists = n_lists;
+        s_arg.dir_bits = dir_bits;
+        s_arg.ks = ks;
+        s_arg.cap = cap;
+        s_arg.slots_at = keep_slots ? ((lds_keys + 1) & ~1) * 12 : 0;     // behind the sorted query (tol_lds_bytes)
+        s_arg.excl = exclude_ids ? exclude_ids[q] : -1;
+    }
+    if (keep_slots) {                        // nothing kept yet: the first pass A probes
+        uint32_t *ts = reinterpret_cast<uint32_t *>(smem + ((lds_keys + 1) & ~1) * 12);
+        for (int e = threadIdx.x; e < m * kTolIxCells; e += kTolBlock) ts[e] = kTolIxRedo;
+    }
+    __syncthreads();
+
+    const int grp = bx / split, prt = bx - grp * split;
+    const int sub_lo = grp * spb;
+    const int sub_hi = sub_lo + spb < n_sub ? sub_lo + spb : n_sub;
+    unsigned long long thr = kTolPad;        // TOPK: the wave's k-th word
+    int n_stage = 0, n_hits = 0;             // TOPK: wave-uniform
+
+    for (int sub = sub_lo; sub < sub_hi; ++sub) {
+        // ---- pass A ----
+        const unsigned char *a_dir = s_arg.dir;
+        const uint16_t *a_post = s_arg.post;
+        const double a_w = s_arg.cellw, a_tol = s_arg.tol;
+        const int a_ks = s_arg.ks, es = 16 + 2 * a_ks;
+        const int dir_log2 = s_arg.dir_bits & 0xff;
+        const uint32_t smask = (1u << (s_arg.dir_bits >> 8)) - 1u;      // probes wrap inside the directory slice
+        uint32_t *tslot = s_arg.slots_at ? reinterpret_cast<uint32_t *>(smem + s_arg.slots_at) : nullptr;
+        auto probe = [&](int64_t cell) -> uint32_t {             // the directory slot of a cell, kTolIxNoSlot if none
+            uint32_t slot = ix_slot(cell, dir_log2);
+            for (int probes = 0; probes < kIxMaxProbe; ++probes) {
+                const int2 h = *reinterpret_cast<const int2 *>(a_dir + (size_t)slot * es);
+                const int64_t ek = (int64_t)(((uint64_t)(uint32_t)h.y << 32) | (uint32_t)h.x);
+                if (ek == cell) return slot;
+                if (ek == kEmpty) break;
+                slot = (slot & ~smask) | ((slot + 1) & smask);
+            }
+            return kTolIxNoSlot;
+        };
+        auto walk = [&](uint32_t slot) {                         // the entry's postings in this sub-index mark their rows
+            if (slot == kTolIxNoSlot) return;
+            const unsigned char *e = a_dir + (size_t)slot * es;
+            const int4 h = *reinterpret_cast<const int4 *>(e);
+            uint32_t p = (uint32_t)h.z, len = (uint32_t)h.w;
+            if (a_ks) {
+                const uint16_t *cn = reinterpret_cast<const uint16_t *>(e + 16);
+                for (int t = 0; t < sub; ++t) p += cn[t];
+                len = cn[sub];
+            }
+            for (uint32_t t = 0; t < len; ++t) {
+                const uint32_t r = a_post[p + t];
+                const uint32_t bit = 1u << (r & 31u);
+                const uint32_t old = atomicOr(&s_bm1[r >> 5], bit);
+                if (min_match >= 2 && (old & bit)) atomicOr(&s_bm2[r >> 5], bit);
+            }
+        };
+        for (int task = threadIdx.x; task < m * kTolIxCells; task += kTolBlock) {
+            uint32_t slot0 = tslot ? tslot[task] : kTolIxRedo;
+            if (slot0 == kTolIxRedo) {
+                const int j = task & (kTolIxCells - 1);
+                int64_t c_lo, c_hi;
+                tol_probe_range(s[task / kTolIxCells], a_tol, a_w, c_lo, c_hi);
+                slot0 = c_lo + j <= c_hi ? probe(c_lo + j) : kTolIxNoSlot;
+                // the last task of an element takes whatever lies beyond the fourth cell: nothing, by the proof
+                const bool more = j == kTolIxCells - 1 && c_lo + j < c_hi;
+                if (more)
+                    for (int64_t cell = c_lo + j + 1; cell <= c_hi; ++cell) walk(probe(cell));
+                if (tslot) tslot[task] = more ? kTolIxRedo : slot0;
+            }
+            walk(slot0);
+        }
+        __syncthreads();
+        // ---- rank: candidates before every bitmap word (thread t owns words t * kTolIxWpt ..) ----
+        const uint32_t *cand = min_match >= 2 ? s_bm2 : s_bm1;
+        uint32_t c = 0;
+#pragma unroll
+        for (int w = 0; w < kTolIxWpt; ++w) c += __popc(cand[threadIdx.x * kTolIxWpt + w]);
+        const uint32_t incl = wave_scan_incl(c);
+        if (lane == 63) s_ws[wv] = incl;
+        __syncthreads();
+        uint32_t run = incl - c, n_cand = 0;
+#pragma unroll
+        for (int w = 0; w < kTolBlock / 64; ++w) {
+            const uint32_t a = s_ws[w];
+            if (w < wv) run += a;
+            n_cand += a;
+        }
+#pragma unroll
+        for (int w = 0; w < kTolIxWpt; ++w) {
+            s_rank[threadIdx.x * kTolIxWpt + w] = (uint16_t)run;
+            run += __popc(cand[threadIdx.x * kTolIxWpt + w]);
+        }
+        __syncthreads();
+        // ---- verify + emit: group g of part prt takes candidates prt * 16 + g, + split * 16, ... ----
+        const uint32_t row0 = (uint32_t)sub << kSubLog2, n_idx = (uint32_t)n_indexed;   // (rows are counted in 31 bits)
+        for (uint32_t base = (uint32_t)(prt * kTolGroups + wv * (64 / kGroup)); base < n_cand;
+             base += (uint32_t)(split * kTolGroups)) {       // wave-uniform: the wave compacts as one
+            const uint32_t idx = base + (uint32_t)(g & (64 / kGroup - 1));
+            const bool in = idx < n_cand;
+            int lo = 0, hi = kTolIxWords;                    // the last word whose rank is <= idx: it holds candidate idx
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if ((uint32_t)s_rank[mid] <= idx) lo = mid; else hi = mid;
+            }
+            uint32_t word = cand[lo];
+            for (uint32_t skip = in ? idx - (uint32_t)s_rank[lo] : 0u; skip; --skip) word &= word - 1u;
+            const uint32_t r = row0 + (uint32_t)(lo * 32 + (word ? __ffs((int)word) - 1 : 0));
+            const bool reach = in && r < n_idx;
+            const int32_t vid = s_arg.ivid[reach ? r : row0];   // unconditional loads (row0 < n_indexed: the sub-index exists)
+            const Row row = load_row(s_arg.irows + (reach ? r : row0));
+            const bool live = reach && vid >= 0 && vid != s_arg.excl;   // replaced since the build / the query's own video
+            uint32_t cnt, m1, m2, tk[kTop];
+            const int64_t *rk = s_arg.keys + row.off;        // (a live row's first key also serves the lanes past its end)
+            tol_row_scan<MODE>(rk, rk, live ? row.len : 0, s, pos, m, a_tol, gl, cnt, m1, m2, tk);
+            const bool hit = live && (int64_t)cnt >= (int64_t)min_match;
+            if (__ballot(hit) == 0ull) continue;
+            tol_row_reduce<MODE>(m1, m2, tk);
+            uint32_t kth;
+            if constexpr (MODE == kModeM2) kth = min_match == 1 ? m1 : m2;
+            else kth = tk[min_match - 1];
+            const bool lead = hit && gl == 0;
+            if constexpr (TOPK) {
+                const unsigned long long word64 = ix_tk_pack((int32_t)kth, vid, cnt);
+                n_hits += __popcll(__ballot(lead));
+                const bool cd = lead && word64 < thr;
+                const unsigned long long cb = __ballot(cd);
+                if (cb != 0ull) {
+                    const int before = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(cb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cb, 0u));
+                    if (cd) stage[n_stage + before] = word64;
+                    n_stage += __popcll(cb);
+                    if (n_stage > 64 - 64 / kGroup) {                // the next step may bring one per group
+                        __builtin_amdgcn_wave_barrier();
+                        thr = tol_topk_compact(kept, stage, n_stage, k, lane);
+                        n_stage = 0;
+                    }
+                }
+            } else if (lead) {
+                const int slot = atomicAdd(&s_nhits, 1);             // LDS
+                if (slot < kQ1Stage) {
+                    s_stage[slot * 3 + 0] = vid;
+                    s_stage[slot * 3 + 1] = (int32_t)cnt;
+                    s_stage[slot * 3 + 2] = (int32_t)kth;
+                } else {                                             // more than the stage holds: one by one
+                    const int gs = atomicAdd(&s_arg.hits_n[blockIdx.y], 1);
+                    if (gs < s_arg.cap) {
+                        int32_t *h = s_arg.hits + ((int64_t)blockIdx.y * s_arg.cap + gs) * 3;
+                        h[0] = vid;
+                        h[1] = (int32_t)cnt;
+                        h[2] = (int32_t)kth;
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        if (sub + 1 < sub_hi) {
+            for (int i = threadIdx.x; i < kTolIxWords; i += kTolBlock) { s_bm1[i] = 0; s_bm2[i] = 0; }
+            __syncthreads();
+        }
+    }
+    if constexpr (TOPK) {
+        tol_topk_flush(kept, stage, n_stage, thr, k, lane);
+        if (lane == 0 && n_hits) atomicAdd(&s_nhits, n_hits);            // LDS
+        __syncthreads();
+        if (wv == 0) {                                                   // wave 0 takes the other waves' lists into its own
+#pragma unroll 1
+            for (int j = 1; j < kTolTopkWaves; ++j) tol_topk_take(kept, stage, n_stage, s_kept[j * 64 + lane], thr, k, lane);
+            tol_topk_flush(kept, stage, n_stage, thr, k, lane);
+            if (lane < k) s_arg.part[((int64_t)q * s_arg.n_lists + bx) * k + lane] = kept[lane];
+        }
+        if (threadIdx.x == 0 && s_nhits) atomicAdd(&s_arg.hits_n[q], s_nhits);
+    } else {
+        const int staged = s_nhits < kQ1Stage ? s_nhits : kQ1Stage;
+        if (staged == 0) return;                                 // block-uniform
+        if (threadIdx.x == 0) s_stage_base = atomicAdd(&s_arg.hits_n[q], staged);
+        __syncthreads();
+        const int hb = s_stage_base, a_cap = s_arg.cap;
+        int32_t *dst = s_arg.hits + ((int64_t)q * a_cap + hb) * 3;
+        const int room = a_cap - hb < staged ? (a_cap - hb > 0 ? a_cap - hb : 0) : staged;
+        for (int i = threadIdx.x; i < room * 3; i += kTolBlock) dst[i] = s_stage[i];
+    }
+}
+
+}  // namespace

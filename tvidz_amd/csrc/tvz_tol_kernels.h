@@ -540,13 +540,15 @@ __device__ __forceinline__ void tol_topk_flush(unsigned long long *kept, unsigne
 }
 
 // grid = (row blocks, Q), the sorted query always in LDS (lds_keys >= every query's length, <= kTolTopkMaxLen).
-// part: uint64[Q][gridDim.x][k]; totals[q] (zeroed by ts_tol_sort_kernel) += the block's hits, one atomic.
+// part: uint64[Q][n_lists][k], block bx writes list list0 + bx (the sweep alone: n_lists = gridDim.x, list0 = 0; behind
+// the cell-posting lookup of tvz_tol_index_kernels.h: the lookup's lists come first); totals[q] (zeroed by
+// ts_tol_sort_kernel) += the block's hits, one atomic.
 template <int MODE>
 __global__ __launch_bounds__(kTolBlock) void ts_tol_topk_kernel(
     const Row *__restrict__ rows, int64_t n_rows, const int64_t *__restrict__ keys, const double *__restrict__ sv,
     const int32_t *__restrict__ sp, const int64_t *__restrict__ q_offsets, const int32_t *__restrict__ qm,
     int32_t lds_keys, double tol, int32_t min_match, const int32_t *__restrict__ exclude_ids, int32_t k,
-    unsigned long long *__restrict__ part, int32_t *__restrict__ totals) {
+    unsigned long long *__restrict__ part, int32_t n_lists, int32_t list0, int32_t *__restrict__ totals) {
     static_assert(MODE == kModeM2 || MODE == kModeTop5, "kth is known inside the sweep for min_match 1..5");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ unsigned long long s_kept[kTolTopkWaves * 64], s_stg[kTolTopkWaves * 64];
@@ -620,7 +622,7 @@ __global__ __launch_bounds__(kTolBlock) void ts_tol_topk_kernel(
 #pragma unroll 1
         for (int j = 1; j < kTolTopkWaves; ++j) tol_topk_take(kept, stage, n_stage, s_kept[j * 64 + lane], thr, k, lane);
         tol_topk_flush(kept, stage, n_stage, thr, k, lane);
-        if (lane < k) part[((int64_t)q * gridDim.x + bx) * k + lane] = kept[lane];
+        if (lane < k) part[((int64_t)q * n_lists + list0 + bx) * k + lane] = kept[lane];
     }
     if (threadIdx.x == 0 && s_nhits) atomicAdd(&totals[q], s_nhits);
 }

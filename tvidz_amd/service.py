@@ -158,11 +158,36 @@ class TickBatcher:
         self._thread.join(timeout=10)
 
 
+def check_tol_index(cell: float, match_tolerance: float = 0.0) -> float:
+    """`--match-tol-index CELL`: 0 (off) or a finite cell width in seconds that is not below the service's
+    tolerance - cell postings answer a tolerant ask only for tolerance <= cell, so narrower ones would be built at
+    every index rebuild and never used."""
+    cell = float(cell)
+    if not (0.0 <= cell <= sys.float_info.max):
+        raise ValueError(f"match_tol_index must be finite and >= 0, got {cell!r}")
+    if 0.0 < cell < float(match_tolerance):
+        raise ValueError(f"match_tol_index={cell!r} is below match_tolerance={float(match_tolerance)!r}: the cell "
+                         "postings would never be used (they serve tolerances up to the cell width)")
+    return cell
+
+
+def set_tol_index(shards, cell: float) -> None:
+    """Turn the cell postings on for every shard handle (DeviceCorpus.set_tol_index); nothing is called at 0, so a
+    service started without the flag never names them."""
+    if not cell:
+        return
+    for s in shards:
+        if not hasattr(s, "set_tol_index"):
+            raise RuntimeError(f"match_tol_index={cell!r}: {type(s).__name__} keeps no cell postings (set_tol_index)")
+        s.set_tol_index(cell)
+
+
 class ShardedCorpus:
     """DeviceCorpus's call shapes over R shard handles on one GPU.  db.Store(url, corpus=this) +
     inspector.Inspector(store) is the sharded service in one process."""
 
-    def __init__(self, device: int = 0, n_shards: int = 8, k: int = 64, cap: int = 4096, linger_s: float = 0.0):
+    def __init__(self, device: int = 0, n_shards: int = 8, k: int = 64, cap: int = 4096, linger_s: float = 0.0,
+                 tol_index_cell: float = 0.0):
         from . import corpus as tc
         self._tc = tc
         self.device = int(device)
@@ -170,6 +195,7 @@ class ShardedCorpus:
         self.R = int(n_shards)
         self.k, self.cap = int(k), max(int(cap), int(k))
         self.shards = [tc.DeviceCorpus(self.device) for _ in range(self.R)]
+        set_tol_index(self.shards, check_tol_index(tol_index_cell))
         # the tick thread's own stream, at high priority: a tick is a few tiny kernels and two tiny copies
         # that otherwise queue behind the upload workers' scene kernels
         self.stream = torch.cuda.Stream(self.dev, priority=-1)
@@ -324,8 +350,10 @@ class RankCorpus:
     e.g. bench.py's ranked e2e leg, must do the same)."""
 
     def __init__(self, shard, matcher, group=None, xdev="cpu", tick_s: float = 0.0005, max_batch: int = 1024,
-                 owner_fn: Optional[Callable[[int], int]] = None, idle_tick_s: float = 0.005, idle_after: int = 400):
+                 owner_fn: Optional[Callable[[int], int]] = None, idle_tick_s: float = 0.005, idle_after: int = 400,
+                 tol_index_cell: float = 0.0):
         self.shard, self.matcher, self.group = shard, matcher, group
+        set_tol_index([shard], check_tol_index(tol_index_cell))   # `--match-tol-index`: cell postings on this rank's handle
         self.xdev = torch.device(xdev)
         inited = dist.is_available() and dist.is_initialized()
         self.world = dist.get_world_size(group) if inited else 1
@@ -664,7 +692,7 @@ def _child_main(a) -> int:
     group = dist.new_group(backend=a.backend)                   # the tick thread's own (see RankCorpus)
     parts = (_load_hook(a.parts) if a.parts else _hip_parts)(a.rank, a.ranks, group, a)
     rc = RankCorpus(parts["shard"], parts["matcher"], group=group, xdev=parts["xdev"], tick_s=a.tick_s,
-                    owner_fn=FilenameOwner(a.db, a.ranks))
+                    owner_fn=FilenameOwner(a.db, a.ranks), tol_index_cell=a.match_tol_index)
     store = db.Store(a.db, corpus=rc, census=False)
     inspector = parts["inspector"](store)
     app = create_app(inspector)
@@ -783,7 +811,7 @@ class RankService:
     def __init__(self, ranks: int, db_url: str, base_port: int = 5000, backend: str = "gloo", parts: str = "",
                  devices: Optional[List[int]] = None, k: int = 64, cap: int = 4096, workers: int = 16,
                  tick_s: float = 0.0005, env: Optional[dict] = None, ready_timeout: float = 300.0,
-                 match_tolerance: float = 0.0):
+                 match_tolerance: float = 0.0, match_tol_index: float = 0.0):
         import socket
         import subprocess
         from . import db
@@ -791,6 +819,7 @@ class RankService:
         match_tolerance = float(match_tolerance)
         if not (0.0 <= match_tolerance <= sys.float_info.max):           # Inspector's rule, before any rank starts
             raise ValueError(f"match_tolerance must be finite and >= 0, got {match_tolerance!r}")
+        match_tol_index = check_tol_index(match_tol_index, match_tolerance)   # likewise before any rank starts
         db.create_schema(db_url)                                # once, before N processes open it side by side
         with socket.socket() as s:                              # a free rendezvous port
             s.bind(("127.0.0.1", 0))
@@ -804,7 +833,8 @@ class RankService:
                    "--backend", backend, "--device", str(devices[r]), "--k", str(k), "--cap", str(cap),
                    "--workers", str(workers), "--tick-s", str(tick_s), "--parent-pid", str(os.getpid())] + \
                   (["--parts", parts] if parts else []) + \
-                  (["--match-tolerance", repr(match_tolerance)] if match_tolerance else [])
+                  (["--match-tolerance", repr(match_tolerance)] if match_tolerance else []) + \
+                  (["--match-tol-index", repr(match_tol_index)] if match_tol_index else [])
             e = dict(os.environ)
             e.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")     # dmabuf IPC: RCCL between processes needs it here
             e.update(env or {})
@@ -864,6 +894,11 @@ def main(argv=None) -> int:  # pragma: no cover - exercised through subprocesses
     ap.add_argument("--match-tolerance", type=float, default=0.0,
                     help="seconds; > 0 turns on the opt-in tolerant duplicate match (Inspector(match_tolerance=...)): "
                          "~0.001 for remuxes, half a frame for frame-rate conversions; 0 = the exact verdict")
+    ap.add_argument("--match-tol-index", type=float, default=0.0, metavar="CELL",
+                    help="seconds; > 0 makes every rank's corpus handle keep cell postings of this width "
+                         "(tvz_corpus_tol_index): tolerant asks with tolerance <= CELL are then answered from the "
+                         "postings near their timestamps instead of a sweep of the shard.  Its own switch: it does not "
+                         "follow from --match-tolerance, and a CELL below it is refused.  0 = off")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--rank", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--master-port", type=int, default=29500, help=argparse.SUPPRESS)
@@ -874,7 +909,8 @@ def main(argv=None) -> int:  # pragma: no cover - exercised through subprocesses
     if a.child:
         return _child_main(a)
     svc = RankService(a.ranks, a.db, base_port=a.port, backend=a.backend, parts=a.parts, k=a.k, cap=a.cap,
-                      workers=a.workers, tick_s=a.tick_s, match_tolerance=a.match_tolerance)
+                      workers=a.workers, tick_s=a.tick_s, match_tolerance=a.match_tolerance,
+                      match_tol_index=a.match_tol_index)
 
     def monitor():
         while True:
