@@ -15,228 +15,20 @@
 // upsert path waits for the host or for matches in flight (only a compaction or a growth of the
 // arena beyond its reservation drains them).
 //
-// Kernels: tvz_match_kernels.h.  No process-global mutable state: the sweep algorithm is a
-// per-call argument and scratch is the caller's workspace.
-#include <algorithm>
+// Kernels: tvz_match_kernels.h; the handle: tvz_handle.h; its index build: tvz_index_build.h.  No process-global
+// mutable state: the sweep algorithm is a per-call argument and scratch is the caller's workspace.
 #include <cfloat>
-#include <cstdlib>
-#include <ctime>
-#include <atomic>
-#include <condition_variable>
-#include <mutex>
-#include <shared_mutex>
-#include <thread>
 #include <type_traits>
-#include <unordered_map>
-#include <vector>
 
 #include "tvz_match_kernels.h"
 #include "tvz_index_kernels.h"
 #include "tvz_index_wave_kernels.h"
 #include "tvz_tol_kernels.h"
 #include "tvz_tol_index_kernels.h"
+#include "tvz_handle.h"
+#include "tvz_index_build.h"
 
 namespace {
-
-// A device buffer of `cap` elements, grown by ensure(); it frees itself.
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    int64_t cap = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-};
-
-// A pinned host buffer (pinned_alloc); a MAPPED one is also addressable from the device at `d`, where the
-// single-query kernels write their hits.  It frees itself.
-template <typename T>
-struct Pinned {
-    T *h = nullptr;
-    T *d = nullptr;
-    Pinned() = default;
-    Pinned(const Pinned &) = delete;
-    Pinned &operator=(const Pinned &) = delete;
-    ~Pinned() { if (h) (void)hipHostFree(h); }
-};
-
-// Per-thread-of-control scratch of tvz_find_duplicates: its own stream, a pinned query buffer
-// and a pinned, device-mapped hit buffer the kernel writes into.  Sized at create / reserve /
-// upload for the reserved row count, so a query allocates nothing.
-struct Staging {
-    hipStream_t stream = nullptr;
-    Pinned<int64_t> query;           // {0, n} + canonical-order query keys (as double bits)
-    DevBuf<int64_t> d_query;         // device copy of the same
-    Pinned<int32_t> hits;            // mapped: [blocks][region][3]
-    Pinned<int32_t> counts;          // mapped: [kQ1MaxBlocks] per sweep block, then one per sub-index
-    int64_t hit_slots = 0;           // capacity of `hits` in hits
-    Pinned<int32_t> ix_hits;         // mapped: hits of the index lookup [ix_slots][3]
-    int64_t ix_slots = 0;
-    DevBuf<int32_t> d_hits;          // device hit list [3 per hit] for the paths that need a fix-up pass
-    DevBuf<int32_t> d_hits_n;
-    DevBuf<int64_t> d_sq;            // long queries: sorted distinct keys + multiplicities
-    DevBuf<int32_t> d_smult;
-    // tvz_find_duplicates_tol: the sorted query (values, then positions) of up to kMaxQueryLen timestamps,
-    // pinned + its device copy; longer queries use the growable d_tol_big
-    Pinned<unsigned char> tol;
-    DevBuf<unsigned char> d_tol;
-    DevBuf<unsigned char> d_tol_big;
-    std::vector<std::pair<double, int32_t>> tol_sort;   // host sort scratch (keeps its capacity)
-    std::atomic<int> busy{0};        // a sweep of this staging is in flight (drain() waits for it)
-    int gen = 0;                     // index generation that sweep reads
-    ~Staging() { if (stream) (void)hipStreamDestroy(stream); }
-};
-
-
-constexpr int kQ1MaxBlocks = 2048;
-constexpr int kStageGroups = kIxBlock / kGroup;   // row groups of the widest sweep block (the fused lookup's): every
-                                                  // block's hit region rounds up to whole row groups
-constexpr int64_t kQueryStageKeys = kMaxQueryLen + 1;
-// a query's sorted values + positions (12 B per timestamp), then for min_match > 5 the raw query (8 B per timestamp)
-constexpr size_t kTolStageBytes = (size_t)kQueryStageKeys * 20 + 64;
-constexpr int kRingSlots = 16;                    // pinned upsert payload ring
-constexpr int64_t kRingSlotKeys = 8192;           // 64 KiB each
-
-struct RingSlot {
-    int64_t *h = nullptr;
-    hipEvent_t ev = nullptr;
-    bool pending = false;
-};
-
-// Inverted index over rows [0, n_main) as they were when it was built (tvz_index_kernels.h) plus
-// the DELTA table: the current entry of every row that was added or replaced since.  A match with
-// the index = index lookup (rows that are unchanged since the build) + a sweep of the delta table.
-constexpr int kLdsPerWorkgroup = 160 * 1024;        // gfx950
-constexpr int kIxResidentBlocks = 256 * 4;          // lookup blocks (512 threads, <= 40 KiB of LDS) resident on an MI355X
-constexpr int kQ1StaticLds = kQ1Stage * 12 + 64;    // ts_match_q1_kernel: per-block hit staging + a few words (3,088 B in the code object)
-constexpr int kIxMaxLds = 159 * 1024;               // gfx950: 160 KiB of LDS per workgroup, less the static part
-constexpr int64_t kIxSliceBytes = 32 * 1024;        // a directory slice, built by one block in LDS
-constexpr int64_t kIxSliceBytesMax = 128 * 1024;
-constexpr int kIxSliceLdsFloor = 40 * 1024;         // LDS asked for per slice block: at most 3 per CU, 40 KB stay free
-// Directory load.  Every probe step of a lookup is a dependent random line fetch, and a wave waits for its
-// LONGEST chain - the 13 % of a shard batch's keys that are in no row of the shard walk to the next free slot.
-// Measured on rank 0's 1/8 shard of config 4 (Q = 4096, lookup kernel, rocprofv3): load <= 0.9 / 0.8: 86 us,
-// <= 0.5: 60.4, <= 0.25: 57.7, <= 0.12: 57.8 (full corpus 347 -> 341 us).  Memory is not the constraint
-// (64 MB of directory at config 4 on a 288 GB device).
-constexpr int kIxDirLoadPct = 25;
-#ifndef TVZ_BK_FILL_PCT
-#define TVZ_BK_FILL_PCT 35
-#endif
-constexpr int kBkFillPct = TVZ_BK_FILL_PCT;       // bucket directory (one-sub-index handles): payload bytes in use, target
-constexpr int64_t kIndexMinRows = 4096;           // a corpus grown by upserts gets its first index here
-constexpr int64_t kIndexMinDelta = 512;           // rebuilt when the delta exceeds max(this, n_main / 256)
-
-// One generation of the index's device image (tvz_index_kernels.h).  There are two: matches read
-// `cur`, a rebuild fills the other one (the SHADOW) while they keep running, and a swap under the
-// handle's lock makes it current - no reader ever waits for a rebuild.
-struct IndexBuf {
-    DevBuf<unsigned char> dir;        // 2^dir_log2 entries of 16 + 2 ks bytes
-    DevBuf<uint16_t> post;
-    DevBuf<int32_t> ivid;
-    DevBuf<Row> drows;                // the delta table that goes with this generation
-    int dir_log2 = 0;
-    int slice_log2 = 0;               // entries per directory slice (probing wraps inside a slice)
-    // A handle of ONE sub-index keeps the BUCKET directory of tvz_bucket_dir.h: nb buckets of 128 bytes - a key's
-    // entry and its postings in one line - + the external lists behind them, all in `dir`; `post` is unused.
-    uint32_t nb = 0;
-    int dir_bits() const { return nb ? -(int)nb : ix_dir_bits(dir_log2, slice_log2); }   // the kernels' argument
-    const uint16_t *post_ptr() const { return nb ? reinterpret_cast<const uint16_t *>(dir.p) : post.p; }
-    int n_sub = 0;                    // sub-indexes of kSubRows rows
-    int ks = 0;                       // uint16 counts per directory entry
-    int64_t n_main = 0;               // rows [0, n_main) are indexed
-    int64_t n_post = 0, n_distinct = 0;
-    int64_t n_spilled = 0, n_ext = 0, max_spill = 0, ext_used = 0;   // bucket directory: keys outside their home bucket / with external lists
-    // Cell postings of the tolerant lookup (tvz_tol_index_kernels.h), carried only while the handle asks for them
-    // (t_cell > 0: the cell width this generation was built with): a classic directory over the CELL ids of the same
-    // rows [0, n_main), built from the same snapshot, and the rows' 16-byte entries as they were at that snapshot.
-    DevBuf<unsigned char> tdir;
-    DevBuf<uint16_t> tpost;
-    DevBuf<Row> irows;
-    double t_cell = 0.0;
-    int t_dir_log2 = 0, t_slice_log2 = 0, t_ks = 0;
-    int64_t t_post = 0, t_cells = 0;
-    int t_dir_bits() const { return ix_dir_bits(t_dir_log2, t_slice_log2); }
-};
-
-struct Index {
-    IndexBuf buf[2];
-    int cur = 0;                      // the generation matches read (valid only if `valid`)
-    bool valid = false;
-    int64_t n_delta = 0;
-    int64_t builds = 0;
-    int64_t hint_post = 0, hint_distinct = 0;   // postings / distinct keys of the last build (sizes the next directory)
-    double tol_cell = 0.0;            // tvz_corpus_tol_index: > 0 = every build also makes cell postings of this width
-    int64_t tol_builds = 0;           // builds that carried them
-    int64_t thint_post = 0, thint_distinct = 0;   // the same hints for the cell directory
-    std::unordered_map<int64_t, int32_t> delta_slot;   // row index -> slot in buf[cur].drows
-    // build scratch (only the builder touches it)
-    IxBuildInfo *info = nullptr;      // device
-    DevBuf<uint32_t> fillc;           // per (entry, sub-index pair) fill cursors (unpartitioned build only)
-    DevBuf<int64_t> pkeys;            // partitioned build: the (key, row) pairs grouped by directory slice
-    DevBuf<uint32_t> prows;
-    DevBuf<uint32_t> pcnt;            // per slice: pair counts | first pair (+1 entry) | scatter cursors
-    DevBuf<Row> snap_rows;            // the row table as it was when a background build started
-    DevBuf<int32_t> dead_rows;        // rows upserted during that build (dead in the new generation)
-    hipStream_t bstream = nullptr;    // background builds run here, not on the mutation stream
-    hipEvent_t snap_ev = nullptr;
-    hipEvent_t build_ev = nullptr;    // polled by the builder (wait_stream_polling)
-    // a background build is running (its thread has released the handle's lock)
-    bool building = false;
-    std::vector<int64_t> since_snap;  // rows upserted since its snapshot
-    // PINNED host buffers: a copy to or from pageable memory makes the runtime wait for the stream
-    // while it holds internal locks - a lookup issued meanwhile waited for the whole count pass
-    IxBuildInfo *h_info = nullptr;    // read-back of `info`
-    Row *h_swap_rows = nullptr;       // sources of the swap's two small copies: they stay untouched until
-    int32_t *h_swap_dead = nullptr;   // the next swap, so the swap needs no synchronisation
-    int64_t h_swap_cap = 0;
-    std::condition_variable_any cv;   // signalled when it ends
-    IndexBuf &now() { return buf[cur]; }
-    const IndexBuf &now() const { return buf[cur]; }
-};
-
-}  // namespace
-
-struct tvz_corpus {
-    int device = 0;
-    std::shared_mutex mu;        // exclusive: host bookkeeping of a mutation; shared: enqueueing a match
-    std::mutex ev_mu;
-    std::mutex stage_mu;
-    DevBuf<int64_t> keys;
-    DevBuf<Row> rows;
-    std::vector<int64_t> h_keys;  // host mirror of the arena (for compaction)
-    std::vector<Row> h_rows;
-    std::unordered_map<int32_t, int64_t> first_row;  // video_id -> first row index
-    int64_t live_keys = 0;
-    // matches in flight (only compaction / reallocation / upload / destroy wait for them)
-    static constexpr int kEvents = 32;
-    hipEvent_t events[kEvents] = {};
-    bool ev_pending[kEvents] = {};
-    int ev_gen[kEvents] = {};    // index generation the match behind the event reads
-    int ev_next = 0;
-    // mutation stream: upsert payload copies + row swaps, in order
-    hipStream_t mstream = nullptr;
-    hipEvent_t mut_done = nullptr;   // re-recorded after every mutation; matches wait on it
-    bool mut_any = false;
-    RingSlot ring[kRingSlots];
-    int ring_next = 0;
-    std::vector<Staging *> free_staging;
-    std::vector<Staging *> all_staging;   // every staging ever made (checked out or free)
-    int64_t stage_rows = 0;          // rows the stagings are sized for
-    Index ix;
-    int64_t ix_next_try_rows = 0;    // a corpus without an index tries to build one from this size on
-};
-
-namespace {
-
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev); else prev = -1;
-    }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 
 // canonical, sorted, unique keys of one row appended to `out` (padded to an even count)
 int64_t canon_row(const double *src, int64_t n, std::vector<int64_t> &out) {
@@ -250,80 +42,6 @@ int64_t canon_row(const double *src, int64_t n, std::vector<int64_t> &out) {
     const int64_t len = (int64_t)(out.size() - start);
     if (out.size() & 1) out.push_back(kEmpty);  // keep every row 16-byte aligned
     return len;
-}
-
-// grow a device buffer (the caller has drained every reader); old contents [0, keep) survive
-template <typename T>
-int ensure(DevBuf<T> &b, int64_t need, int64_t keep) {
-    if (need <= b.cap) return TVZ_OK;
-    int64_t cap = std::max<int64_t>(need, b.cap * 2);
-    cap = std::max<int64_t>(cap, 1024);
-    T *np = nullptr;
-    if (hipMalloc(&np, (size_t)cap * sizeof(T)) != hipSuccess) {
-        (void)hipGetLastError();                  // not sticky: the next launch check must not report it
-        return tvz::fail(TVZ_ERR_NOMEM, "hipMalloc of %lld bytes failed",
-                         (long long)(cap * (int64_t)sizeof(T)));
-    }
-    if (b.p && keep > 0) {
-        const hipError_t e = hipMemcpy(np, b.p, (size_t)keep * sizeof(T), hipMemcpyDeviceToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(np);
-            return tvz::fail(TVZ_ERR_HIP, "device copy while growing a corpus buffer failed: %s",
-                             hipGetErrorString(e));
-        }
-    }
-    if (b.p) (void)hipFree(b.p);
-    b.p = np;
-    b.cap = cap;
-    return TVZ_OK;
-}
-
-// (re)allocate a pinned buffer of n elements, mapped into the device's address space if asked; old contents are lost
-template <typename T>
-int pinned_alloc(Pinned<T> &b, int64_t n, bool mapped) {
-    if (b.h) (void)hipHostFree(b.h);
-    b.h = b.d = nullptr;
-    TVZ_HIP(hipHostMalloc(&b.h, (size_t)n * sizeof(T), mapped ? hipHostMallocMapped : hipHostMallocDefault));
-    if (mapped) TVZ_HIP(hipHostGetDevicePointer(reinterpret_cast<void **>(&b.d), b.h, 0));
-    return TVZ_OK;
-}
-
-// wait for every match enqueued so far and for the mutation stream (caller holds mu exclusively)
-int drain(tvz_corpus *c) {
-    {
-        std::lock_guard<std::mutex> lk(c->ev_mu);
-        for (int i = 0; i < tvz_corpus::kEvents; ++i)
-            if (c->ev_pending[i]) {
-                TVZ_HIP(hipEventSynchronize(c->events[i]));
-                c->ev_pending[i] = false;
-            }
-    }
-    TVZ_HIP(hipStreamSynchronize(c->mstream));
-    for (RingSlot &s : c->ring) s.pending = false;
-    // single-query sweeps are not event-tracked (their caller waits for them itself): a few us each
-    {
-        std::lock_guard<std::mutex> lk(c->stage_mu);
-        for (Staging *s : c->all_staging)
-            while (s->busy.load(std::memory_order_acquire)) std::this_thread::yield();
-    }
-    return TVZ_OK;
-}
-
-int record(tvz_corpus *c, hipStream_t st) {
-    std::lock_guard<std::mutex> lk(c->ev_mu);
-    const int i = c->ev_next;
-    c->ev_next = (i + 1) % tvz_corpus::kEvents;
-    if (c->ev_pending[i]) TVZ_HIP(hipEventSynchronize(c->events[i]));
-    TVZ_HIP(hipEventRecord(c->events[i], st));
-    c->ev_pending[i] = true;
-    c->ev_gen[i] = c->ix.cur;
-    return TVZ_OK;
-}
-
-// every sweep enqueued from now on sees the mutations that have returned (caller holds mu shared)
-int wait_mutations(tvz_corpus *c, hipStream_t st) {
-    if (c->mut_any) TVZ_HIP(hipStreamWaitEvent(st, c->mut_done, 0));
-    return TVZ_OK;
 }
 
 // whole host mirror -> device (caller holds mu exclusively and has drained)
@@ -353,470 +71,6 @@ int compact(tvz_corpus *c) {
     return upload_all(c, 0, 0);
 }
 
-static bool tvz_debug() { static const bool on = getenv("TVZ_DEBUG") != nullptr; return on; }
-static double tvz_now_us() {
-    timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3;
-}
-
-// ---- inverted index: build ---------------------------------------------------------------------
-void index_drop(tvz_corpus *c) {
-    Index &ix = c->ix;
-    ix.valid = false;
-    ix.n_delta = 0;
-    ix.delta_slot.clear();
-}
-
-// The delta table holds delta_capacity() entries; a rebuild is started when it is HALF full, so
-// upserts keep landing in the old generation's table while the new one is being built.
-// A SMALL delta table: a build is ~1 ms per 20 M keys (9 ms for the unpartitioned build of a 1 M-row
-// corpus) and runs in the background - a few microseconds of GPU per upsert at this trigger - while
-// every batched match sweeps the whole delta table: 4096 queries against the 12,500 delta rows that
-// max(4096, n / 8) allowed at 100k rows cost more than their lookup in the index of 100,000
-// (profiles/r3_delta_probe.txt).
-int64_t delta_trigger(int64_t n_main) { return std::max<int64_t>(kIndexMinDelta, n_main / 256); }
-int64_t delta_capacity(int64_t n_main) { return 2 * delta_trigger(n_main) + 64; }
-
-// Order `st` behind every match that has been enqueued so far: the event-tracked batched calls by
-// a device-side wait (no host stall), the single-query sweeps in flight - not event-tracked, their
-// callers are blocked in a stream synchronisation, ~20 us each - by waiting for them here.  Caller
-// holds mu exclusively, so no new match can be enqueued meanwhile.
-int stream_wait_readers(tvz_corpus *c, hipStream_t st) {
-    {
-        std::lock_guard<std::mutex> lk(c->ev_mu);
-        for (int i = 0; i < tvz_corpus::kEvents; ++i)
-            if (c->ev_pending[i]) TVZ_HIP(hipStreamWaitEvent(st, c->events[i], 0));
-    }
-    std::lock_guard<std::mutex> lk(c->stage_mu);
-    for (Staging *s : c->all_staging)
-        while (s->busy.load(std::memory_order_acquire)) std::this_thread::yield();
-    return TVZ_OK;
-}
-
-// Host-side wait for the matches that still read index generation `gen` (the shadow about to be
-// rebuilt: they were enqueued before the previous swap, i.e. thousands of upserts ago - this
-// returns at once in practice).  Caller holds mu exclusively.
-int wait_generation_idle(tvz_corpus *c, int gen) {
-    {
-        std::lock_guard<std::mutex> lk(c->ev_mu);
-        for (int i = 0; i < tvz_corpus::kEvents; ++i)
-            if (c->ev_pending[i] && c->ev_gen[i] == gen) {
-                TVZ_HIP(hipEventSynchronize(c->events[i]));
-                c->ev_pending[i] = false;
-            }
-    }
-    std::lock_guard<std::mutex> lk(c->stage_mu);
-    for (Staging *s : c->all_staging)
-        while (s->gen == gen && s->busy.load(std::memory_order_acquire)) std::this_thread::yield();
-    return TVZ_OK;
-}
-
-// Wait for `st` without blocking inside the runtime: record an event and poll it.  A thread parked
-// in hipStreamSynchronize for the length of a count pass (~1 ms) held up a lookup that called
-// hipStreamSynchronize on ITS stream meanwhile (tests/rebuild_latency.c: one lookup per rebuild
-// returned right when the builder's wait ended); a query of an event takes no such turn.
-int wait_stream_polling(hipStream_t st, hipEvent_t ev) {
-    TVZ_HIP(hipEventRecord(ev, st));
-    while (true) {
-        const hipError_t e = hipEventQuery(ev);
-        if (e == hipSuccess) return TVZ_OK;
-        if (e != hipErrorNotReady) return tvz::fail(TVZ_ERR_HIP, "index build failed: %s", hipGetErrorString(e));
-        timespec nap = {0, 20 * 1000};
-        nanosleep(&nap, nullptr);
-    }
-}
-
-// The sizes of one generation's buffers and of the partitioned build's scratch, in elements, for a build of
-// `live_keys` keys into a corpus reservation of rows_cap rows / keys_cap keys.  The build ensures them; build_index
-// pre-sizes the shadow generation with them.
-struct GenSizes {
-    int64_t rows;     // ivid; the delta table holds delta_capacity(rows)
-    int64_t pairs;    // (key, row) pairs: ix.pkeys / ix.prows
-    // classic postings (+64: the lookup's last step reads up to 63 postings past the last list and discards them; x2 +
-    // a line per size class and slice: the partitioned build pads keys to line-friendly places)
-    int64_t post() const { return 2 * pairs + (int64_t)kIxMaxParts * kIxClasses * 64 + kIxPostPad; }
-    int64_t ext16() const { return 2 * pairs + 64 * 1024; }      // external lists: whole lines, lists of > 40 postings only
-    int64_t bucket_dir_bytes(uint32_t nb) const { return (int64_t)nb * kBkBytes + 2 * (ext16() + kIxPostPad); }
-};
-
-GenSizes gen_sizes(int64_t n_rows, int64_t live_keys, int64_t rows_cap, int64_t keys_cap) {
-    return {std::max<int64_t>(rows_cap, n_rows), std::max<int64_t>(keys_cap, live_keys)};
-}
-
-// the classic directory of 2^log2 entries of `es` bytes, and the unpartitioned build's fill cursors for it
-int64_t classic_dir_bytes(int log2, int es) { return ((int64_t)1 << log2) * es; }
-int64_t fillc_words(int log2, int ks) { return ((int64_t)1 << log2) * (ks ? ks / 2 : 1); }
-
-// The first half of the partitioned build, the same for both directory formats: every row's ivid entry, and the
-// (key, row) pairs of rows [0, n_rows) grouped by directory slice in ix.pkeys / ix.prows; ix.pcnt holds the per-slice
-// counts, then the slice starts (ix.pcnt.p + kIxMaxParts), then the scatter cursors.
-int build_partition(tvz_corpus *c, const Row *d_rows, int64_t n_rows, int64_t live_keys, int64_t pairs, int bits,
-                    int64_t n_parts, int32_t *ivid, hipStream_t st, double cellw = 0.0) {
-    Index &ix = c->ix;
-    if (int rc = ensure(ix.pkeys, pairs, 0)) return rc;
-    if (int rc = ensure(ix.prows, pairs, 0)) return rc;
-    if (int rc = ensure(ix.pcnt, 6 * (int64_t)kIxMaxParts + 8, 0)) return rc;
-    uint32_t *cnt = ix.pcnt.p, *start = cnt + kIxMaxParts, *cur = start + kIxMaxParts + 1;
-    // rows per block of the partition kernels: ~16 pairs per block and slice, so that a block's
-    // one reservation per slice is a small share of its work
-    const int64_t mean_len = std::max<int64_t>(1, live_keys / n_rows);
-    const int32_t rpb = (int32_t)std::min<int64_t>(4096, std::max<int64_t>(kBlock / 64 * 2, 16 * n_parts / mean_len));
-    hipLaunchKernelGGL(ix_part_clear_kernel, dim3(4), dim3(kBlock), 0, st, cnt, (int)n_parts, ix.info);
-    hipLaunchKernelGGL(ix_partition_kernel, dim3((unsigned)tvz::ceil_div(n_rows, rpb)), dim3(kBlock), (size_t)n_parts * 4, st,
-                       d_rows, n_rows, rpb, c->keys.p, bits, (int)n_parts, cnt, ivid, cellw);
-    hipLaunchKernelGGL(ix_part_scan_kernel, dim3(1), dim3(1024), 0, st, cnt, (int)n_parts, start, cur, ix.info);
-    // the scatter: rows worth about one staging area per block
-    const int32_t srpb = (int32_t)std::max<int64_t>(1, kIxStagePairs / mean_len);
-    const size_t sclds = (size_t)kIxStagePairs * 12 + ((size_t)3 * n_parts + 1) * 4;
-    hipLaunchKernelGGL(ix_scatter_kernel, dim3((unsigned)tvz::ceil_div(n_rows, srpb)), dim3(kIxScatterBlock), sclds,
-                       st, d_rows, n_rows, srpb, c->keys.p, bits, (int)n_parts, cur, ix.pkeys.p, ix.prows.p, cellw);
-    return TVZ_OK;
-}
-
-// the build's result, read back once its launches are done
-int read_build_info(Index &ix, hipStream_t st, IxBuildInfo &info) {
-    TVZ_HIP(hipGetLastError());
-    TVZ_HIP(hipMemcpyAsync(ix.h_info, ix.info, sizeof(info), hipMemcpyDeviceToHost, st));
-    if (int rc = wait_stream_polling(st, ix.build_ev)) return rc;
-    info = *ix.h_info;
-    return TVZ_OK;
-}
-
-// One sub-index: the bucket directory (tvz_bucket_dir.h).  Bytes the records need: 8 per distinct key + 2 per posting;
-// buckets for a fill of kBkFillPct % of their payload.  Fuller: more lists do not fit beside their bucket's other
-// records and move to the external area - a second line for every lookup that asks for them, and the long lists are
-// the ones asked for most; emptier: a larger table.  The distinct keys are known from the last build, else guessed and
-// the build repeated once at the size the count revealed.  Leaves b.nb = 0 when the keys do not fit (the classic
-// format then).
-int build_bucket_dir(tvz_corpus *c, IndexBuf &b, const Row *d_rows, int64_t n_rows, int64_t live_keys,
-                     const GenSizes &sz, hipStream_t st, IxBuildInfo &info) {
-    Index &ix = c->ix;
-    auto buckets_for = [&](double distinct) {
-        const double bytes = 8.0 * distinct + 2.0 * (double)live_keys;
-        const int64_t want = (int64_t)(bytes * 100.0 / ((double)kBkFillPct * kBkPayload)) + 1;
-        return (uint32_t)std::min<int64_t>(tvz::round_up(std::max<int64_t>(want, kBkSlice), kBkSlice), (int64_t)kIxMaxParts * kBkSlice);
-    };
-    double distinct = ix.hint_post > 0 ? (double)ix.hint_distinct * (double)live_keys / (double)ix.hint_post * 1.1
-                                       : (double)live_keys / 4.0;
-    uint32_t nb = buckets_for(distinct);
-    bool resized = false;
-    for (int attempt = 0; attempt < 8; ++attempt) {
-        const int64_t n_parts = nb / kBkSlice;
-        if (int rc = build_partition(c, d_rows, n_rows, live_keys, sz.pairs, -(int)nb, n_parts, b.ivid.p, st)) return rc;
-        if (int rc = ensure(b.dir, sz.bucket_dir_bytes(nb), 0)) return rc;
-        hipLaunchKernelGGL(bk_slice_build_kernel, dim3((unsigned)n_parts), dim3(kBkBuildBlock), kBkBuildLds, st,
-                           ix.pkeys.p, ix.prows.p, ix.pcnt.p + kIxMaxParts, b.dir.p, nb,
-                           (uint32_t)std::min<int64_t>(sz.ext16(), 0x7fffffffLL), ix.info);
-        if (int rc = read_build_info(ix, st, info)) return rc;
-        if (!info.failed) {
-            const uint32_t fit = buckets_for((double)info.n_distinct);
-            // (a first build that guessed the distinct keys: once more at the right size if it is off by a quarter)
-            if (!resized && (fit > nb + nb / 4 || fit + fit / 4 < nb)) { nb = fit; resized = true; continue; }
-            b.nb = nb;
-            b.ks = 0;
-            b.dir_log2 = 0;
-            b.slice_log2 = 0;
-            return TVZ_OK;
-        }
-        if (nb >= (uint32_t)kIxMaxParts * kBkSlice) break;            // too many keys for slices of 256 buckets: classic format
-        nb = (uint32_t)std::min<int64_t>(tvz::round_up((int64_t)nb + nb / 2, kBkSlice), (int64_t)kIxMaxParts * kBkSlice);
-    }
-    return TVZ_OK;
-}
-
-// The classic directory (tvz_index_kernels.h): ONE directory over the distinct keys of all rows, load <= 0.25
-// (kIxDirLoadPct).  Sized from a guess - a fingerprint corpus repeats its keys many times over (cuts sit on frame
-// grids) - and doubled while too crowded.
-// cellw > 0: the CELL directory of the tolerant lookup instead - the same build over cell ids (ix_build_key) into
-// b.tdir / b.tpost, sized from its own hints (the first time: from the key directory's distinct keys, an upper bound
-// on the distinct cells - every key has one cell).  Every (cell, row) pair is posted ONCE (ix_build_key drops a key
-// whose cell is its arena predecessor's): the uint16 counts per (cell, sub-index) rely on it.
-int build_classic(tvz_corpus *c, IndexBuf &b, const Row *d_rows, int64_t n_rows, int64_t live_keys,
-                  const GenSizes &sz, int n_sub, hipStream_t st, IxBuildInfo &info, double cellw = 0.0) {
-    Index &ix = c->ix;
-    const bool cells = cellw > 0.0;
-    DevBuf<unsigned char> &b_dir = cells ? b.tdir : b.dir;
-    DevBuf<uint16_t> &b_post = cells ? b.tpost : b.post;
-    const int64_t hint_post = cells ? ix.thint_post : ix.hint_post, hint_distinct = cells ? ix.thint_distinct : ix.hint_distinct;
-    const int ks = ix_ks(n_sub), es = ix_entry_bytes(ks);
-    const int64_t post_cap = sz.post();
-    // the size for `distinct` keys: load <= kIxDirLoadPct - unless that directory is too large for the
-    // partitioned build while one of half the size (load <= 0.5) is not (1 M rows x 62 sub-indexes: 144-byte
-    // entries, 4,096 slices of 128 KB at load 0.5)
-    auto partitionable = [&](int lg) {
-        int sl = 6;
-        while (((int64_t)2 << sl) * es <= kIxSliceBytes && sl < lg) ++sl;
-        while ((((int64_t)1 << lg) >> sl) > kIxMaxParts && ((int64_t)2 << sl) * es <= kIxSliceBytesMax) ++sl;
-        return (((int64_t)1 << lg) >> sl) <= kIxMaxParts && ((int64_t)es << sl) <= kIxSliceBytesMax;
-    };
-    auto size_for = [&](double distinct) {
-        int lg = 10;
-        while ((double)((int64_t)1 << lg) * kIxDirLoadPct < 100.0 * distinct && lg < 30) ++lg;
-        if (!partitionable(lg) && partitionable(lg - 1) && (double)((int64_t)1 << (lg - 1)) >= 2.0 * distinct) --lg;
-        return lg;
-    };
-    if (int rc = ensure(b_post, post_cap, 0)) return rc;
-    int log2 = 10;
-    if (hint_post > 0) {
-        // the last build knows how often this corpus repeats its keys: one pass, no retry
-        log2 = size_for((double)hint_distinct * (double)live_keys / (double)hint_post * 1.25);
-    } else if (cells && ix.hint_distinct > 0) {
-        log2 = size_for((double)ix.hint_distinct);     // (the key directory of this snapshot was built a moment ago)
-    } else {
-        while (((int64_t)1 << log2) < live_keys / 8) ++log2;
-    }
-    // one row per wave and SHORT-LIVED blocks (no grid-stride loop): a background build shares the GPU
-    // with lookups, whose few blocks get a CU as soon as any of these retires
-    const int64_t blocks = tvz::ceil_div(n_rows, kBlock / 64);
-    int slice_log2 = 0;
-    bool shrunk = false;
-    while (true) {
-        TVZ_REQUIRE(log2 <= 30, "index directory would exceed 2^30 entries");
-        const int64_t dn = (int64_t)1 << log2;
-        if (int rc = ensure(b_dir, classic_dir_bytes(log2, es), 0)) return rc;
-        // Directory slices of ~32 KB (one block builds a slice in LDS; three such blocks leave room on
-        // a CU for a lookup's block); larger ones if the slices would otherwise outnumber what the
-        // partition kernels keep in LDS.  A directory of more than kIxMaxParts slices of 128 KB takes
-        // the unpartitioned build (count + fill over the whole directory: one slice).
-        slice_log2 = 6;
-        while (((int64_t)2 << slice_log2) * es <= kIxSliceBytes && slice_log2 < log2) ++slice_log2;
-        while ((dn >> slice_log2) > kIxMaxParts && ((int64_t)2 << slice_log2) * es <= kIxSliceBytesMax) ++slice_log2;
-        const int64_t n_parts = dn >> slice_log2;
-        const bool partitioned = n_parts <= kIxMaxParts && post_cap < (int64_t)0xfffffff0LL &&   // (32-bit posting offsets)
-                                 ((int64_t)es << slice_log2) <= kIxSliceBytesMax;   // (entries of > 2 KB: > 16 M rows)
-        if (!partitioned) slice_log2 = log2;
-        const int bits = ix_dir_bits(log2, slice_log2);
-        if (partitioned) {
-            if (int rc = build_partition(c, d_rows, n_rows, live_keys, sz.pairs, bits, n_parts, b.ivid.p, st, cellw)) return rc;
-            uint32_t *start = ix.pcnt.p + kIxMaxParts, *ptot = start + 2 * kIxMaxParts + 1, *pstart = ptot + kIxMaxParts;
-            uint32_t *scratch = pstart + kIxMaxParts + 1;
-            const size_t slds = std::max<size_t>(((size_t)es << slice_log2), (size_t)kIxSliceLdsFloor);
-            hipLaunchKernelGGL(ix_slice_count_kernel, dim3((unsigned)n_parts), dim3(kIxSliceBlock), slds, st,
-                               ix.pkeys.p, ix.prows.p, start, b_dir.p, es, ks, bits, ptot, ix.info);
-            hipLaunchKernelGGL(ix_part_scan_kernel, dim3(1), dim3(1024), 0, st, ptot, (int)n_parts, pstart, scratch,
-                               static_cast<IxBuildInfo *>(nullptr));
-            hipLaunchKernelGGL(ix_slice_fill_kernel, dim3((unsigned)n_parts), dim3(kIxSliceBlock), slds, st,
-                               ix.pkeys.p, ix.prows.p, start, pstart, b_dir.p, es, ks, bits, b_post.p);
-        } else {
-            const int64_t fillc = tvz::round_up(fillc_words(log2, ks), 4);
-            if (int rc = ensure(ix.fillc, fillc, 0)) return rc;
-            hipLaunchKernelGGL(ix_clear_kernel, dim3(2048), dim3(kBlock), 0, st, reinterpret_cast<uint4 *>(b_dir.p),
-                               (size_t)(dn * es / 16), es / 16, reinterpret_cast<uint4 *>(ix.fillc.p),
-                               (size_t)(fillc / 4), ix.info);
-            hipLaunchKernelGGL(ix_count_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, d_rows, n_rows, c->keys.p,
-                               b_dir.p, es, ks, bits, b.ivid.p, ix.info, cellw);
-        }
-        if (int rc = read_build_info(ix, st, info)) return rc;
-        if (!info.failed && (int64_t)info.n_distinct * 2 <= dn) {            // accepted up to load 0.5; sized for kIxDirLoadPct
-            // A directory guessed from the key count of a corpus that repeats its keys (the first
-            // build of a handle) comes out many times too large - 4 M entries for 442 k distinct keys
-            // at 100k rows, 128 MB instead of 32 - and at 1 M rows too large for the partitioned
-            // build.  The count is cheap enough to run once more at the size it has just revealed
-            // (load <= kIxDirLoadPct), if that is at least four times smaller.
-            const int fit = size_for((double)info.n_distinct);
-            if (!shrunk && (fit + 1 < log2 || fit > log2)) { log2 = fit; shrunk = true; continue; }   // (or too small for the target load)
-            if (partitioned) break;
-            hipLaunchKernelGGL(ix_offsets_kernel, dim3((unsigned)tvz::ceil_div(dn, kBlock)), dim3(kBlock), 0, st, b_dir.p,
-                               (size_t)dn, es, ks, ix.info);
-            hipLaunchKernelGGL(ix_fill_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, d_rows, n_rows, c->keys.p,
-                               b_dir.p, es, ks, bits, ix.fillc.p, b_post.p, cellw);
-            if (int rc = read_build_info(ix, st, info)) return rc;
-            break;
-        }
-        ++log2;                                       // too crowded (or a slice overflowed): twice the directory
-    }
-    if (cells) {
-        b.t_ks = ks;
-        b.t_dir_log2 = log2;
-        b.t_slice_log2 = slice_log2;
-        return TVZ_OK;
-    }
-    b.ks = ks;
-    b.dir_log2 = log2;
-    b.slice_log2 = slice_log2;
-    return TVZ_OK;
-}
-
-// Build the index of rows [0, n_rows) of the row table image `d_rows` (keys in c->keys) into
-// generation `b` on stream `st`, and wait for it.  `b` must have no reader; nothing of the handle's
-// published state is touched.  rows_cap / keys_cap: the corpus RESERVATION the buffers are sized
-// with, so the rebuilds that upserts trigger allocate nothing until the corpus outgrows it.
-// cellw > 0 (the handle's tvz_corpus_tol_index width, read under its lock by the caller): the generation also gets the
-// cell postings and the rows' entries of this snapshot.
-int build_kernels(tvz_corpus *c, IndexBuf &b, const Row *d_rows, int64_t n_rows, int64_t live_keys,
-                  int64_t rows_cap, int64_t keys_cap, hipStream_t st, double cellw) {
-    Index &ix = c->ix;
-    // posting offsets and counts are 32-bit: a larger shard is swept (shard it over more GPUs)
-    if (n_rows == 0 || live_keys >= (int64_t)0xfffffff0LL)
-        return tvz::fail(TVZ_ERR_UNSUPPORTED, "corpus of %lld rows / %lld keys gets no index", (long long)n_rows,
-                         (long long)live_keys);
-    const int n_sub = (int)tvz::ceil_div(n_rows, kSubRows);
-    TVZ_REQUIRE(n_sub <= 4096, "too many rows for the index (%lld)", (long long)n_rows);
-    const GenSizes sz = gen_sizes(n_rows, live_keys, rows_cap, keys_cap);
-    if (int rc = ensure(b.ivid, sz.rows, 0)) return rc;
-    if (int rc = ensure(b.drows, delta_capacity(sz.rows), 0)) return rc;
-    IxBuildInfo info{};
-    b.nb = 0;
-    if (n_sub == 1)
-        if (int rc = build_bucket_dir(c, b, d_rows, n_rows, live_keys, sz, st, info)) return rc;
-    if (b.nb == 0)
-        if (int rc = build_classic(c, b, d_rows, n_rows, live_keys, sz, n_sub, st, info)) return rc;
-    if ((int64_t)info.cursor != live_keys)
-        return tvz::fail(TVZ_ERR_INVALID, "internal: index holds %u postings for %lld keys", info.cursor,
-                         (long long)live_keys);
-    b.n_sub = n_sub;
-    b.n_main = n_rows;
-    b.n_post = info.cursor;
-    b.n_distinct = info.n_distinct;
-    b.n_spilled = info.n_spilled;
-    b.n_ext = info.n_ext;
-    b.max_spill = info.max_spill;
-    b.ext_used = info.ext_cursor;
-    ix.hint_post = (int64_t)info.cursor;
-    ix.hint_distinct = (int64_t)info.n_distinct;
-    b.t_cell = 0.0;
-    b.t_post = b.t_cells = 0;
-    if (cellw > 0.0) {
-        IxBuildInfo tinfo{};
-        if (int rc = build_classic(c, b, d_rows, n_rows, live_keys, sz, n_sub, st, tinfo, cellw)) return rc;
-        if ((int64_t)tinfo.cursor > live_keys)         // (one posting per cell and row: at most one per key)
-            return tvz::fail(TVZ_ERR_INVALID, "internal: cell index holds %u postings for %lld keys", tinfo.cursor,
-                             (long long)live_keys);
-        if (int rc = ensure(b.irows, sz.rows, 0)) return rc;
-        TVZ_HIP(hipMemcpyAsync(b.irows.p, d_rows, (size_t)n_rows * sizeof(Row), hipMemcpyDeviceToDevice, st));
-        if (int rc = wait_stream_polling(st, ix.build_ev)) return rc;
-        b.t_cell = cellw;
-        b.t_post = (int64_t)tinfo.cursor;
-        b.t_cells = (int64_t)tinfo.n_distinct;
-        ix.thint_post = b.t_post;
-        ix.thint_distinct = b.t_cells;
-    }
-    if (b.nb && tvz_debug())
-        fprintf(stderr, "[tvz] bucket directory: %u buckets (%.1f MB) for %u keys / %u postings, fill %.2f, %u keys walked on "
-                "(max %u buckets), %u external lists (%.1f MB)\n", b.nb, b.nb * 128e-6, info.n_distinct, info.cursor,
-                (8.0 * info.n_distinct + 2.0 * info.cursor) / ((double)b.nb * kBkPayload), info.n_spilled, info.max_spill,
-                info.n_ext, info.ext_cursor * 2e-6);
-    return TVZ_OK;
-}
-
-// Synchronous build of the whole row table (upload, explicit rebuild, after a compaction).  Caller
-// holds mu exclusively, has drained every reader and no background build is running.
-int build_index(tvz_corpus *c) {
-    Index &ix = c->ix;
-    index_drop(c);
-    const int64_t n_rows = (int64_t)c->h_rows.size();
-    if (n_rows == 0 || c->live_keys >= (int64_t)0xfffffff0LL) return TVZ_OK;
-    IndexBuf &b = ix.buf[ix.cur ^ 1];
-    if (int rc = build_kernels(c, b, c->rows.p, n_rows, c->live_keys, c->rows.cap, c->keys.cap, c->mstream, ix.tol_cell))
-        return rc;
-    ix.cur ^= 1;
-    ix.valid = true;
-    ++ix.builds;
-    if (b.t_cell > 0.0) ++ix.tol_builds;
-    // size the OTHER generation and the snapshot buffer now, while nobody is waiting: a background
-    // rebuild then allocates nothing (hipMalloc / hipFree synchronise the whole device - a lookup in
-    // flight would wait for them).  `post` as large as the current generation's: nothing for a bucket directory,
-    // whose postings live in `dir`.
-    IndexBuf &o = ix.buf[ix.cur ^ 1];
-    const IndexBuf &n = ix.buf[ix.cur];
-    const GenSizes sz = gen_sizes(n_rows, c->live_keys, c->rows.cap, c->keys.cap);
-    const int64_t dir_bytes = n.nb ? n.dir.cap / 2 : classic_dir_bytes(n.dir_log2, ix_entry_bytes(n.ks));
-    (void)ensure(o.dir, 2 * dir_bytes, 0);         // room for the directory to double once
-    if (n.slice_log2 == n.dir_log2)                // the unpartitioned build's cursors
-        (void)ensure(ix.fillc, 2 * fillc_words(n.dir_log2, n.ks), 0);
-    (void)ensure(o.post, n.post.cap, 0);
-    (void)ensure(o.ivid, n.ivid.cap, 0);
-    (void)ensure(o.drows, n.drows.cap, 0);
-    if (n.t_cell > 0.0) {                          // the cell postings' buffers, the same way
-        (void)ensure(o.tdir, 2 * classic_dir_bytes(n.t_dir_log2, ix_entry_bytes(n.t_ks)), 0);
-        if (n.t_slice_log2 == n.t_dir_log2) (void)ensure(ix.fillc, 2 * fillc_words(n.t_dir_log2, n.t_ks), 0);
-        (void)ensure(o.tpost, n.tpost.cap, 0);
-        (void)ensure(o.irows, n.irows.cap, 0);
-    }
-    (void)ensure(ix.snap_rows, sz.rows, 0);
-    (void)ensure(ix.dead_rows, n.drows.cap, 0);
-    return TVZ_OK;
-}
-
-// No mutation that moves or frees the arena / row table / index buffers may run while a background
-// build reads them: wait for it (the lock is released while waiting).
-void wait_no_build(tvz_corpus *c, std::unique_lock<std::shared_mutex> &lk) {
-    while (c->ix.building) c->ix.cv.wait(lk);
-}
-
-// Background rebuild, run by the upserting thread that crossed the threshold.  The handle's lock is
-// RELEASED while the GPU builds: matches keep reading the current generation + its delta table,
-// upserts keep landing there (and are logged in since_snap).  The build reads a stream-ordered
-// snapshot of the row table and the append-only arena, fills the shadow generation on its own
-// stream, and the swap - a few host operations plus one small copy and one small kernel on the
-// mutation stream - publishes it.  Matches enqueued before the swap finish on the old generation,
-// whose buffers stay untouched until the NEXT rebuild (which first waits for them).
-int rebuild_in_background(tvz_corpus *c, std::unique_lock<std::shared_mutex> &lk) {
-    Index &ix = c->ix;
-    const double t_dbg0 = tvz_debug() ? tvz_now_us() : 0.0;
-    const int64_t n_snap = (int64_t)c->h_rows.size();
-    const int64_t live = c->live_keys, rows_cap = c->rows.cap, keys_cap = c->keys.cap;
-    const double cellw = ix.tol_cell;
-    const int shadow = ix.cur ^ 1;
-    if (int rc = wait_generation_idle(c, shadow)) return rc;
-    if (int rc = ensure(ix.snap_rows, std::max<int64_t>(rows_cap, n_snap), 0)) return rc;
-    // the snapshot is ordered on the mutation stream: behind every upsert that has returned, ahead
-    // of every later one
-    TVZ_HIP(hipMemcpyAsync(ix.snap_rows.p, c->rows.p, (size_t)n_snap * sizeof(Row), hipMemcpyDeviceToDevice,
-                           c->mstream));
-    TVZ_HIP(hipEventRecord(ix.snap_ev, c->mstream));
-    TVZ_HIP(hipStreamWaitEvent(ix.bstream, ix.snap_ev, 0));
-    ix.building = true;
-    ix.since_snap.clear();
-    lk.unlock();
-    const double t_dbg1 = tvz_debug() ? tvz_now_us() : 0.0;
-    int rc = build_kernels(c, ix.buf[shadow], ix.snap_rows.p, n_snap, live, rows_cap, keys_cap, ix.bstream, cellw);
-    char msg[512];
-    if (rc) snprintf(msg, sizeof msg, "%s", tvz::err_buf());
-    const double t_dbg2 = tvz_debug() ? tvz_now_us() : 0.0;
-    lk.lock();
-    if (tvz_debug())
-        fprintf(stderr, "[tvz] rebuild: %lld rows, %lld keys, rc %d: locked prologue %.0f us, build (unlocked) %.0f us, "
-                        "relock %.0f us, delta so far %lld\n", (long long)n_snap, (long long)live, rc, t_dbg1 - t_dbg0,
-                t_dbg2 - t_dbg1, tvz_now_us() - t_dbg2, (long long)ix.since_snap.size());
-    struct Done { Index &ix; ~Done() { ix.building = false; ix.since_snap.clear(); ix.cv.notify_all(); } } done{ix};
-    if (rc) { snprintf(tvz::err_buf(), 512, "%s", msg); return rc; }
-    IndexBuf &nb = ix.buf[shadow];
-    // the new delta table: every row upserted since the snapshot, once, with its CURRENT entry
-    std::vector<int64_t> &rs = ix.since_snap;
-    std::sort(rs.begin(), rs.end());
-    rs.erase(std::unique(rs.begin(), rs.end()), rs.end());
-    const int64_t d = (int64_t)rs.size();
-    if (d > std::min<int64_t>(std::min(nb.drows.cap, ix.h_swap_cap), delta_capacity(nb.n_main)))
-        return tvz::fail(TVZ_ERR_UNSUPPORTED, "%lld rows changed while the index was being rebuilt", (long long)d);
-    if (d) {
-        int64_t n_dead = 0;
-        for (int64_t i = 0; i < d; ++i) {
-            ix.h_swap_rows[i] = c->h_rows[(size_t)rs[(size_t)i]];
-            if (rs[(size_t)i] < nb.n_main) ix.h_swap_dead[n_dead++] = (int32_t)rs[(size_t)i];
-        }
-        TVZ_HIP(hipMemcpyAsync(nb.drows.p, ix.h_swap_rows, (size_t)d * sizeof(Row), hipMemcpyHostToDevice, c->mstream));
-        if (n_dead) {
-            if (int rc2 = ensure(ix.dead_rows, n_dead, 0)) return rc2;
-            TVZ_HIP(hipMemcpyAsync(ix.dead_rows.p, ix.h_swap_dead, (size_t)n_dead * 4, hipMemcpyHostToDevice, c->mstream));
-            hipLaunchKernelGGL(ix_mark_dead_kernel, dim3((unsigned)tvz::ceil_div(n_dead, kBlock)),
-                               dim3(kBlock), 0, c->mstream, nb.ivid.p, ix.dead_rows.p, (int32_t)n_dead);
-            TVZ_HIP(hipGetLastError());
-        }
-        TVZ_HIP(hipEventRecord(c->mut_done, c->mstream));
-        c->mut_any = true;
-    }
-    ix.delta_slot.clear();
-    for (int64_t i = 0; i < d; ++i) ix.delta_slot.emplace(rs[(size_t)i], (int32_t)i);
-    ix.n_delta = d;
-    ix.cur = shadow;
-    ix.valid = true;
-    ++ix.builds;
-    if (nb.t_cell > 0.0) ++ix.tol_builds;
-    return TVZ_OK;
-}
-
 // ---- single-query staging --------------------------------------------------------------------
 // room for the hits of `rows` corpus rows (every block's region rounds up to whole row groups)
 int staging_size(Staging *s, int64_t rows) {
@@ -840,7 +94,7 @@ int staging_new(tvz_corpus *c, Staging **out) {
     {                                    // single-query lookups: ahead of background index builds
         int least = 0, greatest = 0;
         TVZ_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        TVZ_HIP(hipStreamCreateWithPriority(&s->stream, hipStreamNonBlocking, greatest));
+        TVZ_HIP(hipStreamCreateWithPriority(&s->stream.s, hipStreamNonBlocking, greatest));
     }
     if (int rc = pinned_alloc(s->query, kQueryStageKeys + 2, false)) return rc;
     if (int rc = ensure(s->d_query, kQueryStageKeys + 2, 0)) return rc;
@@ -891,12 +145,10 @@ int reserve_locked(tvz_corpus *c, int64_t n_rows, int64_t n_keys) {
     c->ix.since_snap.reserve((size_t)delta_capacity(c->rows.cap));
     if (delta_capacity(c->rows.cap) > c->ix.h_swap_cap) {
         Index &ix = c->ix;
-        if (ix.h_swap_rows) (void)hipHostFree(ix.h_swap_rows);
-        if (ix.h_swap_dead) (void)hipHostFree(ix.h_swap_dead);
-        ix.h_swap_rows = nullptr; ix.h_swap_dead = nullptr; ix.h_swap_cap = 0;
         const int64_t cap = delta_capacity(c->rows.cap);
-        TVZ_HIP(hipHostMalloc(&ix.h_swap_rows, (size_t)cap * sizeof(Row), hipHostMallocDefault));
-        TVZ_HIP(hipHostMalloc(&ix.h_swap_dead, (size_t)cap * 4, hipHostMallocDefault));
+        ix.h_swap_cap = 0;
+        if (int rc = pinned_alloc(ix.h_swap_rows, cap, false)) return rc;
+        if (int rc = pinned_alloc(ix.h_swap_dead, cap, false)) return rc;
         ix.h_swap_cap = cap;
     }
     if (n_rows > c->stage_rows) {
@@ -1211,7 +463,7 @@ int launch_index(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offs
     const size_t lds = ix_lds_bytes(max_query_len, spb);
     if (int rc = by_mode<!HOSTOUT>(min_match, [&](auto mode) {
             hipLaunchKernelGGL((ts_match_index_kernel<HOSTOUT, mode.value>), dim3((unsigned)Q, (unsigned)groups),
-                               dim3(kIxBlock), lds, st, ix.dir.p, ix.dir_bits(), ix.ks, ix.post_ptr(), ix.ivid.p,
+                               dim3(kIxBlock), lds, st, ix.keys.dir.p, ix.keys.bits(), ix.keys.ks, ix.keys.post_ptr(), ix.ivid.p,
                                ix.n_main, ix.n_sub, spb, d_queries, d_q_offsets, max_query_len, min_match,
                                d_exclude_ids, exclude_one, cap, d_hits, d_hits_n, ns, byval ? *byval : kNoQuery);
             return launched();
@@ -1243,7 +495,7 @@ bool index_topk_usable(const tvz_corpus *c, int32_t Q, int32_t max_query_len, in
 bool wave_usable(const tvz_corpus *c, int32_t max_query_len, int32_t min_match, int32_t k, int32_t algo) {
     if (!kWqUsable || !c->ix.valid || (algo != TVZ_ALGO_AUTO && algo != TVZ_ALGO_INDEX)) return false;
     const IndexBuf &ix = c->ix.now();
-    return ix.n_sub == 1 && ix.nb > 0 && ix.n_main <= kWqRows && max_query_len <= kWqMaxLen && min_match >= 1 &&
+    return ix.n_sub == 1 && ix.keys.nb > 0 && ix.n_main <= kWqRows && max_query_len <= kWqMaxLen && min_match >= 1 &&
            min_match <= kTop && k <= kIxTkMaxK;
 }
 
@@ -1259,8 +511,8 @@ int launch_index_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q
     if (wave) {
         const size_t lds = wq_lds_bytes(max_query_len);
         return by_mode<false>(min_match, [&](auto mode) {
-            hipLaunchKernelGGL((ts_match_wq_topk_kernel<mode.value>), dim3((unsigned)Q), dim3(64), lds, st, ix.dir.p,
-                               ix.dir_bits(), ix.post_ptr(), ix.ivid.p, ix.n_main, d_queries, d_q_offsets, Q,
+            hipLaunchKernelGGL((ts_match_wq_topk_kernel<mode.value>), dim3((unsigned)Q), dim3(64), lds, st, ix.keys.dir.p,
+                               ix.keys.bits(), ix.keys.post_ptr(), ix.ivid.p, ix.n_main, d_queries, d_q_offsets, Q,
                                max_query_len, min_match, d_exclude_ids, cap, k, d_block);
             return launched();
         });
@@ -1275,14 +527,14 @@ int launch_index_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q
     // (On a handle of ONE sub-index pairs answered a stream of batches sooner - 42 against 46 us - and a lone batch
     // later - 66 against 62: streams of batches take the wave kernel there now, so the block kernel's default on such
     // a handle is the shape that answers a lone batch soonest.)
-    const bool pair = Q >= 2 && ((Q >= 2 * kIxResidentBlocks && ix.nb == 0) || force_pair) &&
+    const bool pair = Q >= 2 && ((Q >= 2 * kIxResidentBlocks && ix.keys.nb == 0) || force_pair) &&
                       lds2 + 256 <= (size_t)kLdsPerWorkgroup / 4 && !no_pair;   // (+ the body's static LDS)
     const size_t lds = pair ? lds2 : ix_lds_bytes(max_query_len, ix.n_sub, true);
     const unsigned grid = pair ? (unsigned)((Q + 1) / 2) : (unsigned)Q;
     return by_mode<false>(min_match, [&](auto mode) {
 #define TVZ_IXK(NQ)                                                                                            \
-    hipLaunchKernelGGL((ts_match_index_topk_kernel<mode.value, NQ>), dim3(grid), dim3(kIxBlock), lds, st, ix.dir.p, \
-                       ix.dir_bits(), ix.ks, ix.post_ptr(), ix.ivid.p, ix.n_main, ix.n_sub, d_queries, d_q_offsets, Q, \
+    hipLaunchKernelGGL((ts_match_index_topk_kernel<mode.value, NQ>), dim3(grid), dim3(kIxBlock), lds, st, ix.keys.dir.p, \
+                       ix.keys.bits(), ix.keys.ks, ix.keys.post_ptr(), ix.ivid.p, ix.n_main, ix.n_sub, d_queries, d_q_offsets, Q, \
                        max_query_len, min_match, d_exclude_ids, cap, k, d_block)
         if (pair) TVZ_IXK(2); else TVZ_IXK(1);
 #undef TVZ_IXK
@@ -1578,6 +830,13 @@ int32_t *tvz_ws_local_block(void *d_workspace, int32_t Q, int32_t max_query_len,
     return ws_layout(d_workspace, Q, max_query_len, cap, k, n_ranks).local;
 }
 
+// a kernel may ask for up to `bytes` of dynamic LDS
+template <typename K>
+int max_dynamic_lds(K *kernel, int bytes) {
+    TVZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    return TVZ_OK;
+}
+
 static int tvz_corpus_create_impl(tvz_corpus **out, int device) {
     TVZ_REQUIRE(out != nullptr, "out is NULL");
     int n = 0;
@@ -1587,67 +846,46 @@ static int tvz_corpus_create_impl(tvz_corpus **out, int device) {
     tvz_corpus *c = new tvz_corpus();
     c->device = device;
     struct Guard { tvz_corpus *c; ~Guard() { if (c) (void)tvz_corpus_destroy(c); } } g{c};
-    for (int i = 0; i < tvz_corpus::kEvents; ++i)
-        TVZ_HIP(hipEventCreateWithFlags(&c->events[i], hipEventDisableTiming));
-    TVZ_HIP(hipStreamCreateWithFlags(&c->mstream, hipStreamNonBlocking));
-    TVZ_HIP(hipEventCreateWithFlags(&c->mut_done, hipEventDisableTiming));
+    for (Event &ev : c->events) TVZ_HIP(hipEventCreateWithFlags(&ev.e, hipEventDisableTiming));
+    TVZ_HIP(hipStreamCreateWithFlags(&c->mstream.s, hipStreamNonBlocking));
+    TVZ_HIP(hipEventCreateWithFlags(&c->mut_done.e, hipEventDisableTiming));
     {   // background index builds: their own stream, lowest priority (lookups and upserts go first).
         // Created here, not at the first rebuild: creating a stream takes milliseconds and holds
         // runtime locks a lookup in flight would wait for
         int least = 0, greatest = 0;
         TVZ_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        TVZ_HIP(hipStreamCreateWithPriority(&c->ix.bstream, hipStreamNonBlocking, least));
-        TVZ_HIP(hipEventCreateWithFlags(&c->ix.snap_ev, hipEventDisableTiming));
-        TVZ_HIP(hipEventCreateWithFlags(&c->ix.build_ev, hipEventDisableTiming));
-        TVZ_HIP(hipMalloc(&c->ix.info, sizeof(IxBuildInfo)));
-        TVZ_HIP(hipHostMalloc(&c->ix.h_info, sizeof(IxBuildInfo), hipHostMallocDefault));
+        TVZ_HIP(hipStreamCreateWithPriority(&c->ix.bstream.s, hipStreamNonBlocking, least));
+        TVZ_HIP(hipEventCreateWithFlags(&c->ix.snap_ev.e, hipEventDisableTiming));
+        TVZ_HIP(hipEventCreateWithFlags(&c->ix.build_ev.e, hipEventDisableTiming));
+        if (int rc = dev_alloc(c->ix.info, 1)) return rc;
+        if (int rc = pinned_alloc(c->ix.h_info, 1, false)) return rc;
     }
     for (RingSlot &s : c->ring) {
-        TVZ_HIP(hipHostMalloc(&s.h, (size_t)kRingSlotKeys * 8, hipHostMallocDefault));
-        TVZ_HIP(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+        if (int rc = pinned_alloc(s.buf, kRingSlotKeys, false)) return rc;
+        TVZ_HIP(hipEventCreateWithFlags(&s.ev.e, hipEventDisableTiming));
     }
-    TVZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ts_match_tile_kernel<false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTileLds));
-    TVZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ts_match_tile_kernel<true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTileLds));
-    TVZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ts_match_join_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kJoinLds));
-#define TVZ_IX_ATTR(H, M)                                                                          \
-    TVZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ts_match_index_kernel<H, M>),           \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kIxMaxLds))
-    TVZ_IX_ATTR(false, kModeM2); TVZ_IX_ATTR(false, kModeTop5); TVZ_IX_ATTR(false, kModeCount);
-    TVZ_IX_ATTR(true, kModeM2); TVZ_IX_ATTR(true, kModeTop5);
-#undef TVZ_IX_ATTR
-#define TVZ_IXK_ATTR(M, NQ)                                                                       \
-    TVZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ts_match_index_topk_kernel<M, NQ>),    \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kIxMaxLds))
-    TVZ_IXK_ATTR(kModeM2, 1); TVZ_IXK_ATTR(kModeTop5, 1); TVZ_IXK_ATTR(kModeM2, 2); TVZ_IXK_ATTR(kModeTop5, 2);
-#undef TVZ_IXK_ATTR
-    TVZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ts_match_wq_topk_kernel<kModeM2>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)wq_lds_bytes(kWqMaxLen)));
-    TVZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ts_match_wq_topk_kernel<kModeTop5>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)wq_lds_bytes(kWqMaxLen)));
-    TVZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(bk_slice_build_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBkBuildLds));
-    TVZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ix_slice_count_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kIxSliceBytesMax));
-    TVZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ix_slice_fill_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kIxSliceBytesMax));
-    TVZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ix_scatter_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                kIxStagePairs * 12 + (3 * kIxMaxParts + 1) * 4));
-    TVZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ts_find_fused_kernel<false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kIxMaxLds));
-    TVZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ts_find_fused_kernel<true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kIxMaxLds));
-    const int q1max = (int)q1_lds_bytes(kQ1MaxLog2);
-#define TVZ_Q1_ATTR(M, H)                                                                     \
-    TVZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ts_match_q1_kernel<M, H>),       \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, q1max))
-    TVZ_Q1_ATTR(kModeM2, false); TVZ_Q1_ATTR(kModeM2, true);
-    TVZ_Q1_ATTR(kModeTop5, false); TVZ_Q1_ATTR(kModeTop5, true);
-    TVZ_Q1_ATTR(kModeCount, false); TVZ_Q1_ATTR(kModeCount, true);
-#undef TVZ_Q1_ATTR
+    if (int rc = max_dynamic_lds(ts_match_tile_kernel<false>, (int)kTileLds)) return rc;
+    if (int rc = max_dynamic_lds(ts_match_tile_kernel<true>, (int)kTileLds)) return rc;
+    if (int rc = max_dynamic_lds(ts_match_join_kernel, (int)kJoinLds)) return rc;
+    for (auto *k : {ts_match_index_kernel<false, kModeM2>, ts_match_index_kernel<false, kModeTop5>,
+                    ts_match_index_kernel<false, kModeCount>, ts_match_index_kernel<true, kModeM2>,
+                    ts_match_index_kernel<true, kModeTop5>})
+        if (int rc = max_dynamic_lds(k, kIxMaxLds)) return rc;
+    for (auto *k : {ts_match_index_topk_kernel<kModeM2, 1>, ts_match_index_topk_kernel<kModeTop5, 1>,
+                    ts_match_index_topk_kernel<kModeM2, 2>, ts_match_index_topk_kernel<kModeTop5, 2>})
+        if (int rc = max_dynamic_lds(k, kIxMaxLds)) return rc;
+    if (int rc = max_dynamic_lds(ts_match_wq_topk_kernel<kModeM2>, (int)wq_lds_bytes(kWqMaxLen))) return rc;
+    if (int rc = max_dynamic_lds(ts_match_wq_topk_kernel<kModeTop5>, (int)wq_lds_bytes(kWqMaxLen))) return rc;
+    if (int rc = max_dynamic_lds(bk_slice_build_kernel, (int)kBkBuildLds)) return rc;
+    if (int rc = max_dynamic_lds(ix_slice_count_kernel, (int)kIxSliceBytesMax)) return rc;
+    if (int rc = max_dynamic_lds(ix_slice_fill_kernel, (int)kIxSliceBytesMax)) return rc;
+    if (int rc = max_dynamic_lds(ix_scatter_kernel, kIxStagePairs * 12 + (3 * kIxMaxParts + 1) * 4)) return rc;
+    if (int rc = max_dynamic_lds(ts_find_fused_kernel<false>, kIxMaxLds)) return rc;
+    if (int rc = max_dynamic_lds(ts_find_fused_kernel<true>, kIxMaxLds)) return rc;
+    for (auto *k : {ts_match_q1_kernel<kModeM2, false>, ts_match_q1_kernel<kModeM2, true>,
+                    ts_match_q1_kernel<kModeTop5, false>, ts_match_q1_kernel<kModeTop5, true>,
+                    ts_match_q1_kernel<kModeCount, false>, ts_match_q1_kernel<kModeCount, true>})
+        if (int rc = max_dynamic_lds(k, (int)q1_lds_bytes(kQ1MaxLog2))) return rc;
     // default reservation: 64 Ki rows / 2 Mi keys (16 MiB) and two single-query stagings, so a
     // fresh service handles its first uploads without allocating on the hot calls
     c->stage_rows = 1 << 16;
@@ -1670,25 +908,8 @@ static int tvz_corpus_destroy_impl(tvz_corpus *c) {
     {
         std::unique_lock<std::shared_mutex> lk(c->mu);
         wait_no_build(c, lk);
-        if (c->mstream) (void)drain(c);
+        if (c->mstream.s) (void)drain(c);
         for (Staging *s : c->all_staging) delete s;
-        c->all_staging.clear();
-        c->free_staging.clear();
-        for (RingSlot &s : c->ring) {
-            if (s.h) (void)hipHostFree(s.h);
-            if (s.ev) (void)hipEventDestroy(s.ev);
-        }
-        if (c->ix.info) (void)hipFree(c->ix.info);
-        if (c->ix.h_info) (void)hipHostFree(c->ix.h_info);
-        if (c->ix.h_swap_rows) (void)hipHostFree(c->ix.h_swap_rows);
-        if (c->ix.h_swap_dead) (void)hipHostFree(c->ix.h_swap_dead);
-        if (c->ix.snap_ev) (void)hipEventDestroy(c->ix.snap_ev);
-        if (c->ix.build_ev) (void)hipEventDestroy(c->ix.build_ev);
-        if (c->ix.bstream) (void)hipStreamDestroy(c->ix.bstream);
-        for (int i = 0; i < tvz_corpus::kEvents; ++i)
-            if (c->events[i]) (void)hipEventDestroy(c->events[i]);
-        if (c->mut_done) (void)hipEventDestroy(c->mut_done);
-        if (c->mstream) (void)hipStreamDestroy(c->mstream);
     }
     delete c;
     return TVZ_OK;
@@ -1868,8 +1089,8 @@ static int tvz_corpus_upsert_impl(tvz_corpus *c, int32_t video_id, const double 
     if (added > kRingSlotKeys) {
         // a row too long for a ring slot (> 8192 cuts): copy straight from the mirror, synchronously
         hipError_t e = hipMemcpyAsync(c->keys.p + off, c->h_keys.data() + off, (size_t)added * 8,
-                                      hipMemcpyHostToDevice, c->mstream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->mstream);
+                                      hipMemcpyHostToDevice, c->mstream.s);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->mstream.s);
         if (e != hipSuccess) {
             rollback();
             return tvz::fail(TVZ_ERR_HIP, "upsert copy failed: %s", hipGetErrorString(e));
@@ -1878,12 +1099,12 @@ static int tvz_corpus_upsert_impl(tvz_corpus *c, int32_t video_id, const double 
         RingSlot &s = c->ring[c->ring_next];
         c->ring_next = (c->ring_next + 1) % kRingSlots;
         hipError_t e = hipSuccess;
-        if (s.pending) e = hipEventSynchronize(s.ev);      // 16 upserts ago: long done
+        if (s.pending) e = hipEventSynchronize(s.ev.e);      // 16 upserts ago: long done
         if (e == hipSuccess) {
-            memcpy(s.h, tmp.data(), (size_t)added * 8);
-            e = hipMemcpyAsync(c->keys.p + off, s.h, (size_t)added * 8, hipMemcpyHostToDevice, c->mstream);
+            memcpy(s.buf.h, tmp.data(), (size_t)added * 8);
+            e = hipMemcpyAsync(c->keys.p + off, s.buf.h, (size_t)added * 8, hipMemcpyHostToDevice, c->mstream.s);
         }
-        if (e == hipSuccess) e = hipEventRecord(s.ev, c->mstream);
+        if (e == hipSuccess) e = hipEventRecord(s.ev.e, c->mstream.s);
         if (e != hipSuccess) {
             rollback();
             return tvz::fail(TVZ_ERR_HIP, "upsert copy failed: %s", hipGetErrorString(e));
@@ -1898,15 +1119,15 @@ static int tvz_corpus_upsert_impl(tvz_corpus *c, int32_t video_id, const double 
         // them dead therefore waits - on the device - for every match enqueued so far; those matches
         // see the old row, every later one the new row, none neither (db.py:83 under Postgres MVCC
         // cannot lose a row either).
-        if (kills_postings && stream_wait_readers(c, c->mstream) != TVZ_OK) e = hipErrorUnknown;
+        if (kills_postings && stream_wait_readers(c, c->mstream.s) != TVZ_OK) e = hipErrorUnknown;
         if (e == hipSuccess)
-            hipLaunchKernelGGL(ts_row_write3_kernel, dim3(1), dim3(1), 0, c->mstream, c->rows.p + r,
+            hipLaunchKernelGGL(ts_row_write3_kernel, dim3(1), dim3(1), 0, c->mstream.s, c->rows.p + r,
                                ix.now().drows.p + slot, kills_postings ? ix.now().ivid.p + r : nullptr, new_row);
     } else {
-        hipLaunchKernelGGL(ts_row_write_kernel, dim3(1), dim3(1), 0, c->mstream, c->rows.p + r, new_row);
+        hipLaunchKernelGGL(ts_row_write_kernel, dim3(1), dim3(1), 0, c->mstream.s, c->rows.p + r, new_row);
     }
     if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = hipEventRecord(c->mut_done, c->mstream);
+    if (e == hipSuccess) e = hipEventRecord(c->mut_done.e, c->mstream.s);
     if (e != hipSuccess) {
         rollback();
         return tvz::fail(TVZ_ERR_HIP, "upsert row swap failed: %s", hipGetErrorString(e));
@@ -1933,7 +1154,7 @@ static int tvz_corpus_clear_impl(tvz_corpus *c) {
     // it stays UNCHANGED - the arena is reused from offset 0 by the next upsert, whose copy runs on
     // the mutation stream, so that stream is made to wait (on the device) for every match enqueued
     // so far.  No host stall.
-    if (int rc = stream_wait_readers(c, c->mstream)) return rc;
+    if (int rc = stream_wait_readers(c, c->mstream.s)) return rc;
     c->h_keys.clear();
     c->h_rows.clear();
     c->first_row.clear();
@@ -1970,8 +1191,8 @@ static int tvz_corpus_index_stats_impl(tvz_corpus *c, int64_t *n_indexed, int64_
     const Index &ix = c->ix;
     if (n_indexed) *n_indexed = ix.valid ? ix.now().n_main : 0;
     if (n_delta) *n_delta = ix.valid ? ix.n_delta : 0;
-    if (n_post) *n_post = ix.valid ? ix.now().n_post : 0;
-    if (n_distinct) *n_distinct = ix.valid ? ix.now().n_distinct : 0;
+    if (n_post) *n_post = ix.valid ? ix.now().keys.n_post : 0;
+    if (n_distinct) *n_distinct = ix.valid ? ix.now().keys.n_distinct : 0;
     if (n_builds) *n_builds = ix.builds;
     return TVZ_OK;
 }
@@ -2005,8 +1226,8 @@ static int tvz_corpus_tol_index_stats_impl(tvz_corpus *c, double *cell, int64_t 
     const bool on = ix.valid && ix.now().t_cell > 0.0;
     if (cell) *cell = on ? ix.now().t_cell : 0.0;
     if (out) {
-        out[0] = on ? ix.now().t_cells : 0;
-        out[1] = on ? ix.now().t_post : 0;
+        out[0] = on ? ix.now().cells.n_distinct : 0;
+        out[1] = on ? ix.now().cells.n_post : 0;
         out[2] = ix.tol_builds;
         out[3] = on ? ix.n_delta : 0;
     }
@@ -2129,14 +1350,14 @@ int pinned_sweep(tvz_corpus *c, Staging *s, const char *what, Launch &&launch, i
                     // the corpus outgrew its reservation (see tvz_corpus_reserve): grow this staging
                     if (int rc = staging_size(s, std::max<int64_t>(2 * n_rows, c->stage_rows))) return rc;
                 }
-                if (int rc = wait_mutations(c, s->stream)) return rc;
+                if (int rc = wait_mutations(c, s->stream.s)) return rc;
                 s->busy.store(1, std::memory_order_release);
                 if (int rc = launch(n_rows, blocks, region)) return rc;
             }
         }
         // (polling the per-block counts from the host instead was tried: it needs a system-scope
         // release per block, which saved 1.5 us at 5k rows and cost 60 us at 100k)
-        const hipError_t e = hipStreamSynchronize(s->stream);
+        const hipError_t e = hipStreamSynchronize(s->stream.s);
         if (e != hipSuccess) return tvz::fail(TVZ_ERR_HIP, "%ssingle-query match failed: %s", what, hipGetErrorString(e));
     }
     // compact the per-block regions in place (block order; sorted by the caller anyway)
@@ -2169,7 +1390,7 @@ int find_pinned(tvz_corpus *c, Staging *s, const double *h_query, int64_t n, int
         s->query.h[0] = 0;
         s->query.h[1] = n;
         memcpy(s->query.h + 2, h_query, (size_t)n * 8);
-        TVZ_HIP(hipMemcpyAsync(s->d_query.p, s->query.h, (size_t)(n + 2) * 8, hipMemcpyHostToDevice, s->stream));
+        TVZ_HIP(hipMemcpyAsync(s->d_query.p, s->query.h, (size_t)(n + 2) * 8, hipMemcpyHostToDevice, s->stream.s));
     }
     const double *dq = by_value ? nullptr : reinterpret_cast<const double *>(s->d_query.p + 2);
     const int64_t *dqo = by_value ? nullptr : s->d_query.p;
@@ -2197,7 +1418,7 @@ int find_pinned(tvz_corpus *c, Staging *s, const double *h_query, int64_t n, int
                     static const QByVal kNoQuery = {};
                     return by_mode<false>(min_match, [&](auto mode) -> int {
                         hipLaunchKernelGGL((ts_find_fused_kernel<mode.value == kModeTop5>), dim3((unsigned)(n_sub + blocks)),
-                                           dim3(kIxBlock), lds, s->stream, ib.dir.p, ib.dir_bits(), ib.ks, ib.post_ptr(),
+                                           dim3(kIxBlock), lds, s->stream.s, ib.keys.dir.p, ib.keys.bits(), ib.keys.ks, ib.keys.post_ptr(),
                                            ib.ivid.p, ib.n_main, ib.n_sub, 1, n_sub, dq, dqo, (int32_t)n, min_match, excl,
                                            s->ix_hits.d, s->counts.d + kQ1MaxBlocks, span.p, span.n, c->keys.p, s_log2,
                                            ho, by_value ? qv : kNoQuery);
@@ -2206,7 +1427,7 @@ int find_pinned(tvz_corpus *c, Staging *s, const double *h_query, int64_t n, int
                     });
                 }
                 if (int rc = launch_index<true>(c, dq, dqo, 1, (int32_t)n, min_match, nullptr, excl, 0, s->ix_hits.d,
-                                                s->counts.d + kQ1MaxBlocks, 1, s->stream, by_value ? &qv : nullptr))
+                                                s->counts.d + kQ1MaxBlocks, 1, s->stream.s, by_value ? &qv : nullptr))
                     return rc;
             }
             if (!span.n) return TVZ_OK;
@@ -2214,7 +1435,7 @@ int find_pinned(tvz_corpus *c, Staging *s, const double *h_query, int64_t n, int
             region = (int)(tvz::ceil_div(span.n, (int64_t)blocks * kQ1Groups) * kQ1Groups);
             const HostOut ho{s->hits.d, s->counts.d, region};
             return launch_q1<true>(c, span, dq, dqo, 1, (int32_t)n, min_match, nullptr, excl, 0, nullptr, nullptr, 1,
-                                   blocks, ho, s->stream, by_value ? &qv : nullptr);
+                                   blocks, ho, s->stream.s, by_value ? &qv : nullptr);
         };
         if (int rc = pinned_sweep(c, s, "", launch, n_hits)) return rc;
         bool refused = false;
@@ -2252,32 +1473,32 @@ int find_device(tvz_corpus *c, Staging *s, const double *h_query, int64_t n, int
         if (int rc = ensure(s->d_smult, m + 1, 0)) return rc;
         d_q = s->d_sq.p + m;                                 // {0, n} + raw query
         const int64_t qoff[2] = {0, n};
-        TVZ_HIP(hipMemcpyAsync(d_q, qoff, 16, hipMemcpyHostToDevice, s->stream));
-        TVZ_HIP(hipMemcpyAsync(d_q + 2, h_query, (size_t)n * 8, hipMemcpyHostToDevice, s->stream));
+        TVZ_HIP(hipMemcpyAsync(d_q, qoff, 16, hipMemcpyHostToDevice, s->stream.s));
+        TVZ_HIP(hipMemcpyAsync(d_q + 2, h_query, (size_t)n * 8, hipMemcpyHostToDevice, s->stream.s));
         if (m) {
-            TVZ_HIP(hipMemcpyAsync(s->d_sq.p, uq.data(), (size_t)m * 8, hipMemcpyHostToDevice, s->stream));
-            TVZ_HIP(hipMemcpyAsync(s->d_smult.p, mult.data(), (size_t)m * 4, hipMemcpyHostToDevice, s->stream));
+            TVZ_HIP(hipMemcpyAsync(s->d_sq.p, uq.data(), (size_t)m * 8, hipMemcpyHostToDevice, s->stream.s));
+            TVZ_HIP(hipMemcpyAsync(s->d_smult.p, mult.data(), (size_t)m * 4, hipMemcpyHostToDevice, s->stream.s));
         }
     } else {
         s->query.h[0] = 0;
         s->query.h[1] = n;
         if (n) memcpy(s->query.h + 2, h_query, (size_t)n * 8);
-        TVZ_HIP(hipMemcpyAsync(s->d_query.p, s->query.h, (size_t)(n + 2) * 8, hipMemcpyHostToDevice, s->stream));
+        TVZ_HIP(hipMemcpyAsync(s->d_query.p, s->query.h, (size_t)(n + 2) * 8, hipMemcpyHostToDevice, s->stream.s));
     }
     {
         std::shared_lock<std::shared_mutex> lk(c->mu);
         const int64_t n_rows = (int64_t)c->h_rows.size();
-        if (int rc = wait_mutations(c, s->stream)) return rc;
-        if (int rc = launch_prep(s->d_hits_n.p, 1, 1, nullptr, 0, nullptr, 0, s->stream)) return rc;
+        if (int rc = wait_mutations(c, s->stream.s)) return rc;
+        if (int rc = launch_prep(s->d_hits_n.p, 1, 1, nullptr, 0, nullptr, 0, s->stream.s)) return rc;
         if (n_rows) {
             if (longq) {
                 hipLaunchKernelGGL(ts_match_longq_kernel, dim3((unsigned)tvz::ceil_div(n_rows, kGroupsPerBlock)),
-                                   dim3(kBlock), 0, s->stream, c->rows.p, n_rows, c->keys.p, s->d_sq.p,
+                                   dim3(kBlock), 0, s->stream.s, c->rows.p, n_rows, c->keys.p, s->d_sq.p,
                                    s->d_smult.p, (int32_t)uq.size(), min_match, -1, (int32_t)want, s->d_hits.p,
                                    s->d_hits_n.p, static_cast<const int32_t *>(nullptr), static_cast<const int32_t *>(nullptr));
                 TVZ_HIP(hipGetLastError());
                 if (min_match > 0) {
-                    hipLaunchKernelGGL(ts_kth_fixup_kernel, dim3(1), dim3(kBlock), 0, s->stream, c->rows.p,
+                    hipLaunchKernelGGL(ts_kth_fixup_kernel, dim3(1), dim3(kBlock), 0, s->stream.s, c->rows.p,
                                        c->keys.p, reinterpret_cast<const double *>(d_q + 2), d_q, min_match,
                                        (int32_t)want, s->d_hits.p, s->d_hits_n.p, 1);
                     TVZ_HIP(hipGetLastError());
@@ -2288,20 +1509,20 @@ int find_device(tvz_corpus *c, Staging *s, const double *h_query, int64_t n, int
                 // sweep; the fix-ups are part of those paths
                 if (int rc = launch_match_short(c, reinterpret_cast<const double *>(d_q + 2), d_q, 1, (int32_t)n, min_match,
                                                 nullptr, (int32_t)want, s->d_hits.p, s->d_hits_n.p, 1, nullptr, 0,
-                                                TVZ_ALGO_AUTO, s->stream))
+                                                TVZ_ALGO_AUTO, s->stream.s))
                     return rc;
             }
         }
-        if (int rc = record(c, s->stream)) return rc;
+        if (int rc = record(c, s->stream.s)) return rc;
     }
     int32_t h_n = 0;
-    TVZ_HIP(hipMemcpyAsync(&h_n, s->d_hits_n.p, 4, hipMemcpyDeviceToHost, s->stream));
-    TVZ_HIP(hipStreamSynchronize(s->stream));   // also: uq / mult / h_query were read by now
+    TVZ_HIP(hipMemcpyAsync(&h_n, s->d_hits_n.p, 4, hipMemcpyDeviceToHost, s->stream.s));
+    TVZ_HIP(hipStreamSynchronize(s->stream.s));   // also: uq / mult / h_query were read by now
     *n_found = h_n;
     hits.resize((size_t)std::min<int64_t>(h_n, want));
     if (!hits.empty()) {
-        TVZ_HIP(hipMemcpyAsync(hits.data(), s->d_hits.p, hits.size() * 12, hipMemcpyDeviceToHost, s->stream));
-        TVZ_HIP(hipStreamSynchronize(s->stream));
+        TVZ_HIP(hipMemcpyAsync(hits.data(), s->d_hits.p, hits.size() * 12, hipMemcpyDeviceToHost, s->stream.s));
+        TVZ_HIP(hipStreamSynchronize(s->stream.s));
     }
     if (excl >= 0) {
         const size_t before = hits.size();
@@ -2511,7 +1732,7 @@ int launch_tol_index(tvz_corpus *c, const TolIxShape &sh, const double *sv, cons
     return by_mode<false>(min_match, [&](auto mode) {
         hipLaunchKernelGGL((ts_tol_index_kernel<mode.value, TOPK>), grid, dim3(kTolBlock),
                            tol_index_lds_bytes(lds_keys, keep_slots), st,
-                           b.tdir.p, b.t_dir_bits(), b.t_ks, b.tpost.p, b.ivid.p, b.irows.p, b.n_main, b.n_sub, sh.spb,
+                           b.cells.dir.p, b.cells.bits(), b.cells.ks, b.cells.post.p, b.ivid.p, b.irows.p, b.n_main, b.n_sub, sh.spb,
                            sh.split, b.t_cell, c->keys.p, sv, sp, q_offsets, qm, lds_keys, tol, min_match, d_exclude_ids,
                            cap, d_hits, d_hits_n, k, part, n_lists, keep_slots ? 1 : 0);
         return launched();
@@ -2558,7 +1779,7 @@ static int tvz_find_duplicates_tol_impl(tvz_corpus *c, const double *h_query, in
         hp[t] = srt[t].second;
     }
     if (fixup && n) memcpy(h + raw_at, h_query, (size_t)n * 8);
-    if (bytes) TVZ_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s->stream));
+    if (bytes) TVZ_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s->stream.s));
     const double *dv = reinterpret_cast<const double *>(d);
     const int32_t *dp = reinterpret_cast<const int32_t *>(d + (size_t)m_even * 8);
     auto launch = [&](int64_t n_rows, int &blocks, int &region) -> int {
@@ -2567,10 +1788,10 @@ static int tvz_find_duplicates_tol_impl(tvz_corpus *c, const double *h_query, in
         const HostOut ho{s->hits.d, s->counts.d, region};
         const int32_t lds_keys = m <= kTolLdsKeys ? (int32_t)std::max<int64_t>(m, 1) : 0;
         if (int rc = launch_tol<true>(c, c->rows.p, n_rows, dv, dp, nullptr, nullptr, (int32_t)m, lds_keys, 1, tol, min_match,
-                                      nullptr, excl, 0, nullptr, nullptr, blocks, ho, s->stream))
+                                      nullptr, excl, 0, nullptr, nullptr, blocks, ho, s->stream.s))
             return rc;
         if (!fixup) return TVZ_OK;
-        hipLaunchKernelGGL(ts_tol_kth_fixup_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, s->stream, c->rows.p,
+        hipLaunchKernelGGL(ts_tol_kth_fixup_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, s->stream.s, c->rows.p,
                            c->keys.p, reinterpret_cast<const double *>(d + raw_at), static_cast<const int64_t *>(nullptr),
                            (int32_t)n, tol, min_match, s->hits.d, s->counts.d, region);
         return launched();
@@ -2805,11 +2026,11 @@ static int tvz_corpus_bucket_stats_impl(tvz_corpus *c, int64_t *out) {
     for (int i = 0; i < 6; ++i) out[i] = 0;
     if (!ix.valid) return TVZ_OK;
     const IndexBuf &b = ix.now();
-    out[0] = b.nb;
-    out[1] = b.nb ? b.n_spilled : 0;
-    out[2] = b.nb ? b.max_spill : 0;
-    out[3] = b.nb ? b.n_ext : 0;
-    out[4] = b.nb ? b.ext_used : 0;
+    out[0] = b.keys.nb;
+    out[1] = b.keys.nb ? b.n_spilled : 0;
+    out[2] = b.keys.nb ? b.max_spill : 0;
+    out[3] = b.keys.nb ? b.n_ext : 0;
+    out[4] = b.keys.nb ? b.ext_used : 0;
     out[5] = b.n_sub;
     return TVZ_OK;
 }
