@@ -293,6 +293,60 @@ def test_hit_list_overflow_reports_true_count(dc):
     assert (hits[0, :, 0] >= 1).all()
 
 
+def past_the_stage_case():
+    """70,000 rows that are ALL hits of 8 queries: row i (video id i) holds six shared timestamps and one of its own;
+    query j is the shared six, rotated by j, with two values that match nothing put in at places that depend on j.  A sweep gives a query
+    256 blocks of 16 row groups, 274 rows each here, and a block stages 256 hits in LDS: every block goes past its stage.
+    -> (ids, offsets, keys, queries, exclude ids, {min_match: [kth per query]})."""
+    C, Q = 70_000, 8
+    assert C > 256 * 256
+    shared = [10.0, 20.0, 30.0, 40.0, 50.0, 60.0]
+    ids = np.arange(1, C + 1, dtype=np.int32)
+    keys = np.empty((C, 7))
+    keys[:, :6] = shared
+    keys[:, 6] = 1000.0 + ids
+    queries = []
+    for j in range(Q):
+        q = shared[j % 6:] + shared[:j % 6]
+        q.insert(j % 3, -1.0 - j)
+        q.insert(3 + j % 5, -100.0 - j)
+        queries.append(q)
+    kth = {mm: [[i for i, v in enumerate(q) if v in shared][mm - 1] for q in queries] for mm in (1, 3, 6)}
+    assert all(len(set(k)) > 1 for k in kth.values())         # kth differs between the queries
+    return ids, np.arange(C + 1, dtype=np.int64) * 7, keys.reshape(-1), queries, [1 + 1000 * j for j in range(Q)], kth
+
+
+def check_past_the_stage(run, ids, excl, kth):
+    """run(min_match, cap) -> (hits [Q, cap, 3], n [Q]) as numpy arrays."""
+    C = len(ids)
+    for mm in (1, 3, 6):                         # two smallest positions / five smallest / count + the fix-up walk
+        hits, n = run(mm, C)
+        for j, e in enumerate(excl):
+            assert n[j] == C - 1, (mm, j, n[j])
+            h = hits[j, :C - 1]
+            assert np.array_equal(np.sort(h[:, 0]), ids[ids != e]), (mm, j)
+            assert (h[:, 1] == 6).all() and (h[:, 2] == kth[mm][j]).all(), (mm, j)
+    hits, n = run(3, 1000)                       # the flush clipped to cap
+    for j, e in enumerate(excl):
+        assert n[j] == C - 1, (j, n[j])
+        h = hits[j]
+        assert len(np.unique(h[:, 0])) == 1000 and (h[:, 0] >= 1).all() and (h[:, 0] <= C).all() and (h[:, 0] != e).all(), j
+        assert (h[:, 1] == 6).all() and (h[:, 2] == kth[3][j]).all(), j
+
+
+def test_block_hit_list_past_its_stage(dc):
+    ids, offs, keys, queries, excl, kth = past_the_stage_case()
+    dc.upload_csr(ids, offs, keys)
+    d_q, d_off, max_len = tc.pack_queries(queries, DEV)
+    d_ex = torch.tensor(excl, dtype=torch.int32, device=DEV)
+
+    def run(mm, cap):
+        hits, n = dc.match(d_q, d_off, max_len, mm, cap, d_exclude_ids=d_ex, algo=_lib.ALGO_Q1)
+        torch.cuda.synchronize()
+        return hits.cpu().numpy(), n.cpu().numpy()
+    check_past_the_stage(run, ids, excl, kth)
+
+
 def test_upsert_replaces_first_row_and_compacts(dc):
     dc.upload([(1, [1.0, 2.0]), (2, [3.0, 4.0]), (1, [9.0])])     # duplicate video_id rows allowed
     assert dc.find_duplicates([9.0, 1.0], 1) == [(1, 1), (1, 1)]

@@ -157,6 +157,23 @@ def test_cap_truncation_reports_the_true_count(dc):
         assert n == 50 and got == exp[:cap]
 
 
+def test_block_hit_list_past_its_stage(dc):
+    """test_match_gpu's case through match_tol (the sweep: no cell postings): every block of ts_match_tol_kernel goes
+    past its 256-entry stage, at min_match 6 the hits go through the tolerant fix-up walk, and a small cap clips the
+    flush."""
+    from tests.test_match_gpu import check_past_the_stage, past_the_stage_case
+    ids, offs, keys, queries, excl, kth = past_the_stage_case()
+    dc.upload_csr(ids, offs, keys)
+    d_q, d_off, max_len = tc.pack_queries(queries, DEV)
+    d_ex = torch.tensor(excl, dtype=torch.int32, device=DEV)
+
+    def run(mm, cap):
+        hits, n = dc.match_tol(d_q, d_off, max_len, 0.001, mm, cap, d_exclude_ids=d_ex)
+        torch.cuda.synchronize()
+        return hits.cpu().numpy(), n.cpu().numpy()
+    check_past_the_stage(run, ids, excl, kth)
+
+
 # ---- 3. query lengths across every internal boundary ------------------------------------------------------------
 @pytest.mark.parametrize("n", [1, 255, 256, 257, 4095, 4096, 4097, LDS_KEYS - 1, LDS_KEYS, LDS_KEYS + 1, 10000])
 def test_query_lengths_across_the_boundaries(dc, n):

@@ -45,6 +45,7 @@
 // for directories of more than 4,096 slices: 2.7 ms).
 #pragma once
 #include "tvz_match_kernels.h"
+#include "tvz_wave.h"
 
 namespace {
 
@@ -936,7 +937,7 @@ __device__ __forceinline__ void ix_lookup_body(
             p0 = incl - len0;
             const unsigned long long some = __ballot(len0 != 0u);
             if (len0) {
-                const uint32_t j = __builtin_amdgcn_mbcnt_hi((uint32_t)(some >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)some, 0u));
+                const uint32_t j = lanes_below(some);
                 lst[j] = make_uint2(off0 - p0, (uint32_t)i);             // local posting t of the wave = post[.x + t]
                 if (p0 < (uint32_t)kIxPW) atomicOr(&lbits[p0 >> 5], 1u << (p0 & 31u));
             }
@@ -964,8 +965,7 @@ __device__ __forceinline__ void ix_lookup_body(
                 uint32_t before = 0;
 #pragma unroll
                 for (int u = 0; u < N; ++u) {
-                    const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(M[u] >> 32),
-                                           __builtin_amdgcn_mbcnt_lo((uint32_t)M[u], 0u));   // starts before this lane
+                    const uint32_t below = lanes_below(M[u]);   // starts before this lane
                     const uint32_t here = (uint32_t)((M[u] >> lane) & 1ull);
                     e[u] = lst[before + below + here - 1u];
                     before += (uint32_t)__popcll(M[u]);

@@ -23,6 +23,7 @@
 // Results are identical to ts_match_index_topk_kernel (tests/test_index_topk_gpu.py runs both on the same handle).
 #pragma once
 #include "tvz_index_kernels.h"
+#include "tvz_wave.h"
 
 namespace {
 
@@ -200,7 +201,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
             const uint32_t p0 = tw + incl - len_[c];
             const unsigned long long some = __ballot(len_[c] != 0u);
             if (len_[c]) {
-                const uint32_t j = n_lists + __builtin_amdgcn_mbcnt_hi((uint32_t)(some >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)some, 0u));
+                const uint32_t j = n_lists + lanes_below(some);
                 lst[j] = make_uint2(off_[c] - p0, (uint32_t)((c0 + c) * 64 + lane) | (len_[c] << 9));    // local posting t of the wave = post[.x + t]
                 if (p0 < (uint32_t)kWqRegPost) atomicOr(&lbits[p0 >> 5], 1u << (p0 & 31u));
             }
@@ -282,7 +283,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
                     const uint32_t mlo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)Mv);
                     const uint32_t mhi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(Mv >> 32));
                     const unsigned long long M = ((unsigned long long)mhi << 32) | mlo;      // in SGPRs
-                    const uint32_t below = __builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, 0u));   // starts before this lane
+                    const uint32_t below = lanes_below(M);   // starts before this lane
                     const uint32_t here = (uint32_t)((M >> lane) & 1ull);
                     const uint32_t j = before + below + here;          // (>= 1 wherever a posting exists)
                     e[u] = lst[j ? j - 1u : 0u];

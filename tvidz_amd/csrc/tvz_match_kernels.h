@@ -21,6 +21,7 @@
 #include <cstring>
 
 #include "tvz_common.h"
+#include "tvz_wave.h"
 
 #ifndef TVZ_MATCH_STEP
 #define TVZ_MATCH_STEP 2   // 16-byte key loads per lane and sweep step (4 keys); 3/4/6 measured no faster
@@ -50,35 +51,6 @@ __device__ __forceinline__ Row load_row(const Row *p) {
     r.len = v.z;
     r.vid = v.w;
     return r;
-}
-
-// LDS counters updated by other lanes of the SAME wave are read back by plain loads: make the
-// compiler keep the order (the hardware completes a wave's LDS operations in order).
-__device__ __forceinline__ void wave_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// ---- wave64 inclusive prefix sum on the VALU (six DPP adds: row_shr 1/2/4/8 inside the 16-lane rows,
-// then row_bcast 15 and 31 across them).  A __shfl_up ladder is six ds_bpermute round trips through
-// the LDS crossbar (~100 cycles each, and LDS-pipe time): the index lookup runs five scans per
-// sub-index and was paying ~3,000 cycles of pure latency for them.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_add_u32(uint32_t v) {
-    // lanes whose DPP source is invalid or masked take `old` = 0
-    return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);
-}
-__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v) {
-    v = dpp_add_u32<0x111, 0xf>(v);  // row_shr:1
-    v = dpp_add_u32<0x112, 0xf>(v);  // row_shr:2
-    v = dpp_add_u32<0x114, 0xf>(v);  // row_shr:4
-    v = dpp_add_u32<0x118, 0xf>(v);  // row_shr:8   -> inclusive scan inside each row
-    v = dpp_add_u32<0x142, 0xa>(v);  // row_bcast:15 into rows 1,3
-    v = dpp_add_u32<0x143, 0xc>(v);  // row_bcast:31 into rows 2,3
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_total(uint32_t incl) {       // of an inclusive scan
-    return (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
 }
 
 // ---- canonical key: integer-only so subnormals / signed zero never meet FP modes ----
@@ -116,12 +88,8 @@ constexpr size_t kTileLds = (size_t)kTileSlots * 4 + (size_t)kTileMaxEntries * 8
                             (size_t)(kTileBlock / 64) * kRing * 12;
 
 // Per (row group, query of the tile) state in LDS: a hit counter and the FIVE smallest matching
-// query positions, packed as 5 x 12 bits (ascending from bit 0, 0xfff = none) in one 64-bit word
-// updated with a CAS loop.  kth for min_match <= 5 (the reference's default and the driver's 2)
-// is read straight from it.
-constexpr int kTop = 5;
-constexpr unsigned long long kTopNone = 0x0fffffffffffffffULL;   // 5 fields of 0xfff
-
+// query positions, packed in one 64-bit word (tvz_wave.h: top5_insert) updated with a CAS loop.
+// kth for min_match <= 5 (the reference's default and the driver's 2) is read straight from it.
 // How much of kth a kernel tracks: the MODE template argument of the Q1, tolerant, index and one-wave kernels, picked
 // from min_match by kth_mode (the fused lookup's TOP5 is MODE == kModeTop5).
 constexpr int kModeM2 = 0;                            // min_match 1..2: the two smallest positions
@@ -131,20 +99,16 @@ constexpr int kth_mode(int32_t min_match) {
     return min_match < 1 || min_match > kTop ? kModeCount : min_match <= 2 ? kModeM2 : kModeTop5;
 }
 
-__device__ __forceinline__ unsigned long long top5_insert(unsigned long long p, uint32_t x) {
-    uint32_t a[kTop];
-#pragma unroll
-    for (int i = 0; i < kTop; ++i) a[i] = (uint32_t)(p >> (12 * i)) & 0xfffu;
-#pragma unroll
-    for (int i = 0; i < kTop; ++i) {      // insertion network: keep the smaller, carry the larger
-        const uint32_t lo = a[i] < x ? a[i] : x;
-        x = a[i] < x ? x : a[i];
-        a[i] = lo;
-    }
-    unsigned long long r = 0;
-#pragma unroll
-    for (int i = 0; i < kTop; ++i) r |= (unsigned long long)a[i] << (12 * i);
-    return r;
+// kth of a hit with min_match >= 1, from what the MODE kept: the group's two smallest matching
+// positions, its five smallest (`top`: top5_insert's packed word, or an ascending array), or nothing -
+// then the row goes into the field for the fix-up kernel to resolve.
+__device__ __forceinline__ uint32_t top5_at(unsigned long long top, int i) { return (uint32_t)(top >> (12 * i)) & 0xfffu; }
+__device__ __forceinline__ uint32_t top5_at(const uint32_t (&top)[kTop], int i) { return top[i]; }
+template <int MODE, class TOP>
+__device__ __forceinline__ int32_t kth_of(int32_t min_match, uint32_t m1, uint32_t m2, const TOP &top, int64_t row) {
+    if constexpr (MODE == kModeM2) return (int32_t)(min_match == 1 ? m1 : m2);
+    else if constexpr (MODE == kModeTop5) return (int32_t)top5_at(top, min_match - 1);
+    else return -2 - (int32_t)row;
 }
 
 // pair index (13 bits) and tag (16 bits) from one mix of the key: 9 full-rate VALU ops (one
@@ -365,8 +329,7 @@ __global__ __launch_bounds__(kTileBlock) void ts_match_tile_kernel(
                 const bool slow = valid & (((w[j].x >> 16) == tg[j]) | (w[j].y != kFree));
                 const unsigned long long bal = __ballot(slow);
                 if (bal) {                                        // wave-uniform
-                    const uint32_t ofs = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32),
-                                         __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+                    const uint32_t ofs = lanes_below(bal);
                     if (slow) {
                         const uint32_t idx = (qtail + ofs) & (kRing - 1);
                         qk[idx] = kk[j];
@@ -572,8 +535,7 @@ __global__ __launch_bounds__(kJoinBlock, 8) void ts_match_join_kernel(
         auto push = [&](bool cand, uint32_t slot, uint32_t ki) {
             const unsigned long long bal = __ballot(cand);
             if (bal) {                                                // wave-uniform
-                const uint32_t ofs = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32),
-                                     __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+                const uint32_t ofs = lanes_below(bal);
                 if (cand) {
                     const uint32_t idx = (qtail + ofs) & (uint32_t)(kJoinRing - 1);
                     rslot[idx] = slot;
@@ -662,11 +624,6 @@ __global__ __launch_bounds__(kJoinBlock, 8) void ts_match_join_kernel(
 // Rare (a video with thousands of cuts), so simple beats fast: a 16-lane group owns a row, every
 // row key is binary-searched in the query's sorted distinct keys (sq, with multiplicities) and the
 // hit (video_id, count) is emitted with kth = -2 - row, which ts_kth_fixup_kernel resolves.
-template <int CTRL>
-__device__ __forceinline__ int dpp_row16(int v) {
-    return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true);
-}
-
 // ---- a batch's long queries, prepared ON THE DEVICE (no host copy, no allocation, no synchronisation) ----------
 // One block per long query: its canonical keys into a power-of-two scratch (NaN -> the largest int64: sorted to the
 // end, never a key), bitonic sort there, then the distinct keys and their multiplicities - what
@@ -767,10 +724,7 @@ __global__ __launch_bounds__(kBlock) void ts_match_longq_kernel(
         }
         if (lo < m && sq[lo] == k) cnt += smult[lo];
     }
-    cnt += dpp_row16<0xB1>(cnt);    // quad_perm [1,0,3,2]
-    cnt += dpp_row16<0x4E>(cnt);    // quad_perm [2,3,0,1]
-    cnt += dpp_row16<0x141>(cnt);   // row_half_mirror
-    cnt += dpp_row16<0x140>(cnt);   // row_mirror
+    cnt = group16_sum(cnt);
     if (gl == 0 && cnt >= min_match && row.vid != exclude_one) {
         const int slot = atomicAdd(&hits_n[0], 1);
         if (slot < cap) {
@@ -781,6 +735,29 @@ __global__ __launch_bounds__(kBlock) void ts_match_longq_kernel(
     }
 }
 
+// The walk of the kth fix-ups: the position of the min_match-th of a query's qlen values that the row
+// holds, TVZ_KTH_NEVER if fewer do.  A group takes 16 values per step; holds(i) is a lane's test of value i.
+template <class LEN, class HOLDS>
+__device__ __forceinline__ int kth_walk(LEN qlen, int32_t min_match, HOLDS holds) {
+    const int gl = threadIdx.x & (kGroup - 1);
+    const int gshift = (threadIdx.x & 63) & ~(kGroup - 1);
+    int kth = TVZ_KTH_NEVER;
+    int running = 0;
+    for (LEN base = 0; base < qlen && kth == TVZ_KTH_NEVER; base += kGroup) {
+        const LEN i = base + gl;
+        const bool hit = i < qlen && holds(i);
+        const uint32_t m16 = (uint32_t)(__ballot(hit) >> gshift) & 0xffffu;
+        const int c = __popc(m16);
+        if (running + c >= min_match) {
+            uint32_t m = m16;
+            for (int need = min_match - running; need > 1; --need) m &= m - 1;
+            kth = (int)(base + (__ffs(m) - 1));
+        }
+        running += c;
+    }
+    return kth;
+}
+
 // kth for min_match > 5: per stored hit, walk the query in order and binary-search the row.
 __global__ __launch_bounds__(kBlock) void ts_kth_fixup_kernel(
     const Row *__restrict__ rows, const int64_t *__restrict__ keys,
@@ -789,7 +766,6 @@ __global__ __launch_bounds__(kBlock) void ts_kth_fixup_kernel(
     const int q = blockIdx.x;
     const int gl = threadIdx.x & (kGroup - 1);
     const int g = threadIdx.x / kGroup;
-    const int gshift = (threadIdx.x & 63) & ~(kGroup - 1);
     int n = hits_n[(size_t)q * ns];
     if (n > cap) n = cap;
     const int64_t qo = q_offsets[q];
@@ -801,29 +777,16 @@ __global__ __launch_bounds__(kBlock) void ts_kth_fixup_kernel(
         if (code > -2) continue;
         const Row row = load_row(rows + (-2 - code));
         const int64_t *rk = keys + row.off;
-        int kth = TVZ_KTH_NEVER;
-        int running = 0;
-        for (int base = 0; base < qlen && kth == TVZ_KTH_NEVER; base += kGroup) {
-            const int i = base + gl;
-            bool hit = false;
+        const int kth = kth_walk(qlen, min_match, [&](int i) {
             int64_t k;
-            if (i < qlen && canon_key(qv[i], k)) {
-                int lo = 0, hi = row.len;
-                while (lo < hi) {
-                    const int mid = (lo + hi) >> 1;
-                    if (rk[mid] < k) lo = mid + 1; else hi = mid;
-                }
-                hit = lo < row.len && rk[lo] == k;
+            if (!canon_key(qv[i], k)) return false;
+            int lo = 0, hi = row.len;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (rk[mid] < k) lo = mid + 1; else hi = mid;
             }
-            const uint32_t m16 = (uint32_t)(__ballot(hit) >> gshift) & 0xffffu;
-            const int c = __popc(m16);
-            if (running + c >= min_match) {
-                uint32_t m = m16;
-                for (int need = min_match - running; need > 1; --need) m &= m - 1;
-                kth = base + (__ffs(m) - 1);
-            }
-            running += c;
-        }
+            return lo < row.len && rk[lo] == k;
+        });
         if (gl == 0) h[2] = kth;
     }
 }
@@ -1047,22 +1010,65 @@ inline size_t q1_lds_bytes(int s_log2) {
     return (((size_t)8 + 2) << s_log2) + ((size_t)8 << q1_bloom_log2(s_log2));
 }
 
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp16(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
+// ---- the block's hit list ---------------------------------------------------------------------
+// Hits that are not written to the host (HOSTOUT = false) are staged per block in LDS and the
+// block reserves its range of the query's list with ONE global atomic at the end: at min_match 2 a
+// query has thousands of accidental hits, and a returning atomic per hit on one counter serialised
+// them (1.96 TB/s against 3.66 TB/s for the same sweep at min_match 5).  A HOSTOUT block owns a
+// region of the pinned list and writes there directly.
+// A kernel has one sink, in static LDS of its own (the stage and two words: kQ1StaticLds, kTolIxStaticLds):
+// hit_open() by one thread before a barrier, hit_emit() per hit, hit_flush() by every thread BEHIND a
+// barrier that follows the last emit.  `dest` is a callable that returns the query's HitList; it is
+// called where the list is needed and not before, so a kernel that keeps these arguments out of
+// registers (ts_tol_index_kernel) reads them on the rare path only.
+constexpr int kQ1Stage = 256;                         // staged hits per block (12 B each); more go out directly
+__shared__ int32_t s_stage[kQ1Stage * 3];
+__shared__ int32_t s_stage_n, s_stage_base;               // the block's hits so far; the stage's place in the query's list
+struct HitList {           // where a query's hits go in device memory
+    int32_t *hits;         // [queries][cap][3]
+    int32_t *n;            // the query's counter
+    int64_t q;             // the query
+    int32_t cap;           // hits its list holds
+};
+__device__ __forceinline__ void hit_write(int32_t *h, int32_t vid, int32_t cnt, int32_t kth) {
+    h[0] = vid;
+    h[1] = cnt;
+    h[2] = kth;
 }
-template <int CTRL>
-__device__ __forceinline__ unsigned long long dpp16_64(unsigned long long v) {
-    return ((unsigned long long)dpp16<CTRL>((uint32_t)(v >> 32)) << 32) | dpp16<CTRL>((uint32_t)v);
+__device__ __forceinline__ void hit_open() { s_stage_n = 0; }
+
+template <bool HOSTOUT, class DEST>
+__device__ __forceinline__ void hit_emit(int32_t vid, int32_t cnt, int32_t kth, const HostOut &ho, int bx, DEST dest) {
+    const int slot = atomicAdd(&s_stage_n, 1);                        // LDS
+    if constexpr (HOSTOUT) {
+        hit_write(ho.hits + ((int64_t)bx * ho.region + slot) * 3, vid, cnt, kth);
+    } else if (slot < kQ1Stage) {
+        hit_write(&s_stage[slot * 3], vid, cnt, kth);
+    } else {                                                        // a block with > 256 hits: the rest one by one
+        const int gs = atomicAdd(dest().n, 1);
+        if (gs < dest().cap) {
+            const HitList l = dest();
+            hit_write(l.hits + (l.q * l.cap + gs) * 3, vid, cnt, kth);
+        }
+    }
 }
 
-// butterfly over a 16-lane DPP row: after the four steps every lane holds the reduction of all
-// 16; each step combines two DISJOINT sets of lanes (needed for the second-smallest merge)
-#define TVZ_ROW16_BUTTERFLY(STEP) \
-    STEP(0xB1)  /* quad_perm [1,0,3,2] */ \
-    STEP(0x4E)  /* quad_perm [2,3,0,1] */ \
-    STEP(0x141) /* row_half_mirror     */ \
-    STEP(0x140) /* row_mirror          */
+template <bool HOSTOUT, int BS, class DEST>
+__device__ __forceinline__ void hit_flush(const HostOut &ho, int bx, DEST dest) {
+    if constexpr (HOSTOUT) {
+        if (threadIdx.x == 0) ho.counts[bx] = s_stage_n;
+    } else {
+        const int staged = s_stage_n < kQ1Stage ? s_stage_n : kQ1Stage;
+        if (staged == 0) return;                                    // block-uniform
+        if (threadIdx.x == 0) s_stage_base = atomicAdd(dest().n, staged);
+        __syncthreads();
+        const int hb = s_stage_base;
+        const HitList l = dest();
+        int32_t *dst = l.hits + (l.q * l.cap + hb) * 3;
+        const int room = l.cap - hb < staged ? (l.cap - hb > 0 ? l.cap - hb : 0) : staged;
+        for (int i = threadIdx.x; i < room * 3; i += BS) dst[i] = s_stage[i];   // consecutive dwords: coalesced
+    }
+}
 
 // the 32-bit mix every Q1 hash is cut from (bits 0-4 / 5-9: the two Bloom bits; x * C: the slots)
 __device__ __forceinline__ uint32_t q1_mix(int64_t k) {
@@ -1075,11 +1081,7 @@ __device__ __forceinline__ uint32_t q1_mix(int64_t k) {
 // The body is a device function over (block bx of nbx along the rows, query q) with BS threads, so
 // that tvz_find_duplicates can run it NEXT TO the index lookup in one launch (ts_find_fused_kernel:
 // the lookup's blocks answer the indexed rows, these sweep the delta table).
-// Hits that are not written to the host (HOSTOUT = false) are staged per block in LDS and the
-// block reserves its range of the query's list with ONE global atomic at the end: at min_match 2 a
-// query has thousands of accidental hits, and a returning atomic per hit on one counter serialised
-// them (1.96 TB/s against 3.66 TB/s for the same sweep at min_match 5).
-constexpr int kQ1Stage = 256;                         // staged hits per block (12 B each); more go out directly
+// Hits leave through the block's hit sink.
 template <int MODE, bool HOSTOUT, int BS>
 __device__ __forceinline__ void q1_body(
     const Row *__restrict__ rows, int64_t n_rows, const int64_t *__restrict__ keys,
@@ -1088,18 +1090,16 @@ __device__ __forceinline__ void q1_body(
     int32_t *__restrict__ hits, int32_t *__restrict__ hits_n, int32_t ns, int32_t s_log2, HostOut ho,
     const QByVal &qv, const int bx, const int nbx, const int q) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    __shared__ int32_t s_stage[HOSTOUT ? 1 : kQ1Stage * 3];
-    __shared__ int32_t s_stage_base;
     const int S = 1 << s_log2;
     const int b_log2 = s_log2 < kQ1BloomMaxLog2 ? s_log2 : kQ1BloomMaxLog2;
     int64_t *skey = reinterpret_cast<int64_t *>(smem);
     uint2 *bloom = reinterpret_cast<uint2 *>(skey + S);
     uint16_t *spos = reinterpret_cast<uint16_t *>(bloom + ((size_t)1 << b_log2));
-    __shared__ int32_t s_nhits, s_dups;
+    __shared__ int32_t s_dups;
     const bool byval = q_offsets == nullptr;          // the query is in the kernel arguments
     const int64_t qo = byval ? 0 : q_offsets[q];
     const int64_t n = byval ? qv.n : q_offsets[q + 1] - qo;
-    if (threadIdx.x == 0) { s_nhits = 0; s_dups = 0; }
+    if (threadIdx.x == 0) { hit_open(); s_dups = 0; }
     if (2 * n > S) {
         // the caller's max_query_len was not an upper bound (the tables are sized from it)
         if (!HOSTOUT && threadIdx.x == 0) hits_n[(size_t)q * ns] = INT32_MIN;
@@ -1156,6 +1156,7 @@ __device__ __forceinline__ void q1_body(
         const uint2 w = bloom[y >> word_shift];
         return (w.x >> (x & 31u)) & (w.y >> ((x >> 5) & 31u)) & 1u;
     };
+    auto dest = [&] { return HitList{hits, &hits_n[(size_t)q * ns], q, cap}; };
     int64_t r = (int64_t)bx * kGroups + g;
     const int64_t last_row = n_rows - 1;
     Row row = load_row(rows + (r < n_rows ? r : last_row));       // past the end: a valid row, never used
@@ -1180,9 +1181,7 @@ __device__ __forceinline__ void q1_body(
                 may += (maybe(cur[j].x) & (uint32_t)(i < row.len)) + (maybe(cur[j].y) & (uint32_t)(i + 1 < row.len));
             }
         }
-#define TVZ_SUM_STEP(C) may += dpp16<C>(may);
-        TVZ_ROW16_BUTTERFLY(TVZ_SUM_STEP)
-#undef TVZ_SUM_STEP
+        may = group16_sum(may);
         const bool cand = (int32_t)may >= thr;
         if (__ballot(cand) != 0ull) {
             // ---- exact pass over the candidate rows of this wave (their keys are L2-hot) ----
@@ -1234,67 +1233,22 @@ __device__ __forceinline__ void q1_body(
                 }
             }
             // the group's totals (every lane ends up with them; non-candidate groups carry zeros)
-#define TVZ_SUM_STEP(C) cnt += dpp16<C>(cnt);
-            TVZ_ROW16_BUTTERFLY(TVZ_SUM_STEP)
-#undef TVZ_SUM_STEP
+            cnt = group16_sum(cnt);
             const bool hit = cand && (int64_t)cnt >= (int64_t)min_match && row.vid != excl;
             if (__ballot(hit) != 0ull) {
-                if constexpr (MODE == kModeM2) {
-#define TVZ_M2_STEP(C) { const uint32_t p1 = dpp16<C>(m1), p2 = dpp16<C>(m2); \
-                    const uint32_t lo = m1 < p1 ? m1 : p1, hi = m1 < p1 ? p1 : m1, r2 = m2 < p2 ? m2 : p2; \
-                    m1 = lo; m2 = hi < r2 ? hi : r2; }
-                    TVZ_ROW16_BUTTERFLY(TVZ_M2_STEP)
-#undef TVZ_M2_STEP
-                } else if constexpr (MODE == kModeTop5) {
-#define TVZ_T5_STEP(C) { const unsigned long long p = dpp16_64<C>(top); \
-                    _Pragma("unroll") for (int i = 0; i < kTop; ++i) top = top5_insert(top, (uint32_t)(p >> (12 * i)) & 0xfffu); }
-                    TVZ_ROW16_BUTTERFLY(TVZ_T5_STEP)
-#undef TVZ_T5_STEP
-                }
+                if constexpr (MODE == kModeM2) group16_min2(m1, m2);
+                else if constexpr (MODE == kModeTop5) group16_top5(top);
             }
             if (hit && gl == 0) {
-                int32_t kth;
-                if (min_match <= 0) kth = -1;
-                else if constexpr (MODE == kModeM2) kth = (int32_t)(min_match == 1 ? m1 : m2);
-                else if constexpr (MODE == kModeTop5) kth = (int32_t)((top >> (12 * (min_match - 1))) & 0xfffu);
-                else kth = -2 - (int32_t)r;                 // resolved by ts_kth_fixup_kernel
-                const int slot = atomicAdd(&s_nhits, 1);            // LDS
-                if constexpr (HOSTOUT) {
-                    int32_t *h = ho.hits + ((int64_t)bx * ho.region + slot) * 3;
-                    h[0] = row.vid;
-                    h[1] = (int32_t)cnt;
-                    h[2] = kth;
-                } else if (slot < kQ1Stage) {
-                    s_stage[slot * 3 + 0] = row.vid;
-                    s_stage[slot * 3 + 1] = (int32_t)cnt;
-                    s_stage[slot * 3 + 2] = kth;
-                } else {                                            // a block with > 256 hits: the rest one by one
-                    const int gs = atomicAdd(&hits_n[(size_t)q * ns], 1);
-                    if (gs < cap) {
-                        int32_t *h = hits + ((int64_t)q * cap + gs) * 3;
-                        h[0] = row.vid;
-                        h[1] = (int32_t)cnt;
-                        h[2] = kth;
-                    }
-                }
+                const int32_t kth = min_match <= 0 ? -1 : kth_of<MODE>(min_match, m1, m2, top, r);
+                hit_emit<HOSTOUT>(row.vid, (int32_t)cnt, kth, ho, bx, dest);
             }
         }
         row = nrow;
         r = rn;
     }
     __syncthreads();
-    if constexpr (HOSTOUT) {
-        if (threadIdx.x == 0) ho.counts[bx] = s_nhits;
-    } else {
-        const int staged = s_nhits < kQ1Stage ? s_nhits : kQ1Stage;
-        if (staged == 0) return;                                    // block-uniform
-        if (threadIdx.x == 0) s_stage_base = atomicAdd(&hits_n[(size_t)q * ns], staged);
-        __syncthreads();
-        const int base = s_stage_base;
-        int32_t *dst = hits + ((int64_t)q * cap + base) * 3;
-        const int room = cap - base < staged ? (cap - base > 0 ? cap - base : 0) : staged;
-        for (int i = threadIdx.x; i < room * 3; i += BS) dst[i] = s_stage[i];   // consecutive dwords: coalesced
-    }
+    hit_flush<HOSTOUT, BS>(ho, bx, dest);
 }
 
 template <int MODE, bool HOSTOUT>
@@ -1551,8 +1505,7 @@ __device__ __forceinline__ void wave_topk_body(
             for (int e = 0; e < E; ++e) {
                 const bool is = bin[e] >= 0 && bin[e] <= B;
                 const unsigned long long bal = __ballot(is);
-                const uint32_t ofs = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32),
-                                     __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+                const uint32_t ofs = lanes_below(bal);
                 if (is) { ck[base + ofs] = key[e]; cc[base + ofs] = cnt[e]; }
                 base += (uint32_t)__popcll(bal);
             }

@@ -1,6 +1,6 @@
 // tvz_tol_index_kernels.h — the tolerant match through CELL postings (tvz_corpus_tol_index), gfx950 wave64.
-// Included by tvz_match.hip only, after tvz_index_kernels.h (directory format, tol_cell_of) and tvz_tol_kernels.h
-// (tol_row_scan / tol_row_reduce, the top-k lists).
+// Included by tvz_match.hip only.  From tvz_index_kernels.h: the directory format, tol_cell_of; from tvz_tol_kernels.h:
+// tol_row_scan / tol_row_reduce, the top-k keeper; from tvz_match_kernels.h: the block's hit sink, kth_of.
 //
 // The sweeps of tvz_tol_kernels.h read every row to learn, almost always, that it has nothing near the query.  A
 // generation of the index that carries cell postings knows, per cell of `w` seconds, the indexed rows that own a key in
@@ -35,6 +35,10 @@
 //           per wave and written as one partial list with one atomic for the total (tvz_match_tol_topk).
 // Nothing in device memory grows with candidates or hits.
 #pragma once
+#include "tvz_index_kernels.h"
+#include "tvz_match_kernels.h"
+#include "tvz_tol_kernels.h"
+#include "tvz_wave.h"
 
 namespace {
 
@@ -96,10 +100,7 @@ __global__ __launch_bounds__(kTolBlock) void ts_tol_index_kernel(
     __shared__ uint32_t s_bm1[kTolIxWords], s_bm2[kTolIxWords];
     __shared__ uint16_t s_rank[kTolIxWords];
     __shared__ uint32_t s_ws[kTolBlock / 64];
-    __shared__ int32_t s_nhits, s_stage_base;
     __shared__ TolIxParked s_arg;
-    __shared__ int32_t s_stage[TOPK ? 1 : kQ1Stage * 3];
-    __shared__ unsigned long long s_kept[TOPK ? kTolTopkWaves * 64 : 1], s_stg[TOPK ? kTolTopkWaves * 64 : 1];
     const int q = blockIdx.y;
     const int bx = blockIdx.x;
     const int64_t at = q_offsets[q] - q_offsets[0];
@@ -108,23 +109,18 @@ __global__ __launch_bounds__(kTolBlock) void ts_tol_index_kernel(
         if (!TOPK && threadIdx.x == 0 && bx == 0) hits_n[q] = INT32_MIN;
         return;                              // (TOPK: ts_tol_topk_reduce_kernel flags it)
     }
-    double *lv = reinterpret_cast<double *>(smem);
-    int32_t *lp = reinterpret_cast<int32_t *>(smem + (size_t)((lds_keys + 1) & ~1) * 8);
-    for (int e = threadIdx.x; e < m; e += kTolBlock) {
-        lv[e] = sv[at + e];
-        lp[e] = sp[at + e];
-    }
-    const double *s = lv;
-    const int32_t *pos = lp;
+    const TolQuery lq = tol_query_to_lds(smem, lds_keys, sv, sp, at, m);
+    const double *s = lq.s;
+    const int32_t *pos = lq.pos;
     const int lane = threadIdx.x & 63;
     const int wv = threadIdx.x >> 6;
     const int gl = threadIdx.x & (kGroup - 1);
     const int g = threadIdx.x / kGroup;
-    unsigned long long *kept = s_kept + (TOPK ? wv * 64 : 0), *stage = s_stg + (TOPK ? wv * 64 : 0);
-    if (TOPK) kept[lane] = kTolPad;
+    TolTopkWave tw = {};
+    if constexpr (TOPK) tw = tol_topk_open(wv, lane);
     for (int i = threadIdx.x; i < kTolIxWords; i += kTolBlock) { s_bm1[i] = 0; s_bm2[i] = 0; }
     if (threadIdx.x == 0) {
-        s_nhits = 0;
+        if constexpr (!TOPK) hit_open();
         s_arg.dir = dir;
         s_arg.post = post;
         s_arg.cellw = cellw;
@@ -151,8 +147,7 @@ __global__ __launch_bounds__(kTolBlock) void ts_tol_index_kernel(
     const int grp = bx / split, prt = bx - grp * split;
     const int sub_lo = grp * spb;
     const int sub_hi = sub_lo + spb < n_sub ? sub_lo + spb : n_sub;
-    unsigned long long thr = kTolPad;        // TOPK: the wave's k-th word
-    int n_stage = 0, n_hits = 0;             // TOPK: wave-uniform
+    auto dest = [&] { return HitList{s_arg.hits, &s_arg.hits_n[blockIdx.y], blockIdx.y, s_arg.cap}; };
 
     for (int sub = sub_lo; sub < sub_hi; ++sub) {
         // ---- pass A ----
@@ -252,41 +247,10 @@ __global__ __launch_bounds__(kTolBlock) void ts_tol_index_kernel(
             const bool hit = live && (int64_t)cnt >= (int64_t)min_match;
             if (__ballot(hit) == 0ull) continue;
             tol_row_reduce<MODE>(m1, m2, tk);
-            uint32_t kth;
-            if constexpr (MODE == kModeM2) kth = min_match == 1 ? m1 : m2;
-            else kth = tk[min_match - 1];
+            const int32_t kth = kth_of<MODE>(min_match, m1, m2, tk, r);
             const bool lead = hit && gl == 0;
-            if constexpr (TOPK) {
-                const unsigned long long word64 = ix_tk_pack((int32_t)kth, vid, cnt);
-                n_hits += __popcll(__ballot(lead));
-                const bool cd = lead && word64 < thr;
-                const unsigned long long cb = __ballot(cd);
-                if (cb != 0ull) {
-                    const int before = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(cb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cb, 0u));
-                    if (cd) stage[n_stage + before] = word64;
-                    n_stage += __popcll(cb);
-                    if (n_stage > 64 - 64 / kGroup) {                // the next step may bring one per group
-                        __builtin_amdgcn_wave_barrier();
-                        thr = tol_topk_compact(kept, stage, n_stage, k, lane);
-                        n_stage = 0;
-                    }
-                }
-            } else if (lead) {
-                const int slot = atomicAdd(&s_nhits, 1);             // LDS
-                if (slot < kQ1Stage) {
-                    s_stage[slot * 3 + 0] = vid;
-                    s_stage[slot * 3 + 1] = (int32_t)cnt;
-                    s_stage[slot * 3 + 2] = (int32_t)kth;
-                } else {                                             // more than the stage holds: one by one
-                    const int gs = atomicAdd(&s_arg.hits_n[blockIdx.y], 1);
-                    if (gs < s_arg.cap) {
-                        int32_t *h = s_arg.hits + ((int64_t)blockIdx.y * s_arg.cap + gs) * 3;
-                        h[0] = vid;
-                        h[1] = (int32_t)cnt;
-                        h[2] = (int32_t)kth;
-                    }
-                }
-            }
+            if constexpr (TOPK) tol_topk_offer(tw, lead, ix_tk_pack(kth, vid, cnt), k, lane);
+            else if (lead) hit_emit<false>(vid, (int32_t)cnt, kth, HostOut{}, bx, dest);
         }
         __syncthreads();
         if (sub + 1 < sub_hi) {
@@ -294,26 +258,13 @@ __global__ __launch_bounds__(kTolBlock) void ts_tol_index_kernel(
             __syncthreads();
         }
     }
+    // (the walk's last barrier is behind the last emit)
     if constexpr (TOPK) {
-        tol_topk_flush(kept, stage, n_stage, thr, k, lane);
-        if (lane == 0 && n_hits) atomicAdd(&s_nhits, n_hits);            // LDS
-        __syncthreads();
-        if (wv == 0) {                                                   // wave 0 takes the other waves' lists into its own
-#pragma unroll 1
-            for (int j = 1; j < kTolTopkWaves; ++j) tol_topk_take(kept, stage, n_stage, s_kept[j * 64 + lane], thr, k, lane);
-            tol_topk_flush(kept, stage, n_stage, thr, k, lane);
-            if (lane < k) s_arg.part[((int64_t)q * s_arg.n_lists + bx) * k + lane] = kept[lane];
-        }
-        if (threadIdx.x == 0 && s_nhits) atomicAdd(&s_arg.hits_n[q], s_nhits);
+        tol_topk_finish(tw, k, wv, lane, [&] {
+            return TolTopkOut{s_arg.part + ((int64_t)q * s_arg.n_lists + bx) * k, &s_arg.hits_n[q]};
+        });
     } else {
-        const int staged = s_nhits < kQ1Stage ? s_nhits : kQ1Stage;
-        if (staged == 0) return;                                 // block-uniform
-        if (threadIdx.x == 0) s_stage_base = atomicAdd(&s_arg.hits_n[q], staged);
-        __syncthreads();
-        const int hb = s_stage_base, a_cap = s_arg.cap;
-        int32_t *dst = s_arg.hits + ((int64_t)q * a_cap + hb) * 3;
-        const int room = a_cap - hb < staged ? (a_cap - hb > 0 ? a_cap - hb : 0) : staged;
-        for (int i = threadIdx.x; i < room * 3; i += kTolBlock) dst[i] = s_stage[i];
+        hit_flush<false, kTolBlock>(HostOut{}, bx, dest);
     }
 }
 

@@ -1,5 +1,6 @@
 // tvz_tol_kernels.h — opt-in tolerant duplicate match (tvz_find_duplicates_tol / tvz_match_tol), gfx950 wave64.
-// Included by tvz_match.hip only, after tvz_match_kernels.h (Row, canon_key, dpp16, HostOut, the Q1 staging).
+// Included by tvz_match.hip only.  From tvz_match_kernels.h: Row, the kth modes and kth_of, HostOut and the block's
+// hit sink, the fix-up walk; from tvz_index_kernels.h: ix_tk_pack; from tvz_wave.h: the group reductions.
 //
 // Contract (include/tvz.h): query element q[i] matches row r iff q[i] is not NaN and some key of r has
 //   key == q[i]  or  fabs(q[i] - key) <= tol       (ONE IEEE double subtraction, rounded to nearest)
@@ -25,6 +26,9 @@
 // ts_tol_topk_kernel      the sweep that keeps the k best hits of its block on chip (min_match 1..5) and
 // ts_tol_topk_reduce_kernel  the per-query selection over the blocks' lists: tvz_match_tol_topk.
 #pragma once
+#include "tvz_index_kernels.h"
+#include "tvz_match_kernels.h"
+#include "tvz_wave.h"
 
 namespace {
 
@@ -154,7 +158,7 @@ __device__ __forceinline__ void tol_row_scan(const int64_t *__restrict__ keys, c
             }
             const uint32_t cy = (uint32_t)(ny ? loy : hiy) | (ny ? 0x80000000u : 0u);
             // arena predecessor of x: y of lane gl-1; for lane 0 the y of lane 15 one load earlier
-            const uint32_t t = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)cy, 0x121, 0xf, 0xf, false);  // row_ror:1
+            const uint32_t t = group16_prev(cy);
             const uint32_t px = gl == 0 ? carry : t;
             carry = t;
             auto first_pos_prev = [&]() -> int {                         // hi of arena key 0
@@ -185,20 +189,14 @@ __device__ __forceinline__ void tol_row_scan(const int64_t *__restrict__ keys, c
             }
         }
     }
-#define TVZ_SUM_STEP(C) cnt += dpp16<C>(cnt);
-    TVZ_ROW16_BUTTERFLY(TVZ_SUM_STEP)
-#undef TVZ_SUM_STEP
+    cnt = group16_sum(cnt);
 }
 
 // The butterfly behind tol_row_scan: every lane of the group leaves with the group's smallest positions.
 template <int MODE>
 __device__ __forceinline__ void tol_row_reduce(uint32_t &m1, uint32_t &m2, uint32_t (&tk)[kTop]) {
     if constexpr (MODE == kModeM2) {
-#define TVZ_M2_STEP(C) { const uint32_t p1 = dpp16<C>(m1), p2 = dpp16<C>(m2); \
-        const uint32_t lo = m1 < p1 ? m1 : p1, hi = m1 < p1 ? p1 : m1, r2 = m2 < p2 ? m2 : p2; \
-        m1 = lo; m2 = hi < r2 ? hi : r2; }
-        TVZ_ROW16_BUTTERFLY(TVZ_M2_STEP)
-#undef TVZ_M2_STEP
+        group16_min2(m1, m2);
     } else if constexpr (MODE == kModeTop5) {
         // each step merges two DISJOINT sets of positions (every union element is visited once)
 #define TVZ_T5_STEP(C) { uint32_t o[kTop]; \
@@ -207,6 +205,24 @@ __device__ __forceinline__ void tol_row_reduce(uint32_t &m1, uint32_t &m2, uint3
         TVZ_ROW16_BUTTERFLY(TVZ_T5_STEP)
 #undef TVZ_T5_STEP
     }
+}
+
+// A sorted query: m values ascending and their positions in the query as it was given.
+struct TolQuery {
+    const double *s;
+    const int32_t *pos;
+};
+// The sorted query at sv/sp[at ..) into dynamic LDS laid out for lds_keys values (tol_lds_bytes).  The caller's next
+// block barrier publishes the copy.
+__device__ __forceinline__ TolQuery tol_query_to_lds(unsigned char *smem, int32_t lds_keys, const double *sv,
+                                                     const int32_t *sp, int64_t at, int32_t m) {
+    double *lv = reinterpret_cast<double *>(smem);
+    int32_t *lp = reinterpret_cast<int32_t *>(smem + (size_t)((lds_keys + 1) & ~1) * 8);
+    for (int e = threadIdx.x; e < m; e += kTolBlock) {
+        lv[e] = sv[at + e];
+        lp[e] = sp[at + e];
+    }
+    return TolQuery{lv, lp};
 }
 
 // Batch query preparation.  grid = (ceil(max_query_len / kTolSortBlock), Q).  Query q's non-NaN values go,
@@ -276,8 +292,6 @@ __global__ __launch_bounds__(kTolBlock) void ts_match_tol_kernel(
     const int32_t *__restrict__ exclude_ids, int32_t exclude_one, int32_t cap, int32_t *__restrict__ hits,
     int32_t *__restrict__ hits_n, HostOut ho) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    __shared__ int32_t s_stage[HOSTOUT ? 1 : kQ1Stage * 3];
-    __shared__ int32_t s_nhits, s_stage_base;
     const int q = blockIdx.y;
     const int bx = blockIdx.x;
     int64_t at = 0;
@@ -295,21 +309,17 @@ __global__ __launch_bounds__(kTolBlock) void ts_match_tol_kernel(
     const double *s = sv + at;
     const int32_t *pos = sp + at;
     if constexpr (LDSQ) {
-        double *lv = reinterpret_cast<double *>(smem);
-        int32_t *lp = reinterpret_cast<int32_t *>(smem + (size_t)((lds_keys + 1) & ~1) * 8);
-        for (int e = threadIdx.x; e < m; e += kTolBlock) {
-            lv[e] = s[e];
-            lp[e] = pos[e];
-        }
-        s = lv;
-        pos = lp;
+        const TolQuery lq = tol_query_to_lds(smem, lds_keys, sv, sp, at, m);
+        s = lq.s;
+        pos = lq.pos;
     }
-    if (threadIdx.x == 0) s_nhits = 0;
+    if (threadIdx.x == 0) hit_open();
     __syncthreads();
 
     const int gl = threadIdx.x & (kGroup - 1);
     const int g = threadIdx.x / kGroup;
     const int32_t excl = exclude_ids ? exclude_ids[q] : exclude_one;
+    auto dest = [&] { return HitList{hits, &hits_n[q], q, cap}; };
     const int64_t stride = (int64_t)gridDim.x * kTolGroups;
     int64_t r = (int64_t)bx * kTolGroups + g;
     const int64_t last_row = n_rows - 1;
@@ -323,47 +333,14 @@ __global__ __launch_bounds__(kTolBlock) void ts_match_tol_kernel(
         const bool hit = (int64_t)cnt >= (int64_t)min_match && row.vid != excl;
         if (__ballot(hit) != 0ull) tol_row_reduce<MODE>(m1, m2, tk);
         if (hit && gl == 0) {
-            int32_t kth;
-            if (min_match <= 0) kth = -1;
-            else if constexpr (MODE == kModeM2) kth = (int32_t)(min_match == 1 ? m1 : m2);
-            else if constexpr (MODE == kModeTop5) kth = (int32_t)tk[min_match - 1];
-            else kth = -2 - (int32_t)r;                          // resolved by ts_tol_kth_fixup_kernel
-            const int slot = atomicAdd(&s_nhits, 1);             // LDS
-            if constexpr (HOSTOUT) {
-                int32_t *h = ho.hits + ((int64_t)bx * ho.region + slot) * 3;
-                h[0] = row.vid;
-                h[1] = (int32_t)cnt;
-                h[2] = kth;
-            } else if (slot < kQ1Stage) {
-                s_stage[slot * 3 + 0] = row.vid;
-                s_stage[slot * 3 + 1] = (int32_t)cnt;
-                s_stage[slot * 3 + 2] = kth;
-            } else {                                             // a block with > 256 hits: the rest one by one
-                const int gs = atomicAdd(&hits_n[q], 1);
-                if (gs < cap) {
-                    int32_t *h = hits + ((int64_t)q * cap + gs) * 3;
-                    h[0] = row.vid;
-                    h[1] = (int32_t)cnt;
-                    h[2] = kth;
-                }
-            }
+            const int32_t kth = min_match <= 0 ? -1 : kth_of<MODE>(min_match, m1, m2, tk, r);   // (count: ts_tol_kth_fixup_kernel)
+            hit_emit<HOSTOUT>(row.vid, (int32_t)cnt, kth, ho, bx, dest);
         }
         row = nrow;
         r = rn;
     }
     __syncthreads();
-    if constexpr (HOSTOUT) {
-        if (threadIdx.x == 0) ho.counts[bx] = s_nhits;
-    } else {
-        const int staged = s_nhits < kQ1Stage ? s_nhits : kQ1Stage;
-        if (staged == 0) return;                                 // block-uniform
-        if (threadIdx.x == 0) s_stage_base = atomicAdd(&hits_n[q], staged);
-        __syncthreads();
-        const int hb = s_stage_base;
-        int32_t *dst = hits + ((int64_t)q * cap + hb) * 3;
-        const int room = cap - hb < staged ? (cap - hb > 0 ? cap - hb : 0) : staged;
-        for (int i = threadIdx.x; i < room * 3; i += kTolBlock) dst[i] = s_stage[i];
-    }
+    hit_flush<HOSTOUT, kTolBlock>(ho, bx, dest);
 }
 
 // does some key of the row match q?  The row's numeric order is arena [p-1 .. 0] then [p .. len-1] (p = negative
@@ -401,7 +378,6 @@ __global__ __launch_bounds__(kBlock) void ts_tol_kth_fixup_kernel(
     const int b = blockIdx.x;
     const int gl = threadIdx.x & (kGroup - 1);
     const int g = threadIdx.x / kGroup;
-    const int gshift = (threadIdx.x & 63) & ~(kGroup - 1);
     int n = counts[b];
     if (n > region) n = region;
     int64_t qo = 0, qlen = n_one;
@@ -426,24 +402,10 @@ __global__ __launch_bounds__(kBlock) void ts_tol_kth_fixup_kernel(
                 pn = half;
             }
         }
-        int kth = TVZ_KTH_NEVER;
-        int running = 0;
-        for (int64_t base = 0; base < qlen && kth == TVZ_KTH_NEVER; base += kGroup) {
-            const int64_t i = base + gl;
-            bool hit = false;
-            if (i < qlen) {
-                const double x = qv[i];
-                hit = x == x && tol_row_has(rk, row.len, p0, x, tol);
-            }
-            const uint32_t m16 = (uint32_t)(__ballot(hit) >> gshift) & 0xffffu;
-            const int c = __popc(m16);
-            if (running + c >= min_match) {
-                uint32_t mm = m16;
-                for (int need = min_match - running; need > 1; --need) mm &= mm - 1;
-                kth = (int)(base + (__ffs(mm) - 1));
-            }
-            running += c;
-        }
+        const int kth = kth_walk(qlen, min_match, [&](int64_t i) {
+            const double x = qv[i];
+            return x == x && tol_row_has(rk, row.len, p0, x, tol);
+        });
         if (gl == 0) h[2] = kth;
     }
 }
@@ -509,34 +471,85 @@ __device__ __forceinline__ unsigned long long tol_topk_compact(unsigned long lon
     return kept[k - 1];
 }
 
+// What a wave knows of its list (wave-uniform) and where the list lives.
+struct TolTopkWave {
+    unsigned long long *kept, *stage;      // 64 LDS words each, the wave's own
+    unsigned long long thr;                // the list's k-th word: words at or above it cannot enter
+    int n_stage, n_hits;                   // words in the stage; hits offered so far
+};
+
+// the lanes of ballot `cb` append their word to the stage (the caller has made sure they fit)
+__device__ __forceinline__ void tol_topk_place(TolTopkWave &w, bool cand, unsigned long long cb, unsigned long long word) {
+    if (cand) w.stage[w.n_stage + (int)lanes_below(cb)] = word;
+    w.n_stage += __popcll(cb);
+}
+
+// the stage into the list
+__device__ __forceinline__ void tol_topk_settle(TolTopkWave &w, int k, int lane) {
+    __builtin_amdgcn_wave_barrier();
+    w.thr = tol_topk_compact(w.kept, w.stage, w.n_stage, k, lane);
+    w.n_stage = 0;
+}
+__device__ __forceinline__ void tol_topk_flush(TolTopkWave &w, int k, int lane) {
+    if (w.n_stage != 0) tol_topk_settle(w, k, lane);
+}
+
 // One wave takes up to 64 more words (one per lane, kTolPad where there is none) towards its list: those below the
-// list's k-th word `thr` are appended to the stage, which is compacted only when they would not fit - a sorted list
+// list's k-th word are appended to the stage, which is compacted only when they would not fit - a sorted list
 // from another block rarely has more than a few words below a live threshold, so most lists cost their load and a
 // ballot.  tol_topk_flush compacts what is left.
-__device__ __forceinline__ void tol_topk_take(unsigned long long *kept, unsigned long long *stage, int &n_stage,
-                                              unsigned long long w, unsigned long long &thr, int k, int lane) {
-    bool cand = w < thr;
+__device__ __forceinline__ void tol_topk_take(TolTopkWave &w, unsigned long long word, int k, int lane) {
+    bool cand = word < w.thr;
     unsigned long long cb = __ballot(cand);
     if (cb == 0ull) return;
-    if (n_stage + __popcll(cb) > 64) {
-        __builtin_amdgcn_wave_barrier();
-        thr = tol_topk_compact(kept, stage, n_stage, k, lane);
-        n_stage = 0;
-        cand = w < thr;
+    if (w.n_stage + __popcll(cb) > 64) {
+        tol_topk_settle(w, k, lane);
+        cand = word < w.thr;
         cb = __ballot(cand);
         if (cb == 0ull) return;
     }
-    const int before = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(cb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cb, 0u));
-    if (cand) stage[n_stage + before] = w;
-    n_stage += __popcll(cb);
+    tol_topk_place(w, cand, cb, word);
 }
 
-__device__ __forceinline__ void tol_topk_flush(unsigned long long *kept, unsigned long long *stage, int &n_stage,
-                                               unsigned long long &thr, int k, int lane) {
-    if (n_stage == 0) return;
-    __builtin_amdgcn_wave_barrier();
-    thr = tol_topk_compact(kept, stage, n_stage, k, lane);
-    n_stage = 0;
+// The sweeps' step: the leads of the wave's groups (`lead`) offer the word of their row's hit.  At most one word per
+// group and step, so the stage is compacted as soon as the next step might not fit.
+__device__ __forceinline__ void tol_topk_offer(TolTopkWave &w, bool lead, unsigned long long word, int k, int lane) {
+    w.n_hits += __popcll(__ballot(lead));
+    const bool cand = lead && word < w.thr;
+    const unsigned long long cb = __ballot(cand);
+    if (cb == 0ull) return;
+    tol_topk_place(w, cand, cb, word);
+    if (w.n_stage > 64 - 64 / kGroup) tol_topk_settle(w, k, lane);
+}
+
+// A sweep block's side: the lists of its waves and its hit count, in static LDS of the kernel (kTolTopkStaticLds).
+__shared__ unsigned long long s_topk_kept[kTolTopkWaves * 64], s_topk_stg[kTolTopkWaves * 64];
+__shared__ int32_t s_topk_nhits;
+// before a block barrier: the block's lists, empty, and this wave's view of its own
+__device__ __forceinline__ TolTopkWave tol_topk_open(int wv, int lane) {
+    s_topk_kept[wv * 64 + lane] = kTolPad;
+    if (threadIdx.x == 0) s_topk_nhits = 0;
+    return TolTopkWave{s_topk_kept + wv * 64, s_topk_stg + wv * 64, kTolPad, 0, 0};
+}
+struct TolTopkOut {
+    unsigned long long *list;              // the block's k words of part[q][..][k]
+    int32_t *total;                        // the query's hit total
+};
+// Behind the row loop, the whole block: every wave settles its stage; behind the one barrier wave 0 takes the other
+// waves' lists into its own and writes the block's k words, and the block's hits go to the total in one atomic.
+// `out` is a callable that returns the TolTopkOut, called where it is needed (as hit_emit's `dest`).
+template <class OUT>
+__device__ __forceinline__ void tol_topk_finish(TolTopkWave &w, int k, int wv, int lane, OUT out) {
+    tol_topk_flush(w, k, lane);
+    if (lane == 0 && w.n_hits) atomicAdd(&s_topk_nhits, w.n_hits);   // LDS
+    __syncthreads();
+    if (wv == 0) {
+#pragma unroll 1
+        for (int j = 1; j < kTolTopkWaves; ++j) tol_topk_take(w, s_topk_kept[j * 64 + lane], k, lane);
+        tol_topk_flush(w, k, lane);
+        if (lane < k) out().list[lane] = w.kept[lane];
+    }
+    if (threadIdx.x == 0 && s_topk_nhits) atomicAdd(out().total, s_topk_nhits);
 }
 
 // grid = (row blocks, Q), the sorted query always in LDS (lds_keys >= every query's length, <= kTolTopkMaxLen).
@@ -551,26 +564,17 @@ __global__ __launch_bounds__(kTolBlock) void ts_tol_topk_kernel(
     unsigned long long *__restrict__ part, int32_t n_lists, int32_t list0, int32_t *__restrict__ totals) {
     static_assert(MODE == kModeM2 || MODE == kModeTop5, "kth is known inside the sweep for min_match 1..5");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    __shared__ unsigned long long s_kept[kTolTopkWaves * 64], s_stg[kTolTopkWaves * 64];
-    __shared__ int32_t s_nhits;
     const int q = blockIdx.y;
     const int bx = blockIdx.x;
     const int64_t at = q_offsets[q] - q_offsets[0];
     const int32_t m = qm[q];
     if (m < 0 || m > lds_keys) return;       // refused by the preparation: ts_tol_topk_reduce_kernel flags it
-    double *lv = reinterpret_cast<double *>(smem);
-    int32_t *lp = reinterpret_cast<int32_t *>(smem + (size_t)((lds_keys + 1) & ~1) * 8);
-    for (int e = threadIdx.x; e < m; e += kTolBlock) {
-        lv[e] = sv[at + e];
-        lp[e] = sp[at + e];
-    }
-    const double *s = lv;
-    const int32_t *pos = lp;
+    const TolQuery lq = tol_query_to_lds(smem, lds_keys, sv, sp, at, m);
+    const double *s = lq.s;
+    const int32_t *pos = lq.pos;
     const int lane = threadIdx.x & 63;
     const int wv = threadIdx.x >> 6;
-    unsigned long long *kept = s_kept + wv * 64, *stage = s_stg + wv * 64;
-    kept[lane] = kTolPad;
-    if (threadIdx.x == 0) s_nhits = 0;
+    TolTopkWave tw = tol_topk_open(wv, lane);
     __syncthreads();
 
     const int gl = threadIdx.x & (kGroup - 1);
@@ -581,8 +585,6 @@ __global__ __launch_bounds__(kTolBlock) void ts_tol_topk_kernel(
     int64_t r_wave = (int64_t)bx * kTolGroups + wv * (64 / kGroup);    // the wave's first group: its longest loop
     const int64_t last_row = n_rows - 1;
     Row row = load_row(rows + (r < n_rows ? r : last_row));
-    unsigned long long thr = kTolPad;        // the list's k-th word: hits at or above it cannot enter
-    int n_stage = 0, n_hits = 0;             // wave-uniform
     while (r_wave < n_rows) {                // wave-uniform: the wave compacts as one
         const int64_t rn = r + stride;
         const Row nrow = load_row(rows + (rn < n_rows ? rn : last_row));
@@ -592,39 +594,16 @@ __global__ __launch_bounds__(kTolBlock) void ts_tol_topk_kernel(
         const bool hit = live && (int64_t)cnt >= (int64_t)min_match && row.vid != excl;
         if (__ballot(hit) != 0ull) {
             tol_row_reduce<MODE>(m1, m2, tk);
-            uint32_t kth;
-            if constexpr (MODE == kModeM2) kth = min_match == 1 ? m1 : m2;
-            else kth = tk[min_match - 1];
-            const unsigned long long word = ix_tk_pack((int32_t)kth, row.vid, cnt);
-            const bool lead = hit && gl == 0;
-            n_hits += __popcll(__ballot(lead));
-            const bool cand = lead && word < thr;
-            const unsigned long long cb = __ballot(cand);
-            if (cb != 0ull) {
-                const int before = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(cb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cb, 0u));
-                if (cand) stage[n_stage + before] = word;
-                n_stage += __popcll(cb);
-                if (n_stage > 64 - 64 / kGroup) {                    // the next step may bring one per group
-                    __builtin_amdgcn_wave_barrier();
-                    thr = tol_topk_compact(kept, stage, n_stage, k, lane);
-                    n_stage = 0;
-                }
-            }
+            const unsigned long long word = ix_tk_pack(kth_of<MODE>(min_match, m1, m2, tk, r), row.vid, cnt);
+            tol_topk_offer(tw, hit && gl == 0, word, k, lane);
         }
         row = nrow;
         r = rn;
         r_wave += stride;
     }
-    tol_topk_flush(kept, stage, n_stage, thr, k, lane);
-    if (lane == 0 && n_hits) atomicAdd(&s_nhits, n_hits);            // LDS
-    __syncthreads();
-    if (wv == 0) {                                                   // wave 0 takes the other waves' lists into its own
-#pragma unroll 1
-        for (int j = 1; j < kTolTopkWaves; ++j) tol_topk_take(kept, stage, n_stage, s_kept[j * 64 + lane], thr, k, lane);
-        tol_topk_flush(kept, stage, n_stage, thr, k, lane);
-        if (lane < k) part[((int64_t)q * n_lists + list0 + bx) * k + lane] = kept[lane];
-    }
-    if (threadIdx.x == 0 && s_nhits) atomicAdd(&totals[q], s_nhits);
+    tol_topk_finish(tw, k, wv, lane, [&] {
+        return TolTopkOut{part + ((int64_t)q * n_lists + list0 + bx) * k, &totals[q]};
+    });
 }
 
 // One block per query: the k smallest words of its n_lists sorted partial lists -> d_out[q] = int32[k+1][3]: k rows
@@ -642,12 +621,10 @@ __global__ __launch_bounds__(kTolReduceBlock) void ts_tol_topk_reduce_kernel(
     int32_t *out = d_out + (int64_t)q * (k + 1) * 3;
     const int32_t m = qm[q];
     const bool refused = m < 0 || m > lds_keys;
-    unsigned long long *kept = s_kept + wv * 64, *stage = s_stg + wv * 64;
-    kept[lane] = kTolPad;
+    TolTopkWave tw{s_kept + wv * 64, s_stg + wv * 64, kTolPad, 0, 0};
+    tw.kept[lane] = kTolPad;
     if (!refused) {
         const unsigned long long *lists = part + (int64_t)q * n_lists * k;
-        unsigned long long thr = kTolPad;
-        int n_stage = 0;
         for (int l0 = wv; l0 < n_lists; l0 += kTolReduceLd * kTolReduceWaves) {   // wave-uniform
             unsigned long long w[kTolReduceLd];
 #pragma unroll
@@ -656,18 +633,18 @@ __global__ __launch_bounds__(kTolReduceBlock) void ts_tol_topk_reduce_kernel(
                 w[j] = (l < n_lists && lane < k) ? lists[(int64_t)l * k + lane] : kTolPad;
             }
 #pragma unroll
-            for (int j = 0; j < kTolReduceLd; ++j) tol_topk_take(kept, stage, n_stage, w[j], thr, k, lane);
+            for (int j = 0; j < kTolReduceLd; ++j) tol_topk_take(tw, w[j], k, lane);
         }
-        tol_topk_flush(kept, stage, n_stage, thr, k, lane);
+        tol_topk_flush(tw, k, lane);
         __syncthreads();
         if (wv == 0) {
 #pragma unroll 1
-            for (int j = 1; j < kTolReduceWaves; ++j) tol_topk_take(kept, stage, n_stage, s_kept[j * 64 + lane], thr, k, lane);
-            tol_topk_flush(kept, stage, n_stage, thr, k, lane);
+            for (int j = 1; j < kTolReduceWaves; ++j) tol_topk_take(tw, s_kept[j * 64 + lane], k, lane);
+            tol_topk_flush(tw, k, lane);
         }
     }
     if (wv != 0) return;
-    const unsigned long long w = kept[lane];                             // all padding for a refused query
+    const unsigned long long w = tw.kept[lane];                          // all padding for a refused query
     if (lane < k) {
         const bool pad = w == kTolPad;
         out[lane * 3 + 0] = pad ? -1 : (int32_t)((w >> 12) & 0xffffffffu);
