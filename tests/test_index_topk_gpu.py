@@ -120,6 +120,15 @@ def test_fused_topk_with_huge_ties_and_late_first_hits(dc):
         for k, cap in ((16, C), (1, C), (64, C), (16, 300), (8, 512)):
             _check_topk(dc, exp, queries, mm, k, cap)
             _check_topk(dc, exp_x, queries, mm, k, cap, excl=excl)
+    # A second batch on the same handle: queries of more than 512 timestamps - later chunks of query positions,
+    # walked from the lists in both passes - through the fused top-k, in the pair and the one-query form.  (Its own
+    # batch: the one above stays within the one-wave lookup's 512 positions and is compared with it.)
+    long_queries = [rng.choice(grid, size=n, replace=False) for n in (513, 600, 1400)]
+    long_queries.append(rng.choice(grid, size=37, replace=False))
+    for mm in (1, 2, 4):
+        exp = _expected_rows(rows, long_queries, mm)
+        for k, cap in ((16, C), (64, C), (8, 512)):
+            _check_topk(dc, exp, long_queries, mm, k, cap)
 
 
 def test_fused_topk_over_several_sub_indexes_and_a_delta_table(dc):

@@ -680,18 +680,50 @@ __device__ unsigned long long g_ix_stamps[16];
 constexpr int kIxTkCap = 128;              // candidate entries (8 B each) held between compactions
 constexpr int kIxTkMaxK = 64;              // k up to this (kIxTkCap >= 2 k)
 constexpr int kIxTkBins = 64;              // kth histogram: bins 0..62 exact, bin 63 = "63 or later"
-constexpr size_t kIxTkBytes = (size_t)kIxTkCap * 8 + (size_t)kIxTkBins * 4 + 8;
 
-// dynamic LDS: [bm1][bm2][tcnt][ttop][cache][lst u64 x waves x 64][lbits][top-k: entries, histogram,
-// fill][e_cur x L][elist u16][rank u16][e_len u16 x L x nsb] (nsb = sub-indexes this block walks,
-// rounded up to even): 32.5 KiB (+ 1.3 KiB with the fused top-k) + 20 B per query position at 7..8
-// sub-indexes - FOUR blocks (32 waves) per CU for queries of up to ~300 timestamps.
-inline int ix_nsb_padded(int spb) { return (spb + 1) & ~1; }
+// dynamic LDS of ix_lookup_body: 32.5 KiB (+ 1.3 KiB with the fused top-k) + 20 B per query position at 7..8
+// sub-indexes - FOUR blocks (32 waves) per CU for queries of up to ~300 timestamps.  L = positions of all of the
+// block's queries, nsb = sub-indexes the block walks, rounded up to even.
+struct IxLds {
+    uint32_t *bm1, *bm2;               // row bitmaps: seen once, seen twice
+    uint32_t *tcnt;                    // candidate slots: count ...
+    unsigned long long *ttop;          // ... and smallest positions (kModeM2: two arrays of kIxSlots words in the same 8 B per slot)
+    uint32_t *cache;                   // cached postings: row | position << kSubLog2
+    uint2 *lst;                        // per wave: non-empty list j = {first posting - local start, position}
+    uint32_t *lbits;                   // per wave: bit t = a list starts at local posting t
+    unsigned long long *tkb;           // TOPK: kept hits
+    uint32_t *kh;                      // TOPK: hits per kth bin, all sub-indexes so far
+    uint32_t *tk_n;                    // TOPK: entries in tkb (+ one pad word)
+    uint32_t *e_cur;                   // [L] first posting of position i in the CURRENT sub-index
+    uint16_t *elist;                   // row (in the sub-index) of slot k
+    uint16_t *rank;                    // candidates before bitmap word j
+    uint16_t *e_len;                   // [L][nsb] postings of position i per sub-index
+    // every array in carve order: f(field, elements).  The kernel's carve and the host's size both come from here.
+    template <typename F>
+    __host__ __device__ __forceinline__ void each(size_t L, int nsb, bool topk, F f) {
+        f(bm1, kIxWords); f(bm2, kIxWords); f(tcnt, kIxSlots); f(ttop, kIxSlots); f(cache, kIxCache);
+        f(lst, kIxWaves * 64); f(lbits, kIxWaves * kIxLW);
+        if (topk) { f(tkb, kIxTkCap); f(kh, kIxTkBins); f(tk_n, 2); }
+        f(e_cur, L + 1); f(elist, kIxSlots); f(rank, kIxWords); f(e_len, L * (size_t)nsb);
+    }
+};
+// a struct's arrays cut from `p` one after the other (device), or their bytes summed up (host)
+template <typename LDS, typename... A>
+__device__ __forceinline__ LDS lds_carve(unsigned char *p, A... a) {
+    LDS s;
+    s.each(a..., [&](auto *&f, size_t n) { f = reinterpret_cast<decltype(+f)>(p); p += n * sizeof(*f); });
+    return s;
+}
+template <typename LDS, typename... A>
+inline size_t lds_carve_bytes(A... a) {
+    LDS s;
+    size_t bytes = 0;
+    s.each(a..., [&](auto *&f, size_t n) { bytes += n * sizeof(*f); });
+    return bytes;
+}
+__host__ __device__ inline int ix_nsb_padded(int spb) { return (spb + 1) & ~1; }
 inline size_t ix_lds_bytes(int max_len, int spb, bool topk = false) {
-    const size_t L = (size_t)(max_len > 0 ? max_len : 1);
-    return (size_t)2 * kIxWords * 4 + (size_t)kIxSlots * 14 + (size_t)kIxCache * 4 + (size_t)kIxWaves * 64 * 8 +
-           (size_t)kIxWaves * kIxLW * 4 + (topk ? kIxTkBytes : 0) + (L + 1) * 4 + (size_t)kIxWords * 2 +
-           L * 2 * (size_t)ix_nsb_padded(spb) + 16;
+    return lds_carve_bytes<IxLds>((size_t)(max_len > 0 ? max_len : 1), ix_nsb_padded(spb), topk) + 16;
 }
 
 // MODE (how a candidate's slot accounts for its postings):
@@ -743,127 +775,318 @@ __device__ __forceinline__ unsigned long long ix_tk_pack(int32_t kth, int32_t vi
     return ((unsigned long long)(uint32_t)kth << 44) | ((unsigned long long)(uint32_t)vid << 12) | cnt;
 }
 
-// NQ (TOPK only): queries per block.  With NQ = 2 block b takes queries 2 b and 2 b + 1: BOTH are probed in the one
-// probe phase at the start (a query of ~200 timestamps occupies 200 of the block's 512 threads there, and the phase is
-// two dependent round trips - keys, directory entries - during which the block does nothing else: a third of a
-// block's time on a 1/8 shard), then walked one after the other.  `q` = the block's first query, `Q` = queries in the batch.
-template <bool HOSTOUT, int MODE, bool TOPK, int NQ = 1>
-__device__ __forceinline__ void ix_lookup_body(
-    const unsigned char *__restrict__ dir, int dir_bits, int ks, const uint16_t *__restrict__ post,
-    const int32_t *__restrict__ ivid, int64_t n_indexed, int32_t n_sub, int32_t spb,
-    const double *__restrict__ queries, const int64_t *__restrict__ q_offsets, int32_t max_len,
-    int32_t min_match, const int32_t *__restrict__ exclude_ids, int32_t exclude_one, int32_t cap,
-    int32_t *__restrict__ hits, int32_t *__restrict__ hits_n, int32_t ns, const QByVal *qv, const int q_first,
-    const int group, const int n_groups, const int32_t tk_k = 0, const int32_t Q = 0) {
-    static_assert(!(TOPK && (HOSTOUT || MODE == kModeCount)), "the fused top-k needs kth in the block and a device list");
-    static_assert(NQ == 1 || (NQ == 2 && TOPK), "two queries per block: the top-k form only");
-    constexpr bool TOP5 = MODE == kModeTop5;
-    const int dir_log2 = dir_bits & 0xff;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    uint32_t *bm1 = reinterpret_cast<uint32_t *>(smem);
-    uint32_t *bm2 = bm1 + kIxWords;
-    uint32_t *tcnt = bm2 + kIxWords;
-    unsigned long long *ttop = reinterpret_cast<unsigned long long *>(tcnt + kIxSlots);
-    uint32_t *m1 = reinterpret_cast<uint32_t *>(ttop), *m2 = m1 + kIxSlots;   // kModeM2: the same 8 B per slot
-    uint32_t *pcache_all = reinterpret_cast<uint32_t *>(ttop + kIxSlots);  // cached postings: row | position << kSubLog2
-    const int L = NQ * (max_len > 0 ? max_len : 1);        // positions of all of the block's queries
-    uint2 *lst_all = reinterpret_cast<uint2 *>(pcache_all + kIxCache);  // per wave: non-empty list j = {first posting - local start, position}
-    uint32_t *lbits_all = reinterpret_cast<uint32_t *>(lst_all + kIxWaves * 64);   // per wave: bit t = a list starts at local posting t
-    unsigned long long *tkb = reinterpret_cast<unsigned long long *>(lbits_all + kIxWaves * kIxLW);   // TOPK: kept hits
-    uint32_t *kh = reinterpret_cast<uint32_t *>(tkb + kIxTkCap);        // TOPK: hits per kth bin, all sub-indexes so far
-    uint32_t *tk_n = kh + kIxTkBins;                                    // TOPK: entries in tkb (+ one pad word)
-    uint32_t *e_cur_all = TOPK ? tk_n + 2 : reinterpret_cast<uint32_t *>(tkb);   // [L] first posting of position i in the CURRENT sub-index
-    uint16_t *elist = reinterpret_cast<uint16_t *>(e_cur_all + L + 1);  // row (in the sub-index) of slot k
-    uint16_t *rank = elist + kIxSlots;                                  // candidates before bitmap word j
-    uint16_t *e_len_all = rank + kIxWords;                              // [L][nsb] postings of position i per sub-index
-    __shared__ uint32_t s_wb[kIxWaves], s_wc[kIxWaves];
-    __shared__ uint32_t s_bcast;
-    __shared__ uint32_t s_tk[TOPK ? kIxWaves : 1];
-    __shared__ unsigned long long s_tkT;
+// ---- steps shared by ix_lookup_body, ts_match_wq_topk_kernel (tvz_index_wave_kernels.h) and ts_tol_index_kernel
+// (tvz_tol_index_kernels.h).  The helpers take the addresses they work on: the LDS layouts stay their callers'.
 
-    const int sub_lo = group * spb;
-    const int sub_hi = sub_lo + spb < n_sub ? sub_lo + spb : n_sub;
-    const int nsb = (spb + 1) & ~1;
-    const bool alone = n_groups == 1;                  // this block owns the query's hit list
-    const bool byval = !TOPK && q_offsets == nullptr;      // (the query travels in the kernel arguments)
-    int64_t qo_[NQ];
-    int n_[NQ];
-    bool skip_[NQ];                                        // refused (too long), or past the end of the batch
+// The directory slot of key k, kIxNoSlot if it has none: linear probing that wraps inside the key's slice, up to
+// kIxMaxProbe steps.  HEAD = what one step loads of an entry - int4: key, base and total in ONE trip; int2: the key
+// alone; the entry's is left in `h`.  (Not unrolled: a chain is one or two steps long.)
+constexpr uint32_t kIxNoSlot = 0xffffffffu;
+template <typename HEAD>
+__device__ __forceinline__ uint32_t ix_probe(const unsigned char *dir, int es, int dir_log2, uint32_t smask, int64_t k,
+                                             HEAD &h) {
+    uint32_t s = ix_slot(k, dir_log2);
+#pragma unroll 1
+    for (int probes = 0; probes < kIxMaxProbe; ++probes) {
+        const HEAD cur = *reinterpret_cast<const HEAD *>(dir + (size_t)s * es);
+        const int64_t ek = (int64_t)(((uint64_t)(uint32_t)cur.y << 32) | (uint32_t)cur.x);
+        if (ek == k) { h = cur; return s; }
+        if (ek == kEmpty) break;
+        s = (s & ~smask) | ((s + 1) & smask);
+    }
+    return kIxNoSlot;
+}
+// pass A's bookkeeping for one posting of row r: seen once in bm1, seen again in bm2
+__device__ __forceinline__ void ix_touch(uint32_t *bm1, uint32_t *bm2, int32_t min_match, uint32_t r) {
+    const uint32_t bit = 1u << (r & 31u);
+    const uint32_t old = atomicOr(&bm1[r >> 5], bit);
+    if (min_match >= 2 && (old & bit)) atomicOr(&bm2[r >> 5], bit);
+}
+// rank: thread-owned bitmap words cw[] that have `run` candidates before them -> candidates before each word
+template <int WPT>
+__device__ __forceinline__ void ix_rank_store(uint16_t *rank, const uint32_t (&cw)[WPT], uint32_t run) {
 #pragma unroll
-    for (int j = 0; j < NQ; ++j) {
-        const int q = q_first + j;
-        skip_[j] = NQ > 1 && q >= Q;
-        qo_[j] = 0;
-        n_[j] = 0;
-        if (skip_[j]) continue;
-        qo_[j] = byval ? 0 : q_offsets[q];
-        const int64_t n64 = byval ? qv->n : q_offsets[q + 1] - qo_[j];
-        if (n64 > max_len) {   // max_query_len was not an upper bound (the LDS arrays are sized from it)
-            if (TOPK) {        // what the top-k kernels make of a refused query: padding + the poisoned total
-                int32_t *o = hits + (int64_t)q * (tk_k + 1) * 3;
-                for (int i = threadIdx.x; i <= tk_k; i += kIxBlock) {
-                    o[i * 3 + 0] = -1;
-                    o[i * 3 + 1] = i == tk_k ? INT32_MIN : 0;
-                    o[i * 3 + 2] = TVZ_KTH_NEVER;
-                }
-            } else if (HOSTOUT) { for (int s = sub_lo + threadIdx.x; s < sub_hi; s += kIxBlock) hits_n[s] = INT32_MIN; }
-            else if (threadIdx.x == 0) hits_n[(size_t)q * ns] = INT32_MIN;
-            skip_[j] = true;
-            if (NQ == 1) return;
-            continue;
+    for (int w = 0; w < WPT; ++w) { rank[w] = (uint16_t)run; run += __popc(cw[w]); }
+}
+// the rows of a part's slots (slot = rank of the candidate - lo), written by the owners of the bitmap words (word0 =
+// this thread's first, rk0 = candidates before it): no compaction, no atomics
+template <int SLOTS, int WPT>
+__device__ __forceinline__ void ix_slot_rows(uint16_t *elist, const uint32_t (&cw)[WPT], uint32_t word0, uint32_t rk0,
+                                             uint32_t lo) {
+    uint32_t run = rk0;
+#pragma unroll
+    for (int ww = 0; ww < WPT; ++ww) {
+        const uint32_t wi = word0 + ww;
+        for (uint32_t rest = cw[ww], i = 0; rest; rest &= rest - 1, ++i) {
+            const uint32_t idx = run + i - lo;
+            if (idx < (uint32_t)SLOTS) elist[idx] = (uint16_t)(wi * 32u + ((uint32_t)__ffs(rest) - 1u));
         }
-        n_[j] = (int)n64;
+        run += __popc(cw[ww]);
     }
-    const int n_all = NQ == 1 ? n_[0] : n_[0] + n_[NQ - 1];
-#ifdef TVZ_IX_STAMP
-    unsigned long long st_acc[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long st_last = __builtin_amdgcn_s_memtime();
-#endif
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // in an SGPR: scalar loop bounds
-    uint32_t *pcache = pcache_all + wave * kIxPW;
-    uint2 *lst = lst_all + wave * 64;
-    uint32_t *lbits = lbits_all + wave * kIxLW;
-    auto reset_slot = [&](uint32_t k) {
+}
+// the video id of slot k's row (row0 = the sub-index's first row), -1 if it is no hit whatever its count: past the part's
+// slots or the indexed rows, replaced since the build (ivid = -1), the query's own video.  The load is unconditional.
+__device__ __forceinline__ int32_t ix_slot_vid(const int32_t *__restrict__ ivid, const uint16_t *elist, uint32_t k,
+                                               uint32_t n_list, int64_t row0, int64_t n_indexed, int32_t excl) {
+    const int64_t row = row0 + (k < n_list ? elist[k] : 0u);
+    const int32_t vid = ivid[k < n_list && row < n_indexed ? row : row0];
+    return k >= n_list || row >= n_indexed || vid == excl ? -1 : vid;
+}
+// A part's candidate slots: the count, and in the 8 bytes of `ttop` the smallest query positions - five of 12 bits in
+// one CAS word (kModeTop5), or the two smallest in two atomicMin words (kModeM2): two plain LDS atomics per candidate
+// posting.  Those two words are a slot's own 8 bytes (PAIRED: the wave kernel) or two arrays of SLOTS words (the block
+// kernel).  kModeCount keeps the count alone.
+template <int MODE, int SLOTS, bool PAIRED>
+struct IxSlotTable {
+    uint32_t *tcnt;
+    unsigned long long *ttop;
+    __device__ __forceinline__ uint32_t *min1(uint32_t k) const { return reinterpret_cast<uint32_t *>(ttop) + (PAIRED ? 2 * k : k); }
+    __device__ __forceinline__ uint32_t *min2(uint32_t k) const { return reinterpret_cast<uint32_t *>(ttop) + (PAIRED ? 2 * k + 1 : SLOTS + k); }
+    __device__ __forceinline__ void reset(uint32_t k) const {
         tcnt[k] = 0;
-        if (TOP5) ttop[k] = kTopNone; else if (MODE == kModeM2) { m1[k] = 0xffffffffu; m2[k] = 0xffffffffu; }
-    };
-    for (int i = threadIdx.x; i < kIxWords; i += kIxBlock) { bm1[i] = 0; bm2[i] = 0; }
-    for (int i = threadIdx.x; i < kIxWaves * kIxLW; i += kIxBlock) lbits_all[i] = 0;
-    for (int i = threadIdx.x; i < kIxSlots; i += kIxBlock) reset_slot((uint32_t)i);
-    if (TOPK) {
-        for (int i = threadIdx.x; i < kIxTkBins + 2; i += kIxBlock) kh[i] = 0;      // histogram, fill, pad
+        if constexpr (MODE == kModeTop5) ttop[k] = kTopNone;
+        else if constexpr (MODE == kModeM2 && PAIRED) ttop[k] = ~0ull;
+        else if constexpr (MODE == kModeM2) { *min1(k) = 0xffffffffu; *min2(k) = 0xffffffffu; }
     }
-    unsigned long long tk_cut = ~0ull;                     // TOPK: hits >= this cannot make the top-k (block-uniform)
-    uint32_t tk_bmax = 0xffffffffu;                        // TOPK: hits with kth beyond this neither (block-uniform)
+    __device__ __forceinline__ void account(uint32_t idx, uint32_t pos) const {   // one posting of slot idx's row, at query position pos
+        atomicAdd(&tcnt[idx], 1u);
+        if constexpr (MODE == kModeTop5) {
+            unsigned long long seen = ttop[idx];
+            while (true) {
+                if (((uint32_t)(seen >> (12 * (kTop - 1))) & 0xfffu) <= pos) break;   // not among the 5 smallest
+                const unsigned long long old = atomicCAS(&ttop[idx], seen, top5_insert(seen, pos));
+                if (old == seen) break;
+                seen = old;
+            }
+        } else if constexpr (MODE == kModeM2) {
+            const uint32_t o = atomicMin(min1(idx), pos);                // positions of one row are distinct
+            atomicMin(min2(idx), o > pos ? o : pos);                     // larger of two hits >= 2nd smallest
+        }
+    }
+    __device__ __forceinline__ int32_t kth_of(uint32_t k, int32_t min_match) const {   // (kModeTop5, kModeM2)
+        if constexpr (MODE == kModeTop5) return (int32_t)((uint32_t)(ttop[k] >> (12 * (min_match - 1))) & 0xfffu);
+        else return (int32_t)(min_match == 1 ? *min1(k) : *min2(k));
+    }
+};
 
-    // ---- directory: ONE probe per query position; the counts of this block's sub-indexes to LDS ----
+// ---- the fused top-k.  Who runs a step - the block of ix_lookup_body or the one wave of ts_match_wq_topk_kernel: the
+// threads that take part, the fence between two steps, and how a sum or the k-th best entry gets to everybody.
+struct IxBlockTeam {
+    static constexpr int kThreads = kIxBlock;
+    uint32_t *s_sum;                   // [kIxWaves]
+    unsigned long long *s_kth;
+    int wave, lane;
+    __device__ __forceinline__ void fence() const { __syncthreads(); }
+    __device__ __forceinline__ void sums(uint32_t incl, uint32_t &before, uint32_t &all) const {   // of the waves' inclusive scans
+        if (lane == 63) s_sum[wave] = incl;
+        __syncthreads();
+        waves_sum<kIxWaves>(s_sum, wave, before, all);
+    }
+    __device__ __forceinline__ void kth_clear() {}
+    __device__ __forceinline__ void kth_post(unsigned long long e) { *s_kth = e; }        // (behind it: a fence)
+    __device__ __forceinline__ unsigned long long kth_get() const { return *s_kth; }
+};
+struct IxWaveTeam {
+    static constexpr int kThreads = 64;
+    int lane;
+    unsigned long long kth;
+    __device__ __forceinline__ void fence() const { wave_lds_fence(); }
+    __device__ __forceinline__ void sums(uint32_t incl, uint32_t &before, uint32_t &all) const {
+        before = 0;
+        all = wave_total(incl);
+    }
+    __device__ __forceinline__ void kth_clear() { kth = ~0ull; }
+    __device__ __forceinline__ void kth_post(unsigned long long e) { kth = e; }
+    __device__ __forceinline__ unsigned long long kth_get() const {    // held by exactly one lane; min over the wave (the others hold ~0)
+        unsigned long long t = kth;
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) {
+            const unsigned long long other = ((unsigned long long)(uint32_t)__shfl_xor((int)(uint32_t)(t >> 32), d) << 32) |
+                                             (uint32_t)__shfl_xor((int)(uint32_t)t, d);
+            t = other < t ? other : t;
+        }
+        return t;
+    }
+};
+
+// rows have .. k of a query's k + 1: padding (-1, 0, NEVER) and, as row k, the totals row (-1, total, NEVER).  A refused
+// query is k rows of padding + the poisoned total INT32_MIN, as the top-k kernels make it.
+template <int THREADS>
+__device__ __forceinline__ void ix_tk_pad(int32_t *o, uint32_t have, int32_t tk_k, int32_t total) {
+    for (uint32_t i = have + threadIdx.x; i <= (uint32_t)tk_k; i += THREADS) {
+        o[i * 3 + 0] = -1;
+        o[i * 3 + 1] = i == (uint32_t)tk_k ? total : 0;
+        o[i * 3 + 2] = TVZ_KTH_NEVER;
+    }
+}
+// A hit of the part as its sortable word, ~0 if it cannot make the top-k any more.  Only hits with kth <= tk_bmax, the
+// threshold bin of the parts so far (no bound before k hits below position 63 exist), are looked at any further: after
+// the first sub-index that is a few per cent of the hits.  They bump their kth's bin and count in the high half of
+// `mine`.  The bin "63 or later" is never counted: no threshold is ever read from it, and with ~70 % of a part's hits in
+// it the one LDS address was a serialised atomic per hit.
+__device__ __forceinline__ unsigned long long ix_tk_offer(uint32_t kth, int32_t vid, uint32_t cnt, uint32_t tk_bmax,
+                                                          uint32_t *kh, uint32_t &mine) {
+    if (kth > tk_bmax) return ~0ull;
+    const unsigned long long ek = ix_tk_pack((int32_t)kth, vid, cnt);
+    if (kth < (uint32_t)kIxTkBins - 1u) atomicAdd(&kh[kth], 1u);
+    mine += 1u << 16;
+    return ek;
+}
+// b* = the first kth bin whose prefix reaches k; every wave scans the bins itself (the histogram does not change before
+// the next part's emit: same result in all of them).  Returns the part's keepers at most; lowers cut and tk_bmax to b*.
+__device__ __forceinline__ uint32_t ix_tk_threshold(const uint32_t *kh, int lane, int32_t tk_k, uint32_t n_cand_tk,
+                                                    unsigned long long &cut, uint32_t &tk_bmax) {
+    const uint32_t hincl = wave_scan_incl(lane < kIxTkBins - 1 ? kh[lane] : 0u);
+    const unsigned long long reach = __ballot(hincl >= (uint32_t)tk_k);
+    const int bfirst = __builtin_amdgcn_readfirstlane(reach ? __ffsll((long long)reach) - 1 : kIxTkBins);
+    uint32_t bound = n_cand_tk;
+    if (bfirst < kIxTkBins - 1) {
+        const uint32_t cum = (uint32_t)__builtin_amdgcn_readlane((int)hincl, bfirst);
+        bound = cum < n_cand_tk ? cum : n_cand_tk;
+        const unsigned long long bc = (unsigned long long)(bfirst + 1) << 44;
+        cut = bc < cut ? bc : cut;
+        tk_bmax = (uint32_t)bfirst < tk_bmax ? (uint32_t)bfirst : tk_bmax;
+    }
+    return bound;
+}
+// the rank of kept hit `me` (= e) among the N kept: entries before it in (word, place) order
+__device__ __forceinline__ uint32_t ix_tk_rank(const unsigned long long *tkb, uint32_t N, uint32_t me, unsigned long long e) {
+    uint32_t r = 0;
+    for (uint32_t i = 0; i < N; ++i) {
+        const unsigned long long x = tkb[i];
+        r += (x < e || (x == e && i < me)) ? 1u : 0u;
+    }
+    return r;
+}
+// the N <= kIxTkCap kept hits reduced to their k best by rank counting, which also yields the exact cut-off: the k-th
+// best entry bounds tk_cut, and nothing beyond its kth matters (tk_bmax).  Returns the entries left.
+template <typename TEAM>
+__device__ __forceinline__ uint32_t ix_tk_reduce(TEAM &tm, unsigned long long *tkb, uint32_t *tk_n, uint32_t N, int32_t tk_k,
+                                                 unsigned long long &tk_cut, uint32_t &tk_bmax) {
+    constexpr int EPT = (kIxTkCap + TEAM::kThreads - 1) / TEAM::kThreads;    // entries per thread
+    unsigned long long e[EPT];
+    uint32_t r[EPT];
+#pragma unroll
+    for (int h = 0; h < EPT; ++h) {
+        const uint32_t me = (uint32_t)(h * TEAM::kThreads) + threadIdx.x;
+        e[h] = ~0ull;
+        r[h] = 0;
+        if (me < N) { e[h] = tkb[me]; r[h] = ix_tk_rank(tkb, N, me, e[h]); }
+    }
+    tm.fence();                                            // every read of the old list before the first write of the new
+    tm.kth_clear();
+#pragma unroll
+    for (int h = 0; h < EPT; ++h) {
+        const uint32_t me = (uint32_t)(h * TEAM::kThreads) + threadIdx.x;
+        if (me < N && r[h] < (uint32_t)tk_k) tkb[r[h]] = e[h];
+        if (me < N && r[h] == (uint32_t)tk_k - 1u) tm.kth_post(e[h]);
+    }
+    const uint32_t left = N < (uint32_t)tk_k ? N : (uint32_t)tk_k;
+    if (threadIdx.x == 0) *tk_n = left;
+    tm.fence();
+    if (N >= (uint32_t)tk_k) {
+        const unsigned long long t = tm.kth_get();
+        tk_cut = t < tk_cut ? t : tk_cut;
+        const uint32_t tb = (uint32_t)(tk_cut >> 44);
+        tk_bmax = tb < tk_bmax ? tb : tk_bmax;
+    }
+    return left;
+}
+// Keep the part's hits that can still make the top-k.  word(u), u < NW = this thread's hits as sortable words (~0: none);
+// tk_before = kept hits before the part; n_cand_tk = the part's hits at or below the threshold bin (team-uniform, > 0).
+// The hits below b*'s cut are appended by an LDS atomic if they must fit.  Otherwise - rare: hundreds of hits in the
+// threshold bin (true duplicates share their kth) or none of the first k hits below position 63 - the list is reduced
+// to its k best and the part's keepers are fed in rounds of what fits.
+template <int NW, typename TEAM, typename WORD>
+__device__ __forceinline__ void ix_tk_keep(TEAM &tm, WORD word, const uint32_t *kh, unsigned long long *tkb, uint32_t *tk_n,
+                                           uint32_t tk_before, uint32_t n_cand_tk, int32_t tk_k, int lane,
+                                           unsigned long long &tk_cut, uint32_t &tk_bmax) {
+    unsigned long long cut = tk_cut;
+    const uint32_t bound = ix_tk_threshold(kh, lane, tk_k, n_cand_tk, cut, tk_bmax);
+    if (tk_before + bound <= (uint32_t)kIxTkCap) {
+#pragma unroll
+        for (int u = 0; u < NW; ++u) {
+            const unsigned long long ek = word(u);
+            if (ek < cut) tkb[atomicAdd(tk_n, 1u)] = ek;
+        }
+        return;
+    }
+    uint32_t nb = ix_tk_reduce(tm, tkb, tk_n, tk_before, tk_k, tk_cut, tk_bmax);
+    while (true) {                                         // team-uniform
+        cut = tk_cut < cut ? tk_cut : cut;
+        uint32_t c = 0;
+#pragma unroll 1
+        for (int u = 0; u < NW; ++u) c += word(u) < cut ? 1u : 0u;
+        const uint32_t ci = wave_scan_incl(c);
+        uint32_t before, tot;
+        tm.sums(ci, before, tot);
+        if (tot == 0) break;
+        const uint32_t room = (uint32_t)kIxTkCap - nb;
+        uint32_t off = before + ci - c;
+#pragma unroll 1
+        for (int u = 0; u < NW; ++u) {
+            const unsigned long long ek = word(u);
+            if (ek < cut) {
+                if (off < room) { tkb[nb + off] = ek; word(u) = ~0ull; }
+                ++off;
+            }
+        }
+        const uint32_t placed = tot < room ? tot : room;
+        if (threadIdx.x == 0) *tk_n = nb + placed;
+        tm.fence();
+        nb += placed;
+        if (tot <= room) break;
+        nb = ix_tk_reduce(tm, tkb, tk_n, nb, tk_k, tk_cut, tk_bmax);
+    }
+}
+// the k best of the N kept hits, each written to the row of its rank; padding; the totals row (-1, n, NEVER), n negated
+// when n > cap
+template <int THREADS>
+__device__ __forceinline__ void ix_tk_write(int32_t *o, const unsigned long long *tkb, uint32_t N, int32_t tk_k,
+                                            uint32_t emitted, int32_t cap) {
+#pragma unroll
+    for (int h = 0; h < (kIxTkCap + THREADS - 1) / THREADS; ++h) {
+        const uint32_t me = (uint32_t)(h * THREADS) + threadIdx.x;
+        if (me < N) {
+            const unsigned long long e = tkb[me];
+            const uint32_t r = ix_tk_rank(tkb, N, me, e);
+            if (r < (uint32_t)tk_k) {
+                o[r * 3 + 0] = (int32_t)(uint32_t)(e >> 12);
+                o[r * 3 + 1] = (int32_t)((uint32_t)e & 0xfffu);
+                o[r * 3 + 2] = (int32_t)(e >> 44);
+            }
+        }
+    }
+    ix_tk_pad<THREADS>(o, N < (uint32_t)tk_k ? N : (uint32_t)tk_k, tk_k,
+                       (int64_t)emitted > (int64_t)cap ? -(int32_t)emitted : (int32_t)emitted);
+}
+
+// ---- the phases of ix_lookup_body, in the order it runs them ----
+
+// directory: ONE probe per position of the block's queries (n_all of them, at q_at(i)); the posting counts of the
+// block's sub-indexes [sub_lo, sub_hi) go to e_len[i][nsb], the first posting in sub_lo to e_cur[i]
+template <typename QAT>
+__device__ __forceinline__ void ix_probe_phase(const unsigned char *__restrict__ dir, int dir_bits, int ks, QAT q_at, int n_all,
+                                               int sub_lo, int sub_hi, int nsb, uint16_t *e_len, uint32_t *e_cur) {
+    const int dir_log2 = dir_bits & 0xff;
     const uint32_t smask = dir_bits < 0 ? 0u : (1u << (dir_bits >> 8)) - 1u;   // probes wrap inside the directory slice
     const int es = 16 + 2 * ks;
     for (int i = threadIdx.x; i < n_all; i += kIxBlock) {
         uint32_t base = 0, total = 0;
-        const unsigned char *ent = nullptr;
+        const unsigned char *ent = nullptr;                              // the key's entry in the classic directory
         int64_t k;
-        // (position i of the block = position i of its first query, or i - n_[0] of its second)
-        const int64_t kq = NQ == 1 || i < n_[0] ? qo_[0] + i : qo_[NQ - 1] + (i - n_[0]);
-        if (canon_key(byval ? qv->k[i] : queries[kq], k)) {               // NaN never matches
-            if (dir_bits < 0) {                                              // the bucket directory of a one-sub-index handle
+        if (canon_key(q_at(i), k)) {                                     // NaN never matches
+            if (dir_bits < 0) {                                          // the bucket directory of a one-sub-index handle
                 const BkHit hb = bk_find(dir, (uint32_t)(-dir_bits), k);
                 base = hb.base;
                 total = hb.n;
             } else {
-            uint32_t s = ix_slot(k, dir_log2);
-            for (int probes = 0; probes < kIxMaxProbe; ++probes) {
-                const unsigned char *e = dir + (size_t)s * es;
-                const int4 h = *reinterpret_cast<const int4 *>(e);
-                const int64_t ek = (int64_t)(((uint64_t)(uint32_t)h.y << 32) | (uint32_t)h.x);
-                if (ek == k) { base = (uint32_t)h.z; total = (uint32_t)h.w; ent = e; break; }
-                if (ek == kEmpty) break;
-                s = (s & ~smask) | ((s + 1) & smask);
-            }
+                int4 h;
+                const uint32_t s = ix_probe(dir, es, dir_log2, smask, k, h);
+                if (s != kIxNoSlot) { base = (uint32_t)h.z; total = (uint32_t)h.w; ent = dir + (size_t)s * es; }
             }
         }
-        uint16_t *el = e_len_all + (size_t)i * nsb;
+        uint16_t *el = e_len + (size_t)i * nsb;
         if (ks == 0) {                                                   // one sub-index: the total is its count
             el[0] = (uint16_t)total;
             el[1] = 0;
@@ -884,21 +1107,313 @@ __device__ __forceinline__ void ix_lookup_body(
                 }
             }
         }
-        e_cur_all[i] = base;
+        e_cur[i] = base;
     }
+}
+// The lists of the lanes in `todo`, one after the other, the WAVE walking each 64 postings at a time (a lane walking its
+// own list alone was a chain of dependent loads): f(row, position) for postings first .. len - 1 of post[off ..]
+template <typename F>
+__device__ __forceinline__ void ix_walk_lists(const uint16_t *__restrict__ post, const int lane, unsigned long long todo,
+                                              uint32_t off, uint32_t len, uint32_t first, uint32_t posn, F f) {
+    while (todo) {                                         // wave-uniform
+        const int src = __builtin_amdgcn_readfirstlane(__ffsll((long long)todo) - 1);
+        todo &= todo - 1;
+        const uint32_t o = (uint32_t)__builtin_amdgcn_readlane((int)off, src);
+        const uint32_t l = (uint32_t)__builtin_amdgcn_readlane((int)len, src);
+        const uint32_t k0 = (uint32_t)__builtin_amdgcn_readlane((int)first, src);
+        const uint32_t ps = (uint32_t)__builtin_amdgcn_readlane((int)posn, src);
+        for (uint32_t k = k0 + (uint32_t)lane; k < l; k += 64u) f((uint32_t)post[o + k], ps);
+    }
+}
+// A wave's posting lists in the sub-index the block is walking: what the layout leaves for the two passes.
+// Query position i = chunk * block + lane * waves + wave belongs to wave `wave`, lane `lane`.
+struct IxWalk {
+    const uint16_t *__restrict__ post;
+    uint32_t *pcache;                  // this wave's pieces of IxLds::cache, lst, lbits
+    uint2 *lst;
+    uint32_t *lbits;
+    uint32_t *e_cur;                   // the query's rows of IxLds::e_cur, e_len
+    const uint16_t *e_len;
+    int n, n_chunks, nsb, sub_at;      // positions, chunks of kIxBlock positions; e_len's row length and this sub-index's column
+    int lane, wave;
+    uint32_t off0, len0, p0;           // this lane's chunk-0 list: first posting, length, local start
+    uint32_t tw, c_hi;                 // postings of the wave's chunk-0 lists; the cached part of them
+
+    __device__ __forceinline__ bool any_uncached() const { return tw > (uint32_t)kIxPW || n_chunks > 1; }
+    // Postings outside the cached range - the tail of a wave with more than kIxPW postings in this sub-index (5 % of the
+    // waves on the config-4 corpus, 1 % of the postings), and every later chunk of a query of more than 512 timestamps.
+    // f(row, position) for all of them.
+    template <typename F>
+    __device__ __forceinline__ void each_uncached(F f) const {
+        if (tw > (uint32_t)kIxPW) {
+            const uint32_t first = p0 < (uint32_t)kIxPW ? (uint32_t)kIxPW - p0 : 0u;
+            ix_walk_lists(post, lane, __ballot(first < len0), off0, len0, first, (uint32_t)(lane * kIxWaves + wave), f);
+        }
+        for (int c = 1; c < n_chunks; ++c) {
+            const int i = c * kIxBlock + ix_opaque(lane) * kIxWaves + wave;
+            const uint32_t len = i < n ? e_len[(size_t)i * nsb + sub_at] : 0u;
+            const uint32_t off = i < n ? e_cur[i] - len : 0u;             // (e_cur was advanced by ix_pass_a)
+            ix_walk_lists(post, lane, __ballot(len != 0u), off, len, 0u, (uint32_t)i, f);
+        }
+    }
+};
+
+// layout: chunk 0 - every position of a query of up to 512 timestamps - is laid out in the wave's LOCAL flat posting
+// space: non-empty lists compacted by a ballot, their starts marked in a bitmap
+__device__ __forceinline__ void ix_layout_chunk0(IxWalk &wk) {
+    wk.off0 = 0;
+    wk.len0 = 0;
+    const int i = wk.lane * kIxWaves + wk.wave;
+    if (i < wk.n) {
+        wk.len0 = wk.e_len[(size_t)i * wk.nsb + wk.sub_at];
+        wk.off0 = wk.e_cur[i];
+        wk.e_cur[i] = wk.off0 + wk.len0;                                 // the key's next piece follows
+    }
+    const uint32_t incl = wave_scan_incl(wk.len0);
+    wk.tw = wave_total(incl);
+    wk.p0 = incl - wk.len0;
+    const unsigned long long some = __ballot(wk.len0 != 0u);
+    if (wk.len0) {
+        const uint32_t j = lanes_below(some);
+        wk.lst[j] = make_uint2(wk.off0 - wk.p0, (uint32_t)i);            // local posting t of the wave = post[.x + t]
+        if (wk.p0 < (uint32_t)kIxPW) atomicOr(&wk.lbits[wk.p0 >> 5], 1u << (wk.p0 & 31u));
+    }
+    wave_lds_fence();
+    wk.c_hi = wk.tw < (uint32_t)kIxPW ? wk.tw : (uint32_t)kIxPW;
+}
+// pass A over the wave's cached postings, one trip of N steps.  The list of local posting t = (list starts at or
+// before t) - 1.  A step is 64 consecutive postings = two words of the start bitmap, read by the whole wave (one
+// broadcast read); the starts before the step are carried in a scalar: no search, no per-posting table lookup.  All N
+// posting loads are in flight, N = the exact number of steps (eight-step trips with masked-off steps were 40 % of this
+// loop's instructions).  Stage by stage, so that the N steps' LDS round trips overlap: start masks -> list entries ->
+// posting loads.  Lanes past the end of the postings (last step only) read up to 63 postings beyond the wave's last
+// list: the posting buffer is padded for that, and the value is discarded.
+template <int N>
+__device__ __forceinline__ void ix_pass_a_trip(const IxWalk &wk, uint32_t *bm1, uint32_t *bm2, int32_t min_match) {
+    const int lane = wk.lane;
+    unsigned long long M[N];
+#pragma unroll
+    for (int u = 0; u < N; ++u) M[u] = *reinterpret_cast<const unsigned long long *>(wk.lbits + 2 * u);
+    uint2 e[N];
+    uint32_t before = 0;
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+        const uint32_t below = lanes_below(M[u]);          // starts before this lane
+        const uint32_t here = (uint32_t)((M[u] >> lane) & 1ull);
+        e[u] = wk.lst[before + below + here - 1u];
+        before += (uint32_t)__popcll(M[u]);
+    }
+    uint32_t r[N];
+#pragma unroll
+#ifdef TVZ_IX_FAKEPOST      // diagnostic build only (WRONG results): no posting line is fetched, the row is made up from the address
+    for (int u = 0; u < N; ++u) r[u] = ((e[u].x + (uint32_t)(u * 64 + lane)) * 2654435761u) >> (32 - kSubLog2);
+#else
+    for (int u = 0; u < N; ++u) r[u] = wk.post[e[u].x + (uint32_t)(u * 64 + lane)];
+#endif
+#pragma unroll
+    for (int u = 0; u < N; ++u) wk.lbits[2 * u + (lane & 1)] = 0;        // done with: ready for the next sub-index
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+        const uint32_t t = (uint32_t)(u * 64 + lane);
+        if (t >= wk.c_hi) continue;
+        wk.pcache[t] = r[u] | (e[u].y << kSubLog2);
+        ix_touch(bm1, bm2, min_match, r[u]);
+    }
+}
+// pass A: which rows are touched (twice) - the cached trip, then the lists outside the cache
+__device__ __forceinline__ void ix_pass_a(const IxWalk &wk, uint32_t *bm1, uint32_t *bm2, int32_t min_match) {
+    if (wk.c_hi) switch ((wk.c_hi + 63u) >> 6) {           // wave-uniform (scalar)
+        case 1: ix_pass_a_trip<1>(wk, bm1, bm2, min_match); break;
+        case 2: ix_pass_a_trip<2>(wk, bm1, bm2, min_match); break;
+        case 3: ix_pass_a_trip<3>(wk, bm1, bm2, min_match); break;
+        case 4: ix_pass_a_trip<4>(wk, bm1, bm2, min_match); break;
+        case 5: ix_pass_a_trip<5>(wk, bm1, bm2, min_match); break;
+        case 6: ix_pass_a_trip<6>(wk, bm1, bm2, min_match); break;
+        case 7: ix_pass_a_trip<7>(wk, bm1, bm2, min_match); break;
+        default: ix_pass_a_trip<8>(wk, bm1, bm2, min_match); break;
+    }
+    for (int c = 1; c < wk.n_chunks; ++c) {                // advance the later chunks' cursors (once per sub-index)
+        const int i = c * kIxBlock + ix_opaque(wk.lane) * kIxWaves + wk.wave;
+        if (i < wk.n) wk.e_cur[i] += wk.e_len[(size_t)i * wk.nsb + wk.sub_at];
+    }
+    if (wk.any_uncached()) wk.each_uncached([&](uint32_t r, uint32_t) { ix_touch(bm1, bm2, min_match, r); });
+}
+// rank: candidates before every bitmap word (thread t owns words t * kIxWpt .. + kIxWpt - 1, read into cw[]; rk0 =
+// candidates before its first).  Returns the candidates in all; one block barrier.
+__device__ __forceinline__ uint32_t ix_rank_phase(const IxBlockTeam &team, const uint32_t *cand, uint16_t *rank,
+                                                  uint32_t (&cw)[kIxWpt], uint32_t &rk0) {
+    uint32_t c = 0, n_cand;
+#pragma unroll
+    for (int w = 0; w < kIxWpt; ++w) { cw[w] = cand[threadIdx.x * kIxWpt + w]; c += __popc(cw[w]); }
+    const uint32_t incl = wave_scan_incl(c);
+    team.sums(incl, rk0, n_cand);
+    rk0 += incl - c;
+    ix_rank_store(rank + threadIdx.x * kIxWpt, cw, rk0);
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)n_cand);
+}
+// pass B for the part of kIxSlots candidates from candidate `lo`: every posting of a candidate row is accounted for in
+// the row's slot.  The wave's cached postings go up to four per lane at a time: all reads of a stage before the next
+// stage (one posting per trip was a chain of four dependent LDS round trips per posting).
+template <typename SLOTS>
+__device__ __forceinline__ void ix_pass_b(const IxWalk &wk, const SLOTS &slots, const uint32_t *cand, const uint16_t *rank,
+                                          uint32_t lo) {
+    const int lane = wk.lane;
+    const uint32_t c_hi = wk.c_hi;
+    auto account = [&](uint32_t r, uint32_t pos, uint32_t w, uint32_t rkw) {
+        const uint32_t bit = r & 31u;
+        if (!((w >> bit) & 1u)) return;
+        const uint32_t idx = rkw + __popc(w & ((1u << bit) - 1u)) - lo;    // the row's slot in this part
+        if (idx >= (uint32_t)kIxSlots) return;                       // another part's (wraps below lo)
+        slots.account(idx, pos);
+    };
+    auto tripb = [&](auto nc, const uint32_t t0) {
+        constexpr int N = decltype(nc)::value;
+        uint32_t e[N], w[N], rkw[N];
+#pragma unroll
+        for (int u = 0; u < N; ++u) {
+            const uint32_t t = t0 + (uint32_t)(u * 64 + lane);
+            e[u] = wk.pcache[t < c_hi ? t : c_hi - 1u];
+        }
+#pragma unroll
+        for (int u = 0; u < N; ++u) {
+            const uint32_t r = e[u] & (uint32_t)(kSubRows - 1);
+            w[u] = cand[r >> 5];
+            rkw[u] = rank[r >> 5];
+        }
+#pragma unroll
+        for (int u = 0; u < N; ++u) {
+            if (t0 + (uint32_t)(u * 64 + lane) >= c_hi) continue;
+            account(e[u] & (uint32_t)(kSubRows - 1), e[u] >> kSubLog2, w[u], rkw[u]);
+        }
+    };
+    for (uint32_t t0 = 0; t0 < c_hi; t0 += 256u) {
+        const uint32_t steps = (c_hi - t0 + 63u) >> 6;                // wave-uniform (scalar)
+        switch (steps >= 4u ? 4u : steps) {
+            case 1: tripb(IxN<1>{}, t0); break;
+            case 2: tripb(IxN<2>{}, t0); break;
+            case 3: tripb(IxN<3>{}, t0); break;
+            default: tripb(IxN<4>{}, t0); break;
+        }
+    }
+    if (wk.any_uncached())
+        wk.each_uncached([&](uint32_t r, uint32_t pos) { account(r, pos, cand[r >> 5], rank[r >> 5]); });
+}
+// emit to a hit list: this thread's live hits (vid[u] >= 0) of the part go to rows o, o + 1, .. of out_hits, as far as
+// the list has room; kth(k) = the kth of slot k.  The part's slots are reset by their last readers.
+template <typename SLOTS, typename KTH>
+__device__ __forceinline__ void ix_emit_list(const SLOTS &slots, const int32_t (&vid)[kIxSlots / kIxBlock], uint32_t n_list,
+                                             KTH kth, uint32_t o, int64_t room, int32_t *out_hits) {
+#pragma unroll
+    for (int u = 0; u < kIxSlots / kIxBlock; ++u) {
+        const uint32_t k = (uint32_t)u * kIxBlock + threadIdx.x;
+        if (vid[u] >= 0) {
+            if ((int64_t)o < room) {
+                int32_t *hp = out_hits + (int64_t)o * 3;
+                const int32_t kth_k = kth(k);
+                // streaming stores: 100 MB of hits per batch would otherwise push the posting
+                // lines a block comes back to in its next sub-index out of the XCD's 4 MB L2
+                // (HBM reads per launch 559 -> 507 MB, profiles/r3_match_pmc.txt)
+                __builtin_nontemporal_store(vid[u], &hp[0]);
+                __builtin_nontemporal_store((int32_t)slots.tcnt[k], &hp[1]);
+                __builtin_nontemporal_store(kth_k, &hp[2]);
+            }
+            ++o;
+        }
+        if (k < n_list) slots.reset(k);                    // this thread was the slot's last reader
+    }
+}
+
+// The lookup of one block: the phases above in the order of the comment at the top of this file.
+// NQ (TOPK only): queries per block.  With NQ = 2 block b takes queries 2 b and 2 b + 1: BOTH are probed in the one
+// probe phase at the start (a query of ~200 timestamps occupies 200 of the block's 512 threads there, and the phase is
+// two dependent round trips - keys, directory entries - during which the block does nothing else: a third of a
+// block's time on a 1/8 shard), then walked one after the other.  `q` = the block's first query, `Q` = queries in the batch.
+template <bool HOSTOUT, int MODE, bool TOPK, int NQ = 1>
+__device__ __forceinline__ void ix_lookup_body(
+    const unsigned char *__restrict__ dir, int dir_bits, int ks, const uint16_t *__restrict__ post,
+    const int32_t *__restrict__ ivid, int64_t n_indexed, int32_t n_sub, int32_t spb,
+    const double *__restrict__ queries, const int64_t *__restrict__ q_offsets, int32_t max_len,
+    int32_t min_match, const int32_t *__restrict__ exclude_ids, int32_t exclude_one, int32_t cap,
+    int32_t *__restrict__ hits, int32_t *__restrict__ hits_n, int32_t ns, const QByVal *qv, const int q_first,
+    const int group, const int n_groups, const int32_t tk_k = 0, const int32_t Q = 0) {
+    static_assert(!(TOPK && (HOSTOUT || MODE == kModeCount)), "the fused top-k needs kth in the block and a device list");
+    static_assert(NQ == 1 || (NQ == 2 && TOPK), "two queries per block: the top-k form only");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int nsb = ix_nsb_padded(spb);
+    const IxLds lds = lds_carve<IxLds>(smem, (size_t)(NQ * (max_len > 0 ? max_len : 1)), nsb, TOPK);
+    uint32_t *const bm1 = lds.bm1, *const bm2 = lds.bm2, *const tcnt = lds.tcnt, *const kh = lds.kh, *const tk_n = lds.tk_n;
+    uint16_t *const elist = lds.elist, *const rank = lds.rank;
+    const IxSlotTable<MODE, kIxSlots, false> slots{lds.tcnt, lds.ttop};
+    __shared__ uint32_t s_wb[kIxWaves], s_wc[kIxWaves];
+    __shared__ uint32_t s_bcast;
+    __shared__ uint32_t s_tk[TOPK ? kIxWaves : 1];
+    __shared__ unsigned long long s_tkT;
+
+    // ---- set-up: the block's queries; a query longer than max_query_len is refused ----
+    const int sub_lo = group * spb;
+    const int sub_hi = sub_lo + spb < n_sub ? sub_lo + spb : n_sub;
+    const bool alone = n_groups == 1;                  // this block owns the query's hit list
+    const bool byval = !TOPK && q_offsets == nullptr;      // (the query travels in the kernel arguments)
+    int64_t qo_[NQ];
+    int n_[NQ];
+    bool skip_[NQ];                                        // refused (too long), or past the end of the batch
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+        const int q = q_first + j;
+        skip_[j] = NQ > 1 && q >= Q;
+        qo_[j] = 0;
+        n_[j] = 0;
+        if (skip_[j]) continue;
+        qo_[j] = byval ? 0 : q_offsets[q];
+        const int64_t n64 = byval ? qv->n : q_offsets[q + 1] - qo_[j];
+        if (n64 > max_len) {   // max_query_len was not an upper bound (the LDS arrays are sized from it)
+            if (TOPK) ix_tk_pad<kIxBlock>(hits + (int64_t)q * (tk_k + 1) * 3, 0, tk_k, INT32_MIN);
+            else if (HOSTOUT) { for (int s = sub_lo + threadIdx.x; s < sub_hi; s += kIxBlock) hits_n[s] = INT32_MIN; }
+            else if (threadIdx.x == 0) hits_n[(size_t)q * ns] = INT32_MIN;
+            skip_[j] = true;
+            if (NQ == 1) return;
+            continue;
+        }
+        n_[j] = (int)n64;
+    }
+    const int n_all = NQ == 1 ? n_[0] : n_[0] + n_[NQ - 1];
+#ifdef TVZ_IX_STAMP
+    unsigned long long st_acc[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long st_last = __builtin_amdgcn_s_memtime();
+#endif
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // in an SGPR: scalar loop bounds
+    IxBlockTeam team{s_wb, &s_tkT, wave, lane}, team_tk{s_tk, &s_tkT, wave, lane};
+    IxWalk wk;
+    wk.post = post;
+    wk.pcache = lds.cache + wave * kIxPW;
+    wk.lst = lds.lst + wave * 64;
+    wk.lbits = lds.lbits + wave * kIxLW;
+    wk.nsb = nsb;
+    wk.lane = lane;
+    wk.wave = wave;
+    for (int i = threadIdx.x; i < kIxWords; i += kIxBlock) { bm1[i] = 0; bm2[i] = 0; }
+    for (int i = threadIdx.x; i < kIxWaves * kIxLW; i += kIxBlock) lds.lbits[i] = 0;
+    for (int i = threadIdx.x; i < kIxSlots; i += kIxBlock) slots.reset((uint32_t)i);
+    if (TOPK) for (int i = threadIdx.x; i < kIxTkBins + 2; i += kIxBlock) kh[i] = 0;      // histogram, fill, pad
+    unsigned long long tk_cut = ~0ull;                     // TOPK: hits >= this cannot make the top-k (block-uniform)
+    uint32_t tk_bmax = 0xffffffffu;                        // TOPK: hits with kth beyond this neither (block-uniform)
+
+    // (position i of the block = position i of its first query, or i - n_[0] of its second)
+    ix_probe_phase(dir, dir_bits, ks, [&](int i) {
+        return byval ? qv->k[i] : queries[NQ == 1 || i < n_[0] ? qo_[0] + i : qo_[NQ - 1] + (i - n_[0])];
+    }, n_all, sub_lo, sub_hi, nsb, lds.e_len, lds.e_cur);
     __syncthreads();
     TVZ_STAMP(0);
-#if defined(TVZ_IX_STOP) && TVZ_IX_STOP == 1
-    return;
-#endif
 
 #pragma unroll 1
     for (int qj = 0; qj < NQ; ++qj) {                      // the block's queries, one after the other
     if (skip_[qj]) continue;                               // (block-uniform)
     const int q = q_first + qj;
-    const int n = n_[qj];
-    uint32_t *e_cur = e_cur_all + (qj ? n_[0] : 0);
-    uint16_t *e_len = e_len_all + (size_t)(qj ? n_[0] : 0) * nsb;
+    wk.n = n_[qj];
+    wk.n_chunks = (wk.n + kIxBlock - 1) / kIxBlock;        // query positions come in chunks of one per thread
+    wk.e_cur = lds.e_cur + (qj ? n_[0] : 0);
+    wk.e_len = lds.e_len + (size_t)(qj ? n_[0] : 0) * nsb;
     if (NQ > 1 && qj) {
         // the first query's epilogue has read the kept hits: start the second one's list and histogram
         __syncthreads();
@@ -908,181 +1423,28 @@ __device__ __forceinline__ void ix_lookup_body(
         __syncthreads();
     }
     const int32_t excl = exclude_ids ? exclude_ids[q] : exclude_one;
-    const int n_chunks = (n + kIxBlock - 1) / kIxBlock;    // query positions come in chunks of one per thread
     uint32_t emitted = 0;                                  // hits so far (identical in every thread)
     for (int sub = sub_lo; sub < sub_hi; ++sub) {
         if (HOSTOUT) emitted = 0;                          // every sub-index has its own region and count
         // HOSTOUT: the sub-index's own hit region [sub][kSubRows][3] and count in pinned host memory
         int32_t *out_n = HOSTOUT ? hits_n + sub : hits_n + (size_t)q * ns;
         int32_t *out_hits = HOSTOUT ? hits + (int64_t)sub * kSubRows * 3 : hits + (int64_t)q * cap * 3;
-        auto touch = [&](uint32_t r) {                     // pass A's bookkeeping for one posting of row r
-            const uint32_t bit = 1u << (r & 31u);
-            const uint32_t old = atomicOr(&bm1[r >> 5], bit);
-            if (min_match >= 2 && (old & bit)) atomicOr(&bm2[r >> 5], bit);
-        };
-        // ---- this wave's posting lists (position i = chunk * block + lane * waves + wave) ----
-        // chunk 0 - every position of a query of up to 512 timestamps - is laid out in the wave's LOCAL
-        // flat posting space: non-empty lists compacted by a ballot, their starts marked in a bitmap
-        uint32_t off0 = 0, len0 = 0, p0 = 0;               // this lane's chunk-0 list: first posting, length, local start
-        uint32_t tw;                                       // postings of the wave's chunk-0 lists
-        {
-            const int i = lane * kIxWaves + wave;
-            if (i < n) {
-                len0 = e_len[(size_t)i * nsb + (sub - sub_lo)];
-                off0 = e_cur[i];
-                e_cur[i] = off0 + len0;                                  // the key's next piece follows
-            }
-            const uint32_t incl = wave_scan_incl(len0);
-            tw = wave_total(incl);
-            p0 = incl - len0;
-            const unsigned long long some = __ballot(len0 != 0u);
-            if (len0) {
-                const uint32_t j = lanes_below(some);
-                lst[j] = make_uint2(off0 - p0, (uint32_t)i);             // local posting t of the wave = post[.x + t]
-                if (p0 < (uint32_t)kIxPW) atomicOr(&lbits[p0 >> 5], 1u << (p0 & 31u));
-            }
-            wave_lds_fence();
-        }
-        const uint32_t c_hi = tw < (uint32_t)kIxPW ? tw : (uint32_t)kIxPW;   // cached part of the local space
+        wk.sub_at = sub - sub_lo;
+        ix_layout_chunk0(wk);
         TVZ_STAMP(1);
-        // ---- pass A: which rows are touched (twice) ----
-        if (c_hi) {
-            // the list of local posting t = (list starts at or before t) - 1.  A step is 64 consecutive
-            // postings = two words of the start bitmap, read by the whole wave (one broadcast read); the
-            // starts before the step are carried in a scalar: no search, no per-posting table lookup.
-            // A trip = N steps with all N posting loads in flight, N = the exact number of steps
-            // (eight-step trips with masked-off steps were 40 % of this loop's instructions).
-            auto trip = [&](auto nc) {
-                constexpr int N = decltype(nc)::value;
-                // stage by stage, so that the N steps' LDS round trips overlap: start masks -> list
-                // entries -> posting loads.  Lanes past the end of the postings (last step only) read up
-                // to 63 postings beyond the wave's last list: the posting buffer is padded for that, and
-                // the value is discarded.
-                unsigned long long M[N];
-#pragma unroll
-                for (int u = 0; u < N; ++u) M[u] = *reinterpret_cast<const unsigned long long *>(lbits + 2 * u);
-                uint2 e[N];
-                uint32_t before = 0;
-#pragma unroll
-                for (int u = 0; u < N; ++u) {
-                    const uint32_t below = lanes_below(M[u]);   // starts before this lane
-                    const uint32_t here = (uint32_t)((M[u] >> lane) & 1ull);
-                    e[u] = lst[before + below + here - 1u];
-                    before += (uint32_t)__popcll(M[u]);
-                }
-                uint32_t r[N];
-#pragma unroll
-#ifdef TVZ_IX_FAKEPOST      // diagnostic build only (WRONG results): no posting line is fetched, the row is made up from the address
-                for (int u = 0; u < N; ++u) r[u] = ((e[u].x + (uint32_t)(u * 64 + lane)) * 2654435761u) >> (32 - kSubLog2);
-#else
-                for (int u = 0; u < N; ++u) r[u] = post[e[u].x + (uint32_t)(u * 64 + lane)];
-#endif
-#pragma unroll
-                for (int u = 0; u < N; ++u) lbits[2 * u + (lane & 1)] = 0;      // done with: ready for the next sub-index
-#pragma unroll
-                for (int u = 0; u < N; ++u) {
-                    const uint32_t t = (uint32_t)(u * 64 + lane);
-                    if (t >= c_hi) continue;
-                    pcache[t] = r[u] | (e[u].y << kSubLog2);
-                    touch(r[u]);
-                }
-            };
-            switch ((c_hi + 63u) >> 6) {                   // wave-uniform (scalar)
-                case 1: trip(IxN<1>{}); break;
-                case 2: trip(IxN<2>{}); break;
-                case 3: trip(IxN<3>{}); break;
-                case 4: trip(IxN<4>{}); break;
-                case 5: trip(IxN<5>{}); break;
-                case 6: trip(IxN<6>{}); break;
-                case 7: trip(IxN<7>{}); break;
-                default: trip(IxN<8>{}); break;
-            }
-        }
-        // postings outside the cached range - the tail of a wave with more than kIxPW postings in this
-        // sub-index (5 % of the waves on the config-4 corpus, 1 % of the postings), and every later chunk
-        // of a query of more than 512 timestamps.  The WAVE walks those lists one after the other, 64
-        // postings at a time (a lane walking its own list alone was a chain of dependent loads).
-        // `each_uncached(f)` calls f(row, position) for all of them; pass B uses it again.
-        auto walk_lists = [&](unsigned long long todo, uint32_t off, uint32_t len, uint32_t first, uint32_t posn, auto f) {
-            while (todo) {                                 // wave-uniform
-                const int src = __builtin_amdgcn_readfirstlane(__ffsll((long long)todo) - 1);
-                todo &= todo - 1;
-                const uint32_t o = (uint32_t)__builtin_amdgcn_readlane((int)off, src);
-                const uint32_t l = (uint32_t)__builtin_amdgcn_readlane((int)len, src);
-                const uint32_t k0 = (uint32_t)__builtin_amdgcn_readlane((int)first, src);
-                const uint32_t ps = (uint32_t)__builtin_amdgcn_readlane((int)posn, src);
-                for (uint32_t k = k0 + (uint32_t)lane; k < l; k += 64u) f((uint32_t)post[o + k], ps);
-            }
-        };
-        auto each_uncached = [&](auto f) {
-            if (tw > (uint32_t)kIxPW) {
-                const uint32_t first = p0 < (uint32_t)kIxPW ? (uint32_t)kIxPW - p0 : 0u;
-                walk_lists(__ballot(first < len0), off0, len0, first, (uint32_t)(lane * kIxWaves + wave), f);
-            }
-            for (int c = 1; c < n_chunks; ++c) {
-                const int i = c * kIxBlock + ix_opaque(lane) * kIxWaves + wave;
-                const uint32_t len = i < n ? e_len[(size_t)i * nsb + (sub - sub_lo)] : 0u;
-                const uint32_t off = i < n ? e_cur[i] - len : 0u;         // (e_cur was advanced below)
-                walk_lists(__ballot(len != 0u), off, len, 0u, (uint32_t)i, f);
-            }
-        };
-        for (int c = 1; c < n_chunks; ++c) {               // advance the later chunks' cursors (once per sub-index)
-            const int i = c * kIxBlock + ix_opaque(lane) * kIxWaves + wave;
-            if (i < n) e_cur[i] += e_len[(size_t)i * nsb + (sub - sub_lo)];
-        }
-        if (tw > (uint32_t)kIxPW || n_chunks > 1) each_uncached([&](uint32_t r, uint32_t) { touch(r); });
+        ix_pass_a(wk, bm1, bm2, min_match);
         TVZ_STAMP(2);
         __syncthreads();
         TVZ_STAMP(3);
-#if defined(TVZ_IX_STOP) && TVZ_IX_STOP == 3
-        for (int i = threadIdx.x; i < kIxWords; i += kIxBlock) { bm1[i] = 0; bm2[i] = 0; }
-        __syncthreads();
-        continue;
-#endif
         const uint32_t *cand = min_match >= 2 ? bm2 : bm1;
-        // ---- rank: candidates before every bitmap word (thread t owns words t*kIxWpt .. +kIxWpt-1) ----
-        uint32_t cw[kIxWpt], c = 0;
-#pragma unroll
-        for (int w = 0; w < kIxWpt; ++w) { cw[w] = cand[threadIdx.x * kIxWpt + w]; c += __popc(cw[w]); }
-        uint32_t rk0;                                      // candidates before this thread's first word
-        {
-            const uint32_t incl = wave_scan_incl(c);
-            if (lane == 63) s_wb[wave] = incl;
-            __syncthreads();
-            rk0 = incl - c;
-        }
-        uint32_t n_cand = 0;
-#pragma unroll
-        for (int w = 0; w < kIxWaves; ++w) {
-            const uint32_t a = s_wb[w];
-            if (w < wave) rk0 += a;
-            n_cand += a;
-        }
-        n_cand = (uint32_t)__builtin_amdgcn_readfirstlane((int)n_cand);
-        {
-            uint32_t run = rk0;
-#pragma unroll
-            for (int w = 0; w < kIxWpt; ++w) { rank[threadIdx.x * kIxWpt + w] = (uint16_t)run; run += __popc(cw[w]); }
-        }
+        uint32_t cw[kIxWpt], rk0;
+        const uint32_t n_cand = ix_rank_phase(team, cand, rank, cw, rk0);
         static_assert(kIxSlots % kIxBlock == 0, "whole rounds of the block over the slots");
         const int64_t row0 = (int64_t)sub << kSubLog2;
 
         // ---- pass B + emit, kIxSlots candidates at a time ----
         for (uint32_t lo = 0; lo < n_cand; lo += kIxSlots) {
-            // the rows of this part's slots (slot = rank of the candidate - lo): written by the owners of
-            // the bitmap words, no compaction, no atomics
-            {
-                uint32_t run = rk0;
-#pragma unroll
-                for (int ww = 0; ww < kIxWpt; ++ww) {
-                    const uint32_t wi = threadIdx.x * kIxWpt + ww;
-                    for (uint32_t rest = cw[ww], i = 0; rest; rest &= rest - 1, ++i) {
-                        const uint32_t idx = run + i - lo;
-                        if (idx < (uint32_t)kIxSlots) elist[idx] = wi * 32u + ((uint32_t)__ffs(rest) - 1u);
-                    }
-                    run += __popc(cw[ww]);
-                }
-            }
+            ix_slot_rows<kIxSlots>(elist, cw, threadIdx.x * kIxWpt, rk0, lo);
             TVZ_STAMP(4);
             __syncthreads();                               // (first round: also publishes rank)
             TVZ_STAMP(5);
@@ -1090,82 +1452,17 @@ __device__ __forceinline__ void ix_lookup_body(
             // the video ids of the slots' rows: loads issued now, used after pass B (which touches LDS only)
             int32_t vid[kIxSlots / kIxBlock];
 #pragma unroll
-            for (int u = 0; u < kIxSlots / kIxBlock; ++u) {
-                const uint32_t k = (uint32_t)u * kIxBlock + threadIdx.x;
-                const int64_t row = row0 + (k < n_list ? elist[k] : 0u);
-#ifdef TVZ_IX_NOIVID
-                vid[u] = (int32_t)row;
-#else
-                vid[u] = ivid[k < n_list && row < n_indexed ? row : row0];  // unconditional load
-#endif
-                // replaced since the build (-1) / the query's own video: not a hit
-                if (k >= n_list || row >= n_indexed || vid[u] == excl) vid[u] = -1;
-            }
-            auto account = [&](uint32_t r, uint32_t pos, uint32_t w, uint32_t rkw) {
-                const uint32_t bit = r & 31u;
-                if (!((w >> bit) & 1u)) return;
-                const uint32_t idx = rkw + __popc(w & ((1u << bit) - 1u)) - lo;
-                if (idx >= (uint32_t)kIxSlots) return;                       // another part's (wraps below lo)
-                atomicAdd(&tcnt[idx], 1u);
-                if constexpr (TOP5) {
-                    unsigned long long seen = ttop[idx];
-                    while (true) {
-                        if (((uint32_t)(seen >> (12 * (kTop - 1))) & 0xfffu) <= pos) break;   // not among the 5 smallest
-                        const unsigned long long old = atomicCAS(&ttop[idx], seen, top5_insert(seen, pos));
-                        if (old == seen) break;
-                        seen = old;
-                    }
-                } else if constexpr (MODE == kModeM2) {
-                    const uint32_t o = atomicMin(&m1[idx], pos);             // positions of one row are distinct
-                    atomicMin(&m2[idx], o > pos ? o : pos);                  // larger of two hits >= 2nd smallest
-                }
-            };
-            // the wave's cached postings, up to four per lane at a time: all reads of a stage before the
-            // next stage (one posting per trip was a chain of four dependent LDS round trips per posting)
-            auto tripb = [&](auto nc, const uint32_t t0) {
-                constexpr int N = decltype(nc)::value;
-                uint32_t e[N], w[N], rkw[N];
-#pragma unroll
-                for (int u = 0; u < N; ++u) {
-                    const uint32_t t = t0 + (uint32_t)(u * 64 + lane);
-                    e[u] = pcache[t < c_hi ? t : c_hi - 1u];
-                }
-#pragma unroll
-                for (int u = 0; u < N; ++u) {
-                    const uint32_t r = e[u] & (uint32_t)(kSubRows - 1);
-                    w[u] = cand[r >> 5];
-                    rkw[u] = rank[r >> 5];
-                }
-#pragma unroll
-                for (int u = 0; u < N; ++u) {
-                    if (t0 + (uint32_t)(u * 64 + lane) >= c_hi) continue;
-                    account(e[u] & (uint32_t)(kSubRows - 1), e[u] >> kSubLog2, w[u], rkw[u]);
-                }
-            };
-            for (uint32_t t0 = 0; t0 < c_hi; t0 += 256u) {
-                const uint32_t steps = (c_hi - t0 + 63u) >> 6;                // wave-uniform (scalar)
-                switch (steps >= 4u ? 4u : steps) {
-                    case 1: tripb(IxN<1>{}, t0); break;
-                    case 2: tripb(IxN<2>{}, t0); break;
-                    case 3: tripb(IxN<3>{}, t0); break;
-                    default: tripb(IxN<4>{}, t0); break;
-                }
-            }
-            if (tw > (uint32_t)kIxPW || n_chunks > 1)
-                each_uncached([&](uint32_t r, uint32_t pos) { account(r, pos, cand[r >> 5], rank[r >> 5]); });
+            for (int u = 0; u < kIxSlots / kIxBlock; ++u)
+                vid[u] = ix_slot_vid(ivid, elist, (uint32_t)u * kIxBlock + threadIdx.x, n_list, row0, n_indexed, excl);
+            ix_pass_b(wk, slots, cand, rank, lo);
             TVZ_STAMP(6);
             __syncthreads();
             TVZ_STAMP(7);
-#if defined(TVZ_IX_STOP) && TVZ_IX_STOP == 4
-            for (int i = threadIdx.x; i < kIxSlots; i += kIxBlock) reset_slot((uint32_t)i);
-            break;
-#endif
             // emit: one slot per thread and round; the slots that reached min_match and are live hits get
             // a place by a block-wide scan - one reservation per block, none when the block owns the list
             auto kth_of = [&](uint32_t k) -> int32_t {
                 if constexpr (MODE == kModeCount) return -2 - (int32_t)(row0 + elist[k]);   // ts_kth_fixup_kernel resolves it
-                else if constexpr (TOP5) return (int32_t)((uint32_t)(ttop[k] >> (12 * (min_match - 1))) & 0xfffu);
-                else return (int32_t)(min_match == 1 ? m1[k] : m2[k]);
+                else return slots.kth_of(k, min_match);
             };
             uint32_t mine = 0;
             unsigned long long ek[kIxSlots / kIxBlock];    // TOPK: this thread's hits as sortable words
@@ -1176,21 +1473,9 @@ __device__ __forceinline__ void ix_lookup_body(
                 const uint32_t k = (uint32_t)u * kIxBlock + threadIdx.x;
                 if (vid[u] >= 0 && (int32_t)tcnt[k] < min_match) vid[u] = -1;
                 mine += vid[u] >= 0 ? 1u : 0u;
-                if constexpr (TOPK) {
-                    // Only hits that can still make the top-k are looked at any further: kth <= tk_bmax, the
-                    // threshold bin of the parts so far (block-uniform; no bound before k hits below position 63
-                    // exist).  After the first sub-index that is a few per cent of the hits.  The bin "63 or
-                    // later" is never counted: no threshold is ever read from it, and with ~70 % of a part's
-                    // hits in it the one LDS address was a serialised atomic per hit.
+                if constexpr (TOPK) {                      // (high half of mine: candidates for the list; <= 1024 per part)
                     ek[u] = ~0ull;
-                    if (vid[u] >= 0) {
-                        const uint32_t kth = (uint32_t)kth_of(k);
-                        if (kth <= tk_bmax) {
-                            ek[u] = ix_tk_pack((int32_t)kth, vid[u], tcnt[k]);
-                            if (kth < (uint32_t)kIxTkBins - 1u) atomicAdd(&kh[kth], 1u);
-                            mine += 1u << 16;              // (high half: candidates for the list; <= 1024 per part)
-                        }
-                    }
+                    if (vid[u] >= 0) ek[u] = ix_tk_offer((uint32_t)kth_of(k), vid[u], tcnt[k], tk_bmax, kh, mine);
                 }
             }
             const uint32_t incl = wave_scan_incl(mine);
@@ -1205,135 +1490,29 @@ __device__ __forceinline__ void ix_lookup_body(
             }
             __syncthreads();
             TVZ_STAMP(8);
-            uint32_t base = 0, all = 0;
-#pragma unroll
-            for (int x = 0; x < kIxWaves; ++x) {
-                const uint32_t a = s_wc[x];
-                if (x < wave) base += a;
-                all += a;
-            }
+            uint32_t base, all;
+            waves_sum<kIxWaves>(s_wc, wave, base, all);
             if constexpr (TOPK) {
                 emitted += all & 0xffffu;
                 const uint32_t n_cand_tk = all >> 16;      // this part's hits at or below the threshold bin
-                if (n_cand_tk) {                           // block-uniform (nothing to keep otherwise: most later parts)
-                    // b* = the first kth bin whose prefix reaches k; every wave scans the bins itself (the
-                    // histogram does not change before the next part's emit: same result in all of them)
-                    const uint32_t hincl = wave_scan_incl(lane < kIxTkBins - 1 ? kh[lane] : 0u);
-                    const unsigned long long reach = __ballot(hincl >= (uint32_t)tk_k);
-                    const int bfirst = __builtin_amdgcn_readfirstlane(reach ? __ffsll((long long)reach) - 1 : kIxTkBins);
-                    uint32_t bound = n_cand_tk;            // this part's keepers, at most
-                    unsigned long long cut = tk_cut;
-                    if (bfirst < kIxTkBins - 1) {
-                        const uint32_t cum = (uint32_t)__builtin_amdgcn_readlane((int)hincl, bfirst);
-                        bound = cum < n_cand_tk ? cum : n_cand_tk;
-                        const unsigned long long bc = (unsigned long long)(bfirst + 1) << 44;
-                        cut = bc < cut ? bc : cut;
-                        tk_bmax = (uint32_t)bfirst < tk_bmax ? (uint32_t)bfirst : tk_bmax;
-                    }
-                    if (tk_before + bound <= (uint32_t)kIxTkCap) {
-#pragma unroll
-                        for (int u = 0; u < kIxSlots / kIxBlock; ++u)
-                            if (ek[u] < cut) tkb[atomicAdd(tk_n, 1u)] = ek[u];
-                    } else {
-                        // rare: hundreds of hits in the threshold bin (true duplicates share their kth) or
-                        // none of the first k hits below position 63.  Reduce the list to its k best - which
-                        // gives the exact cut-off - and feed the part's keepers in rounds of what fits.
-                        auto reduce = [&](uint32_t N) -> uint32_t {
-                            unsigned long long e = ~0ull;
-                            uint32_t r = 0;
-                            if (threadIdx.x < N) {
-                                e = tkb[threadIdx.x];
-                                for (uint32_t i = 0; i < N; ++i) {
-                                    const unsigned long long o = tkb[i];
-                                    r += (o < e || (o == e && i < threadIdx.x)) ? 1u : 0u;
-                                }
-                            }
-                            __syncthreads();
-                            if (threadIdx.x < N && r < (uint32_t)tk_k) tkb[r] = e;
-                            if (threadIdx.x < N && r == (uint32_t)tk_k - 1u) s_tkT = e;
-                            const uint32_t left = N < (uint32_t)tk_k ? N : (uint32_t)tk_k;
-                            if (threadIdx.x == 0) *tk_n = left;
-                            __syncthreads();
-                            if (N >= (uint32_t)tk_k) {
-                                const unsigned long long t = s_tkT;
-                                tk_cut = t < tk_cut ? t : tk_cut;
-                                const uint32_t tb = (uint32_t)(tk_cut >> 44);          // nothing beyond the k-th best's kth matters
-                                tk_bmax = tb < tk_bmax ? tb : tk_bmax;
-                            }
-                            return left;
-                        };
-                        uint32_t nb = reduce(tk_before);
-                        while (true) {                     // block-uniform
-                            cut = tk_cut < cut ? tk_cut : cut;
-                            uint32_t c = 0;
-#pragma unroll
-                            for (int u = 0; u < kIxSlots / kIxBlock; ++u) c += ek[u] < cut ? 1u : 0u;
-                            const uint32_t ci = wave_scan_incl(c);
-                            if (lane == 63) s_tk[wave] = ci;
-                            __syncthreads();
-                            uint32_t before = 0, tot = 0;
-#pragma unroll
-                            for (int x = 0; x < kIxWaves; ++x) {
-                                const uint32_t a = s_tk[x];
-                                if (x < wave) before += a;
-                                tot += a;
-                            }
-                            if (tot == 0) break;
-                            const uint32_t room = (uint32_t)kIxTkCap - nb;
-                            uint32_t off = before + ci - c;
-#pragma unroll
-                            for (int u = 0; u < kIxSlots / kIxBlock; ++u) {
-                                if (ek[u] < cut) {
-                                    if (off < room) { tkb[nb + off] = ek[u]; ek[u] = ~0ull; }
-                                    ++off;
-                                }
-                            }
-                            const uint32_t placed = tot < room ? tot : room;
-                            if (threadIdx.x == 0) *tk_n = nb + placed;
-                            __syncthreads();
-                            nb += placed;
-                            if (tot <= room) break;
-                            nb = reduce(nb);
-                        }
-                    }
-                }
+                if (n_cand_tk)                             // block-uniform (nothing to keep otherwise: most later parts)
+                    ix_tk_keep<kIxSlots / kIxBlock>(team_tk, [&](int u) -> unsigned long long & { return ek[u]; }, kh,
+                                                    lds.tkb, tk_n, tk_before, n_cand_tk, tk_k, lane, tk_cut, tk_bmax);
 #pragma unroll
                 for (int u = 0; u < kIxSlots / kIxBlock; ++u) {
                     const uint32_t k = (uint32_t)u * kIxBlock + threadIdx.x;
-                    if (k < n_list) reset_slot(k);         // this thread was the slot's last reader
+                    if (k < n_list) slots.reset(k);         // this thread was the slot's last reader
                 }
             } else {
-            uint32_t start = emitted;
-            if (!HOSTOUT && !alone && all) {               // block-uniform: the blocks of a query share its list
-                if (threadIdx.x == 0) s_bcast = (uint32_t)atomicAdd(out_n, (int32_t)all);
-                __syncthreads();
-                start = s_bcast;
-            }
-            emitted += all;
-            uint32_t o = start + base + incl - mine;
-            const int64_t room = HOSTOUT ? (int64_t)kSubRows : (int64_t)cap;
-#pragma unroll
-            for (int u = 0; u < kIxSlots / kIxBlock; ++u) {
-                const uint32_t k = (uint32_t)u * kIxBlock + threadIdx.x;
-                if (vid[u] >= 0) {
-#ifdef TVZ_IX_NOSTORE
-                    if ((int64_t)o < room && tcnt[k] == 0x7fffffffu) {
-#else
-                    if ((int64_t)o < room) {
-#endif
-                        int32_t *hp = out_hits + (int64_t)o * 3;
-                        const int32_t kth = kth_of(k);
-                        // streaming stores: 100 MB of hits per batch would otherwise push the posting
-                        // lines a block comes back to in its next sub-index out of the XCD's 4 MB L2
-                        // (HBM reads per launch 559 -> 507 MB, profiles/r3_match_pmc.txt)
-                        __builtin_nontemporal_store(vid[u], &hp[0]);
-                        __builtin_nontemporal_store((int32_t)tcnt[k], &hp[1]);
-                        __builtin_nontemporal_store(kth, &hp[2]);
-                    }
-                    ++o;
+                uint32_t start = emitted;
+                if (!HOSTOUT && !alone && all) {           // block-uniform: the blocks of a query share its list
+                    if (threadIdx.x == 0) s_bcast = (uint32_t)atomicAdd(out_n, (int32_t)all);
+                    __syncthreads();
+                    start = s_bcast;
                 }
-                if (k < n_list) reset_slot(k);             // this thread was the slot's last reader
-            }
+                emitted += all;
+                ix_emit_list(slots, vid, n_list, kth_of, start + base + incl - mine,
+                             HOSTOUT ? (int64_t)kSubRows : (int64_t)cap, out_hits);
             }
             if (lo + kIxSlots < n_cand) __syncthreads();   // the next part rewrites elist and refills the slots
         }
@@ -1346,29 +1525,8 @@ __device__ __forceinline__ void ix_lookup_body(
         TVZ_STAMP(9);
     }
     if constexpr (TOPK) {
-        // the k best of the kept hits, each written to the row of its rank; padding; the totals row
         __syncthreads();                                   // the last part's appends
-        const uint32_t N = *tk_n;
-        int32_t *o = hits + (int64_t)q * (tk_k + 1) * 3;
-        if (threadIdx.x < N) {
-            const unsigned long long e = tkb[threadIdx.x];
-            uint32_t r = 0;
-            for (uint32_t i = 0; i < N; ++i) {
-                const unsigned long long x = tkb[i];
-                r += (x < e || (x == e && i < threadIdx.x)) ? 1u : 0u;
-            }
-            if (r < (uint32_t)tk_k) {
-                o[r * 3 + 0] = (int32_t)(uint32_t)(e >> 12);
-                o[r * 3 + 1] = (int32_t)((uint32_t)e & 0xfffu);
-                o[r * 3 + 2] = (int32_t)(e >> 44);
-            }
-        }
-        const uint32_t have = N < (uint32_t)tk_k ? N : (uint32_t)tk_k;
-        for (uint32_t i = have + threadIdx.x; i <= (uint32_t)tk_k; i += kIxBlock) {
-            o[i * 3 + 0] = -1;
-            o[i * 3 + 1] = i == (uint32_t)tk_k ? ((int64_t)emitted > (int64_t)cap ? -(int32_t)emitted : (int32_t)emitted) : 0;
-            o[i * 3 + 2] = TVZ_KTH_NEVER;
-        }
+        ix_tk_write<kIxBlock>(hits + (int64_t)q * (tk_k + 1) * 3, lds.tkb, *tk_n, tk_k, emitted, cap);
         TVZ_STAMP(10);
     } else if (!HOSTOUT && alone && threadIdx.x == 0) hits_n[(size_t)q * ns] = (int32_t)emitted;
     }                                                      // (the block's next query)

@@ -72,7 +72,7 @@ struct TolIxParked {
     int32_t dir_bits, ks, cap, n_lists;
     int32_t slots_at, excl;             // LDS offset of the kept directory slots (one per pass-A task); 0 = none kept
 };
-constexpr uint32_t kTolIxNoSlot = 0xffffffffu;     // a task's cell has no directory entry (or the task has no cell)
+constexpr uint32_t kTolIxNoSlot = kIxNoSlot;       // a task's cell has no directory entry (or the task has no cell)
 constexpr uint32_t kTolIxRedo = 0xfffffffeu;       // a task with cells beyond its first: not kept, probed again
 // A block that walks several sub-indexes keeps every task's directory slot from its first pass A (4 B per task, 16 B
 // per query timestamp) when that fits next to the sorted query: the later passes then read the entry straight away -
@@ -159,15 +159,8 @@ __global__ __launch_bounds__(kTolBlock) void ts_tol_index_kernel(
         const uint32_t smask = (1u << (s_arg.dir_bits >> 8)) - 1u;      // probes wrap inside the directory slice
         uint32_t *tslot = s_arg.slots_at ? reinterpret_cast<uint32_t *>(smem + s_arg.slots_at) : nullptr;
         auto probe = [&](int64_t cell) -> uint32_t {             // the directory slot of a cell, kTolIxNoSlot if none
-            uint32_t slot = ix_slot(cell, dir_log2);
-            for (int probes = 0; probes < kIxMaxProbe; ++probes) {
-                const int2 h = *reinterpret_cast<const int2 *>(a_dir + (size_t)slot * es);
-                const int64_t ek = (int64_t)(((uint64_t)(uint32_t)h.y << 32) | (uint32_t)h.x);
-                if (ek == cell) return slot;
-                if (ek == kEmpty) break;
-                slot = (slot & ~smask) | ((slot + 1) & smask);
-            }
-            return kTolIxNoSlot;
+            int2 key;                                            // (a step loads the entry's key alone: the walk reads its head)
+            return ix_probe(a_dir, es, dir_log2, smask, cell, key);
         };
         auto walk = [&](uint32_t slot) {                         // the entry's postings in this sub-index mark their rows
             if (slot == kTolIxNoSlot) return;
@@ -179,12 +172,7 @@ __global__ __launch_bounds__(kTolBlock) void ts_tol_index_kernel(
                 for (int t = 0; t < sub; ++t) p += cn[t];
                 len = cn[sub];
             }
-            for (uint32_t t = 0; t < len; ++t) {
-                const uint32_t r = a_post[p + t];
-                const uint32_t bit = 1u << (r & 31u);
-                const uint32_t old = atomicOr(&s_bm1[r >> 5], bit);
-                if (min_match >= 2 && (old & bit)) atomicOr(&s_bm2[r >> 5], bit);
-            }
+            for (uint32_t t = 0; t < len; ++t) ix_touch(s_bm1, s_bm2, min_match, a_post[p + t]);
         };
         for (int task = threadIdx.x; task < m * kTolIxCells; task += kTolBlock) {
             uint32_t slot0 = tslot ? tslot[task] : kTolIxRedo;
@@ -204,24 +192,15 @@ __global__ __launch_bounds__(kTolBlock) void ts_tol_index_kernel(
         __syncthreads();
         // ---- rank: candidates before every bitmap word (thread t owns words t * kTolIxWpt ..) ----
         const uint32_t *cand = min_match >= 2 ? s_bm2 : s_bm1;
-        uint32_t c = 0;
+        uint32_t cw[kTolIxWpt], c = 0;
 #pragma unroll
-        for (int w = 0; w < kTolIxWpt; ++w) c += __popc(cand[threadIdx.x * kTolIxWpt + w]);
+        for (int w = 0; w < kTolIxWpt; ++w) { cw[w] = cand[threadIdx.x * kTolIxWpt + w]; c += __popc(cw[w]); }
         const uint32_t incl = wave_scan_incl(c);
         if (lane == 63) s_ws[wv] = incl;
         __syncthreads();
-        uint32_t run = incl - c, n_cand = 0;
-#pragma unroll
-        for (int w = 0; w < kTolBlock / 64; ++w) {
-            const uint32_t a = s_ws[w];
-            if (w < wv) run += a;
-            n_cand += a;
-        }
-#pragma unroll
-        for (int w = 0; w < kTolIxWpt; ++w) {
-            s_rank[threadIdx.x * kTolIxWpt + w] = (uint16_t)run;
-            run += __popc(cand[threadIdx.x * kTolIxWpt + w]);
-        }
+        uint32_t before, n_cand;
+        waves_sum<kTolBlock / 64>(s_ws, wv, before, n_cand);
+        ix_rank_store(s_rank + threadIdx.x * kTolIxWpt, cw, before + incl - c);
         __syncthreads();
         // ---- verify + emit: group g of part prt takes candidates prt * 16 + g, + split * 16, ... ----
         const uint32_t row0 = (uint32_t)sub << kSubLog2, n_idx = (uint32_t)n_indexed;   // (rows are counted in 31 bits)

@@ -55,6 +55,20 @@ __device__ __forceinline__ uint32_t wave_total(uint32_t incl) {       // of an i
     return (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
 }
 
+// ---- sums over the waves of a block, through one LDS word per wave: lane 63 of every wave posts the total of its
+// inclusive scan; behind a block barrier every thread reads the sum of the waves before its own, and of all
+template <int WAVES>
+__device__ __forceinline__ void waves_sum(const uint32_t *s_w, int wave, uint32_t &before, uint32_t &all) {
+    before = 0;
+    all = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) {
+        const uint32_t a = s_w[w];
+        if (w < wave) before += a;
+        all += a;
+    }
+}
+
 // ---- butterfly over a group: after the four steps every lane holds the reduction of all 16; each
 // step combines two DISJOINT sets of lanes (needed for the second-smallest and top-5 merges)
 #define TVZ_ROW16_BUTTERFLY(STEP) \
