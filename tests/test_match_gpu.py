@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from oracle import oracle
+from tests import topk_ref
 from tvidz_amd import _lib, corpus as tc, synth
 
 pytestmark = pytest.mark.gpu
@@ -404,10 +405,12 @@ def test_topk_merges_gathered_shards(dc):
 
 @pytest.mark.parametrize("R,k", [(8, 16), (16, 64), (3, 1), (8, 40), (20, 64)])
 def test_merge_of_gathered_rank_blocks(dc, R, k):
-    """tvz_topk_merge over [R, Q, k+1, 3] blocks as the all-gather delivers them (one wave per query
-    while R*k <= 1024, the block kernel beyond): order (kth, video_id, count), padding, totals =
-    sum of |n| negated when any shard overflowed; ties of hundreds of entries in one kth (true
-    duplicates on every rank) take the wave kernel's k-rounds path."""
+    """tvz_topk_merge over [R, Q, k+1, 3] blocks as the all-gather delivers them: order (kth, video_id, count),
+    padding, totals = sum of |n| negated when any shard overflowed; ties of hundreds of entries in one kth (true
+    duplicates on every rank).  The dispatch (launch_topk_lists): up to 16 ranks and k <= 64 - the first four
+    shapes here - are a k-way merge of the SORTED blocks (ts_topk_merge_sorted_kernel); (20, 64) is 1280 entries,
+    more than the one-wave kernel's 1024, and goes to the block kernel (ts_topk_kernel).  The one-wave kernel's
+    merges (more than 16 ranks, R*k <= 1024) and its k-rounds path are in tests/test_topk_edges_gpu.py."""
     rng = np.random.default_rng(R * 100 + k)
     Q = 37
     g = np.zeros((R, Q, k + 1, 3), dtype=np.int32)
@@ -484,12 +487,15 @@ def test_every_producer_of_rank_blocks_meets_the_sorted_merge_precondition(dc):
                 assert (b == blocks["block"]).all(), name
         g = np.stack([blocks[n] for n in ("block", "wave", "tile+select", "refused")])
         merged, totals = tc.topk_merge(torch.from_numpy(g).to(DEV), k)
-        merged = merged.cpu().numpy()
+        merged, totals = merged.cpu().numpy(), totals.cpu().numpy()
         for q in range(Q):
             flat = [tuple(int(x) for x in e) for r in range(g.shape[0]) for e in g[r, q, :k] if e[0] >= 0]
             exp = sorted(flat, key=lambda h: (h[2], h[0], h[1]))[:k]
             exp += [(-1, 0, NEVER)] * (k - len(exp))
             assert [tuple(int(x) for x in r) for r in merged[q]] == exp, (k, q)
+            # totals by the header's rule (tvz.h, tvz_topk_merge and tvz_match_tol_sharded's paragraph on refused queries)
+            assert int(totals[q]) == topk_ref.merge([[tuple(int(x) for x in e) for e in g[r, q]] for r in range(g.shape[0])], k)[1], (k, q)
+        assert int(totals[7]) == -(2**31 - 1)               # three true counts + the refused rank's INT32_MIN: saturated, negated
     # with a delta table: the lookup's block and the delta sweep's are merged pairwise (mode 3) - still sorted;
     # and k beyond the fused lookup's 64 (the unfused pipeline)
     for j in range(40):
