@@ -384,6 +384,42 @@ int tvz_match_sharded(tvz_corpus *c, tvz_comm *comm, const double *d_queries,
 int tvz_align(tvz_corpus *c, const double *d_query, int32_t n, double eps, double max_offset,
               int32_t *d_out, int64_t out_rows, int64_t *n_rows, void *hip_stream);
 
+/* The alignment score for a BATCH of queries with the k best-aligned rows kept inside the sweep: no row per corpus
+ * row, nothing that grows with rows or hits.  (TVZ_VERSION unchanged: new exports only.)  For query q and row r the
+ * votes and bins are tvz_align's, word for word: the row is a set; query NaNs are skipped, query duplicates vote again;
+ * B = floor(max_offset/eps + 0.5); the pair (key c, value x) votes into floor((c - x)/eps + 0.5) when that lies in
+ * [-B, B] (ONE IEEE subtraction, ONE true division: no reciprocal, no FMA); best bin = most votes, then smaller |bin|,
+ * then the negative one.  Then, with nv = the query's non-NaN values and votes = the votes in the best bin:
+ *   v     = min(votes, nv, row_len),  u = nv + row_len - v
+ *   score = (v << 20) / u   in 64-bit integer division: the tolerant Jaccard above in 20-bit fixed point,
+ *           0 <= score <= 2^20 (u >= v); a host restates it exactly
+ *   hit  <=> v >= min_votes and score >= min_score and video_id != exclude_id[q]
+ *   order : ascending by the 64-bit word (2^20 - score) << 43 | video_id << 12 | (best_bin + 2048)  (21 + 31 + 12
+ *           bits): better score first, then smaller video id; hits with equal words (two rows of one video_id) by
+ *           (row_len, votes) ascending; rows equal in all of that are identical output rows and are all kept.
+ *   d_out : int32[Q][k+1][4] = the k best hits as (video_id, row_len, best_bin, votes) - votes raw, as tvz_align
+ *           reports it -, padding rows (-1, 0, 0, 0), and a last row (-1, n_hits, 0, 0) with the TRUE number of
+ *           hits, never negated.  n_hits = INT32_MIN (all rows padding) for a query longer than max_query_len or one
+ *           whose sorted copy does not fit the workspace; 0 for an empty corpus, an empty or a NaN-only query.
+ * The rows seen are the handle's table at the call (upserts made before the call are seen).  Enqueues only: no
+ * allocation, no host synchronisation.  Refusals, nothing written: eps / max_offset as tvz_align (TVZ_ERR_INVALID;
+ * TVZ_ERR_UNSUPPORTED for more than 4,096 bins); min_votes < 1 or min_score outside 0..2^20: TVZ_ERR_INVALID; k outside
+ * 1..64 or max_query_len > 4,095: TVZ_ERR_UNSUPPORTED; a workspace below the fixed parts + one query of max_query_len
+ * values (tvz_align_topk_workspace_bytes(Q, max_query_len, max_query_len, k)): TVZ_ERR_WORKSPACE with the bytes missing.
+ * Workspace = tvz_match_tol_workspace_bytes(Q, max_query_len, max(total_query_keys, max_query_len))   (the sorted queries;
+ *             total_query_keys = the length of d_queries, 0: Q x max_query_len)
+ *           + 4 Q                                                                      (hit totals)
+ *           + max(6080, 95 Q) x k x 16                                                  (one kept list - k words and k
+ *             payloads - per sweep block: min(rows / 4, 6080 / Q clamped to 95..2048) row blocks per query)
+ *           + alignment (each part to 256 B).
+ * Cost: per row key one binary search of the sorted query (in LDS) + the votes that count - the query values that
+ * vote for a key are one contiguous run of the sorted query -, not queries x row keys, and no pass over the bins. */
+size_t tvz_align_topk_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k);
+int tvz_align_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
+                   int32_t max_query_len, double eps, double max_offset, int32_t min_votes,
+                   int32_t min_score, const int32_t *d_exclude_ids, int32_t k, int32_t *d_out,
+                   void *d_workspace, size_t workspace_bytes, void *hip_stream);
+
 /* ------------------------------------------------------------------------
  * Opt-in TOLERANT duplicate match.  NOT the reference's verdict: db.py:79,85-91 match exact float64
  * values, and that stays the default everywhere (tolerance 0).  README.md:291 promises "0.1 second

@@ -62,6 +62,32 @@ def tol_topk_workspace_bytes(Q: int, max_query_len: int, total_query_keys: int =
                                                               int(k), int(n_ranks)))
 
 
+def align_topk_workspace_bytes(Q: int, max_query_len: int, total_query_keys: int = 0, k: int = 16) -> int:
+    """tvz_align_topk_workspace_bytes: the sorted queries, the hit totals and one kept list per sweep block - nothing
+    in it grows with rows or hits."""
+    return int(_lib.load().tvz_align_topk_workspace_bytes(int(Q), int(max_query_len), int(total_query_keys), int(k)))
+
+
+ALIGN_SCORE_ONE = 1 << 20
+ALIGN_TOPK_MAX_LEN = 4095
+ALIGN_REFUSED = -(1 << 31)                  # a query's total when tvz_align_topk refused it (INT32_MIN)
+
+
+def align_score(votes: int, nv: int, row_len: int) -> int:
+    """The score tvz_align_topk orders by: the tolerant Jaccard v / (nv + row_len - v), v = min(votes, nv, row_len), in
+    20-bit fixed point, floor((v << 20) / u) - exact integer arithmetic, 0..2^20 (0 where nothing can match)."""
+    v = min(int(votes), int(nv), int(row_len))
+    u = int(nv) + int(row_len) - v
+    return (v << 20) // u if u > 0 else 0
+
+
+def align_order_key(row, nv: int):
+    """Sort key of one (video_id, row_len, best_bin, votes) hit of a query with nv non-NaN values: the order
+    tvz_align_topk keeps its rows in (better score, smaller video id, bin, then row_len and votes)."""
+    vid, row_len, best_bin, votes = (int(x) for x in row)
+    return (-align_score(votes, nv, row_len), vid, best_bin, row_len, votes)
+
+
 class DeviceCorpus:
     """tvz_corpus handle: rows of (video_id, sorted-unique canonical float64 keys) in HBM."""
 
@@ -209,6 +235,46 @@ class DeviceCorpus:
                 return out[:n_rows.value].cpu().numpy()
             cap = n_rows.value + n_rows.value // 4 + 64     # rows were upserted since stats(): retry with room
         raise RuntimeError("tvz_align: the table kept growing faster than the output was resized")
+
+    def align_topk(self, queries, *, eps: float, max_offset: float, k: int = 16, min_votes: int = 1,
+                   min_score: int = 0, exclude_ids=None, max_query_len: Optional[int] = None):
+        """tvz_align_topk: the k best-aligned rows of every query of a batch, kept inside the sweep.
+        `queries`: a list of timestamp lists, or device tensors (d_queries float64, d_q_offsets int64[Q+1]) as the
+        batched match calls take them; `exclude_ids`: None or one video id per query (list or device int32 tensor).
+        -> (rows int32[Q, k, 4] of (video_id, row_len, best_bin, votes), padded with (-1, 0, 0, 0); totals int32[Q] =
+        the true number of hits, ALIGN_REFUSED for a query longer than max_query_len - default: the longest query,
+        at most 4,095), as numpy arrays.  Order: align_order_key.  One device-to-host copy of Q x (k + 1) x 16 bytes."""
+        dev = torch.device("cuda", self.device)
+        if isinstance(queries, tuple) and len(queries) == 2 and torch.is_tensor(queries[0]):
+            d_q, d_off = queries
+            self._check_queries(d_q, d_off)
+            Q = d_off.numel() - 1
+            if max_query_len is None:
+                max_query_len = min(int((d_off[1:] - d_off[:-1]).max()) if Q else 0, ALIGN_TOPK_MAX_LEN)
+        else:
+            d_q, d_off, longest = pack_queries(queries, dev)
+            Q = len(queries)
+            if max_query_len is None:
+                max_query_len = min(longest, ALIGN_TOPK_MAX_LEN)
+        d_ex = None
+        if exclude_ids is not None:
+            d_ex = exclude_ids if torch.is_tensor(exclude_ids) else \
+                torch.as_tensor(np.asarray(exclude_ids, dtype=np.int32).reshape(-1)).to(dev)
+            if d_ex.dtype != torch.int32 or d_ex.numel() != Q or d_ex.device != dev:
+                raise RuntimeError(f"exclude_ids must be {Q} int32 values on {dev}")
+        out = torch.empty((Q, k + 1, 4), dtype=torch.int32, device=dev)
+        s = torch.cuda.current_stream(dev)
+        need = align_topk_workspace_bytes(Q, max_query_len, d_q.numel(), k)
+        # cached per calling thread (calls of several threads overlap); idle again when the copy below has returned
+        ws = getattr(self._tls, "align_ws", None)
+        if ws is None or ws.numel() < need:
+            ws = self._tls.align_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        _lib.check(self.lib.tvz_align_topk(
+            self._h, d_q.data_ptr(), d_off.data_ptr(), Q, int(max_query_len), float(eps), float(max_offset),
+            int(min_votes), int(min_score), d_ex.data_ptr() if d_ex is not None else None, int(k), out.data_ptr(),
+            ws.data_ptr(), ws.numel(), s.cuda_stream))
+        h = out.cpu().numpy()
+        return np.ascontiguousarray(h[:, :k]), np.ascontiguousarray(h[:, k, 1])
 
     # ---- batched, device resident ----
     def _check_queries(self, d_queries, d_q_offsets):

@@ -25,6 +25,7 @@
 #include "tvz_index_wave_kernels.h"
 #include "tvz_tol_kernels.h"
 #include "tvz_tol_index_kernels.h"
+#include "tvz_align_kernels.h"
 #include "tvz_handle.h"
 #include "tvz_index_build.h"
 
@@ -1974,6 +1975,96 @@ static int tvz_match_tol_topk_impl(tvz_corpus *c, const double *d_queries, const
                                     d_out, d_workspace, workspace_bytes, 1, hip_stream, nullptr, nullptr);
 }
 
+// ---- alignment top-k (tvz_align_kernels.h) ------------------------------------------------------------------
+namespace {
+
+// Workspace of tvz_align_topk, in front of the sorted queries (tvz_match_tol's layout, which takes the rest): the
+// queries' hit totals and one kept list - k words and k payloads - per sweep block.  The sizing function knows no row
+// count: the lists are sized by the grid's upper bound, as the tolerant top-k's are.
+struct AlignTopkWs {
+    int32_t *totals = nullptr;             // [Q]
+    unsigned long long *part_w = nullptr;  // [Q][blocks][k]
+    unsigned long long *part_p = nullptr;  // [Q][blocks][k]
+    unsigned char *rest = nullptr;         // the sorted queries
+    size_t fixed = 0;                      // bytes in front of `rest`, the base's alignment included
+};
+
+AlignTopkWs align_topk_ws_layout(void *base, int32_t Q, int32_t k) {
+    AlignTopkWs w;
+    const uintptr_t p0 = (reinterpret_cast<uintptr_t>(base) + 255) & ~(uintptr_t)255;
+    uintptr_t p = p0;
+    const size_t lists = al256((size_t)tol_topk_max_lists(Q) * (size_t)k * 8);
+    w.totals = reinterpret_cast<int32_t *>(p);
+    p += al256((size_t)Q * 4);
+    w.part_w = reinterpret_cast<unsigned long long *>(p);
+    p += lists;
+    w.part_p = reinterpret_cast<unsigned long long *>(p);
+    p += lists;
+    w.rest = reinterpret_cast<unsigned char *>(p);
+    w.fixed = (size_t)(p - p0) + 255;
+    return w;
+}
+
+size_t align_topk_ws_bytes(int32_t Q, int64_t keys, int32_t k) {
+    return align_topk_ws_layout(nullptr, Q, k).fixed + tol_ws_fixed(Q) + (size_t)keys * 12;
+}
+
+}  // namespace
+
+static int tvz_align_topk_impl(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
+                               int32_t max_query_len, double eps, double max_offset, int32_t min_votes,
+                               int32_t min_score, const int32_t *d_exclude_ids, int32_t k, int32_t *d_out,
+                               void *d_workspace, size_t workspace_bytes, void *hip_stream) {
+    if (int rc = check_batch_args(c, d_queries, d_q_offsets, Q, max_query_len, 0)) return rc;
+    TVZ_REQUIRE(eps > 0.0 && max_offset >= 0.0, "eps must be > 0 and max_offset >= 0");
+    const double nb = floor(max_offset / eps + 0.5);
+    if (!(2 * nb + 1 <= kAlignMaxBins))                 // also refuses NaN (eps = max_offset = inf)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "max_offset/eps = %.0f needs more than %d bins", nb, kAlignMaxBins);
+    TVZ_REQUIRE(min_votes >= 1, "alignment top-k: min_votes %d below 1", (int)min_votes);
+    TVZ_REQUIRE(min_score >= 0 && min_score <= kAlScoreOne, "alignment top-k: min_score %d outside 0..%d", (int)min_score,
+                kAlScoreOne);
+    if (k < 1 || k > kAlMaxK)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment top-k: k=%d outside 1..%d", (int)k, kAlMaxK);
+    if (max_query_len > kAlMaxLen)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment top-k: max_query_len %d above %d", (int)max_query_len, kAlMaxLen);
+    if (Q == 0) return TVZ_OK;
+    // the fixed parts and room for ONE query of max_query_len values; what the caller gave beyond that holds more
+    const size_t have = d_workspace ? workspace_bytes : 0;
+    const size_t least = align_topk_ws_bytes(Q, max_query_len, k);
+    if (have < least)
+        return tvz::fail(TVZ_ERR_WORKSPACE, "alignment top-k: workspace of %zu bytes, %zu bytes missing (size it with "
+                                            "tvz_align_topk_workspace_bytes)", have, least - have);
+    TVZ_REQUIRE(d_out != nullptr, "d_out is NULL");
+    const AlignTopkWs w = align_topk_ws_layout(d_workspace, Q, k);
+    const TolWs t = tol_ws_layout(w.rest, Q, tol_ws_room(Q, have - w.fixed));
+    const int32_t B = (int32_t)nb;
+    const int32_t lds_keys = std::max(max_query_len, 1);
+    const size_t lds = al_lds_bytes(lds_keys, B);
+    TVZ_REQUIRE(lds + kAlStaticLds <= (size_t)kLdsPerWorkgroup,
+                "alignment top-k sweep: %zu B of dynamic + %d B of static LDS exceed a gfx950 workgroup's", lds, kAlStaticLds);
+    DeviceGuard dg(c->device);
+    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+    // per query: sorted values (+ positions, unused here), counts, hit totals = 0
+    hipLaunchKernelGGL(ts_tol_sort_kernel, dim3((unsigned)tvz::ceil_div(lds_keys, kTolSortBlock), (unsigned)Q),
+                       dim3(kTolSortBlock), 0, st, d_queries, d_q_offsets, max_query_len, t.room, t.sv, t.sp, t.qm,
+                       w.totals);
+    TVZ_HIP(hipGetLastError());
+    std::shared_lock<std::shared_mutex> lk(c->mu);
+    const int64_t n_rows = (int64_t)c->h_rows.size();
+    if (int rc = wait_mutations(c, st)) return rc;
+    const int blocks = n_rows ? (int)std::min<int64_t>(tvz::ceil_div(n_rows, (int64_t)kAlWaves), tol_topk_max_blocks(Q)) : 0;
+    if (blocks) {
+        hipLaunchKernelGGL(ts_align_topk_kernel, dim3((unsigned)blocks, (unsigned)Q), dim3(kAlBlock), lds, st, c->rows.p,
+                           n_rows, c->keys.p, t.sv, d_q_offsets, t.qm, lds_keys, eps, B, min_votes, min_score,
+                           d_exclude_ids, k, w.part_w, w.part_p, blocks, w.totals);
+        TVZ_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(ts_align_topk_reduce_kernel, dim3((unsigned)Q), dim3(kAlReduceBlock), 0, st, w.part_w, w.part_p,
+                       blocks, k, t.qm, lds_keys, w.totals, d_out);
+    TVZ_HIP(hipGetLastError());
+    return record(c, st);
+}
+
 #ifdef TVZ_IX_STAMP
 // diagnostic build only: read (and clear) the per-phase cycle totals of ts_match_index_kernel
 TVZ_EXPORT int tvz_debug_ix_stamps(unsigned long long *out16) {
@@ -2117,6 +2208,20 @@ TVZ_EXPORT int tvz_align(tvz_corpus *c, const double *d_query, int32_t n, double
                          double max_offset, int32_t *d_out, int64_t out_rows, int64_t *n_rows,
                          void *hip_stream) {
     TVZ_GUARDED(tvz_align_impl(c, d_query, n, eps, max_offset, d_out, out_rows, n_rows, hip_stream));
+}
+
+TVZ_EXPORT size_t tvz_align_topk_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k) {
+    if (Q < 0 || max_query_len < 0 || total_query_keys < 0 || k < 1) return 0;
+    const int64_t keys = total_query_keys > 0 ? total_query_keys : (int64_t)Q * max_query_len;
+    return align_topk_ws_bytes(Q, std::max<int64_t>(keys, max_query_len), k);
+}
+
+TVZ_EXPORT int tvz_align_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
+                              int32_t max_query_len, double eps, double max_offset, int32_t min_votes,
+                              int32_t min_score, const int32_t *d_exclude_ids, int32_t k, int32_t *d_out,
+                              void *d_workspace, size_t workspace_bytes, void *hip_stream) {
+    TVZ_GUARDED(tvz_align_topk_impl(c, d_queries, d_q_offsets, Q, max_query_len, eps, max_offset, min_votes, min_score,
+                                    d_exclude_ids, k, d_out, d_workspace, workspace_bytes, hip_stream));
 }
 
 TVZ_EXPORT int tvz_find_duplicates_tol(tvz_corpus *c, const double *h_query, int64_t n, double tol, int32_t min_match,

@@ -83,8 +83,19 @@ class Inspector:
                  pts_policy: str = scene.PTS_POLICY_G6, batch: int = 256, max_workers: int = 16,
                  near_duplicates: bool = False, near_eps: float = 1.0 / 30, near_max_offset: float = 30.0,
                  near_jaccard: float = 0.8, slot_bytes: int = 64 << 20, n_slots: Optional[int] = None,
-                 profile: bool = False, match_tolerance: float = 0.0):
+                 profile: bool = False, match_tolerance: float = 0.0, near_top_k: Optional[int] = None):
         self.store = store
+        # opt-in: the near-duplicate report from the K best-aligned rows the device keeps (tvz_align_topk) instead of
+        # one row per corpus row walked here.  None: the walk, exactly as before.  Refused here where the store's
+        # corpus cannot do it.
+        self.near_top_k = None if near_top_k is None else int(near_top_k)
+        if self.near_top_k is not None:
+            if not 1 <= self.near_top_k <= 64:
+                raise ValueError(f"near_top_k must be None or 1..64, got {near_top_k!r}")
+            if not hasattr(getattr(store, "corpus", None), "align_topk"):
+                raise RuntimeError(f"near_top_k={self.near_top_k}: the store's corpus "
+                                   f"({type(getattr(store, 'corpus', None)).__name__}) has no align_topk; "
+                                   "use a DeviceCorpus or a service.ShardedCorpus")
         # opt-in, never the default: duplicates by the TOLERANT count (include/tvz.h tvz_find_duplicates_tol)
         # instead of the reference's exact float64 equality; the verdict, the truncation at kth and the stored
         # duplicates all follow it.  Refused here, before any upload, where the store's corpus cannot do it.
@@ -328,8 +339,7 @@ class Inspector:
         out = []
         if len(scene_timestamps) < 2:
             return out
-        for vid, row_len, best_bin, votes, _zero in self.store.corpus.align(
-                scene_timestamps, eps=self.near_eps, max_offset=self.near_max_offset):
+        for vid, row_len, best_bin, votes, *_zero in self._near_rows(video_id, scene_timestamps):
             if vid == video_id or row_len == 0:
                 continue
             # votes counts (query, row) pairs: cuts closer than eps can give more than either list holds
@@ -340,6 +350,20 @@ class Inspector:
                 out.append({"filename": v.filename if v else None, "video_id": int(vid),
                             "shift_seconds": float(best_bin) * self.near_eps, "jaccard": round(jacc, 4)})
         return sorted(out, key=lambda d: (-d["jaccard"], d["video_id"]))
+
+    def _near_rows(self, video_id: int, scene_timestamps):
+        """(video_id, row_len, best_bin, votes[, ...]) of the rows _near filters: every row of the table (near_top_k None), or
+        the near_top_k best-aligned ones, selected on the device with min_score = floor(near_jaccard x 2^20) - a
+        superset of the float filter, since v / u >= j implies floor(v 2^20 / u) >= floor(j 2^20)."""
+        corpus = self.store.corpus
+        if self.near_top_k is not None:
+            one = 1 << 20
+            min_score = max(0, min(one, int(self.near_jaccard * one)))          # int() floors: the value is >= 0
+            rows, totals = corpus.align_topk([scene_timestamps], eps=self.near_eps, max_offset=self.near_max_offset,
+                                             k=self.near_top_k, min_score=min_score, exclude_ids=[int(video_id)])
+            if int(totals[0]) >= 0:                                            # (refused: more than 4,095 cuts -> the walk)
+                return [r for r in rows[0] if r[0] >= 0]
+        return corpus.align(scene_timestamps, eps=self.near_eps, max_offset=self.near_max_offset)
 
     def _progress(self, analysis_key, scene_timestamps, frames_done, total_frames, dups_to_report):
         if total_frames > 0 and frames_done > 0:                           # app.py:259-260

@@ -250,6 +250,37 @@ class ShardedCorpus:
         return np.concatenate([s.align(timestamps, eps=eps, max_offset=max_offset) for s in self.shards]
                               + [np.zeros((0, 5), dtype=np.int32)])
 
+    def align_topk(self, queries, *, eps: float, max_offset: float, k: int = 16, min_votes: int = 1,
+                   min_score: int = 0, exclude_ids=None, max_query_len=None):
+        """DeviceCorpus.align_topk over every shard with the same k, the shards' blocks merged on the host by the
+        contract's order (at most n_shards x k rows per query).  Totals are summed; a query some shard refused stays
+        refused (ALIGN_REFUSED, all rows padding)."""
+        tc = self._tc
+        if isinstance(queries, tuple) and len(queries) == 2 and torch.is_tensor(queries[0]):
+            flat, off = queries[0].cpu().numpy(), queries[1].cpu().numpy()
+            nv = [int(np.count_nonzero(~np.isnan(flat[off[i]:off[i + 1]]))) for i in range(len(off) - 1)]
+        else:
+            queries = [np.asarray(q, dtype=np.float64).reshape(-1) for q in queries]
+            nv = [int(np.count_nonzero(~np.isnan(q))) for q in queries]
+            if max_query_len is None:
+                max_query_len = min(max((q.size for q in queries), default=0), tc.ALIGN_TOPK_MAX_LEN)
+        parts = [s.align_topk(queries, eps=eps, max_offset=max_offset, k=k, min_votes=min_votes, min_score=min_score,
+                              exclude_ids=exclude_ids, max_query_len=max_query_len) for s in self.shards]
+        Q = len(nv)
+        rows = np.zeros((Q, k, 4), dtype=np.int32)
+        rows[:, :, 0] = -1
+        totals = np.zeros(Q, dtype=np.int32)
+        for q in range(Q):
+            if any(int(t[q]) < 0 for _, t in parts):
+                totals[q] = tc.ALIGN_REFUSED
+                continue
+            totals[q] = sum(int(t[q]) for _, t in parts)
+            best = sorted((r for b, _ in parts for r in b[q].tolist() if r[0] >= 0),
+                          key=lambda r: tc.align_order_key(r, nv[q]))[:k]
+            if best:
+                rows[q, :len(best)] = best
+        return rows, totals
+
     # ---- matches ----
     supports_tolerance = True             # tolerant asks go to every shard in turn (inspector.Inspector checks)
 
