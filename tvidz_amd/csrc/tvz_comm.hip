@@ -164,14 +164,13 @@ static int tvz_match_sharded_impl(tvz_corpus *c, tvz_comm *comm, const double *d
     TVZ_REQUIRE(comm != nullptr && comm->comm != nullptr, "communicator is NULL");
     TVZ_REQUIRE(Q == 0 || d_topk != nullptr, "d_topk is NULL");
     if (Q == 0) return TVZ_OK;
-    int32_t *gathered = nullptr;
+    ShardBlocks blk;
     // local sweep + per-shard top-k into the workspace's own block
-    if (int rc = tvz_match_topk_local(c, d_queries, d_q_offsets, Q, max_query_len, min_match,
-                                      d_exclude_ids, cap, k, nullptr, d_workspace, workspace_bytes,
-                                      comm->n_ranks, algo, hip_stream, &gathered))
+    if (int rc = tvz_match_topk_local(c, Batch{d_queries, d_q_offsets, Q, max_query_len, min_match, d_exclude_ids}, cap, k,
+                                      nullptr, Workspace{d_workspace, workspace_bytes}, comm->n_ranks, algo, hip_stream,
+                                      &blk))
         return rc;
-    const int32_t *local = tvz_ws_local_block(d_workspace, Q, max_query_len, cap, k, comm->n_ranks);
-    return gather_and_merge(comm, local, gathered, Q, k, d_topk, d_totals, hip_stream);
+    return gather_and_merge(comm, blk.local, blk.gathered, Q, k, d_topk, d_totals, hip_stream);
 }
 
 static int tvz_match_tol_sharded_impl(tvz_corpus *c, tvz_comm *comm, const double *d_queries,
@@ -181,14 +180,14 @@ static int tvz_match_tol_sharded_impl(tvz_corpus *c, tvz_comm *comm, const doubl
                                       void *hip_stream) {
     TVZ_REQUIRE(comm != nullptr && comm->comm != nullptr, "communicator is NULL");
     TVZ_REQUIRE(Q <= 0 || d_topk != nullptr, "d_topk is NULL");
-    int32_t *local = nullptr, *gathered = nullptr;
+    ShardBlocks blk;
     // the tolerant sweep keeps its k best itself and writes them into the workspace's own block
-    if (int rc = tvz_match_tol_topk_local(c, d_queries, d_q_offsets, Q, max_query_len, tol, min_match, d_exclude_ids,
-                                          k, nullptr, d_workspace, workspace_bytes, comm->n_ranks, hip_stream, &local,
-                                          &gathered))
+    if (int rc = tvz_match_tol_topk_local(c, Batch{d_queries, d_q_offsets, Q, max_query_len, min_match, d_exclude_ids}, tol,
+                                          k, nullptr, Workspace{d_workspace, workspace_bytes}, comm->n_ranks, hip_stream,
+                                          &blk))
         return rc;
     if (Q == 0) return TVZ_OK;
-    return gather_and_merge(comm, local, gathered, Q, k, d_topk, d_totals, hip_stream);
+    return gather_and_merge(comm, blk.local, blk.gathered, Q, k, d_topk, d_totals, hip_stream);
 }
 
 TVZ_EXPORT int tvz_comm_unique_id(void *out_id) { TVZ_GUARDED(tvz_comm_unique_id_impl(out_id)); }

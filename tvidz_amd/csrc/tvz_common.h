@@ -65,18 +65,26 @@ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 }  // namespace tvz
 
-// Internal (not exported): local sweep + per-shard top-k with the hit lists in the workspace
-// (tvz_match.hip); d_out = NULL writes the block into the workspace's own [Q][k+1][3] area.
-int tvz_match_topk_local(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets,
-                         int32_t Q, int32_t max_query_len, int32_t min_match,
-                         const int32_t *d_exclude_ids, int32_t cap, int32_t k, int32_t *d_out,
-                         void *d_workspace, size_t workspace_bytes, int32_t n_ranks, int32_t algo,
-                         void *hip_stream, int32_t **gathered_out);
-int32_t *tvz_ws_local_block(void *d_workspace, int32_t Q, int32_t max_query_len, int32_t cap,
-                            int32_t k, int32_t n_ranks);
-// The tolerant counterpart (tvz_match.hip): the sweep keeps the k best itself; *local_out = where the block went
-// (d_out, or the workspace's own area for d_out = NULL), *gathered_out = the workspace's [n_ranks][Q][k+1][3].
-int tvz_match_tol_topk_local(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
-                             int32_t max_query_len, double tol, int32_t min_match, const int32_t *d_exclude_ids,
-                             int32_t k, int32_t *d_out, void *d_workspace, size_t workspace_bytes, int32_t n_ranks,
-                             void *hip_stream, int32_t **local_out, int32_t **gathered_out);
+// What the batched calls pass around between the C ABI and the launches: plain aggregates, no behaviour.
+struct Batch {                       // the queries of one call
+    const double *d_queries;
+    const int64_t *d_q_offsets;
+    int32_t Q, max_query_len, min_match;
+    const int32_t *d_exclude_ids;
+};
+struct Workspace {                   // the caller's scratch
+    void *p;
+    size_t bytes;
+};
+struct ShardBlocks {                 // where a local top-k left its block, and the all-gather's target next to it
+    int32_t *local = nullptr;        // int32[Q][k+1][3]: d_out, or the workspace's own area for d_out = NULL
+    int32_t *gathered = nullptr;     // int32[n_ranks][Q][k+1][3] in the workspace
+};
+
+// Internal (not exported): local sweep + per-shard top-k with the hit lists in the workspace (tvz_match.hip);
+// `blocks` (may be NULL) is told where the block went.
+int tvz_match_topk_local(tvz_corpus *c, const Batch &b, int32_t cap, int32_t k, int32_t *d_out, Workspace ws,
+                         int32_t n_ranks, int32_t algo, void *hip_stream, ShardBlocks *blocks);
+// The tolerant counterpart (tvz_match.hip): the sweep keeps the k best itself.
+int tvz_match_tol_topk_local(tvz_corpus *c, const Batch &b, double tol, int32_t k, int32_t *d_out, Workspace ws,
+                             int32_t n_ranks, void *hip_stream, ShardBlocks *blocks);

@@ -18,6 +18,7 @@
 // Kernels: tvz_match_kernels.h; the handle: tvz_handle.h; its index build: tvz_index_build.h.  No process-global
 // mutable state: the sweep algorithm is a per-call argument and scratch is the caller's workspace.
 #include <cfloat>
+#include <optional>
 #include <type_traits>
 
 #include "tvz_match_kernels.h"
@@ -161,6 +162,34 @@ int reserve_locked(tvz_corpus *c, int64_t n_rows, int64_t n_keys) {
     return TVZ_OK;
 }
 
+// ---- what a batched call hands to its launches (next to the Batch of tvz_common.h) ------------
+// Plain aggregates.  `exclude_one`, the single-query exclusion, is no batch property: it stays an argument by name.
+struct HitSink {                     // where the hits of the queries go
+    int32_t cap;                     // hits a query's list holds
+    int32_t *d_hits;                 // [Q][cap][3]
+    int32_t *d_hits_n;               // [Q] counters, `ns` int32 apart
+    int32_t ns;
+    // the caller's dense counters / the workspace's one-counter-per-line scratch
+    static HitSink dense(int32_t cap, int32_t *d_hits, int32_t *d_hits_n) { return {cap, d_hits, d_hits_n, 1}; }
+    static HitSink per_line(int32_t cap, int32_t *d_hits, int32_t *counters) { return {cap, d_hits, counters, kCountStride}; }
+};
+struct JoinScratch {                 // the hash join's tables and, where the batch may hold long queries, their tail
+    unsigned char *ws = nullptr;
+    size_t ws_bytes = 0;
+    unsigned char *lq = nullptr;
+    size_t lq_bytes = 0;
+};
+struct TolSorted {                   // the tolerant calls' queries as ts_tol_sort_kernel (or the host) left them
+    const double *sv;                // sorted values
+    const int32_t *sp;               // their positions in the query
+    const int32_t *qm;               // [Q] values per query; NULL: one query of m_one values
+    int32_t m_one;
+    int32_t lds_keys;                // > 0: every query has at most this many values, they go to LDS
+    double tol;
+};
+const QByVal kNoQuery = {};          // a launch whose query does not travel in the kernel arguments
+const HitSink kHostSink = HitSink::dense(0, nullptr, nullptr);   // ... whose hits go to pinned host memory (HostOut)
+
 // ---- workspace layout of the batched calls -------------------------------------------------
 struct JoinShape {
     int n_tiles = 0;
@@ -184,6 +213,41 @@ JoinShape join_shape(int32_t Q, int32_t max_query_len) {
     return j;
 }
 
+// ---- the one carver of every workspace layout ----
+// Walks a caller's buffer: the base is aligned up to 256 once, then take<T>(count) hands out regions, each rounded to 256
+// bytes.  used() is what the regions occupy from the aligned base on; walked from NULL that is what a sizing function
+// starts from.  The caller's base need not be aligned, so every size adds slack for it - in one of three ways, all of
+// them part of the ABI (callers size buffers with the answers):
+//   + 256          WsLayout::total: a whole line for the base.
+//   + 255          the `fixed` of a front part (TolFront): the most the base's alignment can cost.
+//   256 + 2 * 255  kTolWsSlack, tol_ws_bytes: a line for the base and, since the sorted queries take whatever is left
+//                  (tol_ws_room divides it by TolWs::kPerKey), the most the roundings of their two regions can cost.
+// The slack of a front part and that of the TolWs behind it simply add up (tvz_match_tol_topk_workspace_bytes).
+size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+struct Carver {
+    const unsigned char *base;
+    uintptr_t p0, p;
+    explicit Carver(const void *b) : base(static_cast<const unsigned char *>(b)), p0(al256(reinterpret_cast<uintptr_t>(b))), p(p0) {}
+    template <typename T>
+    T *take(size_t count) {
+        T *r = reinterpret_cast<T *>(p);
+        p += al256(count * sizeof(T));
+        return r;
+    }
+    size_t used() const { return (size_t)(p - p0); }
+    size_t fixed() const { return used() + 255; }       // as a front part: what it costs a caller's buffer at most
+    // of a buffer of `bytes` at the base: what lies behind the regions taken so far
+    size_t left(size_t bytes) const {
+        const uintptr_t end = reinterpret_cast<uintptr_t>(base) + bytes;
+        return end > p ? (size_t)(end - p) : 0;
+    }
+};
+
+// scratch the long queries of a batch need (ts_longq_sort_kernel): per query of n keys a power-of-two sort buffer
+// (< 2 n x 8 B), n + 1 distinct keys (8 B) and multiplicities (4 B), a counter; T = keys of all long queries, L = how many
+inline size_t longq_bytes_bound(int64_t T, int64_t L) { return (size_t)(28 * T + 64 * L + 512); }
+
 struct WsLayout {
     unsigned char *join = nullptr;  size_t join_bytes = 0;
     int32_t *counters = nullptr;    // [Q] one per 128-byte line
@@ -194,56 +258,40 @@ struct WsLayout {
     int32_t *flags = nullptr;       // [Q] queries the one-wave top-k left to the block kernels
     int32_t *pair = nullptr;        // [2][Q][k+1][3] fused lookup: the index's block + the delta sweep's, merged into `local`
     unsigned char *longq = nullptr; // scratch of the batch's long queries (> 4,095 timestamps): LAST, so that a larger
-    size_t total = 0;               //   workspace (tvz_match_workspace_bytes_long) simply has more of it
-    // the long queries' scratch in the caller's workspace of `bytes` at `base`: its whole tail from `longq` on
-    size_t longq_bytes(const void *base, size_t bytes) const {
-        return longq ? (size_t)(static_cast<const unsigned char *>(base) + bytes - longq) : 0;
-    }
+    size_t longq_bytes = 0;         //   workspace (tvz_match_workspace_bytes_long) simply has more of it: its whole tail
+    size_t total = 0;
+    HitSink sink(int32_t cap) const { return HitSink::per_line(cap, hits, counters); }
+    JoinScratch scratch() const { return {join, join_bytes, longq, longq_bytes}; }
 };
 
-// scratch the long queries of a batch need (ts_longq_sort_kernel): per query of n keys a power-of-two sort buffer
-// (< 2 n x 8 B), n + 1 distinct keys (8 B) and multiplicities (4 B), a counter; T = keys of all long queries, L = how many
-inline size_t longq_bytes_bound(int64_t T, int64_t L) { return (size_t)(28 * T + 64 * L + 512); }
-
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-WsLayout ws_layout(void *base, int32_t Q, int32_t max_query_len, int32_t cap, int32_t k,
-                   int32_t n_ranks, int64_t total_query_keys = 0) {
+// the layout in a workspace of `bytes` at `base`; from NULL: its size
+WsLayout ws_layout(void *base, size_t bytes, int32_t Q, int32_t max_query_len, int32_t cap, int32_t k, int32_t n_ranks,
+                   int64_t total_query_keys = 0) {
     WsLayout w;
-    uintptr_t p = (reinterpret_cast<uintptr_t>(base) + 255) & ~(uintptr_t)255;
-    const uintptr_t p0 = p;
+    Carver cv(base);
     const int32_t true_max_len = max_query_len;
     if (max_query_len > kMaxQueryLen) max_query_len = kMaxQueryLen;   // longer queries do not use the tables
     w.join_bytes = join_shape(Q, max_query_len).bytes();
-    w.join = reinterpret_cast<unsigned char *>(p);
-    p += al256(w.join_bytes);
-    w.counters = reinterpret_cast<int32_t *>(p);
-    p += al256((size_t)Q * kCountStride * 4);
+    w.join = cv.take<unsigned char>(w.join_bytes);
+    w.counters = cv.take<int32_t>((size_t)Q * kCountStride);
     if (k > 0) {
-        w.hits = reinterpret_cast<int32_t *>(p);
-        p += al256((size_t)Q * (size_t)cap * 12);
-        w.hits_n = reinterpret_cast<int32_t *>(p);
-        p += al256((size_t)Q * 4);
-        w.local = reinterpret_cast<int32_t *>(p);
-        p += al256((size_t)Q * (size_t)(k + 1) * 12);
-        w.gathered = reinterpret_cast<int32_t *>(p);
-        p += al256((size_t)(n_ranks > 1 ? n_ranks : 1) * (size_t)Q * (size_t)(k + 1) * 12);
-        w.flags = reinterpret_cast<int32_t *>(p);
-        p += al256((size_t)Q * 4);
-        if (k <= kIxTkMaxK) {
-            w.pair = reinterpret_cast<int32_t *>(p);
-            p += al256((size_t)2 * (size_t)Q * (size_t)(k + 1) * 12);
-        }
+        const size_t block = (size_t)Q * (size_t)(k + 1) * 3;
+        w.hits = cv.take<int32_t>((size_t)Q * (size_t)cap * 3);
+        w.hits_n = cv.take<int32_t>((size_t)Q);
+        w.local = cv.take<int32_t>(block);
+        w.gathered = cv.take<int32_t>((size_t)(n_ranks > 1 ? n_ranks : 1) * block);
+        w.flags = cv.take<int32_t>((size_t)Q);
+        if (k <= kIxTkMaxK) w.pair = cv.take<int32_t>(2 * block);
     }
     if (true_max_len > kMaxQueryLen) {
         // without the batch's key count: room for ONE query of max_query_len keys (tvz_match_workspace_bytes);
         // with it (tvz_match_workspace_bytes_long): for any split of the keys into long queries
         const int64_t T = total_query_keys > 0 ? total_query_keys : (int64_t)true_max_len;
         const int64_t L = std::min<int64_t>(Q > 0 ? Q : 1, T / (kMaxQueryLen + 1) + 1);
-        w.longq = reinterpret_cast<unsigned char *>(p);
-        p += al256(longq_bytes_bound(T, L));
+        w.longq_bytes = cv.left(bytes);
+        w.longq = cv.take<unsigned char>(longq_bytes_bound(T, L));
     }
-    w.total = (size_t)(p - p0) + 256;
+    w.total = cv.used() + 256;
     return w;
 }
 
@@ -274,6 +322,12 @@ int pick_algo(int32_t algo, int32_t Q, int64_t n_rows, int32_t max_query_len, in
     return algo;
 }
 
+// the status of the launch just enqueued
+int launched() {
+    TVZ_HIP(hipGetLastError());
+    return TVZ_OK;
+}
+
 int launch_prep(int32_t *d_hits_n, int32_t ns, int32_t Q, void *ones, size_t ones_bytes, void *zeros,
                 size_t zero_bytes, hipStream_t st) {
     const size_t work = std::max<size_t>((size_t)Q, std::max(ones_bytes, zero_bytes) / 16);
@@ -281,8 +335,12 @@ int launch_prep(int32_t *d_hits_n, int32_t ns, int32_t Q, void *ones, size_t one
     hipLaunchKernelGGL(ts_prep_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, d_hits_n, ns, Q,
                        reinterpret_cast<uint4 *>(ones), ones_bytes / 16,
                        reinterpret_cast<uint4 *>(zeros), zero_bytes / 16);
-    TVZ_HIP(hipGetLastError());
-    return TVZ_OK;
+    return launched();
+}
+
+// hit counters of Q queries = 0
+int zero_counts(const HitSink &out, int32_t Q, hipStream_t st) {
+    return launch_prep(out.d_hits_n, out.ns, Q, nullptr, 0, nullptr, 0, st);
 }
 
 // The rows a sweep reads: the whole row table, or the delta table of an indexed corpus.
@@ -291,20 +349,18 @@ struct RowSpan {
     int64_t n;
 };
 
-int launch_join(tvz_corpus *c, RowSpan span, bool zero_counts, const double *d_queries,
-                const int64_t *d_q_offsets, int32_t Q, int32_t max_query_len, int32_t min_match,
-                const int32_t *d_exclude_ids, int32_t cap, int32_t *d_hits, int32_t *d_hits_n, int32_t ns,
-                unsigned char *ws, size_t ws_bytes, hipStream_t st) {
+int launch_join(tvz_corpus *c, RowSpan span, bool zero, const Batch &b, const HitSink &out, const JoinScratch &scratch,
+                hipStream_t st) {
     const int64_t n_rows = span.n;
-    const JoinShape j = join_shape(Q, max_query_len);
-    if (ws == nullptr || ws_bytes < j.bytes())
+    const JoinShape j = join_shape(b.Q, b.max_query_len);
+    if (scratch.ws == nullptr || scratch.ws_bytes < j.bytes())
         return tvz::fail(TVZ_ERR_WORKSPACE, "hash join needs a workspace of %zu bytes (got %zu): size it "
-                                            "with tvz_match_workspace_bytes", j.bytes(), ws_bytes);
-    uint32_t *table = reinterpret_cast<uint32_t *>(ws);
+                                            "with tvz_match_workspace_bytes", j.bytes(), scratch.ws_bytes);
+    uint32_t *table = reinterpret_cast<uint32_t *>(scratch.ws);
     // one launch: hit counters = 0, every table slot = free
-    if (int rc = launch_prep(d_hits_n, ns, zero_counts ? Q : 0, table, j.bytes(), nullptr, 0, st)) return rc;
-    hipLaunchKernelGGL(ts_join_build_kernel, dim3((unsigned)tvz::ceil_div(Q, kBlock / 64)), dim3(kBlock), 0, st, d_queries, d_q_offsets, Q, max_query_len, j.q_per_tile, j.s_log2,
-                       table, d_hits_n, ns);
+    if (int rc = launch_prep(out.d_hits_n, out.ns, zero ? b.Q : 0, table, j.bytes(), nullptr, 0, st)) return rc;
+    hipLaunchKernelGGL(ts_join_build_kernel, dim3((unsigned)tvz::ceil_div(b.Q, kBlock / 64)), dim3(kBlock), 0, st,
+                       b.d_queries, b.d_q_offsets, b.Q, b.max_query_len, j.q_per_tile, j.s_log2, table, out.d_hits_n, out.ns);
     TVZ_HIP(hipGetLastError());
     // ONE launch per tile, each filling the chip (two 16-wave blocks per CU): tiles that ran side by
     // side (a 2-D grid) had their 2 MiB tables compete for the same 4 MiB of L2 - 4 tiles cost
@@ -314,16 +370,10 @@ int launch_join(tvz_corpus *c, RowSpan span, bool zero_counts, const double *d_q
     const int64_t chunks = std::max<int64_t>(1, std::min<int64_t>(512, tvz::ceil_div(n_rows, kJoinWaves)));
     for (int t = 0; t < j.n_tiles; ++t) {
         hipLaunchKernelGGL(ts_match_join_kernel, dim3((unsigned)chunks), dim3(kJoinBlock), kJoinLds, st, span.p,
-                           n_rows, c->keys.p, d_queries, d_q_offsets, table, j.s_log2, Q, j.q_per_tile, t,
-                           min_match, d_exclude_ids, cap, d_hits, d_hits_n, ns);
+                           n_rows, c->keys.p, b.d_queries, b.d_q_offsets, table, j.s_log2, b.Q, j.q_per_tile, t,
+                           b.min_match, b.d_exclude_ids, out.cap, out.d_hits, out.d_hits_n, out.ns);
         TVZ_HIP(hipGetLastError());
     }
-    return TVZ_OK;
-}
-
-// the status of the launch just enqueued
-int launched() {
-    TVZ_HIP(hipGetLastError());
     return TVZ_OK;
 }
 
@@ -340,14 +390,11 @@ int by_mode(int32_t min_match, Launch &&launch) {
 }
 
 template <bool HOSTOUT>
-int launch_q1(tvz_corpus *c, RowSpan span, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
-              int32_t max_query_len, int32_t min_match, const int32_t *d_exclude_ids,
-              int32_t exclude_one, int32_t cap, int32_t *d_hits, int32_t *d_hits_n, int32_t ns,
-              int blocks_x, HostOut ho, hipStream_t st, const QByVal *byval = nullptr) {
-    static const QByVal kNoQuery = {};
+int launch_q1(tvz_corpus *c, RowSpan span, const Batch &b, int32_t exclude_one, const HitSink &out, int blocks_x,
+              HostOut ho, hipStream_t st, const QByVal *byval = nullptr) {
     const QByVal &qv = byval ? *byval : kNoQuery;
     const int64_t n_rows = span.n;
-    const int s_log2 = q1_slots_log2(max_query_len);
+    const int s_log2 = q1_slots_log2(b.max_query_len);
     const size_t lds = q1_lds_bytes(s_log2);
     // The launch limit, named: a workgroup gets at most 160 KiB of LDS on gfx950, and this
     // kernel's request is dynamic (query table + Bloom words, up to 112 KiB at 4095 timestamps) PLUS static
@@ -359,17 +406,16 @@ int launch_q1(tvz_corpus *c, RowSpan span, const double *d_queries, const int64_
     TVZ_REQUIRE(lds + kQ1StaticLds <= (size_t)kLdsPerWorkgroup,
                 "single-query sweep: %zu B of dynamic + %d B of static LDS exceed the %d B a gfx950 workgroup can have",
                 lds, kQ1StaticLds, kLdsPerWorkgroup);
-    const dim3 grid((unsigned)blocks_x, (unsigned)Q);
-    return by_mode(min_match, [&](auto mode) {
+    const dim3 grid((unsigned)blocks_x, (unsigned)b.Q);
+    return by_mode(b.min_match, [&](auto mode) {
         hipLaunchKernelGGL((ts_match_q1_kernel<mode.value, HOSTOUT>), grid, dim3(kQ1Block), lds, st, span.p, n_rows,
-                           c->keys.p, d_queries, d_q_offsets, min_match, d_exclude_ids, exclude_one, cap, d_hits,
-                           d_hits_n, ns, s_log2, ho, qv);
+                           c->keys.p, b.d_queries, b.d_q_offsets, b.min_match, b.d_exclude_ids, exclude_one, out.cap,
+                           out.d_hits, out.d_hits_n, out.ns, s_log2, ho, qv);
         return launched();
     });
 }
 
 int q1_blocks(int64_t n_rows, int32_t Q) {
-
     // every row group gets >= 1 row; about 8 blocks per CU in total over the Q block columns
     int64_t b = tvz::ceil_div(n_rows, kQ1Groups);
     const int64_t per_q = std::max<int64_t>(256, kQ1MaxBlocks / std::max(1, Q));
@@ -377,28 +423,29 @@ int q1_blocks(int64_t n_rows, int32_t Q) {
     return (int)b;
 }
 
+// min_match > 5: the hits left with kth = -2 - row (a row of `rows`) are resolved by a walk of the row
+int launch_kth_fixup(tvz_corpus *c, const Row *rows, const Batch &b, const HitSink &out, hipStream_t st) {
+    hipLaunchKernelGGL(ts_kth_fixup_kernel, dim3((unsigned)b.Q), dim3(kBlock), 0, st, rows, c->keys.p, b.d_queries,
+                       b.d_q_offsets, b.min_match, out.cap, out.d_hits, out.d_hits_n, out.ns);
+    return launched();
+}
+
 // one sweep of `span` with a resolved scan algorithm (Q1 / TILE / JOIN); appends to the hit lists
-int launch_scan(tvz_corpus *c, RowSpan span, int a, bool zero_counts, const double *d_queries,
-                const int64_t *d_q_offsets, int32_t Q, int32_t max_query_len, int32_t min_match,
-                const int32_t *d_exclude_ids, int32_t cap, int32_t *d_hits, int32_t *d_hits_n, int32_t ns,
-                unsigned char *ws, size_t ws_bytes, hipStream_t st) {
+int launch_scan(tvz_corpus *c, RowSpan span, int a, bool zero, const Batch &b, const HitSink &out,
+                const JoinScratch &scratch, hipStream_t st) {
     const int64_t n_rows = span.n;
-    if (zero_counts && (n_rows == 0 || a != TVZ_ALGO_JOIN))
-        if (int rc = launch_prep(d_hits_n, ns, Q, nullptr, 0, nullptr, 0, st)) return rc;
-    if (n_rows == 0 || Q == 0) return TVZ_OK;
-    if (a == TVZ_ALGO_JOIN)
-        return launch_join(c, span, zero_counts, d_queries, d_q_offsets, Q, max_query_len, min_match,
-                           d_exclude_ids, cap, d_hits, d_hits_n, ns, ws, ws_bytes, st);
+    if (zero && (n_rows == 0 || a != TVZ_ALGO_JOIN))
+        if (int rc = zero_counts(out, b.Q, st)) return rc;
+    if (n_rows == 0 || b.Q == 0) return TVZ_OK;
+    if (a == TVZ_ALGO_JOIN) return launch_join(c, span, zero, b, out, scratch, st);
     if (a == TVZ_ALGO_Q1) {
-        if (int rc = launch_q1<false>(c, span, d_queries, d_q_offsets, Q, max_query_len, min_match,
-                                      d_exclude_ids, -1, cap, d_hits, d_hits_n, ns, q1_blocks(n_rows, Q),
-                                      HostOut{nullptr, nullptr, 0}, st))
+        if (int rc = launch_q1<false>(c, span, b, /* exclude_one */ -1, out, q1_blocks(n_rows, b.Q), HostOut{nullptr, nullptr, 0}, st))
             return rc;
     } else {
         // queries per tile: as many as keep the shared table at load <= 0.5 (at most 16)
-        int nq = max_query_len > 0 ? kTileMaxEntries / max_query_len : kTileQ;
+        int nq = b.max_query_len > 0 ? kTileMaxEntries / b.max_query_len : kTileQ;
         nq = std::max(1, std::min(nq, kTileQ));
-        const int64_t tiles = tvz::ceil_div(Q, nq);
+        const int64_t tiles = tvz::ceil_div(b.Q, nq);
         // one 1024-thread block per CU (LDS): aim at just under two full rounds of 256 blocks (a
         // third, mostly empty round costs a whole block time), but >= 2 rows per 16-lane group so
         // that building the tile's table (per block) stays a small part of the block's life
@@ -408,23 +455,13 @@ int launch_scan(tvz_corpus *c, RowSpan span, int a, bool zero_counts, const doub
         chunks = tvz::ceil_div(n_rows, rpb);
         if (tiles > 65535)
             return tvz::fail(TVZ_ERR_UNSUPPORTED, "too many query tiles (%lld)", (long long)tiles);
-        if (min_match <= 2)
-            hipLaunchKernelGGL(ts_match_tile_kernel<false>, dim3((unsigned)chunks, (unsigned)tiles),
-                               dim3(kTileBlock), kTileLds, st, span.p, n_rows, c->keys.p, d_queries,
-                               d_q_offsets, Q, nq, min_match, d_exclude_ids, cap, d_hits, d_hits_n, ns,
-                               (int32_t)rpb);
-        else
-            hipLaunchKernelGGL(ts_match_tile_kernel<true>, dim3((unsigned)chunks, (unsigned)tiles),
-                               dim3(kTileBlock), kTileLds, st, span.p, n_rows, c->keys.p, d_queries,
-                               d_q_offsets, Q, nq, min_match, d_exclude_ids, cap, d_hits, d_hits_n, ns,
-                               (int32_t)rpb);
+        auto tile = b.min_match <= 2 ? ts_match_tile_kernel<false> : ts_match_tile_kernel<true>;
+        hipLaunchKernelGGL(tile, dim3((unsigned)chunks, (unsigned)tiles), dim3(kTileBlock), kTileLds, st, span.p, n_rows,
+                           c->keys.p, b.d_queries, b.d_q_offsets, b.Q, nq, b.min_match, b.d_exclude_ids, out.cap, out.d_hits,
+                           out.d_hits_n, out.ns, (int32_t)rpb);
         TVZ_HIP(hipGetLastError());
     }
-    if (min_match > kTop) {
-        hipLaunchKernelGGL(ts_kth_fixup_kernel, dim3((unsigned)Q), dim3(kBlock), 0, st, span.p,
-                           c->keys.p, d_queries, d_q_offsets, min_match, cap, d_hits, d_hits_n, ns);
-        TVZ_HIP(hipGetLastError());
-    }
+    if (b.min_match > kTop) return launch_kth_fixup(c, span.p, b, out, st);
     return TVZ_OK;
 }
 
@@ -451,32 +488,26 @@ int index_subs_per_block(int32_t Q, int n_sub, int32_t max_query_len, bool hosto
 // Callers check index_usable first: min_match >= 1, so min_match > 5 is the only count-only case (the
 // kth fix-up below), and HOSTOUT (tvz_find_duplicates) only ever sees 1..5.
 template <bool HOSTOUT>
-int launch_index(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
-                 int32_t max_query_len, int32_t min_match, const int32_t *d_exclude_ids, int32_t exclude_one,
-                 int32_t cap, int32_t *d_hits, int32_t *d_hits_n, int32_t ns, hipStream_t st,
+int launch_index(tvz_corpus *c, const Batch &b, int32_t exclude_one, const HitSink &out, hipStream_t st,
                  const QByVal *byval = nullptr) {
-    static const QByVal kNoQuery = {};
     const IndexBuf &ix = c->ix.now();
-    const int spb = index_subs_per_block(Q, ix.n_sub, max_query_len, HOSTOUT);
+    const int spb = index_subs_per_block(b.Q, ix.n_sub, b.max_query_len, HOSTOUT);
     const int groups = (int)tvz::ceil_div(ix.n_sub, spb);
     if (!HOSTOUT && groups > 1)
-        if (int rc = launch_prep(d_hits_n, ns, Q, nullptr, 0, nullptr, 0, st)) return rc;
-    const size_t lds = ix_lds_bytes(max_query_len, spb);
-    if (int rc = by_mode<!HOSTOUT>(min_match, [&](auto mode) {
-            hipLaunchKernelGGL((ts_match_index_kernel<HOSTOUT, mode.value>), dim3((unsigned)Q, (unsigned)groups),
+        if (int rc = zero_counts(out, b.Q, st)) return rc;
+    const size_t lds = ix_lds_bytes(b.max_query_len, spb);
+    if (int rc = by_mode<!HOSTOUT>(b.min_match, [&](auto mode) {
+            hipLaunchKernelGGL((ts_match_index_kernel<HOSTOUT, mode.value>), dim3((unsigned)b.Q, (unsigned)groups),
                                dim3(kIxBlock), lds, st, ix.keys.dir.p, ix.keys.bits(), ix.keys.ks, ix.keys.post_ptr(), ix.ivid.p,
-                               ix.n_main, ix.n_sub, spb, d_queries, d_q_offsets, max_query_len, min_match,
-                               d_exclude_ids, exclude_one, cap, d_hits, d_hits_n, ns, byval ? *byval : kNoQuery);
+                               ix.n_main, ix.n_sub, spb, b.d_queries, b.d_q_offsets, b.max_query_len, b.min_match,
+                               b.d_exclude_ids, exclude_one, out.cap, out.d_hits, out.d_hits_n, out.ns,
+                               byval ? *byval : kNoQuery);
             return launched();
         }))
         return rc;
-    if (!HOSTOUT && min_match > kTop) {
-        // the hits left with kth = -2 - row (a row of the MAIN table: unchanged since the build, or it
-        // would be dead in the index); resolved here, before a delta sweep appends codes of its own table
-        hipLaunchKernelGGL(ts_kth_fixup_kernel, dim3((unsigned)Q), dim3(kBlock), 0, st, c->rows.p, c->keys.p,
-                           d_queries, d_q_offsets, min_match, cap, d_hits, d_hits_n, ns);
-        TVZ_HIP(hipGetLastError());
-    }
+    // (the fix-up's rows are of the MAIN table: unchanged since the build, or they would be dead in the index; it runs
+    // here, before a delta sweep appends codes of its own table)
+    if (!HOSTOUT && b.min_match > kTop) return launch_kth_fixup(c, c->rows.p, b, out, st);
     return TVZ_OK;
 }
 
@@ -503,18 +534,18 @@ bool wave_usable(const tvz_corpus *c, int32_t max_query_len, int32_t min_match, 
 // (A separate probe pass in front of this kernel - every directory probe of the batch in one launch, the
 // lookup blocks starting from coalesced records - was measured in round 4 and lost: the lookup got 10.7 us
 // faster on a 1/8 shard, the probe pass cost 27 us: profiles/r4_probe_prepass.txt.)
-int launch_index_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
-                      int32_t max_query_len, int32_t min_match, const int32_t *d_exclude_ids, int32_t cap,
-                      int32_t k, int32_t *d_block, bool wave, int32_t flags, hipStream_t st) {
+int launch_index_topk(tvz_corpus *c, const Batch &b, int32_t cap, int32_t k, int32_t *d_block, bool wave, int32_t flags,
+                      hipStream_t st) {
     const IndexBuf &ix = c->ix.now();
+    const int32_t Q = b.Q, max_query_len = b.max_query_len;
     // wave (wave_usable and asked for): one WAVE per query - no barriers, every probe of the query in flight at once,
     // the postings in registers between the passes.
     if (wave) {
         const size_t lds = wq_lds_bytes(max_query_len);
-        return by_mode<false>(min_match, [&](auto mode) {
+        return by_mode<false>(b.min_match, [&](auto mode) {
             hipLaunchKernelGGL((ts_match_wq_topk_kernel<mode.value>), dim3((unsigned)Q), dim3(64), lds, st, ix.keys.dir.p,
-                               ix.keys.bits(), ix.keys.post_ptr(), ix.ivid.p, ix.n_main, d_queries, d_q_offsets, Q,
-                               max_query_len, min_match, d_exclude_ids, cap, k, d_block);
+                               ix.keys.bits(), ix.keys.post_ptr(), ix.ivid.p, ix.n_main, b.d_queries, b.d_q_offsets, Q,
+                               max_query_len, b.min_match, b.d_exclude_ids, cap, k, d_block);
             return launched();
         });
     }
@@ -532,21 +563,40 @@ int launch_index_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q
                       lds2 + 256 <= (size_t)kLdsPerWorkgroup / 4 && !no_pair;   // (+ the body's static LDS)
     const size_t lds = pair ? lds2 : ix_lds_bytes(max_query_len, ix.n_sub, true);
     const unsigned grid = pair ? (unsigned)((Q + 1) / 2) : (unsigned)Q;
-    return by_mode<false>(min_match, [&](auto mode) {
-#define TVZ_IXK(NQ)                                                                                            \
-    hipLaunchKernelGGL((ts_match_index_topk_kernel<mode.value, NQ>), dim3(grid), dim3(kIxBlock), lds, st, ix.keys.dir.p, \
-                       ix.keys.bits(), ix.keys.ks, ix.keys.post_ptr(), ix.ivid.p, ix.n_main, ix.n_sub, d_queries, d_q_offsets, Q, \
-                       max_query_len, min_match, d_exclude_ids, cap, k, d_block)
-        if (pair) TVZ_IXK(2); else TVZ_IXK(1);
-#undef TVZ_IXK
+    return by_mode<false>(b.min_match, [&](auto mode) {
+        auto lookup = pair ? ts_match_index_topk_kernel<mode.value, 2> : ts_match_index_topk_kernel<mode.value, 1>;
+        hipLaunchKernelGGL(lookup, dim3(grid), dim3(kIxBlock), lds, st, ix.keys.dir.p, ix.keys.bits(), ix.keys.ks,
+                           ix.keys.post_ptr(), ix.ivid.p, ix.n_main, ix.n_sub, b.d_queries, b.d_q_offsets, Q, max_query_len,
+                           b.min_match, b.d_exclude_ids, cap, k, d_block);
         return launched();
     });
 }
 
-int launch_match_short(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
-                       int32_t max_query_len, int32_t min_match, const int32_t *d_exclude_ids,
-                       int32_t cap, int32_t *d_hits, int32_t *d_hits_n, int32_t ns, unsigned char *ws,
-                       size_t ws_bytes, int32_t algo, hipStream_t st);
+int launch_match_short(tvz_corpus *c, const Batch &b, const HitSink &out, const JoinScratch &scratch, int32_t algo,
+                       hipStream_t st) {
+    const int32_t Q = b.Q, max_query_len = b.max_query_len, min_match = b.min_match;
+    if (int rc = wait_mutations(c, st)) return rc;
+    RowSpan span{c->rows.p, (int64_t)c->h_rows.size()};
+    bool zero = true;
+    if (algo == TVZ_ALGO_INDEX && !index_usable(c, min_match))
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "TVZ_ALGO_INDEX: %s", c->ix.valid
+                             ? "the index answers min_match >= 1 only" : "this corpus has no index (tvz_corpus_build_index)");
+    if ((algo == TVZ_ALGO_AUTO || algo == TVZ_ALGO_INDEX) && index_usable(c, min_match) && Q > 0) {
+        // unchanged rows through the index, rows added or replaced since its build through a sweep
+        // of the delta table - a row is in exactly one of the two
+        if (int rc = launch_index<false>(c, b, /* exclude_one */ -1, out, st)) return rc;
+        if (c->ix.n_delta == 0) return TVZ_OK;
+        span = RowSpan{c->ix.now().drows.p, c->ix.n_delta};
+        zero = false;
+        algo = TVZ_ALGO_AUTO;
+    }
+    int a = pick_algo(algo, Q, span.n, max_query_len, min_match);
+    // AUTO never fails for want of scratch: without the join's tables it takes the LDS tile
+    if (a == TVZ_ALGO_JOIN && algo == TVZ_ALGO_AUTO &&
+        (scratch.ws == nullptr || scratch.ws_bytes < join_shape(Q, max_query_len).bytes()))
+        a = TVZ_ALGO_TILE;
+    return launch_scan(c, span, a, zero, b, out, scratch, st);
+}
 
 // sorted distinct canonical keys + multiplicities of one query (what ts_match_longq_kernel searches)
 void sorted_distinct(const double *q, int64_t n, std::vector<int64_t> &uq, std::vector<int32_t> &mult) {
@@ -571,15 +621,15 @@ void sorted_distinct(const double *q, int64_t n, std::vector<int64_t> &uq, std::
 // the normal way (which marks the long ones INT32_MIN), and every long query is then swept on its
 // own: its sorted distinct keys + multiplicities are searched per row key (ts_match_longq_kernel),
 // kth resolved by the fix-up walk - the path tvz_find_duplicates takes for such a query.
-int launch_match_with_long(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
-                           int32_t min_match, const int32_t *d_exclude_ids, int32_t cap, int32_t *d_hits,
-                           int32_t *d_hits_n, int32_t ns, unsigned char *ws, size_t ws_bytes, unsigned char *lq,
-                           size_t lq_bytes, int32_t algo, hipStream_t st) {
+int launch_match_with_long(tvz_corpus *c, const Batch &b, const HitSink &out, const JoinScratch &scratch, int32_t algo,
+                           hipStream_t st) {
+    const int32_t Q = b.Q, min_match = b.min_match;
+    unsigned char *lq = scratch.lq;
     // The ONE synchronisation of this path: the host has to learn which queries are long (their launches are
     // shaped by their lengths).  Everything after it is enqueued: no allocation (the scratch is a tail of the
     // caller's workspace), no further copy, no wait - VERDICT r4 item 7.
     std::vector<int64_t> h_off((size_t)Q + 1);
-    TVZ_HIP(hipMemcpyAsync(h_off.data(), d_q_offsets, ((size_t)Q + 1) * 8, hipMemcpyDeviceToHost, st));
+    TVZ_HIP(hipMemcpyAsync(h_off.data(), b.d_q_offsets, ((size_t)Q + 1) * 8, hipMemcpyDeviceToHost, st));
     TVZ_HIP(hipStreamSynchronize(st));
     int64_t short_max = 0;
     std::vector<int32_t> longs;
@@ -589,8 +639,8 @@ int launch_match_with_long(tvz_corpus *c, const double *d_queries, const int64_t
         if (n > kMaxQueryLen) longs.push_back(q);
         else short_max = std::max(short_max, n);
     }
-    if (int rc = launch_match_short(c, d_queries, d_q_offsets, Q, (int32_t)short_max, min_match, d_exclude_ids, cap,
-                                    d_hits, d_hits_n, ns, ws, ws_bytes, algo, st))
+    if (int rc = launch_match_short(c, Batch{b.d_queries, b.d_q_offsets, Q, (int32_t)short_max, min_match, b.d_exclude_ids}, out,
+                                    scratch, algo, st))
         return rc;
     if (longs.empty()) return TVZ_OK;
     const int64_t n_rows = (int64_t)c->h_rows.size();
@@ -618,81 +668,47 @@ int launch_match_with_long(tvz_corpus *c, const double *d_queries, const int64_t
         e.mult_at = (int64_t)(cursor / 4);
         cursor = (cursor + (size_t)(n + 1) * 4 + 15) & ~(size_t)15;
     }
-    if (lq == nullptr || cursor > lq_bytes)
+    if (lq == nullptr || cursor > scratch.lq_bytes)
         return tvz::fail(TVZ_ERR_WORKSPACE, "the batch's %zu queries of more than %d timestamps need %zu bytes of scratch, the "
                          "workspace has %zu for them: size it with tvz_match_workspace_bytes_long (the batch's key count)",
-                         longs.size(), kMaxQueryLen, cursor, lq ? lq_bytes : (size_t)0);
+                         longs.size(), kMaxQueryLen, cursor, lq ? scratch.lq_bytes : (size_t)0);
     int64_t *area = reinterpret_cast<int64_t *>(lq);
     for (size_t i0 = 0; i0 < table.size(); i0 += kLongPerLaunch) {
         LongQTable t{};
         const size_t cnt = std::min<size_t>(kLongPerLaunch, table.size() - i0);
         for (size_t i = 0; i < cnt; ++i) t.e[i] = table[i0 + i];
-        hipLaunchKernelGGL(ts_longq_sort_kernel, dim3((unsigned)cnt), dim3(kLongSortBlock), 0, st, d_queries, t, area);
+        hipLaunchKernelGGL(ts_longq_sort_kernel, dim3((unsigned)cnt), dim3(kLongSortBlock), 0, st, b.d_queries, t, area);
         TVZ_HIP(hipGetLastError());
     }
     for (size_t i = 0; i < longs.size(); ++i) {
         const int32_t q = longs[i];
         const LongQ &e = table[i];
-        int32_t *cnt = d_hits_n + (size_t)q * ns;
-        int32_t *hl = d_hits + (int64_t)q * cap * 3;
-        if (int rc = launch_prep(cnt, ns, 1, nullptr, 0, nullptr, 0, st)) return rc;    // un-poison: 0 hits so far
+        const HitSink one{out.cap, out.d_hits + (int64_t)q * out.cap * 3, out.d_hits_n + (size_t)q * out.ns, out.ns};
+        if (int rc = zero_counts(one, 1, st)) return rc;    // un-poison: 0 hits so far
         if (!n_rows) continue;
         // (no distinct key: min_match <= 0 makes every row a hit with count 0, db.py:90: 0 >= min_match)
         hipLaunchKernelGGL(ts_match_longq_kernel, dim3((unsigned)tvz::ceil_div(n_rows, kGroupsPerBlock)), dim3(kBlock),
                            0, st, c->rows.p, n_rows, c->keys.p, area + e.uq_at, reinterpret_cast<int32_t *>(lq) + e.mult_at,
-                           0, min_match, -1, cap, hl, cnt, reinterpret_cast<int32_t *>(lq) + e.m_at,
-                           d_exclude_ids ? d_exclude_ids + q : nullptr);
+                           0, min_match, -1, one.cap, one.d_hits, one.d_hits_n, reinterpret_cast<int32_t *>(lq) + e.m_at,
+                           b.d_exclude_ids ? b.d_exclude_ids + q : nullptr);
         TVZ_HIP(hipGetLastError());
         if (min_match > 0) {
-            hipLaunchKernelGGL(ts_kth_fixup_kernel, dim3(1), dim3(kBlock), 0, st, c->rows.p, c->keys.p, d_queries,
-                               d_q_offsets + q, min_match, cap, hl, cnt, ns);
+            hipLaunchKernelGGL(ts_kth_fixup_kernel, dim3(1), dim3(kBlock), 0, st, c->rows.p, c->keys.p, b.d_queries,
+                               b.d_q_offsets + q, min_match, one.cap, one.d_hits, one.d_hits_n, one.ns);
             TVZ_HIP(hipGetLastError());
         }
     }
     return TVZ_OK;
 }
 
-int launch_match(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
-                 int32_t max_query_len, int32_t min_match, const int32_t *d_exclude_ids,
-                 int32_t cap, int32_t *d_hits, int32_t *d_hits_n, int32_t ns, unsigned char *ws,
-                 size_t ws_bytes, int32_t algo, hipStream_t st, unsigned char *lq = nullptr, size_t lq_bytes = 0) {
+int launch_match(tvz_corpus *c, const Batch &b, const HitSink &out, const JoinScratch &scratch, int32_t algo,
+                 hipStream_t st) {
     TVZ_REQUIRE(algo >= TVZ_ALGO_AUTO && algo <= TVZ_ALGO_INDEX, "unknown algo %d", algo);
-    if (max_query_len > kMaxQueryLen) {
+    if (b.max_query_len > kMaxQueryLen) {
         if (int rc = wait_mutations(c, st)) return rc;
-        return launch_match_with_long(c, d_queries, d_q_offsets, Q, min_match, d_exclude_ids, cap, d_hits, d_hits_n,
-                                      ns, ws, ws_bytes, lq, lq_bytes, algo, st);
+        return launch_match_with_long(c, b, out, scratch, algo, st);
     }
-    return launch_match_short(c, d_queries, d_q_offsets, Q, max_query_len, min_match, d_exclude_ids, cap, d_hits,
-                              d_hits_n, ns, ws, ws_bytes, algo, st);
-}
-
-int launch_match_short(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
-                       int32_t max_query_len, int32_t min_match, const int32_t *d_exclude_ids,
-                       int32_t cap, int32_t *d_hits, int32_t *d_hits_n, int32_t ns, unsigned char *ws,
-                       size_t ws_bytes, int32_t algo, hipStream_t st) {
-    if (int rc = wait_mutations(c, st)) return rc;
-    RowSpan span{c->rows.p, (int64_t)c->h_rows.size()};
-    bool zero_counts = true;
-    if (algo == TVZ_ALGO_INDEX && !index_usable(c, min_match))
-        return tvz::fail(TVZ_ERR_UNSUPPORTED, "TVZ_ALGO_INDEX: %s", c->ix.valid
-                             ? "the index answers min_match >= 1 only" : "this corpus has no index (tvz_corpus_build_index)");
-    if ((algo == TVZ_ALGO_AUTO || algo == TVZ_ALGO_INDEX) && index_usable(c, min_match) && Q > 0) {
-        // unchanged rows through the index, rows added or replaced since its build through a sweep
-        // of the delta table - a row is in exactly one of the two
-        if (int rc = launch_index<false>(c, d_queries, d_q_offsets, Q, max_query_len, min_match, d_exclude_ids,
-                                         -1, cap, d_hits, d_hits_n, ns, st))
-            return rc;
-        if (c->ix.n_delta == 0) return TVZ_OK;
-        span = RowSpan{c->ix.now().drows.p, c->ix.n_delta};
-        zero_counts = false;
-        algo = TVZ_ALGO_AUTO;
-    }
-    int a = pick_algo(algo, Q, span.n, max_query_len, min_match);
-    // AUTO never fails for want of scratch: without the join's tables it takes the LDS tile
-    if (a == TVZ_ALGO_JOIN && algo == TVZ_ALGO_AUTO && (ws == nullptr || ws_bytes < join_shape(Q, max_query_len).bytes()))
-        a = TVZ_ALGO_TILE;
-    return launch_scan(c, span, a, zero_counts, d_queries, d_q_offsets, Q, max_query_len, min_match,
-                       d_exclude_ids, cap, d_hits, d_hits_n, ns, ws, ws_bytes, st);
+    return launch_match_short(c, b, out, scratch, algo, st);
 }
 
 constexpr int kTopkFallbackBlocks = 256 * 5;     // the block kernels behind the one-wave kernel: a chip-full, grid-stride
@@ -754,36 +770,34 @@ int launch_topk_lists(const int32_t *d_lists, const int32_t *d_lists_n, int32_t 
     return TVZ_OK;
 }
 
-int check_batch_args(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
-                     int32_t max_query_len, int32_t cap) {
+int check_batch_args(tvz_corpus *c, const Batch &b, int32_t cap) {
     TVZ_REQUIRE(c != nullptr, "corpus is NULL");
-    TVZ_REQUIRE(Q >= 0 && Q <= 65535, "Q=%d out of range [0, 65535]", Q);
-    TVZ_REQUIRE(max_query_len >= 0 && cap >= 0, "negative size");
-    TVZ_REQUIRE(Q == 0 || d_q_offsets, "NULL query offsets");
-    TVZ_REQUIRE(d_queries || max_query_len == 0 || Q == 0, "d_queries is NULL");
+    TVZ_REQUIRE(b.Q >= 0 && b.Q <= 65535, "Q=%d out of range [0, 65535]", b.Q);
+    TVZ_REQUIRE(b.max_query_len >= 0 && cap >= 0, "negative size");
+    TVZ_REQUIRE(b.Q == 0 || b.d_q_offsets, "NULL query offsets");
+    TVZ_REQUIRE(b.d_queries || b.max_query_len == 0 || b.Q == 0, "d_queries is NULL");
     return TVZ_OK;
 }
 
 }  // namespace
 
 // used by tvz_comm.hip (same shared object, not exported)
-int tvz_match_topk_local(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets,
-                         int32_t Q, int32_t max_query_len, int32_t min_match,
-                         const int32_t *d_exclude_ids, int32_t cap, int32_t k, int32_t *d_out,
-                         void *d_workspace, size_t workspace_bytes, int32_t n_ranks, int32_t algo,
-                         void *hip_stream, int32_t **gathered_out) {
-    if (int rc = check_batch_args(c, d_queries, d_q_offsets, Q, max_query_len, cap)) return rc;
+int tvz_match_topk_local(tvz_corpus *c, const Batch &b, int32_t cap, int32_t k, int32_t *d_out, Workspace ws,
+                         int32_t n_ranks, int32_t algo, void *hip_stream, ShardBlocks *blocks) {
+    const int32_t Q = b.Q, max_query_len = b.max_query_len, min_match = b.min_match;
+    if (int rc = check_batch_args(c, b, cap)) return rc;
     TVZ_REQUIRE(k >= 1 && k <= kSortCap / 2, "k=%d out of range [1, %d]", k, kSortCap / 2);
     constexpr int32_t kShape = TVZ_ALGO_PAIR | TVZ_ALGO_NO_PAIR | TVZ_ALGO_WAVE | TVZ_ALGO_NO_WAVE | TVZ_ALGO_PREFER_WAVE;
     const int32_t flags = algo & kShape;                                  // shape of the fused lookup (tvz.h)
     algo &= ~kShape;
     if (Q == 0) return TVZ_OK;
-    TVZ_REQUIRE(d_workspace != nullptr, "d_workspace is NULL");
-    const WsLayout w = ws_layout(d_workspace, Q, max_query_len, cap, k, n_ranks);
-    if (workspace_bytes < w.total)
-        return tvz::fail(TVZ_ERR_WORKSPACE, "workspace of %zu bytes, need %zu", workspace_bytes, w.total);
+    TVZ_REQUIRE(ws.p != nullptr, "d_workspace is NULL");
+    const WsLayout w = ws_layout(ws.p, ws.bytes, Q, max_query_len, cap, k, n_ranks);
+    if (ws.bytes < w.total)
+        return tvz::fail(TVZ_ERR_WORKSPACE, "workspace of %zu bytes, need %zu", ws.bytes, w.total);
     if (d_out == nullptr) d_out = w.local;
-    if (gathered_out) *gathered_out = w.gathered;
+    if (blocks) *blocks = ShardBlocks{d_out, w.gathered};
+    const HitSink out = w.sink(cap);   // (one-counter-per-line scratch: the select kernel reads it as it is)
     DeviceGuard dg(c->device);
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
     std::shared_lock<std::shared_mutex> lk(c->mu);
@@ -799,17 +813,13 @@ int tvz_match_topk_local(tvz_corpus *c, const double *d_queries, const int64_t *
         if (int rc = wait_mutations(c, st)) return rc;
         const int64_t n_delta = c->ix.n_delta;
         int32_t *blk = n_delta ? w.pair : d_out;
-        if (int rc = launch_index_topk(c, d_queries, d_q_offsets, Q, max_query_len, min_match, d_exclude_ids, cap, k,
-                                       blk, wave, flags, st))
-            return rc;
+        if (int rc = launch_index_topk(c, b, cap, k, blk, wave, flags, st)) return rc;
         if (n_delta) {
             const RowSpan span{c->ix.now().drows.p, n_delta};
             int a = pick_algo(TVZ_ALGO_AUTO, Q, span.n, max_query_len, min_match);
-            if (int rc = launch_scan(c, span, a, true, d_queries, d_q_offsets, Q, max_query_len, min_match,
-                                     d_exclude_ids, cap, w.hits, w.counters, kCountStride, w.join, w.join_bytes, st))
-                return rc;
+            if (int rc = launch_scan(c, span, a, true, b, out, w.scratch(), st)) return rc;
             int32_t *blk2 = w.pair + (size_t)Q * (size_t)(k + 1) * 3;
-            if (int rc = launch_topk_local(w.hits, w.counters, kCountStride, Q, cap, k, blk2, 1, w.flags, st)) return rc;
+            if (int rc = launch_topk_local(out.d_hits, out.d_hits_n, out.ns, Q, cap, k, blk2, 1, w.flags, st)) return rc;
             hipLaunchKernelGGL(ts_topk_wave_kernel, dim3((unsigned)tvz::ceil_div(Q, kBlock / 64)), dim3(kBlock), 0, st,
                                w.pair, nullptr, /* mode 3: ns = the hit capacity */ cap, 2, Q, k + 1, k, d_out, 3,
                                nullptr, nullptr);
@@ -817,18 +827,9 @@ int tvz_match_topk_local(tvz_corpus *c, const double *d_queries, const int64_t *
         }
         return record(c, st);
     }
-    // the sweeps count into one-counter-per-line scratch; the select kernel reads it as it is
-    if (int rc = launch_match(c, d_queries, d_q_offsets, Q, max_query_len, min_match, d_exclude_ids, cap, w.hits,
-                              w.counters, kCountStride, w.join, w.join_bytes, algo, st, w.longq,
-                              w.longq_bytes(d_workspace, workspace_bytes)))
-        return rc;
-    if (int rc = launch_topk_local(w.hits, w.counters, kCountStride, Q, cap, k, d_out, 1, w.flags, st)) return rc;
+    if (int rc = launch_match(c, b, out, w.scratch(), algo, st)) return rc;
+    if (int rc = launch_topk_local(out.d_hits, out.d_hits_n, out.ns, Q, cap, k, d_out, 1, w.flags, st)) return rc;
     return record(c, st);
-}
-
-int32_t *tvz_ws_local_block(void *d_workspace, int32_t Q, int32_t max_query_len, int32_t cap,
-                            int32_t k, int32_t n_ranks) {
-    return ws_layout(d_workspace, Q, max_query_len, cap, k, n_ranks).local;
 }
 
 // a kernel may ask for up to `bytes` of dynamic LDS
@@ -1240,7 +1241,8 @@ static int tvz_match_impl(tvz_corpus *c, const double *d_queries, const int64_t 
                          const int32_t *d_exclude_ids, int32_t cap, int32_t *d_hits,
                          int32_t *d_hits_n, void *d_workspace, size_t workspace_bytes, int32_t algo,
                          void *hip_stream) {
-    if (int rc = check_batch_args(c, d_queries, d_q_offsets, Q, max_query_len, cap)) return rc;
+    const Batch b{d_queries, d_q_offsets, Q, max_query_len, min_match, d_exclude_ids};
+    if (int rc = check_batch_args(c, b, cap)) return rc;
     if (Q == 0) return TVZ_OK;
     TVZ_REQUIRE(d_hits_n && (cap == 0 || d_hits), "NULL output");
     DeviceGuard dg(c->device);
@@ -1248,33 +1250,24 @@ static int tvz_match_impl(tvz_corpus *c, const double *d_queries, const int64_t 
     // with a workspace (tvz_match_workspace_bytes(Q, max_query_len, 0, 0, 1)) the sweeps count into
     // one-counter-per-cache-line scratch and may use the hash join; without one they fall back to
     // the caller's dense counters and the LDS kernels
-    unsigned char *ws = nullptr, *lq = nullptr;
-    size_t ws_bytes = 0, lq_bytes = 0;
-    int32_t *cnt = d_hits_n;
-    int32_t ns = 1;
+    JoinScratch scratch;
+    HitSink out = HitSink::dense(cap, d_hits, d_hits_n);
     if (d_workspace) {
-        const WsLayout w = ws_layout(d_workspace, Q, max_query_len, cap, 0, 1);
+        const WsLayout w = ws_layout(d_workspace, workspace_bytes, Q, max_query_len, cap, 0, 1);
         if (workspace_bytes >= w.total) {
-            ws = w.join;
-            ws_bytes = w.join_bytes;
-            lq = w.longq;
-            lq_bytes = w.longq_bytes(d_workspace, workspace_bytes);
-            if (Q > 1) {                 // a lone query's counter shares its line with nobody: no gather launch
-                cnt = w.counters;
-                ns = kCountStride;
-            }
+            scratch = w.scratch();
+            // (a lone query's counter shares its line with nobody: no gather launch)
+            if (Q > 1) out = HitSink::per_line(cap, d_hits, w.counters);
         } else if (algo == TVZ_ALGO_JOIN) {
             return tvz::fail(TVZ_ERR_WORKSPACE, "workspace of %zu bytes, the hash join needs %zu: size it with "
                                                 "tvz_match_workspace_bytes", workspace_bytes, w.total);
         }
     }
     std::shared_lock<std::shared_mutex> lk(c->mu);
-    if (int rc = launch_match(c, d_queries, d_q_offsets, Q, max_query_len, min_match,
-                              d_exclude_ids, cap, d_hits, cnt, ns, ws, ws_bytes, algo, st, lq, lq_bytes))
-        return rc;
-    if (ns != 1) {
+    if (int rc = launch_match(c, b, out, scratch, algo, st)) return rc;
+    if (out.ns != 1) {
         hipLaunchKernelGGL(ts_counts_gather_kernel, dim3((unsigned)tvz::ceil_div(Q, kBlock)), dim3(kBlock), 0, st,
-                           cnt, ns, d_hits_n, Q);
+                           out.d_hits_n, out.ns, d_hits_n, Q);
         TVZ_HIP(hipGetLastError());
     }
     return record(c, st);
@@ -1286,8 +1279,8 @@ static int tvz_match_topk_impl(tvz_corpus *c, const double *d_queries, const int
                               void *d_workspace, size_t workspace_bytes, int32_t algo,
                               void *hip_stream) {
     TVZ_REQUIRE(d_out != nullptr || Q == 0, "d_out is NULL");
-    return tvz_match_topk_local(c, d_queries, d_q_offsets, Q, max_query_len, min_match, d_exclude_ids,
-                                cap, k, d_out, d_workspace, workspace_bytes, 1, algo, hip_stream, nullptr);
+    return tvz_match_topk_local(c, Batch{d_queries, d_q_offsets, Q, max_query_len, min_match, d_exclude_ids}, cap, k, d_out,
+                                Workspace{d_workspace, workspace_bytes}, 1, algo, hip_stream, nullptr);
 }
 
 namespace {
@@ -1302,6 +1295,16 @@ int check_find_args(const tvz_corpus *c, const double *h_query, int64_t n, int64
     TVZ_REQUIRE(n == 0 || h_query, "h_query is NULL");
     TVZ_REQUIRE(cap == 0 || (h_out_ids && h_out_counts), "NULL outputs");
     TVZ_REQUIRE(n <= INT32_MAX, "query too long");
+    return TVZ_OK;
+}
+
+// eps and max_offset of tvz_align and tvz_align_topk; *nb = the offset bins on either side of zero
+int check_align_bins(double eps, double max_offset, int32_t *nb_out) {
+    TVZ_REQUIRE(eps > 0.0 && max_offset >= 0.0, "eps must be > 0 and max_offset >= 0");
+    const double nb = floor(max_offset / eps + 0.5);
+    if (!(2 * nb + 1 <= kAlignMaxBins))                 // also refuses NaN (eps = max_offset = inf)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "max_offset/eps = %.0f needs more than %d bins", nb, kAlignMaxBins);
+    *nb_out = (int32_t)nb;
     return TVZ_OK;
 }
 
@@ -1395,6 +1398,7 @@ int find_pinned(tvz_corpus *c, Staging *s, const double *h_query, int64_t n, int
     }
     const double *dq = by_value ? nullptr : reinterpret_cast<const double *>(s->d_query.p + 2);
     const int64_t *dqo = by_value ? nullptr : s->d_query.p;
+    const Batch one{dq, dqo, 1, (int32_t)n, min_match, nullptr};
     // with an index: rows unchanged since its build are answered by the lookup kernel (one
     // block), rows in the delta table by the sweep - both write to pinned host memory, one
     // synchronisation for the two.  A query the lookup refuses (> 4 G postings) is swept.
@@ -1416,7 +1420,6 @@ int find_pinned(tvz_corpus *c, Staging *s, const double *h_query, int64_t n, int
                     blocks = (int)std::max<int64_t>(1, std::min<int64_t>(tvz::ceil_div(span.n, kFG), kQ1MaxBlocks));
                     region = (int)(tvz::ceil_div(span.n, (int64_t)blocks * kFG) * kFG);
                     const HostOut ho{s->hits.d, s->counts.d, region};
-                    static const QByVal kNoQuery = {};
                     return by_mode<false>(min_match, [&](auto mode) -> int {
                         hipLaunchKernelGGL((ts_find_fused_kernel<mode.value == kModeTop5>), dim3((unsigned)(n_sub + blocks)),
                                            dim3(kIxBlock), lds, s->stream.s, ib.keys.dir.p, ib.keys.bits(), ib.keys.ks, ib.keys.post_ptr(),
@@ -1427,16 +1430,16 @@ int find_pinned(tvz_corpus *c, Staging *s, const double *h_query, int64_t n, int
                         return TVZ_OK;
                     });
                 }
-                if (int rc = launch_index<true>(c, dq, dqo, 1, (int32_t)n, min_match, nullptr, excl, 0, s->ix_hits.d,
-                                                s->counts.d + kQ1MaxBlocks, 1, s->stream.s, by_value ? &qv : nullptr))
+                // (one region and one count per sub-index)
+                if (int rc = launch_index<true>(c, one, excl, HitSink::dense(0, s->ix_hits.d, s->counts.d + kQ1MaxBlocks),
+                                                s->stream.s, by_value ? &qv : nullptr))
                     return rc;
             }
             if (!span.n) return TVZ_OK;
             blocks = q1_blocks(span.n, 1);
             region = (int)(tvz::ceil_div(span.n, (int64_t)blocks * kQ1Groups) * kQ1Groups);
             const HostOut ho{s->hits.d, s->counts.d, region};
-            return launch_q1<true>(c, span, dq, dqo, 1, (int32_t)n, min_match, nullptr, excl, 0, nullptr, nullptr, 1,
-                                   blocks, ho, s->stream.s, by_value ? &qv : nullptr);
+            return launch_q1<true>(c, span, one, excl, kHostSink, blocks, ho, s->stream.s, by_value ? &qv : nullptr);
         };
         if (int rc = pinned_sweep(c, s, "", launch, n_hits)) return rc;
         bool refused = false;
@@ -1490,7 +1493,8 @@ int find_device(tvz_corpus *c, Staging *s, const double *h_query, int64_t n, int
         std::shared_lock<std::shared_mutex> lk(c->mu);
         const int64_t n_rows = (int64_t)c->h_rows.size();
         if (int rc = wait_mutations(c, s->stream.s)) return rc;
-        if (int rc = launch_prep(s->d_hits_n.p, 1, 1, nullptr, 0, nullptr, 0, s->stream.s)) return rc;
+        const HitSink out = HitSink::dense((int32_t)want, s->d_hits.p, s->d_hits_n.p);
+        if (int rc = zero_counts(out, 1, s->stream.s)) return rc;
         if (n_rows) {
             if (longq) {
                 hipLaunchKernelGGL(ts_match_longq_kernel, dim3((unsigned)tvz::ceil_div(n_rows, kGroupsPerBlock)),
@@ -1508,10 +1512,8 @@ int find_device(tvz_corpus *c, Staging *s, const double *h_query, int64_t n, int
                 // min_match > 5 (or <= 0): what a batch of one takes - on an indexed handle the lookup with a
                 // count-only pass B + the kth fix-up walk and a sweep of the delta table, else the single-query
                 // sweep; the fix-ups are part of those paths
-                if (int rc = launch_match_short(c, reinterpret_cast<const double *>(d_q + 2), d_q, 1, (int32_t)n, min_match,
-                                                nullptr, (int32_t)want, s->d_hits.p, s->d_hits_n.p, 1, nullptr, 0,
-                                                TVZ_ALGO_AUTO, s->stream.s))
-                    return rc;
+                const Batch one{reinterpret_cast<const double *>(d_q + 2), d_q, 1, (int32_t)n, min_match, nullptr};
+                if (int rc = launch_match_short(c, one, out, JoinScratch{}, TVZ_ALGO_AUTO, s->stream.s)) return rc;
             }
         }
         if (int rc = record(c, s->stream.s)) return rc;
@@ -1595,12 +1597,12 @@ static int tvz_match_topk_shards_impl(tvz_corpus *const *shards, int32_t n_shard
     TVZ_REQUIRE(shards != nullptr && n_shards >= 1, "no shards");
     TVZ_REQUIRE(Q == 0 || (d_blocks && d_topk && d_totals), "NULL output");
     if (Q == 0) return TVZ_OK;
+    const Batch b{d_queries, d_q_offsets, Q, max_query_len, min_match, d_exclude_ids};
     for (int32_t r = 0; r < n_shards; ++r) {
         TVZ_REQUIRE(shards[r] != nullptr && shards[r]->device == shards[0]->device,
                     "shard %d is NULL or on another device than shard 0", r);
-        if (int rc = tvz_match_topk_local(shards[r], d_queries, d_q_offsets, Q, max_query_len, min_match, d_exclude_ids,
-                                          cap, k, d_blocks + (size_t)r * (size_t)Q * (size_t)(k + 1) * 3, d_workspace,
-                                          workspace_bytes, 1, algo, hip_stream, nullptr))
+        if (int rc = tvz_match_topk_local(shards[r], b, cap, k, d_blocks + (size_t)r * (size_t)Q * (size_t)(k + 1) * 3,
+                                          Workspace{d_workspace, workspace_bytes}, 1, algo, hip_stream, nullptr))
             return rc;
     }
     DeviceGuard dg(shards[0]->device);
@@ -1613,11 +1615,8 @@ static int tvz_align_impl(tvz_corpus *c, const double *d_query, int32_t n, doubl
     TVZ_REQUIRE(c != nullptr && n_rows_out != nullptr, "NULL argument");
     TVZ_REQUIRE(n >= 0 && (n == 0 || d_query), "bad query");
     TVZ_REQUIRE(out_rows >= 0, "out_rows must be >= 0");
-    TVZ_REQUIRE(eps > 0.0 && max_offset >= 0.0, "eps must be > 0 and max_offset >= 0");
-    const double nb = floor(max_offset / eps + 0.5);
-    if (!(2 * nb + 1 <= kAlignMaxBins))                 // also refuses NaN (eps = max_offset = inf)
-        return tvz::fail(TVZ_ERR_UNSUPPORTED, "max_offset/eps = %.0f needs more than %d bins", nb,
-                         kAlignMaxBins);
+    int32_t nb = 0;
+    if (int rc = check_align_bins(eps, max_offset, &nb)) return rc;
     DeviceGuard dg(c->device);
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
     std::shared_lock<std::shared_mutex> lk(c->mu);
@@ -1630,7 +1629,7 @@ static int tvz_align_impl(tvz_corpus *c, const double *d_query, int32_t n, doubl
     if (int rc = wait_mutations(c, st)) return rc;
     const int64_t blocks = std::min<int64_t>(tvz::ceil_div(n_write, kBlock / 64), 256 * 8);
     hipLaunchKernelGGL(ts_align_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, c->rows.p, n_write,
-                       c->keys.p, d_query, n, eps, (int32_t)nb, d_out);
+                       c->keys.p, d_query, n, eps, nb, d_out);
     TVZ_HIP(hipGetLastError());
     return record(c, st);
 }
@@ -1644,56 +1643,53 @@ int check_tol(double tol) {
     return TVZ_OK;
 }
 
-// The sweep, one launch: the sorted query's values sv[..) and positions sp[..) (per query, see ts_match_tol_kernel),
-// in LDS when lds_keys > 0 (every query of the launch has at most lds_keys values).
+// The sweep, one launch: the sorted queries (q.sv, q.sp: per query, see ts_match_tol_kernel), in LDS when q.lds_keys > 0
+// (every query of the launch has at most that many values).
 template <bool HOSTOUT>
-int launch_tol(tvz_corpus *c, const Row *rows, int64_t n_rows, const double *sv, const int32_t *sp, const int64_t *q_offsets,
-               const int32_t *qm, int32_t m_one, int32_t lds_keys, int32_t Q, double tol, int32_t min_match,
-               const int32_t *d_exclude_ids, int32_t exclude_one, int32_t cap, int32_t *d_hits, int32_t *d_hits_n,
+int launch_tol(tvz_corpus *c, RowSpan span, const Batch &b, const TolSorted &q, int32_t exclude_one, const HitSink &out,
                int blocks_x, HostOut ho, hipStream_t st) {
-    const size_t lds = lds_keys > 0 ? tol_lds_bytes(lds_keys) : 0;
+    const size_t lds = q.lds_keys > 0 ? tol_lds_bytes(q.lds_keys) : 0;
     TVZ_REQUIRE(lds + kQ1Stage * 12 + 64 <= (size_t)kLdsPerWorkgroup, "tolerant sweep: %zu B of LDS exceed a gfx950 workgroup's",
                 lds);
-    const dim3 grid((unsigned)blocks_x, (unsigned)Q);
-    return by_mode(min_match, [&](auto mode) {
-#define TVZ_TOL(LDSQ)                                                                                                 \
-    hipLaunchKernelGGL((ts_match_tol_kernel<mode.value, HOSTOUT, LDSQ>), grid, dim3(kTolBlock), lds, st, rows,        \
-                       n_rows, c->keys.p, sv, sp, q_offsets, qm, m_one, lds_keys, tol, min_match, d_exclude_ids,      \
-                       exclude_one, cap, d_hits, d_hits_n, ho)
-        if (lds_keys > 0) TVZ_TOL(true); else TVZ_TOL(false);
-#undef TVZ_TOL
+    const dim3 grid((unsigned)blocks_x, (unsigned)b.Q);
+    return by_mode(b.min_match, [&](auto mode) {
+        auto sweep = q.lds_keys > 0 ? ts_match_tol_kernel<mode.value, HOSTOUT, true> : ts_match_tol_kernel<mode.value, HOSTOUT, false>;
+        hipLaunchKernelGGL(sweep, grid, dim3(kTolBlock), lds, st, span.p, span.n, c->keys.p, q.sv, q.sp, b.d_q_offsets, q.qm,
+                           q.m_one, q.lds_keys, q.tol, b.min_match, b.d_exclude_ids, exclude_one, out.cap, out.d_hits,
+                           out.d_hits_n, ho);
         return launched();
     });
 }
 
-// workspace of tvz_match_tol: per query its count of non-NaN values, then room for `keys` sorted values + positions
+// Workspace of the sorted queries (every tolerant batched call ends in it): per query its count of non-NaN values,
+// then room for `room` sorted values + positions.
 struct TolWs {
     int32_t *qm = nullptr;
     double *sv = nullptr;
     int32_t *sp = nullptr;
     int64_t room = 0;
-    size_t total = 0;
+    static constexpr size_t kPerKey = sizeof(double) + sizeof(int32_t);
 };
+constexpr size_t kTolWsSlack = 256 + 2 * 255;         // (see Carver)
 
-TolWs tol_ws_layout(void *base, int32_t Q, int64_t keys) {
+TolWs tol_ws_layout(Carver &cv, int32_t Q, int64_t keys) {
     TolWs w;
-    uintptr_t p = (reinterpret_cast<uintptr_t>(base) + 255) & ~(uintptr_t)255;
-    const uintptr_t p0 = p;
-    w.qm = reinterpret_cast<int32_t *>(p);
-    p += al256((size_t)Q * 4);
-    w.sv = reinterpret_cast<double *>(p);
-    p += al256((size_t)keys * 8);
-    w.sp = reinterpret_cast<int32_t *>(p);
-    p += al256((size_t)keys * 4);
+    w.qm = cv.take<int32_t>((size_t)Q);
+    w.sv = cv.take<double>((size_t)keys);
+    w.sp = cv.take<int32_t>((size_t)keys);
     w.room = keys;
-    w.total = (size_t)(p - p0) + 256;
     return w;
 }
 
-// the most sorted values a workspace of `bytes` holds next to Q counts (-1: not even the counts)
-size_t tol_ws_fixed(int32_t Q) { return al256((size_t)Q * 4) + 256 + 2 * 255; }
+// bytes for `keys` sorted values next to Q counts; the most values a workspace of `bytes` holds (-1: not even the
+// counts) - tol_ws_room(Q, tol_ws_bytes(Q, keys)) is `keys`
+size_t tol_ws_bytes(int32_t Q, int64_t keys) {
+    Carver cv(nullptr);
+    tol_ws_layout(cv, Q, 0);
+    return cv.used() + kTolWsSlack + (size_t)keys * TolWs::kPerKey;
+}
 int64_t tol_ws_room(int32_t Q, size_t bytes) {
-    return bytes < tol_ws_fixed(Q) ? -1 : (int64_t)((bytes - tol_ws_fixed(Q)) / 12);
+    return bytes < tol_ws_bytes(Q, 0) ? -1 : (int64_t)((bytes - tol_ws_bytes(Q, 0)) / TolWs::kPerKey);
 }
 
 // ---- the lookup through cell postings (tvz_tol_index_kernels.h) ----
@@ -1723,21 +1719,72 @@ TolIxShape tol_index_shape(int n_sub, int32_t Q) {
 }
 
 template <bool TOPK>
-int launch_tol_index(tvz_corpus *c, const TolIxShape &sh, const double *sv, const int32_t *sp, const int64_t *q_offsets,
-                     const int32_t *qm, int32_t lds_keys, int32_t Q, double tol, int32_t min_match,
-                     const int32_t *d_exclude_ids, int32_t cap, int32_t *d_hits, int32_t *d_hits_n, int32_t k,
+int launch_tol_index(tvz_corpus *c, const TolIxShape &sh, const Batch &b, const TolSorted &q, const HitSink &out, int32_t k,
                      unsigned long long *part, int32_t n_lists, hipStream_t st) {
-    const IndexBuf &b = c->ix.now();
-    const dim3 grid((unsigned)sh.blocks(), (unsigned)Q);
-    const bool keep_slots = sh.spb > 1 && lds_keys <= kTolIxSlotKeys;
-    return by_mode<false>(min_match, [&](auto mode) {
+    const IndexBuf &ib = c->ix.now();
+    const dim3 grid((unsigned)sh.blocks(), (unsigned)b.Q);
+    const bool keep_slots = sh.spb > 1 && q.lds_keys <= kTolIxSlotKeys;
+    return by_mode<false>(b.min_match, [&](auto mode) {
         hipLaunchKernelGGL((ts_tol_index_kernel<mode.value, TOPK>), grid, dim3(kTolBlock),
-                           tol_index_lds_bytes(lds_keys, keep_slots), st,
-                           b.cells.dir.p, b.cells.bits(), b.cells.ks, b.cells.post.p, b.ivid.p, b.irows.p, b.n_main, b.n_sub, sh.spb,
-                           sh.split, b.t_cell, c->keys.p, sv, sp, q_offsets, qm, lds_keys, tol, min_match, d_exclude_ids,
-                           cap, d_hits, d_hits_n, k, part, n_lists, keep_slots ? 1 : 0);
+                           tol_index_lds_bytes(q.lds_keys, keep_slots), st,
+                           ib.cells.dir.p, ib.cells.bits(), ib.cells.ks, ib.cells.post.p, ib.ivid.p, ib.irows.p, ib.n_main, ib.n_sub,
+                           sh.spb, sh.split, ib.t_cell, c->keys.p, q.sv, q.sp, b.d_q_offsets, q.qm, q.lds_keys, q.tol, b.min_match,
+                           b.d_exclude_ids, out.cap, out.d_hits, out.d_hits_n, k, part, n_lists, keep_slots ? 1 : 0);
         return launched();
     });
+}
+
+// What a tolerant batched call does with the rows: with usable cell postings (tol_index_usable) the indexed rows are
+// answered by the lookup, in front, and the sweep is left the delta table - every row is in exactly one; otherwise the
+// sweep reads all rows.
+struct TolPlan {
+    RowSpan sweep;
+    bool lookup = false;
+    TolIxShape sh;
+};
+TolPlan tol_plan(const tvz_corpus *c, const Batch &b, const TolSorted &q, int64_t n_rows) {
+    TolPlan p{RowSpan{c->rows.p, n_rows}};
+    if (tol_index_usable(c, q.tol, b.min_match, q.lds_keys)) {
+        p.lookup = true;
+        p.sh = tol_index_shape(c->ix.now().n_sub, b.Q);
+        p.sweep = RowSpan{c->ix.now().drows.p, c->ix.n_delta};
+    }
+    return p;
+}
+
+// The opening of every tolerant batched call.  The entry point has carved its own regions (f.cv; `fixed` bytes, none:
+// 0); this checks the workspace of `have` bytes against them plus the sorted queries' fixed part and `min_keys`
+// values, runs the entry point's remaining checks (args_ok), carves TolWs from all that is left, launches the sort
+// (per query: sorted values + positions, counts, f.zeroed[q] = 0), takes the shared lock and waits for the mutations.
+struct TolFront {
+    Carver cv;
+    size_t fixed;
+    int32_t *zeroed;                 // [Q] hit counters or totals
+    const char *what, *sizer;        // the workspace error names the call and its sizing function
+};
+struct TolCall {
+    std::optional<DeviceGuard> dg;
+    std::shared_lock<std::shared_mutex> lk;
+    TolWs ws;
+    int64_t n_rows = 0;
+};
+template <typename ArgsOk>
+int tol_prelude(tvz_corpus *c, const Batch &b, TolFront f, size_t have, int64_t min_keys, hipStream_t st, ArgsOk &&args_ok,
+                TolCall &t) {
+    const size_t need = f.fixed + tol_ws_bytes(b.Q, min_keys);
+    if (have < need)
+        return tvz::fail(TVZ_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu bytes missing (size it with %s)", f.what, have,
+                         need - have, f.sizer);
+    if (int rc = args_ok()) return rc;
+    t.ws = tol_ws_layout(f.cv, b.Q, tol_ws_room(b.Q, have - f.fixed));
+    t.dg.emplace(c->device);
+    hipLaunchKernelGGL(ts_tol_sort_kernel, dim3((unsigned)tvz::ceil_div(std::max(b.max_query_len, 1), kTolSortBlock), (unsigned)b.Q),
+                       dim3(kTolSortBlock), 0, st, b.d_queries, b.d_q_offsets, b.max_query_len, t.ws.room, t.ws.sv, t.ws.sp,
+                       t.ws.qm, f.zeroed);
+    TVZ_HIP(hipGetLastError());
+    t.lk = std::shared_lock<std::shared_mutex>(c->mu);
+    t.n_rows = (int64_t)c->h_rows.size();
+    return wait_mutations(c, st);
 }
 
 }  // namespace
@@ -1788,8 +1835,9 @@ static int tvz_find_duplicates_tol_impl(tvz_corpus *c, const double *h_query, in
         region = (int)(tvz::ceil_div(n_rows, (int64_t)blocks * kTolGroups) * kTolGroups);
         const HostOut ho{s->hits.d, s->counts.d, region};
         const int32_t lds_keys = m <= kTolLdsKeys ? (int32_t)std::max<int64_t>(m, 1) : 0;
-        if (int rc = launch_tol<true>(c, c->rows.p, n_rows, dv, dp, nullptr, nullptr, (int32_t)m, lds_keys, 1, tol, min_match,
-                                      nullptr, excl, 0, nullptr, nullptr, blocks, ho, s->stream.s))
+        const Batch one{nullptr, nullptr, 1, (int32_t)m, min_match, nullptr};      // (the sorted form is all the sweep reads)
+        if (int rc = launch_tol<true>(c, RowSpan{c->rows.p, n_rows}, one, TolSorted{dv, dp, nullptr, (int32_t)m, lds_keys, tol},
+                                      excl, kHostSink, blocks, ho, s->stream.s))
             return rc;
         if (!fixup) return TVZ_OK;
         hipLaunchKernelGGL(ts_tol_kth_fixup_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, s->stream.s, c->rows.p,
@@ -1807,45 +1855,25 @@ static int tvz_match_tol_impl(tvz_corpus *c, const double *d_queries, const int6
                               int32_t max_query_len, double tol, int32_t min_match, const int32_t *d_exclude_ids,
                               int32_t cap, int32_t *d_hits, int32_t *d_hits_n, void *d_workspace,
                               size_t workspace_bytes, void *hip_stream) {
-    if (int rc = check_batch_args(c, d_queries, d_q_offsets, Q, max_query_len, cap)) return rc;
+    const Batch b{d_queries, d_q_offsets, Q, max_query_len, min_match, d_exclude_ids};
+    if (int rc = check_batch_args(c, b, cap)) return rc;
     if (int rc = check_tol(tol)) return rc;
     if (Q == 0) return TVZ_OK;
     TVZ_REQUIRE(d_hits_n && (cap == 0 || d_hits), "NULL output");
-    const int64_t room = tol_ws_room(Q, d_workspace ? workspace_bytes : 0);
-    if (room < 0) {
-        const size_t have = d_workspace ? workspace_bytes : 0;
-        return tvz::fail(TVZ_ERR_WORKSPACE, "tolerant match: workspace of %zu bytes, %zu bytes missing (size it with "
-                                            "tvz_match_tol_workspace_bytes)", have, tol_ws_fixed(Q) - have);
-    }
-    const TolWs w = tol_ws_layout(d_workspace, Q, room);
-    DeviceGuard dg(c->device);
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    // per query: sorted values + positions, counts, hit counters = 0
-    hipLaunchKernelGGL(ts_tol_sort_kernel, dim3((unsigned)tvz::ceil_div(std::max(max_query_len, 1), kTolSortBlock), (unsigned)Q),
-                       dim3(kTolSortBlock), 0, st, d_queries, d_q_offsets, max_query_len, w.room, w.sv, w.sp, w.qm,
-                       d_hits_n);
-    TVZ_HIP(hipGetLastError());
-    std::shared_lock<std::shared_mutex> lk(c->mu);
-    const int64_t n_rows = (int64_t)c->h_rows.size();
-    if (int rc = wait_mutations(c, st)) return rc;
-    const int32_t lds_keys = max_query_len <= kTolLdsKeys ? std::max(max_query_len, 1) : 0;
-    if (tol_index_usable(c, tol, min_match, lds_keys)) {
-        // the indexed rows through their cell postings, the delta table by the sweep: every row is in exactly one
-        const Index &ix = c->ix;
-        if (int rc = launch_tol_index<false>(c, tol_index_shape(ix.now().n_sub, Q), w.sv, w.sp, d_q_offsets, w.qm, lds_keys,
-                                             Q, tol, min_match, d_exclude_ids, cap, d_hits, d_hits_n, 0, nullptr, 0, st))
-            return rc;
-        if (ix.n_delta)
-            if (int rc = launch_tol<false>(c, ix.now().drows.p, ix.n_delta, w.sv, w.sp, d_q_offsets, w.qm, 0, lds_keys, Q,
-                                           tol, min_match, d_exclude_ids, -1, cap, d_hits, d_hits_n,
-                                           q1_blocks(ix.n_delta, Q), HostOut{}, st))
-                return rc;
-        return record(c, st);
-    }
-    if (int rc = launch_tol<false>(c, c->rows.p, n_rows, w.sv, w.sp, d_q_offsets, w.qm, 0, lds_keys, Q, tol, min_match,
-                                   d_exclude_ids, -1, cap, d_hits, d_hits_n, q1_blocks(n_rows, Q), HostOut{}, st))
+    TolCall t;
+    if (int rc = tol_prelude(c, b, TolFront{Carver(d_workspace), 0, d_hits_n, "tolerant match", "tvz_match_tol_workspace_bytes"},
+                             d_workspace ? workspace_bytes : 0, 0, st, [] { return TVZ_OK; }, t))
         return rc;
-    if (min_match > kTop && n_rows) {
+    const TolSorted q{t.ws.sv, t.ws.sp, t.ws.qm, 0, max_query_len <= kTolLdsKeys ? std::max(max_query_len, 1) : 0, tol};
+    const HitSink out = HitSink::dense(cap, d_hits, d_hits_n);
+    const TolPlan plan = tol_plan(c, b, q, t.n_rows);
+    if (plan.lookup)
+        if (int rc = launch_tol_index<false>(c, plan.sh, b, q, out, 0, nullptr, 0, st)) return rc;
+    if (!plan.lookup || plan.sweep.n)      // (behind the lookup an empty delta table needs no launch)
+        if (int rc = launch_tol<false>(c, plan.sweep, b, q, /* exclude_one */ -1, out, q1_blocks(plan.sweep.n, Q), HostOut{}, st))
+            return rc;
+    if (min_match > kTop && t.n_rows) {    // (never behind the lookup: it takes min_match 1..5)
         hipLaunchKernelGGL(ts_tol_kth_fixup_kernel, dim3((unsigned)Q), dim3(kBlock), 0, st, c->rows.p, c->keys.p,
                            d_queries, d_q_offsets, 0, tol, min_match, d_hits, d_hits_n, cap);
         TVZ_HIP(hipGetLastError());
@@ -1855,7 +1883,7 @@ static int tvz_match_tol_impl(tvz_corpus *c, const double *d_queries, const int6
 
 namespace {
 
-// Workspace of the top-k form, in front of tvz_match_tol's own (which takes the rest): the queries' hit totals,
+// Workspace of the top-k form, in front of the sorted queries (TolWs, which takes the rest): the queries' hit totals,
 // one kept list per sweep block, the local block and the gathered ones.  The sizing function knows no row count:
 // the lists are sized by the grid's upper bound, Q * tol_topk_max_blocks(Q) <= tol_topk_max_lists(Q).
 struct TolTopkWs {
@@ -1863,37 +1891,27 @@ struct TolTopkWs {
     unsigned long long *part = nullptr;    // [Q][blocks][k]
     int32_t *local = nullptr;              // [Q][k+1][3]
     int32_t *gathered = nullptr;           // [n_ranks][Q][k+1][3]
-    unsigned char *rest = nullptr;         // tvz_match_tol's workspace
-    size_t fixed = 0;                      // bytes in front of `rest`, the base's alignment included
 };
 
-TolTopkWs tol_topk_ws_layout(void *base, int32_t Q, int32_t k, int32_t n_ranks) {
+TolTopkWs tol_topk_ws_layout(Carver &cv, int32_t Q, int32_t k, int32_t n_ranks) {
     TolTopkWs w;
-    uintptr_t p = (reinterpret_cast<uintptr_t>(base) + 255) & ~(uintptr_t)255;
-    const size_t block = (size_t)Q * (size_t)(k + 1) * 12;
-    w.totals = reinterpret_cast<int32_t *>(p);
-    p += al256((size_t)Q * 4);
-    w.part = reinterpret_cast<unsigned long long *>(p);
-    p += al256((size_t)tol_topk_max_lists(Q) * (size_t)k * 8);
-    w.local = reinterpret_cast<int32_t *>(p);
-    p += al256(block);
-    w.gathered = reinterpret_cast<int32_t *>(p);
-    p += al256((size_t)(n_ranks > 1 ? n_ranks : 1) * block);
-    w.rest = reinterpret_cast<unsigned char *>(p);
-    w.fixed = (size_t)(p - ((reinterpret_cast<uintptr_t>(base) + 255) & ~(uintptr_t)255)) + 255;
+    const size_t block = (size_t)Q * (size_t)(k + 1) * 3;
+    w.totals = cv.take<int32_t>((size_t)Q);
+    w.part = cv.take<unsigned long long>((size_t)tol_topk_max_lists(Q) * (size_t)k);
+    w.local = cv.take<int32_t>(block);
+    w.gathered = cv.take<int32_t>((size_t)(n_ranks > 1 ? n_ranks : 1) * block);
     return w;
 }
 
 }  // namespace
 
 // used by tvz_comm.hip (same shared object, not exported): sort -> sweep that keeps the k best -> per-query
-// selection.  d_out = NULL writes the block into the workspace's own area; local_out / gathered_out name it and
-// the all-gather's target.
-int tvz_match_tol_topk_local(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
-                             int32_t max_query_len, double tol, int32_t min_match, const int32_t *d_exclude_ids,
-                             int32_t k, int32_t *d_out, void *d_workspace, size_t workspace_bytes, int32_t n_ranks,
-                             void *hip_stream, int32_t **local_out, int32_t **gathered_out) {
-    if (int rc = check_batch_args(c, d_queries, d_q_offsets, Q, max_query_len, 0)) return rc;
+// selection.  d_out = NULL writes the block into the workspace's own area; `blocks` is told where it went and where
+// the all-gather's target is.
+int tvz_match_tol_topk_local(tvz_corpus *c, const Batch &b, double tol, int32_t k, int32_t *d_out, Workspace ws,
+                             int32_t n_ranks, void *hip_stream, ShardBlocks *blocks) {
+    const int32_t Q = b.Q, max_query_len = b.max_query_len, min_match = b.min_match;
+    if (int rc = check_batch_args(c, b, 0)) return rc;
     if (int rc = check_tol(tol)) return rc;
     if (min_match < 1 || min_match > kTop)
         return tvz::fail(TVZ_ERR_UNSUPPORTED, "tolerant top-k: min_match %d outside 1..%d (kth needs the hit lists of "
@@ -1904,64 +1922,46 @@ int tvz_match_tol_topk_local(tvz_corpus *c, const double *d_queries, const int64
         return tvz::fail(TVZ_ERR_UNSUPPORTED, "tolerant top-k: max_query_len %d above %d (use tvz_match_tol)",
                          (int)max_query_len, kTolTopkMaxLen);
     if (Q == 0) return TVZ_OK;
-    const TolTopkWs w = tol_topk_ws_layout(d_workspace, Q, k, n_ranks);
-    const size_t have = d_workspace ? workspace_bytes : 0;
-    const int64_t room = have < w.fixed ? -1 : tol_ws_room(Q, have - w.fixed);
-    if (room < 0)
-        return tvz::fail(TVZ_ERR_WORKSPACE, "tolerant top-k: workspace of %zu bytes, %zu bytes missing (size it with "
-                                            "tvz_match_tol_topk_workspace_bytes)", have, w.fixed + tol_ws_fixed(Q) - have);
-    TVZ_REQUIRE(d_out || local_out, "NULL output");
-    if (d_out == nullptr) d_out = w.local;
-    if (local_out) *local_out = d_out;
-    if (gathered_out) *gathered_out = w.gathered;
-    const TolWs t = tol_ws_layout(w.rest, Q, room);
+    Carver cv(ws.p);
+    const TolTopkWs w = tol_topk_ws_layout(cv, Q, k, n_ranks);
     const int32_t lds_keys = std::max(max_query_len, 1);
     const size_t lds = tol_lds_bytes(lds_keys);
-    TVZ_REQUIRE(lds + kTolTopkStaticLds <= (size_t)kLdsPerWorkgroup,
-                "tolerant top-k sweep: %zu B of dynamic + %d B of static LDS exceed a gfx950 workgroup's", lds,
-                kTolTopkStaticLds);
-    DeviceGuard dg(c->device);
+    auto args_ok = [&]() -> int {
+        TVZ_REQUIRE(d_out || blocks, "NULL output");
+        if (d_out == nullptr) d_out = w.local;
+        if (blocks) *blocks = ShardBlocks{d_out, w.gathered};
+        TVZ_REQUIRE(lds + kTolTopkStaticLds <= (size_t)kLdsPerWorkgroup,
+                    "tolerant top-k sweep: %zu B of dynamic + %d B of static LDS exceed a gfx950 workgroup's", lds,
+                    kTolTopkStaticLds);
+        return TVZ_OK;
+    };
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    // per query: sorted values + positions, counts, hit totals = 0
-    hipLaunchKernelGGL(ts_tol_sort_kernel, dim3((unsigned)tvz::ceil_div(lds_keys, kTolSortBlock), (unsigned)Q),
-                       dim3(kTolSortBlock), 0, st, d_queries, d_q_offsets, max_query_len, t.room, t.sv, t.sp, t.qm,
-                       w.totals);
-    TVZ_HIP(hipGetLastError());
-    std::shared_lock<std::shared_mutex> lk(c->mu);
-    const int64_t n_rows = (int64_t)c->h_rows.size();
-    if (int rc = wait_mutations(c, st)) return rc;
-    // The rows the sweep reads and the lists in front of its own: with cell postings the indexed rows are answered by
-    // the lookup (one list per block of it) and the sweep is left the delta table; the selection takes all lists alike.
-    const Row *sweep_rows = c->rows.p;
-    int64_t sweep_n = n_rows;
-    int lists0 = 0;
-    TolIxShape sh;
-    if (tol_index_usable(c, tol, min_match, lds_keys)) {
-        const Index &ix = c->ix;
-        sh = tol_index_shape(ix.now().n_sub, Q);
-        lists0 = sh.blocks();
-        sweep_rows = ix.now().drows.p;
-        sweep_n = ix.n_delta;
-    }
+    TolCall t;
+    if (int rc = tol_prelude(c, b, TolFront{cv, cv.fixed(), w.totals, "tolerant top-k", "tvz_match_tol_topk_workspace_bytes"},
+                             ws.p ? ws.bytes : 0, 0, st, args_ok, t))
+        return rc;
+    // The lists in front of the sweep's own: one per block of the lookup; the selection takes all lists alike.
+    const TolSorted q{t.ws.sv, t.ws.sp, t.ws.qm, 0, lds_keys, tol};
+    const TolPlan plan = tol_plan(c, b, q, t.n_rows);
+    const int lists0 = plan.lookup ? plan.sh.blocks() : 0;
     // (lists0 <= kTolIxMaxGroups < kTolTopkMinBlocks: the workspace's tol_topk_max_lists(Q) lists still suffice)
-    const int blocks = sweep_n ? std::min(q1_blocks(sweep_n, Q), tol_topk_max_blocks(Q) - lists0) : 0;
-    const int n_lists = lists0 + blocks;
+    const int n_blocks = plan.sweep.n ? std::min(q1_blocks(plan.sweep.n, Q), tol_topk_max_blocks(Q) - lists0) : 0;
+    const int n_lists = lists0 + n_blocks;
     if (lists0)
-        if (int rc = launch_tol_index<true>(c, sh, t.sv, t.sp, d_q_offsets, t.qm, lds_keys,
-                                            Q, tol, min_match, d_exclude_ids, 0, nullptr, w.totals, k, w.part, n_lists, st))
+        if (int rc = launch_tol_index<true>(c, plan.sh, b, q, HitSink::dense(0, nullptr, w.totals), k, w.part, n_lists, st))
             return rc;
-    if (blocks) {
-        const dim3 grid((unsigned)blocks, (unsigned)Q);
+    if (n_blocks) {
+        const dim3 grid((unsigned)n_blocks, (unsigned)Q);
         if (int rc = by_mode<false>(min_match, [&](auto mode) {
-                hipLaunchKernelGGL((ts_tol_topk_kernel<mode.value>), grid, dim3(kTolBlock), lds, st, sweep_rows, sweep_n,
-                                   c->keys.p, t.sv, t.sp, d_q_offsets, t.qm, lds_keys, tol, min_match, d_exclude_ids, k,
+                hipLaunchKernelGGL((ts_tol_topk_kernel<mode.value>), grid, dim3(kTolBlock), lds, st, plan.sweep.p, plan.sweep.n,
+                                   c->keys.p, q.sv, q.sp, b.d_q_offsets, q.qm, lds_keys, tol, min_match, b.d_exclude_ids, k,
                                    w.part, n_lists, lists0, w.totals);
                 return launched();
             }))
             return rc;
     }
     hipLaunchKernelGGL(ts_tol_topk_reduce_kernel, dim3((unsigned)Q), dim3(kTolReduceBlock), 0, st, w.part, n_lists, k,
-                       t.qm, lds_keys, w.totals, d_out);
+                       q.qm, lds_keys, w.totals, d_out);
     TVZ_HIP(hipGetLastError());
     return record(c, st);
 }
@@ -1971,42 +1971,35 @@ static int tvz_match_tol_topk_impl(tvz_corpus *c, const double *d_queries, const
                                    const int32_t *d_exclude_ids, int32_t k, int32_t *d_out, void *d_workspace,
                                    size_t workspace_bytes, void *hip_stream) {
     TVZ_REQUIRE(Q <= 0 || d_out != nullptr, "d_out is NULL");
-    return tvz_match_tol_topk_local(c, d_queries, d_q_offsets, Q, max_query_len, tol, min_match, d_exclude_ids, k,
-                                    d_out, d_workspace, workspace_bytes, 1, hip_stream, nullptr, nullptr);
+    return tvz_match_tol_topk_local(c, Batch{d_queries, d_q_offsets, Q, max_query_len, min_match, d_exclude_ids}, tol, k,
+                                    d_out, Workspace{d_workspace, workspace_bytes}, 1, hip_stream, nullptr);
 }
 
 // ---- alignment top-k (tvz_align_kernels.h) ------------------------------------------------------------------
 namespace {
 
-// Workspace of tvz_align_topk, in front of the sorted queries (tvz_match_tol's layout, which takes the rest): the
-// queries' hit totals and one kept list - k words and k payloads - per sweep block.  The sizing function knows no row
-// count: the lists are sized by the grid's upper bound, as the tolerant top-k's are.
+// Workspace of tvz_align_topk, in front of the sorted queries (TolWs, which takes the rest): the queries' hit totals
+// and one kept list - k words and k payloads - per sweep block.  The sizing function knows no row count: the lists are
+// sized by the grid's upper bound, as the tolerant top-k's are.
 struct AlignTopkWs {
     int32_t *totals = nullptr;             // [Q]
     unsigned long long *part_w = nullptr;  // [Q][blocks][k]
     unsigned long long *part_p = nullptr;  // [Q][blocks][k]
-    unsigned char *rest = nullptr;         // the sorted queries
-    size_t fixed = 0;                      // bytes in front of `rest`, the base's alignment included
 };
 
-AlignTopkWs align_topk_ws_layout(void *base, int32_t Q, int32_t k) {
+AlignTopkWs align_topk_ws_layout(Carver &cv, int32_t Q, int32_t k) {
     AlignTopkWs w;
-    const uintptr_t p0 = (reinterpret_cast<uintptr_t>(base) + 255) & ~(uintptr_t)255;
-    uintptr_t p = p0;
-    const size_t lists = al256((size_t)tol_topk_max_lists(Q) * (size_t)k * 8);
-    w.totals = reinterpret_cast<int32_t *>(p);
-    p += al256((size_t)Q * 4);
-    w.part_w = reinterpret_cast<unsigned long long *>(p);
-    p += lists;
-    w.part_p = reinterpret_cast<unsigned long long *>(p);
-    p += lists;
-    w.rest = reinterpret_cast<unsigned char *>(p);
-    w.fixed = (size_t)(p - p0) + 255;
+    const size_t lists = (size_t)tol_topk_max_lists(Q) * (size_t)k;
+    w.totals = cv.take<int32_t>((size_t)Q);
+    w.part_w = cv.take<unsigned long long>(lists);
+    w.part_p = cv.take<unsigned long long>(lists);
     return w;
 }
 
 size_t align_topk_ws_bytes(int32_t Q, int64_t keys, int32_t k) {
-    return align_topk_ws_layout(nullptr, Q, k).fixed + tol_ws_fixed(Q) + (size_t)keys * 12;
+    Carver cv(nullptr);
+    align_topk_ws_layout(cv, Q, k);
+    return cv.fixed() + tol_ws_bytes(Q, keys);
 }
 
 }  // namespace
@@ -2015,11 +2008,10 @@ static int tvz_align_topk_impl(tvz_corpus *c, const double *d_queries, const int
                                int32_t max_query_len, double eps, double max_offset, int32_t min_votes,
                                int32_t min_score, const int32_t *d_exclude_ids, int32_t k, int32_t *d_out,
                                void *d_workspace, size_t workspace_bytes, void *hip_stream) {
-    if (int rc = check_batch_args(c, d_queries, d_q_offsets, Q, max_query_len, 0)) return rc;
-    TVZ_REQUIRE(eps > 0.0 && max_offset >= 0.0, "eps must be > 0 and max_offset >= 0");
-    const double nb = floor(max_offset / eps + 0.5);
-    if (!(2 * nb + 1 <= kAlignMaxBins))                 // also refuses NaN (eps = max_offset = inf)
-        return tvz::fail(TVZ_ERR_UNSUPPORTED, "max_offset/eps = %.0f needs more than %d bins", nb, kAlignMaxBins);
+    const Batch b{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids};
+    if (int rc = check_batch_args(c, b, 0)) return rc;
+    int32_t B = 0;
+    if (int rc = check_align_bins(eps, max_offset, &B)) return rc;
     TVZ_REQUIRE(min_votes >= 1, "alignment top-k: min_votes %d below 1", (int)min_votes);
     TVZ_REQUIRE(min_score >= 0 && min_score <= kAlScoreOne, "alignment top-k: min_score %d outside 0..%d", (int)min_score,
                 kAlScoreOne);
@@ -2028,39 +2020,33 @@ static int tvz_align_topk_impl(tvz_corpus *c, const double *d_queries, const int
     if (max_query_len > kAlMaxLen)
         return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment top-k: max_query_len %d above %d", (int)max_query_len, kAlMaxLen);
     if (Q == 0) return TVZ_OK;
-    // the fixed parts and room for ONE query of max_query_len values; what the caller gave beyond that holds more
-    const size_t have = d_workspace ? workspace_bytes : 0;
-    const size_t least = align_topk_ws_bytes(Q, max_query_len, k);
-    if (have < least)
-        return tvz::fail(TVZ_ERR_WORKSPACE, "alignment top-k: workspace of %zu bytes, %zu bytes missing (size it with "
-                                            "tvz_align_topk_workspace_bytes)", have, least - have);
-    TVZ_REQUIRE(d_out != nullptr, "d_out is NULL");
-    const AlignTopkWs w = align_topk_ws_layout(d_workspace, Q, k);
-    const TolWs t = tol_ws_layout(w.rest, Q, tol_ws_room(Q, have - w.fixed));
-    const int32_t B = (int32_t)nb;
+    Carver cv(d_workspace);
+    const AlignTopkWs w = align_topk_ws_layout(cv, Q, k);
     const int32_t lds_keys = std::max(max_query_len, 1);
     const size_t lds = al_lds_bytes(lds_keys, B);
-    TVZ_REQUIRE(lds + kAlStaticLds <= (size_t)kLdsPerWorkgroup,
-                "alignment top-k sweep: %zu B of dynamic + %d B of static LDS exceed a gfx950 workgroup's", lds, kAlStaticLds);
-    DeviceGuard dg(c->device);
+    auto args_ok = [&]() -> int {
+        TVZ_REQUIRE(d_out != nullptr, "d_out is NULL");
+        TVZ_REQUIRE(lds + kAlStaticLds <= (size_t)kLdsPerWorkgroup,
+                    "alignment top-k sweep: %zu B of dynamic + %d B of static LDS exceed a gfx950 workgroup's", lds, kAlStaticLds);
+        return TVZ_OK;
+    };
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    // per query: sorted values (+ positions, unused here), counts, hit totals = 0
-    hipLaunchKernelGGL(ts_tol_sort_kernel, dim3((unsigned)tvz::ceil_div(lds_keys, kTolSortBlock), (unsigned)Q),
-                       dim3(kTolSortBlock), 0, st, d_queries, d_q_offsets, max_query_len, t.room, t.sv, t.sp, t.qm,
-                       w.totals);
-    TVZ_HIP(hipGetLastError());
-    std::shared_lock<std::shared_mutex> lk(c->mu);
-    const int64_t n_rows = (int64_t)c->h_rows.size();
-    if (int rc = wait_mutations(c, st)) return rc;
+    // the fixed parts and room for ONE query of max_query_len values; what the caller gave beyond that holds more
+    // (the sorted positions are unused here)
+    TolCall t;
+    if (int rc = tol_prelude(c, b, TolFront{cv, cv.fixed(), w.totals, "alignment top-k", "tvz_align_topk_workspace_bytes"},
+                             d_workspace ? workspace_bytes : 0, max_query_len, st, args_ok, t))
+        return rc;
+    const int64_t n_rows = t.n_rows;
     const int blocks = n_rows ? (int)std::min<int64_t>(tvz::ceil_div(n_rows, (int64_t)kAlWaves), tol_topk_max_blocks(Q)) : 0;
     if (blocks) {
         hipLaunchKernelGGL(ts_align_topk_kernel, dim3((unsigned)blocks, (unsigned)Q), dim3(kAlBlock), lds, st, c->rows.p,
-                           n_rows, c->keys.p, t.sv, d_q_offsets, t.qm, lds_keys, eps, B, min_votes, min_score,
+                           n_rows, c->keys.p, t.ws.sv, d_q_offsets, t.ws.qm, lds_keys, eps, B, min_votes, min_score,
                            d_exclude_ids, k, w.part_w, w.part_p, blocks, w.totals);
         TVZ_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(ts_align_topk_reduce_kernel, dim3((unsigned)Q), dim3(kAlReduceBlock), 0, st, w.part_w, w.part_p,
-                       blocks, k, t.qm, lds_keys, w.totals, d_out);
+                       blocks, k, t.ws.qm, lds_keys, w.totals, d_out);
     TVZ_HIP(hipGetLastError());
     return record(c, st);
 }
@@ -2079,13 +2065,13 @@ TVZ_EXPORT int tvz_debug_ix_stamps(unsigned long long *out16) {
 TVZ_EXPORT size_t tvz_match_workspace_bytes(int32_t Q, int32_t max_query_len, int32_t cap, int32_t k,
                                             int32_t n_ranks) {
     if (Q < 0 || max_query_len < 0 || cap < 0 || k < 0) return 0;
-    return ws_layout(nullptr, Q, max_query_len, cap, k, n_ranks).total;
+    return ws_layout(nullptr, 0, Q, max_query_len, cap, k, n_ranks).total;
 }
 
 TVZ_EXPORT size_t tvz_match_workspace_bytes_long(int32_t Q, int32_t max_query_len, int32_t cap, int32_t k,
                                                  int32_t n_ranks, int64_t total_query_keys) {
     if (Q < 0 || max_query_len < 0 || cap < 0 || k < 0 || total_query_keys < 0) return 0;
-    return ws_layout(nullptr, Q, max_query_len, cap, k, n_ranks, std::max<int64_t>(total_query_keys, max_query_len)).total;
+    return ws_layout(nullptr, 0, Q, max_query_len, cap, k, n_ranks, std::max<int64_t>(total_query_keys, max_query_len)).total;
 }
 
 TVZ_EXPORT int tvz_corpus_create(tvz_corpus **out, int device) {
@@ -2234,7 +2220,7 @@ TVZ_EXPORT int tvz_find_duplicates_tol(tvz_corpus *c, const double *h_query, int
 TVZ_EXPORT size_t tvz_match_tol_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys) {
     if (Q < 0 || max_query_len < 0 || total_query_keys < 0) return 0;
     const int64_t keys = total_query_keys > 0 ? total_query_keys : (int64_t)Q * max_query_len;
-    return tol_ws_fixed(Q) + (size_t)keys * 12;          // tol_ws_room() of this many bytes is `keys`
+    return tol_ws_bytes(Q, keys);
 }
 
 TVZ_EXPORT int tvz_match_tol(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
@@ -2248,8 +2234,9 @@ TVZ_EXPORT int tvz_match_tol(tvz_corpus *c, const double *d_queries, const int64
 TVZ_EXPORT size_t tvz_match_tol_topk_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys,
                                                      int32_t k, int32_t n_ranks) {
     if (Q < 0 || max_query_len < 0 || total_query_keys < 0 || k < 1 || n_ranks < 0) return 0;
-    return tol_topk_ws_layout(nullptr, Q, k, n_ranks).fixed +
-           tvz_match_tol_workspace_bytes(Q, max_query_len, total_query_keys);
+    Carver cv(nullptr);
+    tol_topk_ws_layout(cv, Q, k, n_ranks);
+    return cv.fixed() + tvz_match_tol_workspace_bytes(Q, max_query_len, total_query_keys);
 }
 
 TVZ_EXPORT int tvz_match_tol_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
