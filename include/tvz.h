@@ -420,6 +420,49 @@ int tvz_align_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q_of
                    int32_t min_score, const int32_t *d_exclude_ids, int32_t k, int32_t *d_out,
                    void *d_workspace, size_t workspace_bytes, void *hip_stream);
 
+/* The alignment top-k over a SHARDED table.  The block of tvz_align_topk is what travels: int32[Q][k+1][4], k rows
+ * ascending in the order above, padding, then (-1, n_hits, 0, 0).  (TVZ_VERSION unchanged: new exports only.)
+ *
+ * tvz_align_topk_merge: d_gathered int32[n_lists][Q][k+1][4] (the shards' blocks, as an all-gather delivers them) ->
+ * d_topk int32[Q][k][4], d_totals int32[Q].  A block row does not carry its order word: the score depends on nv, the
+ * query's non-NaN count, which no block holds - so the merge takes the queries too, counts nv and rebuilds every
+ * row's word with the expressions above.  Rules:
+ *   - the k rows are the k smallest of the union by (word, row_len, votes); rows equal in all of that are identical
+ *     rows and are all kept; fewer than k: padding rows (-1, 0, 0, 0) behind them;
+ *   - a row with video_id < 0 is padding wherever it stands; so is a row whose u = nv + row_len - v would be 0
+ *     (nv = 0 and row_len = 0: tvz_align_topk never writes one) - nothing divides by zero;
+ *   - every list must be sorted as tvz_align_topk writes it (the merge stops reading a list at the first row that
+ *     does not come before the k-th kept);
+ *   - d_totals[q] = the lists' n_hits summed in 64 bits, clamped to INT32_MAX;
+ *   - a query is REFUSED - all k rows padding, d_totals[q] = INT32_MIN - when any list's n_hits is negative (a shard
+ *     refused it) or it is longer than 4,095 values.
+ * n_lists outside 1..16 or k outside 1..64: TVZ_ERR_UNSUPPORTED; a NULL pointer, a negative Q, d_gathered or d_topk
+ * not 16-byte aligned: TVZ_ERR_INVALID; nothing is written on a refusal; Q = 0 returns TVZ_OK.  Enqueues one launch. */
+int tvz_align_topk_merge(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t k, const double *d_queries,
+                         const int64_t *d_q_offsets, int32_t *d_topk, int32_t *d_totals, void *hip_stream);
+/* The shards of ONE process (several handles on one device, as tvz_match_topk_shards): tvz_align_topk on every handle
+ * in turn on `hip_stream`, the blocks written to d_blocks int32[n_shards][Q][k+1][4], then tvz_align_topk_merge ->
+ * d_topk, d_totals.  One workspace sized for ONE handle (tvz_align_topk_workspace_bytes) serves all of them.  Refuses
+ * what tvz_align_topk and the merge refuse (n_shards outside 1..16 included) before anything is enqueued. */
+int tvz_align_topk_shards(tvz_corpus *const *shards, int32_t n_shards, const double *d_queries,
+                          const int64_t *d_q_offsets, int32_t Q, int32_t max_query_len, double eps, double max_offset,
+                          int32_t min_votes, int32_t min_score, const int32_t *d_exclude_ids, int32_t k,
+                          int32_t *d_blocks, int32_t *d_topk, int32_t *d_totals, void *d_workspace,
+                          size_t workspace_bytes, void *hip_stream);
+/* One process per GPU: tvz_align_topk into the workspace's own block -> the ONE ncclAllGather of Q x (k+1) x 4 int32
+ * per rank, ordered on the communicator with the other sharded calls' collectives -> tvz_align_topk_merge; every rank
+ * gets the same d_topk int32[Q][k][4] and d_totals int32[Q].  Up to 16 ranks.
+ * Workspace = tvz_align_topk_workspace_bytes(Q, max_query_len, total_query_keys, k)
+ *           + (1 + max(n_ranks, 1)) x Q x (k + 1) x 16                                  (local + gathered blocks)
+ *           + alignment (each part to 256 B).
+ * Has run on hardware at ONE rank only. */
+size_t tvz_align_topk_sharded_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k,
+                                              int32_t n_ranks);
+int tvz_align_topk_sharded(tvz_corpus *c, tvz_comm *comm, const double *d_queries, const int64_t *d_q_offsets,
+                           int32_t Q, int32_t max_query_len, double eps, double max_offset, int32_t min_votes,
+                           int32_t min_score, const int32_t *d_exclude_ids, int32_t k, int32_t *d_topk,
+                           int32_t *d_totals, void *d_workspace, size_t workspace_bytes, void *hip_stream);
+
 /* ------------------------------------------------------------------------
  * Opt-in TOLERANT duplicate match.  NOT the reference's verdict: db.py:79,85-91 match exact float64
  * values, and that stays the default everywhere (tolerance 0).  README.md:291 promises "0.1 second

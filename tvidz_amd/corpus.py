@@ -68,6 +68,14 @@ def align_topk_workspace_bytes(Q: int, max_query_len: int, total_query_keys: int
     return int(_lib.load().tvz_align_topk_workspace_bytes(int(Q), int(max_query_len), int(total_query_keys), int(k)))
 
 
+def align_topk_sharded_workspace_bytes(Q: int, max_query_len: int, total_query_keys: int = 0, k: int = 16,
+                                       n_ranks: int = 1) -> int:
+    """tvz_align_topk_sharded_workspace_bytes: align_topk_workspace_bytes + the local block and `n_ranks` gathered ones
+    (Q x (k + 1) x 16 bytes each)."""
+    return int(_lib.load().tvz_align_topk_sharded_workspace_bytes(int(Q), int(max_query_len), int(total_query_keys),
+                                                                  int(k), int(n_ranks)))
+
+
 ALIGN_SCORE_ONE = 1 << 20
 ALIGN_TOPK_MAX_LEN = 4095
 ALIGN_REFUSED = -(1 << 31)                  # a query's total when tvz_align_topk refused it (INT32_MIN)
@@ -276,6 +284,24 @@ class DeviceCorpus:
         h = out.cpu().numpy()
         return np.ascontiguousarray(h[:, :k]), np.ascontiguousarray(h[:, k, 1])
 
+    def align_topk_block(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, eps: float,
+                         max_offset: float, k: int, min_votes: int = 1, min_score: int = 0,
+                         d_exclude_ids: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                         stream: Optional[torch.cuda.Stream] = None,
+                         workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """tvz_align_topk, device in / device out: enqueue Q queries -> the block int32 [Q, k+1, 4] that the sharded
+        forms gather and merge (align_topk_merge)."""
+        dev, Q = self._check_queries(d_queries, d_q_offsets)
+        if out is None:
+            out = torch.empty((Q, k + 1, 4), dtype=torch.int32, device=dev)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        ws = self._workspace(workspace, align_topk_workspace_bytes(Q, max_query_len, d_queries.numel(), k), dev, s)
+        _lib.check(self.lib.tvz_align_topk(
+            self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps), float(max_offset),
+            int(min_votes), int(min_score), d_exclude_ids.data_ptr() if d_exclude_ids is not None else None, int(k),
+            out.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
+        return out
+
     # ---- batched, device resident ----
     def _check_queries(self, d_queries, d_q_offsets):
         dev = d_queries.device
@@ -454,6 +480,26 @@ class Comm:
         return merged, totals
 
 
+    def align_topk_sharded(self, corpus: DeviceCorpus, d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
+                           max_query_len: int, *, eps: float, max_offset: float, k: int, min_votes: int = 1,
+                           min_score: int = 0, d_exclude_ids: Optional[torch.Tensor] = None,
+                           workspace: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
+                           out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+        """tvz_align_topk_sharded: the local alignment top-k -> ncclAllGather of the [Q,k+1,4] blocks -> the merge;
+        -> (rows int32 [Q,k,4], totals int32 [Q]), identical on every rank."""
+        dev, Q = corpus._check_queries(d_queries, d_q_offsets)
+        rows, totals = _align_out(out, Q, k, dev)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        ws = corpus._workspace(workspace, align_topk_sharded_workspace_bytes(Q, max_query_len, d_queries.numel(), k,
+                                                                             self.n_ranks), dev, s)
+        _lib.check(self.lib.tvz_align_topk_sharded(
+            corpus._h, self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps),
+            float(max_offset), int(min_votes), int(min_score),
+            d_exclude_ids.data_ptr() if d_exclude_ids is not None else None, int(k), rows.data_ptr(), totals.data_ptr(),
+            ws.data_ptr(), ws.numel(), s.cuda_stream))
+        return rows, totals
+
+
 def topk(lists: torch.Tensor, lists_n: Optional[torch.Tensor], k: int,
          out: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
     """Per-query k best hits ordered by (kth, video_id, count).
@@ -518,6 +564,53 @@ def topk_merge(gathered: torch.Tensor, k: int, stream: Optional[torch.cuda.Strea
         _lib.check(_lib.load().tvz_topk_merge(gathered.data_ptr(), R, Q, k, out.data_ptr(),
                                               totals.data_ptr(), s.cuda_stream))
     return out, totals
+
+
+def _align_out(out, Q: int, k: int, dev):
+    if out is not None:
+        rows, totals = out
+        if rows.shape != (Q, k, 4) or totals.shape != (Q,) or rows.dtype != torch.int32 \
+                or totals.dtype != torch.int32 or not rows.is_contiguous():
+            raise RuntimeError("out must be (int32 [Q,k,4], int32 [Q])")
+        return rows, totals
+    return torch.empty((Q, k, 4), dtype=torch.int32, device=dev), torch.empty(Q, dtype=torch.int32, device=dev)
+
+
+def align_topk_merge(gathered: torch.Tensor, k: int, d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
+                     stream: Optional[torch.cuda.Stream] = None, out=None):
+    """tvz_align_topk_merge: the shards' blocks int32 [R,Q,k+1,4] (+ the queries: the order word needs their non-NaN
+    counts) -> (rows int32 [Q,k,4], totals int32 [Q]; ALIGN_REFUSED for a query some shard refused)."""
+    R, Q, k1, w = gathered.shape
+    if k1 != k + 1 or w != 4 or gathered.dtype != torch.int32 or not gathered.is_contiguous():
+        raise RuntimeError("gathered must be a contiguous int32 [R,Q,k+1,4]")
+    rows, totals = _align_out(out, Q, k, gathered.device)
+    s = stream if stream is not None else torch.cuda.current_stream(gathered.device)
+    with torch.cuda.device(gathered.device):
+        _lib.check(_lib.load().tvz_align_topk_merge(gathered.data_ptr(), R, Q, int(k), d_queries.data_ptr(),
+                                                    d_q_offsets.data_ptr(), rows.data_ptr(), totals.data_ptr(),
+                                                    s.cuda_stream))
+    return rows, totals
+
+
+def align_topk_shards(shards: Sequence["DeviceCorpus"], d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
+                      max_query_len: int, *, eps: float, max_offset: float, k: int, workspace: torch.Tensor,
+                      min_votes: int = 1, min_score: int = 0, d_exclude_ids: Optional[torch.Tensor] = None,
+                      stream: Optional[torch.cuda.Stream] = None):
+    """tvz_align_topk on every handle of ONE device + the merge behind one library call (tvz_align_topk_shards):
+    -> (blocks int32 [R,Q,k+1,4], rows int32 [Q,k,4], totals int32 [Q]).  `workspace`: align_topk_workspace_bytes."""
+    dev = d_queries.device
+    R, Q = len(shards), d_q_offsets.numel() - 1
+    blocks = torch.empty((R, Q, k + 1, 4), dtype=torch.int32, device=dev)
+    rows, totals = _align_out(None, Q, k, dev)
+    handles = (C.c_void_p * R)(*[s._h for s in shards])
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().tvz_align_topk_shards(
+            handles, R, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps),
+            float(max_offset), int(min_votes), int(min_score),
+            d_exclude_ids.data_ptr() if d_exclude_ids is not None else None, int(k), blocks.data_ptr(), rows.data_ptr(),
+            totals.data_ptr(), workspace.data_ptr(), workspace.numel(), s.cuda_stream))
+    return blocks, rows, totals
 
 
 def pack_queries(queries: Sequence[Sequence[float]], device) -> Tuple[torch.Tensor, torch.Tensor, int]:

@@ -264,4 +264,88 @@ __global__ __launch_bounds__(kAlReduceBlock) void ts_align_topk_reduce_kernel(
     }
 }
 
+// ---- the merge of the shards' blocks (tvz_align_topk_merge) ----------------------------------------------------
+constexpr int kAlMergeBlock = 256;
+constexpr int kAlMergeWaves = kAlMergeBlock / 64;      // queries per block: a wave each
+constexpr int kAlMergeMaxLists = 16;                   // one n_hits per lane, far below a wave
+
+// A list held one entry per lane whose padding may stand ANYWHERE (`live`: the lanes that hold a hit): the live
+// entries are offered in lane order until one is refused.  As al_take, the early exit needs the live entries
+// ascending - which every block of ts_align_topk_reduce_kernel is, by contract.
+__device__ __forceinline__ void al_take_live(unsigned long long &kw, unsigned long long &kp, unsigned long long ew,
+                                             unsigned long long ep, unsigned long long live, int k, int lane) {
+    while (live) {                                                 // wave-uniform
+        const int e = __ffsll((long long)live) - 1;
+        live &= live - 1;
+        if (!al_insert(kw, kp, __shfl(ew, e), __shfl(ep, e), k, lane)) break;
+    }
+}
+
+// gathered int32[n_lists][Q][k+1][4], every [k+1][4] block as ts_align_topk_reduce_kernel writes it (k rows ascending
+// in the contract's order, padding, then (-1, n_hits, 0, 0)) -> d_topk int32[Q][k][4], d_totals int32[Q].
+// One wave per query, no LDS, no barrier.  A block row does not carry its order word - the score depends on nv, the
+// query's count of non-NaN values, which no block holds - so the wave counts nv from the query itself and rebuilds
+// (word, payload) with the sweep's expressions; a row with video_id < 0 is padding wherever it stands, and so is one
+// whose u = nv + row_len - v would be 0 (nothing divides by zero).  The lists are SORTED BY CONTRACT: that is the
+// precondition of the fold's early exit (al_take_live, as al_take).  Equal (word, payload) are identical rows and
+// are all kept.  d_totals[q] = the lists' n_hits summed in 64 bits, clamped to INT32_MAX.  Refused - all k rows
+// padding, d_totals[q] = INT32_MIN - when a list's n_hits is negative (INT32_MIN: a rank refused the query) or the
+// query is longer than kAlMaxLen.  n_lists <= kAlMergeMaxLists, k <= kAlMaxK; gathered and d_topk 16-byte aligned.
+__global__ __launch_bounds__(kAlMergeBlock) void ts_align_topk_merge_kernel(
+    const int32_t *__restrict__ gathered, int32_t n_lists, int32_t Q, int32_t k, const double *__restrict__ queries,
+    const int64_t *__restrict__ q_offsets, int32_t *__restrict__ d_topk, int32_t *__restrict__ d_totals) {
+    const int lane = threadIdx.x & 63;
+    const int q = blockIdx.x * kAlMergeWaves + (threadIdx.x >> 6);
+    if (q >= Q) return;                                            // wave-uniform
+    const int64_t k1 = (int64_t)k + 1;
+    const int4 *blocks = reinterpret_cast<const int4 *>(gathered);            // [n_lists][Q][k+1] rows of 16 bytes
+    // the lists' totals, one per lane; a negative one refuses the query
+    const int32_t nh = lane < n_lists ? gathered[(((int64_t)lane * Q + q) * k1 + k) * 4 + 1] : 0;
+    long long total = nh;
+    for (int off = 32; off > 0; off >>= 1) total += __shfl_xor(total, off);
+    const int64_t qo = q_offsets[q];
+    const int64_t len = q_offsets[q + 1] - qo;
+    const bool refused = __ballot(nh < 0) != 0ull || len > kAlMaxLen;
+    unsigned long long kw = kAlPad, kp = kAlPad;
+    if (!refused) {
+        int32_t nvl = 0;
+        for (int64_t e = lane; e < len; e += 64) {
+            const double x = queries[qo + e];
+            nvl += x == x ? 1 : 0;
+        }
+        for (int off = 32; off > 0; off >>= 1) nvl += __shfl_xor(nvl, off);
+        const uint32_t nv = (uint32_t)nvl;
+        for (int l0 = 0; l0 < n_lists; l0 += kAlReduceLd) {        // wave-uniform
+            int4 row[kAlReduceLd];
+#pragma unroll
+            for (int j = 0; j < kAlReduceLd; ++j) {                // the loads of kAlReduceLd lists in flight together
+                const int l = l0 + j;
+                row[j] = l < n_lists && lane < k ? blocks[((int64_t)l * Q + q) * k1 + lane] : make_int4(-1, 0, 0, 0);
+            }
+#pragma unroll
+            for (int j = 0; j < kAlReduceLd; ++j) {
+                const uint32_t rl = (uint32_t)row[j].y, votes = (uint32_t)row[j].w;
+                uint32_t v = votes < nv ? votes : nv;
+                v = v < rl ? v : rl;
+                const uint32_t u = nv + rl - v;
+                const bool hit = row[j].x >= 0 && u != 0u;
+                const uint32_t score = hit ? (v << 20) / u : 0u;   // v <= nv <= 4095: the shift fits 32 bits
+                const unsigned long long ew = hit ? al_word(score, row[j].x, row[j].z) : kAlPad;
+                const unsigned long long ep = hit ? ((unsigned long long)rl << 32) | votes : kAlPad;
+                al_take_live(kw, kp, ew, ep, __ballot(hit), k, lane);
+            }
+        }
+    }
+    if (lane < k) {
+        const bool pad = kw == kAlPad;
+        int4 o;
+        o.x = pad ? -1 : (int32_t)((kw >> 12) & 0x7fffffffu);
+        o.y = pad ? 0 : (int32_t)(kp >> 32);
+        o.z = pad ? 0 : (int32_t)(kw & 0xfffu) - 2048;
+        o.w = pad ? 0 : (int32_t)(kp & 0xffffffffu);
+        reinterpret_cast<int4 *>(d_topk)[(int64_t)q * k + lane] = o;
+    }
+    if (lane == 0) d_totals[q] = refused ? INT32_MIN : (int32_t)(total > INT32_MAX ? INT32_MAX : total);
+}
+
 }  // namespace

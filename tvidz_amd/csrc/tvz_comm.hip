@@ -126,12 +126,13 @@ static int tvz_comm_destroy_impl(tvz_comm *comm) {
     return TVZ_OK;
 }
 
-// The exchange behind a local per-shard top-k: ONE ncclAllGather of the ranks' int32[Q][k+1][3] blocks on
-// `hip_stream`, ordered behind the communicator's previous collective, then the merge every rank runs alike.
-static int gather_and_merge(tvz_comm *comm, const int32_t *local, int32_t *gathered, int32_t Q, int32_t k,
-                            int32_t *d_topk, int32_t *d_totals, void *hip_stream) {
+// The exchange behind a local per-shard top-k: ONE ncclAllGather of the ranks' blocks of `count` int32 (Q x (k+1) rows
+// of 3, of 4 for the alignment top-k) on `hip_stream`, ordered behind the communicator's previous collective, then
+// `merge`, which every rank runs alike on the gathered blocks.
+template <typename Merge>
+static int gather_and_merge(tvz_comm *comm, const int32_t *local, int32_t *gathered, size_t count, void *hip_stream,
+                            Merge &&merge) {
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    const size_t count = (size_t)Q * (size_t)(k + 1) * 3;
     // RCCL enqueues on the communicator's device: make it current for the call (a host that drives
     // several GPUs from one thread may have another one selected)
     int prev = -1;
@@ -150,10 +151,20 @@ static int gather_and_merge(tvz_comm *comm, const int32_t *local, int32_t *gathe
             comm->any = true;
         }
     }
+    // the merge is launched like the collective, with the communicator's device current
+    const int mrc = herr == hipSuccess && !grc ? merge() : TVZ_OK;
     if (prev >= 0 && prev != comm->device) (void)hipSetDevice(prev);
     if (herr != hipSuccess) return tvz::fail(TVZ_ERR_HIP, "ordering the collective failed: %s", hipGetErrorString(herr));
     if (grc) return nccl_fail("ncclAllGather", grc);
-    return tvz_topk_merge(gathered, comm->n_ranks, Q, k, d_topk, d_totals, hip_stream);
+    return mrc;
+}
+
+// the merge of the exact and the tolerant match: blocks of rows of 3
+static int gather_and_merge_topk(tvz_comm *comm, const ShardBlocks &blk, int32_t Q, int32_t k, int32_t *d_topk,
+                                 int32_t *d_totals, void *hip_stream) {
+    return gather_and_merge(comm, blk.local, blk.gathered, (size_t)Q * (size_t)(k + 1) * 3, hip_stream, [&] {
+        return tvz_topk_merge(blk.gathered, comm->n_ranks, Q, k, d_topk, d_totals, hip_stream);
+    });
 }
 
 static int tvz_match_sharded_impl(tvz_corpus *c, tvz_comm *comm, const double *d_queries,
@@ -170,7 +181,7 @@ static int tvz_match_sharded_impl(tvz_corpus *c, tvz_comm *comm, const double *d
                                       nullptr, Workspace{d_workspace, workspace_bytes}, comm->n_ranks, algo, hip_stream,
                                       &blk))
         return rc;
-    return gather_and_merge(comm, blk.local, blk.gathered, Q, k, d_topk, d_totals, hip_stream);
+    return gather_and_merge_topk(comm, blk, Q, k, d_topk, d_totals, hip_stream);
 }
 
 static int tvz_match_tol_sharded_impl(tvz_corpus *c, tvz_comm *comm, const double *d_queries,
@@ -187,7 +198,29 @@ static int tvz_match_tol_sharded_impl(tvz_corpus *c, tvz_comm *comm, const doubl
                                           &blk))
         return rc;
     if (Q == 0) return TVZ_OK;
-    return gather_and_merge(comm, blk.local, blk.gathered, Q, k, d_topk, d_totals, hip_stream);
+    return gather_and_merge_topk(comm, blk, Q, k, d_topk, d_totals, hip_stream);
+}
+
+static int tvz_align_topk_sharded_impl(tvz_corpus *c, tvz_comm *comm, const double *d_queries,
+                                       const int64_t *d_q_offsets, int32_t Q, int32_t max_query_len, double eps,
+                                       double max_offset, int32_t min_votes, int32_t min_score,
+                                       const int32_t *d_exclude_ids, int32_t k, int32_t *d_topk, int32_t *d_totals,
+                                       void *d_workspace, size_t workspace_bytes, void *hip_stream) {
+    TVZ_REQUIRE(comm != nullptr && comm->comm != nullptr, "communicator is NULL");
+    TVZ_REQUIRE(Q <= 0 || (d_topk != nullptr && d_totals != nullptr), "d_topk or d_totals is NULL");
+    TVZ_REQUIRE((reinterpret_cast<uintptr_t>(d_topk) & 15) == 0, "d_topk must be 16-byte aligned");
+    if (comm->n_ranks > 16)          // (the merge's limit: refused here, before the local sweep is enqueued)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment top-k: %d ranks, the merge takes up to 16", (int)comm->n_ranks);
+    ShardBlocks blk;
+    // the sweep keeps its k best itself and writes them into the workspace's own block
+    if (int rc = tvz_align_topk_local(c, Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids},
+                                      AlignCall{eps, max_offset, min_votes, min_score}, k, nullptr,
+                                      Workspace{d_workspace, workspace_bytes}, comm->n_ranks, hip_stream, &blk))
+        return rc;
+    if (Q == 0) return TVZ_OK;
+    return gather_and_merge(comm, blk.local, blk.gathered, (size_t)Q * (size_t)(k + 1) * 4, hip_stream, [&] {
+        return tvz_align_topk_merge(blk.gathered, comm->n_ranks, Q, k, d_queries, d_q_offsets, d_topk, d_totals, hip_stream);
+    });
 }
 
 TVZ_EXPORT int tvz_comm_unique_id(void *out_id) { TVZ_GUARDED(tvz_comm_unique_id_impl(out_id)); }
@@ -219,4 +252,11 @@ TVZ_EXPORT int tvz_match_tol_sharded(tvz_corpus *c, tvz_comm *comm, const double
                                      int32_t min_match, const int32_t *d_exclude_ids, int32_t k, int32_t *d_topk,
                                      int32_t *d_totals, void *d_workspace, size_t workspace_bytes, void *hip_stream) {
     TVZ_GUARDED(tvz_match_tol_sharded_impl(c, comm, d_queries, d_q_offsets, Q, max_query_len, tol, min_match, d_exclude_ids, k, d_topk, d_totals, d_workspace, workspace_bytes, hip_stream));
+}
+
+TVZ_EXPORT int tvz_align_topk_sharded(tvz_corpus *c, tvz_comm *comm, const double *d_queries, const int64_t *d_q_offsets,
+                                      int32_t Q, int32_t max_query_len, double eps, double max_offset, int32_t min_votes,
+                                      int32_t min_score, const int32_t *d_exclude_ids, int32_t k, int32_t *d_topk,
+                                      int32_t *d_totals, void *d_workspace, size_t workspace_bytes, void *hip_stream) {
+    TVZ_GUARDED(tvz_align_topk_sharded_impl(c, comm, d_queries, d_q_offsets, Q, max_query_len, eps, max_offset, min_votes, min_score, d_exclude_ids, k, d_topk, d_totals, d_workspace, workspace_bytes, hip_stream));
 }

@@ -76,9 +76,13 @@ struct Workspace {                   // the caller's scratch
     void *p;
     size_t bytes;
 };
+struct AlignCall {                   // what an alignment top-k call asks of a (query, row) pair
+    double eps, max_offset;
+    int32_t min_votes, min_score;
+};
 struct ShardBlocks {                 // where a local top-k left its block, and the all-gather's target next to it
     int32_t *local = nullptr;        // int32[Q][k+1][3]: d_out, or the workspace's own area for d_out = NULL
-    int32_t *gathered = nullptr;     // int32[n_ranks][Q][k+1][3] in the workspace
+    int32_t *gathered = nullptr;     // int32[n_ranks][Q][k+1][3] in the workspace  (rows of 4 for the alignment top-k)
 };
 
 // Internal (not exported): local sweep + per-shard top-k with the hit lists in the workspace (tvz_match.hip);
@@ -88,3 +92,6 @@ int tvz_match_topk_local(tvz_corpus *c, const Batch &b, int32_t cap, int32_t k, 
 // The tolerant counterpart (tvz_match.hip): the sweep keeps the k best itself.
 int tvz_match_tol_topk_local(tvz_corpus *c, const Batch &b, double tol, int32_t k, int32_t *d_out, Workspace ws,
                              int32_t n_ranks, void *hip_stream, ShardBlocks *blocks);
+// The alignment top-k (tvz_match.hip): n_ranks = 0 is tvz_align_topk itself, whose workspace holds no blocks.
+int tvz_align_topk_local(tvz_corpus *c, const Batch &b, const AlignCall &a, int32_t k, int32_t *d_out, Workspace ws,
+                         int32_t n_ranks, void *hip_stream, ShardBlocks *blocks);

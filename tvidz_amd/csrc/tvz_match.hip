@@ -1980,52 +1980,76 @@ namespace {
 
 // Workspace of tvz_align_topk, in front of the sorted queries (TolWs, which takes the rest): the queries' hit totals
 // and one kept list - k words and k payloads - per sweep block.  The sizing function knows no row count: the lists are
-// sized by the grid's upper bound, as the tolerant top-k's are.
+// sized by the grid's upper bound, as the tolerant top-k's are.  The sharded forms (n_blocks > 0: the communicator's
+// ranks, at least 1) add the local block and the gathered ones behind them; tvz_align_topk itself (n_blocks = 0) has
+// neither, and its size is what it was.
 struct AlignTopkWs {
     int32_t *totals = nullptr;             // [Q]
     unsigned long long *part_w = nullptr;  // [Q][blocks][k]
     unsigned long long *part_p = nullptr;  // [Q][blocks][k]
+    int32_t *local = nullptr;              // [Q][k+1][4]
+    int32_t *gathered = nullptr;           // [n_blocks][Q][k+1][4]
 };
 
-AlignTopkWs align_topk_ws_layout(Carver &cv, int32_t Q, int32_t k) {
+AlignTopkWs align_topk_ws_layout(Carver &cv, int32_t Q, int32_t k, int32_t n_blocks) {
     AlignTopkWs w;
     const size_t lists = (size_t)tol_topk_max_lists(Q) * (size_t)k;
     w.totals = cv.take<int32_t>((size_t)Q);
     w.part_w = cv.take<unsigned long long>(lists);
     w.part_p = cv.take<unsigned long long>(lists);
+    if (n_blocks > 0) {
+        const size_t block = (size_t)Q * (size_t)(k + 1) * 4;
+        w.local = cv.take<int32_t>(block);
+        w.gathered = cv.take<int32_t>((size_t)n_blocks * block);
+    }
     return w;
 }
 
-size_t align_topk_ws_bytes(int32_t Q, int64_t keys, int32_t k) {
+size_t align_topk_ws_bytes(int32_t Q, int64_t keys, int32_t k, int32_t n_blocks) {
     Carver cv(nullptr);
-    align_topk_ws_layout(cv, Q, k);
+    align_topk_ws_layout(cv, Q, k, n_blocks);
     return cv.fixed() + tol_ws_bytes(Q, keys);
 }
 
+// what tvz_align_topk_merge refuses, apart from its pointers
+int check_align_merge(int32_t n_lists, int32_t k) {
+    if (n_lists < 1 || n_lists > kAlMergeMaxLists)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment top-k merge: %d lists outside 1..%d", (int)n_lists, kAlMergeMaxLists);
+    if (k < 1 || k > kAlMaxK)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment top-k: k=%d outside 1..%d", (int)k, kAlMaxK);
+    return TVZ_OK;
+}
+
+bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 }  // namespace
 
-static int tvz_align_topk_impl(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
-                               int32_t max_query_len, double eps, double max_offset, int32_t min_votes,
-                               int32_t min_score, const int32_t *d_exclude_ids, int32_t k, int32_t *d_out,
-                               void *d_workspace, size_t workspace_bytes, void *hip_stream) {
-    const Batch b{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids};
+// used by tvz_comm.hip (same shared object, not exported): sort -> sweep that keeps the k best -> per-query selection.
+// n_ranks = 0: tvz_align_topk itself, d_out is the caller's.  n_ranks >= 1: the workspace also holds the local block
+// and n_ranks gathered ones (tvz_align_topk_sharded_workspace_bytes); d_out = NULL writes the block into the
+// workspace's own, and `blocks` is told where it went and where the all-gather's target is.
+int tvz_align_topk_local(tvz_corpus *c, const Batch &b, const AlignCall &a, int32_t k, int32_t *d_out, Workspace ws,
+                         int32_t n_ranks, void *hip_stream, ShardBlocks *blocks) {
+    const int32_t Q = b.Q, max_query_len = b.max_query_len;
     if (int rc = check_batch_args(c, b, 0)) return rc;
     int32_t B = 0;
-    if (int rc = check_align_bins(eps, max_offset, &B)) return rc;
-    TVZ_REQUIRE(min_votes >= 1, "alignment top-k: min_votes %d below 1", (int)min_votes);
-    TVZ_REQUIRE(min_score >= 0 && min_score <= kAlScoreOne, "alignment top-k: min_score %d outside 0..%d", (int)min_score,
+    if (int rc = check_align_bins(a.eps, a.max_offset, &B)) return rc;
+    TVZ_REQUIRE(a.min_votes >= 1, "alignment top-k: min_votes %d below 1", (int)a.min_votes);
+    TVZ_REQUIRE(a.min_score >= 0 && a.min_score <= kAlScoreOne, "alignment top-k: min_score %d outside 0..%d", (int)a.min_score,
                 kAlScoreOne);
     if (k < 1 || k > kAlMaxK)
         return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment top-k: k=%d outside 1..%d", (int)k, kAlMaxK);
     if (max_query_len > kAlMaxLen)
         return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment top-k: max_query_len %d above %d", (int)max_query_len, kAlMaxLen);
     if (Q == 0) return TVZ_OK;
-    Carver cv(d_workspace);
-    const AlignTopkWs w = align_topk_ws_layout(cv, Q, k);
+    Carver cv(ws.p);
+    const AlignTopkWs w = align_topk_ws_layout(cv, Q, k, n_ranks);
     const int32_t lds_keys = std::max(max_query_len, 1);
     const size_t lds = al_lds_bytes(lds_keys, B);
     auto args_ok = [&]() -> int {
-        TVZ_REQUIRE(d_out != nullptr, "d_out is NULL");
+        TVZ_REQUIRE(d_out != nullptr || w.local != nullptr, "d_out is NULL");
+        if (d_out == nullptr) d_out = w.local;
+        if (blocks) *blocks = ShardBlocks{d_out, w.gathered};
         TVZ_REQUIRE(lds + kAlStaticLds <= (size_t)kLdsPerWorkgroup,
                     "alignment top-k sweep: %zu B of dynamic + %d B of static LDS exceed a gfx950 workgroup's", lds, kAlStaticLds);
         return TVZ_OK;
@@ -2034,21 +2058,71 @@ static int tvz_align_topk_impl(tvz_corpus *c, const double *d_queries, const int
     // the fixed parts and room for ONE query of max_query_len values; what the caller gave beyond that holds more
     // (the sorted positions are unused here)
     TolCall t;
-    if (int rc = tol_prelude(c, b, TolFront{cv, cv.fixed(), w.totals, "alignment top-k", "tvz_align_topk_workspace_bytes"},
-                             d_workspace ? workspace_bytes : 0, max_query_len, st, args_ok, t))
+    if (int rc = tol_prelude(c, b, TolFront{cv, cv.fixed(), w.totals, "alignment top-k",
+                                            n_ranks > 0 ? "tvz_align_topk_sharded_workspace_bytes" : "tvz_align_topk_workspace_bytes"},
+                             ws.p ? ws.bytes : 0, max_query_len, st, args_ok, t))
         return rc;
     const int64_t n_rows = t.n_rows;
-    const int blocks = n_rows ? (int)std::min<int64_t>(tvz::ceil_div(n_rows, (int64_t)kAlWaves), tol_topk_max_blocks(Q)) : 0;
-    if (blocks) {
-        hipLaunchKernelGGL(ts_align_topk_kernel, dim3((unsigned)blocks, (unsigned)Q), dim3(kAlBlock), lds, st, c->rows.p,
-                           n_rows, c->keys.p, t.ws.sv, d_q_offsets, t.ws.qm, lds_keys, eps, B, min_votes, min_score,
-                           d_exclude_ids, k, w.part_w, w.part_p, blocks, w.totals);
+    const int n_blocks = n_rows ? (int)std::min<int64_t>(tvz::ceil_div(n_rows, (int64_t)kAlWaves), tol_topk_max_blocks(Q)) : 0;
+    if (n_blocks) {
+        hipLaunchKernelGGL(ts_align_topk_kernel, dim3((unsigned)n_blocks, (unsigned)Q), dim3(kAlBlock), lds, st, c->rows.p,
+                           n_rows, c->keys.p, t.ws.sv, b.d_q_offsets, t.ws.qm, lds_keys, a.eps, B, a.min_votes, a.min_score,
+                           b.d_exclude_ids, k, w.part_w, w.part_p, n_blocks, w.totals);
         TVZ_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(ts_align_topk_reduce_kernel, dim3((unsigned)Q), dim3(kAlReduceBlock), 0, st, w.part_w, w.part_p,
-                       blocks, k, t.ws.qm, lds_keys, w.totals, d_out);
+                       n_blocks, k, t.ws.qm, lds_keys, w.totals, d_out);
     TVZ_HIP(hipGetLastError());
     return record(c, st);
+}
+
+static int tvz_align_topk_impl(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
+                               int32_t max_query_len, double eps, double max_offset, int32_t min_votes,
+                               int32_t min_score, const int32_t *d_exclude_ids, int32_t k, int32_t *d_out,
+                               void *d_workspace, size_t workspace_bytes, void *hip_stream) {
+    return tvz_align_topk_local(c, Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids},
+                                AlignCall{eps, max_offset, min_votes, min_score}, k, d_out,
+                                Workspace{d_workspace, workspace_bytes}, 0, hip_stream, nullptr);
+}
+
+static int tvz_align_topk_merge_impl(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t k,
+                                     const double *d_queries, const int64_t *d_q_offsets, int32_t *d_topk,
+                                     int32_t *d_totals, void *hip_stream) {
+    TVZ_REQUIRE(Q >= 0, "Q=%d is negative", (int)Q);
+    if (int rc = check_align_merge(n_lists, k)) return rc;
+    if (Q == 0) return TVZ_OK;
+    TVZ_REQUIRE(d_gathered && d_queries && d_q_offsets && d_topk && d_totals, "NULL argument");
+    TVZ_REQUIRE(aligned16(d_gathered) && aligned16(d_topk), "alignment top-k merge: the blocks and d_topk must be 16-byte aligned");
+    hipLaunchKernelGGL(ts_align_topk_merge_kernel, dim3((unsigned)tvz::ceil_div(Q, kAlMergeWaves)), dim3(kAlMergeBlock), 0,
+                       reinterpret_cast<hipStream_t>(hip_stream), d_gathered, n_lists, Q, k, d_queries, d_q_offsets, d_topk,
+                       d_totals);
+    return launched();
+}
+
+static int tvz_align_topk_shards_impl(tvz_corpus *const *shards, int32_t n_shards, const double *d_queries,
+                                      const int64_t *d_q_offsets, int32_t Q, int32_t max_query_len, double eps,
+                                      double max_offset, int32_t min_votes, int32_t min_score,
+                                      const int32_t *d_exclude_ids, int32_t k, int32_t *d_blocks, int32_t *d_topk,
+                                      int32_t *d_totals, void *d_workspace, size_t workspace_bytes, void *hip_stream) {
+    TVZ_REQUIRE(shards != nullptr && n_shards >= 1, "no shards");
+    TVZ_REQUIRE(Q >= 0, "Q=%d is negative", (int)Q);
+    if (int rc = check_align_merge(n_shards, k)) return rc;
+    for (int32_t r = 0; r < n_shards; ++r)
+        TVZ_REQUIRE(shards[r] != nullptr && shards[r]->device == shards[0]->device,
+                    "shard %d is NULL or on another device than shard 0", r);
+    TVZ_REQUIRE(Q == 0 || (d_blocks && d_topk && d_totals && d_queries && d_q_offsets), "NULL argument");
+    TVZ_REQUIRE(aligned16(d_blocks) && aligned16(d_topk), "alignment top-k merge: the blocks and d_topk must be 16-byte aligned");
+    if (Q == 0) return TVZ_OK;
+    // every handle's call makes the same checks of the same arguments: what one refuses, the first one refuses,
+    // before anything is enqueued
+    const Batch b{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids};
+    const AlignCall a{eps, max_offset, min_votes, min_score};
+    for (int32_t r = 0; r < n_shards; ++r)
+        if (int rc = tvz_align_topk_local(shards[r], b, a, k, d_blocks + (size_t)r * (size_t)Q * (size_t)(k + 1) * 4,
+                                          Workspace{d_workspace, workspace_bytes}, 0, hip_stream, nullptr))
+            return rc;
+    DeviceGuard dg(shards[0]->device);
+    return tvz_align_topk_merge_impl(d_blocks, n_shards, Q, k, d_queries, d_q_offsets, d_topk, d_totals, hip_stream);
 }
 
 #ifdef TVZ_IX_STAMP
@@ -2199,7 +2273,14 @@ TVZ_EXPORT int tvz_align(tvz_corpus *c, const double *d_query, int32_t n, double
 TVZ_EXPORT size_t tvz_align_topk_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k) {
     if (Q < 0 || max_query_len < 0 || total_query_keys < 0 || k < 1) return 0;
     const int64_t keys = total_query_keys > 0 ? total_query_keys : (int64_t)Q * max_query_len;
-    return align_topk_ws_bytes(Q, std::max<int64_t>(keys, max_query_len), k);
+    return align_topk_ws_bytes(Q, std::max<int64_t>(keys, max_query_len), k, 0);
+}
+
+TVZ_EXPORT size_t tvz_align_topk_sharded_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys,
+                                                         int32_t k, int32_t n_ranks) {
+    if (Q < 0 || max_query_len < 0 || total_query_keys < 0 || k < 1 || n_ranks < 0) return 0;
+    const int64_t keys = total_query_keys > 0 ? total_query_keys : (int64_t)Q * max_query_len;
+    return align_topk_ws_bytes(Q, std::max<int64_t>(keys, max_query_len), k, std::max(n_ranks, 1));
 }
 
 TVZ_EXPORT int tvz_align_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
@@ -2208,6 +2289,22 @@ TVZ_EXPORT int tvz_align_topk(tvz_corpus *c, const double *d_queries, const int6
                               void *d_workspace, size_t workspace_bytes, void *hip_stream) {
     TVZ_GUARDED(tvz_align_topk_impl(c, d_queries, d_q_offsets, Q, max_query_len, eps, max_offset, min_votes, min_score,
                                     d_exclude_ids, k, d_out, d_workspace, workspace_bytes, hip_stream));
+}
+
+TVZ_EXPORT int tvz_align_topk_merge(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t k,
+                                    const double *d_queries, const int64_t *d_q_offsets, int32_t *d_topk,
+                                    int32_t *d_totals, void *hip_stream) {
+    TVZ_GUARDED(tvz_align_topk_merge_impl(d_gathered, n_lists, Q, k, d_queries, d_q_offsets, d_topk, d_totals, hip_stream));
+}
+
+TVZ_EXPORT int tvz_align_topk_shards(tvz_corpus *const *shards, int32_t n_shards, const double *d_queries,
+                                     const int64_t *d_q_offsets, int32_t Q, int32_t max_query_len, double eps,
+                                     double max_offset, int32_t min_votes, int32_t min_score,
+                                     const int32_t *d_exclude_ids, int32_t k, int32_t *d_blocks, int32_t *d_topk,
+                                     int32_t *d_totals, void *d_workspace, size_t workspace_bytes, void *hip_stream) {
+    TVZ_GUARDED(tvz_align_topk_shards_impl(shards, n_shards, d_queries, d_q_offsets, Q, max_query_len, eps, max_offset,
+                                           min_votes, min_score, d_exclude_ids, k, d_blocks, d_topk, d_totals, d_workspace,
+                                           workspace_bytes, hip_stream));
 }
 
 TVZ_EXPORT int tvz_find_duplicates_tol(tvz_corpus *c, const double *h_query, int64_t n, double tol, int32_t min_match,

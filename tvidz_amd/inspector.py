@@ -95,7 +95,7 @@ class Inspector:
             if not hasattr(getattr(store, "corpus", None), "align_topk"):
                 raise RuntimeError(f"near_top_k={self.near_top_k}: the store's corpus "
                                    f"({type(getattr(store, 'corpus', None)).__name__}) has no align_topk; "
-                                   "use a DeviceCorpus or a service.ShardedCorpus")
+                                   "use a DeviceCorpus, a service.ShardedCorpus or a service.RankCorpus")
         # opt-in, never the default: duplicates by the TOLERANT count (include/tvz.h tvz_find_duplicates_tol)
         # instead of the reference's exact float64 equality; the verdict, the truncation at kth and the stored
         # duplicates all follow it.  Refused here, before any upload, where the store's corpus cannot do it.
@@ -363,6 +363,8 @@ class Inspector:
                                              k=self.near_top_k, min_score=min_score, exclude_ids=[int(video_id)])
             if int(totals[0]) >= 0:                                            # (refused: more than 4,095 cuts -> the walk)
                 return [r for r in rows[0] if r[0] >= 0]
+            if not hasattr(corpus, "align"):                                   # (a rank corpus has no walk: no report)
+                return []
         return corpus.align(scene_timestamps, eps=self.near_eps, max_offset=self.near_max_offset)
 
     def _progress(self, analysis_key, scene_timestamps, frames_done, total_frames, dups_to_report):

@@ -24,6 +24,11 @@ Two forms of the same composition:
                  through torch.distributed (RCCL on the GPUs, gloo in the CPU test) around
                  sharded.ShardedMatcher / RcclShardedMatcher.  UNMEASURED ON HARDWARE: no box here
                  has more than one GPU; tests/test_service_cpu.py runs it at world size 2 on gloo.
+
+The opt-in near-duplicate search (`align_topk`, Inspector(near_top_k=K), `--near-top-k K`) has both forms too:
+ShardedCorpus runs tvz_align_topk_shards (every shard in turn + the device merge, one call, one copy back), RankCorpus
+sends ASK_NEAR through the tick to `matcher.align_topk`.  The RCCL form (tvz_align_topk_sharded) has run on hardware
+at world size 1 only; tests/test_align_topk_sharded_cpu.py runs the exchange at world sizes 2 and 3 on gloo.
 """
 from __future__ import annotations
 
@@ -203,6 +208,7 @@ class ShardedCorpus:
         self._lock = threading.Lock()
         self._ws = [None] * self.R
         self._stager = _Stage(self.dev)
+        self._near_tls = threading.local()  # align_topk's workspace, per calling thread
         self.exact_asks = 0
         self.tick_host_s = 0.0              # wall time inside _run_batch (host work + the wait for the GPU)
         self.batcher = TickBatcher(self._run_batch, linger_s=linger_s)
@@ -252,34 +258,52 @@ class ShardedCorpus:
 
     def align_topk(self, queries, *, eps: float, max_offset: float, k: int = 16, min_votes: int = 1,
                    min_score: int = 0, exclude_ids=None, max_query_len=None):
-        """DeviceCorpus.align_topk over every shard with the same k, the shards' blocks merged on the host by the
-        contract's order (at most n_shards x k rows per query).  Totals are summed; a query some shard refused stays
-        refused (ALIGN_REFUSED, all rows padding)."""
+        """DeviceCorpus.align_topk over every shard with the same k: ONE library call runs the shards in turn and merges
+        their blocks on the device by the contract's order (tvz_align_topk_shards), ONE device-to-host copy brings rows
+        and totals back.  Totals are summed; a query some shard refused stays refused (ALIGN_REFUSED, all rows
+        padding).  On the caller's current stream, with a workspace per calling thread, as DeviceCorpus.align_topk.
+        More than 16 shards (the merge takes up to 16 lists): one such call per group of 16, the groups' answers put
+        together as blocks again on the device - k sorted rows and a total each - and merged by one
+        tvz_align_topk_merge; still one copy back, same answer."""
         tc = self._tc
+        dev = self.dev
         if isinstance(queries, tuple) and len(queries) == 2 and torch.is_tensor(queries[0]):
-            flat, off = queries[0].cpu().numpy(), queries[1].cpu().numpy()
-            nv = [int(np.count_nonzero(~np.isnan(flat[off[i]:off[i + 1]]))) for i in range(len(off) - 1)]
+            d_q, d_off = queries
+            self.shards[0]._check_queries(d_q, d_off)
+            Q = d_off.numel() - 1
+            longest = int((d_off[1:] - d_off[:-1]).max()) if Q and max_query_len is None else 0
         else:
-            queries = [np.asarray(q, dtype=np.float64).reshape(-1) for q in queries]
-            nv = [int(np.count_nonzero(~np.isnan(q))) for q in queries]
-            if max_query_len is None:
-                max_query_len = min(max((q.size for q in queries), default=0), tc.ALIGN_TOPK_MAX_LEN)
-        parts = [s.align_topk(queries, eps=eps, max_offset=max_offset, k=k, min_votes=min_votes, min_score=min_score,
-                              exclude_ids=exclude_ids, max_query_len=max_query_len) for s in self.shards]
-        Q = len(nv)
-        rows = np.zeros((Q, k, 4), dtype=np.int32)
-        rows[:, :, 0] = -1
-        totals = np.zeros(Q, dtype=np.int32)
-        for q in range(Q):
-            if any(int(t[q]) < 0 for _, t in parts):
-                totals[q] = tc.ALIGN_REFUSED
-                continue
-            totals[q] = sum(int(t[q]) for _, t in parts)
-            best = sorted((r for b, _ in parts for r in b[q].tolist() if r[0] >= 0),
-                          key=lambda r: tc.align_order_key(r, nv[q]))[:k]
-            if best:
-                rows[q, :len(best)] = best
-        return rows, totals
+            d_q, d_off, longest = tc.pack_queries(queries, dev)
+            Q = len(queries)
+        if max_query_len is None:
+            max_query_len = min(longest, tc.ALIGN_TOPK_MAX_LEN)
+        d_ex = None
+        if exclude_ids is not None:
+            d_ex = exclude_ids if torch.is_tensor(exclude_ids) else \
+                torch.as_tensor(np.asarray(exclude_ids, dtype=np.int32).reshape(-1)).to(dev)
+            if d_ex.dtype != torch.int32 or d_ex.numel() != Q or d_ex.device != dev:
+                raise RuntimeError(f"exclude_ids must be {Q} int32 values on {dev}")
+        need = tc.align_topk_workspace_bytes(Q, max_query_len, d_q.numel(), k)
+        ws = getattr(self._near_tls, "ws", None)          # idle again when the copy below has returned
+        if ws is None or ws.numel() < need:
+            ws = self._near_tls.ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        kw = dict(eps=eps, max_offset=max_offset, k=k, workspace=ws, min_votes=min_votes, min_score=min_score,
+                  d_exclude_ids=d_ex)
+        with torch.cuda.device(dev):
+            groups = [self.shards[i:i + 16] for i in range(0, self.R, 16)]      # the merge takes up to 16 lists
+            if len(groups) == 1:
+                _, rows, totals = tc.align_topk_shards(groups[0], d_q, d_off, max_query_len, **kw)
+            else:
+                # more shards than one merge takes: every group's answer is a block again - its k rows, then its total
+                blocks = torch.zeros((len(groups), Q, k + 1, 4), dtype=torch.int32, device=dev)
+                for g, part in enumerate(groups):
+                    _, rows, totals = tc.align_topk_shards(part, d_q, d_off, max_query_len, **kw)
+                    blocks[g, :, :k] = rows
+                    blocks[g, :, k, 0] = -1
+                    blocks[g, :, k, 1] = totals
+                rows, totals = tc.align_topk_merge(blocks, k, d_q, d_off)
+            both = torch.cat([rows.reshape(Q, k * 4), totals.reshape(Q, 1)], dim=1).cpu().numpy()
+        return np.ascontiguousarray(both[:, :k * 4]).reshape(Q, k, 4), np.ascontiguousarray(both[:, k * 4])
 
     # ---- matches ----
     supports_tolerance = True             # tolerant asks go to every shard in turn (inspector.Inspector checks)
@@ -337,7 +361,33 @@ class ShardedCorpus:
         return [(both[i, :k3].reshape(self.k, 3), int(both[i, k3])) for i in range(Q)]
 
 
-ASK_TOPK, ASK_EXACT = 0, 1
+ASK_TOPK, ASK_EXACT, ASK_NEAR = 0, 1, 2
+ASK_HEADER = 10                # (len, exclude, min_match, kind, tolerance, eps, max_offset, k, min_votes, min_score)
+NEAR_MAX_K, NEAR_MAX_BINS, NEAR_SCORE_ONE = 64, 4096, 1 << 20      # include/tvz.h, tvz_align_topk
+
+
+def check_near_top_k(k) -> int:
+    """`--near-top-k K`: 0 (off) or 1..64, the rows tvz_align_topk keeps per query."""
+    if int(k) != k or not 0 <= int(k) <= NEAR_MAX_K:
+        raise ValueError(f"near_top_k must be 0 (off) or 1..{NEAR_MAX_K}, got {k!r}")
+    return int(k)
+
+
+def check_near_params(eps, max_offset, k, min_votes, min_score) -> tuple:
+    """What tvz_align_topk refuses, refused on the host with its rules (include/tvz.h): -> the five values as the
+    ask carries them."""
+    eps, max_offset = float(eps), float(max_offset)
+    if not (0.0 < eps <= sys.float_info.max):
+        raise ValueError(f"eps must be finite and > 0, got {eps!r}")
+    if not (0.0 <= max_offset <= sys.float_info.max):
+        raise ValueError(f"max_offset must be finite and >= 0, got {max_offset!r}")
+    if not 2 * np.floor(max_offset / eps + 0.5) + 1 <= NEAR_MAX_BINS:
+        raise ValueError(f"max_offset / eps = {max_offset / eps:.0f} needs more than {NEAR_MAX_BINS} bins")
+    for name, v, lo, hi in (("k", k, 1, NEAR_MAX_K), ("min_votes", min_votes, 1, (1 << 31) - 1),
+                            ("min_score", min_score, 0, NEAR_SCORE_ONE)):
+        if int(v) != v or not lo <= int(v) <= hi:
+            raise ValueError(f"{name} must be an integer in {lo}..{hi}, got {v!r}")
+    return eps, max_offset, int(k), int(min_votes), int(min_score)
 
 
 class RankCorpus:
@@ -360,6 +410,12 @@ class RankCorpus:
                  top-k ask whose tie set may exceed k (the reference reports ALL rows of the earliest
                  prefix: an upload never fails because of k), by queries of more than 4095 timestamps
                  and by min_match outside 1..5.
+
+      ASK_NEAR   the opt-in near-duplicate search (`align_topk`, what Inspector(near_top_k=K) calls): the k best-aligned
+                 rows of a query over ALL shards, through `matcher.align_topk` (local tvz_align_topk block -> one
+                 all-gather -> the merge by the contract's order).  Its five parameters (eps, max_offset, k, min_votes,
+                 min_score) travel in the ask's header; asks that agree in all five share one batched call per tick.
+                 Nothing is sent unless somebody asks: a service without --near-top-k never names it.
 
     `shard`: this rank's DeviceCorpus (or a stand-in with upload/upsert/clear/find_duplicates);
     `matcher.match_topk(d_q, d_off, max_len, min_match, d_excl) -> (merged [Q,k,3], totals [Q])`;
@@ -432,16 +488,48 @@ class RankCorpus:
         return bool(getattr(self.shard, "supports_tolerance", False)) and \
             bool(getattr(self.matcher, "supports_tolerance", False))
 
-    def _ask(self, q, min_match, exclude_id, kind, tolerance=0.0):
-        fut: Future = Future()
+    def _ask_all(self, asks):
+        """asks: [(q, min_match, exclude_id, kind, tolerance, near parameters or None)] -> their answers; all of them
+        become pending at once, so they share a tick where the batch size allows."""
+        futs = [Future() for _ in asks]
         with self._cv:
             if self.broken is not None:
                 raise RuntimeError(f"rank corpus is broken: {self.broken!r}")
             if self._stop:
                 raise RuntimeError("rank corpus is closed")
-            self._pending.append((q, int(min_match), int(exclude_id), int(kind), fut, float(tolerance)))
+            for (q, min_match, exclude_id, kind, tolerance, near), fut in zip(asks, futs):
+                self._pending.append((q, int(min_match), int(exclude_id), int(kind), fut, float(tolerance), near))
             self._cv.notify()
-        return fut.result()
+        return [f.result() for f in futs]
+
+    def _ask(self, q, min_match, exclude_id, kind, tolerance=0.0):
+        return self._ask_all([(q, min_match, exclude_id, kind, tolerance, None)])[0]
+
+    def align_topk(self, queries, *, eps: float, max_offset: float, k: int, min_votes: int = 1, min_score: int = 0,
+                   exclude_ids=None, max_query_len=None):
+        """DeviceCorpus.align_topk over the shards of all ranks: `queries` = a list of timestamp lists -> (rows int32
+        [Q,k,4], totals int32 [Q]) as numpy arrays, in the contract's order (corpus.align_order_key).  Every query is
+        one ASK_NEAR of the next tick.  Everything a rank's library call would refuse is refused HERE, in the caller
+        (ValueError for a bad parameter, RuntimeError for a matcher without align_topk): a matcher that throws on one
+        rank inside a tick would strand the others.  A query of more than max_query_len (at most 4,095) values is
+        answered here too, as the library answers it: all rows padding, total ALIGN_REFUSED - it never travels."""
+        near = check_near_params(eps, max_offset, k, min_votes, min_score)
+        if not (hasattr(self.matcher, "align_topk") and getattr(self.matcher, "supports_align_topk", True)):
+            raise RuntimeError(f"this rank corpus has no near-duplicate search: its matcher "
+                               f"{type(self.matcher).__name__} has no align_topk")
+        queries = [np.ascontiguousarray(np.asarray(q, dtype=np.float64).reshape(-1)) for q in queries]
+        limit = MAX_BATCH_LEN if max_query_len is None else min(int(max_query_len), MAX_BATCH_LEN)
+        excl = [-1] * len(queries) if exclude_ids is None else [int(e) for e in np.asarray(exclude_ids).reshape(-1)]
+        if len(excl) != len(queries):
+            raise ValueError(f"exclude_ids must hold {len(queries)} video ids")
+        k = near[2]
+        rows = np.zeros((len(queries), k, 4), dtype=np.int32)
+        rows[:, :, 0] = -1
+        totals = np.full(len(queries), -(1 << 31), dtype=np.int64)                 # ALIGN_REFUSED unless answered
+        sent = [i for i, q in enumerate(queries) if q.size <= limit]
+        for i, (r, t) in zip(sent, self._ask_all([(queries[i], 0, excl[i], ASK_NEAR, 0.0, near) for i in sent])):
+            rows[i], totals[i] = r, t
+        return rows, totals.astype(np.int32)
 
     def find_duplicates(self, new_timestamps, min_match: int = 5, exclude_id: int = -1, with_kth: bool = False,
                         tolerance: float = 0.0):
@@ -525,15 +613,19 @@ class RankCorpus:
     def _exchange_and_answer(self, take, allmeta):
         Qcap, Lcap = int(allmeta[:, 0].max()), max(int(allmeta[:, 1].max()), 1)
         # 2) the asks, padded to the largest rank's block, as ONE float64 block per rank:
-        #    [Qcap, 5 + Lcap] = (len, exclude, min_match, kind, tolerance | keys...); small integers are exact in
-        #    float64, and the tolerance IS one
-        blk = np.zeros((Qcap, 5 + Lcap), dtype=np.float64)
-        for i, (q, mm, ex, kind, _, tol) in enumerate(take):
+        #    [Qcap, ASK_HEADER + Lcap] = (len, exclude, min_match, kind, tolerance, and a near ask's eps, max_offset,
+        #    k, min_votes, min_score | keys...); small integers are exact in float64, tolerance, eps and max_offset
+        #    ARE float64
+        H = ASK_HEADER
+        blk = np.zeros((Qcap, H + Lcap), dtype=np.float64)
+        for i, (q, mm, ex, kind, _, tol, near) in enumerate(take):
             blk[i, 0], blk[i, 1], blk[i, 2], blk[i, 3], blk[i, 4] = len(q), ex, mm, kind, tol
-            blk[i, 5:5 + len(q)] = q
-        g = self._gather(torch.from_numpy(blk).to(self.xdev)).cpu().numpy()       # [world, Qcap, 5 + Lcap]
+            if near is not None:
+                blk[i, 5:H] = near
+            blk[i, H:H + len(q)] = q
+        g = self._gather(torch.from_numpy(blk).to(self.xdev)).cpu().numpy()       # [world, Qcap, H + Lcap]
         g_info = g[:, :, :4].astype(np.int64)
-        g_keys = g[:, :, 5:]
+        g_keys = g[:, :, H:]
         # the global batch, in the same order on every rank: rank-major; rows past a rank's count are padding
         valid = np.arange(Qcap)[None, :] < allmeta[:, 0][:, None]                  # [world, Qcap]
         rr, ii = np.nonzero(valid)
@@ -578,6 +670,36 @@ class RankCorpus:
             for j in np.flatnonzero(mine[sel]):
                 a = int(sel[j])
                 take[int(ii[a])][4].set_result((both[j, :k * 3].reshape(k, 3).copy(), int(both[j, k * 3])))
+        # 3b) near asks, one batched sharded alignment top-k per (eps, max_offset, k, min_votes, min_score): every
+        #     rank reads the same parameters off the gathered headers, so every rank makes the same calls in the
+        #     same order
+        near = kind_all == ASK_NEAR
+        if near.any():
+            par_all = g[rr, ii, 5:H]                                               # [n, 5]
+            for par in sorted(set(map(tuple, par_all[near].tolist()))):
+                sel = np.flatnonzero(near & (par_all == np.asarray(par)).all(axis=1))
+                eps, max_offset, k, min_votes, min_score = par[0], par[1], int(par[2]), int(par[3]), int(par[4])
+                lens = lens_all[sel]
+                flat = g_keys[rr[sel], ii[sel]][np.arange(Lcap)[None, :] < lens[:, None]]
+                kw = dict(eps=eps, max_offset=max_offset, k=k, min_votes=min_votes, min_score=min_score)
+                if mdev.type == "cuda":
+                    if self._stager is None:
+                        self._stager = _Stage(mdev)
+                        self._stream = torch.cuda.Stream(mdev, priority=-1)
+                    with torch.cuda.device(mdev), torch.cuda.stream(self._stream):
+                        d_q, d_off, d_ex, _ = self._stager.put_flat(flat, lens, excl_all[sel].astype(np.int32))
+                        rows, totals = self.matcher.align_topk(d_q, d_off, int(lens.max()), d_exclude_ids=d_ex, **kw)
+                        both = torch.cat([rows.reshape(len(sel), k * 4), totals.reshape(len(sel), 1)], dim=1).cpu().numpy()
+                else:
+                    offs = np.zeros(len(sel) + 1, dtype=np.int64)
+                    np.cumsum(lens, out=offs[1:])
+                    d_q = torch.from_numpy(np.ascontiguousarray(flat if flat.size else np.zeros(1), dtype=np.float64))
+                    rows, totals = self.matcher.align_topk(d_q, torch.from_numpy(offs), int(lens.max()),
+                                                           d_exclude_ids=torch.from_numpy(excl_all[sel].astype(np.int32)), **kw)
+                    both = torch.cat([rows.reshape(len(sel), k * 4), totals.reshape(len(sel), 1).to(rows.dtype)], dim=1).numpy()
+                for j in np.flatnonzero(mine[sel]):
+                    a = int(sel[j])
+                    take[int(ii[a])][4].set_result((both[j, :k * 4].reshape(k, 4).copy(), int(both[j, k * 4])))
         # 4) exact asks: every rank asks its own shard, counts and padded hit lists are all-gathered
         sel = np.flatnonzero(kind_all == ASK_EXACT)
         if len(sel):
@@ -682,6 +804,15 @@ def _load_hook(spec: str):
     return getattr(importlib.import_module(mod), fn)
 
 
+def near_kwargs(a) -> dict:
+    """The launcher's --near-* switches as Inspector takes them; nothing at --near-top-k 0: a rank started without
+    the flag builds its driver exactly as before."""
+    if not getattr(a, "near_top_k", 0):
+        return {}
+    return dict(near_duplicates=True, near_top_k=int(a.near_top_k), near_eps=float(a.near_eps),
+                near_max_offset=float(a.near_max_offset), near_jaccard=float(a.near_jaccard))
+
+
 def _hip_parts(rank: int, world: int, group, a):
     """What a rank is made of on an MI355X: its DeviceCorpus, the RCCL matcher behind the C ABI, the
     real driver.  (`--parts module:function` swaps this for test doubles on a CPU box.)"""
@@ -696,7 +827,7 @@ def _hip_parts(rank: int, world: int, group, a):
     xdev = f"cuda:{a.device}" if a.backend == "nccl" else "cpu"
     return dict(shard=shard, matcher=matcher, xdev=xdev,
                 inspector=lambda store: Inspector(store, device=f"cuda:{a.device}", max_workers=a.workers,
-                                                  match_tolerance=a.match_tolerance))
+                                                  match_tolerance=a.match_tolerance, **near_kwargs(a)))
 
 
 def parent_gone(parent_pid: int) -> bool:
@@ -842,7 +973,8 @@ class RankService:
     def __init__(self, ranks: int, db_url: str, base_port: int = 5000, backend: str = "gloo", parts: str = "",
                  devices: Optional[List[int]] = None, k: int = 64, cap: int = 4096, workers: int = 16,
                  tick_s: float = 0.0005, env: Optional[dict] = None, ready_timeout: float = 300.0,
-                 match_tolerance: float = 0.0, match_tol_index: float = 0.0):
+                 match_tolerance: float = 0.0, match_tol_index: float = 0.0, near_top_k: int = 0,
+                 near_eps: float = 1.0 / 30, near_max_offset: float = 30.0, near_jaccard: float = 0.8):
         import socket
         import subprocess
         from . import db
@@ -851,6 +983,13 @@ class RankService:
         if not (0.0 <= match_tolerance <= sys.float_info.max):           # Inspector's rule, before any rank starts
             raise ValueError(f"match_tolerance must be finite and >= 0, got {match_tolerance!r}")
         match_tol_index = check_tol_index(match_tol_index, match_tolerance)   # likewise before any rank starts
+        near = []
+        if check_near_top_k(near_top_k):                                 # likewise: K, and what every near ask will carry
+            check_near_params(near_eps, near_max_offset, near_top_k, 1, 0)
+            if not (0.0 <= float(near_jaccard) <= 1.0):
+                raise ValueError(f"near_jaccard must be in 0..1, got {near_jaccard!r}")
+            near = ["--near-top-k", str(int(near_top_k)), "--near-eps", repr(float(near_eps)),
+                    "--near-max-offset", repr(float(near_max_offset)), "--near-jaccard", repr(float(near_jaccard))]
         db.create_schema(db_url)                                # once, before N processes open it side by side
         with socket.socket() as s:                              # a free rendezvous port
             s.bind(("127.0.0.1", 0))
@@ -865,7 +1004,7 @@ class RankService:
                    "--workers", str(workers), "--tick-s", str(tick_s), "--parent-pid", str(os.getpid())] + \
                   (["--parts", parts] if parts else []) + \
                   (["--match-tolerance", repr(match_tolerance)] if match_tolerance else []) + \
-                  (["--match-tol-index", repr(match_tol_index)] if match_tol_index else [])
+                  (["--match-tol-index", repr(match_tol_index)] if match_tol_index else []) + near
             e = dict(os.environ)
             e.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")     # dmabuf IPC: RCCL between processes needs it here
             e.update(env or {})
@@ -930,6 +1069,13 @@ def main(argv=None) -> int:  # pragma: no cover - exercised through subprocesses
                          "(tvz_corpus_tol_index): tolerant asks with tolerance <= CELL are then answered from the "
                          "postings near their timestamps instead of a sweep of the shard.  Its own switch: it does not "
                          "follow from --match-tolerance, and a CELL below it is refused.  0 = off")
+    ap.add_argument("--near-top-k", type=int, default=0, metavar="K",
+                    help="1..64 turns on the opt-in near-duplicate report of every rank's driver "
+                         "(Inspector(near_duplicates=True, near_top_k=K)): the K best-aligned rows over ALL shards, kept "
+                         "on the devices and merged there (tvz_align_topk_sharded).  0 = off")
+    ap.add_argument("--near-eps", type=float, default=1.0 / 30, help="seconds per offset bin of the near-duplicate search")
+    ap.add_argument("--near-max-offset", type=float, default=30.0, help="largest shift, in seconds, it looks for")
+    ap.add_argument("--near-jaccard", type=float, default=0.8, help="tolerant Jaccard a reported near duplicate reaches")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--rank", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--master-port", type=int, default=29500, help=argparse.SUPPRESS)
@@ -941,7 +1087,8 @@ def main(argv=None) -> int:  # pragma: no cover - exercised through subprocesses
         return _child_main(a)
     svc = RankService(a.ranks, a.db, base_port=a.port, backend=a.backend, parts=a.parts, k=a.k, cap=a.cap,
                       workers=a.workers, tick_s=a.tick_s, match_tolerance=a.match_tolerance,
-                      match_tol_index=a.match_tol_index)
+                      match_tol_index=a.match_tol_index, near_top_k=a.near_top_k, near_eps=a.near_eps,
+                      near_max_offset=a.near_max_offset, near_jaccard=a.near_jaccard)
 
     def monitor():
         while True:

@@ -65,6 +65,14 @@ class HipBackend:
     def topk_merge(self, gathered, k):
         return self._tc.topk_merge(gathered, k)
 
+    def local_align_topk(self, d_q, d_off, max_len, eps, max_offset, k, min_votes, min_score, d_excl):
+        """this rank's alignment top-k block (tvz_align_topk): int32 [Q, k+1, 4] on the device"""
+        return self.corpus.align_topk_block(d_q, d_off, max_len, eps=eps, max_offset=max_offset, k=k,
+                                            min_votes=min_votes, min_score=min_score, d_exclude_ids=d_excl)
+
+    def align_topk_merge(self, gathered, k, d_q, d_off):
+        return self._tc.align_topk_merge(gathered, k, d_q, d_off)
+
 
 class ShardedMatcher:
     """rank-local shard + ONE all-gather of per-shard top-k (+ hit totals) + identical merge on
@@ -127,6 +135,29 @@ class ShardedMatcher:
                                        tolerance=tolerance))
 
 
+    def align_topk(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, eps: float,
+                   max_offset: float, k: int, min_votes: int = 1, min_score: int = 0,
+                   d_exclude_ids: Optional[torch.Tensor] = None):
+        """The near-duplicate search over the sharded table: the local alignment top-k block [Q, k+1, 4] -> ONE
+        all-gather -> the merge by the contract's order, identical on every rank: -> (rows int32 [Q,k,4], totals
+        int32 [Q]; corpus.ALIGN_REFUSED for a query some rank refused).  `k` is the call's own, not the matcher's."""
+        for name in ("local_align_topk", "align_topk_merge"):
+            if not hasattr(self.backend, name):
+                raise RuntimeError(f"{type(self.backend).__name__} has no {name}")
+        local = self.backend.local_align_topk(d_queries, d_q_offsets, max_query_len, eps, max_offset, int(k),
+                                              int(min_votes), int(min_score), d_exclude_ids)
+        Q = local.shape[0]
+        if not self.collective:
+            return self.backend.align_topk_merge(local.view(1, Q, k + 1, 4), k, d_queries, d_q_offsets)
+        flat = torch.empty((self.world * Q, k + 1, 4), dtype=torch.int32, device=local.device)
+        dist.all_gather_into_tensor(flat, local.contiguous(), group=self.group)
+        return self.backend.align_topk_merge(flat.view(self.world, Q, k + 1, 4), k, d_queries, d_q_offsets)
+
+    @property
+    def supports_align_topk(self) -> bool:
+        return hasattr(self.backend, "local_align_topk") and hasattr(self.backend, "align_topk_merge")
+
+
 def make_comm(device: int, group=None):
     """Create the libtvz RCCL communicator of this rank.  torch.distributed (any backend) is used
     ONLY to ship rank 0's 128-byte unique id; a non-Python host ships it by its own means."""
@@ -170,6 +201,8 @@ class RcclShardedMatcher:
         self.streams = [torch.cuda.Stream(self.dev, priority=priority) for _ in range(n_streams)]
         self.ws = [None] * n_streams
         self.out = [None] * n_streams
+        self.near_ws = [None] * n_streams   # align_topk's own workspaces and outputs
+        self.near_out = [None] * n_streams
         self.events = [torch.cuda.Event() for _ in range(n_streams)]
         self._i = 0
         self._plans = {}                    # (slot, query tensors, shape) -> the library call's arguments (submit)
@@ -261,6 +294,37 @@ class RcclShardedMatcher:
     def match_topk(self, d_queries, d_q_offsets, max_query_len, min_match, d_exclude_ids=None, tolerance: float = 0.0):
         return self.finish(self.submit(d_queries, d_q_offsets, max_query_len, min_match, d_exclude_ids,
                                        tolerance=tolerance))
+
+    supports_align_topk = True
+
+    def align_topk(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, eps: float,
+                   max_offset: float, k: int, min_votes: int = 1, min_score: int = 0,
+                   d_exclude_ids: Optional[torch.Tensor] = None):
+        """The near-duplicate search over the sharded table behind ONE library call (tvz_align_topk_sharded): the local
+        alignment top-k -> ncclAllGather of the [Q, k+1, 4] blocks -> the merge, on the next of the matcher's side
+        streams; the current stream waits for it.  -> (rows int32 [Q,k,4], totals int32 [Q]), this matcher's tensors,
+        overwritten `n_streams` calls later.  Its own workspace (the rows are 4 wide, `k` is the call's own) and no
+        plan: the near-duplicate report is one call per upload, not the tick's stream of batches."""
+        from . import corpus as tc
+        i = self._i
+        self._i = (i + 1) % len(self.streams)
+        st = self.streams[i]
+        self.corpus._check_queries(d_queries, d_q_offsets)
+        Q, k = d_q_offsets.numel() - 1, int(k)
+        need = tc.align_topk_sharded_workspace_bytes(Q, max_query_len, d_queries.numel(), k, self.world)
+        if self.near_ws[i] is None or self.near_ws[i].numel() < need:
+            self.near_ws[i] = torch.empty(max(need, 256), dtype=torch.uint8, device=self.dev)
+        if self.near_out[i] is None or self.near_out[i][0].shape[:2] != (Q, k):
+            self.near_out[i] = (torch.empty((Q, k, 4), dtype=torch.int32, device=self.dev),
+                                torch.empty(Q, dtype=torch.int32, device=self.dev))
+        st.wait_stream(torch.cuda.current_stream(self.dev))       # the queries are complete; the slot's last answer is read
+        rows, totals = self.comm.align_topk_sharded(self.corpus, d_queries, d_q_offsets, max_query_len, eps=eps,
+                                                    max_offset=max_offset, k=k, min_votes=min_votes,
+                                                    min_score=min_score, d_exclude_ids=d_exclude_ids,
+                                                    workspace=self.near_ws[i], stream=st, out=self.near_out[i])
+        self.events[i].record(st)
+        torch.cuda.current_stream(self.dev).wait_event(self.events[i])
+        return rows, totals
 
 
 def verdicts_from_topk(merged: np.ndarray):
