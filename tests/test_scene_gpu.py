@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from oracle import oracle
+from tests import scene_cases
 from tvidz_amd import _lib, scene, synth
 
 pytestmark = pytest.mark.gpu
@@ -315,6 +316,34 @@ def test_fuzz_shapes_strides_chunking():
             scores.append(score.cpu().numpy().copy())
         assert (np.concatenate(sads) == o_sad).all(), (trial, H, W, T, step, bd)
         assert (np.concatenate(scores) == o_score).all() and (np.concatenate(sels) == o_sel).all(), trial
+    # None of the 40 views above is one the flat kernel takes (tests/test_scene_cases_cpu.py replays the draws).  A second
+    # generator makes views it does take: tight rows of whole 16-byte chunks, a row offset and padding between frames.
+    added = scene_cases.fuzz_flat_trials()
+    strided = 0
+    for trial, p in enumerate(added):
+        H, W, T, bd = p["H"], p["W"], p["T"], p["bitdepth"]
+        s16 = bd > 8
+        rng = np.random.default_rng(p["seed"])
+        dt = np.uint16 if s16 else np.uint8
+        big = rng.integers(0, 1 << bd, size=(T, H + p["pad_h"], W)).astype(dt)
+        big[T // 2:] = (big[T // 2:] // 3).astype(dt)
+        view_np = big[:, p["off_h"]:p["off_h"] + H, :]
+        d_big = torch.from_numpy(big.view(np.int16) if s16 else big).to(DEV)
+        d_view = d_big[:, p["off_h"]:p["off_h"] + H, :]
+        assert scene_cases.flat_ok_tensor(d_view), (trial, p)
+        strided += T > 1 and d_view.stride(0) > H * W
+        o_sad = oracle.luma_sad(view_np)
+        o_sel, o_score, o_mafd, _ = oracle.scene_select(o_sad, H, W, 0.3, bitdepth=bd)
+        sc = scene.SceneScorer(H, W, p["step"], DEV, 0.3, bitdepth=bd)
+        sads, sels, scores = [], [], []
+        for s0 in range(0, T, p["step"]):
+            sad, mafd, score, sel = sc.score_batch(d_view[s0:s0 + p["step"]])
+            sads.append(sad.cpu().numpy().view(np.uint64).copy())
+            sels.append(sel.cpu().numpy().copy())
+            scores.append(score.cpu().numpy().copy())
+        assert (np.concatenate(sads) == o_sad).all(), ("flat", trial, p)
+        assert (np.concatenate(scores) == o_score).all() and (np.concatenate(sels) == o_sel).all(), ("flat", trial)
+    assert 4 * strided >= len(added) >= 12
 
 
 def test_scene_path_is_graph_capturable():
