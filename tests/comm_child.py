@@ -58,6 +58,44 @@ out["streaming_equal"] = bool(stream_ok)
 m3, t3 = comm.match_sharded(dc, d_q, d_off, max_len, 0, 50, 8)
 torch.cuda.synchronize()
 out["overflow_totals"] = t3.cpu().tolist()
+# RcclShardedMatcher's slots and plans: a fixed sequence of calls over two side streams, every answer equal to the
+# one-shot call's for the same inputs (an 8-row shard, Q = 3, then Q = 2)
+rows8 = [(100 + i, [50.0 * i + 1.5 * j for j in range(6)]) for i in range(8)]
+dc8 = tc.DeviceCorpus(0)
+dc8.upload(rows8)
+qa = [rows8[0][1], [t + 0.3 for t in rows8[1][1]], rows8[2][1][:3] + rows8[3][1][:3]]     # the second: only tolerantly
+a_q, a_off, a_len = tc.pack_queries(qa, dev)
+b_q, b_off, b_len = tc.pack_queries([rows8[4][1], rows8[5][1]], dev)
+a_ex = torch.tensor([-1, -1, rows8[3][0]], dtype=torch.int32, device=dev)
+k8, near8 = 4, dict(eps=0.1, max_offset=3.0, k=3)
+
+
+def _host(pair):
+    torch.cuda.synchronize()
+    return [t.cpu().tolist() for t in pair]
+
+
+want_a = _host(comm.match_sharded(dc8, a_q, a_off, a_len, 2, 8, k8, d_exclude_ids=a_ex))
+want_b = _host(comm.match_sharded(dc8, b_q, b_off, b_len, 2, 8, k8))
+want_tol = _host(comm.match_tol_sharded(dc8, a_q, a_off, a_len, 0.5, 2, k8, d_exclude_ids=a_ex))
+want_near = _host(comm.align_topk_sharded(dc8, a_q, a_off, a_len, d_exclude_ids=a_ex, **near8))
+sm8 = sharded.RcclShardedMatcher(dc8, comm, k=k8, cap=8, n_streams=2)
+steps = [("a", want_a, lambda: sm8.match_topk(a_q, a_off, a_len, 2, a_ex))] * 3          # the third: a plan hit
+steps += [("b", want_b, lambda: sm8.match_topk(b_q, b_off, b_len, 2)),                   # Q = 2: outputs re-made, plans dropped
+          ("a tolerant", want_tol, lambda: sm8.match_topk(a_q, a_off, a_len, 2, a_ex, tolerance=0.5)),
+          ("near", want_near, lambda: sm8.align_topk(a_q, a_off, a_len, d_exclude_ids=a_ex, **near8)),
+          ("a again", want_a, lambda: sm8.match_topk(a_q, a_off, a_len, 2, a_ex))]
+out["slot_sequence"] = [[name, _host(step()) == want] for name, want, step in steps]
+out["slot_premises"] = {"exact_finds_0_and_2": [want_a[1][0] >= 1, want_a[1][1], want_a[1][2] >= 1],
+                        "tolerant_finds_1": want_tol[1][1] >= 1, "near_finds_1": want_near[1][1] >= 1,
+                        "b_differs": want_b != want_a, "plans": len(sm8._plans)}
+# corpus.py's one prelude through the three wrappers that need a communicator (tests/prelude_cases.py says what)
+from tests import prelude_cases as pc  # noqa: E402
+four = tc.DeviceCorpus(0)
+four.upload(pc.ROWS)
+out["prelude_failures"] = {name: pc.failures(name, *spec) for name, spec in pc.wrappers([four], comm).items()}
+four.close()
+dc8.close()
 comm.close()
 dc.close()
 print("RESULT " + json.dumps(out))

@@ -180,6 +180,50 @@ def test_rank_corpus_answers_near_topk_and_exact_asks_of_one_tick(world):
     _run(_rank_worker, world)
 
 
+def test_one_tick_calls_the_matcher_in_sorted_order():
+    """World size 1: one tick that holds an exact ask, a top-k ask, a tolerant top-k ask and two near asks with
+    different parameters, handed over in an order that is NOT the sorted one.  The matcher hears match_topk per
+    (min_match, tolerance) in sorted order - `tolerance` named only where it is non-zero - and then align_topk per
+    (eps, max_offset, k, min_votes, min_score) in sorted order: every rank makes its collective calls in this order."""
+    from tests.tol_fakes import TolBackend, TolCorpus
+
+    class Backend(NearBackend, TolBackend):
+        pass
+
+    calls = []
+
+    class Recorder(sharded.ShardedMatcher):
+        def match_topk(self, d_q, d_off, max_len, min_match, d_excl=None, **kw):
+            calls.append(("match_topk", int(min_match), dict(kw)))
+            return super().match_topk(d_q, d_off, max_len, min_match, d_excl, **kw)
+
+        def align_topk(self, d_q, d_off, max_len, *, eps, max_offset, k, min_votes=1, min_score=0, d_exclude_ids=None):
+            calls.append(("align_topk", eps, max_offset, k, min_votes, min_score))
+            return super().align_topk(d_q, d_off, max_len, eps=eps, max_offset=max_offset, k=k, min_votes=min_votes,
+                                      min_score=min_score, d_exclude_ids=d_exclude_ids)
+
+    rows, queries = _small_table()
+    shard = TolCorpus()
+    rc = service.RankCorpus(shard, Recorder(Backend(live=shard), k=8, cap=64), xdev="cpu", tick_s=0.01)
+    try:
+        rc.upload(rows)
+        dup, q = np.asarray(rows[1][1]), np.asarray(queries[0])
+        near1 = service.check_near_params(EPS, MAX_OFFSET, 4, 1, 0)
+        near2 = service.check_near_params(2 * EPS, MAX_OFFSET, 4, 1, 0)
+        asks = [(dup, 2, -1, service.ASK_EXACT, 0.0, None), (q, 0, -1, service.ASK_NEAR, 0.0, near2),
+                (dup, 3, -1, service.ASK_TOPK, 0.0, None), (q, 0, -1, service.ASK_NEAR, 0.0, near1),
+                (dup, 2, -1, service.ASK_TOPK, 0.5, None)]
+        busy = rc.busy_ticks
+        answers = rc._ask_all(asks)
+        assert rc.busy_ticks == busy + 1                                 # one tick held them all
+        assert calls == [("match_topk", 2, {"tolerance": 0.5}), ("match_topk", 3, {}),
+                         ("align_topk", EPS, MAX_OFFSET, 4, 1, 0), ("align_topk", 2 * EPS, MAX_OFFSET, 4, 1, 0)]
+        assert answers[0] and answers[0][0][0] == rows[1][0]             # the exact ask found the row it copies
+        assert answers[2][0][0][0] == rows[1][0] and rows[1][0] in answers[4][0][:, 0] and rc.broken is None
+    finally:
+        rc.close()
+
+
 def test_a_rank_corpus_whose_matcher_cannot_align_refuses_in_the_caller(tmp_path):
     from tests.fakes import cut_inspector
     from tvidz_amd import db as tdb

@@ -77,7 +77,8 @@ def align_topk_sharded_workspace_bytes(Q: int, max_query_len: int, total_query_k
 
 
 ALIGN_SCORE_ONE = 1 << 20
-ALIGN_TOPK_MAX_LEN = 4095
+ALIGN_TOPK_MAX_LEN = 4095                   # include/tvz.h: the batched calls take queries of up to 4095 timestamps
+ALIGN_TOPK_MAX_K, ALIGN_TOPK_MAX_BINS = 64, 4096     # include/tvz.h, tvz_align_topk: rows kept per query, offset bins
 ALIGN_REFUSED = -(1 << 31)                  # a query's total when tvz_align_topk refused it (INT32_MIN)
 
 
@@ -253,35 +254,10 @@ class DeviceCorpus:
         the true number of hits, ALIGN_REFUSED for a query longer than max_query_len - default: the longest query,
         at most 4,095), as numpy arrays.  Order: align_order_key.  One device-to-host copy of Q x (k + 1) x 16 bytes."""
         dev = torch.device("cuda", self.device)
-        if isinstance(queries, tuple) and len(queries) == 2 and torch.is_tensor(queries[0]):
-            d_q, d_off = queries
-            self._check_queries(d_q, d_off)
-            Q = d_off.numel() - 1
-            if max_query_len is None:
-                max_query_len = min(int((d_off[1:] - d_off[:-1]).max()) if Q else 0, ALIGN_TOPK_MAX_LEN)
-        else:
-            d_q, d_off, longest = pack_queries(queries, dev)
-            Q = len(queries)
-            if max_query_len is None:
-                max_query_len = min(longest, ALIGN_TOPK_MAX_LEN)
-        d_ex = None
-        if exclude_ids is not None:
-            d_ex = exclude_ids if torch.is_tensor(exclude_ids) else \
-                torch.as_tensor(np.asarray(exclude_ids, dtype=np.int32).reshape(-1)).to(dev)
-            if d_ex.dtype != torch.int32 or d_ex.numel() != Q or d_ex.device != dev:
-                raise RuntimeError(f"exclude_ids must be {Q} int32 values on {dev}")
-        out = torch.empty((Q, k + 1, 4), dtype=torch.int32, device=dev)
-        s = torch.cuda.current_stream(dev)
-        need = align_topk_workspace_bytes(Q, max_query_len, d_q.numel(), k)
-        # cached per calling thread (calls of several threads overlap); idle again when the copy below has returned
-        ws = getattr(self._tls, "align_ws", None)
-        if ws is None or ws.numel() < need:
-            ws = self._tls.align_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-        _lib.check(self.lib.tvz_align_topk(
-            self._h, d_q.data_ptr(), d_off.data_ptr(), Q, int(max_query_len), float(eps), float(max_offset),
-            int(min_votes), int(min_score), d_ex.data_ptr() if d_ex is not None else None, int(k), out.data_ptr(),
-            ws.data_ptr(), ws.numel(), s.cuda_stream))
-        h = out.cpu().numpy()
+        d_q, d_off, Q, max_query_len, d_ex = align_inputs(queries, exclude_ids, max_query_len, dev)
+        ws = thread_workspace(self._tls, align_topk_workspace_bytes(Q, max_query_len, d_q.numel(), k), dev)
+        h = self.align_topk_block(d_q, d_off, max_query_len, eps=eps, max_offset=max_offset, k=k, min_votes=min_votes,
+                                  min_score=min_score, d_exclude_ids=d_ex, workspace=ws).cpu().numpy()
         return np.ascontiguousarray(h[:, :k]), np.ascontiguousarray(h[:, k, 1])
 
     def align_topk_block(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, eps: float,
@@ -291,35 +267,35 @@ class DeviceCorpus:
                          workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
         """tvz_align_topk, device in / device out: enqueue Q queries -> the block int32 [Q, k+1, 4] that the sharded
         forms gather and merge (align_topk_merge)."""
-        dev, Q = self._check_queries(d_queries, d_q_offsets)
-        if out is None:
-            out = torch.empty((Q, k + 1, 4), dtype=torch.int32, device=dev)
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
-        ws = self._workspace(workspace, align_topk_workspace_bytes(Q, max_query_len, d_queries.numel(), k), dev, s)
+        Q = d_q_offsets.numel() - 1
+        dev, s, ws, excl = self._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace,
+                                         align_topk_workspace_bytes(Q, max_query_len, d_queries.numel(), k))
+        out = _out(out, (Q, k + 1, 4), dev)
         _lib.check(self.lib.tvz_align_topk(
             self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps), float(max_offset),
-            int(min_votes), int(min_score), d_exclude_ids.data_ptr() if d_exclude_ids is not None else None, int(k),
-            out.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
+            int(min_votes), int(min_score), excl, int(k), out.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
         return out
 
     # ---- batched, device resident ----
     def _check_queries(self, d_queries, d_q_offsets):
-        dev = d_queries.device
-        if dev.type != "cuda" or dev.index != self.device:
-            raise RuntimeError(f"queries must live on cuda:{self.device}")
-        if d_queries.dtype != torch.float64 or d_q_offsets.dtype != torch.int64:
-            raise RuntimeError("queries must be float64 and offsets int64")
-        return dev, d_q_offsets.numel() - 1
+        return _check_queries(self.device, d_queries, d_q_offsets)
 
-    def _workspace(self, workspace, need: int, dev, stream):
+    def _prelude(self, d_queries, d_q_offsets, d_exclude_ids, stream, workspace, need):
+        """What every batched wrapper does before its one library call: the queries are float64 / int64 on this
+        handle's device, the stream is the caller's or the current one, the workspace is the caller's (checked
+        against `need` bytes, the wrapper's sizing function for these queries; None leaves the size to the library)
+        or a fresh one, the exclusions become a pointer or None.  -> (dev, stream, workspace, exclude pointer)."""
+        dev, _ = _check_queries(self.device, d_queries, d_q_offsets)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        need = need or 0
         if workspace is None:
             # per call, from torch's caching allocator (no hipMalloc once warm); pass a persistent
             # one to keep even that off the hot path
             workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-            workspace.record_stream(stream)
+            workspace.record_stream(s)
         elif workspace.device != dev or workspace.dtype != torch.uint8 or workspace.numel() < need:
             raise RuntimeError(f"workspace must be a uint8 tensor of >= {need} bytes on {dev}")
-        return workspace
+        return dev, s, workspace, d_exclude_ids.data_ptr() if d_exclude_ids is not None else None
 
     def match(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int,
               min_match: int, cap: int, d_exclude_ids: Optional[torch.Tensor] = None,
@@ -328,18 +304,13 @@ class DeviceCorpus:
               algo: int = _lib.ALGO_AUTO):
         """Enqueue Q queries; returns (hits int32[Q,cap,3], hits_n int32[Q]) device tensors.
         `algo`: per-call kernel choice (_lib.ALGO_*); results never depend on it."""
-        dev, Q = self._check_queries(d_queries, d_q_offsets)
-        if out_hits is None:
-            out_hits = torch.empty((Q, cap, 3), dtype=torch.int32, device=dev)
-        if out_n is None:
-            out_n = torch.empty(Q, dtype=torch.int32, device=dev)
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
-        ws = self._workspace(workspace, workspace_bytes(Q, max_query_len, total_query_keys=d_queries.numel()), dev, s)
+        Q = d_q_offsets.numel() - 1
+        dev, s, ws, excl = self._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace,
+                                         workspace_bytes(Q, max_query_len, total_query_keys=d_queries.numel()))
+        out_hits, out_n = _out(out_hits, (Q, cap, 3), dev, "out_hits"), _out(out_n, (Q,), dev, "out_n")
         _lib.check(self.lib.tvz_match(
-            self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len),
-            int(min_match), d_exclude_ids.data_ptr() if d_exclude_ids is not None else None,
-            int(cap), out_hits.data_ptr(), out_n.data_ptr(), ws.data_ptr(), ws.numel(), int(algo),
-            s.cuda_stream))
+            self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), int(min_match), excl,
+            int(cap), out_hits.data_ptr(), out_n.data_ptr(), ws.data_ptr(), ws.numel(), int(algo), s.cuda_stream))
         return out_hits, out_n
 
     def match_tol(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, tol: float,
@@ -348,17 +319,13 @@ class DeviceCorpus:
                   stream: Optional[torch.cuda.Stream] = None, workspace: Optional[torch.Tensor] = None):
         """The tolerant form of `match` (tvz_match_tol): enqueue Q queries; returns (hits int32[Q,cap,3],
         hits_n int32[Q]) device tensors in match's layout (topk applies)."""
-        dev, Q = self._check_queries(d_queries, d_q_offsets)
-        if out_hits is None:
-            out_hits = torch.empty((Q, cap, 3), dtype=torch.int32, device=dev)
-        if out_n is None:
-            out_n = torch.empty(Q, dtype=torch.int32, device=dev)
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
-        ws = self._workspace(workspace, tol_workspace_bytes(Q, max_query_len, d_queries.numel()), dev, s)
+        Q = d_q_offsets.numel() - 1
+        dev, s, ws, excl = self._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace,
+                                         tol_workspace_bytes(Q, max_query_len, d_queries.numel()))
+        out_hits, out_n = _out(out_hits, (Q, cap, 3), dev, "out_hits"), _out(out_n, (Q,), dev, "out_n")
         _lib.check(self.lib.tvz_match_tol(
-            self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(tol),
-            int(min_match), d_exclude_ids.data_ptr() if d_exclude_ids is not None else None,
-            int(cap), out_hits.data_ptr(), out_n.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
+            self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(tol), int(min_match),
+            excl, int(cap), out_hits.data_ptr(), out_n.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
         return out_hits, out_n
 
     def match_topk(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int,
@@ -367,14 +334,12 @@ class DeviceCorpus:
                    workspace: Optional[torch.Tensor] = None, algo: int = _lib.ALGO_AUTO) -> torch.Tensor:
         """Sweep + per-shard top-k behind ONE library call (hit lists stay in the workspace):
         -> int32 [Q,k+1,3] = the k best hits by (kth, video_id, count) + a (-1, n_hits, NEVER) row."""
-        dev, Q = self._check_queries(d_queries, d_q_offsets)
-        if out is None:
-            out = torch.empty((Q, k + 1, 3), dtype=torch.int32, device=dev)
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
-        ws = self._workspace(workspace, workspace_bytes(Q, max_query_len, cap, k, total_query_keys=d_queries.numel()), dev, s)
+        Q = d_q_offsets.numel() - 1
+        dev, s, ws, excl = self._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace,
+                                         workspace_bytes(Q, max_query_len, cap, k, total_query_keys=d_queries.numel()))
+        out = _out(out, (Q, k + 1, 3), dev)
         _lib.check(self.lib.tvz_match_topk(
-            self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len),
-            int(min_match), d_exclude_ids.data_ptr() if d_exclude_ids is not None else None,
+            self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), int(min_match), excl,
             int(cap), int(k), out.data_ptr(), ws.data_ptr(), ws.numel(), int(algo), s.cuda_stream))
         return out
 
@@ -385,15 +350,13 @@ class DeviceCorpus:
         """The tolerant sweep with the per-shard top-k kept inside it (tvz_match_tol_topk; min_match 1..5, k <= 64,
         queries of up to 4,095 timestamps): -> int32 [Q,k+1,3] in match_topk's layout.  No cap: the k rows are the
         exact k best and the tail row's n_hits is the true count."""
-        dev, Q = self._check_queries(d_queries, d_q_offsets)
-        if out is None:
-            out = torch.empty((Q, k + 1, 3), dtype=torch.int32, device=dev)
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
-        ws = self._workspace(workspace, tol_topk_workspace_bytes(Q, max_query_len, d_queries.numel(), k), dev, s)
+        Q = d_q_offsets.numel() - 1
+        dev, s, ws, excl = self._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace,
+                                         tol_topk_workspace_bytes(Q, max_query_len, d_queries.numel(), k))
+        out = _out(out, (Q, k + 1, 3), dev)
         _lib.check(self.lib.tvz_match_tol_topk(
-            self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(tol),
-            int(min_match), d_exclude_ids.data_ptr() if d_exclude_ids is not None else None,
-            int(k), out.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
+            self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(tol), int(min_match),
+            excl, int(k), out.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
         return out
 
 
@@ -438,26 +401,15 @@ class Comm:
         """local match + top-k -> ncclAllGather -> merge, all enqueued on `stream` by ONE library
         call; -> (merged int32 [Q,k,3], totals int32 [Q]), identical on every rank.  `out` =
         (merged, totals) buffers to write into (a caller streaming batches keeps its own)."""
-        dev, Q = corpus._check_queries(d_queries, d_q_offsets)
-        merged, totals = self._merged_out(out, Q, k, dev)
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
-        ws = corpus._workspace(workspace, workspace_bytes(Q, max_query_len, cap, k, self.n_ranks, d_queries.numel()), dev, s)
+        Q = d_q_offsets.numel() - 1
+        dev, s, ws, excl = corpus._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace,
+                                           workspace_bytes(Q, max_query_len, cap, k, self.n_ranks, d_queries.numel()))
+        merged, totals = _topk_out(out, Q, k, 3, dev)
         _lib.check(self.lib.tvz_match_sharded(
-            corpus._h, self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len),
-            int(min_match), d_exclude_ids.data_ptr() if d_exclude_ids is not None else None,
-            int(cap), int(k), merged.data_ptr(), totals.data_ptr(), ws.data_ptr(), ws.numel(),
-            int(algo), s.cuda_stream))
+            corpus._h, self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), int(min_match),
+            excl, int(cap), int(k), merged.data_ptr(), totals.data_ptr(), ws.data_ptr(), ws.numel(), int(algo),
+            s.cuda_stream))
         return merged, totals
-
-    def _merged_out(self, out, Q: int, k: int, dev):
-        if out is not None:
-            merged, totals = out
-            if merged.shape != (Q, k, 3) or totals.shape != (Q,) or merged.dtype != torch.int32 \
-                    or totals.dtype != torch.int32 or not merged.is_contiguous():
-                raise RuntimeError("out must be (int32 [Q,k,3], int32 [Q])")
-            return merged, totals
-        return (torch.empty((Q, k, 3), dtype=torch.int32, device=dev),
-                torch.empty(Q, dtype=torch.int32, device=dev))
 
     def match_tol_sharded(self, corpus: DeviceCorpus, d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
                           max_query_len: int, tol: float, min_match: int, k: int,
@@ -468,17 +420,15 @@ class Comm:
         """The tolerant form of `match_sharded` (tvz_match_tol_sharded): the sweep that keeps its k best ->
         ncclAllGather -> merge; -> (merged int32 [Q,k,3], totals int32 [Q]: true counts, negative only
         for a query longer than max_query_len)."""
-        dev, Q = corpus._check_queries(d_queries, d_q_offsets)
-        merged, totals = self._merged_out(out, Q, k, dev)
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
-        ws = corpus._workspace(workspace, tol_topk_workspace_bytes(Q, max_query_len, d_queries.numel(), k, self.n_ranks),
-                               dev, s)
+        Q = d_q_offsets.numel() - 1
+        dev, s, ws, excl = corpus._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace,
+                                           tol_topk_workspace_bytes(Q, max_query_len, d_queries.numel(), k, self.n_ranks))
+        merged, totals = _topk_out(out, Q, k, 3, dev)
         _lib.check(self.lib.tvz_match_tol_sharded(
             corpus._h, self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(tol),
-            int(min_match), d_exclude_ids.data_ptr() if d_exclude_ids is not None else None,
-            int(k), merged.data_ptr(), totals.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
+            int(min_match), excl, int(k), merged.data_ptr(), totals.data_ptr(), ws.data_ptr(), ws.numel(),
+            s.cuda_stream))
         return merged, totals
-
 
     def align_topk_sharded(self, corpus: DeviceCorpus, d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
                            max_query_len: int, *, eps: float, max_offset: float, k: int, min_votes: int = 1,
@@ -487,17 +437,53 @@ class Comm:
                            out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
         """tvz_align_topk_sharded: the local alignment top-k -> ncclAllGather of the [Q,k+1,4] blocks -> the merge;
         -> (rows int32 [Q,k,4], totals int32 [Q]), identical on every rank."""
-        dev, Q = corpus._check_queries(d_queries, d_q_offsets)
-        rows, totals = _align_out(out, Q, k, dev)
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
-        ws = corpus._workspace(workspace, align_topk_sharded_workspace_bytes(Q, max_query_len, d_queries.numel(), k,
-                                                                             self.n_ranks), dev, s)
+        Q = d_q_offsets.numel() - 1
+        dev, s, ws, excl = corpus._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace,
+                                           align_topk_sharded_workspace_bytes(Q, max_query_len, d_queries.numel(), k, self.n_ranks))
+        rows, totals = _topk_out(out, Q, k, 4, dev)
         _lib.check(self.lib.tvz_align_topk_sharded(
             corpus._h, self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps),
-            float(max_offset), int(min_votes), int(min_score),
-            d_exclude_ids.data_ptr() if d_exclude_ids is not None else None, int(k), rows.data_ptr(), totals.data_ptr(),
+            float(max_offset), int(min_votes), int(min_score), excl, int(k), rows.data_ptr(), totals.data_ptr(),
             ws.data_ptr(), ws.numel(), s.cuda_stream))
         return rows, totals
+
+
+def _check_queries(device: int, d_queries, d_q_offsets):
+    dev = d_queries.device
+    if dev.type != "cuda" or dev.index != device:
+        raise RuntimeError(f"queries must live on cuda:{device}")
+    if d_queries.dtype != torch.float64 or d_q_offsets.dtype != torch.int64:
+        raise RuntimeError("queries must be float64 and offsets int64")
+    return dev, d_q_offsets.numel() - 1
+
+
+def _out(out, shape: tuple, dev, name: str = "out"):
+    """One int32 output of a batched call: a fresh tensor, or the caller's, checked - the library is told only where
+    it starts, and would write past the end of a smaller one."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.int32, device=dev)
+    if out.shape != shape or out.dtype != torch.int32 or out.device != dev or not out.is_contiguous():
+        raise RuntimeError(f"{name} must be a contiguous int32 {list(shape)} on {dev}")
+    return out
+
+
+def _topk_out(out, Q: int, k: int, width: int, dev):
+    """The (rows int32 [Q,k,width], totals int32 [Q]) a merge writes: the caller's `out`, checked, or fresh ones
+    (width 3: match hits, 4: alignment rows)."""
+    if out is not None:
+        rows, totals = out
+        if rows.shape != (Q, k, width) or totals.shape != (Q,) or rows.dtype != torch.int32 \
+                or totals.dtype != torch.int32 or not rows.is_contiguous():
+            raise RuntimeError(f"out must be (int32 [Q,k,{width}], int32 [Q])")
+        return rows, totals
+    return torch.empty((Q, k, width), dtype=torch.int32, device=dev), torch.empty(Q, dtype=torch.int32, device=dev)
+
+
+def _shards_out(shards, Q: int, k: int, width: int, dev):
+    """What the two *_shards calls share: the handle array, the blocks [R,Q,k+1,width] and the merge's outputs."""
+    R = len(shards)
+    return ((C.c_void_p * R)(*[s._h for s in shards]),
+            torch.empty((R, Q, k + 1, width), dtype=torch.int32, device=dev)) + _topk_out(None, Q, k, width, dev)
 
 
 def topk(lists: torch.Tensor, lists_n: Optional[torch.Tensor], k: int,
@@ -537,18 +523,15 @@ def match_topk_shards(shards: Sequence["DeviceCorpus"], d_queries: torch.Tensor,
                       algo: int = _lib.ALGO_AUTO):
     """tvz_match_topk on every handle of ONE device + the merge behind one library call:
     -> (blocks int32 [R,Q,k+1,3], merged int32 [Q,k,3], totals int32 [Q])."""
-    dev = d_queries.device
-    R, Q = len(shards), d_q_offsets.numel() - 1
-    blocks = torch.empty((R, Q, k + 1, 3), dtype=torch.int32, device=dev)
-    merged = torch.empty((Q, k, 3), dtype=torch.int32, device=dev)
-    totals = torch.empty(Q, dtype=torch.int32, device=dev)
-    handles = (C.c_void_p * R)(*[s._h for s in shards])
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    Q = d_q_offsets.numel() - 1
+    dev, s, ws, excl = shards[0]._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace,
+                                          workspace_bytes(Q, max_query_len, cap, k, total_query_keys=d_queries.numel()))
+    handles, blocks, merged, totals = _shards_out(shards, Q, k, 3, dev)
     with torch.cuda.device(dev):
         _lib.check(_lib.load().tvz_match_topk_shards(
-            handles, R, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), int(min_match),
-            d_exclude_ids.data_ptr() if d_exclude_ids is not None else None, int(cap), int(k), blocks.data_ptr(),
-            merged.data_ptr(), totals.data_ptr(), workspace.data_ptr(), workspace.numel(), int(algo), s.cuda_stream))
+            handles, len(shards), d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), int(min_match),
+            excl, int(cap), int(k), blocks.data_ptr(), merged.data_ptr(), totals.data_ptr(), ws.data_ptr(), ws.numel(),
+            int(algo), s.cuda_stream))
     return blocks, merged, totals
 
 
@@ -566,16 +549,6 @@ def topk_merge(gathered: torch.Tensor, k: int, stream: Optional[torch.cuda.Strea
     return out, totals
 
 
-def _align_out(out, Q: int, k: int, dev):
-    if out is not None:
-        rows, totals = out
-        if rows.shape != (Q, k, 4) or totals.shape != (Q,) or rows.dtype != torch.int32 \
-                or totals.dtype != torch.int32 or not rows.is_contiguous():
-            raise RuntimeError("out must be (int32 [Q,k,4], int32 [Q])")
-        return rows, totals
-    return torch.empty((Q, k, 4), dtype=torch.int32, device=dev), torch.empty(Q, dtype=torch.int32, device=dev)
-
-
 def align_topk_merge(gathered: torch.Tensor, k: int, d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
                      stream: Optional[torch.cuda.Stream] = None, out=None):
     """tvz_align_topk_merge: the shards' blocks int32 [R,Q,k+1,4] (+ the queries: the order word needs their non-NaN
@@ -583,7 +556,7 @@ def align_topk_merge(gathered: torch.Tensor, k: int, d_queries: torch.Tensor, d_
     R, Q, k1, w = gathered.shape
     if k1 != k + 1 or w != 4 or gathered.dtype != torch.int32 or not gathered.is_contiguous():
         raise RuntimeError("gathered must be a contiguous int32 [R,Q,k+1,4]")
-    rows, totals = _align_out(out, Q, k, gathered.device)
+    rows, totals = _topk_out(out, Q, k, 4, gathered.device)
     s = stream if stream is not None else torch.cuda.current_stream(gathered.device)
     with torch.cuda.device(gathered.device):
         _lib.check(_lib.load().tvz_align_topk_merge(gathered.data_ptr(), R, Q, int(k), d_queries.data_ptr(),
@@ -598,18 +571,16 @@ def align_topk_shards(shards: Sequence["DeviceCorpus"], d_queries: torch.Tensor,
                       stream: Optional[torch.cuda.Stream] = None):
     """tvz_align_topk on every handle of ONE device + the merge behind one library call (tvz_align_topk_shards):
     -> (blocks int32 [R,Q,k+1,4], rows int32 [Q,k,4], totals int32 [Q]).  `workspace`: align_topk_workspace_bytes."""
-    dev = d_queries.device
-    R, Q = len(shards), d_q_offsets.numel() - 1
-    blocks = torch.empty((R, Q, k + 1, 4), dtype=torch.int32, device=dev)
-    rows, totals = _align_out(None, Q, k, dev)
-    handles = (C.c_void_p * R)(*[s._h for s in shards])
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    # (the workspace's size is the library's to judge: it takes one down to a single query's room and refuses the
+    # queries that do not fit one by one)
+    Q = d_q_offsets.numel() - 1
+    dev, s, ws, excl = shards[0]._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace, None)
+    handles, blocks, rows, totals = _shards_out(shards, Q, k, 4, dev)
     with torch.cuda.device(dev):
         _lib.check(_lib.load().tvz_align_topk_shards(
-            handles, R, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps),
-            float(max_offset), int(min_votes), int(min_score),
-            d_exclude_ids.data_ptr() if d_exclude_ids is not None else None, int(k), blocks.data_ptr(), rows.data_ptr(),
-            totals.data_ptr(), workspace.data_ptr(), workspace.numel(), s.cuda_stream))
+            handles, len(shards), d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps),
+            float(max_offset), int(min_votes), int(min_score), excl, int(k), blocks.data_ptr(), rows.data_ptr(),
+            totals.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
     return blocks, rows, totals
 
 
@@ -624,3 +595,34 @@ def pack_queries(queries: Sequence[Sequence[float]], device) -> Tuple[torch.Tens
             flat[o:o + n] = np.asarray(q, dtype=np.float64)
     return (torch.from_numpy(flat).to(device), torch.from_numpy(offs).to(device),
             int(lens.max()) if len(queries) else 0)
+
+
+def align_inputs(queries, exclude_ids, max_query_len: Optional[int], dev):
+    """The host-input prelude of every `align_topk`: `queries` as a list of timestamp lists or as device tensors
+    (d_queries float64, d_q_offsets int64[Q+1]), `exclude_ids` as None, a list or a device int32 tensor, `max_query_len`
+    None for the longest query (at most ALIGN_TOPK_MAX_LEN) -> (d_q, d_off, Q, max_query_len, d_ex) on `dev`."""
+    if isinstance(queries, tuple) and len(queries) == 2 and torch.is_tensor(queries[0]):
+        d_q, d_off = queries
+        _, Q = _check_queries(dev.index, d_q, d_off)
+        longest = int((d_off[1:] - d_off[:-1]).max()) if Q and max_query_len is None else 0
+    else:
+        d_q, d_off, longest = pack_queries(queries, dev)
+        Q = len(queries)
+    if max_query_len is None:
+        max_query_len = min(longest, ALIGN_TOPK_MAX_LEN)
+    d_ex = None
+    if exclude_ids is not None:
+        d_ex = exclude_ids if torch.is_tensor(exclude_ids) else \
+            torch.as_tensor(np.asarray(exclude_ids, dtype=np.int32).reshape(-1)).to(dev)
+        if d_ex.dtype != torch.int32 or d_ex.numel() != Q or d_ex.device != dev:
+            raise RuntimeError(f"exclude_ids must be {Q} int32 values on {dev}")
+    return d_q, d_off, Q, max_query_len, d_ex
+
+
+def thread_workspace(tls: threading.local, need: int, dev) -> torch.Tensor:
+    """align_topk's workspace, cached per calling thread in `tls` (calls of several threads overlap); idle again when
+    the call's copy to the host has returned."""
+    ws = getattr(tls, "align_ws", None)
+    if ws is None or ws.numel() < need:
+        ws = tls.align_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    return ws

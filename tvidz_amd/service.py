@@ -37,14 +37,16 @@ import sys
 import threading
 import time
 from concurrent.futures import Future
-from typing import Callable, List, Optional, Sequence, Tuple
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 import torch.distributed as dist
 
-KTH_NEVER = 0x7FFFFFFF
-MAX_BATCH_LEN = 4095           # include/tvz.h: batched calls take queries of up to 4095 timestamps
+from . import corpus as tc
+from ._lib import KTH_NEVER
+
+MAX_BATCH_LEN = tc.ALIGN_TOPK_MAX_LEN
 
 
 def _hits_from_topk(rows: np.ndarray, total: int):
@@ -61,6 +63,15 @@ def _hits_from_topk(rows: np.ndarray, total: int):
         if hits[-1][2] == kstar:
             return hits, False
     return hits, True
+
+
+def _to_host(rows: torch.Tensor, totals: torch.Tensor):
+    """A batch's answer (rows int32 [Q,k,w], totals [Q]) -> numpy (rows [Q,k,w], totals [Q]), views of ONE block that
+    came to the host in ONE copy: a second device-to-host copy is a second wait for the stream, and a second point
+    where the tick thread gives up the interpreter lock.  (CPU tensors, a matcher on gloo: no copy at all.)"""
+    Q, k, w = rows.shape
+    both = torch.cat([rows.reshape(Q, k * w), totals.reshape(Q, 1).to(rows.dtype)], dim=1).cpu().numpy()
+    return both[:, :k * w].reshape(Q, k, w), both[:, k * w]
 
 
 class _Stage:
@@ -193,8 +204,6 @@ class ShardedCorpus:
 
     def __init__(self, device: int = 0, n_shards: int = 8, k: int = 64, cap: int = 4096, linger_s: float = 0.0,
                  tol_index_cell: float = 0.0):
-        from . import corpus as tc
-        self._tc = tc
         self.device = int(device)
         self.dev = torch.device("cuda", self.device)
         self.R = int(n_shards)
@@ -265,28 +274,9 @@ class ShardedCorpus:
         More than 16 shards (the merge takes up to 16 lists): one such call per group of 16, the groups' answers put
         together as blocks again on the device - k sorted rows and a total each - and merged by one
         tvz_align_topk_merge; still one copy back, same answer."""
-        tc = self._tc
         dev = self.dev
-        if isinstance(queries, tuple) and len(queries) == 2 and torch.is_tensor(queries[0]):
-            d_q, d_off = queries
-            self.shards[0]._check_queries(d_q, d_off)
-            Q = d_off.numel() - 1
-            longest = int((d_off[1:] - d_off[:-1]).max()) if Q and max_query_len is None else 0
-        else:
-            d_q, d_off, longest = tc.pack_queries(queries, dev)
-            Q = len(queries)
-        if max_query_len is None:
-            max_query_len = min(longest, tc.ALIGN_TOPK_MAX_LEN)
-        d_ex = None
-        if exclude_ids is not None:
-            d_ex = exclude_ids if torch.is_tensor(exclude_ids) else \
-                torch.as_tensor(np.asarray(exclude_ids, dtype=np.int32).reshape(-1)).to(dev)
-            if d_ex.dtype != torch.int32 or d_ex.numel() != Q or d_ex.device != dev:
-                raise RuntimeError(f"exclude_ids must be {Q} int32 values on {dev}")
-        need = tc.align_topk_workspace_bytes(Q, max_query_len, d_q.numel(), k)
-        ws = getattr(self._near_tls, "ws", None)          # idle again when the copy below has returned
-        if ws is None or ws.numel() < need:
-            ws = self._near_tls.ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        d_q, d_off, Q, max_query_len, d_ex = tc.align_inputs(queries, exclude_ids, max_query_len, dev)
+        ws = tc.thread_workspace(self._near_tls, tc.align_topk_workspace_bytes(Q, max_query_len, d_q.numel(), k), dev)
         kw = dict(eps=eps, max_offset=max_offset, k=k, workspace=ws, min_votes=min_votes, min_score=min_score,
                   d_exclude_ids=d_ex)
         with torch.cuda.device(dev):
@@ -302,8 +292,8 @@ class ShardedCorpus:
                     blocks[g, :, k, 0] = -1
                     blocks[g, :, k, 1] = totals
                 rows, totals = tc.align_topk_merge(blocks, k, d_q, d_off)
-            both = torch.cat([rows.reshape(Q, k * 4), totals.reshape(Q, 1)], dim=1).cpu().numpy()
-        return np.ascontiguousarray(both[:, :k * 4]).reshape(Q, k, 4), np.ascontiguousarray(both[:, k * 4])
+            rows, totals = _to_host(rows, totals)
+        return np.ascontiguousarray(rows), np.ascontiguousarray(totals)
 
     # ---- matches ----
     supports_tolerance = True             # tolerant asks go to every shard in turn (inspector.Inspector checks)
@@ -333,9 +323,6 @@ class ShardedCorpus:
         self.exact_asks += 1
         return self._exact(q, min_match, exclude_id, True)
 
-    def _stage(self, queries, excl):
-        return self._stager.put(queries, excl)
-
     def _run_batch(self, items):
         """One tick: every shard's lookup (top-k kept in the lookup's epilogue) over the whole batch, the
         blocks written where the merge reads them ([R, Q, k+1, 3], as an all-gather would deliver them),
@@ -343,11 +330,10 @@ class ShardedCorpus:
         share one device, and a cross-stream wait per shard (12-30 us each on this system before the
         waiting queue moves, profiles/r3_shard_pipeline.txt) cost more than the overlap gave."""
         t0 = time.perf_counter()
-        tc = self._tc
         mm = items[0][1]
         Q = len(items)
         with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
-            d_q, d_off, d_ex, max_len = self._stage([q for q, _, _ in items], [e for _, _, e in items])
+            d_q, d_off, d_ex, max_len = self._stager.put([q for q, _, _ in items], [e for _, _, e in items])
             need = tc.workspace_bytes(Q, max_len, self.cap, self.k, total_query_keys=d_q.numel())
             if self._ws[0] is None or self._ws[0].numel() < need:
                 self._ws[0] = torch.empty(need, dtype=torch.uint8, device=self.dev)       # one workspace: the shards run in turn
@@ -355,15 +341,14 @@ class ShardedCorpus:
             # interpreter is a chance to wait for its lock behind 16 upload threads busy in the ORM
             _, merged, totals = tc.match_topk_shards(self.shards, d_q, d_off, max_len, mm, self.cap, self.k,
                                                      self._ws[0], d_exclude_ids=d_ex)
-            both = torch.cat([merged.reshape(Q, self.k * 3), totals.reshape(Q, 1)], dim=1).cpu().numpy()
+            merged, totals = _to_host(merged, totals)
         self.tick_host_s += time.perf_counter() - t0
-        k3 = self.k * 3
-        return [(both[i, :k3].reshape(self.k, 3), int(both[i, k3])) for i in range(Q)]
+        return [(merged[i], int(totals[i])) for i in range(Q)]
 
 
 ASK_TOPK, ASK_EXACT, ASK_NEAR = 0, 1, 2
 ASK_HEADER = 10                # (len, exclude, min_match, kind, tolerance, eps, max_offset, k, min_votes, min_score)
-NEAR_MAX_K, NEAR_MAX_BINS, NEAR_SCORE_ONE = 64, 4096, 1 << 20      # include/tvz.h, tvz_align_topk
+NEAR_MAX_K, NEAR_MAX_BINS, NEAR_SCORE_ONE = tc.ALIGN_TOPK_MAX_K, tc.ALIGN_TOPK_MAX_BINS, tc.ALIGN_SCORE_ONE
 
 
 def check_near_top_k(k) -> int:
@@ -388,6 +373,22 @@ def check_near_params(eps, max_offset, k, min_votes, min_score) -> tuple:
         if int(v) != v or not lo <= int(v) <= hi:
             raise ValueError(f"{name} must be an integer in {lo}..{hi}, got {v!r}")
     return eps, max_offset, int(k), int(min_votes), int(min_score)
+
+
+class _Asks(NamedTuple):
+    """The asks of every rank in one tick, un-padded and in the same order on every rank (rank-major): ask `a` is ask
+    `ii[a]` of rank `rr[a]`, `mine` marks this rank's; `near` holds a near ask's five parameters [n, 5], `keys` the
+    gathered, still padded timestamps [world, Qcap, Lcap]."""
+    rr: np.ndarray
+    ii: np.ndarray
+    lens: np.ndarray
+    excl: np.ndarray
+    min_match: np.ndarray
+    kind: np.ndarray
+    tol: np.ndarray
+    near: np.ndarray
+    keys: np.ndarray
+    mine: np.ndarray
 
 
 class RankCorpus:
@@ -611,11 +612,20 @@ class RankCorpus:
             self._fail(e, take)
 
     def _exchange_and_answer(self, take, allmeta):
+        """One busy tick.  The order of the collectives and of the matcher calls is the same on every rank: the asks'
+        exchange, one match_topk per (min_match, tolerance) and one align_topk per set of near parameters, each in
+        sorted order, then the exact asks' two gathers."""
+        asks = self._gather_asks(take, allmeta)
+        self._answer_topk(asks, take)
+        self._answer_near(asks, take)
+        self._answer_exact(asks, take)
+
+    def _gather_asks(self, take, allmeta) -> _Asks:
         Qcap, Lcap = int(allmeta[:, 0].max()), max(int(allmeta[:, 1].max()), 1)
-        # 2) the asks, padded to the largest rank's block, as ONE float64 block per rank:
-        #    [Qcap, ASK_HEADER + Lcap] = (len, exclude, min_match, kind, tolerance, and a near ask's eps, max_offset,
-        #    k, min_votes, min_score | keys...); small integers are exact in float64, tolerance, eps and max_offset
-        #    ARE float64
+        # the asks, padded to the largest rank's block, as ONE float64 block per rank:
+        # [Qcap, ASK_HEADER + Lcap] = (len, exclude, min_match, kind, tolerance, and a near ask's eps, max_offset,
+        # k, min_votes, min_score | keys...); small integers are exact in float64, tolerance, eps and max_offset
+        # ARE float64
         H = ASK_HEADER
         blk = np.zeros((Qcap, H + Lcap), dtype=np.float64)
         for i, (q, mm, ex, kind, _, tol, near) in enumerate(take):
@@ -624,118 +634,94 @@ class RankCorpus:
                 blk[i, 5:H] = near
             blk[i, H:H + len(q)] = q
         g = self._gather(torch.from_numpy(blk).to(self.xdev)).cpu().numpy()       # [world, Qcap, H + Lcap]
-        g_info = g[:, :, :4].astype(np.int64)
-        g_keys = g[:, :, H:]
         # the global batch, in the same order on every rank: rank-major; rows past a rank's count are padding
         valid = np.arange(Qcap)[None, :] < allmeta[:, 0][:, None]                  # [world, Qcap]
         rr, ii = np.nonzero(valid)
-        lens_all, excl_all, mm_all, kind_all = (g_info[rr, ii, c] for c in range(4))
-        tol_all = g[rr, ii, 4]
-        mine = rr == self.rank
+        lens, excl, min_match, kind = (g[rr, ii, c].astype(np.int64) for c in range(4))
+        return _Asks(rr, ii, lens, excl, min_match, kind, g[rr, ii, 4], g[rr, ii, 5:H], g[:, :, H:], rr == self.rank)
+
+    def _answer_batch(self, asks: _Asks, take, sel, call) -> None:
+        """The asks `sel` of the global batch as ONE batched matcher call, `call(d_q, d_off, max_len, d_excl) -> (rows
+        [n,k,w], totals [n])`; this rank's asks among them get their (rows [k,w], total).  Un-padding is vectorised:
+        no per-ask Python."""
+        lens = asks.lens[sel]
+        flat = asks.keys[asks.rr[sel], asks.ii[sel]][np.arange(asks.keys.shape[2])[None, :] < lens[:, None]]   # ask after ask
+        excl = asks.excl[sel].astype(np.int32)
         mdev = getattr(self.matcher, "dev", torch.device("cpu"))
-        # 3) top-k asks, one batched sharded match per (min_match, tolerance) (vectorised un-padding: no per-ask
-        #    Python); the matcher hears of a tolerance only when there is one
-        topk = kind_all == ASK_TOPK
-        for mm, tol in sorted(set(zip(mm_all[topk].tolist(), tol_all[topk].tolist()))):
-            tol_kw = {"tolerance": tol} if tol else {}
-            sel = np.flatnonzero(topk & (mm_all == mm) & (tol_all == tol))
-            lens = lens_all[sel]
+        if mdev.type == "cuda":
+            # one pinned block, one host-to-device copy for keys + offsets + exclusions; the tick's own
+            # high-priority stream (its tiny kernels and copies otherwise queue behind the scene kernels)
+            if self._stager is None:
+                self._stager = _Stage(mdev)
+                self._stream = torch.cuda.Stream(mdev, priority=-1)
+            with torch.cuda.device(mdev), torch.cuda.stream(self._stream):
+                d_q, d_off, d_ex, _ = self._stager.put_flat(flat, lens, excl)
+                rows, totals = _to_host(*call(d_q, d_off, int(lens.max()), d_ex))
+        else:
             offs = np.zeros(len(sel) + 1, dtype=np.int64)
             np.cumsum(lens, out=offs[1:])
-            keys2d = g_keys[rr[sel], ii[sel]]                                      # [n, Lcap]
-            flat = keys2d[np.arange(Lcap)[None, :] < lens[:, None]]                # row-major: ask after ask
-            if mdev.type == "cuda":
-                # one pinned block, one host-to-device copy for keys + offsets + exclusions; the tick's own
-                # high-priority stream (its tiny kernels and copies otherwise queue behind the scene kernels)
-                if self._stager is None:
-                    self._stager = _Stage(mdev)
-                    self._stream = torch.cuda.Stream(mdev, priority=-1)
-                with torch.cuda.device(mdev), torch.cuda.stream(self._stream):
-                    d_q, d_off, d_ex, _ = self._stager.put_flat(flat, lens, excl_all[sel].astype(np.int32))
-                    merged, totals = self.matcher.match_topk(d_q, d_off, int(lens.max()) if len(lens) else 0, mm, d_ex,
-                                                             **tol_kw)
-                    Qn, k = merged.shape[0], merged.shape[1]
-                    # ONE device-to-host copy per batch: rows and totals together
-                    both = torch.cat([merged.reshape(Qn, k * 3), totals.reshape(Qn, 1)], dim=1).cpu().numpy()
-            else:
-                if flat.size == 0:
-                    flat = np.zeros(1)
-                d_q = torch.from_numpy(np.ascontiguousarray(flat, dtype=np.float64))
-                d_off = torch.from_numpy(offs)
-                d_ex = torch.from_numpy(excl_all[sel].astype(np.int32))
-                merged, totals = self.matcher.match_topk(d_q, d_off, int(lens.max()) if len(lens) else 0, mm, d_ex,
-                                                         **tol_kw)
-                Qn, k = merged.shape[0], merged.shape[1]
-                both = torch.cat([merged.reshape(Qn, k * 3), totals.reshape(Qn, 1).to(merged.dtype)], dim=1).numpy()
-            for j in np.flatnonzero(mine[sel]):
-                a = int(sel[j])
-                take[int(ii[a])][4].set_result((both[j, :k * 3].reshape(k, 3).copy(), int(both[j, k * 3])))
-        # 3b) near asks, one batched sharded alignment top-k per (eps, max_offset, k, min_votes, min_score): every
-        #     rank reads the same parameters off the gathered headers, so every rank makes the same calls in the
-        #     same order
-        near = kind_all == ASK_NEAR
-        if near.any():
-            par_all = g[rr, ii, 5:H]                                               # [n, 5]
-            for par in sorted(set(map(tuple, par_all[near].tolist()))):
-                sel = np.flatnonzero(near & (par_all == np.asarray(par)).all(axis=1))
-                eps, max_offset, k, min_votes, min_score = par[0], par[1], int(par[2]), int(par[3]), int(par[4])
-                lens = lens_all[sel]
-                flat = g_keys[rr[sel], ii[sel]][np.arange(Lcap)[None, :] < lens[:, None]]
-                kw = dict(eps=eps, max_offset=max_offset, k=k, min_votes=min_votes, min_score=min_score)
-                if mdev.type == "cuda":
-                    if self._stager is None:
-                        self._stager = _Stage(mdev)
-                        self._stream = torch.cuda.Stream(mdev, priority=-1)
-                    with torch.cuda.device(mdev), torch.cuda.stream(self._stream):
-                        d_q, d_off, d_ex, _ = self._stager.put_flat(flat, lens, excl_all[sel].astype(np.int32))
-                        rows, totals = self.matcher.align_topk(d_q, d_off, int(lens.max()), d_exclude_ids=d_ex, **kw)
-                        both = torch.cat([rows.reshape(len(sel), k * 4), totals.reshape(len(sel), 1)], dim=1).cpu().numpy()
-                else:
-                    offs = np.zeros(len(sel) + 1, dtype=np.int64)
-                    np.cumsum(lens, out=offs[1:])
-                    d_q = torch.from_numpy(np.ascontiguousarray(flat if flat.size else np.zeros(1), dtype=np.float64))
-                    rows, totals = self.matcher.align_topk(d_q, torch.from_numpy(offs), int(lens.max()),
-                                                           d_exclude_ids=torch.from_numpy(excl_all[sel].astype(np.int32)), **kw)
-                    both = torch.cat([rows.reshape(len(sel), k * 4), totals.reshape(len(sel), 1).to(rows.dtype)], dim=1).numpy()
-                for j in np.flatnonzero(mine[sel]):
-                    a = int(sel[j])
-                    take[int(ii[a])][4].set_result((both[j, :k * 4].reshape(k, 4).copy(), int(both[j, k * 4])))
-        # 4) exact asks: every rank asks its own shard, counts and padded hit lists are all-gathered
-        sel = np.flatnonzero(kind_all == ASK_EXACT)
-        if len(sel):
-            local = []
-            for a in sel:
-                q = g_keys[rr[a], ii[a], :int(lens_all[a])]
-                try:
-                    if self._local_error is not None:
-                        raise self._local_error
-                    tol_kw = {"tolerance": float(tol_all[a])} if tol_all[a] else {}
-                    local.append(self.shard.find_duplicates(q, int(mm_all[a]), exclude_id=int(excl_all[a]), with_kth=True,
-                                                            **tol_kw))
-                except Exception as e:                       # noqa: BLE001 - this rank's own work: finish the tick's collectives
-                    self._local_error = e                    # with a poisoned count (below): every rank stops in this tick
-                    local.append([])
-            # (a rank whose own shard failed sends -1: every rank reads the same counts and stops in THIS tick, before
-            # anybody's ask is answered from an incomplete set of shards)
-            counts = torch.tensor([-1 if self._local_error is not None else len(h) for h in local], dtype=torch.int64,
-                                  device=self.xdev)
-            allcounts = self._gather(counts).cpu().numpy()                         # [world, n]
-            if (allcounts < 0).any():
-                bad = [int(r) for r in np.flatnonzero((allcounts < 0).any(axis=1))]
-                raise RuntimeError(f"the shard of rank(s) {bad} failed: the sharded service stops"
-                                   + (f" ({self._local_error!r})" if self._local_error is not None else ""))
-            width = int(allcounts.max())
-            if width:
-                pad = np.full((len(sel), width, 3), -1, dtype=np.int32)
-                for j, h in enumerate(local):
-                    if h:
-                        pad[j, :len(h)] = np.asarray(h, dtype=np.int32)
-                allhits = self._gather(torch.from_numpy(pad).to(self.xdev)).cpu().numpy()   # [world, n, width, 3]
-            for j in np.flatnonzero(mine[sel]):
-                a = int(sel[j])
-                rows = [allhits[r, j, :int(allcounts[r, j])] for r in range(self.world) if allcounts[r, j]] if width else []
-                hits = sorted((int(v), int(c), int(k)) for v, c, k in np.concatenate(rows)) if rows else []
-                take[int(ii[a])][4].set_result(hits)
+            d_q = torch.from_numpy(np.ascontiguousarray(flat if flat.size else np.zeros(1), dtype=np.float64))
+            rows, totals = _to_host(*call(d_q, torch.from_numpy(offs), int(lens.max()), torch.from_numpy(excl)))
+        for j in np.flatnonzero(asks.mine[sel]):
+            take[int(asks.ii[sel[j]])][4].set_result((rows[j].copy(), int(totals[j])))
+
+    def _answer_topk(self, asks: _Asks, take) -> None:
+        """Top-k asks: one batched sharded match per (min_match, tolerance); the matcher hears of a tolerance only
+        when there is one."""
+        topk = asks.kind == ASK_TOPK
+        for mm, tol in sorted(set(zip(asks.min_match[topk].tolist(), asks.tol[topk].tolist()))):
+            tol_kw = {"tolerance": tol} if tol else {}
+            self._answer_batch(asks, take, np.flatnonzero(topk & (asks.min_match == mm) & (asks.tol == tol)),
+                               lambda d_q, d_off, max_len, d_ex: self.matcher.match_topk(d_q, d_off, max_len, mm, d_ex,
+                                                                                         **tol_kw))
+
+    def _answer_near(self, asks: _Asks, take) -> None:
+        """Near asks: one batched sharded alignment top-k per (eps, max_offset, k, min_votes, min_score): every rank
+        reads the same parameters off the gathered headers, so every rank makes the same calls in the same order."""
+        near = asks.kind == ASK_NEAR
+        for par in sorted(set(map(tuple, asks.near[near].tolist()))):
+            kw = dict(eps=par[0], max_offset=par[1], k=int(par[2]), min_votes=int(par[3]), min_score=int(par[4]))
+            self._answer_batch(asks, take, np.flatnonzero(near & (asks.near == np.asarray(par)).all(axis=1)),
+                               lambda d_q, d_off, max_len, d_ex: self.matcher.align_topk(d_q, d_off, max_len,
+                                                                                         d_exclude_ids=d_ex, **kw))
+
+    def _answer_exact(self, asks: _Asks, take) -> None:
+        """Exact asks: every rank asks its own shard, counts and padded hit lists are all-gathered."""
+        sel = np.flatnonzero(asks.kind == ASK_EXACT)
+        if not len(sel):
+            return
+        local = []
+        for a in sel:
+            q = asks.keys[asks.rr[a], asks.ii[a], :int(asks.lens[a])]
+            try:
+                if self._local_error is not None:
+                    raise self._local_error
+                tol_kw = {"tolerance": float(asks.tol[a])} if asks.tol[a] else {}
+                local.append(self.shard.find_duplicates(q, int(asks.min_match[a]), exclude_id=int(asks.excl[a]),
+                                                        with_kth=True, **tol_kw))
+            except Exception as e:                           # noqa: BLE001 - this rank's own work: finish the tick's collectives
+                self._local_error = e                        # with a poisoned count (below): every rank stops in this tick
+                local.append([])
+        # (a rank whose own shard failed sends -1: every rank reads the same counts and stops in THIS tick, before
+        # anybody's ask is answered from an incomplete set of shards)
+        counts = torch.tensor([-1 if self._local_error is not None else len(h) for h in local], dtype=torch.int64,
+                              device=self.xdev)
+        allcounts = self._gather(counts).cpu().numpy()                             # [world, n]
+        if (allcounts < 0).any():
+            bad = [int(r) for r in np.flatnonzero((allcounts < 0).any(axis=1))]
+            raise RuntimeError(f"the shard of rank(s) {bad} failed: the sharded service stops"
+                               + (f" ({self._local_error!r})" if self._local_error is not None else ""))
+        width = int(allcounts.max())
+        if width:
+            pad = np.full((len(sel), width, 3), -1, dtype=np.int32)
+            for j, h in enumerate(local):
+                if h:
+                    pad[j, :len(h)] = np.asarray(h, dtype=np.int32)
+            allhits = self._gather(torch.from_numpy(pad).to(self.xdev)).cpu().numpy()       # [world, n, width, 3]
+        for j in np.flatnonzero(asks.mine[sel]):
+            rows = [allhits[r, j, :int(allcounts[r, j])] for r in range(self.world) if allcounts[r, j]] if width else []
+            hits = sorted((int(v), int(c), int(k)) for v, c, k in np.concatenate(rows)) if rows else []
+            take[int(asks.ii[sel[j]])][4].set_result(hits)
 
     def close(self) -> None:
         """Collective: every rank calls it; the loops leave together once nothing is pending."""

@@ -18,7 +18,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-KTH_NEVER = 0x7FFFFFFF
+from . import _lib, corpus as tc
+from ._lib import KTH_NEVER
 
 
 def shard_bounds(offsets: np.ndarray, world: int) -> np.ndarray:
@@ -45,8 +46,6 @@ class HipBackend:
     supports_tolerance = True
 
     def __init__(self, corpus):
-        from . import corpus as tc
-        self._tc = tc
         self.corpus = corpus
 
     def match(self, d_q, d_off, max_len, min_match, cap, d_excl):
@@ -60,10 +59,10 @@ class HipBackend:
         return self.corpus.match_topk(d_q, d_off, max_len, min_match, cap, k, d_exclude_ids=d_excl)
 
     def topk_shard(self, hits, hits_n, k):
-        return self._tc.topk_shard(hits, hits_n, k)
+        return tc.topk_shard(hits, hits_n, k)
 
     def topk_merge(self, gathered, k):
-        return self._tc.topk_merge(gathered, k)
+        return tc.topk_merge(gathered, k)
 
     def local_align_topk(self, d_q, d_off, max_len, eps, max_offset, k, min_votes, min_score, d_excl):
         """this rank's alignment top-k block (tvz_align_topk): int32 [Q, k+1, 4] on the device"""
@@ -71,7 +70,7 @@ class HipBackend:
                                             min_votes=min_votes, min_score=min_score, d_exclude_ids=d_excl)
 
     def align_topk_merge(self, gathered, k, d_q, d_off):
-        return self._tc.align_topk_merge(gathered, k, d_q, d_off)
+        return tc.align_topk_merge(gathered, k, d_q, d_off)
 
 
 class ShardedMatcher:
@@ -112,13 +111,18 @@ class ShardedMatcher:
             hits, n = self.backend.match(d_queries, d_q_offsets, max_query_len, min_match, self.cap,
                                          d_exclude_ids)
             local = self.backend.topk_shard(hits, n, self.k)          # [Q, k+1, 3]
-        Q = local.shape[0]
+        return self._all_gather_blocks(local, async_op=True) + (local,)
+
+    def _all_gather_blocks(self, local: torch.Tensor, async_op: bool):
+        """This rank's block [Q, k+1, w] -> (every rank's, as [world, Q, k+1, w]; the collective's work handle, None
+        where there was none to start or to wait for)."""
         if not self.collective:
-            return (local.view(1, Q, self.k + 1, 3), None, local)
+            return local.view((1,) + tuple(local.shape)), None
         # dim-0 concatenation is the layout both RCCL and gloo accept for all_gather_into_tensor
-        flat = torch.empty((self.world * Q, self.k + 1, 3), dtype=torch.int32, device=local.device)
-        work = dist.all_gather_into_tensor(flat, local.contiguous(), group=self.group, async_op=True)
-        return (flat.view(self.world, Q, self.k + 1, 3), work, local)
+        flat = torch.empty((self.world * local.shape[0],) + tuple(local.shape[1:]), dtype=torch.int32,
+                           device=local.device)
+        work = dist.all_gather_into_tensor(flat, local.contiguous(), group=self.group, async_op=async_op)
+        return flat.view((self.world,) + tuple(local.shape)), work
 
     def finish(self, ticket):
         """-> (merged int32 [Q,k,3] of (video_id, count, kth), total_hits int32 [Q]) — identical on
@@ -134,7 +138,6 @@ class ShardedMatcher:
         return self.finish(self.submit(d_queries, d_q_offsets, max_query_len, min_match, d_exclude_ids,
                                        tolerance=tolerance))
 
-
     def align_topk(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, eps: float,
                    max_offset: float, k: int, min_votes: int = 1, min_score: int = 0,
                    d_exclude_ids: Optional[torch.Tensor] = None):
@@ -146,12 +149,8 @@ class ShardedMatcher:
                 raise RuntimeError(f"{type(self.backend).__name__} has no {name}")
         local = self.backend.local_align_topk(d_queries, d_q_offsets, max_query_len, eps, max_offset, int(k),
                                               int(min_votes), int(min_score), d_exclude_ids)
-        Q = local.shape[0]
-        if not self.collective:
-            return self.backend.align_topk_merge(local.view(1, Q, k + 1, 4), k, d_queries, d_q_offsets)
-        flat = torch.empty((self.world * Q, k + 1, 4), dtype=torch.int32, device=local.device)
-        dist.all_gather_into_tensor(flat, local.contiguous(), group=self.group)
-        return self.backend.align_topk_merge(flat.view(self.world, Q, k + 1, 4), k, d_queries, d_q_offsets)
+        gathered, _ = self._all_gather_blocks(local, async_op=False)
+        return self.backend.align_topk_merge(gathered, k, d_queries, d_q_offsets)
 
     @property
     def supports_align_topk(self) -> bool:
@@ -161,7 +160,6 @@ class ShardedMatcher:
 def make_comm(device: int, group=None):
     """Create the libtvz RCCL communicator of this rank.  torch.distributed (any backend) is used
     ONLY to ship rank 0's 128-byte unique id; a non-Python host ships it by its own means."""
-    from . import corpus as tc
     if not dist.is_initialized():          # a single process: a one-rank communicator, same data path
         return tc.Comm(tc.Comm.unique_id(), 1, 0, device)
     world, rank = dist.get_world_size(group), dist.get_rank(group)
@@ -169,6 +167,16 @@ def make_comm(device: int, group=None):
     dist.broadcast_object_list(box, src=dist.get_global_rank(group, 0) if group is not None else 0,
                                group=group)
     return tc.Comm(box[0], world, rank, device)
+
+
+class _Slot:
+    """What one of RcclShardedMatcher's side streams owns: its event, submit's workspace and (merged, totals), and
+    align_topk's own pair (its rows are 4 wide and `k` is the call's own)."""
+    __slots__ = ("stream", "event", "ws", "out", "near_ws", "near_out")
+
+    def __init__(self, stream):
+        self.stream, self.event = stream, torch.cuda.Event()
+        self.ws = self.out = self.near_ws = self.near_out = None
 
 
 class RcclShardedMatcher:
@@ -183,7 +191,6 @@ class RcclShardedMatcher:
         """`priority=-1`: the service's ticks - a few tiny launches that should not queue behind the upload
         workers' scene kernels."""
         self.corpus, self.comm = corpus, comm
-        from . import _lib
         self.algo = int(algo)               # _lib.ALGO_* (+ ALGO_PAIR / ALGO_NO_PAIR) of every batch
         if not self.algo & (_lib.ALGO_PAIR | _lib.ALGO_NO_PAIR) and n_streams < 3:
             # two queries per lookup block pay off when a THIRD batch's blocks fill the longer tail of a launch
@@ -198,12 +205,7 @@ class RcclShardedMatcher:
         self.world, self.rank = comm.n_ranks, comm.rank
         self.collective = True
         self.dev = torch.device("cuda", corpus.device)
-        self.streams = [torch.cuda.Stream(self.dev, priority=priority) for _ in range(n_streams)]
-        self.ws = [None] * n_streams
-        self.out = [None] * n_streams
-        self.near_ws = [None] * n_streams   # align_topk's own workspaces and outputs
-        self.near_out = [None] * n_streams
-        self.events = [torch.cuda.Event() for _ in range(n_streams)]
+        self._slots = [_Slot(torch.cuda.Stream(self.dev, priority=priority)) for _ in range(n_streams)]
         self._i = 0
         self._plans = {}                    # (slot, query tensors, shape) -> the library call's arguments (submit)
         self._lib = _lib
@@ -211,6 +213,15 @@ class RcclShardedMatcher:
         self._call_tol = comm.lib.tvz_match_tol_sharded
 
     supports_tolerance = True
+
+    def _next_slot(self) -> _Slot:
+        """The side stream a call runs on; the calls take them in turn."""
+        slot = self._slots[self._i]
+        self._i = (self._i + 1) % len(self._slots)
+        return slot
+
+    def _drop_plans(self, i: int) -> None:
+        self._plans = {k_: v for k_, v in self._plans.items() if k_[0] != i}
 
     def submit(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int,
                min_match: int, d_exclude_ids: Optional[torch.Tensor] = None, inputs_ready: bool = False,
@@ -228,11 +239,11 @@ class RcclShardedMatcher:
         (profiles/r3_shard_pipeline.txt).
         `tolerance` > 0: the opt-in tolerant match (tvz_match_tol_sharded: the sweep keeps its k best itself, `cap`
         and `algo` play no part); it is part of the plan's key and the plan has its own workspace size."""
-        from . import corpus as tc
         tolerance = float(tolerance)
-        i = self._i
-        self._i = (i + 1) % len(self.streams)
-        st = self.streams[i]
+        i = self._i                         # (the rotation stays written out here: submit is the hot path)
+        self._i = (i + 1) % len(self._slots)
+        slot = self._slots[i]
+        st = slot.stream
         # Steady state: the same query tensors come round again (a service's staging slots, a benchmark's rotating
         # batches).  Everything that does not change with them - workspace, outputs, the seventeen arguments of the
         # library call - is kept as a PLAN per (slot, tensors, shape): a batch on a 1/8 shard is ~40 us of GPU time and
@@ -243,40 +254,36 @@ class RcclShardedMatcher:
             key += (tolerance,)
         plan = self._plans.get(key)
         if plan is None:
-            Q = d_q_offsets.numel() - 1
-            self.corpus._check_queries(d_queries, d_q_offsets)
+            _, Q = self.corpus._check_queries(d_queries, d_q_offsets)
             if tolerance:
                 need = tc.tol_topk_workspace_bytes(Q, max_query_len, d_queries.numel(), self.k, self.world)
             else:
                 need = tc.workspace_bytes(Q, max_query_len, self.cap, self.k, self.world, d_queries.numel())
-            if self.ws[i] is None or self.ws[i].numel() < need:
-                self.ws[i] = torch.empty(need, dtype=torch.uint8, device=self.dev)
-                self._plans = {k_: v for k_, v in self._plans.items() if k_[0] != i}     # (their workspace is gone)
-            if self.out[i] is None or self.out[i][0].shape[0] != Q:
-                self.out[i] = (torch.empty((Q, self.k, 3), dtype=torch.int32, device=self.dev),
-                               torch.empty(Q, dtype=torch.int32, device=self.dev))
-                self._plans = {k_: v for k_, v in self._plans.items() if k_[0] != i}
-            merged, totals = self.out[i]
+            if slot.ws is None or slot.ws.numel() < need:
+                slot.ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+                self._drop_plans(i)         # (their workspace is gone)
+            if slot.out is None or slot.out[0].shape[0] != Q:
+                slot.out = tc._topk_out(None, Q, self.k, 3, self.dev)
+                self._drop_plans(i)
+            merged, totals = slot.out
+            head = (self.corpus._h, self.comm._h, key[1], key[2], Q, key[3])
+            tail = (self.k, merged.data_ptr(), totals.data_ptr(), slot.ws.data_ptr(), slot.ws.numel())
             if tolerance:
                 call = self._call_tol
-                args = (self.corpus._h, self.comm._h, key[1], key[2], Q, key[3], tolerance, key[4], key[5] or None,
-                        self.k, merged.data_ptr(), totals.data_ptr(), self.ws[i].data_ptr(), self.ws[i].numel(),
-                        st.cuda_stream)
+                args = head + (tolerance, key[4], key[5] or None) + tail + (st.cuda_stream,)
             else:
                 call = self._call
-                args = (self.corpus._h, self.comm._h, key[1], key[2], Q, key[3], key[4], key[5] or None, self.cap,
-                        self.k, merged.data_ptr(), totals.data_ptr(), self.ws[i].data_ptr(), self.ws[i].numel(),
-                        self.algo, st.cuda_stream)
+                args = head + (key[4], key[5] or None, self.cap) + tail + (self.algo, st.cuda_stream)
             if len(self._plans) > 256:
                 self._plans.clear()
-            plan = self._plans[key] = (args, merged, totals, self.ws[i], call)
+            plan = self._plans[key] = (args, merged, totals, slot.ws, call)
         args, merged, totals, _ws, call = plan
         if not inputs_ready:
             st.wait_stream(torch.cuda.current_stream(self.dev))   # the queries are complete before the match reads them
         rc = call(*args)
         if rc:
             self._lib.check(rc)
-        ev = self.events[i]
+        ev = slot.event
         ev.record(st)
         return (merged, totals, ev)
 
@@ -305,25 +312,21 @@ class RcclShardedMatcher:
         streams; the current stream waits for it.  -> (rows int32 [Q,k,4], totals int32 [Q]), this matcher's tensors,
         overwritten `n_streams` calls later.  Its own workspace (the rows are 4 wide, `k` is the call's own) and no
         plan: the near-duplicate report is one call per upload, not the tick's stream of batches."""
-        from . import corpus as tc
-        i = self._i
-        self._i = (i + 1) % len(self.streams)
-        st = self.streams[i]
-        self.corpus._check_queries(d_queries, d_q_offsets)
-        Q, k = d_q_offsets.numel() - 1, int(k)
+        slot = self._next_slot()
+        st = slot.stream
+        (_, Q), k = self.corpus._check_queries(d_queries, d_q_offsets), int(k)
         need = tc.align_topk_sharded_workspace_bytes(Q, max_query_len, d_queries.numel(), k, self.world)
-        if self.near_ws[i] is None or self.near_ws[i].numel() < need:
-            self.near_ws[i] = torch.empty(max(need, 256), dtype=torch.uint8, device=self.dev)
-        if self.near_out[i] is None or self.near_out[i][0].shape[:2] != (Q, k):
-            self.near_out[i] = (torch.empty((Q, k, 4), dtype=torch.int32, device=self.dev),
-                                torch.empty(Q, dtype=torch.int32, device=self.dev))
+        if slot.near_ws is None or slot.near_ws.numel() < need:
+            slot.near_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.dev)
+        if slot.near_out is None or slot.near_out[0].shape[:2] != (Q, k):
+            slot.near_out = tc._topk_out(None, Q, k, 4, self.dev)
         st.wait_stream(torch.cuda.current_stream(self.dev))       # the queries are complete; the slot's last answer is read
         rows, totals = self.comm.align_topk_sharded(self.corpus, d_queries, d_q_offsets, max_query_len, eps=eps,
                                                     max_offset=max_offset, k=k, min_votes=min_votes,
                                                     min_score=min_score, d_exclude_ids=d_exclude_ids,
-                                                    workspace=self.near_ws[i], stream=st, out=self.near_out[i])
-        self.events[i].record(st)
-        torch.cuda.current_stream(self.dev).wait_event(self.events[i])
+                                                    workspace=slot.near_ws, stream=st, out=slot.near_out)
+        slot.event.record(st)
+        torch.cuda.current_stream(self.dev).wait_event(slot.event)
         return rows, totals
 
 
