@@ -123,6 +123,23 @@ def test_entry_points_fail_gracefully_without_a_gpu():
         scene.SceneScorer(32, 32, 4, "cpu")
 
 
+def test_topk_entry_points_refuse_k_out_of_range_with_one_message():
+    """tvz_topk, tvz_topk_shard and tvz_topk_merge check k against [1, 1024] in front of every pointer check and HIP
+    call (so with or without a GPU), and say so in the same words."""
+    from tvidz_amd import _lib
+    lib = _lib.load()
+    for k in (0, 1025):
+        calls = (lambda: lib.tvz_topk(None, None, 1, 4, 8, k, None, None),
+                 lambda: lib.tvz_topk_shard(None, None, 4, 8, k, None, None),
+                 lambda: lib.tvz_topk_merge(None, 2, 4, k, None, None, None))
+        msgs = []
+        for call in calls:
+            assert call() != 0
+            msgs.append(lib.tvz_last_error().decode())
+        assert f"k={k} " in msgs[0] and "range [1, 1024]" in msgs[0], msgs
+        assert msgs[0] == msgs[1] == msgs[2], msgs
+
+
 def test_diagnostic_builds_report_the_negated_header_version_and_are_quarantined(tmp_path):
     """A library compiled with one of the TVZ_IX_* diagnostic defines (profiles/variant_build.sh: some return WRONG
     results on purpose) reports a negated version, and the product binding refuses to load it; build.build()

@@ -1,6 +1,7 @@
 """The case tables of the top-k edge tests (tests/topk_cases.py), checked without a GPU: the thresholds they assume are
-the ones in the sources, every branch they name is reached by some case, the generator is deterministic, and the
-reference (tests/topk_ref.py) agrees with the CPU stand-in of the sharded service (tests/fakes.py)."""
+the ones in the sources (tvz_topk_kernels.h and the launchers in tvz_match.hip), every branch they name is reached by
+some case, the generator is deterministic, and the reference (tests/topk_ref.py) agrees with the CPU stand-in of the
+sharded service (tests/fakes.py)."""
 import os
 import re
 
@@ -29,16 +30,17 @@ def _const(text, name):
 
 
 def test_assumed_thresholds_are_the_ones_in_the_sources():
-    kern, host, common = _src("tvz_match_kernels.h"), _src("tvz_match.hip"), _src("tvz_common.h") + _src("tvz_match_kernels.h")
+    kern, host, common = _src("tvz_topk_kernels.h"), _src("tvz_match.hip"), _src("tvz_common.h") + _src("tvz_match_kernels.h")
     C = cases.CONSTANTS
     for name in ("kSelMin", "kSelSmallK", "kSortCap", "kSelBins", "kWsE", "kWsK"):
         assert _const(kern, name) == C[name], name
     assert _const(host, "kTopkFallbackBlocks") == C["kTopkFallbackBlocks"]
     assert _const(common, "kBlock") == C["kBlock"]
     # the sorted merge's bounds and the one-wave merge's, as launch_topk_lists states them
-    m = re.search(r"mode == 2 && n_lists <= (\d+) && k <= (\d+)", host)
-    assert m and (int(m.group(1)), int(m.group(2))) == (C["merge_sorted_max_lists"], C["merge_sorted_max_k"])
-    assert re.search(r"mode == 2 && k <= kWsK && \(int64_t\)n_lists \* k <= kWsMax", host)
+    assert re.search(r"form == kTopkMerge && n_lists <= kMsMaxLists && k <= kMsMaxK", host)
+    assert (_const(kern, "kMsMaxLists"), _const(kern, "kMsMaxK")) == (C["merge_sorted_max_lists"], C["merge_sorted_max_k"])
+    assert re.search(r"form == kTopkMerge && k <= kWsK && \(int64_t\)n_lists \* k <= kWsMax", host)
+    assert re.search(r"enum TopkForm : int32_t \{ kTopkPlain = 0, kTopkShard = 1, kTopkMerge = 2, kTopkPair = 3 \};", kern)
     assert re.search(r"constexpr int kWsMax = 64 \* kWsE;", kern)
     # launch_topk_local: the one-wave kernel in front for k <= kWsK, the smaller select kernel for k <= kSelSmallK
     assert re.search(r"if \(d_flags && k <= kWsK\)", host)
@@ -47,7 +49,7 @@ def test_assumed_thresholds_are_the_ones_in_the_sources():
     # the one-wave kernel's size classes and its `fits` bound; the select kernels' histogram bound and reduction
     assert "if (n <= 64 * 4)" in kern and "else if (n <= 64 * 8)" in kern and "if (n > kWsMax)" in kern
     assert "fits = upto <= 64u;" in kern and "if (n > kSelMin)" in kern
-    assert "if (pos > kSelCap - kSelChunk)" in kern and "if (pos == kSortCap) sort_and_keep();" in kern
+    assert "if (pos > kSelCap - kSelChunk)" in kern and "if (pos == kSortCap) sort_and_keep(key, cnt, pos, k);" in kern
     assert cases.SEL_BINS_PER_THREAD == 17 and cases.WS_BINS_PER_LANE == 66
 
 

@@ -1,6 +1,6 @@
-"""The top-k family of tvz_match_kernels.h - ts_topk_select_kernel<1024 / 2048>, ts_topk_kernel, ts_topk_wave_kernel
-(E = 4/8/16, modes 1, 2, 3), ts_topk_merge_sorted_kernel<1..16> - at every size class, tie path and totals rule the
-dispatch in tvz_match.hip has, against tests/topk_ref.py (a Python sorted() and a sum).  The inputs are the hand-made
+"""The top-k family of tvz_topk_kernels.h - ts_topk_select_kernel<1024 / 2048>, ts_topk_kernel, ts_topk_wave_kernel
+(E = 4/8/16; the shard, merge and pair forms: modes 1, 2, 3 in the case tables), ts_topk_merge_sorted_kernel<1..16> -
+at every size class, tie path and totals rule the dispatch in tvz_match.hip has, against tests/topk_ref.py (a Python sorted() and a sum).  The inputs are the hand-made
 lists of tests/topk_cases.py, each in ascending, descending and shuffled order; every comparison is exact equality of
 int32 rows and totals."""
 import numpy as np
@@ -177,6 +177,28 @@ def test_match_topk_lists_of_chosen_length_and_ties(match_case, algo):
             what = (k, cases.MATCH_LISTS[q][0], cases.local_branches(lst, k, True))
             assert _rows(got[q]) == ref.select(lst, len(lst), cap, k, True), what
             assert (unfused[q] == got[q]).all(), what
+
+
+def test_match_topk_at_the_largest_k_and_past_it():
+    """k = 1024, the largest the library takes: 1,024 rows per query, all but the few hits padding, and the totals
+    row.  k = 1025 is refused."""
+    Q, cap = 3, 1024
+    rows = cases._hit_rows(0, list(range(25)), 1) + cases._hit_rows(1, [7] * 15, 26)         # 40 rows; query 2 hits none
+    queries = [cases.query_keys(i) for i in range(Q)]
+    lists = _oracle_lists(rows, queries)
+    assert len(rows) == 40 and [len(x) for x in lists] == [25, 15, 0]
+    dc = tc.DeviceCorpus(0)
+    try:
+        dc.upload(rows)
+        d_q, d_off, max_len = tc.pack_queries(queries, DEV)
+        with pytest.raises(RuntimeError, match=r"k=1025 out of range \[1, 1024\]"):
+            dc.match_topk(d_q, d_off, max_len, 1, cap, 1025)
+        got = dc.match_topk(d_q, d_off, max_len, 1, cap, 1024).cpu().numpy()
+    finally:
+        dc.close()
+    assert got.shape == (Q, 1025, 3)
+    for q, lst in enumerate(lists):
+        assert _rows(got[q]) == ref.select(lst, len(lst), cap, 1024, True), q
 
 
 @pytest.fixture(scope="module")

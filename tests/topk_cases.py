@@ -3,10 +3,11 @@ checks the tables themselves on any machine).
 
 The tables are data: list lengths, k, cap, R, Q, the kth pattern, the value pattern and the entry order.  Every case
 names the branches it is built to reach; the names come from a restatement, below, of the dispatch in tvz_match.hip
-(launch_topk_local, launch_topk_lists) and of the paths inside the kernels of tvz_match_kernels.h that depend on
-the input alone (histogram or direct sort, mid-stream reduction, the one-wave kernel's E and `fits`, the threshold
-bin's place in the walk).  The thresholds assumed here are in CONSTANTS; test_topk_cases_cpu.py compares them with
-the sources, so a changed threshold fails there instead of silently moving the edges away from the cases."""
+(launch_topk_local, launch_topk_lists, launch_topk_pair) and of the paths inside the kernels of tvz_topk_kernels.h
+that depend on the input alone (histogram or direct sort, mid-stream reduction, the one-wave kernel's E and `fits`,
+the threshold bin's place in the walk).  `mode` 0..3 here is the kernels' TopkForm: plain, shard, merge, pair.  The
+thresholds assumed here are in CONSTANTS; test_topk_cases_cpu.py compares them with the sources, so a changed
+threshold fails there instead of silently moving the edges away from the cases."""
 import zlib
 
 import numpy as np
@@ -25,7 +26,7 @@ CONSTANTS = {
     "kWsK": 64,                     # the one-wave kernel's largest k
     "kTopkFallbackBlocks": 1280,    # grid of the block kernel behind the one-wave kernel
     "kBlock": 256,
-    "merge_sorted_max_lists": 16,   # launch_topk_lists: mode == 2 && n_lists <= 16 && k <= 64
+    "merge_sorted_max_lists": 16,   # launch_topk_lists: the merge form && n_lists <= kMsMaxLists && k <= kMsMaxK
     "merge_sorted_max_k": 64,
 }
 C = CONSTANTS

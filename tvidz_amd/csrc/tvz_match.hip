@@ -711,34 +711,41 @@ int launch_match(tvz_corpus *c, const Batch &b, const HitSink &out, const JoinSc
     return launch_match_short(c, b, out, scratch, algo, st);
 }
 
+// ---- the top-k launchers (forms and kernels: tvz_topk_kernels.h) ----
 constexpr int kTopkFallbackBlocks = 256 * 5;     // the block kernels behind the one-wave kernel: a chip-full, grid-stride
 
+int check_topk_k(int32_t k) {
+    TVZ_REQUIRE(k >= 1 && k <= kSortCap / 2, "k=%d out of range [1, %d]", k, kSortCap / 2);
+    return TVZ_OK;
+}
+
+// one hit list per query (plain) / with its counter, into a block (shard)
 int launch_topk_local(const int32_t *d_hits, const int32_t *d_hits_n, int32_t ns, int32_t Q, int32_t cap,
-                      int32_t k, int32_t *d_out, int mode, int32_t *d_flags, hipStream_t st) {
+                      int32_t k, int32_t *d_out, TopkForm form, int32_t *d_flags, hipStream_t st) {
     // with a flag array (the batched calls' workspace): short lists by one wave each, the block kernel
     // follows with a small grid for the queries that were flagged
     const int32_t *flags = nullptr;
     unsigned grid = (unsigned)Q;
     if (d_flags && k <= kWsK) {
         hipLaunchKernelGGL(ts_topk_wave_kernel, dim3((unsigned)tvz::ceil_div(Q, kBlock / 64)), dim3(kBlock), 0, st,
-                           d_hits, d_hits_n, ns, 1, Q, cap, k, d_out, mode, nullptr, d_flags);
+                           d_hits, d_hits_n, ns, 1, Q, cap, k, d_out, form, nullptr, d_flags, 0);
         flags = d_flags;
         grid = (unsigned)std::min<int64_t>(Q, kTopkFallbackBlocks);
     }
     if (k <= kSelSmallK)
         hipLaunchKernelGGL(ts_topk_select_kernel<4 * kSelSmallK>, dim3(grid), dim3(kBlock), 0, st, d_hits,
-                           d_hits_n, ns, Q, cap, k, d_out, mode, flags);
+                           d_hits_n, ns, Q, cap, k, d_out, form, flags);
     else
         hipLaunchKernelGGL(ts_topk_select_kernel<kSortCap>, dim3(grid), dim3(kBlock), 0, st, d_hits,
-                           d_hits_n, ns, Q, cap, k, d_out, mode, flags);
+                           d_hits_n, ns, Q, cap, k, d_out, form, flags);
     TVZ_HIP(hipGetLastError());
     return TVZ_OK;
 }
 
-// merge of n_lists per-rank blocks of k + 1 rows (mode 2) / plain top-k over n_lists lists (mode 0)
+// merge of n_lists per-rank blocks of k + 1 rows (merge) / top-k over n_lists lists (plain)
 int launch_topk_lists(const int32_t *d_lists, const int32_t *d_lists_n, int32_t n_lists, int32_t Q, int32_t cap,
-                      int32_t k, int32_t *d_topk, int mode, int32_t *d_totals, hipStream_t st) {
-    if (mode == 2 && n_lists <= 16 && k <= 64) {
+                      int32_t k, int32_t *d_topk, TopkForm form, int32_t *d_totals, hipStream_t st) {
+    if (form == kTopkMerge && n_lists <= kMsMaxLists && k <= kMsMaxK) {
         // the gathered blocks are sorted (tvz_match_topk / tvz_topk_shard wrote them): a k-way merge, 64 / G queries
         // per wave, instead of a selection over an unordered set
         int G = 1;
@@ -757,15 +764,24 @@ int launch_topk_lists(const int32_t *d_lists, const int32_t *d_lists_n, int32_t 
         TVZ_HIP(hipGetLastError());
         return TVZ_OK;
     }
-    if (mode == 2 && k <= kWsK && (int64_t)n_lists * k <= kWsMax) {
+    if (form == kTopkMerge && k <= kWsK && (int64_t)n_lists * k <= kWsMax) {
         // n_lists x k entries fit one wave's registers: no block kernel, no flags
         hipLaunchKernelGGL(ts_topk_wave_kernel, dim3((unsigned)tvz::ceil_div(Q, kBlock / 64)), dim3(kBlock), 0, st,
-                           d_lists, nullptr, 1, n_lists, Q, cap, k, d_topk, 2, d_totals, nullptr);
+                           d_lists, nullptr, 1, n_lists, Q, cap, k, d_topk, form, d_totals, nullptr, 0);
         TVZ_HIP(hipGetLastError());
         return TVZ_OK;
     }
     hipLaunchKernelGGL(ts_topk_kernel, dim3((unsigned)Q), dim3(kBlock), 0, st, d_lists, d_lists_n, n_lists, Q,
-                       cap, k, d_topk, mode, d_totals, static_cast<const int32_t *>(nullptr));
+                       cap, k, d_topk, form, d_totals);
+    TVZ_HIP(hipGetLastError());
+    return TVZ_OK;
+}
+
+// the index lookup's block and the delta table's, side by side in pair_blocks -> one block; a total above hit_cap
+// is negated: the one hit list of an unfused match would have overflowed
+int launch_topk_pair(const int32_t *pair_blocks, int32_t Q, int32_t k, int32_t hit_cap, int32_t *d_out, hipStream_t st) {
+    hipLaunchKernelGGL(ts_topk_wave_kernel, dim3((unsigned)tvz::ceil_div(Q, kBlock / 64)), dim3(kBlock), 0, st,
+                       pair_blocks, nullptr, 1, 2, Q, k + 1, k, d_out, kTopkPair, nullptr, nullptr, hit_cap);
     TVZ_HIP(hipGetLastError());
     return TVZ_OK;
 }
@@ -786,7 +802,7 @@ int tvz_match_topk_local(tvz_corpus *c, const Batch &b, int32_t cap, int32_t k, 
                          int32_t n_ranks, int32_t algo, void *hip_stream, ShardBlocks *blocks) {
     const int32_t Q = b.Q, max_query_len = b.max_query_len, min_match = b.min_match;
     if (int rc = check_batch_args(c, b, cap)) return rc;
-    TVZ_REQUIRE(k >= 1 && k <= kSortCap / 2, "k=%d out of range [1, %d]", k, kSortCap / 2);
+    if (int rc = check_topk_k(k)) return rc;
     constexpr int32_t kShape = TVZ_ALGO_PAIR | TVZ_ALGO_NO_PAIR | TVZ_ALGO_WAVE | TVZ_ALGO_NO_WAVE | TVZ_ALGO_PREFER_WAVE;
     const int32_t flags = algo & kShape;                                  // shape of the fused lookup (tvz.h)
     algo &= ~kShape;
@@ -819,16 +835,13 @@ int tvz_match_topk_local(tvz_corpus *c, const Batch &b, int32_t cap, int32_t k, 
             int a = pick_algo(TVZ_ALGO_AUTO, Q, span.n, max_query_len, min_match);
             if (int rc = launch_scan(c, span, a, true, b, out, w.scratch(), st)) return rc;
             int32_t *blk2 = w.pair + (size_t)Q * (size_t)(k + 1) * 3;
-            if (int rc = launch_topk_local(out.d_hits, out.d_hits_n, out.ns, Q, cap, k, blk2, 1, w.flags, st)) return rc;
-            hipLaunchKernelGGL(ts_topk_wave_kernel, dim3((unsigned)tvz::ceil_div(Q, kBlock / 64)), dim3(kBlock), 0, st,
-                               w.pair, nullptr, /* mode 3: ns = the hit capacity */ cap, 2, Q, k + 1, k, d_out, 3,
-                               nullptr, nullptr);
-            TVZ_HIP(hipGetLastError());
+            if (int rc = launch_topk_local(out.d_hits, out.d_hits_n, out.ns, Q, cap, k, blk2, kTopkShard, w.flags, st)) return rc;
+            if (int rc = launch_topk_pair(w.pair, Q, k, cap, d_out, st)) return rc;
         }
         return record(c, st);
     }
     if (int rc = launch_match(c, b, out, w.scratch(), algo, st)) return rc;
-    if (int rc = launch_topk_local(out.d_hits, out.d_hits_n, out.ns, Q, cap, k, d_out, 1, w.flags, st)) return rc;
+    if (int rc = launch_topk_local(out.d_hits, out.d_hits_n, out.ns, Q, cap, k, d_out, kTopkShard, w.flags, st)) return rc;
     return record(c, st);
 }
 
@@ -1562,30 +1575,30 @@ static int tvz_find_duplicates_impl(tvz_corpus *c, const double *h_query, int64_
 static int tvz_topk_impl(const int32_t *d_lists, const int32_t *d_lists_n, int32_t n_lists,
                         int32_t Q, int32_t cap, int32_t k, int32_t *d_topk, void *hip_stream) {
     TVZ_REQUIRE(n_lists >= 1 && Q >= 0 && cap >= 0, "bad list shape");
-    TVZ_REQUIRE(k >= 1 && k <= kSortCap / 2, "k=%d out of range [1, %d]", k, kSortCap / 2);
+    if (int rc = check_topk_k(k)) return rc;
     if (Q == 0) return TVZ_OK;
     TVZ_REQUIRE((d_lists || cap == 0) && d_topk, "NULL argument");
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    if (n_lists == 1) return launch_topk_local(d_lists, d_lists_n, 1, Q, cap, k, d_topk, 0, nullptr, st);
-    return launch_topk_lists(d_lists, d_lists_n, n_lists, Q, cap, k, d_topk, 0, nullptr, st);
+    if (n_lists == 1) return launch_topk_local(d_lists, d_lists_n, 1, Q, cap, k, d_topk, kTopkPlain, nullptr, st);
+    return launch_topk_lists(d_lists, d_lists_n, n_lists, Q, cap, k, d_topk, kTopkPlain, nullptr, st);
 }
 
 static int tvz_topk_shard_impl(const int32_t *d_hits, const int32_t *d_hits_n, int32_t Q,
                               int32_t cap, int32_t k, int32_t *d_out, void *hip_stream) {
     TVZ_REQUIRE(Q >= 0 && cap >= 0, "bad list shape");
-    TVZ_REQUIRE(k >= 1 && k <= kSortCap / 2, "k=%d out of range [1, %d]", k, kSortCap / 2);
+    if (int rc = check_topk_k(k)) return rc;
     if (Q == 0) return TVZ_OK;
     TVZ_REQUIRE((d_hits || cap == 0) && d_hits_n && d_out, "NULL argument");
-    return launch_topk_local(d_hits, d_hits_n, 1, Q, cap, k, d_out, 1, nullptr, reinterpret_cast<hipStream_t>(hip_stream));
+    return launch_topk_local(d_hits, d_hits_n, 1, Q, cap, k, d_out, kTopkShard, nullptr, reinterpret_cast<hipStream_t>(hip_stream));
 }
 
 static int tvz_topk_merge_impl(const int32_t *d_gathered, int32_t n_ranks, int32_t Q, int32_t k,
                               int32_t *d_topk, int32_t *d_totals, void *hip_stream) {
     TVZ_REQUIRE(n_ranks >= 1 && Q >= 0, "bad list shape");
-    TVZ_REQUIRE(k >= 1 && k <= kSortCap / 2, "k=%d out of range [1, %d]", k, kSortCap / 2);
+    if (int rc = check_topk_k(k)) return rc;
     if (Q == 0) return TVZ_OK;
     TVZ_REQUIRE(d_gathered && d_topk, "NULL argument");
-    return launch_topk_lists(d_gathered, nullptr, n_ranks, Q, k + 1, k, d_topk, 2, d_totals,
+    return launch_topk_lists(d_gathered, nullptr, n_ranks, Q, k + 1, k, d_topk, kTopkMerge, d_totals,
                              reinterpret_cast<hipStream_t>(hip_stream));
 }
 
