@@ -420,6 +420,41 @@ int tvz_align_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q_of
                    int32_t min_score, const int32_t *d_exclude_ids, int32_t k, int32_t *d_out,
                    void *d_workspace, size_t workspace_bytes, void *hip_stream);
 
+/* The alignment top-k AT ANY SHIFT: tvz_align_topk over up to 2^22 offset bins on either side of zero, for the copy
+ * whose cut pattern moved by minutes or hours (an intro cut off, an excerpt, a compilation).  (TVZ_VERSION unchanged:
+ * new exports only.)  The contract is tvz_align_topk's, word for word, with three changes:
+ *   bins  : B = floor(max_offset/eps + 0.5) may be anything in 0..TVZ_ALIGN_WIDE_MAX_B; more, max_offset = +inf or a
+ *           NaN quotient: TVZ_ERR_UNSUPPORTED (eps <= 0, max_offset < 0 or a NaN in either: TVZ_ERR_INVALID, as
+ *           before).  The vote is the same floor((c - x)/eps + 0.5) in [-B, B] (ONE IEEE subtraction, ONE true
+ *           division); the best bin - most votes, then smaller |bin|, then the negative one - is chosen over the
+ *           WHOLE range.
+ *   score : flags & TVZ_ALIGN_CONTAIN: u = min(nv, row_len), the containment of the shorter side - a 20-cut excerpt
+ *           of a 400-cut film whose cuts all align scores 2^20, where the Jaccard u = nv + row_len - v gives 0.05.
+ *           score = (v << 20) / u stays in 0..2^20 (v <= u); flags = 0: the Jaccard.  Any other flag bit:
+ *           TVZ_ERR_INVALID.
+ *   order : ascending by the tuple (2^20 - score, video_id, best_bin as a signed number, row_len, votes); rows equal
+ *           in all five are identical rows and are all kept.  For B <= 2047 that is the order of tvz_align_topk's
+ *           word, so with flags = 0 the block equals tvz_align_topk's bit for bit.
+ * d_out, n_hits, INT32_MIN for a refused query, k in 1..64, max_query_len <= 4,095, min_votes >= 1, min_score in
+ * 0..2^20, the refusals (nothing written), enqueue-only, upserts before the call seen: as tvz_align_topk.
+ * Workspace = tvz_match_tol_workspace_bytes(Q, max_query_len, max(total_query_keys, max_query_len))   (the sorted queries)
+ *           + 4 Q                                                                      (hit totals)
+ *           + max(6080, 95 Q) x k x 20                                                  (one kept list per sweep
+ *             block; a kept hit is two 64-bit words - score and video id; bin and row_len - and the 32-bit votes)
+ *           + alignment (each part to 256 B).
+ * Cost: a row's offset range [bin(c_min, x_max), bin(c_max, x_min)], clipped to [-B, B], is walked in windows of 1,024
+ * bins (B <= 2047: one window of all bins, the work of tvz_align_topk); per row key one binary search of the sorted
+ * query, then one step per window, and over all windows every (key, value) pair inside [-B, B] votes once - far more
+ * votes than the bounded search counts.  TVZ_ALIGN_WIDE_MAX_B bounds a row at 8,193 windows.  The sharded forms (tvz_align_topk_merge, _shards, _sharded) do not take these blocks: their merge
+ * rebuilds a 12-bit bin word. */
+#define TVZ_ALIGN_WIDE_MAX_B (1 << 22)   /* bins on either side of zero */
+#define TVZ_ALIGN_CONTAIN 1u             /* flags: score = v / min(nv, row_len) instead of the Jaccard */
+size_t tvz_align_wide_topk_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k);
+int tvz_align_wide_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
+                        int32_t max_query_len, double eps, double max_offset, int32_t min_votes, int32_t min_score,
+                        uint32_t flags, const int32_t *d_exclude_ids, int32_t k, int32_t *d_out,
+                        void *d_workspace, size_t workspace_bytes, void *hip_stream);
+
 /* The alignment top-k over a SHARDED table.  The block of tvz_align_topk is what travels: int32[Q][k+1][4], k rows
  * ascending in the order above, padding, then (-1, n_hits, 0, 0).  (TVZ_VERSION unchanged: new exports only.)
  *

@@ -97,6 +97,30 @@ def align_order_key(row, nv: int):
     return (-align_score(votes, nv, row_len), vid, best_bin, row_len, votes)
 
 
+def align_wide_topk_workspace_bytes(Q: int, max_query_len: int, total_query_keys: int = 0, k: int = 16) -> int:
+    """tvz_align_wide_topk_workspace_bytes: as align_topk_workspace_bytes, with 20 bytes per kept hit instead of 16."""
+    return int(_lib.load().tvz_align_wide_topk_workspace_bytes(int(Q), int(max_query_len), int(total_query_keys), int(k)))
+
+
+ALIGN_WIDE_MAX_B = 1 << 22                  # include/tvz.h TVZ_ALIGN_WIDE_MAX_B: tvz_align_wide_topk's bins per side
+ALIGN_CONTAIN = 1                           # include/tvz.h TVZ_ALIGN_CONTAIN
+
+
+def align_containment(votes: int, nv: int, row_len: int) -> int:
+    """The score tvz_align_wide_topk orders by with TVZ_ALIGN_CONTAIN: v / min(nv, row_len), v = min(votes, nv,
+    row_len), in 20-bit fixed point - 2^20 when every cut of the shorter side aligns."""
+    v = min(int(votes), int(nv), int(row_len))
+    u = min(int(nv), int(row_len))
+    return (v << 20) // u if u > 0 else 0
+
+
+def align_wide_order_key(row, nv: int, contain: bool = False):
+    """align_order_key for tvz_align_wide_topk: the same tuple, scored by either kind."""
+    vid, row_len, best_bin, votes = (int(x) for x in row)
+    score = align_containment if contain else align_score
+    return (-score(votes, nv, row_len), vid, best_bin, row_len, votes)
+
+
 class DeviceCorpus:
     """tvz_corpus handle: rows of (video_id, sorted-unique canonical float64 keys) in HBM."""
 
@@ -274,6 +298,41 @@ class DeviceCorpus:
         _lib.check(self.lib.tvz_align_topk(
             self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps), float(max_offset),
             int(min_votes), int(min_score), excl, int(k), out.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
+        return out
+
+    supports_align_wide = True
+
+    def align_wide_topk(self, queries, *, eps: float, max_offset: Optional[float] = None, k: int = 16, min_votes: int = 1,
+                        min_score: int = 0, contain: bool = False, exclude_ids=None,
+                        max_query_len: Optional[int] = None):
+        """tvz_align_wide_topk: align_topk at any shift - up to ALIGN_WIDE_MAX_B offset bins on either side of zero
+        (`max_offset=None`: ALIGN_WIDE_MAX_B x eps, the widest the library takes).  `contain=True` scores by
+        v / min(nv, row_len) (align_containment) instead of the tolerant Jaccard, for the excerpt of a longer video.
+        Arguments and (rows, totals) otherwise as align_topk; order: align_wide_order_key."""
+        dev = torch.device("cuda", self.device)
+        d_q, d_off, Q, max_query_len, d_ex = align_inputs(queries, exclude_ids, max_query_len, dev)
+        ws = thread_workspace(self._tls, align_wide_topk_workspace_bytes(Q, max_query_len, d_q.numel(), k), dev)
+        h = self.align_wide_topk_block(d_q, d_off, max_query_len, eps=eps, max_offset=max_offset, k=k,
+                                       min_votes=min_votes, min_score=min_score, contain=contain, d_exclude_ids=d_ex,
+                                       workspace=ws).cpu().numpy()
+        return np.ascontiguousarray(h[:, :k]), np.ascontiguousarray(h[:, k, 1])
+
+    def align_wide_topk_block(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, eps: float,
+                              max_offset: Optional[float] = None, k: int, min_votes: int = 1, min_score: int = 0,
+                              contain: bool = False, d_exclude_ids: Optional[torch.Tensor] = None,
+                              out: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
+                              workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """tvz_align_wide_topk, device in / device out: enqueue Q queries -> the block int32 [Q, k+1, 4]."""
+        Q = d_q_offsets.numel() - 1
+        dev, s, ws, excl = self._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace,
+                                         align_wide_topk_workspace_bytes(Q, max_query_len, d_queries.numel(), k))
+        out = _out(out, (Q, k + 1, 4), dev)
+        if max_offset is None:
+            max_offset = ALIGN_WIDE_MAX_B * float(eps)
+        _lib.check(self.lib.tvz_align_wide_topk(
+            self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps), float(max_offset),
+            int(min_votes), int(min_score), ALIGN_CONTAIN if contain else 0, excl, int(k), out.data_ptr(), ws.data_ptr(),
+            ws.numel(), s.cuda_stream))
         return out
 
     # ---- batched, device resident ----

@@ -27,6 +27,7 @@
 #include "tvz_tol_kernels.h"
 #include "tvz_tol_index_kernels.h"
 #include "tvz_align_kernels.h"
+#include "tvz_align_wide_kernels.h"
 #include "tvz_handle.h"
 #include "tvz_index_build.h"
 
@@ -2138,6 +2139,102 @@ static int tvz_align_topk_shards_impl(tvz_corpus *const *shards, int32_t n_shard
     return tvz_align_topk_merge_impl(d_blocks, n_shards, Q, k, d_queries, d_q_offsets, d_topk, d_totals, hip_stream);
 }
 
+// ---- alignment top-k at any shift (tvz_align_wide_kernels.h) ---------------------------------------------------
+namespace {
+
+// eps and max_offset of tvz_align_wide_topk: check_align_bins with the wide limit, kAwMaxB bins on either side
+int check_align_wide_bins(double eps, double max_offset, int32_t *nb_out) {
+    TVZ_REQUIRE(eps > 0.0 && max_offset >= 0.0, "eps must be > 0 and max_offset >= 0");
+    const double nb = floor(max_offset / eps + 0.5);
+    if (!(nb <= (double)kAwMaxB))                       // also refuses max_offset = inf and NaN (eps = max_offset = inf)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "max_offset/eps = %.0f bins on either side of zero, above TVZ_ALIGN_WIDE_MAX_B = %d",
+                         nb, kAwMaxB);
+    *nb_out = (int32_t)nb;
+    return TVZ_OK;
+}
+
+// Workspace of tvz_align_wide_topk, in front of the sorted queries: AlignTopkWs's totals and lists, with a third
+// array for the entries' raw votes (a kept hit is two 64-bit words and one 32-bit one)
+struct AlignWideWs {
+    int32_t *totals = nullptr;             // [Q]
+    unsigned long long *part_w = nullptr;  // [Q][blocks][k]
+    unsigned long long *part_p = nullptr;  // [Q][blocks][k]
+    uint32_t *part_v = nullptr;            // [Q][blocks][k]
+};
+
+AlignWideWs align_wide_ws_layout(Carver &cv, int32_t Q, int32_t k) {
+    AlignWideWs w;
+    const size_t lists = (size_t)tol_topk_max_lists(Q) * (size_t)k;
+    w.totals = cv.take<int32_t>((size_t)Q);
+    w.part_w = cv.take<unsigned long long>(lists);
+    w.part_p = cv.take<unsigned long long>(lists);
+    w.part_v = cv.take<uint32_t>(lists);
+    return w;
+}
+
+size_t align_wide_ws_bytes(int32_t Q, int64_t keys, int32_t k) {
+    Carver cv(nullptr);
+    align_wide_ws_layout(cv, Q, k);
+    return cv.fixed() + tol_ws_bytes(Q, keys);
+}
+
+// sort -> windowed sweep that keeps the k best -> per-query selection
+int tvz_align_wide_topk_local(tvz_corpus *c, const Batch &b, const AlignCall &a, uint32_t flags, int32_t k, int32_t *d_out,
+                              Workspace ws, void *hip_stream) {
+    const int32_t Q = b.Q, max_query_len = b.max_query_len;
+    if (int rc = check_batch_args(c, b, 0)) return rc;
+    int32_t B = 0;
+    if (int rc = check_align_wide_bins(a.eps, a.max_offset, &B)) return rc;
+    TVZ_REQUIRE((flags & ~kAwContain) == 0u, "wide alignment top-k: unknown flag bits 0x%x", (unsigned)(flags & ~kAwContain));
+    TVZ_REQUIRE(a.min_votes >= 1, "wide alignment top-k: min_votes %d below 1", (int)a.min_votes);
+    TVZ_REQUIRE(a.min_score >= 0 && a.min_score <= kAlScoreOne, "wide alignment top-k: min_score %d outside 0..%d",
+                (int)a.min_score, kAlScoreOne);
+    if (k < 1 || k > kAlMaxK)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "wide alignment top-k: k=%d outside 1..%d", (int)k, kAlMaxK);
+    if (max_query_len > kAlMaxLen)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "wide alignment top-k: max_query_len %d above %d", (int)max_query_len, kAlMaxLen);
+    if (Q == 0) return TVZ_OK;
+    Carver cv(ws.p);
+    const AlignWideWs w = align_wide_ws_layout(cv, Q, k);
+    const int32_t lds_keys = std::max(max_query_len, 1);
+    const int32_t width = aw_width(B);
+    const size_t lds = aw_lds_bytes(lds_keys, B, width);
+    auto args_ok = [&]() -> int {
+        TVZ_REQUIRE(d_out != nullptr, "d_out is NULL");
+        TVZ_REQUIRE(lds + kAwStaticLds <= (size_t)kLdsPerWorkgroup,
+                    "wide alignment top-k sweep: %zu B of dynamic + %d B of static LDS exceed a gfx950 workgroup's", lds, kAwStaticLds);
+        return TVZ_OK;
+    };
+    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+    TolCall t;
+    if (int rc = tol_prelude(c, b, TolFront{cv, cv.fixed(), w.totals, "wide alignment top-k", "tvz_align_wide_topk_workspace_bytes"},
+                             ws.p ? ws.bytes : 0, max_query_len, st, args_ok, t))
+        return rc;
+    const int64_t n_rows = t.n_rows;
+    const int n_blocks = n_rows ? (int)std::min<int64_t>(tvz::ceil_div(n_rows, (int64_t)kAlWaves), tol_topk_max_blocks(Q)) : 0;
+    if (n_blocks) {
+        hipLaunchKernelGGL(ts_alignw_sweep_kernel, dim3((unsigned)n_blocks, (unsigned)Q), dim3(kAlBlock), lds, st, c->rows.p,
+                           n_rows, c->keys.p, t.ws.sv, b.d_q_offsets, t.ws.qm, lds_keys, a.eps, B, width, a.min_votes,
+                           a.min_score, flags, b.d_exclude_ids, k, w.part_w, w.part_p, w.part_v, n_blocks, w.totals);
+        TVZ_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(ts_alignw_reduce_kernel, dim3((unsigned)Q), dim3(kAlReduceBlock), 0, st, w.part_w, w.part_p, w.part_v,
+                       n_blocks, k, t.ws.qm, lds_keys, w.totals, d_out);
+    TVZ_HIP(hipGetLastError());
+    return record(c, st);
+}
+
+}  // namespace
+
+static int tvz_align_wide_topk_impl(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
+                                    int32_t max_query_len, double eps, double max_offset, int32_t min_votes,
+                                    int32_t min_score, uint32_t flags, const int32_t *d_exclude_ids, int32_t k,
+                                    int32_t *d_out, void *d_workspace, size_t workspace_bytes, void *hip_stream) {
+    return tvz_align_wide_topk_local(c, Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids},
+                                     AlignCall{eps, max_offset, min_votes, min_score}, flags, k, d_out,
+                                     Workspace{d_workspace, workspace_bytes}, hip_stream);
+}
+
 #ifdef TVZ_IX_STAMP
 // diagnostic build only: read (and clear) the per-phase cycle totals of ts_match_index_kernel
 TVZ_EXPORT int tvz_debug_ix_stamps(unsigned long long *out16) {
@@ -2302,6 +2399,20 @@ TVZ_EXPORT int tvz_align_topk(tvz_corpus *c, const double *d_queries, const int6
                               void *d_workspace, size_t workspace_bytes, void *hip_stream) {
     TVZ_GUARDED(tvz_align_topk_impl(c, d_queries, d_q_offsets, Q, max_query_len, eps, max_offset, min_votes, min_score,
                                     d_exclude_ids, k, d_out, d_workspace, workspace_bytes, hip_stream));
+}
+
+TVZ_EXPORT size_t tvz_align_wide_topk_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k) {
+    if (Q < 0 || max_query_len < 0 || total_query_keys < 0 || k < 1) return 0;
+    const int64_t keys = total_query_keys > 0 ? total_query_keys : (int64_t)Q * max_query_len;
+    return align_wide_ws_bytes(Q, std::max<int64_t>(keys, max_query_len), k);
+}
+
+TVZ_EXPORT int tvz_align_wide_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
+                                   int32_t max_query_len, double eps, double max_offset, int32_t min_votes,
+                                   int32_t min_score, uint32_t flags, const int32_t *d_exclude_ids, int32_t k,
+                                   int32_t *d_out, void *d_workspace, size_t workspace_bytes, void *hip_stream) {
+    TVZ_GUARDED(tvz_align_wide_topk_impl(c, d_queries, d_q_offsets, Q, max_query_len, eps, max_offset, min_votes, min_score,
+                                         flags, d_exclude_ids, k, d_out, d_workspace, workspace_bytes, hip_stream));
 }
 
 TVZ_EXPORT int tvz_align_topk_merge(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t k,

@@ -83,7 +83,8 @@ class Inspector:
                  pts_policy: str = scene.PTS_POLICY_G6, batch: int = 256, max_workers: int = 16,
                  near_duplicates: bool = False, near_eps: float = 1.0 / 30, near_max_offset: float = 30.0,
                  near_jaccard: float = 0.8, slot_bytes: int = 64 << 20, n_slots: Optional[int] = None,
-                 profile: bool = False, match_tolerance: float = 0.0, near_top_k: Optional[int] = None):
+                 profile: bool = False, match_tolerance: float = 0.0, near_top_k: Optional[int] = None,
+                 near_any_offset: bool = False, near_score: str = "jaccard", near_min_votes: int = 1):
         self.store = store
         # opt-in: the near-duplicate report from the K best-aligned rows the device keeps (tvz_align_topk) instead of
         # one row per corpus row walked here.  None: the walk, exactly as before.  Refused here where the store's
@@ -96,6 +97,26 @@ class Inspector:
                 raise RuntimeError(f"near_top_k={self.near_top_k}: the store's corpus "
                                    f"({type(getattr(store, 'corpus', None)).__name__}) has no align_topk; "
                                    "use a DeviceCorpus, a service.ShardedCorpus or a service.RankCorpus")
+        # opt-in: the near-duplicate search at ANY shift (tvz_align_wide_topk, 2^22 bins of near_eps on either side
+        # instead of near_max_offset) - the copy with its intro cut off, the excerpt, the compilation - and, with
+        # near_score="containment", scored by v / min(n, row_len) so that the excerpt of a long video is not thrown
+        # away by its Jaccard; near_min_votes keeps a row of one or two cuts from counting as contained by chance.
+        # Defaults: the bounded search and the Jaccard, exactly as before.
+        self.near_any_offset = bool(near_any_offset)
+        self.near_score, self.near_min_votes = near_score, int(near_min_votes)
+        if near_score not in ("jaccard", "containment"):
+            raise ValueError(f"near_score must be 'jaccard' or 'containment', got {near_score!r}")
+        if self.near_min_votes < 1:
+            raise ValueError(f"near_min_votes must be >= 1, got {near_min_votes!r}")
+        if near_score == "containment" and not self.near_any_offset:
+            raise ValueError("near_score='containment' needs near_any_offset=True (the score of tvz_align_wide_topk)")
+        if self.near_any_offset:
+            if not near_duplicates or self.near_top_k is None:
+                raise ValueError("near_any_offset=True needs near_duplicates=True and near_top_k")
+            if not hasattr(getattr(store, "corpus", None), "align_wide_topk"):
+                raise RuntimeError(f"near_any_offset=True: the store's corpus "
+                                   f"({type(getattr(store, 'corpus', None)).__name__}) has no align_wide_topk; "
+                                   "use a DeviceCorpus (the sharded forms keep the bounded search)")
         # opt-in, never the default: duplicates by the TOLERANT count (include/tvz.h tvz_find_duplicates_tol)
         # instead of the reference's exact float64 equality; the verdict, the truncation at kth and the stored
         # duplicates all follow it.  Refused here, before any upload, where the store's corpus cannot do it.
@@ -344,12 +365,19 @@ class Inspector:
                 continue
             # votes counts (query, row) pairs: cuts closer than eps can give more than either list holds
             v = min(int(votes), len(scene_timestamps), int(row_len))
+            if v < self.near_min_votes and self.near_min_votes > 1:
+                continue
             jacc = v / float(len(scene_timestamps) + row_len - v)
-            if jacc >= self.near_jaccard:
+            contain = self.near_score == "containment"
+            score = v / float(min(len(scene_timestamps), row_len)) if contain else jacc
+            if score >= self.near_jaccard:
                 v = self.store.get_video_by_id(int(vid))
                 out.append({"filename": v.filename if v else None, "video_id": int(vid),
                             "shift_seconds": float(best_bin) * self.near_eps, "jaccard": round(jacc, 4)})
-        return sorted(out, key=lambda d: (-d["jaccard"], d["video_id"]))
+                if contain:
+                    out[-1]["containment"] = round(score, 4)
+        by = "containment" if self.near_score == "containment" else "jaccard"
+        return sorted(out, key=lambda d: (-d[by], d["video_id"]))
 
     def _near_rows(self, video_id: int, scene_timestamps):
         """(video_id, row_len, best_bin, votes[, ...]) of the rows _near filters: every row of the table (near_top_k None), or
@@ -359,8 +387,15 @@ class Inspector:
         if self.near_top_k is not None:
             one = 1 << 20
             min_score = max(0, min(one, int(self.near_jaccard * one)))          # int() floors: the value is >= 0
-            rows, totals = corpus.align_topk([scene_timestamps], eps=self.near_eps, max_offset=self.near_max_offset,
-                                             k=self.near_top_k, min_score=min_score, exclude_ids=[int(video_id)])
+            if self.near_any_offset:
+                rows, totals = corpus.align_wide_topk([scene_timestamps], eps=self.near_eps, max_offset=None,
+                                                      k=self.near_top_k, min_votes=self.near_min_votes,
+                                                      min_score=min_score, contain=self.near_score == "containment",
+                                                      exclude_ids=[int(video_id)])
+            else:
+                kw = {"min_votes": self.near_min_votes} if self.near_min_votes > 1 else {}
+                rows, totals = corpus.align_topk([scene_timestamps], eps=self.near_eps, max_offset=self.near_max_offset,
+                                                 k=self.near_top_k, min_score=min_score, exclude_ids=[int(video_id)], **kw)
             if int(totals[0]) >= 0:                                            # (refused: more than 4,095 cuts -> the walk)
                 return [r for r in rows[0] if r[0] >= 0]
             if not hasattr(corpus, "align"):                                   # (a rank corpus has no walk: no report)
