@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define TVZ_VERSION 403 /* 0.4.3 (unchanged by tvz_corpus_tol_index / tvz_corpus_tol_index_stats: new exports only, nothing existing changes): tvz_match_tol_topk / tvz_match_tol_sharded, the tolerant sweep keeps the per-shard top-k itself (0.4.2: tvz_find_duplicates_tol / tvz_match_tol, the opt-in tolerant match (0.4.1: tvz_align takes its output capacity and reports the row count (0.4.0: the index answers every min_match >= 1; tvz_match_topk keeps the top-k inside the lookup; tvz_match_topk_shards))) */
+#define TVZ_VERSION 404 /* 0.4.4: tvz_corpus_index_layout, a read-only query of what the index build made (0.4.3 (unchanged by tvz_corpus_tol_index / tvz_corpus_tol_index_stats: new exports only, nothing existing changes): tvz_match_tol_topk / tvz_match_tol_sharded, the tolerant sweep keeps the per-shard top-k itself (0.4.2: tvz_find_duplicates_tol / tvz_match_tol, the opt-in tolerant match (0.4.1: tvz_align takes its output capacity and reports the row count (0.4.0: the index answers every min_match >= 1; tvz_match_topk keeps the top-k inside the lookup; tvz_match_topk_shards)))) */
 
 typedef enum tvz_status {
     TVZ_OK = 0,
@@ -190,6 +190,13 @@ int tvz_corpus_index_stats(tvz_corpus *c, int64_t *n_indexed_rows, int64_t *n_de
  * the farthest of them walked (buckets), out[3] = keys whose posting list lives in the external area,
  * out[4] = external postings (uint16 units, whole lines), out[5] = sub-indexes. */
 int tvz_corpus_bucket_stats(tvz_corpus *c, int64_t out[6]);
+/* What the last build made of the open-addressing directory of the current generation (read-only; nothing sets it):
+ * out[0] = bytes per directory entry (16 + 2 per sub-index, sub-indexes rounded up to 8), out[1] = log2 of the
+ * entries, out[2] = log2 of the entries per slice, out[3] = 1 if the directory was built slice by slice (the
+ * partitioned build), 0 if by the count and fill over the whole directory; out[4..7] = the same for the cell
+ * directory of tvz_corpus_tol_index (0 while the generation carries none).  All 0 while there is no index and for a
+ * handle of one sub-index, whose key directory is the bucket table above. */
+int tvz_corpus_index_layout(tvz_corpus *c, int64_t out[8]);
 
 /* ------------------------------------------------------------------------
  * Corpus match   — replaces db.find_duplicates (inspector/db.py:76-94) and

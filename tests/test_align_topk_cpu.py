@@ -132,7 +132,7 @@ def test_declared_exported_and_bound():
     assert src.index("tvz_align_topk(") > src.index("tvz_align(")
     from tvidz_amd import _lib, corpus as tc
     lib = _lib.load()
-    assert _lib.VERSION == 403 and lib.tvz_version() == 403
+    assert _lib.VERSION == 404 and lib.tvz_version() == 404
     for name, n_args in (("tvz_align_topk_workspace_bytes", 4), ("tvz_align_topk", 15)):
         assert hasattr(lib, name) and len(_lib.SIGNATURES[name][1]) == n_args
     # the formula of the header: sorted queries + totals + max(6080, 95 Q) lists of k words and k payloads

@@ -275,7 +275,7 @@ def test_the_binding_knows_the_new_exports():
     for name in ("tvz_align_topk_merge", "tvz_align_topk_shards", "tvz_align_topk_sharded_workspace_bytes",
                  "tvz_align_topk_sharded"):
         assert name in _lib.SIGNATURES and f" {name}(" in text and hasattr(_lib.load(), name)
-    assert _lib.VERSION == 403 and _lib.load().tvz_version() == 403
+    assert _lib.VERSION == 404 and _lib.load().tvz_version() == 404
 
 
 # ---- the launcher ---------------------------------------------------------------------------------------------------

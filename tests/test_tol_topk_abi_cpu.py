@@ -13,7 +13,7 @@ SLACK = 8 * 256                            # alignment: a handful of 256-byte ro
 
 def test_the_entry_points_are_bound():
     lib = _lib.load()
-    assert _lib.VERSION == 403 and lib.tvz_version() == 403
+    assert _lib.VERSION == 404 and lib.tvz_version() == 404
     for name in ("tvz_match_tol_topk_workspace_bytes", "tvz_match_tol_topk", "tvz_match_tol_sharded"):
         assert name in _lib.SIGNATURES and hasattr(lib, name)
 

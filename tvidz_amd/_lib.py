@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("TVZ_LIB") or os.path.join(_HERE, "libtvz.so")
 
 KTH_NEVER = 0x7FFFFFFF
-VERSION = 403
+VERSION = 404
 
 # name -> (restype, argtypes); mirrors include/tvz.h one to one
 _P = C.c_void_p
@@ -45,6 +45,7 @@ SIGNATURES = {
     "tvz_corpus_build_index": (C.c_int, [_P]),
     "tvz_corpus_index_stats": (C.c_int, [_P] + [C.POINTER(C.c_int64)] * 5),
     "tvz_corpus_bucket_stats": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "tvz_corpus_index_layout": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "tvz_corpus_tol_index": (C.c_int, [_P, C.c_double]),
     "tvz_corpus_tol_index_stats": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "tvz_corpus_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64),

@@ -192,6 +192,15 @@ class DeviceCorpus:
         return dict(zip(("buckets", "keys_walked_on", "max_walk", "external_lists", "external_postings", "sub_indexes"),
                         (int(x) for x in v)))
 
+    def index_layout(self) -> dict:
+        """What the last build made of the open-addressing directory (tvz_corpus_index_layout): entry_bytes / log2 /
+        slice_log2 / partitioned (1: built slice by slice, 0: count and fill over the whole directory), and the same
+        with a cell_ prefix for the cell directory; zeros where there is none, and for a bucket directory."""
+        v = (C.c_int64 * 8)()
+        _lib.check(self.lib.tvz_corpus_index_layout(self._h, v))
+        names = ("entry_bytes", "log2", "slice_log2", "partitioned")
+        return dict(zip(names + tuple("cell_" + n for n in names), (int(x) for x in v)))
+
     def set_tol_index(self, cell: float) -> None:
         """tvz_corpus_tol_index: cell > 0 makes every index generation of this handle also carry cell postings of `cell`
         seconds (and builds them now if the handle has an index), which the batched tolerant calls then use for

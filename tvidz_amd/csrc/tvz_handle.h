@@ -121,6 +121,8 @@ struct Directory {
     int log2 = 0;
     int slice_log2 = 0;               // entries per directory slice (probing wraps inside a slice)
     int ks = 0;                       // uint16 counts per directory entry
+    bool partitioned = false;         // built slice by slice (build_classic); a one-slice partitioned build has
+                                      // slice_log2 == log2 too, so the sizes alone do not tell
     // A handle of ONE sub-index keeps the BUCKET directory of tvz_bucket_dir.h: nb buckets of 128 bytes - a key's
     // entry and its postings in one line - + the external lists behind them, all in `dir`; `post` is unused.
     // 0 = the classic format (the cell directory always).

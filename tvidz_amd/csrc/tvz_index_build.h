@@ -162,6 +162,7 @@ int build_bucket_dir(tvz_corpus *c, IndexBuf &b, const Row *d_rows, int64_t n_ro
             d.ks = 0;
             d.log2 = 0;
             d.slice_log2 = 0;
+            d.partitioned = false;
             return TVZ_OK;
         }
         if (nb >= (uint32_t)kIxMaxParts * kBkSlice) break;            // too many keys for slices of 256 buckets: classic format
@@ -213,7 +214,7 @@ int build_classic(tvz_corpus *c, IndexBuf &b, Directory &d, const DirHint &hint,
     // with lookups, whose few blocks get a CU as soon as any of these retires
     const int64_t blocks = tvz::ceil_div(n_rows, kBlock / 64);
     int slice_log2 = 0;
-    bool shrunk = false;
+    bool shrunk = false, partitioned = false;
     while (true) {
         TVZ_REQUIRE(log2 <= 30, "index directory would exceed 2^30 entries");
         const int64_t dn = (int64_t)1 << log2;
@@ -226,8 +227,8 @@ int build_classic(tvz_corpus *c, IndexBuf &b, Directory &d, const DirHint &hint,
         while (((int64_t)2 << slice_log2) * es <= kIxSliceBytes && slice_log2 < log2) ++slice_log2;
         while ((dn >> slice_log2) > kIxMaxParts && ((int64_t)2 << slice_log2) * es <= kIxSliceBytesMax) ++slice_log2;
         const int64_t n_parts = dn >> slice_log2;
-        const bool partitioned = n_parts <= kIxMaxParts && post_cap < (int64_t)0xfffffff0LL &&   // (32-bit posting offsets)
-                                 ((int64_t)es << slice_log2) <= kIxSliceBytesMax;   // (entries of > 2 KB: > 16 M rows)
+        partitioned = n_parts <= kIxMaxParts && post_cap < (int64_t)0xfffffff0LL &&   // (32-bit posting offsets)
+                      ((int64_t)es << slice_log2) <= kIxSliceBytesMax;              // (entries of > 2 KB: > 16 M rows)
         if (!partitioned) slice_log2 = log2;
         const int bits = ix_dir_bits(log2, slice_log2);
         if (partitioned) {
@@ -272,6 +273,7 @@ int build_classic(tvz_corpus *c, IndexBuf &b, Directory &d, const DirHint &hint,
     d.ks = ks;
     d.log2 = log2;
     d.slice_log2 = slice_log2;
+    d.partitioned = partitioned;
     return TVZ_OK;
 }
 

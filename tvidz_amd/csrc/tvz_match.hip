@@ -2300,6 +2300,28 @@ TVZ_EXPORT int tvz_corpus_bucket_stats(tvz_corpus *c, int64_t out[6]) {
     TVZ_GUARDED(tvz_corpus_bucket_stats_impl(c, out));
 }
 
+static int tvz_corpus_index_layout_impl(tvz_corpus *c, int64_t *out) {
+    TVZ_REQUIRE(c != nullptr && out != nullptr, "NULL argument");
+    std::shared_lock<std::shared_mutex> lk(c->mu);
+    const Index &ix = c->ix;
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    if (!ix.valid || ix.now().keys.nb) return TVZ_OK;
+    const IndexBuf &b = ix.now();
+    const Directory *dirs[2] = {&b.keys, b.t_cell > 0.0 ? &b.cells : nullptr};
+    for (int i = 0; i < 2; ++i) {
+        if (!dirs[i]) continue;
+        out[4 * i + 0] = ix_entry_bytes(dirs[i]->ks);
+        out[4 * i + 1] = dirs[i]->log2;
+        out[4 * i + 2] = dirs[i]->slice_log2;
+        out[4 * i + 3] = dirs[i]->partitioned ? 1 : 0;
+    }
+    return TVZ_OK;
+}
+
+TVZ_EXPORT int tvz_corpus_index_layout(tvz_corpus *c, int64_t out[8]) {
+    TVZ_GUARDED(tvz_corpus_index_layout_impl(c, out));
+}
+
 TVZ_EXPORT int tvz_corpus_index_stats(tvz_corpus *c, int64_t *n_indexed_rows, int64_t *n_delta_rows,
                                       int64_t *n_postings, int64_t *n_distinct_keys, int64_t *n_builds) {
     TVZ_GUARDED(tvz_corpus_index_stats_impl(c, n_indexed_rows, n_delta_rows, n_postings, n_distinct_keys, n_builds));
