@@ -1,28 +1,46 @@
-// tvz_align_kernels.h — batched alignment score with the k best rows kept inside the sweep (tvz_align_topk),
-// gfx950 wave64.  Included by tvz_match.hip only.  From tvz_match_kernels.h: Row, load_row; from tvz_tol_kernels.h:
-// ts_tol_sort_kernel (the batch's queries sorted numerically, NaNs dropped, qm = the non-NaN count) and the
-// sweep's block count (tol_topk_max_blocks); from tvz_wave.h: wave_lds_fence.
+// tvz_align_kernels.h — batched alignment score with the k best rows kept inside the sweep, gfx950 wave64: the bounded
+// call (tvz_align_topk, at most kAlignMaxBins bins), the call at any shift (tvz_align_wide_topk, up to kAwMaxB bins on
+// either side of zero) and the merge of the shards' blocks.  Included by tvz_match.hip only.  From tvz_match_kernels.h:
+// Row, load_row; from tvz_tol_kernels.h: ts_tol_sort_kernel (the batch's queries sorted numerically, NaNs dropped, qm =
+// the non-NaN count) and the sweep's block count (tol_topk_max_blocks); from tvz_wave.h: wave_lds_fence.
 //
 // Contract (include/tvz.h): votes and bins are tvz_align's - the pair (row key c, query value x) votes into
 //   d = floor((c - x) / eps + 0.5)      (one IEEE subtraction, one true division)
-// when -B <= d <= B - and a row's hit is ordered by the word (2^20 - score) << 43 | video_id << 12 | bin + 2048,
-// then by (row_len, votes).
+// when -B <= d <= B; the score is the tolerant Jaccard or, for the wide call with TVZ_ALIGN_CONTAIN, v / min(nv,
+// row_len); a row's hit is ordered by the tuple (score descending, video_id, best_bin, row_len, votes).  The two calls
+// pack that tuple differently (AlHit, AwHit below) and share everything else.
 //
-// The window: for a fixed key c each of c - x, / eps, + 0.5 and floor never increases as x grows, so the query
-// values that vote are ONE contiguous run of the sorted query.  Its start is found by a binary search with the
-// vote's own expression (al_left below; never a rewrite such as x >= c - max_offset, which rounds differently);
-// from there the run is walked, voting, until the expression itself says the run has ended.  A NaN (inf - inf, or
-// inf / inf with an infinite eps) is outside the window on the side its x lies on.
+// A key's run: for a fixed key c each of c - x, / eps, + 0.5 and floor never increases as x grows, so the query
+// values that vote into a range of bins are ONE contiguous run of the sorted query.  Its start is found by a binary
+// search with the vote's own expression (al_left below; never a rewrite such as x >= c - max_offset, which rounds
+// differently); from there the run is walked, voting, until the expression itself says the run has ended.  A NaN
+// (inf - inf, or inf / inf with an infinite eps) is outside the range on the side its x lies on.
 //
-// ts_align_topk_kernel         grid = (row blocks, Q): a wave per row.  Per wave a histogram sized by the call's
-//                              bin count, and a list of the bins it has touched.  A vote is a returning LDS add;
-//                              every lane keeps the largest (count << 14 | 16383 - order) it has seen - the lane
-//                              that makes a bin's last increment sees its final count, so the wave's maximum is
-//                              the best bin under the tie rule with no scan of the histogram - and the lane that
-//                              finds a bin at zero notes it, so clearing costs the bins touched, not 2B + 1.
-//                              The wave's k best hits live in registers, one (word, payload) per lane, ascending:
-//                              a hit below the k-th is inserted by one ballot and one lane shift.
-// ts_align_topk_reduce_kernel  one block per query: the k smallest of the blocks' lists -> d_out[q].
+// The sweep (al_sweep), grid = (row blocks, Q): a wave per row.  Per wave a histogram of `width` bins and a list of the
+// bins it has touched.  A vote is a returning LDS add; every lane keeps the largest
+//   count << 33 | (2^33 - 1 - order),   order = 2 |bin| + (bin > 0)
+// it has seen - the lane that makes a bin's last increment sees its final count, so the wave's maximum is the best bin
+// under the tie rule with no scan of the histogram - and the lane that finds a bin at zero notes it, so clearing costs
+// the bins touched, not 2B + 1.  The wave's k best hits live in registers, one hit per lane, ascending: a hit below the
+// k-th is inserted by one ballot and one lane shift (al_insert).  The selection (al_reduce), one block per query: the k
+// smallest of the blocks' lists -> d_out[q].
+//
+// The window walk (al_sweep<.., true>, the wide call): the histogram holds aw_width(B) bins - all 2B + 1 of them while
+// they fit kAwOneWindow, so a call with B <= 2047 is ONE window and does the bounded sweep's work; kAwWidth beyond.
+// Window w of the global grid covers the bins [w * width - B, w * width - B + width - 1], clipped to B.  A row's pairs
+// can only vote inside [bin(c_min, x_max), bin(c_max, x_min)] - every step of the vote's expression is monotone in c
+// and in x - so only the windows that meet that range (clipped to [-B, B]) are visited, from the highest down.  Per
+// window every key's run is found by al_lo with the WINDOW's upper bin as the bound, and walked until the expression
+// falls below the window's lower bin: all votes of one bin fall into one window, so the lane that makes a bin's last
+// increment sees its final count there, and the lane-wise best, whose order is taken on the GLOBAL bin, carries the
+// tie rule across windows.  Between windows the histogram is cleared through the touched list.  The bounded sweep
+// (al_sweep<.., false>) is the one window [-B, B] with none of this compiled in.
+//
+// The resume position: a key's runs move to larger x as the windows descend, and the position where a window's walk
+// stops - the first value whose bin lies below the window - is al_lo's answer for the next window (whose upper bin is
+// this one's lower bin - 1; a walk that stops at a NaN has met a key that never votes).  So only a row's highest
+// window searches; the later ones read the position back, for the row's first kAwResume keys (a u16 per key and
+// wave in LDS, written and read by the same lane); keys beyond them search in every window.
 #pragma once
 #include "tvz_match_kernels.h"
 #include "tvz_tol_kernels.h"
@@ -35,30 +53,42 @@ constexpr int kAlWaves = kAlBlock / 64;                // rows in flight per blo
 constexpr int kAlMaxK = 64;                            // one kept hit per lane
 constexpr int kAlMaxLen = 4095;                        // v << 20 fits 32 bits; the sorted query fits LDS
 constexpr int kAlScoreOne = 1 << 20;
-constexpr int kAlStaticLds = kAlWaves * 64 * 16 + 64;  // the waves' lists at the block's end + a few words
 constexpr int kAlReduceBlock = 1024;
 constexpr int kAlReduceWaves = kAlReduceBlock / 64;
 constexpr int kAlReduceLd = 4;                         // lists a wave loads per step (their loads in flight together)
-constexpr unsigned long long kAlPad = ~0ull;           // no word is all ones: its top field is at most 2^20
+constexpr unsigned long long kAlPad = ~0ull;           // no first word is all ones: its top field is at most 2^20
+constexpr unsigned long long kAlOrderMask = (1ull << 33) - 1;
 
-// dynamic LDS of the sweep: the sorted query, then per wave a histogram (u32 per bin), the touched bins (u16 per
-// bin) and their count
+constexpr int kAwMaxB = 1 << 22;                       // TVZ_ALIGN_WIDE_MAX_B
+constexpr int kAwOneWindow = 4096;                     // a call of at most this many bins is one window: the bounded sweep's shape
+constexpr int kAwWidth = 1024;                         // bins of a window otherwise (measured against 256..4096)
+constexpr int kAwResume = 512;                         // keys of a row whose resume position is kept (a multiple of 64)
+constexpr uint32_t kAwContain = 1u;                    // TVZ_ALIGN_CONTAIN
+
+// bins of a wave's histogram (even: the touched list behind the histograms stays 4-byte aligned).  The bounded call's
+// is aw_width too: its B is at most 2047
 __host__ __device__ inline int al_bins_padded(int32_t B) { return (2 * B + 1 + 1) & ~1; }
-inline size_t al_lds_bytes(int32_t lds_keys, int32_t B) {
-    return (size_t)lds_keys * 8 + (size_t)kAlWaves * ((size_t)al_bins_padded(B) * 6 + 4);
+__host__ __device__ inline int aw_width(int32_t B) { return al_bins_padded(B) <= kAwOneWindow ? al_bins_padded(B) : kAwWidth; }
+// the most windows a row can take: ceil((2B + 1) / width)
+__host__ __device__ inline int aw_max_windows(int32_t B, int width) { return (2 * B + width) / width; }
+// dynamic LDS of the sweep: the sorted query, then per wave a histogram (u32 per bin), the touched bins (u16 per
+// bin), their count and the resume positions (u16 per key; none where the call has one window)
+__host__ __device__ inline int aw_resume_keys(int32_t B, int width) { return aw_max_windows(B, width) > 1 ? kAwResume : 0; }
+inline size_t aw_lds_bytes(int32_t lds_keys, int32_t B, int width) {
+    return (size_t)lds_keys * 8 + (size_t)kAlWaves * ((size_t)width * 6 + 4 + (size_t)aw_resume_keys(B, width) * 2);
 }
 
 // d of the contract, verbatim
 __device__ __forceinline__ double al_bin(double c, double x, double eps) { return floor((c - x) / eps + 0.5); }
 
-// is x in front of key c's window?  d > B; a NaN d counts by the side x lies on (x == c only for two equal
+// is x in front of key c's run?  d > Bd; a NaN d counts by the side x lies on (x == c only for two equal
 // infinities: -inf is the smallest query value, +inf the largest)
 __device__ __forceinline__ bool al_left(double c, double x, double eps, double Bd) {
     const double d = al_bin(c, x, eps);
     return d > Bd || (d != d && (x < c || (x == c && x < 0.0)));
 }
 
-// first t with s[t] not in front of the window: a prefix of the sorted query
+// first t with s[t] not in front of the run: a prefix of the sorted query
 __device__ __forceinline__ int al_lo(const double *s, int m, double c, double eps, double Bd) {
     int lo = 0, len = m;
     while (len > 0) {
@@ -73,56 +103,151 @@ __device__ __forceinline__ int al_lo(const double *s, int m, double c, double ep
     return lo;
 }
 
-// (word, payload) order of the kept lists
-__device__ __forceinline__ bool al_le(unsigned long long w1, unsigned long long p1, unsigned long long w2,
-                                      unsigned long long p2) {
-    return w1 < w2 || (w1 == w2 && p1 <= p2);
-}
+// ---- a kept hit, in the two layouts ------------------------------------------------------------------------------
+// Lists<N>: N hits as a structure of arrays, in static LDS; Parts / ConstParts: the same arrays in the workspace,
+// [Q][n_lists][k] each.  load / store take any of them.
 
-// One wave's list: lane i holds its i-th best hit (ascending, kAlPad behind them and from lane k on).  The wave
-// takes one more hit (wave-uniform w, p): false when it does not come before the k-th.  Equal hits are all kept.
-__device__ __forceinline__ bool al_insert(unsigned long long &kw, unsigned long long &kp, unsigned long long w,
-                                          unsigned long long p, int k, int lane) {
-    const int pos = __popcll(__ballot(al_le(kw, kp, w, p)));       // the kept hits that stay in front: a prefix
+// the bounded call's: 16 bytes, ordered as (w, p)
+struct AlHit {
+    unsigned long long w, p;       // (2^20 - score) << 43 | video_id << 12 | bin + 2048;  row_len << 32 | votes
+    template <int N> struct Lists { unsigned long long w[N], p[N]; };
+    struct Parts { unsigned long long *w, *p; };
+    struct ConstParts { const unsigned long long *w, *p; };
+    static __device__ __forceinline__ AlHit make(uint32_t score, int32_t vid, int bin, uint32_t row_len, uint32_t votes) {
+        return {((unsigned long long)(kAlScoreOne - score) << 43) | ((unsigned long long)((uint32_t)vid & 0x7fffffffu) << 12) |
+                    (unsigned long long)(uint32_t)(bin + 2048),
+                ((unsigned long long)row_len << 32) | votes};
+    }
+    static __device__ __forceinline__ AlHit pad() { return {kAlPad, kAlPad}; }
+    __device__ __forceinline__ bool is_pad() const { return w == kAlPad; }
+    static __device__ __forceinline__ bool le(const AlHit &a, const AlHit &b) { return a.w < b.w || (a.w == b.w && a.p <= b.p); }
+    __device__ __forceinline__ int4 row() const {      // (video_id, row_len, best_bin, votes)
+        const bool pad = is_pad();
+        return make_int4(pad ? -1 : (int32_t)((w >> 12) & 0x7fffffffu), pad ? 0 : (int32_t)(p >> 32),
+                         pad ? 0 : (int32_t)(w & 0xfffu) - 2048, pad ? 0 : (int32_t)(p & 0xffffffffu));
+    }
+    static __device__ __forceinline__ AlHit select(bool c, const AlHit &a, const AlHit &b) { return {c ? a.w : b.w, c ? a.p : b.p}; }
+    __device__ __forceinline__ AlHit lane(int src) const { return {__shfl(w, src), __shfl(p, src)}; }
+    __device__ __forceinline__ AlHit shift_up() const { return {__shfl_up(w, 1), __shfl_up(p, 1)}; }
+    template <class L> static __device__ __forceinline__ AlHit load(const L &l, int64_t i) { return {l.w[i], l.p[i]}; }
+    template <class L> __device__ __forceinline__ void store(L &l, int64_t i) const {
+        l.w[i] = w;
+        l.p[i] = p;
+    }
+};
+
+// the wide call's: 20 bytes, ordered as (w, p, v)
+struct AwHit {
+    unsigned long long w, p;       // (2^20 - score) << 31 | video_id;  (bin + 2^22) << 32 | row_len
+    uint32_t v;                    // the raw votes
+    template <int N> struct Lists { unsigned long long w[N], p[N]; uint32_t v[N]; };
+    struct Parts { unsigned long long *w, *p; uint32_t *v; };
+    struct ConstParts { const unsigned long long *w, *p; const uint32_t *v; };
+    static __device__ __forceinline__ AwHit make(uint32_t score, int32_t vid, int bin, uint32_t row_len, uint32_t votes) {
+        return {((unsigned long long)(kAlScoreOne - score) << 31) | (unsigned long long)((uint32_t)vid & 0x7fffffffu),
+                ((unsigned long long)(uint32_t)(bin + kAwMaxB) << 32) | row_len, votes};
+    }
+    static __device__ __forceinline__ AwHit pad() { return {kAlPad, kAlPad, ~0u}; }
+    __device__ __forceinline__ bool is_pad() const { return w == kAlPad; }
+    static __device__ __forceinline__ bool le(const AwHit &a, const AwHit &b) {
+        return a.w < b.w || (a.w == b.w && (a.p < b.p || (a.p == b.p && a.v <= b.v)));
+    }
+    __device__ __forceinline__ int4 row() const {      // (video_id, row_len, best_bin, votes)
+        const bool pad = is_pad();
+        return make_int4(pad ? -1 : (int32_t)(w & 0x7fffffffu), pad ? 0 : (int32_t)(p & 0xffffffffu),
+                         pad ? 0 : (int32_t)(p >> 32) - kAwMaxB, pad ? 0 : (int32_t)v);
+    }
+    static __device__ __forceinline__ AwHit select(bool c, const AwHit &a, const AwHit &b) {
+        return {c ? a.w : b.w, c ? a.p : b.p, c ? a.v : b.v};
+    }
+    __device__ __forceinline__ AwHit lane(int src) const { return {__shfl(w, src), __shfl(p, src), __shfl(v, src)}; }
+    __device__ __forceinline__ AwHit shift_up() const { return {__shfl_up(w, 1), __shfl_up(p, 1), __shfl_up(v, 1)}; }
+    template <class L> static __device__ __forceinline__ AwHit load(const L &l, int64_t i) { return {l.w[i], l.p[i], l.v[i]}; }
+    template <class L> __device__ __forceinline__ void store(L &l, int64_t i) const {
+        l.w[i] = w;
+        l.p[i] = p;
+        l.v[i] = v;
+    }
+};
+
+// static LDS of a sweep block: the waves' lists at the block's end + a few words
+template <class Hit> constexpr int al_static_lds() { return (int)sizeof(typename Hit::template Lists<kAlWaves * 64>) + 64; }
+
+// One wave's list: lane i holds its i-th best hit (ascending, padding behind them and from lane k on).  The wave
+// takes one more hit (wave-uniform h): false when it does not come before the k-th.  Equal hits are all kept.
+// (Member-wise selects: a conditional assignment of the whole struct compiles to branches and costs registers.)
+template <class Hit> __device__ __forceinline__ bool al_insert(Hit &kept, Hit h, int k, int lane) {
+    const int pos = __popcll(__ballot(Hit::le(kept, h)));          // the kept hits that stay in front: a prefix
     if (pos >= k) return false;
-    const unsigned long long uw = __shfl_up(kw, 1), up = __shfl_up(kp, 1);
-    if (lane > pos) {
-        kw = uw;
-        kp = up;
-    }
-    if (lane == pos) {
-        kw = w;
-        kp = p;
-    }
-    if (lane >= k) kw = kp = kAlPad;
+    const Hit up = kept.shift_up();
+    kept = Hit::select(lane > pos, up, kept);
+    kept = Hit::select(lane == pos, h, kept);
+    kept = Hit::select(lane >= k, Hit::pad(), kept);
     return true;
 }
 
-// ... and a whole sorted list held one entry per lane (ew, ep): entry e is offered until one is refused
-__device__ __forceinline__ void al_take(unsigned long long &kw, unsigned long long &kp, unsigned long long ew,
-                                        unsigned long long ep, int k, int lane) {
-    for (int e = 0; e < k; ++e) {                                  // wave-uniform
-        const unsigned long long w = __shfl(ew, e), p = __shfl(ep, e);
-        if (w == kAlPad || !al_insert(kw, kp, w, p, k, lane)) break;
+// ... and a whole sorted list held one entry per lane (e): entry i is offered until one is refused
+template <class Hit> __device__ __forceinline__ void al_take(Hit &kept, Hit e, int k, int lane) {
+    for (int i = 0; i < k; ++i) {                                  // wave-uniform
+        const Hit h = e.lane(i);
+        if (h.is_pad() || !al_insert(kept, h, k, lane)) break;
     }
 }
 
-__device__ __forceinline__ unsigned long long al_word(uint32_t score, int32_t vid, int bin) {
-    return ((unsigned long long)(kAlScoreOne - score) << 43) | ((unsigned long long)((uint32_t)vid & 0x7fffffffu) << 12) |
-           (unsigned long long)(uint32_t)(bin + 2048);
+// A list held one entry per lane whose padding may stand ANYWHERE (`live`: the lanes that hold a hit; the other
+// lanes' e is never read): the live entries are offered in lane order until one is refused.  As al_take, the early
+// exit needs the live entries ascending - which every block of al_reduce is, by contract.
+template <class Hit> __device__ __forceinline__ void al_take_live(Hit &kept, Hit e, unsigned long long live, int k, int lane) {
+    while (live) {                                                 // wave-uniform
+        const int i = __ffsll((long long)live) - 1;
+        live &= live - 1;
+        if (!al_insert(kept, e.lane(i), k, lane)) break;
+    }
 }
 
+// The block-end merge: every wave leaves its list in LDS, wave 0 folds the others into its own.  Contains a block
+// barrier: every thread of the block calls it.
+template <class Hit, int N> __device__ __forceinline__ void al_merge_waves(Hit &kept, typename Hit::template Lists<N> &s, int wv,
+                                                                           int lane, int k) {
+    kept.store(s, wv * 64 + lane);
+    __syncthreads();
+    if (wv != 0) return;
+#pragma unroll 1
+    for (int j = 1; j < N / 64; ++j) al_take(kept, Hit::load(s, j * 64 + lane), k, lane);
+}
+
+// One wave writes a query's block int32[k+1][4]: k rows (video_id, row_len, best_bin, votes), padding (-1, 0, 0, 0),
+// then (-1, n_hits, 0, 0) with n_hits = INT32_MIN for a refused query
+template <class Hit> __device__ __forceinline__ void al_write_block(const Hit &kept, int32_t *out, int k, int lane, int32_t n_hits) {
+    if (lane < k) {
+        const int4 o = kept.row();
+        out[lane * 4 + 0] = o.x;
+        out[lane * 4 + 1] = o.y;
+        out[lane * 4 + 2] = o.z;
+        out[lane * 4 + 3] = o.w;
+    }
+    if (lane == 0) {
+        out[k * 4 + 0] = -1;
+        out[k * 4 + 1] = n_hits;
+        out[k * 4 + 2] = 0;
+        out[k * 4 + 3] = 0;
+    }
+}
+
+// ---- the sweep and the selection -------------------------------------------------------------------------------
 // grid = (row blocks, Q).  Sorted query q: sv[at .. at + m) with at = q_offsets[q] - q_offsets[0], m = qm[q]
-// (ts_tol_sort_kernel).  part_w / part_p: uint64[Q][n_lists][k], block bx writes list bx; totals[q] (zeroed by the
-// preparation) += the block's hits, one atomic.  Dynamic LDS: al_lds_bytes(lds_keys, B).
-__global__ __launch_bounds__(kAlBlock) void ts_align_topk_kernel(
-    const Row *__restrict__ rows, int64_t n_rows, const int64_t *__restrict__ keys, const double *__restrict__ sv,
-    const int64_t *__restrict__ q_offsets, const int32_t *__restrict__ qm, int32_t lds_keys, double eps, int32_t B,
-    int32_t min_votes, int32_t min_score, const int32_t *__restrict__ exclude_ids, int32_t k,
-    unsigned long long *__restrict__ part_w, unsigned long long *__restrict__ part_p, int32_t n_lists,
-    int32_t *__restrict__ totals) {
+// (ts_tol_sort_kernel).  part: the kept lists, block bx writes list bx; totals[q] (zeroed by the preparation) += the
+// block's hits, one atomic.  width = aw_width(B); dynamic LDS: aw_lds_bytes(lds_keys, B, width).  0 <= B <= kAwMaxB,
+// and B <= 2047 where !kWindowed (the host refuses anything else before the launch).
+template <class Hit, bool kWindowed>
+__device__ __forceinline__ void al_sweep(const Row *__restrict__ rows, int64_t n_rows, const int64_t *__restrict__ keys,
+                                         const double *__restrict__ sv, const int64_t *__restrict__ q_offsets,
+                                         const int32_t *__restrict__ qm, int32_t lds_keys, double eps, int32_t B, int32_t width,
+                                         int32_t min_votes, int32_t min_score, bool contain,
+                                         const int32_t *__restrict__ exclude_ids, int32_t k, typename Hit::Parts part,
+                                         int32_t n_lists, int32_t *__restrict__ totals) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    __shared__ unsigned long long s_w[kAlWaves * 64], s_p[kAlWaves * 64];
+    __shared__ typename Hit::template Lists<kAlWaves * 64> s_kept;
     __shared__ int32_t s_nhits;
     const int q = blockIdx.y;
     const int bx = blockIdx.x;
@@ -131,22 +256,34 @@ __global__ __launch_bounds__(kAlBlock) void ts_align_topk_kernel(
     const int64_t at = q_offsets[q] - q_offsets[0];
     const int lane = threadIdx.x & 63;
     const int wv = threadIdx.x >> 6;
-    const int nbp = al_bins_padded(B);
     double *s = reinterpret_cast<double *>(smem);
-    uint32_t *hist = reinterpret_cast<uint32_t *>(smem + (size_t)lds_keys * 8) + (size_t)wv * nbp;
-    uint16_t *dirty = reinterpret_cast<uint16_t *>(smem + (size_t)lds_keys * 8 + (size_t)kAlWaves * nbp * 4) + (size_t)wv * nbp;
-    uint32_t *n_dirty = reinterpret_cast<uint32_t *>(smem + (size_t)lds_keys * 8 + (size_t)kAlWaves * nbp * 6) + wv;
+    uint32_t *hist = reinterpret_cast<uint32_t *>(smem + (size_t)lds_keys * 8) + (size_t)wv * width;
+    uint16_t *dirty = reinterpret_cast<uint16_t *>(smem + (size_t)lds_keys * 8 + (size_t)kAlWaves * width * 4) + (size_t)wv * width;
+    uint32_t *n_dirty = reinterpret_cast<uint32_t *>(smem + (size_t)lds_keys * 8 + (size_t)kAlWaves * width * 6) + wv;
+    uint16_t *resume = nullptr;
+    int max_windows = 1, resume_keys = 0;
+    if constexpr (kWindowed) {
+        max_windows = aw_max_windows(B, width);
+        resume_keys = aw_resume_keys(B, width);
+        resume = reinterpret_cast<uint16_t *>(smem + (size_t)lds_keys * 8 + (size_t)kAlWaves * ((size_t)width * 6 + 4)) +
+                 (size_t)wv * resume_keys;
+    }
     for (int e = threadIdx.x; e < m; e += kAlBlock) s[e] = sv[at + e];
-    for (int b = lane; b < nbp; b += 64) hist[b] = 0;
+    for (int b = lane; b < width; b += 64) hist[b] = 0;
     if (lane == 0) *n_dirty = 0;
     if (threadIdx.x == 0) s_nhits = 0;
     __syncthreads();
 
     const double Bd = (double)B;
+    double x_min = 0.0, x_max = 0.0;
+    if constexpr (kWindowed) {
+        x_min = s[0];                                                         // sorted numerically, no NaN
+        x_max = s[m - 1];
+    }
     const int32_t excl = exclude_ids ? exclude_ids[q] : -1;
     const int64_t stride = (int64_t)gridDim.x * kAlWaves;
     const int64_t last_row = n_rows - 1;
-    unsigned long long kw = kAlPad, kp = kAlPad;
+    Hit kept = Hit::pad();
     int32_t n_hits = 0;
     int64_t r = (int64_t)bx * kAlWaves + wv;
     Row row = load_row(rows + (r < n_rows ? r : last_row));
@@ -154,114 +291,156 @@ __global__ __launch_bounds__(kAlBlock) void ts_align_topk_kernel(
         const int64_t rn = r + stride;
         const Row nrow = load_row(rows + (rn < n_rows ? rn : last_row));      // lands while this row votes
         const int64_t *rk = keys + row.off;
-        unsigned long long best = 0;
-        for (int j = lane; j < row.len; j += 64) {
-            const double c = __longlong_as_double(rk[j]);
-            for (int t = al_lo(s, m, c, eps, Bd); t < m; ++t) {
-                const double d = al_bin(c, s[t], eps);
-                if (!(d >= -Bd)) break;                                     // behind the window (or NaN there)
-                if (!(d <= Bd)) continue;                                   // (never, behind al_lo: keeps the index in bounds)
-                const int bin = (int)d;
-                const uint32_t cnt = atomicAdd(&hist[bin + B], 1u) + 1u;
-                if (cnt == 1u) dirty[atomicAdd(n_dirty, 1u)] = (uint16_t)(bin + B);
-                const uint32_t order = 2u * (uint32_t)(bin < 0 ? -bin : bin) + (bin > 0 ? 1u : 0u);
-                const unsigned long long key = ((unsigned long long)cnt << 14) | (16383u - order);
-                best = key > best ? key : best;
+        int w0 = 0, w1 = 0;                                                   // the one window [-B, B]
+        if constexpr (kWindowed) {
+            // the row's offset range [bin(c_min, x_max), bin(c_max, x_min)], clipped to [-B, B]; a NaN end (inf - inf)
+            // clips to the bound
+            double c_min = __longlong_as_double(0x7ff0000000000000ll), c_max = -c_min;
+            for (int j = lane; j < row.len; j += 64) {
+                const double c = __longlong_as_double(rk[j]);
+                c_min = c < c_min ? c : c_min;
+                c_max = c > c_max ? c : c_max;
             }
+            for (int off = 32; off > 0; off >>= 1) {
+                const double lo = __shfl_xor(c_min, off), hi = __shfl_xor(c_max, off);
+                c_min = lo < c_min ? lo : c_min;
+                c_max = hi > c_max ? hi : c_max;
+            }
+            const double d_lo = al_bin(c_min, x_max, eps), d_hi = al_bin(c_max, x_min, eps);
+            const double r_lo = d_lo >= -Bd ? d_lo : -Bd, r_hi = d_hi <= Bd ? d_hi : Bd;
+            w1 = -1;                                                          // no window: an empty row, a range outside
+            if (row.len > 0 && r_lo <= r_hi) {                                // -B <= r_lo <= r_hi <= B: both finite
+                w0 = ((int)r_lo + B) / width;
+                w1 = ((int)r_hi + B) / width;
+            }
+            w0 = __builtin_amdgcn_readfirstlane(w0);                          // (equal in every lane already)
+            w1 = __builtin_amdgcn_readfirstlane(w1);
+            w1 = w1 < max_windows - 1 ? w1 : max_windows - 1;                 // (never: (2B) / width is the last window)
+        }
+        unsigned long long best = 0;
+        for (int w = w1; w >= w0; --w) {                                      // wave-uniform, at most max_windows rounds
+            int w_lo = -B, w_hi = B;
+            if constexpr (kWindowed) {
+                w_lo = w * width - B;                                         // >= -B
+                w_hi = w_lo + width - 1 < B ? w_lo + width - 1 : B;
+            }
+            const double lo_d = (double)w_lo, hi_d = (double)w_hi;
+            for (int j = lane; j < row.len; j += 64) {
+                const double c = __longlong_as_double(rk[j]);
+                const bool kept_pos = kWindowed && j < resume_keys;           // (the same in every lane of a round)
+                int t = kept_pos && w != w1 ? (int)resume[j] : al_lo(s, m, c, eps, hi_d);
+                for (; t < m; ++t) {
+                    const double d = al_bin(c, s[t], eps);
+                    if (!(d >= lo_d)) break;                                  // behind the window (or NaN there)
+                    if (!(d <= hi_d)) continue;                               // (never, behind al_lo: keeps the index in bounds)
+                    const int bin = (int)d;                                   // w_lo <= bin <= w_hi
+                    const uint32_t slot = (uint32_t)(bin - w_lo);             // 0 .. width - 1
+                    const uint32_t cnt = atomicAdd(&hist[slot], 1u) + 1u;
+                    if (cnt == 1u) dirty[atomicAdd(n_dirty, 1u)] = (uint16_t)slot;      // at most once per slot: < width
+                    const uint32_t order = 2u * (uint32_t)(bin < 0 ? -bin : bin) + (bin > 0 ? 1u : 0u);
+                    const unsigned long long key = ((unsigned long long)cnt << 33) | (kAlOrderMask - order);
+                    best = key > best ? key : best;
+                }
+                if constexpr (kWindowed) {
+                    if (kept_pos) resume[j] = (uint16_t)t;                    // t <= m <= 4095
+                }
+            }
+            // LDS ops of one wave complete in order: the notes above are visible to the clearing below
+            wave_lds_fence();
+            const int nd = (int)*n_dirty;
+            for (int i = lane; i < nd; i += 64) hist[dirty[i]] = 0;
+            wave_lds_fence();
+            if (lane == 0) *n_dirty = 0;
         }
         for (int off = 32; off > 0; off >>= 1) {
             const unsigned long long o = __shfl_xor(best, off);
             best = o > best ? o : best;
         }
-        // LDS ops of one wave complete in order: the notes above are visible to the clearing below
-        wave_lds_fence();
-        const int nd = (int)*n_dirty;
-        for (int i = lane; i < nd; i += 64) hist[dirty[i]] = 0;
-        wave_lds_fence();
-        if (lane == 0) *n_dirty = 0;
-        const uint32_t votes = (uint32_t)(best >> 14);
+        const uint32_t votes = (uint32_t)(best >> 33);
         const uint32_t rl = (uint32_t)row.len;
         uint32_t v = votes < (uint32_t)m ? votes : (uint32_t)m;
         v = v < rl ? v : rl;
-        if (v >= (uint32_t)min_votes && row.vid != excl) {                  // min_votes >= 1: v >= 1, u >= 1
-            const uint32_t u = (uint32_t)m + rl - v;
-            const uint32_t score = (v << 20) / u;                           // v <= 4095: the shift fits 32 bits
+        if (v >= (uint32_t)min_votes && row.vid != excl) {                  // min_votes >= 1: v >= 1, so m, rl, u >= 1
+            const uint32_t u = contain ? ((uint32_t)m < rl ? (uint32_t)m : rl) : (uint32_t)m + rl - v;
+            const uint32_t score = (v << 20) / u;                           // v <= 4095: the shift fits 32 bits; v <= u
             if (score >= (uint32_t)min_score) {
-                const uint32_t order = 16383u - (uint32_t)(best & 16383u);
+                const uint32_t order = (uint32_t)(kAlOrderMask - (best & kAlOrderMask));
                 const int mag = (int)(order >> 1);
                 ++n_hits;
-                al_insert(kw, kp, al_word(score, row.vid, (order & 1u) ? mag : -mag),
-                          ((unsigned long long)rl << 32) | votes, k, lane);
+                al_insert(kept, Hit::make(score, row.vid, (order & 1u) ? mag : -mag, rl, votes), k, lane);
             }
         }
         row = nrow;
         r = rn;
     }
-    s_w[wv * 64 + lane] = kw;
-    s_p[wv * 64 + lane] = kp;
     if (lane == 0 && n_hits) atomicAdd(&s_nhits, n_hits);                    // LDS
-    __syncthreads();
-    if (wv == 0) {
-#pragma unroll 1
-        for (int j = 1; j < kAlWaves; ++j) al_take(kw, kp, s_w[j * 64 + lane], s_p[j * 64 + lane], k, lane);
-        if (lane < k) {
-            const int64_t o = ((int64_t)q * n_lists + bx) * k + lane;
-            part_w[o] = kw;
-            part_p[o] = kp;
-        }
-    }
+    al_merge_waves<Hit, kAlWaves * 64>(kept, s_kept, wv, lane, k);
+    if (wv == 0 && lane < k) kept.store(part, ((int64_t)q * n_lists + bx) * k + lane);
     if (threadIdx.x == 0 && s_nhits) atomicAdd(&totals[q], s_nhits);
 }
 
-// One block per query: the k smallest (word, payload) of its n_lists sorted partial lists -> d_out[q] =
-// int32[k+1][4]: k rows (video_id, row_len, best_bin, votes), padding (-1, 0, 0, 0), then (-1, n_hits, 0, 0).
-// A query the preparation refused (qm < 0 or > lds_keys): all padding, n_hits = INT32_MIN.
-__global__ __launch_bounds__(kAlReduceBlock) void ts_align_topk_reduce_kernel(
-    const unsigned long long *__restrict__ part_w, const unsigned long long *__restrict__ part_p, int32_t n_lists,
-    int32_t k, const int32_t *__restrict__ qm, int32_t lds_keys, const int32_t *__restrict__ totals,
-    int32_t *__restrict__ d_out) {
-    __shared__ unsigned long long s_w[kAlReduceWaves * 64], s_p[kAlReduceWaves * 64];
+// One block per query: the k smallest hits of its n_lists sorted partial lists -> d_out[q] = int32[k+1][4]
+// (al_write_block).  A query the preparation refused (qm < 0 or > lds_keys): all padding, n_hits = INT32_MIN.
+template <class Hit>
+__device__ __forceinline__ void al_reduce(typename Hit::ConstParts part, int32_t n_lists, int32_t k, const int32_t *__restrict__ qm,
+                                          int32_t lds_keys, const int32_t *__restrict__ totals, int32_t *__restrict__ d_out) {
+    __shared__ typename Hit::template Lists<kAlReduceWaves * 64> s_kept;
     const int q = blockIdx.x;
     const int lane = threadIdx.x & 63;
     const int wv = threadIdx.x >> 6;
     const int32_t m = qm[q];
     const bool refused = m < 0 || m > lds_keys;
-    unsigned long long kw = kAlPad, kp = kAlPad;
+    Hit kept = Hit::pad();
     if (!refused && m > 0) {                                                 // (an empty query's lists were never written)
         const int64_t base = (int64_t)q * n_lists;
         for (int l0 = wv; l0 < n_lists; l0 += kAlReduceLd * kAlReduceWaves) {   // wave-uniform
-            unsigned long long ew[kAlReduceLd], ep[kAlReduceLd];
+            Hit e[kAlReduceLd];
 #pragma unroll
             for (int j = 0; j < kAlReduceLd; ++j) {
                 const int l = l0 + j * kAlReduceWaves;
-                const bool live = l < n_lists && lane < k;
-                ew[j] = live ? part_w[(base + l) * k + lane] : kAlPad;
-                ep[j] = live ? part_p[(base + l) * k + lane] : kAlPad;
+                e[j] = l < n_lists && lane < k ? Hit::load(part, (base + l) * k + lane) : Hit::pad();
             }
 #pragma unroll
-            for (int j = 0; j < kAlReduceLd; ++j) al_take(kw, kp, ew[j], ep[j], k, lane);
+            for (int j = 0; j < kAlReduceLd; ++j) al_take(kept, e[j], k, lane);
         }
     }
-    s_w[wv * 64 + lane] = kw;
-    s_p[wv * 64 + lane] = kp;
-    __syncthreads();
-    if (wv != 0) return;
-#pragma unroll 1
-    for (int j = 1; j < kAlReduceWaves; ++j) al_take(kw, kp, s_w[j * 64 + lane], s_p[j * 64 + lane], k, lane);
-    int32_t *out = d_out + (int64_t)q * (k + 1) * 4;
-    if (lane < k) {
-        const bool pad = kw == kAlPad;
-        out[lane * 4 + 0] = pad ? -1 : (int32_t)((kw >> 12) & 0x7fffffffu);
-        out[lane * 4 + 1] = pad ? 0 : (int32_t)(kp >> 32);
-        out[lane * 4 + 2] = pad ? 0 : (int32_t)(kw & 0xfffu) - 2048;
-        out[lane * 4 + 3] = pad ? 0 : (int32_t)(kp & 0xffffffffu);
-    }
-    if (lane == 0) {
-        out[k * 4 + 0] = -1;
-        out[k * 4 + 1] = refused ? INT32_MIN : totals[q];
-        out[k * 4 + 2] = 0;
-        out[k * 4 + 3] = 0;
-    }
+    al_merge_waves<Hit, kAlReduceWaves * 64>(kept, s_kept, wv, lane, k);
+    if (wv == 0) al_write_block(kept, d_out + (int64_t)q * (k + 1) * 4, k, lane, refused ? INT32_MIN : totals[q]);
+}
+
+// The four entry points only forward.  part_w / part_p: uint64[Q][n_lists][k], part_v: uint32[Q][n_lists][k].
+__global__ __launch_bounds__(kAlBlock) void ts_align_topk_kernel(
+    const Row *__restrict__ rows, int64_t n_rows, const int64_t *__restrict__ keys, const double *__restrict__ sv,
+    const int64_t *__restrict__ q_offsets, const int32_t *__restrict__ qm, int32_t lds_keys, double eps, int32_t B,
+    int32_t min_votes, int32_t min_score, const int32_t *__restrict__ exclude_ids, int32_t k,
+    unsigned long long *__restrict__ part_w, unsigned long long *__restrict__ part_p, int32_t n_lists,
+    int32_t *__restrict__ totals) {
+    al_sweep<AlHit, false>(rows, n_rows, keys, sv, q_offsets, qm, lds_keys, eps, B, al_bins_padded(B), min_votes, min_score,
+                           /* contain */ false, exclude_ids, k, AlHit::Parts{part_w, part_p}, n_lists, totals);
+}
+
+__global__ __launch_bounds__(kAlReduceBlock) void ts_align_topk_reduce_kernel(
+    const unsigned long long *__restrict__ part_w, const unsigned long long *__restrict__ part_p, int32_t n_lists,
+    int32_t k, const int32_t *__restrict__ qm, int32_t lds_keys, const int32_t *__restrict__ totals,
+    int32_t *__restrict__ d_out) {
+    al_reduce<AlHit>(AlHit::ConstParts{part_w, part_p}, n_lists, k, qm, lds_keys, totals, d_out);
+}
+
+__global__ __launch_bounds__(kAlBlock) void ts_alignw_sweep_kernel(
+    const Row *__restrict__ rows, int64_t n_rows, const int64_t *__restrict__ keys, const double *__restrict__ sv,
+    const int64_t *__restrict__ q_offsets, const int32_t *__restrict__ qm, int32_t lds_keys, double eps, int32_t B,
+    int32_t width, int32_t min_votes, int32_t min_score, uint32_t flags, const int32_t *__restrict__ exclude_ids,
+    int32_t k, unsigned long long *__restrict__ part_w, unsigned long long *__restrict__ part_p,
+    uint32_t *__restrict__ part_v, int32_t n_lists, int32_t *__restrict__ totals) {
+    al_sweep<AwHit, true>(rows, n_rows, keys, sv, q_offsets, qm, lds_keys, eps, B, width, min_votes, min_score,
+                          (flags & kAwContain) != 0u, exclude_ids, k, AwHit::Parts{part_w, part_p, part_v}, n_lists, totals);
+}
+
+__global__ __launch_bounds__(kAlReduceBlock) void ts_alignw_reduce_kernel(
+    const unsigned long long *__restrict__ part_w, const unsigned long long *__restrict__ part_p,
+    const uint32_t *__restrict__ part_v, int32_t n_lists, int32_t k, const int32_t *__restrict__ qm, int32_t lds_keys,
+    const int32_t *__restrict__ totals, int32_t *__restrict__ d_out) {
+    al_reduce<AwHit>(AwHit::ConstParts{part_w, part_p, part_v}, n_lists, k, qm, lds_keys, totals, d_out);
 }
 
 // ---- the merge of the shards' blocks (tvz_align_topk_merge) ----------------------------------------------------
@@ -269,26 +448,13 @@ constexpr int kAlMergeBlock = 256;
 constexpr int kAlMergeWaves = kAlMergeBlock / 64;      // queries per block: a wave each
 constexpr int kAlMergeMaxLists = 16;                   // one n_hits per lane, far below a wave
 
-// A list held one entry per lane whose padding may stand ANYWHERE (`live`: the lanes that hold a hit): the live
-// entries are offered in lane order until one is refused.  As al_take, the early exit needs the live entries
-// ascending - which every block of ts_align_topk_reduce_kernel is, by contract.
-__device__ __forceinline__ void al_take_live(unsigned long long &kw, unsigned long long &kp, unsigned long long ew,
-                                             unsigned long long ep, unsigned long long live, int k, int lane) {
-    while (live) {                                                 // wave-uniform
-        const int e = __ffsll((long long)live) - 1;
-        live &= live - 1;
-        if (!al_insert(kw, kp, __shfl(ew, e), __shfl(ep, e), k, lane)) break;
-    }
-}
-
-// gathered int32[n_lists][Q][k+1][4], every [k+1][4] block as ts_align_topk_reduce_kernel writes it (k rows ascending
-// in the contract's order, padding, then (-1, n_hits, 0, 0)) -> d_topk int32[Q][k][4], d_totals int32[Q].
-// One wave per query, no LDS, no barrier.  A block row does not carry its order word - the score depends on nv, the
-// query's count of non-NaN values, which no block holds - so the wave counts nv from the query itself and rebuilds
-// (word, payload) with the sweep's expressions; a row with video_id < 0 is padding wherever it stands, and so is one
-// whose u = nv + row_len - v would be 0 (nothing divides by zero).  The lists are SORTED BY CONTRACT: that is the
-// precondition of the fold's early exit (al_take_live, as al_take).  Equal (word, payload) are identical rows and
-// are all kept.  d_totals[q] = the lists' n_hits summed in 64 bits, clamped to INT32_MAX.  Refused - all k rows
+// gathered int32[n_lists][Q][k+1][4], every [k+1][4] block as al_reduce writes it (k rows ascending in the contract's
+// order, padding, then (-1, n_hits, 0, 0)) -> d_topk int32[Q][k][4], d_totals int32[Q].  One wave per query, no LDS,
+// no barrier.  A block row does not carry its order word - the score depends on nv, the query's count of non-NaN
+// values, which no block holds - so the wave counts nv from the query itself and rebuilds the hit with the sweep's
+// expressions (AlHit::make); a row with video_id < 0 is padding wherever it stands, and so is one whose u = nv +
+// row_len - v would be 0 (nothing divides by zero): neither is live.  The lists are SORTED BY CONTRACT: that is the
+// precondition of the fold's early exit (al_take_live, as al_take).  Equal hits are identical rows and are all kept.  d_totals[q] = the lists' n_hits summed in 64 bits, clamped to INT32_MAX.  Refused - all k rows
 // padding, d_totals[q] = INT32_MIN - when a list's n_hits is negative (INT32_MIN: a rank refused the query) or the
 // query is longer than kAlMaxLen.  n_lists <= kAlMergeMaxLists, k <= kAlMaxK; gathered and d_topk 16-byte aligned.
 __global__ __launch_bounds__(kAlMergeBlock) void ts_align_topk_merge_kernel(
@@ -306,7 +472,7 @@ __global__ __launch_bounds__(kAlMergeBlock) void ts_align_topk_merge_kernel(
     const int64_t qo = q_offsets[q];
     const int64_t len = q_offsets[q + 1] - qo;
     const bool refused = __ballot(nh < 0) != 0ull || len > kAlMaxLen;
-    unsigned long long kw = kAlPad, kp = kAlPad;
+    AlHit kept = AlHit::pad();
     if (!refused) {
         int32_t nvl = 0;
         for (int64_t e = lane; e < len; e += 64) {
@@ -330,21 +496,11 @@ __global__ __launch_bounds__(kAlMergeBlock) void ts_align_topk_merge_kernel(
                 const uint32_t u = nv + rl - v;
                 const bool hit = row[j].x >= 0 && u != 0u;
                 const uint32_t score = hit ? (v << 20) / u : 0u;   // v <= nv <= 4095: the shift fits 32 bits
-                const unsigned long long ew = hit ? al_word(score, row[j].x, row[j].z) : kAlPad;
-                const unsigned long long ep = hit ? ((unsigned long long)rl << 32) | votes : kAlPad;
-                al_take_live(kw, kp, ew, ep, __ballot(hit), k, lane);
+                al_take_live(kept, AlHit::make(score, row[j].x, row[j].z, rl, votes), __ballot(hit), k, lane);
             }
         }
     }
-    if (lane < k) {
-        const bool pad = kw == kAlPad;
-        int4 o;
-        o.x = pad ? -1 : (int32_t)((kw >> 12) & 0x7fffffffu);
-        o.y = pad ? 0 : (int32_t)(kp >> 32);
-        o.z = pad ? 0 : (int32_t)(kw & 0xfffu) - 2048;
-        o.w = pad ? 0 : (int32_t)(kp & 0xffffffffu);
-        reinterpret_cast<int4 *>(d_topk)[(int64_t)q * k + lane] = o;
-    }
+    if (lane < k) reinterpret_cast<int4 *>(d_topk)[(int64_t)q * k + lane] = kept.row();
     if (lane == 0) d_totals[q] = refused ? INT32_MIN : (int32_t)(total > INT32_MAX ? INT32_MAX : total);
 }
 

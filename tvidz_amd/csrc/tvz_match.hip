@@ -27,7 +27,6 @@
 #include "tvz_tol_kernels.h"
 #include "tvz_tol_index_kernels.h"
 #include "tvz_align_kernels.h"
-#include "tvz_align_wide_kernels.h"
 #include "tvz_handle.h"
 #include "tvz_index_build.h"
 
@@ -1312,12 +1311,17 @@ int check_find_args(const tvz_corpus *c, const double *h_query, int64_t n, int64
     return TVZ_OK;
 }
 
-// eps and max_offset of tvz_align and tvz_align_topk; *nb = the offset bins on either side of zero
-int check_align_bins(double eps, double max_offset, int32_t *nb_out) {
+// eps and max_offset of tvz_align, tvz_align_topk and tvz_align_wide_topk; *nb = the offset bins on either side of
+// zero, at most max_bins in all.  A call whose limit is a constant of the header says so by its name (wide_limit).
+int check_align_bins(double eps, double max_offset, int32_t max_bins, const char *wide_limit, int32_t *nb_out) {
     TVZ_REQUIRE(eps > 0.0 && max_offset >= 0.0, "eps must be > 0 and max_offset >= 0");
     const double nb = floor(max_offset / eps + 0.5);
-    if (!(2 * nb + 1 <= kAlignMaxBins))                 // also refuses NaN (eps = max_offset = inf)
-        return tvz::fail(TVZ_ERR_UNSUPPORTED, "max_offset/eps = %.0f needs more than %d bins", nb, kAlignMaxBins);
+    if (!(2 * nb + 1 <= max_bins)) {                    // also refuses max_offset = inf and NaN (eps = max_offset = inf)
+        if (wide_limit)
+            return tvz::fail(TVZ_ERR_UNSUPPORTED, "max_offset/eps = %.0f bins on either side of zero, above %s = %d", nb,
+                             wide_limit, (max_bins - 1) / 2);
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "max_offset/eps = %.0f needs more than %d bins", nb, max_bins);
+    }
     *nb_out = (int32_t)nb;
     return TVZ_OK;
 }
@@ -1630,7 +1634,7 @@ static int tvz_align_impl(tvz_corpus *c, const double *d_query, int32_t n, doubl
     TVZ_REQUIRE(n >= 0 && (n == 0 || d_query), "bad query");
     TVZ_REQUIRE(out_rows >= 0, "out_rows must be >= 0");
     int32_t nb = 0;
-    if (int rc = check_align_bins(eps, max_offset, &nb)) return rc;
+    if (int rc = check_align_bins(eps, max_offset, kAlignMaxBins, nullptr, &nb)) return rc;
     DeviceGuard dg(c->device);
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
     std::shared_lock<std::shared_mutex> lk(c->mu);
@@ -1989,28 +1993,31 @@ static int tvz_match_tol_topk_impl(tvz_corpus *c, const double *d_queries, const
                                     d_out, Workspace{d_workspace, workspace_bytes}, 1, hip_stream, nullptr);
 }
 
-// ---- alignment top-k (tvz_align_kernels.h) ------------------------------------------------------------------
+// ---- alignment top-k, bounded and at any shift (tvz_align_kernels.h) ------------------------------------------
 namespace {
 
-// Workspace of tvz_align_topk, in front of the sorted queries (TolWs, which takes the rest): the queries' hit totals
-// and one kept list - k words and k payloads - per sweep block.  The sizing function knows no row count: the lists are
-// sized by the grid's upper bound, as the tolerant top-k's are.  The sharded forms (n_blocks > 0: the communicator's
-// ranks, at least 1) add the local block and the gathered ones behind them; tvz_align_topk itself (n_blocks = 0) has
-// neither, and its size is what it was.
+// Workspace of both calls, in front of the sorted queries (TolWs, which takes the rest): the queries' hit totals and
+// one kept list per sweep block, as a structure of arrays - k words and k payloads, and for the wide call k raw votes
+// behind them (AlHit::Parts, AwHit::Parts: 16 and 20 bytes per kept hit).  The sizing function knows no row count: the
+// lists are sized by the grid's upper bound, as the tolerant top-k's are.  The sharded forms (n_blocks > 0: the
+// communicator's ranks, at least 1) add the local block and the gathered ones behind them; the plain calls
+// (n_blocks = 0) have neither.
 struct AlignTopkWs {
     int32_t *totals = nullptr;             // [Q]
     unsigned long long *part_w = nullptr;  // [Q][blocks][k]
     unsigned long long *part_p = nullptr;  // [Q][blocks][k]
+    uint32_t *part_v = nullptr;            // [Q][blocks][k], wide only
     int32_t *local = nullptr;              // [Q][k+1][4]
     int32_t *gathered = nullptr;           // [n_blocks][Q][k+1][4]
 };
 
-AlignTopkWs align_topk_ws_layout(Carver &cv, int32_t Q, int32_t k, int32_t n_blocks) {
+AlignTopkWs align_topk_ws_layout(Carver &cv, int32_t Q, int32_t k, bool wide, int32_t n_blocks) {
     AlignTopkWs w;
     const size_t lists = (size_t)tol_topk_max_lists(Q) * (size_t)k;
     w.totals = cv.take<int32_t>((size_t)Q);
     w.part_w = cv.take<unsigned long long>(lists);
     w.part_p = cv.take<unsigned long long>(lists);
+    if (wide) w.part_v = cv.take<uint32_t>(lists);
     if (n_blocks > 0) {
         const size_t block = (size_t)Q * (size_t)(k + 1) * 4;
         w.local = cv.take<int32_t>(block);
@@ -2019,9 +2026,9 @@ AlignTopkWs align_topk_ws_layout(Carver &cv, int32_t Q, int32_t k, int32_t n_blo
     return w;
 }
 
-size_t align_topk_ws_bytes(int32_t Q, int64_t keys, int32_t k, int32_t n_blocks) {
+size_t align_topk_ws_bytes(int32_t Q, int64_t keys, int32_t k, bool wide, int32_t n_blocks) {
     Carver cv(nullptr);
-    align_topk_ws_layout(cv, Q, k, n_blocks);
+    align_topk_ws_layout(cv, Q, k, wide, n_blocks);
     return cv.fixed() + tol_ws_bytes(Q, keys);
 }
 
@@ -2036,58 +2043,91 @@ int check_align_merge(int32_t n_lists, int32_t k) {
 
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-}  // namespace
+// what tells tvz_align_topk and tvz_align_wide_topk apart on the host.  The two sweeps' argument lists differ (the
+// window width, the flags, the third list), so the launches below name the kernels themselves, chosen by `wide`.
+struct AlignTopkForm {
+    bool wide;
+    const char *what, *sizer;        // the call in messages; the sizing function the workspace message names
+    int32_t max_bins;                // 2B + 1 at most
+    const char *wide_limit;          // check_align_bins
+    uint32_t flags;                  // the permitted ones
+    int static_lds;                  // of the sweep
+};
+constexpr AlignTopkForm kAlignBounded{false, "alignment top-k", "tvz_align_topk_workspace_bytes", kAlignMaxBins, nullptr, 0u,
+                                      al_static_lds<AlHit>()};
+constexpr AlignTopkForm kAlignWide{true, "wide alignment top-k", "tvz_align_wide_topk_workspace_bytes", 2 * kAwMaxB + 1,
+                                   "TVZ_ALIGN_WIDE_MAX_B", kAwContain, al_static_lds<AwHit>()};
 
-// used by tvz_comm.hip (same shared object, not exported): sort -> sweep that keeps the k best -> per-query selection.
-// n_ranks = 0: tvz_align_topk itself, d_out is the caller's.  n_ranks >= 1: the workspace also holds the local block
-// and n_ranks gathered ones (tvz_align_topk_sharded_workspace_bytes); d_out = NULL writes the block into the
-// workspace's own, and `blocks` is told where it went and where the all-gather's target is.
-int tvz_align_topk_local(tvz_corpus *c, const Batch &b, const AlignCall &a, int32_t k, int32_t *d_out, Workspace ws,
-                         int32_t n_ranks, void *hip_stream, ShardBlocks *blocks) {
+// Both calls: sort -> sweep that keeps the k best -> per-query selection.  n_ranks = 0: d_out is the caller's.
+// n_ranks >= 1 (bounded only): the workspace also holds the local block and n_ranks gathered ones
+// (tvz_align_topk_sharded_workspace_bytes); d_out = NULL writes the block into the workspace's own, and `blocks` is
+// told where it went and where the all-gather's target is.
+int align_topk_run(const AlignTopkForm &f, tvz_corpus *c, const Batch &b, const AlignCall &a, uint32_t flags, int32_t k,
+                   int32_t *d_out, Workspace ws, int32_t n_ranks, void *hip_stream, ShardBlocks *blocks) {
     const int32_t Q = b.Q, max_query_len = b.max_query_len;
     if (int rc = check_batch_args(c, b, 0)) return rc;
     int32_t B = 0;
-    if (int rc = check_align_bins(a.eps, a.max_offset, &B)) return rc;
-    TVZ_REQUIRE(a.min_votes >= 1, "alignment top-k: min_votes %d below 1", (int)a.min_votes);
-    TVZ_REQUIRE(a.min_score >= 0 && a.min_score <= kAlScoreOne, "alignment top-k: min_score %d outside 0..%d", (int)a.min_score,
+    if (int rc = check_align_bins(a.eps, a.max_offset, f.max_bins, f.wide_limit, &B)) return rc;
+    if (f.wide)                      // (the bounded call has no flags argument)
+        TVZ_REQUIRE((flags & ~f.flags) == 0u, "%s: unknown flag bits 0x%x", f.what, (unsigned)(flags & ~f.flags));
+    TVZ_REQUIRE(a.min_votes >= 1, "%s: min_votes %d below 1", f.what, (int)a.min_votes);
+    TVZ_REQUIRE(a.min_score >= 0 && a.min_score <= kAlScoreOne, "%s: min_score %d outside 0..%d", f.what, (int)a.min_score,
                 kAlScoreOne);
-    if (k < 1 || k > kAlMaxK)
-        return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment top-k: k=%d outside 1..%d", (int)k, kAlMaxK);
+    if (k < 1 || k > kAlMaxK) return tvz::fail(TVZ_ERR_UNSUPPORTED, "%s: k=%d outside 1..%d", f.what, (int)k, kAlMaxK);
     if (max_query_len > kAlMaxLen)
-        return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment top-k: max_query_len %d above %d", (int)max_query_len, kAlMaxLen);
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "%s: max_query_len %d above %d", f.what, (int)max_query_len, kAlMaxLen);
     if (Q == 0) return TVZ_OK;
     Carver cv(ws.p);
-    const AlignTopkWs w = align_topk_ws_layout(cv, Q, k, n_ranks);
+    const AlignTopkWs w = align_topk_ws_layout(cv, Q, k, f.wide, n_ranks);
     const int32_t lds_keys = std::max(max_query_len, 1);
-    const size_t lds = al_lds_bytes(lds_keys, B);
+    const int32_t width = aw_width(B);   // (the bounded call's B <= 2047: all its bins, and no resume positions)
+    const size_t lds = aw_lds_bytes(lds_keys, B, width);
     auto args_ok = [&]() -> int {
         TVZ_REQUIRE(d_out != nullptr || w.local != nullptr, "d_out is NULL");
         if (d_out == nullptr) d_out = w.local;
         if (blocks) *blocks = ShardBlocks{d_out, w.gathered};
-        TVZ_REQUIRE(lds + kAlStaticLds <= (size_t)kLdsPerWorkgroup,
-                    "alignment top-k sweep: %zu B of dynamic + %d B of static LDS exceed a gfx950 workgroup's", lds, kAlStaticLds);
+        TVZ_REQUIRE(lds + f.static_lds <= (size_t)kLdsPerWorkgroup,
+                    "%s sweep: %zu B of dynamic + %d B of static LDS exceed a gfx950 workgroup's", f.what, lds, f.static_lds);
         return TVZ_OK;
     };
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
     // the fixed parts and room for ONE query of max_query_len values; what the caller gave beyond that holds more
     // (the sorted positions are unused here)
     TolCall t;
-    if (int rc = tol_prelude(c, b, TolFront{cv, cv.fixed(), w.totals, "alignment top-k",
-                                            n_ranks > 0 ? "tvz_align_topk_sharded_workspace_bytes" : "tvz_align_topk_workspace_bytes"},
+    if (int rc = tol_prelude(c, b, TolFront{cv, cv.fixed(), w.totals, f.what,
+                                            n_ranks > 0 ? "tvz_align_topk_sharded_workspace_bytes" : f.sizer},
                              ws.p ? ws.bytes : 0, max_query_len, st, args_ok, t))
         return rc;
     const int64_t n_rows = t.n_rows;
     const int n_blocks = n_rows ? (int)std::min<int64_t>(tvz::ceil_div(n_rows, (int64_t)kAlWaves), tol_topk_max_blocks(Q)) : 0;
+    const dim3 grid((unsigned)n_blocks, (unsigned)Q);
     if (n_blocks) {
-        hipLaunchKernelGGL(ts_align_topk_kernel, dim3((unsigned)n_blocks, (unsigned)Q), dim3(kAlBlock), lds, st, c->rows.p,
-                           n_rows, c->keys.p, t.ws.sv, b.d_q_offsets, t.ws.qm, lds_keys, a.eps, B, a.min_votes, a.min_score,
-                           b.d_exclude_ids, k, w.part_w, w.part_p, n_blocks, w.totals);
+        if (f.wide)
+            hipLaunchKernelGGL(ts_alignw_sweep_kernel, grid, dim3(kAlBlock), lds, st, c->rows.p, n_rows, c->keys.p, t.ws.sv,
+                               b.d_q_offsets, t.ws.qm, lds_keys, a.eps, B, width, a.min_votes, a.min_score, flags,
+                               b.d_exclude_ids, k, w.part_w, w.part_p, w.part_v, n_blocks, w.totals);
+        else
+            hipLaunchKernelGGL(ts_align_topk_kernel, grid, dim3(kAlBlock), lds, st, c->rows.p, n_rows, c->keys.p, t.ws.sv,
+                               b.d_q_offsets, t.ws.qm, lds_keys, a.eps, B, a.min_votes, a.min_score, b.d_exclude_ids, k,
+                               w.part_w, w.part_p, n_blocks, w.totals);
         TVZ_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(ts_align_topk_reduce_kernel, dim3((unsigned)Q), dim3(kAlReduceBlock), 0, st, w.part_w, w.part_p,
-                       n_blocks, k, t.ws.qm, lds_keys, w.totals, d_out);
+    if (f.wide)
+        hipLaunchKernelGGL(ts_alignw_reduce_kernel, dim3((unsigned)Q), dim3(kAlReduceBlock), 0, st, w.part_w, w.part_p, w.part_v,
+                           n_blocks, k, t.ws.qm, lds_keys, w.totals, d_out);
+    else
+        hipLaunchKernelGGL(ts_align_topk_reduce_kernel, dim3((unsigned)Q), dim3(kAlReduceBlock), 0, st, w.part_w, w.part_p,
+                           n_blocks, k, t.ws.qm, lds_keys, w.totals, d_out);
     TVZ_HIP(hipGetLastError());
     return record(c, st);
+}
+
+}  // namespace
+
+// used by tvz_comm.hip (same shared object, not exported): the bounded call, with the sharded forms' blocks
+int tvz_align_topk_local(tvz_corpus *c, const Batch &b, const AlignCall &a, int32_t k, int32_t *d_out, Workspace ws,
+                         int32_t n_ranks, void *hip_stream, ShardBlocks *blocks) {
+    return align_topk_run(kAlignBounded, c, b, a, 0u, k, d_out, ws, n_ranks, hip_stream, blocks);
 }
 
 static int tvz_align_topk_impl(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
@@ -2139,100 +2179,13 @@ static int tvz_align_topk_shards_impl(tvz_corpus *const *shards, int32_t n_shard
     return tvz_align_topk_merge_impl(d_blocks, n_shards, Q, k, d_queries, d_q_offsets, d_topk, d_totals, hip_stream);
 }
 
-// ---- alignment top-k at any shift (tvz_align_wide_kernels.h) ---------------------------------------------------
-namespace {
-
-// eps and max_offset of tvz_align_wide_topk: check_align_bins with the wide limit, kAwMaxB bins on either side
-int check_align_wide_bins(double eps, double max_offset, int32_t *nb_out) {
-    TVZ_REQUIRE(eps > 0.0 && max_offset >= 0.0, "eps must be > 0 and max_offset >= 0");
-    const double nb = floor(max_offset / eps + 0.5);
-    if (!(nb <= (double)kAwMaxB))                       // also refuses max_offset = inf and NaN (eps = max_offset = inf)
-        return tvz::fail(TVZ_ERR_UNSUPPORTED, "max_offset/eps = %.0f bins on either side of zero, above TVZ_ALIGN_WIDE_MAX_B = %d",
-                         nb, kAwMaxB);
-    *nb_out = (int32_t)nb;
-    return TVZ_OK;
-}
-
-// Workspace of tvz_align_wide_topk, in front of the sorted queries: AlignTopkWs's totals and lists, with a third
-// array for the entries' raw votes (a kept hit is two 64-bit words and one 32-bit one)
-struct AlignWideWs {
-    int32_t *totals = nullptr;             // [Q]
-    unsigned long long *part_w = nullptr;  // [Q][blocks][k]
-    unsigned long long *part_p = nullptr;  // [Q][blocks][k]
-    uint32_t *part_v = nullptr;            // [Q][blocks][k]
-};
-
-AlignWideWs align_wide_ws_layout(Carver &cv, int32_t Q, int32_t k) {
-    AlignWideWs w;
-    const size_t lists = (size_t)tol_topk_max_lists(Q) * (size_t)k;
-    w.totals = cv.take<int32_t>((size_t)Q);
-    w.part_w = cv.take<unsigned long long>(lists);
-    w.part_p = cv.take<unsigned long long>(lists);
-    w.part_v = cv.take<uint32_t>(lists);
-    return w;
-}
-
-size_t align_wide_ws_bytes(int32_t Q, int64_t keys, int32_t k) {
-    Carver cv(nullptr);
-    align_wide_ws_layout(cv, Q, k);
-    return cv.fixed() + tol_ws_bytes(Q, keys);
-}
-
-// sort -> windowed sweep that keeps the k best -> per-query selection
-int tvz_align_wide_topk_local(tvz_corpus *c, const Batch &b, const AlignCall &a, uint32_t flags, int32_t k, int32_t *d_out,
-                              Workspace ws, void *hip_stream) {
-    const int32_t Q = b.Q, max_query_len = b.max_query_len;
-    if (int rc = check_batch_args(c, b, 0)) return rc;
-    int32_t B = 0;
-    if (int rc = check_align_wide_bins(a.eps, a.max_offset, &B)) return rc;
-    TVZ_REQUIRE((flags & ~kAwContain) == 0u, "wide alignment top-k: unknown flag bits 0x%x", (unsigned)(flags & ~kAwContain));
-    TVZ_REQUIRE(a.min_votes >= 1, "wide alignment top-k: min_votes %d below 1", (int)a.min_votes);
-    TVZ_REQUIRE(a.min_score >= 0 && a.min_score <= kAlScoreOne, "wide alignment top-k: min_score %d outside 0..%d",
-                (int)a.min_score, kAlScoreOne);
-    if (k < 1 || k > kAlMaxK)
-        return tvz::fail(TVZ_ERR_UNSUPPORTED, "wide alignment top-k: k=%d outside 1..%d", (int)k, kAlMaxK);
-    if (max_query_len > kAlMaxLen)
-        return tvz::fail(TVZ_ERR_UNSUPPORTED, "wide alignment top-k: max_query_len %d above %d", (int)max_query_len, kAlMaxLen);
-    if (Q == 0) return TVZ_OK;
-    Carver cv(ws.p);
-    const AlignWideWs w = align_wide_ws_layout(cv, Q, k);
-    const int32_t lds_keys = std::max(max_query_len, 1);
-    const int32_t width = aw_width(B);
-    const size_t lds = aw_lds_bytes(lds_keys, B, width);
-    auto args_ok = [&]() -> int {
-        TVZ_REQUIRE(d_out != nullptr, "d_out is NULL");
-        TVZ_REQUIRE(lds + kAwStaticLds <= (size_t)kLdsPerWorkgroup,
-                    "wide alignment top-k sweep: %zu B of dynamic + %d B of static LDS exceed a gfx950 workgroup's", lds, kAwStaticLds);
-        return TVZ_OK;
-    };
-    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    TolCall t;
-    if (int rc = tol_prelude(c, b, TolFront{cv, cv.fixed(), w.totals, "wide alignment top-k", "tvz_align_wide_topk_workspace_bytes"},
-                             ws.p ? ws.bytes : 0, max_query_len, st, args_ok, t))
-        return rc;
-    const int64_t n_rows = t.n_rows;
-    const int n_blocks = n_rows ? (int)std::min<int64_t>(tvz::ceil_div(n_rows, (int64_t)kAlWaves), tol_topk_max_blocks(Q)) : 0;
-    if (n_blocks) {
-        hipLaunchKernelGGL(ts_alignw_sweep_kernel, dim3((unsigned)n_blocks, (unsigned)Q), dim3(kAlBlock), lds, st, c->rows.p,
-                           n_rows, c->keys.p, t.ws.sv, b.d_q_offsets, t.ws.qm, lds_keys, a.eps, B, width, a.min_votes,
-                           a.min_score, flags, b.d_exclude_ids, k, w.part_w, w.part_p, w.part_v, n_blocks, w.totals);
-        TVZ_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(ts_alignw_reduce_kernel, dim3((unsigned)Q), dim3(kAlReduceBlock), 0, st, w.part_w, w.part_p, w.part_v,
-                       n_blocks, k, t.ws.qm, lds_keys, w.totals, d_out);
-    TVZ_HIP(hipGetLastError());
-    return record(c, st);
-}
-
-}  // namespace
-
 static int tvz_align_wide_topk_impl(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
                                     int32_t max_query_len, double eps, double max_offset, int32_t min_votes,
                                     int32_t min_score, uint32_t flags, const int32_t *d_exclude_ids, int32_t k,
                                     int32_t *d_out, void *d_workspace, size_t workspace_bytes, void *hip_stream) {
-    return tvz_align_wide_topk_local(c, Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids},
-                                     AlignCall{eps, max_offset, min_votes, min_score}, flags, k, d_out,
-                                     Workspace{d_workspace, workspace_bytes}, hip_stream);
+    return align_topk_run(kAlignWide, c, Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids},
+                          AlignCall{eps, max_offset, min_votes, min_score}, flags, k, d_out,
+                          Workspace{d_workspace, workspace_bytes}, 0, hip_stream, nullptr);
 }
 
 #ifdef TVZ_IX_STAMP
@@ -2405,14 +2358,14 @@ TVZ_EXPORT int tvz_align(tvz_corpus *c, const double *d_query, int32_t n, double
 TVZ_EXPORT size_t tvz_align_topk_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k) {
     if (Q < 0 || max_query_len < 0 || total_query_keys < 0 || k < 1) return 0;
     const int64_t keys = total_query_keys > 0 ? total_query_keys : (int64_t)Q * max_query_len;
-    return align_topk_ws_bytes(Q, std::max<int64_t>(keys, max_query_len), k, 0);
+    return align_topk_ws_bytes(Q, std::max<int64_t>(keys, max_query_len), k, false, 0);
 }
 
 TVZ_EXPORT size_t tvz_align_topk_sharded_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys,
                                                          int32_t k, int32_t n_ranks) {
     if (Q < 0 || max_query_len < 0 || total_query_keys < 0 || k < 1 || n_ranks < 0) return 0;
     const int64_t keys = total_query_keys > 0 ? total_query_keys : (int64_t)Q * max_query_len;
-    return align_topk_ws_bytes(Q, std::max<int64_t>(keys, max_query_len), k, std::max(n_ranks, 1));
+    return align_topk_ws_bytes(Q, std::max<int64_t>(keys, max_query_len), k, false, std::max(n_ranks, 1));
 }
 
 TVZ_EXPORT int tvz_align_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
@@ -2426,7 +2379,7 @@ TVZ_EXPORT int tvz_align_topk(tvz_corpus *c, const double *d_queries, const int6
 TVZ_EXPORT size_t tvz_align_wide_topk_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k) {
     if (Q < 0 || max_query_len < 0 || total_query_keys < 0 || k < 1) return 0;
     const int64_t keys = total_query_keys > 0 ? total_query_keys : (int64_t)Q * max_query_len;
-    return align_wide_ws_bytes(Q, std::max<int64_t>(keys, max_query_len), k);
+    return align_topk_ws_bytes(Q, std::max<int64_t>(keys, max_query_len), k, true, 0);
 }
 
 TVZ_EXPORT int tvz_align_wide_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
