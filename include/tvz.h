@@ -452,8 +452,9 @@ int tvz_align_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q_of
  * Cost: a row's offset range [bin(c_min, x_max), bin(c_max, x_min)], clipped to [-B, B], is walked in windows of 1,024
  * bins (B <= 2047: one window of all bins, the work of tvz_align_topk); per row key one binary search of the sorted
  * query, then one step per window, and over all windows every (key, value) pair inside [-B, B] votes once - far more
- * votes than the bounded search counts.  TVZ_ALIGN_WIDE_MAX_B bounds a row at 8,193 windows.  The sharded forms (tvz_align_topk_merge, _shards, _sharded) do not take these blocks: their merge
- * rebuilds a 12-bit bin word. */
+ * votes than the bounded search counts.  TVZ_ALIGN_WIDE_MAX_B bounds a row at 8,193 windows.  These blocks have sharded
+ * forms of their own (tvz_align_wide_topk_merge, _shards, _sharded, below); the bounded ones (tvz_align_topk_merge,
+ * _shards, _sharded) must not be fed them: their merge rebuilds a 12-bit bin word. */
 #define TVZ_ALIGN_WIDE_MAX_B (1 << 22)   /* bins on either side of zero */
 #define TVZ_ALIGN_CONTAIN 1u             /* flags: score = v / min(nv, row_len) instead of the Jaccard */
 size_t tvz_align_wide_topk_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k);
@@ -479,7 +480,9 @@ int tvz_align_wide_topk(tvz_corpus *c, const double *d_queries, const int64_t *d
  *   - a query is REFUSED - all k rows padding, d_totals[q] = INT32_MIN - when any list's n_hits is negative (a shard
  *     refused it) or it is longer than 4,095 values.
  * n_lists outside 1..16 or k outside 1..64: TVZ_ERR_UNSUPPORTED; a NULL pointer, a negative Q, d_gathered or d_topk
- * not 16-byte aligned: TVZ_ERR_INVALID; nothing is written on a refusal; Q = 0 returns TVZ_OK.  Enqueues one launch. */
+ * not 16-byte aligned: TVZ_ERR_INVALID; nothing is written on a refusal; Q = 0 returns TVZ_OK.  Enqueues one launch.
+ * Blocks of tvz_align_wide_topk are NOT this merge's: a best_bin outside +-2047 does not fit the word it rebuilds, and
+ * the wide order is another one (tvz_align_wide_topk_merge takes them). */
 int tvz_align_topk_merge(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t k, const double *d_queries,
                          const int64_t *d_q_offsets, int32_t *d_topk, int32_t *d_totals, void *hip_stream);
 /* The shards of ONE process (several handles on one device, as tvz_match_topk_shards): tvz_align_topk on every handle
@@ -504,6 +507,60 @@ int tvz_align_topk_sharded(tvz_corpus *c, tvz_comm *comm, const double *d_querie
                            int32_t Q, int32_t max_query_len, double eps, double max_offset, int32_t min_votes,
                            int32_t min_score, const int32_t *d_exclude_ids, int32_t k, int32_t *d_topk,
                            int32_t *d_totals, void *d_workspace, size_t workspace_bytes, void *hip_stream);
+
+/* The alignment top-k AT ANY SHIFT over a SHARDED table: the three forms above for the block of tvz_align_wide_topk -
+ * int32[Q][k+1][4], k rows (video_id, row_len, best_bin, votes) with best_bin anywhere in +-TVZ_ALIGN_WIDE_MAX_B,
+ * ascending in the wide order of the call's `flags`, padding, then (-1, n_hits, 0, 0).  (TVZ_VERSION unchanged: new
+ * exports only.)
+ *
+ * tvz_align_wide_topk_merge: d_gathered int32[n_lists][Q][k+1][4] -> d_topk int32[Q][k][4], d_totals int32[Q].  As
+ * tvz_align_topk_merge it takes the queries, counts nv and rebuilds every row's score with the sweep's own
+ * expressions: v = min(votes, nv, row_len); flags = 0: u = nv + row_len - v; flags & TVZ_ALIGN_CONTAIN: u = min(nv,
+ * row_len); score = (v << 20) / u.  Rules:
+ *   - the k rows are the k smallest of the union by the tuple (2^20 - score, video_id, best_bin as a signed number,
+ *     row_len, votes); rows equal in all five are identical rows and are all kept; fewer than k: padding rows
+ *     (-1, 0, 0, 0) behind them;
+ *   - a row with video_id < 0 is padding wherever it stands; so is a row whose u is 0 under the call's score kind
+ *     (with TVZ_ALIGN_CONTAIN any row with row_len = 0, and every row of a query with nv = 0) - nothing divides by
+ *     zero;
+ *   - PRECONDITION: every list is sorted as tvz_align_wide_topk writes it WITH THE SAME `flags` (the merge stops
+ *     reading a list at the first row that does not come before the k-th kept); the two score kinds order
+ *     differently, so blocks made with one must not be merged with the other;
+ *   - d_totals[q] = the lists' n_hits summed in 64 bits, clamped to INT32_MAX;
+ *   - a query is REFUSED - all k rows padding, d_totals[q] = INT32_MIN - when any list's n_hits is negative (a shard
+ *     refused it) or it is longer than 4,095 values.
+ * n_lists outside 1..16 or k outside 1..64: TVZ_ERR_UNSUPPORTED; a flag bit other than TVZ_ALIGN_CONTAIN, a NULL
+ * pointer, a negative Q, d_gathered or d_topk not 16-byte aligned: TVZ_ERR_INVALID; nothing is written on a refusal;
+ * Q = 0 returns TVZ_OK.  Enqueues one launch.  With flags = 0 and every best_bin within +-2047 the result equals
+ * tvz_align_topk_merge's bit for bit. */
+int tvz_align_wide_topk_merge(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t k, uint32_t flags,
+                              const double *d_queries, const int64_t *d_q_offsets, int32_t *d_topk, int32_t *d_totals,
+                              void *hip_stream);
+/* The shards of ONE process (several handles on one device): tvz_align_wide_topk on every handle in turn on
+ * `hip_stream`, the blocks written to d_blocks int32[n_shards][Q][k+1][4], then tvz_align_wide_topk_merge with the same
+ * flags -> d_topk, d_totals.  One workspace sized for ONE handle (tvz_align_wide_topk_workspace_bytes) serves all of
+ * them.  Refuses what tvz_align_wide_topk and the merge refuse (n_shards outside 1..16 included) before anything is
+ * enqueued. */
+int tvz_align_wide_topk_shards(tvz_corpus *const *shards, int32_t n_shards, const double *d_queries,
+                               const int64_t *d_q_offsets, int32_t Q, int32_t max_query_len, double eps,
+                               double max_offset, int32_t min_votes, int32_t min_score, uint32_t flags,
+                               const int32_t *d_exclude_ids, int32_t k, int32_t *d_blocks, int32_t *d_topk,
+                               int32_t *d_totals, void *d_workspace, size_t workspace_bytes, void *hip_stream);
+/* One process per GPU: tvz_align_wide_topk into the workspace's own block -> the ONE ncclAllGather of Q x (k+1) x 4
+ * int32 per rank, ordered on the communicator with the other sharded calls' collectives -> tvz_align_wide_topk_merge
+ * with the same flags; every rank gets the same d_topk int32[Q][k][4] and d_totals int32[Q].  Up to 16 ranks; every
+ * rank passes the same arguments.
+ * Workspace = tvz_align_wide_topk_workspace_bytes(Q, max_query_len, total_query_keys, k)
+ *           + (1 + max(n_ranks, 1)) x Q x (k + 1) x 16                                  (local + gathered blocks)
+ *           + alignment (each part to 256 B).
+ * Has run on hardware at ONE rank only. */
+size_t tvz_align_wide_topk_sharded_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k,
+                                                   int32_t n_ranks);
+int tvz_align_wide_topk_sharded(tvz_corpus *c, tvz_comm *comm, const double *d_queries, const int64_t *d_q_offsets,
+                                int32_t Q, int32_t max_query_len, double eps, double max_offset, int32_t min_votes,
+                                int32_t min_score, uint32_t flags, const int32_t *d_exclude_ids, int32_t k,
+                                int32_t *d_topk, int32_t *d_totals, void *d_workspace, size_t workspace_bytes,
+                                void *hip_stream);
 
 /* ------------------------------------------------------------------------
  * Opt-in TOLERANT duplicate match.  NOT the reference's verdict: db.py:79,85-91 match exact float64

@@ -102,6 +102,14 @@ def align_wide_topk_workspace_bytes(Q: int, max_query_len: int, total_query_keys
     return int(_lib.load().tvz_align_wide_topk_workspace_bytes(int(Q), int(max_query_len), int(total_query_keys), int(k)))
 
 
+def align_wide_topk_sharded_workspace_bytes(Q: int, max_query_len: int, total_query_keys: int = 0, k: int = 16,
+                                            n_ranks: int = 1) -> int:
+    """tvz_align_wide_topk_sharded_workspace_bytes: align_wide_topk_workspace_bytes + the local block and `n_ranks`
+    gathered ones (Q x (k + 1) x 16 bytes each)."""
+    return int(_lib.load().tvz_align_wide_topk_sharded_workspace_bytes(int(Q), int(max_query_len), int(total_query_keys),
+                                                                       int(k), int(n_ranks)))
+
+
 ALIGN_WIDE_MAX_B = 1 << 22                  # include/tvz.h TVZ_ALIGN_WIDE_MAX_B: tvz_align_wide_topk's bins per side
 ALIGN_CONTAIN = 1                           # include/tvz.h TVZ_ALIGN_CONTAIN
 
@@ -336,10 +344,9 @@ class DeviceCorpus:
         dev, s, ws, excl = self._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace,
                                          align_wide_topk_workspace_bytes(Q, max_query_len, d_queries.numel(), k))
         out = _out(out, (Q, k + 1, 4), dev)
-        if max_offset is None:
-            max_offset = ALIGN_WIDE_MAX_B * float(eps)
         _lib.check(self.lib.tvz_align_wide_topk(
-            self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps), float(max_offset),
+            self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps),
+            _wide_offset(eps, max_offset),
             int(min_votes), int(min_score), ALIGN_CONTAIN if contain else 0, excl, int(k), out.data_ptr(), ws.data_ptr(),
             ws.numel(), s.cuda_stream))
         return out
@@ -515,6 +522,31 @@ class Comm:
             ws.data_ptr(), ws.numel(), s.cuda_stream))
         return rows, totals
 
+    def align_wide_topk_sharded(self, corpus: DeviceCorpus, d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
+                                max_query_len: int, *, eps: float, max_offset: Optional[float] = None, k: int,
+                                min_votes: int = 1, min_score: int = 0, contain: bool = False,
+                                d_exclude_ids: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                                stream: Optional[torch.cuda.Stream] = None,
+                                out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+        """tvz_align_wide_topk_sharded: the local alignment top-k at any shift (`max_offset=None`: the widest) ->
+        ncclAllGather of the [Q,k+1,4] blocks -> the wide merge; -> (rows int32 [Q,k,4], totals int32 [Q]), identical
+        on every rank."""
+        Q = d_q_offsets.numel() - 1
+        dev, s, ws, excl = corpus._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace,
+                                           align_wide_topk_sharded_workspace_bytes(Q, max_query_len, d_queries.numel(), k,
+                                                                                   self.n_ranks))
+        rows, totals = _topk_out(out, Q, k, 4, dev)
+        _lib.check(self.lib.tvz_align_wide_topk_sharded(
+            corpus._h, self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps),
+            _wide_offset(eps, max_offset), int(min_votes), int(min_score), ALIGN_CONTAIN if contain else 0, excl, int(k),
+            rows.data_ptr(), totals.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
+        return rows, totals
+
+
+def _wide_offset(eps: float, max_offset: Optional[float]) -> float:
+    """max_offset of the wide calls: None is the widest the library takes, ALIGN_WIDE_MAX_B bins of eps."""
+    return ALIGN_WIDE_MAX_B * float(eps) if max_offset is None else float(max_offset)
+
 
 def _check_queries(device: int, d_queries, d_q_offsets):
     dev = d_queries.device
@@ -649,6 +681,40 @@ def align_topk_shards(shards: Sequence["DeviceCorpus"], d_queries: torch.Tensor,
             handles, len(shards), d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps),
             float(max_offset), int(min_votes), int(min_score), excl, int(k), blocks.data_ptr(), rows.data_ptr(),
             totals.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
+    return blocks, rows, totals
+
+
+def align_wide_topk_merge(gathered: torch.Tensor, k: int, d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
+                          contain: bool = False, stream: Optional[torch.cuda.Stream] = None, out=None):
+    """tvz_align_wide_topk_merge: align_topk_merge for the blocks of align_wide_topk_block - bins anywhere in
+    +-ALIGN_WIDE_MAX_B, every list sorted by align_wide_order_key of the SAME `contain`."""
+    R, Q, k1, w = gathered.shape
+    if k1 != k + 1 or w != 4 or gathered.dtype != torch.int32 or not gathered.is_contiguous():
+        raise RuntimeError("gathered must be a contiguous int32 [R,Q,k+1,4]")
+    rows, totals = _topk_out(out, Q, k, 4, gathered.device)
+    s = stream if stream is not None else torch.cuda.current_stream(gathered.device)
+    with torch.cuda.device(gathered.device):
+        _lib.check(_lib.load().tvz_align_wide_topk_merge(gathered.data_ptr(), R, Q, int(k), ALIGN_CONTAIN if contain else 0,
+                                                         d_queries.data_ptr(), d_q_offsets.data_ptr(), rows.data_ptr(),
+                                                         totals.data_ptr(), s.cuda_stream))
+    return rows, totals
+
+
+def align_wide_topk_shards(shards: Sequence["DeviceCorpus"], d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
+                           max_query_len: int, *, eps: float, max_offset: Optional[float] = None, k: int,
+                           workspace: torch.Tensor, min_votes: int = 1, min_score: int = 0, contain: bool = False,
+                           d_exclude_ids: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None):
+    """tvz_align_wide_topk on every handle of ONE device + the wide merge behind one library call
+    (tvz_align_wide_topk_shards): -> (blocks int32 [R,Q,k+1,4], rows int32 [Q,k,4], totals int32 [Q]).  `workspace`:
+    align_wide_topk_workspace_bytes (its size is the library's to judge, as align_topk_shards')."""
+    Q = d_q_offsets.numel() - 1
+    dev, s, ws, excl = shards[0]._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace, None)
+    handles, blocks, rows, totals = _shards_out(shards, Q, k, 4, dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().tvz_align_wide_topk_shards(
+            handles, len(shards), d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps),
+            _wide_offset(eps, max_offset), int(min_votes), int(min_score), ALIGN_CONTAIN if contain else 0, excl, int(k),
+            blocks.data_ptr(), rows.data_ptr(), totals.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
     return blocks, rows, totals
 
 

@@ -1,8 +1,9 @@
 // tvz_align_kernels.h — batched alignment score with the k best rows kept inside the sweep, gfx950 wave64: the bounded
 // call (tvz_align_topk, at most kAlignMaxBins bins), the call at any shift (tvz_align_wide_topk, up to kAwMaxB bins on
-// either side of zero) and the merge of the shards' blocks.  Included by tvz_match.hip only.  From tvz_match_kernels.h:
-// Row, load_row; from tvz_tol_kernels.h: ts_tol_sort_kernel (the batch's queries sorted numerically, NaNs dropped, qm =
-// the non-NaN count) and the sweep's block count (tol_topk_max_blocks); from tvz_wave.h: wave_lds_fence.
+// either side of zero) and the merges of the shards' blocks, one per call.  Included by tvz_match.hip only.  From
+// tvz_match_kernels.h: Row, load_row; from tvz_tol_kernels.h: ts_tol_sort_kernel (the batch's queries sorted
+// numerically, NaNs dropped, qm = the non-NaN count) and the sweep's block count (tol_topk_max_blocks); from
+// tvz_wave.h: wave_lds_fence.
 //
 // Contract (include/tvz.h): votes and bins are tvz_align's - the pair (row key c, query value x) votes into
 //   d = floor((c - x) / eps + 0.5)      (one IEEE subtraction, one true division)
@@ -443,23 +444,27 @@ __global__ __launch_bounds__(kAlReduceBlock) void ts_alignw_reduce_kernel(
     al_reduce<AwHit>(AwHit::ConstParts{part_w, part_p, part_v}, n_lists, k, qm, lds_keys, totals, d_out);
 }
 
-// ---- the merge of the shards' blocks (tvz_align_topk_merge) ----------------------------------------------------
+// ---- the merge of the shards' blocks (tvz_align_topk_merge, tvz_align_wide_topk_merge) ---------------------------
 constexpr int kAlMergeBlock = 256;
 constexpr int kAlMergeWaves = kAlMergeBlock / 64;      // queries per block: a wave each
 constexpr int kAlMergeMaxLists = 16;                   // one n_hits per lane, far below a wave
 
-// gathered int32[n_lists][Q][k+1][4], every [k+1][4] block as al_reduce writes it (k rows ascending in the contract's
+// gathered int32[n_lists][Q][k+1][4], every [k+1][4] block as al_reduce<Hit> writes it (k rows ascending in Hit's
 // order, padding, then (-1, n_hits, 0, 0)) -> d_topk int32[Q][k][4], d_totals int32[Q].  One wave per query, no LDS,
 // no barrier.  A block row does not carry its order word - the score depends on nv, the query's count of non-NaN
 // values, which no block holds - so the wave counts nv from the query itself and rebuilds the hit with the sweep's
-// expressions (AlHit::make); a row with video_id < 0 is padding wherever it stands, and so is one whose u = nv +
-// row_len - v would be 0 (nothing divides by zero): neither is live.  The lists are SORTED BY CONTRACT: that is the
-// precondition of the fold's early exit (al_take_live, as al_take).  Equal hits are identical rows and are all kept.  d_totals[q] = the lists' n_hits summed in 64 bits, clamped to INT32_MAX.  Refused - all k rows
-// padding, d_totals[q] = INT32_MIN - when a list's n_hits is negative (INT32_MIN: a rank refused the query) or the
-// query is longer than kAlMaxLen.  n_lists <= kAlMergeMaxLists, k <= kAlMaxK; gathered and d_topk 16-byte aligned.
-__global__ __launch_bounds__(kAlMergeBlock) void ts_align_topk_merge_kernel(
-    const int32_t *__restrict__ gathered, int32_t n_lists, int32_t Q, int32_t k, const double *__restrict__ queries,
-    const int64_t *__restrict__ q_offsets, int32_t *__restrict__ d_topk, int32_t *__restrict__ d_totals) {
+// expressions (Hit::make; contain: the wide call's TVZ_ALIGN_CONTAIN, u = min(nv, row_len) instead of nv + row_len -
+// v); a row with video_id < 0 is padding wherever it stands, and so is one whose u would be 0 (nothing divides by
+// zero): neither is live.  The lists are SORTED BY CONTRACT, in the order of the SAME score kind: that is the
+// precondition of the fold's early exit (al_take_live, as al_take).  Equal hits are identical rows and are all kept.
+// d_totals[q] = the lists' n_hits summed in 64 bits, clamped to INT32_MAX.  Refused - all k rows padding, d_totals[q]
+// = INT32_MIN - when a list's n_hits is negative (INT32_MIN: a rank refused the query) or the query is longer than
+// kAlMaxLen.  n_lists <= kAlMergeMaxLists, k <= kAlMaxK; gathered and d_topk 16-byte aligned.  AlHit's word holds a
+// bin of 12 bits: blocks with a bin outside +-2047 (the wide call's) are AwHit's alone.
+template <class Hit>
+__device__ __forceinline__ void al_merge_blocks(const int32_t *__restrict__ gathered, int32_t n_lists, int32_t Q, int32_t k,
+                                                const double *__restrict__ queries, const int64_t *__restrict__ q_offsets,
+                                                bool contain, int32_t *__restrict__ d_topk, int32_t *__restrict__ d_totals) {
     const int lane = threadIdx.x & 63;
     const int q = blockIdx.x * kAlMergeWaves + (threadIdx.x >> 6);
     if (q >= Q) return;                                            // wave-uniform
@@ -472,7 +477,7 @@ __global__ __launch_bounds__(kAlMergeBlock) void ts_align_topk_merge_kernel(
     const int64_t qo = q_offsets[q];
     const int64_t len = q_offsets[q + 1] - qo;
     const bool refused = __ballot(nh < 0) != 0ull || len > kAlMaxLen;
-    AlHit kept = AlHit::pad();
+    Hit kept = Hit::pad();
     if (!refused) {
         int32_t nvl = 0;
         for (int64_t e = lane; e < len; e += 64) {
@@ -493,15 +498,29 @@ __global__ __launch_bounds__(kAlMergeBlock) void ts_align_topk_merge_kernel(
                 const uint32_t rl = (uint32_t)row[j].y, votes = (uint32_t)row[j].w;
                 uint32_t v = votes < nv ? votes : nv;
                 v = v < rl ? v : rl;
-                const uint32_t u = nv + rl - v;
+                const uint32_t u = contain ? (nv < rl ? nv : rl) : nv + rl - v;
                 const bool hit = row[j].x >= 0 && u != 0u;
                 const uint32_t score = hit ? (v << 20) / u : 0u;   // v <= nv <= 4095: the shift fits 32 bits
-                al_take_live(kept, AlHit::make(score, row[j].x, row[j].z, rl, votes), __ballot(hit), k, lane);
+                al_take_live(kept, Hit::make(score, row[j].x, row[j].z, rl, votes), __ballot(hit), k, lane);
             }
         }
     }
     if (lane < k) reinterpret_cast<int4 *>(d_topk)[(int64_t)q * k + lane] = kept.row();
     if (lane == 0) d_totals[q] = refused ? INT32_MIN : (int32_t)(total > INT32_MAX ? INT32_MAX : total);
+}
+
+// The two entry points only forward.
+__global__ __launch_bounds__(kAlMergeBlock) void ts_align_topk_merge_kernel(
+    const int32_t *__restrict__ gathered, int32_t n_lists, int32_t Q, int32_t k, const double *__restrict__ queries,
+    const int64_t *__restrict__ q_offsets, int32_t *__restrict__ d_topk, int32_t *__restrict__ d_totals) {
+    al_merge_blocks<AlHit>(gathered, n_lists, Q, k, queries, q_offsets, /* contain */ false, d_topk, d_totals);
+}
+
+__global__ __launch_bounds__(kAlMergeBlock) void ts_alignw_merge_kernel(
+    const int32_t *__restrict__ gathered, int32_t n_lists, int32_t Q, int32_t k, uint32_t flags,
+    const double *__restrict__ queries, const int64_t *__restrict__ q_offsets, int32_t *__restrict__ d_topk,
+    int32_t *__restrict__ d_totals) {
+    al_merge_blocks<AwHit>(gathered, n_lists, Q, k, queries, q_offsets, (flags & kAwContain) != 0u, d_topk, d_totals);
 }
 
 }  // namespace

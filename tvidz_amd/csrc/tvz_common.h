@@ -92,6 +92,12 @@ int tvz_match_topk_local(tvz_corpus *c, const Batch &b, int32_t cap, int32_t k, 
 // The tolerant counterpart (tvz_match.hip): the sweep keeps the k best itself.
 int tvz_match_tol_topk_local(tvz_corpus *c, const Batch &b, double tol, int32_t k, int32_t *d_out, Workspace ws,
                              int32_t n_ranks, void *hip_stream, ShardBlocks *blocks);
+// ... and at any shift (tvz_align_wide_topk; n_ranks >= 1: tvz_align_wide_topk_sharded's workspace).
+int tvz_align_wide_topk_local(tvz_corpus *c, const Batch &b, const AlignCall &a, uint32_t flags, int32_t k, int32_t *d_out,
+                              Workspace ws, int32_t n_ranks, void *hip_stream, ShardBlocks *blocks);
 // The alignment top-k (tvz_match.hip): n_ranks = 0 is tvz_align_topk itself, whose workspace holds no blocks.
 int tvz_align_topk_local(tvz_corpus *c, const Batch &b, const AlignCall &a, int32_t k, int32_t *d_out, Workspace ws,
                          int32_t n_ranks, void *hip_stream, ShardBlocks *blocks);
+// ... and at any shift (tvz_align_wide_topk; n_ranks >= 1: tvz_align_wide_topk_sharded's workspace).
+int tvz_align_wide_topk_local(tvz_corpus *c, const Batch &b, const AlignCall &a, uint32_t flags, int32_t k, int32_t *d_out,
+                              Workspace ws, int32_t n_ranks, void *hip_stream, ShardBlocks *blocks);

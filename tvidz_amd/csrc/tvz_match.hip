@@ -2032,7 +2032,7 @@ size_t align_topk_ws_bytes(int32_t Q, int64_t keys, int32_t k, bool wide, int32_
     return cv.fixed() + tol_ws_bytes(Q, keys);
 }
 
-// what tvz_align_topk_merge refuses, apart from its pointers
+// what tvz_align_topk_merge and tvz_align_wide_topk_merge refuse, apart from their pointers and flags
 int check_align_merge(int32_t n_lists, int32_t k) {
     if (n_lists < 1 || n_lists > kAlMergeMaxLists)
         return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment top-k merge: %d lists outside 1..%d", (int)n_lists, kAlMergeMaxLists);
@@ -2048,20 +2048,23 @@ bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 
 struct AlignTopkForm {
     bool wide;
     const char *what, *sizer;        // the call in messages; the sizing function the workspace message names
+    const char *sharded_sizer;       // ... and the one it names for the sharded form (n_ranks >= 1)
     int32_t max_bins;                // 2B + 1 at most
     const char *wide_limit;          // check_align_bins
     uint32_t flags;                  // the permitted ones
     int static_lds;                  // of the sweep
 };
-constexpr AlignTopkForm kAlignBounded{false, "alignment top-k", "tvz_align_topk_workspace_bytes", kAlignMaxBins, nullptr, 0u,
+constexpr AlignTopkForm kAlignBounded{false, "alignment top-k", "tvz_align_topk_workspace_bytes",
+                                      "tvz_align_topk_sharded_workspace_bytes", kAlignMaxBins, nullptr, 0u,
                                       al_static_lds<AlHit>()};
-constexpr AlignTopkForm kAlignWide{true, "wide alignment top-k", "tvz_align_wide_topk_workspace_bytes", 2 * kAwMaxB + 1,
-                                   "TVZ_ALIGN_WIDE_MAX_B", kAwContain, al_static_lds<AwHit>()};
+constexpr AlignTopkForm kAlignWide{true, "wide alignment top-k", "tvz_align_wide_topk_workspace_bytes",
+                                   "tvz_align_wide_topk_sharded_workspace_bytes", 2 * kAwMaxB + 1, "TVZ_ALIGN_WIDE_MAX_B",
+                                   kAwContain, al_static_lds<AwHit>()};
 
 // Both calls: sort -> sweep that keeps the k best -> per-query selection.  n_ranks = 0: d_out is the caller's.
-// n_ranks >= 1 (bounded only): the workspace also holds the local block and n_ranks gathered ones
-// (tvz_align_topk_sharded_workspace_bytes); d_out = NULL writes the block into the workspace's own, and `blocks` is
-// told where it went and where the all-gather's target is.
+// n_ranks >= 1: the workspace also holds the local block and n_ranks gathered ones (the form's sharded sizing
+// function); d_out = NULL writes the block into the workspace's own, and `blocks` is told where it went and where the
+// all-gather's target is.
 int align_topk_run(const AlignTopkForm &f, tvz_corpus *c, const Batch &b, const AlignCall &a, uint32_t flags, int32_t k,
                    int32_t *d_out, Workspace ws, int32_t n_ranks, void *hip_stream, ShardBlocks *blocks) {
     const int32_t Q = b.Q, max_query_len = b.max_query_len;
@@ -2095,7 +2098,7 @@ int align_topk_run(const AlignTopkForm &f, tvz_corpus *c, const Batch &b, const 
     // (the sorted positions are unused here)
     TolCall t;
     if (int rc = tol_prelude(c, b, TolFront{cv, cv.fixed(), w.totals, f.what,
-                                            n_ranks > 0 ? "tvz_align_topk_sharded_workspace_bytes" : f.sizer},
+                                            n_ranks > 0 ? f.sharded_sizer : f.sizer},
                              ws.p ? ws.bytes : 0, max_query_len, st, args_ok, t))
         return rc;
     const int64_t n_rows = t.n_rows;
@@ -2124,10 +2127,15 @@ int align_topk_run(const AlignTopkForm &f, tvz_corpus *c, const Batch &b, const 
 
 }  // namespace
 
-// used by tvz_comm.hip (same shared object, not exported): the bounded call, with the sharded forms' blocks
+// used by tvz_comm.hip (same shared object, not exported): either call, with the sharded forms' blocks
 int tvz_align_topk_local(tvz_corpus *c, const Batch &b, const AlignCall &a, int32_t k, int32_t *d_out, Workspace ws,
                          int32_t n_ranks, void *hip_stream, ShardBlocks *blocks) {
     return align_topk_run(kAlignBounded, c, b, a, 0u, k, d_out, ws, n_ranks, hip_stream, blocks);
+}
+
+int tvz_align_wide_topk_local(tvz_corpus *c, const Batch &b, const AlignCall &a, uint32_t flags, int32_t k, int32_t *d_out,
+                              Workspace ws, int32_t n_ranks, void *hip_stream, ShardBlocks *blocks) {
+    return align_topk_run(kAlignWide, c, b, a, flags, k, d_out, ws, n_ranks, hip_stream, blocks);
 }
 
 static int tvz_align_topk_impl(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
@@ -2139,53 +2147,59 @@ static int tvz_align_topk_impl(tvz_corpus *c, const double *d_queries, const int
                                 Workspace{d_workspace, workspace_bytes}, 0, hip_stream, nullptr);
 }
 
-static int tvz_align_topk_merge_impl(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t k,
-                                     const double *d_queries, const int64_t *d_q_offsets, int32_t *d_topk,
-                                     int32_t *d_totals, void *hip_stream) {
+static int tvz_align_wide_topk_impl(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
+                                    int32_t max_query_len, double eps, double max_offset, int32_t min_votes,
+                                    int32_t min_score, uint32_t flags, const int32_t *d_exclude_ids, int32_t k,
+                                    int32_t *d_out, void *d_workspace, size_t workspace_bytes, void *hip_stream) {
+    return tvz_align_wide_topk_local(c, Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids},
+                                     AlignCall{eps, max_offset, min_votes, min_score}, flags, k, d_out,
+                                     Workspace{d_workspace, workspace_bytes}, 0, hip_stream, nullptr);
+}
+
+// The merge of either call's blocks (tvz_align_topk_merge: f = kAlignBounded, flags = 0; tvz_align_wide_topk_merge).
+static int align_merge_impl(const AlignTopkForm &f, const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t k,
+                            uint32_t flags, const double *d_queries, const int64_t *d_q_offsets, int32_t *d_topk,
+                            int32_t *d_totals, void *hip_stream) {
     TVZ_REQUIRE(Q >= 0, "Q=%d is negative", (int)Q);
     if (int rc = check_align_merge(n_lists, k)) return rc;
+    TVZ_REQUIRE((flags & ~f.flags) == 0u, "%s merge: unknown flag bits 0x%x", f.what, (unsigned)(flags & ~f.flags));
     if (Q == 0) return TVZ_OK;
     TVZ_REQUIRE(d_gathered && d_queries && d_q_offsets && d_topk && d_totals, "NULL argument");
     TVZ_REQUIRE(aligned16(d_gathered) && aligned16(d_topk), "alignment top-k merge: the blocks and d_topk must be 16-byte aligned");
-    hipLaunchKernelGGL(ts_align_topk_merge_kernel, dim3((unsigned)tvz::ceil_div(Q, kAlMergeWaves)), dim3(kAlMergeBlock), 0,
-                       reinterpret_cast<hipStream_t>(hip_stream), d_gathered, n_lists, Q, k, d_queries, d_q_offsets, d_topk,
-                       d_totals);
+    const dim3 grid((unsigned)tvz::ceil_div(Q, kAlMergeWaves));
+    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+    if (f.wide)
+        hipLaunchKernelGGL(ts_alignw_merge_kernel, grid, dim3(kAlMergeBlock), 0, st, d_gathered, n_lists, Q, k, flags,
+                           d_queries, d_q_offsets, d_topk, d_totals);
+    else
+        hipLaunchKernelGGL(ts_align_topk_merge_kernel, grid, dim3(kAlMergeBlock), 0, st, d_gathered, n_lists, Q, k, d_queries,
+                           d_q_offsets, d_topk, d_totals);
     return launched();
 }
 
-static int tvz_align_topk_shards_impl(tvz_corpus *const *shards, int32_t n_shards, const double *d_queries,
-                                      const int64_t *d_q_offsets, int32_t Q, int32_t max_query_len, double eps,
-                                      double max_offset, int32_t min_votes, int32_t min_score,
-                                      const int32_t *d_exclude_ids, int32_t k, int32_t *d_blocks, int32_t *d_topk,
-                                      int32_t *d_totals, void *d_workspace, size_t workspace_bytes, void *hip_stream) {
+// The shards of one process, for either call (tvz_align_topk_shards: f = kAlignBounded, flags = 0;
+// tvz_align_wide_topk_shards).
+static int align_shards_impl(const AlignTopkForm &f, tvz_corpus *const *shards, int32_t n_shards, const Batch &b,
+                             const AlignCall &a, uint32_t flags, int32_t k, int32_t *d_blocks, int32_t *d_topk,
+                             int32_t *d_totals, Workspace ws, void *hip_stream) {
+    const int32_t Q = b.Q;
     TVZ_REQUIRE(shards != nullptr && n_shards >= 1, "no shards");
     TVZ_REQUIRE(Q >= 0, "Q=%d is negative", (int)Q);
     if (int rc = check_align_merge(n_shards, k)) return rc;
     for (int32_t r = 0; r < n_shards; ++r)
         TVZ_REQUIRE(shards[r] != nullptr && shards[r]->device == shards[0]->device,
                     "shard %d is NULL or on another device than shard 0", r);
-    TVZ_REQUIRE(Q == 0 || (d_blocks && d_topk && d_totals && d_queries && d_q_offsets), "NULL argument");
+    TVZ_REQUIRE(Q == 0 || (d_blocks && d_topk && d_totals && b.d_queries && b.d_q_offsets), "NULL argument");
     TVZ_REQUIRE(aligned16(d_blocks) && aligned16(d_topk), "alignment top-k merge: the blocks and d_topk must be 16-byte aligned");
     if (Q == 0) return TVZ_OK;
-    // every handle's call makes the same checks of the same arguments: what one refuses, the first one refuses,
-    // before anything is enqueued
-    const Batch b{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids};
-    const AlignCall a{eps, max_offset, min_votes, min_score};
+    // every handle's call makes the same checks of the same arguments (the flags among them): what one refuses, the
+    // first one refuses, before anything is enqueued
     for (int32_t r = 0; r < n_shards; ++r)
-        if (int rc = tvz_align_topk_local(shards[r], b, a, k, d_blocks + (size_t)r * (size_t)Q * (size_t)(k + 1) * 4,
-                                          Workspace{d_workspace, workspace_bytes}, 0, hip_stream, nullptr))
+        if (int rc = align_topk_run(f, shards[r], b, a, flags, k, d_blocks + (size_t)r * (size_t)Q * (size_t)(k + 1) * 4, ws, 0,
+                                    hip_stream, nullptr))
             return rc;
     DeviceGuard dg(shards[0]->device);
-    return tvz_align_topk_merge_impl(d_blocks, n_shards, Q, k, d_queries, d_q_offsets, d_topk, d_totals, hip_stream);
-}
-
-static int tvz_align_wide_topk_impl(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
-                                    int32_t max_query_len, double eps, double max_offset, int32_t min_votes,
-                                    int32_t min_score, uint32_t flags, const int32_t *d_exclude_ids, int32_t k,
-                                    int32_t *d_out, void *d_workspace, size_t workspace_bytes, void *hip_stream) {
-    return align_topk_run(kAlignWide, c, Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids},
-                          AlignCall{eps, max_offset, min_votes, min_score}, flags, k, d_out,
-                          Workspace{d_workspace, workspace_bytes}, 0, hip_stream, nullptr);
+    return align_merge_impl(f, d_blocks, n_shards, Q, k, flags, b.d_queries, b.d_q_offsets, d_topk, d_totals, hip_stream);
 }
 
 #ifdef TVZ_IX_STAMP
@@ -2393,7 +2407,8 @@ TVZ_EXPORT int tvz_align_wide_topk(tvz_corpus *c, const double *d_queries, const
 TVZ_EXPORT int tvz_align_topk_merge(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t k,
                                     const double *d_queries, const int64_t *d_q_offsets, int32_t *d_topk,
                                     int32_t *d_totals, void *hip_stream) {
-    TVZ_GUARDED(tvz_align_topk_merge_impl(d_gathered, n_lists, Q, k, d_queries, d_q_offsets, d_topk, d_totals, hip_stream));
+    TVZ_GUARDED(align_merge_impl(kAlignBounded, d_gathered, n_lists, Q, k, 0u, d_queries, d_q_offsets, d_topk, d_totals,
+                                 hip_stream));
 }
 
 TVZ_EXPORT int tvz_align_topk_shards(tvz_corpus *const *shards, int32_t n_shards, const double *d_queries,
@@ -2401,9 +2416,35 @@ TVZ_EXPORT int tvz_align_topk_shards(tvz_corpus *const *shards, int32_t n_shards
                                      double max_offset, int32_t min_votes, int32_t min_score,
                                      const int32_t *d_exclude_ids, int32_t k, int32_t *d_blocks, int32_t *d_topk,
                                      int32_t *d_totals, void *d_workspace, size_t workspace_bytes, void *hip_stream) {
-    TVZ_GUARDED(tvz_align_topk_shards_impl(shards, n_shards, d_queries, d_q_offsets, Q, max_query_len, eps, max_offset,
-                                           min_votes, min_score, d_exclude_ids, k, d_blocks, d_topk, d_totals, d_workspace,
-                                           workspace_bytes, hip_stream));
+    TVZ_GUARDED(align_shards_impl(kAlignBounded, shards, n_shards,
+                                  Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids},
+                                  AlignCall{eps, max_offset, min_votes, min_score}, 0u, k, d_blocks, d_topk, d_totals,
+                                  Workspace{d_workspace, workspace_bytes}, hip_stream));
+}
+
+TVZ_EXPORT int tvz_align_wide_topk_merge(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t k, uint32_t flags,
+                                         const double *d_queries, const int64_t *d_q_offsets, int32_t *d_topk,
+                                         int32_t *d_totals, void *hip_stream) {
+    TVZ_GUARDED(align_merge_impl(kAlignWide, d_gathered, n_lists, Q, k, flags, d_queries, d_q_offsets, d_topk, d_totals,
+                                 hip_stream));
+}
+
+TVZ_EXPORT int tvz_align_wide_topk_shards(tvz_corpus *const *shards, int32_t n_shards, const double *d_queries,
+                                          const int64_t *d_q_offsets, int32_t Q, int32_t max_query_len, double eps,
+                                          double max_offset, int32_t min_votes, int32_t min_score, uint32_t flags,
+                                          const int32_t *d_exclude_ids, int32_t k, int32_t *d_blocks, int32_t *d_topk,
+                                          int32_t *d_totals, void *d_workspace, size_t workspace_bytes, void *hip_stream) {
+    TVZ_GUARDED(align_shards_impl(kAlignWide, shards, n_shards,
+                                  Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids},
+                                  AlignCall{eps, max_offset, min_votes, min_score}, flags, k, d_blocks, d_topk, d_totals,
+                                  Workspace{d_workspace, workspace_bytes}, hip_stream));
+}
+
+TVZ_EXPORT size_t tvz_align_wide_topk_sharded_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys,
+                                                              int32_t k, int32_t n_ranks) {
+    if (Q < 0 || max_query_len < 0 || total_query_keys < 0 || k < 1) return 0;
+    const int64_t keys = total_query_keys > 0 ? total_query_keys : (int64_t)Q * max_query_len;
+    return align_topk_ws_bytes(Q, std::max<int64_t>(keys, max_query_len), k, true, std::max(n_ranks, 1));
 }
 
 TVZ_EXPORT int tvz_find_duplicates_tol(tvz_corpus *c, const double *h_query, int64_t n, double tol, int32_t min_match,

@@ -116,7 +116,7 @@ class Inspector:
             if not hasattr(getattr(store, "corpus", None), "align_wide_topk"):
                 raise RuntimeError(f"near_any_offset=True: the store's corpus "
                                    f"({type(getattr(store, 'corpus', None)).__name__}) has no align_wide_topk; "
-                                   "use a DeviceCorpus (the sharded forms keep the bounded search)")
+                                   "use a DeviceCorpus, a service.ShardedCorpus or a service.RankCorpus")
         # opt-in, never the default: duplicates by the TOLERANT count (include/tvz.h tvz_find_duplicates_tol)
         # instead of the reference's exact float64 equality; the verdict, the truncation at kth and the stored
         # duplicates all follow it.  Refused here, before any upload, where the store's corpus cannot do it.

@@ -29,6 +29,11 @@ The opt-in near-duplicate search (`align_topk`, Inspector(near_top_k=K), `--near
 ShardedCorpus runs tvz_align_topk_shards (every shard in turn + the device merge, one call, one copy back), RankCorpus
 sends ASK_NEAR through the tick to `matcher.align_topk`.  The RCCL form (tvz_align_topk_sharded) has run on hardware
 at world size 1 only; tests/test_align_topk_sharded_cpu.py runs the exchange at world sizes 2 and 3 on gloo.
+
+So has the search at any shift (`align_wide_topk`, Inspector(near_any_offset=True), `--near-any-offset`): ShardedCorpus
+runs tvz_align_wide_topk_shards, RankCorpus sends ASK_NEAR_WIDE through the tick to `matcher.align_wide_topk`.  Its RCCL
+form (tvz_align_wide_topk_sharded) too has run on hardware at world size 1 only;
+tests/test_align_wide_sharded_cpu.py runs the exchange at world sizes 2 and 3 on gloo.
 """
 from __future__ import annotations
 
@@ -274,24 +279,42 @@ class ShardedCorpus:
         More than 16 shards (the merge takes up to 16 lists): one such call per group of 16, the groups' answers put
         together as blocks again on the device - k sorted rows and a total each - and merged by one
         tvz_align_topk_merge; still one copy back, same answer."""
+        return self._near_shards(tc.align_topk_shards, tc.align_topk_merge, tc.align_topk_workspace_bytes, queries, k,
+                                 exclude_ids, max_query_len, {},
+                                 dict(eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score))
+
+    supports_align_wide = True
+
+    def align_wide_topk(self, queries, *, eps: float, max_offset=None, k: int = 16, min_votes: int = 1,
+                        min_score: int = 0, contain: bool = False, exclude_ids=None, max_query_len=None):
+        """DeviceCorpus.align_wide_topk over every shard - align_topk at any shift (`max_offset=None`: the widest),
+        scored by the containment with `contain`: ONE library call (tvz_align_wide_topk_shards), ONE copy back; more
+        than 16 shards are grouped and re-merged by tvz_align_wide_topk_merge, as align_topk does."""
+        return self._near_shards(tc.align_wide_topk_shards, tc.align_wide_topk_merge, tc.align_wide_topk_workspace_bytes,
+                                 queries, k, exclude_ids, max_query_len, dict(contain=contain),
+                                 dict(eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score,
+                                      contain=contain))
+
+    def _near_shards(self, shards_call, merge_call, sizer, queries, k, exclude_ids, max_query_len, merge_kw, kw):
+        """What align_topk and align_wide_topk share: the inputs, the calling thread's workspace (`sizer`), one
+        `shards_call` per group of 16 shards, the groups' `merge_call`, the one copy back."""
         dev = self.dev
         d_q, d_off, Q, max_query_len, d_ex = tc.align_inputs(queries, exclude_ids, max_query_len, dev)
-        ws = tc.thread_workspace(self._near_tls, tc.align_topk_workspace_bytes(Q, max_query_len, d_q.numel(), k), dev)
-        kw = dict(eps=eps, max_offset=max_offset, k=k, workspace=ws, min_votes=min_votes, min_score=min_score,
-                  d_exclude_ids=d_ex)
+        ws = tc.thread_workspace(self._near_tls, sizer(Q, max_query_len, d_q.numel(), k), dev)
+        kw = dict(kw, k=k, workspace=ws, d_exclude_ids=d_ex)
         with torch.cuda.device(dev):
             groups = [self.shards[i:i + 16] for i in range(0, self.R, 16)]      # the merge takes up to 16 lists
             if len(groups) == 1:
-                _, rows, totals = tc.align_topk_shards(groups[0], d_q, d_off, max_query_len, **kw)
+                _, rows, totals = shards_call(groups[0], d_q, d_off, max_query_len, **kw)
             else:
                 # more shards than one merge takes: every group's answer is a block again - its k rows, then its total
                 blocks = torch.zeros((len(groups), Q, k + 1, 4), dtype=torch.int32, device=dev)
                 for g, part in enumerate(groups):
-                    _, rows, totals = tc.align_topk_shards(part, d_q, d_off, max_query_len, **kw)
+                    _, rows, totals = shards_call(part, d_q, d_off, max_query_len, **kw)
                     blocks[g, :, :k] = rows
                     blocks[g, :, k, 0] = -1
                     blocks[g, :, k, 1] = totals
-                rows, totals = tc.align_topk_merge(blocks, k, d_q, d_off)
+                rows, totals = merge_call(blocks, k, d_q, d_off, **merge_kw)
             rows, totals = _to_host(rows, totals)
         return np.ascontiguousarray(rows), np.ascontiguousarray(totals)
 
@@ -346,8 +369,8 @@ class ShardedCorpus:
         return [(merged[i], int(totals[i])) for i in range(Q)]
 
 
-ASK_TOPK, ASK_EXACT, ASK_NEAR = 0, 1, 2
-ASK_HEADER = 10                # (len, exclude, min_match, kind, tolerance, eps, max_offset, k, min_votes, min_score)
+ASK_TOPK, ASK_EXACT, ASK_NEAR, ASK_NEAR_WIDE = 0, 1, 2, 3
+ASK_HEADER = 11                # (len, exclude, min_match, kind, tolerance, eps, max_offset, k, min_votes, min_score, flags)
 NEAR_MAX_K, NEAR_MAX_BINS, NEAR_SCORE_ONE = tc.ALIGN_TOPK_MAX_K, tc.ALIGN_TOPK_MAX_BINS, tc.ALIGN_SCORE_ONE
 
 
@@ -375,10 +398,27 @@ def check_near_params(eps, max_offset, k, min_votes, min_score) -> tuple:
     return eps, max_offset, int(k), int(min_votes), int(min_score)
 
 
+def check_near_wide_params(eps, max_offset, k, min_votes, min_score, contain=False) -> tuple:
+    """check_near_params for tvz_align_wide_topk: `max_offset=None` is the widest, up to tc.ALIGN_WIDE_MAX_B bins on
+    either side; -> the five values and the call's flags, as an ASK_NEAR_WIDE carries them."""
+    eps = float(eps)
+    if not (0.0 < eps <= sys.float_info.max):
+        raise ValueError(f"eps must be finite and > 0, got {eps!r}")
+    max_offset = tc.ALIGN_WIDE_MAX_B * eps if max_offset is None else float(max_offset)
+    if not (0.0 <= max_offset <= sys.float_info.max):
+        raise ValueError(f"max_offset must be finite and >= 0, got {max_offset!r}")
+    if not np.floor(max_offset / eps + 0.5) <= tc.ALIGN_WIDE_MAX_B:
+        raise ValueError(f"max_offset / eps = {max_offset / eps:.0f} is more than {tc.ALIGN_WIDE_MAX_B} bins "
+                         "(ALIGN_WIDE_MAX_B)")
+    # (at a single bin the bounded rule holds too: the other three are the bounded call's)
+    _, _, k, min_votes, min_score = check_near_params(eps, 0.0, k, min_votes, min_score)
+    return eps, max_offset, k, min_votes, min_score, tc.ALIGN_CONTAIN if contain else 0
+
+
 class _Asks(NamedTuple):
     """The asks of every rank in one tick, un-padded and in the same order on every rank (rank-major): ask `a` is ask
     `ii[a]` of rank `rr[a]`, `mine` marks this rank's; `near` holds a near ask's five parameters [n, 5], `keys` the
-    gathered, still padded timestamps [world, Qcap, Lcap]."""
+    gathered, still padded timestamps [world, Qcap, Lcap], `flags` a wide near ask's flags [n]."""
     rr: np.ndarray
     ii: np.ndarray
     lens: np.ndarray
@@ -389,6 +429,7 @@ class _Asks(NamedTuple):
     near: np.ndarray
     keys: np.ndarray
     mine: np.ndarray
+    flags: np.ndarray
 
 
 class RankCorpus:
@@ -417,6 +458,10 @@ class RankCorpus:
                  all-gather -> the merge by the contract's order).  Its five parameters (eps, max_offset, k, min_votes,
                  min_score) travel in the ask's header; asks that agree in all five share one batched call per tick.
                  Nothing is sent unless somebody asks: a service without --near-top-k never names it.
+      ASK_NEAR_WIDE  the same search at any shift (`align_wide_topk`, Inspector(near_any_offset=True)), through
+                 `matcher.align_wide_topk`: the header carries the call's flags (the score kind) next to the five
+                 parameters, and asks that agree in all six share one batched call.  Sent only by a service started
+                 with --near-any-offset.
 
     `shard`: this rank's DeviceCorpus (or a stand-in with upload/upsert/clear/find_duplicates);
     `matcher.match_topk(d_q, d_off, max_len, min_match, d_excl) -> (merged [Q,k,3], totals [Q])`;
@@ -518,6 +563,27 @@ class RankCorpus:
         if not (hasattr(self.matcher, "align_topk") and getattr(self.matcher, "supports_align_topk", True)):
             raise RuntimeError(f"this rank corpus has no near-duplicate search: its matcher "
                                f"{type(self.matcher).__name__} has no align_topk")
+        return self._near_asks(ASK_NEAR, near, queries, exclude_ids, max_query_len)
+
+    def align_wide_topk(self, queries, *, eps: float, max_offset=None, k: int = 16, min_votes: int = 1,
+                        min_score: int = 0, contain: bool = False, exclude_ids=None, max_query_len=None):
+        """DeviceCorpus.align_wide_topk over the shards of all ranks - align_topk at any shift (`max_offset=None`: the
+        widest), scored by the containment with `contain`; order: corpus.align_wide_order_key.  Every query is one
+        ASK_NEAR_WIDE of the next tick; refused HERE what the library would refuse (ValueError; more than
+        ALIGN_WIDE_MAX_B bins among it), RuntimeError for a matcher without align_wide_topk."""
+        near = check_near_wide_params(eps, max_offset, k, min_votes, min_score, contain)
+        if not (hasattr(self.matcher, "align_wide_topk") and getattr(self.matcher, "supports_align_wide", True)):
+            raise RuntimeError(f"this rank corpus has no near-duplicate search at any shift: its matcher "
+                               f"{type(self.matcher).__name__} has no align_wide_topk")
+        return self._near_asks(ASK_NEAR_WIDE, near, queries, exclude_ids, max_query_len)
+
+    @property
+    def supports_align_wide(self) -> bool:
+        return hasattr(self.matcher, "align_wide_topk") and bool(getattr(self.matcher, "supports_align_wide", True))
+
+    def _near_asks(self, kind, near, queries, exclude_ids, max_query_len):
+        """The queries of one align_topk / align_wide_topk as asks of `kind` with the checked parameters `near` (k is
+        its third) -> (rows int32 [Q,k,4], totals int32 [Q])."""
         queries = [np.ascontiguousarray(np.asarray(q, dtype=np.float64).reshape(-1)) for q in queries]
         limit = MAX_BATCH_LEN if max_query_len is None else min(int(max_query_len), MAX_BATCH_LEN)
         excl = [-1] * len(queries) if exclude_ids is None else [int(e) for e in np.asarray(exclude_ids).reshape(-1)]
@@ -528,7 +594,7 @@ class RankCorpus:
         rows[:, :, 0] = -1
         totals = np.full(len(queries), -(1 << 31), dtype=np.int64)                 # ALIGN_REFUSED unless answered
         sent = [i for i, q in enumerate(queries) if q.size <= limit]
-        for i, (r, t) in zip(sent, self._ask_all([(queries[i], 0, excl[i], ASK_NEAR, 0.0, near) for i in sent])):
+        for i, (r, t) in zip(sent, self._ask_all([(queries[i], 0, excl[i], kind, 0.0, near) for i in sent])):
             rows[i], totals[i] = r, t
         return rows, totals.astype(np.int32)
 
@@ -613,32 +679,34 @@ class RankCorpus:
 
     def _exchange_and_answer(self, take, allmeta):
         """One busy tick.  The order of the collectives and of the matcher calls is the same on every rank: the asks'
-        exchange, one match_topk per (min_match, tolerance) and one align_topk per set of near parameters, each in
-        sorted order, then the exact asks' two gathers."""
+        exchange, one match_topk per (min_match, tolerance), one align_topk per set of near parameters and one
+        align_wide_topk per set of wide ones, each in sorted order, then the exact asks' two gathers."""
         asks = self._gather_asks(take, allmeta)
         self._answer_topk(asks, take)
         self._answer_near(asks, take)
+        self._answer_near_wide(asks, take)
         self._answer_exact(asks, take)
 
     def _gather_asks(self, take, allmeta) -> _Asks:
         Qcap, Lcap = int(allmeta[:, 0].max()), max(int(allmeta[:, 1].max()), 1)
         # the asks, padded to the largest rank's block, as ONE float64 block per rank:
         # [Qcap, ASK_HEADER + Lcap] = (len, exclude, min_match, kind, tolerance, and a near ask's eps, max_offset,
-        # k, min_votes, min_score | keys...); small integers are exact in float64, tolerance, eps and max_offset
-        # ARE float64
+        # k, min_votes, min_score, and a wide one's flags | keys...); small integers are exact in float64, tolerance,
+        # eps and max_offset ARE float64
         H = ASK_HEADER
         blk = np.zeros((Qcap, H + Lcap), dtype=np.float64)
         for i, (q, mm, ex, kind, _, tol, near) in enumerate(take):
             blk[i, 0], blk[i, 1], blk[i, 2], blk[i, 3], blk[i, 4] = len(q), ex, mm, kind, tol
             if near is not None:
-                blk[i, 5:H] = near
+                blk[i, 5:5 + len(near)] = near                                     # five values; six with a wide ask's flags
             blk[i, H:H + len(q)] = q
         g = self._gather(torch.from_numpy(blk).to(self.xdev)).cpu().numpy()       # [world, Qcap, H + Lcap]
         # the global batch, in the same order on every rank: rank-major; rows past a rank's count are padding
         valid = np.arange(Qcap)[None, :] < allmeta[:, 0][:, None]                  # [world, Qcap]
         rr, ii = np.nonzero(valid)
         lens, excl, min_match, kind = (g[rr, ii, c].astype(np.int64) for c in range(4))
-        return _Asks(rr, ii, lens, excl, min_match, kind, g[rr, ii, 4], g[rr, ii, 5:H], g[:, :, H:], rr == self.rank)
+        return _Asks(rr, ii, lens, excl, min_match, kind, g[rr, ii, 4], g[rr, ii, 5:10], g[:, :, H:], rr == self.rank,
+                     g[rr, ii, 10].astype(np.int64))
 
     def _answer_batch(self, asks: _Asks, take, sel, call) -> None:
         """The asks `sel` of the global batch as ONE batched matcher call, `call(d_q, d_off, max_len, d_excl) -> (rows
@@ -684,6 +752,17 @@ class RankCorpus:
             self._answer_batch(asks, take, np.flatnonzero(near & (asks.near == np.asarray(par)).all(axis=1)),
                                lambda d_q, d_off, max_len, d_ex: self.matcher.align_topk(d_q, d_off, max_len,
                                                                                          d_exclude_ids=d_ex, **kw))
+
+    def _answer_near_wide(self, asks: _Asks, take) -> None:
+        """Wide near asks: as _answer_near, one batched matcher.align_wide_topk per (the five parameters, flags)."""
+        wide = asks.kind == ASK_NEAR_WIDE
+        for par in sorted(set(map(tuple, np.column_stack([asks.near[wide], asks.flags[wide]]).tolist()))):
+            kw = dict(eps=par[0], max_offset=par[1], k=int(par[2]), min_votes=int(par[3]), min_score=int(par[4]),
+                      contain=bool(int(par[5]) & tc.ALIGN_CONTAIN))
+            sel = np.flatnonzero(wide & (asks.near == np.asarray(par[:5])).all(axis=1) & (asks.flags == int(par[5])))
+            self._answer_batch(asks, take, sel,
+                               lambda d_q, d_off, max_len, d_ex: self.matcher.align_wide_topk(d_q, d_off, max_len,
+                                                                                              d_exclude_ids=d_ex, **kw))
 
     def _answer_exact(self, asks: _Asks, take) -> None:
         """Exact asks: every rank asks its own shard, counts and padded hit lists are all-gathered."""
@@ -795,8 +874,33 @@ def near_kwargs(a) -> dict:
     the flag builds its driver exactly as before."""
     if not getattr(a, "near_top_k", 0):
         return {}
-    return dict(near_duplicates=True, near_top_k=int(a.near_top_k), near_eps=float(a.near_eps),
-                near_max_offset=float(a.near_max_offset), near_jaccard=float(a.near_jaccard))
+    kw = dict(near_duplicates=True, near_top_k=int(a.near_top_k), near_eps=float(a.near_eps),
+              near_max_offset=float(a.near_max_offset), near_jaccard=float(a.near_jaccard))
+    # (each of the three only when it was given: a rank started without them builds its driver as before)
+    if getattr(a, "near_any_offset", False):
+        kw["near_any_offset"] = True
+    if getattr(a, "near_score", "jaccard") != "jaccard":
+        kw["near_score"] = str(a.near_score)
+    if int(getattr(a, "near_min_votes", 1)) != 1:
+        kw["near_min_votes"] = int(a.near_min_votes)
+    return kw
+
+
+def check_near_switches(near_top_k, near_any_offset=False, near_score="jaccard", near_min_votes=1) -> list:
+    """`--near-any-offset`, `--near-score`, `--near-min-votes`: Inspector's rules for them, before any rank starts ->
+    the switches as a rank process takes them (none where all three are at their defaults)."""
+    if near_score not in ("jaccard", "containment"):
+        raise ValueError(f"near_score must be 'jaccard' or 'containment', got {near_score!r}")
+    if int(near_min_votes) != near_min_votes or int(near_min_votes) < 1:
+        raise ValueError(f"near_min_votes must be an integer >= 1, got {near_min_votes!r}")
+    given = (["--near-any-offset"] if near_any_offset else []) + \
+        (["--near-score", near_score] if near_score != "jaccard" else []) + \
+        (["--near-min-votes", str(int(near_min_votes))] if int(near_min_votes) != 1 else [])
+    if given and not near_top_k:
+        raise ValueError(f"{given[0]} needs --near-top-k")
+    if near_score == "containment" and not near_any_offset:
+        raise ValueError("--near-score containment needs --near-any-offset (the score of tvz_align_wide_topk)")
+    return given
 
 
 def _hip_parts(rank: int, world: int, group, a):
@@ -960,7 +1064,8 @@ class RankService:
                  devices: Optional[List[int]] = None, k: int = 64, cap: int = 4096, workers: int = 16,
                  tick_s: float = 0.0005, env: Optional[dict] = None, ready_timeout: float = 300.0,
                  match_tolerance: float = 0.0, match_tol_index: float = 0.0, near_top_k: int = 0,
-                 near_eps: float = 1.0 / 30, near_max_offset: float = 30.0, near_jaccard: float = 0.8):
+                 near_eps: float = 1.0 / 30, near_max_offset: float = 30.0, near_jaccard: float = 0.8,
+                 near_any_offset: bool = False, near_score: str = "jaccard", near_min_votes: int = 1):
         import socket
         import subprocess
         from . import db
@@ -976,6 +1081,7 @@ class RankService:
                 raise ValueError(f"near_jaccard must be in 0..1, got {near_jaccard!r}")
             near = ["--near-top-k", str(int(near_top_k)), "--near-eps", repr(float(near_eps)),
                     "--near-max-offset", repr(float(near_max_offset)), "--near-jaccard", repr(float(near_jaccard))]
+        near += check_near_switches(near_top_k, near_any_offset, near_score, near_min_votes)
         db.create_schema(db_url)                                # once, before N processes open it side by side
         with socket.socket() as s:                              # a free rendezvous port
             s.bind(("127.0.0.1", 0))
@@ -1062,6 +1168,15 @@ def main(argv=None) -> int:  # pragma: no cover - exercised through subprocesses
     ap.add_argument("--near-eps", type=float, default=1.0 / 30, help="seconds per offset bin of the near-duplicate search")
     ap.add_argument("--near-max-offset", type=float, default=30.0, help="largest shift, in seconds, it looks for")
     ap.add_argument("--near-jaccard", type=float, default=0.8, help="tolerant Jaccard a reported near duplicate reaches")
+    ap.add_argument("--near-any-offset", action="store_true",
+                    help="the near-duplicate search at ANY shift (Inspector(near_any_offset=True)): 2^22 bins of "
+                         "--near-eps on either side instead of --near-max-offset, over all shards "
+                         "(tvz_align_wide_topk_sharded).  Needs --near-top-k")
+    ap.add_argument("--near-score", default="jaccard", choices=["jaccard", "containment"],
+                    help="containment scores a near duplicate by the share of the SHORTER side's cuts that align (the "
+                         "excerpt of a longer video); needs --near-any-offset")
+    ap.add_argument("--near-min-votes", type=int, default=1, metavar="N",
+                    help="aligned cuts a reported near duplicate needs at least.  Needs --near-top-k")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--rank", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--master-port", type=int, default=29500, help=argparse.SUPPRESS)
@@ -1074,7 +1189,8 @@ def main(argv=None) -> int:  # pragma: no cover - exercised through subprocesses
     svc = RankService(a.ranks, a.db, base_port=a.port, backend=a.backend, parts=a.parts, k=a.k, cap=a.cap,
                       workers=a.workers, tick_s=a.tick_s, match_tolerance=a.match_tolerance,
                       match_tol_index=a.match_tol_index, near_top_k=a.near_top_k, near_eps=a.near_eps,
-                      near_max_offset=a.near_max_offset, near_jaccard=a.near_jaccard)
+                      near_max_offset=a.near_max_offset, near_jaccard=a.near_jaccard,
+                      near_any_offset=a.near_any_offset, near_score=a.near_score, near_min_votes=a.near_min_votes)
 
     def monitor():
         while True:

@@ -72,6 +72,15 @@ class HipBackend:
     def align_topk_merge(self, gathered, k, d_q, d_off):
         return tc.align_topk_merge(gathered, k, d_q, d_off)
 
+    def local_align_wide_topk(self, d_q, d_off, max_len, eps, max_offset, k, min_votes, min_score, contain, d_excl):
+        """this rank's block of the alignment top-k at any shift (tvz_align_wide_topk): int32 [Q, k+1, 4]"""
+        return self.corpus.align_wide_topk_block(d_q, d_off, max_len, eps=eps, max_offset=max_offset, k=k,
+                                                 min_votes=min_votes, min_score=min_score, contain=contain,
+                                                 d_exclude_ids=d_excl)
+
+    def align_wide_topk_merge(self, gathered, k, d_q, d_off, contain):
+        return tc.align_wide_topk_merge(gathered, k, d_q, d_off, contain=contain)
+
 
 class ShardedMatcher:
     """rank-local shard + ONE all-gather of per-shard top-k (+ hit totals) + identical merge on
@@ -155,6 +164,23 @@ class ShardedMatcher:
     @property
     def supports_align_topk(self) -> bool:
         return hasattr(self.backend, "local_align_topk") and hasattr(self.backend, "align_topk_merge")
+
+    def align_wide_topk(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, eps: float,
+                        max_offset: Optional[float] = None, k: int, min_votes: int = 1, min_score: int = 0,
+                        contain: bool = False, d_exclude_ids: Optional[torch.Tensor] = None):
+        """align_topk at any shift (`max_offset=None`: the widest), scored by the containment with `contain`: the local
+        tvz_align_wide_topk block -> ONE all-gather -> the wide merge of the same score kind, identical on every rank."""
+        for name in ("local_align_wide_topk", "align_wide_topk_merge"):
+            if not hasattr(self.backend, name):
+                raise RuntimeError(f"{type(self.backend).__name__} has no {name}")
+        local = self.backend.local_align_wide_topk(d_queries, d_q_offsets, max_query_len, eps, max_offset, int(k),
+                                                   int(min_votes), int(min_score), bool(contain), d_exclude_ids)
+        gathered, _ = self._all_gather_blocks(local, async_op=False)
+        return self.backend.align_wide_topk_merge(gathered, k, d_queries, d_q_offsets, bool(contain))
+
+    @property
+    def supports_align_wide(self) -> bool:
+        return hasattr(self.backend, "local_align_wide_topk") and hasattr(self.backend, "align_wide_topk_merge")
 
 
 def make_comm(device: int, group=None):
@@ -312,19 +338,35 @@ class RcclShardedMatcher:
         streams; the current stream waits for it.  -> (rows int32 [Q,k,4], totals int32 [Q]), this matcher's tensors,
         overwritten `n_streams` calls later.  Its own workspace (the rows are 4 wide, `k` is the call's own) and no
         plan: the near-duplicate report is one call per upload, not the tick's stream of batches."""
+        return self._near_call(self.comm.align_topk_sharded, tc.align_topk_sharded_workspace_bytes, d_queries,
+                               d_q_offsets, max_query_len, int(k), eps=eps, max_offset=max_offset, min_votes=min_votes,
+                               min_score=min_score, d_exclude_ids=d_exclude_ids)
+
+    supports_align_wide = True
+
+    def align_wide_topk(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, eps: float,
+                        max_offset: Optional[float] = None, k: int, min_votes: int = 1, min_score: int = 0,
+                        contain: bool = False, d_exclude_ids: Optional[torch.Tensor] = None):
+        """align_topk at any shift behind ONE library call (tvz_align_wide_topk_sharded; `max_offset=None`: the widest,
+        `contain`: scored by the containment), with align_topk's streams, workspace and tensors."""
+        return self._near_call(self.comm.align_wide_topk_sharded, tc.align_wide_topk_sharded_workspace_bytes, d_queries,
+                               d_q_offsets, max_query_len, int(k), eps=eps, max_offset=max_offset, min_votes=min_votes,
+                               min_score=min_score, contain=contain, d_exclude_ids=d_exclude_ids)
+
+    def _near_call(self, call, sizer, d_queries, d_q_offsets, max_query_len, k, **kw):
+        """What align_topk and align_wide_topk share: the next side stream, its near workspace (sized by `sizer`) and
+        (rows, totals), the one library call `call`, the current stream's wait for it."""
         slot = self._next_slot()
         st = slot.stream
-        (_, Q), k = self.corpus._check_queries(d_queries, d_q_offsets), int(k)
-        need = tc.align_topk_sharded_workspace_bytes(Q, max_query_len, d_queries.numel(), k, self.world)
+        _, Q = self.corpus._check_queries(d_queries, d_q_offsets)
+        need = sizer(Q, max_query_len, d_queries.numel(), k, self.world)
         if slot.near_ws is None or slot.near_ws.numel() < need:
             slot.near_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.dev)
         if slot.near_out is None or slot.near_out[0].shape[:2] != (Q, k):
             slot.near_out = tc._topk_out(None, Q, k, 4, self.dev)
         st.wait_stream(torch.cuda.current_stream(self.dev))       # the queries are complete; the slot's last answer is read
-        rows, totals = self.comm.align_topk_sharded(self.corpus, d_queries, d_q_offsets, max_query_len, eps=eps,
-                                                    max_offset=max_offset, k=k, min_votes=min_votes,
-                                                    min_score=min_score, d_exclude_ids=d_exclude_ids,
-                                                    workspace=slot.near_ws, stream=st, out=slot.near_out)
+        rows, totals = call(self.corpus, d_queries, d_q_offsets, max_query_len, k=k, workspace=slot.near_ws, stream=st,
+                            out=slot.near_out, **kw)
         slot.event.record(st)
         torch.cuda.current_stream(self.dev).wait_event(slot.event)
         return rows, totals
