@@ -562,6 +562,67 @@ int tvz_align_wide_topk_sharded(tvz_corpus *c, tvz_comm *comm, const double *d_q
                                 int32_t *d_topk, int32_t *d_totals, void *d_workspace, size_t workspace_bytes,
                                 void *hip_stream);
 
+/* The alignment top-k at any shift FOR SPEED-CHANGED COPIES: tvz_align_wide_topk with a list of rates, for the stored
+ * video that is the upload played at another speed - film 24 -> 25 fps ("PAL speed-up", rate 24/25 or 25/24), the
+ * 1000/1001 NTSC family, the "1.25x" re-upload.  There the cuts are c = rho x + t, and at a single rate the votes
+ * smear over the bins.  (TVZ_VERSION unchanged: new exports only.)  The contract is tvz_align_wide_topk's, word for
+ * word, with these changes:
+ *   rates : h_rates is a HOST array of n_rates doubles, copied into the kernel's arguments - the call still only
+ *           enqueues: no allocation, no host synchronisation.  n_rates outside 1..TVZ_ALIGN_MAX_RATES:
+ *           TVZ_ERR_UNSUPPORTED; a NULL h_rates, or a rate that is NaN, infinite or <= 0: TVZ_ERR_INVALID; nothing is
+ *           written on a refusal.  Equal rates may repeat.
+ *   vote  : at rate i, x' = x * rho_i is ONE IEEE double multiplication rounded to nearest, and the pair (c, x) votes
+ *           into floor((c - x')/eps + 0.5) when that lies in [-B, B].  The subtraction is NOT contracted with the
+ *           product into an FMA.  B, its limits and its refusals are tvz_align_wide_topk's.
+ *   best  : for each rate the best bin and its raw votes are found by the rule above (most votes, then smaller |bin|,
+ *           then the negative one); the row keeps the rate with the MOST raw votes, on equal votes the SMALLER rate
+ *           index - the caller lists rates by preference; no votes at any rate: rate index 0, bin 0.  Then v, u
+ *           (Jaccard or TVZ_ALIGN_CONTAIN), score and the hit test are exactly as before; nv is the query's non-NaN
+ *           count, whatever the rate.  A hit means: stored ~= rate x upload + best_bin x eps.
+ *   order : ascending by the tuple (2^20 - score, video_id, best_bin as a signed number, row_len, votes, rate_index);
+ *           rows equal in all six are identical rows and are all kept.
+ *   d_out : int32[Q][k+1][5] = the k best rows as (video_id, row_len, best_bin, votes, rate_index), padding rows
+ *           (-1, 0, 0, 0, 0), and a last row (-1, n_hits, 0, 0, 0); n_hits as the wide call's, INT32_MIN for a refused
+ *           query included.  Rows are 20 bytes: nothing may assume a row is 16-byte aligned.
+ * With n_rates = 1 and h_rates[0] = 1.0 (x * 1.0 == x) columns 0..3 of every row equal tvz_align_wide_topk's block bit
+ * for bit, and column 4 is 0.
+ * Workspace = tvz_match_tol_workspace_bytes(Q, max_query_len, max(total_query_keys, max_query_len))   (the sorted queries)
+ *           + 4 Q                                                                      (hit totals)
+ *           + max(6080, 95 Q) x k x 24                                                  (one kept list per sweep
+ *             block; a kept hit is the wide call's two 64-bit words and 32-bit votes, and the 32-bit rate index)
+ *           + alignment (each part to 256 B).
+ * A workspace below the fixed parts + one query of max_query_len values: TVZ_ERR_WORKSPACE with the bytes missing.
+ * Cost: a wave walks its row once per rate - n_rates times tvz_align_wide_topk's searches and votes - for ONE sort
+ * of the queries, one read of the table's rows and one selection; and one hit per stored row at its best rate, which
+ * no merge of per-rate calls can give (a block row does not say which table row it came from).
+ *
+ * tvz_align_rates_topk_merge: d_gathered int32[n_lists][Q][k+1][5] -> d_topk int32[Q][k][5], d_totals int32[Q]:
+ * tvz_align_wide_topk_merge's rules with the six-tuple order.  The rate index is carried, never interpreted; the score
+ * is rebuilt from votes, nv and row_len as there.  PRECONDITION: all lists were made with the same `flags` and the
+ * same rate list.  Totals, refusals and limits (n_lists 1..16, k 1..64) as the wide merge; d_gathered and d_topk
+ * 16-byte aligned (the base pointers only: the rows are not).
+ * tvz_align_rates_topk_shards: the shards of ONE process (several handles on one device), as
+ * tvz_align_wide_topk_shards: d_blocks int32[n_shards][Q][k+1][5]; one workspace sized for ONE handle
+ * (tvz_align_rates_topk_workspace_bytes); refuses what tvz_align_rates_topk and the merge refuse before anything is
+ * enqueued.
+ * NOT YET: the RCCL form (_sharded), and with it the service's ask kind and flags - the one-process-per-GPU service
+ * gets them in a follow-up, as the bounded and the wide search did. */
+#define TVZ_ALIGN_MAX_RATES 8
+size_t tvz_align_rates_topk_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k);
+int tvz_align_rates_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
+                         int32_t max_query_len, double eps, double max_offset, const double *h_rates, int32_t n_rates,
+                         int32_t min_votes, int32_t min_score, uint32_t flags, const int32_t *d_exclude_ids, int32_t k,
+                         int32_t *d_out, void *d_workspace, size_t workspace_bytes, void *hip_stream);
+int tvz_align_rates_topk_merge(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t k, uint32_t flags,
+                               const double *d_queries, const int64_t *d_q_offsets, int32_t *d_topk, int32_t *d_totals,
+                               void *hip_stream);
+int tvz_align_rates_topk_shards(tvz_corpus *const *shards, int32_t n_shards, const double *d_queries,
+                                const int64_t *d_q_offsets, int32_t Q, int32_t max_query_len, double eps,
+                                double max_offset, const double *h_rates, int32_t n_rates, int32_t min_votes,
+                                int32_t min_score, uint32_t flags, const int32_t *d_exclude_ids, int32_t k,
+                                int32_t *d_blocks, int32_t *d_topk, int32_t *d_totals, void *d_workspace,
+                                size_t workspace_bytes, void *hip_stream);
+
 /* ------------------------------------------------------------------------
  * Opt-in TOLERANT duplicate match.  NOT the reference's verdict: db.py:79,85-91 match exact float64
  * values, and that stays the default everywhere (tolerance 0).  README.md:291 promises "0.1 second

@@ -129,6 +129,27 @@ def align_wide_order_key(row, nv: int, contain: bool = False):
     return (-score(votes, nv, row_len), vid, best_bin, row_len, votes)
 
 
+ALIGN_MAX_RATES = 8                         # include/tvz.h TVZ_ALIGN_MAX_RATES: tvz_align_rates_topk's rate list
+
+
+def align_rates_topk_workspace_bytes(Q: int, max_query_len: int, total_query_keys: int = 0, k: int = 16) -> int:
+    """tvz_align_rates_topk_workspace_bytes: as align_wide_topk_workspace_bytes, with 24 bytes per kept hit."""
+    return int(_lib.load().tvz_align_rates_topk_workspace_bytes(int(Q), int(max_query_len), int(total_query_keys), int(k)))
+
+
+def align_rates_order_key(row, nv: int, contain: bool = False):
+    """Sort key of one (video_id, row_len, best_bin, votes, rate_index) row of tvz_align_rates_topk:
+    align_wide_order_key, then the rate's index."""
+    return align_wide_order_key(row[:4], nv, contain) + (int(row[4]),)
+
+
+def _rates(rates):
+    """The rate list of the calls with rates -> (a host double array, its length).  What the list may hold is the
+    library's to judge (1..ALIGN_MAX_RATES finite rates > 0)."""
+    r = [float(x) for x in rates]
+    return (C.c_double * max(len(r), 1))(*r), len(r)
+
+
 class DeviceCorpus:
     """tvz_corpus handle: rows of (video_id, sorted-unique canonical float64 keys) in HBM."""
 
@@ -349,6 +370,39 @@ class DeviceCorpus:
             _wide_offset(eps, max_offset),
             int(min_votes), int(min_score), ALIGN_CONTAIN if contain else 0, excl, int(k), out.data_ptr(), ws.data_ptr(),
             ws.numel(), s.cuda_stream))
+        return out
+
+    def align_rates_topk(self, queries, *, eps: float, rates: Sequence[float], max_offset: Optional[float] = None,
+                         k: int = 16, min_votes: int = 1, min_score: int = 0, contain: bool = False, exclude_ids=None,
+                         max_query_len: Optional[int] = None):
+        """tvz_align_rates_topk: align_wide_topk for copies played at another speed - every row is aligned once per
+        rate of `rates` (1..ALIGN_MAX_RATES finite values > 0, in the order of preference; the query's cuts are scaled:
+        stored ~= rate x query + shift) and kept once, at the rate with the most votes.  Arguments otherwise as
+        align_wide_topk.  -> (rows int32[Q, k, 5] of (video_id, row_len, best_bin, votes, rate_index), padded with
+        (-1, 0, 0, 0, 0); totals int32[Q]); order: align_rates_order_key."""
+        dev = torch.device("cuda", self.device)
+        d_q, d_off, Q, max_query_len, d_ex = align_inputs(queries, exclude_ids, max_query_len, dev)
+        ws = thread_workspace(self._tls, align_rates_topk_workspace_bytes(Q, max_query_len, d_q.numel(), k), dev)
+        h = self.align_rates_topk_block(d_q, d_off, max_query_len, eps=eps, rates=rates, max_offset=max_offset, k=k,
+                                        min_votes=min_votes, min_score=min_score, contain=contain, d_exclude_ids=d_ex,
+                                        workspace=ws).cpu().numpy()
+        return np.ascontiguousarray(h[:, :k]), np.ascontiguousarray(h[:, k, 1])
+
+    def align_rates_topk_block(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, eps: float,
+                               rates: Sequence[float], max_offset: Optional[float] = None, k: int, min_votes: int = 1,
+                               min_score: int = 0, contain: bool = False, d_exclude_ids: Optional[torch.Tensor] = None,
+                               out: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
+                               workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """tvz_align_rates_topk, device in / device out: enqueue Q queries -> the block int32 [Q, k+1, 5]."""
+        Q = d_q_offsets.numel() - 1
+        dev, s, ws, excl = self._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace,
+                                         align_rates_topk_workspace_bytes(Q, max_query_len, d_queries.numel(), k))
+        out = _out(out, (Q, k + 1, 5), dev)
+        h_rates, n_rates = _rates(rates)
+        _lib.check(self.lib.tvz_align_rates_topk(
+            self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps),
+            _wide_offset(eps, max_offset), h_rates, n_rates, int(min_votes), int(min_score),
+            ALIGN_CONTAIN if contain else 0, excl, int(k), out.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
         return out
 
     # ---- batched, device resident ----
@@ -715,6 +769,44 @@ def align_wide_topk_shards(shards: Sequence["DeviceCorpus"], d_queries: torch.Te
             handles, len(shards), d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps),
             _wide_offset(eps, max_offset), int(min_votes), int(min_score), ALIGN_CONTAIN if contain else 0, excl, int(k),
             blocks.data_ptr(), rows.data_ptr(), totals.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
+    return blocks, rows, totals
+
+
+def align_rates_topk_merge(gathered: torch.Tensor, k: int, d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
+                           contain: bool = False, stream: Optional[torch.cuda.Stream] = None, out=None):
+    """tvz_align_rates_topk_merge: align_wide_topk_merge for the blocks of align_rates_topk_block, int32 [R,Q,k+1,5] ->
+    (rows int32 [Q,k,5], totals int32 [Q]); every list sorted by align_rates_order_key of the SAME `contain`, made
+    with the same rate list (the rate index is carried, never read)."""
+    R, Q, k1, w = gathered.shape
+    if k1 != k + 1 or w != 5 or gathered.dtype != torch.int32 or not gathered.is_contiguous():
+        raise RuntimeError("gathered must be a contiguous int32 [R,Q,k+1,5]")
+    rows, totals = _topk_out(out, Q, k, 5, gathered.device)
+    s = stream if stream is not None else torch.cuda.current_stream(gathered.device)
+    with torch.cuda.device(gathered.device):
+        _lib.check(_lib.load().tvz_align_rates_topk_merge(gathered.data_ptr(), R, Q, int(k),
+                                                          ALIGN_CONTAIN if contain else 0, d_queries.data_ptr(),
+                                                          d_q_offsets.data_ptr(), rows.data_ptr(), totals.data_ptr(),
+                                                          s.cuda_stream))
+    return rows, totals
+
+
+def align_rates_topk_shards(shards: Sequence["DeviceCorpus"], d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
+                            max_query_len: int, *, eps: float, rates: Sequence[float], max_offset: Optional[float] = None,
+                            k: int, workspace: torch.Tensor, min_votes: int = 1, min_score: int = 0, contain: bool = False,
+                            d_exclude_ids: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None):
+    """tvz_align_rates_topk on every handle of ONE device + its merge behind one library call
+    (tvz_align_rates_topk_shards): -> (blocks int32 [R,Q,k+1,5], rows int32 [Q,k,5], totals int32 [Q]).  `workspace`:
+    align_rates_topk_workspace_bytes (its size is the library's to judge, as align_topk_shards')."""
+    Q = d_q_offsets.numel() - 1
+    dev, s, ws, excl = shards[0]._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace, None)
+    handles, blocks, rows, totals = _shards_out(shards, Q, k, 5, dev)
+    h_rates, n_rates = _rates(rates)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().tvz_align_rates_topk_shards(
+            handles, len(shards), d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps),
+            _wide_offset(eps, max_offset), h_rates, n_rates, int(min_votes), int(min_score),
+            ALIGN_CONTAIN if contain else 0, excl, int(k), blocks.data_ptr(), rows.data_ptr(), totals.data_ptr(),
+            ws.data_ptr(), ws.numel(), s.cuda_stream))
     return blocks, rows, totals
 
 

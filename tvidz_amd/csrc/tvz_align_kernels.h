@@ -42,6 +42,16 @@
 // this one's lower bin - 1; a walk that stops at a NaN has met a key that never votes).  So only a row's highest
 // window searches; the later ones read the position back, for the row's first kAwResume keys (a u16 per key and
 // wave in LDS, written and read by the same lane); keys beyond them search in every window.
+//
+// The rates (al_sweep<.., true, true>, tvz_align_rates_topk): the copy played at another speed, c = rho x + t.  The
+// wave walks its row once per rate rho_i of the call's list (a by-value kernel argument, read with scalar loads: no
+// LDS) with every query value read as x' = x * rho_i - ONE IEEE multiplication that the compiler may not contract
+// with the vote's subtraction (al_scaled) - and keeps the rate whose best bin has the most votes, the smaller index
+// on a tie.  The product keeps the sorted query sorted: for rho > 0, fl(x * rho) never decreases as x grows, and an
+// infinity stays the same infinity.  So al_lo, the runs and the row's window range [bin(c_min, x'_max), bin(c_max,
+// x'_min)] hold per rate, with x'_min / x'_max the products of s[0] / s[m - 1].  The resume positions are one rate's:
+// a rate's highest window searches.  The kept hit carries the rate's index behind the votes (ArHit) and the block
+// has a fifth column; the selection and the merge carry it and never read it.
 #pragma once
 #include "tvz_match_kernels.h"
 #include "tvz_tol_kernels.h"
@@ -65,6 +75,13 @@ constexpr int kAwOneWindow = 4096;                     // a call of at most this
 constexpr int kAwWidth = 1024;                         // bins of a window otherwise (measured against 256..4096)
 constexpr int kAwResume = 512;                         // keys of a row whose resume position is kept (a multiple of 64)
 constexpr uint32_t kAwContain = 1u;                    // TVZ_ALIGN_CONTAIN
+constexpr int kArMaxRates = 8;                         // TVZ_ALIGN_MAX_RATES
+
+// the rates of tvz_align_rates_topk, a kernel argument by value: r[0 .. n), each finite and > 0 (the host's check)
+struct AlRates {
+    double r[kArMaxRates];
+    int32_t n;
+};
 
 // bins of a wave's histogram (even: the touched list behind the histograms stays 4-byte aligned).  The bounded call's
 // is aw_width too: its B is at most 2047
@@ -82,6 +99,18 @@ inline size_t aw_lds_bytes(int32_t lds_keys, int32_t B, int width) {
 // d of the contract, verbatim
 __device__ __forceinline__ double al_bin(double c, double x, double eps) { return floor((c - x) / eps + 0.5); }
 
+// x' = x * rho of the contract: the product is rounded on its own, never fused with al_bin's subtraction
+__device__ __forceinline__ double al_scaled(double x, double rho) {
+#pragma clang fp contract(off)
+    return x * rho;
+}
+
+// the sorted query's value t as the votes see it: scaled by the rate where the sweep has rates
+template <bool kRates> __device__ __forceinline__ double al_x(const double *s, int t, double rho) {
+    if constexpr (kRates) return al_scaled(s[t], rho);
+    else return s[t];
+}
+
 // is x in front of key c's run?  d > Bd; a NaN d counts by the side x lies on (x == c only for two equal
 // infinities: -inf is the smallest query value, +inf the largest)
 __device__ __forceinline__ bool al_left(double c, double x, double eps, double Bd) {
@@ -90,11 +119,12 @@ __device__ __forceinline__ bool al_left(double c, double x, double eps, double B
 }
 
 // first t with s[t] not in front of the run: a prefix of the sorted query
-__device__ __forceinline__ int al_lo(const double *s, int m, double c, double eps, double Bd) {
+template <bool kRates>
+__device__ __forceinline__ int al_lo(const double *s, int m, double c, double eps, double Bd, double rho) {
     int lo = 0, len = m;
     while (len > 0) {
         const int half = len >> 1;
-        if (al_left(c, s[lo + half], eps, Bd)) {
+        if (al_left(c, al_x<kRates>(s, lo + half, rho), eps, Bd)) {
             lo += half + 1;
             len -= half + 1;
         } else {
@@ -104,17 +134,20 @@ __device__ __forceinline__ int al_lo(const double *s, int m, double c, double ep
     return lo;
 }
 
-// ---- a kept hit, in the two layouts ------------------------------------------------------------------------------
+// ---- a kept hit, in the three layouts-----------------------------------------------------------------------------
 // Lists<N>: N hits as a structure of arrays, in static LDS; Parts / ConstParts: the same arrays in the workspace,
-// [Q][n_lists][k] each.  load / store take any of them.
+// [Q][n_lists][k] each.  load / store take any of them.  kCols: the int32 columns of the hit's block row; the fifth
+// (ArHit's alone) is extra().
 
 // the bounded call's: 16 bytes, ordered as (w, p)
 struct AlHit {
     unsigned long long w, p;       // (2^20 - score) << 43 | video_id << 12 | bin + 2048;  row_len << 32 | votes
+    static constexpr int kCols = 4;
     template <int N> struct Lists { unsigned long long w[N], p[N]; };
     struct Parts { unsigned long long *w, *p; };
     struct ConstParts { const unsigned long long *w, *p; };
-    static __device__ __forceinline__ AlHit make(uint32_t score, int32_t vid, int bin, uint32_t row_len, uint32_t votes) {
+    static __device__ __forceinline__ AlHit make(uint32_t score, int32_t vid, int bin, uint32_t row_len, uint32_t votes,
+                                                 uint32_t /* rate */) {
         return {((unsigned long long)(kAlScoreOne - score) << 43) | ((unsigned long long)((uint32_t)vid & 0x7fffffffu) << 12) |
                     (unsigned long long)(uint32_t)(bin + 2048),
                 ((unsigned long long)row_len << 32) | votes};
@@ -141,10 +174,12 @@ struct AlHit {
 struct AwHit {
     unsigned long long w, p;       // (2^20 - score) << 31 | video_id;  (bin + 2^22) << 32 | row_len
     uint32_t v;                    // the raw votes
+    static constexpr int kCols = 4;
     template <int N> struct Lists { unsigned long long w[N], p[N]; uint32_t v[N]; };
     struct Parts { unsigned long long *w, *p; uint32_t *v; };
     struct ConstParts { const unsigned long long *w, *p; const uint32_t *v; };
-    static __device__ __forceinline__ AwHit make(uint32_t score, int32_t vid, int bin, uint32_t row_len, uint32_t votes) {
+    static __device__ __forceinline__ AwHit make(uint32_t score, int32_t vid, int bin, uint32_t row_len, uint32_t votes,
+                                                 uint32_t /* rate */) {
         return {((unsigned long long)(kAlScoreOne - score) << 31) | (unsigned long long)((uint32_t)vid & 0x7fffffffu),
                 ((unsigned long long)(uint32_t)(bin + kAwMaxB) << 32) | row_len, votes};
     }
@@ -168,6 +203,49 @@ struct AwHit {
         l.w[i] = w;
         l.p[i] = p;
         l.v[i] = v;
+    }
+};
+
+// the call with rates' (DESIGN.md 4.12): AwHit and the index of the rate the votes were counted at, 24 bytes, ordered
+// as (w, p, v, r)
+struct ArHit {
+    unsigned long long w, p;       // as AwHit's
+    uint32_t v, r;                 // the raw votes; the rate's index
+    static constexpr int kCols = 5;
+    template <int N> struct Lists { unsigned long long w[N], p[N]; uint32_t v[N], r[N]; };
+    struct Parts { unsigned long long *w, *p; uint32_t *v, *r; };
+    struct ConstParts { const unsigned long long *w, *p; const uint32_t *v, *r; };
+    static __device__ __forceinline__ ArHit make(uint32_t score, int32_t vid, int bin, uint32_t row_len, uint32_t votes,
+                                                 uint32_t rate) {
+        return {((unsigned long long)(kAlScoreOne - score) << 31) | (unsigned long long)((uint32_t)vid & 0x7fffffffu),
+                ((unsigned long long)(uint32_t)(bin + kAwMaxB) << 32) | row_len, votes, rate};
+    }
+    static __device__ __forceinline__ ArHit pad() { return {kAlPad, kAlPad, ~0u, ~0u}; }
+    __device__ __forceinline__ bool is_pad() const { return w == kAlPad; }
+    static __device__ __forceinline__ bool le(const ArHit &a, const ArHit &b) {
+        return a.w < b.w || (a.w == b.w && (a.p < b.p || (a.p == b.p && (a.v < b.v || (a.v == b.v && a.r <= b.r)))));
+    }
+    __device__ __forceinline__ int4 row() const {      // (video_id, row_len, best_bin, votes)
+        const bool pad = is_pad();
+        return make_int4(pad ? -1 : (int32_t)(w & 0x7fffffffu), pad ? 0 : (int32_t)(p & 0xffffffffu),
+                         pad ? 0 : (int32_t)(p >> 32) - kAwMaxB, pad ? 0 : (int32_t)v);
+    }
+    __device__ __forceinline__ int32_t extra() const { return is_pad() ? 0 : (int32_t)r; }      // rate_index
+    static __device__ __forceinline__ ArHit select(bool c, const ArHit &a, const ArHit &b) {
+        return {c ? a.w : b.w, c ? a.p : b.p, c ? a.v : b.v, c ? a.r : b.r};
+    }
+    __device__ __forceinline__ ArHit lane(int src) const { return {__shfl(w, src), __shfl(p, src), __shfl(v, src), __shfl(r, src)}; }
+    __device__ __forceinline__ ArHit shift_up() const {
+        return {__shfl_up(w, 1), __shfl_up(p, 1), __shfl_up(v, 1), __shfl_up(r, 1)};
+    }
+    template <class L> static __device__ __forceinline__ ArHit load(const L &l, int64_t i) {
+        return {l.w[i], l.p[i], l.v[i], l.r[i]};
+    }
+    template <class L> __device__ __forceinline__ void store(L &l, int64_t i) const {
+        l.w[i] = w;
+        l.p[i] = p;
+        l.v[i] = v;
+        l.r[i] = r;
     }
 };
 
@@ -217,21 +295,25 @@ template <class Hit, int N> __device__ __forceinline__ void al_merge_waves(Hit &
     for (int j = 1; j < N / 64; ++j) al_take(kept, Hit::load(s, j * 64 + lane), k, lane);
 }
 
-// One wave writes a query's block int32[k+1][4]: k rows (video_id, row_len, best_bin, votes), padding (-1, 0, 0, 0),
-// then (-1, n_hits, 0, 0) with n_hits = INT32_MIN for a refused query
+// One wave writes a query's block int32[k+1][kCols]: k rows (video_id, row_len, best_bin, votes[, rate_index]), padding
+// (-1, 0, 0, 0[, 0]), then (-1, n_hits, 0, 0[, 0]) with n_hits = INT32_MIN for a refused query.  Word stores: a row of
+// five columns is not 16-byte aligned
 template <class Hit> __device__ __forceinline__ void al_write_block(const Hit &kept, int32_t *out, int k, int lane, int32_t n_hits) {
+    constexpr int kCols = Hit::kCols;
     if (lane < k) {
         const int4 o = kept.row();
-        out[lane * 4 + 0] = o.x;
-        out[lane * 4 + 1] = o.y;
-        out[lane * 4 + 2] = o.z;
-        out[lane * 4 + 3] = o.w;
+        out[lane * kCols + 0] = o.x;
+        out[lane * kCols + 1] = o.y;
+        out[lane * kCols + 2] = o.z;
+        out[lane * kCols + 3] = o.w;
+        if constexpr (kCols == 5) out[lane * kCols + 4] = kept.extra();
     }
     if (lane == 0) {
-        out[k * 4 + 0] = -1;
-        out[k * 4 + 1] = n_hits;
-        out[k * 4 + 2] = 0;
-        out[k * 4 + 3] = 0;
+        out[k * kCols + 0] = -1;
+        out[k * kCols + 1] = n_hits;
+        out[k * kCols + 2] = 0;
+        out[k * kCols + 3] = 0;
+        if constexpr (kCols == 5) out[k * kCols + 4] = 0;
     }
 }
 
@@ -239,14 +321,15 @@ template <class Hit> __device__ __forceinline__ void al_write_block(const Hit &k
 // grid = (row blocks, Q).  Sorted query q: sv[at .. at + m) with at = q_offsets[q] - q_offsets[0], m = qm[q]
 // (ts_tol_sort_kernel).  part: the kept lists, block bx writes list bx; totals[q] (zeroed by the preparation) += the
 // block's hits, one atomic.  width = aw_width(B); dynamic LDS: aw_lds_bytes(lds_keys, B, width).  0 <= B <= kAwMaxB,
-// and B <= 2047 where !kWindowed (the host refuses anything else before the launch).
-template <class Hit, bool kWindowed>
+// and B <= 2047 where !kWindowed (the host refuses anything else before the launch).  kRates: the row is walked once
+// per rate of `rates` (1 .. kArMaxRates of them) and its best rate kept; without, `rates` is never read.
+template <class Hit, bool kWindowed, bool kRates = false>
 __device__ __forceinline__ void al_sweep(const Row *__restrict__ rows, int64_t n_rows, const int64_t *__restrict__ keys,
                                          const double *__restrict__ sv, const int64_t *__restrict__ q_offsets,
                                          const int32_t *__restrict__ qm, int32_t lds_keys, double eps, int32_t B, int32_t width,
                                          int32_t min_votes, int32_t min_score, bool contain,
                                          const int32_t *__restrict__ exclude_ids, int32_t k, typename Hit::Parts part,
-                                         int32_t n_lists, int32_t *__restrict__ totals) {
+                                         int32_t n_lists, int32_t *__restrict__ totals, const AlRates &rates = AlRates{}) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ typename Hit::template Lists<kAlWaves * 64> s_kept;
     __shared__ int32_t s_nhits;
@@ -277,10 +360,11 @@ __device__ __forceinline__ void al_sweep(const Row *__restrict__ rows, int64_t n
 
     const double Bd = (double)B;
     double x_min = 0.0, x_max = 0.0;
-    if constexpr (kWindowed) {
+    if constexpr (kWindowed && !kRates) {
         x_min = s[0];                                                         // sorted numerically, no NaN
         x_max = s[m - 1];
     }
+    const int n_rates = kRates ? rates.n : 1;                                 // >= 1 (the host's check)
     const int32_t excl = exclude_ids ? exclude_ids[q] : -1;
     const int64_t stride = (int64_t)gridDim.x * kAlWaves;
     const int64_t last_row = n_rows - 1;
@@ -292,11 +376,10 @@ __device__ __forceinline__ void al_sweep(const Row *__restrict__ rows, int64_t n
         const int64_t rn = r + stride;
         const Row nrow = load_row(rows + (rn < n_rows ? rn : last_row));      // lands while this row votes
         const int64_t *rk = keys + row.off;
-        int w0 = 0, w1 = 0;                                                   // the one window [-B, B]
+        double c_min = 0.0, c_max = 0.0;
         if constexpr (kWindowed) {
-            // the row's offset range [bin(c_min, x_max), bin(c_max, x_min)], clipped to [-B, B]; a NaN end (inf - inf)
-            // clips to the bound
-            double c_min = __longlong_as_double(0x7ff0000000000000ll), c_max = -c_min;
+            c_min = __longlong_as_double(0x7ff0000000000000ll);
+            c_max = -c_min;
             for (int j = lane; j < row.len; j += 64) {
                 const double c = __longlong_as_double(rk[j]);
                 c_min = c < c_min ? c : c_min;
@@ -307,56 +390,81 @@ __device__ __forceinline__ void al_sweep(const Row *__restrict__ rows, int64_t n
                 c_min = lo < c_min ? lo : c_min;
                 c_max = hi > c_max ? hi : c_max;
             }
-            const double d_lo = al_bin(c_min, x_max, eps), d_hi = al_bin(c_max, x_min, eps);
-            const double r_lo = d_lo >= -Bd ? d_lo : -Bd, r_hi = d_hi <= Bd ? d_hi : Bd;
-            w1 = -1;                                                          // no window: an empty row, a range outside
-            if (row.len > 0 && r_lo <= r_hi) {                                // -B <= r_lo <= r_hi <= B: both finite
-                w0 = ((int)r_lo + B) / width;
-                w1 = ((int)r_hi + B) / width;
-            }
-            w0 = __builtin_amdgcn_readfirstlane(w0);                          // (equal in every lane already)
-            w1 = __builtin_amdgcn_readfirstlane(w1);
-            w1 = w1 < max_windows - 1 ? w1 : max_windows - 1;                 // (never: (2B) / width is the last window)
         }
-        unsigned long long best = 0;
-        for (int w = w1; w >= w0; --w) {                                      // wave-uniform, at most max_windows rounds
-            int w_lo = -B, w_hi = B;
+        unsigned long long best = 0;                                          // of the row: the kept rate's
+        uint32_t best_rate = 0;
+        int ri = 0;
+        do {                                                                  // wave-uniform; one round without rates
+            double rho = 1.0;
+            if constexpr (kRates) {
+                rho = rates.r[ri];
+                x_min = al_x<true>(s, 0, rho);                                // the products stay sorted (header comment)
+                x_max = al_x<true>(s, m - 1, rho);
+            }
+            int w0 = 0, w1 = 0;                                               // the one window [-B, B]
             if constexpr (kWindowed) {
-                w_lo = w * width - B;                                         // >= -B
-                w_hi = w_lo + width - 1 < B ? w_lo + width - 1 : B;
-            }
-            const double lo_d = (double)w_lo, hi_d = (double)w_hi;
-            for (int j = lane; j < row.len; j += 64) {
-                const double c = __longlong_as_double(rk[j]);
-                const bool kept_pos = kWindowed && j < resume_keys;           // (the same in every lane of a round)
-                int t = kept_pos && w != w1 ? (int)resume[j] : al_lo(s, m, c, eps, hi_d);
-                for (; t < m; ++t) {
-                    const double d = al_bin(c, s[t], eps);
-                    if (!(d >= lo_d)) break;                                  // behind the window (or NaN there)
-                    if (!(d <= hi_d)) continue;                               // (never, behind al_lo: keeps the index in bounds)
-                    const int bin = (int)d;                                   // w_lo <= bin <= w_hi
-                    const uint32_t slot = (uint32_t)(bin - w_lo);             // 0 .. width - 1
-                    const uint32_t cnt = atomicAdd(&hist[slot], 1u) + 1u;
-                    if (cnt == 1u) dirty[atomicAdd(n_dirty, 1u)] = (uint16_t)slot;      // at most once per slot: < width
-                    const uint32_t order = 2u * (uint32_t)(bin < 0 ? -bin : bin) + (bin > 0 ? 1u : 0u);
-                    const unsigned long long key = ((unsigned long long)cnt << 33) | (kAlOrderMask - order);
-                    best = key > best ? key : best;
+                // the row's offset range [bin(c_min, x_max), bin(c_max, x_min)], clipped to [-B, B]; a NaN end (inf -
+                // inf) clips to the bound
+                const double d_lo = al_bin(c_min, x_max, eps), d_hi = al_bin(c_max, x_min, eps);
+                const double r_lo = d_lo >= -Bd ? d_lo : -Bd, r_hi = d_hi <= Bd ? d_hi : Bd;
+                w1 = -1;                                                      // no window: an empty row, a range outside
+                if (row.len > 0 && r_lo <= r_hi) {                            // -B <= r_lo <= r_hi <= B: both finite
+                    w0 = ((int)r_lo + B) / width;
+                    w1 = ((int)r_hi + B) / width;
                 }
+                w0 = __builtin_amdgcn_readfirstlane(w0);                      // (equal in every lane already)
+                w1 = __builtin_amdgcn_readfirstlane(w1);
+                w1 = w1 < max_windows - 1 ? w1 : max_windows - 1;             // (never: (2B) / width is the last window)
+            }
+            unsigned long long rbest = 0;                                     // of this rate
+            for (int w = w1; w >= w0; --w) {                                  // wave-uniform, at most max_windows rounds
+                int w_lo = -B, w_hi = B;
                 if constexpr (kWindowed) {
-                    if (kept_pos) resume[j] = (uint16_t)t;                    // t <= m <= 4095
+                    w_lo = w * width - B;                                     // >= -B
+                    w_hi = w_lo + width - 1 < B ? w_lo + width - 1 : B;
                 }
+                const double lo_d = (double)w_lo, hi_d = (double)w_hi;
+                for (int j = lane; j < row.len; j += 64) {
+                    const double c = __longlong_as_double(rk[j]);
+                    const bool kept_pos = kWindowed && j < resume_keys;       // (the same in every lane of a round)
+                    // (w1 is this rate's: the positions another rate left are never read)
+                    int t = kept_pos && w != w1 ? (int)resume[j] : al_lo<kRates>(s, m, c, eps, hi_d, rho);
+                    for (; t < m; ++t) {
+                        const double d = al_bin(c, al_x<kRates>(s, t, rho), eps);
+                        if (!(d >= lo_d)) break;                              // behind the window (or NaN there)
+                        if (!(d <= hi_d)) continue;                           // (never, behind al_lo: keeps the index in bounds)
+                        const int bin = (int)d;                               // w_lo <= bin <= w_hi
+                        const uint32_t slot = (uint32_t)(bin - w_lo);         // 0 .. width - 1
+                        const uint32_t cnt = atomicAdd(&hist[slot], 1u) + 1u;
+                        if (cnt == 1u) dirty[atomicAdd(n_dirty, 1u)] = (uint16_t)slot;  // at most once per slot: < width
+                        const uint32_t order = 2u * (uint32_t)(bin < 0 ? -bin : bin) + (bin > 0 ? 1u : 0u);
+                        const unsigned long long key = ((unsigned long long)cnt << 33) | (kAlOrderMask - order);
+                        rbest = key > rbest ? key : rbest;
+                    }
+                    if constexpr (kWindowed) {
+                        if (kept_pos) resume[j] = (uint16_t)t;                // t <= m <= 4095
+                    }
+                }
+                // LDS ops of one wave complete in order: the notes above are visible to the clearing below
+                wave_lds_fence();
+                const int nd = (int)*n_dirty;
+                for (int i = lane; i < nd; i += 64) hist[dirty[i]] = 0;
+                wave_lds_fence();
+                if (lane == 0) *n_dirty = 0;
             }
-            // LDS ops of one wave complete in order: the notes above are visible to the clearing below
-            wave_lds_fence();
-            const int nd = (int)*n_dirty;
-            for (int i = lane; i < nd; i += 64) hist[dirty[i]] = 0;
-            wave_lds_fence();
-            if (lane == 0) *n_dirty = 0;
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            const unsigned long long o = __shfl_xor(best, off);
-            best = o > best ? o : best;
-        }
+            for (int off = 32; off > 0; off >>= 1) {
+                const unsigned long long o = __shfl_xor(rbest, off);
+                rbest = o > rbest ? o : rbest;
+            }
+            if constexpr (kRates) {
+                if ((rbest >> 33) > (best >> 33)) {                           // strictly more votes: a tie keeps the
+                    best = rbest;                                             // smaller index (wave-uniform)
+                    best_rate = (uint32_t)ri;
+                }
+            } else {
+                best = rbest;
+            }
+        } while (kRates && ++ri < n_rates);
         const uint32_t votes = (uint32_t)(best >> 33);
         const uint32_t rl = (uint32_t)row.len;
         uint32_t v = votes < (uint32_t)m ? votes : (uint32_t)m;
@@ -368,7 +476,7 @@ __device__ __forceinline__ void al_sweep(const Row *__restrict__ rows, int64_t n
                 const uint32_t order = (uint32_t)(kAlOrderMask - (best & kAlOrderMask));
                 const int mag = (int)(order >> 1);
                 ++n_hits;
-                al_insert(kept, Hit::make(score, row.vid, (order & 1u) ? mag : -mag, rl, votes), k, lane);
+                al_insert(kept, Hit::make(score, row.vid, (order & 1u) ? mag : -mag, rl, votes, best_rate), k, lane);
             }
         }
         row = nrow;
@@ -380,7 +488,7 @@ __device__ __forceinline__ void al_sweep(const Row *__restrict__ rows, int64_t n
     if (threadIdx.x == 0 && s_nhits) atomicAdd(&totals[q], s_nhits);
 }
 
-// One block per query: the k smallest hits of its n_lists sorted partial lists -> d_out[q] = int32[k+1][4]
+// One block per query: the k smallest hits of its n_lists sorted partial lists -> d_out[q] = int32[k+1][Hit::kCols]
 // (al_write_block).  A query the preparation refused (qm < 0 or > lds_keys): all padding, n_hits = INT32_MIN.
 template <class Hit>
 __device__ __forceinline__ void al_reduce(typename Hit::ConstParts part, int32_t n_lists, int32_t k, const int32_t *__restrict__ qm,
@@ -406,10 +514,10 @@ __device__ __forceinline__ void al_reduce(typename Hit::ConstParts part, int32_t
         }
     }
     al_merge_waves<Hit, kAlReduceWaves * 64>(kept, s_kept, wv, lane, k);
-    if (wv == 0) al_write_block(kept, d_out + (int64_t)q * (k + 1) * 4, k, lane, refused ? INT32_MIN : totals[q]);
+    if (wv == 0) al_write_block(kept, d_out + (int64_t)q * (k + 1) * Hit::kCols, k, lane, refused ? INT32_MIN : totals[q]);
 }
 
-// The four entry points only forward.  part_w / part_p: uint64[Q][n_lists][k], part_v: uint32[Q][n_lists][k].
+// The six entry points only forward.  part_w / part_p: uint64[Q][n_lists][k], part_v / part_r: uint32[Q][n_lists][k].
 __global__ __launch_bounds__(kAlBlock) void ts_align_topk_kernel(
     const Row *__restrict__ rows, int64_t n_rows, const int64_t *__restrict__ keys, const double *__restrict__ sv,
     const int64_t *__restrict__ q_offsets, const int32_t *__restrict__ qm, int32_t lds_keys, double eps, int32_t B,
@@ -444,7 +552,26 @@ __global__ __launch_bounds__(kAlReduceBlock) void ts_alignw_reduce_kernel(
     al_reduce<AwHit>(AwHit::ConstParts{part_w, part_p, part_v}, n_lists, k, qm, lds_keys, totals, d_out);
 }
 
-// ---- the merge of the shards' blocks (tvz_align_topk_merge, tvz_align_wide_topk_merge) ---------------------------
+__global__ __launch_bounds__(kAlBlock) void ts_alignr_sweep_kernel(
+    const Row *__restrict__ rows, int64_t n_rows, const int64_t *__restrict__ keys, const double *__restrict__ sv,
+    const int64_t *__restrict__ q_offsets, const int32_t *__restrict__ qm, int32_t lds_keys, double eps, int32_t B,
+    int32_t width, AlRates rates, int32_t min_votes, int32_t min_score, uint32_t flags,
+    const int32_t *__restrict__ exclude_ids, int32_t k, unsigned long long *__restrict__ part_w,
+    unsigned long long *__restrict__ part_p, uint32_t *__restrict__ part_v, uint32_t *__restrict__ part_r, int32_t n_lists,
+    int32_t *__restrict__ totals) {
+    al_sweep<ArHit, true, true>(rows, n_rows, keys, sv, q_offsets, qm, lds_keys, eps, B, width, min_votes, min_score,
+                                (flags & kAwContain) != 0u, exclude_ids, k, ArHit::Parts{part_w, part_p, part_v, part_r},
+                                n_lists, totals, rates);
+}
+
+__global__ __launch_bounds__(kAlReduceBlock) void ts_alignr_reduce_kernel(
+    const unsigned long long *__restrict__ part_w, const unsigned long long *__restrict__ part_p,
+    const uint32_t *__restrict__ part_v, const uint32_t *__restrict__ part_r, int32_t n_lists, int32_t k,
+    const int32_t *__restrict__ qm, int32_t lds_keys, const int32_t *__restrict__ totals, int32_t *__restrict__ d_out) {
+    al_reduce<ArHit>(ArHit::ConstParts{part_w, part_p, part_v, part_r}, n_lists, k, qm, lds_keys, totals, d_out);
+}
+
+// ---- the merge of the shards' blocks (tvz_align_topk_merge, tvz_align_wide_topk_merge, tvz_align_rates_topk_merge) ---------------------------
 constexpr int kAlMergeBlock = 256;
 constexpr int kAlMergeWaves = kAlMergeBlock / 64;      // queries per block: a wave each
 constexpr int kAlMergeMaxLists = 16;                   // one n_hits per lane, far below a wave
@@ -461,6 +588,9 @@ constexpr int kAlMergeMaxLists = 16;                   // one n_hits per lane, f
 // = INT32_MIN - when a list's n_hits is negative (INT32_MIN: a rank refused the query) or the query is longer than
 // kAlMaxLen.  n_lists <= kAlMergeMaxLists, k <= kAlMaxK; gathered and d_topk 16-byte aligned.  AlHit's word holds a
 // bin of 12 bits: blocks with a bin outside +-2047 (the wide call's) are AwHit's alone.
+// ArHit's blocks have rows of five columns, 20 bytes - read and written word by word, only the base pointers are
+// aligned -, and the fifth, the rate's index, is carried into the hit's order and out again, never interpreted.
+
 template <class Hit>
 __device__ __forceinline__ void al_merge_blocks(const int32_t *__restrict__ gathered, int32_t n_lists, int32_t Q, int32_t k,
                                                 const double *__restrict__ queries, const int64_t *__restrict__ q_offsets,
@@ -469,9 +599,9 @@ __device__ __forceinline__ void al_merge_blocks(const int32_t *__restrict__ gath
     const int q = blockIdx.x * kAlMergeWaves + (threadIdx.x >> 6);
     if (q >= Q) return;                                            // wave-uniform
     const int64_t k1 = (int64_t)k + 1;
-    const int4 *blocks = reinterpret_cast<const int4 *>(gathered);            // [n_lists][Q][k+1] rows of 16 bytes
+    const int4 *blocks = reinterpret_cast<const int4 *>(gathered);            // [n_lists][Q][k+1] rows of 16 bytes (kCols = 4)
     // the lists' totals, one per lane; a negative one refuses the query
-    const int32_t nh = lane < n_lists ? gathered[(((int64_t)lane * Q + q) * k1 + k) * 4 + 1] : 0;
+    const int32_t nh = lane < n_lists ? gathered[(((int64_t)lane * Q + q) * k1 + k) * Hit::kCols + 1] : 0;
     long long total = nh;
     for (int off = 32; off > 0; off >>= 1) total += __shfl_xor(total, off);
     const int64_t qo = q_offsets[q];
@@ -488,10 +618,21 @@ __device__ __forceinline__ void al_merge_blocks(const int32_t *__restrict__ gath
         const uint32_t nv = (uint32_t)nvl;
         for (int l0 = 0; l0 < n_lists; l0 += kAlReduceLd) {        // wave-uniform
             int4 row[kAlReduceLd];
+            uint32_t rate[kAlReduceLd];
 #pragma unroll
             for (int j = 0; j < kAlReduceLd; ++j) {                // the loads of kAlReduceLd lists in flight together
                 const int l = l0 + j;
-                row[j] = l < n_lists && lane < k ? blocks[((int64_t)l * Q + q) * k1 + lane] : make_int4(-1, 0, 0, 0);
+                rate[j] = 0u;
+                if constexpr (Hit::kCols == 4) {
+                    row[j] = l < n_lists && lane < k ? blocks[((int64_t)l * Q + q) * k1 + lane] : make_int4(-1, 0, 0, 0);
+                } else {
+                    row[j] = make_int4(-1, 0, 0, 0);
+                    if (l < n_lists && lane < k) {                 // rows of 20 bytes: word loads
+                        const int32_t *p = gathered + (((int64_t)l * Q + q) * k1 + lane) * Hit::kCols;
+                        row[j] = make_int4(p[0], p[1], p[2], p[3]);
+                        rate[j] = (uint32_t)p[4];
+                    }
+                }
             }
 #pragma unroll
             for (int j = 0; j < kAlReduceLd; ++j) {
@@ -501,15 +642,25 @@ __device__ __forceinline__ void al_merge_blocks(const int32_t *__restrict__ gath
                 const uint32_t u = contain ? (nv < rl ? nv : rl) : nv + rl - v;
                 const bool hit = row[j].x >= 0 && u != 0u;
                 const uint32_t score = hit ? (v << 20) / u : 0u;   // v <= nv <= 4095: the shift fits 32 bits
-                al_take_live(kept, Hit::make(score, row[j].x, row[j].z, rl, votes), __ballot(hit), k, lane);
+                al_take_live(kept, Hit::make(score, row[j].x, row[j].z, rl, votes, rate[j]), __ballot(hit), k, lane);
             }
         }
     }
-    if (lane < k) reinterpret_cast<int4 *>(d_topk)[(int64_t)q * k + lane] = kept.row();
+    if constexpr (Hit::kCols == 4) {
+        if (lane < k) reinterpret_cast<int4 *>(d_topk)[(int64_t)q * k + lane] = kept.row();
+    } else if (lane < k) {
+        const int4 o = kept.row();
+        int32_t *out = d_topk + ((int64_t)q * k + lane) * Hit::kCols;
+        out[0] = o.x;
+        out[1] = o.y;
+        out[2] = o.z;
+        out[3] = o.w;
+        out[4] = kept.extra();
+    }
     if (lane == 0) d_totals[q] = refused ? INT32_MIN : (int32_t)(total > INT32_MAX ? INT32_MAX : total);
 }
 
-// The two entry points only forward.
+// The three entry points only forward.
 __global__ __launch_bounds__(kAlMergeBlock) void ts_align_topk_merge_kernel(
     const int32_t *__restrict__ gathered, int32_t n_lists, int32_t Q, int32_t k, const double *__restrict__ queries,
     const int64_t *__restrict__ q_offsets, int32_t *__restrict__ d_topk, int32_t *__restrict__ d_totals) {
@@ -521,6 +672,13 @@ __global__ __launch_bounds__(kAlMergeBlock) void ts_alignw_merge_kernel(
     const double *__restrict__ queries, const int64_t *__restrict__ q_offsets, int32_t *__restrict__ d_topk,
     int32_t *__restrict__ d_totals) {
     al_merge_blocks<AwHit>(gathered, n_lists, Q, k, queries, q_offsets, (flags & kAwContain) != 0u, d_topk, d_totals);
+}
+
+__global__ __launch_bounds__(kAlMergeBlock) void ts_alignr_merge_kernel(
+    const int32_t *__restrict__ gathered, int32_t n_lists, int32_t Q, int32_t k, uint32_t flags,
+    const double *__restrict__ queries, const int64_t *__restrict__ q_offsets, int32_t *__restrict__ d_topk,
+    int32_t *__restrict__ d_totals) {
+    al_merge_blocks<ArHit>(gathered, n_lists, Q, k, queries, q_offsets, (flags & kAwContain) != 0u, d_topk, d_totals);
 }
 
 }  // namespace

@@ -84,7 +84,8 @@ class Inspector:
                  near_duplicates: bool = False, near_eps: float = 1.0 / 30, near_max_offset: float = 30.0,
                  near_jaccard: float = 0.8, slot_bytes: int = 64 << 20, n_slots: Optional[int] = None,
                  profile: bool = False, match_tolerance: float = 0.0, near_top_k: Optional[int] = None,
-                 near_any_offset: bool = False, near_score: str = "jaccard", near_min_votes: int = 1):
+                 near_any_offset: bool = False, near_score: str = "jaccard", near_min_votes: int = 1,
+                 near_rates=None):
         self.store = store
         # opt-in: the near-duplicate report from the K best-aligned rows the device keeps (tvz_align_topk) instead of
         # one row per corpus row walked here.  None: the walk, exactly as before.  Refused here where the store's
@@ -117,6 +118,19 @@ class Inspector:
                 raise RuntimeError(f"near_any_offset=True: the store's corpus "
                                    f"({type(getattr(store, 'corpus', None)).__name__}) has no align_wide_topk; "
                                    "use a DeviceCorpus, a service.ShardedCorpus or a service.RankCorpus")
+        # opt-in: the search at any shift for copies played at another speed (tvz_align_rates_topk) - every row is
+        # aligned at each of near_rates (1..8 finite rates > 0, in the order of preference: stored ~= rate x upload +
+        # shift) and reported once, at its best rate, with a "rate" field.  None: nothing changes.
+        self.near_rates = None if near_rates is None else tuple(float(r) for r in near_rates)
+        if self.near_rates is not None:
+            if not 1 <= len(self.near_rates) <= 8 or not all(0.0 < r <= sys.float_info.max for r in self.near_rates):
+                raise ValueError(f"near_rates must be None or 1..8 finite rates > 0, got {near_rates!r}")
+            if not self.near_any_offset or self.near_top_k is None:
+                raise ValueError("near_rates needs near_any_offset=True and near_top_k")
+            if not hasattr(getattr(store, "corpus", None), "align_rates_topk"):
+                raise RuntimeError(f"near_rates={self.near_rates}: the store's corpus "
+                                   f"({type(getattr(store, 'corpus', None)).__name__}) has no align_rates_topk; "
+                                   "use a DeviceCorpus or a service.ShardedCorpus")
         # opt-in, never the default: duplicates by the TOLERANT count (include/tvz.h tvz_find_duplicates_tol)
         # instead of the reference's exact float64 equality; the verdict, the truncation at kth and the stored
         # duplicates all follow it.  Refused here, before any upload, where the store's corpus cannot do it.
@@ -360,7 +374,8 @@ class Inspector:
         out = []
         if len(scene_timestamps) < 2:
             return out
-        for vid, row_len, best_bin, votes, *_zero in self._near_rows(video_id, scene_timestamps):
+        rows, rated = self._near_rows(video_id, scene_timestamps)
+        for vid, row_len, best_bin, votes, *more in rows:
             if vid == video_id or row_len == 0:
                 continue
             # votes counts (query, row) pairs: cuts closer than eps can give more than either list holds
@@ -376,18 +391,27 @@ class Inspector:
                             "shift_seconds": float(best_bin) * self.near_eps, "jaccard": round(jacc, 4)})
                 if contain:
                     out[-1]["containment"] = round(score, 4)
+                if rated:                                                      # stored ~= rate x upload + shift
+                    out[-1]["rate"] = self.near_rates[int(more[0])]
         by = "containment" if self.near_score == "containment" else "jaccard"
         return sorted(out, key=lambda d: (-d[by], d["video_id"]))
 
     def _near_rows(self, video_id: int, scene_timestamps):
         """(video_id, row_len, best_bin, votes[, ...]) of the rows _near filters: every row of the table (near_top_k None), or
         the near_top_k best-aligned ones, selected on the device with min_score = floor(near_jaccard x 2^20) - a
-        superset of the float filter, since v / u >= j implies floor(v 2^20 / u) >= floor(j 2^20)."""
+        superset of the float filter, since v / u >= j implies floor(v 2^20 / u) >= floor(j 2^20).  -> (rows, rated):
+        rated where the fifth column is the index of the row's rate in near_rates (tvz_align_rates_topk)."""
         corpus = self.store.corpus
         if self.near_top_k is not None:
             one = 1 << 20
             min_score = max(0, min(one, int(self.near_jaccard * one)))          # int() floors: the value is >= 0
-            if self.near_any_offset:
+            rated = self.near_rates is not None
+            if rated:
+                rows, totals = corpus.align_rates_topk([scene_timestamps], eps=self.near_eps, rates=self.near_rates,
+                                                       max_offset=None, k=self.near_top_k, min_votes=self.near_min_votes,
+                                                       min_score=min_score, contain=self.near_score == "containment",
+                                                       exclude_ids=[int(video_id)])
+            elif self.near_any_offset:
                 rows, totals = corpus.align_wide_topk([scene_timestamps], eps=self.near_eps, max_offset=None,
                                                       k=self.near_top_k, min_votes=self.near_min_votes,
                                                       min_score=min_score, contain=self.near_score == "containment",
@@ -397,10 +421,10 @@ class Inspector:
                 rows, totals = corpus.align_topk([scene_timestamps], eps=self.near_eps, max_offset=self.near_max_offset,
                                                  k=self.near_top_k, min_score=min_score, exclude_ids=[int(video_id)], **kw)
             if int(totals[0]) >= 0:                                            # (refused: more than 4,095 cuts -> the walk)
-                return [r for r in rows[0] if r[0] >= 0]
+                return [r for r in rows[0] if r[0] >= 0], rated
             if not hasattr(corpus, "align"):                                   # (a rank corpus has no walk: no report)
-                return []
-        return corpus.align(scene_timestamps, eps=self.near_eps, max_offset=self.near_max_offset)
+                return [], False
+        return corpus.align(scene_timestamps, eps=self.near_eps, max_offset=self.near_max_offset), False
 
     def _progress(self, analysis_key, scene_timestamps, frames_done, total_frames, dups_to_report):
         if total_frames > 0 and frames_done > 0:                           # app.py:259-260

@@ -34,6 +34,9 @@ So has the search at any shift (`align_wide_topk`, Inspector(near_any_offset=Tru
 runs tvz_align_wide_topk_shards, RankCorpus sends ASK_NEAR_WIDE through the tick to `matcher.align_wide_topk`.  Its RCCL
 form (tvz_align_wide_topk_sharded) too has run on hardware at world size 1 only;
 tests/test_align_wide_sharded_cpu.py runs the exchange at world sizes 2 and 3 on gloo.
+
+The search for speed-changed copies (`align_rates_topk`, Inspector(near_rates=...)) has the first form only:
+ShardedCorpus runs tvz_align_rates_topk_shards.  RankCorpus has no ask kind for it and the launcher no switch yet.
 """
 from __future__ import annotations
 
@@ -295,8 +298,19 @@ class ShardedCorpus:
                                  dict(eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score,
                                       contain=contain))
 
+    def align_rates_topk(self, queries, *, eps: float, rates, max_offset=None, k: int = 16, min_votes: int = 1,
+                         min_score: int = 0, contain: bool = False, exclude_ids=None, max_query_len=None):
+        """DeviceCorpus.align_rates_topk over every shard - align_wide_topk for copies played at another speed, every
+        row kept once at the best of `rates`; rows of five columns, the last the rate's index: ONE library call
+        (tvz_align_rates_topk_shards), ONE copy back; more than 16 shards are grouped and re-merged by
+        tvz_align_rates_topk_merge, as align_topk does."""
+        return self._near_shards(tc.align_rates_topk_shards, tc.align_rates_topk_merge, tc.align_rates_topk_workspace_bytes,
+                                 queries, k, exclude_ids, max_query_len, dict(contain=contain),
+                                 dict(eps=eps, rates=tuple(rates), max_offset=max_offset, min_votes=min_votes,
+                                      min_score=min_score, contain=contain))
+
     def _near_shards(self, shards_call, merge_call, sizer, queries, k, exclude_ids, max_query_len, merge_kw, kw):
-        """What align_topk and align_wide_topk share: the inputs, the calling thread's workspace (`sizer`), one
+        """What align_topk, align_wide_topk and align_rates_topk share: the inputs, the calling thread's workspace (`sizer`), one
         `shards_call` per group of 16 shards, the groups' `merge_call`, the one copy back."""
         dev = self.dev
         d_q, d_off, Q, max_query_len, d_ex = tc.align_inputs(queries, exclude_ids, max_query_len, dev)
@@ -308,9 +322,12 @@ class ShardedCorpus:
                 _, rows, totals = shards_call(groups[0], d_q, d_off, max_query_len, **kw)
             else:
                 # more shards than one merge takes: every group's answer is a block again - its k rows, then its total
-                blocks = torch.zeros((len(groups), Q, k + 1, 4), dtype=torch.int32, device=dev)
+                # (rows of 4 columns, 5 with rates)
+                blocks = None
                 for g, part in enumerate(groups):
                     _, rows, totals = shards_call(part, d_q, d_off, max_query_len, **kw)
+                    if blocks is None:
+                        blocks = torch.zeros((len(groups), Q, k + 1, rows.shape[2]), dtype=torch.int32, device=dev)
                     blocks[g, :, :k] = rows
                     blocks[g, :, k, 0] = -1
                     blocks[g, :, k, 1] = totals
