@@ -623,6 +623,78 @@ int tvz_align_rates_topk_shards(tvz_corpus *const *shards, int32_t n_shards, con
                                 int32_t *d_blocks, int32_t *d_topk, int32_t *d_totals, void *d_workspace,
                                 size_t workspace_bytes, void *hip_stream);
 
+/* The alignment top-k at any shift WITH THE MATCHED SPAN of every hit, and a score over that span alone:
+ * tvz_align_rates_topk that also says WHERE the votes of the best bin lie - which part of the upload is the copy and
+ * which part of the stored video was taken - for the excerpt from the middle and the clip inside a compilation.
+ * (TVZ_VERSION unchanged: new exports only.)  The argument lists are those of the four tvz_align_rates_topk functions;
+ * the call with the single rate 1.0 is tvz_align_wide_topk with spans.  The contract is tvz_align_rates_topk's, word
+ * for word, with these changes:
+ *   span  : for a row the rates contract has chosen (best_bin, rate_index), with rho = h_rates[rate_index]:
+ *             s[0 .. nv) = the query's non-NaN values sorted ascending numerically;
+ *             x'_t = s[t] * rho, ONE IEEE multiplication, not contracted with the subtraction;
+ *             P = the pairs (row key c, index t) with floor((c - x'_t)/eps + 0.5) == best_bin - the vote's own
+ *                 expression, never a rewrite; |P| is the raw `votes`;
+ *             t_first = min t, t_last = max t over P;  nq = t_last - t_first + 1;
+ *             c_lo, c_hi = the smallest and the largest key in P;  nr = #{keys c of the row : c_lo <= c <= c_hi}.
+ *           Equal query values vote identically, -0.0 and +0.0 give the same difference, and infinities never vote:
+ *           t_first and t_last do not depend on how the sort orders equal values.  A hit has votes >= 1, so P is not
+ *           empty: 0 <= t_first <= t_last < nv, 1 <= nq <= nv, 1 <= nr <= row_len.
+ *   flags : 0 and TVZ_ALIGN_CONTAIN mean what they mean in tvz_align_wide_topk.  TVZ_ALIGN_LOCAL: v = min(votes, nq,
+ *           nr), u = nq + nr - v, score = (v << 20) / u - the Jaccard of the two sides INSIDE THE SPAN, in 0..2^20
+ *           (v <= 4095, u >= v >= 1), exact integer arithmetic.  A 400-cut compilation that holds a 20-cut clip of a
+ *           stored 400-cut film scores 20/780 by the Jaccard and 20/400 by the containment, and 2^20 here.  ONE vote
+ *           gives nq = nr = 1 and the score 2^20: under TVZ_ALIGN_LOCAL min_votes is what keeps chance pairs out.
+ *           TVZ_ALIGN_CONTAIN | TVZ_ALIGN_LOCAL (two score kinds) and any other bit: TVZ_ERR_INVALID.  The rate list
+ *           and the flags are refused before the handle is looked at.  The other calls keep refusing bit 2.
+ *   hit   : unchanged - v >= min_votes, score >= min_score, video_id != exclude_id - with v and score those of the
+ *           call's score kind.
+ *   order : ascending by the tuple (2^20 - score, video_id, best_bin as a signed number, row_len, votes, rate_index,
+ *           t_first, t_last, nr); rows equal in all nine are identical rows and are all kept.
+ *   d_out : int32[Q][k+1][8] = the k best rows as (video_id, row_len, best_bin, votes, rate_index, t_first, t_last,
+ *           nr), padding rows (-1, 0, 0, 0, 0, 0, 0, 0), and a last row (-1, n_hits, 0, ...); n_hits = INT32_MIN for a
+ *           refused query.  Rows are 32 bytes.
+ * Without TVZ_ALIGN_LOCAL columns 0..4 of every row equal tvz_align_rates_topk's block bit for bit; with the single
+ * rate 1.0, columns 0..3 equal tvz_align_wide_topk's.
+ * Workspace = tvz_match_tol_workspace_bytes(Q, max_query_len, max(total_query_keys, max_query_len))   (the sorted queries)
+ *           + 4 Q                                                                      (hit totals)
+ *           + max(6080, 95 Q) x k x 32                                                  (one kept list per sweep
+ *             block; a kept hit is the rates call's 24 bytes, ONE 32-bit word that holds t_first and t_last - 16 bits
+ *             each, both below 4,095 - and the 32-bit nr)
+ *           + alignment (each part to 256 B).
+ * A workspace below the fixed parts + one query of max_query_len values: TVZ_ERR_WORKSPACE with the bytes missing.
+ * Cost: tvz_align_rates_topk's, and for every row that passes min_votes and the exclusion - and, without
+ * TVZ_ALIGN_LOCAL, min_score - one more walk of the row at the single best bin (about one window's visit) and one
+ * pass over its keys that counts nr.
+ *
+ * tvz_align_span_topk_merge: d_gathered int32[n_lists][Q][k+1][8] -> d_topk int32[Q][k][8], d_totals int32[Q]:
+ * tvz_align_rates_topk_merge's rules with the nine-tuple order.  Under flags 0 and TVZ_ALIGN_CONTAIN the score is
+ * rebuilt from votes, nv and row_len as there; the three span columns are carried and take part in the order only.
+ * Under TVZ_ALIGN_LOCAL the score is rebuilt from votes, nq = t_last - t_first + 1 and nr in 64-bit integer
+ * arithmetic; a row with nq <= 0 or nr <= 0 is padding wherever it stands - nothing divides by zero.  Under every
+ * flag a row whose t_first or t_last lies outside 0..4,094 (the call writes none) is padding too: the kept hit holds
+ * 16 bits of each.  PRECONDITION: all lists were made with the same `flags` and the same rate list.  Totals, refusals
+ * and limits (n_lists 1..16, k 1..64, d_gathered and d_topk 16-byte aligned) as the rates merge; the flags are
+ * refused as the call refuses them.
+ * tvz_align_span_topk_shards: the shards of ONE process, as tvz_align_rates_topk_shards: d_blocks
+ * int32[n_shards][Q][k+1][8]; one workspace sized for ONE handle (tvz_align_span_topk_workspace_bytes).
+ * NOT YET: no _sharded (RCCL) form and no service switch - this block gets its RCCL form together with the rates
+ * block's. */
+#define TVZ_ALIGN_LOCAL 2u               /* flags of tvz_align_span_topk: score = the Jaccard inside the span */
+size_t tvz_align_span_topk_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k);
+int tvz_align_span_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
+                        int32_t max_query_len, double eps, double max_offset, const double *h_rates, int32_t n_rates,
+                        int32_t min_votes, int32_t min_score, uint32_t flags, const int32_t *d_exclude_ids, int32_t k,
+                        int32_t *d_out, void *d_workspace, size_t workspace_bytes, void *hip_stream);
+int tvz_align_span_topk_merge(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t k, uint32_t flags,
+                              const double *d_queries, const int64_t *d_q_offsets, int32_t *d_topk, int32_t *d_totals,
+                              void *hip_stream);
+int tvz_align_span_topk_shards(tvz_corpus *const *shards, int32_t n_shards, const double *d_queries,
+                               const int64_t *d_q_offsets, int32_t Q, int32_t max_query_len, double eps,
+                               double max_offset, const double *h_rates, int32_t n_rates, int32_t min_votes,
+                               int32_t min_score, uint32_t flags, const int32_t *d_exclude_ids, int32_t k,
+                               int32_t *d_blocks, int32_t *d_topk, int32_t *d_totals, void *d_workspace,
+                               size_t workspace_bytes, void *hip_stream);
+
 /* ------------------------------------------------------------------------
  * Opt-in TOLERANT duplicate match.  NOT the reference's verdict: db.py:79,85-91 match exact float64
  * values, and that stays the default everywhere (tolerance 0).  README.md:291 promises "0.1 second

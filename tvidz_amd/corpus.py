@@ -143,6 +143,41 @@ def align_rates_order_key(row, nv: int, contain: bool = False):
     return align_wide_order_key(row[:4], nv, contain) + (int(row[4]),)
 
 
+ALIGN_LOCAL = 2                             # include/tvz.h TVZ_ALIGN_LOCAL: tvz_align_span_topk's score inside the span
+
+
+def align_span_topk_workspace_bytes(Q: int, max_query_len: int, total_query_keys: int = 0, k: int = 16) -> int:
+    """tvz_align_span_topk_workspace_bytes: as align_wide_topk_workspace_bytes, with 32 bytes per kept hit."""
+    return int(_lib.load().tvz_align_span_topk_workspace_bytes(int(Q), int(max_query_len), int(total_query_keys), int(k)))
+
+
+def align_local_score(votes: int, nq: int, nr: int) -> int:
+    """The score tvz_align_span_topk orders by with TVZ_ALIGN_LOCAL: the Jaccard of the two sides inside the span, v /
+    (nq + nr - v) with v = min(votes, nq, nr), in 20-bit fixed point; 0 where a side is empty."""
+    nq, nr = int(nq), int(nr)
+    if nq <= 0 or nr <= 0:
+        return 0
+    v = min(int(votes), nq, nr)
+    return (v << 20) // (nq + nr - v)
+
+
+def align_span_order_key(row, nv: int, contain: bool = False, local: bool = False):
+    """Sort key of one (video_id, row_len, best_bin, votes, rate_index, t_first, t_last, nr) row of
+    tvz_align_span_topk: align_rates_order_key - scored inside the span with `local` - then the three span fields."""
+    vid, row_len, best_bin, votes, rate, t_first, t_last, nr = (int(x) for x in row)
+    if contain and local:
+        raise ValueError("contain and local are two score kinds: one of them")
+    if local:
+        head = (-align_local_score(votes, t_last - t_first + 1, nr), vid, best_bin, row_len, votes, rate)
+    else:
+        head = align_rates_order_key(row[:5], nv, contain)
+    return head + (t_first, t_last, nr)
+
+
+def _span_flags(contain: bool, local: bool) -> int:
+    return (ALIGN_CONTAIN if contain else 0) | (ALIGN_LOCAL if local else 0)
+
+
 def _rates(rates):
     """The rate list of the calls with rates -> (a host double array, its length).  What the list may hold is the
     library's to judge (1..ALIGN_MAX_RATES finite rates > 0)."""
@@ -403,6 +438,41 @@ class DeviceCorpus:
             self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps),
             _wide_offset(eps, max_offset), h_rates, n_rates, int(min_votes), int(min_score),
             ALIGN_CONTAIN if contain else 0, excl, int(k), out.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
+        return out
+
+    def align_span_topk(self, queries, *, eps: float, rates: Sequence[float] = (1.0,), max_offset: Optional[float] = None,
+                        k: int = 16, min_votes: int = 1, min_score: int = 0, contain: bool = False, local: bool = False,
+                        exclude_ids=None, max_query_len: Optional[int] = None):
+        """tvz_align_span_topk: align_rates_topk that also says WHERE the best bin's votes lie - (t_first, t_last), the
+        first and last voting index of the query's non-NaN values sorted ascending, and nr, the row's keys between the
+        smallest and the largest voting key.  `local=True` scores by the Jaccard inside that span (align_local_score)
+        and finds the copy that is partial on both sides; min_votes is then what keeps chance pairs out.  -> (rows
+        int32[Q, k, 8] of (video_id, row_len, best_bin, votes, rate_index, t_first, t_last, nr), padded with (-1, 0, ..);
+        totals int32[Q]); order: align_span_order_key."""
+        dev = torch.device("cuda", self.device)
+        d_q, d_off, Q, max_query_len, d_ex = align_inputs(queries, exclude_ids, max_query_len, dev)
+        ws = thread_workspace(self._tls, align_span_topk_workspace_bytes(Q, max_query_len, d_q.numel(), k), dev)
+        h = self.align_span_topk_block(d_q, d_off, max_query_len, eps=eps, rates=rates, max_offset=max_offset, k=k,
+                                       min_votes=min_votes, min_score=min_score, contain=contain, local=local,
+                                       d_exclude_ids=d_ex, workspace=ws).cpu().numpy()
+        return np.ascontiguousarray(h[:, :k]), np.ascontiguousarray(h[:, k, 1])
+
+    def align_span_topk_block(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, eps: float,
+                              rates: Sequence[float] = (1.0,), max_offset: Optional[float] = None, k: int,
+                              min_votes: int = 1, min_score: int = 0, contain: bool = False, local: bool = False,
+                              d_exclude_ids: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                              stream: Optional[torch.cuda.Stream] = None,
+                              workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """tvz_align_span_topk, device in / device out: enqueue Q queries -> the block int32 [Q, k+1, 8]."""
+        Q = d_q_offsets.numel() - 1
+        dev, s, ws, excl = self._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace,
+                                         align_span_topk_workspace_bytes(Q, max_query_len, d_queries.numel(), k))
+        out = _out(out, (Q, k + 1, 8), dev)
+        h_rates, n_rates = _rates(rates)
+        _lib.check(self.lib.tvz_align_span_topk(
+            self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps),
+            _wide_offset(eps, max_offset), h_rates, n_rates, int(min_votes), int(min_score),
+            _span_flags(contain, local), excl, int(k), out.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
         return out
 
     # ---- batched, device resident ----
@@ -806,6 +876,44 @@ def align_rates_topk_shards(shards: Sequence["DeviceCorpus"], d_queries: torch.T
             handles, len(shards), d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps),
             _wide_offset(eps, max_offset), h_rates, n_rates, int(min_votes), int(min_score),
             ALIGN_CONTAIN if contain else 0, excl, int(k), blocks.data_ptr(), rows.data_ptr(), totals.data_ptr(),
+            ws.data_ptr(), ws.numel(), s.cuda_stream))
+    return blocks, rows, totals
+
+
+def align_span_topk_merge(gathered: torch.Tensor, k: int, d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
+                          contain: bool = False, local: bool = False, stream: Optional[torch.cuda.Stream] = None, out=None):
+    """tvz_align_span_topk_merge: align_rates_topk_merge for the blocks of align_span_topk_block, int32 [R,Q,k+1,8] ->
+    (rows int32 [Q,k,8], totals int32 [Q]); every list sorted by align_span_order_key of the SAME `contain` / `local`.
+    With `local` the score is rebuilt from votes, t_last - t_first + 1 and nr; otherwise the span is only carried."""
+    R, Q, k1, w = gathered.shape
+    if k1 != k + 1 or w != 8 or gathered.dtype != torch.int32 or not gathered.is_contiguous():
+        raise RuntimeError("gathered must be a contiguous int32 [R,Q,k+1,8]")
+    rows, totals = _topk_out(out, Q, k, 8, gathered.device)
+    s = stream if stream is not None else torch.cuda.current_stream(gathered.device)
+    with torch.cuda.device(gathered.device):
+        _lib.check(_lib.load().tvz_align_span_topk_merge(gathered.data_ptr(), R, Q, int(k), _span_flags(contain, local),
+                                                         d_queries.data_ptr(), d_q_offsets.data_ptr(), rows.data_ptr(),
+                                                         totals.data_ptr(), s.cuda_stream))
+    return rows, totals
+
+
+def align_span_topk_shards(shards: Sequence["DeviceCorpus"], d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
+                           max_query_len: int, *, eps: float, rates: Sequence[float] = (1.0,),
+                           max_offset: Optional[float] = None, k: int, workspace: torch.Tensor, min_votes: int = 1,
+                           min_score: int = 0, contain: bool = False, local: bool = False,
+                           d_exclude_ids: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None):
+    """tvz_align_span_topk on every handle of ONE device + its merge behind one library call
+    (tvz_align_span_topk_shards): -> (blocks int32 [R,Q,k+1,8], rows int32 [Q,k,8], totals int32 [Q]).  `workspace`:
+    align_span_topk_workspace_bytes (its size is the library's to judge, as align_topk_shards')."""
+    Q = d_q_offsets.numel() - 1
+    dev, s, ws, excl = shards[0]._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace, None)
+    handles, blocks, rows, totals = _shards_out(shards, Q, k, 8, dev)
+    h_rates, n_rates = _rates(rates)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().tvz_align_span_topk_shards(
+            handles, len(shards), d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps),
+            _wide_offset(eps, max_offset), h_rates, n_rates, int(min_votes), int(min_score),
+            _span_flags(contain, local), excl, int(k), blocks.data_ptr(), rows.data_ptr(), totals.data_ptr(),
             ws.data_ptr(), ws.numel(), s.cuda_stream))
     return blocks, rows, totals
 

@@ -52,10 +52,17 @@
 // x'_min)] hold per rate, with x'_min / x'_max the products of s[0] / s[m - 1].  The resume positions are one rate's:
 // a rate's highest window searches.  The kept hit carries the rate's index behind the votes (ArHit) and the block
 // has a fifth column; the selection and the merge carry it and never read it.
+//
+// The span (al_sweep<.., true, true, true>, tvz_align_span_topk): where the votes of the row's best bin
+// lie.  When the rate loop ends the wave knows the row's best bin and rate; a row that can still be a hit is walked
+// once more at that single bin (al_span) for the first and last voting index of the sorted query and the count of
+// row keys between the smallest and the largest voting key.  The kept hit carries them behind the rate's index (AsHit),
+// the block has eight columns, and with TVZ_ALIGN_LOCAL the score is the Jaccard of the two sides inside the span.
 #pragma once
 #include "tvz_match_kernels.h"
 #include "tvz_tol_kernels.h"
 #include "tvz_wave.h"
+#include <type_traits>
 
 namespace {
 
@@ -76,6 +83,7 @@ constexpr int kAwWidth = 1024;                         // bins of a window other
 constexpr int kAwResume = 512;                         // keys of a row whose resume position is kept (a multiple of 64)
 constexpr uint32_t kAwContain = 1u;                    // TVZ_ALIGN_CONTAIN
 constexpr int kArMaxRates = 8;                         // TVZ_ALIGN_MAX_RATES
+constexpr uint32_t kAsLocal = 2u;                      // TVZ_ALIGN_LOCAL
 
 // the rates of tvz_align_rates_topk, a kernel argument by value: r[0 .. n), each finite and > 0 (the host's check)
 struct AlRates {
@@ -136,8 +144,8 @@ __device__ __forceinline__ int al_lo(const double *s, int m, double c, double ep
 
 // ---- a kept hit, in the three layouts-----------------------------------------------------------------------------
 // Lists<N>: N hits as a structure of arrays, in static LDS; Parts / ConstParts: the same arrays in the workspace,
-// [Q][n_lists][k] each.  load / store take any of them.  kCols: the int32 columns of the hit's block row; the fifth
-// (ArHit's alone) is extra().
+// [Q][n_lists][k] each.  load / store take any of them.  kCols: the int32 columns of the hit's block row; column 4 + i
+// (ArHit's one, AsHit's four) is extra(i); make() takes the first, the rate's index, and with_more() those behind it.
 
 // the bounded call's: 16 bytes, ordered as (w, p)
 struct AlHit {
@@ -230,7 +238,7 @@ struct ArHit {
         return make_int4(pad ? -1 : (int32_t)(w & 0x7fffffffu), pad ? 0 : (int32_t)(p & 0xffffffffu),
                          pad ? 0 : (int32_t)(p >> 32) - kAwMaxB, pad ? 0 : (int32_t)v);
     }
-    __device__ __forceinline__ int32_t extra() const { return is_pad() ? 0 : (int32_t)r; }      // rate_index
+    __device__ __forceinline__ int32_t extra(int /* 0 */) const { return is_pad() ? 0 : (int32_t)r; }      // rate_index
     static __device__ __forceinline__ ArHit select(bool c, const ArHit &a, const ArHit &b) {
         return {c ? a.w : b.w, c ? a.p : b.p, c ? a.v : b.v, c ? a.r : b.r};
     }
@@ -246,6 +254,63 @@ struct ArHit {
         l.p[i] = p;
         l.v[i] = v;
         l.r[i] = r;
+    }
+};
+
+// the call with spans' (DESIGN.md 4.13): ArHit and where the best bin's votes lie - the first and the last voting
+// index of the sorted query in ONE word (t_first << 16 | t_last, each at most 4094: the word orders as the pair) and
+// the row keys inside the voting keys' range -, 32 bytes, ordered as (w, p, v, r, t, n)
+struct AsHit {
+    unsigned long long w, p;       // as AwHit's
+    uint32_t v, r, t, n;           // the raw votes; the rate's index; t_first << 16 | t_last; nr
+    static constexpr int kCols = 8;
+    template <int N> struct Lists { unsigned long long w[N], p[N]; uint32_t v[N], r[N], t[N], n[N]; };
+    struct Parts { unsigned long long *w, *p; uint32_t *v, *r, *t, *n; };
+    struct ConstParts { const unsigned long long *w, *p; const uint32_t *v, *r, *t, *n; };
+    static __device__ __forceinline__ AsHit make(uint32_t score, int32_t vid, int bin, uint32_t row_len, uint32_t votes,
+                                                 uint32_t rate) {           // (the span: with_more)
+        return {((unsigned long long)(kAlScoreOne - score) << 31) | (unsigned long long)((uint32_t)vid & 0x7fffffffu),
+                ((unsigned long long)(uint32_t)(bin + kAwMaxB) << 32) | row_len, votes, rate, 0u, 0u};
+    }
+    // the columns behind the rate's: x = (t_first, t_last, nr), the first two below 2^16
+    __device__ __forceinline__ AsHit with_more(const uint32_t *x) const { return {w, p, v, r, (x[0] << 16) | x[1], x[2]}; }
+    static __device__ __forceinline__ AsHit pad() { return {kAlPad, kAlPad, ~0u, ~0u, ~0u, ~0u}; }
+    __device__ __forceinline__ bool is_pad() const { return w == kAlPad; }
+    static __device__ __forceinline__ bool le(const AsHit &a, const AsHit &b) {
+        if (a.w != b.w) return a.w < b.w;
+        if (a.p != b.p) return a.p < b.p;
+        if (a.v != b.v) return a.v < b.v;
+        if (a.r != b.r) return a.r < b.r;
+        return a.t < b.t || (a.t == b.t && a.n <= b.n);
+    }
+    __device__ __forceinline__ int4 row() const {      // (video_id, row_len, best_bin, votes)
+        const bool pad = is_pad();
+        return make_int4(pad ? -1 : (int32_t)(w & 0x7fffffffu), pad ? 0 : (int32_t)(p & 0xffffffffu),
+                         pad ? 0 : (int32_t)(p >> 32) - kAwMaxB, pad ? 0 : (int32_t)v);
+    }
+    __device__ __forceinline__ int32_t extra(int i) const {      // rate_index, t_first, t_last, nr
+        const uint32_t x = i == 0 ? r : i == 1 ? t >> 16 : i == 2 ? t & 0xffffu : n;
+        return is_pad() ? 0 : (int32_t)x;
+    }
+    static __device__ __forceinline__ AsHit select(bool c, const AsHit &a, const AsHit &b) {
+        return {c ? a.w : b.w, c ? a.p : b.p, c ? a.v : b.v, c ? a.r : b.r, c ? a.t : b.t, c ? a.n : b.n};
+    }
+    __device__ __forceinline__ AsHit lane(int src) const {
+        return {__shfl(w, src), __shfl(p, src), __shfl(v, src), __shfl(r, src), __shfl(t, src), __shfl(n, src)};
+    }
+    __device__ __forceinline__ AsHit shift_up() const {
+        return {__shfl_up(w, 1), __shfl_up(p, 1), __shfl_up(v, 1), __shfl_up(r, 1), __shfl_up(t, 1), __shfl_up(n, 1)};
+    }
+    template <class L> static __device__ __forceinline__ AsHit load(const L &l, int64_t i) {
+        return {l.w[i], l.p[i], l.v[i], l.r[i], l.t[i], l.n[i]};
+    }
+    template <class L> __device__ __forceinline__ void store(L &l, int64_t i) const {
+        l.w[i] = w;
+        l.p[i] = p;
+        l.v[i] = v;
+        l.r[i] = r;
+        l.t[i] = t;
+        l.n[i] = n;
     }
 };
 
@@ -295,9 +360,9 @@ template <class Hit, int N> __device__ __forceinline__ void al_merge_waves(Hit &
     for (int j = 1; j < N / 64; ++j) al_take(kept, Hit::load(s, j * 64 + lane), k, lane);
 }
 
-// One wave writes a query's block int32[k+1][kCols]: k rows (video_id, row_len, best_bin, votes[, rate_index]), padding
-// (-1, 0, 0, 0[, 0]), then (-1, n_hits, 0, 0[, 0]) with n_hits = INT32_MIN for a refused query.  Word stores: a row of
-// five columns is not 16-byte aligned
+// One wave writes a query's block int32[k+1][kCols]: k rows (video_id, row_len, best_bin, votes[, the hit's extra
+// columns]), padding (-1, 0, 0, 0[, 0 ..]), then (-1, n_hits, 0, 0[, 0 ..]) with n_hits = INT32_MIN for a refused
+// query.  Word stores: a row of five columns is not 16-byte aligned
 template <class Hit> __device__ __forceinline__ void al_write_block(const Hit &kept, int32_t *out, int k, int lane, int32_t n_hits) {
     constexpr int kCols = Hit::kCols;
     if (lane < k) {
@@ -306,30 +371,89 @@ template <class Hit> __device__ __forceinline__ void al_write_block(const Hit &k
         out[lane * kCols + 1] = o.y;
         out[lane * kCols + 2] = o.z;
         out[lane * kCols + 3] = o.w;
-        if constexpr (kCols == 5) out[lane * kCols + 4] = kept.extra();
+        if constexpr (kCols > 4) {
+#pragma unroll
+            for (int i = 4; i < kCols; ++i) out[lane * kCols + i] = kept.extra(i - 4);
+        }
     }
     if (lane == 0) {
         out[k * kCols + 0] = -1;
         out[k * kCols + 1] = n_hits;
         out[k * kCols + 2] = 0;
         out[k * kCols + 3] = 0;
-        if constexpr (kCols == 5) out[k * kCols + 4] = 0;
+        if constexpr (kCols > 4) {
+#pragma unroll
+            for (int i = 4; i < kCols; ++i) out[k * kCols + i] = 0;
+        }
     }
 }
 
 // ---- the sweep and the selection -------------------------------------------------------------------------------
+// the bin of a lane-wise best (count << 33 | 2^33 - 1 - order)
+__device__ __forceinline__ int al_best_bin(unsigned long long best) {
+    const uint32_t order = (uint32_t)(kAlOrderMask - (best & kAlOrderMask));
+    const int mag = (int)(order >> 1);
+    return (order & 1u) ? mag : -mag;
+}
+
+// The span of a row's best bin (include/tvz.h, tvz_align_span_topk): over the pairs (key c, index t of the sorted
+// query) whose vote - the sweep's own expression at the rate rho - is `bin`, the smallest and the largest t, and nr =
+// the row's keys inside [smallest voting key, largest voting key].  The window loop's walk with the one bin as the
+// window and nothing noted but the four extremes, a wave reduction, then a second lane-strided pass that counts: no
+// LDS beyond the sorted query, no barrier.  The bin has votes (the caller's v >= 1), so both ranges are non-empty.
+struct AlSpan {
+    int t_first, t_last;
+    uint32_t nr;
+};
+__device__ __forceinline__ AlSpan al_span(const int64_t *__restrict__ rk, int len, const double *s, int m, double eps, int bin,
+                                          double rho, int lane) {
+    const double bd = (double)bin;
+    int t_first = m, t_last = -1;
+    double c_lo = __longlong_as_double(0x7ff0000000000000ll), c_hi = -c_lo;
+    for (int j = lane; j < len; j += 64) {
+        const double c = __longlong_as_double(rk[j]);
+        for (int t = al_lo<true>(s, m, c, eps, bd, rho); t < m; ++t) {
+            const double d = al_bin(c, al_x<true>(s, t, rho), eps);
+            if (!(d >= bd)) break;                                        // behind the bin (or NaN there)
+            if (!(d <= bd)) continue;                                     // (never, behind al_lo)
+            t_first = t < t_first ? t : t_first;
+            t_last = t > t_last ? t : t_last;
+            c_lo = c < c_lo ? c : c_lo;
+            c_hi = c > c_hi ? c : c_hi;
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const int tf = __shfl_xor(t_first, off), tl = __shfl_xor(t_last, off);
+        const double lo = __shfl_xor(c_lo, off), hi = __shfl_xor(c_hi, off);
+        t_first = tf < t_first ? tf : t_first;
+        t_last = tl > t_last ? tl : t_last;
+        c_lo = lo < c_lo ? lo : c_lo;
+        c_hi = hi > c_hi ? hi : c_hi;
+    }
+    uint32_t nr = 0;
+    for (int j = lane; j < len; j += 64) {
+        const double c = __longlong_as_double(rk[j]);
+        nr += c >= c_lo && c <= c_hi ? 1u : 0u;
+    }
+    for (int off = 32; off > 0; off >>= 1) nr += __shfl_xor(nr, off);
+    return {t_first, t_last, nr};
+}
+
 // grid = (row blocks, Q).  Sorted query q: sv[at .. at + m) with at = q_offsets[q] - q_offsets[0], m = qm[q]
 // (ts_tol_sort_kernel).  part: the kept lists, block bx writes list bx; totals[q] (zeroed by the preparation) += the
 // block's hits, one atomic.  width = aw_width(B); dynamic LDS: aw_lds_bytes(lds_keys, B, width).  0 <= B <= kAwMaxB,
 // and B <= 2047 where !kWindowed (the host refuses anything else before the launch).  kRates: the row is walked once
-// per rate of `rates` (1 .. kArMaxRates of them) and its best rate kept; without, `rates` is never read.
-template <class Hit, bool kWindowed, bool kRates = false>
+// per rate of `rates` (1 .. kArMaxRates of them) and its best rate kept; without, `rates` is never read.  kSpan (with
+// kRates; Hit = AsHit): a row that can be a hit is walked once more at its best bin and rate for the span (al_span),
+// and with `local` the score is the Jaccard inside the span.
+template <class Hit, bool kWindowed, bool kRates = false, bool kSpan = false>
 __device__ __forceinline__ void al_sweep(const Row *__restrict__ rows, int64_t n_rows, const int64_t *__restrict__ keys,
                                          const double *__restrict__ sv, const int64_t *__restrict__ q_offsets,
                                          const int32_t *__restrict__ qm, int32_t lds_keys, double eps, int32_t B, int32_t width,
                                          int32_t min_votes, int32_t min_score, bool contain,
                                          const int32_t *__restrict__ exclude_ids, int32_t k, typename Hit::Parts part,
-                                         int32_t n_lists, int32_t *__restrict__ totals, const AlRates &rates = AlRates{}) {
+                                         int32_t n_lists, int32_t *__restrict__ totals, const AlRates &rates = AlRates{},
+                                         bool local = false) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ typename Hit::template Lists<kAlWaves * 64> s_kept;
     __shared__ int32_t s_nhits;
@@ -471,8 +595,26 @@ __device__ __forceinline__ void al_sweep(const Row *__restrict__ rows, int64_t n
         v = v < rl ? v : rl;
         if (v >= (uint32_t)min_votes && row.vid != excl) {                  // min_votes >= 1: v >= 1, so m, rl, u >= 1
             const uint32_t u = contain ? ((uint32_t)m < rl ? (uint32_t)m : rl) : (uint32_t)m + rl - v;
-            const uint32_t score = (v << 20) / u;                           // v <= 4095: the shift fits 32 bits; v <= u
-            if (score >= (uint32_t)min_score) {
+            uint32_t score = (v << 20) / u;                                 // v <= 4095: the shift fits 32 bits; v <= u
+            if constexpr (kSpan) {
+                // the span needs the row's best bin and rate, so it is one more walk of the row: only for a row that
+                // can still be a hit - the local score is made from the span, every other score decides first
+                if (local || score >= (uint32_t)min_score) {
+                    const int bin = al_best_bin(best);
+                    const AlSpan sp = al_span(rk, row.len, s, m, eps, bin, rates.r[best_rate], lane);
+                    if (local) {                                            // 1 <= nq <= m, 1 <= nr <= rl: v only shrinks
+                        const uint32_t nq = (uint32_t)(sp.t_last - sp.t_first + 1);
+                        v = votes < nq ? votes : nq;
+                        v = v < sp.nr ? v : sp.nr;
+                        score = (v << 20) / (nq + sp.nr - v);
+                    }
+                    if (v >= (uint32_t)min_votes && score >= (uint32_t)min_score) {
+                        const uint32_t x[3] = {(uint32_t)sp.t_first, (uint32_t)sp.t_last, sp.nr};
+                        ++n_hits;
+                        al_insert(kept, Hit::make(score, row.vid, bin, rl, votes, best_rate).with_more(x), k, lane);
+                    }
+                }
+            } else if (score >= (uint32_t)min_score) {
                 const uint32_t order = (uint32_t)(kAlOrderMask - (best & kAlOrderMask));
                 const int mag = (int)(order >> 1);
                 ++n_hits;
@@ -517,7 +659,7 @@ __device__ __forceinline__ void al_reduce(typename Hit::ConstParts part, int32_t
     if (wv == 0) al_write_block(kept, d_out + (int64_t)q * (k + 1) * Hit::kCols, k, lane, refused ? INT32_MIN : totals[q]);
 }
 
-// The six entry points only forward.  part_w / part_p: uint64[Q][n_lists][k], part_v / part_r: uint32[Q][n_lists][k].
+// The eight entry points only forward.  part_w / part_p: uint64[Q][n_lists][k], part_v / part_r: uint32[Q][n_lists][k].
 __global__ __launch_bounds__(kAlBlock) void ts_align_topk_kernel(
     const Row *__restrict__ rows, int64_t n_rows, const int64_t *__restrict__ keys, const double *__restrict__ sv,
     const int64_t *__restrict__ q_offsets, const int32_t *__restrict__ qm, int32_t lds_keys, double eps, int32_t B,
@@ -571,6 +713,29 @@ __global__ __launch_bounds__(kAlReduceBlock) void ts_alignr_reduce_kernel(
     al_reduce<ArHit>(ArHit::ConstParts{part_w, part_p, part_v, part_r}, n_lists, k, qm, lds_keys, totals, d_out);
 }
 
+// (part_t / part_n: uint32[Q][n_lists][k], the span's two index ends in one word and its count of row keys)
+__global__ __launch_bounds__(kAlBlock) void ts_aligns_sweep_kernel(
+    const Row *__restrict__ rows, int64_t n_rows, const int64_t *__restrict__ keys, const double *__restrict__ sv,
+    const int64_t *__restrict__ q_offsets, const int32_t *__restrict__ qm, int32_t lds_keys, double eps, int32_t B,
+    int32_t width, AlRates rates, int32_t min_votes, int32_t min_score, uint32_t flags,
+    const int32_t *__restrict__ exclude_ids, int32_t k, unsigned long long *__restrict__ part_w,
+    unsigned long long *__restrict__ part_p, uint32_t *__restrict__ part_v, uint32_t *__restrict__ part_r,
+    uint32_t *__restrict__ part_t, uint32_t *__restrict__ part_n, int32_t n_lists, int32_t *__restrict__ totals) {
+    al_sweep<AsHit, true, true, true>(rows, n_rows, keys, sv, q_offsets, qm, lds_keys, eps, B, width, min_votes, min_score,
+                                      (flags & kAwContain) != 0u, exclude_ids, k,
+                                      AsHit::Parts{part_w, part_p, part_v, part_r, part_t, part_n}, n_lists, totals, rates,
+                                      (flags & kAsLocal) != 0u);
+}
+
+__global__ __launch_bounds__(kAlReduceBlock) void ts_aligns_reduce_kernel(
+    const unsigned long long *__restrict__ part_w, const unsigned long long *__restrict__ part_p,
+    const uint32_t *__restrict__ part_v, const uint32_t *__restrict__ part_r, const uint32_t *__restrict__ part_t,
+    const uint32_t *__restrict__ part_n, int32_t n_lists, int32_t k, const int32_t *__restrict__ qm, int32_t lds_keys,
+    const int32_t *__restrict__ totals, int32_t *__restrict__ d_out) {
+    al_reduce<AsHit>(AsHit::ConstParts{part_w, part_p, part_v, part_r, part_t, part_n}, n_lists, k, qm, lds_keys, totals,
+                     d_out);
+}
+
 // ---- the merge of the shards' blocks (tvz_align_topk_merge, tvz_align_wide_topk_merge, tvz_align_rates_topk_merge) ---------------------------
 constexpr int kAlMergeBlock = 256;
 constexpr int kAlMergeWaves = kAlMergeBlock / 64;      // queries per block: a wave each
@@ -590,11 +755,46 @@ constexpr int kAlMergeMaxLists = 16;                   // one n_hits per lane, f
 // bin of 12 bits: blocks with a bin outside +-2047 (the wide call's) are AwHit's alone.
 // ArHit's blocks have rows of five columns, 20 bytes - read and written word by word, only the base pointers are
 // aligned -, and the fifth, the rate's index, is carried into the hit's order and out again, never interpreted.
+// AsHit's have eight, 32 bytes, read and written the same way; its three span columns are carried likewise, and under
+// TVZ_ALIGN_LOCAL the score is rebuilt from them (al_row_score).
+
+// A block row's score under the call's score kind, rebuilt from its columns (x: the columns
+// behind the rate's; nv: the query's non-NaN count), and whether the row is live.  AsHit's with TVZ_ALIGN_LOCAL: v =
+// min(votes, nq, nr), u = nq + nr - v with nq = t_last - t_first + 1, in 64 bits - a block is the caller's memory, and
+// any columns must do no harm; nq <= 0 or nr <= 0 is padding.  An AsHit row whose t_first or t_last lies outside 0 ..
+// kAlMaxLen - 1 - the call writes none - does not fit the hit's word and is padding under every flag.
+struct AlRowScore {
+    uint32_t score;
+    bool hit;
+};
+template <class Hit>
+__device__ __forceinline__ AlRowScore al_row_score(int32_t vid, uint32_t rl, uint32_t votes, const uint32_t *x, uint32_t nv,
+                                                   bool contain, bool local) {
+    if constexpr (std::is_same_v<Hit, AsHit>) {
+        const bool fits = x[0] < (uint32_t)kAlMaxLen && x[1] < (uint32_t)kAlMaxLen;
+        if (local || !fits) {
+            const long long nq = (long long)x[1] - (long long)x[0] + 1, nr = (int32_t)x[2];
+            long long v = (long long)votes < nq ? (long long)votes : nq;
+            v = v < nr ? v : nr;
+            const bool hit = vid >= 0 && fits && nq > 0 && nr > 0;         // then 0 <= v <= u = nq + nr - v, u >= 1
+            return {hit ? (uint32_t)((v << 20) / (nq + nr - v)) : 0u, hit};
+        }
+    }
+    uint32_t v = votes < nv ? votes : nv;
+    v = v < rl ? v : rl;
+    const uint32_t u = contain ? (nv < rl ? nv : rl) : nv + rl - v;
+    const bool hit = vid >= 0 && u != 0u;
+    const uint32_t score = hit ? (v << 20) / u : 0u;                       // v <= nv <= 4095: the shift fits 32 bits
+    return {score, hit};
+}
 
 template <class Hit>
 __device__ __forceinline__ void al_merge_blocks(const int32_t *__restrict__ gathered, int32_t n_lists, int32_t Q, int32_t k,
                                                 const double *__restrict__ queries, const int64_t *__restrict__ q_offsets,
-                                                bool contain, int32_t *__restrict__ d_topk, int32_t *__restrict__ d_totals) {
+                                                bool contain, int32_t *__restrict__ d_topk, int32_t *__restrict__ d_totals,
+                                                bool local = false) {
+    constexpr int kExtra = Hit::kCols - 4;                         // the columns behind the first four: the rate's index,
+    constexpr int kMore = kExtra > 1 ? kExtra - 1 : 0;             // ... and those behind it
     const int lane = threadIdx.x & 63;
     const int q = blockIdx.x * kAlMergeWaves + (threadIdx.x >> 6);
     if (q >= Q) return;                                            // wave-uniform
@@ -619,11 +819,14 @@ __device__ __forceinline__ void al_merge_blocks(const int32_t *__restrict__ gath
         for (int l0 = 0; l0 < n_lists; l0 += kAlReduceLd) {        // wave-uniform
             int4 row[kAlReduceLd];
             uint32_t rate[kAlReduceLd];
+            uint32_t more[kAlReduceLd][kMore ? kMore : 1];
 #pragma unroll
             for (int j = 0; j < kAlReduceLd; ++j) {                // the loads of kAlReduceLd lists in flight together
                 const int l = l0 + j;
                 rate[j] = 0u;
-                if constexpr (Hit::kCols == 4) {
+#pragma unroll
+                for (int i = 0; i < kMore; ++i) more[j][i] = 0u;
+                if constexpr (kExtra == 0) {
                     row[j] = l < n_lists && lane < k ? blocks[((int64_t)l * Q + q) * k1 + lane] : make_int4(-1, 0, 0, 0);
                 } else {
                     row[j] = make_int4(-1, 0, 0, 0);
@@ -631,22 +834,24 @@ __device__ __forceinline__ void al_merge_blocks(const int32_t *__restrict__ gath
                         const int32_t *p = gathered + (((int64_t)l * Q + q) * k1 + lane) * Hit::kCols;
                         row[j] = make_int4(p[0], p[1], p[2], p[3]);
                         rate[j] = (uint32_t)p[4];
+#pragma unroll
+                        for (int i = 0; i < kMore; ++i) more[j][i] = (uint32_t)p[5 + i];
                     }
                 }
             }
 #pragma unroll
             for (int j = 0; j < kAlReduceLd; ++j) {
                 const uint32_t rl = (uint32_t)row[j].y, votes = (uint32_t)row[j].w;
-                uint32_t v = votes < nv ? votes : nv;
-                v = v < rl ? v : rl;
-                const uint32_t u = contain ? (nv < rl ? nv : rl) : nv + rl - v;
-                const bool hit = row[j].x >= 0 && u != 0u;
-                const uint32_t score = hit ? (v << 20) / u : 0u;   // v <= nv <= 4095: the shift fits 32 bits
-                al_take_live(kept, Hit::make(score, row[j].x, row[j].z, rl, votes, rate[j]), __ballot(hit), k, lane);
+                const AlRowScore sc = al_row_score<Hit>(row[j].x, rl, votes, more[j], nv, contain, local);
+                if constexpr (kMore == 0)
+                    al_take_live(kept, Hit::make(sc.score, row[j].x, row[j].z, rl, votes, rate[j]), __ballot(sc.hit), k, lane);
+                else
+                    al_take_live(kept, Hit::make(sc.score, row[j].x, row[j].z, rl, votes, rate[j]).with_more(more[j]),
+                                 __ballot(sc.hit), k, lane);
             }
         }
     }
-    if constexpr (Hit::kCols == 4) {
+    if constexpr (kExtra == 0) {
         if (lane < k) reinterpret_cast<int4 *>(d_topk)[(int64_t)q * k + lane] = kept.row();
     } else if (lane < k) {
         const int4 o = kept.row();
@@ -655,12 +860,13 @@ __device__ __forceinline__ void al_merge_blocks(const int32_t *__restrict__ gath
         out[1] = o.y;
         out[2] = o.z;
         out[3] = o.w;
-        out[4] = kept.extra();
+#pragma unroll
+        for (int i = 0; i < kExtra; ++i) out[4 + i] = kept.extra(i);
     }
     if (lane == 0) d_totals[q] = refused ? INT32_MIN : (int32_t)(total > INT32_MAX ? INT32_MAX : total);
 }
 
-// The three entry points only forward.
+// The four entry points only forward.
 __global__ __launch_bounds__(kAlMergeBlock) void ts_align_topk_merge_kernel(
     const int32_t *__restrict__ gathered, int32_t n_lists, int32_t Q, int32_t k, const double *__restrict__ queries,
     const int64_t *__restrict__ q_offsets, int32_t *__restrict__ d_topk, int32_t *__restrict__ d_totals) {
@@ -679,6 +885,14 @@ __global__ __launch_bounds__(kAlMergeBlock) void ts_alignr_merge_kernel(
     const double *__restrict__ queries, const int64_t *__restrict__ q_offsets, int32_t *__restrict__ d_topk,
     int32_t *__restrict__ d_totals) {
     al_merge_blocks<ArHit>(gathered, n_lists, Q, k, queries, q_offsets, (flags & kAwContain) != 0u, d_topk, d_totals);
+}
+
+__global__ __launch_bounds__(kAlMergeBlock) void ts_aligns_merge_kernel(
+    const int32_t *__restrict__ gathered, int32_t n_lists, int32_t Q, int32_t k, uint32_t flags,
+    const double *__restrict__ queries, const int64_t *__restrict__ q_offsets, int32_t *__restrict__ d_topk,
+    int32_t *__restrict__ d_totals) {
+    al_merge_blocks<AsHit>(gathered, n_lists, Q, k, queries, q_offsets, (flags & kAwContain) != 0u, d_topk, d_totals,
+                           (flags & kAsLocal) != 0u);
 }
 
 }  // namespace

@@ -2012,10 +2012,11 @@ static int tvz_match_tol_topk_impl(tvz_corpus *c, const double *d_queries, const
 // ---- alignment top-k, bounded and at any shift (tvz_align_kernels.h) ------------------------------------------
 namespace {
 
-// Workspace of the three calls, in front of the sorted queries (TolWs, which takes the rest): the queries' hit totals
+// Workspace of the four calls, in front of the sorted queries (TolWs, which takes the rest): the queries' hit totals
 // and one kept list per sweep block, as a structure of arrays - k words and k payloads, for the wide call k raw votes
-// behind them and for the call with rates k rate indexes behind those (AlHit::Parts, AwHit::Parts, ArHit::Parts: 16,
-// 20 and 24 bytes per kept hit).  The sizing function knows no row count: the
+// behind them, for the call with rates k rate indexes behind those and for the call with spans k index pairs and k key
+// counts behind those (AlHit::Parts, AwHit::Parts, ArHit::Parts, AsHit::Parts: 16, 20, 24 and 32 bytes per kept hit).
+// The sizing function knows no row count: the
 // lists are sized by the grid's upper bound, as the tolerant top-k's are.  The sharded forms (n_blocks > 0: the
 // communicator's ranks, at least 1) add the local block and the gathered ones behind them; the plain calls
 // (n_blocks = 0) have neither.
@@ -2024,12 +2025,15 @@ struct AlignTopkWs {
     unsigned long long *part_w = nullptr;  // [Q][blocks][k]
     unsigned long long *part_p = nullptr;  // [Q][blocks][k]
     uint32_t *part_v = nullptr;            // [Q][blocks][k], wide and rates only
-    uint32_t *part_r = nullptr;            // [Q][blocks][k], rates only
+    uint32_t *part_r = nullptr;            // [Q][blocks][k], rates and spans only
+    uint32_t *part_t = nullptr;            // [Q][blocks][k], spans only
+    uint32_t *part_n = nullptr;            // [Q][blocks][k], spans only
     int32_t *local = nullptr;              // [Q][k+1][4]
     int32_t *gathered = nullptr;           // [n_blocks][Q][k+1][4]
 };
 
-AlignTopkWs align_topk_ws_layout(Carver &cv, int32_t Q, int32_t k, bool wide, int32_t n_blocks, bool rates = false) {
+AlignTopkWs align_topk_ws_layout(Carver &cv, int32_t Q, int32_t k, bool wide, int32_t n_blocks, bool rates = false,
+                                 bool span = false) {
     AlignTopkWs w;
     const size_t lists = (size_t)tol_topk_max_lists(Q) * (size_t)k;
     w.totals = cv.take<int32_t>((size_t)Q);
@@ -2037,6 +2041,10 @@ AlignTopkWs align_topk_ws_layout(Carver &cv, int32_t Q, int32_t k, bool wide, in
     w.part_p = cv.take<unsigned long long>(lists);
     if (wide) w.part_v = cv.take<uint32_t>(lists);
     if (rates) w.part_r = cv.take<uint32_t>(lists);
+    if (span) {
+        w.part_t = cv.take<uint32_t>(lists);
+        w.part_n = cv.take<uint32_t>(lists);
+    }
     if (n_blocks > 0) {
         const size_t block = (size_t)Q * (size_t)(k + 1) * 4;
         w.local = cv.take<int32_t>(block);
@@ -2045,14 +2053,15 @@ AlignTopkWs align_topk_ws_layout(Carver &cv, int32_t Q, int32_t k, bool wide, in
     return w;
 }
 
-size_t align_topk_ws_bytes(int32_t Q, int64_t keys, int32_t k, bool wide, int32_t n_blocks, bool rates = false) {
+size_t align_topk_ws_bytes(int32_t Q, int64_t keys, int32_t k, bool wide, int32_t n_blocks, bool rates = false,
+                           bool span = false) {
     Carver cv(nullptr);
-    align_topk_ws_layout(cv, Q, k, wide, n_blocks, rates);
+    align_topk_ws_layout(cv, Q, k, wide, n_blocks, rates, span);
     return cv.fixed() + tol_ws_bytes(Q, keys);
 }
 
-// what tvz_align_topk_merge, tvz_align_wide_topk_merge and tvz_align_rates_topk_merge refuse, apart from their
-// pointers and flags
+// what tvz_align_topk_merge, tvz_align_wide_topk_merge, tvz_align_rates_topk_merge and tvz_align_span_topk_merge
+// refuse, apart from their pointers and flags
 int check_align_merge(int32_t n_lists, int32_t k) {
     if (n_lists < 1 || n_lists > kAlMergeMaxLists)
         return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment top-k merge: %d lists outside 1..%d", (int)n_lists, kAlMergeMaxLists);
@@ -2065,9 +2074,10 @@ bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 
 
 // what tells tvz_align_topk, tvz_align_wide_topk and tvz_align_rates_topk apart on the host.  The sweeps' argument
 // lists differ (the window width, the flags, the rates, the third and fourth list), so the launches below name the
-// kernels themselves, chosen by `wide` and `rates` (rates: wide too, with the rate loop and a block row of 5 columns).
+// kernels themselves, chosen by `wide`, `rates` and `span` (rates: wide too, with the rate loop and a block row of 5
+// columns; span: rates too, with the span pass and a block row of 8).
 struct AlignTopkForm {
-    bool wide, rates;
+    bool wide, rates, span;
     int cols;                        // int32 columns of a block row
     const char *what, *sizer;        // the call in messages; the sizing function the workspace message names
     const char *sharded_sizer;       // ... and the one it names for the sharded form (n_ranks >= 1)
@@ -2076,18 +2086,41 @@ struct AlignTopkForm {
     uint32_t flags;                  // the permitted ones
     int static_lds;                  // of the sweep
 };
-constexpr AlignTopkForm kAlignBounded{false, false, 4, "alignment top-k", "tvz_align_topk_workspace_bytes",
+constexpr AlignTopkForm kAlignBounded{false, false, false, 4, "alignment top-k", "tvz_align_topk_workspace_bytes",
                                       "tvz_align_topk_sharded_workspace_bytes", kAlignMaxBins, nullptr, 0u,
                                       al_static_lds<AlHit>()};
-constexpr AlignTopkForm kAlignWide{true, false, 4, "wide alignment top-k", "tvz_align_wide_topk_workspace_bytes",
+constexpr AlignTopkForm kAlignWide{true, false, false, 4, "wide alignment top-k", "tvz_align_wide_topk_workspace_bytes",
                                    "tvz_align_wide_topk_sharded_workspace_bytes", 2 * kAwMaxB + 1, "TVZ_ALIGN_WIDE_MAX_B",
                                    kAwContain, al_static_lds<AwHit>()};
 // (no RCCL form yet: the sharded sizer is never named)
-constexpr AlignTopkForm kAlignRates{true, true, 5, "alignment top-k with rates", "tvz_align_rates_topk_workspace_bytes",
+constexpr AlignTopkForm kAlignRates{true, true, false, 5, "alignment top-k with rates", "tvz_align_rates_topk_workspace_bytes",
                                     "tvz_align_rates_topk_workspace_bytes", 2 * kAwMaxB + 1, "TVZ_ALIGN_WIDE_MAX_B",
                                     kAwContain, al_static_lds<ArHit>()};
+constexpr AlignTopkForm kAlignSpan{true, true, true, 8, "alignment top-k with spans", "tvz_align_span_topk_workspace_bytes",
+                                   "tvz_align_span_topk_workspace_bytes", 2 * kAwMaxB + 1, "TVZ_ALIGN_WIDE_MAX_B",
+                                   kAwContain | kAsLocal, al_static_lds<AsHit>()};
 
-// The three calls: sort -> sweep that keeps the k best -> per-query selection.  rates: f.rates' list, checked by the
+// the flags of tvz_align_span_topk and its merge: TVZ_ALIGN_CONTAIN or TVZ_ALIGN_LOCAL, not both (two score kinds)
+int check_align_span_flags(uint32_t flags) {
+    TVZ_REQUIRE((flags & ~kAlignSpan.flags) == 0u, "%s: unknown flag bits 0x%x", kAlignSpan.what,
+                (unsigned)(flags & ~kAlignSpan.flags));
+    TVZ_REQUIRE(flags != (kAwContain | kAsLocal), "%s: TVZ_ALIGN_CONTAIN and TVZ_ALIGN_LOCAL are two score kinds: one of them",
+                kAlignSpan.what);
+    return TVZ_OK;
+}
+
+// the limits of every call that need neither the handle nor the device
+int check_align_limits(const AlignTopkForm &f, const AlignCall &a, int32_t k, int32_t max_query_len) {
+    TVZ_REQUIRE(a.min_votes >= 1, "%s: min_votes %d below 1", f.what, (int)a.min_votes);
+    TVZ_REQUIRE(a.min_score >= 0 && a.min_score <= kAlScoreOne, "%s: min_score %d outside 0..%d", f.what, (int)a.min_score,
+                kAlScoreOne);
+    if (k < 1 || k > kAlMaxK) return tvz::fail(TVZ_ERR_UNSUPPORTED, "%s: k=%d outside 1..%d", f.what, (int)k, kAlMaxK);
+    if (max_query_len > kAlMaxLen)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "%s: max_query_len %d above %d", f.what, (int)max_query_len, kAlMaxLen);
+    return TVZ_OK;
+}
+
+// The four calls: sort -> sweep that keeps the k best -> per-query selection.  rates: f.rates' list, checked by the
 // caller (check_align_rates), NULL otherwise.  n_ranks = 0: d_out is the caller's.
 // n_ranks >= 1: the workspace also holds the local block and n_ranks gathered ones (the form's sharded sizing
 // function); d_out = NULL writes the block into the workspace's own, and `blocks` is told where it went and where the
@@ -2101,15 +2134,10 @@ int align_topk_run(const AlignTopkForm &f, tvz_corpus *c, const Batch &b, const 
     if (int rc = check_align_bins(a.eps, a.max_offset, f.max_bins, f.wide_limit, &B)) return rc;
     if (f.wide)                      // (the bounded call has no flags argument)
         TVZ_REQUIRE((flags & ~f.flags) == 0u, "%s: unknown flag bits 0x%x", f.what, (unsigned)(flags & ~f.flags));
-    TVZ_REQUIRE(a.min_votes >= 1, "%s: min_votes %d below 1", f.what, (int)a.min_votes);
-    TVZ_REQUIRE(a.min_score >= 0 && a.min_score <= kAlScoreOne, "%s: min_score %d outside 0..%d", f.what, (int)a.min_score,
-                kAlScoreOne);
-    if (k < 1 || k > kAlMaxK) return tvz::fail(TVZ_ERR_UNSUPPORTED, "%s: k=%d outside 1..%d", f.what, (int)k, kAlMaxK);
-    if (max_query_len > kAlMaxLen)
-        return tvz::fail(TVZ_ERR_UNSUPPORTED, "%s: max_query_len %d above %d", f.what, (int)max_query_len, kAlMaxLen);
+    if (int rc = check_align_limits(f, a, k, max_query_len)) return rc;
     if (Q == 0) return TVZ_OK;
     Carver cv(ws.p);
-    const AlignTopkWs w = align_topk_ws_layout(cv, Q, k, f.wide, n_ranks, f.rates);
+    const AlignTopkWs w = align_topk_ws_layout(cv, Q, k, f.wide, n_ranks, f.rates, f.span);
     const int32_t lds_keys = std::max(max_query_len, 1);
     const int32_t width = aw_width(B);   // (the bounded call's B <= 2047: all its bins, and no resume positions)
     const size_t lds = aw_lds_bytes(lds_keys, B, width);
@@ -2133,7 +2161,12 @@ int align_topk_run(const AlignTopkForm &f, tvz_corpus *c, const Batch &b, const 
     const int n_blocks = n_rows ? (int)std::min<int64_t>(tvz::ceil_div(n_rows, (int64_t)kAlWaves), tol_topk_max_blocks(Q)) : 0;
     const dim3 grid((unsigned)n_blocks, (unsigned)Q);
     if (n_blocks) {
-        if (f.rates)
+        if (f.span)
+            hipLaunchKernelGGL(ts_aligns_sweep_kernel, grid, dim3(kAlBlock), lds, st, c->rows.p, n_rows, c->keys.p, t.ws.sv,
+                               b.d_q_offsets, t.ws.qm, lds_keys, a.eps, B, width, *rates, a.min_votes, a.min_score, flags,
+                               b.d_exclude_ids, k, w.part_w, w.part_p, w.part_v, w.part_r, w.part_t, w.part_n, n_blocks,
+                               w.totals);
+        else if (f.rates)
             hipLaunchKernelGGL(ts_alignr_sweep_kernel, grid, dim3(kAlBlock), lds, st, c->rows.p, n_rows, c->keys.p, t.ws.sv,
                                b.d_q_offsets, t.ws.qm, lds_keys, a.eps, B, width, *rates, a.min_votes, a.min_score, flags,
                                b.d_exclude_ids, k, w.part_w, w.part_p, w.part_v, w.part_r, n_blocks, w.totals);
@@ -2147,7 +2180,10 @@ int align_topk_run(const AlignTopkForm &f, tvz_corpus *c, const Batch &b, const 
                                w.part_w, w.part_p, n_blocks, w.totals);
         TVZ_HIP(hipGetLastError());
     }
-    if (f.rates)
+    if (f.span)
+        hipLaunchKernelGGL(ts_aligns_reduce_kernel, dim3((unsigned)Q), dim3(kAlReduceBlock), 0, st, w.part_w, w.part_p, w.part_v,
+                           w.part_r, w.part_t, w.part_n, n_blocks, k, t.ws.qm, lds_keys, w.totals, d_out);
+    else if (f.rates)
         hipLaunchKernelGGL(ts_alignr_reduce_kernel, dim3((unsigned)Q), dim3(kAlReduceBlock), 0, st, w.part_w, w.part_p, w.part_v,
                            w.part_r, n_blocks, k, t.ws.qm, lds_keys, w.totals, d_out);
     else if (f.wide)
@@ -2204,19 +2240,24 @@ static int tvz_align_rates_topk_impl(tvz_corpus *c, const double *d_queries, con
 }
 
 // The merge of any call's blocks (tvz_align_topk_merge: f = kAlignBounded, flags = 0; tvz_align_wide_topk_merge;
-// tvz_align_rates_topk_merge, whose rows have f.cols = 5 columns).
+// tvz_align_rates_topk_merge and tvz_align_span_topk_merge, whose rows have f.cols = 5 and 8 columns).
 static int align_merge_impl(const AlignTopkForm &f, const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t k,
                             uint32_t flags, const double *d_queries, const int64_t *d_q_offsets, int32_t *d_topk,
                             int32_t *d_totals, void *hip_stream) {
     TVZ_REQUIRE(Q >= 0, "Q=%d is negative", (int)Q);
     if (int rc = check_align_merge(n_lists, k)) return rc;
     TVZ_REQUIRE((flags & ~f.flags) == 0u, "%s merge: unknown flag bits 0x%x", f.what, (unsigned)(flags & ~f.flags));
+    if (f.span)
+        if (int rc = check_align_span_flags(flags)) return rc;
     if (Q == 0) return TVZ_OK;
     TVZ_REQUIRE(d_gathered && d_queries && d_q_offsets && d_topk && d_totals, "NULL argument");
     TVZ_REQUIRE(aligned16(d_gathered) && aligned16(d_topk), "alignment top-k merge: the blocks and d_topk must be 16-byte aligned");
     const dim3 grid((unsigned)tvz::ceil_div(Q, kAlMergeWaves));
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    if (f.rates)
+    if (f.span)
+        hipLaunchKernelGGL(ts_aligns_merge_kernel, grid, dim3(kAlMergeBlock), 0, st, d_gathered, n_lists, Q, k, flags,
+                           d_queries, d_q_offsets, d_topk, d_totals);
+    else if (f.rates)
         hipLaunchKernelGGL(ts_alignr_merge_kernel, grid, dim3(kAlMergeBlock), 0, st, d_gathered, n_lists, Q, k, flags,
                            d_queries, d_q_offsets, d_topk, d_totals);
     else if (f.wide)
@@ -2229,7 +2270,7 @@ static int align_merge_impl(const AlignTopkForm &f, const int32_t *d_gathered, i
 }
 
 // The shards of one process, for any call (tvz_align_topk_shards: f = kAlignBounded, flags = 0;
-// tvz_align_wide_topk_shards; tvz_align_rates_topk_shards with the checked `rates`).
+// tvz_align_wide_topk_shards; tvz_align_rates_topk_shards and tvz_align_span_topk_shards with the checked `rates`).
 static int align_shards_impl(const AlignTopkForm &f, tvz_corpus *const *shards, int32_t n_shards, const Batch &b,
                              const AlignCall &a, uint32_t flags, int32_t k, int32_t *d_blocks, int32_t *d_topk,
                              int32_t *d_totals, Workspace ws, void *hip_stream, const AlRates *rates = nullptr) {
@@ -2531,6 +2572,63 @@ TVZ_EXPORT int tvz_align_rates_topk_shards(tvz_corpus *const *shards, int32_t n_
                                            int32_t *d_blocks, int32_t *d_topk, int32_t *d_totals, void *d_workspace,
                                            size_t workspace_bytes, void *hip_stream) {
     TVZ_GUARDED(tvz_align_rates_topk_shards_impl(
+        shards, n_shards, Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids},
+        AlignCall{eps, max_offset, min_votes, min_score}, h_rates, n_rates, flags, k, d_blocks, d_topk, d_totals,
+        Workspace{d_workspace, workspace_bytes}, hip_stream));
+}
+
+TVZ_EXPORT size_t tvz_align_span_topk_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k) {
+    if (Q < 0 || max_query_len < 0 || total_query_keys < 0 || k < 1) return 0;
+    const int64_t keys = total_query_keys > 0 ? total_query_keys : (int64_t)Q * max_query_len;
+    return align_topk_ws_bytes(Q, std::max<int64_t>(keys, max_query_len), k, true, 0, true, true);
+}
+
+// the rates, the flags and the limits are refused before the handle is looked at
+static int tvz_align_span_topk_impl(tvz_corpus *c, const Batch &b, const AlignCall &a, const double *h_rates, int32_t n_rates,
+                                    uint32_t flags, int32_t k, int32_t *d_out, Workspace ws, void *hip_stream) {
+    AlRates rates;
+    if (int rc = check_align_rates(h_rates, n_rates, &rates)) return rc;
+    if (int rc = check_align_span_flags(flags)) return rc;
+    if (int rc = check_align_limits(kAlignSpan, a, k, b.max_query_len)) return rc;
+    return align_topk_run(kAlignSpan, c, b, a, flags, k, d_out, ws, 0, hip_stream, nullptr, &rates);
+}
+
+TVZ_EXPORT int tvz_align_span_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
+                                   int32_t max_query_len, double eps, double max_offset, const double *h_rates,
+                                   int32_t n_rates, int32_t min_votes, int32_t min_score, uint32_t flags,
+                                   const int32_t *d_exclude_ids, int32_t k, int32_t *d_out, void *d_workspace,
+                                   size_t workspace_bytes, void *hip_stream) {
+    TVZ_GUARDED(tvz_align_span_topk_impl(
+        c, Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids},
+        AlignCall{eps, max_offset, min_votes, min_score}, h_rates, n_rates, flags, k, d_out,
+        Workspace{d_workspace, workspace_bytes}, hip_stream));
+}
+
+TVZ_EXPORT int tvz_align_span_topk_merge(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t k, uint32_t flags,
+                                         const double *d_queries, const int64_t *d_q_offsets, int32_t *d_topk,
+                                         int32_t *d_totals, void *hip_stream) {
+    TVZ_GUARDED(align_merge_impl(kAlignSpan, d_gathered, n_lists, Q, k, flags, d_queries, d_q_offsets, d_topk, d_totals,
+                                 hip_stream));
+}
+
+static int tvz_align_span_topk_shards_impl(tvz_corpus *const *shards, int32_t n_shards, const Batch &b, const AlignCall &a,
+                                           const double *h_rates, int32_t n_rates, uint32_t flags, int32_t k,
+                                           int32_t *d_blocks, int32_t *d_topk, int32_t *d_totals, Workspace ws,
+                                           void *hip_stream) {
+    AlRates rates;
+    if (int rc = check_align_rates(h_rates, n_rates, &rates)) return rc;
+    if (int rc = check_align_span_flags(flags)) return rc;
+    if (int rc = check_align_limits(kAlignSpan, a, k, b.max_query_len)) return rc;
+    return align_shards_impl(kAlignSpan, shards, n_shards, b, a, flags, k, d_blocks, d_topk, d_totals, ws, hip_stream, &rates);
+}
+
+TVZ_EXPORT int tvz_align_span_topk_shards(tvz_corpus *const *shards, int32_t n_shards, const double *d_queries,
+                                          const int64_t *d_q_offsets, int32_t Q, int32_t max_query_len, double eps,
+                                          double max_offset, const double *h_rates, int32_t n_rates, int32_t min_votes,
+                                          int32_t min_score, uint32_t flags, const int32_t *d_exclude_ids, int32_t k,
+                                          int32_t *d_blocks, int32_t *d_topk, int32_t *d_totals, void *d_workspace,
+                                          size_t workspace_bytes, void *hip_stream) {
+    TVZ_GUARDED(tvz_align_span_topk_shards_impl(
         shards, n_shards, Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids},
         AlignCall{eps, max_offset, min_votes, min_score}, h_rates, n_rates, flags, k, d_blocks, d_topk, d_totals,
         Workspace{d_workspace, workspace_bytes}, hip_stream));

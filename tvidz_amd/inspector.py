@@ -36,6 +36,7 @@ import uuid
 from concurrent.futures import ThreadPoolExecutor
 from typing import Callable, Dict, List, Optional
 
+import numpy as np
 import torch
 
 from . import scene
@@ -85,7 +86,7 @@ class Inspector:
                  near_jaccard: float = 0.8, slot_bytes: int = 64 << 20, n_slots: Optional[int] = None,
                  profile: bool = False, match_tolerance: float = 0.0, near_top_k: Optional[int] = None,
                  near_any_offset: bool = False, near_score: str = "jaccard", near_min_votes: int = 1,
-                 near_rates=None):
+                 near_rates=None, near_spans: bool = False):
         self.store = store
         # opt-in: the near-duplicate report from the K best-aligned rows the device keeps (tvz_align_topk) instead of
         # one row per corpus row walked here.  None: the walk, exactly as before.  Refused here where the store's
@@ -105,8 +106,8 @@ class Inspector:
         # Defaults: the bounded search and the Jaccard, exactly as before.
         self.near_any_offset = bool(near_any_offset)
         self.near_score, self.near_min_votes = near_score, int(near_min_votes)
-        if near_score not in ("jaccard", "containment"):
-            raise ValueError(f"near_score must be 'jaccard' or 'containment', got {near_score!r}")
+        if near_score not in ("jaccard", "containment", "local"):
+            raise ValueError(f"near_score must be 'jaccard', 'containment' or 'local', got {near_score!r}")
         if self.near_min_votes < 1:
             raise ValueError(f"near_min_votes must be >= 1, got {near_min_votes!r}")
         if near_score == "containment" and not self.near_any_offset:
@@ -130,6 +131,22 @@ class Inspector:
             if not hasattr(getattr(store, "corpus", None), "align_rates_topk"):
                 raise RuntimeError(f"near_rates={self.near_rates}: the store's corpus "
                                    f"({type(getattr(store, 'corpus', None)).__name__}) has no align_rates_topk; "
+                                   "use a DeviceCorpus or a service.ShardedCorpus")
+        # opt-in: where the copy is (tvz_align_span_topk) - every entry gains "upload_span" and "stored_span", the first
+        # and the last aligned cut on either side in seconds - and, with near_score="local", the score over that span
+        # alone, which finds the copy that is partial on BOTH sides (a clip inside a compilation).  One aligned pair
+        # scores 1.0 by construction, so "local" needs near_min_votes >= 2.  Neither set: nothing changes.
+        self.near_spans = bool(near_spans)
+        if near_score == "local" or self.near_spans:
+            what = "near_score='local'" if near_score == "local" else "near_spans=True"
+            if not self.near_any_offset or self.near_top_k is None:
+                raise ValueError(f"{what} needs near_any_offset=True and near_top_k")
+            if near_score == "local" and self.near_min_votes < 2:
+                raise ValueError(f"near_score='local' needs near_min_votes >= 2 (one aligned pair scores 1.0), "
+                                 f"got {near_min_votes!r}")
+            if not hasattr(getattr(store, "corpus", None), "align_span_topk"):
+                raise RuntimeError(f"{what}: the store's corpus "
+                                   f"({type(getattr(store, 'corpus', None)).__name__}) has no align_span_topk; "
                                    "use a DeviceCorpus or a service.ShardedCorpus")
         # opt-in, never the default: duplicates by the TOLERANT count (include/tvz.h tvz_find_duplicates_tol)
         # instead of the reference's exact float64 equality; the verdict, the truncation at kth and the stored
@@ -375,38 +392,60 @@ class Inspector:
         if len(scene_timestamps) < 2:
             return out
         rows, rated = self._near_rows(video_id, scene_timestamps)
+        local = self.near_score == "local"
+        cuts = None                                                            # the upload's non-NaN cuts, sorted
         for vid, row_len, best_bin, votes, *more in rows:
             if vid == video_id or row_len == 0:
                 continue
+            spanned = len(more) == 4                                           # (rate_index, t_first, t_last, nr)
+            if local and not spanned:                                          # (the walk has no span: no local score)
+                continue
             # votes counts (query, row) pairs: cuts closer than eps can give more than either list holds
             v = min(int(votes), len(scene_timestamps), int(row_len))
+            jacc = v / float(len(scene_timestamps) + row_len - v)
+            if local:                                                          # the two sides inside the span
+                nq, nr = int(more[2]) - int(more[1]) + 1, int(more[3])
+                v = min(int(votes), nq, nr)
             if v < self.near_min_votes and self.near_min_votes > 1:
                 continue
-            jacc = v / float(len(scene_timestamps) + row_len - v)
             contain = self.near_score == "containment"
-            score = v / float(min(len(scene_timestamps), row_len)) if contain else jacc
+            score = v / float(nq + nr - v) if local else v / float(min(len(scene_timestamps), row_len)) if contain else jacc
             if score >= self.near_jaccard:
                 v = self.store.get_video_by_id(int(vid))
                 out.append({"filename": v.filename if v else None, "video_id": int(vid),
                             "shift_seconds": float(best_bin) * self.near_eps, "jaccard": round(jacc, 4)})
-                if contain:
-                    out[-1]["containment"] = round(score, 4)
+                if contain or local:
+                    out[-1][self.near_score] = round(score, 4)
                 if rated:                                                      # stored ~= rate x upload + shift
                     out[-1]["rate"] = self.near_rates[int(more[0])]
-        by = "containment" if self.near_score == "containment" else "jaccard"
+                if spanned:
+                    if cuts is None:
+                        cuts = np.sort(np.asarray(scene_timestamps, dtype=np.float64))
+                        cuts = cuts[~np.isnan(cuts)]
+                    rate = self.near_rates[int(more[0])] if rated else 1.0
+                    first, last = float(cuts[int(more[1])]), float(cuts[int(more[2])])
+                    out[-1]["upload_span"] = [first, last]
+                    out[-1]["stored_span"] = [rate * first + out[-1]["shift_seconds"], rate * last + out[-1]["shift_seconds"]]
+        by = self.near_score if self.near_score in ("containment", "local") else "jaccard"
         return sorted(out, key=lambda d: (-d[by], d["video_id"]))
 
     def _near_rows(self, video_id: int, scene_timestamps):
         """(video_id, row_len, best_bin, votes[, ...]) of the rows _near filters: every row of the table (near_top_k None), or
         the near_top_k best-aligned ones, selected on the device with min_score = floor(near_jaccard x 2^20) - a
         superset of the float filter, since v / u >= j implies floor(v 2^20 / u) >= floor(j 2^20).  -> (rows, rated):
-        rated where the fifth column is the index of the row's rate in near_rates (tvz_align_rates_topk)."""
+        rated where the fifth column is the index of the row's rate in near_rates (tvz_align_rates_topk); rows of eight
+        columns carry the span behind it (tvz_align_span_topk)."""
         corpus = self.store.corpus
         if self.near_top_k is not None:
             one = 1 << 20
             min_score = max(0, min(one, int(self.near_jaccard * one)))          # int() floors: the value is >= 0
             rated = self.near_rates is not None
-            if rated:
+            if self.near_spans or self.near_score == "local":
+                rows, totals = corpus.align_span_topk([scene_timestamps], eps=self.near_eps, rates=self.near_rates or (1.0,),
+                                                      max_offset=None, k=self.near_top_k, min_votes=self.near_min_votes,
+                                                      min_score=min_score, contain=self.near_score == "containment",
+                                                      local=self.near_score == "local", exclude_ids=[int(video_id)])
+            elif rated:
                 rows, totals = corpus.align_rates_topk([scene_timestamps], eps=self.near_eps, rates=self.near_rates,
                                                        max_offset=None, k=self.near_top_k, min_votes=self.near_min_votes,
                                                        min_score=min_score, contain=self.near_score == "containment",

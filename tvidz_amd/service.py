@@ -37,6 +37,8 @@ tests/test_align_wide_sharded_cpu.py runs the exchange at world sizes 2 and 3 on
 
 The search for speed-changed copies (`align_rates_topk`, Inspector(near_rates=...)) has the first form only:
 ShardedCorpus runs tvz_align_rates_topk_shards.  RankCorpus has no ask kind for it and the launcher no switch yet.
+The same holds for the search with spans (`align_span_topk`, Inspector(near_spans=True, near_score="local")):
+ShardedCorpus runs tvz_align_span_topk_shards, and nothing else knows it yet.
 """
 from __future__ import annotations
 
@@ -309,8 +311,19 @@ class ShardedCorpus:
                                  dict(eps=eps, rates=tuple(rates), max_offset=max_offset, min_votes=min_votes,
                                       min_score=min_score, contain=contain))
 
+    def align_span_topk(self, queries, *, eps: float, rates=(1.0,), max_offset=None, k: int = 16, min_votes: int = 1,
+                        min_score: int = 0, contain: bool = False, local: bool = False, exclude_ids=None,
+                        max_query_len=None):
+        """DeviceCorpus.align_span_topk over every shard - align_rates_topk with the span of every hit, scored inside
+        it with `local`; rows of eight columns: ONE library call (tvz_align_span_topk_shards), ONE copy back; more than
+        16 shards are grouped and re-merged by tvz_align_span_topk_merge, as align_topk does."""
+        return self._near_shards(tc.align_span_topk_shards, tc.align_span_topk_merge, tc.align_span_topk_workspace_bytes,
+                                 queries, k, exclude_ids, max_query_len, dict(contain=contain, local=local),
+                                 dict(eps=eps, rates=tuple(rates), max_offset=max_offset, min_votes=min_votes,
+                                      min_score=min_score, contain=contain, local=local))
+
     def _near_shards(self, shards_call, merge_call, sizer, queries, k, exclude_ids, max_query_len, merge_kw, kw):
-        """What align_topk, align_wide_topk and align_rates_topk share: the inputs, the calling thread's workspace (`sizer`), one
+        """What align_topk, align_wide_topk, align_rates_topk and align_span_topk share: the inputs, the calling thread's workspace (`sizer`), one
         `shards_call` per group of 16 shards, the groups' `merge_call`, the one copy back."""
         dev = self.dev
         d_q, d_off, Q, max_query_len, d_ex = tc.align_inputs(queries, exclude_ids, max_query_len, dev)
@@ -322,7 +335,7 @@ class ShardedCorpus:
                 _, rows, totals = shards_call(groups[0], d_q, d_off, max_query_len, **kw)
             else:
                 # more shards than one merge takes: every group's answer is a block again - its k rows, then its total
-                # (rows of 4 columns, 5 with rates)
+                # (rows of 4 columns, 5 with rates, 8 with spans)
                 blocks = None
                 for g, part in enumerate(groups):
                     _, rows, totals = shards_call(part, d_q, d_off, max_query_len, **kw)
