@@ -1,9 +1,10 @@
 // Stand-alone host program (its own main) for tests/test_align_topk_sharded_host_cpu.py: the sizing and carving code of
-// the alignment top-k - plain, sharded and wide, one layout -, built for the HOST only with -fsanitize=address,undefined and run without a GPU.  It
-// includes the library's translation unit, so the functions under test are the product's own, not copies.
-//   - walks align_topk_ws_layout + tol_ws_layout over a real host buffer at aligned and misaligned bases, for
-//     tvz_align_topk, its sharded form and tvz_align_wide_topk: every region lies inside the buffer of the sizing
-//     function's byte count, in order, none overlapping, and is written to its end - so each sizing export equals the walk;
+// the alignment top-k - every form of the table, plain and sharded, one layout -, built for the HOST only with
+// -fsanitize=address,undefined and run without a GPU.  It includes the library's translation unit, so the functions
+// under test are the product's own, not copies.
+//   - walks align_topk_ws_layout + tol_ws_layout over a real host buffer at aligned and misaligned bases, for the four
+//     forms and the sharded forms of the first two: every region lies inside the buffer of the sizing function's byte
+//     count, in order, none overlapping, and is written to its end - so each sizing export equals the walk;
 //   - the exported sizing functions: the sharded size = the plain one + the blocks, monotone in every argument;
 //   - the refusals of the new entry points that return before any HIP call.
 #include <cstdio>
@@ -27,28 +28,42 @@ struct Region {
     size_t bytes;
 };
 
-// wide: tvz_align_wide_topk (n_ranks = 0: it has no sharded form)
-void carve(int32_t Q, int32_t max_len, int64_t keys, int32_t k, bool wide, int32_t n_ranks, size_t misalign) {
-    const size_t need = wide      ? tvz_align_wide_topk_workspace_bytes(Q, max_len, keys, k)
-                        : n_ranks ? tvz_align_topk_sharded_workspace_bytes(Q, max_len, keys, k, n_ranks)
-                                  : tvz_align_topk_workspace_bytes(Q, max_len, keys, k);
+// the form's sizing export for this many ranks (0: the plain call); only the first two forms have a sharded one
+size_t sized(AlignForm form, int32_t Q, int32_t max_len, int64_t keys, int32_t k, int32_t n_ranks) {
+    switch (form) {
+    case kAlignBounded:
+        return n_ranks ? tvz_align_topk_sharded_workspace_bytes(Q, max_len, keys, k, n_ranks)
+                       : tvz_align_topk_workspace_bytes(Q, max_len, keys, k);
+    case kAlignWide:
+        return n_ranks ? tvz_align_wide_topk_sharded_workspace_bytes(Q, max_len, keys, k, n_ranks)
+                       : tvz_align_wide_topk_workspace_bytes(Q, max_len, keys, k);
+    case kAlignRates: return tvz_align_rates_topk_workspace_bytes(Q, max_len, keys, k);
+    default: return tvz_align_span_topk_workspace_bytes(Q, max_len, keys, k);
+    }
+}
+
+void carve(AlignForm form, int32_t Q, int32_t max_len, int64_t keys, int32_t k, int32_t n_ranks, size_t misalign) {
+    const AlignTopkForm &f = kAlignForms[form];
+    const size_t need = sized(form, Q, max_len, keys, k, n_ranks);
     CHECK(need > 0);
     std::vector<unsigned char> buf(need + 512);
     unsigned char *base = buf.data() + misalign;
     Carver cv(base);
-    const AlignTopkWs w = align_topk_ws_layout(cv, Q, k, wide, n_ranks);
+    const AlignTopkWs w = align_topk_ws_layout(cv, f, Q, k, n_ranks);
     {   // the sizing export is the same walk from NULL, + the sorted queries' part
         Carver from_null(nullptr);
-        align_topk_ws_layout(from_null, Q, k, wide, n_ranks);
+        align_topk_ws_layout(from_null, f, Q, k, n_ranks);
         CHECK(need == from_null.fixed() + tol_ws_bytes(Q, std::max<int64_t>(keys > 0 ? keys : (int64_t)Q * max_len, max_len)));
     }
     const int64_t room = tol_ws_room(Q, need - cv.fixed());
     CHECK(room >= std::max<int64_t>(keys, max_len));
-    const size_t lists = (size_t)tol_topk_max_lists(Q) * (size_t)k, block = (size_t)Q * (size_t)(k + 1) * 16;
+    const size_t lists = (size_t)tol_topk_max_lists(Q) * (size_t)k, block = (size_t)Q * (size_t)(k + 1) * 4 * f.cols;
     std::vector<Region> r = {{(unsigned char *)w.totals, (size_t)Q * 4}, {(unsigned char *)w.part_w, lists * 8},
                              {(unsigned char *)w.part_p, lists * 8}};
-    CHECK((w.part_v != nullptr) == wide);
-    if (wide) r.push_back({(unsigned char *)w.part_v, lists * 4});
+    for (int i = 0; i < 4; ++i) {    // the form's uint32 lists and no others: a kept hit is 16 + 4 * part32 bytes
+        CHECK((w.part32[i] != nullptr) == (i < f.part32));
+        if (w.part32[i]) r.push_back({(unsigned char *)w.part32[i], lists * 4});
+    }
     if (n_ranks) {
         CHECK(w.local != nullptr && w.gathered != nullptr);
         r.push_back({(unsigned char *)w.local, block});
@@ -74,14 +89,17 @@ int main() {
     for (size_t mis : {(size_t)0, (size_t)8, (size_t)248})
         for (int32_t Q : {1, 3, 64})
             for (int32_t k : {1, 5, 64})
-                for (int32_t n_ranks : {0, 1, 3, 16}) {
-                    carve(Q, 40, 0, k, false, n_ranks, mis);
-                    carve(Q, 4095, (int64_t)Q * 100 + 4095, k, false, n_ranks, mis);
-                    if (n_ranks == 0) {
-                        carve(Q, 40, 0, k, true, 0, mis);
-                        carve(Q, 4095, (int64_t)Q * 100 + 4095, k, true, 0, mis);
+                for (int form = 0; form < kAlignFormCount; ++form)
+                    for (int32_t n_ranks : {0, 1, 3, 16}) {
+                        if (n_ranks && !kAlignForms[form].sharded_sizer) continue;      // (no RCCL form: nothing to size)
+                        carve((AlignForm)form, Q, 40, 0, k, n_ranks, mis);
+                        carve((AlignForm)form, Q, 4095, (int64_t)Q * 100 + 4095, k, n_ranks, mis);
                     }
-                }
+    // the table's arithmetic: bytes per kept hit, and only the first two forms are sharded
+    CHECK(kAlignForms[kAlignBounded].part32 == 0 && kAlignForms[kAlignWide].part32 == 1);
+    CHECK(kAlignForms[kAlignRates].part32 == 2 && kAlignForms[kAlignSpan].part32 == 4);
+    CHECK(kAlignForms[kAlignRates].cols == 5 && kAlignForms[kAlignSpan].cols == 8);
+    CHECK(kAlignForms[kAlignRates].sharded_sizer == nullptr && kAlignForms[kAlignSpan].sharded_sizer == nullptr);
     // the sharded size: the plain one + local and gathered blocks, each rounded to 256 bytes; monotone
     for (int32_t Q : {0, 1, 2, 7, 64})
         for (int32_t len : {0, 1, 40, 4095})

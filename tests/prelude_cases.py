@@ -1,4 +1,4 @@
-"""What tests/test_py_prelude_gpu.py (the seven wrappers that need no communicator) and tests/comm_child.py (the three
+"""What tests/test_py_prelude_gpu.py (the thirteen wrappers that need no communicator) and tests/comm_child.py (the three
 of corpus.Comm) ask of every batched wrapper of tvidz_amd.corpus: bad queries, a workspace one byte short or a
 mis-shaped output raise RuntimeError and leave outputs that were filled with a sentinel as they were, and a workspace
 of exactly the sizing function's bytes is accepted.
@@ -14,9 +14,12 @@ ROWS = [(10, [1.0, 2.5, 4.0, 7.25]), (11, [1.0, 2.5, 9.0]), (12, [20.0, 21.5]), 
 QUERIES = [[1.0, 2.5, 4.0, 7.25], []]
 Q, K, CAP, MM, TOL = 2, 2, 4, 2, 0.01
 NEAR = dict(eps=0.1, max_offset=1.0, k=K)
+RATES = (1.0, 25 / 24)
 SENTINEL = -7
 DEV = "cuda:0"
-LEFT_TO_THE_LIBRARY = {("align_topk_shards", "a workspace one byte short")}      # every other refusal is Python's
+# every other refusal is Python's
+LEFT_TO_THE_LIBRARY = {(name, "a workspace one byte short") for name in
+                       ("align_topk_shards", "align_wide_topk_shards", "align_rates_topk_shards", "align_span_topk_shards")}
 
 
 def _full(*shape):
@@ -30,7 +33,7 @@ def batch():
 def wrappers(shards, comm=None):
     """name -> (call(d_q, d_off, workspace, out), the sizing function's bytes for batch(), good(): sentinel-filled
     outputs, bad(): mis-shaped ones) of the wrappers of the handles `shards` (the single-handle ones: of the first), or
-    of `comm` over the first.  The two *_shards forms make their outputs themselves: good and bad are None."""
+    of `comm` over the first.  The *_shards forms make their outputs themselves: good and bad are None."""
     dc = shards[0]
     _, _, L = batch()
     n = sum(len(q) for q in QUERIES)
@@ -73,6 +76,22 @@ def wrappers(shards, comm=None):
                               tc.workspace_bytes(Q, L, CAP, K, total_query_keys=n), None, None),
         "align_topk_shards": (lambda q, o, ws, out: tc.align_topk_shards(shards, q, o, L, workspace=ws, **NEAR),
                               tc.align_topk_workspace_bytes(Q, L, n, K), None, None),
+        "align_wide_topk_block": (lambda q, o, ws, out: dc.align_wide_topk_block(q, o, L, out=out, workspace=ws, **NEAR),
+                                  tc.align_wide_topk_workspace_bytes(Q, L, n, K)) + good_and_bad(block, 4),
+        "align_rates_topk_block": (lambda q, o, ws, out: dc.align_rates_topk_block(q, o, L, rates=RATES, out=out,
+                                                                                   workspace=ws, **NEAR),
+                                   tc.align_rates_topk_workspace_bytes(Q, L, n, K)) + good_and_bad(block, 5),
+        "align_span_topk_block": (lambda q, o, ws, out: dc.align_span_topk_block(q, o, L, rates=RATES, out=out,
+                                                                                 workspace=ws, **NEAR),
+                                  tc.align_span_topk_workspace_bytes(Q, L, n, K)) + good_and_bad(block, 8),
+        "align_wide_topk_shards": (lambda q, o, ws, out: tc.align_wide_topk_shards(shards, q, o, L, workspace=ws, **NEAR),
+                                   tc.align_wide_topk_workspace_bytes(Q, L, n, K), None, None),
+        "align_rates_topk_shards": (lambda q, o, ws, out: tc.align_rates_topk_shards(shards, q, o, L, rates=RATES,
+                                                                                     workspace=ws, **NEAR),
+                                    tc.align_rates_topk_workspace_bytes(Q, L, n, K), None, None),
+        "align_span_topk_shards": (lambda q, o, ws, out: tc.align_span_topk_shards(shards, q, o, L, rates=RATES,
+                                                                                   workspace=ws, **NEAR),
+                                   tc.align_span_topk_workspace_bytes(Q, L, n, K), None, None),
     }
 
 

@@ -1,4 +1,4 @@
-"""The one prelude of corpus.py's batched wrappers, asked through each of the seven that need no communicator (the
+"""The one prelude of corpus.py's batched wrappers, asked through each of the thirteen that need no communicator (the
 three of corpus.Comm are asked in tests/test_comm_gpu.py's child process): tests/prelude_cases.py says what."""
 import pytest
 
@@ -7,7 +7,8 @@ from tvidz_amd import corpus as tc
 
 pytestmark = pytest.mark.gpu
 NAMES = ["match", "match_tol", "match_topk", "match_tol_topk", "align_topk_block", "match_topk_shards",
-         "align_topk_shards"]
+         "align_topk_shards", "align_wide_topk_block", "align_rates_topk_block", "align_span_topk_block",
+         "align_wide_topk_shards", "align_rates_topk_shards", "align_span_topk_shards"]
 
 
 @pytest.fixture(scope="module")

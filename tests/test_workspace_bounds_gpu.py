@@ -1,6 +1,6 @@
 """The batched calls keep inside the workspace they are given.  Every call that carves a workspace - tvz_match,
-tvz_match_topk, tvz_match_tol, tvz_match_tol_topk, tvz_align_topk - gets a slice of EXACTLY its sizing function's byte
-count out of a larger buffer filled with 0xA5, starting 4,096 bytes in plus 0, 8 or 248 bytes (the carver aligns the
+tvz_match_topk, tvz_match_tol, tvz_match_tol_topk, tvz_align_topk and its wide, rates and span forms - gets a slice of
+EXACTLY its sizing function's byte count out of a larger buffer filled with 0xA5, starting 4,096 bytes in plus 0, 8 or 248 bytes (the carver aligns the
 base up itself); afterwards every byte outside the slice is still 0xA5, and the outputs equal those of the same call
 with a separately allocated workspace of twice the size.
 
@@ -8,6 +8,7 @@ This test is about pointers: it compares the library with itself, on purpose (th
 suites).  Top-k blocks are ordered and compared as they are.  The order inside a hit list is unspecified (blocks append
 with atomics), so the lists of tvz_match and tvz_match_tol are compared as counts plus sorted triples; every query here
 has fewer hits than `cap`, so both runs hold the whole list."""
+import ctypes as C
 import functools
 
 import numpy as np
@@ -99,12 +100,42 @@ def _align_topk(dc, b, ws):
     return _block(out)
 
 
+RATES = (1.0, 25 / 24)
+
+
+def _align_wide_topk(dc, b, ws):
+    out = torch.empty((b[3], K + 1, 4), dtype=torch.int32, device=DEV)
+    _lib.check(dc.lib.tvz_align_wide_topk(dc._h, b[0].data_ptr(), b[1].data_ptr(), b[3], b[2], 0.05, 1.0, 1, 0, 0, None, K,
+                                          out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                          torch.cuda.current_stream().cuda_stream))
+    return _block(out)
+
+
+def _align_rates_topk(dc, b, ws):
+    out = torch.empty((b[3], K + 1, 5), dtype=torch.int32, device=DEV)
+    _lib.check(dc.lib.tvz_align_rates_topk(dc._h, b[0].data_ptr(), b[1].data_ptr(), b[3], b[2], 0.05, 1.0,
+                                           (C.c_double * len(RATES))(*RATES), len(RATES), 1, 0, 0, None, K, out.data_ptr(),
+                                           ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream))
+    return _block(out)
+
+
+def _align_span_topk(dc, b, ws):
+    out = torch.empty((b[3], K + 1, 8), dtype=torch.int32, device=DEV)
+    _lib.check(dc.lib.tvz_align_span_topk(dc._h, b[0].data_ptr(), b[1].data_ptr(), b[3], b[2], 0.05, 1.0,
+                                          (C.c_double * len(RATES))(*RATES), len(RATES), 1, 0, 0, None, K, out.data_ptr(),
+                                          ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream))
+    return _block(out)
+
+
 CALLS = {
     "match": (lambda b: tc.workspace_bytes(b[3], b[2], 0, 0, 1, b[0].numel()), _match),
     "match_topk": (lambda b: tc.workspace_bytes(b[3], b[2], CAP, K, 1, b[0].numel()), _match_topk),
     "match_tol": (lambda b: tc.tol_workspace_bytes(b[3], b[2], b[0].numel()), _match_tol),
     "match_tol_topk": (lambda b: tc.tol_topk_workspace_bytes(b[3], b[2], b[0].numel(), K, 1), _match_tol_topk),
     "align_topk": (lambda b: tc.align_topk_workspace_bytes(b[3], b[2], b[0].numel(), K), _align_topk),
+    "align_wide_topk": (lambda b: tc.align_wide_topk_workspace_bytes(b[3], b[2], b[0].numel(), K), _align_wide_topk),
+    "align_rates_topk": (lambda b: tc.align_rates_topk_workspace_bytes(b[3], b[2], b[0].numel(), K), _align_rates_topk),
+    "align_span_topk": (lambda b: tc.align_span_topk_workspace_bytes(b[3], b[2], b[0].numel(), K), _align_span_topk),
 }
 
 

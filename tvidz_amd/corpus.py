@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import threading
+from dataclasses import dataclass
 from typing import Iterable, Optional, Sequence, Tuple
 
 import numpy as np
@@ -62,18 +63,61 @@ def tol_topk_workspace_bytes(Q: int, max_query_len: int, total_query_keys: int =
                                                               int(k), int(n_ranks)))
 
 
+@dataclass(frozen=True)
+class AlignForm:
+    """One form of the alignment top-k as the wrappers below see it; what the form is to the library is said in one
+    place too (csrc/tvz_match.hip, kAlignForms).  A form is declared here once; the public align_* functions of this
+    module, of DeviceCorpus and of Comm are forwards that name theirs."""
+    stem: str                   # the library's tvz_<stem>, tvz_<stem>_workspace_bytes, tvz_<stem>_merge, tvz_<stem>_shards, ..
+    cols: int                   # int32 columns of a row
+    widest: bool                # max_offset=None means ALIGN_WIDE_MAX_B x eps
+    rates: bool                 # a rate list is passed
+    flags: Tuple[str, ...]      # which of contain / local exist: () has no flags argument at all
+
+    def fn(self, suffix: str = ""):
+        return getattr(_lib.load(), "tvz_" + self.stem + suffix)
+
+
+FORM_BOUNDED = AlignForm("align_topk", 4, False, False, ())
+FORM_WIDE = AlignForm("align_wide_topk", 4, True, False, ("contain",))
+FORM_RATES = AlignForm("align_rates_topk", 5, True, True, ("contain",))
+FORM_SPAN = AlignForm("align_span_topk", 8, True, True, ("contain", "local"))
+ALIGN_FORMS = (FORM_BOUNDED, FORM_WIDE, FORM_RATES, FORM_SPAN)
+
+
+def _align_args(f: AlignForm, eps, max_offset, min_votes, min_score, rates=None, contain=False, local=False) -> list:
+    """What a form's call, its _shards and its _sharded take between max_query_len and the exclusions, in the ABI's
+    order: eps, max_offset, [h_rates, n_rates,] min_votes, min_score, [flags]."""
+    a = [float(eps), _wide_offset(eps, max_offset) if f.widest else float(max_offset)]
+    if f.rates:
+        a += _rates(rates)
+    return a + [int(min_votes), int(min_score)] + _align_flags(f, contain, local)
+
+
+def _align_flags(f: AlignForm, contain=False, local=False) -> list:
+    """The flags argument of a form's calls and of its merge: none at all for the form without flags."""
+    return [_span_flags(contain, local)] if f.flags else []
+
+
+def form_workspace_bytes(f: AlignForm, Q: int, max_query_len: int, total_query_keys: int, k: int,
+                         n_ranks: Optional[int] = None) -> int:
+    """tvz_<stem>_workspace_bytes, or with `n_ranks` tvz_<stem>_sharded_workspace_bytes of a form that has one."""
+    if n_ranks is None:
+        return int(f.fn("_workspace_bytes")(int(Q), int(max_query_len), int(total_query_keys), int(k)))
+    return int(f.fn("_sharded_workspace_bytes")(int(Q), int(max_query_len), int(total_query_keys), int(k), int(n_ranks)))
+
+
 def align_topk_workspace_bytes(Q: int, max_query_len: int, total_query_keys: int = 0, k: int = 16) -> int:
     """tvz_align_topk_workspace_bytes: the sorted queries, the hit totals and one kept list per sweep block - nothing
     in it grows with rows or hits."""
-    return int(_lib.load().tvz_align_topk_workspace_bytes(int(Q), int(max_query_len), int(total_query_keys), int(k)))
+    return form_workspace_bytes(FORM_BOUNDED, Q, max_query_len, total_query_keys, k)
 
 
 def align_topk_sharded_workspace_bytes(Q: int, max_query_len: int, total_query_keys: int = 0, k: int = 16,
                                        n_ranks: int = 1) -> int:
     """tvz_align_topk_sharded_workspace_bytes: align_topk_workspace_bytes + the local block and `n_ranks` gathered ones
     (Q x (k + 1) x 16 bytes each)."""
-    return int(_lib.load().tvz_align_topk_sharded_workspace_bytes(int(Q), int(max_query_len), int(total_query_keys),
-                                                                  int(k), int(n_ranks)))
+    return form_workspace_bytes(FORM_BOUNDED, Q, max_query_len, total_query_keys, k, n_ranks)
 
 
 ALIGN_SCORE_ONE = 1 << 20
@@ -99,15 +143,14 @@ def align_order_key(row, nv: int):
 
 def align_wide_topk_workspace_bytes(Q: int, max_query_len: int, total_query_keys: int = 0, k: int = 16) -> int:
     """tvz_align_wide_topk_workspace_bytes: as align_topk_workspace_bytes, with 20 bytes per kept hit instead of 16."""
-    return int(_lib.load().tvz_align_wide_topk_workspace_bytes(int(Q), int(max_query_len), int(total_query_keys), int(k)))
+    return form_workspace_bytes(FORM_WIDE, Q, max_query_len, total_query_keys, k)
 
 
 def align_wide_topk_sharded_workspace_bytes(Q: int, max_query_len: int, total_query_keys: int = 0, k: int = 16,
                                             n_ranks: int = 1) -> int:
     """tvz_align_wide_topk_sharded_workspace_bytes: align_wide_topk_workspace_bytes + the local block and `n_ranks`
     gathered ones (Q x (k + 1) x 16 bytes each)."""
-    return int(_lib.load().tvz_align_wide_topk_sharded_workspace_bytes(int(Q), int(max_query_len), int(total_query_keys),
-                                                                       int(k), int(n_ranks)))
+    return form_workspace_bytes(FORM_WIDE, Q, max_query_len, total_query_keys, k, n_ranks)
 
 
 ALIGN_WIDE_MAX_B = 1 << 22                  # include/tvz.h TVZ_ALIGN_WIDE_MAX_B: tvz_align_wide_topk's bins per side
@@ -134,7 +177,7 @@ ALIGN_MAX_RATES = 8                         # include/tvz.h TVZ_ALIGN_MAX_RATES:
 
 def align_rates_topk_workspace_bytes(Q: int, max_query_len: int, total_query_keys: int = 0, k: int = 16) -> int:
     """tvz_align_rates_topk_workspace_bytes: as align_wide_topk_workspace_bytes, with 24 bytes per kept hit."""
-    return int(_lib.load().tvz_align_rates_topk_workspace_bytes(int(Q), int(max_query_len), int(total_query_keys), int(k)))
+    return form_workspace_bytes(FORM_RATES, Q, max_query_len, total_query_keys, k)
 
 
 def align_rates_order_key(row, nv: int, contain: bool = False):
@@ -148,7 +191,7 @@ ALIGN_LOCAL = 2                             # include/tvz.h TVZ_ALIGN_LOCAL: tvz
 
 def align_span_topk_workspace_bytes(Q: int, max_query_len: int, total_query_keys: int = 0, k: int = 16) -> int:
     """tvz_align_span_topk_workspace_bytes: as align_wide_topk_workspace_bytes, with 32 bytes per kept hit."""
-    return int(_lib.load().tvz_align_span_topk_workspace_bytes(int(Q), int(max_query_len), int(total_query_keys), int(k)))
+    return form_workspace_bytes(FORM_SPAN, Q, max_query_len, total_query_keys, k)
 
 
 def align_local_score(votes: int, nq: int, nr: int) -> int:
@@ -350,12 +393,8 @@ class DeviceCorpus:
         -> (rows int32[Q, k, 4] of (video_id, row_len, best_bin, votes), padded with (-1, 0, 0, 0); totals int32[Q] =
         the true number of hits, ALIGN_REFUSED for a query longer than max_query_len - default: the longest query,
         at most 4,095), as numpy arrays.  Order: align_order_key.  One device-to-host copy of Q x (k + 1) x 16 bytes."""
-        dev = torch.device("cuda", self.device)
-        d_q, d_off, Q, max_query_len, d_ex = align_inputs(queries, exclude_ids, max_query_len, dev)
-        ws = thread_workspace(self._tls, align_topk_workspace_bytes(Q, max_query_len, d_q.numel(), k), dev)
-        h = self.align_topk_block(d_q, d_off, max_query_len, eps=eps, max_offset=max_offset, k=k, min_votes=min_votes,
-                                  min_score=min_score, d_exclude_ids=d_ex, workspace=ws).cpu().numpy()
-        return np.ascontiguousarray(h[:, :k]), np.ascontiguousarray(h[:, k, 1])
+        return self._align_host(FORM_BOUNDED, queries, k, exclude_ids, max_query_len, eps=eps, max_offset=max_offset,
+                                min_votes=min_votes, min_score=min_score)
 
     def align_topk_block(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, eps: float,
                          max_offset: float, k: int, min_votes: int = 1, min_score: int = 0,
@@ -364,14 +403,8 @@ class DeviceCorpus:
                          workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
         """tvz_align_topk, device in / device out: enqueue Q queries -> the block int32 [Q, k+1, 4] that the sharded
         forms gather and merge (align_topk_merge)."""
-        Q = d_q_offsets.numel() - 1
-        dev, s, ws, excl = self._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace,
-                                         align_topk_workspace_bytes(Q, max_query_len, d_queries.numel(), k))
-        out = _out(out, (Q, k + 1, 4), dev)
-        _lib.check(self.lib.tvz_align_topk(
-            self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps), float(max_offset),
-            int(min_votes), int(min_score), excl, int(k), out.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
-        return out
+        return self._align_block(FORM_BOUNDED, d_queries, d_q_offsets, max_query_len, k, d_exclude_ids, out, stream,
+                                 workspace, eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score)
 
     supports_align_wide = True
 
@@ -382,13 +415,8 @@ class DeviceCorpus:
         (`max_offset=None`: ALIGN_WIDE_MAX_B x eps, the widest the library takes).  `contain=True` scores by
         v / min(nv, row_len) (align_containment) instead of the tolerant Jaccard, for the excerpt of a longer video.
         Arguments and (rows, totals) otherwise as align_topk; order: align_wide_order_key."""
-        dev = torch.device("cuda", self.device)
-        d_q, d_off, Q, max_query_len, d_ex = align_inputs(queries, exclude_ids, max_query_len, dev)
-        ws = thread_workspace(self._tls, align_wide_topk_workspace_bytes(Q, max_query_len, d_q.numel(), k), dev)
-        h = self.align_wide_topk_block(d_q, d_off, max_query_len, eps=eps, max_offset=max_offset, k=k,
-                                       min_votes=min_votes, min_score=min_score, contain=contain, d_exclude_ids=d_ex,
-                                       workspace=ws).cpu().numpy()
-        return np.ascontiguousarray(h[:, :k]), np.ascontiguousarray(h[:, k, 1])
+        return self._align_host(FORM_WIDE, queries, k, exclude_ids, max_query_len, eps=eps, max_offset=max_offset,
+                                min_votes=min_votes, min_score=min_score, contain=contain)
 
     def align_wide_topk_block(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, eps: float,
                               max_offset: Optional[float] = None, k: int, min_votes: int = 1, min_score: int = 0,
@@ -396,16 +424,8 @@ class DeviceCorpus:
                               out: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
                               workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
         """tvz_align_wide_topk, device in / device out: enqueue Q queries -> the block int32 [Q, k+1, 4]."""
-        Q = d_q_offsets.numel() - 1
-        dev, s, ws, excl = self._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace,
-                                         align_wide_topk_workspace_bytes(Q, max_query_len, d_queries.numel(), k))
-        out = _out(out, (Q, k + 1, 4), dev)
-        _lib.check(self.lib.tvz_align_wide_topk(
-            self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps),
-            _wide_offset(eps, max_offset),
-            int(min_votes), int(min_score), ALIGN_CONTAIN if contain else 0, excl, int(k), out.data_ptr(), ws.data_ptr(),
-            ws.numel(), s.cuda_stream))
-        return out
+        return self._align_block(FORM_WIDE, d_queries, d_q_offsets, max_query_len, k, d_exclude_ids, out, stream, workspace,
+                                 eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score, contain=contain)
 
     def align_rates_topk(self, queries, *, eps: float, rates: Sequence[float], max_offset: Optional[float] = None,
                          k: int = 16, min_votes: int = 1, min_score: int = 0, contain: bool = False, exclude_ids=None,
@@ -415,13 +435,8 @@ class DeviceCorpus:
         stored ~= rate x query + shift) and kept once, at the rate with the most votes.  Arguments otherwise as
         align_wide_topk.  -> (rows int32[Q, k, 5] of (video_id, row_len, best_bin, votes, rate_index), padded with
         (-1, 0, 0, 0, 0); totals int32[Q]); order: align_rates_order_key."""
-        dev = torch.device("cuda", self.device)
-        d_q, d_off, Q, max_query_len, d_ex = align_inputs(queries, exclude_ids, max_query_len, dev)
-        ws = thread_workspace(self._tls, align_rates_topk_workspace_bytes(Q, max_query_len, d_q.numel(), k), dev)
-        h = self.align_rates_topk_block(d_q, d_off, max_query_len, eps=eps, rates=rates, max_offset=max_offset, k=k,
-                                        min_votes=min_votes, min_score=min_score, contain=contain, d_exclude_ids=d_ex,
-                                        workspace=ws).cpu().numpy()
-        return np.ascontiguousarray(h[:, :k]), np.ascontiguousarray(h[:, k, 1])
+        return self._align_host(FORM_RATES, queries, k, exclude_ids, max_query_len, eps=eps, max_offset=max_offset,
+                                min_votes=min_votes, min_score=min_score, rates=rates, contain=contain)
 
     def align_rates_topk_block(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, eps: float,
                                rates: Sequence[float], max_offset: Optional[float] = None, k: int, min_votes: int = 1,
@@ -429,16 +444,9 @@ class DeviceCorpus:
                                out: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
                                workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
         """tvz_align_rates_topk, device in / device out: enqueue Q queries -> the block int32 [Q, k+1, 5]."""
-        Q = d_q_offsets.numel() - 1
-        dev, s, ws, excl = self._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace,
-                                         align_rates_topk_workspace_bytes(Q, max_query_len, d_queries.numel(), k))
-        out = _out(out, (Q, k + 1, 5), dev)
-        h_rates, n_rates = _rates(rates)
-        _lib.check(self.lib.tvz_align_rates_topk(
-            self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps),
-            _wide_offset(eps, max_offset), h_rates, n_rates, int(min_votes), int(min_score),
-            ALIGN_CONTAIN if contain else 0, excl, int(k), out.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
-        return out
+        return self._align_block(FORM_RATES, d_queries, d_q_offsets, max_query_len, k, d_exclude_ids, out, stream, workspace,
+                                 eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score, rates=rates,
+                                 contain=contain)
 
     def align_span_topk(self, queries, *, eps: float, rates: Sequence[float] = (1.0,), max_offset: Optional[float] = None,
                         k: int = 16, min_votes: int = 1, min_score: int = 0, contain: bool = False, local: bool = False,
@@ -449,13 +457,8 @@ class DeviceCorpus:
         and finds the copy that is partial on both sides; min_votes is then what keeps chance pairs out.  -> (rows
         int32[Q, k, 8] of (video_id, row_len, best_bin, votes, rate_index, t_first, t_last, nr), padded with (-1, 0, ..);
         totals int32[Q]); order: align_span_order_key."""
-        dev = torch.device("cuda", self.device)
-        d_q, d_off, Q, max_query_len, d_ex = align_inputs(queries, exclude_ids, max_query_len, dev)
-        ws = thread_workspace(self._tls, align_span_topk_workspace_bytes(Q, max_query_len, d_q.numel(), k), dev)
-        h = self.align_span_topk_block(d_q, d_off, max_query_len, eps=eps, rates=rates, max_offset=max_offset, k=k,
-                                       min_votes=min_votes, min_score=min_score, contain=contain, local=local,
-                                       d_exclude_ids=d_ex, workspace=ws).cpu().numpy()
-        return np.ascontiguousarray(h[:, :k]), np.ascontiguousarray(h[:, k, 1])
+        return self._align_host(FORM_SPAN, queries, k, exclude_ids, max_query_len, eps=eps, max_offset=max_offset,
+                                min_votes=min_votes, min_score=min_score, rates=rates, contain=contain, local=local)
 
     def align_span_topk_block(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, eps: float,
                               rates: Sequence[float] = (1.0,), max_offset: Optional[float] = None, k: int,
@@ -464,15 +467,28 @@ class DeviceCorpus:
                               stream: Optional[torch.cuda.Stream] = None,
                               workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
         """tvz_align_span_topk, device in / device out: enqueue Q queries -> the block int32 [Q, k+1, 8]."""
+        return self._align_block(FORM_SPAN, d_queries, d_q_offsets, max_query_len, k, d_exclude_ids, out, stream, workspace,
+                                 eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score, rates=rates,
+                                 contain=contain, local=local)
+
+    def _align_host(self, f: AlignForm, queries, k, exclude_ids, max_query_len, **ask):
+        """Any form, host in / host out: the inputs, the calling thread's workspace, the block call, ONE copy back,
+        the split into (rows [Q, k, cols], totals [Q])."""
+        dev = torch.device("cuda", self.device)
+        d_q, d_off, Q, max_query_len, d_ex = align_inputs(queries, exclude_ids, max_query_len, dev)
+        ws = thread_workspace(self._tls, form_workspace_bytes(f, Q, max_query_len, d_q.numel(), k), dev)
+        h = self._align_block(f, d_q, d_off, max_query_len, k, d_ex, None, None, ws, **ask).cpu().numpy()
+        return np.ascontiguousarray(h[:, :k]), np.ascontiguousarray(h[:, k, 1])
+
+    def _align_block(self, f: AlignForm, d_queries, d_q_offsets, max_query_len, k, d_exclude_ids, out, stream, workspace,
+                     **ask):
+        """Any form, device in / device out: the prelude, the block int32 [Q, k+1, cols], one library call."""
         Q = d_q_offsets.numel() - 1
         dev, s, ws, excl = self._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace,
-                                         align_span_topk_workspace_bytes(Q, max_query_len, d_queries.numel(), k))
-        out = _out(out, (Q, k + 1, 8), dev)
-        h_rates, n_rates = _rates(rates)
-        _lib.check(self.lib.tvz_align_span_topk(
-            self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps),
-            _wide_offset(eps, max_offset), h_rates, n_rates, int(min_votes), int(min_score),
-            _span_flags(contain, local), excl, int(k), out.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
+                                         form_workspace_bytes(f, Q, max_query_len, d_queries.numel(), k))
+        out = _out(out, (Q, k + 1, f.cols), dev)
+        _lib.check(f.fn()(self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len),
+                          *_align_args(f, **ask), excl, int(k), out.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
         return out
 
     # ---- batched, device resident ----
@@ -636,15 +652,8 @@ class Comm:
                            out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
         """tvz_align_topk_sharded: the local alignment top-k -> ncclAllGather of the [Q,k+1,4] blocks -> the merge;
         -> (rows int32 [Q,k,4], totals int32 [Q]), identical on every rank."""
-        Q = d_q_offsets.numel() - 1
-        dev, s, ws, excl = corpus._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace,
-                                           align_topk_sharded_workspace_bytes(Q, max_query_len, d_queries.numel(), k, self.n_ranks))
-        rows, totals = _topk_out(out, Q, k, 4, dev)
-        _lib.check(self.lib.tvz_align_topk_sharded(
-            corpus._h, self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps),
-            float(max_offset), int(min_votes), int(min_score), excl, int(k), rows.data_ptr(), totals.data_ptr(),
-            ws.data_ptr(), ws.numel(), s.cuda_stream))
-        return rows, totals
+        return self._align_sharded(FORM_BOUNDED, corpus, d_queries, d_q_offsets, max_query_len, k, d_exclude_ids, workspace,
+                                   stream, out, eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score)
 
     def align_wide_topk_sharded(self, corpus: DeviceCorpus, d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
                                 max_query_len: int, *, eps: float, max_offset: Optional[float] = None, k: int,
@@ -655,15 +664,20 @@ class Comm:
         """tvz_align_wide_topk_sharded: the local alignment top-k at any shift (`max_offset=None`: the widest) ->
         ncclAllGather of the [Q,k+1,4] blocks -> the wide merge; -> (rows int32 [Q,k,4], totals int32 [Q]), identical
         on every rank."""
+        return self._align_sharded(FORM_WIDE, corpus, d_queries, d_q_offsets, max_query_len, k, d_exclude_ids, workspace,
+                                   stream, out, eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score,
+                                   contain=contain)
+
+    def _align_sharded(self, f: AlignForm, corpus, d_queries, d_q_offsets, max_query_len, k, d_exclude_ids, workspace, stream,
+                       out, **ask):
+        """A form's RCCL call: the prelude with the sharded workspace, the merge's outputs, one library call."""
         Q = d_q_offsets.numel() - 1
         dev, s, ws, excl = corpus._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace,
-                                           align_wide_topk_sharded_workspace_bytes(Q, max_query_len, d_queries.numel(), k,
-                                                                                   self.n_ranks))
-        rows, totals = _topk_out(out, Q, k, 4, dev)
-        _lib.check(self.lib.tvz_align_wide_topk_sharded(
-            corpus._h, self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps),
-            _wide_offset(eps, max_offset), int(min_votes), int(min_score), ALIGN_CONTAIN if contain else 0, excl, int(k),
-            rows.data_ptr(), totals.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
+                                           form_workspace_bytes(f, Q, max_query_len, d_queries.numel(), k, self.n_ranks))
+        rows, totals = _topk_out(out, Q, k, f.cols, dev)
+        _lib.check(f.fn("_sharded")(corpus._h, self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len),
+                                    *_align_args(f, **ask), excl, int(k), rows.data_ptr(), totals.data_ptr(), ws.data_ptr(),
+                                    ws.numel(), s.cuda_stream))
         return rows, totals
 
 
@@ -777,16 +791,7 @@ def align_topk_merge(gathered: torch.Tensor, k: int, d_queries: torch.Tensor, d_
                      stream: Optional[torch.cuda.Stream] = None, out=None):
     """tvz_align_topk_merge: the shards' blocks int32 [R,Q,k+1,4] (+ the queries: the order word needs their non-NaN
     counts) -> (rows int32 [Q,k,4], totals int32 [Q]; ALIGN_REFUSED for a query some shard refused)."""
-    R, Q, k1, w = gathered.shape
-    if k1 != k + 1 or w != 4 or gathered.dtype != torch.int32 or not gathered.is_contiguous():
-        raise RuntimeError("gathered must be a contiguous int32 [R,Q,k+1,4]")
-    rows, totals = _topk_out(out, Q, k, 4, gathered.device)
-    s = stream if stream is not None else torch.cuda.current_stream(gathered.device)
-    with torch.cuda.device(gathered.device):
-        _lib.check(_lib.load().tvz_align_topk_merge(gathered.data_ptr(), R, Q, int(k), d_queries.data_ptr(),
-                                                    d_q_offsets.data_ptr(), rows.data_ptr(), totals.data_ptr(),
-                                                    s.cuda_stream))
-    return rows, totals
+    return form_merge(FORM_BOUNDED, gathered, k, d_queries, d_q_offsets, stream, out)
 
 
 def align_topk_shards(shards: Sequence["DeviceCorpus"], d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
@@ -797,31 +802,15 @@ def align_topk_shards(shards: Sequence["DeviceCorpus"], d_queries: torch.Tensor,
     -> (blocks int32 [R,Q,k+1,4], rows int32 [Q,k,4], totals int32 [Q]).  `workspace`: align_topk_workspace_bytes."""
     # (the workspace's size is the library's to judge: it takes one down to a single query's room and refuses the
     # queries that do not fit one by one)
-    Q = d_q_offsets.numel() - 1
-    dev, s, ws, excl = shards[0]._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace, None)
-    handles, blocks, rows, totals = _shards_out(shards, Q, k, 4, dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().tvz_align_topk_shards(
-            handles, len(shards), d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps),
-            float(max_offset), int(min_votes), int(min_score), excl, int(k), blocks.data_ptr(), rows.data_ptr(),
-            totals.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
-    return blocks, rows, totals
+    return form_shards(FORM_BOUNDED, shards, d_queries, d_q_offsets, max_query_len, k, workspace, d_exclude_ids, stream,
+                       eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score)
 
 
 def align_wide_topk_merge(gathered: torch.Tensor, k: int, d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
                           contain: bool = False, stream: Optional[torch.cuda.Stream] = None, out=None):
     """tvz_align_wide_topk_merge: align_topk_merge for the blocks of align_wide_topk_block - bins anywhere in
     +-ALIGN_WIDE_MAX_B, every list sorted by align_wide_order_key of the SAME `contain`."""
-    R, Q, k1, w = gathered.shape
-    if k1 != k + 1 or w != 4 or gathered.dtype != torch.int32 or not gathered.is_contiguous():
-        raise RuntimeError("gathered must be a contiguous int32 [R,Q,k+1,4]")
-    rows, totals = _topk_out(out, Q, k, 4, gathered.device)
-    s = stream if stream is not None else torch.cuda.current_stream(gathered.device)
-    with torch.cuda.device(gathered.device):
-        _lib.check(_lib.load().tvz_align_wide_topk_merge(gathered.data_ptr(), R, Q, int(k), ALIGN_CONTAIN if contain else 0,
-                                                         d_queries.data_ptr(), d_q_offsets.data_ptr(), rows.data_ptr(),
-                                                         totals.data_ptr(), s.cuda_stream))
-    return rows, totals
+    return form_merge(FORM_WIDE, gathered, k, d_queries, d_q_offsets, stream, out, contain=contain)
 
 
 def align_wide_topk_shards(shards: Sequence["DeviceCorpus"], d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
@@ -831,15 +820,8 @@ def align_wide_topk_shards(shards: Sequence["DeviceCorpus"], d_queries: torch.Te
     """tvz_align_wide_topk on every handle of ONE device + the wide merge behind one library call
     (tvz_align_wide_topk_shards): -> (blocks int32 [R,Q,k+1,4], rows int32 [Q,k,4], totals int32 [Q]).  `workspace`:
     align_wide_topk_workspace_bytes (its size is the library's to judge, as align_topk_shards')."""
-    Q = d_q_offsets.numel() - 1
-    dev, s, ws, excl = shards[0]._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace, None)
-    handles, blocks, rows, totals = _shards_out(shards, Q, k, 4, dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().tvz_align_wide_topk_shards(
-            handles, len(shards), d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps),
-            _wide_offset(eps, max_offset), int(min_votes), int(min_score), ALIGN_CONTAIN if contain else 0, excl, int(k),
-            blocks.data_ptr(), rows.data_ptr(), totals.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
-    return blocks, rows, totals
+    return form_shards(FORM_WIDE, shards, d_queries, d_q_offsets, max_query_len, k, workspace, d_exclude_ids, stream,
+                       eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score, contain=contain)
 
 
 def align_rates_topk_merge(gathered: torch.Tensor, k: int, d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
@@ -847,17 +829,7 @@ def align_rates_topk_merge(gathered: torch.Tensor, k: int, d_queries: torch.Tens
     """tvz_align_rates_topk_merge: align_wide_topk_merge for the blocks of align_rates_topk_block, int32 [R,Q,k+1,5] ->
     (rows int32 [Q,k,5], totals int32 [Q]); every list sorted by align_rates_order_key of the SAME `contain`, made
     with the same rate list (the rate index is carried, never read)."""
-    R, Q, k1, w = gathered.shape
-    if k1 != k + 1 or w != 5 or gathered.dtype != torch.int32 or not gathered.is_contiguous():
-        raise RuntimeError("gathered must be a contiguous int32 [R,Q,k+1,5]")
-    rows, totals = _topk_out(out, Q, k, 5, gathered.device)
-    s = stream if stream is not None else torch.cuda.current_stream(gathered.device)
-    with torch.cuda.device(gathered.device):
-        _lib.check(_lib.load().tvz_align_rates_topk_merge(gathered.data_ptr(), R, Q, int(k),
-                                                          ALIGN_CONTAIN if contain else 0, d_queries.data_ptr(),
-                                                          d_q_offsets.data_ptr(), rows.data_ptr(), totals.data_ptr(),
-                                                          s.cuda_stream))
-    return rows, totals
+    return form_merge(FORM_RATES, gathered, k, d_queries, d_q_offsets, stream, out, contain=contain)
 
 
 def align_rates_topk_shards(shards: Sequence["DeviceCorpus"], d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
@@ -867,17 +839,8 @@ def align_rates_topk_shards(shards: Sequence["DeviceCorpus"], d_queries: torch.T
     """tvz_align_rates_topk on every handle of ONE device + its merge behind one library call
     (tvz_align_rates_topk_shards): -> (blocks int32 [R,Q,k+1,5], rows int32 [Q,k,5], totals int32 [Q]).  `workspace`:
     align_rates_topk_workspace_bytes (its size is the library's to judge, as align_topk_shards')."""
-    Q = d_q_offsets.numel() - 1
-    dev, s, ws, excl = shards[0]._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace, None)
-    handles, blocks, rows, totals = _shards_out(shards, Q, k, 5, dev)
-    h_rates, n_rates = _rates(rates)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().tvz_align_rates_topk_shards(
-            handles, len(shards), d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps),
-            _wide_offset(eps, max_offset), h_rates, n_rates, int(min_votes), int(min_score),
-            ALIGN_CONTAIN if contain else 0, excl, int(k), blocks.data_ptr(), rows.data_ptr(), totals.data_ptr(),
-            ws.data_ptr(), ws.numel(), s.cuda_stream))
-    return blocks, rows, totals
+    return form_shards(FORM_RATES, shards, d_queries, d_q_offsets, max_query_len, k, workspace, d_exclude_ids, stream,
+                       eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score, rates=rates, contain=contain)
 
 
 def align_span_topk_merge(gathered: torch.Tensor, k: int, d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
@@ -885,16 +848,7 @@ def align_span_topk_merge(gathered: torch.Tensor, k: int, d_queries: torch.Tenso
     """tvz_align_span_topk_merge: align_rates_topk_merge for the blocks of align_span_topk_block, int32 [R,Q,k+1,8] ->
     (rows int32 [Q,k,8], totals int32 [Q]); every list sorted by align_span_order_key of the SAME `contain` / `local`.
     With `local` the score is rebuilt from votes, t_last - t_first + 1 and nr; otherwise the span is only carried."""
-    R, Q, k1, w = gathered.shape
-    if k1 != k + 1 or w != 8 or gathered.dtype != torch.int32 or not gathered.is_contiguous():
-        raise RuntimeError("gathered must be a contiguous int32 [R,Q,k+1,8]")
-    rows, totals = _topk_out(out, Q, k, 8, gathered.device)
-    s = stream if stream is not None else torch.cuda.current_stream(gathered.device)
-    with torch.cuda.device(gathered.device):
-        _lib.check(_lib.load().tvz_align_span_topk_merge(gathered.data_ptr(), R, Q, int(k), _span_flags(contain, local),
-                                                         d_queries.data_ptr(), d_q_offsets.data_ptr(), rows.data_ptr(),
-                                                         totals.data_ptr(), s.cuda_stream))
-    return rows, totals
+    return form_merge(FORM_SPAN, gathered, k, d_queries, d_q_offsets, stream, out, contain=contain, local=local)
 
 
 def align_span_topk_shards(shards: Sequence["DeviceCorpus"], d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
@@ -905,16 +859,38 @@ def align_span_topk_shards(shards: Sequence["DeviceCorpus"], d_queries: torch.Te
     """tvz_align_span_topk on every handle of ONE device + its merge behind one library call
     (tvz_align_span_topk_shards): -> (blocks int32 [R,Q,k+1,8], rows int32 [Q,k,8], totals int32 [Q]).  `workspace`:
     align_span_topk_workspace_bytes (its size is the library's to judge, as align_topk_shards')."""
+    return form_shards(FORM_SPAN, shards, d_queries, d_q_offsets, max_query_len, k, workspace, d_exclude_ids, stream,
+                       eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score, rates=rates, contain=contain,
+                       local=local)
+
+
+def form_merge(f: AlignForm, gathered: torch.Tensor, k: int, d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
+               stream: Optional[torch.cuda.Stream] = None, out=None, contain: bool = False, local: bool = False):
+    """tvz_<stem>_merge of any form: the blocks int32 [R,Q,k+1,cols] -> (rows int32 [Q,k,cols], totals int32 [Q])."""
+    R, Q, k1, w = gathered.shape
+    if k1 != k + 1 or w != f.cols or gathered.dtype != torch.int32 or not gathered.is_contiguous():
+        raise RuntimeError(f"gathered must be a contiguous int32 [R,Q,k+1,{f.cols}]")
+    rows, totals = _topk_out(out, Q, k, f.cols, gathered.device)
+    s = stream if stream is not None else torch.cuda.current_stream(gathered.device)
+    with torch.cuda.device(gathered.device):
+        _lib.check(f.fn("_merge")(gathered.data_ptr(), R, Q, int(k), *_align_flags(f, contain, local), d_queries.data_ptr(),
+                                  d_q_offsets.data_ptr(), rows.data_ptr(), totals.data_ptr(), s.cuda_stream))
+    return rows, totals
+
+
+def form_shards(f: AlignForm, shards: Sequence["DeviceCorpus"], d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
+                max_query_len: int, k: int, workspace: torch.Tensor, d_exclude_ids: Optional[torch.Tensor] = None,
+                stream: Optional[torch.cuda.Stream] = None, **ask):
+    """tvz_<stem>_shards of any form: the form's call on every handle of ONE device + its merge behind one library call
+    -> (blocks int32 [R,Q,k+1,cols], rows int32 [Q,k,cols], totals int32 [Q]).  `ask`: _align_args' keywords."""
     Q = d_q_offsets.numel() - 1
     dev, s, ws, excl = shards[0]._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace, None)
-    handles, blocks, rows, totals = _shards_out(shards, Q, k, 8, dev)
-    h_rates, n_rates = _rates(rates)
+    handles, blocks, rows, totals = _shards_out(shards, Q, k, f.cols, dev)
+    args = _align_args(f, **ask)
     with torch.cuda.device(dev):
-        _lib.check(_lib.load().tvz_align_span_topk_shards(
-            handles, len(shards), d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), float(eps),
-            _wide_offset(eps, max_offset), h_rates, n_rates, int(min_votes), int(min_score),
-            _span_flags(contain, local), excl, int(k), blocks.data_ptr(), rows.data_ptr(), totals.data_ptr(),
-            ws.data_ptr(), ws.numel(), s.cuda_stream))
+        _lib.check(f.fn("_shards")(handles, len(shards), d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len),
+                                   *args, excl, int(k), blocks.data_ptr(), rows.data_ptr(), totals.data_ptr(), ws.data_ptr(),
+                                   ws.numel(), s.cuda_stream))
     return blocks, rows, totals
 
 

@@ -1,6 +1,8 @@
 // tvz_align_kernels.h — batched alignment score with the k best rows kept inside the sweep, gfx950 wave64: the bounded
 // call (tvz_align_topk, at most kAlignMaxBins bins), the call at any shift (tvz_align_wide_topk, up to kAwMaxB bins on
-// either side of zero) and the merges of the shards' blocks, one per call.  Included by tvz_match.hip only.  From
+// either side of zero), that call with rates (tvz_align_rates_topk) and with the matched span (tvz_align_span_topk),
+// and the merges of the shards' blocks, one per form.  Included by tvz_match.hip only, whose table kAlignForms says
+// what each form is on the host.  From
 // tvz_match_kernels.h: Row, load_row; from tvz_tol_kernels.h: ts_tol_sort_kernel (the batch's queries sorted
 // numerically, NaNs dropped, qm = the non-NaN count) and the sweep's block count (tol_topk_max_blocks); from
 // tvz_wave.h: wave_lds_fence.
@@ -8,8 +10,8 @@
 // Contract (include/tvz.h): votes and bins are tvz_align's - the pair (row key c, query value x) votes into
 //   d = floor((c - x) / eps + 0.5)      (one IEEE subtraction, one true division)
 // when -B <= d <= B; the score is the tolerant Jaccard or, for the wide call with TVZ_ALIGN_CONTAIN, v / min(nv,
-// row_len); a row's hit is ordered by the tuple (score descending, video_id, best_bin, row_len, votes).  The two calls
-// pack that tuple differently (AlHit, AwHit below) and share everything else.
+// row_len); a row's hit is ordered by the tuple (score descending, video_id, best_bin, row_len, votes).  The forms
+// pack that tuple differently (AlHit, AwHit, ArHit, AsHit below) and share everything else.
 //
 // A key's run: for a fixed key c each of c - x, / eps, + 0.5 and floor never increases as x grows, so the query
 // values that vote into a range of bins are ONE contiguous run of the sorted query.  Its start is found by a binary
@@ -142,7 +144,7 @@ __device__ __forceinline__ int al_lo(const double *s, int m, double c, double ep
     return lo;
 }
 
-// ---- a kept hit, in the three layouts-----------------------------------------------------------------------------
+// ---- a kept hit, in the forms' layouts ----------------------------------------------------------------------------
 // Lists<N>: N hits as a structure of arrays, in static LDS; Parts / ConstParts: the same arrays in the workspace,
 // [Q][n_lists][k] each.  load / store take any of them.  kCols: the int32 columns of the hit's block row; column 4 + i
 // (ArHit's one, AsHit's four) is extra(i); make() takes the first, the rate's index, and with_more() those behind it.
@@ -736,7 +738,7 @@ __global__ __launch_bounds__(kAlReduceBlock) void ts_aligns_reduce_kernel(
                      d_out);
 }
 
-// ---- the merge of the shards' blocks (tvz_align_topk_merge, tvz_align_wide_topk_merge, tvz_align_rates_topk_merge) ---------------------------
+// ---- the merge of the shards' blocks (every form's tvz_align_*_topk_merge) -------------------------------------------
 constexpr int kAlMergeBlock = 256;
 constexpr int kAlMergeWaves = kAlMergeBlock / 64;      // queries per block: a wave each
 constexpr int kAlMergeMaxLists = 16;                   // one n_hits per lane, far below a wave

@@ -201,9 +201,10 @@ static int tvz_match_tol_sharded_impl(tvz_corpus *c, tvz_comm *comm, const doubl
     return gather_and_merge_topk(comm, blk, Q, k, d_topk, d_totals, hip_stream);
 }
 
-// Both alignment top-k calls (tvz_align_topk_sharded: wide = false, flags = 0; tvz_align_wide_topk_sharded): the local
-// sweep keeps its k best itself and writes them into the workspace's own block, then the gather and the call's merge.
-static int align_topk_sharded_impl(bool wide, tvz_corpus *c, tvz_comm *comm, const Batch &b, const AlignCall &a,
+// The alignment top-k forms that have an RCCL form (tvz_align_topk_sharded: flags = 0; tvz_align_wide_topk_sharded): the
+// local sweep keeps its k best itself and writes them into the workspace's own block, then the gather and the form's
+// merge.  Both forms' block rows have 4 columns.
+static int align_topk_sharded_impl(AlignForm form, tvz_corpus *c, tvz_comm *comm, const Batch &b, const AlignCall &a,
                                    uint32_t flags, int32_t k, int32_t *d_topk, int32_t *d_totals, Workspace ws,
                                    void *hip_stream) {
     const int32_t Q = b.Q;
@@ -213,15 +214,11 @@ static int align_topk_sharded_impl(bool wide, tvz_corpus *c, tvz_comm *comm, con
     if (comm->n_ranks > 16)          // (the merge's limit: refused here, before the local sweep is enqueued)
         return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment top-k: %d ranks, the merge takes up to 16", (int)comm->n_ranks);
     ShardBlocks blk;
-    if (int rc = wide ? tvz_align_wide_topk_local(c, b, a, flags, k, nullptr, ws, comm->n_ranks, hip_stream, &blk)
-                      : tvz_align_topk_local(c, b, a, k, nullptr, ws, comm->n_ranks, hip_stream, &blk))
-        return rc;
+    if (int rc = tvz_align_topk_local(form, c, b, a, flags, k, nullptr, ws, comm->n_ranks, hip_stream, &blk)) return rc;
     if (Q == 0) return TVZ_OK;
     return gather_and_merge(comm, blk.local, blk.gathered, (size_t)Q * (size_t)(k + 1) * 4, hip_stream, [&] {
-        return wide ? tvz_align_wide_topk_merge(blk.gathered, comm->n_ranks, Q, k, flags, b.d_queries, b.d_q_offsets, d_topk,
-                                                d_totals, hip_stream)
-                    : tvz_align_topk_merge(blk.gathered, comm->n_ranks, Q, k, b.d_queries, b.d_q_offsets, d_topk, d_totals,
-                                           hip_stream);
+        return tvz_align_merge_local(form, blk.gathered, comm->n_ranks, Q, k, flags, b.d_queries, b.d_q_offsets, d_topk,
+                                     d_totals, hip_stream);
     });
 }
 
@@ -260,7 +257,7 @@ TVZ_EXPORT int tvz_align_topk_sharded(tvz_corpus *c, tvz_comm *comm, const doubl
                                       int32_t Q, int32_t max_query_len, double eps, double max_offset, int32_t min_votes,
                                       int32_t min_score, const int32_t *d_exclude_ids, int32_t k, int32_t *d_topk,
                                       int32_t *d_totals, void *d_workspace, size_t workspace_bytes, void *hip_stream) {
-    TVZ_GUARDED(align_topk_sharded_impl(false, c, comm,
+    TVZ_GUARDED(align_topk_sharded_impl(kAlignBounded, c, comm,
                                         Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids},
                                         AlignCall{eps, max_offset, min_votes, min_score}, 0u, k, d_topk, d_totals,
                                         Workspace{d_workspace, workspace_bytes}, hip_stream));
@@ -271,7 +268,7 @@ TVZ_EXPORT int tvz_align_wide_topk_sharded(tvz_corpus *c, tvz_comm *comm, const 
                                            double max_offset, int32_t min_votes, int32_t min_score, uint32_t flags,
                                            const int32_t *d_exclude_ids, int32_t k, int32_t *d_topk, int32_t *d_totals,
                                            void *d_workspace, size_t workspace_bytes, void *hip_stream) {
-    TVZ_GUARDED(align_topk_sharded_impl(true, c, comm,
+    TVZ_GUARDED(align_topk_sharded_impl(kAlignWide, c, comm,
                                         Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids},
                                         AlignCall{eps, max_offset, min_votes, min_score}, flags, k, d_topk, d_totals,
                                         Workspace{d_workspace, workspace_bytes}, hip_stream));

@@ -92,12 +92,13 @@ int tvz_match_topk_local(tvz_corpus *c, const Batch &b, int32_t cap, int32_t k, 
 // The tolerant counterpart (tvz_match.hip): the sweep keeps the k best itself.
 int tvz_match_tol_topk_local(tvz_corpus *c, const Batch &b, double tol, int32_t k, int32_t *d_out, Workspace ws,
                              int32_t n_ranks, void *hip_stream, ShardBlocks *blocks);
-// ... and at any shift (tvz_align_wide_topk; n_ranks >= 1: tvz_align_wide_topk_sharded's workspace).
-int tvz_align_wide_topk_local(tvz_corpus *c, const Batch &b, const AlignCall &a, uint32_t flags, int32_t k, int32_t *d_out,
-                              Workspace ws, int32_t n_ranks, void *hip_stream, ShardBlocks *blocks);
-// The alignment top-k (tvz_match.hip): n_ranks = 0 is tvz_align_topk itself, whose workspace holds no blocks.
-int tvz_align_topk_local(tvz_corpus *c, const Batch &b, const AlignCall &a, int32_t k, int32_t *d_out, Workspace ws,
-                         int32_t n_ranks, void *hip_stream, ShardBlocks *blocks);
-// ... and at any shift (tvz_align_wide_topk; n_ranks >= 1: tvz_align_wide_topk_sharded's workspace).
-int tvz_align_wide_topk_local(tvz_corpus *c, const Batch &b, const AlignCall &a, uint32_t flags, int32_t k, int32_t *d_out,
-                              Workspace ws, int32_t n_ranks, void *hip_stream, ShardBlocks *blocks);
+// The forms of the alignment top-k, in the order of tvz_match.hip's table kAlignForms, which says what each one is.
+enum AlignForm { kAlignBounded, kAlignWide, kAlignRates, kAlignSpan, kAlignFormCount };
+// A form's call (tvz_match.hip): n_ranks = 0 is the call of the C ABI, whose workspace holds no blocks; n_ranks >= 1 is
+// the workspace of the form's sharded sizing function.  `flags`: 0 for the form that has none.
+int tvz_align_topk_local(AlignForm form, tvz_corpus *c, const Batch &b, const AlignCall &a, uint32_t flags, int32_t k,
+                         int32_t *d_out, Workspace ws, int32_t n_ranks, void *hip_stream, ShardBlocks *blocks);
+// ... and the merge of its gathered blocks.
+int tvz_align_merge_local(AlignForm form, const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t k, uint32_t flags,
+                          const double *d_queries, const int64_t *d_q_offsets, int32_t *d_topk, int32_t *d_totals,
+                          void *hip_stream);

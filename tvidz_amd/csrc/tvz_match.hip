@@ -1311,7 +1311,7 @@ int check_find_args(const tvz_corpus *c, const double *h_query, int64_t n, int64
     return TVZ_OK;
 }
 
-// eps and max_offset of tvz_align, tvz_align_topk and tvz_align_wide_topk; *nb = the offset bins on either side of
+// eps and max_offset of tvz_align and of every form of the alignment top-k; *nb = the offset bins on either side of
 // zero, at most max_bins in all.  A call whose limit is a constant of the header says so by its name (wide_limit).
 int check_align_bins(double eps, double max_offset, int32_t max_bins, const char *wide_limit, int32_t *nb_out) {
     TVZ_REQUIRE(eps > 0.0 && max_offset >= 0.0, "eps must be > 0 and max_offset >= 0");
@@ -1326,7 +1326,7 @@ int check_align_bins(double eps, double max_offset, int32_t max_bins, const char
     return TVZ_OK;
 }
 
-// the rate list of tvz_align_rates_topk: 1..kArMaxRates finite rates > 0 on the host -> the sweep's by-value argument
+// the rate list of the forms that take one: 1..kArMaxRates finite rates > 0 on the host -> the sweep's by-value argument
 int check_align_rates(const double *h_rates, int32_t n_rates, AlRates *out) {
     if (n_rates < 1 || n_rates > kArMaxRates)
         return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment top-k with rates: n_rates=%d outside 1..%d (TVZ_ALIGN_MAX_RATES)",
@@ -2009,59 +2009,170 @@ static int tvz_match_tol_topk_impl(tvz_corpus *c, const double *d_queries, const
                                     d_out, Workspace{d_workspace, workspace_bytes}, 1, hip_stream, nullptr);
 }
 
-// ---- alignment top-k, bounded and at any shift (tvz_align_kernels.h) ------------------------------------------
+// ---- alignment top-k: the forms of one call (tvz_align_kernels.h) -----------------------------------------------
 namespace {
 
-// Workspace of the four calls, in front of the sorted queries (TolWs, which takes the rest): the queries' hit totals
-// and one kept list per sweep block, as a structure of arrays - k words and k payloads, for the wide call k raw votes
-// behind them, for the call with rates k rate indexes behind those and for the call with spans k index pairs and k key
-// counts behind those (AlHit::Parts, AwHit::Parts, ArHit::Parts, AsHit::Parts: 16, 20, 24 and 32 bytes per kept hit).
-// The sizing function knows no row count: the
-// lists are sized by the grid's upper bound, as the tolerant top-k's are.  The sharded forms (n_blocks > 0: the
-// communicator's ranks, at least 1) add the local block and the gathered ones behind them; the plain calls
-// (n_blocks = 0) have neither.
+// Workspace of every form, in front of the sorted queries (TolWs, which takes the rest): the queries' hit totals and
+// one kept list per sweep block, as a structure of arrays - k words and k payloads, and behind them the form's part32
+// lists of k uint32: the raw votes, the rate indexes, the index pairs and the key counts (AlHit::Parts, AwHit::Parts,
+// ArHit::Parts, AsHit::Parts).  The sizing function knows no row count: the lists are sized by the grid's upper bound,
+// as the tolerant top-k's are.  The sharded forms (n_blocks > 0: the communicator's ranks, at least 1) add the local
+// block and the gathered ones behind them; the plain calls (n_blocks = 0) have neither.
 struct AlignTopkWs {
     int32_t *totals = nullptr;             // [Q]
     unsigned long long *part_w = nullptr;  // [Q][blocks][k]
     unsigned long long *part_p = nullptr;  // [Q][blocks][k]
-    uint32_t *part_v = nullptr;            // [Q][blocks][k], wide and rates only
-    uint32_t *part_r = nullptr;            // [Q][blocks][k], rates and spans only
-    uint32_t *part_t = nullptr;            // [Q][blocks][k], spans only
-    uint32_t *part_n = nullptr;            // [Q][blocks][k], spans only
-    int32_t *local = nullptr;              // [Q][k+1][4]
-    int32_t *gathered = nullptr;           // [n_blocks][Q][k+1][4]
+    uint32_t *part32[4] = {};              // [Q][blocks][k] each, the form's first part32 of them
+    int32_t *local = nullptr;              // [Q][k+1][cols]
+    int32_t *gathered = nullptr;           // [n_blocks][Q][k+1][cols]
 };
 
-AlignTopkWs align_topk_ws_layout(Carver &cv, int32_t Q, int32_t k, bool wide, int32_t n_blocks, bool rates = false,
-                                 bool span = false) {
+// Everything a form's sweep or selection launch may need; each kernel takes the part of it that is its own.
+struct AlignLaunch {
+    dim3 grid;
+    size_t lds;                      // dynamic, of the sweep
+    hipStream_t st;
+    const tvz_corpus *c;
+    int64_t n_rows;
+    const Batch *b;
+    const TolWs *q;                  // the sorted queries
+    const AlignCall *a;
+    const AlRates *rates;
+    uint32_t flags;
+    int32_t lds_keys, B, width, k, n_lists;
+    const AlignTopkWs *w;
+    int32_t *d_out;
+};
+struct AlignMergeArgs {              // ... and its merge launch
+    dim3 grid;
+    hipStream_t st;
+    const int32_t *d_gathered;
+    int32_t n_lists, Q, k;
+    uint32_t flags;
+    const double *d_queries;
+    const int64_t *d_q_offsets;
+    int32_t *d_topk, *d_totals;
+};
+
+// What a form of the alignment top-k is, on the host: tvz_align_topk, tvz_align_wide_topk, tvz_align_rates_topk and
+// tvz_align_span_topk are one entry each of kAlignForms (indexed by AlignForm, tvz_common.h), and nothing below the
+// table asks which form it has.  The kernels' argument lists differ (the window width, the flags, the rates, the lists
+// behind the first two), so every kernel is launched from its form's entry.  A new form, or the RCCL variant of an
+// existing one, is an entry here (and its exports); only what is genuinely new needs code.
+struct AlignTopkForm {
+    int cols;                        // int32 columns of a block row
+    int part32;                      // uint32 lists behind the two uint64 ones: a kept hit is 16 + 4 * part32 bytes
+    bool takes_rates;                // the call has a rate list (check_align_rates)
+    bool limits_first;               // the flags and the limits are refused before the handle is looked at
+    const char *what, *sizer;        // the call in messages; the sizing function the workspace message names
+    const char *sharded_sizer;       // ... and the one it names for the sharded form (n_ranks >= 1); NULL: no RCCL form
+    int32_t max_bins;                // 2B + 1 at most
+    const char *bins_limit;          // the header's name of that limit, if it has one (check_align_bins)
+    uint32_t flags;                  // the permitted ones
+    uint32_t exclusive;              // ... of which these two are two score kinds: one of them
+    int static_lds;                  // of the sweep
+    void (*sweep)(const AlignLaunch &);
+    void (*reduce)(const AlignLaunch &);
+    void (*merge)(const AlignMergeArgs &);
+};
+
+AlignTopkWs align_topk_ws_layout(Carver &cv, const AlignTopkForm &f, int32_t Q, int32_t k, int32_t n_blocks) {
     AlignTopkWs w;
     const size_t lists = (size_t)tol_topk_max_lists(Q) * (size_t)k;
     w.totals = cv.take<int32_t>((size_t)Q);
     w.part_w = cv.take<unsigned long long>(lists);
     w.part_p = cv.take<unsigned long long>(lists);
-    if (wide) w.part_v = cv.take<uint32_t>(lists);
-    if (rates) w.part_r = cv.take<uint32_t>(lists);
-    if (span) {
-        w.part_t = cv.take<uint32_t>(lists);
-        w.part_n = cv.take<uint32_t>(lists);
-    }
+    for (int i = 0; i < f.part32; ++i) w.part32[i] = cv.take<uint32_t>(lists);
     if (n_blocks > 0) {
-        const size_t block = (size_t)Q * (size_t)(k + 1) * 4;
+        const size_t block = (size_t)Q * (size_t)(k + 1) * (size_t)f.cols;
         w.local = cv.take<int32_t>(block);
         w.gathered = cv.take<int32_t>((size_t)n_blocks * block);
     }
     return w;
 }
 
-size_t align_topk_ws_bytes(int32_t Q, int64_t keys, int32_t k, bool wide, int32_t n_blocks, bool rates = false,
-                           bool span = false) {
+size_t align_topk_ws_bytes(const AlignTopkForm &f, int32_t Q, int64_t keys, int32_t k, int32_t n_blocks) {
     Carver cv(nullptr);
-    align_topk_ws_layout(cv, Q, k, wide, n_blocks, rates, span);
+    align_topk_ws_layout(cv, f, Q, k, n_blocks);
     return cv.fixed() + tol_ws_bytes(Q, keys);
 }
 
-// what tvz_align_topk_merge, tvz_align_wide_topk_merge, tvz_align_rates_topk_merge and tvz_align_span_topk_merge
-// refuse, apart from their pointers and flags
+// The table: each kernel is launched once, here, with its own argument list out of the aggregate.
+constexpr AlignTopkForm kAlignForms[] = {
+    // kAlignBounded: tvz_align_topk.  It has no flags argument (its callers pass 0), and its B <= 2047 fits the window:
+    // all its bins, and no resume positions
+    {4, 0, false, false, "alignment top-k", "tvz_align_topk_workspace_bytes", "tvz_align_topk_sharded_workspace_bytes",
+     kAlignMaxBins, nullptr, 0u, 0u, al_static_lds<AlHit>(),
+     [](const AlignLaunch &l) {
+         hipLaunchKernelGGL(ts_align_topk_kernel, l.grid, dim3(kAlBlock), l.lds, l.st, l.c->rows.p, l.n_rows, l.c->keys.p,
+                            l.q->sv, l.b->d_q_offsets, l.q->qm, l.lds_keys, l.a->eps, l.B, l.a->min_votes, l.a->min_score,
+                            l.b->d_exclude_ids, l.k, l.w->part_w, l.w->part_p, l.n_lists, l.w->totals);
+     },
+     [](const AlignLaunch &l) {
+         hipLaunchKernelGGL(ts_align_topk_reduce_kernel, l.grid, dim3(kAlReduceBlock), 0, l.st, l.w->part_w, l.w->part_p,
+                            l.n_lists, l.k, l.q->qm, l.lds_keys, l.w->totals, l.d_out);
+     },
+     [](const AlignMergeArgs &m) {
+         hipLaunchKernelGGL(ts_align_topk_merge_kernel, m.grid, dim3(kAlMergeBlock), 0, m.st, m.d_gathered, m.n_lists, m.Q,
+                            m.k, m.d_queries, m.d_q_offsets, m.d_topk, m.d_totals);
+     }},
+    // kAlignWide: tvz_align_wide_topk
+    {4, 1, false, false, "wide alignment top-k", "tvz_align_wide_topk_workspace_bytes",
+     "tvz_align_wide_topk_sharded_workspace_bytes", 2 * kAwMaxB + 1, "TVZ_ALIGN_WIDE_MAX_B", kAwContain, 0u,
+     al_static_lds<AwHit>(),
+     [](const AlignLaunch &l) {
+         hipLaunchKernelGGL(ts_alignw_sweep_kernel, l.grid, dim3(kAlBlock), l.lds, l.st, l.c->rows.p, l.n_rows, l.c->keys.p,
+                            l.q->sv, l.b->d_q_offsets, l.q->qm, l.lds_keys, l.a->eps, l.B, l.width, l.a->min_votes,
+                            l.a->min_score, l.flags, l.b->d_exclude_ids, l.k, l.w->part_w, l.w->part_p, l.w->part32[0],
+                            l.n_lists, l.w->totals);
+     },
+     [](const AlignLaunch &l) {
+         hipLaunchKernelGGL(ts_alignw_reduce_kernel, l.grid, dim3(kAlReduceBlock), 0, l.st, l.w->part_w, l.w->part_p,
+                            l.w->part32[0], l.n_lists, l.k, l.q->qm, l.lds_keys, l.w->totals, l.d_out);
+     },
+     [](const AlignMergeArgs &m) {
+         hipLaunchKernelGGL(ts_alignw_merge_kernel, m.grid, dim3(kAlMergeBlock), 0, m.st, m.d_gathered, m.n_lists, m.Q, m.k,
+                            m.flags, m.d_queries, m.d_q_offsets, m.d_topk, m.d_totals);
+     }},
+    // kAlignRates: tvz_align_rates_topk - the wide call with the rate loop
+    {5, 2, true, false, "alignment top-k with rates", "tvz_align_rates_topk_workspace_bytes", nullptr, 2 * kAwMaxB + 1,
+     "TVZ_ALIGN_WIDE_MAX_B", kAwContain, 0u, al_static_lds<ArHit>(),
+     [](const AlignLaunch &l) {
+         hipLaunchKernelGGL(ts_alignr_sweep_kernel, l.grid, dim3(kAlBlock), l.lds, l.st, l.c->rows.p, l.n_rows, l.c->keys.p,
+                            l.q->sv, l.b->d_q_offsets, l.q->qm, l.lds_keys, l.a->eps, l.B, l.width, *l.rates,
+                            l.a->min_votes, l.a->min_score, l.flags, l.b->d_exclude_ids, l.k, l.w->part_w, l.w->part_p,
+                            l.w->part32[0], l.w->part32[1], l.n_lists, l.w->totals);
+     },
+     [](const AlignLaunch &l) {
+         hipLaunchKernelGGL(ts_alignr_reduce_kernel, l.grid, dim3(kAlReduceBlock), 0, l.st, l.w->part_w, l.w->part_p,
+                            l.w->part32[0], l.w->part32[1], l.n_lists, l.k, l.q->qm, l.lds_keys, l.w->totals, l.d_out);
+     },
+     [](const AlignMergeArgs &m) {
+         hipLaunchKernelGGL(ts_alignr_merge_kernel, m.grid, dim3(kAlMergeBlock), 0, m.st, m.d_gathered, m.n_lists, m.Q, m.k,
+                            m.flags, m.d_queries, m.d_q_offsets, m.d_topk, m.d_totals);
+     }},
+    // kAlignSpan: tvz_align_span_topk - the call with rates and the span pass
+    {8, 4, true, true, "alignment top-k with spans", "tvz_align_span_topk_workspace_bytes", nullptr, 2 * kAwMaxB + 1,
+     "TVZ_ALIGN_WIDE_MAX_B", kAwContain | kAsLocal, kAwContain | kAsLocal, al_static_lds<AsHit>(),
+     [](const AlignLaunch &l) {
+         hipLaunchKernelGGL(ts_aligns_sweep_kernel, l.grid, dim3(kAlBlock), l.lds, l.st, l.c->rows.p, l.n_rows, l.c->keys.p,
+                            l.q->sv, l.b->d_q_offsets, l.q->qm, l.lds_keys, l.a->eps, l.B, l.width, *l.rates,
+                            l.a->min_votes, l.a->min_score, l.flags, l.b->d_exclude_ids, l.k, l.w->part_w, l.w->part_p,
+                            l.w->part32[0], l.w->part32[1], l.w->part32[2], l.w->part32[3], l.n_lists, l.w->totals);
+     },
+     [](const AlignLaunch &l) {
+         hipLaunchKernelGGL(ts_aligns_reduce_kernel, l.grid, dim3(kAlReduceBlock), 0, l.st, l.w->part_w, l.w->part_p,
+                            l.w->part32[0], l.w->part32[1], l.w->part32[2], l.w->part32[3], l.n_lists, l.k, l.q->qm,
+                            l.lds_keys, l.w->totals, l.d_out);
+     },
+     [](const AlignMergeArgs &m) {
+         hipLaunchKernelGGL(ts_aligns_merge_kernel, m.grid, dim3(kAlMergeBlock), 0, m.st, m.d_gathered, m.n_lists, m.Q, m.k,
+                            m.flags, m.d_queries, m.d_q_offsets, m.d_topk, m.d_totals);
+     }},
+};
+static_assert(sizeof(kAlignForms) / sizeof(kAlignForms[0]) == kAlignFormCount, "one entry per AlignForm, in its order");
+
+// what every form's merge refuses, apart from its pointers and flags
 int check_align_merge(int32_t n_lists, int32_t k) {
     if (n_lists < 1 || n_lists > kAlMergeMaxLists)
         return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment top-k merge: %d lists outside 1..%d", (int)n_lists, kAlMergeMaxLists);
@@ -2072,40 +2183,11 @@ int check_align_merge(int32_t n_lists, int32_t k) {
 
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-// what tells tvz_align_topk, tvz_align_wide_topk and tvz_align_rates_topk apart on the host.  The sweeps' argument
-// lists differ (the window width, the flags, the rates, the third and fourth list), so the launches below name the
-// kernels themselves, chosen by `wide`, `rates` and `span` (rates: wide too, with the rate loop and a block row of 5
-// columns; span: rates too, with the span pass and a block row of 8).
-struct AlignTopkForm {
-    bool wide, rates, span;
-    int cols;                        // int32 columns of a block row
-    const char *what, *sizer;        // the call in messages; the sizing function the workspace message names
-    const char *sharded_sizer;       // ... and the one it names for the sharded form (n_ranks >= 1)
-    int32_t max_bins;                // 2B + 1 at most
-    const char *wide_limit;          // check_align_bins
-    uint32_t flags;                  // the permitted ones
-    int static_lds;                  // of the sweep
-};
-constexpr AlignTopkForm kAlignBounded{false, false, false, 4, "alignment top-k", "tvz_align_topk_workspace_bytes",
-                                      "tvz_align_topk_sharded_workspace_bytes", kAlignMaxBins, nullptr, 0u,
-                                      al_static_lds<AlHit>()};
-constexpr AlignTopkForm kAlignWide{true, false, false, 4, "wide alignment top-k", "tvz_align_wide_topk_workspace_bytes",
-                                   "tvz_align_wide_topk_sharded_workspace_bytes", 2 * kAwMaxB + 1, "TVZ_ALIGN_WIDE_MAX_B",
-                                   kAwContain, al_static_lds<AwHit>()};
-// (no RCCL form yet: the sharded sizer is never named)
-constexpr AlignTopkForm kAlignRates{true, true, false, 5, "alignment top-k with rates", "tvz_align_rates_topk_workspace_bytes",
-                                    "tvz_align_rates_topk_workspace_bytes", 2 * kAwMaxB + 1, "TVZ_ALIGN_WIDE_MAX_B",
-                                    kAwContain, al_static_lds<ArHit>()};
-constexpr AlignTopkForm kAlignSpan{true, true, true, 8, "alignment top-k with spans", "tvz_align_span_topk_workspace_bytes",
-                                   "tvz_align_span_topk_workspace_bytes", 2 * kAwMaxB + 1, "TVZ_ALIGN_WIDE_MAX_B",
-                                   kAwContain | kAsLocal, al_static_lds<AsHit>()};
-
-// the flags of tvz_align_span_topk and its merge: TVZ_ALIGN_CONTAIN or TVZ_ALIGN_LOCAL, not both (two score kinds)
-int check_align_span_flags(uint32_t flags) {
-    TVZ_REQUIRE((flags & ~kAlignSpan.flags) == 0u, "%s: unknown flag bits 0x%x", kAlignSpan.what,
-                (unsigned)(flags & ~kAlignSpan.flags));
-    TVZ_REQUIRE(flags != (kAwContain | kAsLocal), "%s: TVZ_ALIGN_CONTAIN and TVZ_ALIGN_LOCAL are two score kinds: one of them",
-                kAlignSpan.what);
+// the flags of a call (where = "") or of its merge (" merge"): the form's own, and of two score kinds one
+int check_align_flags(const AlignTopkForm &f, uint32_t flags, const char *where) {
+    TVZ_REQUIRE((flags & ~f.flags) == 0u, "%s%s: unknown flag bits 0x%x", f.what, where, (unsigned)(flags & ~f.flags));
+    TVZ_REQUIRE(f.exclusive == 0u || (flags & f.exclusive) != f.exclusive,
+                "%s: TVZ_ALIGN_CONTAIN and TVZ_ALIGN_LOCAL are two score kinds: one of them", f.what);
     return TVZ_OK;
 }
 
@@ -2120,26 +2202,46 @@ int check_align_limits(const AlignTopkForm &f, const AlignCall &a, int32_t k, in
     return TVZ_OK;
 }
 
-// The four calls: sort -> sweep that keeps the k best -> per-query selection.  rates: f.rates' list, checked by the
-// caller (check_align_rates), NULL otherwise.  n_ranks = 0: d_out is the caller's.
-// n_ranks >= 1: the workspace also holds the local block and n_ranks gathered ones (the form's sharded sizing
-// function); d_out = NULL writes the block into the workspace's own, and `blocks` is told where it went and where the
-// all-gather's target is.
-int align_topk_run(const AlignTopkForm &f, tvz_corpus *c, const Batch &b, const AlignCall &a, uint32_t flags, int32_t k,
-                   int32_t *d_out, Workspace ws, int32_t n_ranks, void *hip_stream, ShardBlocks *blocks,
-                   const AlRates *rates = nullptr) {
-    const int32_t Q = b.Q, max_query_len = b.max_query_len;
+// The arguments of a call and of its _shards form beyond the batch and the sink.
+struct AlignAsk {
+    AlignCall a;
+    const double *h_rates;           // the forms that take rates; NULL, 0 otherwise
+    int32_t n_rates;
+    uint32_t flags;                  // 0 for the form that has none
+    int32_t k;
+};
+
+// What a form refuses before any handle is looked at, for the call and for its _shards form alike: the rate list
+// (-> *rates, the sweep's by-value argument), then - limits_first - the flags and the limits.
+int check_align_early(const AlignTopkForm &f, const AlignAsk &s, int32_t max_query_len, AlRates *rates) {
+    if (f.takes_rates)
+        if (int rc = check_align_rates(s.h_rates, s.n_rates, rates)) return rc;
+    if (f.limits_first) {
+        if (int rc = check_align_flags(f, s.flags, "")) return rc;
+        if (int rc = check_align_limits(f, s.a, s.k, max_query_len)) return rc;
+    }
+    return TVZ_OK;
+}
+
+// One handle: sort -> sweep that keeps the k best -> per-query selection.  `rates`: checked (check_align_early).
+// n_ranks = 0: d_out is the caller's.  n_ranks >= 1: the workspace also holds the local block and n_ranks gathered ones
+// (the form's sharded sizing function); d_out = NULL writes the block into the workspace's own, and `blocks` is told
+// where it went and where the all-gather's target is.
+int align_topk_run(const AlignTopkForm &f, tvz_corpus *c, const Batch &b, const AlignAsk &s, const AlRates &rates,
+                   int32_t *d_out, Workspace ws, int32_t n_ranks, void *hip_stream, ShardBlocks *blocks) {
+    const AlignCall &a = s.a;
+    const int32_t Q = b.Q, max_query_len = b.max_query_len, k = s.k;
+    TVZ_REQUIRE(n_ranks == 0 || f.sharded_sizer != nullptr, "%s: it has no sharded form", f.what);
     if (int rc = check_batch_args(c, b, 0)) return rc;
     int32_t B = 0;
-    if (int rc = check_align_bins(a.eps, a.max_offset, f.max_bins, f.wide_limit, &B)) return rc;
-    if (f.wide)                      // (the bounded call has no flags argument)
-        TVZ_REQUIRE((flags & ~f.flags) == 0u, "%s: unknown flag bits 0x%x", f.what, (unsigned)(flags & ~f.flags));
+    if (int rc = check_align_bins(a.eps, a.max_offset, f.max_bins, f.bins_limit, &B)) return rc;
+    if (int rc = check_align_flags(f, s.flags, "")) return rc;
     if (int rc = check_align_limits(f, a, k, max_query_len)) return rc;
     if (Q == 0) return TVZ_OK;
     Carver cv(ws.p);
-    const AlignTopkWs w = align_topk_ws_layout(cv, Q, k, f.wide, n_ranks, f.rates, f.span);
+    const AlignTopkWs w = align_topk_ws_layout(cv, f, Q, k, n_ranks);
     const int32_t lds_keys = std::max(max_query_len, 1);
-    const int32_t width = aw_width(B);   // (the bounded call's B <= 2047: all its bins, and no resume positions)
+    const int32_t width = aw_width(B);
     const size_t lds = aw_lds_bytes(lds_keys, B, width);
     auto args_ok = [&]() -> int {
         TVZ_REQUIRE(d_out != nullptr || w.local != nullptr, "d_out is NULL");
@@ -2159,122 +2261,34 @@ int align_topk_run(const AlignTopkForm &f, tvz_corpus *c, const Batch &b, const 
         return rc;
     const int64_t n_rows = t.n_rows;
     const int n_blocks = n_rows ? (int)std::min<int64_t>(tvz::ceil_div(n_rows, (int64_t)kAlWaves), tol_topk_max_blocks(Q)) : 0;
-    const dim3 grid((unsigned)n_blocks, (unsigned)Q);
+    AlignLaunch l{dim3((unsigned)n_blocks, (unsigned)Q), lds, st, c, n_rows, &b, &t.ws, &a, &rates, s.flags, lds_keys, B,
+                  width, k, n_blocks, &w, d_out};
     if (n_blocks) {
-        if (f.span)
-            hipLaunchKernelGGL(ts_aligns_sweep_kernel, grid, dim3(kAlBlock), lds, st, c->rows.p, n_rows, c->keys.p, t.ws.sv,
-                               b.d_q_offsets, t.ws.qm, lds_keys, a.eps, B, width, *rates, a.min_votes, a.min_score, flags,
-                               b.d_exclude_ids, k, w.part_w, w.part_p, w.part_v, w.part_r, w.part_t, w.part_n, n_blocks,
-                               w.totals);
-        else if (f.rates)
-            hipLaunchKernelGGL(ts_alignr_sweep_kernel, grid, dim3(kAlBlock), lds, st, c->rows.p, n_rows, c->keys.p, t.ws.sv,
-                               b.d_q_offsets, t.ws.qm, lds_keys, a.eps, B, width, *rates, a.min_votes, a.min_score, flags,
-                               b.d_exclude_ids, k, w.part_w, w.part_p, w.part_v, w.part_r, n_blocks, w.totals);
-        else if (f.wide)
-            hipLaunchKernelGGL(ts_alignw_sweep_kernel, grid, dim3(kAlBlock), lds, st, c->rows.p, n_rows, c->keys.p, t.ws.sv,
-                               b.d_q_offsets, t.ws.qm, lds_keys, a.eps, B, width, a.min_votes, a.min_score, flags,
-                               b.d_exclude_ids, k, w.part_w, w.part_p, w.part_v, n_blocks, w.totals);
-        else
-            hipLaunchKernelGGL(ts_align_topk_kernel, grid, dim3(kAlBlock), lds, st, c->rows.p, n_rows, c->keys.p, t.ws.sv,
-                               b.d_q_offsets, t.ws.qm, lds_keys, a.eps, B, a.min_votes, a.min_score, b.d_exclude_ids, k,
-                               w.part_w, w.part_p, n_blocks, w.totals);
+        f.sweep(l);
         TVZ_HIP(hipGetLastError());
     }
-    if (f.span)
-        hipLaunchKernelGGL(ts_aligns_reduce_kernel, dim3((unsigned)Q), dim3(kAlReduceBlock), 0, st, w.part_w, w.part_p, w.part_v,
-                           w.part_r, w.part_t, w.part_n, n_blocks, k, t.ws.qm, lds_keys, w.totals, d_out);
-    else if (f.rates)
-        hipLaunchKernelGGL(ts_alignr_reduce_kernel, dim3((unsigned)Q), dim3(kAlReduceBlock), 0, st, w.part_w, w.part_p, w.part_v,
-                           w.part_r, n_blocks, k, t.ws.qm, lds_keys, w.totals, d_out);
-    else if (f.wide)
-        hipLaunchKernelGGL(ts_alignw_reduce_kernel, dim3((unsigned)Q), dim3(kAlReduceBlock), 0, st, w.part_w, w.part_p, w.part_v,
-                           n_blocks, k, t.ws.qm, lds_keys, w.totals, d_out);
-    else
-        hipLaunchKernelGGL(ts_align_topk_reduce_kernel, dim3((unsigned)Q), dim3(kAlReduceBlock), 0, st, w.part_w, w.part_p,
-                           n_blocks, k, t.ws.qm, lds_keys, w.totals, d_out);
+    l.grid = dim3((unsigned)Q);
+    f.reduce(l);
     TVZ_HIP(hipGetLastError());
     return record(c, st);
 }
 
-}  // namespace
-
-// used by tvz_comm.hip (same shared object, not exported): either call, with the sharded forms' blocks
-int tvz_align_topk_local(tvz_corpus *c, const Batch &b, const AlignCall &a, int32_t k, int32_t *d_out, Workspace ws,
-                         int32_t n_ranks, void *hip_stream, ShardBlocks *blocks) {
-    return align_topk_run(kAlignBounded, c, b, a, 0u, k, d_out, ws, n_ranks, hip_stream, blocks);
+// A call of the C ABI: what the form refuses early, then the handle.
+int align_topk_call(AlignForm form, tvz_corpus *c, const Batch &b, const AlignAsk &s, int32_t *d_out, Workspace ws,
+                    int32_t n_ranks, void *hip_stream, ShardBlocks *blocks) {
+    const AlignTopkForm &f = kAlignForms[form];
+    AlRates rates{};
+    if (int rc = check_align_early(f, s, b.max_query_len, &rates)) return rc;
+    return align_topk_run(f, c, b, s, rates, d_out, ws, n_ranks, hip_stream, blocks);
 }
 
-int tvz_align_wide_topk_local(tvz_corpus *c, const Batch &b, const AlignCall &a, uint32_t flags, int32_t k, int32_t *d_out,
-                              Workspace ws, int32_t n_ranks, void *hip_stream, ShardBlocks *blocks) {
-    return align_topk_run(kAlignWide, c, b, a, flags, k, d_out, ws, n_ranks, hip_stream, blocks);
-}
-
-static int tvz_align_topk_impl(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
-                               int32_t max_query_len, double eps, double max_offset, int32_t min_votes,
-                               int32_t min_score, const int32_t *d_exclude_ids, int32_t k, int32_t *d_out,
-                               void *d_workspace, size_t workspace_bytes, void *hip_stream) {
-    return tvz_align_topk_local(c, Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids},
-                                AlignCall{eps, max_offset, min_votes, min_score}, k, d_out,
-                                Workspace{d_workspace, workspace_bytes}, 0, hip_stream, nullptr);
-}
-
-static int tvz_align_wide_topk_impl(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
-                                    int32_t max_query_len, double eps, double max_offset, int32_t min_votes,
-                                    int32_t min_score, uint32_t flags, const int32_t *d_exclude_ids, int32_t k,
-                                    int32_t *d_out, void *d_workspace, size_t workspace_bytes, void *hip_stream) {
-    return tvz_align_wide_topk_local(c, Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids},
-                                     AlignCall{eps, max_offset, min_votes, min_score}, flags, k, d_out,
-                                     Workspace{d_workspace, workspace_bytes}, 0, hip_stream, nullptr);
-}
-
-static int tvz_align_rates_topk_impl(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
-                                     int32_t max_query_len, double eps, double max_offset, const double *h_rates,
-                                     int32_t n_rates, int32_t min_votes, int32_t min_score, uint32_t flags,
-                                     const int32_t *d_exclude_ids, int32_t k, int32_t *d_out, void *d_workspace,
-                                     size_t workspace_bytes, void *hip_stream) {
-    AlRates rates;
-    if (int rc = check_align_rates(h_rates, n_rates, &rates)) return rc;
-    return align_topk_run(kAlignRates, c, Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids},
-                          AlignCall{eps, max_offset, min_votes, min_score}, flags, k, d_out,
-                          Workspace{d_workspace, workspace_bytes}, 0, hip_stream, nullptr, &rates);
-}
-
-// The merge of any call's blocks (tvz_align_topk_merge: f = kAlignBounded, flags = 0; tvz_align_wide_topk_merge;
-// tvz_align_rates_topk_merge and tvz_align_span_topk_merge, whose rows have f.cols = 5 and 8 columns).
-static int align_merge_impl(const AlignTopkForm &f, const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t k,
-                            uint32_t flags, const double *d_queries, const int64_t *d_q_offsets, int32_t *d_topk,
-                            int32_t *d_totals, void *hip_stream) {
-    TVZ_REQUIRE(Q >= 0, "Q=%d is negative", (int)Q);
-    if (int rc = check_align_merge(n_lists, k)) return rc;
-    TVZ_REQUIRE((flags & ~f.flags) == 0u, "%s merge: unknown flag bits 0x%x", f.what, (unsigned)(flags & ~f.flags));
-    if (f.span)
-        if (int rc = check_align_span_flags(flags)) return rc;
-    if (Q == 0) return TVZ_OK;
-    TVZ_REQUIRE(d_gathered && d_queries && d_q_offsets && d_topk && d_totals, "NULL argument");
-    TVZ_REQUIRE(aligned16(d_gathered) && aligned16(d_topk), "alignment top-k merge: the blocks and d_topk must be 16-byte aligned");
-    const dim3 grid((unsigned)tvz::ceil_div(Q, kAlMergeWaves));
-    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    if (f.span)
-        hipLaunchKernelGGL(ts_aligns_merge_kernel, grid, dim3(kAlMergeBlock), 0, st, d_gathered, n_lists, Q, k, flags,
-                           d_queries, d_q_offsets, d_topk, d_totals);
-    else if (f.rates)
-        hipLaunchKernelGGL(ts_alignr_merge_kernel, grid, dim3(kAlMergeBlock), 0, st, d_gathered, n_lists, Q, k, flags,
-                           d_queries, d_q_offsets, d_topk, d_totals);
-    else if (f.wide)
-        hipLaunchKernelGGL(ts_alignw_merge_kernel, grid, dim3(kAlMergeBlock), 0, st, d_gathered, n_lists, Q, k, flags,
-                           d_queries, d_q_offsets, d_topk, d_totals);
-    else
-        hipLaunchKernelGGL(ts_align_topk_merge_kernel, grid, dim3(kAlMergeBlock), 0, st, d_gathered, n_lists, Q, k, d_queries,
-                           d_q_offsets, d_topk, d_totals);
-    return launched();
-}
-
-// The shards of one process, for any call (tvz_align_topk_shards: f = kAlignBounded, flags = 0;
-// tvz_align_wide_topk_shards; tvz_align_rates_topk_shards and tvz_align_span_topk_shards with the checked `rates`).
-static int align_shards_impl(const AlignTopkForm &f, tvz_corpus *const *shards, int32_t n_shards, const Batch &b,
-                             const AlignCall &a, uint32_t flags, int32_t k, int32_t *d_blocks, int32_t *d_topk,
-                             int32_t *d_totals, Workspace ws, void *hip_stream, const AlRates *rates = nullptr) {
-    const int32_t Q = b.Q;
+// The shards of one process, for any form: every handle's call into its block of d_blocks, then the merge.
+int align_shards_impl(AlignForm form, tvz_corpus *const *shards, int32_t n_shards, const Batch &b, const AlignAsk &s,
+                      int32_t *d_blocks, int32_t *d_topk, int32_t *d_totals, Workspace ws, void *hip_stream) {
+    const AlignTopkForm &f = kAlignForms[form];
+    const int32_t Q = b.Q, k = s.k;
+    AlRates rates{};
+    if (int rc = check_align_early(f, s, b.max_query_len, &rates)) return rc;
     TVZ_REQUIRE(shards != nullptr && n_shards >= 1, "no shards");
     TVZ_REQUIRE(Q >= 0, "Q=%d is negative", (int)Q);
     if (int rc = check_align_merge(n_shards, k)) return rc;
@@ -2287,12 +2301,49 @@ static int align_shards_impl(const AlignTopkForm &f, tvz_corpus *const *shards, 
     // every handle's call makes the same checks of the same arguments (the flags among them): what one refuses, the
     // first one refuses, before anything is enqueued
     for (int32_t r = 0; r < n_shards; ++r)
-        if (int rc = align_topk_run(f, shards[r], b, a, flags, k,
+        if (int rc = align_topk_run(f, shards[r], b, s, rates,
                                     d_blocks + (size_t)r * (size_t)Q * (size_t)(k + 1) * (size_t)f.cols, ws, 0, hip_stream,
-                                    nullptr, rates))
+                                    nullptr))
             return rc;
     DeviceGuard dg(shards[0]->device);
-    return align_merge_impl(f, d_blocks, n_shards, Q, k, flags, b.d_queries, b.d_q_offsets, d_topk, d_totals, hip_stream);
+    return tvz_align_merge_local(form, d_blocks, n_shards, Q, k, s.flags, b.d_queries, b.d_q_offsets, d_topk, d_totals,
+                                 hip_stream);
+}
+
+Batch align_batch(const double *d_queries, const int64_t *d_q_offsets, int32_t Q, int32_t max_query_len,
+                  const int32_t *d_exclude_ids) {
+    return Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids};
+}
+
+// What the sizing exports share: the argument refusals, the `keys` default and the room for one longest query.
+size_t align_sizing(AlignForm form, int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k, int32_t n_blocks) {
+    if (Q < 0 || max_query_len < 0 || total_query_keys < 0 || k < 1) return 0;
+    const int64_t keys = total_query_keys > 0 ? total_query_keys : (int64_t)Q * max_query_len;
+    return align_topk_ws_bytes(kAlignForms[form], Q, std::max<int64_t>(keys, max_query_len), k, n_blocks);
+}
+
+}  // namespace
+
+// used by tvz_comm.hip (same shared object, not exported): a form's call with the sharded forms' blocks
+int tvz_align_topk_local(AlignForm form, tvz_corpus *c, const Batch &b, const AlignCall &a, uint32_t flags, int32_t k,
+                         int32_t *d_out, Workspace ws, int32_t n_ranks, void *hip_stream, ShardBlocks *blocks) {
+    return align_topk_call(form, c, b, AlignAsk{a, nullptr, 0, flags, k}, d_out, ws, n_ranks, hip_stream, blocks);
+}
+
+// ... and the merge of a form's blocks, rows of f.cols columns (the form without flags: 0)
+int tvz_align_merge_local(AlignForm form, const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t k, uint32_t flags,
+                          const double *d_queries, const int64_t *d_q_offsets, int32_t *d_topk, int32_t *d_totals,
+                          void *hip_stream) {
+    const AlignTopkForm &f = kAlignForms[form];
+    TVZ_REQUIRE(Q >= 0, "Q=%d is negative", (int)Q);
+    if (int rc = check_align_merge(n_lists, k)) return rc;
+    if (int rc = check_align_flags(f, flags, " merge")) return rc;
+    if (Q == 0) return TVZ_OK;
+    TVZ_REQUIRE(d_gathered && d_queries && d_q_offsets && d_topk && d_totals, "NULL argument");
+    TVZ_REQUIRE(aligned16(d_gathered) && aligned16(d_topk), "alignment top-k merge: the blocks and d_topk must be 16-byte aligned");
+    f.merge(AlignMergeArgs{dim3((unsigned)tvz::ceil_div(Q, kAlMergeWaves)), reinterpret_cast<hipStream_t>(hip_stream),
+                           d_gathered, n_lists, Q, k, flags, d_queries, d_q_offsets, d_topk, d_totals});
+    return launched();
 }
 
 #ifdef TVZ_IX_STAMP
@@ -2462,46 +2513,44 @@ TVZ_EXPORT int tvz_align(tvz_corpus *c, const double *d_query, int32_t n, double
     TVZ_GUARDED(tvz_align_impl(c, d_query, n, eps, max_offset, d_out, out_rows, n_rows, hip_stream));
 }
 
+// The alignment top-k's exports: each names its form (kAlignForms) and hands its arguments on.
+
 TVZ_EXPORT size_t tvz_align_topk_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k) {
-    if (Q < 0 || max_query_len < 0 || total_query_keys < 0 || k < 1) return 0;
-    const int64_t keys = total_query_keys > 0 ? total_query_keys : (int64_t)Q * max_query_len;
-    return align_topk_ws_bytes(Q, std::max<int64_t>(keys, max_query_len), k, false, 0);
+    return align_sizing(kAlignBounded, Q, max_query_len, total_query_keys, k, 0);
 }
 
 TVZ_EXPORT size_t tvz_align_topk_sharded_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys,
                                                          int32_t k, int32_t n_ranks) {
-    if (Q < 0 || max_query_len < 0 || total_query_keys < 0 || k < 1 || n_ranks < 0) return 0;
-    const int64_t keys = total_query_keys > 0 ? total_query_keys : (int64_t)Q * max_query_len;
-    return align_topk_ws_bytes(Q, std::max<int64_t>(keys, max_query_len), k, false, std::max(n_ranks, 1));
+    return n_ranks < 0 ? 0 : align_sizing(kAlignBounded, Q, max_query_len, total_query_keys, k, std::max(n_ranks, 1));
 }
 
 TVZ_EXPORT int tvz_align_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
                               int32_t max_query_len, double eps, double max_offset, int32_t min_votes,
                               int32_t min_score, const int32_t *d_exclude_ids, int32_t k, int32_t *d_out,
                               void *d_workspace, size_t workspace_bytes, void *hip_stream) {
-    TVZ_GUARDED(tvz_align_topk_impl(c, d_queries, d_q_offsets, Q, max_query_len, eps, max_offset, min_votes, min_score,
-                                    d_exclude_ids, k, d_out, d_workspace, workspace_bytes, hip_stream));
+    TVZ_GUARDED(align_topk_call(kAlignBounded, c, align_batch(d_queries, d_q_offsets, Q, max_query_len, d_exclude_ids),
+                                AlignAsk{{eps, max_offset, min_votes, min_score}, nullptr, 0, 0u, k}, d_out,
+                                Workspace{d_workspace, workspace_bytes}, 0, hip_stream, nullptr));
 }
 
 TVZ_EXPORT size_t tvz_align_wide_topk_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k) {
-    if (Q < 0 || max_query_len < 0 || total_query_keys < 0 || k < 1) return 0;
-    const int64_t keys = total_query_keys > 0 ? total_query_keys : (int64_t)Q * max_query_len;
-    return align_topk_ws_bytes(Q, std::max<int64_t>(keys, max_query_len), k, true, 0);
+    return align_sizing(kAlignWide, Q, max_query_len, total_query_keys, k, 0);
 }
 
 TVZ_EXPORT int tvz_align_wide_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
                                    int32_t max_query_len, double eps, double max_offset, int32_t min_votes,
                                    int32_t min_score, uint32_t flags, const int32_t *d_exclude_ids, int32_t k,
                                    int32_t *d_out, void *d_workspace, size_t workspace_bytes, void *hip_stream) {
-    TVZ_GUARDED(tvz_align_wide_topk_impl(c, d_queries, d_q_offsets, Q, max_query_len, eps, max_offset, min_votes, min_score,
-                                         flags, d_exclude_ids, k, d_out, d_workspace, workspace_bytes, hip_stream));
+    TVZ_GUARDED(align_topk_call(kAlignWide, c, align_batch(d_queries, d_q_offsets, Q, max_query_len, d_exclude_ids),
+                                AlignAsk{{eps, max_offset, min_votes, min_score}, nullptr, 0, flags, k}, d_out,
+                                Workspace{d_workspace, workspace_bytes}, 0, hip_stream, nullptr));
 }
 
 TVZ_EXPORT int tvz_align_topk_merge(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t k,
                                     const double *d_queries, const int64_t *d_q_offsets, int32_t *d_topk,
                                     int32_t *d_totals, void *hip_stream) {
-    TVZ_GUARDED(align_merge_impl(kAlignBounded, d_gathered, n_lists, Q, k, 0u, d_queries, d_q_offsets, d_topk, d_totals,
-                                 hip_stream));
+    TVZ_GUARDED(tvz_align_merge_local(kAlignBounded, d_gathered, n_lists, Q, k, 0u, d_queries, d_q_offsets, d_topk, d_totals,
+                                      hip_stream));
 }
 
 TVZ_EXPORT int tvz_align_topk_shards(tvz_corpus *const *shards, int32_t n_shards, const double *d_queries,
@@ -2510,16 +2559,16 @@ TVZ_EXPORT int tvz_align_topk_shards(tvz_corpus *const *shards, int32_t n_shards
                                      const int32_t *d_exclude_ids, int32_t k, int32_t *d_blocks, int32_t *d_topk,
                                      int32_t *d_totals, void *d_workspace, size_t workspace_bytes, void *hip_stream) {
     TVZ_GUARDED(align_shards_impl(kAlignBounded, shards, n_shards,
-                                  Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids},
-                                  AlignCall{eps, max_offset, min_votes, min_score}, 0u, k, d_blocks, d_topk, d_totals,
-                                  Workspace{d_workspace, workspace_bytes}, hip_stream));
+                                  align_batch(d_queries, d_q_offsets, Q, max_query_len, d_exclude_ids),
+                                  AlignAsk{{eps, max_offset, min_votes, min_score}, nullptr, 0, 0u, k}, d_blocks, d_topk,
+                                  d_totals, Workspace{d_workspace, workspace_bytes}, hip_stream));
 }
 
 TVZ_EXPORT int tvz_align_wide_topk_merge(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t k, uint32_t flags,
                                          const double *d_queries, const int64_t *d_q_offsets, int32_t *d_topk,
                                          int32_t *d_totals, void *hip_stream) {
-    TVZ_GUARDED(align_merge_impl(kAlignWide, d_gathered, n_lists, Q, k, flags, d_queries, d_q_offsets, d_topk, d_totals,
-                                 hip_stream));
+    TVZ_GUARDED(tvz_align_merge_local(kAlignWide, d_gathered, n_lists, Q, k, flags, d_queries, d_q_offsets, d_topk, d_totals,
+                                      hip_stream));
 }
 
 TVZ_EXPORT int tvz_align_wide_topk_shards(tvz_corpus *const *shards, int32_t n_shards, const double *d_queries,
@@ -2528,15 +2577,13 @@ TVZ_EXPORT int tvz_align_wide_topk_shards(tvz_corpus *const *shards, int32_t n_s
                                           const int32_t *d_exclude_ids, int32_t k, int32_t *d_blocks, int32_t *d_topk,
                                           int32_t *d_totals, void *d_workspace, size_t workspace_bytes, void *hip_stream) {
     TVZ_GUARDED(align_shards_impl(kAlignWide, shards, n_shards,
-                                  Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids},
-                                  AlignCall{eps, max_offset, min_votes, min_score}, flags, k, d_blocks, d_topk, d_totals,
-                                  Workspace{d_workspace, workspace_bytes}, hip_stream));
+                                  align_batch(d_queries, d_q_offsets, Q, max_query_len, d_exclude_ids),
+                                  AlignAsk{{eps, max_offset, min_votes, min_score}, nullptr, 0, flags, k}, d_blocks, d_topk,
+                                  d_totals, Workspace{d_workspace, workspace_bytes}, hip_stream));
 }
 
 TVZ_EXPORT size_t tvz_align_rates_topk_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k) {
-    if (Q < 0 || max_query_len < 0 || total_query_keys < 0 || k < 1) return 0;
-    const int64_t keys = total_query_keys > 0 ? total_query_keys : (int64_t)Q * max_query_len;
-    return align_topk_ws_bytes(Q, std::max<int64_t>(keys, max_query_len), k, true, 0, true);
+    return align_sizing(kAlignRates, Q, max_query_len, total_query_keys, k, 0);
 }
 
 TVZ_EXPORT int tvz_align_rates_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
@@ -2544,25 +2591,16 @@ TVZ_EXPORT int tvz_align_rates_topk(tvz_corpus *c, const double *d_queries, cons
                                     int32_t n_rates, int32_t min_votes, int32_t min_score, uint32_t flags,
                                     const int32_t *d_exclude_ids, int32_t k, int32_t *d_out, void *d_workspace,
                                     size_t workspace_bytes, void *hip_stream) {
-    TVZ_GUARDED(tvz_align_rates_topk_impl(c, d_queries, d_q_offsets, Q, max_query_len, eps, max_offset, h_rates, n_rates,
-                                          min_votes, min_score, flags, d_exclude_ids, k, d_out, d_workspace, workspace_bytes,
-                                          hip_stream));
+    TVZ_GUARDED(align_topk_call(kAlignRates, c, align_batch(d_queries, d_q_offsets, Q, max_query_len, d_exclude_ids),
+                                AlignAsk{{eps, max_offset, min_votes, min_score}, h_rates, n_rates, flags, k}, d_out,
+                                Workspace{d_workspace, workspace_bytes}, 0, hip_stream, nullptr));
 }
 
 TVZ_EXPORT int tvz_align_rates_topk_merge(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t k, uint32_t flags,
                                           const double *d_queries, const int64_t *d_q_offsets, int32_t *d_topk,
                                           int32_t *d_totals, void *hip_stream) {
-    TVZ_GUARDED(align_merge_impl(kAlignRates, d_gathered, n_lists, Q, k, flags, d_queries, d_q_offsets, d_topk, d_totals,
-                                 hip_stream));
-}
-
-static int tvz_align_rates_topk_shards_impl(tvz_corpus *const *shards, int32_t n_shards, const Batch &b, const AlignCall &a,
-                                            const double *h_rates, int32_t n_rates, uint32_t flags, int32_t k,
-                                            int32_t *d_blocks, int32_t *d_topk, int32_t *d_totals, Workspace ws,
-                                            void *hip_stream) {
-    AlRates rates;
-    if (int rc = check_align_rates(h_rates, n_rates, &rates)) return rc;
-    return align_shards_impl(kAlignRates, shards, n_shards, b, a, flags, k, d_blocks, d_topk, d_totals, ws, hip_stream, &rates);
+    TVZ_GUARDED(tvz_align_merge_local(kAlignRates, d_gathered, n_lists, Q, k, flags, d_queries, d_q_offsets, d_topk, d_totals,
+                                      hip_stream));
 }
 
 TVZ_EXPORT int tvz_align_rates_topk_shards(tvz_corpus *const *shards, int32_t n_shards, const double *d_queries,
@@ -2571,26 +2609,14 @@ TVZ_EXPORT int tvz_align_rates_topk_shards(tvz_corpus *const *shards, int32_t n_
                                            int32_t min_score, uint32_t flags, const int32_t *d_exclude_ids, int32_t k,
                                            int32_t *d_blocks, int32_t *d_topk, int32_t *d_totals, void *d_workspace,
                                            size_t workspace_bytes, void *hip_stream) {
-    TVZ_GUARDED(tvz_align_rates_topk_shards_impl(
-        shards, n_shards, Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids},
-        AlignCall{eps, max_offset, min_votes, min_score}, h_rates, n_rates, flags, k, d_blocks, d_topk, d_totals,
-        Workspace{d_workspace, workspace_bytes}, hip_stream));
+    TVZ_GUARDED(align_shards_impl(kAlignRates, shards, n_shards,
+                                  align_batch(d_queries, d_q_offsets, Q, max_query_len, d_exclude_ids),
+                                  AlignAsk{{eps, max_offset, min_votes, min_score}, h_rates, n_rates, flags, k}, d_blocks,
+                                  d_topk, d_totals, Workspace{d_workspace, workspace_bytes}, hip_stream));
 }
 
 TVZ_EXPORT size_t tvz_align_span_topk_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k) {
-    if (Q < 0 || max_query_len < 0 || total_query_keys < 0 || k < 1) return 0;
-    const int64_t keys = total_query_keys > 0 ? total_query_keys : (int64_t)Q * max_query_len;
-    return align_topk_ws_bytes(Q, std::max<int64_t>(keys, max_query_len), k, true, 0, true, true);
-}
-
-// the rates, the flags and the limits are refused before the handle is looked at
-static int tvz_align_span_topk_impl(tvz_corpus *c, const Batch &b, const AlignCall &a, const double *h_rates, int32_t n_rates,
-                                    uint32_t flags, int32_t k, int32_t *d_out, Workspace ws, void *hip_stream) {
-    AlRates rates;
-    if (int rc = check_align_rates(h_rates, n_rates, &rates)) return rc;
-    if (int rc = check_align_span_flags(flags)) return rc;
-    if (int rc = check_align_limits(kAlignSpan, a, k, b.max_query_len)) return rc;
-    return align_topk_run(kAlignSpan, c, b, a, flags, k, d_out, ws, 0, hip_stream, nullptr, &rates);
+    return align_sizing(kAlignSpan, Q, max_query_len, total_query_keys, k, 0);
 }
 
 TVZ_EXPORT int tvz_align_span_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
@@ -2598,28 +2624,16 @@ TVZ_EXPORT int tvz_align_span_topk(tvz_corpus *c, const double *d_queries, const
                                    int32_t n_rates, int32_t min_votes, int32_t min_score, uint32_t flags,
                                    const int32_t *d_exclude_ids, int32_t k, int32_t *d_out, void *d_workspace,
                                    size_t workspace_bytes, void *hip_stream) {
-    TVZ_GUARDED(tvz_align_span_topk_impl(
-        c, Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids},
-        AlignCall{eps, max_offset, min_votes, min_score}, h_rates, n_rates, flags, k, d_out,
-        Workspace{d_workspace, workspace_bytes}, hip_stream));
+    TVZ_GUARDED(align_topk_call(kAlignSpan, c, align_batch(d_queries, d_q_offsets, Q, max_query_len, d_exclude_ids),
+                                AlignAsk{{eps, max_offset, min_votes, min_score}, h_rates, n_rates, flags, k}, d_out,
+                                Workspace{d_workspace, workspace_bytes}, 0, hip_stream, nullptr));
 }
 
 TVZ_EXPORT int tvz_align_span_topk_merge(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t k, uint32_t flags,
                                          const double *d_queries, const int64_t *d_q_offsets, int32_t *d_topk,
                                          int32_t *d_totals, void *hip_stream) {
-    TVZ_GUARDED(align_merge_impl(kAlignSpan, d_gathered, n_lists, Q, k, flags, d_queries, d_q_offsets, d_topk, d_totals,
-                                 hip_stream));
-}
-
-static int tvz_align_span_topk_shards_impl(tvz_corpus *const *shards, int32_t n_shards, const Batch &b, const AlignCall &a,
-                                           const double *h_rates, int32_t n_rates, uint32_t flags, int32_t k,
-                                           int32_t *d_blocks, int32_t *d_topk, int32_t *d_totals, Workspace ws,
-                                           void *hip_stream) {
-    AlRates rates;
-    if (int rc = check_align_rates(h_rates, n_rates, &rates)) return rc;
-    if (int rc = check_align_span_flags(flags)) return rc;
-    if (int rc = check_align_limits(kAlignSpan, a, k, b.max_query_len)) return rc;
-    return align_shards_impl(kAlignSpan, shards, n_shards, b, a, flags, k, d_blocks, d_topk, d_totals, ws, hip_stream, &rates);
+    TVZ_GUARDED(tvz_align_merge_local(kAlignSpan, d_gathered, n_lists, Q, k, flags, d_queries, d_q_offsets, d_topk, d_totals,
+                                      hip_stream));
 }
 
 TVZ_EXPORT int tvz_align_span_topk_shards(tvz_corpus *const *shards, int32_t n_shards, const double *d_queries,
@@ -2628,17 +2642,17 @@ TVZ_EXPORT int tvz_align_span_topk_shards(tvz_corpus *const *shards, int32_t n_s
                                           int32_t min_score, uint32_t flags, const int32_t *d_exclude_ids, int32_t k,
                                           int32_t *d_blocks, int32_t *d_topk, int32_t *d_totals, void *d_workspace,
                                           size_t workspace_bytes, void *hip_stream) {
-    TVZ_GUARDED(tvz_align_span_topk_shards_impl(
-        shards, n_shards, Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids},
-        AlignCall{eps, max_offset, min_votes, min_score}, h_rates, n_rates, flags, k, d_blocks, d_topk, d_totals,
-        Workspace{d_workspace, workspace_bytes}, hip_stream));
+    TVZ_GUARDED(align_shards_impl(kAlignSpan, shards, n_shards,
+                                  align_batch(d_queries, d_q_offsets, Q, max_query_len, d_exclude_ids),
+                                  AlignAsk{{eps, max_offset, min_votes, min_score}, h_rates, n_rates, flags, k}, d_blocks,
+                                  d_topk, d_totals, Workspace{d_workspace, workspace_bytes}, hip_stream));
 }
 
+// (unlike its bounded twin this one sizes n_ranks < 0 as one rank instead of answering 0: callers' buffers were sized by
+// it, so the difference is kept on purpose)
 TVZ_EXPORT size_t tvz_align_wide_topk_sharded_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys,
                                                               int32_t k, int32_t n_ranks) {
-    if (Q < 0 || max_query_len < 0 || total_query_keys < 0 || k < 1) return 0;
-    const int64_t keys = total_query_keys > 0 ? total_query_keys : (int64_t)Q * max_query_len;
-    return align_topk_ws_bytes(Q, std::max<int64_t>(keys, max_query_len), k, true, std::max(n_ranks, 1));
+    return align_sizing(kAlignWide, Q, max_query_len, total_query_keys, k, std::max(n_ranks, 1));
 }
 
 TVZ_EXPORT int tvz_find_duplicates_tol(tvz_corpus *c, const double *h_query, int64_t n, double tol, int32_t min_match,

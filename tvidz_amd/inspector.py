@@ -440,25 +440,21 @@ class Inspector:
             one = 1 << 20
             min_score = max(0, min(one, int(self.near_jaccard * one)))          # int() floors: the value is >= 0
             rated = self.near_rates is not None
-            if self.near_spans or self.near_score == "local":
-                rows, totals = corpus.align_span_topk([scene_timestamps], eps=self.near_eps, rates=self.near_rates or (1.0,),
-                                                      max_offset=None, k=self.near_top_k, min_votes=self.near_min_votes,
-                                                      min_score=min_score, contain=self.near_score == "containment",
-                                                      local=self.near_score == "local", exclude_ids=[int(video_id)])
+            contain, local = self.near_score == "containment", self.near_score == "local"
+            # the method and what only it takes; the bounded call is told min_votes only where it is above 1
+            kw = dict(max_offset=None, min_votes=self.near_min_votes, contain=contain)
+            if self.near_spans or local:
+                call, kw = corpus.align_span_topk, dict(kw, rates=self.near_rates or (1.0,), local=local)
             elif rated:
-                rows, totals = corpus.align_rates_topk([scene_timestamps], eps=self.near_eps, rates=self.near_rates,
-                                                       max_offset=None, k=self.near_top_k, min_votes=self.near_min_votes,
-                                                       min_score=min_score, contain=self.near_score == "containment",
-                                                       exclude_ids=[int(video_id)])
+                call, kw = corpus.align_rates_topk, dict(kw, rates=self.near_rates)
             elif self.near_any_offset:
-                rows, totals = corpus.align_wide_topk([scene_timestamps], eps=self.near_eps, max_offset=None,
-                                                      k=self.near_top_k, min_votes=self.near_min_votes,
-                                                      min_score=min_score, contain=self.near_score == "containment",
-                                                      exclude_ids=[int(video_id)])
+                call = corpus.align_wide_topk
             else:
-                kw = {"min_votes": self.near_min_votes} if self.near_min_votes > 1 else {}
-                rows, totals = corpus.align_topk([scene_timestamps], eps=self.near_eps, max_offset=self.near_max_offset,
-                                                 k=self.near_top_k, min_score=min_score, exclude_ids=[int(video_id)], **kw)
+                call, kw = corpus.align_topk, dict(max_offset=self.near_max_offset)
+                if self.near_min_votes > 1:
+                    kw["min_votes"] = self.near_min_votes
+            rows, totals = call([scene_timestamps], eps=self.near_eps, k=self.near_top_k, min_score=min_score,
+                                exclude_ids=[int(video_id)], **kw)
             if int(totals[0]) >= 0:                                            # (refused: more than 4,095 cuts -> the walk)
                 return [r for r in rows[0] if r[0] >= 0], rated
             if not hasattr(corpus, "align"):                                   # (a rank corpus has no walk: no report)

@@ -284,9 +284,8 @@ class ShardedCorpus:
         More than 16 shards (the merge takes up to 16 lists): one such call per group of 16, the groups' answers put
         together as blocks again on the device - k sorted rows and a total each - and merged by one
         tvz_align_topk_merge; still one copy back, same answer."""
-        return self._near_shards(tc.align_topk_shards, tc.align_topk_merge, tc.align_topk_workspace_bytes, queries, k,
-                                 exclude_ids, max_query_len, {},
-                                 dict(eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score))
+        return self._near_shards(tc.FORM_BOUNDED, queries, k, exclude_ids, max_query_len, eps=eps, max_offset=max_offset,
+                                 min_votes=min_votes, min_score=min_score)
 
     supports_align_wide = True
 
@@ -295,10 +294,8 @@ class ShardedCorpus:
         """DeviceCorpus.align_wide_topk over every shard - align_topk at any shift (`max_offset=None`: the widest),
         scored by the containment with `contain`: ONE library call (tvz_align_wide_topk_shards), ONE copy back; more
         than 16 shards are grouped and re-merged by tvz_align_wide_topk_merge, as align_topk does."""
-        return self._near_shards(tc.align_wide_topk_shards, tc.align_wide_topk_merge, tc.align_wide_topk_workspace_bytes,
-                                 queries, k, exclude_ids, max_query_len, dict(contain=contain),
-                                 dict(eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score,
-                                      contain=contain))
+        return self._near_shards(tc.FORM_WIDE, queries, k, exclude_ids, max_query_len, eps=eps, max_offset=max_offset,
+                                 min_votes=min_votes, min_score=min_score, contain=contain)
 
     def align_rates_topk(self, queries, *, eps: float, rates, max_offset=None, k: int = 16, min_votes: int = 1,
                          min_score: int = 0, contain: bool = False, exclude_ids=None, max_query_len=None):
@@ -306,10 +303,8 @@ class ShardedCorpus:
         row kept once at the best of `rates`; rows of five columns, the last the rate's index: ONE library call
         (tvz_align_rates_topk_shards), ONE copy back; more than 16 shards are grouped and re-merged by
         tvz_align_rates_topk_merge, as align_topk does."""
-        return self._near_shards(tc.align_rates_topk_shards, tc.align_rates_topk_merge, tc.align_rates_topk_workspace_bytes,
-                                 queries, k, exclude_ids, max_query_len, dict(contain=contain),
-                                 dict(eps=eps, rates=tuple(rates), max_offset=max_offset, min_votes=min_votes,
-                                      min_score=min_score, contain=contain))
+        return self._near_shards(tc.FORM_RATES, queries, k, exclude_ids, max_query_len, eps=eps, max_offset=max_offset,
+                                 min_votes=min_votes, min_score=min_score, rates=tuple(rates), contain=contain)
 
     def align_span_topk(self, queries, *, eps: float, rates=(1.0,), max_offset=None, k: int = 16, min_votes: int = 1,
                         min_score: int = 0, contain: bool = False, local: bool = False, exclude_ids=None,
@@ -317,34 +312,32 @@ class ShardedCorpus:
         """DeviceCorpus.align_span_topk over every shard - align_rates_topk with the span of every hit, scored inside
         it with `local`; rows of eight columns: ONE library call (tvz_align_span_topk_shards), ONE copy back; more than
         16 shards are grouped and re-merged by tvz_align_span_topk_merge, as align_topk does."""
-        return self._near_shards(tc.align_span_topk_shards, tc.align_span_topk_merge, tc.align_span_topk_workspace_bytes,
-                                 queries, k, exclude_ids, max_query_len, dict(contain=contain, local=local),
-                                 dict(eps=eps, rates=tuple(rates), max_offset=max_offset, min_votes=min_votes,
-                                      min_score=min_score, contain=contain, local=local))
+        return self._near_shards(tc.FORM_SPAN, queries, k, exclude_ids, max_query_len, eps=eps, max_offset=max_offset,
+                                 min_votes=min_votes, min_score=min_score, rates=tuple(rates), contain=contain, local=local)
 
-    def _near_shards(self, shards_call, merge_call, sizer, queries, k, exclude_ids, max_query_len, merge_kw, kw):
-        """What align_topk, align_wide_topk, align_rates_topk and align_span_topk share: the inputs, the calling thread's workspace (`sizer`), one
-        `shards_call` per group of 16 shards, the groups' `merge_call`, the one copy back."""
+    def _near_shards(self, form, queries, k, exclude_ids, max_query_len, **ask):
+        """What the four methods above share, for their `form` (corpus.ALIGN_FORMS) and what they `ask`: the inputs, the
+        calling thread's workspace, one tvz_<stem>_shards per group of 16 shards, the groups' tvz_<stem>_merge, the one
+        copy back."""
         dev = self.dev
         d_q, d_off, Q, max_query_len, d_ex = tc.align_inputs(queries, exclude_ids, max_query_len, dev)
-        ws = tc.thread_workspace(self._near_tls, sizer(Q, max_query_len, d_q.numel(), k), dev)
-        kw = dict(kw, k=k, workspace=ws, d_exclude_ids=d_ex)
+        ws = tc.thread_workspace(self._near_tls, tc.form_workspace_bytes(form, Q, max_query_len, d_q.numel(), k), dev)
         with torch.cuda.device(dev):
             groups = [self.shards[i:i + 16] for i in range(0, self.R, 16)]      # the merge takes up to 16 lists
             if len(groups) == 1:
-                _, rows, totals = shards_call(groups[0], d_q, d_off, max_query_len, **kw)
+                _, rows, totals = tc.form_shards(form, groups[0], d_q, d_off, max_query_len, k, ws, d_ex, **ask)
             else:
-                # more shards than one merge takes: every group's answer is a block again - its k rows, then its total
-                # (rows of 4 columns, 5 with rates, 8 with spans)
+                # more shards than one merge takes: every group's answer is a block again - its k rows, then its total;
+                # the merge takes the form's score kinds from the ask
                 blocks = None
                 for g, part in enumerate(groups):
-                    _, rows, totals = shards_call(part, d_q, d_off, max_query_len, **kw)
+                    _, rows, totals = tc.form_shards(form, part, d_q, d_off, max_query_len, k, ws, d_ex, **ask)
                     if blocks is None:
-                        blocks = torch.zeros((len(groups), Q, k + 1, rows.shape[2]), dtype=torch.int32, device=dev)
+                        blocks = torch.zeros((len(groups), Q, k + 1, form.cols), dtype=torch.int32, device=dev)
                     blocks[g, :, :k] = rows
                     blocks[g, :, k, 0] = -1
                     blocks[g, :, k, 1] = totals
-                rows, totals = merge_call(blocks, k, d_q, d_off, **merge_kw)
+                rows, totals = tc.form_merge(form, blocks, k, d_q, d_off, **{n: ask[n] for n in form.flags})
             rows, totals = _to_host(rows, totals)
         return np.ascontiguousarray(rows), np.ascontiguousarray(totals)
 
