@@ -1,41 +1,55 @@
 """Test-only stand-ins for the near-duplicate search over a sharded table (never imported by the product):
-tests/fakes.py's oracle shard and matcher backend, with sharded.HipBackend's two alignment methods answered by the
-plain-Python restatements (tests/align_topk_ref.py for a rank's block, tests/align_topk_shard_ref.py for the merge)."""
+tests/fakes.py's oracle shard and matcher backend, with sharded.HipBackend's local_align / align_merge answered by the
+plain-Python restatements: tests/align_topk_ref.py and tests/align_wide_ref.py for a rank's block of the bounded and
+of the wide form, tests/align_topk_shard_ref.py and tests/align_wide_shard_ref.py for their merges."""
 import numpy as np
 import torch
 
-from tests import align_topk_ref as atr, align_topk_shard_ref as asr
+from tests import align_topk_ref as atr, align_topk_shard_ref as asr, align_wide_ref as awr, align_wide_shard_ref as wsr
 from tests.fakes import CutReader, OracleBackend, OracleCorpus, cut_inspector, cuts_of_key
+from tvidz_amd.corpus import FORM_BOUNDED, FORM_WIDE
+
+
+def _queries(d_q, d_off):
+    q_all, off = d_q.numpy(), d_off.numpy()
+    return [q_all[off[i]:off[i + 1]].tolist() for i in range(len(off) - 1)]
 
 
 class NearBackend(OracleBackend):
-    """fakes.OracleBackend + local_align_topk / align_topk_merge on CPU tensors."""
+    """fakes.OracleBackend + local_align / align_merge on CPU tensors, for the forms named in `align_forms` (both it
+    knows unless told: `align_forms=(FORM_BOUNDED,)` is a backend with the bounded pair only)."""
 
-    def __init__(self, *a, **kw):
+    def __init__(self, *a, align_forms=(FORM_BOUNDED, FORM_WIDE), **kw):
         super().__init__(*a, **kw)
-        self.near_calls = []                # (Q, eps, max_offset, k, min_votes, min_score) of every batch
+        self.align_forms = tuple(align_forms)
+        self.near_calls = []                # (Q, eps, max_offset, k, min_votes, min_score) of every bounded batch
+        self.wide_calls = []                # (Q, eps, max_offset, k, min_votes, min_score, contain) of every wide batch
 
-    def local_align_topk(self, d_q, d_off, max_len, eps, max_offset, k, min_votes, min_score, d_excl):
-        q_all, off = d_q.numpy(), d_off.numpy()
-        Q = len(off) - 1
-        self.near_calls.append((Q, float(eps), float(max_offset), int(k), int(min_votes), int(min_score)))
+    def local_align(self, form, d_q, d_off, max_len, k, d_excl, *, eps, max_offset, min_votes, min_score, contain=False):
+        queries = _queries(d_q, d_off)
         ids, offs, keys = self._csr()
         rows = [(int(ids[c]), keys[offs[c]:offs[c + 1]].tolist()) for c in range(len(ids))]
-        queries = [q_all[off[i]:off[i + 1]].tolist() for i in range(Q)]
         excl = None if d_excl is None else [int(e) for e in d_excl]
-        block = atr.topk_ref(rows, queries, eps, max_offset, k, min_votes, min_score, excl, max_query_len=max_len)
+        if form == FORM_BOUNDED:
+            self.near_calls.append((len(queries), float(eps), float(max_offset), int(k), int(min_votes), int(min_score)))
+            block = atr.topk_ref(rows, queries, eps, max_offset, k, min_votes, min_score, excl, max_query_len=max_len)
+        else:
+            max_offset = awr.MAX_B * float(eps) if max_offset is None else float(max_offset)
+            self.wide_calls.append((len(queries), float(eps), max_offset, int(k), int(min_votes), int(min_score),
+                                    bool(contain)))
+            block = awr.topk_wide_ref(rows, queries, eps, max_offset, k, min_votes, min_score, contain, excl,
+                                      max_query_len=max_len)
         return torch.from_numpy(block.astype(np.int32))
 
-    def align_topk_merge(self, gathered, k, d_q, d_off):
-        q_all, off = d_q.numpy(), d_off.numpy()
-        queries = [q_all[off[i]:off[i + 1]].tolist() for i in range(len(off) - 1)]
-        rows, totals = asr.merge_ref(gathered.numpy(), queries)
+    def align_merge(self, form, gathered, k, d_q, d_off, **flags):
+        ref = asr.merge_ref if form == FORM_BOUNDED else wsr.merge_ref
+        rows, totals = ref(gathered.numpy(), _queries(d_q, d_off), *(flags[n] for n in form.flags))
         return torch.from_numpy(rows.astype(np.int32)), torch.from_numpy(totals.astype(np.int32))
 
 
 def near_rank_parts(rank, world, group, a):
-    """service.py `--parts tests.near_fakes:near_rank_parts`: fakes.cpu_rank_parts with the alignment stand-ins, and
-    the launcher's --near-* switches handed to the driver as service._hip_parts does."""
+    """service.py `--parts tests.near_fakes:near_rank_parts`: fakes.cpu_rank_parts with the alignment stand-ins of both
+    forms, and the launcher's --near-* switches handed to the driver as service._hip_parts does."""
     from tvidz_amd import service, sharded
     shard = OracleCorpus()
     matcher = sharded.ShardedMatcher(NearBackend(live=shard), k=a.k, cap=max(a.cap, a.k), group=group)

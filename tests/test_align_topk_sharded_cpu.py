@@ -81,10 +81,10 @@ def _matcher_worker(rank, world, port, out):
             dist.all_gather_object(everyone, (got_rows.tolist(), got_totals.tolist()))
             assert all(e == everyone[0] for e in everyone)                       # identical on every rank
         assert exp_totals[-1] == atr.REFUSED and _expected(rows, queries, 5)[1][0] > 5
-        # a backend without the two methods is refused by name
+        # a backend without the form is refused by name
         plain = sharded.ShardedMatcher(OracleBackend(*tc.rows_to_csr(rows[rank::world])), k=4, cap=64)
-        assert plain.supports_align_topk is False
-        with pytest.raises(RuntimeError, match="local_align_topk"):
+        assert plain.supports_align_topk is False and plain.align_forms == ()
+        with pytest.raises(RuntimeError, match=f"OracleBackend has no {tc.FORM_BOUNDED.stem}"):
             plain.align_topk(d_q, d_off, 45, eps=EPS, max_offset=MAX_OFFSET, k=4)
         out.put((rank, "ok"))
     except Exception as e:  # pragma: no cover
@@ -127,8 +127,8 @@ def _rank_worker(rank, world, port, out):
         # (2) one tick's worth of asks of every kind, pending at once on every rank: two near asks with one eps, one
         #     with another, a top-k ask and an exact ask - each answered as it is alone
         qa, qb = np.asarray(queries[rank % 2]), np.asarray(queries[2])
-        near1 = service.check_near_params(EPS, MAX_OFFSET, 4, 1, 0)
-        near2 = service.check_near_params(2 * EPS, MAX_OFFSET, 4, 1, 0)
+        near1 = service.check_near(tc.FORM_BOUNDED, EPS, MAX_OFFSET, 4, 1, 0)
+        near2 = service.check_near(tc.FORM_BOUNDED, 2 * EPS, MAX_OFFSET, 4, 1, 0)
         dup = np.asarray(rows[1][1])
         asks = [(qa, 0, -1, service.ASK_NEAR, 0.0, near1), (dup, 2, -1, service.ASK_TOPK, 0.0, None),
                 (qb, 0, rows[4][0], service.ASK_NEAR, 0.0, near1), (dup, 2, -1, service.ASK_EXACT, 0.0, None),
@@ -183,8 +183,8 @@ def test_rank_corpus_answers_near_topk_and_exact_asks_of_one_tick(world):
 def test_one_tick_calls_the_matcher_in_sorted_order():
     """World size 1: one tick that holds an exact ask, a top-k ask, a tolerant top-k ask and two near asks with
     different parameters, handed over in an order that is NOT the sorted one.  The matcher hears match_topk per
-    (min_match, tolerance) in sorted order - `tolerance` named only where it is non-zero - and then align_topk per
-    (eps, max_offset, k, min_votes, min_score) in sorted order: every rank makes its collective calls in this order."""
+    (min_match, tolerance) in sorted order - `tolerance` named only where it is non-zero - and then align for align_topk
+    per (eps, max_offset, k, min_votes, min_score) in sorted order: every rank makes its collective calls in this order."""
     from tests.tol_fakes import TolBackend, TolCorpus
 
     class Backend(NearBackend, TolBackend):
@@ -197,10 +197,10 @@ def test_one_tick_calls_the_matcher_in_sorted_order():
             calls.append(("match_topk", int(min_match), dict(kw)))
             return super().match_topk(d_q, d_off, max_len, min_match, d_excl, **kw)
 
-        def align_topk(self, d_q, d_off, max_len, *, eps, max_offset, k, min_votes=1, min_score=0, d_exclude_ids=None):
-            calls.append(("align_topk", eps, max_offset, k, min_votes, min_score))
-            return super().align_topk(d_q, d_off, max_len, eps=eps, max_offset=max_offset, k=k, min_votes=min_votes,
-                                      min_score=min_score, d_exclude_ids=d_exclude_ids)
+        def align(self, form, d_q, d_off, max_len, *, eps, max_offset, k, min_votes, min_score, d_exclude_ids=None):
+            calls.append((form.stem, eps, max_offset, k, min_votes, min_score))
+            return super().align(form, d_q, d_off, max_len, eps=eps, max_offset=max_offset, k=k, min_votes=min_votes,
+                                 min_score=min_score, d_exclude_ids=d_exclude_ids)
 
     rows, queries = _small_table()
     shard = TolCorpus()
@@ -208,8 +208,8 @@ def test_one_tick_calls_the_matcher_in_sorted_order():
     try:
         rc.upload(rows)
         dup, q = np.asarray(rows[1][1]), np.asarray(queries[0])
-        near1 = service.check_near_params(EPS, MAX_OFFSET, 4, 1, 0)
-        near2 = service.check_near_params(2 * EPS, MAX_OFFSET, 4, 1, 0)
+        near1 = service.check_near(tc.FORM_BOUNDED, EPS, MAX_OFFSET, 4, 1, 0)
+        near2 = service.check_near(tc.FORM_BOUNDED, 2 * EPS, MAX_OFFSET, 4, 1, 0)
         asks = [(dup, 2, -1, service.ASK_EXACT, 0.0, None), (q, 0, -1, service.ASK_NEAR, 0.0, near2),
                 (dup, 3, -1, service.ASK_TOPK, 0.0, None), (q, 0, -1, service.ASK_NEAR, 0.0, near1),
                 (dup, 2, -1, service.ASK_TOPK, 0.5, None)]

@@ -1,6 +1,6 @@
 """The near-duplicate search at any shift over a sharded table without a GPU.  The reference merge
 (tests/align_wide_shard_ref.py) of per-shard blocks equals the restatement of tvz_align_wide_topk on the WHOLE table,
-for both score kinds; over gloo at world sizes 2 and 3, with the numpy backend of tests/near_wide_fakes.py,
+for both score kinds; over gloo at world sizes 2 and 3, with the numpy backend of tests/near_fakes.py,
 sharded.ShardedMatcher.align_wide_topk is identical on every rank and equal to it, and a service.RankCorpus tick that
 carries wide near asks of both score kinds, a bounded near ask, a top-k ask and an exact ask answers each as it would
 alone; what the library would refuse is refused in the caller; the launcher passes --near-any-offset, --near-score and
@@ -17,7 +17,6 @@ import torch.multiprocessing as mp
 from tests import align_topk_ref as atr, align_wide_ref as awr, align_wide_shard_ref as wsr
 from tests.fakes import OracleCorpus
 from tests.near_fakes import NearBackend, free_port_run
-from tests.near_wide_fakes import WideBackend
 from tvidz_amd import corpus as tc, service, sharded
 
 EPS = wsr.EPS
@@ -97,7 +96,7 @@ def _matcher_worker(rank, world, port, out):
     _init(rank, world, port)
     try:
         rows, queries = _small_table()
-        sm = sharded.ShardedMatcher(WideBackend(*tc.rows_to_csr(rows[rank::world])), k=16, cap=64)
+        sm = sharded.ShardedMatcher(NearBackend(*tc.rows_to_csr(rows[rank::world])), k=16, cap=64)
         assert sm.world == world and sm.supports_align_wide and sm.supports_align_topk
         d_q, d_off = _pack(queries)
         excl = [rows[1][0]] + [-1] * (len(queries) - 1)
@@ -116,9 +115,10 @@ def _matcher_worker(rank, world, port, out):
             assert all(e == everyone[0] for e in everyone)                       # identical on every rank
         assert exp_totals[-1] == atr.REFUSED and np.abs(_expected(rows, queries, 5)[0][0, :, 2]).min() > 2047
         # a backend with the bounded pair only is refused by name
-        plain = sharded.ShardedMatcher(NearBackend(*tc.rows_to_csr(rows[rank::world])), k=4, cap=64)
+        plain = sharded.ShardedMatcher(NearBackend(*tc.rows_to_csr(rows[rank::world]), align_forms=(tc.FORM_BOUNDED,)),
+                                       k=4, cap=64)
         assert plain.supports_align_wide is False and plain.supports_align_topk is True
-        with pytest.raises(RuntimeError, match="local_align_wide_topk"):
+        with pytest.raises(RuntimeError, match=f"NearBackend has no {tc.FORM_WIDE.stem}"):
             plain.align_wide_topk(d_q, d_off, 45, eps=EPS, k=4)
         out.put((rank, "ok"))
     except Exception as e:  # pragma: no cover
@@ -140,7 +140,7 @@ def _rank_worker(rank, world, port, out):
         rows, queries = _small_table()
         shard = OracleCorpus()
         g = dist.new_group(backend="gloo")                            # the tick thread's own group
-        backend = WideBackend(live=shard)
+        backend = NearBackend(live=shard)
         rc = service.RankCorpus(shard, sharded.ShardedMatcher(backend, k=8, cap=64, group=g), group=g, xdev="cpu",
                                 tick_s=0.01)
         assert rc.supports_align_wide
@@ -167,9 +167,9 @@ def _rank_worker(rank, world, port, out):
         # (2) one tick's worth of asks of every kind, pending at once on every rank: wide near asks of both score kinds,
         #     a bounded near ask, a top-k ask and an exact ask - each answered as it is alone
         qa, qb = np.asarray(queries[rank % 2]), np.asarray(queries[1])
-        wide_j = service.check_near_wide_params(EPS, None, 4, 1, 0, False)
-        wide_c = service.check_near_wide_params(EPS, None, 4, 1, 0, True)
-        near = service.check_near_params(EPS, 3.0, 4, 1, 0)
+        wide_j = service.check_near(tc.FORM_WIDE, EPS, None, 4, 1, 0, False)
+        wide_c = service.check_near(tc.FORM_WIDE, EPS, None, 4, 1, 0, True)
+        near = service.check_near(tc.FORM_BOUNDED, EPS, 3.0, 4, 1, 0)
         dup = np.asarray(rows[1][1])
         asks = [(qa, 0, -1, service.ASK_NEAR_WIDE, 0.0, wide_j), (dup, 2, -1, service.ASK_TOPK, 0.0, None),
                 (qb, 0, rows[4][0], service.ASK_NEAR_WIDE, 0.0, wide_c), (dup, 2, -1, service.ASK_EXACT, 0.0, None),
@@ -233,24 +233,23 @@ def test_one_tick_calls_align_wide_topk_after_align_topk_in_sorted_order():
     calls = []
 
     class Recorder(sharded.ShardedMatcher):
-        def align_topk(self, d_q, d_off, max_len, **kw):
-            calls.append(("align_topk", kw["eps"], kw["k"]))
-            return super().align_topk(d_q, d_off, max_len, **kw)
-
-        def align_wide_topk(self, d_q, d_off, max_len, **kw):
-            calls.append(("align_wide_topk", kw["eps"], kw["max_offset"], kw["k"], kw["min_votes"], kw["contain"]))
-            return super().align_wide_topk(d_q, d_off, max_len, **kw)
+        def align(self, form, d_q, d_off, max_len, **kw):
+            if form == tc.FORM_BOUNDED:
+                calls.append((form.stem, kw["eps"], kw["k"]))
+            else:
+                calls.append((form.stem, kw["eps"], kw["max_offset"], kw["k"], kw["min_votes"], kw["contain"]))
+            return super().align(form, d_q, d_off, max_len, **kw)
 
     rows, queries = _small_table()
     shard = OracleCorpus()
-    rc = service.RankCorpus(shard, Recorder(WideBackend(live=shard), k=8, cap=64), xdev="cpu", tick_s=0.01)
+    rc = service.RankCorpus(shard, Recorder(NearBackend(live=shard), k=8, cap=64), xdev="cpu", tick_s=0.01)
     try:
         rc.upload(rows)
         q = np.asarray(queries[0])
-        c2 = service.check_near_wide_params(EPS, None, 4, 2, 0, True)
-        j2 = service.check_near_wide_params(EPS, None, 4, 2, 0, False)
-        j1 = service.check_near_wide_params(EPS, 100.0, 4, 1, 0, False)
-        near = service.check_near_params(EPS, 3.0, 4, 1, 0)
+        c2 = service.check_near(tc.FORM_WIDE, EPS, None, 4, 2, 0, True)
+        j2 = service.check_near(tc.FORM_WIDE, EPS, None, 4, 2, 0, False)
+        j1 = service.check_near(tc.FORM_WIDE, EPS, 100.0, 4, 1, 0, False)
+        near = service.check_near(tc.FORM_BOUNDED, EPS, 3.0, 4, 1, 0)
         assert c2[:5] == j2[:5] and (c2[5], j2[5]) == (tc.ALIGN_CONTAIN, 0)
         asks = [(q, 0, -1, service.ASK_NEAR_WIDE, 0.0, c2), (q, 0, -1, service.ASK_NEAR, 0.0, near),
                 (q, 0, -1, service.ASK_NEAR_WIDE, 0.0, j1), (q, 0, -1, service.ASK_NEAR_WIDE, 0.0, j2),
@@ -269,7 +268,8 @@ def test_a_rank_corpus_whose_matcher_has_no_wide_form_refuses_in_the_caller(tmp_
     from tests.fakes import CutReader, cut_inspector
     from tvidz_amd import db as tdb
     shard = OracleCorpus()
-    rc = service.RankCorpus(shard, sharded.ShardedMatcher(NearBackend(live=shard), k=4, cap=64), xdev="cpu")
+    rc = service.RankCorpus(shard, sharded.ShardedMatcher(NearBackend(live=shard, align_forms=(tc.FORM_BOUNDED,)), k=4, cap=64),
+                            xdev="cpu")
     try:
         assert rc.supports_align_wide is False
         with pytest.raises(RuntimeError, match="no align_wide_topk"):
@@ -281,7 +281,7 @@ def test_a_rank_corpus_whose_matcher_has_no_wide_form_refuses_in_the_caller(tmp_
     # the driver takes near_any_offset over a rank corpus that can, and reports the excerpt of a longer upload whose
     # cuts moved by minutes, which neither the bounded search nor the Jaccard finds
     shard = OracleCorpus()
-    rc = service.RankCorpus(shard, sharded.ShardedMatcher(WideBackend(live=shard), k=4, cap=64), xdev="cpu")
+    rc = service.RankCorpus(shard, sharded.ShardedMatcher(NearBackend(live=shard), k=4, cap=64), xdev="cpu")
     store = tdb.Store(f"sqlite:///{tmp_path}/t.db", corpus=rc, census=False)
     film = [100.0 + 7.0 * i + 0.05 * i * i for i in range(40)]                       # no two gaps alike: one shift aligns
     cuts = {"film.y4m": film, "clip.y4m": [c - 150.0 for c in film[12:32]]}          # 4,500 bins of 1/30 s

@@ -77,6 +77,11 @@ class AlignForm:
     def fn(self, suffix: str = ""):
         return getattr(_lib.load(), "tvz_" + self.stem + suffix)
 
+    @property
+    def rccl(self) -> bool:
+        """Does the library have the form's RCCL call, tvz_<stem>_sharded (Comm.align_sharded)?"""
+        return "tvz_" + self.stem + "_sharded" in _lib.SIGNATURES
+
 
 FORM_BOUNDED = AlignForm("align_topk", 4, False, False, ())
 FORM_WIDE = AlignForm("align_wide_topk", 4, True, False, ("contain",))
@@ -652,7 +657,7 @@ class Comm:
                            out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
         """tvz_align_topk_sharded: the local alignment top-k -> ncclAllGather of the [Q,k+1,4] blocks -> the merge;
         -> (rows int32 [Q,k,4], totals int32 [Q]), identical on every rank."""
-        return self._align_sharded(FORM_BOUNDED, corpus, d_queries, d_q_offsets, max_query_len, k, d_exclude_ids, workspace,
+        return self.align_sharded(FORM_BOUNDED, corpus, d_queries, d_q_offsets, max_query_len, k, d_exclude_ids, workspace,
                                    stream, out, eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score)
 
     def align_wide_topk_sharded(self, corpus: DeviceCorpus, d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
@@ -664,11 +669,11 @@ class Comm:
         """tvz_align_wide_topk_sharded: the local alignment top-k at any shift (`max_offset=None`: the widest) ->
         ncclAllGather of the [Q,k+1,4] blocks -> the wide merge; -> (rows int32 [Q,k,4], totals int32 [Q]), identical
         on every rank."""
-        return self._align_sharded(FORM_WIDE, corpus, d_queries, d_q_offsets, max_query_len, k, d_exclude_ids, workspace,
+        return self.align_sharded(FORM_WIDE, corpus, d_queries, d_q_offsets, max_query_len, k, d_exclude_ids, workspace,
                                    stream, out, eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score,
                                    contain=contain)
 
-    def _align_sharded(self, f: AlignForm, corpus, d_queries, d_q_offsets, max_query_len, k, d_exclude_ids, workspace, stream,
+    def align_sharded(self, f: AlignForm, corpus, d_queries, d_q_offsets, max_query_len, k, d_exclude_ids, workspace, stream,
                        out, **ask):
         """A form's RCCL call: the prelude with the sharded workspace, the merge's outputs, one library call."""
         Q = d_q_offsets.numel() - 1

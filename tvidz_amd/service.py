@@ -25,20 +25,15 @@ Two forms of the same composition:
                  sharded.ShardedMatcher / RcclShardedMatcher.  UNMEASURED ON HARDWARE: no box here
                  has more than one GPU; tests/test_service_cpu.py runs it at world size 2 on gloo.
 
-The opt-in near-duplicate search (`align_topk`, Inspector(near_top_k=K), `--near-top-k K`) has both forms too:
-ShardedCorpus runs tvz_align_topk_shards (every shard in turn + the device merge, one call, one copy back), RankCorpus
-sends ASK_NEAR through the tick to `matcher.align_topk`.  The RCCL form (tvz_align_topk_sharded) has run on hardware
-at world size 1 only; tests/test_align_topk_sharded_cpu.py runs the exchange at world sizes 2 and 3 on gloo.
-
-So has the search at any shift (`align_wide_topk`, Inspector(near_any_offset=True), `--near-any-offset`): ShardedCorpus
-runs tvz_align_wide_topk_shards, RankCorpus sends ASK_NEAR_WIDE through the tick to `matcher.align_wide_topk`.  Its RCCL
-form (tvz_align_wide_topk_sharded) too has run on hardware at world size 1 only;
-tests/test_align_wide_sharded_cpu.py runs the exchange at world sizes 2 and 3 on gloo.
-
-The search for speed-changed copies (`align_rates_topk`, Inspector(near_rates=...)) has the first form only:
-ShardedCorpus runs tvz_align_rates_topk_shards.  RankCorpus has no ask kind for it and the launcher no switch yet.
-The same holds for the search with spans (`align_span_topk`, Inspector(near_spans=True, near_score="local")):
-ShardedCorpus runs tvz_align_span_topk_shards, and nothing else knows it yet.
+The opt-in near-duplicate search (Inspector(near_top_k=K), `--near-top-k K`) is written once per composition, for any
+form of corpus.ALIGN_FORMS: ShardedCorpus._near_shards runs tvz_<stem>_shards (every shard in turn + the device merge,
+one call, one copy back) and serves all four; RankCorpus._near sends an ask of the form's kind (NEAR_FORMS) through the
+tick to `matcher.align(form, ...)`, and has a kind for two: `align_topk` (ASK_NEAR) and the search at any shift,
+`align_wide_topk` (ASK_NEAR_WIDE; Inspector(near_any_offset=True), `--near-any-offset`).  Their RCCL calls
+(tvz_<stem>_sharded) have run on hardware at world size 1 only; tests/test_align_topk_sharded_cpu.py and
+tests/test_align_wide_sharded_cpu.py run the exchange at world sizes 2 and 3 on gloo.  The search for speed-changed
+copies (`align_rates_topk`, Inspector(near_rates=...)) and the one with spans (`align_span_topk`,
+Inspector(near_spans=True, near_score="local")) have no ask kind, no RCCL call and no launcher switch yet.
 """
 from __future__ import annotations
 
@@ -394,6 +389,8 @@ class ShardedCorpus:
 
 ASK_TOPK, ASK_EXACT, ASK_NEAR, ASK_NEAR_WIDE = 0, 1, 2, 3
 ASK_HEADER = 11                # (len, exclude, min_match, kind, tolerance, eps, max_offset, k, min_votes, min_score, flags)
+NEAR_FORMS = {ASK_NEAR: tc.FORM_BOUNDED, ASK_NEAR_WIDE: tc.FORM_WIDE}      # a near ask's kind -> its form of the alignment top-k
+NEAR_KINDS = {form: kind for kind, form in NEAR_FORMS.items()}
 NEAR_MAX_K, NEAR_MAX_BINS, NEAR_SCORE_ONE = tc.ALIGN_TOPK_MAX_K, tc.ALIGN_TOPK_MAX_BINS, tc.ALIGN_SCORE_ONE
 
 
@@ -404,44 +401,36 @@ def check_near_top_k(k) -> int:
     return int(k)
 
 
-def check_near_params(eps, max_offset, k, min_votes, min_score) -> tuple:
-    """What tvz_align_topk refuses, refused on the host with its rules (include/tvz.h): -> the five values as the
-    ask carries them."""
-    eps, max_offset = float(eps), float(max_offset)
+def check_near(form, eps, max_offset, k, min_votes, min_score, contain=False) -> tuple:
+    """What tvz_<stem> of `form` (NEAR_FORMS) refuses, refused on the host with its rules (include/tvz.h): -> the six
+    values as a near ask carries them, the call's flags last (0 for the form without flags).  `max_offset=None` is the
+    widest of a form that has one, tc.ALIGN_WIDE_MAX_B bins of eps on either side of zero; the bounded form takes
+    NEAR_MAX_BINS bins in all."""
+    eps, max_offset = float(eps), None if form.widest and max_offset is None else float(max_offset)
     if not (0.0 < eps <= sys.float_info.max):
         raise ValueError(f"eps must be finite and > 0, got {eps!r}")
+    if max_offset is None:
+        max_offset = tc.ALIGN_WIDE_MAX_B * eps
     if not (0.0 <= max_offset <= sys.float_info.max):
         raise ValueError(f"max_offset must be finite and >= 0, got {max_offset!r}")
-    if not 2 * np.floor(max_offset / eps + 0.5) + 1 <= NEAR_MAX_BINS:
+    side = np.floor(max_offset / eps + 0.5)                   # bins on either side of zero
+    if form.widest:
+        if not side <= tc.ALIGN_WIDE_MAX_B:
+            raise ValueError(f"max_offset / eps = {max_offset / eps:.0f} is more than {tc.ALIGN_WIDE_MAX_B} bins "
+                             "(ALIGN_WIDE_MAX_B)")
+    elif not 2 * side + 1 <= NEAR_MAX_BINS:
         raise ValueError(f"max_offset / eps = {max_offset / eps:.0f} needs more than {NEAR_MAX_BINS} bins")
     for name, v, lo, hi in (("k", k, 1, NEAR_MAX_K), ("min_votes", min_votes, 1, (1 << 31) - 1),
                             ("min_score", min_score, 0, NEAR_SCORE_ONE)):
         if int(v) != v or not lo <= int(v) <= hi:
             raise ValueError(f"{name} must be an integer in {lo}..{hi}, got {v!r}")
-    return eps, max_offset, int(k), int(min_votes), int(min_score)
-
-
-def check_near_wide_params(eps, max_offset, k, min_votes, min_score, contain=False) -> tuple:
-    """check_near_params for tvz_align_wide_topk: `max_offset=None` is the widest, up to tc.ALIGN_WIDE_MAX_B bins on
-    either side; -> the five values and the call's flags, as an ASK_NEAR_WIDE carries them."""
-    eps = float(eps)
-    if not (0.0 < eps <= sys.float_info.max):
-        raise ValueError(f"eps must be finite and > 0, got {eps!r}")
-    max_offset = tc.ALIGN_WIDE_MAX_B * eps if max_offset is None else float(max_offset)
-    if not (0.0 <= max_offset <= sys.float_info.max):
-        raise ValueError(f"max_offset must be finite and >= 0, got {max_offset!r}")
-    if not np.floor(max_offset / eps + 0.5) <= tc.ALIGN_WIDE_MAX_B:
-        raise ValueError(f"max_offset / eps = {max_offset / eps:.0f} is more than {tc.ALIGN_WIDE_MAX_B} bins "
-                         "(ALIGN_WIDE_MAX_B)")
-    # (at a single bin the bounded rule holds too: the other three are the bounded call's)
-    _, _, k, min_votes, min_score = check_near_params(eps, 0.0, k, min_votes, min_score)
-    return eps, max_offset, k, min_votes, min_score, tc.ALIGN_CONTAIN if contain else 0
+    return eps, max_offset, int(k), int(min_votes), int(min_score), tc.ALIGN_CONTAIN if contain and form.flags else 0
 
 
 class _Asks(NamedTuple):
     """The asks of every rank in one tick, un-padded and in the same order on every rank (rank-major): ask `a` is ask
-    `ii[a]` of rank `rr[a]`, `mine` marks this rank's; `near` holds a near ask's five parameters [n, 5], `keys` the
-    gathered, still padded timestamps [world, Qcap, Lcap], `flags` a wide near ask's flags [n]."""
+    `ii[a]` of rank `rr[a]`, `mine` marks this rank's; `near` holds a near ask's six parameters [n, 6] (check_near),
+    `keys` the gathered, still padded timestamps [world, Qcap, Lcap]."""
     rr: np.ndarray
     ii: np.ndarray
     lens: np.ndarray
@@ -452,7 +441,6 @@ class _Asks(NamedTuple):
     near: np.ndarray
     keys: np.ndarray
     mine: np.ndarray
-    flags: np.ndarray
 
 
 class RankCorpus:
@@ -476,15 +464,14 @@ class RankCorpus:
                  prefix: an upload never fails because of k), by queries of more than 4095 timestamps
                  and by min_match outside 1..5.
 
-      ASK_NEAR   the opt-in near-duplicate search (`align_topk`, what Inspector(near_top_k=K) calls): the k best-aligned
-                 rows of a query over ALL shards, through `matcher.align_topk` (local tvz_align_topk block -> one
-                 all-gather -> the merge by the contract's order).  Its five parameters (eps, max_offset, k, min_votes,
-                 min_score) travel in the ask's header; asks that agree in all five share one batched call per tick.
-                 Nothing is sent unless somebody asks: a service without --near-top-k never names it.
-      ASK_NEAR_WIDE  the same search at any shift (`align_wide_topk`, Inspector(near_any_offset=True)), through
-                 `matcher.align_wide_topk`: the header carries the call's flags (the score kind) next to the five
-                 parameters, and asks that agree in all six share one batched call.  Sent only by a service started
-                 with --near-any-offset.
+      ASK_NEAR, ASK_NEAR_WIDE  the opt-in near-duplicate search, one kind per form it has here (NEAR_FORMS: `align_topk`,
+                 what Inspector(near_top_k=K) calls, and `align_wide_topk`, the same at any shift, what
+                 Inspector(near_any_offset=True) calls): the k best-aligned rows of a query over ALL shards, through
+                 `matcher.align(form, ...)` (the local block -> one all-gather -> the merge by the contract's order).
+                 Its six parameters (eps, max_offset, k, min_votes, min_score, and the call's flags: the score kind,
+                 0 for the form without flags) travel in the ask's header; asks of one kind that agree in all six share
+                 one batched call per tick.  Nothing is sent unless somebody asks: a service without --near-top-k
+                 (--near-any-offset) never names it.
 
     `shard`: this rank's DeviceCorpus (or a stand-in with upload/upsert/clear/find_duplicates);
     `matcher.match_topk(d_q, d_off, max_len, min_match, d_excl) -> (merged [Q,k,3], totals [Q])`;
@@ -578,42 +565,43 @@ class RankCorpus:
                    exclude_ids=None, max_query_len=None):
         """DeviceCorpus.align_topk over the shards of all ranks: `queries` = a list of timestamp lists -> (rows int32
         [Q,k,4], totals int32 [Q]) as numpy arrays, in the contract's order (corpus.align_order_key).  Every query is
-        one ASK_NEAR of the next tick.  Everything a rank's library call would refuse is refused HERE, in the caller
-        (ValueError for a bad parameter, RuntimeError for a matcher without align_topk): a matcher that throws on one
-        rank inside a tick would strand the others.  A query of more than max_query_len (at most 4,095) values is
-        answered here too, as the library answers it: all rows padding, total ALIGN_REFUSED - it never travels."""
-        near = check_near_params(eps, max_offset, k, min_votes, min_score)
-        if not (hasattr(self.matcher, "align_topk") and getattr(self.matcher, "supports_align_topk", True)):
-            raise RuntimeError(f"this rank corpus has no near-duplicate search: its matcher "
-                               f"{type(self.matcher).__name__} has no align_topk")
-        return self._near_asks(ASK_NEAR, near, queries, exclude_ids, max_query_len)
+        one ASK_NEAR of the next tick (`_near`)."""
+        return self._near(tc.FORM_BOUNDED, queries, exclude_ids, max_query_len, eps, max_offset, k, min_votes, min_score)
 
     def align_wide_topk(self, queries, *, eps: float, max_offset=None, k: int = 16, min_votes: int = 1,
                         min_score: int = 0, contain: bool = False, exclude_ids=None, max_query_len=None):
         """DeviceCorpus.align_wide_topk over the shards of all ranks - align_topk at any shift (`max_offset=None`: the
         widest), scored by the containment with `contain`; order: corpus.align_wide_order_key.  Every query is one
-        ASK_NEAR_WIDE of the next tick; refused HERE what the library would refuse (ValueError; more than
-        ALIGN_WIDE_MAX_B bins among it), RuntimeError for a matcher without align_wide_topk."""
-        near = check_near_wide_params(eps, max_offset, k, min_votes, min_score, contain)
-        if not (hasattr(self.matcher, "align_wide_topk") and getattr(self.matcher, "supports_align_wide", True)):
-            raise RuntimeError(f"this rank corpus has no near-duplicate search at any shift: its matcher "
-                               f"{type(self.matcher).__name__} has no align_wide_topk")
-        return self._near_asks(ASK_NEAR_WIDE, near, queries, exclude_ids, max_query_len)
+        ASK_NEAR_WIDE of the next tick (`_near`)."""
+        return self._near(tc.FORM_WIDE, queries, exclude_ids, max_query_len, eps, max_offset, k, min_votes, min_score,
+                          contain)
 
     @property
     def supports_align_wide(self) -> bool:
-        return hasattr(self.matcher, "align_wide_topk") and bool(getattr(self.matcher, "supports_align_wide", True))
+        return tc.FORM_WIDE in getattr(self.matcher, "align_forms", ())
+
+    def _near(self, form, queries, exclude_ids, max_query_len, eps, max_offset, k, min_votes, min_score, contain=False):
+        """What the two calls above share, for their `form`.  Everything a rank's library call would refuse is refused
+        HERE, in the caller (check_near's ValueError for a bad parameter, RuntimeError for a matcher without the form):
+        a matcher that throws on one rank inside a tick would strand the others.  A query of more than max_query_len
+        (at most 4,095) values is answered here too, as the library answers it: all rows padding, total ALIGN_REFUSED -
+        it never travels."""
+        near = check_near(form, eps, max_offset, k, min_votes, min_score, contain)
+        if form not in getattr(self.matcher, "align_forms", ()):
+            raise RuntimeError(f"this rank corpus has no near-duplicate search of this form: its matcher "
+                               f"{type(self.matcher).__name__} has no {form.stem}")
+        return self._near_asks(NEAR_KINDS[form], near, queries, exclude_ids, max_query_len)
 
     def _near_asks(self, kind, near, queries, exclude_ids, max_query_len):
-        """The queries of one align_topk / align_wide_topk as asks of `kind` with the checked parameters `near` (k is
-        its third) -> (rows int32 [Q,k,4], totals int32 [Q])."""
+        """The queries of one near-duplicate search as asks of `kind` with the checked parameters `near` (k is its
+        third) -> (rows int32 [Q,k,cols of the kind's form], totals int32 [Q])."""
         queries = [np.ascontiguousarray(np.asarray(q, dtype=np.float64).reshape(-1)) for q in queries]
         limit = MAX_BATCH_LEN if max_query_len is None else min(int(max_query_len), MAX_BATCH_LEN)
         excl = [-1] * len(queries) if exclude_ids is None else [int(e) for e in np.asarray(exclude_ids).reshape(-1)]
         if len(excl) != len(queries):
             raise ValueError(f"exclude_ids must hold {len(queries)} video ids")
         k = near[2]
-        rows = np.zeros((len(queries), k, 4), dtype=np.int32)
+        rows = np.zeros((len(queries), k, NEAR_FORMS[kind].cols), dtype=np.int32)
         rows[:, :, 0] = -1
         totals = np.full(len(queries), -(1 << 31), dtype=np.int64)                 # ALIGN_REFUSED unless answered
         sent = [i for i, q in enumerate(queries) if q.size <= limit]
@@ -702,34 +690,32 @@ class RankCorpus:
 
     def _exchange_and_answer(self, take, allmeta):
         """One busy tick.  The order of the collectives and of the matcher calls is the same on every rank: the asks'
-        exchange, one match_topk per (min_match, tolerance), one align_topk per set of near parameters and one
-        align_wide_topk per set of wide ones, each in sorted order, then the exact asks' two gathers."""
+        exchange, one match_topk per (min_match, tolerance) in sorted order, one align per near kind and set of its
+        parameters in sorted order, then the exact asks' two gathers."""
         asks = self._gather_asks(take, allmeta)
         self._answer_topk(asks, take)
         self._answer_near(asks, take)
-        self._answer_near_wide(asks, take)
         self._answer_exact(asks, take)
 
     def _gather_asks(self, take, allmeta) -> _Asks:
         Qcap, Lcap = int(allmeta[:, 0].max()), max(int(allmeta[:, 1].max()), 1)
         # the asks, padded to the largest rank's block, as ONE float64 block per rank:
         # [Qcap, ASK_HEADER + Lcap] = (len, exclude, min_match, kind, tolerance, and a near ask's eps, max_offset,
-        # k, min_votes, min_score, and a wide one's flags | keys...); small integers are exact in float64, tolerance,
-        # eps and max_offset ARE float64
+        # k, min_votes, min_score, flags | keys...); small integers are exact in float64, tolerance, eps and max_offset
+        # ARE float64
         H = ASK_HEADER
         blk = np.zeros((Qcap, H + Lcap), dtype=np.float64)
         for i, (q, mm, ex, kind, _, tol, near) in enumerate(take):
             blk[i, 0], blk[i, 1], blk[i, 2], blk[i, 3], blk[i, 4] = len(q), ex, mm, kind, tol
             if near is not None:
-                blk[i, 5:5 + len(near)] = near                                     # five values; six with a wide ask's flags
+                blk[i, 5:5 + len(near)] = near                                     # check_near's six values
             blk[i, H:H + len(q)] = q
         g = self._gather(torch.from_numpy(blk).to(self.xdev)).cpu().numpy()       # [world, Qcap, H + Lcap]
         # the global batch, in the same order on every rank: rank-major; rows past a rank's count are padding
         valid = np.arange(Qcap)[None, :] < allmeta[:, 0][:, None]                  # [world, Qcap]
         rr, ii = np.nonzero(valid)
         lens, excl, min_match, kind = (g[rr, ii, c].astype(np.int64) for c in range(4))
-        return _Asks(rr, ii, lens, excl, min_match, kind, g[rr, ii, 4], g[rr, ii, 5:10], g[:, :, H:], rr == self.rank,
-                     g[rr, ii, 10].astype(np.int64))
+        return _Asks(rr, ii, lens, excl, min_match, kind, g[rr, ii, 4], g[rr, ii, 5:H], g[:, :, H:], rr == self.rank)
 
     def _answer_batch(self, asks: _Asks, take, sel, call) -> None:
         """The asks `sel` of the global batch as ONE batched matcher call, `call(d_q, d_off, max_len, d_excl) -> (rows
@@ -767,25 +753,18 @@ class RankCorpus:
                                                                                          **tol_kw))
 
     def _answer_near(self, asks: _Asks, take) -> None:
-        """Near asks: one batched sharded alignment top-k per (eps, max_offset, k, min_votes, min_score): every rank
-        reads the same parameters off the gathered headers, so every rank makes the same calls in the same order."""
-        near = asks.kind == ASK_NEAR
-        for par in sorted(set(map(tuple, asks.near[near].tolist()))):
-            kw = dict(eps=par[0], max_offset=par[1], k=int(par[2]), min_votes=int(par[3]), min_score=int(par[4]))
-            self._answer_batch(asks, take, np.flatnonzero(near & (asks.near == np.asarray(par)).all(axis=1)),
-                               lambda d_q, d_off, max_len, d_ex: self.matcher.align_topk(d_q, d_off, max_len,
-                                                                                         d_exclude_ids=d_ex, **kw))
-
-    def _answer_near_wide(self, asks: _Asks, take) -> None:
-        """Wide near asks: as _answer_near, one batched matcher.align_wide_topk per (the five parameters, flags)."""
-        wide = asks.kind == ASK_NEAR_WIDE
-        for par in sorted(set(map(tuple, np.column_stack([asks.near[wide], asks.flags[wide]]).tolist()))):
-            kw = dict(eps=par[0], max_offset=par[1], k=int(par[2]), min_votes=int(par[3]), min_score=int(par[4]),
-                      contain=bool(int(par[5]) & tc.ALIGN_CONTAIN))
-            sel = np.flatnonzero(wide & (asks.near == np.asarray(par[:5])).all(axis=1) & (asks.flags == int(par[5])))
-            self._answer_batch(asks, take, sel,
-                               lambda d_q, d_off, max_len, d_ex: self.matcher.align_wide_topk(d_q, d_off, max_len,
-                                                                                              d_exclude_ids=d_ex, **kw))
+        """Near asks: per kind in ascending order, one batched `matcher.align` of the kind's form per (eps, max_offset,
+        k, min_votes, min_score, flags) in sorted order: every rank reads the same kinds and parameters off the gathered
+        headers, so every rank makes the same calls in the same order."""
+        for kind, form in sorted(NEAR_FORMS.items()):
+            of_kind = asks.kind == kind
+            for par in sorted(set(map(tuple, asks.near[of_kind].tolist()))):
+                kw = dict(eps=par[0], max_offset=par[1], k=int(par[2]), min_votes=int(par[3]), min_score=int(par[4]))
+                if "contain" in form.flags:
+                    kw["contain"] = bool(int(par[5]) & tc.ALIGN_CONTAIN)
+                self._answer_batch(asks, take, np.flatnonzero(of_kind & (asks.near == np.asarray(par)).all(axis=1)),
+                                   lambda d_q, d_off, max_len, d_ex: self.matcher.align(form, d_q, d_off, max_len,
+                                                                                        d_exclude_ids=d_ex, **kw))
 
     def _answer_exact(self, asks: _Asks, take) -> None:
         """Exact asks: every rank asks its own shard, counts and padded hit lists are all-gathered."""
@@ -1099,7 +1078,7 @@ class RankService:
         match_tol_index = check_tol_index(match_tol_index, match_tolerance)   # likewise before any rank starts
         near = []
         if check_near_top_k(near_top_k):                                 # likewise: K, and what every near ask will carry
-            check_near_params(near_eps, near_max_offset, near_top_k, 1, 0)
+            check_near(tc.FORM_BOUNDED, near_eps, near_max_offset, near_top_k, 1, 0)
             if not (0.0 <= float(near_jaccard) <= 1.0):
                 raise ValueError(f"near_jaccard must be in 0..1, got {near_jaccard!r}")
             near = ["--near-top-k", str(int(near_top_k)), "--near-eps", repr(float(near_eps)),

@@ -64,25 +64,45 @@ class HipBackend:
     def topk_merge(self, gathered, k):
         return tc.topk_merge(gathered, k)
 
-    def local_align_topk(self, d_q, d_off, max_len, eps, max_offset, k, min_votes, min_score, d_excl):
-        """this rank's alignment top-k block (tvz_align_topk): int32 [Q, k+1, 4] on the device"""
-        return self.corpus.align_topk_block(d_q, d_off, max_len, eps=eps, max_offset=max_offset, k=k,
-                                            min_votes=min_votes, min_score=min_score, d_exclude_ids=d_excl)
+    align_forms = (tc.FORM_BOUNDED, tc.FORM_WIDE)     # the forms of the alignment top-k this backend answers
 
-    def align_topk_merge(self, gathered, k, d_q, d_off):
-        return tc.align_topk_merge(gathered, k, d_q, d_off)
+    def local_align(self, form, d_q, d_off, max_len, k, d_excl, **ask):
+        """this rank's alignment top-k block of `form` (tvz_<stem>): int32 [Q, k+1, form.cols] on the device"""
+        return self.corpus._align_block(form, d_q, d_off, max_len, k, d_excl, None, None, None, **ask)
 
-    def local_align_wide_topk(self, d_q, d_off, max_len, eps, max_offset, k, min_votes, min_score, contain, d_excl):
-        """this rank's block of the alignment top-k at any shift (tvz_align_wide_topk): int32 [Q, k+1, 4]"""
-        return self.corpus.align_wide_topk_block(d_q, d_off, max_len, eps=eps, max_offset=max_offset, k=k,
-                                                 min_votes=min_votes, min_score=min_score, contain=contain,
-                                                 d_exclude_ids=d_excl)
-
-    def align_wide_topk_merge(self, gathered, k, d_q, d_off, contain):
-        return tc.align_wide_topk_merge(gathered, k, d_q, d_off, contain=contain)
+    def align_merge(self, form, gathered, k, d_q, d_off, **flags):
+        return tc.form_merge(form, gathered, k, d_q, d_off, **flags)
 
 
-class ShardedMatcher:
+class _AlignForwards:
+    """The near-duplicate search as both matchers offer it on top of their `align(form, ...)` and `align_forms`: the
+    public calls are forwards that name their form, the supports_* flags views of `align_forms`."""
+
+    def align_topk(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, eps: float,
+                   max_offset: float, k: int, min_votes: int = 1, min_score: int = 0,
+                   d_exclude_ids: Optional[torch.Tensor] = None):
+        """`align` for tvz_align_topk: -> (rows int32 [Q,k,4], totals int32 [Q])."""
+        return self.align(tc.FORM_BOUNDED, d_queries, d_q_offsets, max_query_len, k=k, d_exclude_ids=d_exclude_ids,
+                          eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score)
+
+    def align_wide_topk(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, eps: float,
+                        max_offset: Optional[float] = None, k: int, min_votes: int = 1, min_score: int = 0,
+                        contain: bool = False, d_exclude_ids: Optional[torch.Tensor] = None):
+        """`align` for tvz_align_wide_topk: align_topk at any shift (`max_offset=None`: the widest), scored by the
+        containment with `contain`."""
+        return self.align(tc.FORM_WIDE, d_queries, d_q_offsets, max_query_len, k=k, d_exclude_ids=d_exclude_ids,
+                          eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score, contain=contain)
+
+    @property
+    def supports_align_topk(self) -> bool:
+        return tc.FORM_BOUNDED in self.align_forms
+
+    @property
+    def supports_align_wide(self) -> bool:
+        return tc.FORM_WIDE in self.align_forms
+
+
+class ShardedMatcher(_AlignForwards):
     """rank-local shard + ONE all-gather of per-shard top-k (+ hit totals) + identical merge on
     every rank."""
 
@@ -147,40 +167,23 @@ class ShardedMatcher:
         return self.finish(self.submit(d_queries, d_q_offsets, max_query_len, min_match, d_exclude_ids,
                                        tolerance=tolerance))
 
-    def align_topk(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, eps: float,
-                   max_offset: float, k: int, min_votes: int = 1, min_score: int = 0,
-                   d_exclude_ids: Optional[torch.Tensor] = None):
-        """The near-duplicate search over the sharded table: the local alignment top-k block [Q, k+1, 4] -> ONE
-        all-gather -> the merge by the contract's order, identical on every rank: -> (rows int32 [Q,k,4], totals
-        int32 [Q]; corpus.ALIGN_REFUSED for a query some rank refused).  `k` is the call's own, not the matcher's."""
-        for name in ("local_align_topk", "align_topk_merge"):
-            if not hasattr(self.backend, name):
-                raise RuntimeError(f"{type(self.backend).__name__} has no {name}")
-        local = self.backend.local_align_topk(d_queries, d_q_offsets, max_query_len, eps, max_offset, int(k),
-                                              int(min_votes), int(min_score), d_exclude_ids)
-        gathered, _ = self._all_gather_blocks(local, async_op=False)
-        return self.backend.align_topk_merge(gathered, k, d_queries, d_q_offsets)
-
     @property
-    def supports_align_topk(self) -> bool:
-        return hasattr(self.backend, "local_align_topk") and hasattr(self.backend, "align_topk_merge")
+    def align_forms(self) -> tuple:
+        """The forms of the alignment top-k (corpus.ALIGN_FORMS) `align` answers: the backend's."""
+        return tuple(getattr(self.backend, "align_forms", ()))
 
-    def align_wide_topk(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, eps: float,
-                        max_offset: Optional[float] = None, k: int, min_votes: int = 1, min_score: int = 0,
-                        contain: bool = False, d_exclude_ids: Optional[torch.Tensor] = None):
-        """align_topk at any shift (`max_offset=None`: the widest), scored by the containment with `contain`: the local
-        tvz_align_wide_topk block -> ONE all-gather -> the wide merge of the same score kind, identical on every rank."""
-        for name in ("local_align_wide_topk", "align_wide_topk_merge"):
-            if not hasattr(self.backend, name):
-                raise RuntimeError(f"{type(self.backend).__name__} has no {name}")
-        local = self.backend.local_align_wide_topk(d_queries, d_q_offsets, max_query_len, eps, max_offset, int(k),
-                                                   int(min_votes), int(min_score), bool(contain), d_exclude_ids)
+    def align(self, form, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, k: int,
+              d_exclude_ids: Optional[torch.Tensor] = None, **ask):
+        """The near-duplicate search over the sharded table, for `form` and what the call may `ask` of it (eps,
+        max_offset, min_votes, min_score, its flags): the local block [Q, k+1, form.cols] -> ONE all-gather -> the merge
+        by the contract's order and the ask's score kind, identical on every rank: -> (rows int32 [Q,k,form.cols],
+        totals int32 [Q]; corpus.ALIGN_REFUSED for a query some rank refused).  `k` is the call's own, not the
+        matcher's."""
+        if form not in self.align_forms:
+            raise RuntimeError(f"{type(self.backend).__name__} has no {form.stem}")
+        local = self.backend.local_align(form, d_queries, d_q_offsets, max_query_len, int(k), d_exclude_ids, **ask)
         gathered, _ = self._all_gather_blocks(local, async_op=False)
-        return self.backend.align_wide_topk_merge(gathered, k, d_queries, d_q_offsets, bool(contain))
-
-    @property
-    def supports_align_wide(self) -> bool:
-        return hasattr(self.backend, "local_align_wide_topk") and hasattr(self.backend, "align_wide_topk_merge")
+        return self.backend.align_merge(form, gathered, k, d_queries, d_q_offsets, **{n: ask[n] for n in form.flags})
 
 
 def make_comm(device: int, group=None):
@@ -197,7 +200,7 @@ def make_comm(device: int, group=None):
 
 class _Slot:
     """What one of RcclShardedMatcher's side streams owns: its event, submit's workspace and (merged, totals), and
-    align_topk's own pair (its rows are 4 wide and `k` is the call's own)."""
+    align's own pair (its rows are the form's width and `k` is the call's own)."""
     __slots__ = ("stream", "event", "ws", "out", "near_ws", "near_out")
 
     def __init__(self, stream):
@@ -205,7 +208,7 @@ class _Slot:
         self.ws = self.out = self.near_ws = self.near_out = None
 
 
-class RcclShardedMatcher:
+class RcclShardedMatcher(_AlignForwards):
     """The sharded match with the collective BEHIND the C ABI (tvz_match_sharded): local sweep +
     per-shard top-k -> ncclAllGather -> merge are enqueued on one HIP stream by one library call.
     submit() alternates between two side streams with their own workspaces, so the all-gather and
@@ -328,45 +331,34 @@ class RcclShardedMatcher:
         return self.finish(self.submit(d_queries, d_q_offsets, max_query_len, min_match, d_exclude_ids,
                                        tolerance=tolerance))
 
-    supports_align_topk = True
+    align_forms = tuple(f for f in tc.ALIGN_FORMS if f.rccl)
 
-    def align_topk(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, eps: float,
-                   max_offset: float, k: int, min_votes: int = 1, min_score: int = 0,
-                   d_exclude_ids: Optional[torch.Tensor] = None):
-        """The near-duplicate search over the sharded table behind ONE library call (tvz_align_topk_sharded): the local
-        alignment top-k -> ncclAllGather of the [Q, k+1, 4] blocks -> the merge, on the next of the matcher's side
-        streams; the current stream waits for it.  -> (rows int32 [Q,k,4], totals int32 [Q]), this matcher's tensors,
-        overwritten `n_streams` calls later.  Its own workspace (the rows are 4 wide, `k` is the call's own) and no
-        plan: the near-duplicate report is one call per upload, not the tick's stream of batches."""
-        return self._near_call(self.comm.align_topk_sharded, tc.align_topk_sharded_workspace_bytes, d_queries,
-                               d_q_offsets, max_query_len, int(k), eps=eps, max_offset=max_offset, min_votes=min_votes,
-                               min_score=min_score, d_exclude_ids=d_exclude_ids)
+    def align(self, form, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, k: int,
+              d_exclude_ids: Optional[torch.Tensor] = None, **ask):
+        """The near-duplicate search over the sharded table behind ONE library call (tvz_<stem>_sharded), for `form`
+        and what the call may `ask` of it, as ShardedMatcher.align: the local alignment top-k -> ncclAllGather of the
+        [Q, k+1, form.cols] blocks -> the merge, on the next of the matcher's side streams; the current stream waits
+        for it.  -> (rows int32 [Q,k,form.cols], totals int32 [Q]), this matcher's tensors, overwritten `n_streams`
+        calls later.  Its own workspace (`k` is the call's own) and no plan: the near-duplicate report is one call per
+        upload, not the tick's stream of batches."""
+        if form not in self.align_forms:
+            raise RuntimeError(f"{type(self).__name__} has no {form.stem}: the library has no tvz_{form.stem}_sharded")
+        return self._near_call(form, d_queries, d_q_offsets, max_query_len, int(k), d_exclude_ids, **ask)
 
-    supports_align_wide = True
-
-    def align_wide_topk(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, eps: float,
-                        max_offset: Optional[float] = None, k: int, min_votes: int = 1, min_score: int = 0,
-                        contain: bool = False, d_exclude_ids: Optional[torch.Tensor] = None):
-        """align_topk at any shift behind ONE library call (tvz_align_wide_topk_sharded; `max_offset=None`: the widest,
-        `contain`: scored by the containment), with align_topk's streams, workspace and tensors."""
-        return self._near_call(self.comm.align_wide_topk_sharded, tc.align_wide_topk_sharded_workspace_bytes, d_queries,
-                               d_q_offsets, max_query_len, int(k), eps=eps, max_offset=max_offset, min_votes=min_votes,
-                               min_score=min_score, contain=contain, d_exclude_ids=d_exclude_ids)
-
-    def _near_call(self, call, sizer, d_queries, d_q_offsets, max_query_len, k, **kw):
-        """What align_topk and align_wide_topk share: the next side stream, its near workspace (sized by `sizer`) and
-        (rows, totals), the one library call `call`, the current stream's wait for it."""
+    def _near_call(self, form, d_queries, d_q_offsets, max_query_len, k, d_exclude_ids, **ask):
+        """`align` on the next side stream: its near workspace and (rows, totals), the form's one library call, the
+        current stream's wait for it."""
         slot = self._next_slot()
         st = slot.stream
         _, Q = self.corpus._check_queries(d_queries, d_q_offsets)
-        need = sizer(Q, max_query_len, d_queries.numel(), k, self.world)
+        need = tc.form_workspace_bytes(form, Q, max_query_len, d_queries.numel(), k, self.world)
         if slot.near_ws is None or slot.near_ws.numel() < need:
             slot.near_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.dev)
-        if slot.near_out is None or slot.near_out[0].shape[:2] != (Q, k):
-            slot.near_out = tc._topk_out(None, Q, k, 4, self.dev)
+        if slot.near_out is None or slot.near_out[0].shape != (Q, k, form.cols):
+            slot.near_out = tc._topk_out(None, Q, k, form.cols, self.dev)
         st.wait_stream(torch.cuda.current_stream(self.dev))       # the queries are complete; the slot's last answer is read
-        rows, totals = call(self.corpus, d_queries, d_q_offsets, max_query_len, k=k, workspace=slot.near_ws, stream=st,
-                            out=slot.near_out, **kw)
+        rows, totals = self.comm.align_sharded(form, self.corpus, d_queries, d_q_offsets, max_query_len, k, d_exclude_ids,
+                                               slot.near_ws, st, slot.near_out, **ask)
         slot.event.record(st)
         torch.cuda.current_stream(self.dev).wait_event(slot.event)
         return rows, totals
