@@ -695,6 +695,63 @@ int tvz_align_span_topk_shards(tvz_corpus *const *shards, int32_t n_shards, cons
                                int32_t *d_blocks, int32_t *d_topk, int32_t *d_totals, void *d_workspace,
                                size_t workspace_bytes, void *hip_stream);
 
+/* EVERY ALIGNED PART of a named stored video: the refinement behind a search.  tvz_align_span_topk reports a stored
+ * video once, at its single best shift; a re-upload with a part put in or taken out - an inserted ad, a removed
+ * scene, two clips of one film - aligns at TWO shifts, and the search reports the larger half.  Given a batch of
+ * uploads and, per upload, up to k stored video ids - out of a span block the search just wrote, an exact match, or a
+ * pair a user reported - this call aligns each (upload, id) pair in full and reports up to TVZ_ALIGN_MAX_PARTS
+ * disjoint parts.  Q x k row walks, not one per row of the table.  (TVZ_VERSION unchanged: new exports only.)
+ *   ids    : the id of pair (q, j), 0 <= j < k, is d_video_ids[q * query_id_stride + j * id_stride]; the strides are in
+ *            int32 units, so a span block int32[Q][k+1][8] is passed with strides (k+1)*8 and 8 and no copy.  A negative
+ *            id (-1) is no pair.
+ *   refused before the handle is looked at, with tvz_align_span_topk's rules, order and messages: the host rate list
+ *            (1..TVZ_ALIGN_MAX_RATES rates, each finite and > 0), min_votes >= 1, k in 1..64, max_query_len <= 4,095;
+ *            then max_parts outside 1..TVZ_ALIGN_MAX_PARTS (TVZ_ERR_UNSUPPORTED), then eps > 0, max_offset >= 0 and
+ *            B = floor(max_offset/eps + 0.5) <= TVZ_ALIGN_WIDE_MAX_B.
+ *   pair   : s[0 .. m) = the query's non-NaN values sorted ascending, x'_t = s[t] * rho (ONE IEEE multiplication, as in
+ *            tvz_align_rates_topk); the pair (key c, index t) votes into floor((c - x'_t)/eps + 0.5).  The candidate
+ *            rows are the rows of the table, as the alignment sweeps read it, whose video_id is the id; n_rows of them.
+ *   part 0 of a row is tvz_align_span_topk's contract: per rate the best bin of [-B, B] (most votes; ties by the wide
+ *            call's bin order), the rate with the most raw votes (the smaller index on a tie); P_0 = the pairs that
+ *            vote into that bin at that rate, t_first / t_last the smallest / largest index and c_lo / c_hi the
+ *            smallest / largest key over P_0; nq = t_last - t_first + 1, nr = the row's keys in [c_lo, c_hi].
+ *   part i >= 1, at part 0's rate: the ALLOWED pairs have t outside every earlier part's [t_first, t_last] and c
+ *            outside every earlier part's [c_lo, c_hi]; the best bin over them under the same tie rule; P_i, t_first,
+ *            t_last, c_lo, c_hi from the allowed pairs at that bin; nq_i = the indices in [t_first_i, t_last_i] outside
+ *            the earlier index ranges, nr_i = the row's keys in [c_lo_i, c_hi_i] outside the earlier key ranges.
+ *   n_parts: a part is reported iff its raw votes are >= min_votes; the first part that fails ends the list, and so
+ *            does max_parts.
+ *   row    : among the rows that share the id, the one with the most part-0 votes; the earlier row of the table on a
+ *            tie.  row_len and rate_index are that row's even when n_parts = 0.
+ *   Equal query values vote identically, -0.0 and +0.0 give the same difference and infinities never vote: nothing
+ *   depends on how the sort orders equal values.
+ *   d_parts: int32[Q][k][1 + max_parts][6].  Row 0 = (video_id, row_len, rate_index, n_parts, n_rows, m); rows 1.. =
+ *            (bin, votes, t_first, t_last, nq, nr), zeros beyond n_parts.  A negative id: (-1, 0, 0, 0, 0, m).  An id
+ *            the table does not hold: (id, 0, 0, 0, 0, m).  n_parts = INT32_MIN marks a REFUSED pair, (id, 0, 0,
+ *            INT32_MIN, n_rows, m): its query has more than max_query_len values (or more than 4,095; m reads 0 then),
+ *            or more than TVZ_ALIGN_PARTS_MAX_ROWS rows share the id - n_rows still holds the true count.
+ * The call only enqueues: no allocation, no host synchronisation; it takes the handle's shared lock and waits for the
+ * mutations that have returned, as the other batched calls do.
+ * Workspace = tvz_match_tol_workspace_bytes(Q, max_query_len, max(total_query_keys, max_query_len))   (the sorted queries)
+ *           + Q k x 4                                     (rows per pair)
+ *           + Q k x 8 x 8                                 (the candidate rows of a pair)
+ *           + Q k x 8 x (1 + max_parts) x 24              (every candidate's parts)
+ *           + alignment (each part to 256 B).
+ * tvz_align_parts_workspace_bytes answers 0 for a negative size, k < 1 or max_parts outside 1..4.  A workspace below the
+ * fixed parts + one query of max_query_len values: TVZ_ERR_WORKSPACE with the bytes missing.
+ * Cost: one pass over the row table's 16-byte rows (a thread per row), then per (pair, candidate row) the span call's
+ * walk of that one row and one more walk per further part.
+ * NOT YET: no _shards / _sharded form and no service switch; a sharded table asks every shard and keeps, per pair, the
+ * answer with the most part-0 votes (service.ShardedCorpus.align_parts). */
+#define TVZ_ALIGN_MAX_PARTS 4
+#define TVZ_ALIGN_PARTS_MAX_ROWS 8
+size_t tvz_align_parts_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k,
+                                       int32_t max_parts);
+int tvz_align_parts(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q, int32_t max_query_len,
+                    const int32_t *d_video_ids, int64_t id_stride, int64_t query_id_stride, int32_t k, double eps,
+                    double max_offset, const double *h_rates, int32_t n_rates, int32_t min_votes, int32_t max_parts,
+                    int32_t *d_parts, void *d_workspace, size_t workspace_bytes, void *hip_stream);
+
 /* ------------------------------------------------------------------------
  * Opt-in TOLERANT duplicate match.  NOT the reference's verdict: db.py:79,85-91 match exact float64
  * values, and that stays the default everywhere (tolerance 0).  README.md:291 promises "0.1 second

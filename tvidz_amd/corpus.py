@@ -226,6 +226,49 @@ def _span_flags(contain: bool, local: bool) -> int:
     return (ALIGN_CONTAIN if contain else 0) | (ALIGN_LOCAL if local else 0)
 
 
+ALIGN_MAX_PARTS, ALIGN_PARTS_MAX_ROWS = 4, 8     # include/tvz.h TVZ_ALIGN_MAX_PARTS, TVZ_ALIGN_PARTS_MAX_ROWS
+
+
+def align_parts_workspace_bytes(Q: int, max_query_len: int, total_query_keys: int = 0, k: int = 16,
+                                max_parts: int = ALIGN_MAX_PARTS) -> int:
+    """tvz_align_parts_workspace_bytes: the sorted queries and, per (query, id) pair, the count of rows that carry the
+    id, eight candidate rows and every candidate's (1 + max_parts) x 6 words."""
+    return int(_lib.load().tvz_align_parts_workspace_bytes(int(Q), int(max_query_len), int(total_query_keys), int(k),
+                                                           int(max_parts)))
+
+
+def align_parts_ids(video_ids, Q: int, dev) -> torch.Tensor:
+    """The ids of tvz_align_parts as a 2-D int32 tensor [Q, k] on `dev`: a device tensor (any strides) as it is, host
+    lists or arrays copied once."""
+    if torch.is_tensor(video_ids):
+        return video_ids
+    a = np.asarray(video_ids, dtype=np.int32)
+    if Q == 0 and a.ndim != 2:
+        a = np.zeros((0, 1), dtype=np.int32)                # no query: k is of no account
+    if a.ndim != 2 or a.shape[0] != Q:
+        raise RuntimeError(f"video_ids must be [{Q}][k] ids, one list of k per query")
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
+def align_parts_merge(answers: np.ndarray) -> np.ndarray:
+    """The answers of R shards to one align_parts call, on the host: int32 [R, Q, k, 1 + P, 6] -> int32 [Q, k, 1 + P,
+    6].  Per pair, among the shards that hold a row of the id, the answer with the most part-0 votes, the lower shard
+    on a tie (shard 0's where none holds one); n_rows is summed; a pair some shard refused stays refused.  Q x k
+    blocks of at most 120 bytes per shard: host arithmetic behind the one copy back."""
+    R = answers.shape[0]
+    n_rows = answers[:, :, :, 0, 4].astype(np.int64)
+    votes = answers[:, :, :, 1, 1].astype(np.int64)
+    key = np.where(n_rows > 0, votes + 1, 0) * R + (R - 1 - np.arange(R, dtype=np.int64).reshape(R, 1, 1))
+    best = key.argmax(0)[None, :, :, None, None]
+    out = np.take_along_axis(answers, best, 0)[0].copy()
+    out[:, :, 0, 4] = np.minimum(n_rows.sum(0), (1 << 31) - 1)
+    refused = (answers[:, :, :, 0, 3] == ALIGN_REFUSED).any(0)
+    out[refused, 1:] = 0
+    out[refused, 0, 1:3] = 0
+    out[refused, 0, 3] = ALIGN_REFUSED
+    return out
+
+
 def _rates(rates):
     """The rate list of the calls with rates -> (a host double array, its length).  What the list may hold is the
     library's to judge (1..ALIGN_MAX_RATES finite rates > 0)."""
@@ -475,6 +518,47 @@ class DeviceCorpus:
         return self._align_block(FORM_SPAN, d_queries, d_q_offsets, max_query_len, k, d_exclude_ids, out, stream, workspace,
                                  eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score, rates=rates,
                                  contain=contain, local=local)
+
+    def align_parts(self, queries, video_ids, *, eps: float, max_offset: Optional[float] = None,
+                    rates: Sequence[float] = (1.0,), min_votes: int, max_parts: int,
+                    max_query_len: Optional[int] = None):
+        """tvz_align_parts: EVERY aligned part of named stored videos - the refinement behind a search, for the copy
+        with a part put in or taken out, which aligns at two shifts.  `queries` as align_topk takes them; `video_ids`:
+        up to k stored video ids per query as an int32 [Q][k] array (list, numpy, device tensor) or any strided 2-D
+        view of a device int32 tensor - `block[:, :k, 0]` of a span block is passed with its strides, no copy; -1 is
+        no pair.  Every pair is aligned in full at the best of `rates` and up to `max_parts` (1..ALIGN_MAX_PARTS)
+        disjoint parts of at least `min_votes` votes are reported.  -> int32 [Q, k, 1 + max_parts, 6] as a numpy
+        array: row 0 (video_id, row_len, rate_index, n_parts, n_rows, m), then per part (bin, votes, t_first, t_last,
+        nq, nr), zeros beyond n_parts; n_parts = ALIGN_REFUSED marks a refused pair (include/tvz.h)."""
+        dev = torch.device("cuda", self.device)
+        d_q, d_off, Q, max_query_len, _ = align_inputs(queries, None, max_query_len, dev)
+        d_ids = align_parts_ids(video_ids, Q, dev)
+        ws = thread_workspace(self._tls, align_parts_workspace_bytes(Q, max_query_len, d_q.numel(), d_ids.shape[1], max_parts),
+                              dev)
+        return self.align_parts_block(d_q, d_off, max_query_len, d_ids, eps=eps, max_offset=max_offset, rates=rates,
+                                      min_votes=min_votes, max_parts=max_parts, workspace=ws).cpu().numpy()
+
+    def align_parts_block(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int,
+                          d_video_ids: torch.Tensor, *, eps: float, max_offset: Optional[float] = None,
+                          rates: Sequence[float] = (1.0,), min_votes: int, max_parts: int,
+                          out: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
+                          workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """tvz_align_parts, device in / device out: enqueue Q x k pairs -> int32 [Q, k, 1 + max_parts, 6].
+        `d_video_ids`: a 2-D int32 view [Q, k] on this device, of any strides."""
+        Q = d_q_offsets.numel() - 1
+        if d_video_ids.dim() != 2 or d_video_ids.shape[0] != Q or d_video_ids.dtype != torch.int32 \
+                or d_video_ids.device != d_queries.device:
+            raise RuntimeError(f"video_ids must be an int32 [{Q}, k] tensor on {d_queries.device}")
+        k, P = int(d_video_ids.shape[1]), int(max_parts)
+        dev, s, ws, _ = self._prelude(d_queries, d_q_offsets, None, stream, workspace,
+                                      align_parts_workspace_bytes(Q, max_query_len, d_queries.numel(), k, P))
+        out = _out(out, (Q, k, 1 + max(P, 0), 6), dev)
+        _lib.check(self.lib.tvz_align_parts(self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len),
+                                            d_video_ids.data_ptr() if d_video_ids.numel() else None,
+                                            int(d_video_ids.stride(1)), int(d_video_ids.stride(0)), k, float(eps),
+                                            _wide_offset(eps, max_offset), *_rates(rates), int(min_votes), P,
+                                            out.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
+        return out
 
     def _align_host(self, f: AlignForm, queries, k, exclude_ids, max_query_len, **ask):
         """Any form, host in / host out: the inputs, the calling thread's workspace, the block call, ONE copy back,

@@ -1,0 +1,394 @@
+// tvz_align_parts_kernels.h — every aligned part of a NAMED stored video (tvz_align_parts), gfx950
+// wave64.  Included by tvz_match.hip only, behind tvz_align_kernels.h, whose device helpers it uses as they are:
+// al_bin, al_scaled, al_x, al_lo (the vote's expression and the start of a key's run), al_best_bin, aw_width /
+// aw_max_windows / aw_resume_keys / aw_lds_bytes (the window arithmetic and the sweep's LDS layout), AlRates, Row,
+// load_row, wave_lds_fence; the queries are sorted by ts_tol_sort_kernel, as the sweep's are.  Nothing of the sweep
+// is changed: this is a kernel family beside it.
+//
+// The call is a refinement: the search (tvz_align_span_topk), an exact match or a user has named up to k stored video
+// ids per upload, and every (upload, id) pair is aligned in full - Q x k row walks, not one per row of the table.
+//
+// Contract (include/tvz.h): part 0 of a row is the span call's - per rate the best bin of [-B, B] under the wide call's
+// tie rule, the rate with the most votes kept (the smaller index on a tie), and over the pairs (key c, index t of the
+// sorted query) that vote into that bin the extremes t_first / t_last / c_lo / c_hi.  Part i >= 1, at the kept rate:
+// the same over the pairs whose t lies outside every earlier [t_first, t_last] and whose c lies outside every earlier
+// [c_lo, c_hi]; nq / nr count the indices / row keys inside the part's own ranges and outside the earlier ones.  The
+// list ends at the first part with fewer than min_votes votes, or at max_parts.
+//
+// Three launches:
+//   ts_alignp_locate_kernel  grid (row blocks, Q): one pass over the row table, a thread per row, the query's ids in
+//                            LDS; a row whose video_id is the id of pair (q, j) takes a slot of that pair through the
+//                            pair's atomic counter (zeroed by the host's memset) - kApMaxRows slots, and the counter
+//                            keeps counting past them: it is n_rows.
+//   ts_alignp_walk_kernel    grid (k, Q): one block of kAlWaves waves per pair, a wave per candidate slot, then slots
+//                            4..7.  The sorted query lies in LDS once per block and every wave has a histogram
+//                            window, a touched list and resume positions of its own - the sweep's layout
+//                            (aw_lds_bytes) - so the only block barrier stands in front of the row walks.  Part 0 is
+//                            the sweep's window walk over the rates (ap_votes<false>); every later part the same walk
+//                            at the kept rate where a pair votes only if its t and c pass the at most three exclusion
+//                            ranges, which live in registers (ApRanges: constant indices only).  After each part the
+//                            four extremes by one shfl_xor reduction (ap_extremes) and one counting pass each for nr
+//                            and nq.  A slot's result goes to the workspace: int32[1 + max_parts][6].
+//   ts_alignp_pick_kernel    a wave per pair: the slot with the most part-0 votes, the earlier row of the table on a
+//                            tie (the slots fill in no fixed order: the row's index decides), is copied out with
+//                            n_rows and m in its header and zeros behind n_parts; or the refused / absent / no-pair
+//                            form is written.
+// No scratch memory, no block barrier inside a row walk; global memory is written with vector stores only.
+#pragma once
+#include "tvz_align_kernels.h"
+
+namespace {
+
+constexpr int kApMaxParts = 4;                         // TVZ_ALIGN_MAX_PARTS
+constexpr int kApMaxRows = 8;                          // TVZ_ALIGN_PARTS_MAX_ROWS: candidate slots of a pair
+constexpr int kApCols = 6;                             // int32 columns of a row of d_parts
+constexpr int kApLocateBlock = 256;
+constexpr int kApLocateMaxBlocks = 1024;               // per query: a thread then takes a few rows of a large table
+constexpr int kApPickBlock = 256;
+constexpr int kApPickWaves = kApPickBlock / 64;        // pairs per block: a wave each
+
+// int32 words of one slot's (and one pair's) result
+__host__ __device__ inline int ap_words(int32_t max_parts) { return (1 + max_parts) * kApCols; }
+
+// The index and key ranges of the earlier parts, at most kApMaxParts - 1 of them.  Members are only ever named with
+// constant indices (unrolled loops, ap_push's shift), so the struct stays in registers.  An unused entry is the empty
+// range: no t is >= 1 and <= 0, no c is >= +inf and <= -inf.
+struct ApRanges {
+    int tf[kApMaxParts - 1], tl[kApMaxParts - 1];
+    double lo[kApMaxParts - 1], hi[kApMaxParts - 1];
+};
+__device__ __forceinline__ ApRanges ap_no_ranges() {
+    ApRanges ex;
+    const double inf = __longlong_as_double(0x7ff0000000000000ll);
+#pragma unroll
+    for (int i = 0; i < kApMaxParts - 1; ++i) {
+        ex.tf[i] = 1;
+        ex.tl[i] = 0;
+        ex.lo[i] = inf;
+        ex.hi[i] = -inf;
+    }
+    return ex;
+}
+// one more part's ranges; the oldest entry falls out (the caller never has more than kApMaxParts - 1: its last part
+// pushes nothing that is read)
+__device__ __forceinline__ void ap_push(ApRanges &ex, int tf, int tl, double lo, double hi) {
+#pragma unroll
+    for (int i = kApMaxParts - 2; i > 0; --i) {
+        ex.tf[i] = ex.tf[i - 1];
+        ex.tl[i] = ex.tl[i - 1];
+        ex.lo[i] = ex.lo[i - 1];
+        ex.hi[i] = ex.hi[i - 1];
+    }
+    ex.tf[0] = tf;
+    ex.tl[0] = tl;
+    ex.lo[0] = lo;
+    ex.hi[0] = hi;
+}
+__device__ __forceinline__ bool ap_t_free(const ApRanges &ex, int t) {
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < kApMaxParts - 1; ++i) ok = ok && !(t >= ex.tf[i] && t <= ex.tl[i]);
+    return ok;
+}
+__device__ __forceinline__ bool ap_c_free(const ApRanges &ex, double c) {
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < kApMaxParts - 1; ++i) ok = ok && !(c >= ex.lo[i] && c <= ex.hi[i]);
+    return ok;
+}
+
+// a wave's own LDS (the sweep's layout, aw_lds_bytes) and the call's window shape
+struct ApWave {
+    uint32_t *hist;
+    uint16_t *dirty;
+    uint32_t *n_dirty;
+    uint16_t *resume;
+    int width, max_windows, resume_keys;
+};
+
+// The best bin of one row at one rate, as the sweep finds it (al_sweep's window loop: see tvz_align_kernels.h for why
+// the lane that makes a bin's last increment sees its final count, why the windows descend and what the resume
+// positions are) -> count << 33 | (2^33 - 1 - order), reduced over the wave; 0: no pair votes.  kExcl: only the pairs
+// whose t and c lie outside the ranges of `ex` vote - a key inside a range is skipped whole, an index inside one is
+// walked over (the run's end is found by the expression, which does not know the ranges).  c_min / c_max: the row's
+// smallest and largest key.  The histogram is clean on entry and on return.  m >= 1, len >= 1.
+template <bool kExcl>
+__device__ __forceinline__ unsigned long long ap_votes(const int64_t *__restrict__ rk, int len, const double *s, int m, double eps,
+                                                       int32_t B, double c_min, double c_max, double rho, const ApWave &w,
+                                                       const ApRanges &ex, int lane) {
+    const double Bd = (double)B;
+    const double x_min = al_x<true>(s, 0, rho), x_max = al_x<true>(s, m - 1, rho);     // the products stay sorted
+    // the row's offset range [bin(c_min, x_max), bin(c_max, x_min)], clipped to [-B, B]; a NaN end clips to the bound
+    const double d_lo = al_bin(c_min, x_max, eps), d_hi = al_bin(c_max, x_min, eps);
+    const double r_lo = d_lo >= -Bd ? d_lo : -Bd, r_hi = d_hi <= Bd ? d_hi : Bd;
+    int w0 = 0, w1 = -1;
+    if (r_lo <= r_hi) {                                                   // -B <= r_lo <= r_hi <= B: both finite
+        w0 = ((int)r_lo + B) / w.width;
+        w1 = ((int)r_hi + B) / w.width;
+    }
+    w0 = __builtin_amdgcn_readfirstlane(w0);
+    w1 = __builtin_amdgcn_readfirstlane(w1);
+    w1 = w1 < w.max_windows - 1 ? w1 : w.max_windows - 1;
+    unsigned long long best = 0;
+    for (int wi = w1; wi >= w0; --wi) {                                   // wave-uniform
+        const int w_lo = wi * w.width - B;
+        const int w_hi = w_lo + w.width - 1 < B ? w_lo + w.width - 1 : B;
+        const double lo_d = (double)w_lo, hi_d = (double)w_hi;
+        for (int j = lane; j < len; j += 64) {
+            const double c = __longlong_as_double(rk[j]);
+            const bool kept_pos = j < w.resume_keys;
+            int t = kept_pos && wi != w1 ? (int)w.resume[j] : al_lo<true>(s, m, c, eps, hi_d, rho);
+            const bool c_ok = !kExcl || ap_c_free(ex, c);
+            for (; t < m; ++t) {
+                const double d = al_bin(c, al_x<true>(s, t, rho), eps);
+                if (!(d >= lo_d)) break;                                  // behind the window (or NaN there)
+                if (!(d <= hi_d)) continue;                               // (never, behind al_lo: keeps the index in bounds)
+                if (kExcl && !(c_ok && ap_t_free(ex, t))) continue;
+                const int bin = (int)d;                                   // w_lo <= bin <= w_hi
+                const uint32_t slot = (uint32_t)(bin - w_lo);             // 0 .. width - 1
+                const uint32_t cnt = atomicAdd(&w.hist[slot], 1u) + 1u;
+                if (cnt == 1u) w.dirty[atomicAdd(w.n_dirty, 1u)] = (uint16_t)slot;      // at most once per slot: < width
+                const uint32_t order = 2u * (uint32_t)(bin < 0 ? -bin : bin) + (bin > 0 ? 1u : 0u);
+                const unsigned long long key = ((unsigned long long)cnt << 33) | (kAlOrderMask - order);
+                best = key > best ? key : best;
+            }
+            if (kept_pos) w.resume[j] = (uint16_t)t;                      // t <= m <= 4095
+        }
+        wave_lds_fence();
+        const int nd = (int)*w.n_dirty;
+        for (int i = lane; i < nd; i += 64) w.hist[w.dirty[i]] = 0;
+        wave_lds_fence();
+        if (lane == 0) *w.n_dirty = 0;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_xor(best, off);
+        best = o > best ? o : best;
+    }
+    return best;
+}
+
+// Where a part's votes lie: over the allowed pairs that vote into `bin`, the smallest and largest index and key,
+// reduced over the wave (al_span's walk with the ranges of `ex` applied).  The bin has votes: no range comes back empty.
+struct ApExtremes {
+    int t_first, t_last;
+    double c_lo, c_hi;
+};
+__device__ __forceinline__ ApExtremes ap_extremes(const int64_t *__restrict__ rk, int len, const double *s, int m, double eps,
+                                                  int bin, double rho, const ApRanges &ex, int lane) {
+    const double bd = (double)bin;
+    int t_first = m, t_last = -1;
+    double c_lo = __longlong_as_double(0x7ff0000000000000ll), c_hi = -c_lo;
+    for (int j = lane; j < len; j += 64) {
+        const double c = __longlong_as_double(rk[j]);
+        if (!ap_c_free(ex, c)) continue;
+        for (int t = al_lo<true>(s, m, c, eps, bd, rho); t < m; ++t) {
+            const double d = al_bin(c, al_x<true>(s, t, rho), eps);
+            if (!(d >= bd)) break;                                        // behind the bin (or NaN there)
+            if (!(d <= bd) || !ap_t_free(ex, t)) continue;
+            t_first = t < t_first ? t : t_first;
+            t_last = t > t_last ? t : t_last;
+            c_lo = c < c_lo ? c : c_lo;
+            c_hi = c > c_hi ? c : c_hi;
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const int tf = __shfl_xor(t_first, off), tl = __shfl_xor(t_last, off);
+        const double lo = __shfl_xor(c_lo, off), hi = __shfl_xor(c_hi, off);
+        t_first = tf < t_first ? tf : t_first;
+        t_last = tl > t_last ? tl : t_last;
+        c_lo = lo < c_lo ? lo : c_lo;
+        c_hi = hi > c_hi ? hi : c_hi;
+    }
+    return {t_first, t_last, c_lo, c_hi};
+}
+
+// grid = (row blocks, Q), any number of row blocks.  ids: the id of pair (q, j) is ids[q * query_id_stride + j *
+// id_stride]; a negative id names no pair.  counts int32[Q][k], zeroed before the launch: += 1 per matching row, so
+// it ends as n_rows; slots int64[Q][k][kApMaxRows]: the first kApMaxRows matching rows' indices, in no fixed order.
+__global__ __launch_bounds__(kApLocateBlock) void ts_alignp_locate_kernel(
+    const Row *__restrict__ rows, int64_t n_rows, const int32_t *__restrict__ ids, int64_t id_stride, int64_t query_id_stride,
+    int32_t k, int32_t *__restrict__ counts, int64_t *__restrict__ slots) {
+    __shared__ int32_t s_ids[kAlMaxK];
+    const int q = blockIdx.y;
+    if ((int)threadIdx.x < k) s_ids[threadIdx.x] = ids[(int64_t)q * query_id_stride + (int64_t)threadIdx.x * id_stride];
+    __syncthreads();
+    const int64_t stride = (int64_t)gridDim.x * kApLocateBlock;
+    for (int64_t r = (int64_t)blockIdx.x * kApLocateBlock + threadIdx.x; r < n_rows; r += stride) {
+        const int32_t vid = load_row(rows + r).vid;
+        if (vid < 0) continue;
+        for (int j = 0; j < k; ++j) {                                     // the same LDS address in every lane: a broadcast
+            if (s_ids[j] != vid) continue;
+            const int64_t pair = (int64_t)q * k + j;
+            const int32_t n = atomicAdd(&counts[pair], 1);
+            if (n >= 0 && n < kApMaxRows) slots[pair * kApMaxRows + n] = r;
+        }
+    }
+}
+
+// grid = (k, Q), kAlBlock threads; dynamic LDS: aw_lds_bytes(lds_keys, B, width), width = aw_width(B).  Sorted query q:
+// sv[at .. at + m), at = q_offsets[q] - q_offsets[0], m = qm[q] (ts_tol_sort_kernel).  A pair with a refused query, a
+// negative id, no row or more than kApMaxRows rows is left to the pick.  Slot n of pair p writes scratch[(p *
+// kApMaxRows + n) * ap_words(max_parts) ..): the header (video_id, row_len, rate_index, n_parts, 0, m) and per part
+// (bin, votes, t_first, t_last, nq, nr) - part 0's row always (zeros without a vote: the pick orders the slots by its
+// votes), a later part's only when it is reported.  1 <= max_parts <= kApMaxParts, min_votes >= 1, rates.n >= 1.
+__global__ __launch_bounds__(kAlBlock) void ts_alignp_walk_kernel(
+    const Row *__restrict__ rows, const int64_t *__restrict__ keys, const double *__restrict__ sv,
+    const int64_t *__restrict__ q_offsets, const int32_t *__restrict__ qm, int32_t lds_keys, double eps, int32_t B, int32_t width,
+    AlRates rates, int32_t min_votes, int32_t max_parts, const int32_t *__restrict__ ids, int64_t id_stride,
+    int64_t query_id_stride, int32_t k, const int32_t *__restrict__ counts, const int64_t *__restrict__ slots,
+    int32_t *__restrict__ scratch) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int j = blockIdx.x, q = blockIdx.y;
+    const int64_t pair = (int64_t)q * k + j;
+    const int32_t m = qm[q];
+    const int32_t id = ids[(int64_t)q * query_id_stride + (int64_t)j * id_stride];
+    const int32_t n_slots = counts[pair];
+    if (m < 0 || m > lds_keys || id < 0 || n_slots <= 0 || n_slots > kApMaxRows) return;     // block-uniform
+    const int64_t at = q_offsets[q] - q_offsets[0];
+    const int lane = threadIdx.x & 63;
+    const int wv = threadIdx.x >> 6;
+    double *s = reinterpret_cast<double *>(smem);
+    ApWave w;
+    w.width = width;
+    w.max_windows = aw_max_windows(B, width);
+    w.resume_keys = aw_resume_keys(B, width);
+    w.hist = reinterpret_cast<uint32_t *>(smem + (size_t)lds_keys * 8) + (size_t)wv * width;
+    w.dirty = reinterpret_cast<uint16_t *>(smem + (size_t)lds_keys * 8 + (size_t)kAlWaves * width * 4) + (size_t)wv * width;
+    w.n_dirty = reinterpret_cast<uint32_t *>(smem + (size_t)lds_keys * 8 + (size_t)kAlWaves * width * 6) + wv;
+    w.resume = reinterpret_cast<uint16_t *>(smem + (size_t)lds_keys * 8 + (size_t)kAlWaves * ((size_t)width * 6 + 4)) +
+               (size_t)wv * w.resume_keys;
+    for (int e = threadIdx.x; e < m; e += kAlBlock) s[e] = sv[at + e];
+    for (int b = lane; b < width; b += 64) w.hist[b] = 0;
+    if (lane == 0) *w.n_dirty = 0;
+    __syncthreads();
+
+    const int words = ap_words(max_parts);
+    for (int slot = wv; slot < n_slots; slot += kAlWaves) {               // wave-uniform: no block barrier inside
+        const Row row = load_row(rows + slots[pair * kApMaxRows + slot]);
+        const int64_t *rk = keys + row.off;
+        int32_t *o = scratch + (pair * kApMaxRows + slot) * words;
+        double c_min = __longlong_as_double(0x7ff0000000000000ll), c_max = -c_min;
+        for (int i = lane; i < row.len; i += 64) {
+            const double c = __longlong_as_double(rk[i]);
+            c_min = c < c_min ? c : c_min;
+            c_max = c > c_max ? c : c_max;
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            const double lo = __shfl_xor(c_min, off), hi = __shfl_xor(c_max, off);
+            c_min = lo < c_min ? lo : c_min;
+            c_max = hi > c_max ? hi : c_max;
+        }
+        const bool can_vote = m > 0 && row.len > 0;
+        ApRanges ex = ap_no_ranges();
+        unsigned long long best = 0;                                      // part 0: the kept rate's
+        uint32_t best_rate = 0;
+        if (can_vote) {
+            for (int ri = 0; ri < rates.n; ++ri) {                        // wave-uniform
+                const unsigned long long rbest = ap_votes<false>(rk, row.len, s, m, eps, B, c_min, c_max, rates.r[ri], w, ex, lane);
+                if ((rbest >> 33) > (best >> 33)) {                       // strictly more votes: a tie keeps the smaller index
+                    best = rbest;
+                    best_rate = (uint32_t)ri;
+                }
+            }
+        }
+        const double rho = rates.r[best_rate];
+        int32_t n_parts = 0;
+        for (int p = 0; p < max_parts; ++p) {                             // wave-uniform
+            if (p > 0) best = ap_votes<true>(rk, row.len, s, m, eps, B, c_min, c_max, rho, w, ex, lane);
+            const int32_t votes = (int32_t)(best >> 33);
+            if (votes < min_votes && p > 0) break;
+            int32_t part[kApCols] = {0, 0, 0, 0, 0, 0};
+            if (votes > 0) {
+                const int bin = al_best_bin(best);
+                const ApExtremes x = ap_extremes(rk, row.len, s, m, eps, bin, rho, ex, lane);
+                int32_t nq = 0, nr = 0;
+                for (int t = x.t_first + lane; t <= x.t_last; t += 64) nq += ap_t_free(ex, t) ? 1 : 0;
+                for (int i = lane; i < row.len; i += 64) {
+                    const double c = __longlong_as_double(rk[i]);
+                    nr += c >= x.c_lo && c <= x.c_hi && ap_c_free(ex, c) ? 1 : 0;
+                }
+                for (int off = 32; off > 0; off >>= 1) {
+                    nq += __shfl_xor(nq, off);
+                    nr += __shfl_xor(nr, off);
+                }
+                part[0] = bin;
+                part[1] = votes;
+                part[2] = x.t_first;
+                part[3] = x.t_last;
+                part[4] = nq;
+                part[5] = nr;
+                ap_push(ex, x.t_first, x.t_last, x.c_lo, x.c_hi);
+            }
+            if (lane == 0) {
+#pragma unroll
+                for (int i = 0; i < kApCols; ++i) o[(1 + p) * kApCols + i] = part[i];
+            }
+            if (votes < min_votes) break;                                 // part 0 below the bar: written, not reported
+            n_parts = p + 1;
+        }
+        if (lane == 0) {
+            o[0] = row.vid;
+            o[1] = row.len;
+            o[2] = (int32_t)best_rate;
+            o[3] = n_parts;
+            o[4] = 0;
+            o[5] = m;
+        }
+    }
+}
+
+// grid = ceil(Q * k / kApPickWaves), a wave per pair -> d_parts int32[Q][k][1 + max_parts][6].  Row 0 is (video_id,
+// row_len, rate_index, n_parts, n_rows, m), the part rows follow, zeros behind n_parts.  A negative id: (-1, 0, 0, 0,
+// 0, m).  No row of that id: (id, 0, 0, 0, 0, m).  Refused - a query the preparation refused (m reads 0 then), or
+// more than kApMaxRows rows of the id -: (id, 0, 0, INT32_MIN, n_rows, m).
+__global__ __launch_bounds__(kApPickBlock) void ts_alignp_pick_kernel(
+    const int32_t *__restrict__ ids, int64_t id_stride, int64_t query_id_stride, int32_t Q, int32_t k, int32_t max_parts,
+    const int32_t *__restrict__ qm, int32_t lds_keys, const int32_t *__restrict__ counts, const int64_t *__restrict__ slots,
+    const int32_t *__restrict__ scratch, int32_t *__restrict__ d_parts) {
+    const int lane = threadIdx.x & 63;
+    const int64_t pair = (int64_t)blockIdx.x * kApPickWaves + (threadIdx.x >> 6);
+    if (pair >= (int64_t)Q * k) return;                                   // wave-uniform
+    const int q = (int)(pair / k), j = (int)(pair % k);
+    const int words = ap_words(max_parts);                                // <= 30: a lane per word
+    const int32_t id = ids[(int64_t)q * query_id_stride + (int64_t)j * id_stride];
+    const int32_t qmv = qm[q];
+    const bool bad_query = qmv < 0 || qmv > lds_keys;
+    const int32_t m = bad_query ? 0 : qmv;
+    const int32_t n_rows = id < 0 ? 0 : counts[pair];
+    int32_t *out = d_parts + pair * words;
+    if (id < 0 || bad_query || n_rows <= 0 || n_rows > kApMaxRows) {
+        const bool refused = id >= 0 && (bad_query || n_rows > kApMaxRows);
+        int32_t v = 0;
+        v = lane == 0 ? (id < 0 ? -1 : id) : v;
+        v = lane == 3 && refused ? INT32_MIN : v;
+        v = lane == 4 ? n_rows : v;
+        v = lane == 5 ? m : v;
+        if (lane < words) out[lane] = v;
+        return;
+    }
+    // the winner: most part-0 votes, then the earlier row of the table; lanes without a slot lose to every slot
+    const bool has = lane < n_rows;
+    int32_t votes = has ? scratch[(pair * kApMaxRows + lane) * words + kApCols + 1] : -1;
+    int64_t row = has ? slots[pair * kApMaxRows + lane] : INT64_MAX;
+    int slot = lane;
+    for (int off = 32; off > 0; off >>= 1) {
+        const int32_t ov = __shfl_xor(votes, off);
+        const int64_t orow = __shfl_xor(row, off);
+        const int os = __shfl_xor(slot, off);
+        const bool take = ov > votes || (ov == votes && orow < row);
+        votes = take ? ov : votes;
+        row = take ? orow : row;
+        slot = take ? os : slot;
+    }
+    const int32_t *src = scratch + (pair * kApMaxRows + slot) * words;
+    const int32_t n_parts = src[3];
+    if (lane < words) {
+        int32_t v = src[lane];
+        v = lane == 4 ? n_rows : v;
+        v = lane == 5 ? m : v;
+        v = lane >= kApCols && lane / kApCols - 1 >= n_parts ? 0 : v;
+        out[lane] = v;
+    }
+}
+
+}  // namespace

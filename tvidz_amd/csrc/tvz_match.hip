@@ -27,6 +27,7 @@
 #include "tvz_tol_kernels.h"
 #include "tvz_tol_index_kernels.h"
 #include "tvz_align_kernels.h"
+#include "tvz_align_parts_kernels.h"
 #include "tvz_handle.h"
 #include "tvz_index_build.h"
 
@@ -2322,6 +2323,87 @@ size_t align_sizing(AlignForm form, int32_t Q, int32_t max_query_len, int64_t to
     return align_topk_ws_bytes(kAlignForms[form], Q, std::max<int64_t>(keys, max_query_len), k, n_blocks);
 }
 
+// ---- every aligned part of a named stored video (tvz_align_parts; tvz_align_parts_kernels.h) ----------------------
+// Workspace in front of the sorted queries (TolWs, which takes the rest): per pair the count of rows that carry its id,
+// the candidate slots' row indices and every slot's result.
+struct AlignPartsWs {
+    int32_t *counts = nullptr;             // [Q][k]
+    int64_t *slots = nullptr;              // [Q][k][kApMaxRows]
+    int32_t *scratch = nullptr;            // [Q][k][kApMaxRows][1 + max_parts][6]
+};
+
+AlignPartsWs align_parts_ws_layout(Carver &cv, int32_t Q, int32_t k, int32_t max_parts) {
+    AlignPartsWs w;
+    const size_t pairs = (size_t)Q * (size_t)k;
+    w.counts = cv.take<int32_t>(pairs);
+    w.slots = cv.take<int64_t>(pairs * kApMaxRows);
+    w.scratch = cv.take<int32_t>(pairs * kApMaxRows * (size_t)ap_words(max_parts));
+    return w;
+}
+
+size_t align_parts_ws_bytes(int32_t Q, int64_t keys, int32_t k, int32_t max_parts) {
+    Carver cv(nullptr);
+    align_parts_ws_layout(cv, Q, k, max_parts);
+    return cv.fixed() + tol_ws_bytes(Q, keys);
+}
+
+// The call in messages and limits: no entry of kAlignForms (it keeps no hit and has no block), only what the shared
+// checks read of one - the name, the sizing function and the bins' limit.
+constexpr AlignTopkForm kAlignPartsForm = {kApCols, 0, true, true, "alignment parts", "tvz_align_parts_workspace_bytes", nullptr,
+                                           2 * kAwMaxB + 1, "TVZ_ALIGN_WIDE_MAX_B", 0u, 0u, 0, nullptr, nullptr, nullptr};
+
+// sort -> locate the ids' rows -> walk every (pair, candidate row) -> pick per pair.  Everything that needs neither
+// the handle nor the device is refused first, in the span call's order: the rate list, min_votes, k, the query limit;
+// then max_parts and the bins.
+int align_parts_impl(tvz_corpus *c, const Batch &b, const int32_t *d_video_ids, int64_t id_stride, int64_t query_id_stride,
+                     int32_t k, double eps, double max_offset, const double *h_rates, int32_t n_rates, int32_t min_votes,
+                     int32_t max_parts, int32_t *d_parts, Workspace ws, void *hip_stream) {
+    const AlignTopkForm &f = kAlignPartsForm;
+    const int32_t Q = b.Q, max_query_len = b.max_query_len;
+    AlRates rates{};
+    if (int rc = check_align_rates(h_rates, n_rates, &rates)) return rc;
+    if (int rc = check_align_limits(f, AlignCall{eps, max_offset, min_votes, 0}, k, max_query_len)) return rc;
+    if (max_parts < 1 || max_parts > kApMaxParts)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "%s: max_parts=%d outside 1..%d (TVZ_ALIGN_MAX_PARTS)", f.what, (int)max_parts,
+                         kApMaxParts);
+    int32_t B = 0;
+    if (int rc = check_align_bins(eps, max_offset, f.max_bins, f.bins_limit, &B)) return rc;
+    if (int rc = check_batch_args(c, b, 0)) return rc;
+    if (Q == 0) return TVZ_OK;
+    Carver cv(ws.p);
+    const AlignPartsWs w = align_parts_ws_layout(cv, Q, k, max_parts);
+    const int32_t lds_keys = std::max(max_query_len, 1);
+    const int32_t width = aw_width(B);
+    const size_t lds = aw_lds_bytes(lds_keys, B, width);
+    auto args_ok = [&]() -> int {
+        TVZ_REQUIRE(d_video_ids != nullptr && d_parts != nullptr, "NULL argument");
+        TVZ_REQUIRE(lds <= (size_t)kLdsPerWorkgroup, "%s walk: %zu B of dynamic LDS exceed a gfx950 workgroup's", f.what, lds);
+        return TVZ_OK;
+    };
+    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+    TolCall t;                                                                // (the sort zeroes counts[0 .. Q) too)
+    if (int rc = tol_prelude(c, b, TolFront{cv, cv.fixed(), w.counts, f.what, f.sizer}, ws.p ? ws.bytes : 0, max_query_len, st,
+                             args_ok, t))
+        return rc;
+    const int64_t n_rows = t.n_rows;
+    TVZ_HIP(hipMemsetAsync(w.counts, 0, (size_t)Q * (size_t)k * sizeof(int32_t), st));
+    if (n_rows) {
+        const unsigned row_blocks = (unsigned)std::min<int64_t>(tvz::ceil_div(n_rows, (int64_t)kApLocateBlock), kApLocateMaxBlocks);
+        hipLaunchKernelGGL(ts_alignp_locate_kernel, dim3(row_blocks, (unsigned)Q), dim3(kApLocateBlock), 0, st, c->rows.p, n_rows,
+                           d_video_ids, id_stride, query_id_stride, k, w.counts, w.slots);
+        TVZ_HIP(hipGetLastError());
+        hipLaunchKernelGGL(ts_alignp_walk_kernel, dim3((unsigned)k, (unsigned)Q), dim3(kAlBlock), lds, st, c->rows.p, c->keys.p,
+                           t.ws.sv, b.d_q_offsets, t.ws.qm, lds_keys, eps, B, width, rates, min_votes, max_parts, d_video_ids,
+                           id_stride, query_id_stride, k, w.counts, w.slots, w.scratch);
+        TVZ_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(ts_alignp_pick_kernel, dim3((unsigned)tvz::ceil_div((int64_t)Q * k, (int64_t)kApPickWaves)),
+                       dim3(kApPickBlock), 0, st, d_video_ids, id_stride, query_id_stride, Q, k, max_parts, t.ws.qm, lds_keys,
+                       w.counts, w.slots, w.scratch, d_parts);
+    TVZ_HIP(hipGetLastError());
+    return record(c, st);
+}
+
 }  // namespace
 
 // used by tvz_comm.hip (same shared object, not exported): a form's call with the sharded forms' blocks
@@ -2646,6 +2728,23 @@ TVZ_EXPORT int tvz_align_span_topk_shards(tvz_corpus *const *shards, int32_t n_s
                                   align_batch(d_queries, d_q_offsets, Q, max_query_len, d_exclude_ids),
                                   AlignAsk{{eps, max_offset, min_votes, min_score}, h_rates, n_rates, flags, k}, d_blocks,
                                   d_topk, d_totals, Workspace{d_workspace, workspace_bytes}, hip_stream));
+}
+
+TVZ_EXPORT size_t tvz_align_parts_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k,
+                                                  int32_t max_parts) {
+    if (Q < 0 || max_query_len < 0 || total_query_keys < 0 || k < 1 || max_parts < 1 || max_parts > kApMaxParts) return 0;
+    const int64_t keys = total_query_keys > 0 ? total_query_keys : (int64_t)Q * max_query_len;
+    return align_parts_ws_bytes(Q, std::max<int64_t>(keys, max_query_len), k, max_parts);
+}
+
+TVZ_EXPORT int tvz_align_parts(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
+                               int32_t max_query_len, const int32_t *d_video_ids, int64_t id_stride, int64_t query_id_stride,
+                               int32_t k, double eps, double max_offset, const double *h_rates, int32_t n_rates,
+                               int32_t min_votes, int32_t max_parts, int32_t *d_parts, void *d_workspace,
+                               size_t workspace_bytes, void *hip_stream) {
+    TVZ_GUARDED(align_parts_impl(c, align_batch(d_queries, d_q_offsets, Q, max_query_len, nullptr), d_video_ids, id_stride,
+                                 query_id_stride, k, eps, max_offset, h_rates, n_rates, min_votes, max_parts, d_parts,
+                                 Workspace{d_workspace, workspace_bytes}, hip_stream));
 }
 
 // (unlike its bounded twin this one sizes n_ranks < 0 as one rank instead of answering 0: callers' buffers were sized by

@@ -86,7 +86,7 @@ class Inspector:
                  near_jaccard: float = 0.8, slot_bytes: int = 64 << 20, n_slots: Optional[int] = None,
                  profile: bool = False, match_tolerance: float = 0.0, near_top_k: Optional[int] = None,
                  near_any_offset: bool = False, near_score: str = "jaccard", near_min_votes: int = 1,
-                 near_rates=None, near_spans: bool = False):
+                 near_rates=None, near_spans: bool = False, near_parts: Optional[int] = None):
         self.store = store
         # opt-in: the near-duplicate report from the K best-aligned rows the device keeps (tvz_align_topk) instead of
         # one row per corpus row walked here.  None: the walk, exactly as before.  Refused here where the store's
@@ -147,6 +147,20 @@ class Inspector:
             if not hasattr(getattr(store, "corpus", None), "align_span_topk"):
                 raise RuntimeError(f"{what}: the store's corpus "
                                    f"({type(getattr(store, 'corpus', None)).__name__}) has no align_span_topk; "
+                                   "use a DeviceCorpus or a service.ShardedCorpus")
+        # opt-in: EVERY aligned part of each reported video (tvz_align_parts) - the copy with an ad put in or a scene
+        # taken out aligns at two shifts, and the search reports the larger half.  After the search one call aligns the
+        # upload with every reported id in full: each entry gains "parts", up to near_parts of them, each with its own
+        # shift and spans, and "parts_score", the local score over all parts together.  None: nothing changes.
+        self.near_parts = None if near_parts is None else int(near_parts)
+        if self.near_parts is not None:
+            if not 2 <= self.near_parts <= 4:
+                raise ValueError(f"near_parts must be None or 2..4, got {near_parts!r}")
+            if not self.near_any_offset or self.near_top_k is None or near_score != "local":
+                raise ValueError(f"near_parts={self.near_parts} needs near_top_k, near_any_offset=True and near_score='local'")
+            if not hasattr(getattr(store, "corpus", None), "align_parts"):
+                raise RuntimeError(f"near_parts={self.near_parts}: the store's corpus "
+                                   f"({type(getattr(store, 'corpus', None)).__name__}) has no align_parts; "
                                    "use a DeviceCorpus or a service.ShardedCorpus")
         # opt-in, never the default: duplicates by the TOLERANT count (include/tvz.h tvz_find_duplicates_tol)
         # instead of the reference's exact float64 equality; the verdict, the truncation at kth and the stored
@@ -426,8 +440,33 @@ class Inspector:
                     first, last = float(cuts[int(more[1])]), float(cuts[int(more[2])])
                     out[-1]["upload_span"] = [first, last]
                     out[-1]["stored_span"] = [rate * first + out[-1]["shift_seconds"], rate * last + out[-1]["shift_seconds"]]
+        if self.near_parts is not None and out:
+            self._near_parts(out, scene_timestamps)
         by = self.near_score if self.near_score in ("containment", "local") else "jaccard"
         return sorted(out, key=lambda d: (-d[by], d["video_id"]))
+
+    def _near_parts(self, out, scene_timestamps) -> None:
+        """near_parts: ONE align_parts call for the reported ids; every entry whose pair was not refused gains "parts" -
+        per part the shift, the spans (as "upload_span" / "stored_span" are made) and the raw votes - and
+        "parts_score": with v = the sum of min(votes_i, nq_i, nr_i), v / (sum nq_i + sum nr_i - v)."""
+        rates = self.near_rates or (1.0,)
+        blocks = self.store.corpus.align_parts([scene_timestamps], [[d["video_id"] for d in out]], eps=self.near_eps,
+                                               rates=rates, min_votes=self.near_min_votes, max_parts=self.near_parts)[0]
+        cuts = np.sort(np.asarray(scene_timestamps, dtype=np.float64))
+        cuts = cuts[~np.isnan(cuts)]
+        for d, block in zip(out, blocks):
+            n = int(block[0][3])
+            if n < 0:                                                          # a refused pair: the entry stays as it is
+                continue
+            rate, parts, v, u = rates[int(block[0][2])], [], 0, 0
+            for best_bin, votes, t_first, t_last, nq, nr in (tuple(int(x) for x in p) for p in block[1:1 + n]):
+                shift, first, last = float(best_bin) * self.near_eps, float(cuts[t_first]), float(cuts[t_last])
+                parts.append({"shift_seconds": shift, "upload_span": [first, last],
+                              "stored_span": [rate * first + shift, rate * last + shift], "votes": votes})
+                v += min(votes, nq, nr)
+                u += nq + nr
+            d["parts"] = parts
+            d["parts_score"] = round(v / float(u - v), 4) if u > v else 0.0
 
     def _near_rows(self, video_id: int, scene_timestamps):
         """(video_id, row_len, best_bin, votes[, ...]) of the rows _near filters: every row of the table (near_top_k None), or

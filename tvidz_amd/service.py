@@ -33,7 +33,9 @@ tick to `matcher.align(form, ...)`, and has a kind for two: `align_topk` (ASK_NE
 (tvz_<stem>_sharded) have run on hardware at world size 1 only; tests/test_align_topk_sharded_cpu.py and
 tests/test_align_wide_sharded_cpu.py run the exchange at world sizes 2 and 3 on gloo.  The search for speed-changed
 copies (`align_rates_topk`, Inspector(near_rates=...)) and the one with spans (`align_span_topk`,
-Inspector(near_spans=True, near_score="local")) have no ask kind, no RCCL call and no launcher switch yet.
+Inspector(near_spans=True, near_score="local")) have no ask kind, no RCCL call and no launcher switch yet.  Neither has
+the refinement behind the search, every aligned part of the reported videos (`align_parts`, Inspector(near_parts=P)):
+ShardedCorpus.align_parts asks every shard of the one process and keeps the best answer per pair; RankCorpus has none.
 """
 from __future__ import annotations
 
@@ -309,6 +311,24 @@ class ShardedCorpus:
         16 shards are grouped and re-merged by tvz_align_span_topk_merge, as align_topk does."""
         return self._near_shards(tc.FORM_SPAN, queries, k, exclude_ids, max_query_len, eps=eps, max_offset=max_offset,
                                  min_votes=min_votes, min_score=min_score, rates=tuple(rates), contain=contain, local=local)
+
+    def align_parts(self, queries, video_ids, *, eps: float, max_offset=None, rates=(1.0,), min_votes: int,
+                    max_parts: int, max_query_len=None):
+        """DeviceCorpus.align_parts over every shard: each shard is asked for every pair with the calling thread's one
+        workspace, the answers come back in ONE copy, and per pair the one with the most part-0 votes is kept, the
+        lower shard on a tie (corpus.align_parts_merge); n_rows is the shards' sum.  More than ALIGN_PARTS_MAX_ROWS
+        rows of one id refuse the pair only where they lie in ONE shard."""
+        dev = self.dev
+        d_q, d_off, Q, max_query_len, _ = tc.align_inputs(queries, None, max_query_len, dev)
+        d_ids = tc.align_parts_ids(video_ids, Q, dev)
+        ws = tc.thread_workspace(self._near_tls, tc.align_parts_workspace_bytes(Q, max_query_len, d_q.numel(),
+                                                                                d_ids.shape[1], max_parts), dev)
+        with torch.cuda.device(dev):
+            out = torch.empty((self.R, Q, d_ids.shape[1], 1 + int(max_parts), 6), dtype=torch.int32, device=dev)
+            for r, s in enumerate(self.shards):
+                s.align_parts_block(d_q, d_off, max_query_len, d_ids, eps=eps, max_offset=max_offset, rates=tuple(rates),
+                                    min_votes=min_votes, max_parts=max_parts, out=out[r], workspace=ws)
+            return tc.align_parts_merge(out.cpu().numpy())
 
     def _near_shards(self, form, queries, k, exclude_ids, max_query_len, **ask):
         """What the four methods above share, for their `form` (corpus.ALIGN_FORMS) and what they `ask`: the inputs, the
