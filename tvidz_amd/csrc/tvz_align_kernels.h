@@ -2,10 +2,9 @@
 // call (tvz_align_topk, at most kAlignMaxBins bins), the call at any shift (tvz_align_wide_topk, up to kAwMaxB bins on
 // either side of zero), that call with rates (tvz_align_rates_topk) and with the matched span (tvz_align_span_topk),
 // and the merges of the shards' blocks, one per form.  Included by tvz_match.hip only, whose table kAlignForms says
-// what each form is on the host.  From
-// tvz_match_kernels.h: Row, load_row; from tvz_tol_kernels.h: ts_tol_sort_kernel (the batch's queries sorted
-// numerically, NaNs dropped, qm = the non-NaN count) and the sweep's block count (tol_topk_max_blocks); from
-// tvz_wave.h: wave_lds_fence.
+// what each form is on the host.  From tvz_match_kernels.h: Row, load_row, al_bin (the vote's expression); from
+// tvz_tol_kernels.h: ts_tol_sort_kernel (the batch's queries sorted numerically, NaNs dropped, qm = the non-NaN
+// count) and the sweep's block count (tol_topk_max_blocks); from tvz_wave.h: wave_lds_fence.
 //
 // Contract (include/tvz.h): votes and bins are tvz_align's - the pair (row key c, query value x) votes into
 //   d = floor((c - x) / eps + 0.5)      (one IEEE subtraction, one true division)
@@ -105,9 +104,33 @@ __host__ __device__ inline int aw_resume_keys(int32_t B, int width) { return aw_
 inline size_t aw_lds_bytes(int32_t lds_keys, int32_t B, int width) {
     return (size_t)lds_keys * 8 + (size_t)kAlWaves * ((size_t)width * 6 + 4 + (size_t)aw_resume_keys(B, width) * 2);
 }
-
-// d of the contract, verbatim
-__device__ __forceinline__ double al_bin(double c, double x, double eps) { return floor((c - x) / eps + 0.5); }
+// ... and wave wv's part of it, with the call's window shape.  Without kWindowed: the one window, no resume positions
+struct AlWave {
+    uint32_t *hist;
+    uint16_t *dirty;
+    uint32_t *n_dirty;
+    uint16_t *resume;
+    int width, max_windows, resume_keys;
+};
+template <bool kWindowed>
+__device__ __forceinline__ AlWave al_wave(unsigned char *smem, int32_t lds_keys, int32_t B, int32_t width, int wv) {
+    unsigned char *waves = smem + (size_t)lds_keys * 8;
+    uint32_t *counts = reinterpret_cast<uint32_t *>(waves + (size_t)kAlWaves * width * 6);      // behind the waves' bins
+    AlWave w{reinterpret_cast<uint32_t *>(waves) + (size_t)wv * width,
+             reinterpret_cast<uint16_t *>(waves + (size_t)kAlWaves * width * 4) + (size_t)wv * width, counts + wv, nullptr,
+             width, 1, 0};
+    if constexpr (kWindowed) {
+        w.max_windows = aw_max_windows(B, width);
+        w.resume_keys = aw_resume_keys(B, width);
+        w.resume = reinterpret_cast<uint16_t *>(counts + kAlWaves) + (size_t)wv * w.resume_keys;
+    }
+    return w;
+}
+// a clean histogram and an empty touched list, which every row walk expects and leaves behind
+__device__ __forceinline__ void al_wave_clear(const AlWave &w, int lane) {
+    for (int b = lane; b < w.width; b += 64) w.hist[b] = 0;
+    if (lane == 0) *w.n_dirty = 0;
+}
 
 // x' = x * rho of the contract: the product is rounded on its own, never fused with al_bin's subtraction
 __device__ __forceinline__ double al_scaled(double x, double rho) {
@@ -390,34 +413,62 @@ template <class Hit> __device__ __forceinline__ void al_write_block(const Hit &k
     }
 }
 
-// ---- the sweep and the selection -------------------------------------------------------------------------------
-// the bin of a lane-wise best (count << 33 | 2^33 - 1 - order)
+// ---- what a wave does with one row, shared with tvz_align_parts_kernels.h ----------------------------------------------
+// the bin of a best (count << 33 | 2^33 - 1 - order)
 __device__ __forceinline__ int al_best_bin(unsigned long long best) {
     const uint32_t order = (uint32_t)(kAlOrderMask - (best & kAlOrderMask));
     const int mag = (int)(order >> 1);
     return (order & 1u) ? mag : -mag;
 }
 
-// The span of a row's best bin (include/tvz.h, tvz_align_span_topk): over the pairs (key c, index t of the sorted
-// query) whose vote - the sweep's own expression at the rate rho - is `bin`, the smallest and the largest t, and nr =
-// the row's keys inside [smallest voting key, largest voting key].  The window loop's walk with the one bin as the
-// window and nothing noted but the four extremes, a wave reduction, then a second lane-strided pass that counts: no
-// LDS beyond the sorted query, no barrier.  The bin has votes (the caller's v >= 1), so both ranges are non-empty.
-struct AlSpan {
-    int t_first, t_last;
-    uint32_t nr;
+// Which pairs (row key c, index t of the sorted query) al_bin_extremes counts: key(c) is asked once per key, index(t)
+// once per pair that votes into the bin.  The span allows every pair, and both tests fold away; the parts walk's is
+// ApOutside.
+struct AlAllPairs {
+    __device__ __forceinline__ bool key(double) const { return true; }
+    __device__ __forceinline__ bool index(int) const { return true; }
 };
-__device__ __forceinline__ AlSpan al_span(const int64_t *__restrict__ rk, int len, const double *s, int m, double eps, int bin,
-                                          double rho, int lane) {
+
+// a row's smallest and largest key, in every lane (+inf and -inf for an empty row)
+struct AlKeyRange {
+    double c_min, c_max;
+};
+__device__ __forceinline__ AlKeyRange al_key_range(const int64_t *__restrict__ rk, int len, int lane) {
+    double c_min = __longlong_as_double(0x7ff0000000000000ll), c_max = -c_min;
+    for (int j = lane; j < len; j += 64) {
+        const double c = __longlong_as_double(rk[j]);
+        c_min = c < c_min ? c : c_min;
+        c_max = c > c_max ? c : c_max;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const double lo = __shfl_xor(c_min, off), hi = __shfl_xor(c_max, off);
+        c_min = lo < c_min ? lo : c_min;
+        c_max = hi > c_max ? hi : c_max;
+    }
+    return {c_min, c_max};
+}
+
+// Where the votes of one bin lie: over the allowed pairs whose vote - the walk's own expression at the rate rho - is
+// `bin`, the smallest and the largest index and key, the same in every lane.  The window loop's walk with the one bin
+// as the window and nothing noted but the four extremes: no LDS beyond the sorted query, no barrier.  The bin has allowed
+// votes (the caller's count of them is >= 1), so no range comes back empty.
+struct AlExtremes {
+    int t_first, t_last;
+    double c_lo, c_hi;
+};
+template <class Allow>
+__device__ __forceinline__ AlExtremes al_bin_extremes(const int64_t *__restrict__ rk, int len, const double *s, int m, double eps,
+                                                      int bin, double rho, const Allow &allow, int lane) {
     const double bd = (double)bin;
     int t_first = m, t_last = -1;
     double c_lo = __longlong_as_double(0x7ff0000000000000ll), c_hi = -c_lo;
     for (int j = lane; j < len; j += 64) {
         const double c = __longlong_as_double(rk[j]);
+        if (!allow.key(c)) continue;
         for (int t = al_lo<true>(s, m, c, eps, bd, rho); t < m; ++t) {
             const double d = al_bin(c, al_x<true>(s, t, rho), eps);
             if (!(d >= bd)) break;                                        // behind the bin (or NaN there)
-            if (!(d <= bd)) continue;                                     // (never, behind al_lo)
+            if (!(d <= bd) || !allow.index(t)) continue;                  // (the first: never, behind al_lo)
             t_first = t < t_first ? t : t_first;
             t_last = t > t_last ? t : t_last;
             c_lo = c < c_lo ? c : c_lo;
@@ -432,13 +483,25 @@ __device__ __forceinline__ AlSpan al_span(const int64_t *__restrict__ rk, int le
         c_lo = lo < c_lo ? lo : c_lo;
         c_hi = hi > c_hi ? hi : c_hi;
     }
+    return {t_first, t_last, c_lo, c_hi};
+}
+
+// The span of a row's best bin (include/tvz.h, tvz_align_span_topk): the extremes of every pair that votes into it, and
+// nr = the row's keys inside [smallest voting key, largest voting key], counted by a second lane-strided pass.
+struct AlSpan {
+    int t_first, t_last;
+    uint32_t nr;
+};
+__device__ __forceinline__ AlSpan al_span(const int64_t *__restrict__ rk, int len, const double *s, int m, double eps, int bin,
+                                          double rho, int lane) {
+    const AlExtremes x = al_bin_extremes(rk, len, s, m, eps, bin, rho, AlAllPairs{}, lane);
     uint32_t nr = 0;
     for (int j = lane; j < len; j += 64) {
         const double c = __longlong_as_double(rk[j]);
-        nr += c >= c_lo && c <= c_hi ? 1u : 0u;
+        nr += c >= x.c_lo && c <= x.c_hi ? 1u : 0u;
     }
     for (int off = 32; off > 0; off >>= 1) nr += __shfl_xor(nr, off);
-    return {t_first, t_last, nr};
+    return {x.t_first, x.t_last, nr};
 }
 
 // grid = (row blocks, Q).  Sorted query q: sv[at .. at + m) with at = q_offsets[q] - q_offsets[0], m = qm[q]
@@ -467,20 +530,9 @@ __device__ __forceinline__ void al_sweep(const Row *__restrict__ rows, int64_t n
     const int lane = threadIdx.x & 63;
     const int wv = threadIdx.x >> 6;
     double *s = reinterpret_cast<double *>(smem);
-    uint32_t *hist = reinterpret_cast<uint32_t *>(smem + (size_t)lds_keys * 8) + (size_t)wv * width;
-    uint16_t *dirty = reinterpret_cast<uint16_t *>(smem + (size_t)lds_keys * 8 + (size_t)kAlWaves * width * 4) + (size_t)wv * width;
-    uint32_t *n_dirty = reinterpret_cast<uint32_t *>(smem + (size_t)lds_keys * 8 + (size_t)kAlWaves * width * 6) + wv;
-    uint16_t *resume = nullptr;
-    int max_windows = 1, resume_keys = 0;
-    if constexpr (kWindowed) {
-        max_windows = aw_max_windows(B, width);
-        resume_keys = aw_resume_keys(B, width);
-        resume = reinterpret_cast<uint16_t *>(smem + (size_t)lds_keys * 8 + (size_t)kAlWaves * ((size_t)width * 6 + 4)) +
-                 (size_t)wv * resume_keys;
-    }
+    const AlWave w = al_wave<kWindowed>(smem, lds_keys, B, width, wv);
     for (int e = threadIdx.x; e < m; e += kAlBlock) s[e] = sv[at + e];
-    for (int b = lane; b < width; b += 64) hist[b] = 0;
-    if (lane == 0) *n_dirty = 0;
+    al_wave_clear(w, lane);
     if (threadIdx.x == 0) s_nhits = 0;
     __syncthreads();
 
@@ -502,21 +554,8 @@ __device__ __forceinline__ void al_sweep(const Row *__restrict__ rows, int64_t n
         const int64_t rn = r + stride;
         const Row nrow = load_row(rows + (rn < n_rows ? rn : last_row));      // lands while this row votes
         const int64_t *rk = keys + row.off;
-        double c_min = 0.0, c_max = 0.0;
-        if constexpr (kWindowed) {
-            c_min = __longlong_as_double(0x7ff0000000000000ll);
-            c_max = -c_min;
-            for (int j = lane; j < row.len; j += 64) {
-                const double c = __longlong_as_double(rk[j]);
-                c_min = c < c_min ? c : c_min;
-                c_max = c > c_max ? c : c_max;
-            }
-            for (int off = 32; off > 0; off >>= 1) {
-                const double lo = __shfl_xor(c_min, off), hi = __shfl_xor(c_max, off);
-                c_min = lo < c_min ? lo : c_min;
-                c_max = hi > c_max ? hi : c_max;
-            }
-        }
+        AlKeyRange kr{0.0, 0.0};
+        if constexpr (kWindowed) kr = al_key_range(rk, row.len, lane);
         unsigned long long best = 0;                                          // of the row: the kept rate's
         uint32_t best_rate = 0;
         int ri = 0;
@@ -531,52 +570,52 @@ __device__ __forceinline__ void al_sweep(const Row *__restrict__ rows, int64_t n
             if constexpr (kWindowed) {
                 // the row's offset range [bin(c_min, x_max), bin(c_max, x_min)], clipped to [-B, B]; a NaN end (inf -
                 // inf) clips to the bound
-                const double d_lo = al_bin(c_min, x_max, eps), d_hi = al_bin(c_max, x_min, eps);
+                const double d_lo = al_bin(kr.c_min, x_max, eps), d_hi = al_bin(kr.c_max, x_min, eps);
                 const double r_lo = d_lo >= -Bd ? d_lo : -Bd, r_hi = d_hi <= Bd ? d_hi : Bd;
                 w1 = -1;                                                      // no window: an empty row, a range outside
                 if (row.len > 0 && r_lo <= r_hi) {                            // -B <= r_lo <= r_hi <= B: both finite
-                    w0 = ((int)r_lo + B) / width;
-                    w1 = ((int)r_hi + B) / width;
+                    w0 = ((int)r_lo + B) / w.width;
+                    w1 = ((int)r_hi + B) / w.width;
                 }
                 w0 = __builtin_amdgcn_readfirstlane(w0);                      // (equal in every lane already)
                 w1 = __builtin_amdgcn_readfirstlane(w1);
-                w1 = w1 < max_windows - 1 ? w1 : max_windows - 1;             // (never: (2B) / width is the last window)
+                w1 = w1 < w.max_windows - 1 ? w1 : w.max_windows - 1;         // (never: (2B) / w.width is the last window)
             }
             unsigned long long rbest = 0;                                     // of this rate
-            for (int w = w1; w >= w0; --w) {                                  // wave-uniform, at most max_windows rounds
+            for (int wi = w1; wi >= w0; --wi) {                               // wave-uniform, at most w.max_windows rounds
                 int w_lo = -B, w_hi = B;
                 if constexpr (kWindowed) {
-                    w_lo = w * width - B;                                     // >= -B
-                    w_hi = w_lo + width - 1 < B ? w_lo + width - 1 : B;
+                    w_lo = wi * w.width - B;                                  // >= -B
+                    w_hi = w_lo + w.width - 1 < B ? w_lo + w.width - 1 : B;
                 }
                 const double lo_d = (double)w_lo, hi_d = (double)w_hi;
                 for (int j = lane; j < row.len; j += 64) {
                     const double c = __longlong_as_double(rk[j]);
-                    const bool kept_pos = kWindowed && j < resume_keys;       // (the same in every lane of a round)
+                    const bool kept_pos = kWindowed && j < w.resume_keys;     // (the same in every lane of a round)
                     // (w1 is this rate's: the positions another rate left are never read)
-                    int t = kept_pos && w != w1 ? (int)resume[j] : al_lo<kRates>(s, m, c, eps, hi_d, rho);
+                    int t = kept_pos && wi != w1 ? (int)w.resume[j] : al_lo<kRates>(s, m, c, eps, hi_d, rho);
                     for (; t < m; ++t) {
                         const double d = al_bin(c, al_x<kRates>(s, t, rho), eps);
                         if (!(d >= lo_d)) break;                              // behind the window (or NaN there)
                         if (!(d <= hi_d)) continue;                           // (never, behind al_lo: keeps the index in bounds)
                         const int bin = (int)d;                               // w_lo <= bin <= w_hi
-                        const uint32_t slot = (uint32_t)(bin - w_lo);         // 0 .. width - 1
-                        const uint32_t cnt = atomicAdd(&hist[slot], 1u) + 1u;
-                        if (cnt == 1u) dirty[atomicAdd(n_dirty, 1u)] = (uint16_t)slot;  // at most once per slot: < width
+                        const uint32_t slot = (uint32_t)(bin - w_lo);         // 0 .. w.width - 1
+                        const uint32_t cnt = atomicAdd(&w.hist[slot], 1u) + 1u;
+                        if (cnt == 1u) w.dirty[atomicAdd(w.n_dirty, 1u)] = (uint16_t)slot;  // at most once per slot: < w.width
                         const uint32_t order = 2u * (uint32_t)(bin < 0 ? -bin : bin) + (bin > 0 ? 1u : 0u);
                         const unsigned long long key = ((unsigned long long)cnt << 33) | (kAlOrderMask - order);
                         rbest = key > rbest ? key : rbest;
                     }
                     if constexpr (kWindowed) {
-                        if (kept_pos) resume[j] = (uint16_t)t;                // t <= m <= 4095
+                        if (kept_pos) w.resume[j] = (uint16_t)t;              // t <= m <= 4095
                     }
                 }
                 // LDS ops of one wave complete in order: the notes above are visible to the clearing below
                 wave_lds_fence();
-                const int nd = (int)*n_dirty;
-                for (int i = lane; i < nd; i += 64) hist[dirty[i]] = 0;
+                const int nd = (int)*w.n_dirty;
+                for (int i = lane; i < nd; i += 64) w.hist[w.dirty[i]] = 0;
                 wave_lds_fence();
-                if (lane == 0) *n_dirty = 0;
+                if (lane == 0) *w.n_dirty = 0;
             }
             for (int off = 32; off > 0; off >>= 1) {
                 const unsigned long long o = __shfl_xor(rbest, off);
@@ -617,10 +656,8 @@ __device__ __forceinline__ void al_sweep(const Row *__restrict__ rows, int64_t n
                     }
                 }
             } else if (score >= (uint32_t)min_score) {
-                const uint32_t order = (uint32_t)(kAlOrderMask - (best & kAlOrderMask));
-                const int mag = (int)(order >> 1);
                 ++n_hits;
-                al_insert(kept, Hit::make(score, row.vid, (order & 1u) ? mag : -mag, rl, votes, best_rate), k, lane);
+                al_insert(kept, Hit::make(score, row.vid, al_best_bin(best), rl, votes, best_rate), k, lane);
             }
         }
         row = nrow;

@@ -1,9 +1,9 @@
 // tvz_align_parts_kernels.h — every aligned part of a NAMED stored video (tvz_align_parts), gfx950
-// wave64.  Included by tvz_match.hip only, behind tvz_align_kernels.h, whose device helpers it uses as they are:
-// al_bin, al_scaled, al_x, al_lo (the vote's expression and the start of a key's run), al_best_bin, aw_width /
-// aw_max_windows / aw_resume_keys / aw_lds_bytes (the window arithmetic and the sweep's LDS layout), AlRates, Row,
-// load_row, wave_lds_fence; the queries are sorted by ts_tol_sort_kernel, as the sweep's are.  Nothing of the sweep
-// is changed: this is a kernel family beside it.
+// wave64.  Included by tvz_match.hip only, behind tvz_align_kernels.h, whose functions for one row it shares: al_wave /
+// al_wave_clear (a wave's part of the LDS, aw_lds_bytes), al_key_range, al_bin_extremes (where a bin's votes lie, with
+// ApOutside below as the rule for which pairs count) and al_best_bin; also al_bin, al_x, al_lo, AlRates, Row, load_row.
+// The window walk itself, ap_votes, is the one copy left of al_sweep's loop: it stays because moving both into one
+// function moved the sweeps' machine code.  The queries are sorted by ts_tol_sort_kernel.
 //
 // The call is a refinement: the search (tvz_align_span_topk), an exact match or a user has named up to k stored video
 // ids per upload, and every (upload, id) pair is aligned in full - Q x k row walks, not one per row of the table.
@@ -22,12 +22,12 @@
 //                            keeps counting past them: it is n_rows.
 //   ts_alignp_walk_kernel    grid (k, Q): one block of kAlWaves waves per pair, a wave per candidate slot, then slots
 //                            4..7.  The sorted query lies in LDS once per block and every wave has a histogram
-//                            window, a touched list and resume positions of its own - the sweep's layout
-//                            (aw_lds_bytes) - so the only block barrier stands in front of the row walks.  Part 0 is
-//                            the sweep's window walk over the rates (ap_votes<false>); every later part the same walk
-//                            at the kept rate where a pair votes only if its t and c pass the at most three exclusion
-//                            ranges, which live in registers (ApRanges: constant indices only).  After each part the
-//                            four extremes by one shfl_xor reduction (ap_extremes) and one counting pass each for nr
+//                            window, a touched list and resume positions of its own - the sweep's layout (al_wave)
+//                            - so the only block barrier stands in front of the row walks.  Part 0 is the sweep's
+//                            window walk over the rates (ap_votes<false>); every later part the same walk at the
+//                            kept rate where a pair votes only if its t and c pass the at most three exclusion
+//                            ranges, which live in registers (ApRanges: constant indices only).  After each part
+//                            the four extremes (al_bin_extremes with ApOutside) and one counting pass each for nr
 //                            and nq.  A slot's result goes to the workspace: int32[1 + max_parts][6].
 //   ts_alignp_pick_kernel    a wave per pair: the slot with the most part-0 votes, the earlier row of the table on a
 //                            tie (the slots fill in no fixed order: the row's index decides), is copied out with
@@ -97,13 +97,11 @@ __device__ __forceinline__ bool ap_c_free(const ApRanges &ex, double c) {
     return ok;
 }
 
-// a wave's own LDS (the sweep's layout, aw_lds_bytes) and the call's window shape
-struct ApWave {
-    uint32_t *hist;
-    uint16_t *dirty;
-    uint32_t *n_dirty;
-    uint16_t *resume;
-    int width, max_windows, resume_keys;
+// The parts' rule for al_bin_extremes: only the pairs whose t and c lie outside the ranges count
+struct ApOutside {
+    const ApRanges &ex;
+    __device__ __forceinline__ bool key(double c) const { return ap_c_free(ex, c); }
+    __device__ __forceinline__ bool index(int t) const { return ap_t_free(ex, t); }
 };
 
 // The best bin of one row at one rate, as the sweep finds it (al_sweep's window loop: see tvz_align_kernels.h for why
@@ -114,7 +112,7 @@ struct ApWave {
 // smallest and largest key.  The histogram is clean on entry and on return.  m >= 1, len >= 1.
 template <bool kExcl>
 __device__ __forceinline__ unsigned long long ap_votes(const int64_t *__restrict__ rk, int len, const double *s, int m, double eps,
-                                                       int32_t B, double c_min, double c_max, double rho, const ApWave &w,
+                                                       int32_t B, double c_min, double c_max, double rho, const AlWave &w,
                                                        const ApRanges &ex, int lane) {
     const double Bd = (double)B;
     const double x_min = al_x<true>(s, 0, rho), x_max = al_x<true>(s, m - 1, rho);     // the products stay sorted
@@ -167,41 +165,6 @@ __device__ __forceinline__ unsigned long long ap_votes(const int64_t *__restrict
     return best;
 }
 
-// Where a part's votes lie: over the allowed pairs that vote into `bin`, the smallest and largest index and key,
-// reduced over the wave (al_span's walk with the ranges of `ex` applied).  The bin has votes: no range comes back empty.
-struct ApExtremes {
-    int t_first, t_last;
-    double c_lo, c_hi;
-};
-__device__ __forceinline__ ApExtremes ap_extremes(const int64_t *__restrict__ rk, int len, const double *s, int m, double eps,
-                                                  int bin, double rho, const ApRanges &ex, int lane) {
-    const double bd = (double)bin;
-    int t_first = m, t_last = -1;
-    double c_lo = __longlong_as_double(0x7ff0000000000000ll), c_hi = -c_lo;
-    for (int j = lane; j < len; j += 64) {
-        const double c = __longlong_as_double(rk[j]);
-        if (!ap_c_free(ex, c)) continue;
-        for (int t = al_lo<true>(s, m, c, eps, bd, rho); t < m; ++t) {
-            const double d = al_bin(c, al_x<true>(s, t, rho), eps);
-            if (!(d >= bd)) break;                                        // behind the bin (or NaN there)
-            if (!(d <= bd) || !ap_t_free(ex, t)) continue;
-            t_first = t < t_first ? t : t_first;
-            t_last = t > t_last ? t : t_last;
-            c_lo = c < c_lo ? c : c_lo;
-            c_hi = c > c_hi ? c : c_hi;
-        }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        const int tf = __shfl_xor(t_first, off), tl = __shfl_xor(t_last, off);
-        const double lo = __shfl_xor(c_lo, off), hi = __shfl_xor(c_hi, off);
-        t_first = tf < t_first ? tf : t_first;
-        t_last = tl > t_last ? tl : t_last;
-        c_lo = lo < c_lo ? lo : c_lo;
-        c_hi = hi > c_hi ? hi : c_hi;
-    }
-    return {t_first, t_last, c_lo, c_hi};
-}
-
 // grid = (row blocks, Q), any number of row blocks.  ids: the id of pair (q, j) is ids[q * query_id_stride + j *
 // id_stride]; a negative id names no pair.  counts int32[Q][k], zeroed before the launch: += 1 per matching row, so
 // it ends as n_rows; slots int64[Q][k][kApMaxRows]: the first kApMaxRows matching rows' indices, in no fixed order.
@@ -248,18 +211,9 @@ __global__ __launch_bounds__(kAlBlock) void ts_alignp_walk_kernel(
     const int lane = threadIdx.x & 63;
     const int wv = threadIdx.x >> 6;
     double *s = reinterpret_cast<double *>(smem);
-    ApWave w;
-    w.width = width;
-    w.max_windows = aw_max_windows(B, width);
-    w.resume_keys = aw_resume_keys(B, width);
-    w.hist = reinterpret_cast<uint32_t *>(smem + (size_t)lds_keys * 8) + (size_t)wv * width;
-    w.dirty = reinterpret_cast<uint16_t *>(smem + (size_t)lds_keys * 8 + (size_t)kAlWaves * width * 4) + (size_t)wv * width;
-    w.n_dirty = reinterpret_cast<uint32_t *>(smem + (size_t)lds_keys * 8 + (size_t)kAlWaves * width * 6) + wv;
-    w.resume = reinterpret_cast<uint16_t *>(smem + (size_t)lds_keys * 8 + (size_t)kAlWaves * ((size_t)width * 6 + 4)) +
-               (size_t)wv * w.resume_keys;
+    const AlWave w = al_wave<true>(smem, lds_keys, B, width, wv);
     for (int e = threadIdx.x; e < m; e += kAlBlock) s[e] = sv[at + e];
-    for (int b = lane; b < width; b += 64) w.hist[b] = 0;
-    if (lane == 0) *w.n_dirty = 0;
+    al_wave_clear(w, lane);
     __syncthreads();
 
     const int words = ap_words(max_parts);
@@ -267,24 +221,14 @@ __global__ __launch_bounds__(kAlBlock) void ts_alignp_walk_kernel(
         const Row row = load_row(rows + slots[pair * kApMaxRows + slot]);
         const int64_t *rk = keys + row.off;
         int32_t *o = scratch + (pair * kApMaxRows + slot) * words;
-        double c_min = __longlong_as_double(0x7ff0000000000000ll), c_max = -c_min;
-        for (int i = lane; i < row.len; i += 64) {
-            const double c = __longlong_as_double(rk[i]);
-            c_min = c < c_min ? c : c_min;
-            c_max = c > c_max ? c : c_max;
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            const double lo = __shfl_xor(c_min, off), hi = __shfl_xor(c_max, off);
-            c_min = lo < c_min ? lo : c_min;
-            c_max = hi > c_max ? hi : c_max;
-        }
-        const bool can_vote = m > 0 && row.len > 0;
+        const AlKeyRange kr = al_key_range(rk, row.len, lane);
         ApRanges ex = ap_no_ranges();
         unsigned long long best = 0;                                      // part 0: the kept rate's
         uint32_t best_rate = 0;
-        if (can_vote) {
+        if (m > 0 && row.len > 0) {
             for (int ri = 0; ri < rates.n; ++ri) {                        // wave-uniform
-                const unsigned long long rbest = ap_votes<false>(rk, row.len, s, m, eps, B, c_min, c_max, rates.r[ri], w, ex, lane);
+                const unsigned long long rbest =
+                    ap_votes<false>(rk, row.len, s, m, eps, B, kr.c_min, kr.c_max, rates.r[ri], w, ex, lane);
                 if ((rbest >> 33) > (best >> 33)) {                       // strictly more votes: a tie keeps the smaller index
                     best = rbest;
                     best_rate = (uint32_t)ri;
@@ -294,13 +238,13 @@ __global__ __launch_bounds__(kAlBlock) void ts_alignp_walk_kernel(
         const double rho = rates.r[best_rate];
         int32_t n_parts = 0;
         for (int p = 0; p < max_parts; ++p) {                             // wave-uniform
-            if (p > 0) best = ap_votes<true>(rk, row.len, s, m, eps, B, c_min, c_max, rho, w, ex, lane);
+            if (p > 0) best = ap_votes<true>(rk, row.len, s, m, eps, B, kr.c_min, kr.c_max, rho, w, ex, lane);
             const int32_t votes = (int32_t)(best >> 33);
             if (votes < min_votes && p > 0) break;
             int32_t part[kApCols] = {0, 0, 0, 0, 0, 0};
             if (votes > 0) {
                 const int bin = al_best_bin(best);
-                const ApExtremes x = ap_extremes(rk, row.len, s, m, eps, bin, rho, ex, lane);
+                const AlExtremes x = al_bin_extremes(rk, row.len, s, m, eps, bin, rho, ApOutside{ex}, lane);
                 int32_t nq = 0, nr = 0;
                 for (int t = x.t_first + lane; t <= x.t_last; t += 64) nq += ap_t_free(ex, t) ? 1 : 0;
                 for (int i = lane; i < row.len; i += 64) {

@@ -2224,6 +2224,17 @@ int check_align_early(const AlignTopkForm &f, const AlignAsk &s, int32_t max_que
     return TVZ_OK;
 }
 
+// The dynamic LDS of a block of row walks (aw_lds_bytes) for a call of B bins on either side and queries of at most
+// max_query_len values, and whether it fits a gfx950 workgroup beside the static LDS the kernel declares.  The caller
+// words the refusal.
+struct AlignLds {
+    int32_t lds_keys, width;
+    size_t bytes;
+    AlignLds(int32_t max_query_len, int32_t B)
+        : lds_keys(std::max(max_query_len, 1)), width(aw_width(B)), bytes(aw_lds_bytes(lds_keys, B, width)) {}
+    bool fits(int static_lds) const { return bytes + (size_t)static_lds <= (size_t)kLdsPerWorkgroup; }
+};
+
 // One handle: sort -> sweep that keeps the k best -> per-query selection.  `rates`: checked (check_align_early).
 // n_ranks = 0: d_out is the caller's.  n_ranks >= 1: the workspace also holds the local block and n_ranks gathered ones
 // (the form's sharded sizing function); d_out = NULL writes the block into the workspace's own, and `blocks` is told
@@ -2241,15 +2252,13 @@ int align_topk_run(const AlignTopkForm &f, tvz_corpus *c, const Batch &b, const 
     if (Q == 0) return TVZ_OK;
     Carver cv(ws.p);
     const AlignTopkWs w = align_topk_ws_layout(cv, f, Q, k, n_ranks);
-    const int32_t lds_keys = std::max(max_query_len, 1);
-    const int32_t width = aw_width(B);
-    const size_t lds = aw_lds_bytes(lds_keys, B, width);
+    const AlignLds lds(max_query_len, B);
     auto args_ok = [&]() -> int {
         TVZ_REQUIRE(d_out != nullptr || w.local != nullptr, "d_out is NULL");
         if (d_out == nullptr) d_out = w.local;
         if (blocks) *blocks = ShardBlocks{d_out, w.gathered};
-        TVZ_REQUIRE(lds + f.static_lds <= (size_t)kLdsPerWorkgroup,
-                    "%s sweep: %zu B of dynamic + %d B of static LDS exceed a gfx950 workgroup's", f.what, lds, f.static_lds);
+        TVZ_REQUIRE(lds.fits(f.static_lds), "%s sweep: %zu B of dynamic + %d B of static LDS exceed a gfx950 workgroup's", f.what,
+                    lds.bytes, f.static_lds);
         return TVZ_OK;
     };
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
@@ -2262,8 +2271,8 @@ int align_topk_run(const AlignTopkForm &f, tvz_corpus *c, const Batch &b, const 
         return rc;
     const int64_t n_rows = t.n_rows;
     const int n_blocks = n_rows ? (int)std::min<int64_t>(tvz::ceil_div(n_rows, (int64_t)kAlWaves), tol_topk_max_blocks(Q)) : 0;
-    AlignLaunch l{dim3((unsigned)n_blocks, (unsigned)Q), lds, st, c, n_rows, &b, &t.ws, &a, &rates, s.flags, lds_keys, B,
-                  width, k, n_blocks, &w, d_out};
+    AlignLaunch l{dim3((unsigned)n_blocks, (unsigned)Q), lds.bytes, st, c, n_rows, &b, &t.ws, &a, &rates, s.flags, lds.lds_keys,
+                  B, lds.width, k, n_blocks, &w, d_out};
     if (n_blocks) {
         f.sweep(l);
         TVZ_HIP(hipGetLastError());
@@ -2372,12 +2381,11 @@ int align_parts_impl(tvz_corpus *c, const Batch &b, const int32_t *d_video_ids, 
     if (Q == 0) return TVZ_OK;
     Carver cv(ws.p);
     const AlignPartsWs w = align_parts_ws_layout(cv, Q, k, max_parts);
-    const int32_t lds_keys = std::max(max_query_len, 1);
-    const int32_t width = aw_width(B);
-    const size_t lds = aw_lds_bytes(lds_keys, B, width);
+    const AlignLds lds(max_query_len, B);
     auto args_ok = [&]() -> int {
         TVZ_REQUIRE(d_video_ids != nullptr && d_parts != nullptr, "NULL argument");
-        TVZ_REQUIRE(lds <= (size_t)kLdsPerWorkgroup, "%s walk: %zu B of dynamic LDS exceed a gfx950 workgroup's", f.what, lds);
+        TVZ_REQUIRE(lds.fits(/* static LDS: none */ 0), "%s walk: %zu B of dynamic LDS exceed a gfx950 workgroup's", f.what,
+                    lds.bytes);
         return TVZ_OK;
     };
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
@@ -2392,13 +2400,13 @@ int align_parts_impl(tvz_corpus *c, const Batch &b, const int32_t *d_video_ids, 
         hipLaunchKernelGGL(ts_alignp_locate_kernel, dim3(row_blocks, (unsigned)Q), dim3(kApLocateBlock), 0, st, c->rows.p, n_rows,
                            d_video_ids, id_stride, query_id_stride, k, w.counts, w.slots);
         TVZ_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ts_alignp_walk_kernel, dim3((unsigned)k, (unsigned)Q), dim3(kAlBlock), lds, st, c->rows.p, c->keys.p,
-                           t.ws.sv, b.d_q_offsets, t.ws.qm, lds_keys, eps, B, width, rates, min_votes, max_parts, d_video_ids,
-                           id_stride, query_id_stride, k, w.counts, w.slots, w.scratch);
+        hipLaunchKernelGGL(ts_alignp_walk_kernel, dim3((unsigned)k, (unsigned)Q), dim3(kAlBlock), lds.bytes, st, c->rows.p,
+                           c->keys.p, t.ws.sv, b.d_q_offsets, t.ws.qm, lds.lds_keys, eps, B, lds.width, rates, min_votes, max_parts,
+                           d_video_ids, id_stride, query_id_stride, k, w.counts, w.slots, w.scratch);
         TVZ_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(ts_alignp_pick_kernel, dim3((unsigned)tvz::ceil_div((int64_t)Q * k, (int64_t)kApPickWaves)),
-                       dim3(kApPickBlock), 0, st, d_video_ids, id_stride, query_id_stride, Q, k, max_parts, t.ws.qm, lds_keys,
+                       dim3(kApPickBlock), 0, st, d_video_ids, id_stride, query_id_stride, Q, k, max_parts, t.ws.qm, lds.lds_keys,
                        w.counts, w.slots, w.scratch, d_parts);
     TVZ_HIP(hipGetLastError());
     return record(c, st);

@@ -804,6 +804,10 @@ namespace {
 // negative one), its votes, and the votes of bin 0 (tolerant count without shift).
 constexpr int kAlignMaxBins = 4096;   // 16 KB of u32 per wave, 4 waves per block
 
+// the bin a pair (row key c, query value x) votes into, the contract's d verbatim: one IEEE subtraction, one true
+// division.  Every alignment kernel's (tvz_align_kernels.h, tvz_align_parts_kernels.h)
+__device__ __forceinline__ double al_bin(double c, double x, double eps) { return floor((c - x) / eps + 0.5); }
+
 __global__ __launch_bounds__(kBlock) void ts_align_kernel(
     const Row *__restrict__ rows, int64_t n_rows, const int64_t *__restrict__ keys,
     const double *__restrict__ query, int32_t n, double eps, int32_t B,
@@ -823,7 +827,7 @@ __global__ __launch_bounds__(kBlock) void ts_align_kernel(
             for (int i = 0; i < n; ++i) {
                 const double q = query[i];
                 if (q != q) continue;                              // NaN never aligns
-                const double d = floor((c - q) / eps + 0.5);
+                const double d = al_bin(c, q, eps);
                 if (d >= -(double)B && d <= (double)B) atomicAdd(&hist[(int)d + B], 1u);
             }
         }
