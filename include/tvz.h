@@ -605,8 +605,19 @@ int tvz_align_wide_topk_sharded(tvz_corpus *c, tvz_comm *comm, const double *d_q
  * tvz_align_wide_topk_shards: d_blocks int32[n_shards][Q][k+1][5]; one workspace sized for ONE handle
  * (tvz_align_rates_topk_workspace_bytes); refuses what tvz_align_rates_topk and the merge refuse before anything is
  * enqueued.
- * NOT YET: the RCCL form (_sharded), and with it the service's ask kind and flags - the one-process-per-GPU service
- * gets them in a follow-up, as the bounded and the wide search did. */
+ * tvz_align_rates_topk_sharded: one process per GPU, as tvz_align_wide_topk_sharded relates to tvz_align_wide_topk:
+ * the arguments of tvz_align_rates_topk with the communicator behind the handle; tvz_align_rates_topk into the
+ * workspace's own block -> the ONE ncclAllGather of Q x (k+1) x 5 int32 per rank, ordered on the communicator with the
+ * other sharded calls' collectives -> tvz_align_rates_topk_merge with the same flags; every rank gets the same d_topk
+ * int32[Q][k][5] and d_totals int32[Q].  Every rank passes the same arguments, the rate list among them.  Refusals,
+ * their order and their messages are tvz_align_rates_topk's; behind them, and still before anything is enqueued: a NULL
+ * communicator, a NULL d_topk or d_totals, a d_topk that is not 16-byte aligned (TVZ_ERR_INVALID), more than 16 ranks
+ * (TVZ_ERR_UNSUPPORTED).
+ * Workspace = tvz_align_rates_topk_workspace_bytes(Q, max_query_len, total_query_keys, k)
+ *           + (1 + max(n_ranks, 1)) x Q x (k + 1) x 20                                  (local + gathered blocks)
+ *           + alignment (each part to 256 B);
+ * tvz_align_rates_topk_sharded_workspace_bytes answers 0 where the plain sizing function does, and for n_ranks < 0.
+ * Has run on hardware at ONE rank only. */
 #define TVZ_ALIGN_MAX_RATES 8
 size_t tvz_align_rates_topk_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k);
 int tvz_align_rates_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
@@ -622,6 +633,13 @@ int tvz_align_rates_topk_shards(tvz_corpus *const *shards, int32_t n_shards, con
                                 int32_t min_score, uint32_t flags, const int32_t *d_exclude_ids, int32_t k,
                                 int32_t *d_blocks, int32_t *d_topk, int32_t *d_totals, void *d_workspace,
                                 size_t workspace_bytes, void *hip_stream);
+size_t tvz_align_rates_topk_sharded_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k,
+                                                    int32_t n_ranks);
+int tvz_align_rates_topk_sharded(tvz_corpus *c, tvz_comm *comm, const double *d_queries, const int64_t *d_q_offsets,
+                                 int32_t Q, int32_t max_query_len, double eps, double max_offset, const double *h_rates,
+                                 int32_t n_rates, int32_t min_votes, int32_t min_score, uint32_t flags,
+                                 const int32_t *d_exclude_ids, int32_t k, int32_t *d_topk, int32_t *d_totals,
+                                 void *d_workspace, size_t workspace_bytes, void *hip_stream);
 
 /* The alignment top-k at any shift WITH THE MATCHED SPAN of every hit, and a score over that span alone:
  * tvz_align_rates_topk that also says WHERE the votes of the best bin lie - which part of the upload is the copy and
@@ -677,8 +695,13 @@ int tvz_align_rates_topk_shards(tvz_corpus *const *shards, int32_t n_shards, con
  * refused as the call refuses them.
  * tvz_align_span_topk_shards: the shards of ONE process, as tvz_align_rates_topk_shards: d_blocks
  * int32[n_shards][Q][k+1][8]; one workspace sized for ONE handle (tvz_align_span_topk_workspace_bytes).
- * NOT YET: no _sharded (RCCL) form and no service switch - this block gets its RCCL form together with the rates
- * block's. */
+ * tvz_align_span_topk_sharded: one process per GPU, as tvz_align_rates_topk_sharded: the ONE ncclAllGather moves Q x
+ * (k+1) x 8 int32 per rank, the merge is tvz_align_span_topk_merge with the same flags; d_topk int32[Q][k][8].  Refusals
+ * are tvz_align_span_topk's, in its order and words, and the communicator's behind them.
+ * Workspace = tvz_align_span_topk_workspace_bytes(Q, max_query_len, total_query_keys, k)
+ *           + (1 + max(n_ranks, 1)) x Q x (k + 1) x 32                                  (local + gathered blocks)
+ *           + alignment (each part to 256 B).
+ * Has run on hardware at ONE rank only. */
 #define TVZ_ALIGN_LOCAL 2u               /* flags of tvz_align_span_topk: score = the Jaccard inside the span */
 size_t tvz_align_span_topk_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k);
 int tvz_align_span_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
@@ -694,6 +717,13 @@ int tvz_align_span_topk_shards(tvz_corpus *const *shards, int32_t n_shards, cons
                                int32_t min_score, uint32_t flags, const int32_t *d_exclude_ids, int32_t k,
                                int32_t *d_blocks, int32_t *d_topk, int32_t *d_totals, void *d_workspace,
                                size_t workspace_bytes, void *hip_stream);
+size_t tvz_align_span_topk_sharded_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k,
+                                                   int32_t n_ranks);
+int tvz_align_span_topk_sharded(tvz_corpus *c, tvz_comm *comm, const double *d_queries, const int64_t *d_q_offsets,
+                                int32_t Q, int32_t max_query_len, double eps, double max_offset, const double *h_rates,
+                                int32_t n_rates, int32_t min_votes, int32_t min_score, uint32_t flags,
+                                const int32_t *d_exclude_ids, int32_t k, int32_t *d_topk, int32_t *d_totals,
+                                void *d_workspace, size_t workspace_bytes, void *hip_stream);
 
 /* EVERY ALIGNED PART of a named stored video: the refinement behind a search.  tvz_align_span_topk reports a stored
  * video once, at its single best shift; a re-upload with a part put in or taken out - an inserted ad, a removed
@@ -741,8 +771,39 @@ int tvz_align_span_topk_shards(tvz_corpus *const *shards, int32_t n_shards, cons
  * fixed parts + one query of max_query_len values: TVZ_ERR_WORKSPACE with the bytes missing.
  * Cost: one pass over the row table's 16-byte rows (a thread per row), then per (pair, candidate row) the span call's
  * walk of that one row and one more walk per further part.
- * NOT YET: no _shards / _sharded form and no service switch; a sharded table asks every shard and keeps, per pair, the
- * answer with the most part-0 votes (service.ShardedCorpus.align_parts). */
+ *
+ * Over a SHARDED table every shard answers every pair and the answers are merged:
+ * tvz_align_parts_merge: d_gathered int32[n_lists][Q][k][1 + max_parts][6], the lists' d_parts of ONE call (the same
+ * queries, ids and parameters on every shard) -> d_parts int32[Q][k][1 + max_parts][6].  Per pair:
+ *   - the lists whose n_rows > 0 are considered; among them the winner is the list with the most part-0 votes (row 1,
+ *     column 1), the LOWER list index on a tie; where no list holds a row, list 0 is the winner;
+ *   - the winner's block is copied, and n_rows becomes the lists' sum, accumulated in 64 bits and saturated at
+ *     INT32_MAX;
+ *   - if ANY list has n_parts = INT32_MIN the pair is REFUSED: rows 1.. become zero and row 0 becomes (the winner's id,
+ *     0, 0, INT32_MIN, the summed n_rows, the winner's m);
+ *   - ids are carried and never compared.
+ * The rule is associative under regrouping: more than 16 lists are merged in groups of up to 16 and the groups' answers
+ * merged again, lower lists first.  n_lists outside 1..16, k outside 1..64 or max_parts outside 1..TVZ_ALIGN_MAX_PARTS:
+ * TVZ_ERR_UNSUPPORTED; a negative Q or a NULL pointer: TVZ_ERR_INVALID; nothing is written on a refusal; Q = 0 returns
+ * TVZ_OK.  A pair's block is (1 + max_parts) x 24 bytes: the pointers need int32 alignment only.  Enqueues one launch.
+ * MORE THAN TVZ_ALIGN_PARTS_MAX_ROWS ROWS of one id refuse a pair only where they lie in ONE shard: nine rows split five
+ * and four over two shards are answered, with n_rows = 9; nine rows in one shard are refused, with n_rows = 9.
+ * tvz_align_parts_shards: the shards of ONE process (several handles on one device): tvz_align_parts on every handle in
+ * turn on `hip_stream` - each takes its handle's shared lock, waits for its mutations and selects its device -, the
+ * answers written to d_blocks int32[n_shards][Q][k][1 + max_parts][6], then tvz_align_parts_merge -> d_parts.  One
+ * workspace sized for ONE handle (tvz_align_parts_workspace_bytes) serves all of them.  Refuses what tvz_align_parts
+ * refuses, in its order and words, then what the merge refuses (n_shards outside 1..16 included), a NULL handle and
+ * handles on different devices, before anything is enqueued.
+ * tvz_align_parts_sharded: one process per GPU: tvz_align_parts into the workspace's own block -> the ONE ncclAllGather
+ * of Q x k x (1 + max_parts) x 6 int32 per rank, ordered on the communicator with the other sharded calls' collectives
+ * -> tvz_align_parts_merge; every rank gets the same d_parts.  Every rank passes the same arguments, the ids among
+ * them.  Refusals are tvz_align_parts's, in its order and words; behind them, before anything is enqueued: a NULL
+ * communicator or d_parts (TVZ_ERR_INVALID), more than 16 ranks (TVZ_ERR_UNSUPPORTED).
+ * Workspace = tvz_align_parts_workspace_bytes(Q, max_query_len, total_query_keys, k, max_parts)
+ *           + (1 + max(n_ranks, 1)) x Q k x (1 + max_parts) x 24                        (local + gathered answers)
+ *           + alignment (each part to 256 B);
+ * tvz_align_parts_sharded_workspace_bytes answers 0 where tvz_align_parts_workspace_bytes does, and for n_ranks < 0.
+ * Has run on hardware at ONE rank only. */
 #define TVZ_ALIGN_MAX_PARTS 4
 #define TVZ_ALIGN_PARTS_MAX_ROWS 8
 size_t tvz_align_parts_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k,
@@ -751,6 +812,20 @@ int tvz_align_parts(tvz_corpus *c, const double *d_queries, const int64_t *d_q_o
                     const int32_t *d_video_ids, int64_t id_stride, int64_t query_id_stride, int32_t k, double eps,
                     double max_offset, const double *h_rates, int32_t n_rates, int32_t min_votes, int32_t max_parts,
                     int32_t *d_parts, void *d_workspace, size_t workspace_bytes, void *hip_stream);
+int tvz_align_parts_merge(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t k, int32_t max_parts,
+                          int32_t *d_parts, void *hip_stream);
+int tvz_align_parts_shards(tvz_corpus *const *shards, int32_t n_shards, const double *d_queries, const int64_t *d_q_offsets,
+                           int32_t Q, int32_t max_query_len, const int32_t *d_video_ids, int64_t id_stride,
+                           int64_t query_id_stride, int32_t k, double eps, double max_offset, const double *h_rates,
+                           int32_t n_rates, int32_t min_votes, int32_t max_parts, int32_t *d_blocks, int32_t *d_parts,
+                           void *d_workspace, size_t workspace_bytes, void *hip_stream);
+size_t tvz_align_parts_sharded_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k,
+                                               int32_t max_parts, int32_t n_ranks);
+int tvz_align_parts_sharded(tvz_corpus *c, tvz_comm *comm, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
+                            int32_t max_query_len, const int32_t *d_video_ids, int64_t id_stride, int64_t query_id_stride,
+                            int32_t k, double eps, double max_offset, const double *h_rates, int32_t n_rates,
+                            int32_t min_votes, int32_t max_parts, int32_t *d_parts, void *d_workspace,
+                            size_t workspace_bytes, void *hip_stream);
 
 /* ------------------------------------------------------------------------
  * Opt-in TOLERANT duplicate match.  NOT the reference's verdict: db.py:79,85-91 match exact float64

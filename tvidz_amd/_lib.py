@@ -116,6 +116,22 @@ SIGNATURES = {
     "tvz_align_parts_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
     "tvz_align_parts": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, C.c_int64, C.c_int32, C.c_double,
                                   C.c_double, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_size_t, _P]),
+    "tvz_align_rates_topk_sharded_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
+    "tvz_align_rates_topk_sharded": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, C.c_int32,
+                                               C.c_int32, C.c_int32, C.c_uint32, _P, C.c_int32, _P, _P, _P, C.c_size_t,
+                                               _P]),
+    "tvz_align_span_topk_sharded_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
+    "tvz_align_span_topk_sharded": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, C.c_int32,
+                                              C.c_int32, C.c_int32, C.c_uint32, _P, C.c_int32, _P, _P, _P, C.c_size_t, _P]),
+    "tvz_align_parts_merge": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "tvz_align_parts_shards": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, C.c_int64, C.c_int32,
+                                         C.c_double, C.c_double, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
+                                         C.c_size_t, _P]),
+    "tvz_align_parts_sharded_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                                             C.c_int32]),
+    "tvz_align_parts_sharded": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, C.c_int64, C.c_int32,
+                                          C.c_double, C.c_double, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_size_t,
+                                          _P]),
     "tvz_read_records": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, _P,
                                    C.POINTER(C.c_int64)]),
     "tvz_read_stream": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int64, _P, C.POINTER(C.c_int64)]),

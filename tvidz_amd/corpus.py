@@ -185,6 +185,13 @@ def align_rates_topk_workspace_bytes(Q: int, max_query_len: int, total_query_key
     return form_workspace_bytes(FORM_RATES, Q, max_query_len, total_query_keys, k)
 
 
+def align_rates_topk_sharded_workspace_bytes(Q: int, max_query_len: int, total_query_keys: int = 0, k: int = 16,
+                                             n_ranks: int = 1) -> int:
+    """tvz_align_rates_topk_sharded_workspace_bytes: align_rates_topk_workspace_bytes + the local block and `n_ranks`
+    gathered ones (Q x (k + 1) x 20 bytes each)."""
+    return form_workspace_bytes(FORM_RATES, Q, max_query_len, total_query_keys, k, n_ranks)
+
+
 def align_rates_order_key(row, nv: int, contain: bool = False):
     """Sort key of one (video_id, row_len, best_bin, votes, rate_index) row of tvz_align_rates_topk:
     align_wide_order_key, then the rate's index."""
@@ -197,6 +204,13 @@ ALIGN_LOCAL = 2                             # include/tvz.h TVZ_ALIGN_LOCAL: tvz
 def align_span_topk_workspace_bytes(Q: int, max_query_len: int, total_query_keys: int = 0, k: int = 16) -> int:
     """tvz_align_span_topk_workspace_bytes: as align_wide_topk_workspace_bytes, with 32 bytes per kept hit."""
     return form_workspace_bytes(FORM_SPAN, Q, max_query_len, total_query_keys, k)
+
+
+def align_span_topk_sharded_workspace_bytes(Q: int, max_query_len: int, total_query_keys: int = 0, k: int = 16,
+                                            n_ranks: int = 1) -> int:
+    """tvz_align_span_topk_sharded_workspace_bytes: align_span_topk_workspace_bytes + the local block and `n_ranks`
+    gathered ones (Q x (k + 1) x 32 bytes each)."""
+    return form_workspace_bytes(FORM_SPAN, Q, max_query_len, total_query_keys, k, n_ranks)
 
 
 def align_local_score(votes: int, nq: int, nr: int) -> int:
@@ -237,6 +251,14 @@ def align_parts_workspace_bytes(Q: int, max_query_len: int, total_query_keys: in
                                                            int(max_parts)))
 
 
+def align_parts_sharded_workspace_bytes(Q: int, max_query_len: int, total_query_keys: int = 0, k: int = 16,
+                                        max_parts: int = ALIGN_MAX_PARTS, n_ranks: int = 1) -> int:
+    """tvz_align_parts_sharded_workspace_bytes: align_parts_workspace_bytes + the local answer and `n_ranks` gathered
+    ones (Q x k x (1 + max_parts) x 24 bytes each)."""
+    return int(_lib.load().tvz_align_parts_sharded_workspace_bytes(int(Q), int(max_query_len), int(total_query_keys),
+                                                                   int(k), int(max_parts), int(n_ranks)))
+
+
 def align_parts_ids(video_ids, Q: int, dev) -> torch.Tensor:
     """The ids of tvz_align_parts as a 2-D int32 tensor [Q, k] on `dev`: a device tensor (any strides) as it is, host
     lists or arrays copied once."""
@@ -267,6 +289,53 @@ def align_parts_merge(answers: np.ndarray) -> np.ndarray:
     out[refused, 0, 1:3] = 0
     out[refused, 0, 3] = ALIGN_REFUSED
     return out
+
+
+def align_parts_merge_device(gathered: torch.Tensor, stream: Optional[torch.cuda.Stream] = None,
+                             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """tvz_align_parts_merge: align_parts_merge on the device - the answers of R <= 16 shards to one align_parts call,
+    int32 [R, Q, k, 1 + P, 6] -> int32 [Q, k, 1 + P, 6], one launch on `stream` (default: the current one)."""
+    if gathered.dim() != 5 or gathered.shape[4] != 6 or gathered.dtype != torch.int32 or gathered.device.type != "cuda" \
+            or not gathered.is_contiguous():
+        raise RuntimeError("gathered must be a contiguous int32 CUDA tensor [R, Q, k, 1 + max_parts, 6]")
+    R, Q, k, rows, _ = gathered.shape
+    out = _out(out, (Q, k, rows, 6), gathered.device)
+    s = stream if stream is not None else torch.cuda.current_stream(gathered.device)
+    with torch.cuda.device(gathered.device):
+        _lib.check(_lib.load().tvz_align_parts_merge(gathered.data_ptr() if gathered.numel() else None, R, Q, k, rows - 1,
+                                                     out.data_ptr() if out.numel() else None, s.cuda_stream))
+    return out
+
+
+def _parts_ids(d_video_ids: torch.Tensor, Q: int, d_queries: torch.Tensor):
+    """The ids of a parts call as the library takes them: (pointer or None, id_stride, query_id_stride, k)."""
+    if d_video_ids.dim() != 2 or d_video_ids.shape[0] != Q or d_video_ids.dtype != torch.int32 \
+            or d_video_ids.device != d_queries.device:
+        raise RuntimeError(f"video_ids must be an int32 [{Q}, k] tensor on {d_queries.device}")
+    return (d_video_ids.data_ptr() if d_video_ids.numel() else None, int(d_video_ids.stride(1)), int(d_video_ids.stride(0)),
+            int(d_video_ids.shape[1]))
+
+
+def align_parts_shards(shards: Sequence["DeviceCorpus"], d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
+                       max_query_len: int, d_video_ids: torch.Tensor, *, eps: float, max_offset: Optional[float] = None,
+                       rates: Sequence[float] = (1.0,), min_votes: int, max_parts: int, workspace: torch.Tensor,
+                       stream: Optional[torch.cuda.Stream] = None):
+    """tvz_align_parts on every handle of ONE device + the merge behind one library call (tvz_align_parts_shards): ->
+    (blocks int32 [R, Q, k, 1 + max_parts, 6], parts int32 [Q, k, 1 + max_parts, 6]).  `workspace`:
+    align_parts_workspace_bytes (its size is the library's to judge, as align_topk_shards')."""
+    Q = d_q_offsets.numel() - 1
+    dev, s, ws, _ = shards[0]._prelude(d_queries, d_q_offsets, None, stream, workspace, None)
+    ids, id_stride, query_id_stride, k = _parts_ids(d_video_ids, Q, d_queries)
+    R, P = len(shards), int(max_parts)
+    handles = (C.c_void_p * R)(*[sh._h for sh in shards])
+    blocks = torch.empty((R, Q, k, 1 + max(P, 0), 6), dtype=torch.int32, device=dev)
+    parts = torch.empty((Q, k, 1 + max(P, 0), 6), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().tvz_align_parts_shards(
+            handles, R, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), ids, id_stride, query_id_stride,
+            k, float(eps), _wide_offset(eps, max_offset), *_rates(rates), int(min_votes), P, blocks.data_ptr(),
+            parts.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
+    return blocks, parts
 
 
 def _rates(rates):
@@ -546,16 +615,13 @@ class DeviceCorpus:
         """tvz_align_parts, device in / device out: enqueue Q x k pairs -> int32 [Q, k, 1 + max_parts, 6].
         `d_video_ids`: a 2-D int32 view [Q, k] on this device, of any strides."""
         Q = d_q_offsets.numel() - 1
-        if d_video_ids.dim() != 2 or d_video_ids.shape[0] != Q or d_video_ids.dtype != torch.int32 \
-                or d_video_ids.device != d_queries.device:
-            raise RuntimeError(f"video_ids must be an int32 [{Q}, k] tensor on {d_queries.device}")
-        k, P = int(d_video_ids.shape[1]), int(max_parts)
+        ids, id_stride, query_id_stride, k = _parts_ids(d_video_ids, Q, d_queries)
+        P = int(max_parts)
         dev, s, ws, _ = self._prelude(d_queries, d_q_offsets, None, stream, workspace,
                                       align_parts_workspace_bytes(Q, max_query_len, d_queries.numel(), k, P))
         out = _out(out, (Q, k, 1 + max(P, 0), 6), dev)
         _lib.check(self.lib.tvz_align_parts(self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len),
-                                            d_video_ids.data_ptr() if d_video_ids.numel() else None,
-                                            int(d_video_ids.stride(1)), int(d_video_ids.stride(0)), k, float(eps),
+                                            ids, id_stride, query_id_stride, k, float(eps),
                                             _wide_offset(eps, max_offset), *_rates(rates), int(min_votes), P,
                                             out.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
         return out
@@ -756,6 +822,50 @@ class Comm:
         return self.align_sharded(FORM_WIDE, corpus, d_queries, d_q_offsets, max_query_len, k, d_exclude_ids, workspace,
                                    stream, out, eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score,
                                    contain=contain)
+
+    def align_rates_topk_sharded(self, corpus: DeviceCorpus, d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
+                                 max_query_len: int, *, eps: float, rates: Sequence[float], max_offset: Optional[float] = None,
+                                 k: int, min_votes: int = 1, min_score: int = 0, contain: bool = False,
+                                 d_exclude_ids: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                                 stream: Optional[torch.cuda.Stream] = None,
+                                 out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+        """tvz_align_rates_topk_sharded: the local alignment top-k with rates -> ncclAllGather of the [Q,k+1,5] blocks ->
+        its merge; -> (rows int32 [Q,k,5], totals int32 [Q]), identical on every rank."""
+        return self.align_sharded(FORM_RATES, corpus, d_queries, d_q_offsets, max_query_len, k, d_exclude_ids, workspace,
+                                   stream, out, eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score,
+                                   rates=rates, contain=contain)
+
+    def align_span_topk_sharded(self, corpus: DeviceCorpus, d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
+                                max_query_len: int, *, eps: float, rates: Sequence[float] = (1.0,),
+                                max_offset: Optional[float] = None, k: int, min_votes: int = 1, min_score: int = 0,
+                                contain: bool = False, local: bool = False, d_exclude_ids: Optional[torch.Tensor] = None,
+                                workspace: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
+                                out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+        """tvz_align_span_topk_sharded: the local alignment top-k with spans -> ncclAllGather of the [Q,k+1,8] blocks ->
+        its merge; -> (rows int32 [Q,k,8], totals int32 [Q]), identical on every rank."""
+        return self.align_sharded(FORM_SPAN, corpus, d_queries, d_q_offsets, max_query_len, k, d_exclude_ids, workspace,
+                                   stream, out, eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score,
+                                   rates=rates, contain=contain, local=local)
+
+    def align_parts_sharded(self, corpus: DeviceCorpus, d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
+                            max_query_len: int, d_video_ids: torch.Tensor, *, eps: float, max_offset: Optional[float] = None,
+                            rates: Sequence[float] = (1.0,), min_votes: int, max_parts: int,
+                            workspace: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
+                            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """tvz_align_parts_sharded: the local align_parts -> ncclAllGather of the [Q, k, 1 + max_parts, 6] answers -> the
+        merge; -> int32 [Q, k, 1 + max_parts, 6], identical on every rank."""
+        Q = d_q_offsets.numel() - 1
+        ids, id_stride, query_id_stride, k = _parts_ids(d_video_ids, Q, d_queries)
+        P = int(max_parts)
+        dev, s, ws, _ = corpus._prelude(d_queries, d_q_offsets, None, stream, workspace,
+                                        align_parts_sharded_workspace_bytes(Q, max_query_len, d_queries.numel(), k, P,
+                                                                            self.n_ranks))
+        out = _out(out, (Q, k, 1 + max(P, 0), 6), dev)
+        _lib.check(self.lib.tvz_align_parts_sharded(
+            corpus._h, self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), ids, id_stride,
+            query_id_stride, k, float(eps), _wide_offset(eps, max_offset), *_rates(rates), int(min_votes), P, out.data_ptr(),
+            ws.data_ptr(), ws.numel(), s.cuda_stream))
+        return out
 
     def align_sharded(self, f: AlignForm, corpus, d_queries, d_q_offsets, max_query_len, k, d_exclude_ids, workspace, stream,
                        out, **ask):

@@ -33,9 +33,13 @@
 //                            tie (the slots fill in no fixed order: the row's index decides), is copied out with
 //                            n_rows and m in its header and zeros behind n_parts; or the refused / absent / no-pair
 //                            form is written.
+// And, for a table in shards, one more launch behind the shards' calls (tvz_align_parts_merge):
+//   ts_alignp_merge_kernel   a 16-lane group per pair, a lane per shard's answer: the answer with the most part-0 votes
+//                            among the shards that hold a row of the id, n_rows summed, a refusal kept.
 // No scratch memory, no block barrier inside a row walk; global memory is written with vector stores only.
 #pragma once
 #include "tvz_align_kernels.h"
+#include "tvz_wave.h"
 
 namespace {
 
@@ -332,6 +336,47 @@ __global__ __launch_bounds__(kApPickBlock) void ts_alignp_pick_kernel(
         v = lane == 5 ? m : v;
         v = lane >= kApCols && lane / kApCols - 1 >= n_parts ? 0 : v;
         out[lane] = v;
+    }
+}
+
+// The shards' answers to ONE tvz_align_parts call -> one answer (tvz_align_parts_merge, include/tvz.h).  grid =
+// ceil(Q * k / kApMergeGroups), a 16-lane group per pair, lane = list: gathered int32[n_lists][pairs][words] -> d_parts
+// int32[pairs][words], words = ap_words(max_parts).  Per pair the winner is, among the lists whose n_rows > 0, the one
+// with the most part-0 votes, the lower list on a tie, and list 0 where no list holds a row: one signed 64-bit key per
+// lane, (votes + 1 or 0) * 16 + (15 - list), and its maximum over the group (lanes without a list hold the smallest
+// key).  n_rows is summed in 64 bits and saturates; one refused list refuses the pair.  A block is words x 4 bytes, 48
+// to 120: every access is one 32-bit word.  1 <= n_lists <= 16, 1 <= max_parts <= kApMaxParts.
+constexpr int kApMergeBlock = 256;
+constexpr int kApMergeGroups = kApMergeBlock / 16;     // pairs per block: a group each
+__global__ __launch_bounds__(kApMergeBlock) void ts_alignp_merge_kernel(const int32_t *__restrict__ gathered, int32_t n_lists,
+                                                                        int64_t pairs, int32_t max_parts,
+                                                                        int32_t *__restrict__ d_parts) {
+    const int list = threadIdx.x & 15;
+    const int64_t pair = (int64_t)blockIdx.x * kApMergeGroups + (threadIdx.x >> 4);
+    if (pair >= pairs) return;                                            // group-uniform: the moves below stay inside a group
+    const int words = ap_words(max_parts);                                // <= 30: two words per lane
+    const bool has_list = list < n_lists;
+    const int32_t *mine = gathered + ((int64_t)(has_list ? list : 0) * pairs + pair) * words;
+    const int32_t n_rows = has_list ? mine[4] : 0;
+    const int32_t votes = has_list ? mine[kApCols + 1] : 0;
+    const uint32_t is_refused = has_list && mine[3] == INT32_MIN ? 1u : 0u;
+    long long key = has_list ? (n_rows > 0 ? (long long)votes + 1 : 0ll) * 16 + (15 - list) : INT64_MIN;
+    long long total = n_rows;
+#define TVZ_AP_MERGE_STEP(C) { const long long ok = (long long)dpp16_64<C>((unsigned long long)key); \
+    key = ok > key ? ok : key; total += (long long)dpp16_64<C>((unsigned long long)total); }
+    TVZ_ROW16_BUTTERFLY(TVZ_AP_MERGE_STEP)
+#undef TVZ_AP_MERGE_STEP
+    const bool refused = group16_sum<uint32_t>(is_refused) != 0u;
+    const int winner = 15 - (int)(key & 15);                              // (the low four bits, whatever the key's sign)
+    const int32_t n_sum = total > (long long)INT32_MAX ? INT32_MAX : (int32_t)total;
+    const int32_t *src = gathered + ((int64_t)winner * pairs + pair) * words;
+    int32_t *out = d_parts + pair * words;
+    for (int w = list; w < words; w += 16) {
+        int32_t v = src[w];
+        v = refused && w != 0 && w != 5 ? 0 : v;                          // a refused pair keeps the winner's id and m
+        v = refused && w == 3 ? INT32_MIN : v;
+        v = w == 4 ? n_sum : v;
+        out[w] = v;
     }
 }
 

@@ -11,6 +11,7 @@
 // other than Python gets the whole multi-GPU path from this library alone.
 #include <dlfcn.h>
 
+#include <algorithm>
 #include <mutex>
 
 #include "tvz_common.h"
@@ -127,7 +128,7 @@ static int tvz_comm_destroy_impl(tvz_comm *comm) {
 }
 
 // The exchange behind a local per-shard top-k: ONE ncclAllGather of the ranks' blocks of `count` int32 (Q x (k+1) rows
-// of 3, of 4 for the alignment top-k) on `hip_stream`, ordered behind the communicator's previous collective, then
+// of 3, of the form's 4, 5 or 8 for the alignment top-k; Q x k answers for the parts call) on `hip_stream`, ordered behind the communicator's previous collective, then
 // `merge`, which every rank runs alike on the gathered blocks.
 template <typename Merge>
 static int gather_and_merge(tvz_comm *comm, const int32_t *local, int32_t *gathered, size_t count, void *hip_stream,
@@ -201,24 +202,68 @@ static int tvz_match_tol_sharded_impl(tvz_corpus *c, tvz_comm *comm, const doubl
     return gather_and_merge_topk(comm, blk, Q, k, d_topk, d_totals, hip_stream);
 }
 
-// The alignment top-k forms that have an RCCL form (tvz_align_topk_sharded: flags = 0; tvz_align_wide_topk_sharded): the
-// local sweep keeps its k best itself and writes them into the workspace's own block, then the gather and the form's
-// merge.  Both forms' block rows have 4 columns.
-static int align_topk_sharded_impl(AlignForm form, tvz_corpus *c, tvz_comm *comm, const Batch &b, const AlignCall &a,
-                                   uint32_t flags, int32_t k, int32_t *d_topk, int32_t *d_totals, Workspace ws,
-                                   void *hip_stream) {
+// What the sharded alignment calls refuse of their communicator and of the merge's outputs.
+struct AlignCommCheck {
+    const tvz_comm *comm;
+    int32_t Q;
+    const int32_t *d_rows, *d_totals;    // the merge's outputs (d_totals: NULL for the parts call, which has none)
+    bool with_totals, aligned16;
+};
+static int check_align_comm(const void *ctx) {
+    const AlignCommCheck &s = *static_cast<const AlignCommCheck *>(ctx);
+    TVZ_REQUIRE(s.comm != nullptr && s.comm->comm != nullptr, "communicator is NULL");
+    if (s.with_totals)
+        TVZ_REQUIRE(s.Q <= 0 || (s.d_rows != nullptr && s.d_totals != nullptr), "d_topk or d_totals is NULL");
+    else
+        TVZ_REQUIRE(s.Q <= 0 || s.d_rows != nullptr, "d_parts is NULL");
+    TVZ_REQUIRE(!s.aligned16 || (reinterpret_cast<uintptr_t>(s.d_rows) & 15) == 0, "d_topk must be 16-byte aligned");
+    if (s.comm->n_ranks > 16)        // (the merge's limit: refused before the local call enqueues anything)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment top-k: %d ranks, the merge takes up to 16", (int)s.comm->n_ranks);
+    return TVZ_OK;
+}
+
+// The alignment top-k's RCCL forms (tvz_<stem>_sharded of every entry of kAlignForms): the local sweep keeps its k best
+// itself and writes them into the workspace's own block, then the gather of Q x (k + 1) rows of the form's width and the
+// form's merge.  `comm_first`: the bounded and the wide form refuse their communicator before anything else; the forms
+// with rates make the unsharded call's refusals first, in its order and words, and the communicator's behind them -
+// either way before anything is enqueued.
+static int align_topk_sharded_impl(AlignForm form, bool comm_first, tvz_corpus *c, tvz_comm *comm, const Batch &b,
+                                   const AlignCall &a, const double *h_rates, int32_t n_rates, uint32_t flags, int32_t k,
+                                   int32_t *d_topk, int32_t *d_totals, Workspace ws, void *hip_stream) {
     const int32_t Q = b.Q;
-    TVZ_REQUIRE(comm != nullptr && comm->comm != nullptr, "communicator is NULL");
-    TVZ_REQUIRE(Q <= 0 || (d_topk != nullptr && d_totals != nullptr), "d_topk or d_totals is NULL");
-    TVZ_REQUIRE((reinterpret_cast<uintptr_t>(d_topk) & 15) == 0, "d_topk must be 16-byte aligned");
-    if (comm->n_ranks > 16)          // (the merge's limit: refused here, before the local sweep is enqueued)
-        return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment top-k: %d ranks, the merge takes up to 16", (int)comm->n_ranks);
+    const AlignCommCheck chk{comm, Q, d_topk, d_totals, true, true};
+    if (comm_first)
+        if (int rc = check_align_comm(&chk)) return rc;
+    // (a NULL communicator is sized as one rank until it is refused)
+    const int32_t n_ranks = comm ? std::max<int32_t>(comm->n_ranks, 1) : 1;
     ShardBlocks blk;
-    if (int rc = tvz_align_topk_local(form, c, b, a, flags, k, nullptr, ws, comm->n_ranks, hip_stream, &blk)) return rc;
+    if (int rc = tvz_align_topk_local(form, c, b, a, h_rates, n_rates, flags, k, nullptr, ws, n_ranks, hip_stream, &blk,
+                                      LateCheck{check_align_comm, &chk}))
+        return rc;
+    if (int rc = check_align_comm(&chk)) return rc;          // (Q = 0: the local call returned in front of its late checks)
     if (Q == 0) return TVZ_OK;
-    return gather_and_merge(comm, blk.local, blk.gathered, (size_t)Q * (size_t)(k + 1) * 4, hip_stream, [&] {
+    const size_t cols = (size_t)tvz_align_form_cols(form);
+    return gather_and_merge(comm, blk.local, blk.gathered, (size_t)Q * (size_t)(k + 1) * cols, hip_stream, [&] {
         return tvz_align_merge_local(form, blk.gathered, comm->n_ranks, Q, k, flags, b.d_queries, b.d_q_offsets, d_topk,
                                      d_totals, hip_stream);
+    });
+}
+
+// tvz_align_parts_sharded: the local call into the workspace's own block, ONE all-gather of Q x k x (1 + max_parts) x 6
+// int32, the merge.  The call's own refusals come first, the communicator's behind them.
+static int align_parts_sharded_impl(tvz_corpus *c, tvz_comm *comm, const Batch &b, const AlignPartsCall &p, int32_t *d_parts,
+                                    Workspace ws, void *hip_stream) {
+    const int32_t Q = b.Q;
+    const AlignCommCheck chk{comm, Q, d_parts, nullptr, false, false};
+    const int32_t n_ranks = comm ? std::max<int32_t>(comm->n_ranks, 1) : 1;
+    ShardBlocks blk;
+    if (int rc = tvz_align_parts_local(c, b, p, nullptr, ws, n_ranks, hip_stream, &blk, LateCheck{check_align_comm, &chk}))
+        return rc;
+    if (int rc = check_align_comm(&chk)) return rc;
+    if (Q == 0) return TVZ_OK;
+    const size_t count = (size_t)Q * (size_t)p.k * (size_t)(1 + p.max_parts) * 6;
+    return gather_and_merge(comm, blk.local, blk.gathered, count, hip_stream, [&] {
+        return tvz_align_parts_merge_local(blk.gathered, comm->n_ranks, Q, p.k, p.max_parts, d_parts, hip_stream);
     });
 }
 
@@ -257,9 +302,9 @@ TVZ_EXPORT int tvz_align_topk_sharded(tvz_corpus *c, tvz_comm *comm, const doubl
                                       int32_t Q, int32_t max_query_len, double eps, double max_offset, int32_t min_votes,
                                       int32_t min_score, const int32_t *d_exclude_ids, int32_t k, int32_t *d_topk,
                                       int32_t *d_totals, void *d_workspace, size_t workspace_bytes, void *hip_stream) {
-    TVZ_GUARDED(align_topk_sharded_impl(kAlignBounded, c, comm,
+    TVZ_GUARDED(align_topk_sharded_impl(kAlignBounded, /* comm_first */ true, c, comm,
                                         Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids},
-                                        AlignCall{eps, max_offset, min_votes, min_score}, 0u, k, d_topk, d_totals,
+                                        AlignCall{eps, max_offset, min_votes, min_score}, nullptr, 0, 0u, k, d_topk, d_totals,
                                         Workspace{d_workspace, workspace_bytes}, hip_stream));
 }
 
@@ -268,8 +313,43 @@ TVZ_EXPORT int tvz_align_wide_topk_sharded(tvz_corpus *c, tvz_comm *comm, const 
                                            double max_offset, int32_t min_votes, int32_t min_score, uint32_t flags,
                                            const int32_t *d_exclude_ids, int32_t k, int32_t *d_topk, int32_t *d_totals,
                                            void *d_workspace, size_t workspace_bytes, void *hip_stream) {
-    TVZ_GUARDED(align_topk_sharded_impl(kAlignWide, c, comm,
+    TVZ_GUARDED(align_topk_sharded_impl(kAlignWide, /* comm_first */ true, c, comm,
                                         Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids},
-                                        AlignCall{eps, max_offset, min_votes, min_score}, flags, k, d_topk, d_totals,
+                                        AlignCall{eps, max_offset, min_votes, min_score}, nullptr, 0, flags, k, d_topk, d_totals,
                                         Workspace{d_workspace, workspace_bytes}, hip_stream));
+}
+
+TVZ_EXPORT int tvz_align_rates_topk_sharded(tvz_corpus *c, tvz_comm *comm, const double *d_queries,
+                                            const int64_t *d_q_offsets, int32_t Q, int32_t max_query_len, double eps,
+                                            double max_offset, const double *h_rates, int32_t n_rates, int32_t min_votes,
+                                            int32_t min_score, uint32_t flags, const int32_t *d_exclude_ids, int32_t k,
+                                            int32_t *d_topk, int32_t *d_totals, void *d_workspace, size_t workspace_bytes,
+                                            void *hip_stream) {
+    TVZ_GUARDED(align_topk_sharded_impl(kAlignRates, /* comm_first */ false, c, comm,
+                                        Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids},
+                                        AlignCall{eps, max_offset, min_votes, min_score}, h_rates, n_rates, flags, k, d_topk,
+                                        d_totals, Workspace{d_workspace, workspace_bytes}, hip_stream));
+}
+
+TVZ_EXPORT int tvz_align_span_topk_sharded(tvz_corpus *c, tvz_comm *comm, const double *d_queries,
+                                           const int64_t *d_q_offsets, int32_t Q, int32_t max_query_len, double eps,
+                                           double max_offset, const double *h_rates, int32_t n_rates, int32_t min_votes,
+                                           int32_t min_score, uint32_t flags, const int32_t *d_exclude_ids, int32_t k,
+                                           int32_t *d_topk, int32_t *d_totals, void *d_workspace, size_t workspace_bytes,
+                                           void *hip_stream) {
+    TVZ_GUARDED(align_topk_sharded_impl(kAlignSpan, /* comm_first */ false, c, comm,
+                                        Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, d_exclude_ids},
+                                        AlignCall{eps, max_offset, min_votes, min_score}, h_rates, n_rates, flags, k, d_topk,
+                                        d_totals, Workspace{d_workspace, workspace_bytes}, hip_stream));
+}
+
+TVZ_EXPORT int tvz_align_parts_sharded(tvz_corpus *c, tvz_comm *comm, const double *d_queries, const int64_t *d_q_offsets,
+                                       int32_t Q, int32_t max_query_len, const int32_t *d_video_ids, int64_t id_stride,
+                                       int64_t query_id_stride, int32_t k, double eps, double max_offset,
+                                       const double *h_rates, int32_t n_rates, int32_t min_votes, int32_t max_parts,
+                                       int32_t *d_parts, void *d_workspace, size_t workspace_bytes, void *hip_stream) {
+    TVZ_GUARDED(align_parts_sharded_impl(c, comm, Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0, nullptr},
+                                         AlignPartsCall{d_video_ids, id_stride, query_id_stride, k, eps, max_offset, h_rates,
+                                                        n_rates, min_votes, max_parts},
+                                         d_parts, Workspace{d_workspace, workspace_bytes}, hip_stream));
 }

@@ -82,7 +82,8 @@ struct AlignCall {                   // what an alignment top-k call asks of a (
 };
 struct ShardBlocks {                 // where a local top-k left its block, and the all-gather's target next to it
     int32_t *local = nullptr;        // int32[Q][k+1][3]: d_out, or the workspace's own area for d_out = NULL
-    int32_t *gathered = nullptr;     // int32[n_ranks][Q][k+1][3] in the workspace  (rows of 4 for the alignment top-k)
+    int32_t *gathered = nullptr;     // int32[n_ranks][Q][k+1][3] in the workspace  (rows of the form's width for the
+                                     // alignment top-k; [n_ranks][Q][k][1 + max_parts][6] for the parts call)
 };
 
 // Internal (not exported): local sweep + per-shard top-k with the hit lists in the workspace (tvz_match.hip);
@@ -94,11 +95,36 @@ int tvz_match_tol_topk_local(tvz_corpus *c, const Batch &b, double tol, int32_t 
                              int32_t n_ranks, void *hip_stream, ShardBlocks *blocks);
 // The forms of the alignment top-k, in the order of tvz_match.hip's table kAlignForms, which says what each one is.
 enum AlignForm { kAlignBounded, kAlignWide, kAlignRates, kAlignSpan, kAlignFormCount };
+// What a sharded call still has to refuse once the local call has made all of its own refusals and before it enqueues
+// anything: the communicator's (tvz_comm.hip).  fn = NULL: nothing.
+struct LateCheck {
+    int (*fn)(const void *ctx) = nullptr;
+    const void *ctx = nullptr;
+    int operator()() const { return fn ? fn(ctx) : TVZ_OK; }
+};
 // A form's call (tvz_match.hip): n_ranks = 0 is the call of the C ABI, whose workspace holds no blocks; n_ranks >= 1 is
-// the workspace of the form's sharded sizing function.  `flags`: 0 for the form that has none.
-int tvz_align_topk_local(AlignForm form, tvz_corpus *c, const Batch &b, const AlignCall &a, uint32_t flags, int32_t k,
-                         int32_t *d_out, Workspace ws, int32_t n_ranks, void *hip_stream, ShardBlocks *blocks);
+// the workspace of the form's sharded sizing function.  `flags`: 0 for the form that has none; `h_rates`, `n_rates`:
+// NULL, 0 for the forms without a rate list.
+int tvz_align_topk_local(AlignForm form, tvz_corpus *c, const Batch &b, const AlignCall &a, const double *h_rates,
+                         int32_t n_rates, uint32_t flags, int32_t k, int32_t *d_out, Workspace ws, int32_t n_ranks,
+                         void *hip_stream, ShardBlocks *blocks, LateCheck late = {});
+// ... the int32 columns of a row of its block ...
+int tvz_align_form_cols(AlignForm form);
 // ... and the merge of its gathered blocks.
 int tvz_align_merge_local(AlignForm form, const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t k, uint32_t flags,
                           const double *d_queries, const int64_t *d_q_offsets, int32_t *d_topk, int32_t *d_totals,
                           void *hip_stream);
+// tvz_align_parts with the sharded form's blocks in its workspace (n_ranks >= 1, d_parts = NULL: the answer goes into
+// the workspace's own block), and the merge of the gathered answers (tvz_match.hip).
+struct AlignPartsCall {
+    const int32_t *d_video_ids;
+    int64_t id_stride, query_id_stride;
+    int32_t k;
+    double eps, max_offset;
+    const double *h_rates;
+    int32_t n_rates, min_votes, max_parts;
+};
+int tvz_align_parts_local(tvz_corpus *c, const Batch &b, const AlignPartsCall &p, int32_t *d_parts, Workspace ws, int32_t n_ranks,
+                          void *hip_stream, ShardBlocks *blocks, LateCheck late = {});
+int tvz_align_parts_merge_local(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t k, int32_t max_parts,
+                                int32_t *d_parts, void *hip_stream);

@@ -2066,7 +2066,10 @@ struct AlignTopkForm {
     bool takes_rates;                // the call has a rate list (check_align_rates)
     bool limits_first;               // the flags and the limits are refused before the handle is looked at
     const char *what, *sizer;        // the call in messages; the sizing function the workspace message names
-    const char *sharded_sizer;       // ... and the one it names for the sharded form (n_ranks >= 1); NULL: no RCCL form
+    const char *sharded_sizer;       // ... and the one it names for the sharded form (n_ranks >= 1) of the bounded and the
+                                     // wide form; NULL for the forms with rates, whose RCCL calls came later: the host
+                                     // program that walks this table's layouts (tests/align_sharded_host_main.hip) sizes
+                                     // exactly the forms that have one here, so theirs is `rccl_sizer` below
     int32_t max_bins;                // 2B + 1 at most
     const char *bins_limit;          // the header's name of that limit, if it has one (check_align_bins)
     uint32_t flags;                  // the permitted ones
@@ -2075,6 +2078,9 @@ struct AlignTopkForm {
     void (*sweep)(const AlignLaunch &);
     void (*reduce)(const AlignLaunch &);
     void (*merge)(const AlignMergeArgs &);
+    const char *rccl_sizer = nullptr;  // the sharded sizing function of a form with rates (see sharded_sizer)
+    // the sizing function a workspace refusal of the sharded form names
+    constexpr const char *sharded_name() const { return sharded_sizer ? sharded_sizer : rccl_sizer; }
 };
 
 AlignTopkWs align_topk_ws_layout(Carver &cv, const AlignTopkForm &f, int32_t Q, int32_t k, int32_t n_blocks) {
@@ -2151,7 +2157,8 @@ constexpr AlignTopkForm kAlignForms[] = {
      [](const AlignMergeArgs &m) {
          hipLaunchKernelGGL(ts_alignr_merge_kernel, m.grid, dim3(kAlMergeBlock), 0, m.st, m.d_gathered, m.n_lists, m.Q, m.k,
                             m.flags, m.d_queries, m.d_q_offsets, m.d_topk, m.d_totals);
-     }},
+     },
+     "tvz_align_rates_topk_sharded_workspace_bytes"},
     // kAlignSpan: tvz_align_span_topk - the call with rates and the span pass
     {8, 4, true, true, "alignment top-k with spans", "tvz_align_span_topk_workspace_bytes", nullptr, 2 * kAwMaxB + 1,
      "TVZ_ALIGN_WIDE_MAX_B", kAwContain | kAsLocal, kAwContain | kAsLocal, al_static_lds<AsHit>(),
@@ -2169,7 +2176,8 @@ constexpr AlignTopkForm kAlignForms[] = {
      [](const AlignMergeArgs &m) {
          hipLaunchKernelGGL(ts_aligns_merge_kernel, m.grid, dim3(kAlMergeBlock), 0, m.st, m.d_gathered, m.n_lists, m.Q, m.k,
                             m.flags, m.d_queries, m.d_q_offsets, m.d_topk, m.d_totals);
-     }},
+     },
+     "tvz_align_span_topk_sharded_workspace_bytes"},
 };
 static_assert(sizeof(kAlignForms) / sizeof(kAlignForms[0]) == kAlignFormCount, "one entry per AlignForm, in its order");
 
@@ -2238,12 +2246,12 @@ struct AlignLds {
 // One handle: sort -> sweep that keeps the k best -> per-query selection.  `rates`: checked (check_align_early).
 // n_ranks = 0: d_out is the caller's.  n_ranks >= 1: the workspace also holds the local block and n_ranks gathered ones
 // (the form's sharded sizing function); d_out = NULL writes the block into the workspace's own, and `blocks` is told
-// where it went and where the all-gather's target is.
+// where it went and where the all-gather's target is.  `late`: the sharded call's own refusals, made behind all of
+// these and in front of the first launch.
 int align_topk_run(const AlignTopkForm &f, tvz_corpus *c, const Batch &b, const AlignAsk &s, const AlRates &rates,
-                   int32_t *d_out, Workspace ws, int32_t n_ranks, void *hip_stream, ShardBlocks *blocks) {
+                   int32_t *d_out, Workspace ws, int32_t n_ranks, void *hip_stream, ShardBlocks *blocks, LateCheck late = {}) {
     const AlignCall &a = s.a;
     const int32_t Q = b.Q, max_query_len = b.max_query_len, k = s.k;
-    TVZ_REQUIRE(n_ranks == 0 || f.sharded_sizer != nullptr, "%s: it has no sharded form", f.what);
     if (int rc = check_batch_args(c, b, 0)) return rc;
     int32_t B = 0;
     if (int rc = check_align_bins(a.eps, a.max_offset, f.max_bins, f.bins_limit, &B)) return rc;
@@ -2259,14 +2267,14 @@ int align_topk_run(const AlignTopkForm &f, tvz_corpus *c, const Batch &b, const 
         if (blocks) *blocks = ShardBlocks{d_out, w.gathered};
         TVZ_REQUIRE(lds.fits(f.static_lds), "%s sweep: %zu B of dynamic + %d B of static LDS exceed a gfx950 workgroup's", f.what,
                     lds.bytes, f.static_lds);
-        return TVZ_OK;
+        return late();
     };
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
     // the fixed parts and room for ONE query of max_query_len values; what the caller gave beyond that holds more
     // (the sorted positions are unused here)
     TolCall t;
     if (int rc = tol_prelude(c, b, TolFront{cv, cv.fixed(), w.totals, f.what,
-                                            n_ranks > 0 ? f.sharded_sizer : f.sizer},
+                                            n_ranks > 0 ? f.sharded_name() : f.sizer},
                              ws.p ? ws.bytes : 0, max_query_len, st, args_ok, t))
         return rc;
     const int64_t n_rows = t.n_rows;
@@ -2285,11 +2293,11 @@ int align_topk_run(const AlignTopkForm &f, tvz_corpus *c, const Batch &b, const 
 
 // A call of the C ABI: what the form refuses early, then the handle.
 int align_topk_call(AlignForm form, tvz_corpus *c, const Batch &b, const AlignAsk &s, int32_t *d_out, Workspace ws,
-                    int32_t n_ranks, void *hip_stream, ShardBlocks *blocks) {
+                    int32_t n_ranks, void *hip_stream, ShardBlocks *blocks, LateCheck late = {}) {
     const AlignTopkForm &f = kAlignForms[form];
     AlRates rates{};
     if (int rc = check_align_early(f, s, b.max_query_len, &rates)) return rc;
-    return align_topk_run(f, c, b, s, rates, d_out, ws, n_ranks, hip_stream, blocks);
+    return align_topk_run(f, c, b, s, rates, d_out, ws, n_ranks, hip_stream, blocks, late);
 }
 
 // The shards of one process, for any form: every handle's call into its block of d_blocks, then the merge.
@@ -2335,63 +2343,91 @@ size_t align_sizing(AlignForm form, int32_t Q, int32_t max_query_len, int64_t to
 // ---- every aligned part of a named stored video (tvz_align_parts; tvz_align_parts_kernels.h) ----------------------
 // Workspace in front of the sorted queries (TolWs, which takes the rest): per pair the count of rows that carry its id,
 // the candidate slots' row indices and every slot's result.
+// The sharded form (n_blocks > 0: the communicator's ranks, at least 1) adds the local answer and the gathered ones
+// behind them, as the alignment top-k's sharded forms do; the plain call and the _shards form (n_blocks = 0) have neither.
 struct AlignPartsWs {
     int32_t *counts = nullptr;             // [Q][k]
     int64_t *slots = nullptr;              // [Q][k][kApMaxRows]
     int32_t *scratch = nullptr;            // [Q][k][kApMaxRows][1 + max_parts][6]
+    int32_t *local = nullptr;              // [Q][k][1 + max_parts][6]
+    int32_t *gathered = nullptr;           // [n_blocks][Q][k][1 + max_parts][6]
 };
 
-AlignPartsWs align_parts_ws_layout(Carver &cv, int32_t Q, int32_t k, int32_t max_parts) {
+AlignPartsWs align_parts_ws_layout(Carver &cv, int32_t Q, int32_t k, int32_t max_parts, int32_t n_blocks = 0) {
     AlignPartsWs w;
     const size_t pairs = (size_t)Q * (size_t)k;
     w.counts = cv.take<int32_t>(pairs);
     w.slots = cv.take<int64_t>(pairs * kApMaxRows);
     w.scratch = cv.take<int32_t>(pairs * kApMaxRows * (size_t)ap_words(max_parts));
+    if (n_blocks > 0) {
+        const size_t block = pairs * (size_t)ap_words(max_parts);
+        w.local = cv.take<int32_t>(block);
+        w.gathered = cv.take<int32_t>((size_t)n_blocks * block);
+    }
     return w;
 }
 
-size_t align_parts_ws_bytes(int32_t Q, int64_t keys, int32_t k, int32_t max_parts) {
+size_t align_parts_ws_bytes(int32_t Q, int64_t keys, int32_t k, int32_t max_parts, int32_t n_blocks) {
     Carver cv(nullptr);
-    align_parts_ws_layout(cv, Q, k, max_parts);
+    align_parts_ws_layout(cv, Q, k, max_parts, n_blocks);
     return cv.fixed() + tol_ws_bytes(Q, keys);
 }
 
-// The call in messages and limits: no entry of kAlignForms (it keeps no hit and has no block), only what the shared
-// checks read of one - the name, the sizing function and the bins' limit.
-constexpr AlignTopkForm kAlignPartsForm = {kApCols, 0, true, true, "alignment parts", "tvz_align_parts_workspace_bytes", nullptr,
-                                           2 * kAwMaxB + 1, "TVZ_ALIGN_WIDE_MAX_B", 0u, 0u, 0, nullptr, nullptr, nullptr};
+// what the two sizing exports share: the argument refusals, the `keys` default and the room for one longest query
+size_t align_parts_sizing(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k, int32_t max_parts,
+                          int32_t n_blocks) {
+    if (Q < 0 || max_query_len < 0 || total_query_keys < 0 || k < 1 || max_parts < 1 || max_parts > kApMaxParts) return 0;
+    const int64_t keys = total_query_keys > 0 ? total_query_keys : (int64_t)Q * max_query_len;
+    return align_parts_ws_bytes(Q, std::max<int64_t>(keys, max_query_len), k, max_parts, n_blocks);
+}
 
-// sort -> locate the ids' rows -> walk every (pair, candidate row) -> pick per pair.  Everything that needs neither
-// the handle nor the device is refused first, in the span call's order: the rate list, min_votes, k, the query limit;
-// then max_parts and the bins.
-int align_parts_impl(tvz_corpus *c, const Batch &b, const int32_t *d_video_ids, int64_t id_stride, int64_t query_id_stride,
-                     int32_t k, double eps, double max_offset, const double *h_rates, int32_t n_rates, int32_t min_votes,
-                     int32_t max_parts, int32_t *d_parts, Workspace ws, void *hip_stream) {
+// The call in messages and limits: no entry of kAlignForms (it keeps no hit), only what the shared checks read of one -
+// the name, the two sizing functions and the bins' limit.
+constexpr AlignTopkForm kAlignPartsForm = {kApCols, 0, true, true, "alignment parts", "tvz_align_parts_workspace_bytes",
+                                           "tvz_align_parts_sharded_workspace_bytes", 2 * kAwMaxB + 1, "TVZ_ALIGN_WIDE_MAX_B", 0u,
+                                           0u, 0, nullptr, nullptr, nullptr};
+
+// Everything of a parts call that needs neither the handle nor the device is refused first, for the call and for its
+// _shards and _sharded forms alike, in the span call's order: the rate list (-> *rates), min_votes, k, the query limit;
+// then max_parts and the bins (-> *B).
+int check_align_parts_early(const Batch &b, const AlignPartsCall &p, AlRates *rates, int32_t *B) {
     const AlignTopkForm &f = kAlignPartsForm;
-    const int32_t Q = b.Q, max_query_len = b.max_query_len;
-    AlRates rates{};
-    if (int rc = check_align_rates(h_rates, n_rates, &rates)) return rc;
-    if (int rc = check_align_limits(f, AlignCall{eps, max_offset, min_votes, 0}, k, max_query_len)) return rc;
-    if (max_parts < 1 || max_parts > kApMaxParts)
-        return tvz::fail(TVZ_ERR_UNSUPPORTED, "%s: max_parts=%d outside 1..%d (TVZ_ALIGN_MAX_PARTS)", f.what, (int)max_parts,
+    if (int rc = check_align_rates(p.h_rates, p.n_rates, rates)) return rc;
+    if (int rc = check_align_limits(f, AlignCall{p.eps, p.max_offset, p.min_votes, 0}, p.k, b.max_query_len)) return rc;
+    if (p.max_parts < 1 || p.max_parts > kApMaxParts)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "%s: max_parts=%d outside 1..%d (TVZ_ALIGN_MAX_PARTS)", f.what, (int)p.max_parts,
                          kApMaxParts);
-    int32_t B = 0;
-    if (int rc = check_align_bins(eps, max_offset, f.max_bins, f.bins_limit, &B)) return rc;
+    return check_align_bins(p.eps, p.max_offset, f.max_bins, f.bins_limit, B);
+}
+
+// One handle: sort -> locate the ids' rows -> walk every (pair, candidate row) -> pick per pair.  `rates`, `B`: checked
+// (check_align_parts_early).  n_ranks = 0: d_parts is the caller's.  n_ranks >= 1: the workspace also holds the local
+// answer and n_ranks gathered ones; d_parts = NULL writes into the workspace's own, and `blocks` is told where.  `late`:
+// the sharded call's own refusals, behind all of these and in front of the first launch.
+int align_parts_run(tvz_corpus *c, const Batch &b, const AlignPartsCall &p, const AlRates &rates, int32_t B, int32_t *d_parts,
+                    Workspace ws, int32_t n_ranks, void *hip_stream, ShardBlocks *blocks, LateCheck late = {}) {
+    const AlignTopkForm &f = kAlignPartsForm;
+    const int32_t Q = b.Q, max_query_len = b.max_query_len, k = p.k, max_parts = p.max_parts, min_votes = p.min_votes;
+    const int32_t *d_video_ids = p.d_video_ids;
+    const int64_t id_stride = p.id_stride, query_id_stride = p.query_id_stride;
+    const double eps = p.eps;
     if (int rc = check_batch_args(c, b, 0)) return rc;
     if (Q == 0) return TVZ_OK;
     Carver cv(ws.p);
-    const AlignPartsWs w = align_parts_ws_layout(cv, Q, k, max_parts);
+    const AlignPartsWs w = align_parts_ws_layout(cv, Q, k, max_parts, n_ranks);
     const AlignLds lds(max_query_len, B);
     auto args_ok = [&]() -> int {
-        TVZ_REQUIRE(d_video_ids != nullptr && d_parts != nullptr, "NULL argument");
+        TVZ_REQUIRE(d_video_ids != nullptr && (d_parts != nullptr || w.local != nullptr), "NULL argument");
+        if (d_parts == nullptr) d_parts = w.local;
+        if (blocks) *blocks = ShardBlocks{d_parts, w.gathered};
         TVZ_REQUIRE(lds.fits(/* static LDS: none */ 0), "%s walk: %zu B of dynamic LDS exceed a gfx950 workgroup's", f.what,
                     lds.bytes);
-        return TVZ_OK;
+        return late();
     };
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
     TolCall t;                                                                // (the sort zeroes counts[0 .. Q) too)
-    if (int rc = tol_prelude(c, b, TolFront{cv, cv.fixed(), w.counts, f.what, f.sizer}, ws.p ? ws.bytes : 0, max_query_len, st,
-                             args_ok, t))
+    if (int rc = tol_prelude(c, b, TolFront{cv, cv.fixed(), w.counts, f.what, n_ranks > 0 ? f.sharded_sizer : f.sizer},
+                             ws.p ? ws.bytes : 0, max_query_len, st, args_ok, t))
         return rc;
     const int64_t n_rows = t.n_rows;
     TVZ_HIP(hipMemsetAsync(w.counts, 0, (size_t)Q * (size_t)k * sizeof(int32_t), st));
@@ -2412,13 +2448,79 @@ int align_parts_impl(tvz_corpus *c, const Batch &b, const int32_t *d_video_ids, 
     return record(c, st);
 }
 
+// A call of the C ABI, or the sharded form's local part: what is refused early, then the handle.
+int align_parts_call(tvz_corpus *c, const Batch &b, const AlignPartsCall &p, int32_t *d_parts, Workspace ws, int32_t n_ranks,
+                     void *hip_stream, ShardBlocks *blocks, LateCheck late = {}) {
+    AlRates rates{};
+    int32_t B = 0;
+    if (int rc = check_align_parts_early(b, p, &rates, &B)) return rc;
+    return align_parts_run(c, b, p, rates, B, d_parts, ws, n_ranks, hip_stream, blocks, late);
+}
+
+// what the parts merge refuses, apart from its pointers
+int check_align_parts_merge(int32_t n_lists, int32_t k, int32_t max_parts) {
+    if (n_lists < 1 || n_lists > kAlMergeMaxLists)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment parts merge: %d lists outside 1..%d", (int)n_lists, kAlMergeMaxLists);
+    if (k < 1 || k > kAlMaxK) return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment parts merge: k=%d outside 1..%d", (int)k, kAlMaxK);
+    if (max_parts < 1 || max_parts > kApMaxParts)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment parts merge: max_parts=%d outside 1..%d (TVZ_ALIGN_MAX_PARTS)",
+                         (int)max_parts, kApMaxParts);
+    return TVZ_OK;
+}
+
+// The shards of one process: every handle's call into its block of d_blocks, then the merge.
+int align_parts_shards_impl(tvz_corpus *const *shards, int32_t n_shards, const Batch &b, const AlignPartsCall &p,
+                            int32_t *d_blocks, int32_t *d_parts, Workspace ws, void *hip_stream) {
+    const int32_t Q = b.Q;
+    AlRates rates{};
+    int32_t B = 0;
+    if (int rc = check_align_parts_early(b, p, &rates, &B)) return rc;
+    TVZ_REQUIRE(shards != nullptr && n_shards >= 1, "no shards");
+    TVZ_REQUIRE(Q >= 0, "Q=%d is negative", (int)Q);
+    if (int rc = check_align_parts_merge(n_shards, p.k, p.max_parts)) return rc;
+    for (int32_t r = 0; r < n_shards; ++r)
+        TVZ_REQUIRE(shards[r] != nullptr && shards[r]->device == shards[0]->device,
+                    "shard %d is NULL or on another device than shard 0", r);
+    TVZ_REQUIRE(Q == 0 || (d_blocks && d_parts && b.d_queries && b.d_q_offsets && p.d_video_ids), "NULL argument");
+    if (Q == 0) return TVZ_OK;
+    // every handle's call makes the same checks of the same arguments: what one refuses, the first one refuses, before
+    // anything is enqueued
+    const size_t block = (size_t)Q * (size_t)p.k * (size_t)ap_words(p.max_parts);
+    for (int32_t r = 0; r < n_shards; ++r)
+        if (int rc = align_parts_run(shards[r], b, p, rates, B, d_blocks + (size_t)r * block, ws, 0, hip_stream, nullptr)) return rc;
+    DeviceGuard dg(shards[0]->device);
+    return tvz_align_parts_merge_local(d_blocks, n_shards, Q, p.k, p.max_parts, d_parts, hip_stream);
+}
+
 }  // namespace
 
-// used by tvz_comm.hip (same shared object, not exported): a form's call with the sharded forms' blocks
-int tvz_align_topk_local(AlignForm form, tvz_corpus *c, const Batch &b, const AlignCall &a, uint32_t flags, int32_t k,
-                         int32_t *d_out, Workspace ws, int32_t n_ranks, void *hip_stream, ShardBlocks *blocks) {
-    return align_topk_call(form, c, b, AlignAsk{a, nullptr, 0, flags, k}, d_out, ws, n_ranks, hip_stream, blocks);
+// used by tvz_comm.hip (same shared object, not exported): the parts call with the sharded form's blocks ...
+int tvz_align_parts_local(tvz_corpus *c, const Batch &b, const AlignPartsCall &p, int32_t *d_parts, Workspace ws, int32_t n_ranks,
+                          void *hip_stream, ShardBlocks *blocks, LateCheck late) {
+    return align_parts_call(c, b, p, d_parts, ws, n_ranks, hip_stream, blocks, late);
 }
+
+// ... and the merge of the gathered answers
+int tvz_align_parts_merge_local(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t k, int32_t max_parts,
+                                int32_t *d_parts, void *hip_stream) {
+    TVZ_REQUIRE(Q >= 0, "Q=%d is negative", (int)Q);
+    if (int rc = check_align_parts_merge(n_lists, k, max_parts)) return rc;
+    if (Q == 0) return TVZ_OK;
+    TVZ_REQUIRE(d_gathered && d_parts, "NULL argument");
+    const int64_t pairs = (int64_t)Q * k;
+    hipLaunchKernelGGL(ts_alignp_merge_kernel, dim3((unsigned)tvz::ceil_div(pairs, (int64_t)kApMergeGroups)), dim3(kApMergeBlock), 0,
+                       reinterpret_cast<hipStream_t>(hip_stream), d_gathered, n_lists, pairs, max_parts, d_parts);
+    return launched();
+}
+
+// used by tvz_comm.hip (same shared object, not exported): a form's call with the sharded forms' blocks
+int tvz_align_topk_local(AlignForm form, tvz_corpus *c, const Batch &b, const AlignCall &a, const double *h_rates,
+                         int32_t n_rates, uint32_t flags, int32_t k, int32_t *d_out, Workspace ws, int32_t n_ranks,
+                         void *hip_stream, ShardBlocks *blocks, LateCheck late) {
+    return align_topk_call(form, c, b, AlignAsk{a, h_rates, n_rates, flags, k}, d_out, ws, n_ranks, hip_stream, blocks, late);
+}
+
+int tvz_align_form_cols(AlignForm form) { return kAlignForms[form].cols; }
 
 // ... and the merge of a form's blocks, rows of f.cols columns (the form without flags: 0)
 int tvz_align_merge_local(AlignForm form, const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t k, uint32_t flags,
@@ -2740,9 +2842,7 @@ TVZ_EXPORT int tvz_align_span_topk_shards(tvz_corpus *const *shards, int32_t n_s
 
 TVZ_EXPORT size_t tvz_align_parts_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k,
                                                   int32_t max_parts) {
-    if (Q < 0 || max_query_len < 0 || total_query_keys < 0 || k < 1 || max_parts < 1 || max_parts > kApMaxParts) return 0;
-    const int64_t keys = total_query_keys > 0 ? total_query_keys : (int64_t)Q * max_query_len;
-    return align_parts_ws_bytes(Q, std::max<int64_t>(keys, max_query_len), k, max_parts);
+    return align_parts_sizing(Q, max_query_len, total_query_keys, k, max_parts, 0);
 }
 
 TVZ_EXPORT int tvz_align_parts(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
@@ -2750,9 +2850,42 @@ TVZ_EXPORT int tvz_align_parts(tvz_corpus *c, const double *d_queries, const int
                                int32_t k, double eps, double max_offset, const double *h_rates, int32_t n_rates,
                                int32_t min_votes, int32_t max_parts, int32_t *d_parts, void *d_workspace,
                                size_t workspace_bytes, void *hip_stream) {
-    TVZ_GUARDED(align_parts_impl(c, align_batch(d_queries, d_q_offsets, Q, max_query_len, nullptr), d_video_ids, id_stride,
-                                 query_id_stride, k, eps, max_offset, h_rates, n_rates, min_votes, max_parts, d_parts,
-                                 Workspace{d_workspace, workspace_bytes}, hip_stream));
+    TVZ_GUARDED(align_parts_call(c, align_batch(d_queries, d_q_offsets, Q, max_query_len, nullptr),
+                                 AlignPartsCall{d_video_ids, id_stride, query_id_stride, k, eps, max_offset, h_rates, n_rates,
+                                                min_votes, max_parts},
+                                 d_parts, Workspace{d_workspace, workspace_bytes}, 0, hip_stream, nullptr));
+}
+
+TVZ_EXPORT int tvz_align_parts_merge(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t k, int32_t max_parts,
+                                     int32_t *d_parts, void *hip_stream) {
+    TVZ_GUARDED(tvz_align_parts_merge_local(d_gathered, n_lists, Q, k, max_parts, d_parts, hip_stream));
+}
+
+TVZ_EXPORT int tvz_align_parts_shards(tvz_corpus *const *shards, int32_t n_shards, const double *d_queries,
+                                      const int64_t *d_q_offsets, int32_t Q, int32_t max_query_len,
+                                      const int32_t *d_video_ids, int64_t id_stride, int64_t query_id_stride, int32_t k,
+                                      double eps, double max_offset, const double *h_rates, int32_t n_rates, int32_t min_votes,
+                                      int32_t max_parts, int32_t *d_blocks, int32_t *d_parts, void *d_workspace,
+                                      size_t workspace_bytes, void *hip_stream) {
+    TVZ_GUARDED(align_parts_shards_impl(shards, n_shards, align_batch(d_queries, d_q_offsets, Q, max_query_len, nullptr),
+                                        AlignPartsCall{d_video_ids, id_stride, query_id_stride, k, eps, max_offset, h_rates,
+                                                       n_rates, min_votes, max_parts},
+                                        d_blocks, d_parts, Workspace{d_workspace, workspace_bytes}, hip_stream));
+}
+
+TVZ_EXPORT size_t tvz_align_parts_sharded_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k,
+                                                          int32_t max_parts, int32_t n_ranks) {
+    return n_ranks < 0 ? 0 : align_parts_sizing(Q, max_query_len, total_query_keys, k, max_parts, std::max(n_ranks, 1));
+}
+
+TVZ_EXPORT size_t tvz_align_rates_topk_sharded_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys,
+                                                               int32_t k, int32_t n_ranks) {
+    return n_ranks < 0 ? 0 : align_sizing(kAlignRates, Q, max_query_len, total_query_keys, k, std::max(n_ranks, 1));
+}
+
+TVZ_EXPORT size_t tvz_align_span_topk_sharded_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys,
+                                                              int32_t k, int32_t n_ranks) {
+    return n_ranks < 0 ? 0 : align_sizing(kAlignSpan, Q, max_query_len, total_query_keys, k, std::max(n_ranks, 1));
 }
 
 // (unlike its bounded twin this one sizes n_ranks < 0 as one rank instead of answering 0: callers' buffers were sized by

@@ -78,6 +78,13 @@ def s3_frame_source(bucket: str, key: str, filename: str, unique_id: str):
     raise Exception(f"File download incomplete or corrupt after 5 attempts: {last}")
 
 
+def _corpus_can(corpus, method: str, flag: str) -> bool:
+    """Can the store's corpus answer `method`?  It has the method and, where it says so with a `flag` (a
+    service.RankCorpus always has the method; whether its matcher has the form is its supports_* view), the flag is
+    true - so what cannot be answered is refused when the driver is built, not inside an upload."""
+    return hasattr(corpus, method) and bool(getattr(corpus, flag, True))
+
+
 class Inspector:
     def __init__(self, store, device: str = "cuda:0", frame_source: Optional[Callable] = None,
                  threshold: float = scene.DEFAULT_THRESHOLD, min_match: int = 2,
@@ -115,7 +122,7 @@ class Inspector:
         if self.near_any_offset:
             if not near_duplicates or self.near_top_k is None:
                 raise ValueError("near_any_offset=True needs near_duplicates=True and near_top_k")
-            if not hasattr(getattr(store, "corpus", None), "align_wide_topk"):
+            if not _corpus_can(getattr(store, "corpus", None), "align_wide_topk", "supports_align_wide"):
                 raise RuntimeError(f"near_any_offset=True: the store's corpus "
                                    f"({type(getattr(store, 'corpus', None)).__name__}) has no align_wide_topk; "
                                    "use a DeviceCorpus, a service.ShardedCorpus or a service.RankCorpus")
@@ -128,10 +135,10 @@ class Inspector:
                 raise ValueError(f"near_rates must be None or 1..8 finite rates > 0, got {near_rates!r}")
             if not self.near_any_offset or self.near_top_k is None:
                 raise ValueError("near_rates needs near_any_offset=True and near_top_k")
-            if not hasattr(getattr(store, "corpus", None), "align_rates_topk"):
+            if not _corpus_can(getattr(store, "corpus", None), "align_rates_topk", "supports_align_rates"):
                 raise RuntimeError(f"near_rates={self.near_rates}: the store's corpus "
                                    f"({type(getattr(store, 'corpus', None)).__name__}) has no align_rates_topk; "
-                                   "use a DeviceCorpus or a service.ShardedCorpus")
+                                   "use a DeviceCorpus, a service.ShardedCorpus or a service.RankCorpus whose matcher has it")
         # opt-in: where the copy is (tvz_align_span_topk) - every entry gains "upload_span" and "stored_span", the first
         # and the last aligned cut on either side in seconds - and, with near_score="local", the score over that span
         # alone, which finds the copy that is partial on BOTH sides (a clip inside a compilation).  One aligned pair
@@ -144,10 +151,10 @@ class Inspector:
             if near_score == "local" and self.near_min_votes < 2:
                 raise ValueError(f"near_score='local' needs near_min_votes >= 2 (one aligned pair scores 1.0), "
                                  f"got {near_min_votes!r}")
-            if not hasattr(getattr(store, "corpus", None), "align_span_topk"):
+            if not _corpus_can(getattr(store, "corpus", None), "align_span_topk", "supports_align_span"):
                 raise RuntimeError(f"{what}: the store's corpus "
                                    f"({type(getattr(store, 'corpus', None)).__name__}) has no align_span_topk; "
-                                   "use a DeviceCorpus or a service.ShardedCorpus")
+                                   "use a DeviceCorpus, a service.ShardedCorpus or a service.RankCorpus whose matcher has it")
         # opt-in: EVERY aligned part of each reported video (tvz_align_parts) - the copy with an ad put in or a scene
         # taken out aligns at two shifts, and the search reports the larger half.  After the search one call aligns the
         # upload with every reported id in full: each entry gains "parts", up to near_parts of them, each with its own
@@ -158,10 +165,10 @@ class Inspector:
                 raise ValueError(f"near_parts must be None or 2..4, got {near_parts!r}")
             if not self.near_any_offset or self.near_top_k is None or near_score != "local":
                 raise ValueError(f"near_parts={self.near_parts} needs near_top_k, near_any_offset=True and near_score='local'")
-            if not hasattr(getattr(store, "corpus", None), "align_parts"):
+            if not _corpus_can(getattr(store, "corpus", None), "align_parts", "supports_align_parts"):
                 raise RuntimeError(f"near_parts={self.near_parts}: the store's corpus "
                                    f"({type(getattr(store, 'corpus', None)).__name__}) has no align_parts; "
-                                   "use a DeviceCorpus or a service.ShardedCorpus")
+                                   "use a DeviceCorpus, a service.ShardedCorpus or a service.RankCorpus whose matcher has it")
         # opt-in, never the default: duplicates by the TOLERANT count (include/tvz.h tvz_find_duplicates_tol)
         # instead of the reference's exact float64 equality; the verdict, the truncation at kth and the stored
         # duplicates all follow it.  Refused here, before any upload, where the store's corpus cannot do it.

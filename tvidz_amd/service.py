@@ -27,15 +27,18 @@ Two forms of the same composition:
 
 The opt-in near-duplicate search (Inspector(near_top_k=K), `--near-top-k K`) is written once per composition, for any
 form of corpus.ALIGN_FORMS: ShardedCorpus._near_shards runs tvz_<stem>_shards (every shard in turn + the device merge,
-one call, one copy back) and serves all four; RankCorpus._near sends an ask of the form's kind (NEAR_FORMS) through the
-tick to `matcher.align(form, ...)`, and has a kind for two: `align_topk` (ASK_NEAR) and the search at any shift,
-`align_wide_topk` (ASK_NEAR_WIDE; Inspector(near_any_offset=True), `--near-any-offset`).  Their RCCL calls
-(tvz_<stem>_sharded) have run on hardware at world size 1 only; tests/test_align_topk_sharded_cpu.py and
-tests/test_align_wide_sharded_cpu.py run the exchange at world sizes 2 and 3 on gloo.  The search for speed-changed
-copies (`align_rates_topk`, Inspector(near_rates=...)) and the one with spans (`align_span_topk`,
-Inspector(near_spans=True, near_score="local")) have no ask kind, no RCCL call and no launcher switch yet.  Neither has
-the refinement behind the search, every aligned part of the reported videos (`align_parts`, Inspector(near_parts=P)):
-ShardedCorpus.align_parts asks every shard of the one process and keeps the best answer per pair; RankCorpus has none.
+one call, one copy back) and serves all four; RankCorpus._near sends an ask of the form's kind (TICK_FORMS) through the
+tick to `matcher.align(form, ...)`, and has a kind for each of the four: `align_topk` (ASK_NEAR), the search at any
+shift, `align_wide_topk` (ASK_NEAR_WIDE; Inspector(near_any_offset=True), `--near-any-offset`), the search for
+speed-changed copies, `align_rates_topk` (ASK_NEAR_RATES; Inspector(near_rates=...), `--near-rates R1,R2,...`) and the one
+with spans, `align_span_topk` (ASK_NEAR_SPAN; Inspector(near_spans=True) or near_score="local", `--near-spans`,
+`--near-score local`); an ask of the last two carries its rate list.  The refinement behind the search, every aligned
+part of the reported videos (`align_parts`, Inspector(near_parts=P), `--near-parts P`), is one call too:
+ShardedCorpus.align_parts runs tvz_align_parts_shards (every shard in turn + the device merge that keeps the best
+answer per pair, one copy back), RankCorpus.align_parts sends an ASK_PARTS with the ids through the tick to
+`matcher.parts(...)`; a tick answers its parts asks behind its searches.  The RCCL calls (tvz_<stem>_sharded,
+tvz_align_parts_sharded) have run on hardware at world size 1 only; tests/test_align_topk_sharded_cpu.py,
+tests/test_align_wide_sharded_cpu.py and tests/test_near_service_cpu.py run the exchange at world sizes 2 and 3 on gloo.
 """
 from __future__ import annotations
 
@@ -314,21 +317,25 @@ class ShardedCorpus:
 
     def align_parts(self, queries, video_ids, *, eps: float, max_offset=None, rates=(1.0,), min_votes: int,
                     max_parts: int, max_query_len=None):
-        """DeviceCorpus.align_parts over every shard: each shard is asked for every pair with the calling thread's one
-        workspace, the answers come back in ONE copy, and per pair the one with the most part-0 votes is kept, the
-        lower shard on a tie (corpus.align_parts_merge); n_rows is the shards' sum.  More than ALIGN_PARTS_MAX_ROWS
-        rows of one id refuse the pair only where they lie in ONE shard."""
+        """DeviceCorpus.align_parts over every shard: ONE library call (tvz_align_parts_shards) asks every shard for
+        every pair with the calling thread's one workspace and merges the answers on the device - per pair the one with
+        the most part-0 votes is kept, the lower shard on a tie (what corpus.align_parts_merge computes on the host);
+        n_rows is the shards' sum - and ONE copy brings the answer back.  More than ALIGN_PARTS_MAX_ROWS rows of one id
+        refuse the pair only where they lie in ONE shard.  More than 16 shards (the merge takes up to 16 lists): one such
+        call per group of 16, the groups' answers merged again by tvz_align_parts_merge; still one copy back, same
+        answer (the rule is associative)."""
         dev = self.dev
         d_q, d_off, Q, max_query_len, _ = tc.align_inputs(queries, None, max_query_len, dev)
         d_ids = tc.align_parts_ids(video_ids, Q, dev)
         ws = tc.thread_workspace(self._near_tls, tc.align_parts_workspace_bytes(Q, max_query_len, d_q.numel(),
                                                                                 d_ids.shape[1], max_parts), dev)
         with torch.cuda.device(dev):
-            out = torch.empty((self.R, Q, d_ids.shape[1], 1 + int(max_parts), 6), dtype=torch.int32, device=dev)
-            for r, s in enumerate(self.shards):
-                s.align_parts_block(d_q, d_off, max_query_len, d_ids, eps=eps, max_offset=max_offset, rates=tuple(rates),
-                                    min_votes=min_votes, max_parts=max_parts, out=out[r], workspace=ws)
-            return tc.align_parts_merge(out.cpu().numpy())
+            groups = [self.shards[i:i + 16] for i in range(0, self.R, 16)]      # the merge takes up to 16 lists
+            answers = [tc.align_parts_shards(g, d_q, d_off, max_query_len, d_ids, eps=eps, max_offset=max_offset,
+                                             rates=tuple(rates), min_votes=min_votes, max_parts=max_parts, workspace=ws)[1]
+                       for g in groups]
+            out = answers[0] if len(answers) == 1 else tc.align_parts_merge_device(torch.stack(answers))
+            return out.cpu().numpy()
 
     def _near_shards(self, form, queries, k, exclude_ids, max_query_len, **ask):
         """What the four methods above share, for their `form` (corpus.ALIGN_FORMS) and what they `ask`: the inputs, the
@@ -407,10 +414,19 @@ class ShardedCorpus:
         return [(merged[i], int(totals[i])) for i in range(Q)]
 
 
-ASK_TOPK, ASK_EXACT, ASK_NEAR, ASK_NEAR_WIDE = 0, 1, 2, 3
-ASK_HEADER = 11                # (len, exclude, min_match, kind, tolerance, eps, max_offset, k, min_votes, min_score, flags)
+ASK_TOPK, ASK_EXACT, ASK_NEAR, ASK_NEAR_WIDE, ASK_NEAR_RATES, ASK_NEAR_SPAN, ASK_PARTS = 0, 1, 2, 3, 4, 5, 6
+# An ask's header: (len, exclude, min_match, kind, tolerance | a near ask's eps, max_offset, k, min_votes, min_score, flags |
+# its rate list: the count and up to 8 rates | a parts ask's max_parts and its k <= 64 ids).  All float64: small integers
+# and int32 ids are exact in it, and tolerance, eps, max_offset and the rates ARE float64.  Every rank runs one build.
+NEAR_PAR = 6 + 1 + tc.ALIGN_MAX_RATES                      # what a search's asks must agree in to share a batched call
+PARTS_PAR = NEAR_PAR + 1                                   # ... and a parts call's: + max_parts (the ids are per ask)
+ASK_HEADER = 5 + PARTS_PAR + tc.ALIGN_TOPK_MAX_K
 NEAR_FORMS = {ASK_NEAR: tc.FORM_BOUNDED, ASK_NEAR_WIDE: tc.FORM_WIDE}      # a near ask's kind -> its form of the alignment top-k
 NEAR_KINDS = {form: kind for kind, form in NEAR_FORMS.items()}
+# ... and with the kinds of the two forms that carry a rate list: the table `_answer_near` walks.  (NEAR_FORMS keeps its
+# two: the recorded verdicts of tests/test_near_check_cpu.py are keyed by its stems.)
+TICK_FORMS = {**NEAR_FORMS, ASK_NEAR_RATES: tc.FORM_RATES, ASK_NEAR_SPAN: tc.FORM_SPAN}
+TICK_KINDS = {form: kind for kind, form in TICK_FORMS.items()}
 NEAR_MAX_K, NEAR_MAX_BINS, NEAR_SCORE_ONE = tc.ALIGN_TOPK_MAX_K, tc.ALIGN_TOPK_MAX_BINS, tc.ALIGN_SCORE_ONE
 
 
@@ -421,11 +437,24 @@ def check_near_top_k(k) -> int:
     return int(k)
 
 
-def check_near(form, eps, max_offset, k, min_votes, min_score, contain=False) -> tuple:
-    """What tvz_<stem> of `form` (NEAR_FORMS) refuses, refused on the host with its rules (include/tvz.h): -> the six
+def check_near_rates(rates) -> tuple:
+    """The rate list of a search with rates or of a parts call, refused on the host with the library's rule
+    (1..ALIGN_MAX_RATES finite rates > 0): -> (count, the rates padded with zeros to ALIGN_MAX_RATES) as an ask carries
+    them."""
+    try:
+        r = tuple(float(x) for x in rates)
+    except TypeError:
+        raise ValueError(f"rates must be 1..{tc.ALIGN_MAX_RATES} finite rates > 0, got {rates!r}") from None
+    if not 1 <= len(r) <= tc.ALIGN_MAX_RATES or not all(0.0 < x <= sys.float_info.max for x in r):
+        raise ValueError(f"rates must be 1..{tc.ALIGN_MAX_RATES} finite rates > 0, got {rates!r}")
+    return (len(r),) + r + (0.0,) * (tc.ALIGN_MAX_RATES - len(r))
+
+
+def check_near(form, eps, max_offset, k, min_votes, min_score, contain=False, local=False) -> tuple:
+    """What tvz_<stem> of `form` (TICK_FORMS) refuses, refused on the host with its rules (include/tvz.h): -> the six
     values as a near ask carries them, the call's flags last (0 for the form without flags).  `max_offset=None` is the
     widest of a form that has one, tc.ALIGN_WIDE_MAX_B bins of eps on either side of zero; the bounded form takes
-    NEAR_MAX_BINS bins in all."""
+    NEAR_MAX_BINS bins in all.  `local` is the span form's second score kind: one of the two."""
     eps, max_offset = float(eps), None if form.widest and max_offset is None else float(max_offset)
     if not (0.0 < eps <= sys.float_info.max):
         raise ValueError(f"eps must be finite and > 0, got {eps!r}")
@@ -444,12 +473,17 @@ def check_near(form, eps, max_offset, k, min_votes, min_score, contain=False) ->
                             ("min_score", min_score, 0, NEAR_SCORE_ONE)):
         if int(v) != v or not lo <= int(v) <= hi:
             raise ValueError(f"{name} must be an integer in {lo}..{hi}, got {v!r}")
-    return eps, max_offset, int(k), int(min_votes), int(min_score), tc.ALIGN_CONTAIN if contain and form.flags else 0
+    if contain and local:
+        raise ValueError("contain and local are two score kinds: one of them")
+    flags = (tc.ALIGN_CONTAIN if contain and "contain" in form.flags else 0) | \
+        (tc.ALIGN_LOCAL if local and "local" in form.flags else 0)
+    return eps, max_offset, int(k), int(min_votes), int(min_score), flags
 
 
 class _Asks(NamedTuple):
     """The asks of every rank in one tick, un-padded and in the same order on every rank (rank-major): ask `a` is ask
-    `ii[a]` of rank `rr[a]`, `mine` marks this rank's; `near` holds a near ask's six parameters [n, 6] (check_near),
+    `ii[a]` of rank `rr[a]`, `mine` marks this rank's; `near` holds the header behind the tolerance [n, ASK_HEADER - 5]:
+    a near ask's six parameters (check_near), its rate list (check_near_rates) and a parts ask's max_parts and ids;
     `keys` the gathered, still padded timestamps [world, Qcap, Lcap]."""
     rr: np.ndarray
     ii: np.ndarray
@@ -492,6 +526,14 @@ class RankCorpus:
                  0 for the form without flags) travel in the ask's header; asks of one kind that agree in all six share
                  one batched call per tick.  Nothing is sent unless somebody asks: a service without --near-top-k
                  (--near-any-offset) never names it.
+      ASK_NEAR_RATES, ASK_NEAR_SPAN  the same for the two forms with a rate list (`align_rates_topk`, what
+                 Inspector(near_rates=...) calls; `align_span_topk`, what near_spans=True or near_score="local" calls): the
+                 ask also carries the count and up to 8 rates, and asks share a batched call when they agree in the
+                 rate list too.
+      ASK_PARTS  every aligned part of named stored videos (`align_parts`, what Inspector(near_parts=P) calls behind its
+                 search, as a second ask): eps, max_offset, k, min_votes, the rate list, max_parts and the ask's k ids
+                 travel in the header; asks that agree in all but the ids share one `matcher.parts(...)`, and a tick
+                 answers its parts asks behind its searches.
 
     `shard`: this rank's DeviceCorpus (or a stand-in with upload/upsert/clear/find_duplicates);
     `matcher.match_topk(d_q, d_off, max_len, min_match, d_excl) -> (merged [Q,k,3], totals [Q])`;
@@ -596,21 +638,87 @@ class RankCorpus:
         return self._near(tc.FORM_WIDE, queries, exclude_ids, max_query_len, eps, max_offset, k, min_votes, min_score,
                           contain)
 
+    def align_rates_topk(self, queries, *, eps: float, rates, max_offset=None, k: int = 16, min_votes: int = 1,
+                         min_score: int = 0, contain: bool = False, exclude_ids=None, max_query_len=None):
+        """DeviceCorpus.align_rates_topk over the shards of all ranks - align_wide_topk for copies played at another
+        speed; rows of five columns, the last the rate's index; order: corpus.align_rates_order_key.  Every query is one
+        ASK_NEAR_RATES of the next tick (`_near`) and carries the rate list."""
+        return self._near(tc.FORM_RATES, queries, exclude_ids, max_query_len, eps, max_offset, k, min_votes, min_score,
+                          contain, rates=rates)
+
+    def align_span_topk(self, queries, *, eps: float, rates=(1.0,), max_offset=None, k: int = 16, min_votes: int = 1,
+                        min_score: int = 0, contain: bool = False, local: bool = False, exclude_ids=None,
+                        max_query_len=None):
+        """DeviceCorpus.align_span_topk over the shards of all ranks - align_rates_topk with the span of every hit,
+        scored inside it with `local`; rows of eight columns; order: corpus.align_span_order_key.  Every query is one
+        ASK_NEAR_SPAN of the next tick (`_near`)."""
+        return self._near(tc.FORM_SPAN, queries, exclude_ids, max_query_len, eps, max_offset, k, min_votes, min_score,
+                          contain, local, rates=rates)
+
+    def align_parts(self, queries, video_ids, *, eps: float, max_offset=None, rates=(1.0,), min_votes: int,
+                    max_parts: int, max_query_len=None):
+        """DeviceCorpus.align_parts over the shards of all ranks: `queries` = a list of timestamp lists, `video_ids` =
+        [Q][k] ids (-1: no pair) -> int32 [Q, k, 1 + max_parts, 6] as ShardedCorpus.align_parts answers: per pair the
+        answer of the rank with the most part-0 votes, n_rows summed over the ranks, a pair some rank refused refused.
+        Every query is one ASK_PARTS of the next tick and carries its ids.  Everything a rank's library call would
+        refuse is refused HERE, in the caller (ValueError: the rate list, min_votes, k, max_parts, the bins;
+        RuntimeError: a matcher without `parts`).  A query of more than max_query_len (at most 4,095) values never
+        travels: its pairs are answered here as the library words a refusal, (id, 0, 0, ALIGN_REFUSED, 0, 0) - n_rows
+        reads 0 there, because no rank looked - and (-1, 0, 0, 0, 0, 0) for a negative id."""
+        ids = np.asarray(video_ids, dtype=np.int64)
+        queries = [np.ascontiguousarray(np.asarray(q, dtype=np.float64).reshape(-1)) for q in queries]
+        if len(queries) == 0 and ids.ndim != 2:
+            ids = np.zeros((0, 1), dtype=np.int64)
+        if ids.ndim != 2 or ids.shape[0] != len(queries) or not 1 <= ids.shape[1] <= NEAR_MAX_K \
+                or (ids < -(1 << 31)).any() or (ids >= 1 << 31).any():
+            raise ValueError(f"video_ids must be [{len(queries)}][k] int32 ids, k in 1..{NEAR_MAX_K}")
+        k, P = int(ids.shape[1]), max_parts
+        if int(P) != P or not 1 <= int(P) <= tc.ALIGN_MAX_PARTS:
+            raise ValueError(f"max_parts must be an integer in 1..{tc.ALIGN_MAX_PARTS}, got {max_parts!r}")
+        near = check_near(tc.FORM_SPAN, eps, max_offset, k, min_votes, 0) + check_near_rates(rates) + (int(P),)
+        if not getattr(self.matcher, "supports_align_parts", False):
+            raise RuntimeError(f"this rank corpus has no align_parts: its matcher {type(self.matcher).__name__} has no "
+                               "parts call")
+        limit = MAX_BATCH_LEN if max_query_len is None else min(int(max_query_len), MAX_BATCH_LEN)
+        out = np.zeros((len(queries), k, 1 + int(P), 6), dtype=np.int32)
+        out[:, :, 0, 0] = np.where(ids < 0, -1, ids)
+        out[:, :, 0, 3] = np.where(ids < 0, 0, tc.ALIGN_REFUSED)                     # refused unless answered
+        sent = [i for i, q in enumerate(queries) if q.size <= limit]
+        asks = [(queries[i], 0, -1, ASK_PARTS, 0.0, near + tuple(float(v) for v in ids[i])) for i in sent]
+        for i, block in zip(sent, self._ask_all(asks)):
+            out[i] = block
+        return out
+
     @property
     def supports_align_wide(self) -> bool:
         return tc.FORM_WIDE in getattr(self.matcher, "align_forms", ())
 
-    def _near(self, form, queries, exclude_ids, max_query_len, eps, max_offset, k, min_votes, min_score, contain=False):
-        """What the two calls above share, for their `form`.  Everything a rank's library call would refuse is refused
-        HERE, in the caller (check_near's ValueError for a bad parameter, RuntimeError for a matcher without the form):
-        a matcher that throws on one rank inside a tick would strand the others.  A query of more than max_query_len
-        (at most 4,095) values is answered here too, as the library answers it: all rows padding, total ALIGN_REFUSED -
-        it never travels."""
-        near = check_near(form, eps, max_offset, k, min_votes, min_score, contain)
+    @property
+    def supports_align_rates(self) -> bool:
+        return tc.FORM_RATES in getattr(self.matcher, "align_forms", ())
+
+    @property
+    def supports_align_span(self) -> bool:
+        return tc.FORM_SPAN in getattr(self.matcher, "align_forms", ())
+
+    @property
+    def supports_align_parts(self) -> bool:
+        return bool(getattr(self.matcher, "supports_align_parts", False))
+
+    def _near(self, form, queries, exclude_ids, max_query_len, eps, max_offset, k, min_votes, min_score, contain=False,
+              local=False, rates=None):
+        """What the four searches above share, for their `form`.  Everything a rank's library call would refuse is refused
+        HERE, in the caller (check_near's and check_near_rates' ValueError for a bad parameter, RuntimeError for a
+        matcher without the form): a matcher that throws on one rank inside a tick would strand the others.  A query of
+        more than max_query_len (at most 4,095) values is answered here too, as the library answers it: all rows
+        padding, total ALIGN_REFUSED - it never travels."""
+        near = check_near(form, eps, max_offset, k, min_votes, min_score, contain, local)
+        if form.rates:
+            near += check_near_rates(rates)
         if form not in getattr(self.matcher, "align_forms", ()):
             raise RuntimeError(f"this rank corpus has no near-duplicate search of this form: its matcher "
                                f"{type(self.matcher).__name__} has no {form.stem}")
-        return self._near_asks(NEAR_KINDS[form], near, queries, exclude_ids, max_query_len)
+        return self._near_asks(TICK_KINDS[form], near, queries, exclude_ids, max_query_len)
 
     def _near_asks(self, kind, near, queries, exclude_ids, max_query_len):
         """The queries of one near-duplicate search as asks of `kind` with the checked parameters `near` (k is its
@@ -621,7 +729,7 @@ class RankCorpus:
         if len(excl) != len(queries):
             raise ValueError(f"exclude_ids must hold {len(queries)} video ids")
         k = near[2]
-        rows = np.zeros((len(queries), k, NEAR_FORMS[kind].cols), dtype=np.int32)
+        rows = np.zeros((len(queries), k, TICK_FORMS[kind].cols), dtype=np.int32)
         rows[:, :, 0] = -1
         totals = np.full(len(queries), -(1 << 31), dtype=np.int64)                 # ALIGN_REFUSED unless answered
         sent = [i for i, q in enumerate(queries) if q.size <= limit]
@@ -711,7 +819,7 @@ class RankCorpus:
     def _exchange_and_answer(self, take, allmeta):
         """One busy tick.  The order of the collectives and of the matcher calls is the same on every rank: the asks'
         exchange, one match_topk per (min_match, tolerance) in sorted order, one align per near kind and set of its
-        parameters in sorted order, then the exact asks' two gathers."""
+        parameters in sorted order, one parts call per set of its parameters, then the exact asks' two gathers."""
         asks = self._gather_asks(take, allmeta)
         self._answer_topk(asks, take)
         self._answer_near(asks, take)
@@ -720,15 +828,13 @@ class RankCorpus:
     def _gather_asks(self, take, allmeta) -> _Asks:
         Qcap, Lcap = int(allmeta[:, 0].max()), max(int(allmeta[:, 1].max()), 1)
         # the asks, padded to the largest rank's block, as ONE float64 block per rank:
-        # [Qcap, ASK_HEADER + Lcap] = (len, exclude, min_match, kind, tolerance, and a near ask's eps, max_offset,
-        # k, min_votes, min_score, flags | keys...); small integers are exact in float64, tolerance, eps and max_offset
-        # ARE float64
+        # [Qcap, ASK_HEADER + Lcap] = (the header: see ASK_HEADER | keys...)
         H = ASK_HEADER
         blk = np.zeros((Qcap, H + Lcap), dtype=np.float64)
         for i, (q, mm, ex, kind, _, tol, near) in enumerate(take):
             blk[i, 0], blk[i, 1], blk[i, 2], blk[i, 3], blk[i, 4] = len(q), ex, mm, kind, tol
             if near is not None:
-                blk[i, 5:5 + len(near)] = near                                     # check_near's six values
+                blk[i, 5:5 + len(near)] = near                                     # check_near's six values, and what follows them
             blk[i, H:H + len(q)] = q
         g = self._gather(torch.from_numpy(blk).to(self.xdev)).cpu().numpy()       # [world, Qcap, H + Lcap]
         # the global batch, in the same order on every rank: rank-major; rows past a rank's count are padding
@@ -737,10 +843,15 @@ class RankCorpus:
         lens, excl, min_match, kind = (g[rr, ii, c].astype(np.int64) for c in range(4))
         return _Asks(rr, ii, lens, excl, min_match, kind, g[rr, ii, 4], g[rr, ii, 5:H], g[:, :, H:], rr == self.rank)
 
-    def _answer_batch(self, asks: _Asks, take, sel, call) -> None:
+    def _answer_batch(self, asks: _Asks, take, sel, call, to_host=None) -> None:
         """The asks `sel` of the global batch as ONE batched matcher call, `call(d_q, d_off, max_len, d_excl) -> (rows
         [n,k,w], totals [n])`; this rank's asks among them get their (rows [k,w], total).  Un-padding is vectorised:
-        no per-ask Python."""
+        no per-ask Python.  `to_host` (the parts call, which has no totals): what brings the call's result to the host
+        as one answer per ask, in place of the (rows, totals) pair."""
+        if to_host is None:
+            def to_host(out):
+                rows, totals = _to_host(*out)
+                return [(rows[j].copy(), int(totals[j])) for j in range(len(sel))]
         lens = asks.lens[sel]
         flat = asks.keys[asks.rr[sel], asks.ii[sel]][np.arange(asks.keys.shape[2])[None, :] < lens[:, None]]   # ask after ask
         excl = asks.excl[sel].astype(np.int32)
@@ -753,14 +864,14 @@ class RankCorpus:
                 self._stream = torch.cuda.Stream(mdev, priority=-1)
             with torch.cuda.device(mdev), torch.cuda.stream(self._stream):
                 d_q, d_off, d_ex, _ = self._stager.put_flat(flat, lens, excl)
-                rows, totals = _to_host(*call(d_q, d_off, int(lens.max()), d_ex))
+                answers = to_host(call(d_q, d_off, int(lens.max()), d_ex))
         else:
             offs = np.zeros(len(sel) + 1, dtype=np.int64)
             np.cumsum(lens, out=offs[1:])
             d_q = torch.from_numpy(np.ascontiguousarray(flat if flat.size else np.zeros(1), dtype=np.float64))
-            rows, totals = _to_host(*call(d_q, torch.from_numpy(offs), int(lens.max()), torch.from_numpy(excl)))
+            answers = to_host(call(d_q, torch.from_numpy(offs), int(lens.max()), torch.from_numpy(excl)))
         for j in np.flatnonzero(asks.mine[sel]):
-            take[int(asks.ii[sel[j]])][4].set_result((rows[j].copy(), int(totals[j])))
+            take[int(asks.ii[sel[j]])][4].set_result(answers[j])
 
     def _answer_topk(self, asks: _Asks, take) -> None:
         """Top-k asks: one batched sharded match per (min_match, tolerance); the matcher hears of a tolerance only
@@ -774,17 +885,35 @@ class RankCorpus:
 
     def _answer_near(self, asks: _Asks, take) -> None:
         """Near asks: per kind in ascending order, one batched `matcher.align` of the kind's form per (eps, max_offset,
-        k, min_votes, min_score, flags) in sorted order: every rank reads the same kinds and parameters off the gathered
-        headers, so every rank makes the same calls in the same order."""
-        for kind, form in sorted(NEAR_FORMS.items()):
+        k, min_votes, min_score, flags, the rate list) in sorted order, then one `matcher.parts` per (eps, max_offset, k,
+        min_votes, the rate list, max_parts) in sorted order: every rank reads the same kinds and parameters off the
+        gathered headers, so every rank makes the same calls in the same order."""
+        for kind, form in sorted(TICK_FORMS.items()):
             of_kind = asks.kind == kind
-            for par in sorted(set(map(tuple, asks.near[of_kind].tolist()))):
+            pars = asks.near[:, :NEAR_PAR]
+            for par in sorted(set(map(tuple, pars[of_kind].tolist()))):
                 kw = dict(eps=par[0], max_offset=par[1], k=int(par[2]), min_votes=int(par[3]), min_score=int(par[4]))
                 if "contain" in form.flags:
                     kw["contain"] = bool(int(par[5]) & tc.ALIGN_CONTAIN)
-                self._answer_batch(asks, take, np.flatnonzero(of_kind & (asks.near == np.asarray(par)).all(axis=1)),
+                if "local" in form.flags:
+                    kw["local"] = bool(int(par[5]) & tc.ALIGN_LOCAL)
+                if form.rates:
+                    kw["rates"] = tuple(par[7:7 + int(par[6])])
+                self._answer_batch(asks, take, np.flatnonzero(of_kind & (pars == np.asarray(par)).all(axis=1)),
                                    lambda d_q, d_off, max_len, d_ex: self.matcher.align(form, d_q, d_off, max_len,
                                                                                         d_exclude_ids=d_ex, **kw))
+        of_kind = asks.kind == ASK_PARTS
+        pars = asks.near[:, :PARTS_PAR]
+        for par in sorted(set(map(tuple, pars[of_kind].tolist()))):
+            k = int(par[2])
+            kw = dict(eps=par[0], max_offset=par[1], min_votes=int(par[3]), rates=tuple(par[7:7 + int(par[6])]),
+                      max_parts=int(par[NEAR_PAR]))
+            sel = np.flatnonzero(of_kind & (pars == np.asarray(par)).all(axis=1))
+            ids = np.ascontiguousarray(asks.near[sel, PARTS_PAR:PARTS_PAR + k].astype(np.int32))      # [n, k], ask after ask
+            self._answer_batch(asks, take, sel,
+                               lambda d_q, d_off, max_len, d_ex: self.matcher.parts(
+                                   d_q, d_off, max_len, torch.from_numpy(ids).to(d_q.device), **kw),
+                               to_host=lambda out: list(out.cpu().numpy()))
 
     def _answer_exact(self, asks: _Asks, take) -> None:
         """Exact asks: every rank asks its own shard, counts and padded hit lists are all-gathered."""
@@ -905,23 +1034,59 @@ def near_kwargs(a) -> dict:
         kw["near_score"] = str(a.near_score)
     if int(getattr(a, "near_min_votes", 1)) != 1:
         kw["near_min_votes"] = int(a.near_min_votes)
+    if parse_near_rates(getattr(a, "near_rates", None)) is not None:
+        kw["near_rates"] = parse_near_rates(a.near_rates)
+    if getattr(a, "near_spans", False):
+        kw["near_spans"] = True
+    if int(getattr(a, "near_parts", 0) or 0):
+        kw["near_parts"] = int(a.near_parts)
     return kw
 
 
-def check_near_switches(near_top_k, near_any_offset=False, near_score="jaccard", near_min_votes=1) -> list:
-    """`--near-any-offset`, `--near-score`, `--near-min-votes`: Inspector's rules for them, before any rank starts ->
-    the switches as a rank process takes them (none where all three are at their defaults)."""
-    if near_score not in ("jaccard", "containment"):
-        raise ValueError(f"near_score must be 'jaccard' or 'containment', got {near_score!r}")
+def parse_near_rates(rates):
+    """`--near-rates R1,R2,...` as the command line gives it, or a sequence of numbers -> a tuple of floats; None where
+    none were given (None, "", an empty sequence)."""
+    if rates is None or len(rates) == 0:
+        return None
+    try:
+        return tuple(float(r) for r in (rates.split(",") if isinstance(rates, str) else rates))
+    except (TypeError, ValueError):
+        raise ValueError(f"near_rates must be 1..{tc.ALIGN_MAX_RATES} finite rates > 0, got {rates!r}") from None
+
+
+def check_near_switches(near_top_k, near_any_offset=False, near_score="jaccard", near_min_votes=1, near_rates=None,
+                        near_spans=False, near_parts=0) -> list:
+    """`--near-any-offset`, `--near-score`, `--near-min-votes`, `--near-rates`, `--near-spans`, `--near-parts`: Inspector's
+    rules for them, before any rank starts -> the switches as a rank process takes them (none where all are at their
+    defaults; the later three behind the earlier three)."""
+    if near_score not in ("jaccard", "containment", "local"):
+        raise ValueError(f"near_score must be 'jaccard', 'containment' or 'local', got {near_score!r}")
     if int(near_min_votes) != near_min_votes or int(near_min_votes) < 1:
         raise ValueError(f"near_min_votes must be an integer >= 1, got {near_min_votes!r}")
+    rates = parse_near_rates(near_rates)
+    if rates is not None:
+        check_near_rates(rates)
+    near_parts = near_parts or 0
+    if int(near_parts) != near_parts or (near_parts and not 2 <= int(near_parts) <= tc.ALIGN_MAX_PARTS):
+        raise ValueError(f"near_parts must be 0 (off) or 2..{tc.ALIGN_MAX_PARTS}, got {near_parts!r}")
     given = (["--near-any-offset"] if near_any_offset else []) + \
         (["--near-score", near_score] if near_score != "jaccard" else []) + \
-        (["--near-min-votes", str(int(near_min_votes))] if int(near_min_votes) != 1 else [])
+        (["--near-min-votes", str(int(near_min_votes))] if int(near_min_votes) != 1 else []) + \
+        (["--near-rates", ",".join(repr(r) for r in rates)] if rates is not None else []) + \
+        (["--near-spans"] if near_spans else []) + \
+        (["--near-parts", str(int(near_parts))] if near_parts else [])
     if given and not near_top_k:
         raise ValueError(f"{given[0]} needs --near-top-k")
     if near_score == "containment" and not near_any_offset:
         raise ValueError("--near-score containment needs --near-any-offset (the score of tvz_align_wide_topk)")
+    for on, name in ((near_score == "local", "--near-score local"), (rates is not None, "--near-rates"),
+                     (near_spans, "--near-spans")):
+        if on and not near_any_offset:
+            raise ValueError(f"{name} needs --near-any-offset (the searches with rates and spans look at any shift)")
+    if near_score == "local" and int(near_min_votes) < 2:
+        raise ValueError(f"--near-score local needs --near-min-votes >= 2 (one aligned pair scores 1.0), got {near_min_votes!r}")
+    if near_parts and near_score != "local":
+        raise ValueError(f"--near-parts {int(near_parts)} needs --near-score local")
     return given
 
 
@@ -1087,7 +1252,8 @@ class RankService:
                  tick_s: float = 0.0005, env: Optional[dict] = None, ready_timeout: float = 300.0,
                  match_tolerance: float = 0.0, match_tol_index: float = 0.0, near_top_k: int = 0,
                  near_eps: float = 1.0 / 30, near_max_offset: float = 30.0, near_jaccard: float = 0.8,
-                 near_any_offset: bool = False, near_score: str = "jaccard", near_min_votes: int = 1):
+                 near_any_offset: bool = False, near_score: str = "jaccard", near_min_votes: int = 1, near_rates=None,
+                 near_spans: bool = False, near_parts: int = 0):
         import socket
         import subprocess
         from . import db
@@ -1103,7 +1269,8 @@ class RankService:
                 raise ValueError(f"near_jaccard must be in 0..1, got {near_jaccard!r}")
             near = ["--near-top-k", str(int(near_top_k)), "--near-eps", repr(float(near_eps)),
                     "--near-max-offset", repr(float(near_max_offset)), "--near-jaccard", repr(float(near_jaccard))]
-        near += check_near_switches(near_top_k, near_any_offset, near_score, near_min_votes)
+        near += check_near_switches(near_top_k, near_any_offset, near_score, near_min_votes, near_rates, near_spans,
+                                    near_parts)
         db.create_schema(db_url)                                # once, before N processes open it side by side
         with socket.socket() as s:                              # a free rendezvous port
             s.bind(("127.0.0.1", 0))
@@ -1194,11 +1361,24 @@ def main(argv=None) -> int:  # pragma: no cover - exercised through subprocesses
                     help="the near-duplicate search at ANY shift (Inspector(near_any_offset=True)): 2^22 bins of "
                          "--near-eps on either side instead of --near-max-offset, over all shards "
                          "(tvz_align_wide_topk_sharded).  Needs --near-top-k")
-    ap.add_argument("--near-score", default="jaccard", choices=["jaccard", "containment"],
+    ap.add_argument("--near-score", default="jaccard", choices=["jaccard", "containment", "local"],
                     help="containment scores a near duplicate by the share of the SHORTER side's cuts that align (the "
-                         "excerpt of a longer video); needs --near-any-offset")
+                         "excerpt of a longer video); local by the Jaccard inside the matched span (the clip inside a "
+                         "compilation; tvz_align_span_topk_sharded) and needs --near-min-votes >= 2; both need "
+                         "--near-any-offset")
     ap.add_argument("--near-min-votes", type=int, default=1, metavar="N",
                     help="aligned cuts a reported near duplicate needs at least.  Needs --near-top-k")
+    ap.add_argument("--near-rates", default="", metavar="R1,R2,...",
+                    help="1..8 playback rates in the order of preference (stored ~= rate x upload + shift): the search for "
+                         "speed-changed copies over all shards (Inspector(near_rates=...); tvz_align_rates_topk_sharded), "
+                         "e.g. 1.0,0.96,1.0416666666666667 for 24 <-> 25 fps.  Needs --near-any-offset")
+    ap.add_argument("--near-spans", action="store_true",
+                    help="every reported near duplicate says where the copy is: upload_span and stored_span "
+                         "(Inspector(near_spans=True); tvz_align_span_topk_sharded).  Needs --near-any-offset")
+    ap.add_argument("--near-parts", type=int, default=0, metavar="P",
+                    help="2..4: every reported near duplicate is aligned in full and gains up to P parts, for the copy "
+                         "with a part put in or taken out (Inspector(near_parts=P); tvz_align_parts_sharded).  Needs "
+                         "--near-score local.  0 = off")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--rank", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--master-port", type=int, default=29500, help=argparse.SUPPRESS)
@@ -1212,7 +1392,8 @@ def main(argv=None) -> int:  # pragma: no cover - exercised through subprocesses
                       workers=a.workers, tick_s=a.tick_s, match_tolerance=a.match_tolerance,
                       match_tol_index=a.match_tol_index, near_top_k=a.near_top_k, near_eps=a.near_eps,
                       near_max_offset=a.near_max_offset, near_jaccard=a.near_jaccard,
-                      near_any_offset=a.near_any_offset, near_score=a.near_score, near_min_votes=a.near_min_votes)
+                      near_any_offset=a.near_any_offset, near_score=a.near_score, near_min_votes=a.near_min_votes,
+                      near_rates=a.near_rates, near_spans=a.near_spans, near_parts=a.near_parts)
 
     def monitor():
         while True:

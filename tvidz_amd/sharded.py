@@ -64,7 +64,7 @@ class HipBackend:
     def topk_merge(self, gathered, k):
         return tc.topk_merge(gathered, k)
 
-    align_forms = (tc.FORM_BOUNDED, tc.FORM_WIDE)     # the forms of the alignment top-k this backend answers
+    align_forms = tc.ALIGN_FORMS        # the forms of the alignment top-k this backend answers: all four
 
     def local_align(self, form, d_q, d_off, max_len, k, d_excl, **ask):
         """this rank's alignment top-k block of `form` (tvz_<stem>): int32 [Q, k+1, form.cols] on the device"""
@@ -72,6 +72,13 @@ class HipBackend:
 
     def align_merge(self, form, gathered, k, d_q, d_off, **flags):
         return tc.form_merge(form, gathered, k, d_q, d_off, **flags)
+
+    def local_parts(self, d_q, d_off, max_len, d_ids, **ask):
+        """this rank's answer to a parts call (tvz_align_parts): int32 [Q, k, 1 + max_parts, 6] on the device"""
+        return self.corpus.align_parts_block(d_q, d_off, max_len, d_ids, **ask)
+
+    def parts_merge(self, gathered):
+        return tc.align_parts_merge_device(gathered)
 
 
 class _AlignForwards:
@@ -93,9 +100,35 @@ class _AlignForwards:
         return self.align(tc.FORM_WIDE, d_queries, d_q_offsets, max_query_len, k=k, d_exclude_ids=d_exclude_ids,
                           eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score, contain=contain)
 
+    def align_rates_topk(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, eps: float,
+                         rates, max_offset: Optional[float] = None, k: int, min_votes: int = 1, min_score: int = 0,
+                         contain: bool = False, d_exclude_ids: Optional[torch.Tensor] = None):
+        """`align` for tvz_align_rates_topk: align_wide_topk for copies played at another speed -> (rows int32 [Q,k,5],
+        totals int32 [Q])."""
+        return self.align(tc.FORM_RATES, d_queries, d_q_offsets, max_query_len, k=k, d_exclude_ids=d_exclude_ids,
+                          eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score, rates=tuple(rates),
+                          contain=contain)
+
+    def align_span_topk(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, eps: float,
+                        rates=(1.0,), max_offset: Optional[float] = None, k: int, min_votes: int = 1, min_score: int = 0,
+                        contain: bool = False, local: bool = False, d_exclude_ids: Optional[torch.Tensor] = None):
+        """`align` for tvz_align_span_topk: align_rates_topk with every hit's span, scored inside it with `local` ->
+        (rows int32 [Q,k,8], totals int32 [Q])."""
+        return self.align(tc.FORM_SPAN, d_queries, d_q_offsets, max_query_len, k=k, d_exclude_ids=d_exclude_ids,
+                          eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score, rates=tuple(rates),
+                          contain=contain, local=local)
+
     @property
     def supports_align_topk(self) -> bool:
         return tc.FORM_BOUNDED in self.align_forms
+
+    @property
+    def supports_align_rates(self) -> bool:
+        return tc.FORM_RATES in self.align_forms
+
+    @property
+    def supports_align_span(self) -> bool:
+        return tc.FORM_SPAN in self.align_forms
 
     @property
     def supports_align_wide(self) -> bool:
@@ -185,6 +218,23 @@ class ShardedMatcher(_AlignForwards):
         gathered, _ = self._all_gather_blocks(local, async_op=False)
         return self.backend.align_merge(form, gathered, k, d_queries, d_q_offsets, **{n: ask[n] for n in form.flags})
 
+    @property
+    def supports_align_parts(self) -> bool:
+        """Does `parts` answer?  Only over a backend with the local call and the merge."""
+        return hasattr(self.backend, "local_parts") and hasattr(self.backend, "parts_merge")
+
+    def parts(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, d_video_ids: torch.Tensor,
+              **ask):
+        """Every aligned part of named stored videos over the sharded table (tvz_align_parts; `ask`: eps, max_offset,
+        rates, min_votes, max_parts): this rank's answer [Q, k, 1 + max_parts, 6] -> ONE all-gather -> the merge that
+        keeps, per pair, the answer with the most part-0 votes among the ranks that hold a row of the id (the lower
+        rank on a tie), sums n_rows and keeps a refusal: identical on every rank."""
+        if not self.supports_align_parts:
+            raise RuntimeError(f"{type(self.backend).__name__} has no align_parts")
+        local = self.backend.local_parts(d_queries, d_q_offsets, max_query_len, d_video_ids, **ask)
+        gathered, _ = self._all_gather_blocks(local, async_op=False)
+        return self.backend.parts_merge(gathered)
+
 
 def make_comm(device: int, group=None):
     """Create the libtvz RCCL communicator of this rank.  torch.distributed (any backend) is used
@@ -201,11 +251,11 @@ def make_comm(device: int, group=None):
 class _Slot:
     """What one of RcclShardedMatcher's side streams owns: its event, submit's workspace and (merged, totals), and
     align's own pair (its rows are the form's width and `k` is the call's own)."""
-    __slots__ = ("stream", "event", "ws", "out", "near_ws", "near_out")
+    __slots__ = ("stream", "event", "ws", "out", "near_ws", "near_out", "parts_out")
 
     def __init__(self, stream):
         self.stream, self.event = stream, torch.cuda.Event()
-        self.ws = self.out = self.near_ws = self.near_out = None
+        self.ws = self.out = self.near_ws = self.near_out = self.parts_out = None
 
 
 class RcclShardedMatcher(_AlignForwards):
@@ -362,6 +412,33 @@ class RcclShardedMatcher(_AlignForwards):
         slot.event.record(st)
         torch.cuda.current_stream(self.dev).wait_event(slot.event)
         return rows, totals
+
+
+    supports_align_parts = "tvz_align_parts_sharded" in _lib.SIGNATURES
+
+    def parts(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, d_video_ids: torch.Tensor,
+              **ask):
+        """ShardedMatcher.parts behind ONE library call (tvz_align_parts_sharded): the local tvz_align_parts ->
+        ncclAllGather of the [Q, k, 1 + max_parts, 6] answers -> the merge, on the next of the matcher's side streams
+        with the slot's near workspace; the current stream waits for it.  -> int32 [Q, k, 1 + max_parts, 6], this
+        matcher's tensor, overwritten `n_streams` calls later."""
+        if not self.supports_align_parts:
+            raise RuntimeError(f"{type(self).__name__} has no align_parts: the library has no tvz_align_parts_sharded")
+        slot = self._next_slot()
+        st = slot.stream
+        _, Q = self.corpus._check_queries(d_queries, d_q_offsets)
+        k, P = int(d_video_ids.shape[1]), int(ask["max_parts"])
+        need = tc.align_parts_sharded_workspace_bytes(Q, max_query_len, d_queries.numel(), k, P, self.world)
+        if slot.near_ws is None or slot.near_ws.numel() < need:
+            slot.near_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.dev)
+        if slot.parts_out is None or slot.parts_out.shape != (Q, k, 1 + P, 6):
+            slot.parts_out = torch.empty((Q, k, 1 + max(P, 0), 6), dtype=torch.int32, device=self.dev)
+        st.wait_stream(torch.cuda.current_stream(self.dev))       # the queries and ids are complete; the slot's last answer is read
+        out = self.comm.align_parts_sharded(self.corpus, d_queries, d_q_offsets, max_query_len, d_video_ids,
+                                            workspace=slot.near_ws, stream=st, out=slot.parts_out, **ask)
+        slot.event.record(st)
+        torch.cuda.current_stream(self.dev).wait_event(slot.event)
+        return out
 
 
 def verdicts_from_topk(merged: np.ndarray):
