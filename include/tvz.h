@@ -457,6 +457,36 @@ int tvz_align_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q_of
  * _shards, _sharded) must not be fed them: their merge rebuilds a 12-bit bin word. */
 #define TVZ_ALIGN_WIDE_MAX_B (1 << 22)   /* bins on either side of zero */
 #define TVZ_ALIGN_CONTAIN 1u             /* flags: score = v / min(nv, row_len) instead of the Jaccard */
+
+/* TVZ_ALIGN_TWO_BINS: the votes of a row counted over a window of TWO ADJACENT BINS that slides by one bin, for the
+ * copy whose true shift lies near a bin's edge: the cuts' jitter (a remux, a re-timing to another frame grid) then
+ * sends about half the votes to bin b and half to b + 1, and the best single bin holds half of them.  A flag of
+ * tvz_align_wide_topk, tvz_align_rates_topk and tvz_align_span_topk, combined freely with TVZ_ALIGN_CONTAIN and, on the
+ * span call, with TVZ_ALIGN_LOCAL (TVZ_ALIGN_CONTAIN | TVZ_ALIGN_LOCAL stays refused, with or without it).  Its value
+ * is 8: bit 4 is no flag of any call and stays refused everywhere (TVZ_ERR_INVALID), as every other unknown bit.
+ * (TVZ_VERSION unchanged; a library built before the flag existed refuses it with TVZ_ERR_INVALID.)  With the flag
+ * clear every output of every call is what it was.  With it, for a row at one rate:
+ *   counts : h[b], b in [-B, B], is the votes of bin b as above - the same expression, the same single subtraction and
+ *            single division, the same multiplication by the rate with no FMA -; outside [-B, B] h is 0.  The window
+ *            count is J[b] = h[b] + h[b + 1] for b in [-B, B], so J[B] = h[B].
+ *   best   : the most J, then the most h[b], then the bin order above (smaller |b|, then the negative one).  No votes
+ *            at all: bin 0 with 0 votes, as before.  By the second key a window whose lower bin is empty never wins
+ *            (b + 1 covers the same votes and has h > 0), so the candidates are exactly the bins with votes; a row
+ *            whose votes all lie in one bin reports that bin; with B = 0 the flag changes nothing.
+ *   block  : best_bin holds b, the window's LOWER bin, and votes holds J[b] raw.  A hit now means stored = rate x
+ *            upload + (best_bin + 0.5) x eps, within one eps.
+ *   score  : v, u, the score (Jaccard, containment or local), min_votes, min_score, the exclusion, the order tuples
+ *            and the block layouts take the new votes and best_bin and are otherwise as written for each call.
+ *   rates  : per rate the best window by the rule above; the row keeps the rate with the most J, the smaller index on
+ *            a tie.
+ *   span   : P is the pairs that vote into b or into b + 1 - the latter only where b + 1 <= B -; t_first, t_last,
+ *            c_lo, c_hi, nq and nr are defined over that P exactly as before, and TVZ_ALIGN_LOCAL scores from them.
+ *   merges : tvz_align_{wide,rates,span}_topk_merge accept the bit and ignore it - the score is rebuilt from votes, nv
+ *            and row_len, or from nq and nr, whichever way the votes were counted.  "All lists made with the same
+ *            flags" covers this bit too.  _shards and _sharded pass it to the local call and to the merge.
+ * No workspace size changes; the refusals keep their order and words; the flags are still checked where they were.
+ * Cost: two more LDS reads per bin a row touches, no pass over the bins. */
+#define TVZ_ALIGN_TWO_BINS 8u            /* flags: votes counted over two adjacent bins; best_bin = the lower one */
 size_t tvz_align_wide_topk_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t k);
 int tvz_align_wide_topk(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
                         int32_t max_query_len, double eps, double max_offset, int32_t min_votes, int32_t min_score,

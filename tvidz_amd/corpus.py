@@ -72,7 +72,9 @@ class AlignForm:
     cols: int                   # int32 columns of a row
     widest: bool                # max_offset=None means ALIGN_WIDE_MAX_B x eps
     rates: bool                 # a rate list is passed
-    flags: Tuple[str, ...]      # which of contain / local exist: () has no flags argument at all
+    flags: Tuple[str, ...]      # which of contain / local exist: () has no flags argument at all.  The score kinds: what
+    #                             a form's merge is told too
+    two_bins: bool = False      # its calls take `two_bins` (TVZ_ALIGN_TWO_BINS); its merge accepts the bit and ignores it
 
     def fn(self, suffix: str = ""):
         return getattr(_lib.load(), "tvz_" + self.stem + suffix)
@@ -84,24 +86,27 @@ class AlignForm:
 
 
 FORM_BOUNDED = AlignForm("align_topk", 4, False, False, ())
-FORM_WIDE = AlignForm("align_wide_topk", 4, True, False, ("contain",))
-FORM_RATES = AlignForm("align_rates_topk", 5, True, True, ("contain",))
-FORM_SPAN = AlignForm("align_span_topk", 8, True, True, ("contain", "local"))
+FORM_WIDE = AlignForm("align_wide_topk", 4, True, False, ("contain",), True)
+FORM_RATES = AlignForm("align_rates_topk", 5, True, True, ("contain",), True)
+FORM_SPAN = AlignForm("align_span_topk", 8, True, True, ("contain", "local"), True)
 ALIGN_FORMS = (FORM_BOUNDED, FORM_WIDE, FORM_RATES, FORM_SPAN)
 
 
-def _align_args(f: AlignForm, eps, max_offset, min_votes, min_score, rates=None, contain=False, local=False) -> list:
+def _align_args(f: AlignForm, eps, max_offset, min_votes, min_score, rates=None, contain=False, local=False,
+                two_bins=False) -> list:
     """What a form's call, its _shards and its _sharded take between max_query_len and the exclusions, in the ABI's
     order: eps, max_offset, [h_rates, n_rates,] min_votes, min_score, [flags]."""
     a = [float(eps), _wide_offset(eps, max_offset) if f.widest else float(max_offset)]
     if f.rates:
         a += _rates(rates)
-    return a + [int(min_votes), int(min_score)] + _align_flags(f, contain, local)
+    return a + [int(min_votes), int(min_score)] + _align_flags(f, contain, local, two_bins)
 
 
-def _align_flags(f: AlignForm, contain=False, local=False) -> list:
+def _align_flags(f: AlignForm, contain=False, local=False, two_bins=False) -> list:
     """The flags argument of a form's calls and of its merge: none at all for the form without flags."""
-    return [_span_flags(contain, local)] if f.flags else []
+    if two_bins and not f.two_bins:
+        raise ValueError(f"tvz_{f.stem} has no TVZ_ALIGN_TWO_BINS")
+    return [_span_flags(contain, local, two_bins)] if f.flags else []
 
 
 def form_workspace_bytes(f: AlignForm, Q: int, max_query_len: int, total_query_keys: int, k: int,
@@ -160,6 +165,8 @@ def align_wide_topk_sharded_workspace_bytes(Q: int, max_query_len: int, total_qu
 
 ALIGN_WIDE_MAX_B = 1 << 22                  # include/tvz.h TVZ_ALIGN_WIDE_MAX_B: tvz_align_wide_topk's bins per side
 ALIGN_CONTAIN = 1                           # include/tvz.h TVZ_ALIGN_CONTAIN
+ALIGN_TWO_BINS = 8                          # include/tvz.h TVZ_ALIGN_TWO_BINS: votes counted over two adjacent bins, best_bin
+#                                             the lower one (4 is no flag).  `two_bins=True` of the wide, rates and span calls
 
 
 def align_containment(votes: int, nv: int, row_len: int) -> int:
@@ -236,8 +243,8 @@ def align_span_order_key(row, nv: int, contain: bool = False, local: bool = Fals
     return head + (t_first, t_last, nr)
 
 
-def _span_flags(contain: bool, local: bool) -> int:
-    return (ALIGN_CONTAIN if contain else 0) | (ALIGN_LOCAL if local else 0)
+def _span_flags(contain: bool, local: bool, two_bins: bool = False) -> int:
+    return (ALIGN_CONTAIN if contain else 0) | (ALIGN_LOCAL if local else 0) | (ALIGN_TWO_BINS if two_bins else 0)
 
 
 ALIGN_MAX_PARTS, ALIGN_PARTS_MAX_ROWS = 4, 8     # include/tvz.h TVZ_ALIGN_MAX_PARTS, TVZ_ALIGN_PARTS_MAX_ROWS
@@ -526,26 +533,31 @@ class DeviceCorpus:
     supports_align_wide = True
 
     def align_wide_topk(self, queries, *, eps: float, max_offset: Optional[float] = None, k: int = 16, min_votes: int = 1,
-                        min_score: int = 0, contain: bool = False, exclude_ids=None,
+                        min_score: int = 0, contain: bool = False, two_bins: bool = False, exclude_ids=None,
                         max_query_len: Optional[int] = None):
         """tvz_align_wide_topk: align_topk at any shift - up to ALIGN_WIDE_MAX_B offset bins on either side of zero
         (`max_offset=None`: ALIGN_WIDE_MAX_B x eps, the widest the library takes).  `contain=True` scores by
         v / min(nv, row_len) (align_containment) instead of the tolerant Jaccard, for the excerpt of a longer video.
+        `two_bins=True` (TVZ_ALIGN_TWO_BINS; the calls with rates and spans take it too) counts a row's votes over the
+        best window of two adjacent bins - best_bin is then the window's LOWER bin, votes the window's count, the
+        shift (best_bin + 0.5) x eps - for the copy whose shift lies near a bin's edge.
         Arguments and (rows, totals) otherwise as align_topk; order: align_wide_order_key."""
         return self._align_host(FORM_WIDE, queries, k, exclude_ids, max_query_len, eps=eps, max_offset=max_offset,
-                                min_votes=min_votes, min_score=min_score, contain=contain)
+                                min_votes=min_votes, min_score=min_score, contain=contain, two_bins=two_bins)
 
     def align_wide_topk_block(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, eps: float,
                               max_offset: Optional[float] = None, k: int, min_votes: int = 1, min_score: int = 0,
-                              contain: bool = False, d_exclude_ids: Optional[torch.Tensor] = None,
+                              contain: bool = False, two_bins: bool = False, d_exclude_ids: Optional[torch.Tensor] = None,
                               out: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
                               workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
         """tvz_align_wide_topk, device in / device out: enqueue Q queries -> the block int32 [Q, k+1, 4]."""
         return self._align_block(FORM_WIDE, d_queries, d_q_offsets, max_query_len, k, d_exclude_ids, out, stream, workspace,
-                                 eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score, contain=contain)
+                                 eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score, contain=contain,
+                                 two_bins=two_bins)
 
     def align_rates_topk(self, queries, *, eps: float, rates: Sequence[float], max_offset: Optional[float] = None,
-                         k: int = 16, min_votes: int = 1, min_score: int = 0, contain: bool = False, exclude_ids=None,
+                         k: int = 16, min_votes: int = 1, min_score: int = 0, contain: bool = False,
+                         two_bins: bool = False, exclude_ids=None,
                          max_query_len: Optional[int] = None):
         """tvz_align_rates_topk: align_wide_topk for copies played at another speed - every row is aligned once per
         rate of `rates` (1..ALIGN_MAX_RATES finite values > 0, in the order of preference; the query's cuts are scaled:
@@ -553,20 +565,22 @@ class DeviceCorpus:
         align_wide_topk.  -> (rows int32[Q, k, 5] of (video_id, row_len, best_bin, votes, rate_index), padded with
         (-1, 0, 0, 0, 0); totals int32[Q]); order: align_rates_order_key."""
         return self._align_host(FORM_RATES, queries, k, exclude_ids, max_query_len, eps=eps, max_offset=max_offset,
-                                min_votes=min_votes, min_score=min_score, rates=rates, contain=contain)
+                                min_votes=min_votes, min_score=min_score, rates=rates, contain=contain, two_bins=two_bins)
 
     def align_rates_topk_block(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, eps: float,
                                rates: Sequence[float], max_offset: Optional[float] = None, k: int, min_votes: int = 1,
-                               min_score: int = 0, contain: bool = False, d_exclude_ids: Optional[torch.Tensor] = None,
+                               min_score: int = 0, contain: bool = False,
+                               two_bins: bool = False, d_exclude_ids: Optional[torch.Tensor] = None,
                                out: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
                                workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
         """tvz_align_rates_topk, device in / device out: enqueue Q queries -> the block int32 [Q, k+1, 5]."""
         return self._align_block(FORM_RATES, d_queries, d_q_offsets, max_query_len, k, d_exclude_ids, out, stream, workspace,
                                  eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score, rates=rates,
-                                 contain=contain)
+                                 contain=contain, two_bins=two_bins)
 
     def align_span_topk(self, queries, *, eps: float, rates: Sequence[float] = (1.0,), max_offset: Optional[float] = None,
                         k: int = 16, min_votes: int = 1, min_score: int = 0, contain: bool = False, local: bool = False,
+                        two_bins: bool = False,
                         exclude_ids=None, max_query_len: Optional[int] = None):
         """tvz_align_span_topk: align_rates_topk that also says WHERE the best bin's votes lie - (t_first, t_last), the
         first and last voting index of the query's non-NaN values sorted ascending, and nr, the row's keys between the
@@ -575,18 +589,20 @@ class DeviceCorpus:
         int32[Q, k, 8] of (video_id, row_len, best_bin, votes, rate_index, t_first, t_last, nr), padded with (-1, 0, ..);
         totals int32[Q]); order: align_span_order_key."""
         return self._align_host(FORM_SPAN, queries, k, exclude_ids, max_query_len, eps=eps, max_offset=max_offset,
-                                min_votes=min_votes, min_score=min_score, rates=rates, contain=contain, local=local)
+                                min_votes=min_votes, min_score=min_score, rates=rates, contain=contain, local=local,
+                                two_bins=two_bins)
 
     def align_span_topk_block(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, eps: float,
                               rates: Sequence[float] = (1.0,), max_offset: Optional[float] = None, k: int,
                               min_votes: int = 1, min_score: int = 0, contain: bool = False, local: bool = False,
+                              two_bins: bool = False,
                               d_exclude_ids: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
                               stream: Optional[torch.cuda.Stream] = None,
                               workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
         """tvz_align_span_topk, device in / device out: enqueue Q queries -> the block int32 [Q, k+1, 8]."""
         return self._align_block(FORM_SPAN, d_queries, d_q_offsets, max_query_len, k, d_exclude_ids, out, stream, workspace,
                                  eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score, rates=rates,
-                                 contain=contain, local=local)
+                                 contain=contain, local=local, two_bins=two_bins)
 
     def align_parts(self, queries, video_ids, *, eps: float, max_offset: Optional[float] = None,
                     rates: Sequence[float] = (1.0,), min_votes: int, max_parts: int,
@@ -812,7 +828,7 @@ class Comm:
 
     def align_wide_topk_sharded(self, corpus: DeviceCorpus, d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
                                 max_query_len: int, *, eps: float, max_offset: Optional[float] = None, k: int,
-                                min_votes: int = 1, min_score: int = 0, contain: bool = False,
+                                min_votes: int = 1, min_score: int = 0, contain: bool = False, two_bins: bool = False,
                                 d_exclude_ids: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
                                 stream: Optional[torch.cuda.Stream] = None,
                                 out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
@@ -821,11 +837,11 @@ class Comm:
         on every rank."""
         return self.align_sharded(FORM_WIDE, corpus, d_queries, d_q_offsets, max_query_len, k, d_exclude_ids, workspace,
                                    stream, out, eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score,
-                                   contain=contain)
+                                   contain=contain, two_bins=two_bins)
 
     def align_rates_topk_sharded(self, corpus: DeviceCorpus, d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
                                  max_query_len: int, *, eps: float, rates: Sequence[float], max_offset: Optional[float] = None,
-                                 k: int, min_votes: int = 1, min_score: int = 0, contain: bool = False,
+                                 k: int, min_votes: int = 1, min_score: int = 0, contain: bool = False, two_bins: bool = False,
                                  d_exclude_ids: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
                                  stream: Optional[torch.cuda.Stream] = None,
                                  out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
@@ -833,19 +849,20 @@ class Comm:
         its merge; -> (rows int32 [Q,k,5], totals int32 [Q]), identical on every rank."""
         return self.align_sharded(FORM_RATES, corpus, d_queries, d_q_offsets, max_query_len, k, d_exclude_ids, workspace,
                                    stream, out, eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score,
-                                   rates=rates, contain=contain)
+                                   rates=rates, contain=contain, two_bins=two_bins)
 
     def align_span_topk_sharded(self, corpus: DeviceCorpus, d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
                                 max_query_len: int, *, eps: float, rates: Sequence[float] = (1.0,),
                                 max_offset: Optional[float] = None, k: int, min_votes: int = 1, min_score: int = 0,
-                                contain: bool = False, local: bool = False, d_exclude_ids: Optional[torch.Tensor] = None,
+                                contain: bool = False, local: bool = False,
+                                two_bins: bool = False, d_exclude_ids: Optional[torch.Tensor] = None,
                                 workspace: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
                                 out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
         """tvz_align_span_topk_sharded: the local alignment top-k with spans -> ncclAllGather of the [Q,k+1,8] blocks ->
         its merge; -> (rows int32 [Q,k,8], totals int32 [Q]), identical on every rank."""
         return self.align_sharded(FORM_SPAN, corpus, d_queries, d_q_offsets, max_query_len, k, d_exclude_ids, workspace,
                                    stream, out, eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score,
-                                   rates=rates, contain=contain, local=local)
+                                   rates=rates, contain=contain, local=local, two_bins=two_bins)
 
     def align_parts_sharded(self, corpus: DeviceCorpus, d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
                             max_query_len: int, d_video_ids: torch.Tensor, *, eps: float, max_offset: Optional[float] = None,
@@ -1006,65 +1023,74 @@ def align_topk_shards(shards: Sequence["DeviceCorpus"], d_queries: torch.Tensor,
 
 
 def align_wide_topk_merge(gathered: torch.Tensor, k: int, d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
-                          contain: bool = False, stream: Optional[torch.cuda.Stream] = None, out=None):
+                          contain: bool = False, stream: Optional[torch.cuda.Stream] = None, out=None,
+                          two_bins: bool = False):
     """tvz_align_wide_topk_merge: align_topk_merge for the blocks of align_wide_topk_block - bins anywhere in
     +-ALIGN_WIDE_MAX_B, every list sorted by align_wide_order_key of the SAME `contain`."""
-    return form_merge(FORM_WIDE, gathered, k, d_queries, d_q_offsets, stream, out, contain=contain)
+    return form_merge(FORM_WIDE, gathered, k, d_queries, d_q_offsets, stream, out, contain=contain, two_bins=two_bins)
 
 
 def align_wide_topk_shards(shards: Sequence["DeviceCorpus"], d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
                            max_query_len: int, *, eps: float, max_offset: Optional[float] = None, k: int,
                            workspace: torch.Tensor, min_votes: int = 1, min_score: int = 0, contain: bool = False,
+                           two_bins: bool = False,
                            d_exclude_ids: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None):
     """tvz_align_wide_topk on every handle of ONE device + the wide merge behind one library call
     (tvz_align_wide_topk_shards): -> (blocks int32 [R,Q,k+1,4], rows int32 [Q,k,4], totals int32 [Q]).  `workspace`:
     align_wide_topk_workspace_bytes (its size is the library's to judge, as align_topk_shards')."""
     return form_shards(FORM_WIDE, shards, d_queries, d_q_offsets, max_query_len, k, workspace, d_exclude_ids, stream,
-                       eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score, contain=contain)
+                       eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score, contain=contain,
+                       two_bins=two_bins)
 
 
 def align_rates_topk_merge(gathered: torch.Tensor, k: int, d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
-                           contain: bool = False, stream: Optional[torch.cuda.Stream] = None, out=None):
+                           contain: bool = False, stream: Optional[torch.cuda.Stream] = None, out=None,
+                          two_bins: bool = False):
     """tvz_align_rates_topk_merge: align_wide_topk_merge for the blocks of align_rates_topk_block, int32 [R,Q,k+1,5] ->
     (rows int32 [Q,k,5], totals int32 [Q]); every list sorted by align_rates_order_key of the SAME `contain`, made
     with the same rate list (the rate index is carried, never read)."""
-    return form_merge(FORM_RATES, gathered, k, d_queries, d_q_offsets, stream, out, contain=contain)
+    return form_merge(FORM_RATES, gathered, k, d_queries, d_q_offsets, stream, out, contain=contain, two_bins=two_bins)
 
 
 def align_rates_topk_shards(shards: Sequence["DeviceCorpus"], d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
                             max_query_len: int, *, eps: float, rates: Sequence[float], max_offset: Optional[float] = None,
                             k: int, workspace: torch.Tensor, min_votes: int = 1, min_score: int = 0, contain: bool = False,
+                            two_bins: bool = False,
                             d_exclude_ids: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None):
     """tvz_align_rates_topk on every handle of ONE device + its merge behind one library call
     (tvz_align_rates_topk_shards): -> (blocks int32 [R,Q,k+1,5], rows int32 [Q,k,5], totals int32 [Q]).  `workspace`:
     align_rates_topk_workspace_bytes (its size is the library's to judge, as align_topk_shards')."""
     return form_shards(FORM_RATES, shards, d_queries, d_q_offsets, max_query_len, k, workspace, d_exclude_ids, stream,
-                       eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score, rates=rates, contain=contain)
+                       eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score, rates=rates, contain=contain,
+                       two_bins=two_bins)
 
 
 def align_span_topk_merge(gathered: torch.Tensor, k: int, d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
-                          contain: bool = False, local: bool = False, stream: Optional[torch.cuda.Stream] = None, out=None):
+                          contain: bool = False, local: bool = False, stream: Optional[torch.cuda.Stream] = None, out=None,
+                          two_bins: bool = False):
     """tvz_align_span_topk_merge: align_rates_topk_merge for the blocks of align_span_topk_block, int32 [R,Q,k+1,8] ->
     (rows int32 [Q,k,8], totals int32 [Q]); every list sorted by align_span_order_key of the SAME `contain` / `local`.
     With `local` the score is rebuilt from votes, t_last - t_first + 1 and nr; otherwise the span is only carried."""
-    return form_merge(FORM_SPAN, gathered, k, d_queries, d_q_offsets, stream, out, contain=contain, local=local)
+    return form_merge(FORM_SPAN, gathered, k, d_queries, d_q_offsets, stream, out, contain=contain, local=local,
+    two_bins=two_bins)
 
 
 def align_span_topk_shards(shards: Sequence["DeviceCorpus"], d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
                            max_query_len: int, *, eps: float, rates: Sequence[float] = (1.0,),
                            max_offset: Optional[float] = None, k: int, workspace: torch.Tensor, min_votes: int = 1,
-                           min_score: int = 0, contain: bool = False, local: bool = False,
+                           min_score: int = 0, contain: bool = False, local: bool = False, two_bins: bool = False,
                            d_exclude_ids: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None):
     """tvz_align_span_topk on every handle of ONE device + its merge behind one library call
     (tvz_align_span_topk_shards): -> (blocks int32 [R,Q,k+1,8], rows int32 [Q,k,8], totals int32 [Q]).  `workspace`:
     align_span_topk_workspace_bytes (its size is the library's to judge, as align_topk_shards')."""
     return form_shards(FORM_SPAN, shards, d_queries, d_q_offsets, max_query_len, k, workspace, d_exclude_ids, stream,
                        eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score, rates=rates, contain=contain,
-                       local=local)
+                       local=local, two_bins=two_bins)
 
 
 def form_merge(f: AlignForm, gathered: torch.Tensor, k: int, d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
-               stream: Optional[torch.cuda.Stream] = None, out=None, contain: bool = False, local: bool = False):
+               stream: Optional[torch.cuda.Stream] = None, out=None, contain: bool = False, local: bool = False,
+               two_bins: bool = False):
     """tvz_<stem>_merge of any form: the blocks int32 [R,Q,k+1,cols] -> (rows int32 [Q,k,cols], totals int32 [Q])."""
     R, Q, k1, w = gathered.shape
     if k1 != k + 1 or w != f.cols or gathered.dtype != torch.int32 or not gathered.is_contiguous():
@@ -1072,7 +1098,8 @@ def form_merge(f: AlignForm, gathered: torch.Tensor, k: int, d_queries: torch.Te
     rows, totals = _topk_out(out, Q, k, f.cols, gathered.device)
     s = stream if stream is not None else torch.cuda.current_stream(gathered.device)
     with torch.cuda.device(gathered.device):
-        _lib.check(f.fn("_merge")(gathered.data_ptr(), R, Q, int(k), *_align_flags(f, contain, local), d_queries.data_ptr(),
+        _lib.check(f.fn("_merge")(gathered.data_ptr(), R, Q, int(k), *_align_flags(f, contain, local, two_bins),
+                                  d_queries.data_ptr(),
                                   d_q_offsets.data_ptr(), rows.data_ptr(), totals.data_ptr(), s.cuda_stream))
     return rows, totals
 

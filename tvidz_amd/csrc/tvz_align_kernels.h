@@ -59,6 +59,16 @@
 // once more at that single bin (al_span) for the first and last voting index of the sorted query and the count of
 // row keys between the smallest and the largest voting key.  The kept hit carries them behind the rate's index (AsHit),
 // the block has eight columns, and with TVZ_ALIGN_LOCAL the score is the Jaccard of the two sides inside the span.
+//
+// Two bins (al_sweep<.., kTwoBins = true>, TVZ_ALIGN_TWO_BINS on the three calls above): the row's best
+// WINDOW of two adjacent bins, J[b] = h[b] + h[b + 1], ordered by (J, h[b], the bin order) - for the copy whose shift
+// lies near a bin's edge.  A window needs two bins' FINAL counts, so the lane-wise best of the vote loop is not
+// taken; behind the fence that precedes the clearing every lane reads h[s] and h[s + 1] for its slots of the touched
+// list - the candidates are exactly the touched bins, the second key rules a window with an empty lower bin out - and
+// keeps the best.  The windows descend, so the bin above a window's last slot is the lowest bin of the window visited
+// before: its count is carried in one word per wave, 0 for the first window of a rate.  The kept hit holds the
+// window's lower bin and J; the span walks the two bins.  Kernels of their own (ts_align{w,r,s}2_sweep_kernel): the
+// single-bin sweeps keep their machine code.
 #pragma once
 #include "tvz_match_kernels.h"
 #include "tvz_tol_kernels.h"
@@ -85,6 +95,7 @@ constexpr int kAwResume = 512;                         // keys of a row whose re
 constexpr uint32_t kAwContain = 1u;                    // TVZ_ALIGN_CONTAIN
 constexpr int kArMaxRates = 8;                         // TVZ_ALIGN_MAX_RATES
 constexpr uint32_t kAsLocal = 2u;                      // TVZ_ALIGN_LOCAL
+constexpr uint32_t kAlTwoBins = 8u;                    // TVZ_ALIGN_TWO_BINS (4 is no flag, and stays refused)
 
 // the rates of tvz_align_rates_topk, a kernel argument by value: r[0 .. n), each finite and > 0 (the host's check)
 struct AlRates {
@@ -456,19 +467,21 @@ struct AlExtremes {
     int t_first, t_last;
     double c_lo, c_hi;
 };
-template <class Allow>
+template <class Allow, bool kTwoBins = false>
 __device__ __forceinline__ AlExtremes al_bin_extremes(const int64_t *__restrict__ rk, int len, const double *s, int m, double eps,
-                                                      int bin, double rho, const Allow &allow, int lane) {
+                                                      int bin, double rho, const Allow &allow, int lane, int bin_hi = 0) {
     const double bd = (double)bin;
+    double hd = bd;                                                           // kTwoBins: the bins [bin, bin_hi], bin_hi = bin
+    if constexpr (kTwoBins) hd = (double)bin_hi;                              // or bin + 1; the one bin otherwise
     int t_first = m, t_last = -1;
     double c_lo = __longlong_as_double(0x7ff0000000000000ll), c_hi = -c_lo;
     for (int j = lane; j < len; j += 64) {
         const double c = __longlong_as_double(rk[j]);
         if (!allow.key(c)) continue;
-        for (int t = al_lo<true>(s, m, c, eps, bd, rho); t < m; ++t) {
+        for (int t = al_lo<true>(s, m, c, eps, hd, rho); t < m; ++t) {
             const double d = al_bin(c, al_x<true>(s, t, rho), eps);
             if (!(d >= bd)) break;                                        // behind the bin (or NaN there)
-            if (!(d <= bd) || !allow.index(t)) continue;                  // (the first: never, behind al_lo)
+            if (!(d <= hd) || !allow.index(t)) continue;                  // (the first: never, behind al_lo)
             t_first = t < t_first ? t : t_first;
             t_last = t > t_last ? t : t_last;
             c_lo = c < c_lo ? c : c_lo;
@@ -492,9 +505,10 @@ struct AlSpan {
     int t_first, t_last;
     uint32_t nr;
 };
+template <bool kTwoBins = false>
 __device__ __forceinline__ AlSpan al_span(const int64_t *__restrict__ rk, int len, const double *s, int m, double eps, int bin,
-                                          double rho, int lane) {
-    const AlExtremes x = al_bin_extremes(rk, len, s, m, eps, bin, rho, AlAllPairs{}, lane);
+                                          double rho, int lane, int bin_hi = 0) {
+    const AlExtremes x = al_bin_extremes<AlAllPairs, kTwoBins>(rk, len, s, m, eps, bin, rho, AlAllPairs{}, lane, bin_hi);
     uint32_t nr = 0;
     for (int j = lane; j < len; j += 64) {
         const double c = __longlong_as_double(rk[j]);
@@ -510,8 +524,9 @@ __device__ __forceinline__ AlSpan al_span(const int64_t *__restrict__ rk, int le
 // and B <= 2047 where !kWindowed (the host refuses anything else before the launch).  kRates: the row is walked once
 // per rate of `rates` (1 .. kArMaxRates of them) and its best rate kept; without, `rates` is never read.  kSpan (with
 // kRates; Hit = AsHit): a row that can be a hit is walked once more at its best bin and rate for the span (al_span),
-// and with `local` the score is the Jaccard inside the span.
-template <class Hit, bool kWindowed, bool kRates = false, bool kSpan = false>
+// and with `local` the score is the Jaccard inside the span.  kTwoBins (with kWindowed): the row's best window of two
+// adjacent bins instead of its best bin (the header comment); nothing of it is compiled into the other sweeps.
+template <class Hit, bool kWindowed, bool kRates = false, bool kSpan = false, bool kTwoBins = false>
 __device__ __forceinline__ void al_sweep(const Row *__restrict__ rows, int64_t n_rows, const int64_t *__restrict__ keys,
                                          const double *__restrict__ sv, const int64_t *__restrict__ q_offsets,
                                          const int32_t *__restrict__ qm, int32_t lds_keys, double eps, int32_t B, int32_t width,
@@ -582,6 +597,10 @@ __device__ __forceinline__ void al_sweep(const Row *__restrict__ rows, int64_t n
                 w1 = w1 < w.max_windows - 1 ? w1 : w.max_windows - 1;         // (never: (2B) / w.width is the last window)
             }
             unsigned long long rbest = 0;                                     // of this rate
+            // kTwoBins: the lane's best window (J, h << 33 | 2^33 - 1 - order), and the count of the bin above the
+            // window's top slot - the lowest bin of the window visited before (the one above), 0 for the first
+            [[maybe_unused]] uint32_t jbest = 0;
+            [[maybe_unused]] uint32_t carry = 0;
             for (int wi = w1; wi >= w0; --wi) {                               // wave-uniform, at most w.max_windows rounds
                 int w_lo = -B, w_hi = B;
                 if constexpr (kWindowed) {
@@ -602,9 +621,11 @@ __device__ __forceinline__ void al_sweep(const Row *__restrict__ rows, int64_t n
                         const uint32_t slot = (uint32_t)(bin - w_lo);         // 0 .. w.width - 1
                         const uint32_t cnt = atomicAdd(&w.hist[slot], 1u) + 1u;
                         if (cnt == 1u) w.dirty[atomicAdd(w.n_dirty, 1u)] = (uint16_t)slot;  // at most once per slot: < w.width
-                        const uint32_t order = 2u * (uint32_t)(bin < 0 ? -bin : bin) + (bin > 0 ? 1u : 0u);
-                        const unsigned long long key = ((unsigned long long)cnt << 33) | (kAlOrderMask - order);
-                        rbest = key > rbest ? key : rbest;
+                        if constexpr (!kTwoBins) {
+                            const uint32_t order = 2u * (uint32_t)(bin < 0 ? -bin : bin) + (bin > 0 ? 1u : 0u);
+                            const unsigned long long key = ((unsigned long long)cnt << 33) | (kAlOrderMask - order);
+                            rbest = key > rbest ? key : rbest;
+                        }
                     }
                     if constexpr (kWindowed) {
                         if (kept_pos) w.resume[j] = (uint16_t)t;              // t <= m <= 4095
@@ -613,13 +634,42 @@ __device__ __forceinline__ void al_sweep(const Row *__restrict__ rows, int64_t n
                 // LDS ops of one wave complete in order: the notes above are visible to the clearing below
                 wave_lds_fence();
                 const int nd = (int)*w.n_dirty;
+                if constexpr (kTwoBins) {
+                    // every count is final: the window of two bins that starts at each touched bin, J = h[b] + h[b + 1].
+                    // Slot + 1 inside the histogram is bin b + 1 or a slot no vote reaches (beyond B: 0); behind its
+                    // last slot b + 1 is the lowest bin of the window above, whose count is the carry
+                    for (int i = lane; i < nd; i += 64) {
+                        const int slot = (int)w.dirty[i];                     // < w.width
+                        const uint32_t h = w.hist[slot];
+                        const uint32_t up = slot + 1 < w.width ? w.hist[slot + 1] : carry;
+                        const int bin = w_lo + slot;
+                        const uint32_t order = 2u * (uint32_t)(bin < 0 ? -bin : bin) + (bin > 0 ? 1u : 0u);
+                        const uint32_t j = h + up;
+                        const unsigned long long key = ((unsigned long long)h << 33) | (kAlOrderMask - order);
+                        const bool better = j > jbest || (j == jbest && key > rbest);
+                        jbest = better ? j : jbest;
+                        rbest = better ? key : rbest;
+                    }
+                    carry = w.hist[0];                                        // (the same word in every lane)
+                }
                 for (int i = lane; i < nd; i += 64) w.hist[w.dirty[i]] = 0;
                 wave_lds_fence();
                 if (lane == 0) *w.n_dirty = 0;
             }
-            for (int off = 32; off > 0; off >>= 1) {
-                const unsigned long long o = __shfl_xor(rbest, off);
-                rbest = o > rbest ? o : rbest;
+            if constexpr (kTwoBins) {
+                for (int off = 32; off > 0; off >>= 1) {
+                    const uint32_t oj = __shfl_xor(jbest, off);
+                    const unsigned long long o = __shfl_xor(rbest, off);
+                    const bool better = oj > jbest || (oj == jbest && o > rbest);
+                    jbest = better ? oj : jbest;
+                    rbest = better ? o : rbest;
+                }
+                rbest = ((unsigned long long)jbest << 33) | (rbest & kAlOrderMask);   // the window's count and its lower bin
+            } else {
+                for (int off = 32; off > 0; off >>= 1) {
+                    const unsigned long long o = __shfl_xor(rbest, off);
+                    rbest = o > rbest ? o : rbest;
+                }
             }
             if constexpr (kRates) {
                 if ((rbest >> 33) > (best >> 33)) {                           // strictly more votes: a tie keeps the
@@ -642,7 +692,9 @@ __device__ __forceinline__ void al_sweep(const Row *__restrict__ rows, int64_t n
                 // can still be a hit - the local score is made from the span, every other score decides first
                 if (local || score >= (uint32_t)min_score) {
                     const int bin = al_best_bin(best);
-                    const AlSpan sp = al_span(rk, row.len, s, m, eps, bin, rates.r[best_rate], lane);
+                    // kTwoBins: the pairs of the window's two bins, the upper one only inside the range
+                    const AlSpan sp = al_span<kTwoBins>(rk, row.len, s, m, eps, bin, rates.r[best_rate], lane,
+                                                        bin < B ? bin + 1 : bin);
                     if (local) {                                            // 1 <= nq <= m, 1 <= nr <= rl: v only shrinks
                         const uint32_t nq = (uint32_t)(sp.t_last - sp.t_first + 1);
                         v = votes < nq ? votes : nq;
@@ -698,7 +750,8 @@ __device__ __forceinline__ void al_reduce(typename Hit::ConstParts part, int32_t
     if (wv == 0) al_write_block(kept, d_out + (int64_t)q * (k + 1) * Hit::kCols, k, lane, refused ? INT32_MIN : totals[q]);
 }
 
-// The eight entry points only forward.  part_w / part_p: uint64[Q][n_lists][k], part_v / part_r: uint32[Q][n_lists][k].
+// The eight entry points only forward (and the three of TVZ_ALIGN_TWO_BINS behind them).  part_w / part_p:
+// uint64[Q][n_lists][k], part_v / part_r: uint32[Q][n_lists][k].
 __global__ __launch_bounds__(kAlBlock) void ts_align_topk_kernel(
     const Row *__restrict__ rows, int64_t n_rows, const int64_t *__restrict__ keys, const double *__restrict__ sv,
     const int64_t *__restrict__ q_offsets, const int32_t *__restrict__ qm, int32_t lds_keys, double eps, int32_t B,
@@ -773,6 +826,44 @@ __global__ __launch_bounds__(kAlReduceBlock) void ts_aligns_reduce_kernel(
     const int32_t *__restrict__ totals, int32_t *__restrict__ d_out) {
     al_reduce<AsHit>(AsHit::ConstParts{part_w, part_p, part_v, part_r, part_t, part_n}, n_lists, k, qm, lds_keys, totals,
                      d_out);
+}
+
+// The sweeps under TVZ_ALIGN_TWO_BINS: the three above with al_sweep's kTwoBins, kernels of their own so
+// that the ones above keep their code.  Their lists go through the same selections and merges.
+__global__ __launch_bounds__(kAlBlock) void ts_alignw2_sweep_kernel(
+    const Row *__restrict__ rows, int64_t n_rows, const int64_t *__restrict__ keys, const double *__restrict__ sv,
+    const int64_t *__restrict__ q_offsets, const int32_t *__restrict__ qm, int32_t lds_keys, double eps, int32_t B,
+    int32_t width, int32_t min_votes, int32_t min_score, uint32_t flags, const int32_t *__restrict__ exclude_ids,
+    int32_t k, unsigned long long *__restrict__ part_w, unsigned long long *__restrict__ part_p,
+    uint32_t *__restrict__ part_v, int32_t n_lists, int32_t *__restrict__ totals) {
+    al_sweep<AwHit, true, false, false, true>(rows, n_rows, keys, sv, q_offsets, qm, lds_keys, eps, B, width, min_votes,
+                                              min_score, (flags & kAwContain) != 0u, exclude_ids, k,
+                                              AwHit::Parts{part_w, part_p, part_v}, n_lists, totals);
+}
+
+__global__ __launch_bounds__(kAlBlock) void ts_alignr2_sweep_kernel(
+    const Row *__restrict__ rows, int64_t n_rows, const int64_t *__restrict__ keys, const double *__restrict__ sv,
+    const int64_t *__restrict__ q_offsets, const int32_t *__restrict__ qm, int32_t lds_keys, double eps, int32_t B,
+    int32_t width, AlRates rates, int32_t min_votes, int32_t min_score, uint32_t flags,
+    const int32_t *__restrict__ exclude_ids, int32_t k, unsigned long long *__restrict__ part_w,
+    unsigned long long *__restrict__ part_p, uint32_t *__restrict__ part_v, uint32_t *__restrict__ part_r, int32_t n_lists,
+    int32_t *__restrict__ totals) {
+    al_sweep<ArHit, true, true, false, true>(rows, n_rows, keys, sv, q_offsets, qm, lds_keys, eps, B, width, min_votes,
+                                             min_score, (flags & kAwContain) != 0u, exclude_ids, k,
+                                             ArHit::Parts{part_w, part_p, part_v, part_r}, n_lists, totals, rates);
+}
+
+__global__ __launch_bounds__(kAlBlock) void ts_aligns2_sweep_kernel(
+    const Row *__restrict__ rows, int64_t n_rows, const int64_t *__restrict__ keys, const double *__restrict__ sv,
+    const int64_t *__restrict__ q_offsets, const int32_t *__restrict__ qm, int32_t lds_keys, double eps, int32_t B,
+    int32_t width, AlRates rates, int32_t min_votes, int32_t min_score, uint32_t flags,
+    const int32_t *__restrict__ exclude_ids, int32_t k, unsigned long long *__restrict__ part_w,
+    unsigned long long *__restrict__ part_p, uint32_t *__restrict__ part_v, uint32_t *__restrict__ part_r,
+    uint32_t *__restrict__ part_t, uint32_t *__restrict__ part_n, int32_t n_lists, int32_t *__restrict__ totals) {
+    al_sweep<AsHit, true, true, true, true>(rows, n_rows, keys, sv, q_offsets, qm, lds_keys, eps, B, width, min_votes,
+                                            min_score, (flags & kAwContain) != 0u, exclude_ids, k,
+                                            AsHit::Parts{part_w, part_p, part_v, part_r, part_t, part_n}, n_lists, totals,
+                                            rates, (flags & kAsLocal) != 0u);
 }
 
 // ---- the merge of the shards' blocks (every form's tvz_align_*_topk_merge) -------------------------------------------

@@ -2125,10 +2125,11 @@ constexpr AlignTopkForm kAlignForms[] = {
      }},
     // kAlignWide: tvz_align_wide_topk
     {4, 1, false, false, "wide alignment top-k", "tvz_align_wide_topk_workspace_bytes",
-     "tvz_align_wide_topk_sharded_workspace_bytes", 2 * kAwMaxB + 1, "TVZ_ALIGN_WIDE_MAX_B", kAwContain, 0u,
+     "tvz_align_wide_topk_sharded_workspace_bytes", 2 * kAwMaxB + 1, "TVZ_ALIGN_WIDE_MAX_B", kAwContain | kAlTwoBins, 0u,
      al_static_lds<AwHit>(),
      [](const AlignLaunch &l) {
-         hipLaunchKernelGGL(ts_alignw_sweep_kernel, l.grid, dim3(kAlBlock), l.lds, l.st, l.c->rows.p, l.n_rows, l.c->keys.p,
+         const auto sweep = (l.flags & kAlTwoBins) ? ts_alignw2_sweep_kernel : ts_alignw_sweep_kernel;   // (one argument list)
+         hipLaunchKernelGGL(sweep, l.grid, dim3(kAlBlock), l.lds, l.st, l.c->rows.p, l.n_rows, l.c->keys.p,
                             l.q->sv, l.b->d_q_offsets, l.q->qm, l.lds_keys, l.a->eps, l.B, l.width, l.a->min_votes,
                             l.a->min_score, l.flags, l.b->d_exclude_ids, l.k, l.w->part_w, l.w->part_p, l.w->part32[0],
                             l.n_lists, l.w->totals);
@@ -2143,9 +2144,10 @@ constexpr AlignTopkForm kAlignForms[] = {
      }},
     // kAlignRates: tvz_align_rates_topk - the wide call with the rate loop
     {5, 2, true, false, "alignment top-k with rates", "tvz_align_rates_topk_workspace_bytes", nullptr, 2 * kAwMaxB + 1,
-     "TVZ_ALIGN_WIDE_MAX_B", kAwContain, 0u, al_static_lds<ArHit>(),
+     "TVZ_ALIGN_WIDE_MAX_B", kAwContain | kAlTwoBins, 0u, al_static_lds<ArHit>(),
      [](const AlignLaunch &l) {
-         hipLaunchKernelGGL(ts_alignr_sweep_kernel, l.grid, dim3(kAlBlock), l.lds, l.st, l.c->rows.p, l.n_rows, l.c->keys.p,
+         const auto sweep = (l.flags & kAlTwoBins) ? ts_alignr2_sweep_kernel : ts_alignr_sweep_kernel;   // (one argument list)
+         hipLaunchKernelGGL(sweep, l.grid, dim3(kAlBlock), l.lds, l.st, l.c->rows.p, l.n_rows, l.c->keys.p,
                             l.q->sv, l.b->d_q_offsets, l.q->qm, l.lds_keys, l.a->eps, l.B, l.width, *l.rates,
                             l.a->min_votes, l.a->min_score, l.flags, l.b->d_exclude_ids, l.k, l.w->part_w, l.w->part_p,
                             l.w->part32[0], l.w->part32[1], l.n_lists, l.w->totals);
@@ -2161,9 +2163,10 @@ constexpr AlignTopkForm kAlignForms[] = {
      "tvz_align_rates_topk_sharded_workspace_bytes"},
     // kAlignSpan: tvz_align_span_topk - the call with rates and the span pass
     {8, 4, true, true, "alignment top-k with spans", "tvz_align_span_topk_workspace_bytes", nullptr, 2 * kAwMaxB + 1,
-     "TVZ_ALIGN_WIDE_MAX_B", kAwContain | kAsLocal, kAwContain | kAsLocal, al_static_lds<AsHit>(),
+     "TVZ_ALIGN_WIDE_MAX_B", kAwContain | kAsLocal | kAlTwoBins, kAwContain | kAsLocal, al_static_lds<AsHit>(),
      [](const AlignLaunch &l) {
-         hipLaunchKernelGGL(ts_aligns_sweep_kernel, l.grid, dim3(kAlBlock), l.lds, l.st, l.c->rows.p, l.n_rows, l.c->keys.p,
+         const auto sweep = (l.flags & kAlTwoBins) ? ts_aligns2_sweep_kernel : ts_aligns_sweep_kernel;   // (one argument list)
+         hipLaunchKernelGGL(sweep, l.grid, dim3(kAlBlock), l.lds, l.st, l.c->rows.p, l.n_rows, l.c->keys.p,
                             l.q->sv, l.b->d_q_offsets, l.q->qm, l.lds_keys, l.a->eps, l.B, l.width, *l.rates,
                             l.a->min_votes, l.a->min_score, l.flags, l.b->d_exclude_ids, l.k, l.w->part_w, l.w->part_p,
                             l.w->part32[0], l.w->part32[1], l.w->part32[2], l.w->part32[3], l.n_lists, l.w->totals);

@@ -93,7 +93,8 @@ class Inspector:
                  near_jaccard: float = 0.8, slot_bytes: int = 64 << 20, n_slots: Optional[int] = None,
                  profile: bool = False, match_tolerance: float = 0.0, near_top_k: Optional[int] = None,
                  near_any_offset: bool = False, near_score: str = "jaccard", near_min_votes: int = 1,
-                 near_rates=None, near_spans: bool = False, near_parts: Optional[int] = None):
+                 near_rates=None, near_spans: bool = False, near_parts: Optional[int] = None,
+                 near_two_bins: bool = False):
         self.store = store
         # opt-in: the near-duplicate report from the K best-aligned rows the device keeps (tvz_align_topk) instead of
         # one row per corpus row walked here.  None: the walk, exactly as before.  Refused here where the store's
@@ -169,6 +170,23 @@ class Inspector:
                 raise RuntimeError(f"near_parts={self.near_parts}: the store's corpus "
                                    f"({type(getattr(store, 'corpus', None)).__name__}) has no align_parts; "
                                    "use a DeviceCorpus, a service.ShardedCorpus or a service.RankCorpus whose matcher has it")
+        # opt-in: the votes of a row counted over two adjacent offset bins (TVZ_ALIGN_TWO_BINS) - the copy whose shift
+        # lies near a bin's edge (a remux, a re-timing to another frame grid) splits its votes over two bins and the
+        # best single bin holds half of them.  The search goes through the calls that take flags: without
+        # near_any_offset that is align_wide_topk with max_offset=near_max_offset (the bounded call's answer for its
+        # range).  best_bin is then the window's lower bin, so shift_seconds is (best_bin + 0.5) x near_eps.
+        # tvz_align_parts has no flags argument: near_parts with it is refused.  False: nothing changes.
+        self.near_two_bins = bool(near_two_bins)
+        if self.near_two_bins:
+            if not near_duplicates or self.near_top_k is None:
+                raise ValueError("near_two_bins=True needs near_duplicates=True and near_top_k")
+            if self.near_parts is not None:
+                raise ValueError(f"near_two_bins=True with near_parts={self.near_parts}: align_parts counts single bins "
+                                 "(it has no flags); use one of them")
+            if not _corpus_can(getattr(store, "corpus", None), "align_wide_topk", "supports_align_wide"):
+                raise RuntimeError(f"near_two_bins=True: the store's corpus "
+                                   f"({type(getattr(store, 'corpus', None)).__name__}) has no align_wide_topk; "
+                                   "use a DeviceCorpus, a service.ShardedCorpus or a service.RankCorpus")
         # opt-in, never the default: duplicates by the TOLERANT count (include/tvz.h tvz_find_duplicates_tol)
         # instead of the reference's exact float64 equality; the verdict, the truncation at kth and the stored
         # duplicates all follow it.  Refused here, before any upload, where the store's corpus cannot do it.
@@ -412,7 +430,7 @@ class Inspector:
         out = []
         if len(scene_timestamps) < 2:
             return out
-        rows, rated = self._near_rows(video_id, scene_timestamps)
+        rows, rated, half = self._near_search(video_id, scene_timestamps)
         local = self.near_score == "local"
         cuts = None                                                            # the upload's non-NaN cuts, sorted
         for vid, row_len, best_bin, votes, *more in rows:
@@ -434,7 +452,7 @@ class Inspector:
             if score >= self.near_jaccard:
                 v = self.store.get_video_by_id(int(vid))
                 out.append({"filename": v.filename if v else None, "video_id": int(vid),
-                            "shift_seconds": float(best_bin) * self.near_eps, "jaccard": round(jacc, 4)})
+                            "shift_seconds": (float(best_bin) + half) * self.near_eps, "jaccard": round(jacc, 4)})
                 if contain or local:
                     out[-1][self.near_score] = round(score, 4)
                 if rated:                                                      # stored ~= rate x upload + shift
@@ -476,11 +494,16 @@ class Inspector:
             d["parts_score"] = round(v / float(u - v), 4) if u > v else 0.0
 
     def _near_rows(self, video_id: int, scene_timestamps):
+        """_near_search's (rows, rated)."""
+        return self._near_search(video_id, scene_timestamps)[:2]
+
+    def _near_search(self, video_id: int, scene_timestamps):
         """(video_id, row_len, best_bin, votes[, ...]) of the rows _near filters: every row of the table (near_top_k None), or
         the near_top_k best-aligned ones, selected on the device with min_score = floor(near_jaccard x 2^20) - a
-        superset of the float filter, since v / u >= j implies floor(v 2^20 / u) >= floor(j 2^20).  -> (rows, rated):
-        rated where the fifth column is the index of the row's rate in near_rates (tvz_align_rates_topk); rows of eight
-        columns carry the span behind it (tvz_align_span_topk)."""
+        superset of the float filter, since v / u >= j implies floor(v 2^20 / u) >= floor(j 2^20).  -> (rows, rated,
+        half): rated where the fifth column is the index of the row's rate in near_rates (tvz_align_rates_topk); rows
+        of eight columns carry the span behind it (tvz_align_span_topk); half = 0.5 where best_bin is the lower bin of
+        a window of two (near_two_bins), so the shift is (best_bin + half) x near_eps, and 0.0 otherwise."""
         corpus = self.store.corpus
         if self.near_top_k is not None:
             one = 1 << 20
@@ -496,16 +519,20 @@ class Inspector:
             elif self.near_any_offset:
                 call = corpus.align_wide_topk
             else:
-                call, kw = corpus.align_topk, dict(max_offset=self.near_max_offset)
+                # (with near_two_bins: the call that takes flags, over the bounded range)
+                call = corpus.align_wide_topk if self.near_two_bins else corpus.align_topk
+                kw = dict(max_offset=self.near_max_offset)
                 if self.near_min_votes > 1:
                     kw["min_votes"] = self.near_min_votes
+            if self.near_two_bins:                                             # (told only where it is set)
+                kw["two_bins"] = True
             rows, totals = call([scene_timestamps], eps=self.near_eps, k=self.near_top_k, min_score=min_score,
                                 exclude_ids=[int(video_id)], **kw)
             if int(totals[0]) >= 0:                                            # (refused: more than 4,095 cuts -> the walk)
-                return [r for r in rows[0] if r[0] >= 0], rated
+                return [r for r in rows[0] if r[0] >= 0], rated, 0.5 if self.near_two_bins else 0.0
             if not hasattr(corpus, "align"):                                   # (a rank corpus has no walk: no report)
-                return [], False
-        return corpus.align(scene_timestamps, eps=self.near_eps, max_offset=self.near_max_offset), False
+                return [], False, 0.0
+        return corpus.align(scene_timestamps, eps=self.near_eps, max_offset=self.near_max_offset), False, 0.0
 
     def _progress(self, analysis_key, scene_timestamps, frames_done, total_frames, dups_to_report):
         if total_frames > 0 and frames_done > 0:                           # app.py:259-260

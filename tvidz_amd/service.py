@@ -32,7 +32,10 @@ tick to `matcher.align(form, ...)`, and has a kind for each of the four: `align_
 shift, `align_wide_topk` (ASK_NEAR_WIDE; Inspector(near_any_offset=True), `--near-any-offset`), the search for
 speed-changed copies, `align_rates_topk` (ASK_NEAR_RATES; Inspector(near_rates=...), `--near-rates R1,R2,...`) and the one
 with spans, `align_span_topk` (ASK_NEAR_SPAN; Inspector(near_spans=True) or near_score="local", `--near-spans`,
-`--near-score local`); an ask of the last two carries its rate list.  The refinement behind the search, every aligned
+`--near-score local`); an ask of the last two carries its rate list.  The votes counted over two adjacent bins
+(TVZ_ALIGN_TWO_BINS; Inspector(near_two_bins=True), `--near-two-bins`) are a bit of the ask's flags beside the score
+kinds, on the three forms that take flags, and reach a matcher as `two_bins=True` only where the bit is set.  The
+refinement behind the search, every aligned
 part of the reported videos (`align_parts`, Inspector(near_parts=P), `--near-parts P`), is one call too:
 ShardedCorpus.align_parts runs tvz_align_parts_shards (every shard in turn + the device merge that keeps the best
 answer per pair, one copy back), RankCorpus.align_parts sends an ASK_PARTS with the ids through the tick to
@@ -290,30 +293,34 @@ class ShardedCorpus:
     supports_align_wide = True
 
     def align_wide_topk(self, queries, *, eps: float, max_offset=None, k: int = 16, min_votes: int = 1,
-                        min_score: int = 0, contain: bool = False, exclude_ids=None, max_query_len=None):
+                        min_score: int = 0, contain: bool = False, two_bins: bool = False, exclude_ids=None,
+                        max_query_len=None):
         """DeviceCorpus.align_wide_topk over every shard - align_topk at any shift (`max_offset=None`: the widest),
         scored by the containment with `contain`: ONE library call (tvz_align_wide_topk_shards), ONE copy back; more
         than 16 shards are grouped and re-merged by tvz_align_wide_topk_merge, as align_topk does."""
         return self._near_shards(tc.FORM_WIDE, queries, k, exclude_ids, max_query_len, eps=eps, max_offset=max_offset,
-                                 min_votes=min_votes, min_score=min_score, contain=contain)
+                                 min_votes=min_votes, min_score=min_score, contain=contain, two_bins=two_bins)
 
     def align_rates_topk(self, queries, *, eps: float, rates, max_offset=None, k: int = 16, min_votes: int = 1,
-                         min_score: int = 0, contain: bool = False, exclude_ids=None, max_query_len=None):
+                         min_score: int = 0, contain: bool = False, two_bins: bool = False, exclude_ids=None,
+                         max_query_len=None):
         """DeviceCorpus.align_rates_topk over every shard - align_wide_topk for copies played at another speed, every
         row kept once at the best of `rates`; rows of five columns, the last the rate's index: ONE library call
         (tvz_align_rates_topk_shards), ONE copy back; more than 16 shards are grouped and re-merged by
         tvz_align_rates_topk_merge, as align_topk does."""
         return self._near_shards(tc.FORM_RATES, queries, k, exclude_ids, max_query_len, eps=eps, max_offset=max_offset,
-                                 min_votes=min_votes, min_score=min_score, rates=tuple(rates), contain=contain)
+                                 min_votes=min_votes, min_score=min_score, rates=tuple(rates), contain=contain,
+                                 two_bins=two_bins)
 
     def align_span_topk(self, queries, *, eps: float, rates=(1.0,), max_offset=None, k: int = 16, min_votes: int = 1,
-                        min_score: int = 0, contain: bool = False, local: bool = False, exclude_ids=None,
-                        max_query_len=None):
+                        min_score: int = 0, contain: bool = False, local: bool = False, two_bins: bool = False,
+                        exclude_ids=None, max_query_len=None):
         """DeviceCorpus.align_span_topk over every shard - align_rates_topk with the span of every hit, scored inside
         it with `local`; rows of eight columns: ONE library call (tvz_align_span_topk_shards), ONE copy back; more than
         16 shards are grouped and re-merged by tvz_align_span_topk_merge, as align_topk does."""
         return self._near_shards(tc.FORM_SPAN, queries, k, exclude_ids, max_query_len, eps=eps, max_offset=max_offset,
-                                 min_votes=min_votes, min_score=min_score, rates=tuple(rates), contain=contain, local=local)
+                                 min_votes=min_votes, min_score=min_score, rates=tuple(rates), contain=contain, local=local,
+                                 two_bins=two_bins)
 
     def align_parts(self, queries, video_ids, *, eps: float, max_offset=None, rates=(1.0,), min_votes: int,
                     max_parts: int, max_query_len=None):
@@ -450,11 +457,12 @@ def check_near_rates(rates) -> tuple:
     return (len(r),) + r + (0.0,) * (tc.ALIGN_MAX_RATES - len(r))
 
 
-def check_near(form, eps, max_offset, k, min_votes, min_score, contain=False, local=False) -> tuple:
+def check_near(form, eps, max_offset, k, min_votes, min_score, contain=False, local=False, two_bins=False) -> tuple:
     """What tvz_<stem> of `form` (TICK_FORMS) refuses, refused on the host with its rules (include/tvz.h): -> the six
     values as a near ask carries them, the call's flags last (0 for the form without flags).  `max_offset=None` is the
     widest of a form that has one, tc.ALIGN_WIDE_MAX_B bins of eps on either side of zero; the bounded form takes
-    NEAR_MAX_BINS bins in all.  `local` is the span form's second score kind: one of the two."""
+    NEAR_MAX_BINS bins in all.  `local` is the span form's second score kind: one of the two.  `two_bins`
+    (TVZ_ALIGN_TWO_BINS) travels in the flags beside them, for the forms that take it."""
     eps, max_offset = float(eps), None if form.widest and max_offset is None else float(max_offset)
     if not (0.0 < eps <= sys.float_info.max):
         raise ValueError(f"eps must be finite and > 0, got {eps!r}")
@@ -475,8 +483,10 @@ def check_near(form, eps, max_offset, k, min_votes, min_score, contain=False, lo
             raise ValueError(f"{name} must be an integer in {lo}..{hi}, got {v!r}")
     if contain and local:
         raise ValueError("contain and local are two score kinds: one of them")
+    if two_bins and not form.two_bins:
+        raise ValueError(f"{form.stem} does not count over two bins (no TVZ_ALIGN_TWO_BINS)")
     flags = (tc.ALIGN_CONTAIN if contain and "contain" in form.flags else 0) | \
-        (tc.ALIGN_LOCAL if local and "local" in form.flags else 0)
+        (tc.ALIGN_LOCAL if local and "local" in form.flags else 0) | (tc.ALIGN_TWO_BINS if two_bins else 0)
     return eps, max_offset, int(k), int(min_votes), int(min_score), flags
 
 
@@ -631,29 +641,31 @@ class RankCorpus:
         return self._near(tc.FORM_BOUNDED, queries, exclude_ids, max_query_len, eps, max_offset, k, min_votes, min_score)
 
     def align_wide_topk(self, queries, *, eps: float, max_offset=None, k: int = 16, min_votes: int = 1,
-                        min_score: int = 0, contain: bool = False, exclude_ids=None, max_query_len=None):
+                        min_score: int = 0, contain: bool = False, two_bins: bool = False, exclude_ids=None,
+                        max_query_len=None):
         """DeviceCorpus.align_wide_topk over the shards of all ranks - align_topk at any shift (`max_offset=None`: the
         widest), scored by the containment with `contain`; order: corpus.align_wide_order_key.  Every query is one
         ASK_NEAR_WIDE of the next tick (`_near`)."""
         return self._near(tc.FORM_WIDE, queries, exclude_ids, max_query_len, eps, max_offset, k, min_votes, min_score,
-                          contain)
+                          contain, two_bins=two_bins)
 
     def align_rates_topk(self, queries, *, eps: float, rates, max_offset=None, k: int = 16, min_votes: int = 1,
-                         min_score: int = 0, contain: bool = False, exclude_ids=None, max_query_len=None):
+                         min_score: int = 0, contain: bool = False, two_bins: bool = False, exclude_ids=None,
+                         max_query_len=None):
         """DeviceCorpus.align_rates_topk over the shards of all ranks - align_wide_topk for copies played at another
         speed; rows of five columns, the last the rate's index; order: corpus.align_rates_order_key.  Every query is one
         ASK_NEAR_RATES of the next tick (`_near`) and carries the rate list."""
         return self._near(tc.FORM_RATES, queries, exclude_ids, max_query_len, eps, max_offset, k, min_votes, min_score,
-                          contain, rates=rates)
+                          contain, rates=rates, two_bins=two_bins)
 
     def align_span_topk(self, queries, *, eps: float, rates=(1.0,), max_offset=None, k: int = 16, min_votes: int = 1,
-                        min_score: int = 0, contain: bool = False, local: bool = False, exclude_ids=None,
-                        max_query_len=None):
+                        min_score: int = 0, contain: bool = False, local: bool = False, two_bins: bool = False,
+                        exclude_ids=None, max_query_len=None):
         """DeviceCorpus.align_span_topk over the shards of all ranks - align_rates_topk with the span of every hit,
         scored inside it with `local`; rows of eight columns; order: corpus.align_span_order_key.  Every query is one
         ASK_NEAR_SPAN of the next tick (`_near`)."""
         return self._near(tc.FORM_SPAN, queries, exclude_ids, max_query_len, eps, max_offset, k, min_votes, min_score,
-                          contain, local, rates=rates)
+                          contain, local, rates=rates, two_bins=two_bins)
 
     def align_parts(self, queries, video_ids, *, eps: float, max_offset=None, rates=(1.0,), min_votes: int,
                     max_parts: int, max_query_len=None):
@@ -706,13 +718,13 @@ class RankCorpus:
         return bool(getattr(self.matcher, "supports_align_parts", False))
 
     def _near(self, form, queries, exclude_ids, max_query_len, eps, max_offset, k, min_votes, min_score, contain=False,
-              local=False, rates=None):
+              local=False, rates=None, two_bins=False):
         """What the four searches above share, for their `form`.  Everything a rank's library call would refuse is refused
         HERE, in the caller (check_near's and check_near_rates' ValueError for a bad parameter, RuntimeError for a
         matcher without the form): a matcher that throws on one rank inside a tick would strand the others.  A query of
         more than max_query_len (at most 4,095) values is answered here too, as the library answers it: all rows
         padding, total ALIGN_REFUSED - it never travels."""
-        near = check_near(form, eps, max_offset, k, min_votes, min_score, contain, local)
+        near = check_near(form, eps, max_offset, k, min_votes, min_score, contain, local, two_bins)
         if form.rates:
             near += check_near_rates(rates)
         if form not in getattr(self.matcher, "align_forms", ()):
@@ -897,6 +909,8 @@ class RankCorpus:
                     kw["contain"] = bool(int(par[5]) & tc.ALIGN_CONTAIN)
                 if "local" in form.flags:
                     kw["local"] = bool(int(par[5]) & tc.ALIGN_LOCAL)
+                if int(par[5]) & tc.ALIGN_TWO_BINS:                              # (told only where it is set)
+                    kw["two_bins"] = True
                 if form.rates:
                     kw["rates"] = tuple(par[7:7 + int(par[6])])
                 self._answer_batch(asks, take, np.flatnonzero(of_kind & (pars == np.asarray(par)).all(axis=1)),
@@ -1040,6 +1054,8 @@ def near_kwargs(a) -> dict:
         kw["near_spans"] = True
     if int(getattr(a, "near_parts", 0) or 0):
         kw["near_parts"] = int(a.near_parts)
+    if getattr(a, "near_two_bins", False):
+        kw["near_two_bins"] = True
     return kw
 
 
@@ -1055,10 +1071,10 @@ def parse_near_rates(rates):
 
 
 def check_near_switches(near_top_k, near_any_offset=False, near_score="jaccard", near_min_votes=1, near_rates=None,
-                        near_spans=False, near_parts=0) -> list:
-    """`--near-any-offset`, `--near-score`, `--near-min-votes`, `--near-rates`, `--near-spans`, `--near-parts`: Inspector's
-    rules for them, before any rank starts -> the switches as a rank process takes them (none where all are at their
-    defaults; the later three behind the earlier three)."""
+                        near_spans=False, near_parts=0, near_two_bins=False) -> list:
+    """`--near-any-offset`, `--near-score`, `--near-min-votes`, `--near-rates`, `--near-spans`, `--near-parts`,
+    `--near-two-bins`: Inspector's rules for them, before any rank starts -> the switches as a rank process takes them
+    (none where all are at their defaults; the later ones behind the earlier three)."""
     if near_score not in ("jaccard", "containment", "local"):
         raise ValueError(f"near_score must be 'jaccard', 'containment' or 'local', got {near_score!r}")
     if int(near_min_votes) != near_min_votes or int(near_min_votes) < 1:
@@ -1074,7 +1090,8 @@ def check_near_switches(near_top_k, near_any_offset=False, near_score="jaccard",
         (["--near-min-votes", str(int(near_min_votes))] if int(near_min_votes) != 1 else []) + \
         (["--near-rates", ",".join(repr(r) for r in rates)] if rates is not None else []) + \
         (["--near-spans"] if near_spans else []) + \
-        (["--near-parts", str(int(near_parts))] if near_parts else [])
+        (["--near-parts", str(int(near_parts))] if near_parts else []) + \
+        (["--near-two-bins"] if near_two_bins else [])
     if given and not near_top_k:
         raise ValueError(f"{given[0]} needs --near-top-k")
     if near_score == "containment" and not near_any_offset:
@@ -1087,6 +1104,9 @@ def check_near_switches(near_top_k, near_any_offset=False, near_score="jaccard",
         raise ValueError(f"--near-score local needs --near-min-votes >= 2 (one aligned pair scores 1.0), got {near_min_votes!r}")
     if near_parts and near_score != "local":
         raise ValueError(f"--near-parts {int(near_parts)} needs --near-score local")
+    if near_parts and near_two_bins:
+        raise ValueError(f"--near-two-bins with --near-parts {int(near_parts)}: align_parts counts single bins (it has no "
+                         "flags); use one of them")
     return given
 
 
@@ -1253,7 +1273,7 @@ class RankService:
                  match_tolerance: float = 0.0, match_tol_index: float = 0.0, near_top_k: int = 0,
                  near_eps: float = 1.0 / 30, near_max_offset: float = 30.0, near_jaccard: float = 0.8,
                  near_any_offset: bool = False, near_score: str = "jaccard", near_min_votes: int = 1, near_rates=None,
-                 near_spans: bool = False, near_parts: int = 0):
+                 near_spans: bool = False, near_parts: int = 0, near_two_bins: bool = False):
         import socket
         import subprocess
         from . import db
@@ -1270,7 +1290,7 @@ class RankService:
             near = ["--near-top-k", str(int(near_top_k)), "--near-eps", repr(float(near_eps)),
                     "--near-max-offset", repr(float(near_max_offset)), "--near-jaccard", repr(float(near_jaccard))]
         near += check_near_switches(near_top_k, near_any_offset, near_score, near_min_votes, near_rates, near_spans,
-                                    near_parts)
+                                    near_parts, near_two_bins)
         db.create_schema(db_url)                                # once, before N processes open it side by side
         with socket.socket() as s:                              # a free rendezvous port
             s.bind(("127.0.0.1", 0))
@@ -1379,6 +1399,10 @@ def main(argv=None) -> int:  # pragma: no cover - exercised through subprocesses
                     help="2..4: every reported near duplicate is aligned in full and gains up to P parts, for the copy "
                          "with a part put in or taken out (Inspector(near_parts=P); tvz_align_parts_sharded).  Needs "
                          "--near-score local.  0 = off")
+    ap.add_argument("--near-two-bins", action="store_true",
+                    help="votes counted over two adjacent offset bins, for the copy whose shift lies near a bin's edge (a "
+                         "remux, a re-timing to another frame grid): Inspector(near_two_bins=True); TVZ_ALIGN_TWO_BINS.  "
+                         "Needs --near-top-k; not with --near-parts")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--rank", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--master-port", type=int, default=29500, help=argparse.SUPPRESS)
@@ -1393,7 +1417,8 @@ def main(argv=None) -> int:  # pragma: no cover - exercised through subprocesses
                       match_tol_index=a.match_tol_index, near_top_k=a.near_top_k, near_eps=a.near_eps,
                       near_max_offset=a.near_max_offset, near_jaccard=a.near_jaccard,
                       near_any_offset=a.near_any_offset, near_score=a.near_score, near_min_votes=a.near_min_votes,
-                      near_rates=a.near_rates, near_spans=a.near_spans, near_parts=a.near_parts)
+                      near_rates=a.near_rates, near_spans=a.near_spans, near_parts=a.near_parts,
+                      near_two_bins=a.near_two_bins)
 
     def monitor():
         while True:

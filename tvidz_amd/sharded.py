@@ -81,9 +81,14 @@ class HipBackend:
         return tc.align_parts_merge_device(gathered)
 
 
+def _two_bins(two_bins: bool) -> dict:
+    return {"two_bins": True} if two_bins else {}
+
+
 class _AlignForwards:
     """The near-duplicate search as both matchers offer it on top of their `align(form, ...)` and `align_forms`: the
-    public calls are forwards that name their form, the supports_* flags views of `align_forms`."""
+    public calls are forwards that name their form, the supports_* flags views of `align_forms`.  `two_bins`
+    (TVZ_ALIGN_TWO_BINS) is handed on only where it is set: a backend that has never heard of it keeps working."""
 
     def align_topk(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, eps: float,
                    max_offset: float, k: int, min_votes: int = 1, min_score: int = 0,
@@ -94,29 +99,31 @@ class _AlignForwards:
 
     def align_wide_topk(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, eps: float,
                         max_offset: Optional[float] = None, k: int, min_votes: int = 1, min_score: int = 0,
-                        contain: bool = False, d_exclude_ids: Optional[torch.Tensor] = None):
+                        contain: bool = False, d_exclude_ids: Optional[torch.Tensor] = None, two_bins: bool = False):
         """`align` for tvz_align_wide_topk: align_topk at any shift (`max_offset=None`: the widest), scored by the
         containment with `contain`."""
         return self.align(tc.FORM_WIDE, d_queries, d_q_offsets, max_query_len, k=k, d_exclude_ids=d_exclude_ids,
-                          eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score, contain=contain)
+                          eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score, contain=contain,
+                          **_two_bins(two_bins))
 
     def align_rates_topk(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, eps: float,
                          rates, max_offset: Optional[float] = None, k: int, min_votes: int = 1, min_score: int = 0,
-                         contain: bool = False, d_exclude_ids: Optional[torch.Tensor] = None):
+                         contain: bool = False, d_exclude_ids: Optional[torch.Tensor] = None, two_bins: bool = False):
         """`align` for tvz_align_rates_topk: align_wide_topk for copies played at another speed -> (rows int32 [Q,k,5],
         totals int32 [Q])."""
         return self.align(tc.FORM_RATES, d_queries, d_q_offsets, max_query_len, k=k, d_exclude_ids=d_exclude_ids,
                           eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score, rates=tuple(rates),
-                          contain=contain)
+                          contain=contain, **_two_bins(two_bins))
 
     def align_span_topk(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, eps: float,
                         rates=(1.0,), max_offset: Optional[float] = None, k: int, min_votes: int = 1, min_score: int = 0,
-                        contain: bool = False, local: bool = False, d_exclude_ids: Optional[torch.Tensor] = None):
+                        contain: bool = False, local: bool = False, d_exclude_ids: Optional[torch.Tensor] = None,
+                        two_bins: bool = False):
         """`align` for tvz_align_span_topk: align_rates_topk with every hit's span, scored inside it with `local` ->
         (rows int32 [Q,k,8], totals int32 [Q])."""
         return self.align(tc.FORM_SPAN, d_queries, d_q_offsets, max_query_len, k=k, d_exclude_ids=d_exclude_ids,
                           eps=eps, max_offset=max_offset, min_votes=min_votes, min_score=min_score, rates=tuple(rates),
-                          contain=contain, local=local)
+                          contain=contain, local=local, **_two_bins(two_bins))
 
     @property
     def supports_align_topk(self) -> bool:
