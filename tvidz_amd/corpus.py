@@ -266,6 +266,18 @@ def align_parts_sharded_workspace_bytes(Q: int, max_query_len: int, total_query_
                                                                    int(k), int(max_parts), int(n_ranks)))
 
 
+ALIGN_CANDIDATES_MAX_C, ALIGN_CANDIDATES_MAX_PROBES = 64, 4095     # include/tvz_gap.h TVZ_GAP_MAX_C, TVZ_GAP_MAX_PROBES
+ALIGN_CANDIDATES_REFUSED = -(1 << 31)                               # n_candidates of a refused query
+
+
+def align_candidates_workspace_bytes(Q: int, max_query_len: int, total_query_keys: int = 0, cap: int = 4096,
+                                     c: int = 16) -> int:
+    """tvz_align_candidates_workspace_bytes: the lookup's hit lists (Q x cap x 12 bytes) and its own workspace, then per
+    query value the sorted copy and eight probe slots (76 bytes)."""
+    return int(_lib.load().tvz_align_candidates_workspace_bytes(int(Q), int(max_query_len), int(total_query_keys),
+                                                                int(cap), int(c)))
+
+
 def align_parts_ids(video_ids, Q: int, dev) -> torch.Tensor:
     """The ids of tvz_align_parts as a 2-D int32 tensor [Q, k] on `dev`: a device tensor (any strides) as it is, host
     lists or arrays copied once."""
@@ -443,6 +455,49 @@ class DeviceCorpus:
         cell, v = C.c_double(), (C.c_int64 * 4)()
         _lib.check(self.lib.tvz_corpus_tol_index_stats(self._h, C.byref(cell), v))
         return dict(zip(("cell", "cells", "postings", "builds", "delta_rows"), [float(cell.value)] + [int(x) for x in v]))
+
+    def set_gap_index(self, gap_eps: float) -> None:
+        """tvz_corpus_gap_index: gap_eps > 0 makes the handle keep the gap codes of its rows (three consecutive gaps
+        between cuts, quantised to gap_eps seconds: include/tvz_gap.h) in an index of their own, built now and kept
+        current by every later upload / upsert / clear; 0 drops them.  `align_candidates` needs them; nothing else
+        depends on them."""
+        _lib.check(self.lib.tvz_corpus_gap_index(self._h, float(gap_eps)))
+
+    def gap_index_stats(self) -> dict:
+        """gap_eps (0.0: off) / rows / codes / indexed_rows / delta_rows / builds of the code table; zeros while off."""
+        eps, v = C.c_double(), (C.c_int64 * 5)()
+        _lib.check(self.lib.tvz_corpus_gap_index_stats(self._h, C.byref(eps), v))
+        return dict(zip(("gap_eps", "rows", "codes", "indexed_rows", "delta_rows", "builds"),
+                        [float(eps.value)] + [int(x) for x in v]))
+
+    def align_candidates(self, queries, *, c: int, min_count: int = 2, cap: int = 4096, exclude_ids=None,
+                         max_query_len: Optional[int] = None):
+        """tvz_align_candidates, host in / host out: per query the `c` stored videos that share the most gap codes with
+        it (set_gap_index first) -> (rows int32 [Q, c, 2] of (video_id, count), count descending then id ascending,
+        padded with (-1, 0); totals int32 [Q]: the candidates with count >= min_count, negated when they exceeded
+        `cap`, ALIGN_CANDIDATES_REFUSED for a query of more than 514 values).  `queries`, `exclude_ids` as align_topk
+        takes them."""
+        dev = torch.device("cuda", self.device)
+        d_q, d_off, Q, max_query_len, d_ex = align_inputs(queries, exclude_ids, max_query_len, dev)
+        ws = thread_workspace(self._tls, align_candidates_workspace_bytes(Q, max_query_len, d_q.numel(), cap, c), dev)
+        h = self.align_candidates_block(d_q, d_off, max_query_len, c=c, min_count=min_count, cap=cap, d_exclude_ids=d_ex,
+                                        workspace=ws).cpu().numpy()
+        return np.ascontiguousarray(h[:, :c]), np.ascontiguousarray(h[:, c, 1])
+
+    def align_candidates_block(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, c: int,
+                               min_count: int = 2, cap: int = 4096, d_exclude_ids: Optional[torch.Tensor] = None,
+                               out: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
+                               workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """tvz_align_candidates, device in / device out: enqueue Q queries -> the block int32 [Q, c + 1, 2].
+        `block[:, :c, 0]` is the strided view of ids that align_parts_block takes."""
+        Q = d_q_offsets.numel() - 1
+        dev, s, ws, excl = self._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace,
+                                         align_candidates_workspace_bytes(Q, max_query_len, d_queries.numel(), cap, c))
+        out = _out(out, (Q, max(int(c), 0) + 1, 2), dev)
+        _lib.check(self.lib.tvz_align_candidates(self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len),
+                                                 int(min_count), excl, int(cap), int(c), out.data_ptr(), ws.data_ptr(),
+                                                 ws.numel(), s.cuda_stream))
+        return out
 
     def stats(self) -> Tuple[int, int, int]:
         a, b, c = C.c_int64(), C.c_int64(), C.c_int64()

@@ -1,0 +1,113 @@
+// tvz_gap_codes.h — the gap codes of one stored row, made on the host (include/tvz_gap.h: STORED SIDE), and the
+// workspace layout of tvz_align_candidates.  Plain C++ with no HIP in it: tvz_match.hip includes it for the handle, a
+// stand-alone host program can include it on its own.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+namespace tvz_gap {
+
+constexpr int kBinBits = 17;
+constexpr double kMaxBin = 131071.0;                    // 2^17 - 1
+constexpr double kBin1 = 131072.0;                      // 2^17
+constexpr double kBin2 = 17179869184.0;                 // 2^34
+constexpr int kVariants = 8;                            // probe slots of a query position
+constexpr int kMaxProbes = 4095;                        // probe slots of a query (the lookup's longest query)
+constexpr int kMaxC = 64;
+
+// a bin is valid iff it lies in [0, kMaxBin]: compared on the double, NaN fails
+inline bool bin_valid(double b) { return b >= 0.0 && b <= kMaxBin; }
+
+// r_i of the contract: one subtraction, one true division
+inline double gap_ratio(double lo, double hi, double gap_eps) {
+    const double d = hi - lo;
+    return d / gap_eps;
+}
+
+// the code of three valid bins: exact in a double (below 2^51)
+inline double code_of(double g0, double g1, double g2) { return g0 + g1 * kBin1 + g2 * kBin2; }
+
+// The codes of a row of `len` keys, appended to `out` in position order (duplicates are left in: the table that stores
+// them keeps a row as a set).  `keys` are the handle's canonical bit patterns of float64 values: distinct, no NaN, -0.0
+// folded - but sorted as INTEGERS, which puts negative values in descending order, so they are sorted numerically here
+// first (`vals`: the caller's scratch, it keeps its capacity).  Returns how many codes were appended.
+inline int64_t row_codes(const int64_t *keys, int64_t len, double gap_eps, std::vector<double> &vals, std::vector<double> &out) {
+    if (len < 4) return 0;
+    vals.resize((size_t)len);
+    bool negative = false;
+    for (int64_t i = 0; i < len; ++i) {
+        memcpy(&vals[(size_t)i], &keys[i], 8);
+        negative = negative || keys[i] < 0;
+    }
+    if (negative) std::sort(vals.begin(), vals.end());
+    const size_t before = out.size();
+    double b0 = std::floor(gap_ratio(vals[0], vals[1], gap_eps) + 0.5);
+    double b1 = std::floor(gap_ratio(vals[1], vals[2], gap_eps) + 0.5);
+    for (int64_t i = 0; i + 3 < len; ++i) {
+        const double b2 = std::floor(gap_ratio(vals[(size_t)i + 2], vals[(size_t)i + 3], gap_eps) + 0.5);
+        if (bin_valid(b0) && bin_valid(b1) && bin_valid(b2)) out.push_back(code_of(b0, b1, b2));
+        b0 = b1;
+        b1 = b2;
+    }
+    return (int64_t)(out.size() - before);
+}
+
+// ---- the workspace of tvz_align_candidates ----
+// Regions of 256-byte multiples behind a base aligned up to 256 (the carver of tvz_match.hip walks the same sizes).
+inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// probe slots of a query of m sorted values; -1: the query is refused (m < 0: longer than max_query_len).  constexpr:
+// the kernels call it too
+constexpr int32_t probe_slots(int32_t m) {
+    if (m < 0) return -1;
+    if (m < 4) return 0;
+    const int64_t s = (int64_t)kVariants * (m - 3);
+    return s > kMaxProbes ? -1 : (int32_t)s;
+}
+
+// the longest probe list of a call whose queries have up to max_query_len values (at least one position's worth, so
+// that the lookup never sees a zero length with a non-NULL query array)
+inline int32_t max_probe_len(int32_t max_query_len) {
+    const int64_t s = (int64_t)kVariants * std::max(max_query_len - 3, 1);
+    return (int32_t)std::min<int64_t>(s, kMaxProbes / kVariants * kVariants);
+}
+
+// The lookup's hit lists and counts, the probe offsets, the lookup's own workspace (`match_bytes`: its sizing function's
+// answer) and the queries' counts; then, for `room` query values - the call takes what the caller's buffer holds, at
+// least one longest query - the sorted values, their positions and 8 probe slots per value.  The queries the sort
+// accepts lie in disjoint ranges of [0, room), so their probes never exceed 8 * room slots.
+struct WsRegions {                   // byte offsets from the aligned base
+    size_t hits, hits_n, p_off, match, qm, sv, sp, probes, end;
+};
+constexpr size_t kPerKey = sizeof(double) + sizeof(int32_t) + kVariants * sizeof(double);   // 76
+constexpr size_t kWsSlack = 256 + 3 * 255;              // a line for the base, the roundings of the three sized regions
+
+inline WsRegions ws_regions(int32_t Q, int32_t cap, size_t match_bytes, int64_t room) {
+    WsRegions r;
+    size_t p = 0;
+    r.hits = p;    p += al256((size_t)Q * (size_t)cap * 3 * sizeof(int32_t));
+    r.hits_n = p;  p += al256((size_t)Q * sizeof(int32_t));
+    r.p_off = p;   p += al256(((size_t)Q + 1) * sizeof(int64_t));
+    r.match = p;   p += al256(match_bytes);
+    r.qm = p;      p += al256((size_t)Q * sizeof(int32_t));
+    r.sv = p;      p += al256((size_t)room * sizeof(double));
+    r.sp = p;      p += al256((size_t)room * sizeof(int32_t));
+    r.probes = p;  p += al256((size_t)room * kVariants * sizeof(double));
+    r.end = p;
+    return r;
+}
+// bytes for `keys` query values; the most values a buffer of `bytes` holds (-1: not even the fixed parts) -
+// ws_room(.., ws_bytes(.., keys)) is `keys`, and the regions of that room end inside the buffer at any base
+inline size_t ws_bytes(int32_t Q, int32_t cap, size_t match_bytes, int64_t keys) {
+    return ws_regions(Q, cap, match_bytes, 0).end + kWsSlack + (size_t)keys * kPerKey;
+}
+inline int64_t ws_room(int32_t Q, int32_t cap, size_t match_bytes, size_t bytes) {
+    const size_t fixed = ws_bytes(Q, cap, match_bytes, 0);
+    return bytes < fixed ? -1 : (int64_t)((bytes - fixed) / kPerKey);
+}
+
+}  // namespace tvz_gap

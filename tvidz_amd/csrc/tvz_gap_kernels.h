@@ -1,0 +1,129 @@
+// tvz_gap_kernels.h — the kernels of tvz_align_candidates (include/tvz_gap.h; gfx950, wave64).
+//
+//   ts_gapc_offsets_kernel  where every query's probes go: an exclusive scan of the queries' probe slots.
+//   ts_gapc_probe_kernel    the probes: a thread per (query, position) writes its 8 slots.
+//   ts_gapc_select_kernel   per query the C best of the lookup's hit list, the block and the total.
+//
+// Between the last two the internal match runs over the handle's code table (the queries are the probe lists).
+// The queries come sorted from ts_tol_sort_kernel (tvz_tol_kernels.h): sv[at .. at + m), at = q_offsets[q] -
+// q_offsets[0], m = qm[q]; qm[q] < 0: longer than the call's max_query_len.  From tvz_topk_kernels.h: bitonic_sort,
+// sort_and_keep, topk_total; from tvz_wave.h: wave_scan_incl, waves_sum.  Included by tvz_match.hip behind them.
+#pragma once
+#include "tvz_gap_codes.h"
+#include "tvz_topk_kernels.h"
+
+namespace {
+
+constexpr int kGapOffBlock = 1024;             // one block scans every query of the call (Q <= 65,535: 64 per thread)
+constexpr int kGapProbeBlock = 256;
+
+// Probe slots of a query of m sorted values (tvz_gap::probe_slots); a refused query has none.
+__device__ __forceinline__ bool gapc_refused(int32_t m) { return tvz_gap::probe_slots(m) < 0; }
+__device__ __forceinline__ int32_t gapc_slots(int32_t m) { return gapc_refused(m) ? 0 : tvz_gap::probe_slots(m); }
+
+// p_off[q] = the slots of the queries before q, p_off[Q] = all of them.  grid = 1.
+__global__ __launch_bounds__(kGapOffBlock) void ts_gapc_offsets_kernel(const int32_t *__restrict__ qm, int32_t Q,
+                                                                        int64_t *__restrict__ p_off) {
+    __shared__ uint32_t s_w[kGapOffBlock / 64];
+    const int per = (Q + kGapOffBlock - 1) / kGapOffBlock;
+    const int q0 = (int)threadIdx.x * per;
+    uint32_t mine = 0;
+    for (int q = q0; q < q0 + per && q < Q; ++q) mine += (uint32_t)gapc_slots(qm[q]);
+    const uint32_t incl = wave_scan_incl(mine);
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 63) s_w[wave] = incl;
+    __syncthreads();
+    uint32_t before, all;
+    waves_sum<kGapOffBlock / 64>(s_w, wave, before, all);
+    uint32_t at = before + incl - mine;
+    for (int q = q0; q < q0 + per && q < Q; ++q) {
+        p_off[q] = (int64_t)at;
+        at += (uint32_t)gapc_slots(qm[q]);
+    }
+    if (threadIdx.x == 0) p_off[Q] = (int64_t)all;
+}
+
+// The query side of the contract.  grid = (ceil(positions / kGapProbeBlock), Q); thread i of query q takes position i
+// (i + 3 < m) and writes probes[p_off[q] + 8 i ..+ 8): slot v chooses a_j + ((v >> j) & 1) for gap j.  A choice with
+// an invalid bin is written as NaN: the lookup drops a NaN before it probes (canon_key: "NaN never matches", in every
+// match kernel), so such a slot can match nothing and the slots keep their fixed places.  The division is al_bin's:
+// a subtraction, then a true division.  Four 16-byte stores per thread (p_off is a multiple of 8 slots).
+__global__ __launch_bounds__(kGapProbeBlock) void ts_gapc_probe_kernel(const double *__restrict__ sv,
+                                                                        const int64_t *__restrict__ q_offsets,
+                                                                        const int32_t *__restrict__ qm, double gap_eps,
+                                                                        const int64_t *__restrict__ p_off,
+                                                                        double *__restrict__ probes) {
+    const int q = blockIdx.y;
+    const int32_t m = qm[q];
+    if (gapc_slots(m) == 0) return;                                  // refused, or fewer than 4 values (block-uniform)
+    const int i = (int)blockIdx.x * kGapProbeBlock + (int)threadIdx.x;
+    if (i + 3 >= m) return;
+    const double *s = sv + (q_offsets[q] - q_offsets[0]) + i;
+    const double s0 = s[0], s1 = s[1], s2 = s[2], s3 = s[3];
+    double a[3];
+    a[0] = floor((s1 - s0) / gap_eps);
+    a[1] = floor((s2 - s1) / gap_eps);
+    a[2] = floor((s3 - s2) / gap_eps);
+    double lo[3], hi[3];                                             // a gap's two choices, scaled to their place; NaN: invalid
+    const double place[3] = {1.0, tvz_gap::kBin1, tvz_gap::kBin2};
+    const double none = __longlong_as_double(0x7ff8000000000000LL);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const double b = a[j] + 1.0;
+        lo[j] = (a[j] >= 0.0 && a[j] <= tvz_gap::kMaxBin) ? a[j] * place[j] : none;
+        hi[j] = (b >= 0.0 && b <= tvz_gap::kMaxBin) ? b * place[j] : none;
+    }
+    double2 *o = reinterpret_cast<double2 *>(probes + p_off[q] + (int64_t)tvz_gap::kVariants * i);
+#pragma unroll
+    for (int v = 0; v < tvz_gap::kVariants; v += 2) {                // (NaN + x = NaN: an invalid choice poisons its slots)
+        const double rest = ((v & 2) ? hi[1] : lo[1]) + ((v & 4) ? hi[2] : lo[2]);
+        o[v >> 1] = make_double2(lo[0] + rest, hi[0] + rest);
+    }
+}
+
+// The selection.  grid = Q.  Query q's hit list hits[q][min(hits_n[q], cap)][3] = (video_id, count, kth) -> the C
+// largest by the word count << 32 | (2^31 - 1 - video_id), i.e. count descending, then video_id ascending, written as
+// rows (video_id, count), padded with (-1, 0), and the row (-1, total): topk_total's rule (negated when the list
+// overflowed `cap`).  A refused query: padding and INT32_MIN.  The word is kept complemented, so that the ascending
+// bitonic sort of tvz_topk_kernels.h keeps the largest first and its "no entry" (~0) is the word 0, which no hit has
+// (count >= min_count >= 1).  One 8-byte store per row.
+__global__ __launch_bounds__(kBlock) void ts_gapc_select_kernel(const int32_t *__restrict__ hits,
+                                                                 const int32_t *__restrict__ hits_n,
+                                                                 const int32_t *__restrict__ qm, int32_t cap, int32_t C,
+                                                                 int32_t *__restrict__ out) {
+    __shared__ uint64_t key[kSortCap];
+    __shared__ int32_t cnt[kSortCap];
+    const int q = blockIdx.x;
+    int2 *o = reinterpret_cast<int2 *>(out) + (int64_t)q * (C + 1);
+    if (gapc_refused(qm[q])) {                                       // block-uniform
+        for (int i = threadIdx.x; i <= C; i += kBlock) o[i] = make_int2(-1, i == C ? INT32_MIN : 0);
+        return;
+    }
+    const int32_t total = hits_n[q];
+    const int n = total > cap ? cap : (total < 0 ? 0 : total);
+    const int32_t *src = hits + (int64_t)q * cap * 3;
+    int pos = 0;                                                     // block-uniform fill level
+    int j = 0;
+    while (j < n) {
+        int take = n - j;
+        if (take > kSortCap - pos) take = kSortCap - pos;
+        for (int i = threadIdx.x; i < take; i += kBlock) {
+            const int32_t vid = src[(j + i) * 3], c = src[(j + i) * 3 + 1];
+            key[pos + i] = vid < 0 ? ~0ULL : ~(((uint64_t)(uint32_t)c << 32) | (uint32_t)(0x7fffffff - vid));
+            cnt[pos + i] = c;
+        }
+        pos += take;
+        j += take;
+        __syncthreads();
+        if (pos == kSortCap) sort_and_keep(key, cnt, pos, C);
+    }
+    __syncthreads();
+    sort_and_keep(key, cnt, pos, C);
+    for (int i = threadIdx.x; i < C; i += kBlock) {
+        const uint64_t w = i < pos ? ~key[i] : 0ULL;
+        o[i] = w == 0ULL ? make_int2(-1, 0) : make_int2(0x7fffffff - (int32_t)(uint32_t)w, (int32_t)(w >> 32));
+    }
+    if (threadIdx.x == 0) o[C] = make_int2(-1, topk_total(total < 0 ? 0 : total, total > cap));
+}
+
+}  // namespace

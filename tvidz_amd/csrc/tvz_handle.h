@@ -220,6 +220,11 @@ struct tvz_corpus {
     int64_t stage_rows = 0;          // rows the stagings are sized for
     Index ix;
     int64_t ix_next_try_rows = 0;    // a corpus without an index tries to build one from this size on
+    // tvz_corpus_gap_index: a handle of its own whose rows are this one's rows in the same order, same ids, keys = the
+    // rows' gap codes (tvz_gap_codes.h).  Owned; NULL while off.  Read under mu, changed under mu held exclusively;
+    // its own lock is only ever taken with this one's held (parent, then child).
+    tvz_corpus *gap = nullptr;
+    double gap_eps = 0.0;
 };
 
 namespace {

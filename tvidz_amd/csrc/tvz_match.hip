@@ -28,6 +28,8 @@
 #include "tvz_tol_index_kernels.h"
 #include "tvz_align_kernels.h"
 #include "tvz_align_parts_kernels.h"
+#include "tvz_gap_kernels.h"
+#include "tvz_gap.h"
 #include "tvz_handle.h"
 #include "tvz_index_build.h"
 
@@ -918,12 +920,50 @@ static int tvz_corpus_create_impl(tvz_corpus **out, int device) {
     return TVZ_OK;
 }
 
+// ---- the gap codes of the rows (include/tvz_gap.h): a child handle kept in step with this one --------------------
+static int tvz_corpus_destroy_impl(tvz_corpus *c);
+static int tvz_corpus_upload_impl(tvz_corpus *c, const int32_t *h_video_ids, const int64_t *h_offsets, const double *h_keys,
+                                  int64_t n_rows, int64_t n_keys);
+static int tvz_corpus_upsert_impl(tvz_corpus *c, int32_t video_id, const double *h_keys, int64_t n);
+
+namespace {
+
+// the child's whole table from the parent's host mirror (caller holds the parent's mu exclusively; c->gap exists)
+int gap_upload(tvz_corpus *c) {
+    const int64_t n_rows = (int64_t)c->h_rows.size();
+    std::vector<int32_t> ids((size_t)n_rows);
+    std::vector<int64_t> offs((size_t)n_rows + 1, 0);
+    std::vector<double> codes, vals;
+    codes.reserve((size_t)c->live_keys);
+    for (int64_t r = 0; r < n_rows; ++r) {
+        const Row &row = c->h_rows[(size_t)r];
+        ids[(size_t)r] = row.vid;
+        tvz_gap::row_codes(c->h_keys.data() + row.off, row.len, c->gap_eps, vals, codes);
+        offs[(size_t)r + 1] = (int64_t)codes.size();
+    }
+    return tvz_corpus_upload_impl(c->gap, ids.data(), offs.data(), codes.data(), n_rows, (int64_t)codes.size());
+}
+
+// one row's codes to the child, from the row's canonical keys (caller holds the parent's mu exclusively)
+int gap_upsert(tvz_corpus *c, int32_t video_id, const int64_t *keys, int64_t len) {
+    thread_local std::vector<double> codes, vals;
+    codes.clear();
+    tvz_gap::row_codes(keys, len, c->gap_eps, vals, codes);
+    return tvz_corpus_upsert_impl(c->gap, video_id, codes.data(), (int64_t)codes.size());
+}
+
+}  // namespace
+
 static int tvz_corpus_destroy_impl(tvz_corpus *c) {
     if (!c) return TVZ_OK;
     DeviceGuard dg(c->device);
     {
         std::unique_lock<std::shared_mutex> lk(c->mu);
         wait_no_build(c, lk);
+        if (c->gap) {
+            (void)tvz_corpus_destroy_impl(c->gap);
+            c->gap = nullptr;
+        }
         if (c->mstream.s) (void)drain(c);
         for (Staging *s : c->all_staging) delete s;
     }
@@ -937,7 +977,8 @@ static int tvz_corpus_reserve_impl(tvz_corpus *c, int64_t n_rows, int64_t n_keys
     DeviceGuard dg(c->device);
     std::unique_lock<std::shared_mutex> lk(c->mu);
     wait_no_build(c, lk);
-    return reserve_locked(c, n_rows, n_keys + n_rows /* padding to even row lengths */);
+    if (int rc = reserve_locked(c, n_rows, n_keys + n_rows /* padding to even row lengths */)) return rc;
+    return c->gap ? tvz_corpus_reserve_impl(c->gap, n_rows, n_keys) : TVZ_OK;   // (a row has fewer codes than keys)
 }
 
 static int tvz_corpus_upload_impl(tvz_corpus *c, const int32_t *h_video_ids,
@@ -1008,7 +1049,7 @@ static int tvz_corpus_upload_impl(tvz_corpus *c, const int32_t *h_video_ids,
     if (int rc = reserve_locked(c, want_rows, want_keys)) return rc;
     // a failed index build leaves the corpus without one (every match sweeps): not an upload error
     (void)build_index(c);
-    return TVZ_OK;
+    return c->gap ? gap_upload(c) : TVZ_OK;
 }
 
 static int tvz_corpus_upsert_impl(tvz_corpus *c, int32_t video_id, const double *h_keys, int64_t n) {
@@ -1098,7 +1139,7 @@ static int tvz_corpus_upsert_impl(tvz_corpus *c, int32_t video_id, const double 
             c->ix_next_try_rows = 2 * (int64_t)c->h_rows.size();
             (void)build_index(c);
         }
-        return rc;
+        return c->gap ? gap_upsert(c, video_id, c->h_keys.data() + c->h_rows[r].off, len) : rc;
     }
     // fast path: payload -> pinned ring slot -> async copy into FRESH arena space -> 16-byte row
     // swap, all on the mutation stream; no wait for the host or for running matches
@@ -1150,6 +1191,10 @@ static int tvz_corpus_upsert_impl(tvz_corpus *c, int32_t video_id, const double 
     }
     c->mut_any = true;
     if (ix.building) ix.since_snap.push_back(r);       // dead in the generation being built
+    // the row's codes follow before the lock is let go of (a rebuild below releases it): the code table sees the
+    // upserts in the order of the rows
+    if (c->gap)
+        if (int rc = gap_upsert(c, video_id, tmp.data(), len)) return rc;
     // time for a (new) index?  Built in the background by this thread: the lock is released while
     // the GPU builds, matches and other upserts go on
     const bool want = ix.valid ? ix.n_delta >= delta_trigger(ix.now().n_main)
@@ -1177,7 +1222,7 @@ static int tvz_corpus_clear_impl(tvz_corpus *c) {
     c->live_keys = 0;
     index_drop(c);
     c->ix_next_try_rows = 0;
-    return TVZ_OK;
+    return c->gap ? tvz_corpus_clear_impl(c->gap) : TVZ_OK;
 }
 
 static int tvz_corpus_stats_impl(tvz_corpus *c, int64_t *n_rows, int64_t *n_keys,
@@ -2539,6 +2584,138 @@ int tvz_align_merge_local(AlignForm form, const int32_t *d_gathered, int32_t n_l
     f.merge(AlignMergeArgs{dim3((unsigned)tvz::ceil_div(Q, kAlMergeWaves)), reinterpret_cast<hipStream_t>(hip_stream),
                            d_gathered, n_lists, Q, k, flags, d_queries, d_q_offsets, d_topk, d_totals});
     return launched();
+}
+
+// ---- candidate ids from the gap codes (include/tvz_gap.h; kernels: tvz_gap_kernels.h) ------------------------------
+static int tvz_corpus_gap_index_impl(tvz_corpus *c, double gap_eps) {
+    TVZ_REQUIRE(c != nullptr, "corpus is NULL");
+    if (!(gap_eps >= 0.0 && gap_eps <= DBL_MAX))          // refuses NaN, inf and negative values
+        return tvz::fail(TVZ_ERR_INVALID, "gap_eps must be 0 (off) or finite and > 0 (got %g)", gap_eps);
+    DeviceGuard dg(c->device);
+    std::unique_lock<std::shared_mutex> lk(c->mu);
+    wait_no_build(c, lk);
+    if (int rc = drain(c)) return rc;
+    if (gap_eps == 0.0) {
+        if (c->gap) (void)tvz_corpus_destroy_impl(c->gap);    // (waits for the lookups in flight on it)
+        c->gap = nullptr;
+        c->gap_eps = 0.0;
+        return TVZ_OK;
+    }
+    if (c->gap && c->gap_eps == gap_eps) return TVZ_OK;
+    if (!c->gap)
+        if (int rc = tvz_corpus_create_impl(&c->gap, c->device)) { c->gap = nullptr; return rc; }
+    c->gap_eps = gap_eps;
+    int rc = gap_upload(c);
+    if (rc) {                                             // no half-made table: off, the caller may ask again
+        char msg[512];
+        snprintf(msg, sizeof msg, "%s", tvz::err_buf());
+        (void)tvz_corpus_destroy_impl(c->gap);
+        c->gap = nullptr;
+        c->gap_eps = 0.0;
+        snprintf(tvz::err_buf(), 512, "%s", msg);
+    }
+    return rc;
+}
+
+static int tvz_corpus_gap_index_stats_impl(tvz_corpus *c, double *gap_eps, int64_t *out) {
+    TVZ_REQUIRE(c != nullptr, "corpus is NULL");
+    std::shared_lock<std::shared_mutex> lk(c->mu);
+    if (gap_eps) *gap_eps = c->gap ? c->gap_eps : 0.0;
+    if (!out) return TVZ_OK;
+    for (int i = 0; i < 5; ++i) out[i] = 0;
+    if (!c->gap) return TVZ_OK;
+    if (int rc = tvz_corpus_stats_impl(c->gap, &out[0], &out[1], nullptr)) return rc;
+    return tvz_corpus_index_stats_impl(c->gap, &out[2], &out[3], nullptr, nullptr, &out[4]);
+}
+
+namespace {
+
+// what the call refuses before it looks at the workspace or the handle, in the header's order
+int check_candidates_args(int32_t max_query_len, int32_t min_count, int32_t cap, int32_t C) {
+    if (C < 1 || C > tvz_gap::kMaxC)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment candidates: C=%d outside 1..%d", (int)C, tvz_gap::kMaxC);
+    if (cap < C) return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment candidates: cap=%d below C=%d", (int)cap, (int)C);
+    TVZ_REQUIRE(min_count >= 1, "alignment candidates: min_count %d below 1", (int)min_count);
+    if (max_query_len > kAlMaxLen)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment candidates: max_query_len %d above %d", (int)max_query_len, kAlMaxLen);
+    return TVZ_OK;
+}
+
+// the lookup's own workspace: Q probe lists of up to max_probe_len slots, hit lists in the caller's (this call's) regions
+size_t candidates_match_bytes(int32_t Q, int32_t max_query_len) {
+    return ws_layout(nullptr, 0, Q, tvz_gap::max_probe_len(max_query_len), 0, 0, 1).total;
+}
+
+}  // namespace
+
+static int tvz_align_candidates_impl(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
+                                     int32_t max_query_len, int32_t min_count, const int32_t *d_exclude_ids, int32_t cap,
+                                     int32_t C, int32_t *d_out, void *d_workspace, size_t workspace_bytes, void *hip_stream) {
+    if (int rc = check_candidates_args(max_query_len, min_count, cap, C)) return rc;
+    const Batch b = align_batch(d_queries, d_q_offsets, Q, max_query_len, d_exclude_ids);
+    if (int rc = check_batch_args(c, b, cap)) return rc;
+    if (Q == 0) return TVZ_OK;
+    const size_t match_bytes = candidates_match_bytes(Q, max_query_len);
+    const size_t have = d_workspace ? workspace_bytes : 0;
+    const size_t need = tvz_gap::ws_bytes(Q, cap, match_bytes, max_query_len);
+    if (have < need)
+        return tvz::fail(TVZ_ERR_WORKSPACE, "alignment candidates: workspace of %zu bytes, %zu bytes missing (size it with "
+                         "tvz_align_candidates_workspace_bytes)", have, need - have);
+    TVZ_REQUIRE(d_out != nullptr && (reinterpret_cast<uintptr_t>(d_out) & 7) == 0, "d_out is NULL or not 8-byte aligned");
+    const int64_t room = tvz_gap::ws_room(Q, cap, match_bytes, have);
+    const tvz_gap::WsRegions r = tvz_gap::ws_regions(Q, cap, match_bytes, room);
+    unsigned char *base = reinterpret_cast<unsigned char *>(al256(reinterpret_cast<uintptr_t>(d_workspace)));
+    int32_t *hits = reinterpret_cast<int32_t *>(base + r.hits), *hits_n = reinterpret_cast<int32_t *>(base + r.hits_n);
+    int64_t *p_off = reinterpret_cast<int64_t *>(base + r.p_off);
+    int32_t *qm = reinterpret_cast<int32_t *>(base + r.qm), *sp = reinterpret_cast<int32_t *>(base + r.sp);
+    double *sv = reinterpret_cast<double *>(base + r.sv), *probes = reinterpret_cast<double *>(base + r.probes);
+    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+    DeviceGuard dg(c->device);
+    std::shared_lock<std::shared_mutex> lk(c->mu);            // parent, then (inside the lookup) child
+    if (!c->gap)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment candidates: this corpus keeps no gap codes (tvz_corpus_gap_index)");
+    // the sorted queries (hits_n = 0 meanwhile; the lookup writes every count)
+    hipLaunchKernelGGL(ts_tol_sort_kernel, dim3((unsigned)tvz::ceil_div(std::max(max_query_len, 1), kTolSortBlock), (unsigned)Q),
+                       dim3(kTolSortBlock), 0, st, d_queries, d_q_offsets, max_query_len, room, sv, sp, qm, hits_n);
+    TVZ_HIP(hipGetLastError());
+    hipLaunchKernelGGL(ts_gapc_offsets_kernel, dim3(1), dim3(kGapOffBlock), 0, st, qm, Q, p_off);
+    TVZ_HIP(hipGetLastError());
+    if (max_query_len >= 4) {
+        hipLaunchKernelGGL(ts_gapc_probe_kernel, dim3((unsigned)tvz::ceil_div(max_query_len - 3, kGapProbeBlock), (unsigned)Q),
+                           dim3(kGapProbeBlock), 0, st, sv, d_q_offsets, qm, c->gap_eps, p_off, probes);
+        TVZ_HIP(hipGetLastError());
+    }
+    // count(q, r) is the exact match's count of the probes over the codes: the index, its delta table, the exclusions
+    if (int rc = tvz_match_impl(c->gap, probes, p_off, Q, tvz_gap::max_probe_len(max_query_len), min_count, d_exclude_ids, cap,
+                                hits, hits_n, base + r.match, match_bytes, TVZ_ALGO_AUTO, hip_stream))
+        return rc;
+    hipLaunchKernelGGL(ts_gapc_select_kernel, dim3((unsigned)Q), dim3(kBlock), 0, st, hits, hits_n, qm, cap, C, d_out);
+    TVZ_HIP(hipGetLastError());
+    return record(c, st);
+}
+
+TVZ_EXPORT int tvz_corpus_gap_index(tvz_corpus *c, double gap_eps) {
+    TVZ_GUARDED(tvz_corpus_gap_index_impl(c, gap_eps));
+}
+
+TVZ_EXPORT int tvz_corpus_gap_index_stats(tvz_corpus *c, double *gap_eps, int64_t out[5]) {
+    TVZ_GUARDED(tvz_corpus_gap_index_stats_impl(c, gap_eps, out));
+}
+
+TVZ_EXPORT size_t tvz_align_candidates_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t cap,
+                                                       int32_t C) {
+    if (Q < 0 || Q > 65535 || max_query_len < 0 || max_query_len > kAlMaxLen || total_query_keys < 0 || C < 1 ||
+        C > tvz_gap::kMaxC || cap < C)
+        return 0;
+    const int64_t keys = total_query_keys > 0 ? total_query_keys : (int64_t)Q * max_query_len;
+    return tvz_gap::ws_bytes(Q, cap, candidates_match_bytes(Q, max_query_len), std::max<int64_t>(keys, max_query_len));
+}
+
+TVZ_EXPORT int tvz_align_candidates(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
+                                    int32_t max_query_len, int32_t min_count, const int32_t *d_exclude_ids, int32_t cap, int32_t C,
+                                    int32_t *d_out, void *d_workspace, size_t workspace_bytes, void *hip_stream) {
+    TVZ_GUARDED(tvz_align_candidates_impl(c, d_queries, d_q_offsets, Q, max_query_len, min_count, d_exclude_ids, cap, C, d_out,
+                                          d_workspace, workspace_bytes, hip_stream));
 }
 
 #ifdef TVZ_IX_STAMP

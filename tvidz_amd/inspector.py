@@ -94,7 +94,7 @@ class Inspector:
                  profile: bool = False, match_tolerance: float = 0.0, near_top_k: Optional[int] = None,
                  near_any_offset: bool = False, near_score: str = "jaccard", near_min_votes: int = 1,
                  near_rates=None, near_spans: bool = False, near_parts: Optional[int] = None,
-                 near_two_bins: bool = False):
+                 near_two_bins: bool = False, near_candidates: Optional[int] = None, near_gap_eps: float = 1.0 / 30):
         self.store = store
         # opt-in: the near-duplicate report from the K best-aligned rows the device keeps (tvz_align_topk) instead of
         # one row per corpus row walked here.  None: the walk, exactly as before.  Refused here where the store's
@@ -187,6 +187,36 @@ class Inspector:
                 raise RuntimeError(f"near_two_bins=True: the store's corpus "
                                    f"({type(getattr(store, 'corpus', None)).__name__}) has no align_wide_topk; "
                                    "use a DeviceCorpus, a service.ShardedCorpus or a service.RankCorpus")
+        # opt-in: the search at any shift WITHOUT the sweep over every row - the near_candidates stored videos that share
+        # the most gap codes with the upload (tvz_align_candidates over the corpus's gap index of near_gap_eps seconds,
+        # turned on here, once) are aligned in full by one align_parts call, and the report is made from its part 0 with
+        # the same score, thresholds and order as the sweep's.  Codes are made at rate 1 and the parts call counts single
+        # bins: refused with near_rates and near_two_bins.  An upload the candidates call refuses (more than 514 cuts)
+        # takes the configured sweep.  None: nothing changes.
+        self.near_candidates = None if near_candidates is None else int(near_candidates)
+        self.near_gap_eps = float(near_gap_eps)
+        if self.near_candidates is not None:
+            if not near_duplicates or self.near_top_k is None or not self.near_any_offset:
+                raise ValueError(f"near_candidates={self.near_candidates} needs near_duplicates=True, near_top_k and "
+                                 "near_any_offset=True")
+            if not self.near_top_k <= self.near_candidates <= 64:
+                raise ValueError(f"near_candidates must be None or near_top_k..64 ({self.near_top_k}..64), "
+                                 f"got {near_candidates!r}")
+            if not (0.0 < self.near_gap_eps <= sys.float_info.max):
+                raise ValueError(f"near_gap_eps must be finite and > 0, got {near_gap_eps!r}")
+            what = f"near_candidates={self.near_candidates}"
+            if self.near_rates is not None:
+                raise RuntimeError(f"{what} with near_rates={self.near_rates}: the gap codes are made at rate 1; "
+                                   "use one of them")
+            if self.near_two_bins:
+                raise RuntimeError(f"{what} with near_two_bins=True: align_parts counts single bins (it has no flags); "
+                                   "use one of them")
+            corpus = getattr(store, "corpus", None)
+            if not (_corpus_can(corpus, "align_candidates", "supports_align_candidates") and hasattr(corpus, "set_gap_index")
+                    and _corpus_can(corpus, "align_parts", "supports_align_parts")):
+                raise RuntimeError(f"{what}: the store's corpus ({type(corpus).__name__}) has no align_candidates; "
+                                   "use a DeviceCorpus")
+            corpus.set_gap_index(self.near_gap_eps)
         # opt-in, never the default: duplicates by the TOLERANT count (include/tvz.h tvz_find_duplicates_tol)
         # instead of the reference's exact float64 equality; the verdict, the truncation at kth and the stored
         # duplicates all follow it.  Refused here, before any upload, where the store's corpus cannot do it.
@@ -475,8 +505,12 @@ class Inspector:
         per part the shift, the spans (as "upload_span" / "stored_span" are made) and the raw votes - and
         "parts_score": with v = the sum of min(votes_i, nq_i, nr_i), v / (sum nq_i + sum nr_i - v)."""
         rates = self.near_rates or (1.0,)
-        blocks = self.store.corpus.align_parts([scene_timestamps], [[d["video_id"] for d in out]], eps=self.near_eps,
-                                               rates=rates, min_votes=self.near_min_votes, max_parts=self.near_parts)[0]
+        kept = getattr(self._tls, "candidate_parts", None) if self.near_candidates is not None else None
+        if kept is not None:                                                   # near_candidates: the search's own parts block
+            blocks = [kept[d["video_id"]] for d in out]
+        else:
+            blocks = self.store.corpus.align_parts([scene_timestamps], [[d["video_id"] for d in out]], eps=self.near_eps,
+                                                   rates=rates, min_votes=self.near_min_votes, max_parts=self.near_parts)[0]
         cuts = np.sort(np.asarray(scene_timestamps, dtype=np.float64))
         cuts = cuts[~np.isnan(cuts)]
         for d, block in zip(out, blocks):
@@ -493,6 +527,42 @@ class Inspector:
             d["parts"] = parts
             d["parts_score"] = round(v / float(u - v), 4) if u > v else 0.0
 
+    def _near_candidates(self, video_id: int, scene_timestamps):
+        """near_candidates: the rows _near filters, made without a sweep - ONE align_candidates call names the stored
+        videos that share the most gap codes with the upload, ONE align_parts call aligns them in full, and part 0 of
+        every pair is what the span search reports for that row: (video_id, row_len, best_bin, votes, rate_index,
+        t_first, t_last, nr).  The same fixed-point score, thresholds and order as the sweep keeps its rows by, the
+        near_top_k best.  Rows of four columns where the configuration's sweep reports no span.  None: the candidates
+        call refused the upload.  The parts block stays with the calling thread for _near_parts."""
+        from .corpus import align_span_order_key
+        corpus = self.store.corpus
+        ids, totals = corpus.align_candidates([scene_timestamps], c=self.near_candidates, exclude_ids=[int(video_id)])
+        if int(totals[0]) == -(1 << 31):
+            return None
+        ids = [int(r[0]) for r in ids[0] if r[0] >= 0]
+        if not ids:
+            return []
+        blocks = corpus.align_parts([scene_timestamps], [ids], eps=self.near_eps, rates=(1.0,), min_votes=self.near_min_votes,
+                                    max_parts=self.near_parts or 1)[0]
+        one = 1 << 20
+        min_score = max(0, min(one, int(self.near_jaccard * one)))
+        contain, local = self.near_score == "containment", self.near_score == "local"
+        spans = self.near_spans or local
+        rows, kept = [], {}
+        for block in blocks:
+            vid, row_len, rate, n_parts, _, m = (int(x) for x in block[0])
+            if n_parts < 1:                                                    # refused, no row of the id, or no part
+                continue
+            best_bin, votes, t_first, t_last, _, nr = (int(x) for x in block[1])
+            row = (vid, row_len, best_bin, votes, rate, t_first, t_last, nr)
+            key = align_span_order_key(row, m, contain=contain, local=local)
+            if -key[0] >= min_score:
+                rows.append((key, row))
+                kept[vid] = block
+        rows.sort()
+        self._tls.candidate_parts = kept
+        return [row if spans else row[:4] for _, row in rows[:self.near_top_k]]
+
     def _near_rows(self, video_id: int, scene_timestamps):
         """_near_search's (rows, rated)."""
         return self._near_search(video_id, scene_timestamps)[:2]
@@ -505,6 +575,11 @@ class Inspector:
         of eight columns carry the span behind it (tvz_align_span_topk); half = 0.5 where best_bin is the lower bin of
         a window of two (near_two_bins), so the shift is (best_bin + half) x near_eps, and 0.0 otherwise."""
         corpus = self.store.corpus
+        if self.near_candidates is not None:
+            self._tls.candidate_parts = None
+            rows = self._near_candidates(video_id, scene_timestamps)
+            if rows is not None:                                               # (None: refused -> the configured sweep)
+                return rows, False, 0.0
         if self.near_top_k is not None:
             one = 1 << 20
             min_score = max(0, min(one, int(self.near_jaccard * one)))          # int() floors: the value is >= 0
