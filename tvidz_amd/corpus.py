@@ -278,6 +278,84 @@ def align_candidates_workspace_bytes(Q: int, max_query_len: int, total_query_key
                                                                 int(cap), int(c)))
 
 
+ALIGN_CANDIDATES_MERGE_MAX_LISTS = 16                               # include/tvz_gap_shards.h TVZ_GAP_MERGE_MAX_LISTS
+
+
+def align_candidates_sharded_workspace_bytes(Q: int, max_query_len: int, total_query_keys: int = 0, cap: int = 4096,
+                                             c: int = 16, n_ranks: int = 1) -> int:
+    """tvz_align_candidates_sharded_workspace_bytes: align_candidates_workspace_bytes + the rank's own block and
+    `n_ranks` gathered ones (Q x (c + 1) x 8 bytes each)."""
+    return int(_lib.load().tvz_align_candidates_sharded_workspace_bytes(int(Q), int(max_query_len), int(total_query_keys),
+                                                                        int(cap), int(c), int(n_ranks)))
+
+
+def align_candidates_merge(blocks: np.ndarray) -> np.ndarray:
+    """The blocks of R shards to one align_candidates call, on the host: int32 [R, Q, c + 1, 2] -> int32 [Q, c + 1, 2]
+    (include/tvz_gap_shards.h, THE MERGE).  Per query every row with video_id >= 0 takes part, the c largest by (count
+    descending, video_id ascending) are kept - equal rows all of them - and padded with (-1, 0); the last row is (-1,
+    total): the sum of the shards' |total|, saturated at 2^31 - 1, negated if one was negative, and a query some shard
+    refused (ALIGN_CANDIDATES_REFUSED) is refused.  Any R: the rule is associative."""
+    blocks = np.asarray(blocks, dtype=np.int32)
+    R, Q, c1, _ = blocks.shape
+    c = c1 - 1
+    out = np.empty((Q, c1, 2), dtype=np.int32)
+    out[:, :c, 0], out[:, :c, 1] = -1, 0
+    rows = blocks[:, :, :c].transpose(1, 0, 2, 3).reshape(Q, R * c, 2).astype(np.int64)
+    valid = rows[:, :, 0] >= 0
+    # one sortable word per row, as the kernels': padding sorts last
+    word = np.where(valid, (rows[:, :, 1] << 32) | ((1 << 31) - 1 - rows[:, :, 0]), -1)
+    order = np.argsort(-word, axis=1, kind="stable")[:, :c]
+    best = np.take_along_axis(rows, order[:, :, None], 1)
+    keep = np.take_along_axis(valid, order, 1)
+    out[:, :c][keep] = best[keep].astype(np.int32)
+    t = blocks[:, :, c, 1].astype(np.int64)
+    total = np.minimum(np.abs(t).sum(0), (1 << 31) - 1)
+    total = np.where((t < 0).any(0), -total, total)
+    refused = (t == ALIGN_CANDIDATES_REFUSED).any(0)
+    out[refused, :c] = (-1, 0)
+    out[:, c, 0] = -1
+    out[:, c, 1] = np.where(refused, ALIGN_CANDIDATES_REFUSED, total).astype(np.int32)
+    return out
+
+
+def align_candidates_merge_device(gathered: torch.Tensor, stream: Optional[torch.cuda.Stream] = None,
+                                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """tvz_align_candidates_merge: align_candidates_merge on the device - the blocks of R <= 16 shards to one
+    align_candidates call, int32 [R, Q, c + 1, 2] -> int32 [Q, c + 1, 2], one launch on `stream` (default: the
+    current one)."""
+    if gathered.dim() != 4 or gathered.shape[3] != 2 or gathered.dtype != torch.int32 or gathered.device.type != "cuda" \
+            or not gathered.is_contiguous():
+        raise RuntimeError("gathered must be a contiguous int32 CUDA tensor [R, Q, c + 1, 2]")
+    R, Q, c1, _ = gathered.shape
+    out = _out(out, (Q, c1, 2), gathered.device)
+    s = stream if stream is not None else torch.cuda.current_stream(gathered.device)
+    with torch.cuda.device(gathered.device):
+        _lib.check(_lib.load().tvz_align_candidates_merge(gathered.data_ptr() if gathered.numel() else None, R, Q, c1 - 1,
+                                                          out.data_ptr() if out.numel() else None, s.cuda_stream))
+    return out
+
+
+def align_candidates_shards(shards: Sequence["DeviceCorpus"], d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
+                            max_query_len: int, *, c: int, min_count: int = 2, cap: int = 4096,
+                            d_exclude_ids: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                            stream: Optional[torch.cuda.Stream] = None):
+    """tvz_align_candidates on every handle of ONE device + the merge behind one library call
+    (tvz_align_candidates_shards): -> (blocks int32 [R, Q, c + 1, 2], merged int32 [Q, c + 1, 2]).  `workspace`:
+    align_candidates_workspace_bytes, one handle's, serves all of them."""
+    Q = d_q_offsets.numel() - 1
+    dev, s, ws, excl = shards[0]._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace,
+                                          align_candidates_workspace_bytes(Q, max_query_len, d_queries.numel(), cap, c))
+    R = len(shards)
+    handles = (C.c_void_p * R)(*[sh._h for sh in shards])
+    blocks = torch.empty((R, Q, max(int(c), 0) + 1, 2), dtype=torch.int32, device=dev)
+    merged = torch.empty((Q, max(int(c), 0) + 1, 2), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().tvz_align_candidates_shards(
+            handles, R, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), int(min_count), excl, int(cap),
+            int(c), blocks.data_ptr(), merged.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
+    return blocks, merged
+
+
 def align_parts_ids(video_ids, Q: int, dev) -> torch.Tensor:
     """The ids of tvz_align_parts as a 2-D int32 tensor [Q, k] on `dev`: a device tensor (any strides) as it is, host
     lists or arrays copied once."""
@@ -937,6 +1015,22 @@ class Comm:
             corpus._h, self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), ids, id_stride,
             query_id_stride, k, float(eps), _wide_offset(eps, max_offset), *_rates(rates), int(min_votes), P, out.data_ptr(),
             ws.data_ptr(), ws.numel(), s.cuda_stream))
+        return out
+
+    def align_candidates_sharded(self, corpus: DeviceCorpus, d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
+                                 max_query_len: int, *, c: int, min_count: int = 2, cap: int = 4096,
+                                 d_exclude_ids: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                                 stream: Optional[torch.cuda.Stream] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """tvz_align_candidates_sharded: the local align_candidates -> ncclAllGather of the [Q, c + 1, 2] blocks -> the
+        merge; -> int32 [Q, c + 1, 2], identical on every rank.  Every rank's handle keeps gap codes of one gap_eps."""
+        Q = d_q_offsets.numel() - 1
+        dev, s, ws, excl = corpus._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace,
+                                           align_candidates_sharded_workspace_bytes(Q, max_query_len, d_queries.numel(), cap,
+                                                                                    c, self.n_ranks))
+        out = _out(out, (Q, max(int(c), 0) + 1, 2), dev)
+        _lib.check(self.lib.tvz_align_candidates_sharded(
+            corpus._h, self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), int(min_count), excl,
+            int(cap), int(c), out.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
         return out
 
     def align_sharded(self, f: AlignForm, corpus, d_queries, d_q_offsets, max_query_len, k, d_exclude_ids, workspace, stream,

@@ -128,3 +128,9 @@ int tvz_align_parts_local(tvz_corpus *c, const Batch &b, const AlignPartsCall &p
                           void *hip_stream, ShardBlocks *blocks, LateCheck late = {});
 int tvz_align_parts_merge_local(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t k, int32_t max_parts,
                                 int32_t *d_parts, void *hip_stream);
+// tvz_align_candidates with the sharded form's blocks in front of its workspace (the answer goes into the workspace's
+// own block: `blocks` is told where), and the merge of the gathered blocks (tvz_match.hip).
+int tvz_align_candidates_local(tvz_corpus *c, const Batch &b, int32_t min_count, int32_t cap, int32_t C, Workspace ws,
+                               int32_t n_ranks, void *hip_stream, ShardBlocks *blocks, LateCheck late = {});
+int tvz_align_candidates_merge_local(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t C, int32_t *d_out,
+                                     void *hip_stream);

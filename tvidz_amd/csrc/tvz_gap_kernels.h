@@ -3,11 +3,12 @@
 //   ts_gapc_offsets_kernel  where every query's probes go: an exclusive scan of the queries' probe slots.
 //   ts_gapc_probe_kernel    the probes: a thread per (query, position) writes its 8 slots.
 //   ts_gapc_select_kernel   per query the C best of the lookup's hit list, the block and the total.
+//   ts_gapc_merge_kernel    per query the C best of up to 16 such blocks (tvz_align_candidates_merge).
 //
 // Between the last two the internal match runs over the handle's code table (the queries are the probe lists).
 // The queries come sorted from ts_tol_sort_kernel (tvz_tol_kernels.h): sv[at .. at + m), at = q_offsets[q] -
 // q_offsets[0], m = qm[q]; qm[q] < 0: longer than the call's max_query_len.  From tvz_topk_kernels.h: bitonic_sort,
-// sort_and_keep, topk_total; from tvz_wave.h: wave_scan_incl, waves_sum.  Included by tvz_match.hip behind them.
+// sort_and_keep, topk_total; from tvz_wave.h: wave_scan_incl, waves_sum, wave_lds_fence.  Included by tvz_match.hip behind them.
 #pragma once
 #include "tvz_gap_codes.h"
 #include "tvz_topk_kernels.h"
@@ -124,6 +125,84 @@ __global__ __launch_bounds__(kBlock) void ts_gapc_select_kernel(const int32_t *_
         o[i] = w == 0ULL ? make_int2(-1, 0) : make_int2(0x7fffffff - (int32_t)(uint32_t)w, (int32_t)(w >> 32));
     }
     if (threadIdx.x == 0) o[C] = make_int2(-1, topk_total(total < 0 ? 0 : total, total > cap));
+}
+
+// ---- the merge of the shards' blocks (tvz_align_candidates_merge, include/tvz_gap_shards.h) -------------------------
+constexpr int kGapMergeBlock = 256;
+constexpr int kGapMergeWaves = kGapMergeBlock / 64;    // queries per block: a wave each
+constexpr int kGapMergeMaxLists = 16;                  // one total per lane; 16 x kMaxC = 1,024 rows of a query at most
+
+// dynamic LDS of a launch: every wave's n_lists x C words
+inline size_t gapc_merge_lds_bytes(int32_t n_lists, int32_t C) {
+    return (size_t)kGapMergeWaves * (size_t)n_lists * (size_t)C * sizeof(uint64_t);
+}
+
+// gathered int32[n_lists][Q][C + 1][2] -> out int32[Q][C + 1][2], both in the block format of ts_gapc_select_kernel.
+// grid = ceil(Q / kGapMergeWaves); one wave per query, no block barrier.  A row (video_id >= 0, count >= 0) becomes the
+// word 2^63 | count << 32 | (2^31 - 1 - video_id), padding the word 0, so that "larger word" is the contract's order
+// and padding is last; the words of list l lie in the wave's LDS at [l C, l C + C).  PRECONDITION: every list is sorted
+// by that order (descending words).  The rank of row p of list l is p + over the lists before it their words >= w +
+// over the lists behind it their words > w: equal words are ordered by (list, position), so the ranks of a query's
+// rows are the distinct numbers 0 .. n - 1, and the rows of rank < C are the output - each written by the lane that
+// holds it, the rest of the C rows padded.  A count in a sorted list is a branch-free binary search over LDS.  Whatever
+// the lists hold, a rank is >= 0 and only ranks < C are written: nothing is stored outside the query's block.
+// The total: the lists' last rows by topk_total's rule (|t| summed in 64 bits, saturated, negated if any was negative);
+// INT32_MIN in any list refuses the query (all padding, INT32_MIN).  One 8-byte store per row.
+__global__ __launch_bounds__(kGapMergeBlock) void ts_gapc_merge_kernel(const int32_t *__restrict__ gathered, int32_t n_lists,
+                                                                       int32_t Q, int32_t C, int32_t *__restrict__ out) {
+    extern __shared__ uint64_t gapc_merge_sh[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t q = (int64_t)blockIdx.x * kGapMergeWaves + wave;
+    if (q >= Q) return;                                              // wave-uniform
+    const int n = n_lists * C;                                       // <= 1,024
+    uint64_t *w = gapc_merge_sh + (size_t)wave * n;
+    const int64_t c1 = (int64_t)C + 1;
+    const int2 *blocks = reinterpret_cast<const int2 *>(gathered);   // [n_lists][Q][C + 1] rows of 8 bytes
+    int2 *o = reinterpret_cast<int2 *>(out) + q * c1;
+    // the lists' totals, one per lane
+    const int32_t t = lane < n_lists ? blocks[((int64_t)lane * Q + q) * c1 + C].y : 0;
+    long long sum = t == INT32_MIN ? 0 : (t < 0 ? -(long long)t : (long long)t);
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+    if (__ballot(t == INT32_MIN) != 0ull) {                          // refused: wave-uniform
+        for (int i = lane; i <= C; i += 64) o[i] = make_int2(-1, i == C ? INT32_MIN : 0);
+        return;
+    }
+    const bool over = __ballot(t < 0) != 0ull;
+    int n_rows = 0;                                                  // wave-uniform: the rows that are no padding
+    for (int i0 = 0; i0 < n; i0 += 64) {
+        const int i = i0 + lane;
+        uint64_t word = 0;
+        if (i < n) {
+            const int l = i / C, p = i - l * C;
+            const int2 r = blocks[((int64_t)l * Q + q) * c1 + p];
+            if (r.x >= 0) word = (1ULL << 63) | ((uint64_t)((uint32_t)r.y & 0x7fffffffu) << 32) | (uint32_t)(0x7fffffff - r.x);
+            w[i] = word;
+        }
+        n_rows += __popcll(__ballot(word != 0ULL));
+    }
+    wave_lds_fence();
+    int top = 1;                                                     // the largest power of two <= C
+    while (top * 2 <= C) top *= 2;
+    for (int i0 = 0; i0 < n; i0 += 64) {
+        const int i = i0 + lane;
+        const uint64_t word = i < n ? w[i] : 0ULL;
+        if (word == 0ULL) continue;
+        const int l = i / C;
+        int rank = i - l * C;                                        // the rows before it in its own list
+        for (int m = 0; m < n_lists && rank < C; ++m) {
+            if (m == l) continue;
+            const uint64_t thr = word + (m > l ? 1ULL : 0ULL);       // (a word is below 2^64 - 1: the id's field is 31 bits)
+            const uint64_t *lm = w + m * C;
+            int at = 0;                                              // the words of list m that are >= thr
+            for (int step = top; step > 0; step >>= 1)
+                if (at + step <= C && lm[at + step - 1] >= thr) at += step;
+            rank += at;
+        }
+        if (rank < C)
+            o[rank] = make_int2(0x7fffffff - (int32_t)(uint32_t)(word & 0x7fffffffu), (int32_t)((word >> 32) & 0x7fffffffu));
+    }
+    for (int i = n_rows + lane; i < C; i += 64) o[i] = make_int2(-1, 0);
+    if (lane == 0) o[C] = make_int2(-1, topk_total(sum, over));
 }
 
 }  // namespace

@@ -30,6 +30,7 @@
 #include "tvz_align_parts_kernels.h"
 #include "tvz_gap_kernels.h"
 #include "tvz_gap.h"
+#include "tvz_gap_shards.h"
 #include "tvz_handle.h"
 #include "tvz_index_build.h"
 
@@ -2648,19 +2649,31 @@ size_t candidates_match_bytes(int32_t Q, int32_t max_query_len) {
 
 }  // namespace
 
+// `late`: what a sharded form still refuses behind all of the call's own refusals and in front of the first launch.
+// `gap_eps` (may be NULL): the width of the handle's codes, read under the handle's lock.  `enqueue` = false: the
+// refusals only (the _shards form asks every handle first).  `front`: the sharded form's blocks take that many bytes of
+// the caller's buffer in front of this call's part - workspace_bytes is the WHOLE buffer's size, d_workspace where this
+// call's part starts.
+struct CandidatesFront {
+    size_t bytes = 0;
+    const char *sizer = "tvz_align_candidates_workspace_bytes";
+};
 static int tvz_align_candidates_impl(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
                                      int32_t max_query_len, int32_t min_count, const int32_t *d_exclude_ids, int32_t cap,
-                                     int32_t C, int32_t *d_out, void *d_workspace, size_t workspace_bytes, void *hip_stream) {
+                                     int32_t C, int32_t *d_out, void *d_workspace, size_t workspace_bytes, void *hip_stream,
+                                     LateCheck late = {}, double *gap_eps = nullptr, bool enqueue = true,
+                                     CandidatesFront front = {}) {
     if (int rc = check_candidates_args(max_query_len, min_count, cap, C)) return rc;
     const Batch b = align_batch(d_queries, d_q_offsets, Q, max_query_len, d_exclude_ids);
     if (int rc = check_batch_args(c, b, cap)) return rc;
     if (Q == 0) return TVZ_OK;
     const size_t match_bytes = candidates_match_bytes(Q, max_query_len);
-    const size_t have = d_workspace ? workspace_bytes : 0;
+    const size_t whole = d_workspace ? workspace_bytes : 0;
     const size_t need = tvz_gap::ws_bytes(Q, cap, match_bytes, max_query_len);
-    if (have < need)
-        return tvz::fail(TVZ_ERR_WORKSPACE, "alignment candidates: workspace of %zu bytes, %zu bytes missing (size it with "
-                         "tvz_align_candidates_workspace_bytes)", have, need - have);
+    if (whole < need + front.bytes)
+        return tvz::fail(TVZ_ERR_WORKSPACE, "alignment candidates: workspace of %zu bytes, %zu bytes missing (size it with %s)",
+                         whole, need + front.bytes - whole, front.sizer);
+    const size_t have = whole - front.bytes;
     TVZ_REQUIRE(d_out != nullptr && (reinterpret_cast<uintptr_t>(d_out) & 7) == 0, "d_out is NULL or not 8-byte aligned");
     const int64_t room = tvz_gap::ws_room(Q, cap, match_bytes, have);
     const tvz_gap::WsRegions r = tvz_gap::ws_regions(Q, cap, match_bytes, room);
@@ -2674,6 +2687,9 @@ static int tvz_align_candidates_impl(tvz_corpus *c, const double *d_queries, con
     std::shared_lock<std::shared_mutex> lk(c->mu);            // parent, then (inside the lookup) child
     if (!c->gap)
         return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment candidates: this corpus keeps no gap codes (tvz_corpus_gap_index)");
+    if (gap_eps) *gap_eps = c->gap_eps;
+    if (int rc = late()) return rc;
+    if (!enqueue) return TVZ_OK;
     // the sorted queries (hits_n = 0 meanwhile; the lookup writes every count)
     hipLaunchKernelGGL(ts_tol_sort_kernel, dim3((unsigned)tvz::ceil_div(std::max(max_query_len, 1), kTolSortBlock), (unsigned)Q),
                        dim3(kTolSortBlock), 0, st, d_queries, d_q_offsets, max_query_len, room, sv, sp, qm, hits_n);
@@ -2692,6 +2708,125 @@ static int tvz_align_candidates_impl(tvz_corpus *c, const double *d_queries, con
     hipLaunchKernelGGL(ts_gapc_select_kernel, dim3((unsigned)Q), dim3(kBlock), 0, st, hits, hits_n, qm, cap, C, d_out);
     TVZ_HIP(hipGetLastError());
     return record(c, st);
+}
+
+// ---- the candidates over a sharded table (include/tvz_gap_shards.h) ---------------------------------------------
+namespace {
+
+// what the candidates merge refuses, apart from its pointers
+int check_candidates_merge(int32_t n_lists, int32_t C) {
+    if (n_lists < 1 || n_lists > kGapMergeMaxLists)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment candidates merge: %d lists outside 1..%d", (int)n_lists, kGapMergeMaxLists);
+    if (C < 1 || C > tvz_gap::kMaxC)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment candidates merge: C=%d outside 1..%d", (int)C, tvz_gap::kMaxC);
+    return TVZ_OK;
+}
+
+bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+
+}  // namespace
+
+// used by tvz_comm.hip too (same shared object, not exported): the merge of the gathered blocks
+int tvz_align_candidates_merge_local(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t C, int32_t *d_out,
+                                     void *hip_stream) {
+    if (int rc = check_candidates_merge(n_lists, C)) return rc;
+    TVZ_REQUIRE(Q >= 0, "Q=%d is negative", (int)Q);
+    if (Q == 0) return TVZ_OK;
+    TVZ_REQUIRE(d_gathered && d_out, "NULL argument");
+    TVZ_REQUIRE(aligned8(d_gathered) && aligned8(d_out), "alignment candidates merge: the blocks and d_out must be 8-byte aligned");
+    const uintptr_t g0 = reinterpret_cast<uintptr_t>(d_gathered), o0 = reinterpret_cast<uintptr_t>(d_out);
+    const size_t block = tvz_gap::block_bytes(Q, C);
+    TVZ_REQUIRE(o0 + block <= g0 || g0 + (size_t)n_lists * block <= o0, "alignment candidates merge: d_out lies inside the blocks");
+    hipLaunchKernelGGL(ts_gapc_merge_kernel, dim3((unsigned)tvz::ceil_div(Q, kGapMergeWaves)), dim3(kGapMergeBlock),
+                       gapc_merge_lds_bytes(n_lists, C), reinterpret_cast<hipStream_t>(hip_stream), d_gathered, n_lists, Q, C, d_out);
+    return launched();
+}
+
+// ... and the local call with the sharded form's blocks in front of its workspace (tvz_gap_codes.h: ws_shard_carve)
+int tvz_align_candidates_local(tvz_corpus *c, const Batch &b, int32_t min_count, int32_t cap, int32_t C, Workspace ws,
+                               int32_t n_ranks, void *hip_stream, ShardBlocks *blocks, LateCheck late) {
+    // (arguments the carving cannot take are refused by the call itself, in front of its look at the workspace)
+    const bool carve = ws.p != nullptr && b.Q > 0 && b.Q <= 65535 && C >= 1 && C <= tvz_gap::kMaxC;
+    tvz_gap::ShardWs s{0, 0, 0};
+    if (carve) s = tvz_gap::ws_shard_carve(reinterpret_cast<uintptr_t>(ws.p), ws.bytes, b.Q, C, n_ranks);
+    int32_t *local = reinterpret_cast<int32_t *>(s.front);
+    if (carve && blocks) {
+        const tvz_gap::ShardWsRegions r = tvz_gap::ws_shard_regions(b.Q, C, n_ranks);
+        *blocks = ShardBlocks{local, reinterpret_cast<int32_t *>(s.front + r.gathered)};
+    }
+    // the call judges the WHOLE buffer's size, front included, and lays its own part out from s.plain on
+    const CandidatesFront front{carve ? tvz_gap::ws_shard_front_bytes(b.Q, C, n_ranks) : 0,
+                                "tvz_align_candidates_sharded_workspace_bytes"};
+    return tvz_align_candidates_impl(c, b.d_queries, b.d_q_offsets, b.Q, b.max_query_len, min_count, b.d_exclude_ids, cap, C,
+                                     local, carve ? reinterpret_cast<void *>(s.plain) : nullptr, ws.bytes, hip_stream, late,
+                                     nullptr, true, front);
+}
+
+size_t tvz_align_candidates_sharded_sizing(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t cap, int32_t C,
+                                           int32_t n_ranks) {
+    const size_t plain = tvz_align_candidates_workspace_bytes(Q, max_query_len, total_query_keys, cap, C);
+    if (plain == 0 || n_ranks < 0) return 0;
+    return plain + tvz_gap::ws_shard_front_bytes(Q, C, n_ranks);
+}
+
+// The shards of one process: every handle's call into its block of d_blocks, then the merge.
+static int align_candidates_shards_impl(tvz_corpus *const *shards, int32_t n_shards, const double *d_queries,
+                                        const int64_t *d_q_offsets, int32_t Q, int32_t max_query_len, int32_t min_count,
+                                        const int32_t *d_exclude_ids, int32_t cap, int32_t C, int32_t *d_blocks, int32_t *d_out,
+                                        void *d_workspace, size_t workspace_bytes, void *hip_stream) {
+    if (int rc = check_candidates_args(max_query_len, min_count, cap, C)) return rc;
+    TVZ_REQUIRE(shards != nullptr && n_shards >= 1, "no shards");
+    if (int rc = check_candidates_merge(n_shards, C)) return rc;
+    for (int32_t r = 0; r < n_shards; ++r)
+        TVZ_REQUIRE(shards[r] != nullptr && shards[r]->device == shards[0]->device,
+                    "shard %d is NULL or on another device than shard 0", r);
+    if (int rc = check_batch_args(shards[0], align_batch(d_queries, d_q_offsets, Q, max_query_len, d_exclude_ids), cap)) return rc;
+    if (Q == 0) return TVZ_OK;
+    TVZ_REQUIRE(d_blocks && d_out && aligned8(d_blocks) && aligned8(d_out), "d_blocks or d_out is NULL or not 8-byte aligned");
+    const size_t block = tvz_gap::block_bytes(Q, C);
+    {
+        const uintptr_t g0 = reinterpret_cast<uintptr_t>(d_blocks), o0 = reinterpret_cast<uintptr_t>(d_out);
+        TVZ_REQUIRE(o0 + block <= g0 || g0 + (size_t)n_shards * block <= o0, "alignment candidates merge: d_out lies inside the blocks");
+    }
+    // every handle's refusals first - the arguments' are the same for all, the handle's own (no gap codes) are not -
+    // and the widths compared: nothing is enqueued before all of them agree
+    double eps0 = 0.0;
+    for (int32_t r = 0; r < n_shards; ++r) {
+        double eps = 0.0;
+        if (int rc = tvz_align_candidates_impl(shards[r], d_queries, d_q_offsets, Q, max_query_len, min_count, d_exclude_ids, cap, C,
+                                               d_blocks + (size_t)r * (block / sizeof(int32_t)), d_workspace, workspace_bytes,
+                                               hip_stream, {}, &eps, /* enqueue */ false))
+            return rc;
+        if (r == 0) eps0 = eps;
+        if (eps != eps0)
+            return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment candidates: shard %d keeps gap codes of gap_eps=%.17g, shard 0 of %.17g",
+                             (int)r, eps, eps0);
+    }
+    for (int32_t r = 0; r < n_shards; ++r)
+        if (int rc = tvz_align_candidates_impl(shards[r], d_queries, d_q_offsets, Q, max_query_len, min_count, d_exclude_ids, cap, C,
+                                               d_blocks + (size_t)r * (block / sizeof(int32_t)), d_workspace, workspace_bytes,
+                                               hip_stream))
+            return rc;
+    DeviceGuard dg(shards[0]->device);
+    return tvz_align_candidates_merge_local(d_blocks, n_shards, Q, C, d_out, hip_stream);
+}
+
+TVZ_EXPORT int tvz_align_candidates_merge(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t C, int32_t *d_out,
+                                          void *hip_stream) {
+    TVZ_GUARDED(tvz_align_candidates_merge_local(d_gathered, n_lists, Q, C, d_out, hip_stream));
+}
+
+TVZ_EXPORT int tvz_align_candidates_shards(tvz_corpus *const *shards, int32_t n_shards, const double *d_queries,
+                                           const int64_t *d_q_offsets, int32_t Q, int32_t max_query_len, int32_t min_count,
+                                           const int32_t *d_exclude_ids, int32_t cap, int32_t C, int32_t *d_blocks,
+                                           int32_t *d_out, void *d_workspace, size_t workspace_bytes, void *hip_stream) {
+    TVZ_GUARDED(align_candidates_shards_impl(shards, n_shards, d_queries, d_q_offsets, Q, max_query_len, min_count,
+                                             d_exclude_ids, cap, C, d_blocks, d_out, d_workspace, workspace_bytes, hip_stream));
+}
+
+TVZ_EXPORT size_t tvz_align_candidates_sharded_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys,
+                                                               int32_t cap, int32_t C, int32_t n_ranks) {
+    return tvz_align_candidates_sharded_sizing(Q, max_query_len, total_query_keys, cap, C, n_ranks);
 }
 
 TVZ_EXPORT int tvz_corpus_gap_index(tvz_corpus *c, double gap_eps) {

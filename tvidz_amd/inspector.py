@@ -215,7 +215,8 @@ class Inspector:
             if not (_corpus_can(corpus, "align_candidates", "supports_align_candidates") and hasattr(corpus, "set_gap_index")
                     and _corpus_can(corpus, "align_parts", "supports_align_parts")):
                 raise RuntimeError(f"{what}: the store's corpus ({type(corpus).__name__}) has no align_candidates; "
-                                   "use a DeviceCorpus")
+                                   "use a DeviceCorpus, a service.ShardedCorpus or a service.RankCorpus over a matcher "
+                                   "with `candidates`")
             corpus.set_gap_index(self.near_gap_eps)
         # opt-in, never the default: duplicates by the TOLERANT count (include/tvz.h tvz_find_duplicates_tol)
         # instead of the reference's exact float64 equality; the verdict, the truncation at kth and the stored

@@ -344,6 +344,48 @@ class ShardedCorpus:
             out = answers[0] if len(answers) == 1 else tc.align_parts_merge_device(torch.stack(answers))
             return out.cpu().numpy()
 
+    def set_gap_index(self, gap_eps: float) -> None:
+        """DeviceCorpus.set_gap_index on every shard: every shard keeps the gap codes of its own rows, at one width
+        (0 drops them everywhere).  `align_candidates` needs them."""
+        for s in self.shards:
+            s.set_gap_index(gap_eps)
+
+    def gap_index_stats(self) -> dict:
+        """DeviceCorpus.gap_index_stats summed over the shards, with the width in force (0.0: off; the shards agree,
+        set_gap_index is the only way to set it)."""
+        st = [s.gap_index_stats() for s in self.shards]
+        return {"gap_eps": st[0]["gap_eps"], **{n: sum(x[n] for x in st) for n in st[0] if n != "gap_eps"}}
+
+    @property
+    def supports_align_candidates(self) -> bool:
+        return True
+
+    def align_candidates(self, queries, *, c: int, min_count: int = 2, cap: int = 4096, exclude_ids=None,
+                         max_query_len=None):
+        """DeviceCorpus.align_candidates over every shard (set_gap_index first), with its return shapes: ONE library call
+        (tvz_align_candidates_shards) asks every shard with the calling thread's one workspace and merges the blocks on
+        the device - the c best of all shards' rows, the totals summed (include/tvz_gap_shards.h) - and ONE copy brings
+        the block back.  Exactly one DeviceCorpus's answer over the same rows wherever no shard's candidates exceeded
+        `cap` (the total is negative where one did).  More than 16 shards: one such call per group of 16, the groups'
+        answers merged again by tvz_align_candidates_merge; still one copy back, same answer."""
+        h = self.align_candidates_block(queries, c=c, min_count=min_count, cap=cap, exclude_ids=exclude_ids,
+                                        max_query_len=max_query_len).cpu().numpy()
+        return np.ascontiguousarray(h[:, :c]), np.ascontiguousarray(h[:, c, 1])
+
+    def align_candidates_block(self, queries, *, c: int, min_count: int = 2, cap: int = 4096, exclude_ids=None,
+                               max_query_len=None) -> torch.Tensor:
+        """align_candidates, left on the device: the merged block int32 [Q, c + 1, 2]; `block[:, :c, 0]` is the strided
+        view of ids that the parts calls take."""
+        dev = self.dev
+        d_q, d_off, Q, max_query_len, d_ex = tc.align_inputs(queries, exclude_ids, max_query_len, dev)
+        ws = tc.thread_workspace(self._near_tls, tc.align_candidates_workspace_bytes(Q, max_query_len, d_q.numel(), cap, c),
+                                 dev)
+        with torch.cuda.device(dev):
+            groups = [self.shards[i:i + 16] for i in range(0, self.R, 16)]      # the merge takes up to 16 lists
+            answers = [tc.align_candidates_shards(g, d_q, d_off, max_query_len, c=c, min_count=min_count, cap=cap,
+                                                  d_exclude_ids=d_ex, workspace=ws)[1] for g in groups]
+            return answers[0] if len(answers) == 1 else tc.align_candidates_merge_device(torch.stack(answers))
+
     def _near_shards(self, form, queries, k, exclude_ids, max_query_len, **ask):
         """What the four methods above share, for their `form` (corpus.ALIGN_FORMS) and what they `ask`: the inputs, the
         calling thread's workspace, one tvz_<stem>_shards per group of 16 shards, the groups' tvz_<stem>_merge, the one
@@ -422,6 +464,8 @@ class ShardedCorpus:
 
 
 ASK_TOPK, ASK_EXACT, ASK_NEAR, ASK_NEAR_WIDE, ASK_NEAR_RATES, ASK_NEAR_SPAN, ASK_PARTS = 0, 1, 2, 3, 4, 5, 6
+ASK_CANDIDATES = 7                                         # the candidate ids from the gap codes (align_candidates)
+CAND_PAR = 5                                               # its parameters, in a near ask's slots: (gap_eps, 0, C, min_count, cap)
 # An ask's header: (len, exclude, min_match, kind, tolerance | a near ask's eps, max_offset, k, min_votes, min_score, flags |
 # its rate list: the count and up to 8 rates | a parts ask's max_parts and its k <= 64 ids).  All float64: small integers
 # and int32 ids are exact in it, and tolerance, eps, max_offset and the rates ARE float64.  Every rank runs one build.
@@ -544,6 +588,10 @@ class RankCorpus:
                  search, as a second ask): eps, max_offset, k, min_votes, the rate list, max_parts and the ask's k ids
                  travel in the header; asks that agree in all but the ids share one `matcher.parts(...)`, and a tick
                  answers its parts asks behind its searches.
+      ASK_CANDIDATES  the candidate ids from the gap codes (`align_candidates`, what Inspector(near_candidates=C) calls
+                 in front of its parts ask, as an ask of its own): the gap_eps in force, C (where a search keeps k),
+                 min_count and cap travel in the near slots of the header, which does not grow; asks that agree in all of
+                 them share one `matcher.candidates(...)`, and a tick answers its candidates asks behind its parts asks.
 
     `shard`: this rank's DeviceCorpus (or a stand-in with upload/upsert/clear/find_duplicates);
     `matcher.match_topk(d_q, d_off, max_len, min_match, d_excl) -> (merged [Q,k,3], totals [Q])`;
@@ -717,6 +765,43 @@ class RankCorpus:
     def supports_align_parts(self) -> bool:
         return bool(getattr(self.matcher, "supports_align_parts", False))
 
+    @property
+    def supports_align_candidates(self) -> bool:
+        """Can `align_candidates` answer?  The matcher has `candidates` and this rank's shard can keep gap codes."""
+        return bool(getattr(self.matcher, "supports_align_candidates", False)) and hasattr(self.shard, "set_gap_index")
+
+    def set_gap_index(self, gap_eps: float) -> None:
+        """DeviceCorpus.set_gap_index on this rank's shard.  Every rank sets the same width (the service's
+        `--near-gap-eps`): a rank cannot check the others'."""
+        self.shard.set_gap_index(gap_eps)
+
+    def gap_index_stats(self) -> dict:
+        """This rank's shard's (DeviceCorpus.gap_index_stats)."""
+        return self.shard.gap_index_stats()
+
+    def align_candidates(self, queries, *, c: int, min_count: int = 2, cap: int = 4096, exclude_ids=None,
+                         max_query_len=None):
+        """DeviceCorpus.align_candidates over the shards of all ranks, with its return shapes: (rows int32 [Q, c, 2],
+        totals int32 [Q]).  Every query is one ASK_CANDIDATES of the next tick; its parameters travel in a near ask's
+        slots: the gap_eps in force here, C where a search keeps k, min_count and cap beside it.  Everything a rank's
+        library call would refuse is refused HERE, in the caller (ValueError: C, cap < C, min_count; RuntimeError: a
+        shard without gap codes, a matcher without `candidates`).  A query of more than max_query_len (at most 4,095)
+        values never travels: all rows padding, total ALIGN_CANDIDATES_REFUSED, as the library answers it."""
+        for name, v, lo, hi in (("c", c, 1, tc.ALIGN_CANDIDATES_MAX_C), ("cap", cap, 1, (1 << 31) - 1),
+                                ("min_count", min_count, 1, (1 << 31) - 1)):
+            if int(v) != v or not lo <= int(v) <= hi:
+                raise ValueError(f"{name} must be an integer in {lo}..{hi}, got {v!r}")
+        if int(cap) < int(c):
+            raise ValueError(f"cap={cap!r} is below c={c!r}")
+        if not getattr(self.matcher, "supports_align_candidates", False):
+            raise RuntimeError(f"this rank corpus has no align_candidates: its matcher {type(self.matcher).__name__} has no "
+                               "candidates call")
+        gap_eps = float(self.shard.gap_index_stats()["gap_eps"]) if hasattr(self.shard, "gap_index_stats") else 0.0
+        if not gap_eps > 0.0:
+            raise RuntimeError("this rank corpus keeps no gap codes: set_gap_index first")
+        near = (gap_eps, 0.0, int(c), int(min_count), int(cap))
+        return self._near_asks(ASK_CANDIDATES, near, queries, exclude_ids, max_query_len)
+
     def _near(self, form, queries, exclude_ids, max_query_len, eps, max_offset, k, min_votes, min_score, contain=False,
               local=False, rates=None, two_bins=False):
         """What the four searches above share, for their `form`.  Everything a rank's library call would refuse is refused
@@ -741,7 +826,8 @@ class RankCorpus:
         if len(excl) != len(queries):
             raise ValueError(f"exclude_ids must hold {len(queries)} video ids")
         k = near[2]
-        rows = np.zeros((len(queries), k, TICK_FORMS[kind].cols), dtype=np.int32)
+        cols = 2 if kind == ASK_CANDIDATES else TICK_FORMS[kind].cols              # (a candidates ask: rows of (id, count), k = C)
+        rows = np.zeros((len(queries), k, cols), dtype=np.int32)
         rows[:, :, 0] = -1
         totals = np.full(len(queries), -(1 << 31), dtype=np.int64)                 # ALIGN_REFUSED unless answered
         sent = [i for i, q in enumerate(queries) if q.size <= limit]
@@ -831,7 +917,8 @@ class RankCorpus:
     def _exchange_and_answer(self, take, allmeta):
         """One busy tick.  The order of the collectives and of the matcher calls is the same on every rank: the asks'
         exchange, one match_topk per (min_match, tolerance) in sorted order, one align per near kind and set of its
-        parameters in sorted order, one parts call per set of its parameters, then the exact asks' two gathers."""
+        parameters in sorted order, one parts call per set of its parameters, one candidates call per set of its parameters,
+        then the exact asks' two gathers."""
         asks = self._gather_asks(take, allmeta)
         self._answer_topk(asks, take)
         self._answer_near(asks, take)
@@ -898,7 +985,8 @@ class RankCorpus:
     def _answer_near(self, asks: _Asks, take) -> None:
         """Near asks: per kind in ascending order, one batched `matcher.align` of the kind's form per (eps, max_offset,
         k, min_votes, min_score, flags, the rate list) in sorted order, then one `matcher.parts` per (eps, max_offset, k,
-        min_votes, the rate list, max_parts) in sorted order: every rank reads the same kinds and parameters off the
+        min_votes, the rate list, max_parts) in sorted order, then one `matcher.candidates` per (gap_eps, C, min_count,
+        cap) in sorted order: every rank reads the same kinds and parameters off the
         gathered headers, so every rank makes the same calls in the same order."""
         for kind, form in sorted(TICK_FORMS.items()):
             of_kind = asks.kind == kind
@@ -928,6 +1016,19 @@ class RankCorpus:
                                lambda d_q, d_off, max_len, d_ex: self.matcher.parts(
                                    d_q, d_off, max_len, torch.from_numpy(ids).to(d_q.device), **kw),
                                to_host=lambda out: list(out.cpu().numpy()))
+        of_kind = asks.kind == ASK_CANDIDATES
+        pars = asks.near[:, :CAND_PAR]
+        for par in sorted(set(map(tuple, pars[of_kind].tolist()))):
+            c = int(par[2])
+            kw = dict(c=c, min_count=int(par[3]), cap=int(par[4]))
+
+            def to_host(out, c=c):
+                block = (out.cpu() if torch.is_tensor(out) else torch.as_tensor(out)).numpy()      # [n, c + 1, 2]
+                return [(block[j, :c].copy(), int(block[j, c, 1])) for j in range(block.shape[0])]
+            self._answer_batch(asks, take, np.flatnonzero(of_kind & (pars == np.asarray(par)).all(axis=1)),
+                               lambda d_q, d_off, max_len, d_ex: self.matcher.candidates(d_q, d_off, max_len,
+                                                                                         d_exclude_ids=d_ex, **kw),
+                               to_host=to_host)
 
     def _answer_exact(self, asks: _Asks, take) -> None:
         """Exact asks: every rank asks its own shard, counts and padded hit lists are all-gathered."""
@@ -1056,6 +1157,9 @@ def near_kwargs(a) -> dict:
         kw["near_parts"] = int(a.near_parts)
     if getattr(a, "near_two_bins", False):
         kw["near_two_bins"] = True
+    if int(getattr(a, "near_candidates", 0) or 0):
+        kw["near_candidates"] = int(a.near_candidates)
+        kw["near_gap_eps"] = float(getattr(a, "near_gap_eps", 1.0 / 30))
     return kw
 
 
@@ -1071,9 +1175,10 @@ def parse_near_rates(rates):
 
 
 def check_near_switches(near_top_k, near_any_offset=False, near_score="jaccard", near_min_votes=1, near_rates=None,
-                        near_spans=False, near_parts=0, near_two_bins=False) -> list:
+                        near_spans=False, near_parts=0, near_two_bins=False, near_candidates=0,
+                        near_gap_eps=1.0 / 30) -> list:
     """`--near-any-offset`, `--near-score`, `--near-min-votes`, `--near-rates`, `--near-spans`, `--near-parts`,
-    `--near-two-bins`: Inspector's rules for them, before any rank starts -> the switches as a rank process takes them
+    `--near-two-bins`, `--near-candidates` (with `--near-gap-eps`): Inspector's rules for them, before any rank starts -> the switches as a rank process takes them
     (none where all are at their defaults; the later ones behind the earlier three)."""
     if near_score not in ("jaccard", "containment", "local"):
         raise ValueError(f"near_score must be 'jaccard', 'containment' or 'local', got {near_score!r}")
@@ -1085,13 +1190,20 @@ def check_near_switches(near_top_k, near_any_offset=False, near_score="jaccard",
     near_parts = near_parts or 0
     if int(near_parts) != near_parts or (near_parts and not 2 <= int(near_parts) <= tc.ALIGN_MAX_PARTS):
         raise ValueError(f"near_parts must be 0 (off) or 2..{tc.ALIGN_MAX_PARTS}, got {near_parts!r}")
+    near_candidates = near_candidates or 0
+    if int(near_candidates) != near_candidates or int(near_candidates) < 0:
+        raise ValueError(f"near_candidates must be 0 (off) or near_top_k..{tc.ALIGN_CANDIDATES_MAX_C}, got {near_candidates!r}")
+    if near_candidates and not (0.0 < float(near_gap_eps) <= sys.float_info.max):
+        raise ValueError(f"near_gap_eps must be finite and > 0, got {near_gap_eps!r}")
     given = (["--near-any-offset"] if near_any_offset else []) + \
         (["--near-score", near_score] if near_score != "jaccard" else []) + \
         (["--near-min-votes", str(int(near_min_votes))] if int(near_min_votes) != 1 else []) + \
         (["--near-rates", ",".join(repr(r) for r in rates)] if rates is not None else []) + \
         (["--near-spans"] if near_spans else []) + \
         (["--near-parts", str(int(near_parts))] if near_parts else []) + \
-        (["--near-two-bins"] if near_two_bins else [])
+        (["--near-two-bins"] if near_two_bins else []) + \
+        (["--near-candidates", str(int(near_candidates)), "--near-gap-eps", repr(float(near_gap_eps))]
+         if near_candidates else [])
     if given and not near_top_k:
         raise ValueError(f"{given[0]} needs --near-top-k")
     if near_score == "containment" and not near_any_offset:
@@ -1107,6 +1219,17 @@ def check_near_switches(near_top_k, near_any_offset=False, near_score="jaccard",
     if near_parts and near_two_bins:
         raise ValueError(f"--near-two-bins with --near-parts {int(near_parts)}: align_parts counts single bins (it has no "
                          "flags); use one of them")
+    if near_candidates:
+        what = f"--near-candidates {int(near_candidates)}"
+        if not near_any_offset:
+            raise ValueError(f"{what} needs --near-any-offset (the candidates stand in for the sweep at any shift)")
+        if not int(near_top_k) <= int(near_candidates) <= tc.ALIGN_CANDIDATES_MAX_C:
+            raise ValueError(f"{what}: must be --near-top-k..{tc.ALIGN_CANDIDATES_MAX_C} "
+                             f"({int(near_top_k)}..{tc.ALIGN_CANDIDATES_MAX_C})")
+        if rates is not None:
+            raise ValueError(f"{what} with --near-rates: the gap codes are made at rate 1; use one of them")
+        if near_two_bins:
+            raise ValueError(f"{what} with --near-two-bins: align_parts counts single bins; use one of them")
     return given
 
 
@@ -1273,7 +1396,8 @@ class RankService:
                  match_tolerance: float = 0.0, match_tol_index: float = 0.0, near_top_k: int = 0,
                  near_eps: float = 1.0 / 30, near_max_offset: float = 30.0, near_jaccard: float = 0.8,
                  near_any_offset: bool = False, near_score: str = "jaccard", near_min_votes: int = 1, near_rates=None,
-                 near_spans: bool = False, near_parts: int = 0, near_two_bins: bool = False):
+                 near_spans: bool = False, near_parts: int = 0, near_two_bins: bool = False, near_candidates: int = 0,
+                 near_gap_eps: float = 1.0 / 30):
         import socket
         import subprocess
         from . import db
@@ -1290,7 +1414,7 @@ class RankService:
             near = ["--near-top-k", str(int(near_top_k)), "--near-eps", repr(float(near_eps)),
                     "--near-max-offset", repr(float(near_max_offset)), "--near-jaccard", repr(float(near_jaccard))]
         near += check_near_switches(near_top_k, near_any_offset, near_score, near_min_votes, near_rates, near_spans,
-                                    near_parts, near_two_bins)
+                                    near_parts, near_two_bins, near_candidates, near_gap_eps)
         db.create_schema(db_url)                                # once, before N processes open it side by side
         with socket.socket() as s:                              # a free rendezvous port
             s.bind(("127.0.0.1", 0))
@@ -1403,6 +1527,13 @@ def main(argv=None) -> int:  # pragma: no cover - exercised through subprocesses
                     help="votes counted over two adjacent offset bins, for the copy whose shift lies near a bin's edge (a "
                          "remux, a re-timing to another frame grid): Inspector(near_two_bins=True); TVZ_ALIGN_TWO_BINS.  "
                          "Needs --near-top-k; not with --near-parts")
+    ap.add_argument("--near-candidates", type=int, default=0, metavar="C",
+                    help="near-top-k..64: the search at any shift without the sweep - every rank keeps the gap codes of its "
+                         "shard (--near-gap-eps) and names the C stored videos that share the most with the upload "
+                         "(Inspector(near_candidates=C); tvz_align_candidates_sharded), which one parts call then aligns.  "
+                         "Needs --near-any-offset; not with --near-rates or --near-two-bins.  0 = off")
+    ap.add_argument("--near-gap-eps", type=float, default=1.0 / 30, metavar="SECONDS",
+                    help="the width the gaps between cuts are quantised to for --near-candidates, the same on every rank")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--rank", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--master-port", type=int, default=29500, help=argparse.SUPPRESS)
@@ -1418,7 +1549,7 @@ def main(argv=None) -> int:  # pragma: no cover - exercised through subprocesses
                       near_max_offset=a.near_max_offset, near_jaccard=a.near_jaccard,
                       near_any_offset=a.near_any_offset, near_score=a.near_score, near_min_votes=a.near_min_votes,
                       near_rates=a.near_rates, near_spans=a.near_spans, near_parts=a.near_parts,
-                      near_two_bins=a.near_two_bins)
+                      near_two_bins=a.near_two_bins, near_candidates=a.near_candidates, near_gap_eps=a.near_gap_eps)
 
     def monitor():
         while True:

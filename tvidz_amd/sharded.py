@@ -80,6 +80,14 @@ class HipBackend:
     def parts_merge(self, gathered):
         return tc.align_parts_merge_device(gathered)
 
+    def local_candidates(self, d_q, d_off, max_len, **ask):
+        """this rank's candidate ids (tvz_align_candidates; `ask`: c, min_count, cap, d_exclude_ids): the block int32
+        [Q, c + 1, 2] on the device"""
+        return self.corpus.align_candidates_block(d_q, d_off, max_len, **ask)
+
+    def candidates_merge(self, gathered):
+        return tc.align_candidates_merge_device(gathered)
+
 
 def _two_bins(two_bins: bool) -> dict:
     return {"two_bins": True} if two_bins else {}
@@ -242,6 +250,34 @@ class ShardedMatcher(_AlignForwards):
         gathered, _ = self._all_gather_blocks(local, async_op=False)
         return self.backend.parts_merge(gathered)
 
+    @property
+    def supports_align_candidates(self) -> bool:
+        """Does `candidates` answer?  Only over a backend with the local call and the merge."""
+        return hasattr(self.backend, "local_candidates") and hasattr(self.backend, "candidates_merge")
+
+    def candidates(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, c: int,
+                   min_count: int = 2, cap: int = 4096, d_exclude_ids: Optional[torch.Tensor] = None):
+        """The candidate ids from the gap codes over the sharded table (tvz_align_candidates; every rank's shard keeps
+        codes of the same gap_eps): this rank's block [Q, c + 1, 2] -> ONE all-gather -> the merge that keeps the c
+        best of all ranks' rows and sums their totals (include/tvz_gap_shards.h), identical on every rank: -> the
+        block int32 [Q, c + 1, 2].  More than 16 ranks are merged in groups of 16, the groups' answers again."""
+        if not self.supports_align_candidates:
+            raise RuntimeError(f"{type(self.backend).__name__} has no align_candidates")
+        local = self.backend.local_candidates(d_queries, d_q_offsets, max_query_len, c=int(c), min_count=int(min_count),
+                                              cap=int(cap), d_exclude_ids=d_exclude_ids)
+        gathered, _ = self._all_gather_blocks(local, async_op=False)
+        return merge_candidate_blocks(self.backend.candidates_merge, gathered)
+
+
+def merge_candidate_blocks(merge, gathered):
+    """`merge` (up to corpus.ALIGN_CANDIDATES_MERGE_MAX_LISTS blocks -> one) over any number of them [R, Q, c + 1, 2]:
+    groups of up to 16, then the groups' answers, until one is left - the rule is associative."""
+    n = tc.ALIGN_CANDIDATES_MERGE_MAX_LISTS
+    while gathered.shape[0] > n:
+        lib = torch if torch.is_tensor(gathered) else np
+        gathered = lib.stack([merge(gathered[i:i + n]) for i in range(0, gathered.shape[0], n)])
+    return merge(gathered)
+
 
 def make_comm(device: int, group=None):
     """Create the libtvz RCCL communicator of this rank.  torch.distributed (any backend) is used
@@ -258,11 +294,11 @@ def make_comm(device: int, group=None):
 class _Slot:
     """What one of RcclShardedMatcher's side streams owns: its event, submit's workspace and (merged, totals), and
     align's own pair (its rows are the form's width and `k` is the call's own)."""
-    __slots__ = ("stream", "event", "ws", "out", "near_ws", "near_out", "parts_out")
+    __slots__ = ("stream", "event", "ws", "out", "near_ws", "near_out", "parts_out", "cand_out")
 
     def __init__(self, stream):
         self.stream, self.event = stream, torch.cuda.Event()
-        self.ws = self.out = self.near_ws = self.near_out = self.parts_out = None
+        self.ws = self.out = self.near_ws = self.near_out = self.parts_out = self.cand_out = None
 
 
 class RcclShardedMatcher(_AlignForwards):
@@ -443,6 +479,31 @@ class RcclShardedMatcher(_AlignForwards):
         st.wait_stream(torch.cuda.current_stream(self.dev))       # the queries and ids are complete; the slot's last answer is read
         out = self.comm.align_parts_sharded(self.corpus, d_queries, d_q_offsets, max_query_len, d_video_ids,
                                             workspace=slot.near_ws, stream=st, out=slot.parts_out, **ask)
+        slot.event.record(st)
+        torch.cuda.current_stream(self.dev).wait_event(slot.event)
+        return out
+
+    supports_align_candidates = "tvz_align_candidates_sharded" in _lib.GAP_SHARD_SIGNATURES
+
+    def candidates(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, c: int,
+                   min_count: int = 2, cap: int = 4096, d_exclude_ids: Optional[torch.Tensor] = None):
+        """ShardedMatcher.candidates behind ONE library call (tvz_align_candidates_sharded): the local
+        tvz_align_candidates -> ncclAllGather of the [Q, c + 1, 2] blocks -> the merge, on the next of the matcher's side
+        streams with the slot's near workspace; the current stream waits for it.  -> int32 [Q, c + 1, 2], this
+        matcher's tensor, overwritten `n_streams` calls later."""
+        slot = self._next_slot()
+        st = slot.stream
+        _, Q = self.corpus._check_queries(d_queries, d_q_offsets)
+        c = int(c)
+        need = tc.align_candidates_sharded_workspace_bytes(Q, max_query_len, d_queries.numel(), cap, c, self.world)
+        if slot.near_ws is None or slot.near_ws.numel() < need:
+            slot.near_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.dev)
+        if slot.cand_out is None or slot.cand_out.shape != (Q, c + 1, 2):
+            slot.cand_out = torch.empty((Q, max(c, 0) + 1, 2), dtype=torch.int32, device=self.dev)
+        st.wait_stream(torch.cuda.current_stream(self.dev))       # the queries are complete; the slot's last answer is read
+        out = self.comm.align_candidates_sharded(self.corpus, d_queries, d_q_offsets, max_query_len, c=c, min_count=min_count,
+                                                 cap=cap, d_exclude_ids=d_exclude_ids, workspace=slot.near_ws, stream=st,
+                                                 out=slot.cand_out)
         slot.event.record(st)
         torch.cuda.current_stream(self.dev).wait_event(slot.event)
         return out
