@@ -278,6 +278,15 @@ def align_candidates_workspace_bytes(Q: int, max_query_len: int, total_query_key
                                                                 int(cap), int(c)))
 
 
+def align_candidates_rates_workspace_bytes(Q: int, max_query_len: int, total_query_keys: int = 0, n_rates: int = 1,
+                                           cap: int = 4096, c: int = 16) -> int:
+    """tvz_align_candidates_rates_workspace_bytes: the lookup's hit lists for Q x n_rates probe lists (cap x 12 bytes
+    each) and its own workspace, then per query value the sorted copy and eight probe slots per rate (12 + 64 n_rates
+    bytes).  0 for arguments the call refuses."""
+    return int(_lib.load().tvz_align_candidates_rates_workspace_bytes(int(Q), int(max_query_len), int(total_query_keys),
+                                                                      int(n_rates), int(cap), int(c)))
+
+
 ALIGN_CANDIDATES_MERGE_MAX_LISTS = 16                               # include/tvz_gap_shards.h TVZ_GAP_MERGE_MAX_LISTS
 
 
@@ -575,6 +584,44 @@ class DeviceCorpus:
         _lib.check(self.lib.tvz_align_candidates(self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len),
                                                  int(min_count), excl, int(cap), int(c), out.data_ptr(), ws.data_ptr(),
                                                  ws.numel(), s.cuda_stream))
+        return out
+
+    supports_align_candidate_rates = "tvz_align_candidates_rates" in _lib.GAP_RATE_SIGNATURES
+
+    def align_candidates_rates(self, queries, rates: Sequence[float], *, c: int, min_count: int = 2, cap: int = 4096,
+                               exclude_ids=None, max_query_len: Optional[int] = None):
+        """tvz_align_candidates_rates, host in / host out: align_candidates for copies played at another speed - the
+        upload is probed once per rate of `rates` (1..ALIGN_MAX_RATES finite rates > 0, by preference: stored ~= rate x
+        upload + shift) and a stored video is named ONCE, at its best rate -> (ids int32 [Q, c], counts int32 [Q, c],
+        rate_indexes int32 [Q, c], totals int32 [Q]): the best count per id descending, then id ascending, padded with
+        (-1, 0, 0); totals: the (row, rate) pairs with count >= min_count - an upper bound on the ids, not their count
+        -, negated when a rate's list exceeded `cap`, ALIGN_CANDIDATES_REFUSED for a query of more than 514 values."""
+        dev = torch.device("cuda", self.device)
+        d_q, d_off, Q, max_query_len, d_ex = align_inputs(queries, exclude_ids, max_query_len, dev)
+        need = align_candidates_rates_workspace_bytes(Q, max_query_len, d_q.numel(), len(rates), cap, c)
+        ws = thread_workspace(self._tls, need, dev)
+        h = self.align_candidates_rates_block(d_q, d_off, max_query_len, rates, c=c, min_count=min_count, cap=cap,
+                                              d_exclude_ids=d_ex, workspace=ws).cpu().numpy()
+        return (np.ascontiguousarray(h[:, :c, 0]), np.ascontiguousarray(h[:, :c, 1]), np.ascontiguousarray(h[:, :c, 2]),
+                np.ascontiguousarray(h[:, c, 1]))
+
+    def align_candidates_rates_block(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int,
+                                     rates: Sequence[float], *, c: int, min_count: int = 2, cap: int = 4096,
+                                     d_exclude_ids: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                                     stream: Optional[torch.cuda.Stream] = None,
+                                     workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """tvz_align_candidates_rates, device in / device out: enqueue Q queries -> the block int32 [Q, c + 1, 3] of
+        (video_id, best, rate_index) rows.  `block[:, :c, 0]` is the strided view of ids that align_parts_block takes,
+        with the same `rates`."""
+        Q = d_q_offsets.numel() - 1
+        h_rates, n_rates = _rates(rates)
+        dev, s, ws, excl = self._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace,
+                                         align_candidates_rates_workspace_bytes(Q, max_query_len, d_queries.numel(), n_rates,
+                                                                                cap, c))
+        out = _out(out, (Q, max(int(c), 0) + 1, 3), dev)
+        _lib.check(self.lib.tvz_align_candidates_rates(self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q,
+                                                       int(max_query_len), h_rates, n_rates, int(min_count), excl, int(cap),
+                                                       int(c), out.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
         return out
 
     def stats(self) -> Tuple[int, int, int]:

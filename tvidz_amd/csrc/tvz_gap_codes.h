@@ -1,6 +1,6 @@
 // tvz_gap_codes.h — the gap codes of one stored row, made on the host (include/tvz_gap.h: STORED SIDE), and the
-// workspace layout of tvz_align_candidates.  Plain C++ with no HIP in it: tvz_match.hip includes it for the handle, a
-// stand-alone host program can include it on its own.
+// workspace layouts of tvz_align_candidates, its form with rates and its sharded form.  Plain C++ with no HIP in it:
+// tvz_match.hip includes it for the handle, a stand-alone host program can include it on its own.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -108,6 +108,41 @@ inline size_t ws_bytes(int32_t Q, int32_t cap, size_t match_bytes, int64_t keys)
 inline int64_t ws_room(int32_t Q, int32_t cap, size_t match_bytes, size_t bytes) {
     const size_t fixed = ws_bytes(Q, cap, match_bytes, 0);
     return bytes < fixed ? -1 : (int64_t)((bytes - fixed) / kPerKey);
+}
+
+// ---- the workspace of tvz_align_candidates_rates (include/tvz_gap_rates.h) ----
+// The plain call's regions for the Q * n_rates pseudo-queries (query q at rate i is pseudo-query q * n_rates + i) that
+// the lookup sees: their hit lists, counts, probe offsets and exclusion ids, and the lookup's own workspace for that
+// many probe lists; the sorted values, their positions and counts are the Q queries' own, and a value has 8 probe slots
+// PER RATE.  The same rules otherwise: 256-byte multiples behind a base aligned up to 256, `room` query values.
+struct RateWsRegions {               // byte offsets from the aligned base
+    size_t hits, hits_n, p_off, excl, match, qm, sv, sp, probes, end;
+};
+constexpr size_t rate_per_key(int32_t n_rates) {
+    return sizeof(double) + sizeof(int32_t) + (size_t)n_rates * kVariants * sizeof(double);
+}
+inline RateWsRegions ws_rates_regions(int32_t Q, int32_t n_rates, int32_t cap, size_t match_bytes, int64_t room) {
+    RateWsRegions r;
+    const size_t pq = (size_t)Q * (size_t)n_rates;
+    size_t p = 0;
+    r.hits = p;    p += al256(pq * (size_t)cap * 3 * sizeof(int32_t));
+    r.hits_n = p;  p += al256(pq * sizeof(int32_t));
+    r.p_off = p;   p += al256((pq + 1) * sizeof(int64_t));
+    r.excl = p;    p += al256(pq * sizeof(int32_t));
+    r.match = p;   p += al256(match_bytes);
+    r.qm = p;      p += al256((size_t)Q * sizeof(int32_t));
+    r.sv = p;      p += al256((size_t)room * sizeof(double));
+    r.sp = p;      p += al256((size_t)room * sizeof(int32_t));
+    r.probes = p;  p += al256((size_t)room * (size_t)n_rates * kVariants * sizeof(double));
+    r.end = p;
+    return r;
+}
+inline size_t ws_rates_bytes(int32_t Q, int32_t n_rates, int32_t cap, size_t match_bytes, int64_t keys) {
+    return ws_rates_regions(Q, n_rates, cap, match_bytes, 0).end + kWsSlack + (size_t)keys * rate_per_key(n_rates);
+}
+inline int64_t ws_rates_room(int32_t Q, int32_t n_rates, int32_t cap, size_t match_bytes, size_t bytes) {
+    const size_t fixed = ws_rates_bytes(Q, n_rates, cap, match_bytes, 0);
+    return bytes < fixed ? -1 : (int64_t)((bytes - fixed) / rate_per_key(n_rates));
 }
 
 // ---- the workspace of tvz_align_candidates_sharded ----

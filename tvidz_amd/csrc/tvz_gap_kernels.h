@@ -4,6 +4,7 @@
 //   ts_gapc_probe_kernel    the probes: a thread per (query, position) writes its 8 slots.
 //   ts_gapc_select_kernel   per query the C best of the lookup's hit list, the block and the total.
 //   ts_gapc_merge_kernel    per query the C best of up to 16 such blocks (tvz_align_candidates_merge).
+//   ts_gapr_*_kernel        the same three steps at a list of rates (tvz_align_candidates_rates): at the end of the file.
 //
 // Between the last two the internal match runs over the handle's code table (the queries are the probe lists).
 // The queries come sorted from ts_tol_sort_kernel (tvz_tol_kernels.h): sv[at .. at + m), at = q_offsets[q] -
@@ -203,6 +204,188 @@ __global__ __launch_bounds__(kGapMergeBlock) void ts_gapc_merge_kernel(const int
     }
     for (int i = n_rows + lane; i < C; i += 64) o[i] = make_int2(-1, 0);
     if (lane == 0) o[C] = make_int2(-1, topk_total(sum, over));
+}
+
+// ---- the candidates at a list of rates (tvz_align_candidates_rates, include/tvz_gap_rates.h) ------------------------
+// Query q at rate i is the PSEUDO-QUERY q * R + i of the lookup: its probes are the query side of the contract on
+// x' = x * rho_i (al_scaled of tvz_align_kernels.h: the alignment calls' one multiplication, never contracted).
+//   ts_gapr_offsets_kernel  the pseudo-queries' probe offsets and their queries' exclusion ids.
+//   ts_gapr_probe_kernel    the probes: a thread per (query, rate, position) writes its 8 slots.
+//   ts_gapr_fold_kernel     per query, over its R hit lists: per id the best (count, smallest rate index), the C best
+//                           ids, the block and the total.
+
+// p_off[p] = the slots of the pseudo-queries before p (pseudo-query p has its query's, p / R), p_off[Q R] = all of
+// them; excl_out[p] = exclude_ids[p / R] where the call has exclusions (the lookup reads one id per probe list).
+// grid = 1; Q R <= 65,535: 64 per thread.
+__global__ __launch_bounds__(kGapOffBlock) void ts_gapr_offsets_kernel(const int32_t *__restrict__ qm, int32_t Q, int32_t R,
+                                                                        const int32_t *__restrict__ exclude_ids,
+                                                                        int64_t *__restrict__ p_off,
+                                                                        int32_t *__restrict__ excl_out) {
+    __shared__ uint32_t s_w[kGapOffBlock / 64];
+    const int n = Q * R;
+    const int per = (n + kGapOffBlock - 1) / kGapOffBlock;
+    const int p0 = (int)threadIdx.x * per;
+    uint32_t mine = 0;
+    for (int p = p0; p < p0 + per && p < n; ++p) mine += (uint32_t)gapc_slots(qm[p / R]);
+    const uint32_t incl = wave_scan_incl(mine);
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 63) s_w[wave] = incl;
+    __syncthreads();
+    uint32_t before, all;
+    waves_sum<kGapOffBlock / 64>(s_w, wave, before, all);
+    uint32_t at = before + incl - mine;
+    for (int p = p0; p < p0 + per && p < n; ++p) {
+        p_off[p] = (int64_t)at;
+        at += (uint32_t)gapc_slots(qm[p / R]);
+        if (exclude_ids) excl_out[p] = exclude_ids[p / R];
+    }
+    if (threadIdx.x == 0) p_off[n] = (int64_t)all;
+}
+
+// ts_gapc_probe_kernel on the scaled values.  grid = (ceil(positions / kGapProbeBlock), Q, R); thread i of query q at
+// rate blockIdx.z writes probes[p_off[q R + z] + 8 i ..+ 8), the same slots in the same order with the same four
+// 16-byte stores.  The four values are scaled first, each by one multiplication; from there on the expressions are
+// the plain kernel's, so that at the rate 1.0 (x * 1.0 == x, bit for bit) the probes are the plain kernel's.
+__global__ __launch_bounds__(kGapProbeBlock) void ts_gapr_probe_kernel(const double *__restrict__ sv,
+                                                                        const int64_t *__restrict__ q_offsets,
+                                                                        const int32_t *__restrict__ qm, double gap_eps,
+                                                                        AlRates rates, const int64_t *__restrict__ p_off,
+                                                                        double *__restrict__ probes) {
+    const int q = blockIdx.y;
+    const int32_t m = qm[q];
+    if (gapc_slots(m) == 0) return;                                  // refused, or fewer than 4 values (block-uniform)
+    const int i = (int)blockIdx.x * kGapProbeBlock + (int)threadIdx.x;
+    if (i + 3 >= m) return;
+    const double rho = rates.r[blockIdx.z];                          // (a uniform index: scalar loads of the argument)
+    const double *s = sv + (q_offsets[q] - q_offsets[0]) + i;
+    const double s0 = al_scaled(s[0], rho), s1 = al_scaled(s[1], rho), s2 = al_scaled(s[2], rho), s3 = al_scaled(s[3], rho);
+    double a[3];
+    a[0] = floor((s1 - s0) / gap_eps);
+    a[1] = floor((s2 - s1) / gap_eps);
+    a[2] = floor((s3 - s2) / gap_eps);
+    double lo[3], hi[3];
+    const double place[3] = {1.0, tvz_gap::kBin1, tvz_gap::kBin2};
+    const double none = __longlong_as_double(0x7ff8000000000000LL);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const double b = a[j] + 1.0;
+        lo[j] = (a[j] >= 0.0 && a[j] <= tvz_gap::kMaxBin) ? a[j] * place[j] : none;
+        hi[j] = (b >= 0.0 && b <= tvz_gap::kMaxBin) ? b * place[j] : none;
+    }
+    const int64_t p = (int64_t)q * rates.n + blockIdx.z;
+    double2 *o = reinterpret_cast<double2 *>(probes + p_off[p] + (int64_t)tvz_gap::kVariants * i);
+#pragma unroll
+    for (int v = 0; v < tvz_gap::kVariants; v += 2) {
+        const double rest = ((v & 2) ? hi[1] : lo[1]) + ((v & 4) ? hi[2] : lo[2]);
+        o[v >> 1] = make_double2(lo[0] + rest, hi[0] + rest);
+    }
+}
+
+// The words of the fold.  A count is at most kGaprMaxCount (a query has at most 4,095 probe slots), a rate index at
+// most 7, a video id at most 2^31 - 1: the three fit one 64-bit word, in two orders.  Both are ASCENDING orders for
+// bitonic_sort, whose "no entry" ~0 is above every word (the top bit of a word is clear).
+//   by id:     id << 32 | (4,095 - count) << 4 | rate    id ascending, then count descending, then rate ascending:
+//                                                        the FIRST entry of an id is its best, at its smallest rate
+//   by output: (4,095 - count) << 35 | id << 4 | rate    count descending, then id ascending: the contract's order
+constexpr uint32_t kGaprMaxCount = 4095;
+__device__ __forceinline__ uint64_t gapr_by_id(int32_t vid, int32_t count, int rate) {
+    const uint32_t c = (uint32_t)count > kGaprMaxCount ? kGaprMaxCount : (uint32_t)count;
+    return ((uint64_t)(uint32_t)vid << 32) | ((uint64_t)(kGaprMaxCount - c) << 4) | (uint32_t)rate;
+}
+__device__ __forceinline__ uint64_t gapr_to_output(uint64_t w) {
+    return ((w & 0xfff0ULL) << 31) | ((w >> 32) << 4) | (w & 0xfULL);
+}
+__device__ __forceinline__ uint64_t gapr_to_id(uint64_t w) {
+    return (((w >> 4) & 0x7fffffffULL) << 32) | ((w >> 31) & 0xfff0ULL) | (w & 0xfULL);
+}
+// one output row: a 12-byte vector store (the rows of a block are 4-byte aligned, no more)
+struct GaprRow {                                                     // 12 bytes, 4-byte aligned: never widened to 16
+    int32_t id, best, rate;
+};
+__device__ __forceinline__ void gapr_store_row(int32_t *out, int64_t row, int32_t a, int32_t b, int32_t c) {
+    reinterpret_cast<GaprRow *>(out)[row] = GaprRow{a, b, c};
+}
+
+// The fold and the selection.  grid = Q.  Query q's R hit lists hits[q R + i][min(hits_n[q R + i], cap)][3] =
+// (video_id, count, kth) -> out[q][C + 1][3] as include/tvz_gap_rates.h has it.
+// The lists are streamed as ONE sequence in chunks that fill the sort buffer.  Per chunk: the kept entries (at most C,
+// one per id, in the by-id word) and the chunk's are sorted by id; every entry whose predecessor has its id is dropped -
+// what stays of an id is its largest count at its smallest rate index, for ANY number of entries per id; the rest,
+// turned into the by-output word, is sorted again and the C first are kept.  This is exact: the kept set is the C best
+// of the per-id maxima so far in the order (count, id), an id that is dropped was behind C others, whose maxima only
+// grow, so it can come back only with a larger count - and then that count is its maximum; with an equal count it
+// stays out, rightly, since its place in the order has not changed.
+// n_pairs: the lists' counts summed in 64 bits, negated if any list overflowed `cap` (topk_total).  A refused query:
+// padding and INT32_MIN, through the same two store sites as every other.  cnt[] rides along as zeros (bitonic_sort's second key).  One 12-byte store per row.
+__global__ __launch_bounds__(kBlock) void ts_gapr_fold_kernel(const int32_t *__restrict__ hits,
+                                                               const int32_t *__restrict__ hits_n,
+                                                               const int32_t *__restrict__ qm, int32_t R, int32_t cap,
+                                                               int32_t C, int32_t *__restrict__ out) {
+    __shared__ uint64_t key[kSortCap];
+    __shared__ int32_t cnt[kSortCap];
+    __shared__ int32_t s_start[kArMaxRates + 1];                     // where list i starts in the one sequence
+    const int q = blockIdx.x;
+    const int64_t row0 = (int64_t)q * (C + 1);
+    const bool refused = gapc_refused(qm[q]);                        // block-uniform, like everything up to the loop:
+    long long pairs = 0;                                             // a refused query folds nothing and pads every row
+    bool over = false;
+    int n = 0;
+    for (int i = 0; i < R && !refused; ++i) {
+        const int32_t t = hits_n[(int64_t)q * R + i];
+        if (threadIdx.x == 0) s_start[i] = n;
+        pairs += t < 0 ? 0 : t;
+        over = over || t > cap;
+        n += t > cap ? cap : (t < 0 ? 0 : t);                        // (at most 8 x cap: cap x 12 bytes exist, so cap < 2^28)
+    }
+    if (threadIdx.x == 0) s_start[R] = n;
+    __syncthreads();
+    const int32_t *src = hits + (int64_t)q * R * cap * 3;            // list i starts at src + i * cap * 3
+    int pos = 0;                                                     // the kept entries: by-id words, one per id
+    int j = 0;
+    while (j < n) {
+        int take = n - j;
+        if (take > kSortCap - pos) take = kSortCap - pos;
+        for (int e = threadIdx.x; e < take; e += kBlock) {
+            const int f = j + e;
+            int i = 0;
+            while (f >= s_start[i + 1]) ++i;                         // (f < n = s_start[R]: it ends)
+            const int32_t *h = src + ((int64_t)i * cap + (f - s_start[i])) * 3;
+            const int32_t vid = h[0];
+            key[pos + e] = vid < 0 ? ~0ULL : gapr_by_id(vid, h[1], i);
+            cnt[pos + e] = 0;
+        }
+        pos += take;
+        j += take;
+        __syncthreads();
+        sort_and_keep(key, cnt, pos, kSortCap);                      // by id; keeps all
+        // who repeats its predecessor's id (read everywhere before anyone rewrites)
+        for (int e = threadIdx.x; e < pos; e += kBlock)
+            cnt[e] = e > 0 && key[e] != ~0ULL && (key[e] >> 32) == (key[e - 1] >> 32);
+        __syncthreads();
+        for (int e = threadIdx.x; e < pos; e += kBlock) {
+            const uint64_t w = key[e];
+            key[e] = (cnt[e] || w == ~0ULL) ? ~0ULL : gapr_to_output(w);
+            cnt[e] = 0;
+        }
+        __syncthreads();
+        sort_and_keep(key, cnt, pos, C);                             // by output; pos = min(pos, C)
+        const bool mine = (int)threadIdx.x < pos && key[threadIdx.x] != ~0ULL;      // (C <= 64 < kBlock)
+        pos = __syncthreads_count(mine);                             // the entries are in front of the dropped ones
+        if (j < n) {                                                 // back to the by-id word for the next chunk
+            if (mine) key[threadIdx.x] = gapr_to_id(key[threadIdx.x]);
+            __syncthreads();
+        }
+    }
+    for (int i = threadIdx.x; i < C; i += kBlock) {
+        if (i < pos) {
+            const uint64_t w = key[i];
+            gapr_store_row(out, row0 + i, (int32_t)((w >> 4) & 0x7fffffffULL), (int32_t)(kGaprMaxCount - (uint32_t)(w >> 35)),
+                           (int32_t)(w & 0xfULL));
+        } else {
+            gapr_store_row(out, row0 + i, -1, 0, 0);
+        }
+    }
+    if (threadIdx.x == 0) gapr_store_row(out, row0 + C, -1, refused ? INT32_MIN : topk_total(pairs, over), 0);
 }
 
 }  // namespace

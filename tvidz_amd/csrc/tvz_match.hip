@@ -31,6 +31,7 @@
 #include "tvz_gap_kernels.h"
 #include "tvz_gap.h"
 #include "tvz_gap_shards.h"
+#include "tvz_gap_rates.h"
 #include "tvz_handle.h"
 #include "tvz_index_build.h"
 
@@ -2710,6 +2711,76 @@ static int tvz_align_candidates_impl(tvz_corpus *c, const double *d_queries, con
     return record(c, st);
 }
 
+// ---- the candidates at a list of rates (include/tvz_gap_rates.h) -------------------------------------------------
+namespace {
+
+constexpr int32_t kGaprMaxLists = 65535;      // probe lists of one lookup: Q * n_rates
+
+// what the rates call refuses before its workspace: the plain call's, the rate list, the probe lists
+int check_candidates_rates_args(int32_t Q, int32_t max_query_len, const double *h_rates, int32_t n_rates, int32_t min_count,
+                                int32_t cap, int32_t C, AlRates *rates) {
+    if (int rc = check_candidates_args(max_query_len, min_count, cap, C)) return rc;
+    if (int rc = check_align_rates(h_rates, n_rates, rates)) return rc;
+    if ((int64_t)Q * n_rates > kGaprMaxLists)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment candidates with rates: Q=%d x n_rates=%d is above %d probe lists", (int)Q,
+                         (int)n_rates, kGaprMaxLists);
+    return TVZ_OK;
+}
+
+}  // namespace
+
+static int tvz_align_candidates_rates_impl(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
+                                           int32_t max_query_len, const double *h_rates, int32_t n_rates, int32_t min_count,
+                                           const int32_t *d_exclude_ids, int32_t cap, int32_t C, int32_t *d_out,
+                                           void *d_workspace, size_t workspace_bytes, void *hip_stream) {
+    AlRates rates;
+    if (int rc = check_candidates_rates_args(Q, max_query_len, h_rates, n_rates, min_count, cap, C, &rates)) return rc;
+    const Batch b = align_batch(d_queries, d_q_offsets, Q, max_query_len, d_exclude_ids);
+    if (int rc = check_batch_args(c, b, cap)) return rc;
+    if (Q == 0) return TVZ_OK;
+    const int32_t lists = Q * n_rates;
+    const size_t match_bytes = candidates_match_bytes(lists, max_query_len);
+    const size_t have = d_workspace ? workspace_bytes : 0;
+    const size_t need = tvz_gap::ws_rates_bytes(Q, n_rates, cap, match_bytes, max_query_len);
+    if (have < need)
+        return tvz::fail(TVZ_ERR_WORKSPACE, "alignment candidates with rates: workspace of %zu bytes, %zu bytes missing (size it "
+                                            "with tvz_align_candidates_rates_workspace_bytes)", have, need - have);
+    TVZ_REQUIRE(d_out != nullptr && (reinterpret_cast<uintptr_t>(d_out) & 3) == 0, "d_out is NULL or not 4-byte aligned");
+    const int64_t room = tvz_gap::ws_rates_room(Q, n_rates, cap, match_bytes, have);
+    const tvz_gap::RateWsRegions r = tvz_gap::ws_rates_regions(Q, n_rates, cap, match_bytes, room);
+    unsigned char *base = reinterpret_cast<unsigned char *>(al256(reinterpret_cast<uintptr_t>(d_workspace)));
+    int32_t *hits = reinterpret_cast<int32_t *>(base + r.hits), *hits_n = reinterpret_cast<int32_t *>(base + r.hits_n);
+    int64_t *p_off = reinterpret_cast<int64_t *>(base + r.p_off);
+    int32_t *excl = reinterpret_cast<int32_t *>(base + r.excl);
+    int32_t *qm = reinterpret_cast<int32_t *>(base + r.qm), *sp = reinterpret_cast<int32_t *>(base + r.sp);
+    double *sv = reinterpret_cast<double *>(base + r.sv), *probes = reinterpret_cast<double *>(base + r.probes);
+    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+    DeviceGuard dg(c->device);
+    std::shared_lock<std::shared_mutex> lk(c->mu);            // parent, then (inside the lookup) child
+    if (!c->gap)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment candidates: this corpus keeps no gap codes (tvz_corpus_gap_index)");
+    // the sorted queries, once for all rates (it zeroes the first Q counts; the lookup writes every one of the Q R)
+    hipLaunchKernelGGL(ts_tol_sort_kernel, dim3((unsigned)tvz::ceil_div(std::max(max_query_len, 1), kTolSortBlock), (unsigned)Q),
+                       dim3(kTolSortBlock), 0, st, d_queries, d_q_offsets, max_query_len, room, sv, sp, qm, hits_n);
+    TVZ_HIP(hipGetLastError());
+    hipLaunchKernelGGL(ts_gapr_offsets_kernel, dim3(1), dim3(kGapOffBlock), 0, st, qm, Q, n_rates, d_exclude_ids, p_off, excl);
+    TVZ_HIP(hipGetLastError());
+    if (max_query_len >= 4) {
+        hipLaunchKernelGGL(ts_gapr_probe_kernel,
+                           dim3((unsigned)tvz::ceil_div(max_query_len - 3, kGapProbeBlock), (unsigned)Q, (unsigned)n_rates),
+                           dim3(kGapProbeBlock), 0, st, sv, d_q_offsets, qm, c->gap_eps, rates, p_off, probes);
+        TVZ_HIP(hipGetLastError());
+    }
+    // ONE lookup over the Q R probe lists: count_i(q, r) is the exact match's count of list q R + i over the codes
+    if (int rc = tvz_match_impl(c->gap, probes, p_off, lists, tvz_gap::max_probe_len(max_query_len), min_count,
+                                d_exclude_ids ? excl : nullptr, cap, hits, hits_n, base + r.match, match_bytes, TVZ_ALGO_AUTO,
+                                hip_stream))
+        return rc;
+    hipLaunchKernelGGL(ts_gapr_fold_kernel, dim3((unsigned)Q), dim3(kBlock), 0, st, hits, hits_n, qm, n_rates, cap, C, d_out);
+    TVZ_HIP(hipGetLastError());
+    return record(c, st);
+}
+
 // ---- the candidates over a sharded table (include/tvz_gap_shards.h) ---------------------------------------------
 namespace {
 
@@ -2851,6 +2922,24 @@ TVZ_EXPORT int tvz_align_candidates(tvz_corpus *c, const double *d_queries, cons
                                     int32_t *d_out, void *d_workspace, size_t workspace_bytes, void *hip_stream) {
     TVZ_GUARDED(tvz_align_candidates_impl(c, d_queries, d_q_offsets, Q, max_query_len, min_count, d_exclude_ids, cap, C, d_out,
                                           d_workspace, workspace_bytes, hip_stream));
+}
+
+TVZ_EXPORT size_t tvz_align_candidates_rates_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys,
+                                                             int32_t n_rates, int32_t cap, int32_t C) {
+    if (Q < 0 || Q > 65535 || max_query_len < 0 || max_query_len > kAlMaxLen || total_query_keys < 0 || C < 1 ||
+        C > tvz_gap::kMaxC || cap < C || n_rates < 1 || n_rates > kArMaxRates || (int64_t)Q * n_rates > kGaprMaxLists)
+        return 0;
+    const int64_t keys = total_query_keys > 0 ? total_query_keys : (int64_t)Q * max_query_len;
+    return tvz_gap::ws_rates_bytes(Q, n_rates, cap, candidates_match_bytes(Q * n_rates, max_query_len),
+                                   std::max<int64_t>(keys, max_query_len));
+}
+
+TVZ_EXPORT int tvz_align_candidates_rates(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
+                                          int32_t max_query_len, const double *h_rates, int32_t n_rates, int32_t min_count,
+                                          const int32_t *d_exclude_ids, int32_t cap, int32_t C, int32_t *d_out,
+                                          void *d_workspace, size_t workspace_bytes, void *hip_stream) {
+    TVZ_GUARDED(tvz_align_candidates_rates_impl(c, d_queries, d_q_offsets, Q, max_query_len, h_rates, n_rates, min_count,
+                                                d_exclude_ids, cap, C, d_out, d_workspace, workspace_bytes, hip_stream));
 }
 
 #ifdef TVZ_IX_STAMP

@@ -94,7 +94,8 @@ class Inspector:
                  profile: bool = False, match_tolerance: float = 0.0, near_top_k: Optional[int] = None,
                  near_any_offset: bool = False, near_score: str = "jaccard", near_min_votes: int = 1,
                  near_rates=None, near_spans: bool = False, near_parts: Optional[int] = None,
-                 near_two_bins: bool = False, near_candidates: Optional[int] = None, near_gap_eps: float = 1.0 / 30):
+                 near_two_bins: bool = False, near_candidates: Optional[int] = None, near_gap_eps: float = 1.0 / 30,
+                 near_candidate_rates: bool = False):
         self.store = store
         # opt-in: the near-duplicate report from the K best-aligned rows the device keeps (tvz_align_topk) instead of
         # one row per corpus row walked here.  None: the walk, exactly as before.  Refused here where the store's
@@ -193,8 +194,16 @@ class Inspector:
         # the same score, thresholds and order as the sweep's.  Codes are made at rate 1 and the parts call counts single
         # bins: refused with near_rates and near_two_bins.  An upload the candidates call refuses (more than 514 cuts)
         # takes the configured sweep.  None: nothing changes.
+        # near_candidate_rates=True turns the combination with near_rates ON: the stored codes stay at rate 1 and the
+        # upload is probed once per rate (tvz_align_candidates_rates), the parts call aligns the named videos at the same
+        # rate list and every entry carries its "rate", as the rates sweep's entries do.  False: refused as before.
         self.near_candidates = None if near_candidates is None else int(near_candidates)
         self.near_gap_eps = float(near_gap_eps)
+        self.near_candidate_rates = bool(near_candidate_rates)
+        if self.near_candidate_rates:
+            missing = [n for n, v in (("near_candidates", near_candidates), ("near_rates", near_rates)) if v is None]
+            if missing:
+                raise RuntimeError(f"near_candidate_rates=True needs {' and '.join(missing)}")
         if self.near_candidates is not None:
             if not near_duplicates or self.near_top_k is None or not self.near_any_offset:
                 raise ValueError(f"near_candidates={self.near_candidates} needs near_duplicates=True, near_top_k and "
@@ -205,7 +214,7 @@ class Inspector:
             if not (0.0 < self.near_gap_eps <= sys.float_info.max):
                 raise ValueError(f"near_gap_eps must be finite and > 0, got {near_gap_eps!r}")
             what = f"near_candidates={self.near_candidates}"
-            if self.near_rates is not None:
+            if self.near_rates is not None and not self.near_candidate_rates:
                 raise RuntimeError(f"{what} with near_rates={self.near_rates}: the gap codes are made at rate 1; "
                                    "use one of them")
             if self.near_two_bins:
@@ -217,6 +226,9 @@ class Inspector:
                 raise RuntimeError(f"{what}: the store's corpus ({type(corpus).__name__}) has no align_candidates; "
                                    "use a DeviceCorpus, a service.ShardedCorpus or a service.RankCorpus over a matcher "
                                    "with `candidates`")
+            if self.near_candidate_rates and not _corpus_can(corpus, "align_candidates_rates", "supports_align_candidate_rates"):
+                raise RuntimeError(f"near_candidate_rates=True: the store's corpus ({type(corpus).__name__}) has no "
+                                   "align_candidates_rates; use a DeviceCorpus")
             corpus.set_gap_index(self.near_gap_eps)
         # opt-in, never the default: duplicates by the TOLERANT count (include/tvz.h tvz_find_duplicates_tol)
         # instead of the reference's exact float64 equality; the verdict, the truncation at kth and the stored
@@ -534,16 +546,25 @@ class Inspector:
         every pair is what the span search reports for that row: (video_id, row_len, best_bin, votes, rate_index,
         t_first, t_last, nr).  The same fixed-point score, thresholds and order as the sweep keeps its rows by, the
         near_top_k best.  Rows of four columns where the configuration's sweep reports no span.  None: the candidates
-        call refused the upload.  The parts block stays with the calling thread for _near_parts."""
+        call refused the upload.  The parts block stays with the calling thread for _near_parts.
+        near_candidate_rates: the ids come from ONE align_candidates_rates call with near_rates, the parts call aligns at
+        the same list, and the rate_index of a row is the parts header's (rows of five columns without spans)."""
         from .corpus import align_span_order_key
         corpus = self.store.corpus
-        ids, totals = corpus.align_candidates([scene_timestamps], c=self.near_candidates, exclude_ids=[int(video_id)])
+        rates = self.near_rates if self.near_candidate_rates else (1.0,)
+        if self.near_candidate_rates:
+            ids, _, _, totals = corpus.align_candidates_rates([scene_timestamps], rates=rates, c=self.near_candidates,
+                                                              exclude_ids=[int(video_id)])
+            ids = ids[0]
+        else:
+            ids, totals = corpus.align_candidates([scene_timestamps], c=self.near_candidates, exclude_ids=[int(video_id)])
+            ids = ids[0][:, 0]
         if int(totals[0]) == -(1 << 31):
             return None
-        ids = [int(r[0]) for r in ids[0] if r[0] >= 0]
+        ids = [int(v) for v in ids if v >= 0]
         if not ids:
             return []
-        blocks = corpus.align_parts([scene_timestamps], [ids], eps=self.near_eps, rates=(1.0,), min_votes=self.near_min_votes,
+        blocks = corpus.align_parts([scene_timestamps], [ids], eps=self.near_eps, rates=rates, min_votes=self.near_min_votes,
                                     max_parts=self.near_parts or 1)[0]
         one = 1 << 20
         min_score = max(0, min(one, int(self.near_jaccard * one)))
@@ -562,7 +583,7 @@ class Inspector:
                 kept[vid] = block
         rows.sort()
         self._tls.candidate_parts = kept
-        return [row if spans else row[:4] for _, row in rows[:self.near_top_k]]
+        return [row if spans else row[:5 if self.near_candidate_rates else 4] for _, row in rows[:self.near_top_k]]
 
     def _near_rows(self, video_id: int, scene_timestamps):
         """_near_search's (rows, rated)."""
@@ -580,7 +601,7 @@ class Inspector:
             self._tls.candidate_parts = None
             rows = self._near_candidates(video_id, scene_timestamps)
             if rows is not None:                                               # (None: refused -> the configured sweep)
-                return rows, False, 0.0
+                return rows, self.near_candidate_rates, 0.0
         if self.near_top_k is not None:
             one = 1 << 20
             min_score = max(0, min(one, int(self.near_jaccard * one)))          # int() floors: the value is >= 0
