@@ -21,6 +21,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--rows", type=int, default=100_000)
 ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--sweep-reps", type=int, default=3)
+ap.add_argument("--turns-only", action="store_true", help="the A B A B table only (a parent build against a branch build)")
 args = ap.parse_args()
 
 import torch  # noqa: E402
@@ -78,6 +79,9 @@ for Q in (1, 16, 64):
     same = bool((out_1.cpu().numpy()[:, :, :2] == out_0.cpu().numpy()).all())
     print(f"{Q:3d}   plain {stats(turns[0])}   rates {stats(turns[1])}   plain {stats(turns[2])}   rates {stats(turns[3])}   "
           f"columns 0..1 equal: {same}")
+if args.turns_only:
+    dc.close()
+    sys.exit(0)
 print()
 print("ms per call, median (IQR)")
 print(f"{'Q':>3s} {'R':>2s} {'cand R':>20s} {'cand+parts':>20s} {'sweep R (k=16)':>20s} {'true row first':>15s} "

@@ -124,6 +124,38 @@ def counting_query():
 
 HIT_COUNTS = (0, 1, 15, 16, 17, 63, 64, 65, 255, 256, 257)
 
+# ---- the offsets scan over more queries than it has threads -------------------------------------------------------
+SCAN_Q = 2049                                        # 1,024 threads take 3 probe lists each, the last 341 none
+SCAN_LONG = (1023, 2048)                             # the first list of thread 341, the last list of thread 682 (and of all)
+SCAN_CALL = dict(c=2, min_count=1, cap=4, max_query_len=4)
+
+
+def scan_case():
+    """-> (table, queries, exclude_ids): counting_table(2), whose two rows both hold the base's first position, and
+    SCAN_Q tiny queries on it - that position's 4 values mostly, 3 or 0 values every seventh, and 5 values (longer than
+    the call's max_query_len: refused) at SCAN_LONG - with exclusions that alternate between the two rows' ids and -1."""
+    rows = counting_table(2)
+    q = counting_query()
+    kinds = [q[:4], q[:3], []]
+    queries = [kinds[0] if i % 7 else kinds[1 + (i // 7) % 2] for i in range(SCAN_Q)]
+    for i in SCAN_LONG:
+        queries[i] = q[:5]
+    excl = [rows[0][0] if i % 2 else rows[1][0] if i % 3 == 0 else -1 for i in range(SCAN_Q)]
+    return rows, queries, excl
+
+
+def scan_expected(rows, queries, excl):
+    """-> (int64 [SCAN_Q, 3, 2], memo): the reference's block of every query, computed once per (length, exclusion)"""
+    from tests import gap_candidates_ref as ref
+    memo = {}
+    exp = np.zeros((len(queries), SCAN_CALL["c"] + 1, 2), dtype=np.int64)
+    for i, (query, ex) in enumerate(zip(queries, excl)):
+        key = (len(query), ex)
+        if key not in memo:
+            memo[key] = ref.candidates(rows, [query], GAP_EPS, exclude_ids=[ex], **SCAN_CALL)[0].astype(np.int64)
+        exp[i] = memo[key]
+    return exp, memo
+
 
 def long_query(n, seed):
     """n cuts, gaps of 20 to 400 bins: for the lengths at the probe limit (514 passes, 515 is refused)"""

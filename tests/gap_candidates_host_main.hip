@@ -32,10 +32,10 @@ void carve(int32_t Q, int32_t max_len, int64_t keys, int32_t cap, int32_t C, siz
     unsigned char *given = buf.data() + misalign;
     const size_t match_bytes = candidates_match_bytes(Q, max_len);
     const int64_t want = std::max<int64_t>(keys > 0 ? keys : (int64_t)Q * max_len, max_len);
-    const int64_t room = tvz_gap::ws_room(Q, cap, match_bytes, need);
+    const int64_t room = tvz_gap::ws_room(Q, 1, false, cap, match_bytes, need);
     CHECK(room == want);
-    CHECK(tvz_gap::ws_room(Q, cap, match_bytes, need - 1) == want - 1 || want == 0);
-    const tvz_gap::WsRegions r = tvz_gap::ws_regions(Q, cap, match_bytes, room);
+    CHECK(tvz_gap::ws_room(Q, 1, false, cap, match_bytes, need - 1) == want - 1 || want == 0);
+    const tvz_gap::WsRegions r = tvz_gap::ws_regions(Q, 1, false, cap, match_bytes, room);
     unsigned char *base = reinterpret_cast<unsigned char *>(al256(reinterpret_cast<uintptr_t>(given)));
     const size_t at[] = {r.hits, r.hits_n, r.p_off, r.match, r.qm, r.sv, r.sp, r.probes, r.end};
     const size_t bytes[] = {(size_t)Q * cap * 12, (size_t)Q * 4, ((size_t)Q + 1) * 8, match_bytes, (size_t)Q * 4,

@@ -31,10 +31,10 @@ void carve(int32_t Q, int32_t max_len, int64_t keys, int32_t R, int32_t cap, int
     const size_t lists = (size_t)Q * R;
     const size_t match_bytes = candidates_match_bytes((int32_t)lists, max_len);
     const int64_t want = std::max<int64_t>(keys > 0 ? keys : (int64_t)Q * max_len, max_len);
-    const int64_t room = tvz_gap::ws_rates_room(Q, R, cap, match_bytes, need);
+    const int64_t room = tvz_gap::ws_room(Q, R, true, cap, match_bytes, need);
     CHECK(room == want);
-    CHECK(tvz_gap::ws_rates_room(Q, R, cap, match_bytes, need - 1) == want - 1 || want == 0);
-    const tvz_gap::RateWsRegions r = tvz_gap::ws_rates_regions(Q, R, cap, match_bytes, room);
+    CHECK(tvz_gap::ws_room(Q, R, true, cap, match_bytes, need - 1) == want - 1 || want == 0);
+    const tvz_gap::WsRegions r = tvz_gap::ws_regions(Q, R, true, cap, match_bytes, room);
     unsigned char *base = reinterpret_cast<unsigned char *>(al256(reinterpret_cast<uintptr_t>(given)));
     const size_t at[] = {r.hits, r.hits_n, r.p_off, r.excl, r.match, r.qm, r.sv, r.sp, r.probes, r.end};
     const size_t bytes[] = {lists * cap * 12, lists * 4, (lists + 1) * 8, lists * 4, match_bytes, (size_t)Q * 4,

@@ -44,9 +44,9 @@ void carve(int32_t Q, int32_t max_len, int64_t keys, int32_t cap, int32_t C, int
     // the plain call's part, laid out from s.plain on as tvz_align_candidates lays a caller's buffer out
     const size_t match_bytes = candidates_match_bytes(Q, max_len);
     const int64_t want = std::max<int64_t>(keys > 0 ? keys : (int64_t)Q * max_len, max_len);
-    const int64_t room = tvz_gap::ws_room(Q, cap, match_bytes, s.plain_bytes);
+    const int64_t room = tvz_gap::ws_room(Q, 1, false, cap, match_bytes, s.plain_bytes);
     CHECK(room == want);
-    const tvz_gap::WsRegions w = tvz_gap::ws_regions(Q, cap, match_bytes, room);
+    const tvz_gap::WsRegions w = tvz_gap::ws_regions(Q, 1, false, cap, match_bytes, room);
     unsigned char *base = reinterpret_cast<unsigned char *>(al256(s.plain));
     CHECK(base == pl);                                                    // (its own alignment costs nothing)
     const size_t at[] = {w.hits, w.hits_n, w.p_off, w.match, w.qm, w.sv, w.sp, w.probes, w.end};

@@ -122,6 +122,20 @@ def test_the_premises_of_the_cases_hold():
         assert int(six[64, 1]) == sum(1 for i in range(H) if i % 7 >= 5)
     # the probe limit
     assert int(ref.candidates(rows, [cs.long_query(514, 1), cs.long_query(515, 2)], EPS, 4)[1, 4, 1]) == INT32_MIN
+    # the scan case: more queries than the scan's block has threads, so that a thread has 3 lists and the last none; the
+    # refused queries are a thread's first and a thread's last list; at least four different blocks, not padding alone
+    t, queries, excl = cs.scan_case()
+    per = -(-cs.SCAN_Q // 1024)
+    assert per == 3 and cs.SCAN_LONG[0] % per == 0 and cs.SCAN_LONG[1] % per == per - 1 and cs.SCAN_LONG[1] == cs.SCAN_Q - 1
+    assert {len(q) for q in queries} == {0, 3, 4, 5} and [i for i, q in enumerate(queries) if len(q) == 5] == list(cs.SCAN_LONG)
+    assert set(excl) == {t[0][0], t[1][0], -1} and t[0][0] != t[1][0]
+    exp, memo = cs.scan_expected(t, queries, excl)
+    blocks = {tuple(v.ravel().tolist()) for v in memo.values()}
+    assert len(blocks) >= 4, blocks
+    both = sorted(v for v, _ in t[:2])
+    assert memo[(4, -1)].tolist() == [[both[0], 1], [both[1], 1], [-1, 2]]
+    assert memo[(4, both[0])].tolist() == [[both[1], 1], [-1, 0], [-1, 1]] and memo[(3, -1)].tolist() == [[-1, 0], [-1, 0], [-1, 0]]
+    assert (exp[list(cs.SCAN_LONG), 2, 1] == INT32_MIN).all()
 
 
 # ------------------------------------------------------------------------------------------------- the C ABI
@@ -366,13 +380,18 @@ def test_the_new_kernels_exist_once_with_no_scratch_and_no_spills(kernels):  # n
         (k,) = found
         assert k[".private_segment_fixed_size"] == 0, (name, k[".private_segment_fixed_size"])
         assert k.get(".vgpr_spill_count", 0) == 0 and k.get(".sgpr_spill_count", 0) == 0, (name, k)
+        assert k[".wavefront_size"] == 64
         recorded[name] = (k[".vgpr_count"], k[".sgpr_count"], k[".group_segment_fixed_size"], k[".max_flat_workgroup_size"])
     print("vgprs, sgprs, LDS bytes, block:", recorded)
     assert recorded[NEW[0]][3] == 1024 and recorded[NEW[1]][3] == 256 and recorded[NEW[2]][3] == 256
     # the selection's sort buffers: 2,048 keys and counts; the scan's one word per wave; the probes use no LDS
     assert recorded[NEW[2]][2] == 2048 * 12 and recorded[NEW[0]][2] == 64 and recorded[NEW[1]][2] == 0
-    # registers, as the compiler reported them when the kernels were written (a rise is looked at, not forbidden)
-    assert recorded[NEW[1]][0] <= 64 and recorded[NEW[2]][0] <= 64 and recorded[NEW[0]][0] <= 32
+    # registers, as the compiler reported them when the kernels were written (a rise is looked at, not forbidden); the
+    # scan is the rates call's too and has its bound: it divides by the lists per query
+    assert recorded[NEW[1]][0] <= 64 and recorded[NEW[2]][0] <= 64 and recorded[NEW[0]][0] <= 40
+    # ... and there is ONE scan and ONE probe kernel: the rates call has no copies of its own
+    for name in ("gapr_offsets", "gapr_probe"):
+        assert not [n for n in kernels if name in n], name
 
 
 # ------------------------------------------------------------------------------------ the host code, sanitized

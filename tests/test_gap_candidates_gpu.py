@@ -97,6 +97,22 @@ def test_the_probe_limit_beside_a_good_query_and_no_query(world):
     assert rows_.shape == (0, 4, 2) and totals.shape == (0,)
 
 
+def test_more_queries_than_the_offsets_scan_has_threads(scratch):
+    """Q = 2,049: a thread of the one-block scan takes 3 probe lists and the last threads none; refused queries on both
+    sides of a thread's boundary, queries of 3 and 0 values between those of 4, exclusions that alternate between the
+    table's two ids and -1.  Whole blocks, from the reference once per (length, exclusion)."""
+    dc = scratch
+    rows, queries, excl = cs.scan_case()
+    dc.upload(rows)
+    dc.set_gap_index(EPS)
+    exp, memo = cs.scan_expected(rows, queries, excl)
+    assert len({tuple(v.ravel().tolist()) for v in memo.values()}) >= 4                # (not padding alone)
+    got = _block(dc, queries, exclude_ids=excl, **cs.SCAN_CALL)
+    bad = np.argwhere((got != exp).any(axis=(1, 2)))
+    assert bad.size == 0, [(int(q), got[q].tolist(), exp[q].tolist()) for q in bad[:3, 0]]
+    assert exp[cs.SCAN_LONG[0], 2, 1] == exp[cs.SCAN_LONG[1], 2, 1] == INT32_MIN
+
+
 # -------------------------------------------------------------------------------- 2. table and parameter edges
 @pytest.mark.parametrize("H", cs.HIT_COUNTS)
 def test_hit_counts_ties_and_every_c(scratch, H):

@@ -23,8 +23,10 @@ from tvidz_amd import _lib, build as tbuild, corpus as tc
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "tvz_gap_rates.h")
 MAIN = os.path.join(ROOT, "tests", "gap_candidates_rates_host_main.hip")
-NEW = ("22ts_gapr_offsets_kernelE", "20ts_gapr_probe_kernelE", "19ts_gapr_fold_kernelE")
-OLD = ("22ts_gapc_offsets_kernelE", "20ts_gapc_probe_kernelE", "21ts_gapc_select_kernelE", "20ts_gapc_merge_kernelE")
+# the scan and the probes are the plain call's too (R = 1, the rate 1.0); the fold is this call's own
+NEW = ("22ts_gapc_offsets_kernelE", "20ts_gapc_probe_kernelE", "19ts_gapr_fold_kernelE")
+OLD = ("21ts_gapc_select_kernelE", "20ts_gapc_merge_kernelE")
+GONE = ("gapr_offsets", "gapr_probe")                      # the second copies of the scan and the probes
 EPS = rc.GAP_EPS
 ERR_INVALID, ERR_UNSUPPORTED, ERR_WORKSPACE = -1, -4, -5
 INT32_MIN = -(1 << 31)
@@ -330,7 +332,7 @@ def test_the_new_kernels_exist_once_with_no_scratch_and_the_old_ones_keep_their_
     recorded = {}
     for name in NEW:
         found = [k for n, k in kernels.items() if name in n]
-        assert len(found) == 1, (name, sorted(n for n in kernels if "gapr" in n))
+        assert len(found) == 1, (name, sorted(n for n in kernels if "gap" in n))
         (k,) = found
         assert k[".private_segment_fixed_size"] == 0, (name, k[".private_segment_fixed_size"])
         assert k.get(".vgpr_spill_count", 0) == 0 and k.get(".sgpr_spill_count", 0) == 0, (name, k)
@@ -345,6 +347,8 @@ def test_the_new_kernels_exist_once_with_no_scratch_and_the_old_ones_keep_their_
     assert recorded[NEW[1]][0] <= 64 and recorded[NEW[2]][0] <= 64 and recorded[NEW[0]][0] <= 40
     for name in OLD:
         assert len([n for n in kernels if name in n]) == 1, name
+    for name in GONE:
+        assert not [n for n in kernels if name in n], name
 
 
 # ------------------------------------------------------------------------------------ the host code, sanitized

@@ -1,4 +1,4 @@
-"""GPU parity of tvz_align_candidates_rates (ts_gapr_offsets_kernel, ts_gapr_probe_kernel, ONE lookup over the handle's
+"""GPU parity of tvz_align_candidates_rates (ts_gapc_offsets_kernel, ts_gapc_probe_kernel, ONE lookup over the handle's
 code table for the Q x n_rates probe lists, ts_gapr_fold_kernel) against tests/gap_candidates_rates_ref.py: whole
 [Q, C + 1, 3] blocks, exact integers throughout.  The tables, the uploads and the rate lists are
 tests/gap_candidates_rates_cases.py's; their premises are asserted without a device in

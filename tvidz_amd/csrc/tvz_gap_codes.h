@@ -1,5 +1,5 @@
 // tvz_gap_codes.h — the gap codes of one stored row, made on the host (include/tvz_gap.h: STORED SIDE), and the
-// workspace layouts of tvz_align_candidates, its form with rates and its sharded form.  Plain C++ with no HIP in it:
+// workspace layout of tvz_align_candidates and its form with rates, with the sharded form's front.  Plain C++ with no HIP in it:
 // tvz_match.hip includes it for the handle, a stand-alone host program can include it on its own.
 #pragma once
 #include <algorithm>
@@ -56,7 +56,7 @@ inline int64_t row_codes(const int64_t *keys, int64_t len, double gap_eps, std::
     return (int64_t)(out.size() - before);
 }
 
-// ---- the workspace of tvz_align_candidates ----
+// ---- the workspace of tvz_align_candidates and tvz_align_candidates_rates (include/tvz_gap_rates.h) ----
 // Regions of 256-byte multiples behind a base aligned up to 256 (the carver of tvz_match.hip walks the same sizes).
 inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -76,73 +76,42 @@ inline int32_t max_probe_len(int32_t max_query_len) {
     return (int32_t)std::min<int64_t>(s, kMaxProbes / kVariants * kVariants);
 }
 
-// The lookup's hit lists and counts, the probe offsets, the lookup's own workspace (`match_bytes`: its sizing function's
-// answer) and the queries' counts; then, for `room` query values - the call takes what the caller's buffer holds, at
-// least one longest query - the sorted values, their positions and 8 probe slots per value.  The queries the sort
-// accepts lie in disjoint ranges of [0, room), so their probes never exceed 8 * room slots.
-struct WsRegions {                   // byte offsets from the aligned base
-    size_t hits, hits_n, p_off, match, qm, sv, sp, probes, end;
+// The lookup sees Q * R probe lists, R per query (list q * R + i is query q at rate i; the plain call: R = 1).  Per list:
+// its hit list and count, its probe offset and - `with_excl`, the call with a rate list - its query's exclusion id; then
+// the lookup's own workspace (`match_bytes`: its sizing function's answer for that many lists) and the Q queries'
+// counts; then, for `room` query values - the call takes what the caller's buffer holds, at least one longest query -
+// the sorted values, their positions and 8 probe slots per value and rate.  The queries the sort accepts lie in
+// disjoint ranges of [0, room), so their probes never exceed 8 * R * room slots.
+struct WsRegions {                   // byte offsets from the aligned base; excl is empty (= match) without with_excl
+    size_t hits, hits_n, p_off, excl, match, qm, sv, sp, probes, end;
 };
-constexpr size_t kPerKey = sizeof(double) + sizeof(int32_t) + kVariants * sizeof(double);   // 76
+constexpr size_t per_key(int32_t R) { return sizeof(double) + sizeof(int32_t) + (size_t)R * kVariants * sizeof(double); }
 constexpr size_t kWsSlack = 256 + 3 * 255;              // a line for the base, the roundings of the three sized regions
 
-inline WsRegions ws_regions(int32_t Q, int32_t cap, size_t match_bytes, int64_t room) {
+inline WsRegions ws_regions(int32_t Q, int32_t R, bool with_excl, int32_t cap, size_t match_bytes, int64_t room) {
     WsRegions r;
+    const size_t lists = (size_t)Q * (size_t)R;
     size_t p = 0;
-    r.hits = p;    p += al256((size_t)Q * (size_t)cap * 3 * sizeof(int32_t));
-    r.hits_n = p;  p += al256((size_t)Q * sizeof(int32_t));
-    r.p_off = p;   p += al256(((size_t)Q + 1) * sizeof(int64_t));
+    r.hits = p;    p += al256(lists * (size_t)cap * 3 * sizeof(int32_t));
+    r.hits_n = p;  p += al256(lists * sizeof(int32_t));
+    r.p_off = p;   p += al256((lists + 1) * sizeof(int64_t));
+    r.excl = p;    p += with_excl ? al256(lists * sizeof(int32_t)) : 0;
     r.match = p;   p += al256(match_bytes);
     r.qm = p;      p += al256((size_t)Q * sizeof(int32_t));
     r.sv = p;      p += al256((size_t)room * sizeof(double));
     r.sp = p;      p += al256((size_t)room * sizeof(int32_t));
-    r.probes = p;  p += al256((size_t)room * kVariants * sizeof(double));
+    r.probes = p;  p += al256((size_t)room * (size_t)R * kVariants * sizeof(double));
     r.end = p;
     return r;
 }
 // bytes for `keys` query values; the most values a buffer of `bytes` holds (-1: not even the fixed parts) -
 // ws_room(.., ws_bytes(.., keys)) is `keys`, and the regions of that room end inside the buffer at any base
-inline size_t ws_bytes(int32_t Q, int32_t cap, size_t match_bytes, int64_t keys) {
-    return ws_regions(Q, cap, match_bytes, 0).end + kWsSlack + (size_t)keys * kPerKey;
+inline size_t ws_bytes(int32_t Q, int32_t R, bool with_excl, int32_t cap, size_t match_bytes, int64_t keys) {
+    return ws_regions(Q, R, with_excl, cap, match_bytes, 0).end + kWsSlack + (size_t)keys * per_key(R);
 }
-inline int64_t ws_room(int32_t Q, int32_t cap, size_t match_bytes, size_t bytes) {
-    const size_t fixed = ws_bytes(Q, cap, match_bytes, 0);
-    return bytes < fixed ? -1 : (int64_t)((bytes - fixed) / kPerKey);
-}
-
-// ---- the workspace of tvz_align_candidates_rates (include/tvz_gap_rates.h) ----
-// The plain call's regions for the Q * n_rates pseudo-queries (query q at rate i is pseudo-query q * n_rates + i) that
-// the lookup sees: their hit lists, counts, probe offsets and exclusion ids, and the lookup's own workspace for that
-// many probe lists; the sorted values, their positions and counts are the Q queries' own, and a value has 8 probe slots
-// PER RATE.  The same rules otherwise: 256-byte multiples behind a base aligned up to 256, `room` query values.
-struct RateWsRegions {               // byte offsets from the aligned base
-    size_t hits, hits_n, p_off, excl, match, qm, sv, sp, probes, end;
-};
-constexpr size_t rate_per_key(int32_t n_rates) {
-    return sizeof(double) + sizeof(int32_t) + (size_t)n_rates * kVariants * sizeof(double);
-}
-inline RateWsRegions ws_rates_regions(int32_t Q, int32_t n_rates, int32_t cap, size_t match_bytes, int64_t room) {
-    RateWsRegions r;
-    const size_t pq = (size_t)Q * (size_t)n_rates;
-    size_t p = 0;
-    r.hits = p;    p += al256(pq * (size_t)cap * 3 * sizeof(int32_t));
-    r.hits_n = p;  p += al256(pq * sizeof(int32_t));
-    r.p_off = p;   p += al256((pq + 1) * sizeof(int64_t));
-    r.excl = p;    p += al256(pq * sizeof(int32_t));
-    r.match = p;   p += al256(match_bytes);
-    r.qm = p;      p += al256((size_t)Q * sizeof(int32_t));
-    r.sv = p;      p += al256((size_t)room * sizeof(double));
-    r.sp = p;      p += al256((size_t)room * sizeof(int32_t));
-    r.probes = p;  p += al256((size_t)room * (size_t)n_rates * kVariants * sizeof(double));
-    r.end = p;
-    return r;
-}
-inline size_t ws_rates_bytes(int32_t Q, int32_t n_rates, int32_t cap, size_t match_bytes, int64_t keys) {
-    return ws_rates_regions(Q, n_rates, cap, match_bytes, 0).end + kWsSlack + (size_t)keys * rate_per_key(n_rates);
-}
-inline int64_t ws_rates_room(int32_t Q, int32_t n_rates, int32_t cap, size_t match_bytes, size_t bytes) {
-    const size_t fixed = ws_rates_bytes(Q, n_rates, cap, match_bytes, 0);
-    return bytes < fixed ? -1 : (int64_t)((bytes - fixed) / rate_per_key(n_rates));
+inline int64_t ws_room(int32_t Q, int32_t R, bool with_excl, int32_t cap, size_t match_bytes, size_t bytes) {
+    const size_t fixed = ws_bytes(Q, R, with_excl, cap, match_bytes, 0);
+    return bytes < fixed ? -1 : (int64_t)((bytes - fixed) / per_key(R));
 }
 
 // ---- the workspace of tvz_align_candidates_sharded ----

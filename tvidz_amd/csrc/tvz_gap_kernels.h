@@ -1,15 +1,17 @@
-// tvz_gap_kernels.h — the kernels of tvz_align_candidates (include/tvz_gap.h; gfx950, wave64).
+// tvz_gap_kernels.h — the kernels of tvz_align_candidates (include/tvz_gap.h) and tvz_align_candidates_rates
+// (include/tvz_gap_rates.h); gfx950, wave64.  The two calls share every step but the last:
 //
-//   ts_gapc_offsets_kernel  where every query's probes go: an exclusive scan of the queries' probe slots.
-//   ts_gapc_probe_kernel    the probes: a thread per (query, position) writes its 8 slots.
-//   ts_gapc_select_kernel   per query the C best of the lookup's hit list, the block and the total.
-//   ts_gapc_merge_kernel    per query the C best of up to 16 such blocks (tvz_align_candidates_merge).
-//   ts_gapr_*_kernel        the same three steps at a list of rates (tvz_align_candidates_rates): at the end of the file.
+//   ts_gapc_offsets_kernel  where every probe list goes: an exclusive scan of the probe slots of the Q R lists.
+//   ts_gapc_probe_kernel    the probes: a thread per (query, rate, position) writes its 8 slots.
+//   (the internal match over the handle's code table: the probe lists are its queries)
+//   ts_gapc_select_kernel   the plain call's last step: per query the C best of its hit list, the block and the total.
+//   ts_gapr_fold_kernel     the rates call's: per query its R hit lists folded per id, the C best, the block, the total.
 //
-// Between the last two the internal match runs over the handle's code table (the queries are the probe lists).
-// The queries come sorted from ts_tol_sort_kernel (tvz_tol_kernels.h): sv[at .. at + m), at = q_offsets[q] -
+//   ts_gapc_merge_kernel    per query the C best of up to 16 blocks of the plain call (tvz_align_candidates_merge).
+//
+// The plain call is the shared steps at R = 1 with the rate list {1.0}.  The queries come sorted from ts_tol_sort_kernel (tvz_tol_kernels.h): sv[at .. at + m), at = q_offsets[q] -
 // q_offsets[0], m = qm[q]; qm[q] < 0: longer than the call's max_query_len.  From tvz_topk_kernels.h: bitonic_sort,
-// sort_and_keep, topk_total; from tvz_wave.h: wave_scan_incl, waves_sum, wave_lds_fence.  Included by tvz_match.hip behind them.
+// sort_and_keep, topk_total; from tvz_wave.h: wave_scan_incl, waves_sum, wave_lds_fence; from tvz_align_kernels.h: AlRates, al_scaled.  Included by tvz_match.hip behind them.
 #pragma once
 #include "tvz_gap_codes.h"
 #include "tvz_topk_kernels.h"
@@ -23,14 +25,20 @@ constexpr int kGapProbeBlock = 256;
 __device__ __forceinline__ bool gapc_refused(int32_t m) { return tvz_gap::probe_slots(m) < 0; }
 __device__ __forceinline__ int32_t gapc_slots(int32_t m) { return gapc_refused(m) ? 0 : tvz_gap::probe_slots(m); }
 
-// p_off[q] = the slots of the queries before q, p_off[Q] = all of them.  grid = 1.
-__global__ __launch_bounds__(kGapOffBlock) void ts_gapc_offsets_kernel(const int32_t *__restrict__ qm, int32_t Q,
-                                                                        int64_t *__restrict__ p_off) {
+// The lookup sees Q R probe lists: list p = q R + i is query q at rate i (R = 1, the rate 1.0: the plain call).
+// p_off[p] = the slots of the lists before p (a list has its query's, p / R), p_off[Q R] = all of them; with somewhere
+// to put them (excl_out != NULL), excl_out[p] = exclude_ids[p / R]: the lookup reads one id per probe list, and the
+// plain call, whose lists are its queries, hands it the caller's array instead.  grid = 1; Q R <= 65,535: 64 per thread.
+__global__ __launch_bounds__(kGapOffBlock) void ts_gapc_offsets_kernel(const int32_t *__restrict__ qm, int32_t Q, int32_t R,
+                                                                        const int32_t *__restrict__ exclude_ids,
+                                                                        int64_t *__restrict__ p_off,
+                                                                        int32_t *__restrict__ excl_out) {
     __shared__ uint32_t s_w[kGapOffBlock / 64];
-    const int per = (Q + kGapOffBlock - 1) / kGapOffBlock;
-    const int q0 = (int)threadIdx.x * per;
+    const int n = Q * R;
+    const int per = (n + kGapOffBlock - 1) / kGapOffBlock;
+    const int p0 = (int)threadIdx.x * per;
     uint32_t mine = 0;
-    for (int q = q0; q < q0 + per && q < Q; ++q) mine += (uint32_t)gapc_slots(qm[q]);
+    for (int p = p0; p < p0 + per && p < n; ++p) mine += (uint32_t)gapc_slots(qm[p / R]);
     const uint32_t incl = wave_scan_incl(mine);
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 63) s_w[wave] = incl;
@@ -38,30 +46,37 @@ __global__ __launch_bounds__(kGapOffBlock) void ts_gapc_offsets_kernel(const int
     uint32_t before, all;
     waves_sum<kGapOffBlock / 64>(s_w, wave, before, all);
     uint32_t at = before + incl - mine;
-    for (int q = q0; q < q0 + per && q < Q; ++q) {
-        p_off[q] = (int64_t)at;
-        at += (uint32_t)gapc_slots(qm[q]);
+    for (int p = p0; p < p0 + per && p < n; ++p) {
+        p_off[p] = (int64_t)at;
+        at += (uint32_t)gapc_slots(qm[p / R]);
+        if (excl_out) excl_out[p] = exclude_ids[p / R];
     }
-    if (threadIdx.x == 0) p_off[Q] = (int64_t)all;
+    if (threadIdx.x == 0) p_off[n] = (int64_t)all;
 }
 
-// The query side of the contract.  grid = (ceil(positions / kGapProbeBlock), Q); thread i of query q takes position i
-// (i + 3 < m) and writes probes[p_off[q] + 8 i ..+ 8): slot v chooses a_j + ((v >> j) & 1) for gap j.  A choice with
-// an invalid bin is written as NaN: the lookup drops a NaN before it probes (canon_key: "NaN never matches", in every
-// match kernel), so such a slot can match nothing and the slots keep their fixed places.  The division is al_bin's:
-// a subtraction, then a true division.  Four 16-byte stores per thread (p_off is a multiple of 8 slots).
+// The query side of the contract on x' = x * rho (al_scaled of tvz_align_kernels.h: the alignment calls' one
+// multiplication, never contracted).  grid = (ceil(positions / kGapProbeBlock), Q, R); thread i of query q at rate
+// z = blockIdx.z takes position i (i + 3 < m) and writes probes[p_off[q R + z] + 8 i ..+ 8): slot v chooses
+// a_j + ((v >> j) & 1) for gap j.  A choice with an invalid bin is written as NaN: the lookup drops a NaN before it
+// probes (canon_key: "NaN never matches", in every match kernel), so such a slot can match nothing and the slots keep
+// their fixed places.  The division is al_bin's: a subtraction, then a true division.  Four 16-byte stores per thread
+// (p_off is a multiple of 8 slots).
+// The plain call is R = 1 with the rate list {1.0}, and its probes are bit for bit those of a kernel without the
+// multiplication: x * 1.0 == x for every double (the product is never contracted into what follows: al_scaled is
+// compiled with fp contract(off)), a NaN stays a NaN, and from the four scaled values on the expressions are the same.
 __global__ __launch_bounds__(kGapProbeBlock) void ts_gapc_probe_kernel(const double *__restrict__ sv,
                                                                         const int64_t *__restrict__ q_offsets,
                                                                         const int32_t *__restrict__ qm, double gap_eps,
-                                                                        const int64_t *__restrict__ p_off,
+                                                                        AlRates rates, const int64_t *__restrict__ p_off,
                                                                         double *__restrict__ probes) {
     const int q = blockIdx.y;
     const int32_t m = qm[q];
     if (gapc_slots(m) == 0) return;                                  // refused, or fewer than 4 values (block-uniform)
     const int i = (int)blockIdx.x * kGapProbeBlock + (int)threadIdx.x;
     if (i + 3 >= m) return;
+    const double rho = rates.r[blockIdx.z];                          // (a uniform index: scalar loads of the argument)
     const double *s = sv + (q_offsets[q] - q_offsets[0]) + i;
-    const double s0 = s[0], s1 = s[1], s2 = s[2], s3 = s[3];
+    const double s0 = al_scaled(s[0], rho), s1 = al_scaled(s[1], rho), s2 = al_scaled(s[2], rho), s3 = al_scaled(s[3], rho);
     double a[3];
     a[0] = floor((s1 - s0) / gap_eps);
     a[1] = floor((s2 - s1) / gap_eps);
@@ -75,7 +90,8 @@ __global__ __launch_bounds__(kGapProbeBlock) void ts_gapc_probe_kernel(const dou
         lo[j] = (a[j] >= 0.0 && a[j] <= tvz_gap::kMaxBin) ? a[j] * place[j] : none;
         hi[j] = (b >= 0.0 && b <= tvz_gap::kMaxBin) ? b * place[j] : none;
     }
-    double2 *o = reinterpret_cast<double2 *>(probes + p_off[q] + (int64_t)tvz_gap::kVariants * i);
+    const int64_t p = (int64_t)q * rates.n + blockIdx.z;
+    double2 *o = reinterpret_cast<double2 *>(probes + p_off[p] + (int64_t)tvz_gap::kVariants * i);
 #pragma unroll
     for (int v = 0; v < tvz_gap::kVariants; v += 2) {                // (NaN + x = NaN: an invalid choice poisons its slots)
         const double rest = ((v & 2) ? hi[1] : lo[1]) + ((v & 4) ? hi[2] : lo[2]);
@@ -206,80 +222,9 @@ __global__ __launch_bounds__(kGapMergeBlock) void ts_gapc_merge_kernel(const int
     if (lane == 0) o[C] = make_int2(-1, topk_total(sum, over));
 }
 
-// ---- the candidates at a list of rates (tvz_align_candidates_rates, include/tvz_gap_rates.h) ------------------------
-// Query q at rate i is the PSEUDO-QUERY q * R + i of the lookup: its probes are the query side of the contract on
-// x' = x * rho_i (al_scaled of tvz_align_kernels.h: the alignment calls' one multiplication, never contracted).
-//   ts_gapr_offsets_kernel  the pseudo-queries' probe offsets and their queries' exclusion ids.
-//   ts_gapr_probe_kernel    the probes: a thread per (query, rate, position) writes its 8 slots.
-//   ts_gapr_fold_kernel     per query, over its R hit lists: per id the best (count, smallest rate index), the C best
-//                           ids, the block and the total.
-
-// p_off[p] = the slots of the pseudo-queries before p (pseudo-query p has its query's, p / R), p_off[Q R] = all of
-// them; excl_out[p] = exclude_ids[p / R] where the call has exclusions (the lookup reads one id per probe list).
-// grid = 1; Q R <= 65,535: 64 per thread.
-__global__ __launch_bounds__(kGapOffBlock) void ts_gapr_offsets_kernel(const int32_t *__restrict__ qm, int32_t Q, int32_t R,
-                                                                        const int32_t *__restrict__ exclude_ids,
-                                                                        int64_t *__restrict__ p_off,
-                                                                        int32_t *__restrict__ excl_out) {
-    __shared__ uint32_t s_w[kGapOffBlock / 64];
-    const int n = Q * R;
-    const int per = (n + kGapOffBlock - 1) / kGapOffBlock;
-    const int p0 = (int)threadIdx.x * per;
-    uint32_t mine = 0;
-    for (int p = p0; p < p0 + per && p < n; ++p) mine += (uint32_t)gapc_slots(qm[p / R]);
-    const uint32_t incl = wave_scan_incl(mine);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 63) s_w[wave] = incl;
-    __syncthreads();
-    uint32_t before, all;
-    waves_sum<kGapOffBlock / 64>(s_w, wave, before, all);
-    uint32_t at = before + incl - mine;
-    for (int p = p0; p < p0 + per && p < n; ++p) {
-        p_off[p] = (int64_t)at;
-        at += (uint32_t)gapc_slots(qm[p / R]);
-        if (exclude_ids) excl_out[p] = exclude_ids[p / R];
-    }
-    if (threadIdx.x == 0) p_off[n] = (int64_t)all;
-}
-
-// ts_gapc_probe_kernel on the scaled values.  grid = (ceil(positions / kGapProbeBlock), Q, R); thread i of query q at
-// rate blockIdx.z writes probes[p_off[q R + z] + 8 i ..+ 8), the same slots in the same order with the same four
-// 16-byte stores.  The four values are scaled first, each by one multiplication; from there on the expressions are
-// the plain kernel's, so that at the rate 1.0 (x * 1.0 == x, bit for bit) the probes are the plain kernel's.
-__global__ __launch_bounds__(kGapProbeBlock) void ts_gapr_probe_kernel(const double *__restrict__ sv,
-                                                                        const int64_t *__restrict__ q_offsets,
-                                                                        const int32_t *__restrict__ qm, double gap_eps,
-                                                                        AlRates rates, const int64_t *__restrict__ p_off,
-                                                                        double *__restrict__ probes) {
-    const int q = blockIdx.y;
-    const int32_t m = qm[q];
-    if (gapc_slots(m) == 0) return;                                  // refused, or fewer than 4 values (block-uniform)
-    const int i = (int)blockIdx.x * kGapProbeBlock + (int)threadIdx.x;
-    if (i + 3 >= m) return;
-    const double rho = rates.r[blockIdx.z];                          // (a uniform index: scalar loads of the argument)
-    const double *s = sv + (q_offsets[q] - q_offsets[0]) + i;
-    const double s0 = al_scaled(s[0], rho), s1 = al_scaled(s[1], rho), s2 = al_scaled(s[2], rho), s3 = al_scaled(s[3], rho);
-    double a[3];
-    a[0] = floor((s1 - s0) / gap_eps);
-    a[1] = floor((s2 - s1) / gap_eps);
-    a[2] = floor((s3 - s2) / gap_eps);
-    double lo[3], hi[3];
-    const double place[3] = {1.0, tvz_gap::kBin1, tvz_gap::kBin2};
-    const double none = __longlong_as_double(0x7ff8000000000000LL);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const double b = a[j] + 1.0;
-        lo[j] = (a[j] >= 0.0 && a[j] <= tvz_gap::kMaxBin) ? a[j] * place[j] : none;
-        hi[j] = (b >= 0.0 && b <= tvz_gap::kMaxBin) ? b * place[j] : none;
-    }
-    const int64_t p = (int64_t)q * rates.n + blockIdx.z;
-    double2 *o = reinterpret_cast<double2 *>(probes + p_off[p] + (int64_t)tvz_gap::kVariants * i);
-#pragma unroll
-    for (int v = 0; v < tvz_gap::kVariants; v += 2) {
-        const double rest = ((v & 2) ? hi[1] : lo[1]) + ((v & 4) ? hi[2] : lo[2]);
-        o[v >> 1] = make_double2(lo[0] + rest, hi[0] + rest);
-    }
-}
+// ---- the fold of the call with a rate list (tvz_align_candidates_rates, include/tvz_gap_rates.h) --------------------
+// Behind the shared offsets, probes and lookup, query q has R hit lists, one per rate (list q R + i): per id the best
+// (count, smallest rate index), then the C best ids, the block and the total.
 
 // The words of the fold.  A count is at most kGaprMaxCount (a query has at most 4,095 probe slots), a rate index at
 // most 7, a video id at most 2^31 - 1: the three fit one 64-bit word, in two orders.  Both are ASCENDING orders for

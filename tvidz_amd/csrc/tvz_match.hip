@@ -2643,143 +2643,167 @@ int check_candidates_args(int32_t max_query_len, int32_t min_count, int32_t cap,
     return TVZ_OK;
 }
 
-// the lookup's own workspace: Q probe lists of up to max_probe_len slots, hit lists in the caller's (this call's) regions
-size_t candidates_match_bytes(int32_t Q, int32_t max_query_len) {
-    return ws_layout(nullptr, 0, Q, tvz_gap::max_probe_len(max_query_len), 0, 0, 1).total;
+// the lookup's own workspace: `lists` probe lists of up to max_probe_len slots, hit lists in the caller's (this call's) regions
+size_t candidates_match_bytes(int32_t lists, int32_t max_query_len) {
+    return ws_layout(nullptr, 0, lists, tvz_gap::max_probe_len(max_query_len), 0, 0, 1).total;
 }
-
-}  // namespace
-
-// `late`: what a sharded form still refuses behind all of the call's own refusals and in front of the first launch.
-// `gap_eps` (may be NULL): the width of the handle's codes, read under the handle's lock.  `enqueue` = false: the
-// refusals only (the _shards form asks every handle first).  `front`: the sharded form's blocks take that many bytes of
-// the caller's buffer in front of this call's part - workspace_bytes is the WHOLE buffer's size, d_workspace where this
-// call's part starts.
-struct CandidatesFront {
-    size_t bytes = 0;
-    const char *sizer = "tvz_align_candidates_workspace_bytes";
-};
-static int tvz_align_candidates_impl(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
-                                     int32_t max_query_len, int32_t min_count, const int32_t *d_exclude_ids, int32_t cap,
-                                     int32_t C, int32_t *d_out, void *d_workspace, size_t workspace_bytes, void *hip_stream,
-                                     LateCheck late = {}, double *gap_eps = nullptr, bool enqueue = true,
-                                     CandidatesFront front = {}) {
-    if (int rc = check_candidates_args(max_query_len, min_count, cap, C)) return rc;
-    const Batch b = align_batch(d_queries, d_q_offsets, Q, max_query_len, d_exclude_ids);
-    if (int rc = check_batch_args(c, b, cap)) return rc;
-    if (Q == 0) return TVZ_OK;
-    const size_t match_bytes = candidates_match_bytes(Q, max_query_len);
-    const size_t whole = d_workspace ? workspace_bytes : 0;
-    const size_t need = tvz_gap::ws_bytes(Q, cap, match_bytes, max_query_len);
-    if (whole < need + front.bytes)
-        return tvz::fail(TVZ_ERR_WORKSPACE, "alignment candidates: workspace of %zu bytes, %zu bytes missing (size it with %s)",
-                         whole, need + front.bytes - whole, front.sizer);
-    const size_t have = whole - front.bytes;
-    TVZ_REQUIRE(d_out != nullptr && (reinterpret_cast<uintptr_t>(d_out) & 7) == 0, "d_out is NULL or not 8-byte aligned");
-    const int64_t room = tvz_gap::ws_room(Q, cap, match_bytes, have);
-    const tvz_gap::WsRegions r = tvz_gap::ws_regions(Q, cap, match_bytes, room);
-    unsigned char *base = reinterpret_cast<unsigned char *>(al256(reinterpret_cast<uintptr_t>(d_workspace)));
-    int32_t *hits = reinterpret_cast<int32_t *>(base + r.hits), *hits_n = reinterpret_cast<int32_t *>(base + r.hits_n);
-    int64_t *p_off = reinterpret_cast<int64_t *>(base + r.p_off);
-    int32_t *qm = reinterpret_cast<int32_t *>(base + r.qm), *sp = reinterpret_cast<int32_t *>(base + r.sp);
-    double *sv = reinterpret_cast<double *>(base + r.sv), *probes = reinterpret_cast<double *>(base + r.probes);
-    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    DeviceGuard dg(c->device);
-    std::shared_lock<std::shared_mutex> lk(c->mu);            // parent, then (inside the lookup) child
-    if (!c->gap)
-        return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment candidates: this corpus keeps no gap codes (tvz_corpus_gap_index)");
-    if (gap_eps) *gap_eps = c->gap_eps;
-    if (int rc = late()) return rc;
-    if (!enqueue) return TVZ_OK;
-    // the sorted queries (hits_n = 0 meanwhile; the lookup writes every count)
-    hipLaunchKernelGGL(ts_tol_sort_kernel, dim3((unsigned)tvz::ceil_div(std::max(max_query_len, 1), kTolSortBlock), (unsigned)Q),
-                       dim3(kTolSortBlock), 0, st, d_queries, d_q_offsets, max_query_len, room, sv, sp, qm, hits_n);
-    TVZ_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ts_gapc_offsets_kernel, dim3(1), dim3(kGapOffBlock), 0, st, qm, Q, p_off);
-    TVZ_HIP(hipGetLastError());
-    if (max_query_len >= 4) {
-        hipLaunchKernelGGL(ts_gapc_probe_kernel, dim3((unsigned)tvz::ceil_div(max_query_len - 3, kGapProbeBlock), (unsigned)Q),
-                           dim3(kGapProbeBlock), 0, st, sv, d_q_offsets, qm, c->gap_eps, p_off, probes);
-        TVZ_HIP(hipGetLastError());
-    }
-    // count(q, r) is the exact match's count of the probes over the codes: the index, its delta table, the exclusions
-    if (int rc = tvz_match_impl(c->gap, probes, p_off, Q, tvz_gap::max_probe_len(max_query_len), min_count, d_exclude_ids, cap,
-                                hits, hits_n, base + r.match, match_bytes, TVZ_ALGO_AUTO, hip_stream))
-        return rc;
-    hipLaunchKernelGGL(ts_gapc_select_kernel, dim3((unsigned)Q), dim3(kBlock), 0, st, hits, hits_n, qm, cap, C, d_out);
-    TVZ_HIP(hipGetLastError());
-    return record(c, st);
-}
-
-// ---- the candidates at a list of rates (include/tvz_gap_rates.h) -------------------------------------------------
-namespace {
 
 constexpr int32_t kGaprMaxLists = 65535;      // probe lists of one lookup: Q * n_rates
 
-// what the rates call refuses before its workspace: the plain call's, the rate list, the probe lists
-int check_candidates_rates_args(int32_t Q, int32_t max_query_len, const double *h_rates, int32_t n_rates, int32_t min_count,
-                                int32_t cap, int32_t C, AlRates *rates) {
-    if (int rc = check_candidates_args(max_query_len, min_count, cap, C)) return rc;
-    if (int rc = check_align_rates(h_rates, n_rates, rates)) return rc;
-    if ((int64_t)Q * n_rates > kGaprMaxLists)
-        return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment candidates with rates: Q=%d x n_rates=%d is above %d probe lists", (int)Q,
-                         (int)n_rates, kGaprMaxLists);
-    return TVZ_OK;
+// What a form of the candidates call is, on the host: tvz_align_candidates and tvz_align_candidates_rates are one entry
+// each, and candidates_plan / candidates_enqueue below ask the entry, never which form they have.  The forms share the
+// sorted queries, the offsets, the probes and the lookup over Q * n_rates probe lists (the plain form: one list per
+// query at the rate 1.0); they differ in their last launch and in the row it writes.  A sharded form of the rates call
+// would be its exports and a merge - the front in the workspace is already a parameter of the plan.
+struct CandidatesPlan;
+struct CandidatesForm {
+    int cols;                        // int32 columns of a block row
+    int out_align;                   // bytes d_out must be aligned to: a row is one vector store
+    bool takes_rates;                // the call has a rate list, and with it a region for the lists' exclusion ids
+    const char *what, *sizer;        // the call in messages; the sizing function the workspace message names
+    void (*last)(const CandidatesPlan &);    // the launch behind the lookup
+};
+
+struct CandidatesCall {              // what a call asks, apart from its queries; h_rates, n_rates: NULL, 1 without a rate list
+    const double *h_rates;
+    int32_t n_rates, min_count, cap, C;
+    int32_t *d_out;
+};
+// The sharded form's blocks take `bytes` of the caller's buffer in front of the call's part - the plan is given the
+// WHOLE buffer's size and where the call's part starts - and a workspace refusal names `sizer` (NULL: the form's).
+struct CandidatesFront {
+    size_t bytes = 0;
+    const char *sizer = nullptr;
+};
+
+// Everything candidates_plan decided, for candidates_enqueue to launch from.  It holds the handle's lock (parent, then
+// - inside the lookup - child) from the plan's look at the handle to the end of the enqueue: a plan is made, enqueued
+// and dropped inside one call, one handle at a time.  Q = 0: nothing planned, nothing held, nothing to enqueue.
+struct CandidatesPlan {
+    const CandidatesForm *f = nullptr;
+    tvz_corpus *c = nullptr;
+    Batch b{};
+    CandidatesCall a{};
+    AlRates rates{};
+    int32_t lists = 0;               // Q * n_rates
+    size_t match_bytes = 0;
+    int64_t room = 0;
+    int32_t *hits = nullptr, *hits_n = nullptr, *excl = nullptr, *qm = nullptr, *sp = nullptr;
+    int64_t *p_off = nullptr;
+    double *sv = nullptr, *probes = nullptr;
+    unsigned char *match = nullptr;
+    double gap_eps = 0.0;            // the width of the handle's codes, read under its lock
+    void *hip_stream = nullptr;
+    std::optional<DeviceGuard> dg;   // (declared in front of the lock: the lock goes first)
+    std::shared_lock<std::shared_mutex> lk;
+    hipStream_t st() const { return reinterpret_cast<hipStream_t>(hip_stream); }
+};
+
+constexpr CandidatesForm kCandidatesPlain = {
+    2, 8, false, "alignment candidates", "tvz_align_candidates_workspace_bytes", [](const CandidatesPlan &p) {
+        hipLaunchKernelGGL(ts_gapc_select_kernel, dim3((unsigned)p.b.Q), dim3(kBlock), 0, p.st(), p.hits, p.hits_n, p.qm, p.a.cap,
+                           p.a.C, p.a.d_out);
+    }};
+constexpr CandidatesForm kCandidatesRates = {
+    3, 4, true, "alignment candidates with rates", "tvz_align_candidates_rates_workspace_bytes", [](const CandidatesPlan &p) {
+        hipLaunchKernelGGL(ts_gapr_fold_kernel, dim3((unsigned)p.b.Q), dim3(kBlock), 0, p.st(), p.hits, p.hits_n, p.qm, p.rates.n,
+                           p.a.cap, p.a.C, p.a.d_out);
+    }};
+
+// Everything in front of the first launch: the refusals in the headers' order, the carving of `ws` (the call's part of
+// the caller's buffer; ws.bytes: the whole buffer's, `front` included), the handle's lock and what is read under it.
+// `late`: what a sharded form still refuses behind all of the call's own refusals.
+int candidates_plan(const CandidatesForm &f, tvz_corpus *c, const Batch &b, const CandidatesCall &a, Workspace ws,
+                    void *hip_stream, LateCheck late, CandidatesFront front, CandidatesPlan &p) {
+    if (int rc = check_candidates_args(b.max_query_len, a.min_count, a.cap, a.C)) return rc;
+    p.rates = AlRates{{1.0}, 1};
+    if (f.takes_rates) {
+        if (int rc = check_align_rates(a.h_rates, a.n_rates, &p.rates)) return rc;
+        if ((int64_t)b.Q * a.n_rates > kGaprMaxLists)
+            return tvz::fail(TVZ_ERR_UNSUPPORTED, "%s: Q=%d x n_rates=%d is above %d probe lists", f.what, (int)b.Q, (int)a.n_rates,
+                             kGaprMaxLists);
+    }
+    if (int rc = check_batch_args(c, b, a.cap)) return rc;
+    p.f = &f, p.c = c, p.b = b, p.a = a, p.hip_stream = hip_stream;
+    if (b.Q == 0) return TVZ_OK;
+    const int32_t R = p.rates.n;
+    p.lists = b.Q * R;
+    p.match_bytes = candidates_match_bytes(p.lists, b.max_query_len);
+    const size_t whole = ws.p ? ws.bytes : 0;
+    const size_t need = tvz_gap::ws_bytes(b.Q, R, f.takes_rates, a.cap, p.match_bytes, b.max_query_len) + front.bytes;
+    if (whole < need)
+        return tvz::fail(TVZ_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu bytes missing (size it with %s)", f.what, whole,
+                         need - whole, front.sizer ? front.sizer : f.sizer);
+    TVZ_REQUIRE(a.d_out != nullptr && (reinterpret_cast<uintptr_t>(a.d_out) & (uintptr_t)(f.out_align - 1)) == 0,
+                "d_out is NULL or not %d-byte aligned", f.out_align);
+    p.room = tvz_gap::ws_room(b.Q, R, f.takes_rates, a.cap, p.match_bytes, whole - front.bytes);
+    const tvz_gap::WsRegions r = tvz_gap::ws_regions(b.Q, R, f.takes_rates, a.cap, p.match_bytes, p.room);
+    unsigned char *base = reinterpret_cast<unsigned char *>(al256(reinterpret_cast<uintptr_t>(ws.p)));
+    p.hits = reinterpret_cast<int32_t *>(base + r.hits), p.hits_n = reinterpret_cast<int32_t *>(base + r.hits_n);
+    p.p_off = reinterpret_cast<int64_t *>(base + r.p_off);
+    // (the lists' exclusion ids: a form with several lists per query has the region, a call with exclusions uses it)
+    p.excl = f.takes_rates && b.d_exclude_ids ? reinterpret_cast<int32_t *>(base + r.excl) : nullptr;
+    p.match = base + r.match;
+    p.qm = reinterpret_cast<int32_t *>(base + r.qm), p.sp = reinterpret_cast<int32_t *>(base + r.sp);
+    p.sv = reinterpret_cast<double *>(base + r.sv), p.probes = reinterpret_cast<double *>(base + r.probes);
+    p.dg.emplace(c->device);
+    p.lk = std::shared_lock<std::shared_mutex>(c->mu);        // parent, then (inside the lookup) child
+    if (!c->gap)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment candidates: this corpus keeps no gap codes (tvz_corpus_gap_index)");
+    p.gap_eps = c->gap_eps;
+    return late();
+}
+
+// The launches of a plan: the sort, the offsets, the probes, ONE lookup over the probe lists, the form's last launch.
+int candidates_enqueue(const CandidatesPlan &p) {
+    const Batch &b = p.b;
+    if (b.Q == 0) return TVZ_OK;
+    hipStream_t st = p.st();
+    // the sorted queries, once for all rates (it zeroes the first Q counts; the lookup writes every one of the lists')
+    hipLaunchKernelGGL(ts_tol_sort_kernel, dim3((unsigned)tvz::ceil_div(std::max(b.max_query_len, 1), kTolSortBlock), (unsigned)b.Q),
+                       dim3(kTolSortBlock), 0, st, b.d_queries, b.d_q_offsets, b.max_query_len, p.room, p.sv, p.sp, p.qm, p.hits_n);
+    TVZ_HIP(hipGetLastError());
+    hipLaunchKernelGGL(ts_gapc_offsets_kernel, dim3(1), dim3(kGapOffBlock), 0, st, p.qm, b.Q, p.rates.n, b.d_exclude_ids, p.p_off,
+                       p.excl);
+    TVZ_HIP(hipGetLastError());
+    if (b.max_query_len >= 4) {
+        hipLaunchKernelGGL(ts_gapc_probe_kernel,
+                           dim3((unsigned)tvz::ceil_div(b.max_query_len - 3, kGapProbeBlock), (unsigned)b.Q, (unsigned)p.rates.n),
+                           dim3(kGapProbeBlock), 0, st, p.sv, b.d_q_offsets, p.qm, p.gap_eps, p.rates, p.p_off, p.probes);
+        TVZ_HIP(hipGetLastError());
+    }
+    // count_i(q, r) is the exact match's count of list q R + i over the codes: the index, its delta table, the
+    // exclusions - one id per list, the caller's own where the lists are the queries
+    if (int rc = tvz_match_impl(p.c->gap, p.probes, p.p_off, p.lists, tvz_gap::max_probe_len(b.max_query_len), p.a.min_count,
+                                p.excl ? p.excl : b.d_exclude_ids, p.a.cap, p.hits, p.hits_n, p.match, p.match_bytes,
+                                TVZ_ALGO_AUTO, p.hip_stream))
+        return rc;
+    p.f->last(p);
+    TVZ_HIP(hipGetLastError());
+    return record(p.c, st);
+}
+
+// a call of the C ABI: its plan, enqueued
+int candidates_call(const CandidatesForm &f, tvz_corpus *c, const Batch &b, const CandidatesCall &a, Workspace ws, void *hip_stream,
+                    LateCheck late = {}, CandidatesFront front = {}) {
+    CandidatesPlan p;
+    if (int rc = candidates_plan(f, c, b, a, ws, hip_stream, late, front, p)) return rc;
+    return candidates_enqueue(p);
+}
+
+// What the sizing exports share: the argument refusals, the `keys` default and the room for one longest query.
+size_t candidates_sizing(const CandidatesForm &f, int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t n_rates,
+                         int32_t cap, int32_t C) {
+    if (Q < 0 || Q > 65535 || max_query_len < 0 || max_query_len > kAlMaxLen || total_query_keys < 0 || C < 1 ||
+        C > tvz_gap::kMaxC || cap < C)
+        return 0;
+    if (f.takes_rates && (n_rates < 1 || n_rates > kArMaxRates || (int64_t)Q * n_rates > kGaprMaxLists)) return 0;
+    const int64_t keys = total_query_keys > 0 ? total_query_keys : (int64_t)Q * max_query_len;
+    return tvz_gap::ws_bytes(Q, n_rates, f.takes_rates, cap, candidates_match_bytes(Q * n_rates, max_query_len),
+                             std::max<int64_t>(keys, max_query_len));
 }
 
 }  // namespace
-
-static int tvz_align_candidates_rates_impl(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
-                                           int32_t max_query_len, const double *h_rates, int32_t n_rates, int32_t min_count,
-                                           const int32_t *d_exclude_ids, int32_t cap, int32_t C, int32_t *d_out,
-                                           void *d_workspace, size_t workspace_bytes, void *hip_stream) {
-    AlRates rates;
-    if (int rc = check_candidates_rates_args(Q, max_query_len, h_rates, n_rates, min_count, cap, C, &rates)) return rc;
-    const Batch b = align_batch(d_queries, d_q_offsets, Q, max_query_len, d_exclude_ids);
-    if (int rc = check_batch_args(c, b, cap)) return rc;
-    if (Q == 0) return TVZ_OK;
-    const int32_t lists = Q * n_rates;
-    const size_t match_bytes = candidates_match_bytes(lists, max_query_len);
-    const size_t have = d_workspace ? workspace_bytes : 0;
-    const size_t need = tvz_gap::ws_rates_bytes(Q, n_rates, cap, match_bytes, max_query_len);
-    if (have < need)
-        return tvz::fail(TVZ_ERR_WORKSPACE, "alignment candidates with rates: workspace of %zu bytes, %zu bytes missing (size it "
-                                            "with tvz_align_candidates_rates_workspace_bytes)", have, need - have);
-    TVZ_REQUIRE(d_out != nullptr && (reinterpret_cast<uintptr_t>(d_out) & 3) == 0, "d_out is NULL or not 4-byte aligned");
-    const int64_t room = tvz_gap::ws_rates_room(Q, n_rates, cap, match_bytes, have);
-    const tvz_gap::RateWsRegions r = tvz_gap::ws_rates_regions(Q, n_rates, cap, match_bytes, room);
-    unsigned char *base = reinterpret_cast<unsigned char *>(al256(reinterpret_cast<uintptr_t>(d_workspace)));
-    int32_t *hits = reinterpret_cast<int32_t *>(base + r.hits), *hits_n = reinterpret_cast<int32_t *>(base + r.hits_n);
-    int64_t *p_off = reinterpret_cast<int64_t *>(base + r.p_off);
-    int32_t *excl = reinterpret_cast<int32_t *>(base + r.excl);
-    int32_t *qm = reinterpret_cast<int32_t *>(base + r.qm), *sp = reinterpret_cast<int32_t *>(base + r.sp);
-    double *sv = reinterpret_cast<double *>(base + r.sv), *probes = reinterpret_cast<double *>(base + r.probes);
-    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    DeviceGuard dg(c->device);
-    std::shared_lock<std::shared_mutex> lk(c->mu);            // parent, then (inside the lookup) child
-    if (!c->gap)
-        return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment candidates: this corpus keeps no gap codes (tvz_corpus_gap_index)");
-    // the sorted queries, once for all rates (it zeroes the first Q counts; the lookup writes every one of the Q R)
-    hipLaunchKernelGGL(ts_tol_sort_kernel, dim3((unsigned)tvz::ceil_div(std::max(max_query_len, 1), kTolSortBlock), (unsigned)Q),
-                       dim3(kTolSortBlock), 0, st, d_queries, d_q_offsets, max_query_len, room, sv, sp, qm, hits_n);
-    TVZ_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ts_gapr_offsets_kernel, dim3(1), dim3(kGapOffBlock), 0, st, qm, Q, n_rates, d_exclude_ids, p_off, excl);
-    TVZ_HIP(hipGetLastError());
-    if (max_query_len >= 4) {
-        hipLaunchKernelGGL(ts_gapr_probe_kernel,
-                           dim3((unsigned)tvz::ceil_div(max_query_len - 3, kGapProbeBlock), (unsigned)Q, (unsigned)n_rates),
-                           dim3(kGapProbeBlock), 0, st, sv, d_q_offsets, qm, c->gap_eps, rates, p_off, probes);
-        TVZ_HIP(hipGetLastError());
-    }
-    // ONE lookup over the Q R probe lists: count_i(q, r) is the exact match's count of list q R + i over the codes
-    if (int rc = tvz_match_impl(c->gap, probes, p_off, lists, tvz_gap::max_probe_len(max_query_len), min_count,
-                                d_exclude_ids ? excl : nullptr, cap, hits, hits_n, base + r.match, match_bytes, TVZ_ALGO_AUTO,
-                                hip_stream))
-        return rc;
-    hipLaunchKernelGGL(ts_gapr_fold_kernel, dim3((unsigned)Q), dim3(kBlock), 0, st, hits, hits_n, qm, n_rates, cap, C, d_out);
-    TVZ_HIP(hipGetLastError());
-    return record(c, st);
-}
 
 // ---- the candidates over a sharded table (include/tvz_gap_shards.h) ---------------------------------------------
 namespace {
@@ -2828,9 +2852,8 @@ int tvz_align_candidates_local(tvz_corpus *c, const Batch &b, int32_t min_count,
     // the call judges the WHOLE buffer's size, front included, and lays its own part out from s.plain on
     const CandidatesFront front{carve ? tvz_gap::ws_shard_front_bytes(b.Q, C, n_ranks) : 0,
                                 "tvz_align_candidates_sharded_workspace_bytes"};
-    return tvz_align_candidates_impl(c, b.d_queries, b.d_q_offsets, b.Q, b.max_query_len, min_count, b.d_exclude_ids, cap, C,
-                                     local, carve ? reinterpret_cast<void *>(s.plain) : nullptr, ws.bytes, hip_stream, late,
-                                     nullptr, true, front);
+    return candidates_call(kCandidatesPlain, c, b, CandidatesCall{nullptr, 1, min_count, cap, C, local},
+                           Workspace{carve ? reinterpret_cast<void *>(s.plain) : nullptr, ws.bytes}, hip_stream, late, front);
 }
 
 size_t tvz_align_candidates_sharded_sizing(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t cap, int32_t C,
@@ -2859,25 +2882,24 @@ static int align_candidates_shards_impl(tvz_corpus *const *shards, int32_t n_sha
         const uintptr_t g0 = reinterpret_cast<uintptr_t>(d_blocks), o0 = reinterpret_cast<uintptr_t>(d_out);
         TVZ_REQUIRE(o0 + block <= g0 || g0 + (size_t)n_shards * block <= o0, "alignment candidates merge: d_out lies inside the blocks");
     }
-    // every handle's refusals first - the arguments' are the same for all, the handle's own (no gap codes) are not -
-    // and the widths compared: nothing is enqueued before all of them agree
+    const Batch b = align_batch(d_queries, d_q_offsets, Q, max_query_len, d_exclude_ids);
+    const Workspace ws{d_workspace, workspace_bytes};
+    auto call_of = [&](int32_t r) { return CandidatesCall{nullptr, 1, min_count, cap, C, d_blocks + (size_t)r * (block / sizeof(int32_t))}; };
+    // Every handle is planned first - the arguments' refusals are the same for all, the handle's own (no gap codes) are
+    // not - and the widths compared: nothing is enqueued before all of them agree.  A plan holds its handle's lock, and
+    // the locks are taken one handle at a time (the shards may name a handle twice, and two callers may name them in
+    // different orders), so these plans are dropped again and every shard is planned anew where it is enqueued.
     double eps0 = 0.0;
     for (int32_t r = 0; r < n_shards; ++r) {
-        double eps = 0.0;
-        if (int rc = tvz_align_candidates_impl(shards[r], d_queries, d_q_offsets, Q, max_query_len, min_count, d_exclude_ids, cap, C,
-                                               d_blocks + (size_t)r * (block / sizeof(int32_t)), d_workspace, workspace_bytes,
-                                               hip_stream, {}, &eps, /* enqueue */ false))
-            return rc;
-        if (r == 0) eps0 = eps;
-        if (eps != eps0)
+        CandidatesPlan p;
+        if (int rc = candidates_plan(kCandidatesPlain, shards[r], b, call_of(r), ws, hip_stream, {}, {}, p)) return rc;
+        if (r == 0) eps0 = p.gap_eps;
+        if (p.gap_eps != eps0)
             return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment candidates: shard %d keeps gap codes of gap_eps=%.17g, shard 0 of %.17g",
-                             (int)r, eps, eps0);
+                             (int)r, p.gap_eps, eps0);
     }
     for (int32_t r = 0; r < n_shards; ++r)
-        if (int rc = tvz_align_candidates_impl(shards[r], d_queries, d_q_offsets, Q, max_query_len, min_count, d_exclude_ids, cap, C,
-                                               d_blocks + (size_t)r * (block / sizeof(int32_t)), d_workspace, workspace_bytes,
-                                               hip_stream))
-            return rc;
+        if (int rc = candidates_call(kCandidatesPlain, shards[r], b, call_of(r), ws, hip_stream)) return rc;
     DeviceGuard dg(shards[0]->device);
     return tvz_align_candidates_merge_local(d_blocks, n_shards, Q, C, d_out, hip_stream);
 }
@@ -2910,36 +2932,29 @@ TVZ_EXPORT int tvz_corpus_gap_index_stats(tvz_corpus *c, double *gap_eps, int64_
 
 TVZ_EXPORT size_t tvz_align_candidates_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t cap,
                                                        int32_t C) {
-    if (Q < 0 || Q > 65535 || max_query_len < 0 || max_query_len > kAlMaxLen || total_query_keys < 0 || C < 1 ||
-        C > tvz_gap::kMaxC || cap < C)
-        return 0;
-    const int64_t keys = total_query_keys > 0 ? total_query_keys : (int64_t)Q * max_query_len;
-    return tvz_gap::ws_bytes(Q, cap, candidates_match_bytes(Q, max_query_len), std::max<int64_t>(keys, max_query_len));
+    return candidates_sizing(kCandidatesPlain, Q, max_query_len, total_query_keys, 1, cap, C);
 }
 
 TVZ_EXPORT int tvz_align_candidates(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
                                     int32_t max_query_len, int32_t min_count, const int32_t *d_exclude_ids, int32_t cap, int32_t C,
                                     int32_t *d_out, void *d_workspace, size_t workspace_bytes, void *hip_stream) {
-    TVZ_GUARDED(tvz_align_candidates_impl(c, d_queries, d_q_offsets, Q, max_query_len, min_count, d_exclude_ids, cap, C, d_out,
-                                          d_workspace, workspace_bytes, hip_stream));
+    TVZ_GUARDED(candidates_call(kCandidatesPlain, c, align_batch(d_queries, d_q_offsets, Q, max_query_len, d_exclude_ids),
+                                CandidatesCall{nullptr, 1, min_count, cap, C, d_out}, Workspace{d_workspace, workspace_bytes},
+                                hip_stream));
 }
 
 TVZ_EXPORT size_t tvz_align_candidates_rates_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys,
                                                              int32_t n_rates, int32_t cap, int32_t C) {
-    if (Q < 0 || Q > 65535 || max_query_len < 0 || max_query_len > kAlMaxLen || total_query_keys < 0 || C < 1 ||
-        C > tvz_gap::kMaxC || cap < C || n_rates < 1 || n_rates > kArMaxRates || (int64_t)Q * n_rates > kGaprMaxLists)
-        return 0;
-    const int64_t keys = total_query_keys > 0 ? total_query_keys : (int64_t)Q * max_query_len;
-    return tvz_gap::ws_rates_bytes(Q, n_rates, cap, candidates_match_bytes(Q * n_rates, max_query_len),
-                                   std::max<int64_t>(keys, max_query_len));
+    return candidates_sizing(kCandidatesRates, Q, max_query_len, total_query_keys, n_rates, cap, C);
 }
 
 TVZ_EXPORT int tvz_align_candidates_rates(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
                                           int32_t max_query_len, const double *h_rates, int32_t n_rates, int32_t min_count,
                                           const int32_t *d_exclude_ids, int32_t cap, int32_t C, int32_t *d_out,
                                           void *d_workspace, size_t workspace_bytes, void *hip_stream) {
-    TVZ_GUARDED(tvz_align_candidates_rates_impl(c, d_queries, d_q_offsets, Q, max_query_len, h_rates, n_rates, min_count,
-                                                d_exclude_ids, cap, C, d_out, d_workspace, workspace_bytes, hip_stream));
+    TVZ_GUARDED(candidates_call(kCandidatesRates, c, align_batch(d_queries, d_q_offsets, Q, max_query_len, d_exclude_ids),
+                                CandidatesCall{h_rates, n_rates, min_count, cap, C, d_out}, Workspace{d_workspace, workspace_bytes},
+                                hip_stream));
 }
 
 #ifdef TVZ_IX_STAMP
