@@ -165,6 +165,17 @@ GAP_RATE_SIGNATURES = {
                                              C.c_int32, _P, _P, C.c_size_t, _P]),
 }
 
+# name -> (restype, argtypes); mirrors include/tvz_gap_rates_shards.h one to one (the rates call over a sharded table)
+GAP_RATE_SHARD_SIGNATURES = {
+    "tvz_align_candidates_rates_merge": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "tvz_align_candidates_rates_shards": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P,
+                                                    C.c_int32, C.c_int32, _P, _P, _P, C.c_size_t, _P]),
+    "tvz_align_candidates_rates_sharded_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                                                        C.c_int32, C.c_int32]),
+    "tvz_align_candidates_rates_sharded": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P,
+                                                     C.c_int32, C.c_int32, _P, _P, C.c_size_t, _P]),
+}
+
 # per-call selectors of include/tvz.h
 ALGO_AUTO, ALGO_Q1, ALGO_TILE, ALGO_JOIN, ALGO_INDEX = 0, 1, 2, 3, 4
 ALGO_PAIR, ALGO_NO_PAIR = 0x100, 0x200      # OR-ed into `algo` of the top-k calls: two queries per lookup block always / never
@@ -224,7 +235,8 @@ def load() -> C.CDLL:
                 raise RuntimeError(f"{SO_PATH} is version {lib.tvz_version()}, this binding expects {VERSION}: "
                                    "rebuild it (python -m tvidz_amd.build --force)")
             for name, (res, args) in (list(SIGNATURES.items()) + list(GAP_SIGNATURES.items()) +
-                                      list(GAP_SHARD_SIGNATURES.items()) + list(GAP_RATE_SIGNATURES.items())):
+                                      list(GAP_SHARD_SIGNATURES.items()) + list(GAP_RATE_SIGNATURES.items()) +
+                                      list(GAP_RATE_SHARD_SIGNATURES.items())):
                 fn = getattr(lib, name)
                 fn.restype = res
                 fn.argtypes = args

@@ -365,6 +365,93 @@ def align_candidates_shards(shards: Sequence["DeviceCorpus"], d_queries: torch.T
     return blocks, merged
 
 
+ALIGN_CANDIDATES_RATES_MERGE_MAX_LISTS = 16          # include/tvz_gap_rates_shards.h TVZ_GAP_RATES_MERGE_MAX_LISTS
+
+
+def align_candidates_rates_sharded_workspace_bytes(Q: int, max_query_len: int, total_query_keys: int = 0, n_rates: int = 1,
+                                                   cap: int = 4096, c: int = 16, n_ranks: int = 1) -> int:
+    """tvz_align_candidates_rates_sharded_workspace_bytes: align_candidates_rates_workspace_bytes + the rank's own block
+    and `n_ranks` gathered ones (Q x (c + 1) x 12 bytes each)."""
+    return int(_lib.load().tvz_align_candidates_rates_sharded_workspace_bytes(
+        int(Q), int(max_query_len), int(total_query_keys), int(n_rates), int(cap), int(c), int(n_ranks)))
+
+
+def align_candidates_rates_merge(blocks: np.ndarray) -> np.ndarray:
+    """The blocks of R shards to one align_candidates_rates call, on the host: int32 [R, Q, c + 1, 3] -> int32 [Q, c + 1,
+    3] (include/tvz_gap_rates_shards.h, THE MERGE).  Per query every row with video_id >= 0 takes part; per id the
+    largest best and the smallest rate index that reaches it - an id appears ONCE; the c largest by (best descending,
+    video_id ascending) are kept and padded with (-1, 0, 0); the last row is (-1, total, 0) by align_candidates_merge's
+    totals rule.  The lists need not be sorted.  Any R: the rule is associative."""
+    blocks = np.asarray(blocks, dtype=np.int32)
+    R, Q, c1, _ = blocks.shape
+    c = c1 - 1
+    out = np.zeros((Q, c1, 3), dtype=np.int32)
+    out[:, :, 0] = -1
+    rows = blocks[:, :, :c].transpose(1, 0, 2, 3).reshape(Q, R * c, 3).astype(np.int64)
+    # by id: id ascending, best descending, rate ascending - the first row of an id is the one that stays
+    pad = np.int64((1 << 63) - 1)                             # above every word (an id is below 2^31)
+    by_id = np.where(rows[:, :, 0] >= 0, (rows[:, :, 0] << 32) | ((4095 - rows[:, :, 1]) << 4) | rows[:, :, 2], pad)
+    by_id = np.sort(by_id, axis=1)
+    first = np.ones_like(by_id, dtype=bool)
+    first[:, 1:] = (by_id[:, 1:] >> 32) != (by_id[:, :-1] >> 32)
+    live = first & (by_id != pad)
+    # by output: best descending, id ascending
+    word = np.where(live, (((by_id >> 4) & 4095) << 35) | ((by_id >> 32) << 4) | (by_id & 15), pad)
+    word = np.sort(word, axis=1)[:, :c]
+    keep = word != pad
+    n = word.shape[1]
+    out[:, :n, 0] = np.where(keep, (word >> 4) & 0x7fffffff, -1)
+    out[:, :n, 1] = np.where(keep, 4095 - (word >> 35), 0)
+    out[:, :n, 2] = np.where(keep, word & 15, 0)
+    t = blocks[:, :, c, 1].astype(np.int64)
+    total = np.minimum(np.abs(t).sum(0), (1 << 31) - 1)
+    total = np.where((t < 0).any(0), np.where(total == 0, ALIGN_CANDIDATES_REFUSED, -total), total)
+    refused = (t == ALIGN_CANDIDATES_REFUSED).any(0)
+    out[refused, :c] = (-1, 0, 0)
+    out[:, c, 1] = np.where(refused, ALIGN_CANDIDATES_REFUSED, total).astype(np.int32)
+    return out
+
+
+def align_candidates_rates_merge_device(gathered: torch.Tensor, stream: Optional[torch.cuda.Stream] = None,
+                                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """tvz_align_candidates_rates_merge: align_candidates_rates_merge on the device - the blocks of R <= 16 shards to one
+    align_candidates_rates call, int32 [R, Q, c + 1, 3] -> int32 [Q, c + 1, 3], one launch on `stream` (default: the
+    current one)."""
+    if gathered.dim() != 4 or gathered.shape[3] != 3 or gathered.dtype != torch.int32 or gathered.device.type != "cuda" \
+            or not gathered.is_contiguous():
+        raise RuntimeError("gathered must be a contiguous int32 CUDA tensor [R, Q, c + 1, 3]")
+    R, Q, c1, _ = gathered.shape
+    out = _out(out, (Q, c1, 3), gathered.device)
+    s = stream if stream is not None else torch.cuda.current_stream(gathered.device)
+    with torch.cuda.device(gathered.device):
+        _lib.check(_lib.load().tvz_align_candidates_rates_merge(gathered.data_ptr() if gathered.numel() else None, R, Q, c1 - 1,
+                                                                out.data_ptr() if out.numel() else None, s.cuda_stream))
+    return out
+
+
+def align_candidates_rates_shards(shards: Sequence["DeviceCorpus"], d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
+                                  max_query_len: int, rates: Sequence[float], *, c: int, min_count: int = 2, cap: int = 4096,
+                                  d_exclude_ids: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                                  stream: Optional[torch.cuda.Stream] = None):
+    """tvz_align_candidates_rates on every handle of ONE device + the merge behind one library call
+    (tvz_align_candidates_rates_shards): -> (blocks int32 [R, Q, c + 1, 3], merged int32 [Q, c + 1, 3]).  `workspace`:
+    align_candidates_rates_workspace_bytes, one handle's, serves all of them."""
+    Q = d_q_offsets.numel() - 1
+    h_rates, n_rates = _rates(rates)
+    dev, s, ws, excl = shards[0]._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace,
+                                          align_candidates_rates_workspace_bytes(Q, max_query_len, d_queries.numel(), n_rates,
+                                                                                 cap, c))
+    R = len(shards)
+    handles = (C.c_void_p * R)(*[sh._h for sh in shards])
+    blocks = torch.empty((R, Q, max(int(c), 0) + 1, 3), dtype=torch.int32, device=dev)
+    merged = torch.empty((Q, max(int(c), 0) + 1, 3), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().tvz_align_candidates_rates_shards(
+            handles, R, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), h_rates, n_rates, int(min_count),
+            excl, int(cap), int(c), blocks.data_ptr(), merged.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
+    return blocks, merged
+
+
 def align_parts_ids(video_ids, Q: int, dev) -> torch.Tensor:
     """The ids of tvz_align_parts as a 2-D int32 tensor [Q, k] on `dev`: a device tensor (any strides) as it is, host
     lists or arrays copied once."""
@@ -1078,6 +1165,25 @@ class Comm:
         _lib.check(self.lib.tvz_align_candidates_sharded(
             corpus._h, self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), int(min_count), excl,
             int(cap), int(c), out.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
+        return out
+
+    def align_candidates_rates_sharded(self, corpus: DeviceCorpus, d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
+                                       max_query_len: int, rates: Sequence[float], *, c: int, min_count: int = 2,
+                                       cap: int = 4096, d_exclude_ids: Optional[torch.Tensor] = None,
+                                       workspace: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
+                                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """tvz_align_candidates_rates_sharded: the local align_candidates_rates -> ncclAllGather of the [Q, c + 1, 3]
+        blocks -> the merge; -> int32 [Q, c + 1, 3], identical on every rank.  Every rank's handle keeps gap codes of one
+        gap_eps, and every rank passes the same `rates`."""
+        Q = d_q_offsets.numel() - 1
+        h_rates, n_rates = _rates(rates)
+        dev, s, ws, excl = corpus._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace,
+                                           align_candidates_rates_sharded_workspace_bytes(Q, max_query_len, d_queries.numel(),
+                                                                                          n_rates, cap, c, self.n_ranks))
+        out = _out(out, (Q, max(int(c), 0) + 1, 3), dev)
+        _lib.check(self.lib.tvz_align_candidates_rates_sharded(
+            corpus._h, self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), h_rates, n_rates,
+            int(min_count), excl, int(cap), int(c), out.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
         return out
 
     def align_sharded(self, f: AlignForm, corpus, d_queries, d_q_offsets, max_query_len, k, d_exclude_ids, workspace, stream,

@@ -16,6 +16,7 @@
 
 #include "tvz_common.h"
 #include "tvz_gap_shards.h"
+#include "tvz_gap_rates_shards.h"
 
 namespace {
 
@@ -274,14 +275,16 @@ struct CandidatesCommCheck {
     const tvz_comm *comm;
     int32_t Q;
     const int32_t *d_out;
+    int out_align = 8;                              // bytes of a row's vector store: 8, the rates form 4
+    const char *what = "alignment candidates";      // the call in the message
 };
 static int check_candidates_comm(const void *ctx) {
     const CandidatesCommCheck &s = *static_cast<const CandidatesCommCheck *>(ctx);
     TVZ_REQUIRE(s.comm != nullptr && s.comm->comm != nullptr, "communicator is NULL");
-    TVZ_REQUIRE(s.Q <= 0 || (s.d_out != nullptr && (reinterpret_cast<uintptr_t>(s.d_out) & 7) == 0),
-                "d_out is NULL or not 8-byte aligned");
+    TVZ_REQUIRE(s.Q <= 0 || (s.d_out != nullptr && (reinterpret_cast<uintptr_t>(s.d_out) & (uintptr_t)(s.out_align - 1)) == 0),
+                "d_out is NULL or not %d-byte aligned", s.out_align);
     if (s.comm->n_ranks > 16)        // (the merge's limit: refused before the local call enqueues anything)
-        return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment candidates: %d ranks, the merge takes up to 16", (int)s.comm->n_ranks);
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "%s: %d ranks, the merge takes up to 16", s.what, (int)s.comm->n_ranks);
     return TVZ_OK;
 }
 
@@ -309,6 +312,37 @@ TVZ_EXPORT int tvz_align_candidates_sharded(tvz_corpus *c, tvz_comm *comm, const
     TVZ_GUARDED(align_candidates_sharded_impl(c, comm, Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0,
                                                               d_exclude_ids},
                                               min_count, cap, C, d_out, Workspace{d_workspace, workspace_bytes}, hip_stream));
+}
+
+// tvz_align_candidates_rates_sharded (include/tvz_gap_rates_shards.h): the same with the rates call and rows of 3 -
+// ONE all-gather of Q x (C + 1) x 3 int32, the block-per-query merge.
+static int align_candidates_rates_sharded_impl(tvz_corpus *c, tvz_comm *comm, const Batch &b, const double *h_rates,
+                                               int32_t n_rates, int32_t min_count, int32_t cap, int32_t C, int32_t *d_out,
+                                               Workspace ws, void *hip_stream) {
+    const int32_t Q = b.Q;
+    const CandidatesCommCheck chk{comm, Q, d_out, 4, "alignment candidates with rates"};
+    // (a NULL communicator is sized as one rank until it is refused)
+    const int32_t n_ranks = comm ? std::max<int32_t>(comm->n_ranks, 1) : 1;
+    ShardBlocks blk;
+    if (int rc = tvz_align_candidates_rates_local(c, b, h_rates, n_rates, min_count, cap, C, ws, n_ranks, hip_stream, &blk,
+                                                  LateCheck{check_candidates_comm, &chk}))
+        return rc;
+    if (int rc = check_candidates_comm(&chk)) return rc;   // (Q = 0: the local call returned in front of its late checks)
+    if (Q == 0) return TVZ_OK;
+    return gather_and_merge(comm, blk.local, blk.gathered, (size_t)Q * (size_t)(C + 1) * 3, hip_stream, [&] {
+        return tvz_align_candidates_rates_merge_local(blk.gathered, comm->n_ranks, Q, C, d_out, hip_stream);
+    });
+}
+
+TVZ_EXPORT int tvz_align_candidates_rates_sharded(tvz_corpus *c, tvz_comm *comm, const double *d_queries,
+                                                  const int64_t *d_q_offsets, int32_t Q, int32_t max_query_len,
+                                                  const double *h_rates, int32_t n_rates, int32_t min_count,
+                                                  const int32_t *d_exclude_ids, int32_t cap, int32_t C, int32_t *d_out,
+                                                  void *d_workspace, size_t workspace_bytes, void *hip_stream) {
+    TVZ_GUARDED(align_candidates_rates_sharded_impl(c, comm, Batch{d_queries, d_q_offsets, Q, max_query_len, /* min_match: none */ 0,
+                                                                    d_exclude_ids},
+                                                    h_rates, n_rates, min_count, cap, C, d_out,
+                                                    Workspace{d_workspace, workspace_bytes}, hip_stream));
 }
 
 TVZ_EXPORT int tvz_comm_unique_id(void *out_id) { TVZ_GUARDED(tvz_comm_unique_id_impl(out_id)); }

@@ -134,3 +134,9 @@ int tvz_align_candidates_local(tvz_corpus *c, const Batch &b, int32_t min_count,
                                int32_t n_ranks, void *hip_stream, ShardBlocks *blocks, LateCheck late = {});
 int tvz_align_candidates_merge_local(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t C, int32_t *d_out,
                                      void *hip_stream);
+// The same two for tvz_align_candidates_rates (blocks of rows of 3; include/tvz_gap_rates_shards.h).
+int tvz_align_candidates_rates_local(tvz_corpus *c, const Batch &b, const double *h_rates, int32_t n_rates, int32_t min_count,
+                                     int32_t cap, int32_t C, Workspace ws, int32_t n_ranks, void *hip_stream, ShardBlocks *blocks,
+                                     LateCheck late = {});
+int tvz_align_candidates_rates_merge_local(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t C, int32_t *d_out,
+                                           void *hip_stream);

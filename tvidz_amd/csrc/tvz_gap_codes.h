@@ -117,22 +117,25 @@ inline int64_t ws_room(int32_t Q, int32_t R, bool with_excl, int32_t cap, size_t
 // ---- the workspace of tvz_align_candidates_sharded ----
 // In front, behind a base aligned up to 256: the rank's own block int32[Q][C + 1][2] and the gathered ones
 // int32[max(n_ranks, 1)][Q][C + 1][2]; behind them, from `plain` on (a multiple of 256 from the aligned base, so that
-// its own alignment costs nothing), the whole workspace of the plain call.
+// its own alignment costs nothing), the whole workspace of the plain call.  `cols` = 3: the same front with the rows of
+// tvz_align_candidates_rates_sharded (include/tvz_gap_rates_shards.h), the rates call's workspace behind it.
 struct ShardWsRegions {              // byte offsets from the aligned base
     size_t local, gathered, plain;
 };
-inline size_t block_bytes(int32_t Q, int32_t C) { return (size_t)Q * ((size_t)C + 1) * 2 * sizeof(int32_t); }
-inline ShardWsRegions ws_shard_regions(int32_t Q, int32_t C, int32_t n_ranks) {
+inline size_t block_bytes(int32_t Q, int32_t C, int cols = 2) { return (size_t)Q * ((size_t)C + 1) * (size_t)cols * sizeof(int32_t); }
+inline ShardWsRegions ws_shard_regions(int32_t Q, int32_t C, int32_t n_ranks, int cols = 2) {
     ShardWsRegions r;
     const size_t n = (size_t)(n_ranks > 1 ? n_ranks : 1);
     size_t p = 0;
-    r.local = p;     p += al256(block_bytes(Q, C));
-    r.gathered = p;  p += al256(n * block_bytes(Q, C));
+    r.local = p;     p += al256(block_bytes(Q, C, cols));
+    r.gathered = p;  p += al256(n * block_bytes(Q, C, cols));
     r.plain = p;
     return r;
 }
 // what the front costs a caller's buffer at most: its regions and the base's alignment
-inline size_t ws_shard_front_bytes(int32_t Q, int32_t C, int32_t n_ranks) { return ws_shard_regions(Q, C, n_ranks).plain + 255; }
+inline size_t ws_shard_front_bytes(int32_t Q, int32_t C, int32_t n_ranks, int cols = 2) {
+    return ws_shard_regions(Q, C, n_ranks, cols).plain + 255;
+}
 // A buffer of `bytes` at address `base` -> where the front starts, and the plain call's part behind it.  That part is
 // given bytes - ws_shard_front_bytes (0 if the front does not fit) whatever the base's alignment cost, so that a
 // buffer is refused one byte below the sizing function's answer at every base; it ends inside the buffer.
@@ -140,11 +143,11 @@ struct ShardWs {
     uintptr_t front, plain;
     size_t plain_bytes;
 };
-inline ShardWs ws_shard_carve(uintptr_t base, size_t bytes, int32_t Q, int32_t C, int32_t n_ranks) {
+inline ShardWs ws_shard_carve(uintptr_t base, size_t bytes, int32_t Q, int32_t C, int32_t n_ranks, int cols = 2) {
     ShardWs s;
-    const size_t front = ws_shard_front_bytes(Q, C, n_ranks);
+    const size_t front = ws_shard_front_bytes(Q, C, n_ranks, cols);
     s.front = (uintptr_t)al256((size_t)base);
-    s.plain = s.front + ws_shard_regions(Q, C, n_ranks).plain;
+    s.plain = s.front + ws_shard_regions(Q, C, n_ranks, cols).plain;
     s.plain_bytes = bytes > front ? bytes - front : 0;
     return s;
 }

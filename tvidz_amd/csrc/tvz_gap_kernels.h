@@ -8,6 +8,7 @@
 //   ts_gapr_fold_kernel     the rates call's: per query its R hit lists folded per id, the C best, the block, the total.
 //
 //   ts_gapc_merge_kernel    per query the C best of up to 16 blocks of the plain call (tvz_align_candidates_merge).
+//   ts_gapr_merge_kernel    ... of up to 16 blocks of the rates call, one row per id (tvz_align_candidates_rates_merge).
 //
 // The plain call is the shared steps at R = 1 with the rate list {1.0}.  The queries come sorted from ts_tol_sort_kernel (tvz_tol_kernels.h): sv[at .. at + m), at = q_offsets[q] -
 // q_offsets[0], m = qm[q]; qm[q] < 0: longer than the call's max_query_len.  From tvz_topk_kernels.h: bitonic_sort,
@@ -331,6 +332,82 @@ __global__ __launch_bounds__(kBlock) void ts_gapr_fold_kernel(const int32_t *__r
         }
     }
     if (threadIdx.x == 0) gapr_store_row(out, row0 + C, -1, refused ? INT32_MIN : topk_total(pairs, over), 0);
+}
+
+// ---- the merge of the shards' blocks of the rates call (tvz_align_candidates_rates_merge, -------------------------
+// ---- include/tvz_gap_rates_shards.h) -------------------------------------------------------------------------------
+constexpr int kGaprMergeMaxLists = 16;
+constexpr int kGaprMergeCap = kGaprMergeMaxLists * tvz_gap::kMaxC;   // 1,024 rows of a query at most: 12 KiB of LDS
+
+// gathered int32[n_lists][Q][C + 1][3] -> out int32[Q][C + 1][3], both in the block format of ts_gapr_fold_kernel.
+// grid = Q: one block per query (the wave-per-query plain merge above spends ~1,700 dependent LDS round trips per
+// lane at 16 x 64, and ranks by binary search cannot drop a repeated id).  It is ONE chunk of the fold's procedure, in
+// the fold's words: every row (video_id >= 0) becomes gapr_by_id(id, best, rate index & 15), padding ~0; sorted by id,
+// every entry whose predecessor has its id is dropped - what stays of an id is its largest best at its smallest rate
+// index, however many lists hold it; the rest, as by-output words, is sorted again and the C first are written.  The
+// lists need not be sorted.  The sort buffers are this kernel's own (kGaprMergeCap entries, not the fold's kSortCap),
+// and the chunk body is a copy of the fold's, not a function shared with it: the fold's machine code stays as it was.
+// sort_and_keep pads to the next power of two of n_lists x C only.
+// The total: the lists' last rows through LDS, reduced by every thread alike in 64 bits (16 |t| of up to 2^31 do not
+// fit waves_sum's 32-bit words) by topk_total's rule; INT32_MIN in any list refuses the query, which then folds no row
+// and goes through the same two store sites as every other.  A rate index is masked to its 4 bits and a best clamped
+// to kGaprMaxCount (gapr_by_id), so a row out of the contract's ranges changes this query's rows only; only rows
+// row0 .. row0 + C are ever written.  One 12-byte store per row.
+// LDS as built: 12,608 bytes - the three arrays' 12,352 and 256 more, which the fold carries over its arrays too and
+// ts_gapc_select_kernel (24,576, exactly its arrays) does not: the two kernels that call __syncthreads_count have them,
+// so they are taken to be that call's own words (read off the code objects' metadata, not off the compiler's source).
+__global__ __launch_bounds__(kBlock) void ts_gapr_merge_kernel(const int32_t *__restrict__ gathered, int32_t n_lists,
+                                                                int32_t Q, int32_t C, int32_t *__restrict__ out) {
+    __shared__ uint64_t key[kGaprMergeCap];
+    __shared__ int32_t cnt[kGaprMergeCap];
+    __shared__ int32_t s_t[kGaprMergeMaxLists];
+    const int64_t q = blockIdx.x;
+    const int64_t c1 = (int64_t)C + 1;
+    const int64_t row0 = q * c1;
+    if ((int)threadIdx.x < n_lists) s_t[threadIdx.x] = gathered[(((int64_t)threadIdx.x * Q + q) * c1 + C) * 3 + 1];
+    __syncthreads();
+    long long sum = 0;                                               // block-uniform, like everything below
+    bool over = false, refused = false;
+    for (int l = 0; l < n_lists; ++l) {
+        const int32_t t = s_t[l];
+        refused = refused || t == INT32_MIN;
+        over = over || t < 0;
+        sum += t == INT32_MIN ? 0 : (t < 0 ? -(long long)t : (long long)t);
+    }
+    const int n = refused ? 0 : n_lists * C;                         // <= kGaprMergeCap
+    for (int e = threadIdx.x; e < n; e += kBlock) {
+        const int l = e / C, p = e - l * C;
+        const int32_t *r = gathered + (((int64_t)l * Q + q) * c1 + p) * 3;
+        const int32_t vid = r[0];
+        key[e] = vid < 0 ? ~0ULL : gapr_by_id(vid, r[1], r[2] & 0xf);
+        cnt[e] = 0;
+    }
+    int pos = n;
+    __syncthreads();
+    sort_and_keep(key, cnt, pos, kGaprMergeCap);                     // by id; keeps all
+    // who repeats its predecessor's id (read everywhere before anyone rewrites)
+    for (int e = threadIdx.x; e < pos; e += kBlock)
+        cnt[e] = e > 0 && key[e] != ~0ULL && (key[e] >> 32) == (key[e - 1] >> 32);
+    __syncthreads();
+    for (int e = threadIdx.x; e < pos; e += kBlock) {
+        const uint64_t w = key[e];
+        key[e] = (cnt[e] || w == ~0ULL) ? ~0ULL : gapr_to_output(w);
+        cnt[e] = 0;
+    }
+    __syncthreads();
+    sort_and_keep(key, cnt, pos, C);                                 // by output; pos = min(pos, C)
+    const bool mine = (int)threadIdx.x < pos && key[threadIdx.x] != ~0ULL;          // (C <= 64 < kBlock)
+    pos = __syncthreads_count(mine);                                 // the entries are in front of the dropped ones
+    for (int i = threadIdx.x; i < C; i += kBlock) {
+        if (i < pos) {
+            const uint64_t w = key[i];
+            gapr_store_row(out, row0 + i, (int32_t)((w >> 4) & 0x7fffffffULL), (int32_t)(kGaprMaxCount - (uint32_t)(w >> 35)),
+                           (int32_t)(w & 0xfULL));
+        } else {
+            gapr_store_row(out, row0 + i, -1, 0, 0);
+        }
+    }
+    if (threadIdx.x == 0) gapr_store_row(out, row0 + C, -1, refused ? INT32_MIN : topk_total(sum, over), 0);
 }
 
 }  // namespace

@@ -32,6 +32,7 @@
 #include "tvz_gap.h"
 #include "tvz_gap_shards.h"
 #include "tvz_gap_rates.h"
+#include "tvz_gap_rates_shards.h"
 #include "tvz_handle.h"
 #include "tvz_index_build.h"
 
@@ -2662,6 +2663,8 @@ struct CandidatesForm {
     bool takes_rates;                // the call has a rate list, and with it a region for the lists' exclusion ids
     const char *what, *sizer;        // the call in messages; the sizing function the workspace message names
     void (*last)(const CandidatesPlan &);    // the launch behind the lookup
+    // the merge of n_lists gathered blocks of the form's rows (the sharded calls)
+    void (*merge)(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t C, int32_t *d_out, hipStream_t st);
 };
 
 struct CandidatesCall {              // what a call asks, apart from its queries; h_rates, n_rates: NULL, 1 without a rate list
@@ -2703,26 +2706,40 @@ constexpr CandidatesForm kCandidatesPlain = {
     2, 8, false, "alignment candidates", "tvz_align_candidates_workspace_bytes", [](const CandidatesPlan &p) {
         hipLaunchKernelGGL(ts_gapc_select_kernel, dim3((unsigned)p.b.Q), dim3(kBlock), 0, p.st(), p.hits, p.hits_n, p.qm, p.a.cap,
                            p.a.C, p.a.d_out);
+    },
+    [](const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t C, int32_t *d_out, hipStream_t st) {
+        hipLaunchKernelGGL(ts_gapc_merge_kernel, dim3((unsigned)tvz::ceil_div(Q, kGapMergeWaves)), dim3(kGapMergeBlock),
+                           gapc_merge_lds_bytes(n_lists, C), st, d_gathered, n_lists, Q, C, d_out);
     }};
 constexpr CandidatesForm kCandidatesRates = {
     3, 4, true, "alignment candidates with rates", "tvz_align_candidates_rates_workspace_bytes", [](const CandidatesPlan &p) {
         hipLaunchKernelGGL(ts_gapr_fold_kernel, dim3((unsigned)p.b.Q), dim3(kBlock), 0, p.st(), p.hits, p.hits_n, p.qm, p.rates.n,
                            p.a.cap, p.a.C, p.a.d_out);
+    },
+    [](const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t C, int32_t *d_out, hipStream_t st) {
+        hipLaunchKernelGGL(ts_gapr_merge_kernel, dim3((unsigned)Q), dim3(kBlock), 0, st, d_gathered, n_lists, Q, C, d_out);
     }};
+
+// What a form refuses of its arguments before it looks at the handle, the queries or the workspace, in the headers'
+// order; the checked rate list goes to `rates` (the plain form: {1.0}).
+int check_candidates_front(const CandidatesForm &f, const Batch &b, const CandidatesCall &a, AlRates *rates) {
+    if (int rc = check_candidates_args(b.max_query_len, a.min_count, a.cap, a.C)) return rc;
+    *rates = AlRates{{1.0}, 1};
+    if (f.takes_rates) {
+        if (int rc = check_align_rates(a.h_rates, a.n_rates, rates)) return rc;
+        if ((int64_t)b.Q * a.n_rates > kGaprMaxLists)
+            return tvz::fail(TVZ_ERR_UNSUPPORTED, "%s: Q=%d x n_rates=%d is above %d probe lists", f.what, (int)b.Q, (int)a.n_rates,
+                             kGaprMaxLists);
+    }
+    return TVZ_OK;
+}
 
 // Everything in front of the first launch: the refusals in the headers' order, the carving of `ws` (the call's part of
 // the caller's buffer; ws.bytes: the whole buffer's, `front` included), the handle's lock and what is read under it.
 // `late`: what a sharded form still refuses behind all of the call's own refusals.
 int candidates_plan(const CandidatesForm &f, tvz_corpus *c, const Batch &b, const CandidatesCall &a, Workspace ws,
                     void *hip_stream, LateCheck late, CandidatesFront front, CandidatesPlan &p) {
-    if (int rc = check_candidates_args(b.max_query_len, a.min_count, a.cap, a.C)) return rc;
-    p.rates = AlRates{{1.0}, 1};
-    if (f.takes_rates) {
-        if (int rc = check_align_rates(a.h_rates, a.n_rates, &p.rates)) return rc;
-        if ((int64_t)b.Q * a.n_rates > kGaprMaxLists)
-            return tvz::fail(TVZ_ERR_UNSUPPORTED, "%s: Q=%d x n_rates=%d is above %d probe lists", f.what, (int)b.Q, (int)a.n_rates,
-                             kGaprMaxLists);
-    }
+    if (int rc = check_candidates_front(f, b, a, &p.rates)) return rc;
     if (int rc = check_batch_args(c, b, a.cap)) return rc;
     p.f = &f, p.c = c, p.b = b, p.a = a, p.hip_stream = hip_stream;
     if (b.Q == 0) return TVZ_OK;
@@ -2817,74 +2834,71 @@ int check_candidates_merge(int32_t n_lists, int32_t C) {
     return TVZ_OK;
 }
 
-bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+// a pointer to rows of a form's block: aligned to the row's vector store
+bool aligned_rows(const CandidatesForm &f, const void *p) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(f.out_align - 1)) == 0; }
+size_t form_block_bytes(const CandidatesForm &f, int32_t Q, int32_t C) { return (size_t)Q * ((size_t)C + 1) * (size_t)f.cols * sizeof(int32_t); }
 
-}  // namespace
-
-// used by tvz_comm.hip too (same shared object, not exported): the merge of the gathered blocks
-int tvz_align_candidates_merge_local(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t C, int32_t *d_out,
-                                     void *hip_stream) {
+// the merge of n_lists gathered blocks of a form: its refusals, then the form's one launch
+int candidates_merge_local(const CandidatesForm &f, const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t C,
+                           int32_t *d_out, void *hip_stream) {
     if (int rc = check_candidates_merge(n_lists, C)) return rc;
     TVZ_REQUIRE(Q >= 0, "Q=%d is negative", (int)Q);
     if (Q == 0) return TVZ_OK;
     TVZ_REQUIRE(d_gathered && d_out, "NULL argument");
-    TVZ_REQUIRE(aligned8(d_gathered) && aligned8(d_out), "alignment candidates merge: the blocks and d_out must be 8-byte aligned");
+    TVZ_REQUIRE(aligned_rows(f, d_gathered) && aligned_rows(f, d_out),
+                "alignment candidates merge: the blocks and d_out must be %d-byte aligned", f.out_align);
     const uintptr_t g0 = reinterpret_cast<uintptr_t>(d_gathered), o0 = reinterpret_cast<uintptr_t>(d_out);
-    const size_t block = tvz_gap::block_bytes(Q, C);
+    const size_t block = form_block_bytes(f, Q, C);
     TVZ_REQUIRE(o0 + block <= g0 || g0 + (size_t)n_lists * block <= o0, "alignment candidates merge: d_out lies inside the blocks");
-    hipLaunchKernelGGL(ts_gapc_merge_kernel, dim3((unsigned)tvz::ceil_div(Q, kGapMergeWaves)), dim3(kGapMergeBlock),
-                       gapc_merge_lds_bytes(n_lists, C), reinterpret_cast<hipStream_t>(hip_stream), d_gathered, n_lists, Q, C, d_out);
+    f.merge(d_gathered, n_lists, Q, C, d_out, reinterpret_cast<hipStream_t>(hip_stream));
     return launched();
 }
 
-// ... and the local call with the sharded form's blocks in front of its workspace (tvz_gap_codes.h: ws_shard_carve)
-int tvz_align_candidates_local(tvz_corpus *c, const Batch &b, int32_t min_count, int32_t cap, int32_t C, Workspace ws,
-                               int32_t n_ranks, void *hip_stream, ShardBlocks *blocks, LateCheck late) {
+// The local call of a form with the sharded form's blocks in front of its workspace (tvz_gap_codes.h: ws_shard_carve
+// with the form's columns).
+int candidates_local(const CandidatesForm &f, const char *sharded_sizer, tvz_corpus *c, const Batch &b, const double *h_rates,
+                     int32_t n_rates, int32_t min_count, int32_t cap, int32_t C, Workspace ws, int32_t n_ranks, void *hip_stream,
+                     ShardBlocks *blocks, LateCheck late) {
     // (arguments the carving cannot take are refused by the call itself, in front of its look at the workspace)
     const bool carve = ws.p != nullptr && b.Q > 0 && b.Q <= 65535 && C >= 1 && C <= tvz_gap::kMaxC;
     tvz_gap::ShardWs s{0, 0, 0};
-    if (carve) s = tvz_gap::ws_shard_carve(reinterpret_cast<uintptr_t>(ws.p), ws.bytes, b.Q, C, n_ranks);
+    if (carve) s = tvz_gap::ws_shard_carve(reinterpret_cast<uintptr_t>(ws.p), ws.bytes, b.Q, C, n_ranks, f.cols);
     int32_t *local = reinterpret_cast<int32_t *>(s.front);
     if (carve && blocks) {
-        const tvz_gap::ShardWsRegions r = tvz_gap::ws_shard_regions(b.Q, C, n_ranks);
+        const tvz_gap::ShardWsRegions r = tvz_gap::ws_shard_regions(b.Q, C, n_ranks, f.cols);
         *blocks = ShardBlocks{local, reinterpret_cast<int32_t *>(s.front + r.gathered)};
     }
     // the call judges the WHOLE buffer's size, front included, and lays its own part out from s.plain on
-    const CandidatesFront front{carve ? tvz_gap::ws_shard_front_bytes(b.Q, C, n_ranks) : 0,
-                                "tvz_align_candidates_sharded_workspace_bytes"};
-    return candidates_call(kCandidatesPlain, c, b, CandidatesCall{nullptr, 1, min_count, cap, C, local},
-                           Workspace{carve ? reinterpret_cast<void *>(s.plain) : nullptr, ws.bytes}, hip_stream, late, front);
+    const size_t front_bytes = carve ? tvz_gap::ws_shard_front_bytes(b.Q, C, n_ranks, f.cols) : 0;
+    return candidates_call(f, c, b, CandidatesCall{h_rates, n_rates, min_count, cap, C, local},
+                           Workspace{carve ? reinterpret_cast<void *>(s.plain) : nullptr, ws.bytes}, hip_stream, late,
+                           CandidatesFront{front_bytes, sharded_sizer});
 }
 
-size_t tvz_align_candidates_sharded_sizing(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t cap, int32_t C,
-                                           int32_t n_ranks) {
-    const size_t plain = tvz_align_candidates_workspace_bytes(Q, max_query_len, total_query_keys, cap, C);
-    if (plain == 0 || n_ranks < 0) return 0;
-    return plain + tvz_gap::ws_shard_front_bytes(Q, C, n_ranks);
-}
-
-// The shards of one process: every handle's call into its block of d_blocks, then the merge.
-static int align_candidates_shards_impl(tvz_corpus *const *shards, int32_t n_shards, const double *d_queries,
-                                        const int64_t *d_q_offsets, int32_t Q, int32_t max_query_len, int32_t min_count,
-                                        const int32_t *d_exclude_ids, int32_t cap, int32_t C, int32_t *d_blocks, int32_t *d_out,
-                                        void *d_workspace, size_t workspace_bytes, void *hip_stream) {
-    if (int rc = check_candidates_args(max_query_len, min_count, cap, C)) return rc;
+// The shards of one process: every handle's call of the form into its block of d_blocks, then the merge.
+int candidates_shards(const CandidatesForm &f, tvz_corpus *const *shards, int32_t n_shards, const Batch &b, const double *h_rates,
+                      int32_t n_rates, int32_t min_count, int32_t cap, int32_t C, int32_t *d_blocks, int32_t *d_out, Workspace ws,
+                      void *hip_stream) {
+    const int32_t Q = b.Q;
+    AlRates rates;
+    if (int rc = check_candidates_front(f, b, CandidatesCall{h_rates, n_rates, min_count, cap, C, nullptr}, &rates)) return rc;
     TVZ_REQUIRE(shards != nullptr && n_shards >= 1, "no shards");
     if (int rc = check_candidates_merge(n_shards, C)) return rc;
     for (int32_t r = 0; r < n_shards; ++r)
         TVZ_REQUIRE(shards[r] != nullptr && shards[r]->device == shards[0]->device,
                     "shard %d is NULL or on another device than shard 0", r);
-    if (int rc = check_batch_args(shards[0], align_batch(d_queries, d_q_offsets, Q, max_query_len, d_exclude_ids), cap)) return rc;
+    if (int rc = check_batch_args(shards[0], b, cap)) return rc;
     if (Q == 0) return TVZ_OK;
-    TVZ_REQUIRE(d_blocks && d_out && aligned8(d_blocks) && aligned8(d_out), "d_blocks or d_out is NULL or not 8-byte aligned");
-    const size_t block = tvz_gap::block_bytes(Q, C);
+    TVZ_REQUIRE(d_blocks && d_out && aligned_rows(f, d_blocks) && aligned_rows(f, d_out),
+                "d_blocks or d_out is NULL or not %d-byte aligned", f.out_align);
+    const size_t block = form_block_bytes(f, Q, C);
     {
         const uintptr_t g0 = reinterpret_cast<uintptr_t>(d_blocks), o0 = reinterpret_cast<uintptr_t>(d_out);
         TVZ_REQUIRE(o0 + block <= g0 || g0 + (size_t)n_shards * block <= o0, "alignment candidates merge: d_out lies inside the blocks");
     }
-    const Batch b = align_batch(d_queries, d_q_offsets, Q, max_query_len, d_exclude_ids);
-    const Workspace ws{d_workspace, workspace_bytes};
-    auto call_of = [&](int32_t r) { return CandidatesCall{nullptr, 1, min_count, cap, C, d_blocks + (size_t)r * (block / sizeof(int32_t))}; };
+    auto call_of = [&](int32_t r) {
+        return CandidatesCall{h_rates, n_rates, min_count, cap, C, d_blocks + (size_t)r * (block / sizeof(int32_t))};
+    };
     // Every handle is planned first - the arguments' refusals are the same for all, the handle's own (no gap codes) are
     // not - and the widths compared: nothing is enqueued before all of them agree.  A plan holds its handle's lock, and
     // the locks are taken one handle at a time (the shards may name a handle twice, and two callers may name them in
@@ -2892,16 +2906,48 @@ static int align_candidates_shards_impl(tvz_corpus *const *shards, int32_t n_sha
     double eps0 = 0.0;
     for (int32_t r = 0; r < n_shards; ++r) {
         CandidatesPlan p;
-        if (int rc = candidates_plan(kCandidatesPlain, shards[r], b, call_of(r), ws, hip_stream, {}, {}, p)) return rc;
+        if (int rc = candidates_plan(f, shards[r], b, call_of(r), ws, hip_stream, {}, {}, p)) return rc;
         if (r == 0) eps0 = p.gap_eps;
         if (p.gap_eps != eps0)
             return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment candidates: shard %d keeps gap codes of gap_eps=%.17g, shard 0 of %.17g",
                              (int)r, p.gap_eps, eps0);
     }
     for (int32_t r = 0; r < n_shards; ++r)
-        if (int rc = candidates_call(kCandidatesPlain, shards[r], b, call_of(r), ws, hip_stream)) return rc;
+        if (int rc = candidates_call(f, shards[r], b, call_of(r), ws, hip_stream)) return rc;
     DeviceGuard dg(shards[0]->device);
-    return tvz_align_candidates_merge_local(d_blocks, n_shards, Q, C, d_out, hip_stream);
+    return candidates_merge_local(f, d_blocks, n_shards, Q, C, d_out, hip_stream);
+}
+
+}  // namespace
+
+// used by tvz_comm.hip too (same shared object, not exported): the merges of the gathered blocks ...
+int tvz_align_candidates_merge_local(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t C, int32_t *d_out,
+                                     void *hip_stream) {
+    return candidates_merge_local(kCandidatesPlain, d_gathered, n_lists, Q, C, d_out, hip_stream);
+}
+int tvz_align_candidates_rates_merge_local(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t C, int32_t *d_out,
+                                           void *hip_stream) {
+    return candidates_merge_local(kCandidatesRates, d_gathered, n_lists, Q, C, d_out, hip_stream);
+}
+
+// ... and the local calls with the sharded forms' blocks in front of their workspaces
+int tvz_align_candidates_local(tvz_corpus *c, const Batch &b, int32_t min_count, int32_t cap, int32_t C, Workspace ws,
+                               int32_t n_ranks, void *hip_stream, ShardBlocks *blocks, LateCheck late) {
+    return candidates_local(kCandidatesPlain, "tvz_align_candidates_sharded_workspace_bytes", c, b, nullptr, 1, min_count, cap, C, ws,
+                            n_ranks, hip_stream, blocks, late);
+}
+int tvz_align_candidates_rates_local(tvz_corpus *c, const Batch &b, const double *h_rates, int32_t n_rates, int32_t min_count,
+                                     int32_t cap, int32_t C, Workspace ws, int32_t n_ranks, void *hip_stream, ShardBlocks *blocks,
+                                     LateCheck late) {
+    return candidates_local(kCandidatesRates, "tvz_align_candidates_rates_sharded_workspace_bytes", c, b, h_rates, n_rates, min_count,
+                            cap, C, ws, n_ranks, hip_stream, blocks, late);
+}
+
+size_t tvz_align_candidates_sharded_sizing(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t cap, int32_t C,
+                                           int32_t n_ranks) {
+    const size_t plain = tvz_align_candidates_workspace_bytes(Q, max_query_len, total_query_keys, cap, C);
+    if (plain == 0 || n_ranks < 0) return 0;
+    return plain + tvz_gap::ws_shard_front_bytes(Q, C, n_ranks);
 }
 
 TVZ_EXPORT int tvz_align_candidates_merge(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t C, int32_t *d_out,
@@ -2913,8 +2959,8 @@ TVZ_EXPORT int tvz_align_candidates_shards(tvz_corpus *const *shards, int32_t n_
                                            const int64_t *d_q_offsets, int32_t Q, int32_t max_query_len, int32_t min_count,
                                            const int32_t *d_exclude_ids, int32_t cap, int32_t C, int32_t *d_blocks,
                                            int32_t *d_out, void *d_workspace, size_t workspace_bytes, void *hip_stream) {
-    TVZ_GUARDED(align_candidates_shards_impl(shards, n_shards, d_queries, d_q_offsets, Q, max_query_len, min_count,
-                                             d_exclude_ids, cap, C, d_blocks, d_out, d_workspace, workspace_bytes, hip_stream));
+    TVZ_GUARDED(candidates_shards(kCandidatesPlain, shards, n_shards, align_batch(d_queries, d_q_offsets, Q, max_query_len, d_exclude_ids),
+                                  nullptr, 1, min_count, cap, C, d_blocks, d_out, Workspace{d_workspace, workspace_bytes}, hip_stream));
 }
 
 TVZ_EXPORT size_t tvz_align_candidates_sharded_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys,
@@ -2955,6 +3001,29 @@ TVZ_EXPORT int tvz_align_candidates_rates(tvz_corpus *c, const double *d_queries
     TVZ_GUARDED(candidates_call(kCandidatesRates, c, align_batch(d_queries, d_q_offsets, Q, max_query_len, d_exclude_ids),
                                 CandidatesCall{h_rates, n_rates, min_count, cap, C, d_out}, Workspace{d_workspace, workspace_bytes},
                                 hip_stream));
+}
+
+// ---- the rates call over a sharded table (include/tvz_gap_rates_shards.h) ------------------------------------------
+TVZ_EXPORT int tvz_align_candidates_rates_merge(const int32_t *d_gathered, int32_t n_lists, int32_t Q, int32_t C, int32_t *d_out,
+                                                void *hip_stream) {
+    TVZ_GUARDED(tvz_align_candidates_rates_merge_local(d_gathered, n_lists, Q, C, d_out, hip_stream));
+}
+
+TVZ_EXPORT int tvz_align_candidates_rates_shards(tvz_corpus *const *shards, int32_t n_shards, const double *d_queries,
+                                                 const int64_t *d_q_offsets, int32_t Q, int32_t max_query_len, const double *h_rates,
+                                                 int32_t n_rates, int32_t min_count, const int32_t *d_exclude_ids, int32_t cap,
+                                                 int32_t C, int32_t *d_blocks, int32_t *d_out, void *d_workspace,
+                                                 size_t workspace_bytes, void *hip_stream) {
+    TVZ_GUARDED(candidates_shards(kCandidatesRates, shards, n_shards, align_batch(d_queries, d_q_offsets, Q, max_query_len, d_exclude_ids),
+                                  h_rates, n_rates, min_count, cap, C, d_blocks, d_out, Workspace{d_workspace, workspace_bytes},
+                                  hip_stream));
+}
+
+TVZ_EXPORT size_t tvz_align_candidates_rates_sharded_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys,
+                                                                     int32_t n_rates, int32_t cap, int32_t C, int32_t n_ranks) {
+    const size_t rates = tvz_align_candidates_rates_workspace_bytes(Q, max_query_len, total_query_keys, n_rates, cap, C);
+    if (rates == 0 || n_ranks < 0) return 0;
+    return rates + tvz_gap::ws_shard_front_bytes(Q, C, n_ranks, kCandidatesRates.cols);
 }
 
 #ifdef TVZ_IX_STAMP

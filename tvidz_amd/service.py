@@ -386,6 +386,40 @@ class ShardedCorpus:
                                                   d_exclude_ids=d_ex, workspace=ws)[1] for g in groups]
             return answers[0] if len(answers) == 1 else tc.align_candidates_merge_device(torch.stack(answers))
 
+    @property
+    def supports_align_candidate_rates(self) -> bool:
+        return True
+
+    def align_candidates_rates(self, queries, rates, *, c: int, min_count: int = 2, cap: int = 4096, exclude_ids=None,
+                               max_query_len=None):
+        """DeviceCorpus.align_candidates_rates over every shard (set_gap_index first), with its return shapes: (ids,
+        counts, rate_indexes int32 [Q, c], totals int32 [Q]).  ONE library call (tvz_align_candidates_rates_shards) asks
+        every shard with the calling thread's one workspace and merges the blocks on the device - one row per id, its
+        largest best at the smallest rate index, the c best of them, the totals summed
+        (include/tvz_gap_rates_shards.h) - and ONE copy brings the block back.  Exactly one DeviceCorpus's answer over
+        the same rows wherever no shard's list exceeded `cap` (the total is negative where one did).  More than 16
+        shards: one such call per group of 16, the groups' answers merged again by tvz_align_candidates_rates_merge;
+        still one copy back, same answer."""
+        h = self.align_candidates_rates_block(queries, rates, c=c, min_count=min_count, cap=cap, exclude_ids=exclude_ids,
+                                              max_query_len=max_query_len).cpu().numpy()
+        return (np.ascontiguousarray(h[:, :c, 0]), np.ascontiguousarray(h[:, :c, 1]), np.ascontiguousarray(h[:, :c, 2]),
+                np.ascontiguousarray(h[:, c, 1]))
+
+    def align_candidates_rates_block(self, queries, rates, *, c: int, min_count: int = 2, cap: int = 4096, exclude_ids=None,
+                                     max_query_len=None) -> torch.Tensor:
+        """align_candidates_rates, left on the device: the merged block int32 [Q, c + 1, 3]; `block[:, :c, 0]` is the
+        strided view of ids that the parts calls take, with the same `rates`."""
+        dev = self.dev
+        rates = tuple(rates)
+        d_q, d_off, Q, max_query_len, d_ex = tc.align_inputs(queries, exclude_ids, max_query_len, dev)
+        ws = tc.thread_workspace(self._near_tls, tc.align_candidates_rates_workspace_bytes(Q, max_query_len, d_q.numel(),
+                                                                                           len(rates), cap, c), dev)
+        with torch.cuda.device(dev):
+            groups = [self.shards[i:i + 16] for i in range(0, self.R, 16)]      # the merge takes up to 16 lists
+            answers = [tc.align_candidates_rates_shards(g, d_q, d_off, max_query_len, rates, c=c, min_count=min_count,
+                                                        cap=cap, d_exclude_ids=d_ex, workspace=ws)[1] for g in groups]
+            return answers[0] if len(answers) == 1 else tc.align_candidates_rates_merge_device(torch.stack(answers))
+
     def _near_shards(self, form, queries, k, exclude_ids, max_query_len, **ask):
         """What the four methods above share, for their `form` (corpus.ALIGN_FORMS) and what they `ask`: the inputs, the
         calling thread's workspace, one tvz_<stem>_shards per group of 16 shards, the groups' tvz_<stem>_merge, the one
@@ -466,6 +500,10 @@ class ShardedCorpus:
 ASK_TOPK, ASK_EXACT, ASK_NEAR, ASK_NEAR_WIDE, ASK_NEAR_RATES, ASK_NEAR_SPAN, ASK_PARTS = 0, 1, 2, 3, 4, 5, 6
 ASK_CANDIDATES = 7                                         # the candidate ids from the gap codes (align_candidates)
 CAND_PAR = 5                                               # its parameters, in a near ask's slots: (gap_eps, 0, C, min_count, cap)
+ASK_CANDIDATES_RATES = 8                                   # ... at a list of rates (align_candidates_rates): (gap_eps, 0, C,
+#                                                            min_count, cap, 0) in the near slots, the rate list where the
+#                                                            searches with rates carry theirs - NEAR_PAR values in all
+CAND_RATES_MAX_LISTS = 65535                               # probe lists of one library call: its asks x n_rates
 # An ask's header: (len, exclude, min_match, kind, tolerance | a near ask's eps, max_offset, k, min_votes, min_score, flags |
 # its rate list: the count and up to 8 rates | a parts ask's max_parts and its k <= 64 ids).  All float64: small integers
 # and int32 ids are exact in it, and tolerance, eps, max_offset and the rates ARE float64.  Every rank runs one build.
@@ -802,6 +840,39 @@ class RankCorpus:
         near = (gap_eps, 0.0, int(c), int(min_count), int(cap))
         return self._near_asks(ASK_CANDIDATES, near, queries, exclude_ids, max_query_len)
 
+    @property
+    def supports_align_candidate_rates(self) -> bool:
+        """Can `align_candidates_rates` answer?  The matcher has `candidates_rates` and this rank's shard can keep gap
+        codes."""
+        return bool(getattr(self.matcher, "supports_align_candidate_rates", False)) and hasattr(self.shard, "set_gap_index")
+
+    def align_candidates_rates(self, queries, rates, *, c: int, min_count: int = 2, cap: int = 4096, exclude_ids=None,
+                               max_query_len=None):
+        """DeviceCorpus.align_candidates_rates over the shards of all ranks, with its return shapes: (ids, counts,
+        rate_indexes int32 [Q, c], totals int32 [Q]).  Every query is one ASK_CANDIDATES_RATES of the next tick; its
+        parameters travel in a near ask's slots - (gap_eps, 0, C, min_count, cap, 0) - and its rate list where a search
+        with rates carries its own.  Everything a rank's library call would refuse is refused HERE, in the caller
+        (ValueError: C, cap < C, min_count, the rate list; RuntimeError: a shard without gap codes, a matcher without
+        `candidates_rates`).  A query of more than max_query_len (at most 4,095) values never travels: all rows padding,
+        total ALIGN_CANDIDATES_REFUSED, as the library answers it."""
+        for name, v, lo, hi in (("c", c, 1, tc.ALIGN_CANDIDATES_MAX_C), ("cap", cap, 1, (1 << 31) - 1),
+                                ("min_count", min_count, 1, (1 << 31) - 1)):
+            if int(v) != v or not lo <= int(v) <= hi:
+                raise ValueError(f"{name} must be an integer in {lo}..{hi}, got {v!r}")
+        if int(cap) < int(c):
+            raise ValueError(f"cap={cap!r} is below c={c!r}")
+        rate_slots = check_near_rates(rates)
+        if not getattr(self.matcher, "supports_align_candidate_rates", False):
+            raise RuntimeError(f"this rank corpus has no align_candidates_rates: its matcher {type(self.matcher).__name__} "
+                               "has no candidates_rates call")
+        gap_eps = float(self.shard.gap_index_stats()["gap_eps"]) if hasattr(self.shard, "gap_index_stats") else 0.0
+        if not gap_eps > 0.0:
+            raise RuntimeError("this rank corpus keeps no gap codes: set_gap_index first")
+        near = (gap_eps, 0.0, int(c), int(min_count), int(cap), 0) + rate_slots
+        rows, totals = self._near_asks(ASK_CANDIDATES_RATES, near, queries, exclude_ids, max_query_len)
+        return (np.ascontiguousarray(rows[:, :, 0]), np.ascontiguousarray(rows[:, :, 1]), np.ascontiguousarray(rows[:, :, 2]),
+                totals)
+
     def _near(self, form, queries, exclude_ids, max_query_len, eps, max_offset, k, min_votes, min_score, contain=False,
               local=False, rates=None, two_bins=False):
         """What the four searches above share, for their `form`.  Everything a rank's library call would refuse is refused
@@ -826,7 +897,9 @@ class RankCorpus:
         if len(excl) != len(queries):
             raise ValueError(f"exclude_ids must hold {len(queries)} video ids")
         k = near[2]
-        cols = 2 if kind == ASK_CANDIDATES else TICK_FORMS[kind].cols              # (a candidates ask: rows of (id, count), k = C)
+        # (a candidates ask: rows of (id, count), with rates (id, best, rate_index); k = C)
+        cols = {ASK_CANDIDATES: 2, ASK_CANDIDATES_RATES: 3}[kind] if kind in (ASK_CANDIDATES, ASK_CANDIDATES_RATES) \
+            else TICK_FORMS[kind].cols
         rows = np.zeros((len(queries), k, cols), dtype=np.int32)
         rows[:, :, 0] = -1
         totals = np.full(len(queries), -(1 << 31), dtype=np.int64)                 # ALIGN_REFUSED unless answered
@@ -918,7 +991,8 @@ class RankCorpus:
         """One busy tick.  The order of the collectives and of the matcher calls is the same on every rank: the asks'
         exchange, one match_topk per (min_match, tolerance) in sorted order, one align per near kind and set of its
         parameters in sorted order, one parts call per set of its parameters, one candidates call per set of its parameters,
-        then the exact asks' two gathers."""
+        one candidates call with rates per set of its parameters (split where its probe lists exceed one call's), then the
+        exact asks' two gathers."""
         asks = self._gather_asks(take, allmeta)
         self._answer_topk(asks, take)
         self._answer_near(asks, take)
@@ -986,7 +1060,8 @@ class RankCorpus:
         """Near asks: per kind in ascending order, one batched `matcher.align` of the kind's form per (eps, max_offset,
         k, min_votes, min_score, flags, the rate list) in sorted order, then one `matcher.parts` per (eps, max_offset, k,
         min_votes, the rate list, max_parts) in sorted order, then one `matcher.candidates` per (gap_eps, C, min_count,
-        cap) in sorted order: every rank reads the same kinds and parameters off the
+        cap) in sorted order, then one `matcher.candidates_rates` per (gap_eps, C, min_count, cap, the rate list) in sorted
+        order: every rank reads the same kinds and parameters off the
         gathered headers, so every rank makes the same calls in the same order."""
         for kind, form in sorted(TICK_FORMS.items()):
             of_kind = asks.kind == kind
@@ -1029,6 +1104,28 @@ class RankCorpus:
                                lambda d_q, d_off, max_len, d_ex: self.matcher.candidates(d_q, d_off, max_len,
                                                                                          d_exclude_ids=d_ex, **kw),
                                to_host=to_host)
+        # ... and behind them the candidates asks with a rate list: one `matcher.candidates_rates` per (gap_eps, C,
+        # min_count, cap, the rate list) in sorted order.  A call takes CAND_RATES_MAX_LISTS probe lists, its asks x
+        # n_rates: more asks of one parameter set go in consecutive runs of floor(CAND_RATES_MAX_LISTS / n_rates) - every
+        # rank reads the same asks in the same order, so the split is the same everywhere.
+        of_kind = asks.kind == ASK_CANDIDATES_RATES
+        pars = asks.near[:, :NEAR_PAR]
+        for par in sorted(set(map(tuple, pars[of_kind].tolist()))):
+            c, rates = int(par[2]), tuple(par[7:7 + int(par[6])])
+            kw = dict(c=c, min_count=int(par[3]), cap=int(par[4]))
+
+            def to_host(out, c=c):
+                block = (out.cpu() if torch.is_tensor(out) else torch.as_tensor(out)).numpy()      # [n, c + 1, 3]
+                return [(block[j, :c].copy(), int(block[j, c, 1])) for j in range(block.shape[0])]
+            sel = np.flatnonzero(of_kind & (pars == np.asarray(par)).all(axis=1))
+            if not rates:                    # (the caller's check_near_rates refuses it; every rank reads the same header)
+                raise RuntimeError("a candidates ask with rates arrived with an empty rate list")
+            run = max(CAND_RATES_MAX_LISTS // len(rates), 1)
+            for at in range(0, len(sel), run):
+                self._answer_batch(asks, take, sel[at:at + run],
+                                   lambda d_q, d_off, max_len, d_ex: self.matcher.candidates_rates(
+                                       d_q, d_off, max_len, rates, d_exclude_ids=d_ex, **kw),
+                                   to_host=to_host)
 
     def _answer_exact(self, asks: _Asks, take) -> None:
         """Exact asks: every rank asks its own shard, counts and padded hit lists are all-gathered."""
@@ -1160,6 +1257,8 @@ def near_kwargs(a) -> dict:
     if int(getattr(a, "near_candidates", 0) or 0):
         kw["near_candidates"] = int(a.near_candidates)
         kw["near_gap_eps"] = float(getattr(a, "near_gap_eps", 1.0 / 30))
+    if getattr(a, "near_candidate_rates", False):
+        kw["near_candidate_rates"] = True
     return kw
 
 
@@ -1176,9 +1275,9 @@ def parse_near_rates(rates):
 
 def check_near_switches(near_top_k, near_any_offset=False, near_score="jaccard", near_min_votes=1, near_rates=None,
                         near_spans=False, near_parts=0, near_two_bins=False, near_candidates=0,
-                        near_gap_eps=1.0 / 30) -> list:
+                        near_gap_eps=1.0 / 30, near_candidate_rates=False) -> list:
     """`--near-any-offset`, `--near-score`, `--near-min-votes`, `--near-rates`, `--near-spans`, `--near-parts`,
-    `--near-two-bins`, `--near-candidates` (with `--near-gap-eps`): Inspector's rules for them, before any rank starts -> the switches as a rank process takes them
+    `--near-two-bins`, `--near-candidates` (with `--near-gap-eps`), `--near-candidate-rates`: Inspector's rules for them, before any rank starts -> the switches as a rank process takes them
     (none where all are at their defaults; the later ones behind the earlier three)."""
     if near_score not in ("jaccard", "containment", "local"):
         raise ValueError(f"near_score must be 'jaccard', 'containment' or 'local', got {near_score!r}")
@@ -1203,7 +1302,8 @@ def check_near_switches(near_top_k, near_any_offset=False, near_score="jaccard",
         (["--near-parts", str(int(near_parts))] if near_parts else []) + \
         (["--near-two-bins"] if near_two_bins else []) + \
         (["--near-candidates", str(int(near_candidates)), "--near-gap-eps", repr(float(near_gap_eps))]
-         if near_candidates else [])
+         if near_candidates else []) + \
+        (["--near-candidate-rates"] if near_candidate_rates else [])
     if given and not near_top_k:
         raise ValueError(f"{given[0]} needs --near-top-k")
     if near_score == "containment" and not near_any_offset:
@@ -1219,6 +1319,10 @@ def check_near_switches(near_top_k, near_any_offset=False, near_score="jaccard",
     if near_parts and near_two_bins:
         raise ValueError(f"--near-two-bins with --near-parts {int(near_parts)}: align_parts counts single bins (it has no "
                          "flags); use one of them")
+    if near_candidate_rates:
+        missing = [n for n, v in (("--near-candidates", near_candidates), ("--near-rates", rates)) if not v]
+        if missing:
+            raise ValueError(f"--near-candidate-rates needs {' and '.join(missing)}")
     if near_candidates:
         what = f"--near-candidates {int(near_candidates)}"
         if not near_any_offset:
@@ -1226,7 +1330,7 @@ def check_near_switches(near_top_k, near_any_offset=False, near_score="jaccard",
         if not int(near_top_k) <= int(near_candidates) <= tc.ALIGN_CANDIDATES_MAX_C:
             raise ValueError(f"{what}: must be --near-top-k..{tc.ALIGN_CANDIDATES_MAX_C} "
                              f"({int(near_top_k)}..{tc.ALIGN_CANDIDATES_MAX_C})")
-        if rates is not None:
+        if rates is not None and not near_candidate_rates:
             raise ValueError(f"{what} with --near-rates: the gap codes are made at rate 1; use one of them")
         if near_two_bins:
             raise ValueError(f"{what} with --near-two-bins: align_parts counts single bins; use one of them")
@@ -1397,7 +1501,7 @@ class RankService:
                  near_eps: float = 1.0 / 30, near_max_offset: float = 30.0, near_jaccard: float = 0.8,
                  near_any_offset: bool = False, near_score: str = "jaccard", near_min_votes: int = 1, near_rates=None,
                  near_spans: bool = False, near_parts: int = 0, near_two_bins: bool = False, near_candidates: int = 0,
-                 near_gap_eps: float = 1.0 / 30):
+                 near_gap_eps: float = 1.0 / 30, near_candidate_rates: bool = False):
         import socket
         import subprocess
         from . import db
@@ -1414,7 +1518,8 @@ class RankService:
             near = ["--near-top-k", str(int(near_top_k)), "--near-eps", repr(float(near_eps)),
                     "--near-max-offset", repr(float(near_max_offset)), "--near-jaccard", repr(float(near_jaccard))]
         near += check_near_switches(near_top_k, near_any_offset, near_score, near_min_votes, near_rates, near_spans,
-                                    near_parts, near_two_bins, near_candidates, near_gap_eps)
+                                    near_parts, near_two_bins, near_candidates, near_gap_eps,
+                                    near_candidate_rates=near_candidate_rates)
         db.create_schema(db_url)                                # once, before N processes open it side by side
         with socket.socket() as s:                              # a free rendezvous port
             s.bind(("127.0.0.1", 0))
@@ -1534,6 +1639,12 @@ def main(argv=None) -> int:  # pragma: no cover - exercised through subprocesses
                          "Needs --near-any-offset; not with --near-rates or --near-two-bins.  0 = off")
     ap.add_argument("--near-gap-eps", type=float, default=1.0 / 30, metavar="SECONDS",
                     help="the width the gaps between cuts are quantised to for --near-candidates, the same on every rank")
+    ap.add_argument("--near-candidate-rates", action="store_true",
+                    help="--near-candidates for speed-changed copies: the upload is probed once per rate of --near-rates "
+                         "on every rank and a stored video is named once, at its best rate "
+                         "(Inspector(near_candidate_rates=True); tvz_align_candidates_rates_sharded); the parts call aligns "
+                         "at the same rates.  Needs --near-candidates and --near-rates, which are accepted together only "
+                         "with it")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--rank", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--master-port", type=int, default=29500, help=argparse.SUPPRESS)
@@ -1549,7 +1660,8 @@ def main(argv=None) -> int:  # pragma: no cover - exercised through subprocesses
                       near_max_offset=a.near_max_offset, near_jaccard=a.near_jaccard,
                       near_any_offset=a.near_any_offset, near_score=a.near_score, near_min_votes=a.near_min_votes,
                       near_rates=a.near_rates, near_spans=a.near_spans, near_parts=a.near_parts,
-                      near_two_bins=a.near_two_bins, near_candidates=a.near_candidates, near_gap_eps=a.near_gap_eps)
+                      near_two_bins=a.near_two_bins, near_candidates=a.near_candidates, near_gap_eps=a.near_gap_eps,
+                      near_candidate_rates=a.near_candidate_rates)
 
     def monitor():
         while True:

@@ -88,6 +88,14 @@ class HipBackend:
     def candidates_merge(self, gathered):
         return tc.align_candidates_merge_device(gathered)
 
+    def local_candidates_rates(self, d_q, d_off, max_len, rates, **ask):
+        """this rank's candidate ids at a list of rates (tvz_align_candidates_rates; `ask`: c, min_count, cap,
+        d_exclude_ids): the block int32 [Q, c + 1, 3] on the device"""
+        return self.corpus.align_candidates_rates_block(d_q, d_off, max_len, rates, **ask)
+
+    def candidates_rates_merge(self, gathered):
+        return tc.align_candidates_rates_merge_device(gathered)
+
 
 def _two_bins(two_bins: bool) -> dict:
     return {"two_bins": True} if two_bins else {}
@@ -268,10 +276,29 @@ class ShardedMatcher(_AlignForwards):
         gathered, _ = self._all_gather_blocks(local, async_op=False)
         return merge_candidate_blocks(self.backend.candidates_merge, gathered)
 
+    @property
+    def supports_align_candidate_rates(self) -> bool:
+        """Does `candidates_rates` answer?  Only over a backend with the local call and the merge."""
+        return hasattr(self.backend, "local_candidates_rates") and hasattr(self.backend, "candidates_rates_merge")
+
+    def candidates_rates(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, rates, *, c: int,
+                         min_count: int = 2, cap: int = 4096, d_exclude_ids: Optional[torch.Tensor] = None):
+        """`candidates` for copies played at another speed (tvz_align_candidates_rates with `rates`, the same on every
+        rank): this rank's block [Q, c + 1, 3] -> ONE all-gather -> the merge that keeps one row per id - its largest
+        best at the smallest rate index -, the c best of them, and sums the totals (include/tvz_gap_rates_shards.h),
+        identical on every rank: -> the block int32 [Q, c + 1, 3].  More than 16 ranks are merged in groups of 16."""
+        if not self.supports_align_candidate_rates:
+            raise RuntimeError(f"{type(self.backend).__name__} has no align_candidates_rates")
+        local = self.backend.local_candidates_rates(d_queries, d_q_offsets, max_query_len, tuple(rates), c=int(c),
+                                                    min_count=int(min_count), cap=int(cap), d_exclude_ids=d_exclude_ids)
+        gathered, _ = self._all_gather_blocks(local, async_op=False)
+        return merge_candidate_blocks(self.backend.candidates_rates_merge, gathered)
+
 
 def merge_candidate_blocks(merge, gathered):
-    """`merge` (up to corpus.ALIGN_CANDIDATES_MERGE_MAX_LISTS blocks -> one) over any number of them [R, Q, c + 1, 2]:
-    groups of up to 16, then the groups' answers, until one is left - the rule is associative."""
+    """`merge` (up to corpus.ALIGN_CANDIDATES_MERGE_MAX_LISTS blocks -> one; the plain or the rates merge, which take
+    as many) over any number of them [R, Q, c + 1, 2 or 3]: groups of up to 16, then the groups' answers, until one is
+    left - both rules are associative."""
     n = tc.ALIGN_CANDIDATES_MERGE_MAX_LISTS
     while gathered.shape[0] > n:
         lib = torch if torch.is_tensor(gathered) else np
@@ -294,11 +321,11 @@ def make_comm(device: int, group=None):
 class _Slot:
     """What one of RcclShardedMatcher's side streams owns: its event, submit's workspace and (merged, totals), and
     align's own pair (its rows are the form's width and `k` is the call's own)."""
-    __slots__ = ("stream", "event", "ws", "out", "near_ws", "near_out", "parts_out", "cand_out")
+    __slots__ = ("stream", "event", "ws", "out", "near_ws", "near_out", "parts_out", "cand_out", "cand_rates_out")
 
     def __init__(self, stream):
         self.stream, self.event = stream, torch.cuda.Event()
-        self.ws = self.out = self.near_ws = self.near_out = self.parts_out = self.cand_out = None
+        self.ws = self.out = self.near_ws = self.near_out = self.parts_out = self.cand_out = self.cand_rates_out = None
 
 
 class RcclShardedMatcher(_AlignForwards):
@@ -504,6 +531,32 @@ class RcclShardedMatcher(_AlignForwards):
         out = self.comm.align_candidates_sharded(self.corpus, d_queries, d_q_offsets, max_query_len, c=c, min_count=min_count,
                                                  cap=cap, d_exclude_ids=d_exclude_ids, workspace=slot.near_ws, stream=st,
                                                  out=slot.cand_out)
+        slot.event.record(st)
+        torch.cuda.current_stream(self.dev).wait_event(slot.event)
+        return out
+
+    supports_align_candidate_rates = "tvz_align_candidates_rates_sharded" in _lib.GAP_RATE_SHARD_SIGNATURES
+
+    def candidates_rates(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, rates, *, c: int,
+                         min_count: int = 2, cap: int = 4096, d_exclude_ids: Optional[torch.Tensor] = None):
+        """ShardedMatcher.candidates_rates behind ONE library call (tvz_align_candidates_rates_sharded): the local
+        tvz_align_candidates_rates -> ncclAllGather of the [Q, c + 1, 3] blocks -> the merge, on the next of the
+        matcher's side streams with the slot's near workspace; the current stream waits for it.  -> int32 [Q, c + 1, 3],
+        this matcher's tensor, overwritten `n_streams` calls later."""
+        slot = self._next_slot()
+        st = slot.stream
+        _, Q = self.corpus._check_queries(d_queries, d_q_offsets)
+        c, rates = int(c), tuple(rates)
+        need = tc.align_candidates_rates_sharded_workspace_bytes(Q, max_query_len, d_queries.numel(), len(rates), cap, c,
+                                                                 self.world)
+        if slot.near_ws is None or slot.near_ws.numel() < need:
+            slot.near_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.dev)
+        if slot.cand_rates_out is None or slot.cand_rates_out.shape != (Q, c + 1, 3):
+            slot.cand_rates_out = torch.empty((Q, max(c, 0) + 1, 3), dtype=torch.int32, device=self.dev)
+        st.wait_stream(torch.cuda.current_stream(self.dev))       # the queries are complete; the slot's last answer is read
+        out = self.comm.align_candidates_rates_sharded(self.corpus, d_queries, d_q_offsets, max_query_len, rates, c=c,
+                                                       min_count=min_count, cap=cap, d_exclude_ids=d_exclude_ids,
+                                                       workspace=slot.near_ws, stream=st, out=slot.cand_rates_out)
         slot.event.record(st)
         torch.cuda.current_stream(self.dev).wait_event(slot.event)
         return out
