@@ -176,6 +176,16 @@ GAP_RATE_SHARD_SIGNATURES = {
                                                      C.c_int32, C.c_int32, _P, _P, C.c_size_t, _P]),
 }
 
+# name -> (restype, argtypes); mirrors include/tvz_parts_flags.h one to one (tvz_align_parts and its _shards form with
+# `flags` behind max_parts)
+PARTS_FLAGS_SIGNATURES = {
+    "tvz_align_parts_flags": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, C.c_int64, C.c_int32, C.c_double,
+                                        C.c_double, _P, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, _P, _P, C.c_size_t, _P]),
+    "tvz_align_parts_flags_shards": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, C.c_int64,
+                                               C.c_int32, C.c_double, C.c_double, _P, C.c_int32, C.c_int32, C.c_int32,
+                                               C.c_uint32, _P, _P, _P, C.c_size_t, _P]),
+}
+
 # per-call selectors of include/tvz.h
 ALGO_AUTO, ALGO_Q1, ALGO_TILE, ALGO_JOIN, ALGO_INDEX = 0, 1, 2, 3, 4
 ALGO_PAIR, ALGO_NO_PAIR = 0x100, 0x200      # OR-ed into `algo` of the top-k calls: two queries per lookup block always / never
@@ -236,7 +246,7 @@ def load() -> C.CDLL:
                                    "rebuild it (python -m tvidz_amd.build --force)")
             for name, (res, args) in (list(SIGNATURES.items()) + list(GAP_SIGNATURES.items()) +
                                       list(GAP_SHARD_SIGNATURES.items()) + list(GAP_RATE_SIGNATURES.items()) +
-                                      list(GAP_RATE_SHARD_SIGNATURES.items())):
+                                      list(GAP_RATE_SHARD_SIGNATURES.items()) + list(PARTS_FLAGS_SIGNATURES.items())):
                 fn = getattr(lib, name)
                 fn.restype = res
                 fn.argtypes = args

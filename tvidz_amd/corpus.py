@@ -512,10 +512,11 @@ def _parts_ids(d_video_ids: torch.Tensor, Q: int, d_queries: torch.Tensor):
 def align_parts_shards(shards: Sequence["DeviceCorpus"], d_queries: torch.Tensor, d_q_offsets: torch.Tensor,
                        max_query_len: int, d_video_ids: torch.Tensor, *, eps: float, max_offset: Optional[float] = None,
                        rates: Sequence[float] = (1.0,), min_votes: int, max_parts: int, workspace: torch.Tensor,
-                       stream: Optional[torch.cuda.Stream] = None):
+                       stream: Optional[torch.cuda.Stream] = None, two_bins: bool = False):
     """tvz_align_parts on every handle of ONE device + the merge behind one library call (tvz_align_parts_shards): ->
     (blocks int32 [R, Q, k, 1 + max_parts, 6], parts int32 [Q, k, 1 + max_parts, 6]).  `workspace`:
-    align_parts_workspace_bytes (its size is the library's to judge, as align_topk_shards')."""
+    align_parts_workspace_bytes (its size is the library's to judge, as align_topk_shards').  `two_bins`: the votes
+    counted over two adjacent bins, through tvz_align_parts_flags_shards (include/tvz_parts_flags.h)."""
     Q = d_q_offsets.numel() - 1
     dev, s, ws, _ = shards[0]._prelude(d_queries, d_q_offsets, None, stream, workspace, None)
     ids, id_stride, query_id_stride, k = _parts_ids(d_video_ids, Q, d_queries)
@@ -523,11 +524,14 @@ def align_parts_shards(shards: Sequence["DeviceCorpus"], d_queries: torch.Tensor
     handles = (C.c_void_p * R)(*[sh._h for sh in shards])
     blocks = torch.empty((R, Q, k, 1 + max(P, 0), 6), dtype=torch.int32, device=dev)
     parts = torch.empty((Q, k, 1 + max(P, 0), 6), dtype=torch.int32, device=dev)
+    front = (handles, R, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), ids, id_stride, query_id_stride,
+             k, float(eps), _wide_offset(eps, max_offset), *_rates(rates), int(min_votes), P)
+    back = (blocks.data_ptr(), parts.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream)
     with torch.cuda.device(dev):
-        _lib.check(_lib.load().tvz_align_parts_shards(
-            handles, R, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), ids, id_stride, query_id_stride,
-            k, float(eps), _wide_offset(eps, max_offset), *_rates(rates), int(min_votes), P, blocks.data_ptr(),
-            parts.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
+        if two_bins:
+            _lib.check(_lib.load().tvz_align_parts_flags_shards(*front, ALIGN_TWO_BINS, *back))
+        else:
+            _lib.check(_lib.load().tvz_align_parts_shards(*front, *back))
     return blocks, parts
 
 
@@ -873,7 +877,7 @@ class DeviceCorpus:
 
     def align_parts(self, queries, video_ids, *, eps: float, max_offset: Optional[float] = None,
                     rates: Sequence[float] = (1.0,), min_votes: int, max_parts: int,
-                    max_query_len: Optional[int] = None):
+                    max_query_len: Optional[int] = None, two_bins: bool = False):
         """tvz_align_parts: EVERY aligned part of named stored videos - the refinement behind a search, for the copy
         with a part put in or taken out, which aligns at two shifts.  `queries` as align_topk takes them; `video_ids`:
         up to k stored video ids per query as an int32 [Q][k] array (list, numpy, device tensor) or any strided 2-D
@@ -881,33 +885,42 @@ class DeviceCorpus:
         no pair.  Every pair is aligned in full at the best of `rates` and up to `max_parts` (1..ALIGN_MAX_PARTS)
         disjoint parts of at least `min_votes` votes are reported.  -> int32 [Q, k, 1 + max_parts, 6] as a numpy
         array: row 0 (video_id, row_len, rate_index, n_parts, n_rows, m), then per part (bin, votes, t_first, t_last,
-        nq, nr), zeros beyond n_parts; n_parts = ALIGN_REFUSED marks a refused pair (include/tvz.h)."""
+        nq, nr), zeros beyond n_parts; n_parts = ALIGN_REFUSED marks a refused pair (include/tvz.h).
+        `two_bins=True` (tvz_align_parts_flags with TVZ_ALIGN_TWO_BINS, include/tvz_parts_flags.h): every part is the
+        best window of two adjacent bins - bin = the lower one, votes = both bins', shift = (bin + 0.5) x eps."""
         dev = torch.device("cuda", self.device)
         d_q, d_off, Q, max_query_len, _ = align_inputs(queries, None, max_query_len, dev)
         d_ids = align_parts_ids(video_ids, Q, dev)
         ws = thread_workspace(self._tls, align_parts_workspace_bytes(Q, max_query_len, d_q.numel(), d_ids.shape[1], max_parts),
                               dev)
         return self.align_parts_block(d_q, d_off, max_query_len, d_ids, eps=eps, max_offset=max_offset, rates=rates,
-                                      min_votes=min_votes, max_parts=max_parts, workspace=ws).cpu().numpy()
+                                      min_votes=min_votes, max_parts=max_parts, workspace=ws,
+                                      **({"two_bins": True} if two_bins else {})).cpu().numpy()
 
     def align_parts_block(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int,
                           d_video_ids: torch.Tensor, *, eps: float, max_offset: Optional[float] = None,
                           rates: Sequence[float] = (1.0,), min_votes: int, max_parts: int,
                           out: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
-                          workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+                          workspace: Optional[torch.Tensor] = None, two_bins: bool = False) -> torch.Tensor:
         """tvz_align_parts, device in / device out: enqueue Q x k pairs -> int32 [Q, k, 1 + max_parts, 6].
-        `d_video_ids`: a 2-D int32 view [Q, k] on this device, of any strides."""
+        `d_video_ids`: a 2-D int32 view [Q, k] on this device, of any strides.  `two_bins`: tvz_align_parts_flags with
+        TVZ_ALIGN_TWO_BINS; False calls tvz_align_parts itself."""
         Q = d_q_offsets.numel() - 1
         ids, id_stride, query_id_stride, k = _parts_ids(d_video_ids, Q, d_queries)
         P = int(max_parts)
         dev, s, ws, _ = self._prelude(d_queries, d_q_offsets, None, stream, workspace,
                                       align_parts_workspace_bytes(Q, max_query_len, d_queries.numel(), k, P))
         out = _out(out, (Q, k, 1 + max(P, 0), 6), dev)
-        _lib.check(self.lib.tvz_align_parts(self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len),
-                                            ids, id_stride, query_id_stride, k, float(eps),
-                                            _wide_offset(eps, max_offset), *_rates(rates), int(min_votes), P,
-                                            out.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
+        front = (self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len), ids, id_stride, query_id_stride,
+                 k, float(eps), _wide_offset(eps, max_offset), *_rates(rates), int(min_votes), P)
+        back = (out.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream)
+        if two_bins:
+            _lib.check(self.lib.tvz_align_parts_flags(*front, ALIGN_TWO_BINS, *back))
+        else:
+            _lib.check(self.lib.tvz_align_parts(*front, *back))
         return out
+
+    supports_align_parts_two_bins = "tvz_align_parts_flags" in _lib.PARTS_FLAGS_SIGNATURES
 
     def _align_host(self, f: AlignForm, queries, k, exclude_ids, max_query_len, **ask):
         """Any form, host in / host out: the inputs, the calling thread's workspace, the block call, ONE copy back,

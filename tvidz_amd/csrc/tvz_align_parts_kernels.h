@@ -29,6 +29,9 @@
 //                            ranges, which live in registers (ApRanges: constant indices only).  After each part
 //                            the four extremes (al_bin_extremes with ApOutside) and one counting pass each for nr
 //                            and nq.  A slot's result goes to the workspace: int32[1 + max_parts][6].
+//   ts_alignp2_walk_kernel   the same walk under TVZ_ALIGN_TWO_BINS (tvz_align_parts_flags, include/tvz_parts_flags.h;
+//                            DESIGN.md 4.20): every part is the best WINDOW of two adjacent bins (ap_votes<.., true>,
+//                            al_bin_extremes<ApOutside, true>), launched in the walk's place; locate and pick are shared.
 //   ts_alignp_pick_kernel    a wave per pair: the slot with the most part-0 votes, the earlier row of the table on a
 //                            tie (the slots fill in no fixed order: the row's index decides), is copied out with
 //                            n_rows and m in its header and zeros behind n_parts; or the refused / absent / no-pair
@@ -114,7 +117,12 @@ struct ApOutside {
 // whose t and c lie outside the ranges of `ex` vote - a key inside a range is skipped whole, an index inside one is
 // walked over (the run's end is found by the expression, which does not know the ranges).  c_min / c_max: the row's
 // smallest and largest key.  The histogram is clean on entry and on return.  m >= 1, len >= 1.
-template <bool kExcl>
+// kTwoBins (tvz_align_parts_flags with TVZ_ALIGN_TWO_BINS): the best WINDOW of two adjacent bins, as
+// al_sweep<.., kTwoBins> finds it -> J << 33 | (2^33 - 1 - order of the lower bin).  The vote loop tracks nothing; the
+// windows' counts are read in the pass over the touched list, where every count is final.  The count of the bin above a
+// window's last slot is carried in one word, read from hist[0] before the clearing: it starts at 0 in every call - per
+// rate, per part, per row - and under kExcl it is a count of ALLOWED votes, because only those reach the histogram.
+template <bool kExcl, bool kTwoBins = false>
 __device__ __forceinline__ unsigned long long ap_votes(const int64_t *__restrict__ rk, int len, const double *s, int m, double eps,
                                                        int32_t B, double c_min, double c_max, double rho, const AlWave &w,
                                                        const ApRanges &ex, int lane) {
@@ -132,6 +140,8 @@ __device__ __forceinline__ unsigned long long ap_votes(const int64_t *__restrict
     w1 = __builtin_amdgcn_readfirstlane(w1);
     w1 = w1 < w.max_windows - 1 ? w1 : w.max_windows - 1;
     unsigned long long best = 0;
+    [[maybe_unused]] uint32_t jbest = 0;                                  // kTwoBins: the lane's best window (J, h << 33 | ..)
+    [[maybe_unused]] uint32_t carry = 0;                                  // ... and the lowest bin's count of the window above
     for (int wi = w1; wi >= w0; --wi) {                                   // wave-uniform
         const int w_lo = wi * w.width - B;
         const int w_hi = w_lo + w.width - 1 < B ? w_lo + w.width - 1 : B;
@@ -150,21 +160,51 @@ __device__ __forceinline__ unsigned long long ap_votes(const int64_t *__restrict
                 const uint32_t slot = (uint32_t)(bin - w_lo);             // 0 .. width - 1
                 const uint32_t cnt = atomicAdd(&w.hist[slot], 1u) + 1u;
                 if (cnt == 1u) w.dirty[atomicAdd(w.n_dirty, 1u)] = (uint16_t)slot;      // at most once per slot: < width
-                const uint32_t order = 2u * (uint32_t)(bin < 0 ? -bin : bin) + (bin > 0 ? 1u : 0u);
-                const unsigned long long key = ((unsigned long long)cnt << 33) | (kAlOrderMask - order);
-                best = key > best ? key : best;
+                if constexpr (!kTwoBins) {
+                    const uint32_t order = 2u * (uint32_t)(bin < 0 ? -bin : bin) + (bin > 0 ? 1u : 0u);
+                    const unsigned long long key = ((unsigned long long)cnt << 33) | (kAlOrderMask - order);
+                    best = key > best ? key : best;
+                }
             }
             if (kept_pos) w.resume[j] = (uint16_t)t;                      // t <= m <= 4095
         }
         wave_lds_fence();
         const int nd = (int)*w.n_dirty;
+        if constexpr (kTwoBins) {
+            // every count is final.  Slot + 1 inside the histogram is bin b + 1, the padding slot or a bin beyond B,
+            // which no vote reaches (0); behind the last slot b + 1 is the lowest bin of the window above: the carry
+            for (int i = lane; i < nd; i += 64) {
+                const int slot = (int)w.dirty[i];                         // < width
+                const uint32_t h = w.hist[slot];
+                const uint32_t up = slot + 1 < w.width ? w.hist[slot + 1] : carry;
+                const int bin = w_lo + slot;
+                const uint32_t order = 2u * (uint32_t)(bin < 0 ? -bin : bin) + (bin > 0 ? 1u : 0u);
+                const uint32_t j = h + up;
+                const unsigned long long key = ((unsigned long long)h << 33) | (kAlOrderMask - order);
+                const bool better = j > jbest || (j == jbest && key > best);
+                jbest = better ? j : jbest;
+                best = better ? key : best;
+            }
+            carry = w.hist[0];                                            // (the same word in every lane)
+        }
         for (int i = lane; i < nd; i += 64) w.hist[w.dirty[i]] = 0;
         wave_lds_fence();
         if (lane == 0) *w.n_dirty = 0;
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(best, off);
-        best = o > best ? o : best;
+    if constexpr (kTwoBins) {
+        for (int off = 32; off > 0; off >>= 1) {
+            const uint32_t oj = __shfl_xor(jbest, off);
+            const unsigned long long o = __shfl_xor(best, off);
+            const bool better = oj > jbest || (oj == jbest && o > best);
+            jbest = better ? oj : jbest;
+            best = better ? o : best;
+        }
+        best = ((unsigned long long)jbest << 33) | (best & kAlOrderMask);     // the window's count and its lower bin
+    } else {
+        for (int off = 32; off > 0; off >>= 1) {
+            const unsigned long long o = __shfl_xor(best, off);
+            best = o > best ? o : best;
+        }
     }
     return best;
 }
@@ -198,6 +238,100 @@ __global__ __launch_bounds__(kApLocateBlock) void ts_alignp_locate_kernel(
 // kApMaxRows + n) * ap_words(max_parts) ..): the header (video_id, row_len, rate_index, n_parts, 0, m) and per part
 // (bin, votes, t_first, t_last, nq, nr) - part 0's row always (zeros without a vote: the pick orders the slots by its
 // votes), a later part's only when it is reported.  1 <= max_parts <= kApMaxParts, min_votes >= 1, rates.n >= 1.
+// kTwoBins (ts_alignp2_walk_kernel): every part is the best window of two adjacent bins - bin = the lower one, votes = J,
+// the extremes and nq / nr over the pairs of both bins, the upper one only inside [-B, B].
+template <bool kTwoBins>
+__device__ __forceinline__ void ap_walk(
+    const Row *__restrict__ rows, const int64_t *__restrict__ keys, const double *__restrict__ sv,
+    const int64_t *__restrict__ q_offsets, const int32_t *__restrict__ qm, int32_t lds_keys, double eps, int32_t B, int32_t width,
+    const AlRates &rates, int32_t min_votes, int32_t max_parts, const int32_t *__restrict__ ids, int64_t id_stride,
+    int64_t query_id_stride, int32_t k, const int32_t *__restrict__ counts, const int64_t *__restrict__ slots,
+    int32_t *__restrict__ scratch) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int j = blockIdx.x, q = blockIdx.y;
+    const int64_t pair = (int64_t)q * k + j;
+    const int32_t m = qm[q];
+    const int32_t id = ids[(int64_t)q * query_id_stride + (int64_t)j * id_stride];
+    const int32_t n_slots = counts[pair];
+    if (m < 0 || m > lds_keys || id < 0 || n_slots <= 0 || n_slots > kApMaxRows) return;     // block-uniform
+    const int64_t at = q_offsets[q] - q_offsets[0];
+    const int lane = threadIdx.x & 63;
+    const int wv = threadIdx.x >> 6;
+    double *s = reinterpret_cast<double *>(smem);
+    const AlWave w = al_wave<true>(smem, lds_keys, B, width, wv);
+    for (int e = threadIdx.x; e < m; e += kAlBlock) s[e] = sv[at + e];
+    al_wave_clear(w, lane);
+    __syncthreads();
+
+    const int words = ap_words(max_parts);
+    for (int slot = wv; slot < n_slots; slot += kAlWaves) {               // wave-uniform: no block barrier inside
+        const Row row = load_row(rows + slots[pair * kApMaxRows + slot]);
+        const int64_t *rk = keys + row.off;
+        int32_t *o = scratch + (pair * kApMaxRows + slot) * words;
+        const AlKeyRange kr = al_key_range(rk, row.len, lane);
+        ApRanges ex = ap_no_ranges();
+        unsigned long long best = 0;                                      // part 0: the kept rate's
+        uint32_t best_rate = 0;
+        if (m > 0 && row.len > 0) {
+            for (int ri = 0; ri < rates.n; ++ri) {                        // wave-uniform
+                const unsigned long long rbest =
+                    ap_votes<false, kTwoBins>(rk, row.len, s, m, eps, B, kr.c_min, kr.c_max, rates.r[ri], w, ex, lane);
+                if ((rbest >> 33) > (best >> 33)) {                       // strictly more votes: a tie keeps the smaller index
+                    best = rbest;
+                    best_rate = (uint32_t)ri;
+                }
+            }
+        }
+        const double rho = rates.r[best_rate];
+        int32_t n_parts = 0;
+        for (int p = 0; p < max_parts; ++p) {                             // wave-uniform
+            if (p > 0) best = ap_votes<true, kTwoBins>(rk, row.len, s, m, eps, B, kr.c_min, kr.c_max, rho, w, ex, lane);
+            const int32_t votes = (int32_t)(best >> 33);
+            if (votes < min_votes && p > 0) break;
+            int32_t part[kApCols] = {0, 0, 0, 0, 0, 0};
+            if (votes > 0) {
+                const int bin = al_best_bin(best);
+                const AlExtremes x = al_bin_extremes<ApOutside, kTwoBins>(rk, row.len, s, m, eps, bin, rho, ApOutside{ex}, lane,
+                                                                          bin < B ? bin + 1 : bin);
+                int32_t nq = 0, nr = 0;
+                for (int t = x.t_first + lane; t <= x.t_last; t += 64) nq += ap_t_free(ex, t) ? 1 : 0;
+                for (int i = lane; i < row.len; i += 64) {
+                    const double c = __longlong_as_double(rk[i]);
+                    nr += c >= x.c_lo && c <= x.c_hi && ap_c_free(ex, c) ? 1 : 0;
+                }
+                for (int off = 32; off > 0; off >>= 1) {
+                    nq += __shfl_xor(nq, off);
+                    nr += __shfl_xor(nr, off);
+                }
+                part[0] = bin;
+                part[1] = votes;
+                part[2] = x.t_first;
+                part[3] = x.t_last;
+                part[4] = nq;
+                part[5] = nr;
+                ap_push(ex, x.t_first, x.t_last, x.c_lo, x.c_hi);
+            }
+            if (lane == 0) {
+#pragma unroll
+                for (int i = 0; i < kApCols; ++i) o[(1 + p) * kApCols + i] = part[i];
+            }
+            if (votes < min_votes) break;                                 // part 0 below the bar: written, not reported
+            n_parts = p + 1;
+        }
+        if (lane == 0) {
+            o[0] = row.vid;
+            o[1] = row.len;
+            o[2] = (int32_t)best_rate;
+            o[3] = n_parts;
+            o[4] = 0;
+            o[5] = m;
+        }
+    }
+}
+
+// The single-bin walk keeps a body of its own, word for word ap_walk<false>: forwarding it to the template moved its
+// machine code (9,348 -> 9,296 bytes, 95 -> 93 SGPRs, by value or by reference alike), as moving ap_votes and al_sweep
+// into one function did.  A change of the walk is made in both.
 __global__ __launch_bounds__(kAlBlock) void ts_alignp_walk_kernel(
     const Row *__restrict__ rows, const int64_t *__restrict__ keys, const double *__restrict__ sv,
     const int64_t *__restrict__ q_offsets, const int32_t *__restrict__ qm, int32_t lds_keys, double eps, int32_t B, int32_t width,
@@ -283,6 +417,17 @@ __global__ __launch_bounds__(kAlBlock) void ts_alignp_walk_kernel(
             o[5] = m;
         }
     }
+}
+
+// TVZ_ALIGN_TWO_BINS (tvz_align_parts_flags): a kernel of its own, the same argument list
+__global__ __launch_bounds__(kAlBlock) void ts_alignp2_walk_kernel(
+    const Row *__restrict__ rows, const int64_t *__restrict__ keys, const double *__restrict__ sv,
+    const int64_t *__restrict__ q_offsets, const int32_t *__restrict__ qm, int32_t lds_keys, double eps, int32_t B, int32_t width,
+    AlRates rates, int32_t min_votes, int32_t max_parts, const int32_t *__restrict__ ids, int64_t id_stride,
+    int64_t query_id_stride, int32_t k, const int32_t *__restrict__ counts, const int64_t *__restrict__ slots,
+    int32_t *__restrict__ scratch) {
+    ap_walk<true>(rows, keys, sv, q_offsets, qm, lds_keys, eps, B, width, rates, min_votes, max_parts, ids, id_stride,
+                  query_id_stride, k, counts, slots, scratch);
 }
 
 // grid = ceil(Q * k / kApPickWaves), a wave per pair -> d_parts int32[Q][k][1 + max_parts][6].  Row 0 is (video_id,

@@ -123,6 +123,7 @@ struct AlignPartsCall {
     double eps, max_offset;
     const double *h_rates;
     int32_t n_rates, min_votes, max_parts;
+    uint32_t flags = 0;              // tvz_align_parts_flags: 0 or TVZ_ALIGN_TWO_BINS; the calls without flags leave it 0
 };
 int tvz_align_parts_local(tvz_corpus *c, const Batch &b, const AlignPartsCall &p, int32_t *d_parts, Workspace ws, int32_t n_ranks,
                           void *hip_stream, ShardBlocks *blocks, LateCheck late = {});

@@ -33,6 +33,7 @@
 #include "tvz_gap_shards.h"
 #include "tvz_gap_rates.h"
 #include "tvz_gap_rates_shards.h"
+#include "tvz_parts_flags.h"
 #include "tvz_handle.h"
 #include "tvz_index_build.h"
 
@@ -2435,12 +2436,12 @@ size_t align_parts_sizing(int32_t Q, int32_t max_query_len, int64_t total_query_
 // The call in messages and limits: no entry of kAlignForms (it keeps no hit), only what the shared checks read of one -
 // the name, the two sizing functions and the bins' limit.
 constexpr AlignTopkForm kAlignPartsForm = {kApCols, 0, true, true, "alignment parts", "tvz_align_parts_workspace_bytes",
-                                           "tvz_align_parts_sharded_workspace_bytes", 2 * kAwMaxB + 1, "TVZ_ALIGN_WIDE_MAX_B", 0u,
-                                           0u, 0, nullptr, nullptr, nullptr};
+                                           "tvz_align_parts_sharded_workspace_bytes", 2 * kAwMaxB + 1, "TVZ_ALIGN_WIDE_MAX_B",
+                                           kAlTwoBins, 0u, 0, nullptr, nullptr, nullptr};
 
 // Everything of a parts call that needs neither the handle nor the device is refused first, for the call and for its
 // _shards and _sharded forms alike, in the span call's order: the rate list (-> *rates), min_votes, k, the query limit;
-// then max_parts and the bins (-> *B).
+// then max_parts, the flags (tvz_align_parts_flags; 0 from the calls that have none) and the bins (-> *B).
 int check_align_parts_early(const Batch &b, const AlignPartsCall &p, AlRates *rates, int32_t *B) {
     const AlignTopkForm &f = kAlignPartsForm;
     if (int rc = check_align_rates(p.h_rates, p.n_rates, rates)) return rc;
@@ -2448,6 +2449,7 @@ int check_align_parts_early(const Batch &b, const AlignPartsCall &p, AlRates *ra
     if (p.max_parts < 1 || p.max_parts > kApMaxParts)
         return tvz::fail(TVZ_ERR_UNSUPPORTED, "%s: max_parts=%d outside 1..%d (TVZ_ALIGN_MAX_PARTS)", f.what, (int)p.max_parts,
                          kApMaxParts);
+    if (int rc = check_align_flags(f, p.flags, "")) return rc;
     return check_align_bins(p.eps, p.max_offset, f.max_bins, f.bins_limit, B);
 }
 
@@ -2487,7 +2489,8 @@ int align_parts_run(tvz_corpus *c, const Batch &b, const AlignPartsCall &p, cons
         hipLaunchKernelGGL(ts_alignp_locate_kernel, dim3(row_blocks, (unsigned)Q), dim3(kApLocateBlock), 0, st, c->rows.p, n_rows,
                            d_video_ids, id_stride, query_id_stride, k, w.counts, w.slots);
         TVZ_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ts_alignp_walk_kernel, dim3((unsigned)k, (unsigned)Q), dim3(kAlBlock), lds.bytes, st, c->rows.p,
+        const auto walk = (p.flags & kAlTwoBins) ? ts_alignp2_walk_kernel : ts_alignp_walk_kernel;   // (one argument list)
+        hipLaunchKernelGGL(walk, dim3((unsigned)k, (unsigned)Q), dim3(kAlBlock), lds.bytes, st, c->rows.p,
                            c->keys.p, t.ws.sv, b.d_q_offsets, t.ws.qm, lds.lds_keys, eps, B, lds.width, rates, min_votes, max_parts,
                            d_video_ids, id_stride, query_id_stride, k, w.counts, w.slots, w.scratch);
         TVZ_HIP(hipGetLastError());
@@ -3358,6 +3361,30 @@ TVZ_EXPORT int tvz_align_parts_shards(tvz_corpus *const *shards, int32_t n_shard
     TVZ_GUARDED(align_parts_shards_impl(shards, n_shards, align_batch(d_queries, d_q_offsets, Q, max_query_len, nullptr),
                                         AlignPartsCall{d_video_ids, id_stride, query_id_stride, k, eps, max_offset, h_rates,
                                                        n_rates, min_votes, max_parts},
+                                        d_blocks, d_parts, Workspace{d_workspace, workspace_bytes}, hip_stream));
+}
+
+// include/tvz_parts_flags.h: the two calls above with `flags` behind max_parts (0: the same walk; TVZ_ALIGN_TWO_BINS)
+TVZ_EXPORT int tvz_align_parts_flags(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
+                                     int32_t max_query_len, const int32_t *d_video_ids, int64_t id_stride,
+                                     int64_t query_id_stride, int32_t k, double eps, double max_offset, const double *h_rates,
+                                     int32_t n_rates, int32_t min_votes, int32_t max_parts, uint32_t flags, int32_t *d_parts,
+                                     void *d_workspace, size_t workspace_bytes, void *hip_stream) {
+    TVZ_GUARDED(align_parts_call(c, align_batch(d_queries, d_q_offsets, Q, max_query_len, nullptr),
+                                 AlignPartsCall{d_video_ids, id_stride, query_id_stride, k, eps, max_offset, h_rates, n_rates,
+                                                min_votes, max_parts, flags},
+                                 d_parts, Workspace{d_workspace, workspace_bytes}, 0, hip_stream, nullptr));
+}
+
+TVZ_EXPORT int tvz_align_parts_flags_shards(tvz_corpus *const *shards, int32_t n_shards, const double *d_queries,
+                                            const int64_t *d_q_offsets, int32_t Q, int32_t max_query_len,
+                                            const int32_t *d_video_ids, int64_t id_stride, int64_t query_id_stride, int32_t k,
+                                            double eps, double max_offset, const double *h_rates, int32_t n_rates,
+                                            int32_t min_votes, int32_t max_parts, uint32_t flags, int32_t *d_blocks,
+                                            int32_t *d_parts, void *d_workspace, size_t workspace_bytes, void *hip_stream) {
+    TVZ_GUARDED(align_parts_shards_impl(shards, n_shards, align_batch(d_queries, d_q_offsets, Q, max_query_len, nullptr),
+                                        AlignPartsCall{d_video_ids, id_stride, query_id_stride, k, eps, max_offset, h_rates,
+                                                       n_rates, min_votes, max_parts, flags},
                                         d_blocks, d_parts, Workspace{d_workspace, workspace_bytes}, hip_stream));
 }
 

@@ -95,7 +95,7 @@ class Inspector:
                  near_any_offset: bool = False, near_score: str = "jaccard", near_min_votes: int = 1,
                  near_rates=None, near_spans: bool = False, near_parts: Optional[int] = None,
                  near_two_bins: bool = False, near_candidates: Optional[int] = None, near_gap_eps: float = 1.0 / 30,
-                 near_candidate_rates: bool = False):
+                 near_candidate_rates: bool = False, near_parts_two_bins: bool = False):
         self.store = store
         # opt-in: the near-duplicate report from the K best-aligned rows the device keeps (tvz_align_topk) instead of
         # one row per corpus row walked here.  None: the walk, exactly as before.  Refused here where the store's
@@ -177,11 +177,22 @@ class Inspector:
         # near_any_offset that is align_wide_topk with max_offset=near_max_offset (the bounded call's answer for its
         # range).  best_bin is then the window's lower bin, so shift_seconds is (best_bin + 0.5) x near_eps.
         # tvz_align_parts has no flags argument: near_parts with it is refused.  False: nothing changes.
+        # near_parts_two_bins=True turns the combination with near_parts and with near_candidates ON: the parts call
+        # goes through tvz_align_parts_flags with TVZ_ALIGN_TWO_BINS (align_parts(two_bins=True)), every part is a
+        # window of two bins and its shift is (bin + 0.5) x near_eps.  False: refused as before.
         self.near_two_bins = bool(near_two_bins)
+        self.near_parts_two_bins = bool(near_parts_two_bins)
+        if self.near_parts_two_bins:
+            if not self.near_two_bins or (near_parts is None and near_candidates is None):
+                raise ValueError("near_parts_two_bins=True needs near_two_bins=True and near_parts or near_candidates")
+            if not getattr(getattr(store, "corpus", None), "supports_align_parts_two_bins", False):
+                raise RuntimeError(f"near_parts_two_bins=True: the store's corpus "
+                                   f"({type(getattr(store, 'corpus', None)).__name__}) has no align_parts over two bins "
+                                   "(supports_align_parts_two_bins); use a DeviceCorpus or a service.ShardedCorpus")
         if self.near_two_bins:
             if not near_duplicates or self.near_top_k is None:
                 raise ValueError("near_two_bins=True needs near_duplicates=True and near_top_k")
-            if self.near_parts is not None:
+            if self.near_parts is not None and not self.near_parts_two_bins:
                 raise ValueError(f"near_two_bins=True with near_parts={self.near_parts}: align_parts counts single bins "
                                  "(it has no flags); use one of them")
             if not _corpus_can(getattr(store, "corpus", None), "align_wide_topk", "supports_align_wide"):
@@ -192,8 +203,9 @@ class Inspector:
         # the most gap codes with the upload (tvz_align_candidates over the corpus's gap index of near_gap_eps seconds,
         # turned on here, once) are aligned in full by one align_parts call, and the report is made from its part 0 with
         # the same score, thresholds and order as the sweep's.  Codes are made at rate 1 and the parts call counts single
-        # bins: refused with near_rates and near_two_bins.  An upload the candidates call refuses (more than 514 cuts)
-        # takes the configured sweep.  None: nothing changes.
+        # bins: refused with near_rates and near_two_bins (the latter unless near_parts_two_bins turns the parts call's
+        # flag on, above).  An upload the candidates call refuses (more than 514 cuts) takes the configured sweep.
+        # None: nothing changes.
         # near_candidate_rates=True turns the combination with near_rates ON: the stored codes stay at rate 1 and the
         # upload is probed once per rate (tvz_align_candidates_rates), the parts call aligns the named videos at the same
         # rate list and every entry carries its "rate", as the rates sweep's entries do.  False: refused as before.
@@ -217,7 +229,7 @@ class Inspector:
             if self.near_rates is not None and not self.near_candidate_rates:
                 raise RuntimeError(f"{what} with near_rates={self.near_rates}: the gap codes are made at rate 1; "
                                    "use one of them")
-            if self.near_two_bins:
+            if self.near_two_bins and not self.near_parts_two_bins:
                 raise RuntimeError(f"{what} with near_two_bins=True: align_parts counts single bins (it has no flags); "
                                    "use one of them")
             corpus = getattr(store, "corpus", None)
@@ -516,14 +528,17 @@ class Inspector:
     def _near_parts(self, out, scene_timestamps) -> None:
         """near_parts: ONE align_parts call for the reported ids; every entry whose pair was not refused gains "parts" -
         per part the shift, the spans (as "upload_span" / "stored_span" are made) and the raw votes - and
-        "parts_score": with v = the sum of min(votes_i, nq_i, nr_i), v / (sum nq_i + sum nr_i - v)."""
+        "parts_score": with v = the sum of min(votes_i, nq_i, nr_i), v / (sum nq_i + sum nr_i - v).
+        near_parts_two_bins: the call counts over two bins, and a part's shift is its window's middle."""
         rates = self.near_rates or (1.0,)
+        half = 0.5 if self.near_parts_two_bins else 0.0
         kept = getattr(self._tls, "candidate_parts", None) if self.near_candidates is not None else None
         if kept is not None:                                                   # near_candidates: the search's own parts block
             blocks = [kept[d["video_id"]] for d in out]
         else:
             blocks = self.store.corpus.align_parts([scene_timestamps], [[d["video_id"] for d in out]], eps=self.near_eps,
-                                                   rates=rates, min_votes=self.near_min_votes, max_parts=self.near_parts)[0]
+                                                   rates=rates, min_votes=self.near_min_votes, max_parts=self.near_parts,
+                                                   **self._parts_two_bins())[0]
         cuts = np.sort(np.asarray(scene_timestamps, dtype=np.float64))
         cuts = cuts[~np.isnan(cuts)]
         for d, block in zip(out, blocks):
@@ -532,13 +547,17 @@ class Inspector:
                 continue
             rate, parts, v, u = rates[int(block[0][2])], [], 0, 0
             for best_bin, votes, t_first, t_last, nq, nr in (tuple(int(x) for x in p) for p in block[1:1 + n]):
-                shift, first, last = float(best_bin) * self.near_eps, float(cuts[t_first]), float(cuts[t_last])
+                shift, first, last = (float(best_bin) + half) * self.near_eps, float(cuts[t_first]), float(cuts[t_last])
                 parts.append({"shift_seconds": shift, "upload_span": [first, last],
                               "stored_span": [rate * first + shift, rate * last + shift], "votes": votes})
                 v += min(votes, nq, nr)
                 u += nq + nr
             d["parts"] = parts
             d["parts_score"] = round(v / float(u - v), 4) if u > v else 0.0
+
+    def _parts_two_bins(self) -> dict:
+        """what near_parts_two_bins adds to an align_parts call (told only where it is set)"""
+        return {"two_bins": True} if self.near_parts_two_bins else {}
 
     def _near_candidates(self, video_id: int, scene_timestamps):
         """near_candidates: the rows _near filters, made without a sweep - ONE align_candidates call names the stored
@@ -565,7 +584,7 @@ class Inspector:
         if not ids:
             return []
         blocks = corpus.align_parts([scene_timestamps], [ids], eps=self.near_eps, rates=rates, min_votes=self.near_min_votes,
-                                    max_parts=self.near_parts or 1)[0]
+                                    max_parts=self.near_parts or 1, **self._parts_two_bins())[0]
         one = 1 << 20
         min_score = max(0, min(one, int(self.near_jaccard * one)))
         contain, local = self.near_score == "containment", self.near_score == "local"
@@ -601,7 +620,7 @@ class Inspector:
             self._tls.candidate_parts = None
             rows = self._near_candidates(video_id, scene_timestamps)
             if rows is not None:                                               # (None: refused -> the configured sweep)
-                return rows, self.near_candidate_rates, 0.0
+                return rows, self.near_candidate_rates, 0.5 if self.near_parts_two_bins else 0.0
         if self.near_top_k is not None:
             one = 1 << 20
             min_score = max(0, min(one, int(self.near_jaccard * one)))          # int() floors: the value is >= 0

@@ -322,15 +322,18 @@ class ShardedCorpus:
                                  min_votes=min_votes, min_score=min_score, rates=tuple(rates), contain=contain, local=local,
                                  two_bins=two_bins)
 
+    supports_align_parts_two_bins = tc.DeviceCorpus.supports_align_parts_two_bins
+
     def align_parts(self, queries, video_ids, *, eps: float, max_offset=None, rates=(1.0,), min_votes: int,
-                    max_parts: int, max_query_len=None):
+                    max_parts: int, max_query_len=None, two_bins: bool = False):
         """DeviceCorpus.align_parts over every shard: ONE library call (tvz_align_parts_shards) asks every shard for
         every pair with the calling thread's one workspace and merges the answers on the device - per pair the one with
         the most part-0 votes is kept, the lower shard on a tie (what corpus.align_parts_merge computes on the host);
         n_rows is the shards' sum - and ONE copy brings the answer back.  More than ALIGN_PARTS_MAX_ROWS rows of one id
         refuse the pair only where they lie in ONE shard.  More than 16 shards (the merge takes up to 16 lists): one such
         call per group of 16, the groups' answers merged again by tvz_align_parts_merge; still one copy back, same
-        answer (the rule is associative)."""
+        answer (the rule is associative).  `two_bins=True`: tvz_align_parts_flags_shards with TVZ_ALIGN_TWO_BINS per
+        group (include/tvz_parts_flags.h) and the same merge, which orders by part-0 votes however they were counted."""
         dev = self.dev
         d_q, d_off, Q, max_query_len, _ = tc.align_inputs(queries, None, max_query_len, dev)
         d_ids = tc.align_parts_ids(video_ids, Q, dev)
@@ -339,7 +342,8 @@ class ShardedCorpus:
         with torch.cuda.device(dev):
             groups = [self.shards[i:i + 16] for i in range(0, self.R, 16)]      # the merge takes up to 16 lists
             answers = [tc.align_parts_shards(g, d_q, d_off, max_query_len, d_ids, eps=eps, max_offset=max_offset,
-                                             rates=tuple(rates), min_votes=min_votes, max_parts=max_parts, workspace=ws)[1]
+                                             rates=tuple(rates), min_votes=min_votes, max_parts=max_parts, workspace=ws,
+                                             **({"two_bins": True} if two_bins else {}))[1]
                        for g in groups]
             out = answers[0] if len(answers) == 1 else tc.align_parts_merge_device(torch.stack(answers))
             return out.cpu().numpy()
