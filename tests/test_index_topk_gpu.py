@@ -2,7 +2,12 @@
 tvz_match_topk / tvz_match_sharded take on an indexed corpus) against the oracle's restatement of
 db.find_duplicates (inspector/db.py:76-94) ordered as the streaming verdict needs it (earliest prefix
 first, inspector/app.py:238-245: ascending kth, then video_id), and against the unfused pipeline
-(tvz_match -> tvz_topk_shard).  Bit-exact rows, totals and padding."""
+(tvz_match -> tvz_topk_shard).  Bit-exact rows, totals and padding.
+
+The corpora here are random, plus a few large special cases: they cross the kernels' internal limits by accident.  The
+limits themselves - the per-wave posting cache, the trips, chunks, parts, the histogram and the kept list, the pair
+form's LDS bound, the one-wave kernel's register range - are walked at N - 1, N, N + 1 by tests/test_lookup_edges_gpu.py
+(cases: tests/lookup_cases.py)."""
 import numpy as np
 import pytest
 import torch
