@@ -176,6 +176,13 @@ GAP_RATE_SHARD_SIGNATURES = {
                                                      C.c_int32, C.c_int32, _P, _P, C.c_size_t, _P]),
 }
 
+# name -> (restype, argtypes); mirrors include/tvz_gap_long.h one to one (the candidates for uploads of up to 4,095 values)
+GAP_LONG_SIGNATURES = {
+    "tvz_align_candidates_long_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
+    "tvz_align_candidates_long": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P,
+                                            C.c_size_t, _P]),
+}
+
 # name -> (restype, argtypes); mirrors include/tvz_parts_flags.h one to one (tvz_align_parts and its _shards form with
 # `flags` behind max_parts)
 PARTS_FLAGS_SIGNATURES = {
@@ -246,7 +253,8 @@ def load() -> C.CDLL:
                                    "rebuild it (python -m tvidz_amd.build --force)")
             for name, (res, args) in (list(SIGNATURES.items()) + list(GAP_SIGNATURES.items()) +
                                       list(GAP_SHARD_SIGNATURES.items()) + list(GAP_RATE_SIGNATURES.items()) +
-                                      list(GAP_RATE_SHARD_SIGNATURES.items()) + list(PARTS_FLAGS_SIGNATURES.items())):
+                                      list(GAP_RATE_SHARD_SIGNATURES.items()) + list(PARTS_FLAGS_SIGNATURES.items()) +
+                                      list(GAP_LONG_SIGNATURES.items())):
                 fn = getattr(lib, name)
                 fn.restype = res
                 fn.argtypes = args

@@ -31,7 +31,8 @@ def needs_build() -> bool:
     if not os.path.exists(SO):
         return True
     so_m = os.path.getmtime(SO)
-    headers = ("tvz.h", "tvz_gap.h", "tvz_gap_shards.h", "tvz_gap_rates.h", "tvz_gap_rates_shards.h", "tvz_parts_flags.h")
+    headers = ("tvz.h", "tvz_gap.h", "tvz_gap_shards.h", "tvz_gap_rates.h", "tvz_gap_rates_shards.h", "tvz_parts_flags.h",
+               "tvz_gap_long.h")
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(INCLUDE, h) for h in headers]
     return any(os.path.getmtime(d) > so_m for d in deps)
 

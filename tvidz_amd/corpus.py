@@ -287,6 +287,19 @@ def align_candidates_rates_workspace_bytes(Q: int, max_query_len: int, total_que
                                                                       int(n_rates), int(cap), int(c)))
 
 
+# include/tvz_gap_long.h TVZ_GAP_LONG_SEG_POSITIONS, TVZ_GAP_LONG_MAX_LEN, TVZ_GAP_LONG_LDS_ENTRIES
+ALIGN_CANDIDATES_LONG_SEG_POSITIONS, ALIGN_CANDIDATES_LONG_MAX_LEN, ALIGN_CANDIDATES_LONG_LDS_ENTRIES = 511, 4095, 2048
+
+
+def align_candidates_long_workspace_bytes(Q: int, max_query_len: int, total_query_keys: int = 0, cap: int = 4096,
+                                          c: int = 16) -> int:
+    """tvz_align_candidates_long_workspace_bytes: align_candidates_workspace_bytes with a hit list per SEGMENT of 511
+    positions of the longest query (Q x S x cap x 12 bytes) and, where S x cap is above 2,048, per query the fold's table
+    (8 bytes x the next power of two at or above 2 x S x cap).  0 for arguments the call refuses."""
+    return int(_lib.load().tvz_align_candidates_long_workspace_bytes(int(Q), int(max_query_len), int(total_query_keys),
+                                                                     int(cap), int(c)))
+
+
 ALIGN_CANDIDATES_MERGE_MAX_LISTS = 16                               # include/tvz_gap_shards.h TVZ_GAP_MERGE_MAX_LISTS
 
 
@@ -675,6 +688,37 @@ class DeviceCorpus:
         _lib.check(self.lib.tvz_align_candidates(self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q, int(max_query_len),
                                                  int(min_count), excl, int(cap), int(c), out.data_ptr(), ws.data_ptr(),
                                                  ws.numel(), s.cuda_stream))
+        return out
+
+    supports_align_candidates_long = "tvz_align_candidates_long" in _lib.GAP_LONG_SIGNATURES
+
+    def align_candidates_long(self, queries, *, c: int, min_count: int = 2, cap: int = 4096, exclude_ids=None,
+                              max_query_len: Optional[int] = None):
+        """tvz_align_candidates_long, host in / host out: align_candidates for uploads of up to 4,095 values - the query is
+        looked up in segments of 511 positions and the segments' counts are SUMMED per stored video (min_count and `cap`
+        hold per segment) -> (rows int32 [Q, c, 2], totals int32 [Q]) as align_candidates returns them: an id at most
+        once per query; totals: the distinct candidate ids, or - negated - the segments' hit counts summed when a
+        segment's exceeded `cap`; ALIGN_CANDIDATES_REFUSED for a query longer than max_query_len."""
+        dev = torch.device("cuda", self.device)
+        d_q, d_off, Q, max_query_len, d_ex = align_inputs(queries, exclude_ids, max_query_len, dev)
+        ws = thread_workspace(self._tls, align_candidates_long_workspace_bytes(Q, max_query_len, d_q.numel(), cap, c), dev)
+        h = self.align_candidates_long_block(d_q, d_off, max_query_len, c=c, min_count=min_count, cap=cap, d_exclude_ids=d_ex,
+                                             workspace=ws).cpu().numpy()
+        return np.ascontiguousarray(h[:, :c]), np.ascontiguousarray(h[:, c, 1])
+
+    def align_candidates_long_block(self, d_queries: torch.Tensor, d_q_offsets: torch.Tensor, max_query_len: int, *, c: int,
+                                    min_count: int = 2, cap: int = 4096, d_exclude_ids: Optional[torch.Tensor] = None,
+                                    out: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
+                                    workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """tvz_align_candidates_long, device in / device out: enqueue Q queries -> the block int32 [Q, c + 1, 2], in
+        align_candidates_block's layout: it goes to align_parts_block and to align_candidates_merge_device as it is."""
+        Q = d_q_offsets.numel() - 1
+        dev, s, ws, excl = self._prelude(d_queries, d_q_offsets, d_exclude_ids, stream, workspace,
+                                         align_candidates_long_workspace_bytes(Q, max_query_len, d_queries.numel(), cap, c))
+        out = _out(out, (Q, max(int(c), 0) + 1, 2), dev)
+        _lib.check(self.lib.tvz_align_candidates_long(self._h, d_queries.data_ptr(), d_q_offsets.data_ptr(), Q,
+                                                      int(max_query_len), int(min_count), excl, int(cap), int(c),
+                                                      out.data_ptr(), ws.data_ptr(), ws.numel(), s.cuda_stream))
         return out
 
     supports_align_candidate_rates = "tvz_align_candidates_rates" in _lib.GAP_RATE_SIGNATURES

@@ -114,6 +114,73 @@ inline int64_t ws_room(int32_t Q, int32_t R, bool with_excl, int32_t cap, size_t
     return bytes < fixed ? -1 : (int64_t)((bytes - fixed) / per_key(R));
 }
 
+// ---- tvz_align_candidates_long (include/tvz_gap_long.h): the segments of a long query and its workspace ----
+// The positions 0 .. m - 4 of a query are cut into segments of kLongSegPositions consecutive positions, a probe list
+// each: 8 x 511 = 4,088 slots, the most whole positions the lookup's longest query (kMaxProbes) holds.  constexpr: the
+// kernels call them too.
+constexpr int kLongSegPositions = kMaxProbes / kVariants;             // 511
+constexpr int kLongSegSlots = kLongSegPositions * kVariants;          // 4,088
+constexpr int kLongMaxLen = 4095;                                     // the longest query (the alignment calls')
+constexpr int kLongLdsEntries = 2048;                                 // a query's hit entries that fold in LDS
+constexpr int kLongLdsSlots = 2 * kLongLdsEntries;                    // ... in a table of twice as many slots
+
+// S(m): the segments of a query of m sorted values (m < 4: none)
+constexpr int32_t long_segments(int32_t m) { return m < 4 ? 0 : (m - 3 + kLongSegPositions - 1) / kLongSegPositions; }
+// the probe lists per query of a call whose queries have up to max_query_len values: at least one
+constexpr int32_t long_lists(int32_t max_query_len) {
+    const int32_t s = long_segments(max_query_len > kLongMaxLen ? kLongMaxLen : max_query_len);
+    return s < 1 ? 1 : s;
+}
+// the probe slots of segment s of a query of m values (m < 0: refused, it has none)
+constexpr int32_t long_list_slots(int32_t m, int32_t s) {
+    if (m < 4 || s < 0) return 0;
+    const int32_t left = (m - 3) - s * kLongSegPositions;
+    return left <= 0 ? 0 : kVariants * (left < kLongSegPositions ? left : kLongSegPositions);
+}
+// position i of a query -> its list among the query's, and its first slot in that list
+constexpr int32_t long_list_of(int32_t i) { return i / kLongSegPositions; }
+constexpr int32_t long_place_of(int32_t i) { return kVariants * (i % kLongSegPositions); }
+
+// The fold's table: open addressing over the next power of two at or above 2 n slots (n: the entries to fold; at least
+// 2 slots), keyed by id + 1, the home slot the top bits of a multiplicative hash.
+constexpr uint32_t long_table_slots(int64_t n) {
+    uint32_t s = 2;
+    while ((int64_t)s < 2 * n) s <<= 1;
+    return s;
+}
+constexpr uint32_t long_table_home(uint32_t key, uint32_t slots) {   // slots: a power of two >= 2
+    return (key * 0x9E3779B1u) >> (32 - __builtin_ctz(slots));
+}
+// the table slots a query gets in the workspace: none where every query folds in LDS (lists x cap <= kLongLdsEntries)
+constexpr size_t long_ws_table_slots(int32_t lists_per_query, int32_t cap) {
+    const int64_t n = (int64_t)lists_per_query * cap;
+    return n <= kLongLdsEntries ? 0 : (size_t)long_table_slots(n);
+}
+
+// The regions: those of ws_regions for Q x S lists with the lists' exclusion ids - but 8 probe slots per value, not
+// 8 S: the segments partition a query's positions - and behind them the Q tables of 8-byte slots (id + 1, count).
+struct WsLongRegions : WsRegions {
+    size_t table;
+};
+inline WsLongRegions ws_long_regions(int32_t Q, int32_t S, int32_t cap, size_t match_bytes, int64_t room) {
+    WsLongRegions r;
+    static_cast<WsRegions &>(r) = ws_regions(Q, S, true, cap, match_bytes, 0);
+    size_t p = r.sv;                                                  // (room 0: the fixed regions end here)
+    r.sv = p;      p += al256((size_t)room * sizeof(double));
+    r.sp = p;      p += al256((size_t)room * sizeof(int32_t));
+    r.probes = p;  p += al256((size_t)room * kVariants * sizeof(double));
+    r.table = p;   p += al256((size_t)Q * long_ws_table_slots(S, cap) * 2 * sizeof(int32_t));
+    r.end = p;
+    return r;
+}
+inline size_t ws_long_bytes(int32_t Q, int32_t S, int32_t cap, size_t match_bytes, int64_t keys) {
+    return ws_long_regions(Q, S, cap, match_bytes, 0).end + kWsSlack + (size_t)keys * per_key(1);
+}
+inline int64_t ws_long_room(int32_t Q, int32_t S, int32_t cap, size_t match_bytes, size_t bytes) {
+    const size_t fixed = ws_long_bytes(Q, S, cap, match_bytes, 0);
+    return bytes < fixed ? -1 : (int64_t)((bytes - fixed) / per_key(1));
+}
+
 // ---- the workspace of tvz_align_candidates_sharded ----
 // In front, behind a base aligned up to 256: the rank's own block int32[Q][C + 1][2] and the gathered ones
 // int32[max(n_ranks, 1)][Q][C + 1][2]; behind them, from `plain` on (a multiple of 256 from the aligned base, so that

@@ -29,10 +29,12 @@
 #include "tvz_align_kernels.h"
 #include "tvz_align_parts_kernels.h"
 #include "tvz_gap_kernels.h"
+#include "tvz_gap_long_kernels.h"
 #include "tvz_gap.h"
 #include "tvz_gap_shards.h"
 #include "tvz_gap_rates.h"
 #include "tvz_gap_rates_shards.h"
+#include "tvz_gap_long.h"
 #include "tvz_parts_flags.h"
 #include "tvz_handle.h"
 #include "tvz_index_build.h"
@@ -2823,6 +2825,87 @@ size_t candidates_sizing(const CandidatesForm &f, int32_t Q, int32_t max_query_l
                              std::max<int64_t>(keys, max_query_len));
 }
 
+// ---- the candidates for long uploads (include/tvz_gap_long.h; kernels: tvz_gap_long_kernels.h) ----------------------
+// The plain call's steps with S probe lists per query, S the segments of the call's longest query: the sorted queries,
+// the lists' offsets and the probes (kernels of their own), ONE lookup over the Q S lists, the fold that sums per id.
+// It stands beside the form table, whose entries and whose plan are what they were: it shares their argument checks
+// (check_candidates_args, check_batch_args), the lookup's sizing and nothing else.
+constexpr const char *kCandidatesLongWhat = "alignment candidates";
+
+// what the call refuses behind the plain call's own refusals, in the header's order; -> the lists per query
+int check_candidates_long(const Batch &b, int32_t min_count, int32_t cap, int32_t C, int32_t *S) {
+    if (int rc = check_candidates_args(b.max_query_len, min_count, cap, C)) return rc;
+    *S = tvz_gap::long_lists(b.max_query_len);
+    if ((int64_t)b.Q * *S > kGaprMaxLists)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "%s: Q=%d x %d segments is above %d probe lists", kCandidatesLongWhat, (int)b.Q, (int)*S,
+                         kGaprMaxLists);
+    if ((int64_t)*S * cap * tvz_gap::kLongSegSlots > INT32_MAX)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "%s: %d segments x cap=%d x %d probe slots is above %d", kCandidatesLongWhat, (int)*S,
+                         (int)cap, tvz_gap::kLongSegSlots, INT32_MAX);
+    return TVZ_OK;
+}
+
+int candidates_long_call(tvz_corpus *c, const Batch &b, int32_t min_count, int32_t cap, int32_t C, int32_t *d_out, Workspace ws,
+                         void *hip_stream) {
+    int32_t S = 1;
+    if (int rc = check_candidates_long(b, min_count, cap, C, &S)) return rc;
+    if (int rc = check_batch_args(c, b, cap)) return rc;
+    if (b.Q == 0) return TVZ_OK;
+    const int32_t lists = b.Q * S;
+    const size_t match_bytes = candidates_match_bytes(lists, b.max_query_len);
+    const size_t whole = ws.p ? ws.bytes : 0;
+    const size_t need = tvz_gap::ws_long_bytes(b.Q, S, cap, match_bytes, b.max_query_len);
+    if (whole < need)
+        return tvz::fail(TVZ_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu bytes missing (size it with %s)", kCandidatesLongWhat, whole,
+                         need - whole, "tvz_align_candidates_long_workspace_bytes");
+    TVZ_REQUIRE(d_out != nullptr && (reinterpret_cast<uintptr_t>(d_out) & (uintptr_t)7) == 0, "d_out is NULL or not %d-byte aligned", 8);
+    const int64_t room = tvz_gap::ws_long_room(b.Q, S, cap, match_bytes, whole);
+    const tvz_gap::WsLongRegions r = tvz_gap::ws_long_regions(b.Q, S, cap, match_bytes, room);
+    unsigned char *base = reinterpret_cast<unsigned char *>(al256(reinterpret_cast<uintptr_t>(ws.p)));
+    int32_t *hits = reinterpret_cast<int32_t *>(base + r.hits), *hits_n = reinterpret_cast<int32_t *>(base + r.hits_n);
+    int64_t *p_off = reinterpret_cast<int64_t *>(base + r.p_off);
+    // (the lists' exclusion ids: the lookup reads one id per probe list; a call with exclusions copies the query's to each)
+    int32_t *excl = b.d_exclude_ids ? reinterpret_cast<int32_t *>(base + r.excl) : nullptr;
+    unsigned char *match = base + r.match;
+    int32_t *qm = reinterpret_cast<int32_t *>(base + r.qm), *sp = reinterpret_cast<int32_t *>(base + r.sp);
+    double *sv = reinterpret_cast<double *>(base + r.sv), *probes = reinterpret_cast<double *>(base + r.probes);
+    int2 *table = reinterpret_cast<int2 *>(base + r.table);
+    const size_t table_slots = tvz_gap::long_ws_table_slots(S, cap);
+    DeviceGuard dg(c->device);
+    std::shared_lock<std::shared_mutex> lk(c->mu);            // parent, then (inside the lookup) child
+    if (!c->gap)
+        return tvz::fail(TVZ_ERR_UNSUPPORTED, "alignment candidates: this corpus keeps no gap codes (tvz_corpus_gap_index)");
+    const double gap_eps = c->gap_eps;
+    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+    hipLaunchKernelGGL(ts_tol_sort_kernel, dim3((unsigned)tvz::ceil_div(std::max(b.max_query_len, 1), kTolSortBlock), (unsigned)b.Q),
+                       dim3(kTolSortBlock), 0, st, b.d_queries, b.d_q_offsets, b.max_query_len, room, sv, sp, qm, hits_n);
+    TVZ_HIP(hipGetLastError());
+    hipLaunchKernelGGL(ts_gapl_offsets_kernel, dim3(1), dim3(kGapOffBlock), 0, st, qm, b.Q, S, b.d_exclude_ids, p_off, excl);
+    TVZ_HIP(hipGetLastError());
+    if (b.max_query_len >= 4) {
+        hipLaunchKernelGGL(ts_gapl_probe_kernel, dim3((unsigned)tvz::ceil_div(b.max_query_len - 3, kGapProbeBlock), (unsigned)b.Q),
+                           dim3(kGapProbeBlock), 0, st, sv, b.d_q_offsets, qm, gap_eps, S, p_off, probes);
+        TVZ_HIP(hipGetLastError());
+    }
+    if (int rc = tvz_match_impl(c->gap, probes, p_off, lists, tvz_gap::max_probe_len(b.max_query_len), min_count,
+                                excl ? excl : b.d_exclude_ids, cap, hits, hits_n, match, match_bytes, TVZ_ALGO_AUTO, hip_stream))
+        return rc;
+    hipLaunchKernelGGL(ts_gapl_fold_kernel, dim3((unsigned)b.Q), dim3(kBlock), 0, st, hits, hits_n, qm, S, cap, C, table, table_slots,
+                       d_out);
+    TVZ_HIP(hipGetLastError());
+    return record(c, st);
+}
+
+size_t candidates_long_sizing(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t cap, int32_t C) {
+    if (Q < 0 || Q > 65535 || max_query_len < 0 || max_query_len > kAlMaxLen || total_query_keys < 0 || C < 1 ||
+        C > tvz_gap::kMaxC || cap < C)
+        return 0;
+    const int32_t S = tvz_gap::long_lists(max_query_len);
+    if ((int64_t)Q * S > kGaprMaxLists || (int64_t)S * cap * tvz_gap::kLongSegSlots > INT32_MAX) return 0;
+    const int64_t keys = total_query_keys > 0 ? total_query_keys : (int64_t)Q * max_query_len;
+    return tvz_gap::ws_long_bytes(Q, S, cap, candidates_match_bytes(Q * S, max_query_len), std::max<int64_t>(keys, max_query_len));
+}
+
 }  // namespace
 
 // ---- the candidates over a sharded table (include/tvz_gap_shards.h) ---------------------------------------------
@@ -2990,6 +3073,19 @@ TVZ_EXPORT int tvz_align_candidates(tvz_corpus *c, const double *d_queries, cons
     TVZ_GUARDED(candidates_call(kCandidatesPlain, c, align_batch(d_queries, d_q_offsets, Q, max_query_len, d_exclude_ids),
                                 CandidatesCall{nullptr, 1, min_count, cap, C, d_out}, Workspace{d_workspace, workspace_bytes},
                                 hip_stream));
+}
+
+// ---- the candidates for long uploads (include/tvz_gap_long.h) -----------------------------------------------------
+TVZ_EXPORT size_t tvz_align_candidates_long_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys, int32_t cap,
+                                                            int32_t C) {
+    return candidates_long_sizing(Q, max_query_len, total_query_keys, cap, C);
+}
+
+TVZ_EXPORT int tvz_align_candidates_long(tvz_corpus *c, const double *d_queries, const int64_t *d_q_offsets, int32_t Q,
+                                         int32_t max_query_len, int32_t min_count, const int32_t *d_exclude_ids, int32_t cap,
+                                         int32_t C, int32_t *d_out, void *d_workspace, size_t workspace_bytes, void *hip_stream) {
+    TVZ_GUARDED(candidates_long_call(c, align_batch(d_queries, d_q_offsets, Q, max_query_len, d_exclude_ids), min_count, cap, C, d_out,
+                                     Workspace{d_workspace, workspace_bytes}, hip_stream));
 }
 
 TVZ_EXPORT size_t tvz_align_candidates_rates_workspace_bytes(int32_t Q, int32_t max_query_len, int64_t total_query_keys,

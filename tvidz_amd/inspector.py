@@ -95,7 +95,8 @@ class Inspector:
                  near_any_offset: bool = False, near_score: str = "jaccard", near_min_votes: int = 1,
                  near_rates=None, near_spans: bool = False, near_parts: Optional[int] = None,
                  near_two_bins: bool = False, near_candidates: Optional[int] = None, near_gap_eps: float = 1.0 / 30,
-                 near_candidate_rates: bool = False, near_parts_two_bins: bool = False):
+                 near_candidate_rates: bool = False, near_parts_two_bins: bool = False,
+                 near_candidates_long: bool = False):
         self.store = store
         # opt-in: the near-duplicate report from the K best-aligned rows the device keeps (tvz_align_topk) instead of
         # one row per corpus row walked here.  None: the walk, exactly as before.  Refused here where the store's
@@ -242,6 +243,21 @@ class Inspector:
                 raise RuntimeError(f"near_candidate_rates=True: the store's corpus ({type(corpus).__name__}) has no "
                                    "align_candidates_rates; use a DeviceCorpus")
             corpus.set_gap_index(self.near_gap_eps)
+        # near_candidates_long=True: the ids of EVERY upload come from align_candidates_long (tvz_align_candidates_long:
+        # the upload looked up in segments of 511 positions, the segments' counts summed per stored video), so an
+        # upload of up to 4,095 cuts no longer takes the sweep; a longer one still does.  The rates form stays at 514
+        # values: refused beside near_candidate_rates.  False: nothing changes.
+        self.near_candidates_long = bool(near_candidates_long)
+        if self.near_candidates_long:
+            if self.near_candidates is None:
+                raise RuntimeError("near_candidates_long=True needs near_candidates")
+            if self.near_candidate_rates:
+                raise RuntimeError("near_candidates_long=True with near_candidate_rates=True: the candidates call with "
+                                   "rates takes uploads of up to 514 values; use one of them")
+            corpus = getattr(store, "corpus", None)
+            if not _corpus_can(corpus, "align_candidates_long", "supports_align_candidates_long"):
+                raise RuntimeError(f"near_candidates_long=True: the store's corpus ({type(corpus).__name__}) has no "
+                                   "align_candidates_long; use a DeviceCorpus")
         # opt-in, never the default: duplicates by the TOLERANT count (include/tvz.h tvz_find_duplicates_tol)
         # instead of the reference's exact float64 equality; the verdict, the truncation at kth and the stored
         # duplicates all follow it.  Refused here, before any upload, where the store's corpus cannot do it.
@@ -566,6 +582,8 @@ class Inspector:
         t_first, t_last, nr).  The same fixed-point score, thresholds and order as the sweep keeps its rows by, the
         near_top_k best.  Rows of four columns where the configuration's sweep reports no span.  None: the candidates
         call refused the upload.  The parts block stays with the calling thread for _near_parts.
+        near_candidates_long: the ids come from ONE align_candidates_long call, which refuses an upload only above 4,095
+        values.
         near_candidate_rates: the ids come from ONE align_candidates_rates call with near_rates, the parts call aligns at
         the same list, and the rate_index of a row is the parts header's (rows of five columns without spans)."""
         from .corpus import align_span_order_key
@@ -576,7 +594,8 @@ class Inspector:
                                                               exclude_ids=[int(video_id)])
             ids = ids[0]
         else:
-            ids, totals = corpus.align_candidates([scene_timestamps], c=self.near_candidates, exclude_ids=[int(video_id)])
+            call = corpus.align_candidates_long if self.near_candidates_long else corpus.align_candidates
+            ids, totals = call([scene_timestamps], c=self.near_candidates, exclude_ids=[int(video_id)])
             ids = ids[0][:, 0]
         if int(totals[0]) == -(1 << 31):
             return None
